@@ -13,12 +13,21 @@ One *step* = `reset_U` (U <- Y on the device, a 307 MB device-to-device copy tha
 graph build (kNN + mutual + cap + Laplacian weights) is timed separately, as the reference's own harness does
 (scripts/scale_benchmark.py:44-46).
 
-Protocol (/root/reference/scripts/scale_benchmark.py:23-53 seeds its runs): seeds {0, 1, 2} on
-one GPU (one seed under a communicator unless --seeds says otherwise), per seed W warm-up steps and then EXACTLY K
-timed steps between barrier + device drain on both sides; every step is also timed by itself (the host returns from
-a settle when it has read the last residual).  `ms_per_step` = median over all timed steps (max over the ranks of
-the per-rank medians), p10 / p90 beside it, `value` = 1000 / median; the bracketed regions' mean is reported as
-`ms_per_step_mean` (max over ranks).
+Protocol (the reference's scale benchmark seeds its runs): one seed (0) unless --seeds says
+otherwise, W warm-up steps and then EXACTLY K timed steps between barrier + device drain on both sides; every step is
+also timed by itself (the host returns from a settle when it has read the last residual).  `ms_per_step` = median
+over all timed steps (max over the ranks of the per-rank medians), p10 / p90 beside it, `value` = 1000 / median; the
+bracketed regions' mean is reported as `ms_per_step_mean` (max over ranks).  --full times seeds {0, 1, 2} on one GPU
+(K steps each) and adds the measurements listed below.
+
+--dump-outputs DIR: after the timed steps, what the last timed step of the first seed computed is written as float32 /
+float64 .npy files (rank 0 writes; under a communicator every rank takes part in the read-back):
+  U.npy           : rows of the settled state U (N x D, float32) -- all of them when U fits in 48 MiB, else a fixed
+                    sample of 48 MiB worth of rows (default_rng(DUMP_SAMPLE_SEED), sorted)
+  U_rows.npy      : the row ids of U.npy (float64)
+  settle_iters.npy, settle_res.npy : what that settle() returned (CG iterations, final residual; float64, shape (1,))
+The inputs depend on the seeds and the size arguments only, so two builds run with the same arguments can be compared
+output for output.
 
 N > 1: strong scaling of the same settle -- the CG is column-sharded (per-column alpha/beta), each rank owns a
 D/N column slab and the only per-iteration exchange is one RCCL all-reduce(max) of the residual.  This script uses no
@@ -32,11 +41,13 @@ with the worst child's code.  If the communicator cannot be set up on every rank
 line): N independent replicas are not a measurement of this job.  The JSON line carries `comm` = what the library's
 communicator reports (kind "rccl", world N, RCCL's version) so that a reader can see RCCL really spanned N ranks.
 
-Prints ONE JSON line on rank 0 (contract in the task description) with these extra objects:
+Prints ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step, ...) with this extra
+object, taken from the timed steps themselves:
   roofline        : the operator apply (SpMM, the CG matvec): algorithmic bytes per launch / mean launch time (HIP
                     events on the library's own stream) against the 8 TB/s HBM3E peak; `settle` = the whole settle's
                     algorithmic bytes / ms_per_step; `traffic` only from a committed PMC profile taken with THIS build;
                     `per_rank` = every rank's window apply against its own algorithmic bytes.
+and, with --full only (each takes runs of its own after the timed region; --no-extras / --no-cpu-baseline drop them again):
   knn             : the lattice build: route, device time, GEMM+top-k kernel time, 2 N^2 D flops against the MFMA peak.
   ustar_solve_ms, receipt_ms : medians of the stationary solve and of light / full receipts (U* resident).
   first_settle_ms, mispredict_settle_ms : what a fresh handle's first settle and a settle whose iteration count the
@@ -64,6 +75,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
+DUMP_SAMPLE_SEED = 20240917  # --dump-outputs: the fixed row sample of U when U is larger than DUMP_U_BYTES
+DUMP_U_BYTES = 48 << 20
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 MFMA_F16_DENSE_TFLOPS = 2500.0  # dense f16/bf16 matrix peak (the prefilter route's GEMM)
 MFMA_F32_TFLOPS = 157.3  # fp32 matrix peak (the exact route's GEMM)
@@ -291,15 +304,22 @@ def main():
     ap.add_argument("--tol", type=float, default=1e-3)
     ap.add_argument("--max-iters", type=int, default=12)
     ap.add_argument("--seeds", type=str, default=None,
-                    help="comma-separated anchor seeds, each timed for --steps steps (default: 0,1,2 on one GPU -- "
-                         "BASELINE.md section 2 --, 0 under a communicator)")
+                    help="comma-separated anchor seeds, each timed for --steps steps (default: 0; with --full 0,1,2 on one "
+                         "GPU -- BASELINE.md section 2 --, 0 under a communicator)")
     ap.add_argument("--launch-timeout", type=float, default=1500.0,
                     help="self-launcher: seconds the ranks get before they are killed")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the build / U* / receipt timings after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: seeds 0,1,2 on one GPU, first / mispredicted settle, the build / U* / "
+                         "receipt timings and the CPU oracle baseline (off by default: a plain run only times the steps)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the first-settle / build / U* / receipt timings after the timed region")
     ap.add_argument("--extras", action="store_true",
-                    help="run those timings in a multi-GPU run as well (default there: skipped -- they are collective calls "
-                         "outside the timed region, and the one JSON line should not depend on them)")
+                    help="with --full: run those timings in a multi-GPU run as well (default there: skipped -- they are "
+                         "collective calls outside the timed region, and the one JSON line should not depend on them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (sampled rows of U, the settle's "
+                         "iterations and residual) as DIR/<name>.npy")
     ap.add_argument("--shard", choices=["column", "row"], default="column",
                     help="multi-GPU CG partitioning: column slabs (one all-reduce(max) per iteration, default) or "
                          "row blocks (halo exchange of p + all-reduces of D-vectors, the north-star wording)")
@@ -322,7 +342,7 @@ def main():
     # (rehearsal on a one-GPU box: OSC_BENCH_FORCE_COMM=1 takes the multi-GPU code path -- rendezvous, the library's RCCL
     # communicator, the sharded solve with its second stream, barriers -- with the one rank RCCL allows there)
     launched = world > 1 or bool(os.environ.get("OSC_BENCH_FORCE_COMM"))
-    seeds = [int(x) for x in (args.seeds or ("0" if launched else "0,1,2")).split(",") if x.strip() != ""]
+    seeds = [int(x) for x in (args.seeds or ("0,1,2" if args.full and not launched else "0")).split(",") if x.strip() != ""]
     if not seeds:
         raise SystemExit("bench.py: --seeds is empty")
 
@@ -460,6 +480,8 @@ def main():
         runs.append(r)
     main_run = runs[0]
     lat, Y, psi = main_run["lat"], main_run["Y"], main_run["psi"]
+    if args.dump_outputs:  # before anything else touches the first seed's lattice (the later seeds had their own)
+        dump_outputs(args.dump_outputs, lat, main_run["last"], rank)
     comm_info = main_run["comm"]
     nnz, max_deg = main_run["nnz"], main_run["max_deg"]
 
@@ -585,26 +607,49 @@ def main():
                                 "frac": settle_gbs / (HBM_PEAK_GBS * world)}},
     }
 
-    if not launched and not args.no_extras:
+    out["full"] = bool(args.full)
+    run_extras = args.full and not args.no_extras
+    run_cpu_baseline = args.full and not args.no_cpu_baseline
+    if not launched and run_extras:
         out.update(cold_and_mispredicted(lat, Y, psi, args, k, local_rank, main_run["step"]))
-    if not args.no_extras and (not launched or args.extras):
+    if run_extras and (not launched or args.extras):
         out.update(extras(lat, N, D, args, launched))
-    elif launched:
+    elif launched and run_extras:
         out["extras"] = "skipped in a multi-GPU run (--extras runs them: sharded rebuilds, U* solves, receipts)"
     # The CPU oracle leg is CPU-only: rank 0 takes the device-built graph while the lattice is alive, every rank then
     # leaves the communicator (the other ranks are done), and rank 0 times the oracle -- at every world size, so that a
     # multi-GPU line carries the field too.
     csr = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and run_cpu_baseline:
         csr = lat.graph_csr()[:3]
     if launched:
         sync_all(lat)
         lat.close()
         rdzv.close()
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and run_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(csr, Y, psi, args)
     if rank == 0:
         print(json.dumps(out), flush=True)
+
+
+def dump_outputs(path, lat, last, rank):
+    """--dump-outputs: what the caller of the timed path receives after its last step -- the settled state U (all rows,
+    or a fixed sample of them when U is larger than DUMP_U_BYTES) and the settle's own result.  Every rank reads U back
+    (collective in a sharded run); rank 0 writes."""
+    N, D = lat.N, lat.D
+    n_rows = min(N, max(1, DUMP_U_BYTES // (4 * D)))
+    if n_rows == N:
+        rows = np.arange(N, dtype=np.int64)
+    else:
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(N, size=n_rows, replace=False))
+    U = np.ascontiguousarray(lat.U[rows], dtype=np.float32)
+    if rank != 0:
+        return
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "U.npy"), U)
+    np.save(os.path.join(path, "U_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(path, "settle_iters.npy"), np.array([last["iters"]], dtype=np.float64))
+    np.save(os.path.join(path, "settle_res.npy"), np.array([last["res"]], dtype=np.float64))
 
 
 def cold_and_mispredicted(lat, Y, psi, args, k, device, step):

@@ -4,7 +4,7 @@
 # profiles/<tag>_*.  Counters are collected in their own passes (never combined with sys/hip/hsa tracing).
 set -u
 TAG=${1:-r01}
-ARGS=${2:-"--steps 10 --warmup 2 --no-cpu-baseline"}
+ARGS=${2:-"--full --steps 10 --warmup 2 --no-cpu-baseline"}
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT

@@ -2,7 +2,7 @@
 # Round-6 measurement pass (run on the GPU box from the repo root): everything DESIGN.md quotes from profiles/r06_*.
 set -u
 O=gpurun_out/r06m; mkdir -p $O
-timeout -k 10 500 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+timeout -k 10 500 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
 timeout -k 10 600 python scripts/config_times.py > $O/config_times.txt 2>&1
 timeout -k 10 300 python scripts/request_latency.py > $O/request_latency.txt 2>&1
 { timeout -k 10 400 python scripts/shard_local_times.py c3 1 2 4 8; timeout -k 10 400 python scripts/shard_local_times.py c5 1 4; timeout -k 10 500 python scripts/shard_local_times.py c4 1 8; } > $O/shard_local_times.txt 2>&1

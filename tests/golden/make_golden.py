@@ -162,7 +162,11 @@ def run_case(name, *, N, D, k, gen, psi_mode, chain=None, lamP=0.2, gates=None, 
         out["chain_gain"] = cr["coherence_gain"]
         out["chain_z_struct"] = np.array([e["z_struct"] for e in cr["edges"]])
         out["chain_z_path"] = np.array([e["z_path"] for e in cr["edges"]])
-    np.savez_compressed(os.path.join(HERE, f"case_{name}.npz"), **out)
+    path = os.path.join(HERE, f"case_{name}.npz")
+    np.savez_compressed(path, **out)
+    if os.path.getsize(path) > 1 << 20 and "Ustar" in out:  # no committed file over 1 MiB: U* goes into a second file
+        np.savez_compressed(os.path.join(HERE, f"case_{name}.part2.npz"), Ustar=out.pop("Ustar"))
+        np.savez_compressed(path, **out)
     print(f"{name}: dH={rec['deltaH_total']!r} settle={st['iters']}/{st['res']:.4e} ustar={lat.last_ustar['iters']}/"
           f"{lat.last_ustar['res']:.4e} nnz={len(indices)} nulls={len(rec['null_points'])}")
 

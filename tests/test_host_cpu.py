@@ -295,6 +295,44 @@ def test_bench_refuses_more_gpus_than_devices_before_any_build():
     assert r.returncode != 0 and r.stdout.strip() == "" and "WORLD_SIZE=2" in r.stderr
 
 
+def test_bench_dump_outputs_are_a_fixed_float_sample_within_64_mb(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs`: float32 / float64 .npy files; a U larger than the dump budget is written as the same
+    sorted row sample every time, and those rows are U's own; at config 3 the files stay under 64 MB."""
+    import sys
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    N, D = 100_000, 768
+    rows_c3 = bench.DUMP_U_BYTES // (4 * D)
+    assert 4 * rows_c3 * D + 8 * rows_c3 + 16 <= 64e6 and rows_c3 < N
+
+    class FakeLattice:  # the two attributes and the one property dump_outputs reads
+        pass
+
+    lat = FakeLattice()
+    lat.N, lat.D = 1000, 64
+    lat.U = np.random.default_rng(1).standard_normal((lat.N, lat.D)).astype(np.float32)
+    last = {"iters": 4, "res": 3.5e-4}
+    bench.dump_outputs(str(tmp_path / "all"), lat, last, 0)
+    assert np.array_equal(np.load(tmp_path / "all" / "U.npy"), lat.U)
+    monkeypatch.setattr(bench, "DUMP_U_BYTES", 64 * 1024)
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), lat, last, 0)
+    bench.dump_outputs(str(tmp_path / "rank1"), lat, last, 1)
+    assert not (tmp_path / "rank1").exists()
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["U.npy", "U_rows.npy", "settle_iters.npy", "settle_res.npy"]
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y)
+    U, rows = np.load(tmp_path / "a" / "U.npy"), np.load(tmp_path / "a" / "U_rows.npy")
+    assert U.shape == (64 * 1024 // (4 * lat.D), lat.D) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(U, lat.U[rows.astype(np.int64)])
+    assert np.load(tmp_path / "a" / "settle_iters.npy").tolist() == [4.0]
+    assert np.load(tmp_path / "a" / "settle_res.npy").tolist() == [3.5e-4]
+
+
 def test_panel_kernels_m0_discipline_and_untouched_k_loops(tmp_path):
     """csrc/knn_gemm.hip (round 6): the K loop of k_panel writes M0 -- the LDS destination of an LDS-DMA piece -- with one
     `s_add_i32 m0, base, literal` and issues the `global_load_lds_dwordx4` a few instructions later, WITHOUT saving or restoring
