@@ -190,6 +190,28 @@ int osc_cosine_to_row(osc_handle h, int64_t row, float* out);
  * out_idx in API row order.  *out_count receives the number of rows written. */
 int osc_mmr(osc_handle h, const float* scores, int32_t k, float lambda_div, int32_t* out_idx, int32_t* out_count);
 
+/* ---- multi-query bundles (not in the reference) -------------------------------------------------
+ * For the lattice's current graph, gates, chain and lambdas U*(psi) = X + x psi^T with M X = lamG Y (N x D) and
+ * M x = lamQ B (N x 1): one basis serves every query.  Batches are processed OSC_QUERY_CHUNK queries at a time. */
+#define OSC_QUERY_CHUNK 256
+/* Not in the reference (the basis behind solve_Ustar, lattice.py:232-290, for every psi at once).  fresh != 0 solves X
+ * (Jacobi-PCG from x0 = Y, stop at max_c |r_c| <= tol / 2) and x; fresh == 0 keeps X and continues x from the resident
+ * one.  x is solved to |r_x| <= tol / (2 scale), scale = the largest |psi|_inf it must serve.  iters[2] / res[2] receive
+ * X's and x's iterations and final residuals (X: 0 and -1 when kept).  OSC_E_UNSUPPORTED with a communicator. */
+int osc_query_basis(osc_handle h, float tol, int32_t max_iters, float scale, int32_t fresh, int32_t* iters, float* res,
+                    double* ms);
+/* Not in the reference: the resident basis in API row order (X_out N x D, x_out N; either may be NULL).
+ * OSC_E_STATE without a basis for the current graph. */
+int osc_get_query_basis(osc_handle h, float* X_out, float* x_out);
+/* bundle(k, alpha) (lattice.py:530-568) for Q queries psis (Q x D) from the resident basis: per query
+ * align_i = cos(U*_i, psi), coh_i (receipts.py:28-38) z-scored, score = alpha z + (1 - alpha) align and
+ * mmr_diversify (graph.py:114-133, lambda_div) over the anchors.  ids / score / align are Q x min(k, N), API ids. */
+int osc_bundle_many(osc_handle h, const float* psis, int32_t Q, int32_t k, float alpha, float lambda_div, int32_t* ids,
+                    float* score, float* align);
+/* mmr_diversify (graph.py:114-133) for Q score columns at once: scores N x Q (API row order, queries contiguous per row);
+ * out_idx Q x min(k, N) API ids, the same picks as osc_mmr per column up to rounding of the similarities. */
+int osc_mmr_many(osc_handle h, const float* scores, int32_t Q, int32_t k, float lambda_div, int32_t* out_idx);
+
 /* ---- receipts ------------------------------------------------------------------------------- */
 /* deltaH_trace (receipts.py:10-25) on the resident U and U* */
 int osc_deltaH(osc_handle h, double* dH);

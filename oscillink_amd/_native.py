@@ -14,6 +14,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # OSC_LIB_PATH selects another build of the same library (A/B experiments with kernel variants)
 LIB_PATH = os.environ.get("OSC_LIB_PATH") or os.path.join(_HERE, "liboscillink_hip.so")
 
+OSC_QUERY_CHUNK = 256  # queries per pass of osc_bundle_many / osc_mmr_many (include/oscillink_hip.h)
+
 OSC_OK, OSC_E_INVALID, OSC_E_NODEVICE, OSC_E_HIP, OSC_E_STATE, OSC_E_UNSUPPORTED, OSC_E_COMM = 0, -1, -2, -3, -4, -5, -6
 
 c_f32p = C.POINTER(C.c_float)
@@ -63,6 +65,10 @@ SIGNATURES = {
     "osc_ustar_cosine_to": (C.c_int, [Handle, c_f32p, c_f32p]),
     "osc_cosine_to_row": (C.c_int, [Handle, C.c_int64, c_f32p]),
     "osc_mmr": (C.c_int, [Handle, c_f32p, C.c_int32, C.c_float, c_i32p, c_i32p]),
+    "osc_query_basis": (C.c_int, [Handle, C.c_float, C.c_int32, C.c_float, C.c_int32, c_i32p, c_f32p, c_f64p]),
+    "osc_get_query_basis": (C.c_int, [Handle, c_f32p, c_f32p]),
+    "osc_bundle_many": (C.c_int, [Handle, c_f32p, C.c_int32, C.c_int32, C.c_float, C.c_float, c_i32p, c_f32p, c_f32p]),
+    "osc_mmr_many": (C.c_int, [Handle, c_f32p, C.c_int32, C.c_int32, C.c_float, c_i32p]),
     "osc_deltaH": (C.c_int, [Handle, c_f64p]),
     "osc_receipt_components": (C.c_int, [Handle, c_f32p, c_f32p, c_f32p]),
     "osc_null_points": (C.c_int, [Handle, C.c_float, c_i32p, c_i32p, c_f32p, c_f32p, c_i32p]),

@@ -829,6 +829,37 @@ int osc_mmr(osc_handle h, const float* scores, int32_t k, float lambda_div, int3
   });
 }
 
+int osc_query_basis(osc_handle h, float tol, int32_t max_iters, float scale, int32_t fresh, int32_t* iters, float* res,
+                    double* ms) {
+  return guarded(h, [&](L& l) {
+    if (!iters || !res) throw Invalid("osc_query_basis: NULL buffer");
+    query_basis_solve(l, tol, max_iters, scale, fresh != 0, iters, res, ms);
+  });
+}
+
+int osc_get_query_basis(osc_handle h, float* X_out, float* x_out) {
+  return guarded(h, [&](L& l) { query_basis_download(l, X_out, x_out); });
+}
+
+int osc_bundle_many(osc_handle h, const float* psis, int32_t Q, int32_t k, float alpha, float lambda_div, int32_t* ids,
+                    float* score, float* align) {
+  return guarded(h, [&](L& l) {
+    if (Q < 0) throw Invalid("osc_bundle_many: Q must be >= 0");
+    if (Q > 0 && k > 0 && (!psis || !ids || !score || !align)) throw Invalid("osc_bundle_many: NULL buffer");
+    for (int64_t i = 0; i < (int64_t)Q * l.D; ++i)
+      if (!std::isfinite(psis[i])) throw Invalid("osc_bundle_many: non-finite query");
+    query_bundle_many(l, psis, Q, k, alpha, lambda_div, ids, score, align);
+  });
+}
+
+int osc_mmr_many(osc_handle h, const float* scores, int32_t Q, int32_t k, float lambda_div, int32_t* out_idx) {
+  return guarded(h, [&](L& l) {
+    if (Q < 0) throw Invalid("osc_mmr_many: Q must be >= 0");
+    if (Q > 0 && k > 0 && (!scores || !out_idx)) throw Invalid("osc_mmr_many: NULL buffer");
+    query_mmr_many(l, scores, Q, k, lambda_div, out_idx);
+  });
+}
+
 int osc_ustar_cosine_to(osc_handle h, const float* psi, float* out) {
   return guarded(h, [&](L& l) {
     if (!psi || !out) throw Invalid("osc_ustar_cosine_to: NULL buffer");

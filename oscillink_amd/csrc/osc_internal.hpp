@@ -28,6 +28,7 @@
 #include "perm.hpp"
 #include "dynamics.hpp"
 #include "small.hpp"
+#include "query.hpp"
 
 using namespace osc;
 
@@ -217,6 +218,25 @@ struct osc_lattice {
   std::vector<hipEvent_t> prof_pool;
   int64_t prof_count[5] = {0, 0, 0, 0, 0};
   double prof_ms[5] = {0, 0, 0, 0, 0};
+  // multi-query bundles (osc_query.hip): the query basis M X = lamG Y, M x = lamQ B of the graph / gates / chain / lams it
+  // was solved for (the caller keys it; a new graph_epoch drops it), its per-row constants and the batch scratch
+  struct QueryState {
+    bool have = false;
+    uint64_t epoch = 0;        // graph_epoch of the basis
+    float scale = 0.f;         // |psi|_inf the x part was solved for (its residual target is tol / (2 scale))
+    DevBuf<float> X, x4;       // N x ld, N x 4 (column 0 = x)
+    DevBuf<float> s;           // [N] x / (sd + 1e-12)
+    DevBuf<double> xn2, c0, c2;
+    DevBuf<float> Yn;          // row-normalised anchors (the MMR's representers)
+    uint64_t yn_epoch = 0;
+    DevBuf<float> zero_psi;    // [ld] zeros: the psi of the X solve
+    DevBuf<float> Bt;          // [query_qpad(chunk) x kpad] GEMM operand
+    DevBuf<float> align, pm, cs;  // N x qs: alignment; p, then the MMR's running maxima; coh, then the score
+    DevBuf<double> pn2, pinv, pval;
+    DevBuf<double2> part, stats;
+    DevBuf<int32_t> pid, prow, chosen_api, chosen_row;
+    DevBuf<float> out_score, out_align;
+  } query;
   std::string err;
 
   ~osc_lattice() {
@@ -332,6 +352,12 @@ void read_env_solver(L& h);
 void read_env_build(L& h);
 void read_env(L& h);
 void require_graph(L& h);
+// osc_query.hip (include/oscillink_hip.h: osc_query_basis, osc_get_query_basis, osc_bundle_many, osc_mmr_many)
+void query_basis_solve(L& l, float tol, int32_t max_iters, float scale, bool fresh, int32_t* iters, float* res, double* ms);
+void query_basis_download(L& l, float* X_out, float* x_out);
+void query_bundle_many(L& l, const float* psis, int32_t Q, int32_t k, float alpha, float lambda_div, int32_t* ids,
+                       float* score, float* align);
+void query_mmr_many(L& l, const float* scores, int32_t Q, int32_t k, float lambda_div, int32_t* ids);
 
 struct ProfScope {
   L& h;

@@ -1,0 +1,93 @@
+// Multi-query bundles: the kernels behind osc_bundle_many / osc_mmr_many (query_kernels.hip).
+// Everything is in device row order; queries are contiguous per row (an N x qs array holds query q of row i at i * qs + q).
+#pragma once
+#include "../../include/oscillink_hip.h"
+#include "common.hpp"
+
+namespace osc {
+
+constexpr int kQueryChunk = OSC_QUERY_CHUNK;  // queries per pass (include/oscillink_hip.h)
+constexpr int kQueryTileQ = 128;              // query columns of one k_query_gemm workgroup
+constexpr int kQueryTileK = 32;               // K step of the GEMM (the B operand is padded to a multiple of it)
+
+inline int32_t query_kpad(int32_t D) { return (D + kQueryTileK - 1) / kQueryTileK * kQueryTileK; }
+inline int32_t query_qpad(int32_t Q) { return (Q + kQueryTileQ - 1) / kQueryTileQ * kQueryTileQ; }
+inline int32_t query_qs(int32_t Q) { return (Q + 3) & ~3; }  // row pitch of the N x Q arrays
+
+// per-row constants of a query basis (X, x): s_i = x_i / (sd_i + 1e-12), |X_i|^2 and the two per-edge sums
+//   c0_i = sum_j 1/2 lamC A_ij (|Yn_i - Yn_j|^2 - |P_i - P_j|^2),  c2_i = sum_j 1/2 lamC A_ij (s_i - s_j)^2
+struct QueryBasisArgs {
+  const float* Y;
+  const float* X;       // N x ld
+  const float* x4;      // N x 4, column 0 = x
+  const float* sqrt_deg;
+  const int32_t* col;
+  const float* adj;     // capped adjacency A_ij (ELL)
+  const int32_t* deg;
+  int32_t width, N, D, ld;
+  float lamC;
+  float* s;             // [N]
+  double* xn2;          // [N]
+  double* c0;           // [N]
+  double* c2;           // [N]
+};
+void launch_query_basis_stats(const QueryBasisArgs& a, hipStream_t s);
+
+// C[N x qs] = A[N x D] (row pitch ld) . Bt[qpad x kpad]^T on v_mfma_f32_32x32x2_f32, K in one fixed order for every output.
+// mode 0 (dots): C = g = X psi^T; the epilogue writes align (cos(U*_i, psi_q)) and p = g / (sd_i + 1e-12)
+// mode 1 (mmr):  C = <Yn_i, Yn_pick(q)>; the epilogue folds it into the running maximum (first: replaces it; +inf = taken)
+struct QueryGemmArgs {
+  const float* A;
+  const float* Bt;
+  int32_t N, D, ld, kpad, qs, nq;  // nq: real query columns (< qs are stored, >= nq stored as 0 / untouched)
+  int mode, first;
+  // mode 0
+  const float* x4;
+  const double* xn2;
+  const float* sqrt_deg;
+  const double* pn2;   // [nq] |psi_q|^2
+  const double* pinv;  // [nq] 1 / (|psi_q| + 1e-12)
+  float* align;
+  float* p;
+  // mode 1
+  float* maxsim;
+};
+void launch_query_gemm(const QueryGemmArgs& a, hipStream_t s);
+
+// coh_iq = c0_i - |psi_q|^2 c2_i - sum_j lamC A_ij (s_i - s_j)(p_iq - p_jq) in fp64, stored fp32
+void launch_query_coh(const int32_t* col, const float* adj, const int32_t* deg, int32_t width, int32_t N, float lamC,
+                      const float* s, const double* c0, const double* c2, const double* pn2, const float* p, int32_t qs,
+                      int32_t nq, float* coh, hipStream_t st);
+// score = alpha (coh - mu_q) / sigma_q + (1 - alpha) align, in place over coh; mu / sigma per query from a deterministic
+// two-stage fp64 column reduction (part: [nb x nq] double2 partials, stats: [nq] double2)
+int query_stat_parts(int32_t N);
+void launch_query_score(float* coh_score, const float* align, int32_t N, int32_t qs, int32_t nq, double alpha, double2* part,
+                        double2* stats, hipStream_t st);
+
+// row-normalised anchors Yn_i = Y_i / (|Y_i| + 1e-12) (the MMR's representers; pad columns 0)
+void launch_rows_normalise(const float* Y, float* Yn, int32_t N, int32_t D, int32_t ld, hipStream_t st);
+
+// batched greedy MMR: one step for every query at once.  maxsim: N x qs running maxima (+inf = already chosen);
+// per query the best (1 - lambda) score - lambda maxsim under the total order of osc_mmr (value, then the smaller API id)
+struct MmrManyArgs {
+  const float* score;   // N x qs
+  float* maxsim;        // N x qs
+  const int32_t* api_id;  // nullptr = identity
+  const float* Yn;      // N x ld
+  float* Bt;            // [qpad x kpad] normalised anchor rows of this step's picks (the next GEMM's operand)
+  double* pval;         // [nb x nq]
+  int32_t* pid;
+  int32_t* prow;
+  int32_t* chosen_api;  // [nq x k]
+  int32_t* chosen_row;  // [nq x k]
+  int32_t N, D, ld, kpad, qs, nq, k;
+  double lambda;
+};
+int mmr_many_parts(int32_t N);
+void launch_mmr_many_argmax(const MmrManyArgs& a, int step, hipStream_t st);
+
+// out[q * k + t] = score / align of query q at its t-th pick (0 past the end)
+void launch_query_pack(const float* score, const float* align, const int32_t* chosen_row, int32_t qs, int32_t nq, int32_t k,
+                       float* out_score, float* out_align, hipStream_t st);
+
+}  // namespace osc

@@ -86,6 +86,7 @@ class OscillinkLattice:
                           C.byref(h))
         nat.check(rc, None, "osc_create")
         self._h = h
+        self._has_comm = comm is not None
         if comm is not None:
             uid, rank, world = comm
             nat.check(L.osc_comm_init(h, bytes(uid), int(rank), int(world)), h, "osc_comm_init")
@@ -110,7 +111,12 @@ class OscillinkLattice:
         self._Ustar_cache: Optional[np.ndarray] = None
         self._Ustar_sig: Optional[str] = None
         self._device_ustar_sig: Optional[str] = None
-        self.stats: dict[str, int] = {"ustar_solves": 0, "ustar_cache_hits": 0}
+        self.stats: dict[str, int] = {"ustar_solves": 0, "ustar_cache_hits": 0, "query_basis_solves": 0}
+        # query basis (bundle_many): keyed by graph / gates / chain (this counter) and the lambdas, NOT by psi
+        self._qb_version = 0
+        self._qb_key: Optional[tuple] = None
+        self._qb_scale = 0.0
+        self.last_query_basis: dict[str, Any] = {}
         self._settle_callbacks: list = []
         self._logger = None
         self._receipt_secret: Optional[bytes] = None
@@ -184,6 +190,7 @@ class OscillinkLattice:
         self._B = g.copy()
         self._call("osc_set_query", None, nat.f32(self._B))
         self._touch()
+        self._qb_version += 1
 
     @property
     def psi(self) -> np.ndarray:
@@ -313,6 +320,7 @@ class OscillinkLattice:
         self._call("osc_set_csr", nat.i64(rowptr), nat.i32(col) if col.size else None, nat.f32(a) if a.size else None)
         self._csr = None
         self._touch()
+        self._qb_version += 1
         self._invalidate_cache()
 
     @property
@@ -360,6 +368,7 @@ class OscillinkLattice:
         self._psi = p
         if g is not None:
             self._B = g
+            self._qb_version += 1
         self._call("osc_set_query", nat.f32(self._psi), nat.f32(self._B) if g is not None else None)
         self._touch()
         self._invalidate_cache()
@@ -370,6 +379,7 @@ class OscillinkLattice:
         self._B = np.ascontiguousarray(gates, dtype=np.float32).copy()
         self._call("osc_set_query", None, nat.f32(self._B))
         self._touch()
+        self._qb_version += 1
         self._invalidate_cache()
 
     def add_chain(self, chain: list[int], lamP: float = 0.2, weights: Optional[list[float]] = None) -> None:
@@ -388,6 +398,7 @@ class OscillinkLattice:
         self._chain_nodes = [int(c) for c in chain]
         self._chain_weights = None if weights is None else [float(w) for w in weights]
         self._touch()
+        self._qb_version += 1
         self._invalidate_cache()
         self._log("add_chain", {"length": len(chain), "lamP": lamP})
 
@@ -397,6 +408,7 @@ class OscillinkLattice:
         self._chain_nodes = None
         self._chain_weights = None
         self._touch()
+        self._qb_version += 1
         self._invalidate_cache()
         self._log("clear_chain", {})
 
@@ -770,6 +782,95 @@ class OscillinkLattice:
                    nat.i32(out), C.byref(n))
         return [int(i) for i in out[: int(n.value)]]
 
+    # ------------------------------------------------------------------ multi-query bundles (not in the reference)
+    def bundle_many(self, psis: np.ndarray, k: int = 8, alpha: float = 0.5, *, tol: float = 1e-4, max_iters: int = 256,
+                    as_arrays: bool = False):
+        """`bundle(k, alpha)` for each row of `psis` (Q x D), as if `set_query(psis[q])` had been called, without touching
+        the lattice's state (psi, U, the U* cache, receipts).  One query basis solve (U*(psi) =
+        X + x psi^T) serves every query; a batch is then a GEMM, one graph pass, column statistics and a batched MMR on
+        the device.  Returns Q lists of {"id", "score", "align"} (bundle()'s order), or with `as_arrays=True`
+        (ids, score, align), each Q x min(k, N)."""
+        if self._has_comm:
+            raise NotImplementedError("bundle_many: lattices with a communicator (sharded / multi-rank) are not supported")
+        P = np.asarray(psis)
+        if P.ndim != 2 or P.shape[1] != self.D:
+            raise ValueError(f"psis must be a (Q, {self.D}) array, got shape {P.shape}")
+        P = np.ascontiguousarray(P, dtype=np.float32)
+        bad = np.nonzero(~np.all(np.isfinite(P), axis=1))[0]
+        if bad.size:
+            raise ValueError(f"psis row {int(bad[0])} is not finite")
+        Q = int(P.shape[0])
+        kk = min(int(k), self.N) if k > 0 else 0
+        ids = np.zeros((Q, kk), dtype=np.int32)
+        score = np.zeros((Q, kk), dtype=np.float32)
+        align = np.zeros((Q, kk), dtype=np.float32)
+        if Q > 0 and kk > 0:
+            self._ensure_query_basis(tol, max_iters, float(np.max(np.abs(P))))
+            self._call("osc_bundle_many", nat.f32(P), Q, kk, float(alpha), 0.5, nat.i32(ids), nat.f32(score), nat.f32(align))
+        if as_arrays:
+            return ids, score, align
+        if Q == 0:
+            return []
+        return [[{"id": int(i), "score": float(s), "align": float(a)} for i, s, a in zip(ids[q].tolist(), score[q].tolist(),
+                                                                                    align[q].tolist())] for q in range(Q)]
+
+    def query_basis(self, tol: float = 1e-4, max_iters: int = 256) -> tuple[np.ndarray, np.ndarray]:
+        """The query basis (X N x D, x N) in API row order: U*(psi) = X + x psi^T (diagnostic; not in the reference).
+        Solved for the current psi's |psi|_inf unless a basis of the same graph, gates, chain, lambdas and tolerance is
+        resident already."""
+        if self._has_comm:
+            raise NotImplementedError("query_basis: lattices with a communicator (sharded / multi-rank) are not supported")
+        self._ensure_query_basis(tol, max_iters, float(np.max(np.abs(self._psi))) if self._psi.size else 0.0,
+                                 extend=False)
+        X = np.empty((self.N, self.D), dtype=np.float32)
+        x = np.empty(self.N, dtype=np.float32)
+        self._call("osc_get_query_basis", nat.f32(X), nat.f32(x))
+        return X, x
+
+    def _ensure_query_basis(self, tol: float, max_iters: int, psi_inf: float, extend: bool = True) -> None:
+        """Solve (or extend) the query basis unless the resident one serves |psi|_inf at this tolerance.  The key leaves
+        psi out on purpose: set_query keeps the basis, every change of the operator M drops it."""
+        self._push_params()
+        key = (self._qb_version, float(self.lamG), float(self.lamC), float(self.lamQ), float(self.lamP), float(tol),
+               int(max_iters))
+        scale = max(float(psi_inf), 1e-6)
+        if key == self._qb_key and (scale <= self._qb_scale or not extend):
+            return
+        fresh = key != self._qb_key
+        iters = np.zeros(2, dtype=np.int32)
+        res = np.zeros(2, dtype=np.float32)
+        ms = C.c_double(0.0)
+        self._call("osc_query_basis", float(tol), int(max_iters), scale, int(fresh), nat.i32(iters), nat.f32(res),
+                   C.byref(ms))
+        prev = self.last_query_basis if not fresh else {}
+        it_X = int(iters[0]) if fresh else int(prev["iters"]["X"])
+        res_X = float(res[0]) if fresh else float(prev["res"]["X"])
+        it_x, res_x = int(iters[1]), float(res[1])
+        converged = bool(res_X <= 0.5 * tol * (1 + 1e-5) and res_x * scale <= 0.5 * tol * (1 + 1e-5))
+        self.last_query_basis = {"iters": {"X": it_X, "x": it_x}, "res": {"X": res_X, "x": res_x},
+                                 "converged": converged, "solve_ms": float(ms.value), "psi_inf": scale,
+                                 "x_only": not fresh}
+        self._qb_key = key
+        self._qb_scale = scale
+        self.stats["query_basis_solves"] += 1
+        self._log("query_basis_solve", {"tol": tol, "max_iters": max_iters, **self.last_query_basis})
+        if not converged:
+            self._log("query_basis_convergence_warn", {"res": self.last_query_basis["res"], "tol": tol,
+                                                       "iters": self.last_query_basis["iters"], "psi_inf": scale})
+
+    def _mmr_many(self, scores: np.ndarray, k: int, lambda_div: float) -> np.ndarray:
+        """mmr_diversify (graph.py:114-133) for every column of `scores` (N x Q) at once on the device; (Q, min(k, N))
+        API ids.  Private: the batched MMR of bundle_many, exposed for tests against `_mmr`."""
+        S = np.ascontiguousarray(scores, dtype=np.float32)
+        if S.ndim != 2 or S.shape[0] != self.N:
+            raise ValueError(f"scores must be ({self.N}, Q)")
+        Q = int(S.shape[1])
+        kk = min(int(k), self.N) if k > 0 else 0
+        out = np.zeros((Q, kk), dtype=np.int32)
+        if Q > 0 and kk > 0:
+            self._call("osc_mmr_many", nat.f32(S), Q, kk, float(lambda_div), nat.i32(out))
+        return out
+
     # ------------------------------------------------------------------ callbacks / logging (lattice.py:571-579, 930-949)
     def add_settle_callback(self, fn) -> None:
         self._settle_callbacks.append(fn)
@@ -895,6 +996,7 @@ class OscillinkLattice:
         self._graph_build_ms = 1000.0 * (time.time() - t0)
         self._csr = None
         self._touch()
+        self._qb_version += 1
         self._invalidate_cache()
         self._log("rebuild_graph", {"k": int(self._kneighbors), "row_cap_val": float(self._row_cap_val),
                                     "deterministic_k": self._deterministic_k, "neighbor_seed": self._neighbor_seed})
