@@ -105,8 +105,8 @@ int osc_get_row_order(osc_handle h, int32_t* perm);
 int osc_spmm_plan(osc_handle h, int32_t* launches, int32_t* slab_cols, int32_t* xs_workgroups);
 
 /* the CG matvec of the last general-path solve: src_blocks = 0 for the plain apply, else the number of source-row blocks
- * the blocked apply walked (chosen when the 32-column slab an XCD gathers from, N x 128 B, is at least OSC_BLK_MB = 2
- * MiB; a chain prior of up to 4096 path rows is applied by a small launch behind it; the block count follows the mean degree;
+ * the blocked apply walked (chosen when the 32-column slab an XCD gathers from, N x 128 B, is at least 2 MiB; a chain
+ * prior of up to 4096 path rows is applied by a small launch behind it; the block count follows the mean degree;
  * OSC_SPMM_BLOCKED = 0 off / n forces n blocks); blocked_applies = such matvecs enqueued since creation (measurement
  * aid) */
 int osc_apply_info(osc_handle h, int32_t* src_blocks, int64_t* blocked_applies);
@@ -249,11 +249,7 @@ int osc_dynamics(osc_handle h, const float* U_prev_or_null, const float* U_next_
  * CG matvec; one sample per apply = all its launches), 1 = fused x/r update, 2 = p update, 3 = kNN GEMM+top-k,
  * 4 = the initial-residual apply of a solve (same gather plus the rhs / r / p streams).  Returns samples and the
  * summed device time since the last reset.  Enabling adds two event records per sample.
- * Diagnostic slots of the source-blocked matvec (k_apply_blocked): with OSC_BLK_STAMP=1 in the environment at creation
- * and profiling on, its loop-form launches run a cycle-stamping instantiation; which = 8..11 then return, in *total_ms,
- * the shader cycles a gathering wave spent (mean over the waves, summed over the stamped launches) in all / in its gather
- * rounds / at the workgroup barrier / in its epilogues, 12..13 the list wave's cycles fetching slot rows / at the barrier,
- * and *launches = the stamped launches.  which = 14: *launches = the kernel shape the last blocked matvec ran with
+ * which = 14: *launches = the kernel shape the last blocked matvec ran with
  * (0 = two 8-wave workgroups per CU, one gather round in flight; 1..6 = one workgroup per CU, four rounds in flight,
  * 8 / 12 / 16 / 20 / 24 / 28 row groups per wave; OSC_BLK_VARIANT forces one), *total_ms = 0.  which = 15: *launches = the
  * pieces the last graph build received its anchors in (0: they were resident before it started; negative: a streamed build

@@ -305,7 +305,7 @@ __global__ __launch_bounds__(256) void k_spmm(const SpmmArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Operator apply, source-blocked (the CG matvec wherever the XCD-affine slab mode runs: blocked_plan in osc_api.hip).  Measured (scripts/exp/gather_bench.hip, profiles/r02_gather_bench.txt): a CU completes a random
+// Operator apply, source-blocked (the CG matvec wherever the XCD-affine slab mode runs: host_logic.hpp, plan_apply).  Measured (scripts/exp/gather_bench.hip, profiles/r02_gather_bench.txt): a CU completes a random
 // 128-byte row gather every 2.4 clk when the rows come from <= 3.6 MB per XCD, every 7.0 clk from a 12.8 MB slab -- the
 // request rate, not the bytes, is what the plain apply pays for.  Here the neighbour rows are visited block by block:
 //   * source rows are cut into nb blocks, nb such that a row has ~3.3 edges into each (4 slots per row and block);
@@ -325,8 +325,7 @@ __global__ __launch_bounds__(256) void k_spmm(const SpmmArgs a) {
 // Same terms per row as k_spmm; the order of summation differs where a row has more than OSC_BLK_SLOTS edges into one
 // block (those move to a later block's free slots, launch_blocked_fill): results agree with k_spmm's to fp32 rounding
 // of the sums (3e-8 relative on the state).  The chain prior's few rows are applied by k_chain_fix behind this kernel.
-constexpr int kBlkGroups = 16;   // row groups per gathering wave (4 registers each for the sums)
-constexpr int kBlkGatherWaves = 7;  // + the list wave: workgroups of 512 (3 + 1 with 17 groups: 0.71 instead of 0.66 ms at config 3)
+// (its kernel shapes: host_logic.hpp, kBlkShapes)
 
 __device__ __forceinline__ float4 ld4_at(const float* base, uint32_t byte_off) {
   return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(base) + byte_off);
@@ -380,10 +379,7 @@ __device__ __forceinline__ void blk_fold(float4 dot, float (&red)[NW][32], float
 // miss the L2, so a round of 32 lines practically always waits for one fabric round trip: with one round in flight the
 // kernel is bound by bytes in flight / miss latency.  PD > 1 issues round g + PD - 1 before it consumes round g (the
 // slots' weights and the gathered rows of PD rounds in registers).  WPE: waves per SIMD the register budget is set for.
-// STAMP (diagnostic instantiations, OSC_BLK_STAMP=1; loop form only): every wave adds the shader cycles it spent in its
-// gather rounds / epilogues / at the barrier (the list wave: fetching / at the barrier) to words of its own in the
-// buffer ii.R points to -- where a launch's time goes, wave by wave (osc_profile_get slots 8-13).
-template <int GM, int CW, bool INIT = false, int PD = 1, int WPE = 4, bool STAMP = false>
+template <int GM, int CW, bool INIT = false, int PD = 1, int WPE = 4>
 __global__ __launch_bounds__((CW + 1) * 64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_apply_blocked(const BlkArgs a,
                                                                                                                 const BlkInit ii) {
   constexpr int SL = OSC_BLK_SLOTS, NT = (CW + 1) * 64;
@@ -455,37 +451,16 @@ __global__ __launch_bounds__((CW + 1) * 64) __attribute__((amdgpu_waves_per_eu(W
         }
       }
     };
-    unsigned long long t_fetch = 0, t_bar = 0, t_all = 0, ts = 0;
-    if constexpr (STAMP) t_all = ts = __builtin_amdgcn_s_memtime();
-    auto lap = [&](unsigned long long& into) {
-      if constexpr (STAMP) {
-        const unsigned long long now = __builtin_amdgcn_s_memtime();
-        into += now - ts;
-        ts = now;
-      }
-    };
     if (nphase > 0) fetch_slots(0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    lap(t_fetch);
     __syncthreads();
-    lap(t_bar);
     for (int ph = 0; ph < nphase; ++ph) {
       if (ph + 1 < nphase) fetch_slots(ph + 1);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      lap(t_fetch);
       __syncthreads();
-      lap(t_bar);
       if ((ph + 1) % per_slab == 0) {
         const int sc0 = phase(ph).sc0;
         blk_fold<CW + 1>(f4(0.f), red, a.part, ld, sc0, min(a.c1, sc0 + 32), wave, lane);
-      }
-    }
-    if constexpr (STAMP) {
-      if (lane == 0) {
-        unsigned long long* w = reinterpret_cast<unsigned long long*>(ii.R) + ((size_t)blockIdx.x * (CW + 1) + wave) * 4;
-        w[0] += __builtin_amdgcn_s_memtime() - t_all;
-        w[1] += t_fetch;
-        w[2] += t_bar;
       }
     }
     return;
@@ -495,17 +470,7 @@ __global__ __launch_bounds__((CW + 1) * 64) __attribute__((amdgpu_waves_per_eu(W
   const uint32_t lr16 = (uint32_t)lr * 16u;
   float4 acc[GM];
   float4 dot[1] = {f4(0.f)};
-  unsigned long long t_gather = 0, t_epi = 0, t_bar = 0, t_all = 0, ts = 0;
-  if constexpr (STAMP) t_all = ts = __builtin_amdgcn_s_memtime();
-  auto lap = [&](unsigned long long& into) {
-    if constexpr (STAMP) {
-      const unsigned long long now = __builtin_amdgcn_s_memtime();
-      into += now - ts;
-      ts = now;
-    }
-  };
   __syncthreads();
-  lap(t_bar);
   for (int ph = 0; ph < nphase; ++ph) {
     const BlkPhase p = phase(ph);
     const bool cok = p.sc0 + lr * 4 < a.c1;
@@ -569,7 +534,6 @@ __global__ __launch_bounds__((CW + 1) * 64) __attribute__((amdgpu_waves_per_eu(W
         asm volatile("" : "+v"(acc[g].x), "+v"(acc[g].y), "+v"(acc[g].z), "+v"(acc[g].w));
       }
     }
-    lap(t_gather);
     if (p.b == nb - 1) {  // the rows of this slice are complete: the rest of long lists, diagonal term, output, p.Ap
       const int w8 = opaque(W8);
       const int row_first = rlo + p.slice * slice_rows + ((wgx * CW + wave) << 3) + sub;
@@ -648,21 +612,10 @@ __global__ __launch_bounds__((CW + 1) * 64) __attribute__((amdgpu_waves_per_eu(W
         }
       }
     }
-    lap(t_epi);
     __syncthreads();
-    lap(t_bar);
     if ((ph + 1) % per_slab == 0) {  // the slab's column sums
       blk_fold<CW + 1>(dot[0], red, a.part, ld, p.sc0, min(a.c1, p.sc0 + 32), wave, lane);
       dot[0] = f4(0.f);
-    }
-  }
-  if constexpr (STAMP) {
-    if (lane == 0) {
-      unsigned long long* w = reinterpret_cast<unsigned long long*>(ii.R) + ((size_t)blockIdx.x * (CW + 1) + wave) * 4;
-      w[0] += __builtin_amdgcn_s_memtime() - t_all;
-      w[1] += t_gather;
-      w[2] += t_bar;
-      w[3] += t_epi;
     }
   }
 }
@@ -1164,42 +1117,16 @@ void launch_blocked_fill(const int32_t* col, const float* w, const int32_t* deg,
                      slots, rest, over, over_count);
   HIP_CHECK(hipGetLastError());
 }
-// The shapes of k_apply_blocked the library holds: {row groups per gathering wave, gathering waves per workgroup, gather
-// rounds in flight per wave, waves per SIMD}.  0: rounds 2-4 (two 8-wave workgroups per CU, one round in flight, tests per
-// group).  1-3 (round 5, "wide"): ONE 8-wave workgroup per CU at two waves per SIMD, four rounds in flight, test-free
-// straight-line rounds -- so the group count is a template constant and there are six of them, 8 to 28 groups
-// (blocked_shape_for picks the smallest that holds the lattice's groups).
-struct BlkShape {
-  int gm, cw, pd, wpe;
-};
-constexpr BlkShape kBlkShapes[] = {{kBlkGroups, kBlkGatherWaves, 1, 4}, {8, 7, 4, 2},  {12, 7, 4, 2}, {16, 7, 4, 2},
-                                   {20, 7, 4, 2},                       {24, 7, 4, 2}, {28, 7, 4, 2}};
-constexpr int kBlkShapeCount = (int)(sizeof(kBlkShapes) / sizeof(kBlkShapes[0]));
-#define OSC_BLK_SHAPE_SWITCH(v, CALL) \
-  switch (v) {                        \
-    case 0: CALL(kBlkGroups, kBlkGatherWaves, 1, 4); break; \
-    case 1: CALL(8, 7, 4, 2); break;  \
-    case 2: CALL(12, 7, 4, 2); break; \
-    case 3: CALL(16, 7, 4, 2); break; \
-    case 4: CALL(20, 7, 4, 2); break; \
-    case 5: CALL(24, 7, 4, 2); break; \
-    case 6: CALL(28, 7, 4, 2); break; \
-    default: throw std::runtime_error("blocked apply: unknown kernel shape"); \
+// one instantiation of k_apply_blocked per entry of kBlkShapes (host_logic.hpp)
+#define OSC_BLK_SHAPE_CASE(v, CALL) \
+  case v: CALL(kBlkShapes[v].gm, kBlkShapes[v].cw, kBlkShapes[v].pd, kBlkShapes[v].wpe); break;
+#define OSC_BLK_SHAPE_SWITCH(v, CALL)                                         \
+  switch (v) {                                                               \
+    OSC_BLK_SHAPE_CASE(0, CALL) OSC_BLK_SHAPE_CASE(1, CALL) OSC_BLK_SHAPE_CASE(2, CALL) OSC_BLK_SHAPE_CASE(3, CALL) \
+    OSC_BLK_SHAPE_CASE(4, CALL) OSC_BLK_SHAPE_CASE(5, CALL) OSC_BLK_SHAPE_CASE(6, CALL)                             \
+    default: throw std::runtime_error("blocked apply: unknown kernel shape");    \
   }
-// the cycle-stamping instantiations (diagnostics): the round-4 shape and the widest one
-#define OSC_BLK_STAMP_SWITCH(v, CALL) \
-  switch (v) {                        \
-    case 0: CALL(kBlkGroups, kBlkGatherWaves, 1, 4); break; \
-    case 6: CALL(28, 7, 4, 2); break; \
-    default: throw std::runtime_error("blocked apply: no stamping instantiation of this kernel shape (OSC_BLK_VARIANT=0 or 6)"); \
-  }
-static const BlkShape& blk_shape(int variant) {
-  if (variant < 0 || variant >= kBlkShapeCount) throw std::runtime_error("blocked apply: unknown kernel shape");
-  return kBlkShapes[variant];
-}
-int blocked_variants() { return kBlkShapeCount; }
-int blocked_groups_max(int variant) { return blk_shape(variant).gm; }
-int blocked_gather_waves(int variant) { return blk_shape(variant).cw; }
+static_assert(kBlkShapeCount == 7, "OSC_BLK_SHAPE_SWITCH needs one case per entry of kBlkShapes");
 void launch_rows_to_slab(const float* src, float* dst, int64_t N, int32_t ld, int32_t c0, int32_t c1, int grid, hipStream_t s,
                          const float* sub) {
   for (int32_t s0 = c0; s0 < c1; s0 += 2048) {  // at most 2048 columns per launch, like the other elementwise kernels
@@ -1240,8 +1167,9 @@ int blocked_resident_per_cu(int variant) {
   return n;
 }
 
-void launch_apply_blocked(const BlkArgs& a, int grid, hipStream_t s, const BlkInit* init, int variant, unsigned long long* stamps) {
-  const BlkShape& sh = blk_shape(variant);
+void launch_apply_blocked(const BlkArgs& a, int grid, hipStream_t s, const BlkInit* init, int variant) {
+  if (variant < 0 || variant >= kBlkShapeCount) throw std::runtime_error("blocked apply: unknown kernel shape");
+  const BlkShape& sh = kBlkShapes[variant];
   if (grid < 8 || (grid & 7) != 0 || a.xs < 1 || a.xs > grid / 8 || a.xs_groups < 1 || 8 % a.xs_groups != 0 || a.groups < 1 ||
       a.groups > sh.gm || a.slices < 1 || a.nb < 1 || a.nb > OSC_MAX_SRC_BLOCKS || !a.slots || !a.rest ||
       (int64_t)a.N * a.ld * 4 >= ((int64_t)1 << 32) || (a.c0 & 31) != 0)
@@ -1250,12 +1178,6 @@ void launch_apply_blocked(const BlkArgs& a, int grid, hipStream_t s, const BlkIn
     if (!init->R || !init->Z || !init->psi || init->Z == a.X) throw std::runtime_error("blocked apply: bad INIT arguments");
 #define CALL(G, W, P, E) hipLaunchKernelGGL((k_apply_blocked<G, W, true, P, E>), dim3(grid), dim3((W + 1) * 64), 0, s, a, *init)
     OSC_BLK_SHAPE_SWITCH(variant, CALL);
-#undef CALL
-  } else if (stamps != nullptr) {  // diagnostic: [grid][waves][4] cycle counters, added to launch after launch
-    BlkInit st{};
-    st.R = reinterpret_cast<float*>(stamps);
-#define CALL(G, W, P, E) hipLaunchKernelGGL((k_apply_blocked<G, W, false, P, E, true>), dim3(grid), dim3((W + 1) * 64), 0, s, a, st)
-    OSC_BLK_STAMP_SWITCH(variant, CALL);
 #undef CALL
   } else {
 #define CALL(G, W, P, E) hipLaunchKernelGGL((k_apply_blocked<G, W, false, P, E>), dim3(grid), dim3((W + 1) * 64), 0, s, a, BlkInit{})

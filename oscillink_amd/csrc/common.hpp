@@ -7,6 +7,8 @@
 #include <stdexcept>
 #include <string>
 
+#include "host_logic.hpp"  // (OSC_MAX_SRC_BLOCKS, OSC_CHAIN_FIX_MAX_ROWS, kBlkShapes)
+
 namespace osc {
 
 struct HipError : std::runtime_error {
@@ -96,7 +98,6 @@ struct GraphView {
 // edge that finds the slot row of its block full sits in a later block's free slots instead (k_blk_fill), and what fits
 // nowhere is in over[rest[row].x .. + rest[row].y), added after the blocks (so such rows' sums are formed in a different
 // order than k_spmm's: same terms, last-bit differences).
-constexpr int OSC_MAX_SRC_BLOCKS = 32;  // (register arrays of this size in k_blk_count / k_blk_fill)
 constexpr int OSC_BLK_SLOTS = 4;
 struct BlockedView {
   const int2* slots;    // [nb][N][OSC_BLK_SLOTS]
@@ -211,13 +212,8 @@ void launch_blocked_count(const int32_t* col, const int32_t* deg, int32_t width,
                           unsigned* over_count, hipStream_t s);
 void launch_blocked_fill(const int32_t* col, const float* w, const int32_t* deg, int32_t width, int32_t N, int32_t nb,
                          int2* slots, int2* rest, int2* over, unsigned* over_count, hipStream_t s);
-// row groups per wave the blocked apply holds in registers, and the workgroups per CU it needs resident
-int blocked_variants();                 // kernel shapes of the blocked matvec (OSC_BLK_VARIANT)
-int blocked_groups_max(int variant);
-int blocked_gather_waves(int variant);
 // Chain prior beside the blocked matvec: out_i -= cP sum_j Wp_ij x_j for the (few) rows of the chain's path graph, and
 // the matching terms of the p . Ap column sums into the rows [part_row0, part_row0 + chunks) of `part`.
-constexpr int OSC_CHAIN_FIX_MAX_ROWS = 4096;
 constexpr int OSC_CHAIN_FIX_MAX_CHUNKS = 64;
 struct ChainFixArgs {
   const float* X;        // operand, slab-major
@@ -261,9 +257,8 @@ void launch_rows_to_slab(const float* src, float* dst, int64_t N, int32_t ld, in
 void launch_init_finish(const InitFinishArgs& a, int grid, hipStream_t s);
 int chain_fix_chunks(int32_t prows);
 void launch_chain_fix(const ChainFixArgs& a, hipStream_t s);
-void launch_apply_blocked(const BlkArgs& a, int grid, hipStream_t s, const BlkInit* init = nullptr, int variant = 0,
-                          unsigned long long* stamps = nullptr);
-int blocked_resident_per_cu(int variant);
+void launch_apply_blocked(const BlkArgs& a, int grid, hipStream_t s, const BlkInit* init = nullptr, int variant = 0);
+int blocked_resident_per_cu(int variant);  // workgroups per CU a kernel shape (kBlkShapes) gets resident
 void launch_spmm(int mode, const SpmmArgs& a, int grid, hipStream_t s);
 void launch_update_xr(const UpdateArgs& a, int grid, hipStream_t s);
 void launch_update_p(const UpdateArgs& a, int grid, hipStream_t s);

@@ -7,6 +7,7 @@
 //   pack_csr                          : validation + ELL packing of an injected adjacency (osc_set_csr)
 //   xs_groups / blocked_geometry / blocked_list_extent : launch geometry of the XCD-affine and source-blocked matvec
 //   blocked_block_count               : how many source blocks the blocked matvec walks
+//   plan_apply                        : how a CG solve launches its operator apply (the one place that decides it)
 //   blk_place_row                     : host model of k_blk_count / k_blk_fill (one row of the block-major graph copy)
 //   CgXSchedule                       : which launch of a CG solve carries which iteration's x update (run_cg)
 #pragma once
@@ -18,6 +19,24 @@
 #include <vector>
 
 namespace osc {
+
+// Compile-time limits and kernel shapes of the source-blocked matvec (k_apply_blocked): plan_apply reads them, and
+// cg_kernels.hip instantiates one kernel per shape.
+constexpr int OSC_MAX_SRC_BLOCKS = 32;        // (register arrays of this size in k_blk_count / k_blk_fill)
+constexpr int OSC_CHAIN_FIX_MAX_ROWS = 4096;  // most path rows of a chain prior k_chain_fix applies beside the matvec
+constexpr int kBlkGroups = 16;      // row groups per gathering wave (4 registers each for the sums)
+constexpr int kBlkGatherWaves = 7;  // + the list wave: workgroups of 512 (3 + 1 with 17 groups: 0.71 instead of 0.66 ms at config 3)
+// {row groups per gathering wave, gathering waves per workgroup, gather rounds in flight per wave, waves per SIMD}.  0: rounds
+// 2-4 (two 8-wave workgroups per CU, one round in flight, tests per group).  1-6 (round 5, "wide"): ONE 8-wave workgroup per
+// CU at two waves per SIMD, four rounds in flight, test-free straight-line rounds -- so the group count is a template
+// constant and there are six of them, 8 to 28 groups (plan_apply picks the smallest that holds the lattice's groups).
+struct BlkShape {
+  int gm, cw, pd, wpe;
+};
+constexpr BlkShape kBlkShapes[] = {{kBlkGroups, kBlkGatherWaves, 1, 4}, {8, 7, 4, 2},  {12, 7, 4, 2}, {16, 7, 4, 2},
+                                   {20, 7, 4, 2},                       {24, 7, 4, 2}, {28, 7, 4, 2}};
+constexpr int kBlkShapeCount = (int)(sizeof(kBlkShapes) / sizeof(kBlkShapes[0]));
+
 namespace host {
 
 struct InvalidArg : std::invalid_argument {
@@ -188,16 +207,17 @@ inline int xs_groups(int32_t ncols, int cap = 8) {
   return std::min(g, cap);
 }
 // ... halved until the slabs in flight (groups x N x 128 B) fit 128 MiB of the Infinity Cache; 0 = the mode does not pay:
-// below min_reduced groups (the plain slab apply loses to the general path under 4 groups -- config 5's shape 56.4 ms
-// general, 54.2 at 4 groups, 57.1 at 2, 60.7 at 1 --, the blocked matvec still wins at 2: xs_plan in osc_api.hip; config
+// below min_reduced groups (plan_apply passes kXsGroupsMin: the plain slab apply loses to the general path under 4 groups --
+// config 5's shape 56.4 ms general, 54.2 at 4 groups, 57.1 at 2, 60.7 at 1 --, the blocked matvec still wins at 2; config
 // 4's shape loses at every count)
 // Round 5: beyond that budget (N > 524 288) the mode survives only under the wide blocked matvec -- what it gathers from at one
 // time is a source BLOCK, not a slab, so the slabs in flight need not fit anything -- with at most four slab groups and
 // windows of at least four slabs (profiles/r05_large_n_blocked.txt, per settle against the plain slab apply: 600k x 768 k 32
 // 62.1 -> 45.6 ms, 700k x 384 k 16 21.8 -> 20.9, 800k x 256 16.2 -> 15.6, 1M x 384 31.5 -> 29.6, 1M x 128 10.06 -> 9.98, 1.5M x
 // 256 34.1 -> 32.5; eight groups lose to four: 600k x 768 47.5 vs 45.6; 1M x 64 k 8 loses: 3.70 vs 3.64).  The caller
-// (xs_plan) keeps the mode there only when the blocked matvec can run.
+// (plan_apply) keeps the mode there only when the blocked matvec can run.
 constexpr int64_t kXsBudgetRows = 524288;
+constexpr int kXsGroupsMin = 2;  // fewest slab groups the mode is kept for when the natural count had to be reduced
 inline int xs_groups_for(int64_t N, int32_t ncols, int cap, int min_reduced = 4) {
   const int natural = xs_groups(ncols, cap);
   int g = natural;
@@ -307,6 +327,173 @@ inline void blk_place_row(const int32_t* cols, const float* w, int deg, int32_t 
   }
   for (int q = 0; q < nb; ++q)
     for (int t = tail[(size_t)q]; t < SL; ++t) slots[(size_t)q * SL + t] = BlkEntry{std::min(N - 1, q * rpb), 0.f};
+}
+
+// ---- the operator-apply plan of a CG solve (osc_solve.hip: apply_plan fills the inputs from the handle) ---------------
+// The apply runs as sequential column slabs, or as XCD-affine 32-column slabs (SpmmArgs::xs) with the search direction
+// row-major or slab-major, and under the latter as the source-blocked matvec (k_apply_blocked) in one of kBlkShapes.
+constexpr int kXsMinCols = 32;  // narrowest column window the xs mode is used for (96 until round 3 -- with the blocked
+                                // matvec under it, one- and two-slab windows win too: 100k x 64 k 16 0.505 -> 0.425 ms per
+                                // settle, 100k x 32 0.352 -> 0.309, 200k x 64 k 32 1.43 -> 0.97, 60k x 64 k 32 0.438 -> 0.387)
+constexpr int64_t kXsMinRows = 6144;  // smallest lattice the xs mode is used for (windows of >= 256 columns)
+constexpr double kBlkMinSlabMiB = 2.0;  // smallest slab (N x 128 B) the blocked matvec is chosen for
+constexpr int32_t kMaxSlabCols = 2048;  // widest column window one plain launch covers (8 x 256 floats per row)
+struct ApplyInputs {
+  int64_t N = 0, nnz = 0;             // the handle: rows, edges, ELL width, pitch, column window, BFS order, chain rows
+  int32_t width = 0, ld = 0, c0 = 0, c1 = 0;
+  bool reordered = false;
+  int32_t prows = 0;
+  int32_t sc0 = 0, sc1 = 0, sld = 0;  // the solve: column window, buffer pitch, chain prior active
+  bool with_path = false;
+  int grid = 0;                       // cg_grid
+  int resident[kBlkShapeCount] = {};  // workgroups per XCD each blocked shape gets resident
+  // forcing switches: OSC_SPMM_XS (-1 auto), OSC_XS_NB (0 auto), OSC_SPMM_BLOCKED (< 0 auto), OSC_BLK_VARIANT (-1 auto),
+  // OSC_SPMM_DEEP
+  int spmm_xs = -1, xs_nb = 0, spmm_blocked = -1, blk_variant = -1;
+  bool spmm_deep = true;
+};
+struct ApplyPlan {
+  int xs = 0;          // xs workgroups per XCD for row-major operands; 0 = column slabs
+  int xs_pmajor = 0;   // ... for the slab-major search direction
+  int xs_groups = 0;   // slab groups of the xs mode
+  int32_t slab = 0;    // columns per launch (xs: the whole window)
+  int launches = 0;
+  bool deep = false;   // BFS-ordered lattice: the apply with 8 gathers in flight per row (SpmmArgs::deep)
+  bool pblk = false;   // slab-major search direction
+  int src_blocks = 0;  // source blocks of the blocked matvec; 0 = the plain apply
+  int shape = 0;       // its kernel shape (kBlkShapes)
+  BlockedGeom geom;    // its launch geometry
+};
+inline ApplyPlan plan_apply(const ApplyInputs& in) {
+  const int64_t N = in.N;
+  const int32_t hcols = in.c1 - in.c0, ncols = in.sc1 - in.sc0;
+  auto geometry = [&](int xg, int shape) {
+    return blocked_geometry(N, xg, in.grid, in.resident[shape], kBlkShapes[shape].gm, kBlkShapes[shape].cw);
+  };
+  auto groups = [&](int32_t cols) {  // (forced mode: the natural count)
+    const int g = xs_groups_for(N, cols, 8, kXsGroupsMin);
+    return g > 0 ? g : xs_groups(cols);
+  };
+  // Kernel shape of the blocked matvec for a window cut into xg slab groups.  The wide shapes carry their group count as a
+  // template constant -- the smallest that holds the lattice's groups is used -- and are taken from 96 000 rows on, where
+  // they win at every width measured except one slab per XCD below 150k rows; below 96k rows they are within +-2 % of
+  // shape 0 with single wins and losses of 5-7 % either way, so shape 0 stays there.
+  // Measured against shape 0 (profiles/r05_blk_shape_sweep.txt, per AP launch, exact-fit group counts): 20k x 768 -7.5 %, 20k x
+  // 128 k 16 +5.8 %, 30k-80k x 768 -0.8 ... +2.7 %, 100k x 768 -4.6 %, 100k x 384 k 16 -4.8 %, 100k x 1024 k 48 -4.0 %, 100k x
+  // 96 (rank 0 of 8's window of config 3) -10.9 %, 100k x 192 -2.7 %, 160k x 768 -10.9 %, 200k x 768 -9.6 %, 200k x 64 -13.0 %,
+  // 260k x 512 -15.0 %, 400k x 384 k 16 -7.1 %; one slab per XCD: 100k x 64 k 16 +5.0 %, 100k x 128 k 16 +1.4 %, 130k x 256
+  // +1.4 ... +3.6 % -- there the wide shapes wait for N = 150k.
+  auto shape_for = [&](int xg) {
+    if (in.blk_variant >= 0) return in.blk_variant;
+    const int slabs_per_group = ((hcols + 31) / 32 + xg - 1) / std::max(1, xg);
+    if (N < 96000 || (slabs_per_group < 2 && N < 150000)) return 0;
+    const BlockedGeom g = geometry(xg, kBlkShapeCount - 1);
+    for (int v = 1; v < kBlkShapeCount; ++v)
+      if (g.groups <= kBlkShapes[v].gm) return v;
+    return 0;
+  };
+  // Source blocks of the blocked matvec over the handle's window: 0 = the plain apply.  Chosen wherever the XCD-affine slab
+  // mode itself runs from a 2 MiB slab (N = 16384) on.  Measured against the plain apply (k = 32 unless noted): N = 20k x
+  // 768 -7 %, 35k x 768 -26 %, 40k x 256 (k 8) -25 %, 50k x 512 -30 %, 65k x 256 (k 16) -30 %, 60k x 1024 (k 24) -29 %, 80k x
+  // 768 -39 %, 100k x 768 -39 % (k 16, D 384: -33 %; k 48: -47 %; k 64: -45 %), 100k x 128 (k 16) -35 %, 110k x 768 -40 %,
+  // 130k x 256 -43 %; round 3: 160k x 768 -31 %, 200k x 768 -37 % (k 64: -46 %), 260k x 768 -22 % (k 64: -37 %).
+  auto blocks = [&](bool with_path) {
+    if (in.spmm_blocked == 0 || (with_path && (in.prows < 1 || in.prows > OSC_CHAIN_FIX_MAX_ROWS)) ||
+        N * in.width >= ((int64_t)1 << 28) || N >= ((int64_t)1 << 24) || N * in.ld * 4 >= ((int64_t)1 << 32))
+      return 0;
+    if (in.spmm_blocked > 0) return std::min(in.spmm_blocked, OSC_MAX_SRC_BLOCKS);
+    if ((double)N * 128.0 < kBlkMinSlabMiB * 1024.0 * 1024.0) return 0;
+    // narrow windows of small lattices: the plain slab apply is ahead (round 4 shape sweep: 16384 x 128 k 16 0.205 vs 0.221 ms
+    // per settle; from 20000 rows on a tie or a win)
+    if (N < 20000 && hcols <= 128) return 0;
+    // block count from the mean degree and the lattice size (blocked_edges_per_block); a lattice in BFS order: 2.2 edges per
+    // block -- x4 of x2 / x3 / x4 / x6 / x8 at mean degree 8.3, x8 of x6 / x8 / x12 at 20.2
+    const double mean_deg = N > 0 ? (double)in.nnz / (double)N : 0.0;
+    const double e = in.reordered                ? 2.2
+                     : shape_for(groups(hcols)) > 0 ? blocked_edges_per_block_wide(N)
+                                                    : blocked_edges_per_block(N);
+    return blocked_block_count(mean_deg, e, OSC_MAX_SRC_BLOCKS);
+  };
+  // XCD-affine 32-column slabs: workgroups per XCD, 0 = no.  Pays when the gathered operand is far larger than an XCD's L2
+  // and the graph has no row locality to exploit: each XCD then keeps 4 MB / (N x 128 B) of ITS slab in L2 (31 % at N =
+  // 100k) instead of 4 MB / (N x 512 B) of a slab all eight share.  With fewer than 8 slabs (or a count that is not a
+  // multiple of 8) the XCDs pair up: gcd(8, slabs) slab groups, the XCDs of a group split the rows.  Needs 128-byte-aligned
+  // rows (the handle's pitch and window, whatever the solve's) and the slabs in flight (groups x N x 128 B) inside the
+  // Infinity Cache: measured 1.11 vs 1.26 ms per apply at N = 100k, D = 768; no gain at N = 200k, D = 1536 with 8 slabs
+  // (205 MB) in flight, 4 % with 4 (xs_groups_for); 36 % slower at N = 1M, D = 384.
+  auto xs_workgroups = [&]() -> int {
+    if (in.grid < 8 || (in.grid & 7) != 0) return 0;
+    const int nb = std::max(1, std::min(in.grid / 8, in.xs_nb > 0 ? in.xs_nb : 96));
+    if (in.spmm_xs >= 0) return in.spmm_xs ? nb : 0;
+    if ((in.ld & 31) != 0 || (in.c0 & 31) != 0) return 0;
+    // A lattice stored in BFS order gathers from its XCD's L2 on the general path already (docs/DESIGN_HISTORY.md section 3),
+    // so the slab mode is off for it -- except large narrow ones, where the source-blocked matvec on top of the local order
+    // wins (round 4, scripts/exp/r04_bfs_blocked_sweep.py, clustered anchors, per settle: 300k x 128 k 16 2.17 -> 1.95 ms,
+    // 300k x 256 k 32 6.15 -> 5.0-5.3, 400k x 256 6.35 -> 5.35, 600k x 128 4.79 -> 3.92, 1M x 128 8.15 -> 6.72; at 384
+    // columns a tie (400k 8.06 / 7.98, 1M 20.4 / 20.7), at 200k rows a loss (128 columns: 1.25 -> 1.32)).
+    if (in.reordered) return (N >= 300000 && ncols <= 256 && blocks(false) > 0) ? nb : 0;
+    // from N = 32768 on, and from 6144 (16384 until round 3) for windows of >= 256 columns (N = 20000, D = 256: apply 43.5 ->
+    // 31.4 us); narrower windows: 32768 rows, but 12288 where the window is whole groups of four slabs (every XCD pair a
+    // slab of its own) and 24576 for other windows of >= 128 columns (scripts/exp/xs_narrow_sweep.py, k = 16, per settle:
+    // 20000 x 128 246 -> 223 us, 32000 x 128 347 -> 301, 12000 x 128 192 -> 186, 32000 x 192 484 -> 438, 24000 x 192 393
+    // -> 378, 20000 x 192 345 -> 360; 64 and 32 columns: a tie or a loss up to 32000 rows)
+    const int narrow_rows = ncols < 128 ? 32768 : (ncols % 128) == 0 ? 12288 : 24576;
+    if (N < kXsMinRows || (N < narrow_rows && ncols < 256) || ncols < kXsMinCols) return 0;
+    // below 16384 rows (round 3: the floor was 16384) a 32-column slab is at most 2 MB -- it sits in its XCD's L2 whole,
+    // where the general path spreads N x window over all eight L2s -- which pays once a row has enough gathers: per settle
+    // 6500 x 768 k 32 0.520 -> 0.437 ms, 9000 x 1024 k 32 0.925 -> 0.697, 8192 x 1536 k 32 1.32 -> 0.91, 14000 x 256 k 32
+    // 0.406 -> 0.329, 9000 x 256 k 16 0.236 -> 0.219, 7000 x 512 k 16 0.299 -> 0.280; at k = 8 it loses (14000 x 320: 0.307
+    // -> 0.329)
+    if (N < 16384 && (double)in.nnz < 10.0 * (double)N) return 0;
+    const int xg = xs_groups_for(N, ncols, 8, kXsGroupsMin);
+    if (xg == 0) return 0;
+    // beyond the Infinity-Cache budget only the (wide) blocked matvec keeps the mode: xs_groups_for
+    if (N > kXsBudgetRows && blocks(false) == 0) return 0;
+    // Two slab groups (262k < N <= 524k: four XCDs share a slab) pay only under the blocked matvec -- measured in round 3
+    // against the general path: 300k x 768 k 32 25.96 -> 22.33 ms per settle, 400k x 512 k 32 22.70 -> 19.10, 300k x 768 k
+    // 64 43.1 -> 36.3, 500k x 384 k 16 a tie; the plain slab apply at two groups loses (config 5's shape: 57.1 vs 56.4 ms)
+    // and one group loses either way (700k x 384: 22.8 -> 24.5, config 4: 32.3 -> 34.4)
+    if (xg < 4 && xg != xs_groups(ncols) && blocks(false) == 0) return 0;
+    return nb;
+  };
+
+  ApplyPlan p;
+  p.deep = in.reordered && in.spmm_deep;
+  p.xs = xs_workgroups();
+  if (p.xs) {
+    // workgroups per XCD: 3 per CU when the operand is row-major (2: 1.37, 4: 1.15 ms vs 1.11), 4 per CU when it is
+    // slab-major (3: 1.09, 4: 1.05 ms)
+    p.xs_pmajor = in.xs_nb > 0 ? p.xs : std::min(in.grid / 8, 128);
+    p.xs_groups = groups(ncols);
+    p.slab = ncols;
+    p.launches = 1;
+  } else {
+    // Column slabs, so the gathered operand slab (N x slab x 4 B) stays resident in the 256 MB Infinity Cache while its
+    // rows are re-read ~deg times.  A lattice stored in a local row order gathers from its XCD's L2 whatever the slab: 256
+    // columns (one 1 KB row piece per wave, eight of them in flight: k_spmm's UDEEP variant) ran fastest on 1000 clusters x
+    // 100 rows at N = 100k, D = 768 (0.69 ms per apply at 64 columns, 0.45 at 128, 0.41 at 256 and 512, 0.44 at 768).
+    // Otherwise the slab stays around 50 MB, so it and the streams beside it stay inside 256 MB.
+    const double budget = 56.0 * 1024 * 1024;
+    if (p.deep && ncols > 256) {
+      p.slab = 256;
+    } else if ((double)N * ncols * 4.0 <= 2.0 * budget) {
+      p.slab = std::min(ncols, kMaxSlabCols);
+    } else {
+      p.slab = 64;
+      for (int32_t w : {128, 256, 384, 512, 768, 1024, 2048})
+        if ((double)N * w * 4.0 <= budget) p.slab = w;
+    }
+    p.launches = (ncols + p.slab - 1) / std::max(1, p.slab);
+  }
+  // slab-major search direction: P is private to the solve (N x ld floats either way) and whole 32-column slabs fit its pitch
+  p.pblk = p.xs > 0 && (in.sld & 31) == 0 && (in.sc0 & 31) == 0 && in.sld == in.ld;
+  // the blocked matvec: only over the handle's window (its block-major graph copy and column sums are laid out for that)
+  if (p.pblk && in.sc0 == in.c0 && in.sc1 == in.c1) p.src_blocks = blocks(in.with_path);
+  if (p.src_blocks > 0) {
+    p.shape = shape_for(p.xs_groups);
+    p.geom = geometry(p.xs_groups, p.shape);
+  }
+  return p;
 }
 
 // ---- where the x update of a CG iteration happens (run_cg in osc_api.hip) ---------------------------------------------

@@ -16,15 +16,10 @@ bool env_num(const char* name, int& out) {
 void read_env_solver(L& h) {
   auto num = env_num;
   int v = 0;
-  if (num("OSC_SPMM_SLAB", v)) h.spmm_slab = v < 0 ? -1 : (v / 4) * 4;
   if (num("OSC_SPMM_XS", v)) h.spmm_xs = v != 0 ? 1 : 0;
   if (num("OSC_XS_NB", v)) h.xs_nb = std::max(1, v);
-  if (num("OSC_XS_GROUPS", v)) h.xs_groups_cap = v >= 8 ? 8 : v >= 4 ? 4 : v >= 2 ? 2 : 1;
-  if (num("OSC_P_BLOCKED", v)) h.p_blocked = v != 0;
   if (num("OSC_SPMM_BLOCKED", v)) h.spmm_blocked = v;
-  if (num("OSC_BLK_STAMP", v)) h.blk_stamp = v != 0;
-  if (num("OSC_BLK_VARIANT", v)) h.blk_variant = (v >= 0 && v < blocked_variants()) ? v : -1;
-  if (num("OSC_BLK_WIDE_MIN_ROWS", v)) h.blk_wide_min_rows = std::max(0, v);
+  if (num("OSC_BLK_VARIANT", v)) h.blk_variant = (v >= 0 && v < kBlkShapeCount) ? v : -1;
   if (num("OSC_BLK_INIT", v)) {
     h.blk_init = v != 0;
     h.blk_init_fused = v == 1;
@@ -290,7 +285,7 @@ int osc_build_info(osc_handle h, int32_t* prefilter, int32_t* fallback_rows, int
 
 int osc_apply_info(osc_handle h, int32_t* src_blocks, int64_t* blocked_applies) {
   return guarded(h, [&](L& l) {
-    if (src_blocks) *src_blocks = l.blk_last;
+    if (src_blocks) *src_blocks = l.last_plan.src_blocks;
     if (blocked_applies) *blocked_applies = l.blk_applies;
   });
 }
@@ -346,12 +341,10 @@ int osc_get_row_order(osc_handle h, int32_t* perm) {
 
 int osc_spmm_plan(osc_handle h, int32_t* launches, int32_t* slab_cols, int32_t* xs_workgroups) {
   return guarded(h, [&](L& l) {
-    const int32_t ncols = l.c1 - l.c0;
-    const int nb = xs_plan(l, ncols, cg_grid(l));
-    const int32_t slab = nb ? 32 : auto_slab(l, ncols);
-    if (launches) *launches = nb ? 1 : (ncols + slab - 1) / slab;
-    if (slab_cols) *slab_cols = nb ? ncols : slab;
-    if (xs_workgroups) *xs_workgroups = nb;
+    const host::ApplyPlan p = apply_plan(l, l.c0, l.c1, l.ld, path_active(l));
+    if (launches) *launches = p.launches;
+    if (slab_cols) *slab_cols = p.slab;
+    if (xs_workgroups) *xs_workgroups = p.xs;
   });
 }
 
@@ -873,13 +866,14 @@ int osc_ustar_cosine_to(osc_handle h, const float* psi, float* out) {
 static double quad_form_of_difference(L& l, const float* A, const float* B) {
   ensure_cg_scratch(l, 1);
   const int grid = cg_grid(l);
+  const host::ApplyPlan plan = apply_plan(l, l.c0, l.c1, l.ld, path_active(l));
   // Large lattices on one process: the blocked matvec with its column sums of x . (M x) on the difference, which is formed on
   // its way into the slab-major operand (P; AP takes the product nobody reads): 0.76 instead of 1.23 ms at config 3, and
   // since round 6 without the row-major copy of the difference (one array pass of three less in front of the matvec).  Same
   // terms per row; a row's sum runs block by block instead of in list order (the matvec's 3e-8 relative on the state, far
   // inside the 1e-4 of the receipt's energies).  (A and B are never the solver's scratch arrays: U / U* / dynamics snapshots.)
   if (!row_mode(l) && l.comm == nullptr) {
-    if (const int rows = blocked_quad_form(l, ustar_op(l), A, l.P.p, l.AP.p, path_active(l), B)) {
+    if (const int rows = blocked_quad_form(l, plan, ustar_op(l), A, l.P.p, l.AP.p, path_active(l), B)) {
       launch_reduce_sum(l.part0.p, rows, l.ld, l.c0, l.c1, l.colsum.p, l.stream);
       std::vector<double> cs((size_t)l.ld, 0.0);
       HIP_CHECK(hipMemcpyAsync(cs.data() + l.c0, l.colsum.p + l.c0, (size_t)(l.c1 - l.c0) * 8, hipMemcpyDeviceToHost, l.stream));
@@ -909,12 +903,12 @@ static double quad_form_of_difference(L& l, const float* A, const float* B) {
       sa.row0 = shards[si].r0;
       sa.N = shards[si].r1;
       sa.part = l.part0.p + si * grid * l.ld;
-      spmm_slabbed(l, SPMM_DOT, sa, grid);
+      spmm_slabbed(l, plan, SPMM_DOT, sa, grid);
     }
   } else {
     sa.part = l.part0.p;
     sa.N = l.N;
-    spmm_slabbed(l, SPMM_DOT, sa, grid);
+    spmm_slabbed(l, plan, SPMM_DOT, sa, grid);
   }
   launch_reduce_sum(l.part0.p, nb, l.ld, l.c0, l.c1, l.colsum.p, l.stream);
   std::vector<double> cs((size_t)l.ld, 0.0);
@@ -1274,10 +1268,6 @@ int osc_profile_reset(osc_handle h) {
       l.prof_count[i] = 0;
       l.prof_ms[i] = 0.0;
     }
-    if (l.blk_stamps.n) {
-      HIP_CHECK(hipMemsetAsync(l.blk_stamps.p, 0, l.blk_stamps.n * 8, l.stream));
-      l.blk_stamp_launches = 0;
-    }
   });
 }
 int osc_profile_get(osc_handle h, int32_t which, int64_t* launches, double* total_ms) {
@@ -1293,32 +1283,11 @@ int osc_profile_get(osc_handle h, int32_t which, int64_t* launches, double* tota
       return;
     }
     if (which == 14) {  // the kernel shape of the last blocked matvec
-      if (launches) *launches = l.blk_shape_last;
+      if (launches) *launches = l.last_plan.shape;
       if (total_ms) *total_ms = 0.0;
       return;
     }
-    if (which >= 8 && which <= 13) {
-      // cycle stamps of the blocked matvec (OSC_BLK_STAMP=1): mean over the waves of a role of the shader cycles summed
-      // over the stamped launches.  8-11: gathering waves' lifetime / gather rounds / barrier / epilogue; 12-13: the list
-      // waves' fetch / barrier.  *launches = stamped launches (speculative, gated-off ones included: they add ~nothing).
-      prof_drain(l);
-      sync(l);
-      const int wpg = blocked_gather_waves(l.blk_shape_last) + 1;
-      std::vector<unsigned long long> w(l.blk_stamps.n);
-      if (!w.empty()) HIP_CHECK(hipMemcpy(w.data(), l.blk_stamps.p, w.size() * 8, hipMemcpyDeviceToHost));
-      double sum = 0.0;
-      int64_t cnt = 0;
-      for (size_t i = 0; i + 3 < w.size(); i += 4) {
-        const bool list_wave = (int)((i / 4) % (size_t)wpg) == wpg - 1;
-        if (w[i] == 0 || list_wave != (which >= 12)) continue;  // (workgroups that took no part have no stamps)
-        sum += (double)w[i + (which >= 12 ? which - 11 : which - 8)];
-        cnt += 1;
-      }
-      if (launches) *launches = l.blk_stamp_launches;
-      if (total_ms) *total_ms = cnt ? sum / (double)cnt : 0.0;
-      return;
-    }
-    if (which < 0 || which > 4) throw Invalid("osc_profile_get: which must be 0..4 (or 8..14: blocked matvec diagnostics)");
+    if (which < 0 || which > 4) throw Invalid("osc_profile_get: which must be 0..4 or 14..16");
     prof_drain(l);
     if (launches) *launches = l.prof_count[which];
     if (total_ms) *total_ms = l.prof_ms[which];

@@ -110,16 +110,9 @@ struct osc_lattice {
   int grid_cap = 1024;
   DevBuf<float> vec_q, vec_n;  // query / per-row result scratch of the cosine calls
   int32_t dcols = 0;      // D rounded up to 4: the columns the kernels work on (ld >= dcols is the row pitch)
-  int32_t spmm_slab = 0;  // 0 = whole window per launch
+  // the operator-apply plan's forcing switches (host_logic.hpp: plan_apply)
   int spmm_xs = -1;        // XCD-affine narrow slabs: -1 auto, 0 off, 1 on (OSC_SPMM_XS)
-  bool p_blocked = true;   // slab-major search direction in xs mode (OSC_P_BLOCKED=0 keeps it row-major)
   int xs_nb = 0;           // workgroups per XCD in that mode; 0 = automatic (OSC_XS_NB)
-  int xs_groups_cap = 8;   // upper bound on the slab groups (= slabs in flight) of that mode (OSC_XS_GROUPS)
-  int xs_min_cols = 32;    // narrowest column window the mode is used for (96 until round 3 -- with the
-                           // blocked matvec under it, one- and two-slab windows win too: 100k x 64 k 16 0.505 -> 0.425 ms per
-                           // settle, 100k x 32 0.352 -> 0.309, 200k x 64 k 32 1.43 -> 0.97, 60k x 64 k 32 0.438 -> 0.387)
-  int xs_min_rows = 6144, xs_min_rows_narrow = 0;  // smallest lattice the mode is used for: windows of >= 256 columns / narrower ones (0: by width, xs_plan)
-  int xs_groups_min = 2;   // fewest slab groups the mode is kept for when the natural count had to be reduced
   DevBuf<float> part0, part1, alpha, beta;
   DevBuf<double> rz, colsum;
   DevBuf<uint32_t> res_bits;  // residual slots of the row-sharded solve
@@ -162,18 +155,10 @@ struct osc_lattice {
   // block-major copy of the graph for the source-blocked CG matvec (k_spmm_blocked), built on first use per graph
   DevBuf<int2> blk_slots, blk_rest, blk_over;
   int blk_nb = 0;          // blocks of the copy held (0 = none / stale)
-  int spmm_blocked = -1;   // -1 by lattice size, 0 off, > 0 = that many source blocks (OSC_SPMM_BLOCKED)
-  double blk_mb = 2.0;     // smallest slab (N x 128 B, MiB) the blocked apply is chosen for
-  double blk_edges = 0.0;  // edges of a row per source block the block count aims at; 0 = by lattice size: 3.3 / 2.5
-  mutable int blk_resident[8] = {-1, -1, -1, -1, -1, -1, -1, -1};  // workgroups per XCD each shape of the blocked apply gets resident (queried once)
-  int blk_variant = -1;    // kernel shape of the blocked matvec (cg_kernels.hip: kBlkShapes); -1 = by geometry (blocked_shape_for), OSC_BLK_VARIANT forces one
-  int blk_shape_last = 0;  // the shape the last general-path solve's blocked matvec ran with
-  int blk_wide_min_rows = 0;  // smallest lattice the wide shapes are chosen for (OSC_BLK_WIDE_MIN_ROWS; 0 = default)
-  bool blk_stamp = false;  // OSC_BLK_STAMP=1: while profiling is on, the AP applies run the cycle-stamping instantiation
-  DevBuf<unsigned long long> blk_stamps;  // [grid][waves per workgroup][4] (osc_profile_get slots 8-13)
-  int64_t blk_stamp_launches = 0;
-  int blk_stamp_grid = 0;
-  int blk_last = 0;        // source blocks the last general-path solve's matvec used (0 = plain apply)
+  int spmm_blocked = -1;   // < 0 by lattice size, 0 off, > 0 = that many source blocks (OSC_SPMM_BLOCKED)
+  int blk_variant = -1;    // kernel shape of the blocked matvec (kBlkShapes); -1 = by geometry, OSC_BLK_VARIANT forces one
+  mutable int blk_resident[kBlkShapeCount] = {-1};  // workgroups per XCD each shape gets resident ([0] < 0: not queried yet)
+  host::ApplyPlan last_plan;  // the apply plan of the last general-path solve (osc_apply_info, osc_profile_get slot 14)
   double temporal_mb = 200.0;  // largest solve (5 arrays x N x window) whose update kernels use ordinary instead of nontemporal accesses
   bool spmm_deep = true;   // re-ordered lattices: the operator apply with 8 gathers in flight per row (OSC_SPMM_DEEP=0: the usual 2)
   bool blk_init = true;    // the initial residual goes through the blocked matvec as well (OSC_BLK_INIT=0: plain INIT apply)
@@ -310,8 +295,8 @@ uint32_t* ctrl_segment(L& h, size_t words);
 void ensure_ctrl(L& h, size_t slots);
 void ensure_cg_scratch(L& h, int max_iters);
 int cg_grid(const L& h);
-int blocked_quad_form(L& h, const OpParams& op, const float* x_rows, float* scratch_slab, float* scratch_out, bool with_path,
-                      const float* x_sub = nullptr);  // x_sub: the form of x_rows - x_sub
+int blocked_quad_form(L& h, const host::ApplyPlan& plan, const OpParams& op, const float* x_rows, float* scratch_slab,
+                      float* scratch_out, bool with_path, const float* x_sub = nullptr);  // x_sub: the form of x_rows - x_sub
 GraphView graph_view(L& h, bool with_path);
 void graph_counts(L& h);
 void alloc_ell(L& h, int32_t width);
@@ -327,15 +312,9 @@ void build_graph(L& h, const float* host_Y = nullptr);
 bool path_active(const L& h);
 OpParams settle_op(const L& h, float dt, int precond);
 OpParams ustar_op(const L& h);
-int32_t auto_slab(const L& h, int32_t ncols);
-int xs_groups(int32_t ncols, int cap = 8);
-int xs_groups_for(const L& h, int32_t ncols);
-int xs_plan(const L& h, int32_t ncols, int grid);
-int blocked_resident(const L& h, int shape);
-int blocked_shape_for(const L& h, int xg, int grid);
-int blocked_plan(const L& h, bool with_path);
+host::ApplyPlan apply_plan(const L& h, int32_t c0, int32_t c1, int32_t ld, bool with_path);
 BlockedView blocked_view(L& h, int nb);
-void spmm_slabbed(L& h, int mode, SpmmArgs sa, int grid, int iter = 0);
+void spmm_slabbed(L& h, const host::ApplyPlan& plan, int mode, SpmmArgs sa, int grid, int iter = 0);
 bool run_cg_small(L& h, const OpParams& op, const CgBuffers& b, bool with_path, int max_iters, float tol,
                   CgResult& out);
 CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, int max_iters, float tol);

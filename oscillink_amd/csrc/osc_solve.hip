@@ -35,134 +35,35 @@ OpParams ustar_op(const L& h) {
   return o;
 }
 
-// Operator apply, optionally split into column slabs so the gathered operand slab (N x slab x 4 B) stays resident
-// in the 256 MB Infinity Cache while its rows are re-read ~deg times (MI355X_MICROARCH.md, Infinity Cache rule).
-int32_t auto_slab(const L& h, int32_t ncols) {
-  constexpr int32_t kMaxWindow = 2048;  // widest column window one launch covers (8 x 256 floats per row)
-  if (h.spmm_slab > 0) return std::min(h.spmm_slab, kMaxWindow);
-  if (h.spmm_slab < 0) return std::min(ncols, kMaxWindow);  // OSC_SPMM_SLAB=-1: split only when it must
-  // a lattice stored in a local row order gathers from its XCD's L2 whatever the slab: 256 columns (one 1 KB row piece per
-  // wave, eight of them in flight: k_spmm's UDEEP variant) ran fastest on 1000 clusters x 100 rows at N = 100k, D = 768
-  // (0.69 ms per apply at 64 columns, 0.45 at 128, 0.41 at 256 and 512, 0.44 at 768)
-  if (h.reordered && h.spmm_deep && ncols > 256) return 256;
-  // keep the gathered slab (N x slab x 4 B) around 50 MB so it and the streams beside it stay inside 256 MB
-  const double budget = 56.0 * 1024 * 1024;
-  if ((double)h.N * ncols * 4.0 <= 2.0 * budget) return std::min(ncols, kMaxWindow);
-  int32_t slab = 64;
-  for (int32_t w : {128, 256, 384, 512, 768, 1024, 2048})
-    if ((double)h.N * w * 4.0 <= budget) slab = w;
-  return slab;
-}
-
-// XCD-affine 32-column slabs (SpmmArgs::xs): one launch covers the window; returns the workgroups per XCD to use, 0 = no.
-// Pays when the gathered operand is far larger than an XCD's L2 and the graph has no row locality to exploit: each
-// XCD then keeps 4 MB / (N x 128 B) of ITS slab in L2 (31 % at N = 100k) instead of 4 MB / (N x 512 B) of a slab all
-// eight share.  With fewer than 8 slabs (or a count that is not a multiple of 8) the XCDs pair up: gcd(8, slabs) slab
-// groups, the XCDs of a group split the rows.  Needs 128-byte-aligned rows and the slabs in flight (groups x N x 128 B)
-// inside the Infinity Cache: measured 1.11 vs 1.26 ms per apply at N = 100k, D = 768; no gain at N = 200k, D = 1536 with
-// 8 slabs (205 MB) in flight, 4 % with 4 (xs_groups_for); 36 % slower at N = 1M, D = 384.
-// (the counts themselves: host_logic.hpp)
-int xs_groups(int32_t ncols, int cap) { return host::xs_groups(ncols, cap); }
-int xs_groups_for(const L& h, int32_t ncols) { return host::xs_groups_for(h.N, ncols, h.xs_groups_cap, h.xs_groups_min); }
-int blocked_plan(const L& h, bool with_path);
-int xs_plan(const L& h, int32_t ncols, int grid) {
-  if (grid < 8 || (grid & 7) != 0) return 0;
-  const int nb = std::max(1, std::min(grid / 8, h.xs_nb > 0 ? h.xs_nb : 96));
-  if (h.spmm_xs == 0) return 0;
-  if (h.spmm_xs == 1) return nb;
-  if (h.spmm_slab != 0 || (h.ld & 31) != 0 || (h.c0 & 31) != 0) return 0;
-  // A lattice stored in BFS order gathers from its XCD's L2 on the general path already (docs/DESIGN_HISTORY.md section 3), so the slab
-  // mode is off for it -- except large narrow ones, where the source-blocked matvec on top of the local order wins
-  // (round 4, scripts/exp/r04_bfs_blocked_sweep.py, clustered anchors, per settle: 300k x 128 k 16 2.17 -> 1.95 ms, 300k x
-  // 256 k 32 6.15 -> 5.0-5.3, 400k x 256 6.35 -> 5.35, 600k x 128 4.79 -> 3.92, 1M x 128 8.15 -> 6.72; at 384 columns a tie
-  // (400k 8.06 / 7.98, 1M 20.4 / 20.7), at 200k rows a loss (128 columns: 1.25 -> 1.32)).
-  if (h.reordered) return (h.N >= 300000 && ncols <= 256 && blocked_plan(h, false) > 0) ? nb : 0;
-  // from N = 32768 on, and from 6144 (16384 until round 3) for windows of >= 256 columns (N = 20000, D = 256: apply 43.5 -> 31.4 us)
-  // narrower windows: 32768 rows, but 12288 where the window is whole groups of four slabs (every XCD pair a slab of its
-  // own) and 24576 for other windows of >= 128 columns (scripts/exp/xs_narrow_sweep.py, k = 16, per settle: 20000 x 128
-  // 246 -> 223 us, 32000 x 128 347 -> 301, 12000 x 128 192 -> 186, 32000 x 192 484 -> 438, 24000 x 192 393 -> 378, 20000 x
-  // 192 345 -> 360; 64 and 32 columns: a tie or a loss up to 32000 rows)
-  const int narrow_rows = h.xs_min_rows_narrow > 0 ? h.xs_min_rows_narrow : ncols < 128 ? 32768 : (ncols % 128) == 0 ? 12288 : 24576;
-  if (h.N < h.xs_min_rows || (h.N < narrow_rows && ncols < 256) || ncols < h.xs_min_cols) return 0;
-  // below 16384 rows (round 3: the floor was 16384) a 32-column slab is at most 2 MB -- it sits in its XCD's L2 whole,
-  // where the general path spreads N x window over all eight L2s -- which pays once a row has enough gathers: per settle
-  // 6500 x 768 k 32 0.520 -> 0.437 ms, 9000 x 1024 k 32 0.925 -> 0.697, 8192 x 1536 k 32 1.32 -> 0.91, 14000 x 256 k 32 0.406
-  // -> 0.329, 9000 x 256 k 16 0.236 -> 0.219, 7000 x 512 k 16 0.299 -> 0.280; at k = 8 it loses (14000 x 320: 0.307 -> 0.329)
-  if (h.N < 16384 && (double)h.nnz < 10.0 * (double)h.N) return 0;
-  const int xg = xs_groups_for(h, ncols);
-  if (xg == 0) return 0;
-  // beyond the Infinity-Cache budget only the (wide) blocked matvec keeps the mode: host_logic.hpp, xs_groups_for
-  if (h.N > host::kXsBudgetRows && blocked_plan(h, false) == 0) return 0;
-  // Two slab groups (262k < N <= 524k: four XCDs share a slab) pay only under the blocked matvec -- measured in round 3
-  // against the general path: 300k x 768 k 32 25.96 -> 22.33 ms per settle, 400k x 512 k 32 22.70 -> 19.10, 300k x 768 k 64
-  // 43.1 -> 36.3, 500k x 384 k 16 a tie; the plain slab apply at two groups loses (config 5's shape: 57.1 vs 56.4 ms) and one
-  // group loses either way (700k x 384: 22.8 -> 24.5, config 4: 32.3 -> 34.4)
-  if (xg < 4 && xg != xs_groups(ncols, h.xs_groups_cap) && blocked_plan(h, false) == 0) return 0;
-  return nb;
-}
-
-// workgroups per XCD a shape of the blocked apply gets resident
-int blocked_resident(const L& h, int shape) {
-  if (h.blk_resident[shape] < 0) {
+// The apply plan of a solve over columns [c0, c1) of N x ld buffers: host_logic.hpp, plan_apply, decides; this fills its
+// inputs from the handle.  Row-sharded solves plan for the whole lattice.
+host::ApplyPlan apply_plan(const L& h, int32_t c0, int32_t c1, int32_t ld, bool with_path) {
+  if (h.blk_resident[0] < 0) {  // workgroups per XCD each shape of the blocked matvec gets resident (queried once)
     hipDeviceProp_t prop;
     HIP_CHECK(hipGetDeviceProperties(&prop, h.device));
-    h.blk_resident[shape] = blocked_resident_per_cu(shape) * std::max(1, prop.multiProcessorCount / 8);
+    for (int v = 0; v < kBlkShapeCount; ++v) h.blk_resident[v] = blocked_resident_per_cu(v) * std::max(1, prop.multiProcessorCount / 8);
   }
-  return h.blk_resident[shape];
-}
-
-// Kernel shape of the blocked matvec for a window cut into xg slab groups (cg_kernels.hip: kBlkShapes).  The wide shapes
-// (one workgroup per CU, four gather rounds in flight, no tests in the rounds) carry their group count as a template
-// constant -- the smallest that holds the lattice's groups is used -- and are taken from 96 000 rows on, where they win
-// at every width measured except one slab per XCD below 150k rows; below 96k rows they are within +-2 % of shape 0 with
-// single wins and losses of 5-7 % either way, so shape 0 stays there.
-int blocked_shape_for(const L& h, int xg, int grid) {
-  if (h.blk_variant >= 0) return h.blk_variant;
-  const int wide_last = blocked_variants() - 1;
-  const host::BlockedGeom g = host::blocked_geometry(h.N, xg, grid, blocked_resident(h, wide_last), blocked_groups_max(wide_last),
-                                                     blocked_gather_waves(wide_last));
-  // Measured against shape 0 (profiles/r05_blk_shape_sweep.txt, per AP launch, exact-fit group counts): 20k x 768 -7.5 %, 20k x
-  // 128 k 16 +5.8 %, 30k-80k x 768 -0.8 ... +2.7 %, 100k x 768 -4.6 %, 100k x 384 k 16 -4.8 %, 100k x 1024 k 48 -4.0 %, 100k x
-  // 96 (rank 0 of 8's window of config 3) -10.9 %, 100k x 192 -2.7 %, 160k x 768 -10.9 %, 200k x 768 -9.6 %, 200k x 64 -13.0 %,
-  // 260k x 512 -15.0 %, 400k x 384 k 16 -7.1 %; one slab per XCD: 100k x 64 k 16 +5.0 %, 100k x 128 k 16 +1.4 %, 130k x 256
-  // +1.4 ... +3.6 % -- there the wide shapes wait for N = 150k.
-  const int64_t min_rows = h.blk_wide_min_rows > 0 ? h.blk_wide_min_rows : 96000;
-  const int slabs_per_group = ((h.c1 - h.c0 + 31) / 32 + xg - 1) / std::max(1, xg);
-  if (h.N < min_rows || (h.blk_wide_min_rows <= 0 && slabs_per_group < 2 && h.N < 150000)) return 0;
-  for (int v = 1; v <= wide_last; ++v)
-    if (g.groups <= blocked_groups_max(v)) return v;
-  return 0;
-}
-
-// Source blocks of the blocked CG matvec (k_apply_blocked): 0 = use the plain apply.
-int blocked_plan(const L& h, bool with_path) {
-  if (h.spmm_blocked == 0 || (with_path && (h.prows < 1 || h.prows > OSC_CHAIN_FIX_MAX_ROWS)) || (int64_t)h.N * h.width >= ((int64_t)1 << 28) || h.N >= ((int64_t)1 << 24) ||
-      (int64_t)h.N * h.ld * 4 >= ((int64_t)1 << 32))
-    return 0;
-  if (h.spmm_blocked > 0) return std::min(h.spmm_blocked, OSC_MAX_SRC_BLOCKS);
-  // block count from the mean degree and the lattice size (host_logic.hpp: blocked_edges_per_block)
-  // overrides the edges a row should have per block
-  const double mean_deg = h.N > 0 ? (double)h.nnz / (double)h.N : 0.0;
-  // (a lattice in BFS order: 2.2 edges per block -- x4 of x2 / x3 / x4 / x6 / x8 at mean degree 8.3, x8 of x6 / x8 / x12 at 20.2)
-  const int ncols = h.c1 - h.c0, xg0 = xs_groups_for(h, ncols);
-  const bool wide = blocked_shape_for(h, xg0 > 0 ? xg0 : xs_groups(ncols, h.xs_groups_cap), cg_grid(h)) > 0;
-  const double e = h.blk_edges > 0.0 ? h.blk_edges
-                   : h.reordered     ? 2.2
-                   : wide            ? host::blocked_edges_per_block_wide(h.N)
-                                     : host::blocked_edges_per_block(h.N);
-  const int nb = host::blocked_block_count(mean_deg, e, OSC_MAX_SRC_BLOCKS);
-  if (h.spmm_blocked == -2) return nb;  // "whenever possible" (experiments)
-  // ... and wherever the XCD-affine slab mode itself runs from a 2 MiB slab (N = 16384) on.  Measured against the plain
-  // apply (k = 32 unless noted): N = 20k x 768 -7 %, 35k x 768 -26 %, 40k x 256 (k 8) -25 %, 50k x 512 -30 %, 65k x 256
-  // (k 16) -30 %, 60k x 1024 (k 24) -29 %, 80k x 768 -39 %, 100k x 768 -39 % (k 16, D 384: -33 %; k 48: -47 %; k 64:
-  // -45 %), 100k x 128 (k 16) -35 %, 110k x 768 -40 %, 130k x 256 -43 %; round 3: 160k x 768 -31 %, 200k x 768 -37 %
-  // (k 64: -46 %), 260k x 768 -22 % (k 64: -37 %).
-  const double slab = (double)h.N * 128.0;
-  if (slab < h.blk_mb * 1024.0 * 1024.0) return 0;
-  // narrow windows of small lattices: the plain slab apply is ahead (round 4 shape sweep: 16384 x 128 k 16 0.205 vs 0.221 ms per
-  // settle; from 20000 rows on a tie or a win)
-  if (h.N < 20000 && h.c1 - h.c0 <= 128) return 0;
-  return nb;
+  host::ApplyInputs in;
+  in.N = h.N;
+  in.nnz = h.nnz;
+  in.width = h.width;
+  in.ld = h.ld;
+  in.c0 = h.c0;
+  in.c1 = h.c1;
+  in.reordered = h.reordered;
+  in.prows = h.prows;
+  in.sc0 = c0;
+  in.sc1 = c1;
+  in.sld = ld;
+  in.with_path = with_path;
+  in.grid = cg_grid(h);
+  std::copy(h.blk_resident, h.blk_resident + kBlkShapeCount, in.resident);
+  in.spmm_xs = h.spmm_xs;
+  in.xs_nb = h.xs_nb;
+  in.spmm_blocked = h.spmm_blocked;
+  in.blk_variant = h.blk_variant;
+  in.spmm_deep = h.spmm_deep;
+  return host::plan_apply(in);
 }
 
 BlockedView blocked_view(L& h, int nb) {
@@ -177,8 +78,8 @@ BlockedView blocked_view(L& h, int nb) {
     // the apply's list wave copies whole row groups: up to 8 x gather-waves slot rows past the lattice's end
     // (host_logic.hpp: blocked_list_extent <= N - 1 + 8 x gather waves, swept in tests/host_logic)
     constexpr size_t kPadRows = 8192;
-    for (int v = 0; v < blocked_variants(); ++v)
-      if ((size_t)blocked_gather_waves(v) * 8 > kPadRows) throw std::runtime_error("blocked graph copy: padding too small");
+    for (const BlkShape& sh : kBlkShapes)
+      if ((size_t)sh.cw * 8 > kPadRows) throw std::runtime_error("blocked graph copy: padding too small");
     const size_t nslots = (size_t)nb * h.N * OSC_BLK_SLOTS, npad = kPadRows * OSC_BLK_SLOTS;
     h.blk_slots.alloc(nslots + npad);
     HIP_CHECK(hipMemsetAsync(h.blk_slots.p + nslots, 0, npad * sizeof(int2), h.stream));  // {row 0, 0.0f}
@@ -198,23 +99,20 @@ BlockedView blocked_view(L& h, int nb) {
   return v;
 }
 
-void spmm_slabbed(L& h, int mode, SpmmArgs sa, int grid, int iter) {
+// the plain operator apply over sa's column window, which is the plan's
+void spmm_slabbed(L& h, const host::ApplyPlan& plan, int mode, SpmmArgs sa, int grid, int iter) {
   const int32_t c0 = sa.c0, c1 = sa.c1;
-  sa.deep = (h.reordered && h.spmm_deep) ? 1 : 0;
+  sa.deep = plan.deep ? 1 : 0;
   ProfScope ps(h, mode == SPMM_INIT ? 4 : 0, iter);  // slot 0: AP applies (the CG matvec); slot 4: the INIT apply
-  if (const int nb = xs_plan(h, c1 - c0, grid)) {
-    // workgroups per XCD: 3 per CU when the operand is row-major (2: 1.37, 4: 1.15 ms vs 1.11), 4 per CU when it is
-    // slab-major (3: 1.09, 4: 1.05 ms)
-    sa.xs = (h.xs_nb <= 0 && sa.xblk != 0) ? std::min(grid / 8, 128) : nb;
-    const int xg = xs_groups_for(h, c1 - c0);
-    sa.xs_groups = xg > 0 ? xg : xs_groups(c1 - c0, h.xs_groups_cap);  // forced mode: natural count
+  if (plan.xs) {
+    sa.xs = sa.xblk != 0 ? plan.xs_pmajor : plan.xs;
+    sa.xs_groups = plan.xs_groups;
     launch_spmm(mode, sa, grid, h.stream);
     return;
   }
-  const int32_t slab = auto_slab(h, c1 - c0);
-  for (int32_t s0 = c0; s0 < c1; s0 += slab) {
+  for (int32_t s0 = c0; s0 < c1; s0 += plan.slab) {
     sa.c0 = s0;
-    sa.c1 = std::min(c1, s0 + slab);
+    sa.c1 = std::min(c1, s0 + plan.slab);
     launch_spmm(mode, sa, grid, h.stream);
   }
 }
@@ -329,12 +227,11 @@ CgResult run_cg_rows(L& h, const OpParams& op, const CgBuffers& b, bool with_pat
 bool row_mode(const L& h);
 
 // Arguments of the source-blocked matvec (k_apply_blocked) for the handle's whole column window: X = slab-major input, OUT =
-// row-major output, column sums of X . OUT into h.part0 (grid rows, + the chain fix-up's chunks behind them).  ba.nb stays
-// 0 where the plan says the plain apply serves this lattice (blocked_plan).
-void blocked_setup(L& h, const OpParams& op, const float* X, float* OUT, const float* B, int32_t ld, bool with_path, int grid, BlkArgs& ba,
-                   ChainFixArgs& cf, int& blk_shape) {
-  const int nb = blocked_plan(h, with_path);
-  if (nb == 0) return;
+// row-major output, column sums of X . OUT into h.part0 (grid rows, + the chain fix-up's chunks behind them).  For a plan
+// with source blocks.
+void blocked_setup(L& h, const host::ApplyPlan& plan, const OpParams& op, const float* X, float* OUT, const float* B, int32_t ld,
+                   bool with_path, int grid, BlkArgs& ba, ChainFixArgs& cf) {
+  const int nb = plan.src_blocks;
   const BlockedView bv = blocked_view(h, nb);
   ba.X = X;
   ba.OUT = OUT;
@@ -352,14 +249,10 @@ void blocked_setup(L& h, const OpParams& op, const float* X, float* OUT, const f
   ba.c1 = h.c1;
   ba.nb = nb;
   // workgroups per XCD (what is resident at once), slab groups, row groups per wave, destination slices
-  const int xg0 = xs_groups_for(h, h.c1 - h.c0), xg = xg0 > 0 ? xg0 : xs_groups(h.c1 - h.c0, h.xs_groups_cap);
-  blk_shape = blocked_shape_for(h, xg, grid);
-  const host::BlockedGeom geom = host::blocked_geometry(h.N, xg, grid, blocked_resident(h, blk_shape), blocked_groups_max(blk_shape),
-                                                       blocked_gather_waves(blk_shape));
-  ba.xs = geom.xs;
-  ba.xs_groups = geom.xs_groups;
-  ba.slices = geom.slices;
-  ba.groups = geom.groups;
+  ba.xs = plan.geom.xs;
+  ba.xs_groups = plan.geom.xs_groups;
+  ba.slices = plan.geom.slices;
+  ba.groups = plan.geom.groups;
   if (with_path && op.cP != 0.f) {  // the chain prior's few rows: a small launch behind every blocked apply
     cf.X = X;
     cf.OUT = OUT;
@@ -383,18 +276,17 @@ void blocked_setup(L& h, const OpParams& op, const float* X, float* OUT, const f
 // x . (op x) summed per column into h.part0 for a ROW-major x (N x ld, the handle's whole window) through the blocked matvec:
 // x -> slab-major (scratch_slab), one launch (+ the chain fix-up), op x -> scratch_out.  Returns the rows of partial sums
 // h.part0 holds, 0 where the blocked matvec does not serve this lattice (the caller takes the plain apply's DOT form).
-int blocked_quad_form(L& h, const OpParams& op, const float* x_rows, float* scratch_slab, float* scratch_out, bool with_path,
-                      const float* x_sub) {
+// plan: the handle's window at its pitch.
+int blocked_quad_form(L& h, const host::ApplyPlan& plan, const OpParams& op, const float* x_rows, float* scratch_slab,
+                      float* scratch_out, bool with_path, const float* x_sub) {
+  if (plan.src_blocks == 0) return 0;
   const int grid = cg_grid(h);
-  if (!(h.p_blocked && xs_plan(h, h.c1 - h.c0, grid) > 0 && (h.ld & 31) == 0 && (h.c0 & 31) == 0)) return 0;
   BlkArgs ba{};
   ChainFixArgs cf{};
-  int blk_shape = 0;
-  blocked_setup(h, op, scratch_slab, scratch_out, h.B.p, h.ld, with_path, grid, ba, cf, blk_shape);
-  if (ba.nb == 0) return 0;
+  blocked_setup(h, plan, op, scratch_slab, scratch_out, h.B.p, h.ld, with_path, grid, ba, cf);
   launch_rows_to_slab(x_rows, scratch_slab, h.N, h.ld, h.c0, h.c1, grid, h.stream, x_sub);
   ba.gate = nullptr;
-  launch_apply_blocked(ba, grid, h.stream, nullptr, blk_shape);
+  launch_apply_blocked(ba, grid, h.stream, nullptr, plan.shape);
   h.blk_applies += 1;
   if (cf.chunks > 0) {
     cf.gate = nullptr;
@@ -410,6 +302,7 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
     if (run_cg_small(h, op, b, with_path, max_iters, tol, one)) return one;
   }
   const int grid = cg_grid(h);
+  const host::ApplyPlan plan = apply_plan(h, b.c0, b.c1, b.ld, with_path);
   const size_t nslots = (size_t)max_iters + 2;
   ensure_ctrl(h, nslots);
   uint32_t* const res_slots = ctrl_segment(h, 2 * nslots);  // zeroed: [residual per iteration | arrival counter per iteration]
@@ -466,15 +359,12 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
   sa.Y = b.rhsY;
   sa.gate = nullptr;
   // slab-major search direction: only where the XCD-affine slab apply runs (its gathers then read contiguous slabs)
-  // and P is private to this solve (N x ld floats either way; needs whole 32-column slabs inside the pitch)
-  const bool pblk = h.p_blocked && xs_plan(h, b.c1 - b.c0, grid) > 0 && (b.ld & 31) == 0 && (b.c0 & 31) == 0 &&
-                    b.ld == h.ld;
+  const bool pblk = plan.pblk;
   sa.pblk = pblk ? h.N : 0;
   // source-blocked CG matvec (k_apply_blocked) where the slab an XCD gathers from is far larger than its L2
   BlkArgs ba{};
   ChainFixArgs cf{};
-  int blk_shape = 0;
-  if (pblk && b.c0 == h.c0 && b.c1 == h.c1) blocked_setup(h, op, b.P, b.AP, b.B, b.ld, with_path, grid, ba, cf, blk_shape);
+  if (plan.src_blocks > 0) blocked_setup(h, plan, op, b.P, b.AP, b.B, b.ld, with_path, grid, ba, cf);
 
   // (an inertia start hands over x0 IN the AP array, which the blocked matvec would overwrite with A x0 before
   // init_finish has read x0: such a solve keeps the gathering INIT kernel, which reads x0 completely first)
@@ -504,7 +394,7 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
     bi.md_const = op.precond ? op.md_const : 1.f;
     ba.gate = nullptr;
     ba.OUT = nullptr;
-    launch_apply_blocked(ba, grid, h.stream, &bi, blk_shape);
+    launch_apply_blocked(ba, grid, h.stream, &bi, plan.shape);
     if (cf.chunks > 0) {  // the chain prior's rows: their r, z and r . z still lack the chain term
       ChainFixArgs ci = cf;
       ci.gate = nullptr;
@@ -526,7 +416,7 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
     ProfScope ps(h, 4, 0);
     launch_rows_to_slab(b.x0, b.P, h.N, b.ld, b.c0, b.c1, grid, h.stream);
     ba.gate = nullptr;
-    launch_apply_blocked(ba, grid, h.stream, nullptr, blk_shape);
+    launch_apply_blocked(ba, grid, h.stream, nullptr, plan.shape);
     if (cf.chunks > 0) {
       cf.gate = nullptr;
       launch_chain_fix(cf, h.stream);
@@ -552,7 +442,7 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
       launch_init_finish(fa, grid, h.stream);
     }
   } else {
-    spmm_slabbed(h, SPMM_INIT, sa, grid);
+    spmm_slabbed(h, plan, SPMM_INIT, sa, grid);
   }
   launch_reduce_init(h.part0.p, init_part_rows, b.ld, b.c0, b.c1, h.rz.p, h.stream);
   UpdateArgs ua{};
@@ -576,8 +466,7 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
   sa.OUT = APbuf;
   sa.xblk = pblk ? h.N : 0;
   sa.pblk = 0;
-  h.blk_last = ba.nb;
-  h.blk_shape_last = ba.nb > 0 ? blk_shape : 0;
+  h.last_plan = plan;
   // Deferred x update: iteration it's x += alpha p is applied by iteration it + 1's p update, which reads p anyway (x, r,
   // p in / x, p out there, r, Ap in / r out in the x-r kernel: 8 array passes per iteration instead of 9), or by
   // finish_x behind an iteration that has no successor enqueued.  The iteration expected to be the last (the count of
@@ -616,19 +505,7 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
       ProfScope ps(h, 0, it);
       ba.gate = g.p;
       ba.gate_tol = tol;
-      unsigned long long* stamps = nullptr;
-      if (h.blk_stamp && h.prof_on) {  // diagnostic: per-wave cycle counters of where the launch's time goes
-        const size_t words = (size_t)grid * (size_t)(blocked_gather_waves(blk_shape) + 1) * 4;
-        if (h.blk_stamps.n != words || h.blk_stamp_grid != grid) {
-          h.blk_stamps.alloc(words);
-          HIP_CHECK(hipMemsetAsync(h.blk_stamps.p, 0, words * 8, h.stream));
-          h.blk_stamp_launches = 0;
-          h.blk_stamp_grid = grid;
-        }
-        stamps = h.blk_stamps.p;
-        h.blk_stamp_launches += 1;
-      }
-      launch_apply_blocked(ba, grid, h.stream, nullptr, blk_shape, stamps);
+      launch_apply_blocked(ba, grid, h.stream, nullptr, plan.shape);
       if (cf.chunks > 0) {
         cf.gate = g.p;
         cf.gate_tol = tol;
@@ -636,7 +513,7 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
       }
       h.blk_applies += 1;
     } else {
-      spmm_slabbed(h, SPMM_AP, sa, grid, it);
+      spmm_slabbed(h, plan, SPMM_AP, sa, grid, it);
     }
     launch_reduce_alpha(h.part0.p, grid + (ba.nb > 0 ? cf.chunks : 0), b.ld, b.c0, b.c1, h.rz.p, h.alpha.p, g, h.stream);
     {
@@ -879,6 +756,7 @@ CgResult run_cg_rows(L& h, const OpParams& op, const CgBuffers& b, bool with_pat
   const std::vector<RowShard> shards = row_shards(h);
   const int V = (int)shards.size();
   const int grid = cg_grid(h);
+  const host::ApplyPlan plan = apply_plan(h, b.c0, b.c1, b.ld, with_path);
   const size_t pn = (size_t)V * grid * b.ld;  // one block of partial rows per local shard
   if (h.part0.n < pn) h.part0.alloc(pn);
   if (h.part1.n < pn) h.part1.alloc(pn);
@@ -923,7 +801,7 @@ CgResult run_cg_rows(L& h, const OpParams& op, const CgBuffers& b, bool with_pat
       sa.row0 = shards[(size_t)s].r0;
       sa.N = shards[(size_t)s].r1;
       sa.part = h.part0.p + (size_t)s * grid * b.ld;
-      spmm_slabbed(h, mode, sa, grid, iter);
+      spmm_slabbed(h, plan, mode, sa, grid, iter);
     }
   };
   // r = b - A x0 ; z ; p ; rz

@@ -14,7 +14,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-PLAN_VARS = ("OSC_SPMM_XS", "OSC_SPMM_BLOCKED", "OSC_SMALL_PATH", "OSC_REORDER", "OSC_SPMM_DEEP", "OSC_SPMM_SLAB")
+PLAN_VARS = ("OSC_SPMM_XS", "OSC_SPMM_BLOCKED", "OSC_SMALL_PATH", "OSC_REORDER", "OSC_SPMM_DEEP")
 
 
 def anchors(N, D, kind, seed=0):

@@ -239,8 +239,10 @@ static void check_pack_csr(const Graph& g, std::mt19937_64& rng) {
   }
 }
 
+constexpr int kPadRows = 8192;  // osc_solve.hip, blocked_view: zeroed slot rows behind the last block of the graph copy
+
 static void check_blocked(int64_t N, std::mt19937_64& rng) {
-  constexpr int kGmax = 16, kWaves = 7, kPadRows = 8192;  // cg_kernels.hip: kBlkGroups, kBlkGatherWaves; blocked_view's padding
+  constexpr int kGmax = osc::kBlkGroups, kWaves = osc::kBlkGatherWaves;
   for (int xg : {1, 2, 4, 8})
     for (int resident : {32, 64, 96, 128})
       for (int grid : {8, 64, 512, 1024}) {
@@ -274,6 +276,165 @@ static void check_blk_place(const Graph& g) {
       CHECK(placed == want, "N %lld nb %d row %lld: edges lost or duplicated", (long long)g.N, nb, (long long)i);
       CHECK((int64_t)over.size() == std::max<int64_t>(0, (int64_t)g.deg[(size_t)i] - (int64_t)nb * SL), "overflow count");
     }
+  }
+}
+
+// ---- the operator-apply plan (plan_apply) ----------------------------------------------------------------------------
+// A handle of N rows with mean degree `deg`, pitch ld and column window [c0, c1), planning the solve over that window.
+static ApplyInputs apply_inputs(int64_t N, double deg, int32_t ld, int32_t c0, int32_t c1, bool reordered, int32_t prows, bool with_path) {
+  ApplyInputs in;
+  in.N = N;
+  in.nnz = (int64_t)(deg * (double)N);
+  in.width = (int32_t)(2.0 * deg) + 1;
+  in.ld = ld;
+  in.c0 = in.sc0 = c0;
+  in.c1 = in.sc1 = c1;
+  in.sld = ld;
+  in.reordered = reordered;
+  in.prows = prows;
+  in.with_path = with_path;
+  int64_t g = std::max<int64_t>(1, std::min<int64_t>((N + 3) / 4, 1024));  // osc_runtime.hip: cg_grid
+  in.grid = (int)(g >= 8 ? g & ~(int64_t)7 : g);
+  for (int v = 0; v < osc::kBlkShapeCount; ++v) in.resident[v] = v == 0 ? 64 : 32;  // MI355X: 256 CUs, 2 / 1 workgroups per CU
+  return in;
+}
+// blocked only under the xs mode with a slab-major search direction; a kernel shape whose group count holds the lattice;
+// the list wave's copies within the graph copy's padding; column slabs whose launches cover the window
+static void check_plan(const ApplyInputs& in, std::set<std::vector<int64_t>>& extents_seen) {
+  const ApplyPlan p = plan_apply(in);
+  const int32_t ncols = in.sc1 - in.sc0;
+  const long long N = (long long)in.N;
+  CHECK(p.src_blocks == 0 || (p.xs > 0 && p.pblk), "N %lld window %d..%d: blocked without the slab-major xs mode", N, in.sc0, in.sc1);
+  CHECK(!p.pblk || p.xs > 0, "N %lld: slab-major P outside the xs mode", N);
+  CHECK(p.slab >= 1 && p.launches >= 1 && (int64_t)p.launches * p.slab >= ncols && (int64_t)(p.launches - 1) * p.slab < ncols &&
+            (p.xs > 0 ? p.launches == 1 : p.slab <= kMaxSlabCols),
+        "N %lld window %d..%d: %d launches of %d columns", N, in.sc0, in.sc1, p.launches, p.slab);
+  if (p.xs > 0)
+    CHECK(p.xs <= in.grid / 8 && p.xs_pmajor >= 1 && p.xs_pmajor <= in.grid / 8 && p.xs_groups >= 1 && 8 % p.xs_groups == 0,
+          "N %lld: xs %d / %d workgroups, %d groups, grid %d", N, p.xs, p.xs_pmajor, p.xs_groups, in.grid);
+  if (p.src_blocks == 0) {
+    CHECK(p.shape == 0, "N %lld: a kernel shape without the blocked matvec", N);
+    return;
+  }
+  CHECK(p.src_blocks <= osc::OSC_MAX_SRC_BLOCKS && p.shape >= 0 && p.shape < osc::kBlkShapeCount, "N %lld: %d blocks, shape %d", N, p.src_blocks, p.shape);
+  if (p.shape < 0 || p.shape >= osc::kBlkShapeCount) return;
+  const osc::BlkShape& sh = osc::kBlkShapes[p.shape];
+  CHECK(p.geom.groups >= 1 && p.geom.groups <= sh.gm && p.geom.xs >= 1 && p.geom.xs <= in.grid / 8 && p.geom.xs_groups == p.xs_groups,
+        "N %lld shape %d: %d groups, %d workgroups per XCD", N, p.shape, p.geom.groups, p.geom.xs);
+  if (!extents_seen.insert({in.N, p.geom.xs, p.geom.xs_groups, p.geom.groups, p.geom.slices, sh.cw}).second) return;
+  const int64_t extent = blocked_list_extent(in.N, p.geom, sh.cw);  // throws if the slices do not cover the rows
+  CHECK(extent <= in.N - 1 + 8 * sh.cw && extent <= in.N + kPadRows, "N %lld shape %d: list copies reach row %lld", N, p.shape, (long long)extent);
+}
+static void check_plans() {
+  std::set<std::vector<int64_t>> extents_seen;
+  std::vector<int64_t> ns;
+  for (int64_t n = 1; n <= 1200000; n = n * 6 / 5 + 1) ns.push_back(n);
+  for (int64_t n : {6144, 12288, 16384, 20000, 24576, 32768, 96000, 150000, 300000, 524288, 524289, 1200000}) ns.push_back(n);
+  for (int64_t N : ns)
+    for (int32_t dcols : {4, 64, 96, 128, 192, 256, 384, 768, 1000, 1536})
+      for (int32_t ld : {dcols, (dcols + 31) / 32 * 32, (dcols + 31) / 32 * 32 + 32, dcols + 4})  // aligned and ragged pitches
+        for (int world : {1, 2, 3, 8})  // column windows of one to eight ranks
+          for (int rank : {0, world - 1}) {
+            const auto cw = column_shard(dcols, rank, world);
+            if (cw.second <= cw.first) continue;
+            for (double deg : {2.0, 13.8, 62.0})
+              for (int f = 0; f < 2 * 3 * 8; ++f) {
+                const bool reordered = f & 1;
+                const int32_t prows = (f >> 1) % 3 == 0 ? 0 : (f >> 1) % 3 == 1 ? 64 : 5000;  // chain rows (5000: too many for the fix-up)
+                ApplyInputs in = apply_inputs(N, deg, ld, cw.first, cw.second, reordered, prows, prows > 0);
+                switch (f / 6) {  // each kept forcing switch
+                  case 1: in.spmm_xs = 0; break;
+                  case 2: in.spmm_xs = 1; break;
+                  case 3: in.xs_nb = 40; break;
+                  case 4: in.spmm_blocked = 0; break;
+                  case 5: in.spmm_xs = 1, in.spmm_blocked = 7; break;
+                  case 6: in.spmm_xs = 1, in.blk_variant = (int)(N % osc::kBlkShapeCount); break;
+                  case 7: in.spmm_deep = false; break;
+                }
+                check_plan(in, extents_seen);
+                in.sc0 = 0, in.sc1 = 4, in.sld = 4;  // the single right-hand side solve (osc_cg_single_rhs)
+                check_plan(in, extents_seen);
+              }
+          }
+  // plans recorded at the parent of the planner for the shapes of scripts/shape_sweep.py and configs 3, 4, 5 (whole window
+  // and ranks 0 / 5 of eight, with and without a 64-row chain prior); mean degree 1.5 k, BFS order for the clustered shapes
+  struct Want {
+    int xs, xs_pmajor, xs_groups, slab, launches, pblk, src_blocks, shape, gxs, ggroups, gslices;
+  };
+  struct Row {
+    int64_t N;
+    int k, ld, c0, c1, reordered, chain, world, rank;
+    Want w;
+  };
+  const Row rows[] = {
+      {8000, 8, 64, 0, 64, 0, 0, 1, 0, {0, 0, 0, 64, 1, 0, 0, 0, 0, 0, 0}},
+      {8000, 16, 256, 0, 256, 0, 0, 1, 0, {96, 128, 8, 256, 1, 1, 0, 0, 0, 0, 0}},
+      {8192, 32, 768, 0, 768, 0, 0, 1, 0, {96, 128, 8, 768, 1, 1, 0, 0, 0, 0, 0}},
+      {12000, 32, 1536, 0, 1536, 0, 0, 1, 0, {96, 128, 8, 1536, 1, 1, 0, 0, 0, 0, 0}},
+      {16384, 16, 128, 0, 128, 0, 0, 1, 0, {96, 128, 4, 128, 1, 1, 0, 0, 0, 0, 0}},
+      {20000, 16, 128, 0, 128, 0, 0, 1, 0, {96, 128, 4, 128, 1, 1, 7, 0, 64, 3, 1}},
+      {20000, 32, 768, 0, 768, 0, 0, 1, 0, {96, 128, 8, 768, 1, 1, 15, 0, 64, 6, 1}},
+      {32768, 8, 64, 0, 64, 0, 0, 1, 0, {96, 128, 2, 64, 1, 1, 4, 0, 64, 3, 1}},
+      {40000, 32, 256, 0, 256, 0, 0, 1, 0, {96, 128, 8, 256, 1, 1, 15, 0, 64, 12, 1}},
+      {50000, 32, 512, 0, 512, 0, 0, 1, 0, {96, 128, 8, 512, 1, 1, 15, 0, 64, 14, 1}},
+      {60000, 24, 1056, 0, 1024, 0, 0, 1, 0, {96, 128, 8, 1024, 1, 1, 11, 0, 64, 9, 2}},
+      {65536, 16, 256, 0, 256, 0, 0, 1, 0, {96, 128, 8, 256, 1, 1, 7, 0, 64, 10, 2}},
+      {80000, 32, 768, 0, 768, 0, 0, 1, 0, {96, 128, 8, 768, 1, 1, 15, 0, 64, 12, 2}},
+      {100000, 16, 64, 0, 64, 0, 0, 1, 0, {96, 128, 2, 64, 1, 1, 7, 0, 64, 7, 1}},
+      {100000, 16, 128, 0, 128, 0, 0, 1, 0, {96, 128, 4, 128, 1, 1, 7, 0, 64, 14, 1}},
+      {100000, 16, 384, 0, 384, 0, 0, 1, 0, {96, 128, 4, 384, 1, 1, 7, 6, 32, 28, 1}},
+      {100000, 32, 768, 0, 768, 0, 0, 1, 0, {96, 128, 8, 768, 1, 1, 14, 6, 32, 28, 2}},
+      {100000, 64, 768, 0, 768, 0, 0, 1, 0, {96, 128, 8, 768, 1, 1, 27, 6, 32, 28, 2}},
+      {130000, 32, 256, 0, 256, 0, 0, 1, 0, {96, 128, 8, 256, 1, 1, 15, 0, 64, 13, 3}},
+      {150000, 20, 640, 0, 640, 0, 0, 1, 0, {96, 128, 4, 640, 1, 1, 9, 5, 32, 21, 2}},
+      {160000, 32, 768, 0, 768, 0, 0, 1, 0, {96, 128, 4, 768, 1, 1, 15, 5, 32, 23, 2}},
+      {200000, 32, 64, 0, 64, 0, 0, 1, 0, {96, 128, 2, 64, 1, 1, 15, 6, 32, 28, 1}},
+      {200000, 32, 768, 0, 768, 0, 0, 1, 0, {96, 128, 4, 768, 1, 1, 15, 6, 32, 28, 2}},
+      {200000, 64, 1536, 0, 1536, 0, 0, 1, 0, {96, 128, 4, 1536, 1, 1, 30, 6, 32, 28, 2}},
+      {260000, 64, 768, 0, 768, 0, 0, 1, 0, {96, 128, 4, 768, 1, 1, 32, 6, 32, 25, 3}},
+      {300000, 32, 768, 0, 768, 0, 0, 1, 0, {96, 128, 2, 768, 1, 1, 17, 5, 32, 21, 2}},
+      {400000, 32, 512, 0, 512, 0, 0, 1, 0, {96, 128, 2, 512, 1, 1, 17, 6, 32, 28, 2}},
+      {500000, 16, 384, 0, 384, 0, 0, 1, 0, {96, 128, 2, 384, 1, 1, 11, 5, 32, 24, 3}},
+      {700000, 16, 384, 0, 384, 0, 0, 1, 0, {96, 128, 4, 384, 1, 1, 11, 6, 32, 28, 7}},
+      {1000000, 16, 384, 0, 384, 0, 0, 1, 0, {96, 128, 4, 384, 1, 1, 11, 6, 32, 28, 10}},
+      {1000000, 8, 64, 0, 64, 0, 0, 1, 0, {0, 0, 0, 64, 1, 0, 0, 0, 0, 0, 0}},
+      {9000, 12, 48, 0, 48, 1, 0, 1, 0, {0, 0, 0, 48, 1, 0, 0, 0, 0, 0, 0}},
+      {16384, 16, 64, 0, 64, 1, 0, 1, 0, {0, 0, 0, 64, 1, 0, 0, 0, 0, 0, 0}},
+      {30000, 16, 256, 0, 256, 1, 0, 1, 0, {0, 0, 0, 256, 1, 0, 0, 0, 0, 0, 0}},
+      {50000, 24, 128, 0, 128, 1, 0, 1, 0, {0, 0, 0, 128, 1, 0, 0, 0, 0, 0, 0}},
+      {100000, 32, 768, 0, 768, 1, 0, 1, 0, {0, 0, 0, 256, 3, 0, 0, 0, 0, 0, 0}},
+      {150000, 20, 640, 0, 640, 1, 0, 1, 0, {0, 0, 0, 256, 3, 0, 0, 0, 0, 0, 0}},
+      {200000, 16, 384, 0, 384, 1, 0, 1, 0, {0, 0, 0, 256, 2, 0, 0, 0, 0, 0, 0}},
+      {200000, 32, 1536, 0, 1536, 1, 0, 1, 0, {0, 0, 0, 256, 6, 0, 0, 0, 0, 0, 0}},
+      {400000, 16, 256, 0, 256, 1, 0, 1, 0, {96, 128, 2, 256, 1, 1, 11, 6, 32, 28, 2}},
+      {1000000, 16, 128, 0, 128, 1, 0, 1, 0, {96, 128, 4, 128, 1, 1, 11, 6, 32, 28, 10}},
+      {100000, 32, 768, 0, 768, 0, 0, 1, 0, {96, 128, 8, 768, 1, 1, 14, 6, 32, 28, 2}},
+      {100000, 32, 768, 0, 96, 0, 0, 8, 0, {96, 128, 1, 96, 1, 1, 14, 1, 32, 7, 1}},
+      {100000, 32, 768, 480, 576, 0, 0, 8, 5, {96, 128, 1, 96, 1, 1, 14, 1, 32, 7, 1}},
+      {100000, 32, 768, 0, 768, 0, 1, 1, 0, {96, 128, 8, 768, 1, 1, 14, 6, 32, 28, 2}},
+      {100000, 32, 768, 0, 96, 0, 1, 8, 0, {96, 128, 1, 96, 1, 1, 14, 1, 32, 7, 1}},
+      {100000, 32, 768, 480, 576, 0, 1, 8, 5, {96, 128, 1, 96, 1, 1, 14, 1, 32, 7, 1}},
+      {1000000, 16, 384, 0, 384, 0, 0, 1, 0, {96, 128, 4, 384, 1, 1, 11, 6, 32, 28, 10}},
+      {1000000, 16, 384, 0, 48, 0, 0, 8, 0, {0, 0, 0, 64, 1, 0, 0, 0, 0, 0, 0}},
+      {1000000, 16, 384, 240, 288, 0, 0, 8, 5, {0, 0, 0, 64, 1, 0, 0, 0, 0, 0, 0}},
+      {1000000, 16, 384, 0, 384, 0, 1, 1, 0, {96, 128, 4, 384, 1, 1, 11, 6, 32, 28, 10}},
+      {1000000, 16, 384, 0, 48, 0, 1, 8, 0, {0, 0, 0, 64, 1, 0, 0, 0, 0, 0, 0}},
+      {1000000, 16, 384, 240, 288, 0, 1, 8, 5, {0, 0, 0, 64, 1, 0, 0, 0, 0, 0, 0}},
+      {200000, 64, 1536, 0, 1536, 0, 0, 1, 0, {96, 128, 4, 1536, 1, 1, 30, 6, 32, 28, 2}},
+      {200000, 64, 1536, 0, 192, 0, 0, 8, 0, {96, 128, 2, 192, 1, 1, 30, 6, 32, 28, 1}},
+      {200000, 64, 1536, 960, 1152, 0, 0, 8, 5, {96, 128, 2, 192, 1, 1, 30, 6, 32, 28, 1}},
+      {200000, 64, 1536, 0, 1536, 0, 1, 1, 0, {96, 128, 4, 1536, 1, 1, 30, 6, 32, 28, 2}},
+      {200000, 64, 1536, 0, 192, 0, 1, 8, 0, {96, 128, 2, 192, 1, 1, 30, 6, 32, 28, 1}},
+      {200000, 64, 1536, 960, 1152, 0, 1, 8, 5, {96, 128, 2, 192, 1, 1, 30, 6, 32, 28, 1}},
+  };
+  for (const Row& r : rows) {
+    const ApplyPlan p = plan_apply(apply_inputs(r.N, 1.5 * r.k, r.ld, r.c0, r.c1, r.reordered != 0, r.chain ? 64 : 0, r.chain != 0));
+    const Want& w = r.w;
+    CHECK(p.xs == w.xs && p.xs_pmajor == w.xs_pmajor && p.xs_groups == w.xs_groups && p.slab == w.slab && p.launches == w.launches &&
+              (int)p.pblk == w.pblk && p.src_blocks == w.src_blocks && p.shape == w.shape &&
+              (w.src_blocks == 0 || (p.geom.xs == w.gxs && p.geom.groups == w.ggroups && p.geom.slices == w.gslices)),
+          "N %lld k %d window %d..%d of pitch %d: xs %d, %d launches of %d, %d blocks, shape %d", (long long)r.N, r.k, r.c0, r.c1, r.ld, p.xs,
+          p.launches, p.slab, p.src_blocks, p.shape);
   }
 }
 
@@ -382,6 +543,7 @@ int main(int argc, char** argv) {
       CHECK(g == 0 || (8 % g == 0 && (in_budget || (N > kXsBudgetRows && ncols >= 128 && g <= 4 && g <= xs_groups(ncols, 8)))),
             "N %lld ncols %d groups %d", (long long)N, ncols, g);
     }
+  check_plans();
   for (double deg : {1.0, 13.8, 28.8, 59.5})
     for (int64_t N : {96000, 140000, 220000, 450000, 450001, 2000000}) {
       const int nb = blocked_block_count(deg, blocked_edges_per_block_wide(N), 32);

@@ -74,7 +74,7 @@ def _compare(amd, orc, lat, Y, psi, k, *, gates=None, chain=None, lamP=0.2, labe
 
 def test_config3_full_size_against_oracle(amd, orc, monkeypatch):
     """N=100000, D=768, k=32: the benchmark workload; the default plan must be the one-launch XCD-affine apply."""
-    for v in ("OSC_SPMM_XS", "OSC_SPMM_SLAB", "OSC_KNN_MODE", "OSC_REORDER"):
+    for v in ("OSC_SPMM_XS", "OSC_KNN_MODE", "OSC_REORDER"):
         monkeypatch.delenv(v, raising=False)
     N, D, k = 100_000, 768, 32
     Y, psi = _inputs(0, N, D)
@@ -87,7 +87,7 @@ def test_config3_full_size_against_oracle(amd, orc, monkeypatch):
 
 def test_config5_full_size_gates_chain_against_oracle(amd, orc, monkeypatch):
     """N=200000, D=1536, k=64 with diffusion gates (lamQ diag term) and the chain prior (lamP path term)."""
-    for v in ("OSC_SPMM_XS", "OSC_SPMM_SLAB", "OSC_KNN_MODE", "OSC_REORDER"):
+    for v in ("OSC_SPMM_XS", "OSC_KNN_MODE", "OSC_REORDER"):
         monkeypatch.delenv(v, raising=False)
     N, D, k = 200_000, 1536, 64
     Y, psi = _inputs(5, N, D)
@@ -104,7 +104,7 @@ def test_config4_full_size_against_oracle(amd, orc, plan, monkeypatch):
     """N=1000000, D=384, k=16.  Default plan since round 5: the wide source-blocked matvec with four slab groups (beyond the
     Infinity-Cache budget of the slab mode, where rounds 2-4 fell back to sequential column slabs); "general" keeps that
     sequential column-slab apply under test at this size (OSC_SPMM_XS=0)."""
-    for v in ("OSC_SPMM_XS", "OSC_SPMM_SLAB", "OSC_KNN_MODE", "OSC_REORDER"):
+    for v in ("OSC_SPMM_XS", "OSC_KNN_MODE", "OSC_REORDER"):
         monkeypatch.delenv(v, raising=False)
     if plan == "general":
         monkeypatch.setenv("OSC_SPMM_XS", "0")

@@ -1321,7 +1321,7 @@ def test_inertia_and_cold_starts_on_the_blocked_path(amd, orc, monkeypatch):
     seq = [dict(max_iters=2, tol=1e-9), dict(inertia=0.4, max_iters=12, tol=1e-4), dict(inertia=1.0, max_iters=3, tol=1e-9),
            dict(warm_start=False, max_iters=12, tol=1e-4), dict(inertia=0.7, max_iters=12, tol=1e-5)]
     runs = {}
-    for mode in ("0", "-2"):
+    for mode in ("0", "-1"):
         monkeypatch.setenv("OSC_SPMM_BLOCKED", mode)
         lat = amd.Oscillink(Y, kneighbors=k)
         lat.set_query(psi)
@@ -1329,7 +1329,7 @@ def test_inertia_and_cold_starts_on_the_blocked_path(amd, orc, monkeypatch):
         for kw in seq:
             st = lat.settle(**kw)
             runs[mode].append((st["iters"], st["res"], lat.U.copy()))
-        assert (lat.build_info()["apply_src_blocks"] > 0) == (mode == "-2")
+        assert (lat.build_info()["apply_src_blocks"] > 0) == (mode == "-1")
         if mode == "0":
             rp, col, a, w, sd = lat.graph_csr()
         lat.close()
@@ -1337,7 +1337,7 @@ def test_inertia_and_cold_starts_on_the_blocked_path(amd, orc, monkeypatch):
     ref.set_query(psi)
     for i, kw in enumerate(seq):
         rs = ref.settle(**kw)
-        for mode in ("0", "-2"):
+        for mode in ("0", "-1"):
             it, res, U = runs[mode][i]
             assert it == rs["iters"], (mode, kw)
             assert relerr(U, ref.U) < 2e-6, (mode, kw, relerr(U, ref.U))

@@ -1,4 +1,4 @@
-"""The automatic choice of the operator-apply plan (osc_api.hip: xs_plan / blocked_plan / auto_slab / maybe_reorder, the
+"""The automatic choice of the operator-apply plan (host_logic.hpp: plan_apply; osc_graph.hip: maybe_reorder, the
 measured thresholds VERDICT r03 called a thicket) against every plan that can be forced through the OSC_* switches, on a
 6-shape subset of scripts/shape_sweep.py (the full 41-shape table is profiles/r04_shape_sweep.txt): the default must be
 within 10 % of the best forced plan.  Medians of 12 settles; one retry absorbs a noisy neighbour.
