@@ -1,26 +1,11 @@
 // Launchers of the lattice-build kernels (knn_kernels.hip).
 #pragma once
 #include "common.hpp"
-#include "knn_rowmap.hpp"
+#include "knn_plan.hpp"
 
 namespace osc {
 
-struct KnnPlan {
-  int E;               // list entries per lane (capacity 32E >= keep)
-  int KC;              // candidate slots per (row, split) = 32E
-  int keep;            // entries each list keeps (threshold = similarity at rank keep-1)
-  int row_blocks;      // 128-row blocks this launch covers
-  int S;               // column splits
-  int cols_per_split;  // multiple of 128
-  int rb_begin;        // first row block this process computes (multi-GPU: row-block-sharded build)
-  int rb_count;        // number of row blocks this process computes
-  bool f16;            // prefilter variant (fp16 MFMA on the fp16 image of 16*Yn)
-  const int32_t* qrows;  // optional explicit list of query rows (per-row exact fallback), device pointer
-  int nq;
-};
-
-// keep <= 128 (exact) / <= 96 (f16).  slots = resident blocks on the device (load balance of the split count)
-KnnPlan knn_plan(int32_t N, int32_t keep, int32_t slots, int rb_begin, int rb_count, bool f16, int splits_override = 0);  // (override: OSC_KNN_SPLITS, read by the caller)
+// (KnnPlan, knn_plan: knn_plan.hpp)
 void launch_normalize_rows(const float* Y, int32_t ldy, float* Yn, int32_t ldn, int64_t N, int32_t D, hipStream_t s);
 void launch_rows_dot(const float* Yn, int32_t ldn, const float* q, float* out, int64_t N, int32_t D, hipStream_t s);
 void launch_rows_cosine(const float* A, int32_t ld, const float* q, float* out, int64_t N, int32_t D, hipStream_t s);

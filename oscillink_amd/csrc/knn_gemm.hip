@@ -57,7 +57,7 @@ constexpr int RING = 6;
 constexpr unsigned STAGE_BYTES = 16384;  // one K step of a column tile: 128 rows x 128 B
 // MODE 1: each wave appends its hits to a private LDS list (ds_write is not on the vmcnt queue the DMA ring is counted
 // on: global stores in the epilogue made every tile wait for their completion) and flushes it at the end of the item
-constexpr int HB_CAP = 1792;  // entries of 8 bytes per wave: 4 x 14 KB behind the ring
+// (HB_CAP: hit entries of 8 bytes per wave, 4 x 14 KB behind the ring -- knn_plan.hpp, with the kernels' other capacities)
 constexpr size_t PANEL_LDS = (size_t)RING * STAGE_BYTES + 2048;
 constexpr size_t PANEL_LDS_HITS = PANEL_LDS + (size_t)4 * HB_CAP * 8;
 // Symmetric half sweep (SYM, single-process builds): S = Yh Yh^T is symmetric bit for bit (every product a_ik b_jk is
@@ -85,8 +85,7 @@ constexpr size_t PANEL_LDS_HITS = PANEL_LDS + (size_t)4 * HB_CAP * 8;
 // (the overflow path stays: the rows concerned go to the exact kernel).  (Delivering a half-full list AFTER a tile was
 // not enough: at N = 40 000, D = 256 on clustered anchors a tile adds 39 entries on average to lists of 260, some tiles
 // five times that, and every overflow sends its chunk's 3072 rows to the exact kernel: 8768 fallback rows against 66.)
-constexpr int TC_TILES = 24;       // tiles per chunk the threshold window holds
-constexpr int HB_CAP_SYM = 520;    // coarse entries per wave
+// (TC_TILES: tiles per chunk the threshold window holds; HB_CAP_SYM: coarse entries per wave -- knn_plan.hpp)
 constexpr size_t SYM_CNT_BYTES = (size_t)4 * 8 * TC_TILES * 4;  // per wave [2][4 TC_TILES] ints: bucket counts / cursors, bases
 static_assert((size_t)4 * HB_CAP_SYM * 20 + (size_t)TC_TILES * 512 + SYM_CNT_BYTES <= (size_t)4 * HB_CAP * 8, "SYM layout must fit the hit area");
 constexpr unsigned ROW_SIDE = 1u << 26, COL_SIDE = 1u << 25, COL_MASK = (1u << 25) - 1u;
@@ -737,8 +736,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 // end of the item.  Config 5's build (200k x 1536, k 64) spent 227 of its 257 ms in the list-maintaining full sweep of
 // k_knn_pref; this sweep visits half the tiles and inserts nothing.  LDS: 64 KB of stages + 4 x TH_CAP entries + a
 // threshold window of TT_TILES tiles = 78 KB, two workgroups per CU.
-constexpr int TH_CAP = 320;
-constexpr int TT_TILES = 8;
+// (TH_CAP, TT_TILES: knn_plan.hpp)
 constexpr unsigned TILE_STAGE = (128 + 128) * 128;  // bytes of one stage: A tile, then B tile
 constexpr size_t TILE_LDS = (size_t)2 * TILE_STAGE;
 constexpr size_t TILE_LDS_HITS = TILE_LDS + (size_t)4 * TH_CAP * 8 + (size_t)TT_TILES * 512;
@@ -1219,7 +1217,7 @@ __global__ __launch_bounds__(256) void k_panel_select(const uint2* hit_list, con
 // stages, one workgroup per CU (still two waves per SIMD).  Everything else is k_tile_thr<1>: flat (tile pair, K step)
 // pipeline, threshold test on both sides, fine 8-byte entries in per-(wave, row group) LDS lists that are delivered to the
 // 32-row buckets when the next tile might not fit and at the end of the item.
-constexpr int T2_CAP = 160;  // (the planner's measure of a list: fine entries; the kernel's lists hold T2_HC coarse ones since round 6)
+// (T2_CAP, the planner's measure of a list in fine entries: knn_plan.hpp)
 constexpr int T2_HC = 72;    // coarse entries (20 bytes: header + a row register's four subtile scores) per (wave, row group) list
 constexpr unsigned T2_STAGE = (256 + 256) * 128;
 constexpr size_t T2_LDS = (size_t)2 * T2_STAGE;
@@ -1675,150 +1673,6 @@ void launch_panel(const PanelArgs& a, int nkt, int nrg, bool sym, int grid, hipS
 }
 
 }  // namespace
-
-int knn_panel_nkt(int32_t D) { return D <= 384 ? 6 : D <= 768 ? 12 : 0; }
-// K steps of the tile core (both operands through LDS): any depth; used beyond 768 columns, up to 4096
-int knn_tile_nkt(int32_t D) { return (D > 768 && D <= 4096) ? (D + 63) / 64 : 0; }
-
-void knn_panel_set_pieces(KnnPanelPlan& p, int32_t N, const int32_t* starts, int npieces) {
-  p.map = knn_row_map(N, starts, npieces, p.scatter != 1);
-}
-
-KnnPanelPlan knn_panel_plan(int32_t N, int32_t D, int32_t keep, int32_t cus, bool scatter_rows, bool sym,
-                            const KnnPanelTune& tune) {
-  KnnPanelPlan p{};
-  p.sym = sym;
-  p.map = knn_row_map(N, nullptr, 1, scatter_rows);
-  p.scatter = p.map.a[0];
-  p.nkt = knn_panel_nkt(D);
-  p.tile_core = false;
-  if (p.nkt == 0 && sym && knn_tile_nkt(D) != 0) {  // D > 768: the tile core under the same thresholds / buckets / select
-    p.nkt = knn_tile_nkt(D);
-    p.tile_core = true;
-  }
-  p.ldh = 64 * p.nkt;
-  // row groups per wave: two where the panel is small enough (D <= 384: 2 x 96 registers), see the file header
-  p.npad = ((N + 127) / 128) * 128;
-  p.nrb = p.npad / 128;
-  // (round 6: two row groups also at K depth 12 in the half sweep -- k_panel<12, 1, 2, true>, 64-column passes -- from 720 row
-  // blocks on: gemm_topk at D = 768, one / two groups, profiles/r06_knn_nrg_ab.txt: 40 000 rows 2.05 / 2.23 ms, 60 000 3.64 / 3.73,
-  // 80 000 6.19 / 6.20, 100 000 9.50 / 8.97, 140 000 x 640 16.9 / 15.8, 200 000 33.5 / 31.4 -- the items are twice as long and
-  // half as many, which smaller lattices pay for at the tail of the persistent grid)
-  p.nrg = p.tile_core ? 1 : p.nkt == 6 ? (tune.nrg != 1 ? 2 : 1) : (p.nkt == 12 && sym && (tune.nrg == 2 || (tune.nrg == 0 && p.nrb >= 720))) ? 2 : 1;
-  p.nrg_s = p.nkt == 6 ? p.nrg : 1;
-  p.keep = keep;
-  // Thresholds: the sample holds one column in rho; tau = the 14th largest tile maximum ~ the 15th-17th best sample
-  // score, so about rho * 16 columns of the full sweep beat it (gamma-distributed: 0.1 % of the rows see fewer than
-  // rho * 6 or more than rho * 32).  rho = keep / 4 puts `keep` at the low tail and 8 keep slots above the high one;
-  // OSC_KNN_PANEL_RHO overrides it.
-  const double rho_env = tune.rho;
-  // (round 3, config 4's shape, keep = 24: rho 6 / 8 / 12 / 16 -> build 798 / 790 / 775 / 784 ms with 6 / 1 / 1 / 129 rows sent
-  // to the exact kernel; from 24 on the folded group maxima put tau so low that every hit list overflows.  Config 3,
-  // keep = 48: 8 / 12 / 16 -> 26.5 / 22.2 / 26.8 ms.  Hence at least 12.)
-  // (round 6: beyond 4800 row blocks at most 400 sample tiles -- 51 200 columns -- while rho stays <= 20.  The thresholds are order statistics of <= 128 group maxima, which a
-  // denser sample of a very large lattice does not sharpen, while the sample sweep costs nrb / rho tile passes per row block:
-  // config 4 (7813 row blocks) rho 12 / 16 / 20 / 24 -> build 403 / 399 / 394 / 396 ms, 0 fallback rows each
-  // (scripts/exp/r06/c4_sweep.py); up to 4800 row blocks nothing changes; never beyond 20: 1.5 M x 256 at rho = 29 sent 111
-  // rows to the exact kernel and built slower -- profiles/r06_rho_cap.txt)
-  const double rho = rho_env > 0.0 ? rho_env : std::max(std::max(12.0, keep / 4.0), std::min(20.0, p.nrb / 400.0));
-  p.sample_tiles = (int32_t)std::max(24.0, std::min(p.nrb / 2.0, std::round(p.nrb / rho)));
-  // tile maxima are folded over groups of consecutive sample tiles so that a row has at most 128 of them (the r-th
-  // largest group maximum is still a lower bound of the r-th best sample score)
-  p.group_tiles = (p.sample_tiles + 127) / 128;
-  p.sample_groups = (p.sample_tiles + p.group_tiles - 1) / p.group_tiles;
-  // The threshold rank.  tau = the r-th largest of G group maxima lets (N / sample columns) G -ln(1 - r / G) columns of a row
-  // through in expectation; the target is 4 keep of them (= 16 rho at rho = keep / 4; at least 192), which is rank 14 at
-  // configs 3 / 4 / 5 (G = 65; measured there: rank 16 / 14 / 12 / 10 -> 2 / 2 / 21 / 346 rows short of candidates).  Where
-  // the sample cannot be that sparse (small lattices: at least 24 sample tiles) the rank rises with the need, up to 0.9 G;
-  // the route is offered as long as even that leaves a row twice `keep` candidates.  (Until round 4 the route was held
-  // to N >= 16384 and samples of < keep / 8 density: rows short of candidates went to the exact kernel then; now they are
-  // proven from their buckets, and between 8192 and 16384 rows this route builds in half the tile prefilter's time:
-  // 12000 x 768, k 16: 1.70 -> 0.79 ms; 15000 x 768, k 32: 3.20 -> 1.30 ms.)
-  {
-    const double G = (double)p.sample_groups, per_col = (double)p.nrb / p.sample_tiles;
-    const double target = std::max(4.0 * keep, 192.0);
-    const double rmax = std::floor(0.9 * G);
-    double r = std::ceil(G * (1.0 - std::exp(-target / (per_col * G))) - 0.25);
-    r = std::max(std::min(14.0, rmax), std::min(r, rmax));
-    p.sample_rank = (int32_t)r;
-    p.ok = per_col * G * -std::log(1.0 - rmax / G) >= 2.0 * keep;
-  }
-  if (tune.rank > 0) p.sample_rank = std::max(2, std::min(p.sample_groups, tune.rank));
-  // column splits: whatever leaves the smallest idle tail on `cus` persistent workgroups (per-item overhead ~1 %)
-  // ... and few enough hits per wave and item for its LDS list: 32 rows x ~5 keep / S <= ~2/3 of HB_CAP
-  p.hit_cap = HB_CAP / p.nrg;
-  const int s_min = std::max(1, (int)std::ceil(32.0 * std::max(5.0 * keep, 20.0 * rho) / (0.66 * p.hit_cap)));
-  const int nsets = (p.nrb + p.nrg - 1) / p.nrg;  // work items per split
-  double best = 1e30;
-  p.S = s_min;
-  for (int S = s_min; S <= s_min + 8; ++S) {
-    if (p.nrb / S < 16 && S > s_min) break;
-    const double rounds = (double)nsets * S / std::max(1, cus);
-    const double cost = std::ceil(rounds) / rounds * (1.0 + 0.01 * S);
-    if (cost < best - 1e-9) {
-      best = cost;
-      p.S = S;
-    }
-  }
-  p.tiles_per_split = (p.nrb + p.S - 1) / p.S;
-  // Candidates a row's threshold lets through, in expectation: tau is the r-th largest of G group maxima, so r of G groups
-  // hold a sample column above it; with lambda such columns per group, 1 - exp(-lambda) = r / G, and every sample column
-  // stands for nrb / sample_tiles columns of the sweep.  G = 65 (config 3): 190 (the "16 rho" of round 2); G = 26 (N = 40 000):
-  // 242 -- a bound of max(5 keep, 20 rho) = 240 then sized the 32-row buckets below their mean load and sent whole
-  // buckets to the exact kernel (8768 fallback rows on clustered anchors at N = 40 000, D = 256, k = 24).
-  {
-    const double G = (double)p.sample_groups, r = std::min((double)p.sample_rank, 0.95 * G);
-    const double mean_hits = (double)p.nrb / p.sample_tiles * G * -std::log(1.0 - r / G);
-    p.hit_bound = std::max(std::max(5.0 * keep, 20.0 * rho), 1.25 * mean_hits);
-  }
-  if (sym) {
-    // half sweep: column chunks of T tiles; a (wave, item) list takes the row-side AND the column-side hits of its tiles,
-    // 2 x 32 rows x bound / nrb per tile, and should stay within ~2/3 of its LDS list; the item's column thresholds must
-    // fit their LDS window (TC_TILES); T even where a set holds two row blocks (both then meet their diagonal in one chunk)
-    // (k_tile_thr2 delivers a list before a tile that might not fit: a tile's mean load must stay well below the 96 entries
-    // that check leaves it -- small N with a deep k goes through k_tile_thr<1>, whose lists hold a whole item)
-    p.tile_wide = p.tile_core && tune.tile_wide != 0 && 64.0 * p.hit_bound / p.nrb <= 40.0;
-    p.hit_cap = p.tile_core ? (p.tile_wide ? T2_CAP : TH_CAP) : HB_CAP_SYM / p.nrg;
-    const double bound = p.hit_bound;
-    int T = (int)std::floor(0.66 * p.hit_cap * p.nrb / (64.0 * bound));  // (the tile core's lists are a hard limit)
-    if (!p.tile_core) T = TC_TILES;  // k_panel delivers a list that is half full: the threshold window alone limits an item
-    T = std::max(p.tile_core ? 1 : 2, std::min(p.tile_core ? TT_TILES : TC_TILES, T));
-    if (tune.T > 0) T = std::max(p.tile_core ? 1 : 2, std::min(p.tile_core ? TT_TILES : TC_TILES, tune.T));  // (A/B: tiles per chunk)
-    if (p.tile_wide) T = TT_TILES;  // (its lists are delivered as they fill: the threshold window alone limits an item)
-    if (p.nrg == 2 || p.tile_wide) T &= ~1;
-    p.T = T;
-    p.S = (p.nrb + T - 1) / T;  // chunks
-    p.tiles_per_split = T;
-    p.bucket_cap = (int32_t)(32.0 * 1.5 * bound);  // a group of 32 rows receives all its candidates here; 1.5: rows of a group vary, clustered anchors have heavy tails
-    p.nitems = 0;
-    const int per_item = p.tile_wide ? 2 : p.nrg;  // row blocks of one work item
-    if (p.tile_wide) {  // groups of sets whose image rows fit the Infinity Cache next to the passing chunks (equal sizes)
-      const int nsets = (p.nrb + 1) / 2;
-      const double group_mb = tune.tile_group_mb > 0 ? tune.tile_group_mb : 128.0;
-      const int ngroups = std::max(1, (int)std::ceil(nsets * 256.0 * p.ldh * 2.0 / (group_mb * 1048576.0)));
-      p.tile_group_sets = (nsets + ngroups - 1) / ngroups;
-    }
-    for (int c = 0; c < p.S; ++c) p.nitems += (std::min(p.nrb, (c + 1) * T) + per_item - 1) / per_item;
-  }
-  // phase A: splits of whole tile groups, again for the tail of the persistent grid
-  // (round 4: grouping a row's sample columns by (column split, lane) instead -- 32 running maxima per split, no shuffles and
-  // no stores inside the sweep -- took 0.14 ms off config 3's 1.8 ms sample sweep but moved the thresholds: 16 instead of 1
-  // rows short of candidates at N = 20000, config 4's build 412 -> 419 ms; not kept)
-  best = 1e30;
-  p.SA = 1;
-  const int nsets_s = (p.nrb + p.nrg_s - 1) / p.nrg_s;
-  for (int S = 1; S <= 6 && S <= p.sample_groups; ++S) {
-    const double rounds = (double)nsets_s * S / std::max(1, cus);
-    const double cost = std::ceil(rounds) / rounds * (1.0 + 0.03 * S);
-    if (cost < best - 1e-9) {
-      best = cost;
-      p.SA = S;
-    }
-  }
-  if (tune.sa > 0) p.SA = std::max(1, std::min(tune.sa, p.sample_groups));
-  p.sample_tiles_per_split = ((p.sample_groups + p.SA - 1) / p.SA) * p.group_tiles;
-  return p;
-}
 
 void launch_panel_image(const float* Yn, int32_t ldn, void* Yh, const KnnPanelPlan& p, int32_t N, int32_t D, hipStream_t s, int32_t r0,
                         int32_t r1) {

@@ -7,73 +7,8 @@
 
 namespace osc {
 
-// K steps of 64 halfs the panel kernel is built for: 6 (D <= 384) or 12 (D <= 768); 0 = D not served by this route
-int knn_panel_nkt(int32_t D);
-// ... and of the tile core that serves 768 < D <= 4096 in single-process builds (0 = not served)
-int knn_tile_nkt(int32_t D);
+// (KnnPanelPlan, KnnPanelTune, knn_panel_plan, knn_panel_set_pieces: knn_plan.hpp)
 
-struct KnnPanelPlan {
-  bool ok;             // the lattice is large enough for sampled thresholds (else: use the tile prefilter)
-  int nkt;             // 6 or 12
-  int nrg;             // row groups (32 rows of consecutive 128-row blocks) a wave's register panel holds in the MAIN sweep: 2 at K depth 6 and, round 6, in the half sweep at K depth 12 from 256 row blocks on (64-column passes); else 1
-  int nrg_s;           // ... in the SAMPLE sweep: nrg at K depth 6, else 1 (its running maxima beside 384 panel registers would not fit)
-  int32_t ldh;         // pitch of the fp16 images in halfs = 64 * nkt
-  int32_t npad;        // rows of the query image (N rounded up to 128), zero-filled beyond N
-  int32_t nrb;         // query row blocks (npad / 128)
-  int32_t sample_tiles;  // 128-column tiles of the strided column sample the thresholds come from
-  int32_t group_tiles;   // sample tiles per maximum (so that a row has <= 128 maxima)
-  int32_t sample_groups;
-  int32_t sample_rank;   // threshold = sample_rank-th largest group maximum of the sample
-  int32_t S;           // column splits of the main sweep
-  int32_t tiles_per_split;
-  int32_t SA;          // column splits of the sample sweep
-  int32_t sample_tiles_per_split;
-  int32_t hit_cap;     // entries of one hit list (one per work item and wave)
-  int32_t keep;        // candidates handed to the exact re-scoring
-  double hit_bound;    // candidates per row the thresholds are expected to let through at most: max(5 keep, 20 rho)
-  // Half sweep (single-process builds): the similarity matrix is symmetric bit for bit, so row block I visits only the
-  // column tiles J >= I and every accumulator is tested against its row's AND its column's threshold.  The sweep is cut
-  // into S column CHUNKS of T tiles (S, tiles_per_split = T above); chunk c is swept by the row blocks I < min(nrb,
-  // (c + 1) T): nitems work items in all.  All hits are delivered to buckets of bucket_cap entries, one per group of 32
-  // receiving rows (npad / 32 of them), which is all the select reads.
-  bool sym;
-  bool tile_core;      // D > 768: both operands through LDS (k_tile_thr) instead of the register-resident panel; half sweep only
-  int tile_group_sets;  // k_tile_thr2: row sets per launch
-  bool tile_wide;      // ... its main sweep with 64 x 128 wave tiles (k_tile_thr2); the fp16 image then carries one zero tile behind npad
-  int32_t T;
-  int32_t nitems;
-  int32_t bucket_cap;
-  // Row scatter of the fp16 images: image row r (r < N) holds lattice row (r * scatter) mod N -- a bijection (scatter is
-  // coprime to N; 1 = identity).  Anchors often arrive grouped (documents, clusters): then the 32 rows of a wave all
-  // have their ~cluster-size best columns in the same one or two column tiles, one (work item, wave) hit list takes
-  // 32 x cluster size entries, overflows, and every row of the lattice falls back to the exact kernel (measured: 1000
-  // clusters x 100 rows in cluster order, N = 100k: 100 000 fallback rows, build 190 ms against 39 ms for the same
-  // anchors shuffled).  Scattered, neighbouring image rows are unrelated lattice rows whatever the caller's order.  Only
-  // the prefilter stage works on image rows; k_panel_select hands lattice ids (rows and candidate columns) to the
-  // re-scoring.  Single-process builds and sharded builds that share the half sweep (their ranks own IMAGE row blocks and
-  // assemble the lists by all-reduce: osc_graph.hip); a sharded build with a full sweep per rank (OSC_KNN_PANEL_SYM=0) keeps
-  // the identity, because its ranks own contiguous LATTICE row blocks.
-  int32_t scatter;
-  // ... and the general form every kernel reads (knn.hpp: KnnRowMap): one piece with multiplier `scatter` as planned;
-  // knn_panel_set_pieces cuts the image into pieces that are permuted separately (the streamed create)
-  KnnRowMap map;
-};
-// image row -> lattice row of a plan (rows >= N are padding and map to themselves)
-inline int32_t knn_panel_row(const KnnPanelPlan& p, int32_t N, int32_t r) { return r < N ? knn_map_lattice_row(p.map, N, r) : r; }
-// pieces starting at the given image rows, each holding ITS lattice rows (scattered within the piece iff the plan scatters)
-void knn_panel_set_pieces(KnnPanelPlan& p, int32_t N, const int32_t* starts, int npieces);
-// A/B overrides of the planner (OSC_KNN_PANEL_NRG / _RHO / _T / _RANK, read by the caller; 0 = the planner's own choice)
-struct KnnPanelTune {
-  int nrg = 0;     // 1: one row group per wave also at K depth 6; 2: two also at K depth 12 below 256 row blocks (half sweep)
-  double rho = 0;  // one sample column in rho
-  int T = 0;       // half sweep: tiles per chunk
-  int rank = 0;    // threshold = rank-th largest group maximum of the sample
-  int tile_wide = 1;  // 0: the tile core's main sweep with 32 x 128 wave tiles (k_tile_thr<1>)
-  int tile_group_mb = 0;  // k_tile_thr2: image bytes of one group of row sets (0: 128 MB)
-  int sa = 0;      // sample sweep: splits of the sample's tile groups per row-block set (0: the planner's tail model)
-};
-KnnPanelPlan knn_panel_plan(int32_t N, int32_t D, int32_t keep, int32_t cus, bool scatter_rows = false, bool sym = false,
-                            const KnnPanelTune& tune = KnnPanelTune{});
 // half sweep: the device arrays the sweep and the select share
 struct KnnPanelSymDev {
   void* bucket_ent;      // uint2 [npad / 32][bucket_cap]

@@ -32,7 +32,7 @@ using f32x16 = __attribute__((ext_vector_type(16))) float;
 using half8 = __attribute__((ext_vector_type(8))) _Float16;
 
 constexpr float NEG = -3.0e38f;
-constexpr int BM = 128, BN = 128, BK = 32, LDT = 36;
+constexpr int BM = KNN_BM, BN = KNN_BN, BK = 32, LDT = 36;  // (knn_plan.hpp: knn_plan splits by these tiles)
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
@@ -1326,46 +1326,6 @@ void launch_rows_cosine(const float* A, int32_t ld, const float* q, float* out, 
 void launch_rows_dot(const float* Yn, int32_t ldn, const float* q, float* out, int64_t N, int32_t D, hipStream_t s) {
   hipLaunchKernelGGL(k_rows_dot, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, Yn, ldn, q, out, N, D);
   HIP_CHECK(hipGetLastError());
-}
-
-KnnPlan knn_plan(int32_t N, int32_t keep, int32_t slots, int rb_begin, int rb_count, bool f16, int splits_override) {
-  KnnPlan p{};
-  p.keep = keep;
-  p.E = (keep + 31) / 32;
-  if (p.E == 3 && !f16) p.E = 4;  // exact variants: 1, 2 and the wide one
-  p.KC = 32 * p.E;
-  p.f16 = f16;
-  p.qrows = nullptr;
-  p.nq = 0;
-  const int all_blocks = (N + BM - 1) / BM;
-  p.rb_begin = rb_begin;
-  p.rb_count = rb_count < 0 ? all_blocks : rb_count;
-  p.row_blocks = std::max(1, p.rb_count);
-  const int col_tiles = (N + BN - 1) / BN;
-  // choose the column split count S: enough work items to balance `slots` resident blocks, while keeping
-  // the per-item list warm-up (k log) small.
-  int best_S = 1;
-  double best_cost = 1e300;
-  // a handful of row blocks (the per-row exact fallback of the prefilter routes): up to 64 splits, so that the sweep
-  // of one 128-row block is spread over 64 workgroups instead of 16 (3.5 -> 0.9 ms at N = 100k)
-  // (bounded by the merge's candidate count S x KC <= 2048: its rank-select is quadratic in it)
-  const int max_S = (!f16 && p.row_blocks * 16 < slots / 2) ? std::max(16, std::min(64, 2048 / p.KC)) : 16;
-  for (int S = 1; S <= std::min(col_tiles, max_S); ++S) {
-    const int tiles_per = (col_tiles + S - 1) / S;
-    const int S_eff = (col_tiles + tiles_per - 1) / tiles_per;
-    if (S_eff != S) continue;
-    const long items = (long)p.row_blocks * S;
-    const long rounds = (items + slots - 1) / slots;
-    const double cost = (double)rounds * tiles_per * (1.0 + (f16 ? 0.12 : 0.004) * S);  // imbalance x warm-up overhead
-    if (cost < best_cost) {
-      best_cost = cost;
-      best_S = S;
-    }
-  }
-  if (splits_override > 0) best_S = std::max(1, std::min(col_tiles, splits_override));
-  p.S = best_S;
-  p.cols_per_split = ((col_tiles + p.S - 1) / p.S) * BN;
-  return p;
 }
 
 void launch_to_f16(const float* Yn, int32_t ldn, void* Yh, int32_t ldh, int64_t N, int32_t D, hipStream_t s) {

@@ -47,30 +47,27 @@ void read_env_build(L& h) {
   int v = 0;
   if (num("OSC_REORDER", v)) h.reorder = v != 0 ? 1 : 0;
   else h.reorder = -1;
-  h.knn_mode = 0;
-  if (const char* e = getenv("OSC_KNN_MODE")) h.knn_mode = !strcmp(e, "exact") ? 1 : !strcmp(e, "prefilter") ? 2 : !strcmp(e, "panel") ? 3 : 0;
-  h.knn_fake_shards = 0;
-  if (num("OSC_KNN_FAKE_SHARDS", v)) h.knn_fake_shards = std::max(0, v);
-  h.knn_splits = 0;
-  if (num("OSC_KNN_SPLITS", v)) h.knn_splits = std::max(1, v);
-  h.knn_scatter = !(num("OSC_KNN_PANEL_SCATTER", v) && v == 0);
-  h.knn_sym = !(num("OSC_KNN_PANEL_SYM", v) && v == 0);
-  h.create_stream = !(num("OSC_CREATE_STREAM", v) && v == 0);
+  KnnBuildInputs& kb = h.knn_env;  // (the kNN planner's inputs the switches set; the rest is filled per build: osc_graph.hip)
+  kb = KnnBuildInputs{};
+  if (const char* e = getenv("OSC_KNN_MODE")) kb.mode = !strcmp(e, "exact") ? 1 : !strcmp(e, "prefilter") ? 2 : !strcmp(e, "panel") ? 3 : 0;
+  if (num("OSC_KNN_FAKE_SHARDS", v)) kb.fake_shards = std::max(0, v);
+  if (num("OSC_KNN_SPLITS", v)) kb.splits = std::max(1, v);
+  kb.scatter = !(num("OSC_KNN_PANEL_SCATTER", v) && v == 0);
+  kb.sym = !(num("OSC_KNN_PANEL_SYM", v) && v == 0);
+  kb.create_stream = !(num("OSC_CREATE_STREAM", v) && v == 0);
   h.create_force_retry = num("OSC_CREATE_FORCE_RETRY", v) && v != 0;
-  h.create_min_mb = num("OSC_CREATE_MIN_MB", v) ? std::max(1, v) : 64;
-  h.create_two_mb = num("OSC_CREATE_TWO_PIECE_MB", v) ? std::max(1, v) : 256;
-  h.create_piece_mb_set = num("OSC_CREATE_PIECE_MB", v);
-  h.create_piece_mb = h.create_piece_mb_set ? std::max(1, std::min(v, 1024)) : 24;
-  h.knn_tune = KnnPanelTune{};
-  h.knn_rescore_pair = num("OSC_KNN_RESCORE_PAIR", v) ? std::max(0, std::min(v, 2)) : 1;
-  if (num("OSC_KNN_PANEL_NRG", v)) h.knn_tune.nrg = v;
-  if (const char* e = getenv("OSC_KNN_PANEL_RHO")) h.knn_tune.rho = atof(e);
-  if (num("OSC_KNN_PANEL_T", v)) h.knn_tune.T = v;
-  if (num("OSC_KNN_PANEL_RANK", v)) h.knn_tune.rank = v;
-  if (num("OSC_KNN_PANEL_SA", v)) h.knn_tune.sa = v;
-  if (num("OSC_KNN_TILE_WIDE", v)) h.knn_tune.tile_wide = v != 0 ? 1 : 0;
-  if (num("OSC_KNN_TILE_GROUP_MB", v)) h.knn_tune.tile_group_mb = v;
-  h.knn_force_exchange = num("OSC_KNN_FORCE_EXCHANGE", v) && v != 0;
+  kb.create_min_mb = num("OSC_CREATE_MIN_MB", v) ? std::max(1, v) : 64;
+  kb.create_two_mb = num("OSC_CREATE_TWO_PIECE_MB", v) ? std::max(1, v) : 256;
+  kb.create_piece_mb_set = num("OSC_CREATE_PIECE_MB", v);
+  kb.create_piece_mb = kb.create_piece_mb_set ? std::max(1, std::min(v, 1024)) : 24;
+  kb.rescore_pair = num("OSC_KNN_RESCORE_PAIR", v) ? std::max(0, std::min(v, 2)) : 1;
+  if (num("OSC_KNN_PANEL_NRG", v)) kb.tune.nrg = v;
+  if (const char* e = getenv("OSC_KNN_PANEL_RHO")) kb.tune.rho = atof(e);
+  if (num("OSC_KNN_PANEL_T", v)) kb.tune.T = v;
+  if (num("OSC_KNN_PANEL_RANK", v)) kb.tune.rank = v;
+  if (num("OSC_KNN_PANEL_SA", v)) kb.tune.sa = v;
+  if (num("OSC_KNN_TILE_WIDE", v)) kb.tune.tile_wide = v != 0 ? 1 : 0;
+  kb.force_exchange = num("OSC_KNN_FORCE_EXCHANGE", v) && v != 0;
   h.bfs_host = num("OSC_BFS_HOST", v) && v != 0;
   h.halo_force = 0;
   if (const char* e = getenv("OSC_HALO")) h.halo_force = !strcmp(e, "full") ? 1 : !strcmp(e, "lists") ? 2 : 0;
@@ -277,7 +274,7 @@ int osc_graph_stats(osc_handle h, int64_t* nnz, int32_t* max_deg, double* build_
 
 int osc_build_info(osc_handle h, int32_t* prefilter, int32_t* fallback_rows, int64_t* small_solves) {
   return guarded(h, [&](L& l) {
-    if (prefilter) *prefilter = l.knn_prefilter ? (l.knn_panel ? 2 : 1) : 0;
+    if (prefilter) *prefilter = l.knn_last.prefilter() ? (l.knn_last.route == KnnRoute::panel ? 2 : 1) : 0;
     if (fallback_rows) *fallback_rows = l.knn_fallback_rows;
     if (small_solves) *small_solves = l.small_solves;
   });
@@ -1273,7 +1270,7 @@ int osc_profile_reset(osc_handle h) {
 int osc_profile_get(osc_handle h, int32_t which, int64_t* launches, double* total_ms) {
   return guarded(h, [&](L& l) {
     if (which == 16) {  // main sweep of the last build's prefilter: 0 none, 1 full (per rank), 2 half (one per build)
-      if (launches) *launches = l.knn_sweep;
+      if (launches) *launches = l.knn_last.sweep();
       if (total_ms) *total_ms = 0.0;
       return;
     }

@@ -500,22 +500,298 @@ void build_graph(L& h, const float* host_Y) {
   h.build_ms = now_ms() - t0;
 }
 
+// the caller's anchors (osc_create) to the device, whole, and U = Y
+static void upload_anchors(L& h, const float*& host_Y) {
+  if (host_Y == nullptr) return;
+  upload_rows(h, h.Y.p, host_Y);
+  HIP_CHECK(hipMemcpyAsync(h.U.p, h.Y.p, (size_t)h.N * h.ld * 4, hipMemcpyDeviceToDevice, h.stream));
+  host_Y = nullptr;
+}
+
+// The route of a build (knn_plan.hpp: plan_knn_build) from the handle's switches and the device
+static KnnBuildPlan knn_build_plan(const L& h, bool host_anchors) {
+  hipDeviceProp_t prop;
+  HIP_CHECK(hipGetDeviceProperties(&prop, h.device));
+  KnnBuildInputs in = h.knn_env;  // the OSC_KNN_* / OSC_CREATE_* switches (read_env_build)
+  size_t mem_total = 0;
+  HIP_CHECK(hipMemGetInfo(&in.mem_free, &mem_total));
+  in.N = (int32_t)h.N;
+  in.D = h.D;
+  in.k = h.k_eff;
+  in.world = h.world;
+  in.comm = h.comm != nullptr;
+  in.cus = prop.multiProcessorCount;
+  in.host_anchors = host_anchors;
+  in.ld_is_D = h.ld == h.D;
+  in.stage_bytes = kStageBytes;
+  return plan_knn_build(in);
+}
+
+// The device buffers of one build: they live until its end (a buffer given back to the pool waits for the stream)
+struct KnnWork {
+  const KnnBuildPlan& plan;
+  int32_t ldn, ldh;  // pitches of the unit rows (fp32) and of the tile prefilter's fp16 image (halfs)
+  float delta;       // worst-case |fp16-path score - exact score| of unit rows
+  DevBuf<float> Yn, Yh;  // unit rows; the tile prefilter's fp16 image, viewed as float slots
+  DevBuf<float> cval, cand_val, pair_sc;  // prefilter candidates; the exact pass's; the re-scoring's pair scratch
+  DevBuf<int32_t> cidx, cand_idx, pair_pos, fail_rows, fail_count;
+  DevBuf<float> p_img, p_smp, p_tmax, p_tau;  // panel: query image, sample image, tile maxima, thresholds
+  DevBuf<unsigned long long> p_hits;          // ... hit lists or buckets
+  DevBuf<int32_t> p_hcnt;
+  DevBuf<unsigned> p_queue;
+  DevBuf<float> smp_raw, smp_n;  // the streamed create's column sample: anchors as gathered, unit rows
+  KnnPanelSymDev sym{};
+  KnnWork(const KnnBuildPlan& p, int32_t D)
+      : plan(p), ldn(((D + 31) / 32) * 32), ldh(((D + 63) / 64) * 64), delta(9.8e-4f + 1.2e-7f * (float)D) {}
+};
+
+// the half sweep's buckets: one per group of 32 receiving rows, [bucket counts | chunk flags] zeroed
+static void alloc_buckets(L& h, KnnWork& w) {
+  const KnnPanelPlan& pp = w.plan.pp;
+  const size_t nb = (size_t)pp.npad / 32;
+  w.p_hits.alloc(nb * pp.bucket_cap);
+  w.p_hcnt.alloc(nb + (size_t)pp.S);
+  HIP_CHECK(hipMemsetAsync(w.p_hcnt.p, 0, (nb + (size_t)pp.S) * 4, h.stream));
+  w.sym = KnnPanelSymDev{w.p_hits.p, w.p_hcnt.p, w.p_hcnt.p + nb};
+}
+
+// the thresholds' sample sweep of row blocks [rb_begin, rb_begin + rb_count)
+static void sample_sweep(L& h, KnnWork& w, int rb_begin, int rb_count) {
+  const KnnPanelPlan& pp = w.plan.pp;
+  const int nsets = (rb_count + pp.nrg_s - 1) / pp.nrg_s;  // (work items per column split of the SAMPLE sweep)
+  launch_panel_tilemax(w.p_img.p, w.p_smp.p, pp, (int32_t)h.N, rb_begin, rb_count, w.p_tmax.p, w.p_queue.p,
+                       std::max(1, std::min(w.plan.cus, nsets * pp.SA)), h.stream);
+}
+
+// The exact pass: similarity tiles (fp32, or the tile prefilter's fp16 image) with running lists per column split, then the
+// merge of the splits into the k_out best (`clear`: out_idx first set to -1).  The exact route, the tile prefilter and the
+// fallback rows of both prefilters.
+static void exact_pass(L& h, KnnWork& w, const KnnPlan& plan, const float* Yop, int32_t ld, int32_t k_out, float* out_val,
+                       int32_t* out_idx, int clip, bool timed, bool clear) {
+  const size_t ncand = (size_t)h.N * plan.S * plan.KC;
+  w.cand_val.alloc(ncand);
+  w.cand_idx.alloc(ncand);
+  if (timed) {
+    ProfScope ps(h, 3);
+    launch_knn_topk(plan, Yop, ld, (int32_t)h.N, w.cand_val.p, w.cand_idx.p, h.stream);
+  } else {
+    launch_knn_topk(plan, Yop, ld, (int32_t)h.N, w.cand_val.p, w.cand_idx.p, h.stream);
+  }
+  if (clear) HIP_CHECK(hipMemsetAsync(out_idx, 0xFF, (size_t)h.N * k_out * 4, h.stream));
+  launch_knn_merge(plan, w.cand_val.p, w.cand_idx.p, (int32_t)h.N, k_out, out_val, out_idx, clip, h.stream);
+}
+
+// Unit rows, and the images and candidate arrays of the route; the anchors go to the device first unless the streamed
+// create brings them piece by piece (stream_pieces)
+static void prepare_rows(L& h, KnnWork& w, const float*& host_Y) {
+  const KnnBuildPlan& plan = w.plan;
+  const KnnPanelPlan& pp = plan.pp;
+  const int32_t N = (int32_t)h.N;
+  const bool panel = plan.route == KnnRoute::panel;
+  if (panel) {
+    w.p_img.alloc((size_t)(pp.npad + 128) * pp.ldh / 2);  // (+ one zero tile: k_tile_thr2 sweeps row blocks and column tiles in pairs)
+    HIP_CHECK(hipMemsetAsync(w.p_img.p + (size_t)pp.npad * pp.ldh / 2, 0, (size_t)128 * pp.ldh * 2, h.stream));
+    w.p_smp.alloc((size_t)pp.sample_tiles * 128 * pp.ldh / 2);
+    w.p_tmax.alloc((size_t)pp.npad * pp.sample_groups);
+    w.p_tau.alloc(std::max((size_t)pp.npad, (size_t)plan.rb_per * 128 * plan.parts));  // (whole equal chunks for the all-gather of a sharded half sweep)
+    w.p_queue.alloc(64);  // (one counter per launch in flight: the streamed create runs consecutive pieces on two streams)
+  }
+  if (!plan.streamed()) {
+    upload_anchors(h, host_Y);
+    launch_normalize_rows(h.Y.p, h.ld, w.Yn.p, w.ldn, h.N, h.D, h.stream);
+    if (panel) {
+      launch_panel_image(w.Yn.p, w.ldn, w.p_img.p, pp, N, h.D, h.stream);
+      launch_panel_sample(w.p_img.p, w.p_smp.p, pp, N, h.stream);
+    }
+  }
+  if (!plan.prefilter()) return;
+  if (!panel) {
+    w.Yh.alloc((size_t)h.N * w.ldh / 2);
+    launch_to_f16(w.Yn.p, w.ldn, w.Yh.p, w.ldh, h.N, h.D, h.stream);
+  }
+  w.cval.alloc((size_t)h.N * plan.keep);
+  w.cidx.alloc((size_t)h.N * plan.keep);
+  w.fail_rows.alloc((size_t)h.N);
+  w.fail_count.alloc(1);
+  HIP_CHECK(hipMemsetAsync(w.fail_count.p, 0, 4, h.stream));
+}
+
+// a sharded build runs only its own rank's part; a single process all of them (OSC_KNN_FAKE_SHARDS: one after another)
+static bool runs_part(const L& h, const KnnBuildPlan& plan, int part) { return !plan.sharded || part == h.rank; }
+
+// Half sweep of a sharded build (graph.py:35-65 cut over the ranks): thresholds of a rank's own row blocks, all-gathered;
+// then ONE sweep of the tiles J >= I whose work items the ranks take in turn (item = rank, rank + parts, ...: items of a
+// chunk stay neighbours), every rank delivering into buckets of ALL rows; then the entries of each rank's own rows travel
+// to it (exchange_buckets).  OSC_KNN_FAKE_SHARDS runs the ranks' passes one after another into the same buckets.
+static void sweep_half_sharded(L& h, KnnWork& w) {
+  const KnnBuildPlan& plan = w.plan;
+  const KnnPanelPlan& pp = plan.pp;
+  ProfScope ps(h, 3);
+  for (int part = 0; part < plan.parts; ++part)
+    if (runs_part(h, plan, part)) sample_sweep(h, w, plan.rb_begin(part), plan.rb_count(part));
+  launch_panel_tau(w.p_tmax.p, pp, (int32_t)h.N, w.p_tau.p, h.stream);  // (rows of other ranks' blocks: overwritten by the all-gather)
+  if (plan.exchange) h.comm->allgather(w.p_tau.p, (size_t)plan.rb_per * 128 * 4, h.stream);
+  alloc_buckets(h, w);
+  const int sgrid = std::max(1, std::min(plan.cus, (pp.nitems + plan.parts - 1) / plan.parts));
+  for (int part = 0; part < plan.parts; ++part)
+    if (runs_part(h, plan, part))
+      launch_panel_filter(w.p_img.p, pp, (int32_t)h.N, 0, pp.nrb, w.p_tau.p, w.p_hits.p, w.p_hcnt.p, w.p_queue.p, sgrid, h.stream,
+                          &w.sym, part, plan.parts);
+  if (plan.exchange) exchange_buckets(h, pp, w.sym, plan.rb_per);
+}
+
+// the panel route's lists of one part: thresholds and hits (unless the streamed create or the sharded half sweep ran them),
+// the select, the exact re-scoring
+static void sweep_panel(L& h, KnnWork& w, int rb_begin, int rb_count, const float*& host_Y) {
+  const KnnBuildPlan& plan = w.plan;
+  const KnnPanelPlan& pp = plan.pp;
+  const int32_t N = (int32_t)h.N;
+  if (plan.streamed()) {
+    ProfScope ps(h, 3);
+    alloc_buckets(h, w);
+    stream_pieces(h, host_Y, plan.piece_starts, pp, w.Yn.p, w.ldn, w.p_img.p, w.p_smp.p, w.p_tmax.p, w.p_tau.p, w.p_queue.p, w.sym,
+                  plan.cus, w.smp_raw, w.smp_n);
+    host_Y = nullptr;
+  } else if (!plan.sym_sharded) {
+    ProfScope ps(h, 3);
+    sample_sweep(h, w, rb_begin, rb_count);
+    launch_panel_tau(w.p_tmax.p, pp, N, w.p_tau.p, h.stream);
+    if (pp.sym) {
+      alloc_buckets(h, w);
+      const int sgrid = std::max(1, std::min(plan.cus, pp.nitems));
+      launch_panel_filter(w.p_img.p, pp, N, rb_begin, rb_count, w.p_tau.p, w.p_hits.p, w.p_hcnt.p, w.p_queue.p, sgrid, h.stream, &w.sym);
+    } else {
+      const int nsets = (rb_count + pp.nrg - 1) / pp.nrg;  // work items per column split (knn_gemm.hip)
+      w.p_hits.alloc((size_t)rb_count * pp.S * 4 * pp.hit_cap);  // one list per (work item, wave)
+      w.p_hcnt.alloc((size_t)rb_count * pp.S * 4);
+      launch_panel_filter(w.p_img.p, pp, N, rb_begin, rb_count, w.p_tau.p, w.p_hits.p, w.p_hcnt.p, w.p_queue.p,
+                          std::max(1, std::min(plan.cus, nsets * pp.S)), h.stream);
+    }
+  }
+  launch_panel_select(pp, rb_begin, rb_count, N, w.p_hits.p, w.p_hcnt.p, w.cval.p, w.cidx.p, w.fail_rows.p, w.fail_count.p,
+                      h.stream, pp.sym ? &w.sym : nullptr);
+  if (plan.rescore_pair) {
+    w.pair_sc.alloc((size_t)N * plan.keep);
+    w.pair_pos.alloc((size_t)N * plan.keep);
+  }
+  const KnnPlan kp = knn_plan(N, plan.keep, plan.slots, rb_begin, rb_count, true, plan.splits);  // row range + keep for the re-scoring
+  launch_knn_rescore(kp, w.Yn.p, w.ldn, h.D, N, w.cidx.p, w.cval.p, plan.k, w.delta, h.knn_val.p, h.knn_idx.p, w.fail_rows.p,
+                     w.fail_count.p, h.stream, pp.scatter != 1 ? &pp.map : nullptr, w.pair_sc.p, w.pair_pos.p);
+}
+
+// the top-k lists of one part's row blocks, by the plan's route
+static void sweep_part(L& h, KnnWork& w, int part, const float*& host_Y) {
+  const KnnBuildPlan& plan = w.plan;
+  const int32_t N = (int32_t)h.N, k = plan.k;
+  const int rb_begin = plan.rb_begin(part), rb_count = plan.rb_count(part);
+  switch (plan.route) {
+    case KnnRoute::any_k: {  // chunks of up to ~1 GiB of similarity rows (multiple of 128 rows)
+      const int32_t ldS = ((N + 31) / 32) * 32;
+      const int64_t cap_rows = std::max<int64_t>(128, (((int64_t)1 << 28) / ldS) / 128 * 128);
+      const int32_t row_lo = rb_begin * 128, row_hi = std::min(N, (rb_begin + rb_count) * 128);
+      const int32_t chunk = (int32_t)std::min<int64_t>(cap_rows, ((row_hi - row_lo + 127) / 128) * 128);
+      if (row_hi > row_lo) {
+        DevBuf<float> Sm;
+        Sm.alloc((size_t)chunk * ldS);
+        ProfScope ps(h, 3);
+        for (int32_t r = row_lo; r < row_hi; r += chunk)
+          launch_knn_rows_any(w.Yn.p, w.ldn, N, k, r, std::min(chunk, row_hi - r), Sm.p, ldS, h.knn_val.p, h.knn_idx.p, h.stream);
+        sync(h);  // Sm goes back to the pool at scope exit
+      }
+      break;
+    }
+    case KnnRoute::panel:
+      sweep_panel(h, w, rb_begin, rb_count, host_Y);
+      break;
+    case KnnRoute::tile: {
+      const KnnPlan kp = knn_plan(N, plan.keep, plan.slots, rb_begin, rb_count, true, plan.splits);
+      exact_pass(h, w, kp, w.Yh.p, w.ldh / 2, plan.keep, w.cval.p, w.cidx.p, 0, true, true);
+      launch_knn_rescore(kp, w.Yn.p, w.ldn, h.D, N, w.cidx.p, w.cval.p, k, w.delta, h.knn_val.p, h.knn_idx.p, w.fail_rows.p,
+                         w.fail_count.p, h.stream);
+      break;
+    }
+    case KnnRoute::dense: {  // dense S + per-row argmax selection
+      const int32_t ldS = ((N + 31) / 32) * 32;
+      DevBuf<float> Sm;
+      Sm.alloc((size_t)N * ldS);
+      ProfScope ps(h, 3);
+      launch_knn_dense(w.Yn.p, w.ldn, N, k, Sm.p, ldS, h.knn_val.p, h.knn_idx.p, h.stream);
+      sync(h);  // Sm goes back to the pool at scope exit
+      break;
+    }
+    case KnnRoute::exact:
+      exact_pass(h, w, knn_plan(N, k, plan.slots, rb_begin, rb_count, false, plan.splits), w.Yn.p, w.ldn, k, h.knn_val.p,
+                 h.knn_idx.p, 1, true, false);
+      break;
+  }
+}
+
+// The prefilter routes' rows the re-scoring could not prove: (half sweep) a second proof from the rows' whole buckets, then
+// the exact lists of what is left.  false: a streamed build gives up instead (see build_graph).
+static bool prove_fallback_rows(L& h, KnnWork& w) {
+  const KnnBuildPlan& plan = w.plan;
+  const int32_t N = (int32_t)h.N, k = plan.k;
+  int32_t nfail = 0;
+  HIP_CHECK(hipMemcpyAsync(&nfail, w.fail_count.p, 4, hipMemcpyDeviceToHost, h.stream));
+  sync(h);
+  DevBuf<int32_t> fail_rows2, fail_count2;
+  int32_t* fail_list = w.fail_rows.p;
+  if (plan.route == KnnRoute::panel && plan.pp.sym && nfail > 0) {  // (knn_gemm.hip: k_bucket_rescore)
+    fail_rows2.alloc((size_t)nfail);
+    fail_count2.alloc(1);
+    HIP_CHECK(hipMemsetAsync(fail_count2.p, 0, 4, h.stream));
+    launch_bucket_rescore(plan.pp, w.sym, w.Yn.p, w.ldn, N, w.fail_rows.p, nfail, w.p_tau.p, k, w.delta, h.knn_val.p, h.knn_idx.p,
+                          fail_rows2.p, fail_count2.p, h.stream);
+    HIP_CHECK(hipMemcpyAsync(&nfail, fail_count2.p, 4, hipMemcpyDeviceToHost, h.stream));
+    sync(h);
+    fail_list = fail_rows2.p;
+  }
+  h.knn_fallback_rows = nfail;
+  // (OSC_CREATE_FORCE_RETRY: test hook -- every streamed build gives up here)
+  if (plan.streamed() && (nfail > std::max(64, N / 256) || h.create_force_retry)) return false;
+  bool few_done = false;
+  if (nfail > 0 && nfail <= 32) {  // a handful of rows: stream the columns once, select per row (0.15 vs 3.9 ms at N = 100k)
+    const int32_t ldS = ((N + 31) / 32) * 32;
+    DevBuf<float> Sm;
+    Sm.alloc((size_t)nfail * ldS);
+    few_done = launch_knn_few_rows(w.Yn.p, w.ldn, N, k, fail_list, nfail, Sm.p, ldS, h.knn_val.p, h.knn_idx.p, h.stream);
+    if (few_done) sync(h);  // Sm goes back to the pool at scope exit
+  }
+  if (nfail > 0 && !few_done) {  // redo the unproven rows with the exact kernel (ties / dense clusters of near-equal scores)
+    KnnPlan kp = knn_plan(N, k, plan.slots, 0, (nfail + 127) / 128, false, plan.splits);
+    kp.qrows = fail_list;
+    kp.nq = nfail;
+    exact_pass(h, w, kp, w.Yn.p, w.ldn, k, h.knn_val.p, h.knn_idx.p, 1, false, false);
+  }
+  return true;
+}
+
+// every rank's share of the lists to every rank
+static void assemble_lists(L& h, const KnnBuildPlan& plan) {
+  if (!plan.sharded) return;
+  if (plan.route == KnnRoute::panel && plan.pp.scatter != 1) {
+    // a rank's rows are spread over the lattice (image row blocks): every row has exactly one writer, the others hold the
+    // initial pattern (0.0f / -1), so a sum of the similarities and a max of the indices assemble the lists exactly
+    const size_t cnt = (size_t)h.N * plan.k;
+    h.comm->allreduce(h.knn_val.p, cnt, COMM_F32, COMM_SUM, h.stream);
+    h.comm->allreduce(h.knn_idx.p, cnt, COMM_I32, COMM_MAX, h.stream);
+  } else {
+    const size_t cnt = (size_t)plan.rb_per * 128 * plan.k;  // equal chunk per rank, in place
+    h.comm->allgather(h.knn_val.p, cnt * 4, h.stream);
+    h.comm->allgather(h.knn_idx.p, cnt * 4, h.stream);
+  }
+}
+
 // false: a streamed build gave up before its exact-kernel fallback (see build_graph); Y and U are on the device then
 static bool build_graph_once(L& h, const float* host_Y) {
   const double t0 = now_ms();
   h.create_pieces = 0;
-  auto upload_all = [&] {
-    if (host_Y == nullptr) return;
-    upload_rows(h, h.Y.p, host_Y);
-    HIP_CHECK(hipMemcpyAsync(h.U.p, h.Y.p, (size_t)h.N * h.ld * 4, hipMemcpyDeviceToDevice, h.stream));
-    host_Y = nullptr;
-  };
   drop_order(h);  // the build works on the API's row order
   const int32_t N = (int32_t)h.N;
   h.k_eff = std::min<int32_t>(h.k_eff, std::max<int32_t>(1, N - 1));  // lattice.py:60
   h.have_ustar = false;
   if (N <= 1) {  // graph.py:30-32
-    upload_all();
+    upload_anchors(h, host_Y);
     alloc_ell(h, 1);
     const float one_em6 = 1e-6f;  // sqrt(max(0, 1e-12))
     std::vector<float> sd((size_t)h.N, one_em6);
@@ -528,389 +804,23 @@ static bool build_graph_once(L& h, const float* host_Y) {
     h.build_ms = now_ms() - t0;
     return true;
   }
-  const int32_t k = h.k_eff;
-  // k <= 128: register-resident streaming lists (exact / prefilter / small-dense routes below).  Larger k (the
-  // reference takes any k <= N - 1, lattice.py:60): dense similarity rows in chunks + a radix select per row.
-  const bool any_k = k > 128;
-  const int32_t ldn = ((h.D + 31) / 32) * 32;
-  DevBuf<float> Yn;
-  Yn.alloc((size_t)h.N * ldn);
-  hipDeviceProp_t prop;
-  HIP_CHECK(hipGetDeviceProperties(&prop, h.device));
-  const int slots = prop.multiProcessorCount * (k <= 64 ? 2 : 1);
-  // multi-GPU: row-block-sharded build -- this rank computes the top-k lists of its 128-row blocks against all
-  // columns, then one all-gather of the (idx, sim) lists; mutual test / cap / Laplacian weights run on every rank.
-  const int all_rb = (N + 127) / 128;
-  // OSC_KNN_FAKE_SHARDS=G (test hook): run the G per-rank passes of a sharded build one after another on this GPU
-  const int fake = h.knn_fake_shards;
-  const bool sharded = h.comm != nullptr && h.world > 1;
-  const int parts = sharded ? h.world : (fake > 1 ? fake : 1);
-  const int rb_per = (all_rb + parts - 1) / parts;
-  const size_t list_rows = parts > 1 ? (size_t)rb_per * 128 * parts : (size_t)h.N;
-  h.knn_val.alloc(list_rows * k);
-  h.knn_idx.alloc(list_rows * k);
-  h.knn_k = k;
-  HIP_CHECK(hipMemsetAsync(h.knn_val.p, 0, list_rows * k * 4, h.stream));
-  HIP_CHECK(hipMemsetAsync(h.knn_idx.p, 0xFF, list_rows * k * 4, h.stream));
-  // Two ways to the per-row top-k lists (identical results):
-  //  exact     : fp32 MFMA similarity tiles + running top-k.
-  //  prefilter : fp16 MFMA tiles keep the best KC >= k+16 candidates per row, exact fp32 re-scoring picks the k;
-  //              a row is accepted only if the worst-case fp16 error bound proves no left-out column can belong
-  //              to its top-k, otherwise the row is redone by the exact kernel.
-  // kept candidates per row: k plus a margin; rows whose margin turns out too thin are redone exactly
-  const int keep_f = std::min(96, k + std::max(12, k / 2));
-  constexpr bool dense_small = true;
-  constexpr int dense_max = 8192;
-  // small lattices go through the dense similarity matrix (below) unless the panel route takes them; beyond that the fp16
-  // prefilter pays
-  bool prefilter = (keep_f >= k + 8) && N >= 4096;
-  // OSC_KNN_MODE = exact | prefilter | panel: force one route (tests, A/B)
-  if (h.knn_mode == 1) prefilter = false;
-  if (h.knn_mode == 2) prefilter = (keep_f >= k + 8);
-  if (any_k) prefilter = false;
-  // The prefilter's GEMM has two shapes: "panel" (knn_gemm.hip: query panel in registers, thresholds from a column
-  // sample, hits appended -- D <= 768 and enough row blocks for the sample) and the older 128 x 128 tile with
-  // register-resident sorted lists (k_knn_pref), which serves everything else.
-  // Where the panel route starts.  Until round 6: behind the dense route, at 8193 rows.  With that round's lighter small kernels
-  // (threshold kernel, select, re-scoring tail, row kernels) it is ahead of the dense route from its own lower limit of 6144
-  // rows on wide rows (scripts/exp/r06/route_crossover.py, build in ms, dense / panel: 6144 x 768 k 32 0.83 / 0.63, 8192 x 768
-  // 1.45 / 0.77, 6144 x 1536 1.33 / 0.73, 8192 x 1536 2.34 / 0.83; 7000 x 384 k 16 0.61 / 0.55, 8192 x 384 0.82 / 0.69, but 6144 x
-  // 384 0.48 / 0.55 and 8192 x 128 0.53 / 0.62): from 6144 rows at >= 512 columns, 7168 at >= 320, 8193 below.  (Sharded builds
-  // have no dense route and keep their tile prefilter up to 8192 rows.)
-  const int panel_min = parts == 1 && h.knn_mode == 0 ? (h.D >= 512 ? 6144 : h.D >= 320 ? 7168 : 8193) : 8193;
-  // (a hit entry packs the column index into 25 bits, next to its two side flags)
-  // (D > 768: the same route on the tile core, k_tile_thr -- half sweep only, so single-process builds only)
-  // (round 5: the half sweep also under sharding -- the ranks split the work ITEMS of the one sweep and exchange the hits of
-  // each other's rows, below -- so a sharded build issues the single-GPU build's MFMA work, not twice it, and D > 768 keeps
-  // the threshold route instead of falling back to the list-maintaining tile prefilter)
-  bool sym_ok = h.knn_sym;
-  if (sym_ok && prefilter && N >= panel_min && N < (1 << 25)) {
-    // The half sweep delivers every hit to a bucket per 32 receiving rows: (npad / 32) x bucket_cap entries of 8 bytes --
-    // 2.9 GB of temporaries at N = 1M (config 4), growing with N x the threshold sample's hit bound (the full sweep's
-    // lists: 0.2-0.5 GB).  Beyond a budget, or where the device cannot spare it, the build takes the full sweep (D <= 768)
-    // or the tile prefilter (D > 768) instead of failing in the allocator.
-    const KnnPanelPlan sp = knn_panel_plan(N, h.D, keep_f, prop.multiProcessorCount, false, true, h.knn_tune);
-    const double bucket_bytes = (double)(sp.npad / 32) * (double)sp.bucket_cap * 8.0;
-    size_t mem_free = 0, mem_total = 0;
-    HIP_CHECK(hipMemGetInfo(&mem_free, &mem_total));
-    constexpr double kSymBucketBudget = 12.0 * 1024 * 1024 * 1024;
-    if (sp.ok && (bucket_bytes > kSymBucketBudget || bucket_bytes > 0.5 * (double)mem_free)) sym_ok = false;
-  }
-  const bool depth_ok = knn_panel_nkt(h.D) != 0 || (sym_ok && knn_tile_nkt(h.D) != 0);
-  bool panel = prefilter && depth_ok && N >= panel_min && N < (1 << 25) &&
-               knn_panel_plan(N, h.D, keep_f, prop.multiProcessorCount, false, sym_ok, h.knn_tune).ok;
-  if (h.knn_mode == 0 && dense_small && parts == 1 && N <= dense_max && !panel) prefilter = false;  // the dense route (below)
-  if (h.knn_mode == 3) panel = prefilter = (keep_f >= k + 8) && !any_k && depth_ok && N >= 6144 && N < (1 << 25);
-  if (h.knn_mode == 2) panel = false;
-  h.knn_panel = panel;
-  h.knn_sweep = 0;
-  DevBuf<float> cand_val, cval, pair_sc;  // (pair_sc / pair_pos: the re-scoring's scratch where it scores every undirected pair once)
-  DevBuf<int32_t> pair_pos;
-  DevBuf<int32_t> cand_idx, cidx, fail_rows, fail_count;
-  DevBuf<float> Yh;  // fp16 image, viewed as float slots
-  const int32_t ldh = ((h.D + 63) / 64) * 64;
+  h.knn_last = knn_build_plan(h, host_Y != nullptr);
+  const KnnBuildPlan& plan = h.knn_last;
   h.knn_fallback_rows = 0;
-  h.knn_prefilter = prefilter;
-  KnnPanelPlan pp{};
-  DevBuf<float> p_img, p_smp, p_tmax, p_tau;
-  DevBuf<unsigned long long> p_hits;
-  DevBuf<int32_t> p_hcnt;
-  DevBuf<unsigned> p_queue;
-  KnnPanelSymDev sym_dev{};
-  std::vector<int32_t> piece_starts;  // not empty: the streamed create (below); first image row of each piece
-  DevBuf<float> smp_raw, smp_n;  // ... its column sample: anchors as gathered, unit rows
-  if (panel) {
-    // (image rows scattered over the lattice rows in single-process builds: knn_gemm.hpp, KnnPanelPlan::scatter)
-    // single-process builds sweep only the column tiles J >= I of every row block (knn_gemm.hip: symmetric half sweep);
-    // a sharded build's ranks own row blocks and would have to exchange the column-side hits, so they keep the full sweep
-    // (OSC_KNN_PANEL_SCATTER=0 / OSC_KNN_PANEL_SYM=0: A/B and tests)
-    // (round 5: the row scatter also under a SHARED half sweep -- a rank then owns image row blocks, i.e. lattice rows spread
-    // over the whole lattice, and the ranks' lists are combined by sums instead of an all-gather, below)
-    pp = knn_panel_plan(N, h.D, keep_f, prop.multiProcessorCount, h.knn_scatter && (parts == 1 || sym_ok), sym_ok, h.knn_tune);
-    h.knn_sweep = pp.sym ? 2 : 1;
-    p_img.alloc((size_t)(pp.npad + 128) * pp.ldh / 2);  // (+ one zero tile: k_tile_thr2 sweeps row blocks and column tiles in pairs)
-    HIP_CHECK(hipMemsetAsync(p_img.p + (size_t)pp.npad * pp.ldh / 2, 0, (size_t)128 * pp.ldh * 2, h.stream));
-    p_smp.alloc((size_t)pp.sample_tiles * 128 * pp.ldh / 2);
-    p_tmax.alloc((size_t)pp.npad * pp.sample_groups);
-    p_tau.alloc(std::max((size_t)pp.npad, (size_t)rb_per * 128 * parts));  // (whole equal chunks for the all-gather of a sharded half sweep)
-    p_queue.alloc(64);  // (one counter per launch in flight: the streamed create runs consecutive pieces on two streams)
-    // Anchors still on the host (osc_create) and the half sweep on the panel core ahead: cut the image into equal pieces of
-    // whole column chunks, >= 24 MB of anchors each and at most 16 of them, each permuted within itself
-    // (knn_panel_set_pieces) -- the sweep's chunk c needs the image rows below (c + 1) T 128 and nothing else, i.e. the
-    // pieces up to its own.  (Schedules tried at config 3 / 200k x 384 clustered, create in ms: 11 equal pieces 16.5 / 28.6;
-    // 1, 1, 2, 2, 3, 4, 6, 8 chunks 16.7 / 30.3 -- the kernels run dry while the last large pieces travel --; 1, 1, 2, 2 then
-    // threes 16.7 / 32.3 -- sixteen short sample sweeps fill the CUs badly.  From the third piece on the kernels are the
-    // slower side, so nothing is gained by small first pieces either.)
-    if (host_Y != nullptr && h.create_stream && parts == 1 && h.comm == nullptr && pp.sym && (!pp.tile_core || pp.tile_wide) && h.ld == h.D) {
-      const int64_t row_bytes = (int64_t)h.D * 4, chunk_rows = (int64_t)pp.T * 128;
-      const int64_t smp_bytes = (int64_t)pp.sample_tiles * 128 * row_bytes;
-      int64_t m = std::max<int64_t>(1, (((int64_t)h.create_piece_mb << 20) / row_bytes + chunk_rows - 1) / chunk_rows);
-      m = std::max<int64_t>(m, (pp.S + 15) / 16);
-      // A piece's rows are permuted among themselves only, so the hits of anchors that arrive group by group -- up to the
-      // threshold's bound per row, all of them inside the row's own piece -- spread over the piece's column tiles and no
-      // further; a wave's hit list takes 260 / NRG coarse entries from ONE tile (knn_gemm.hip: HB_CAP_SYM), i.e. 32 rows x
-      // bound / tiles must stay below that: pieces of >= 32 x bound rows leave a factor of two.  (An explicit
-      // OSC_CREATE_PIECE_MB overrides this: tests of the retry below.)
-      // (the wide tile core's lists are shorter and its wave tiles taller -- 64 rows, ~96 entries from one tile: 176 x bound rows;
-      // soak_streamed_create.py, 82 785 x 800, k = 16, grouped: pieces of 8192 rows overflowed and the build handed over)
-      // (two row groups at K depth 12 append per 64-column PASS: half a tile of entries at a time)
-      const double min_rows = pp.tile_core ? 176.0 * pp.hit_bound : 32.0 * pp.hit_bound * (pp.nkt == 12 && pp.nrg == 2 ? 1 : pp.nrg);
-      if (!h.create_piece_mb_set) m = std::max<int64_t>(m, ((int64_t)min_rows + chunk_rows - 1) / chunk_rows);
-      // (what is left over joins the last piece: a piece's rows are permuted among themselves only, so a short piece of
-      // anchors that arrive cluster by cluster packs each cluster into few tiles -- 3072 rows holding 7.7 clusters of 401 gave
-      // every row 17 cluster mates per column tile, more than a wave's hit list takes from one tile)
-      const int64_t rows = m * chunk_rows, pieces = N / rows;
-      // (two pieces from 256 MB of anchors on -- in practice the wide tile core's 176 x bound rows: the second half travels behind
-      // the first half's kernels.  Create, two pieces vs whole array (scripts/exp/r06/create_n.py, profiles/r06_two_piece.txt):
-      // config 5's 1.2 GB 98.9 vs 111.7 ms, 150 000 x 1152 k 56 48.0 vs 54.7, 132 000 x 800 k 48 30.8 vs 34.6; on the panel core
-      // 48 000 x 768 k 64 (147 MB) is a tie, 9.1-9.6 vs 9.4: three pieces stay the rule below)
-      const int64_t min_pieces = (int64_t)N * row_bytes >= ((int64_t)h.create_two_mb << 20) ? 2 : 3;
-      if (pieces >= min_pieces && (int64_t)N * row_bytes >= ((int64_t)h.create_min_mb << 20) && smp_bytes <= 8 * (int64_t)kStageBytes) {  // (up to eight fills of the two staging buffers: stream_pieces)
-        for (int64_t j = 0; j < pieces; ++j) piece_starts.push_back((int32_t)(j * rows));
-        knn_panel_set_pieces(pp, N, piece_starts.data(), (int)piece_starts.size());
-      }
-    }
-  }
-  const bool streamed = !piece_starts.empty();
-  if (!streamed) {
-    upload_all();
-    launch_normalize_rows(h.Y.p, h.ld, Yn.p, ldn, h.N, h.D, h.stream);
-    if (panel) {
-      launch_panel_image(Yn.p, ldn, p_img.p, pp, N, h.D, h.stream);
-      launch_panel_sample(p_img.p, p_smp.p, pp, N, h.stream);
-    }
-  }
-  if (prefilter) {
-    if (!panel) {
-      Yh.alloc((size_t)h.N * ldh / 2);
-      launch_to_f16(Yn.p, ldn, Yh.p, ldh, h.N, h.D, h.stream);
-    }
-    cval.alloc((size_t)h.N * keep_f);
-    cidx.alloc((size_t)h.N * keep_f);
-    fail_rows.alloc((size_t)h.N);
-    fail_count.alloc(1);
-    HIP_CHECK(hipMemsetAsync(fail_count.p, 0, 4, h.stream));
-  }
-  // worst-case |fp16-path score - exact score| for unit rows: (2u + u^2) with u = 2^-11, plus fp32 accumulation
-  const float delta = 9.8e-4f + 1.2e-7f * (float)h.D;
-  // (OSC_KNN_FORCE_EXCHANGE: the same flow with its collectives under a one-rank communicator -- the only form in which the
-  // RCCL backend's all-gather / grouped send-recv / int32 max all-reduce of this path can run on a one-GPU box)
-  const bool exchange = sharded || (h.knn_force_exchange && h.comm != nullptr);
-  const bool sym_sharded = panel && pp.sym && (parts > 1 || exchange);
-  if (sym_sharded) {
-    // Half sweep of a sharded build (graph.py:35-65 cut over the ranks): thresholds of a rank's own row blocks, all-gathered;
-    // then ONE sweep of the tiles J >= I whose work items the ranks take in turn (item = rank, rank + parts, ...: items of a
-    // chunk stay neighbours), every rank delivering into buckets of ALL rows; then the entries of each rank's own rows travel
-    // to it (exchange_buckets).  OSC_KNN_FAKE_SHARDS runs the ranks' passes one after another into the same buckets.
-    ProfScope ps(h, 3);
-    for (int part = 0; part < parts; ++part) {
-      if (sharded && part != h.rank) continue;
-      const int rb_begin = std::min(all_rb, part * rb_per), rb_count = std::max(0, std::min(rb_per, all_rb - rb_begin));
-      const int nsets = (rb_count + pp.nrg_s - 1) / pp.nrg_s;  // (work items per column split of the SAMPLE sweep)
-      launch_panel_tilemax(p_img.p, p_smp.p, pp, N, rb_begin, rb_count, p_tmax.p, p_queue.p,
-                           std::max(1, std::min(prop.multiProcessorCount, nsets * pp.SA)), h.stream);
-    }
-    launch_panel_tau(p_tmax.p, pp, N, p_tau.p, h.stream);  // (rows of other ranks' blocks: overwritten by the all-gather)
-    if (exchange) h.comm->allgather(p_tau.p, (size_t)rb_per * 128 * 4, h.stream);
-    const size_t nb = (size_t)pp.npad / 32;
-    p_hits.alloc(nb * pp.bucket_cap);
-    p_hcnt.alloc(nb + (size_t)pp.S);
-    HIP_CHECK(hipMemsetAsync(p_hcnt.p, 0, (nb + (size_t)pp.S) * 4, h.stream));
-    sym_dev.bucket_ent = p_hits.p;
-    sym_dev.bucket_cnt = p_hcnt.p;
-    sym_dev.flags = p_hcnt.p + nb;
-    const int sgrid = std::max(1, std::min(prop.multiProcessorCount, (pp.nitems + parts - 1) / parts));
-    for (int part = 0; part < parts; ++part) {
-      if (sharded && part != h.rank) continue;
-      launch_panel_filter(p_img.p, pp, N, 0, pp.nrb, p_tau.p, p_hits.p, p_hcnt.p, p_queue.p, sgrid, h.stream, &sym_dev, part, parts);
-    }
-    if (exchange) exchange_buckets(h, pp, sym_dev, rb_per);
-  }
-  for (int part = 0; part < parts; ++part) {
-    if (sharded && part != h.rank) continue;
-    const int rb_begin = std::min(all_rb, part * rb_per);
-    const int rb_count = std::max(0, std::min(rb_per, all_rb - rb_begin));
-    if (any_k) {
-      // chunks of up to ~1 GiB of similarity rows (multiple of 128 rows)
-      const int32_t ldS = ((N + 31) / 32) * 32;
-      const int64_t cap_rows = std::max<int64_t>(128, (((int64_t)1 << 28) / ldS) / 128 * 128);
-      const int32_t row_lo = rb_begin * 128, row_hi = std::min(N, (rb_begin + rb_count) * 128);
-      const int32_t chunk = (int32_t)std::min<int64_t>(cap_rows, ((row_hi - row_lo + 127) / 128) * 128);
-      if (row_hi > row_lo) {
-        DevBuf<float> Sm;
-        Sm.alloc((size_t)chunk * ldS);
-        ProfScope ps(h, 3);
-        for (int32_t r = row_lo; r < row_hi; r += chunk)
-          launch_knn_rows_any(Yn.p, ldn, N, k, r, std::min(chunk, row_hi - r), Sm.p, ldS, h.knn_val.p, h.knn_idx.p, h.stream);
-        sync(h);  // Sm goes back to the pool at scope exit
-      }
-    } else if (panel) {
-      const KnnPlan plan = knn_plan(N, keep_f, slots, rb_begin, rb_count, true, h.knn_splits);  // row range + keep for the re-scoring
-      const int nsets = (rb_count + pp.nrg - 1) / pp.nrg;  // work items per column split (knn_gemm.hip)
-      const int grid = std::max(1, std::min(prop.multiProcessorCount, nsets * pp.S));
-      if (streamed) {
-        ProfScope ps(h, 3);
-        const size_t nb = (size_t)pp.npad / 32;
-        p_hits.alloc(nb * pp.bucket_cap);
-        p_hcnt.alloc(nb + (size_t)pp.S);
-        HIP_CHECK(hipMemsetAsync(p_hcnt.p, 0, (nb + (size_t)pp.S) * 4, h.stream));
-        sym_dev.bucket_ent = p_hits.p;
-        sym_dev.bucket_cnt = p_hcnt.p;
-        sym_dev.flags = p_hcnt.p + nb;
-        stream_pieces(h, host_Y, piece_starts, pp, Yn.p, ldn, p_img.p, p_smp.p, p_tmax.p, p_tau.p, p_queue.p, sym_dev, prop.multiProcessorCount,
-                      smp_raw, smp_n);
-        host_Y = nullptr;
-      } else if (!sym_sharded) {  // (a sharded half sweep has its thresholds and buckets already: above)
-        ProfScope ps(h, 3);
-        launch_panel_tilemax(p_img.p, p_smp.p, pp, N, rb_begin, rb_count, p_tmax.p, p_queue.p,
-                             std::max(1, std::min(prop.multiProcessorCount, (rb_count + pp.nrg_s - 1) / pp.nrg_s * pp.SA)), h.stream);
-        launch_panel_tau(p_tmax.p, pp, N, p_tau.p, h.stream);
-        if (pp.sym) {
-          const size_t nb = (size_t)pp.npad / 32;
-          p_hits.alloc(nb * pp.bucket_cap);  // one bucket per group of 32 receiving rows
-          p_hcnt.alloc(nb + (size_t)pp.S);   // [bucket counts | chunk flags]
-          HIP_CHECK(hipMemsetAsync(p_hcnt.p, 0, (nb + (size_t)pp.S) * 4, h.stream));
-          sym_dev.bucket_ent = p_hits.p;
-          sym_dev.bucket_cnt = p_hcnt.p;
-          sym_dev.flags = p_hcnt.p + nb;
-          const int sgrid = std::max(1, std::min(prop.multiProcessorCount, pp.nitems));
-          launch_panel_filter(p_img.p, pp, N, rb_begin, rb_count, p_tau.p, p_hits.p, p_hcnt.p, p_queue.p, sgrid, h.stream, &sym_dev);
-        } else {
-          p_hits.alloc((size_t)rb_count * pp.S * 4 * pp.hit_cap);  // one list per (work item, wave)
-          p_hcnt.alloc((size_t)rb_count * pp.S * 4);
-          launch_panel_filter(p_img.p, pp, N, rb_begin, rb_count, p_tau.p, p_hits.p, p_hcnt.p, p_queue.p, grid, h.stream);
-        }
-      }
-      static const bool knn_debug = getenv("OSC_KNN_DEBUG") != nullptr;  // diagnostic: where the prefilter loses rows
-      auto failed_so_far = [&] {
-        int32_t n = 0;
-        HIP_CHECK(hipMemcpyAsync(&n, fail_count.p, 4, hipMemcpyDeviceToHost, h.stream));
-        sync(h);
-        return n;
-      };
-      if (knn_debug && pp.sym) {
-        const size_t nb = (size_t)pp.npad / 32;
-        std::vector<int32_t> cnt(nb + (size_t)pp.S);
-        std::vector<float> tau((size_t)pp.npad);
-        HIP_CHECK(hipMemcpyAsync(cnt.data(), p_hcnt.p, cnt.size() * 4, hipMemcpyDeviceToHost, h.stream));
-        HIP_CHECK(hipMemcpyAsync(tau.data(), p_tau.p, tau.size() * 4, hipMemcpyDeviceToHost, h.stream));
-        sync(h);
-        int64_t sum = 0, over = 0, flagged = 0;
-        int32_t mx = 0;
-        int64_t first_over = -1, first_flag = -1;
-        for (size_t b = 0; b < nb; ++b) {
-          sum += cnt[b], mx = std::max(mx, cnt[b]), over += cnt[b] > pp.bucket_cap;
-          if (cnt[b] > pp.bucket_cap && first_over < 0) first_over = (int64_t)b;
-        }
-        for (int c = 0; c < pp.S; ++c) {
-          flagged += cnt[nb + (size_t)c] != 0;
-          if (cnt[nb + (size_t)c] != 0 && first_flag < 0) first_flag = c;
-        }
-        if (over || flagged) fprintf(stderr, "[knn] first bucket over: %lld (rows from %lld), first chunk flagged: %lld\n", (long long)first_over, (long long)first_over * 32, (long long)first_flag);
-        double tsum = 0.0;
-        float tmin = 3e38f, tmax = -3e38f;
-        for (int32_t r = 0; r < N; ++r) tsum += tau[(size_t)r], tmin = std::min(tmin, tau[(size_t)r]), tmax = std::max(tmax, tau[(size_t)r]);
-        fprintf(stderr, "[knn] pieces %d: buckets %zu, entries per 32 rows mean %.0f max %d (cap %d), %lld buckets over, %lld of %d chunks flagged; tau / 256: mean %.4f min %.4f max %.4f; hit bound %.0f keep %d\n",
-                pp.map.npieces, nb, (double)sum / (double)nb, mx, pp.bucket_cap, (long long)over, (long long)flagged, pp.S, tsum / N / 256.0,
-                tmin / 256.0, tmax / 256.0, pp.hit_bound, pp.keep);
-      }
-      launch_panel_select(pp, rb_begin, rb_count, N, p_hits.p, p_hcnt.p, cval.p, cidx.p, fail_rows.p, fail_count.p,
-                          h.stream, pp.sym ? &sym_dev : nullptr);
-      if (knn_debug) fprintf(stderr, "[knn] after the select: %d rows without a candidate list\n", failed_so_far());
-      // (single-process builds of rows of >= 384 columns: every undirected candidate pair is scored once -- two launches and two
-      // N x keep scratch arrays.  A lookup in the partner's list costs keep x 4 bytes and a dependent round trip per candidate,
-      // which short rows do not repay: build with / without, profiles/r06_rescore_ab.txt: config 3 12.07 / 12.54 ms, config 5
-      // 91.7 / 96.1; with the cheaper selection tail of the round's last pass also 140 000 x 576 18.24 / 18.80, 200 000 x 512
-      // 30.74 / 31.05, config 4 (384 columns) 390.8 / 393.6, 100 000 x 384 6.56 / 6.61; 40 000 x 256 a tie, 2.03 / 2.00)
-      if ((h.knn_rescore_pair == 2 || (h.knn_rescore_pair == 1 && h.D >= 384)) && parts == 1 && !exchange && h.comm == nullptr && (int64_t)N * keep_f < ((int64_t)1 << 31)) {
-        pair_sc.alloc((size_t)N * keep_f);
-        pair_pos.alloc((size_t)N * keep_f);
-      }
-      launch_knn_rescore(plan, Yn.p, ldn, h.D, N, cidx.p, cval.p, k, delta, h.knn_val.p, h.knn_idx.p, fail_rows.p,
-                         fail_count.p, h.stream, pp.scatter != 1 ? &pp.map : nullptr, pair_sc.p, pair_pos.p);
-      if (knn_debug) fprintf(stderr, "[knn] after the re-scoring: %d rows unproven\n", failed_so_far());
-    } else if (prefilter) {
-      const KnnPlan plan = knn_plan(N, keep_f, slots, rb_begin, rb_count, true, h.knn_splits);
-      const size_t ncand = (size_t)h.N * plan.S * plan.KC;
-      cand_val.alloc(ncand);
-      cand_idx.alloc(ncand);
-      {
-        ProfScope ps(h, 3);
-        launch_knn_topk(plan, Yh.p, ldh / 2, N, cand_val.p, cand_idx.p, h.stream);
-      }
-      HIP_CHECK(hipMemsetAsync(cidx.p, 0xFF, (size_t)h.N * keep_f * 4, h.stream));
-      launch_knn_merge(plan, cand_val.p, cand_idx.p, N, keep_f, cval.p, cidx.p, 0, h.stream);
-      launch_knn_rescore(plan, Yn.p, ldn, h.D, N, cidx.p, cval.p, k, delta, h.knn_val.p, h.knn_idx.p, fail_rows.p,
-                         fail_count.p, h.stream);
-    } else if (parts == 1 && N <= dense_max && dense_small) {
-      // small lattices: dense S + per-row argmax selection (the streaming kernel's first-tile inserts dominate here)
-      const int32_t ldS = ((N + 31) / 32) * 32;
-      DevBuf<float> Sm;
-      Sm.alloc((size_t)N * ldS);
-      ProfScope ps(h, 3);
-      launch_knn_dense(Yn.p, ldn, N, k, Sm.p, ldS, h.knn_val.p, h.knn_idx.p, h.stream);
-      sync(h);  // Sm goes back to the pool at scope exit
-    } else {
-      const KnnPlan plan = knn_plan(N, k, slots, rb_begin, rb_count, false, h.knn_splits);
-      const size_t ncand = (size_t)h.N * plan.S * plan.KC;
-      cand_val.alloc(ncand);
-      cand_idx.alloc(ncand);
-      {
-        ProfScope ps(h, 3);
-        launch_knn_topk(plan, Yn.p, ldn, N, cand_val.p, cand_idx.p, h.stream);
-      }
-      launch_knn_merge(plan, cand_val.p, cand_idx.p, N, k, h.knn_val.p, h.knn_idx.p, 1, h.stream);
-    }
-  }
-  if (prefilter) {
-    int32_t nfail = 0;
-    HIP_CHECK(hipMemcpyAsync(&nfail, fail_count.p, 4, hipMemcpyDeviceToHost, h.stream));
-    sync(h);
-    DevBuf<int32_t> fail_rows2, fail_count2;
-    int32_t* fail_list = fail_rows.p;
-    if (panel && pp.sym && nfail > 0) {  // second-stage proof from the rows' whole buckets (knn_gemm.hip: k_bucket_rescore)
-      fail_rows2.alloc((size_t)nfail);
-      fail_count2.alloc(1);
-      HIP_CHECK(hipMemsetAsync(fail_count2.p, 0, 4, h.stream));
-      launch_bucket_rescore(pp, sym_dev, Yn.p, ldn, N, fail_rows.p, nfail, p_tau.p, k, delta, h.knn_val.p, h.knn_idx.p,
-                            fail_rows2.p, fail_count2.p, h.stream);
-      HIP_CHECK(hipMemcpyAsync(&nfail, fail_count2.p, 4, hipMemcpyDeviceToHost, h.stream));
-      sync(h);
-      fail_list = fail_rows2.p;
-    }
-    h.knn_fallback_rows = nfail;
-    // (OSC_CREATE_FORCE_RETRY: test hook -- every streamed build gives up here)
-    if (streamed && (nfail > std::max(64, N / 256) || h.create_force_retry)) return false;
-    bool few_done = false;
-    if (nfail > 0 && nfail <= 32) {  // a handful of rows: stream the columns once, select per row (0.15 vs 3.9 ms at N = 100k)
-      const int32_t ldS = ((N + 31) / 32) * 32;
-      DevBuf<float> Sm;
-      Sm.alloc((size_t)nfail * ldS);
-      few_done = launch_knn_few_rows(Yn.p, ldn, N, k, fail_list, nfail, Sm.p, ldS, h.knn_val.p, h.knn_idx.p, h.stream);
-      if (few_done) sync(h);  // Sm goes back to the pool at scope exit
-    }
-    if (nfail > 0 && !few_done) {  // redo the unproven rows with the exact kernel (ties / dense clusters of near-equal scores)
-      KnnPlan plan = knn_plan(N, k, slots, 0, (nfail + 127) / 128, false, h.knn_splits);
-      plan.qrows = fail_list;
-      plan.nq = nfail;
-      const size_t ncand = (size_t)h.N * plan.S * plan.KC;
-      cand_val.alloc(ncand);
-      cand_idx.alloc(ncand);
-      launch_knn_topk(plan, Yn.p, ldn, N, cand_val.p, cand_idx.p, h.stream);
-      launch_knn_merge(plan, cand_val.p, cand_idx.p, N, k, h.knn_val.p, h.knn_idx.p, 1, h.stream);
-    }
-  }
-  if (sharded && panel && pp.scatter != 1) {
-    // a rank's rows are spread over the lattice (image row blocks): every row has exactly one writer, the others hold the
-    // initial pattern (0.0f / -1), so a sum of the similarities and a max of the indices assemble the lists exactly
-    const size_t cnt = (size_t)N * k;
-    h.comm->allreduce(h.knn_val.p, cnt, COMM_F32, COMM_SUM, h.stream);
-    h.comm->allreduce(h.knn_idx.p, cnt, COMM_I32, COMM_MAX, h.stream);
-  } else if (sharded) {
-    const size_t cnt = (size_t)rb_per * 128 * k;  // equal chunk per rank, in place
-    h.comm->allgather(h.knn_val.p, cnt * 4, h.stream);
-    h.comm->allgather(h.knn_idx.p, cnt * 4, h.stream);
-  }
+  KnnWork w(plan, h.D);
+  w.Yn.alloc((size_t)h.N * w.ldn);
+  const int32_t k = plan.k;
+  h.knn_val.alloc(plan.list_rows * k);
+  h.knn_idx.alloc(plan.list_rows * k);
+  h.knn_k = k;
+  HIP_CHECK(hipMemsetAsync(h.knn_val.p, 0, plan.list_rows * k * 4, h.stream));
+  HIP_CHECK(hipMemsetAsync(h.knn_idx.p, 0xFF, plan.list_rows * k * 4, h.stream));
+  prepare_rows(h, w, host_Y);
+  if (plan.sym_sharded) sweep_half_sharded(h, w);
+  for (int part = 0; part < plan.parts; ++part)
+    if (runs_part(h, plan, part)) sweep_part(h, w, part, host_Y);
+  if (plan.prefilter() && !prove_fallback_rows(h, w)) return false;
+  assemble_lists(h, plan);
   alloc_ell(h, k);
   launch_mutual_ell(h.knn_val.p, h.knn_idx.p, N, k, h.width, h.ell_col.p, h.ell_a.p, h.deg.p, h.stream);
   DevBuf<float> scale;

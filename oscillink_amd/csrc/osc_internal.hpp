@@ -87,8 +87,7 @@ struct osc_lattice {
   DevBuf<int32_t> knn_idx;
   int32_t knn_k = 0;
   int32_t knn_fallback_rows = 0;  // rows of the last build the prefilter could not prove and the exact kernel redid
-  bool knn_prefilter = false;     // the last build used the fp16 prefilter
-  bool knn_panel = false;         // ... in its register-resident-panel shape (knn_gemm.hip)
+  KnnBuildPlan knn_last;          // the route of the last build (knn_plan.hpp: plan_knn_build)
   double build_ms = 0.0;
   int64_t nnz = 0;
   int32_t max_deg = 0;
@@ -126,23 +125,10 @@ struct osc_lattice {
   bool fake_window = false;  // OSC_FAKE_COL_SHARD under a one-rank communicator (measurement hook; reported by osc_comm_info)
   // build-route switches (read_env): every OSC_* variable the library reads per handle is read in ONE place, at
   // osc_create and again at osc_rebuild_graph (INTEGRATION.md has the table)
-  int knn_mode = 0;            // OSC_KNN_MODE: 0 automatic, 1 exact, 2 tile prefilter, 3 panel prefilter
-  int knn_fake_shards = 0;     // OSC_KNN_FAKE_SHARDS
-  int knn_splits = 0;          // OSC_KNN_SPLITS (tile / exact routes: column splits)
-  bool knn_scatter = true;     // OSC_KNN_PANEL_SCATTER
-  bool knn_sym = true;         // OSC_KNN_PANEL_SYM
-  bool create_stream = true;   // OSC_CREATE_STREAM: osc_create hands the anchors to the build piece by piece (osc_graph.hip)
-  int32_t create_piece_mb = 24;  // OSC_CREATE_PIECE_MB: anchors per piece, at least (experiments)
-  bool create_piece_mb_set = false;
-  int32_t create_min_mb = 64;  // OSC_CREATE_MIN_MB: anchors below this travel whole (the streamed create's fixed costs)
+  KnnBuildInputs knn_env;      // OSC_KNN_* / OSC_CREATE_*: the kNN planner's switch inputs (knn_plan.hpp)
   bool receipt_pair = true;  // OSC_RECEIPT_PAIR=0: the receipt's per-edge pass from both ends of every edge (one launch)
-  int32_t create_two_mb = 256;  // OSC_CREATE_TWO_PIECE_MB: anchors from this size on may travel in TWO pieces (three below it)
   bool create_force_retry = false;  // OSC_CREATE_FORCE_RETRY (test hook): a streamed build always hands over to the whole-array one
   int32_t create_pieces = 0;   // pieces the last build received its anchors in (0: they were on the device before it started)
-  int knn_rescore_pair = 1;  // OSC_KNN_RESCORE_PAIR: 0 = every candidate pair scored from both ends, 1 = once where rows have >= 384 columns, 2 = once at any width (experiments)
-  int32_t knn_sweep = 0;       // main sweep of the last build's thresholds-and-hits prefilter: 0 none (another route), 1 every column tile per row block, 2 the half sweep (ONE per build, shared by the ranks of a sharded build)
-  bool knn_force_exchange = false;  // OSC_KNN_FORCE_EXCHANGE=1 (test hook): run the sharded half sweep's collectives under a ONE-rank communicator too
-  KnnPanelTune knn_tune{};     // OSC_KNN_PANEL_NRG / _RHO / _T / _RANK
   int halo_force = 0;          // OSC_HALO: 1 full, 2 lists
   bool bfs_host = false;       // OSC_BFS_HOST=1: the breadth-first row order is walked on the host (A/B, tests)
   int fake_col_r = 0, fake_col_w = 0;  // OSC_FAKE_COL_SHARD "r/w"

@@ -5,11 +5,13 @@
 //   usage: sweep_host_logic [max_N]
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <map>
 #include <random>
 #include <set>
 
 #include "../../oscillink_amd/csrc/host_logic.hpp"
+#include "../../oscillink_amd/csrc/knn_plan.hpp"
 #include "../../oscillink_amd/csrc/knn_rowmap.hpp"
 
 using namespace osc::host;
@@ -438,6 +440,141 @@ static void check_plans() {
   }
 }
 
+// ---- the lattice build's route (knn_plan.hpp: plan_knn_build) --------------------------------------------------------
+// Inputs of an MI355X (256 CUs) build; the OSC_* switches at their defaults unless set below.
+static osc::KnnBuildInputs knn_inputs(int32_t N, int32_t D, int32_t k, int world, bool comm, int fake, int mode, bool sym,
+                                      size_t mem_free, bool host_anchors) {
+  osc::KnnBuildInputs in;
+  in.N = N;
+  in.D = D;
+  in.k = std::min<int32_t>(k, std::max<int32_t>(1, N - 1));
+  in.world = world;
+  in.comm = comm;
+  in.fake_shards = fake;
+  in.force_exchange = comm && world == 1;
+  in.cus = 256;
+  in.mem_free = mem_free;
+  in.mode = mode;
+  in.sym = sym;
+  in.host_anchors = host_anchors;
+  in.stage_bytes = (size_t)32 << 20;
+  return in;
+}
+
+static void check_knn_build_plan(const osc::KnnBuildInputs& in) {
+  using osc::KnnRoute;
+  const osc::KnnBuildPlan p = osc::plan_knn_build(in);
+  const osc::KnnPanelPlan& pp = p.pp;
+  const long long N = in.N;
+  CHECK((p.route == KnnRoute::any_k) == (in.k > 128), "N %lld k %d: any-k route", N, in.k);
+  CHECK(!p.prefilter() || p.keep >= in.k + 8, "N %lld k %d: keep %d leaves no margin", N, in.k, p.keep);
+  CHECK(p.route != KnnRoute::dense || (p.parts == 1 && N <= osc::kKnnDenseMaxRows), "N %lld parts %d: dense route", N, p.parts);
+  int32_t rows = 0;
+  for (int part = 0; part < p.parts; ++part) rows += p.rb_count(part);
+  CHECK(rows == p.all_rb && p.list_rows >= (size_t)N, "N %lld parts %d: the parts' row blocks", N, p.parts);
+  if (p.route != KnnRoute::panel) {
+    CHECK(!p.streamed() && !p.sym_sharded && !p.rescore_pair, "N %lld: panel-only choices on route %d", N, (int)p.route);
+    return;
+  }
+  CHECK(N >= osc::kKnnPanelMinRows && N < osc::kKnnPanelMaxRows, "N %lld: panel route", N);
+  CHECK(!pp.tile_core || pp.sym, "N %lld D %d: the tile core without the half sweep", N, in.D);
+  CHECK(pp.sample_rank >= 1 && pp.sample_rank <= pp.sample_groups, "N %lld: sample rank %d of %d", N, pp.sample_rank, pp.sample_groups);
+  CHECK(pp.map.npieces == std::max<int>(1, (int)p.piece_starts.size()) && (int)p.piece_starts.size() <= osc::KNN_MAP_MAX,
+        "N %lld: %zu pieces", N, p.piece_starts.size());
+  for (size_t j = 0; j < p.piece_starts.size(); ++j) {
+    const int32_t s = p.piece_starts[j];
+    CHECK(s % (pp.T * 128) == 0 && (j == 0 ? s == 0 : s > p.piece_starts[j - 1]) && s < N && pp.map.start[j] == s,
+          "N %lld: piece %zu starts at %d (chunks of %d rows)", N, j, s, pp.T * 128);
+  }
+  if (pp.sym) {
+    const int per_item = pp.tile_wide ? 2 : pp.nrg;
+    int32_t items = 0;
+    for (int c = 0; c < pp.S; ++c) items += (std::min(pp.nrb, (c + 1) * pp.T) + per_item - 1) / per_item;
+    CHECK(items == pp.nitems && pp.S == (pp.nrb + pp.T - 1) / pp.T, "N %lld: %d work items over %d chunks", N, pp.nitems, pp.S);
+    // (the automatic route checks the buckets against the budget; OSC_KNN_MODE=panel below 8193 rows does not)
+    const double bucket_bytes = (double)(pp.npad / 32) * (double)pp.bucket_cap * 8.0;
+    if (in.mode == 0 && pp.ok)
+      CHECK(bucket_bytes <= osc::kKnnSymBucketBudget && bucket_bytes <= 0.5 * (double)in.mem_free,
+            "N %lld D %d: %.3g bytes of buckets", N, in.D, bucket_bytes);
+  }
+}
+
+static void check_knn_build_plans() {
+  for (int32_t N : {2, 3, 100, 4095, 4096, 6143, 6144, 7167, 7168, 8192, 8193, 12000, 40000, 100000, 200000, 1000000, 4000000,
+                    16777216, 33554431, 33554432})
+    for (int32_t D : {64, 128, 320, 384, 512, 768, 769, 1536, 4096, 4097}) {
+      // (the tile core's half sweep counts its work items in an int: about nrb^2 / 16 of them at T = 8, past 2^31 from ~23.7M
+      // rows -- lattices of 73 GB and more at 769 columns; the sweep stays below)
+      if (D > 768 && N > 16777216) continue;
+      for (int32_t k : {1, 16, 32, 64, 88, 89, 128, 129})
+        for (int parts = 0; parts < 6; ++parts)
+          for (int mode = 0; mode < 4; ++mode)
+            for (size_t mem : {(size_t)288 << 30, (size_t)1 << 30}) {
+              const int world = parts == 1 ? 2 : parts == 2 ? 8 : 1, fake = parts == 3 ? 2 : parts == 4 ? 3 : 0;
+              const bool comm = parts == 1 || parts == 2 || parts == 5;
+              check_knn_build_plan(knn_inputs(N, D, k, world, comm, fake, mode, (k & 1) == 0 || mode != 0, mem, parts == 0));
+            }
+    }
+  // Plans recorded from the build's decision before it was moved into plan_knn_build (256 CUs, default switches):
+  // {N, D, k, world, communicator, OSC_KNN_FAKE_SHARDS, OSC_KNN_MODE, OSC_KNN_PANEL_SYM, free GiB, anchors on the host,
+  // OSC_KNN_TILE_WIDE} -> {route, keep, parts, sharded half sweep, pair re-scoring, pieces, second piece's start, nkt, nrg,
+  // S, T, SA, sample_tiles, sample_rank, bucket_cap, nitems, scatter}
+  struct In {
+    int32_t N, D, k;
+    int world, comm, fake, mode, sym, mem_gib, host, tile_wide;
+  };
+  struct Want {
+    int route, keep, parts, sym_sharded, rescore_pair, pieces, start1, nkt, nrg, S, T, SA, sample_tiles, sample_rank, bucket_cap, nitems, scatter;
+  };
+  struct Row {
+    In in;
+    Want w;
+  };
+  const Row rows[] = {
+      {{80, 128, 8, 1, 0, 0, 0, 1, 288, 1, 1}, {1, 20, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}},
+      {{1200, 128, 16, 1, 0, 0, 0, 1, 288, 1, 1}, {1, 28, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}},
+      {{100000, 768, 32, 1, 0, 0, 0, 1, 288, 1, 1}, {4, 48, 1, 0, 1, 10, 9216, 12, 2, 33, 24, 3, 65, 14, 11520, 6727, 61803}},
+      {{100000, 768, 32, 1, 0, 0, 0, 1, 288, 0, 1}, {4, 48, 1, 0, 1, 0, 0, 12, 2, 33, 24, 3, 65, 14, 11520, 6727, 61803}},
+      {{1000000, 384, 16, 1, 0, 0, 0, 1, 288, 1, 1}, {4, 28, 1, 0, 1, 15, 64512, 6, 2, 326, 24, 2, 400, 14, 18751, 639607, 618033}},
+      {{200000, 1536, 64, 1, 0, 0, 0, 1, 288, 1, 1}, {4, 96, 1, 0, 1, 2, 84992, 24, 1, 196, 8, 2, 65, 14, 23040, 77222, 123607}},
+      {{200000, 1536, 64, 1, 0, 0, 0, 1, 288, 0, 0}, {4, 96, 1, 0, 1, 0, 0, 24, 1, 196, 8, 2, 65, 14, 23040, 154443, 123607}},
+      {{6143, 768, 32, 1, 0, 0, 0, 1, 288, 0, 1}, {1, 48, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}},
+      {{6144, 768, 32, 1, 0, 0, 0, 1, 288, 0, 1}, {4, 48, 1, 0, 1, 0, 0, 12, 1, 2, 24, 5, 24, 21, 11520, 72, 3797}},
+      {{7167, 384, 16, 1, 0, 0, 0, 1, 288, 0, 1}, {1, 28, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}},
+      {{7168, 384, 16, 1, 0, 0, 0, 1, 288, 0, 1}, {4, 28, 1, 0, 1, 0, 0, 6, 2, 3, 24, 6, 24, 21, 11520, 64, 4433}},
+      {{8192, 128, 16, 1, 0, 0, 0, 1, 288, 0, 1}, {1, 28, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}},
+      {{8193, 128, 16, 1, 0, 0, 0, 1, 288, 0, 1}, {4, 28, 1, 0, 0, 0, 0, 6, 2, 3, 24, 6, 24, 21, 11520, 69, 5063}},
+      {{4096, 128, 16, 2, 1, 0, 0, 1, 288, 0, 1}, {3, 28, 2, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}},
+      {{5000, 64, 200, 1, 0, 0, 0, 1, 288, 0, 1}, {0, 96, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}},
+      {{20000, 128, 100, 1, 0, 0, 0, 1, 288, 0, 1}, {2, 96, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}},
+      {{100000, 768, 32, 2, 1, 0, 0, 1, 288, 0, 1}, {4, 48, 2, 1, 0, 0, 0, 12, 2, 33, 24, 3, 65, 14, 11520, 6727, 61803}},
+      {{1000000, 384, 16, 8, 1, 0, 0, 1, 288, 0, 1}, {4, 28, 8, 1, 0, 0, 0, 6, 2, 326, 24, 2, 400, 14, 18751, 639607, 618033}},
+      {{100000, 768, 32, 8, 1, 0, 0, 0, 288, 0, 1}, {4, 48, 8, 0, 0, 0, 0, 12, 1, 7, 0, 3, 65, 14, 0, 0, 1}},
+      {{20000, 256, 24, 1, 0, 2, 0, 1, 288, 0, 1}, {4, 36, 2, 1, 0, 0, 0, 6, 2, 7, 24, 3, 24, 17, 11606, 331, 12361}},
+      {{20000, 256, 24, 1, 1, 0, 0, 1, 288, 0, 1}, {4, 36, 1, 1, 0, 0, 0, 6, 2, 7, 24, 3, 24, 17, 11606, 331, 12361}},
+      {{20000, 256, 24, 1, 0, 0, 1, 1, 288, 0, 1}, {2, 36, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}},
+      {{20000, 256, 24, 1, 0, 0, 2, 1, 288, 0, 1}, {3, 36, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}},
+      {{6144, 128, 16, 1, 0, 0, 3, 1, 288, 0, 1}, {4, 28, 1, 0, 0, 0, 0, 6, 2, 2, 24, 6, 24, 21, 11520, 36, 3797}},
+      {{1000000, 384, 16, 1, 0, 0, 0, 1, 4, 0, 1}, {4, 28, 1, 0, 1, 0, 0, 6, 2, 22, 0, 2, 400, 14, 0, 0, 618033}},
+      {{200000, 1536, 64, 1, 0, 0, 0, 1, 2, 0, 1}, {3, 96, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}},
+  };
+  for (const Row& r : rows) {
+    const In& i = r.in;
+    osc::KnnBuildInputs in = knn_inputs(i.N, i.D, i.k, i.world, i.comm != 0, i.fake, i.mode, i.sym != 0, (size_t)i.mem_gib << 30, i.host != 0);
+    in.tune.tile_wide = i.tile_wide;
+    const osc::KnnBuildPlan p = osc::plan_knn_build(in);
+    const osc::KnnPanelPlan& pp = p.pp;
+    const bool panel = p.route == osc::KnnRoute::panel;
+    const Want g{(int)p.route, p.keep, p.parts, p.sym_sharded, p.rescore_pair, (int)p.piece_starts.size(),
+                 p.piece_starts.size() > 1 ? p.piece_starts[1] : 0, panel ? pp.nkt : 0, panel ? pp.nrg : 0, panel ? pp.S : 0,
+                 panel ? pp.T : 0, panel ? pp.SA : 0, panel ? pp.sample_tiles : 0, panel ? pp.sample_rank : 0,
+                 panel ? pp.bucket_cap : 0, panel ? pp.nitems : 0, panel ? pp.scatter : 0};
+    CHECK(std::memcmp(&g, &r.w, sizeof(Want)) == 0, "N %d D %d k %d world %d: route %d keep %d, %d pieces, S %d T %d, %d items", i.N, i.D,
+          i.k, i.world, g.route, g.keep, g.pieces, g.S, g.T, g.nitems);
+    check_knn_build_plan(in);
+  }
+}
+
 // ---- CgXSchedule against a model of the device ---------------------------------------------------------------------
 // The host loop of run_cg (osc_api.hip) is replayed here verbatim; the "device" executes the launches in order with the
 // gating rule of the kernels (a gated launch of iteration it runs iff iteration it - 1 did not converge; an ungated
@@ -544,6 +681,7 @@ int main(int argc, char** argv) {
             "N %lld ncols %d groups %d", (long long)N, ncols, g);
     }
   check_plans();
+  check_knn_build_plans();
   for (double deg : {1.0, 13.8, 28.8, 59.5})
     for (int64_t N : {96000, 140000, 220000, 450000, 450001, 2000000}) {
       const int nb = blocked_block_count(deg, blocked_edges_per_block_wide(N), 32);
