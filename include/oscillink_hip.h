@@ -208,6 +208,16 @@ int osc_get_query_basis(osc_handle h, float* X_out, float* x_out);
  * mmr_diversify (graph.py:114-133, lambda_div) over the anchors.  ids / score / align are Q x min(k, N), API ids. */
 int osc_bundle_many(osc_handle h, const float* psis, int32_t Q, int32_t k, float alpha, float lambda_div, int32_t* ids,
                     float* score, float* align);
+/* Not in the reference: receipt() (lattice.py:298-455, receipts.py:10-83) for Q queries psis (Q x D) with the current U,
+ * gates, chain and lambdas held fixed, U*(psi) from the resident basis.  Per query: dH (deltaH_trace
+ * of U against U*(psi_q)); with detail != 0 also coh_sum / anchor_sum / query_sum and the null points at z_th (else 0 and
+ * none).  null_total[q] counts query q's null points; null_cap > 0 keeps the null_cap highest z of a query that has more
+ * (ties in API row order, in that order), else all in API row order.  The kept records of query q are
+ * [null_offsets[q], null_offsets[q + 1]) of i_out / j_out / z_out / r_out (capacity entries; OSC_E_INVALID if too few).
+ * OSC_E_STATE without a basis, OSC_E_UNSUPPORTED with a communicator. */
+int osc_receipt_many(osc_handle h, const float* psis, int32_t Q, int32_t detail, float z_th, int32_t null_cap, double* dH,
+                     double* coh_sum, double* anchor_sum, double* query_sum, int32_t* null_total, int64_t* null_offsets,
+                     int32_t* i_out, int32_t* j_out, float* z_out, float* r_out, int64_t capacity);
 /* mmr_diversify (graph.py:114-133) for Q score columns at once: scores N x Q (API row order, queries contiguous per row);
  * out_idx Q x min(k, N) API ids, the same picks as osc_mmr per column up to rounding of the similarities. */
 int osc_mmr_many(osc_handle h, const float* scores, int32_t Q, int32_t k, float lambda_div, int32_t* out_idx);

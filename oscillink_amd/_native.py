@@ -69,6 +69,8 @@ SIGNATURES = {
     "osc_get_query_basis": (C.c_int, [Handle, c_f32p, c_f32p]),
     "osc_bundle_many": (C.c_int, [Handle, c_f32p, C.c_int32, C.c_int32, C.c_float, C.c_float, c_i32p, c_f32p, c_f32p]),
     "osc_mmr_many": (C.c_int, [Handle, c_f32p, C.c_int32, C.c_int32, C.c_float, c_i32p]),
+    "osc_receipt_many": (C.c_int, [Handle, c_f32p, C.c_int32, C.c_int32, C.c_float, C.c_int32, c_f64p, c_f64p, c_f64p, c_f64p,
+                                   c_i32p, c_i64p, c_i32p, c_i32p, c_f32p, c_f32p, C.c_int64]),
     "osc_deltaH": (C.c_int, [Handle, c_f64p]),
     "osc_receipt_components": (C.c_int, [Handle, c_f32p, c_f32p, c_f32p]),
     "osc_null_points": (C.c_int, [Handle, C.c_float, c_i32p, c_i32p, c_f32p, c_f32p, c_i32p]),

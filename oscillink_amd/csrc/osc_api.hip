@@ -842,6 +842,21 @@ int osc_bundle_many(osc_handle h, const float* psis, int32_t Q, int32_t k, float
   });
 }
 
+int osc_receipt_many(osc_handle h, const float* psis, int32_t Q, int32_t detail, float z_th, int32_t null_cap, double* dH,
+                     double* coh_sum, double* anchor_sum, double* query_sum, int32_t* null_total, int64_t* null_offsets,
+                     int32_t* i_out, int32_t* j_out, float* z_out, float* r_out, int64_t capacity) {
+  return guarded(h, [&](L& l) {
+    if (Q < 0) throw Invalid("osc_receipt_many: Q must be >= 0");
+    if (capacity < 0) throw Invalid("osc_receipt_many: capacity must be >= 0");
+    if (Q > 0 && (!psis || !dH || !coh_sum || !anchor_sum || !query_sum || !null_total || !null_offsets))
+      throw Invalid("osc_receipt_many: NULL buffer");
+    for (int64_t i = 0; i < (int64_t)Q * l.D; ++i)
+      if (!std::isfinite(psis[i])) throw Invalid("osc_receipt_many: non-finite query");
+    query_receipt_many(l, psis, Q, detail, z_th, null_cap, dH, coh_sum, anchor_sum, query_sum, null_total, null_offsets,
+                       i_out, j_out, z_out, r_out, capacity);
+  });
+}
+
 int osc_mmr_many(osc_handle h, const float* scores, int32_t Q, int32_t k, float lambda_div, int32_t* out_idx) {
   return guarded(h, [&](L& l) {
     if (Q < 0) throw Invalid("osc_mmr_many: Q must be >= 0");
@@ -859,8 +874,8 @@ int osc_ustar_cosine_to(osc_handle h, const float* psi, float* out) {
 }
 
 // sum (A - B) . M (A - B) with the stationary operator M = lamG I + lamC L + lamQ B (+ lamP L_path)  (receipts.py:21-25)
-// over this rank's share (column window / row block), completed over the communicator
-static double quad_form_of_difference(L& l, const float* A, const float* B) {
+// over this rank's share (column window / row block), completed over the communicator (C++ linkage: osc_internal.hpp)
+extern "C++" double quad_form_of_difference(L& l, const float* A, const float* B) {
   ensure_cg_scratch(l, 1);
   const int grid = cg_grid(l);
   const host::ApplyPlan plan = apply_plan(l, l.c0, l.c1, l.ld, path_active(l));

@@ -207,6 +207,18 @@ struct osc_lattice {
     DevBuf<double2> part, stats;
     DevBuf<int32_t> pid, prow, chosen_api, chosen_row;
     DevBuf<float> out_score, out_align;
+    // receipt_many: per-basis terms, kept until the next basis solve or extension (gen)
+    uint64_t gen = 0;            // bumped by every basis solve
+    uint64_t rm_gen = 0;         // gen of Mx and the per-basis sums below
+    uint64_t rd_gen = 0;         // gen of dslot
+    DevBuf<double> Mx;           // [N] M x
+    DevBuf<float> dslot;         // [N * width] |P_i - P_j|^2 per ELL slot
+    std::vector<double> rm_vec;  // 4 x D: sum x_i (X_i - Y_i), sum B_i (x_i - 1) X_i, then the column sums of a0 and b0
+    double rm_a0 = 0, rm_b0 = 0, rm_a2 = 0, rm_b2 = 0, rm_h2 = 0;
+    DevBuf<double> rpart, rspart, rsum, rfin, cohpart, cohfin;
+    DevBuf<float> U0, rz, rr, zt, roz, ror;  // U0: X + x psi0^T; rz / rj / rr: N x qs candidates; zt: qs x N
+    DevBuf<int32_t> rj, rtot, rsel, roi, roj;
+    DevBuf<int64_t> roff;
   } query;
   std::string err;
 
@@ -320,6 +332,11 @@ void require_graph(L& h);
 // osc_query.hip (include/oscillink_hip.h: osc_query_basis, osc_get_query_basis, osc_bundle_many, osc_mmr_many)
 void query_basis_solve(L& l, float tol, int32_t max_iters, float scale, bool fresh, int32_t* iters, float* res, double* ms);
 void query_basis_download(L& l, float* X_out, float* x_out);
+void query_receipt_many(L& l, const float* psis, int32_t Q, int32_t detail, float z_th, int32_t null_cap, double* dH,
+                        double* coh_sum, double* anchor_sum, double* query_sum, int32_t* null_total, int64_t* null_offsets,
+                        int32_t* i_out, int32_t* j_out, float* z_out, float* r_out, int64_t capacity);
+// sum (A - B) . M (A - B) with the stationary operator (osc_api.hip; receipts.py:21-25)
+double quad_form_of_difference(L& l, const float* A, const float* B);
 void query_bundle_many(L& l, const float* psis, int32_t Q, int32_t k, float alpha, float lambda_div, int32_t* ids,
                        float* score, float* align);
 void query_mmr_many(L& l, const float* scores, int32_t Q, int32_t k, float lambda_div, int32_t* ids);

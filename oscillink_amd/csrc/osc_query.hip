@@ -1,5 +1,6 @@
-// Multi-query bundles: the query basis solve and the batched bundle / MMR drivers behind
-// osc_query_basis, osc_get_query_basis, osc_bundle_many and osc_mmr_many (see osc_internal.hpp).
+// Multi-query bundles and receipts (DESIGN.md sections 11 and 12): the query basis solve and the batched bundle / MMR /
+// receipt drivers behind osc_query_basis, osc_get_query_basis, osc_bundle_many, osc_mmr_many and osc_receipt_many (see
+// osc_internal.hpp).
 //
 // For the lattice's graph, gates, chain and lambdas, U*(psi) = X + x psi^T with M X = lamG Y and M x = lamQ B, so one
 // basis serves every query: a batch is one GEMM (query dots), one pass over the graph (coherence drop), per-query column
@@ -154,6 +155,7 @@ void query_basis_solve(L& l, float tol, int32_t max_iters, float scale, bool fre
   std::copy(saved_pred, saved_pred + 3, l.predicted_iters);
   l.history = std::move(saved_hist);
   q.have = true;
+  ++q.gen;
   q.epoch = l.graph_epoch;
   q.scale = scale;
   if (ms) *ms = now_ms() - t0;
@@ -266,5 +268,301 @@ void query_mmr_many(L& l, const float* scores, int32_t Q, int32_t k, float lambd
     mmr_many_run(l, qs, nq, kk, lambda_div);
     HIP_CHECK(hipMemcpyAsync(ids + (size_t)c0 * kk, q.chosen_api.p, (size_t)nq * kk * 4, hipMemcpyDeviceToHost, l.stream));
     sync(l);
+  }
+}
+
+
+// ---- receipts --------------------------------------------------------------------------------------
+namespace {
+
+size_t rm_sum_size(const L& l) { return std::max<size_t>((size_t)4 * l.ld + 3, kQueryChunk); }
+
+// the per-basis terms: M x, the D-vectors of the anchor / query sums and the scalars beside them; with full != 0 also the
+// per-slot |P_i - P_j|^2 of the null-point residuals
+void ensure_receipt_basis(L& l, bool full) {
+  auto& q = l.query;
+  const bool need_sums = q.rm_gen != q.gen, need_d = full && q.rd_gen != q.gen;
+  if (!need_sums && !need_d) return;
+  const size_t n = (size_t)l.N;
+  RmBasisArgs b{};
+  b.X = q.X.p;
+  b.x4 = q.x4.p;
+  b.B = l.B.p;
+  b.sqrt_deg = l.sqrt_deg.p;
+  b.g = graph_view(l, path_active(l));
+  b.adj = l.ell_a.p;
+  b.op = ustar_op(l);
+  b.N = (int32_t)l.N;
+  b.D = l.D;
+  b.ld = l.ld;
+  q.Mx.alloc(n);
+  b.Mx = q.Mx.p;
+  if (need_d) {
+    q.dslot.alloc(n * l.width);
+    b.dslot = q.dslot.p;
+  }
+  launch_rm_basis_rows(b, l.stream);
+  if (need_d) q.rd_gen = q.gen;
+  if (!need_sums) return;
+  RmColArgs c{};
+  c.X = q.X.p;
+  c.x4 = q.x4.p;
+  c.Y = l.Y.p;
+  c.B = l.B.p;
+  c.Mx = q.Mx.p;
+  c.N = (int32_t)l.N;
+  c.D = l.D;
+  c.ld = l.ld;
+  c.nb = rm_col_parts(l.N);
+  q.rpart.alloc((size_t)c.nb * 4 * l.ld);
+  q.rspart.alloc((size_t)c.nb * 3);
+  q.rsum.alloc(rm_sum_size(l));
+  c.part = q.rpart.p;
+  c.spart = q.rspart.p;
+  launch_rm_cols(c, 0, l.stream);
+  q.rfin.alloc((size_t)rm_finish_groups(c.nb) * 4 * l.ld);
+  launch_rm_colfinish(q.rpart.p, c.nb, (int64_t)4 * l.ld, q.rsum.p, q.rfin.p, l.stream);
+  launch_rm_colfinish(q.rspart.p, c.nb, 3, q.rsum.p + (size_t)4 * l.ld, q.rfin.p, l.stream);
+  std::vector<double> h((size_t)4 * l.ld + 3);
+  HIP_CHECK(hipMemcpyAsync(h.data(), q.rsum.p, h.size() * 8, hipMemcpyDeviceToHost, l.stream));
+  sync(l);
+  q.rm_vec.assign((size_t)4 * l.D, 0.0);
+  for (int k = 0; k < 4; ++k)
+    for (int32_t d = 0; d < l.D; ++d) q.rm_vec[(size_t)k * l.D + d] = h[(size_t)k * l.ld + d];
+  q.rm_a0 = q.rm_b0 = 0.0;
+  for (int32_t d = 0; d < l.D; ++d) {  // the scalar sums: column by column, in column order
+    q.rm_a0 += q.rm_vec[(size_t)2 * l.D + d];
+    q.rm_b0 += q.rm_vec[(size_t)3 * l.D + d];
+  }
+  q.rm_a2 = h[(size_t)4 * l.ld];
+  q.rm_b2 = h[(size_t)4 * l.ld + 1];
+  q.rm_h2 = h[(size_t)4 * l.ld + 2];
+  q.rm_gen = q.gen;
+}
+
+double dot_f(const float* a, const double* b, int32_t D) {
+  double s = 0.0;
+  for (int32_t d = 0; d < D; ++d) s += (double)a[d] * b[d];
+  return s;
+}
+
+}  // namespace
+
+void query_receipt_many(L& l, const float* psis, int32_t Q, int32_t detail, float z_th, int32_t null_cap, double* dH,
+                        double* coh_sum, double* anchor_sum, double* query_sum, int32_t* null_total, int64_t* null_offsets,
+                        int32_t* i_out, int32_t* j_out, float* z_out, float* r_out, int64_t capacity) {
+  require_basis(l);
+  if (l.comm) throw Unsupported("osc_receipt_many: lattices with a communicator are not supported");
+  if (Q <= 0) {
+    if (null_offsets) null_offsets[0] = 0;
+    return;
+  }
+  const bool full = detail != 0;
+  auto& q = l.query;
+  ensure_receipt_basis(l, full);
+  const int32_t D = l.D, N = (int32_t)l.N;
+  const size_t n = (size_t)l.N;
+  // per call: h1 = E0^T (M x) over E0 = U - X - x psi0^T, and h0 = tr(E0^T M E0) through the operator's quad form
+  std::vector<float> psi0((size_t)l.ld, 0.f);
+  HIP_CHECK(hipMemcpyAsync(psi0.data(), l.psi.p, (size_t)l.ld * 4, hipMemcpyDeviceToHost, l.stream));
+  RmColArgs c{};
+  c.X = q.X.p;
+  c.x4 = q.x4.p;
+  c.Mx = q.Mx.p;
+  c.U = l.U.p;
+  c.psi0 = l.psi.p;
+  q.U0.alloc(n * l.ld);
+  c.U0 = q.U0.p;
+  c.N = N;
+  c.D = D;
+  c.ld = l.ld;
+  c.nb = rm_col_parts(l.N);
+  q.rpart.alloc((size_t)c.nb * 4 * l.ld);
+  q.rsum.alloc(rm_sum_size(l));
+  c.part = q.rpart.p;
+  launch_rm_cols(c, 1, l.stream);
+  q.rfin.alloc((size_t)rm_finish_groups(c.nb) * 4 * l.ld);
+  launch_rm_colfinish(q.rpart.p, c.nb, l.ld, q.rsum.p, q.rfin.p, l.stream);
+  std::vector<double> h1((size_t)l.ld);
+  HIP_CHECK(hipMemcpyAsync(h1.data(), q.rsum.p, h1.size() * 8, hipMemcpyDeviceToHost, l.stream));
+  sync(l);
+  const double h0 = quad_form_of_difference(l, l.U.p, q.U0.p);
+  const double* a1 = q.rm_vec.data();
+  const double* b1 = a1 + D;
+  for (int32_t t = 0; t < Q; ++t) {
+    const float* p = psis + (size_t)t * D;
+    double dh1 = 0.0, dd = 0.0, pp = 0.0;
+    for (int32_t d = 0; d < D; ++d) {
+      const double dl = (double)p[d] - (double)psi0[(size_t)d];
+      dh1 += dl * h1[(size_t)d];
+      dd += dl * dl;
+      pp += (double)p[d] * (double)p[d];
+    }
+    dH[t] = h0 - 2.0 * dh1 + dd * q.rm_h2;
+    if (full) {
+      anchor_sum[t] = (double)l.lamG * (q.rm_a0 + 2.0 * dot_f(p, a1, D) + pp * q.rm_a2);
+      query_sum[t] = (double)l.lamQ * (q.rm_b0 + 2.0 * dot_f(p, b1, D) + pp * q.rm_b2);
+    } else {
+      anchor_sum[t] = query_sum[t] = coh_sum[t] = 0.0;
+    }
+    null_total[t] = 0;
+  }
+  null_offsets[0] = 0;
+  if (!full) {
+    for (int32_t t = 0; t < Q; ++t) null_offsets[t + 1] = 0;
+    return;
+  }
+  // full detail: per chunk the query dots (GEMM), the fused row pass, then the null points per query
+  const int32_t kpad = query_kpad(D);
+  const int nw = rm_row_waves(l.N);
+  q.Bt.alloc((size_t)query_qpad(kQueryChunk) * kpad);
+  q.pn2.alloc(kQueryChunk);
+  q.pinv.alloc(kQueryChunk);
+  q.cohpart.alloc((size_t)nw * kQueryChunk);
+  q.cohfin.alloc((size_t)rm_finish_groups(nw) * kQueryChunk);
+  q.rtot.alloc(kQueryChunk);
+  q.rsel.alloc(kQueryChunk);
+  q.roff.alloc(kQueryChunk);
+  const int32_t* inv = permuted(l) ? l.inv_d.p : nullptr;
+  std::vector<float> bt;
+  std::vector<double> pn2, pinv, csum;
+  std::vector<int32_t> tot, sel, hi, hj;
+  std::vector<int64_t> off;
+  std::vector<float> hz, hr;
+  for (int32_t c0 = 0; c0 < Q; c0 += kQueryChunk) {
+    const int32_t nq = std::min<int32_t>(kQueryChunk, Q - c0);
+    const int32_t qs = query_qs(nq), qpad = query_qpad(nq);
+    q.align.alloc(n * qs);
+    q.pm.alloc(n * qs);
+    q.rz.alloc(n * qs);
+    q.rj.alloc(n * qs);
+    q.rr.alloc(n * qs);
+    q.zt.alloc(n * nq);
+    bt.assign((size_t)qpad * kpad, 0.f);
+    pn2.assign((size_t)nq, 0.0);
+    pinv.assign((size_t)nq, 0.0);
+    for (int32_t t = 0; t < nq; ++t) {
+      const float* p = psis + (size_t)(c0 + t) * D;
+      double s = 0.0;
+      for (int32_t d = 0; d < D; ++d) {
+        bt[(size_t)t * kpad + d] = p[d];
+        s += (double)p[d] * (double)p[d];
+      }
+      pn2[(size_t)t] = s;
+      pinv[(size_t)t] = 1.0 / (std::sqrt(s) + 1e-12);
+    }
+    HIP_CHECK(hipMemcpyAsync(q.Bt.p, bt.data(), bt.size() * 4, hipMemcpyHostToDevice, l.stream));
+    HIP_CHECK(hipMemcpyAsync(q.pn2.p, pn2.data(), (size_t)nq * 8, hipMemcpyHostToDevice, l.stream));
+    HIP_CHECK(hipMemcpyAsync(q.pinv.p, pinv.data(), (size_t)nq * 8, hipMemcpyHostToDevice, l.stream));
+    QueryGemmArgs g{};
+    g.A = q.X.p;
+    g.Bt = q.Bt.p;
+    g.N = N;
+    g.D = D;
+    g.ld = l.ld;
+    g.kpad = kpad;
+    g.qs = qs;
+    g.nq = nq;
+    g.mode = 0;
+    g.x4 = q.x4.p;
+    g.xn2 = q.xn2.p;
+    g.sqrt_deg = l.sqrt_deg.p;
+    g.pn2 = q.pn2.p;
+    g.pinv = q.pinv.p;
+    g.align = q.align.p;
+    g.p = q.pm.p;
+    launch_query_gemm(g, l.stream);
+    RmRowsArgs r{};
+    r.col = l.ell_col.p;
+    r.adj = l.ell_a.p;
+    r.deg = l.deg.p;
+    r.dslot = q.dslot.p;
+    r.s = q.s.p;
+    r.c0 = q.c0.p;
+    r.c2 = q.c2.p;
+    r.pn2 = q.pn2.p;
+    r.p = q.pm.p;
+    r.api_id = permuted(l) ? l.perm_d.p : nullptr;
+    r.width = l.width;
+    r.N = N;
+    r.qs = qs;
+    r.nq = nq;
+    r.nw = nw;
+    r.lamC = l.lamC;
+    r.z_th = z_th;
+    r.cohpart = q.cohpart.p;
+    r.z = q.rz.p;
+    r.j = q.rj.p;
+    r.r = q.rr.p;
+    launch_rm_rows(r, l.stream);
+    launch_rm_colfinish(q.cohpart.p, nw, nq, q.rsum.p, q.cohfin.p, l.stream);
+    launch_rm_transpose(q.rz.p, inv, N, qs, nq, q.zt.p, l.stream);
+    launch_rm_null_count(q.zt.p, N, nq, q.rtot.p, l.stream);
+    csum.assign((size_t)nq, 0.0);
+    tot.assign((size_t)nq, 0);
+    HIP_CHECK(hipMemcpyAsync(csum.data(), q.rsum.p, (size_t)nq * 8, hipMemcpyDeviceToHost, l.stream));
+    HIP_CHECK(hipMemcpyAsync(tot.data(), q.rtot.p, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
+    sync(l);
+    // kept per query: every null point, or the cap highest z (selected on the device up to kRmSelectMax, else here)
+    sel.assign((size_t)nq, 0);
+    off.assign((size_t)nq, 0);
+    int64_t dev_n = 0;
+    for (int32_t t = 0; t < nq; ++t) {
+      coh_sum[c0 + t] = csum[(size_t)t];
+      null_total[c0 + t] = tot[(size_t)t];
+      const bool capped = null_cap > 0 && tot[(size_t)t] > null_cap;
+      sel[(size_t)t] = capped && null_cap <= kRmSelectMax;
+      off[(size_t)t] = dev_n;
+      dev_n += sel[(size_t)t] ? null_cap : tot[(size_t)t];
+      const int64_t kept = capped ? null_cap : tot[(size_t)t];
+      null_offsets[c0 + t + 1] = null_offsets[c0 + t] + kept;
+    }
+    if (null_offsets[c0 + nq] > capacity) throw Invalid("osc_receipt_many: capacity too small for the null points");
+    if (dev_n == 0) continue;
+    q.roi.alloc((size_t)dev_n);
+    q.roj.alloc((size_t)dev_n);
+    q.roz.alloc((size_t)dev_n);
+    q.ror.alloc((size_t)dev_n);
+    HIP_CHECK(hipMemcpyAsync(q.roff.p, off.data(), (size_t)nq * 8, hipMemcpyHostToDevice, l.stream));
+    HIP_CHECK(hipMemcpyAsync(q.rsel.p, sel.data(), (size_t)nq * 4, hipMemcpyHostToDevice, l.stream));
+    RmSelectArgs sa{};
+    sa.zt = q.zt.p;
+    sa.j = q.rj.p;
+    sa.r = q.rr.p;
+    sa.inv = inv;
+    sa.off = q.roff.p;
+    sa.sel = q.rsel.p;
+    sa.N = N;
+    sa.qs = qs;
+    sa.nq = nq;
+    sa.cap = null_cap;
+    sa.oi = q.roi.p;
+    sa.oj = q.roj.p;
+    sa.oz = q.roz.p;
+    sa.orr = q.ror.p;
+    launch_rm_null_select(sa, l.stream);
+    hi.resize((size_t)dev_n);
+    hj.resize((size_t)dev_n);
+    hz.resize((size_t)dev_n);
+    hr.resize((size_t)dev_n);
+    HIP_CHECK(hipMemcpyAsync(hi.data(), q.roi.p, (size_t)dev_n * 4, hipMemcpyDeviceToHost, l.stream));
+    HIP_CHECK(hipMemcpyAsync(hj.data(), q.roj.p, (size_t)dev_n * 4, hipMemcpyDeviceToHost, l.stream));
+    HIP_CHECK(hipMemcpyAsync(hz.data(), q.roz.p, (size_t)dev_n * 4, hipMemcpyDeviceToHost, l.stream));
+    HIP_CHECK(hipMemcpyAsync(hr.data(), q.ror.p, (size_t)dev_n * 4, hipMemcpyDeviceToHost, l.stream));
+    sync(l);
+    for (int32_t t = 0; t < nq; ++t) {
+      const int64_t src = off[(size_t)t], dst = null_offsets[c0 + t], kept = null_offsets[c0 + t + 1] - dst;
+      std::vector<int64_t> order((size_t)(sel[(size_t)t] ? kept : tot[(size_t)t]));
+      for (size_t k = 0; k < order.size(); ++k) order[k] = src + (int64_t)k;
+      if (!sel[(size_t)t] && kept < (int64_t)order.size())  // a cap above the device selection's: the stable z sort here
+        std::stable_sort(order.begin(), order.end(), [&](int64_t x, int64_t y) { return hz[(size_t)x] > hz[(size_t)y]; });
+      for (int64_t k = 0; k < kept; ++k) {
+        const size_t s = (size_t)order[(size_t)k];
+        if (i_out) i_out[dst + k] = hi[s];
+        if (j_out) j_out[dst + k] = hj[s];
+        if (z_out) z_out[dst + k] = hz[s];
+        if (r_out) r_out[dst + k] = hr[s];
+      }
+    }
   }
 }

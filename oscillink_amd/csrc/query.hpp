@@ -91,3 +91,96 @@ void launch_query_pack(const float* score, const float* align, const int32_t* ch
                        float* out_score, float* out_align, hipStream_t st);
 
 }  // namespace osc
+
+// ---- multi-query receipts: receipt_many_kernels.hip ------------------------------------------
+namespace osc {
+
+constexpr int kRmSelectMax = 1024;  // largest null-point cap the device selection keeps (larger caps: host sort)
+
+// per basis, one wave per row: Mx_i = (M x)_i in fp64 (the U* operator with the lattice's gates / chain / lambdas), and
+// with dslot != nullptr d_ij = |P_i - P_j|^2 per ELL slot (k_query_basis_stats' dp, 0 where A_ij <= 0)
+struct RmBasisArgs {
+  const float* X;
+  const float* x4;
+  const float* B;
+  const float* sqrt_deg;
+  GraphView g;       // normalised weights + chain prior (the operator's)
+  const float* adj;  // capped adjacency (the receipt's weights)
+  OpParams op;
+  int32_t N, D, ld;
+  double* Mx;     // [N]
+  float* dslot;   // [N * width] or nullptr
+};
+void launch_rm_basis_rows(const RmBasisArgs& a, hipStream_t s);
+
+// deterministic fp64 column sums over the rows (row r goes to partial r % nb, summed in row order; the partials in block
+// order).  mode 0 (per basis): part[b][4][ld] = x_i (X - Y), B_i (x_i - 1) X, (X - Y)^2, B_i X^2 and spart[b][3] =
+// x_i^2, B_i (x_i - 1)^2, x_i Mx_i.  mode 1 (per call): part[b][1][ld] = (U - X - x psi0)_i Mx_i, and U0 = X + x psi0^T.
+struct RmColArgs {
+  const float* X;
+  const float* x4;
+  const float* Y;   // mode 0
+  const float* B;   // mode 0
+  const double* Mx;
+  const float* U;     // mode 1
+  const float* psi0;  // mode 1, [ld]
+  float* U0;          // mode 1, N x ld
+  int32_t N, D, ld, nb;
+  double* part;
+  double* spart;
+};
+int rm_col_parts(int64_t N);
+void launch_rm_cols(const RmColArgs& a, int mode, hipStream_t s);
+// out[w] = sum_b part[b * W + w] in block order: directly up to kRmFinishRows partials, else by groups of that many
+// (scratch: rm_finish_groups(nb) * W doubles), then the groups in order
+constexpr int kRmFinishRows = 64;
+inline int rm_finish_groups(int nb) { return (nb + kRmFinishRows - 1) / kRmFinishRows; }
+void launch_rm_colfinish(const double* part, int nb, int64_t W, double* out, double* scratch, hipStream_t s);
+
+// fused per-(row, query) pass over the graph: the coherence drop's per-wave sums and each row's null-point candidate
+// R_ij = lamC A_ij (d_ij + 2 (s_i - s_j)(p_i - p_j) + (s_i - s_j)^2 |psi|^2), fp64 S1 / S2 / first argmax.
+// Rows are dealt to nw waves round-robin (fixed for a lattice): cohpart[w * nq + q].  z / j / r are N x qs (device rows;
+// j an API id, z = -inf where the row has no null point).
+struct RmRowsArgs {
+  const int32_t* col;
+  const float* adj;
+  const int32_t* deg;
+  const float* dslot;
+  const float* s;
+  const double* c0;
+  const double* c2;
+  const double* pn2;
+  const float* p;
+  const int32_t* api_id;  // nullptr = identity
+  int32_t width, N, qs, nq, nw;
+  float lamC, z_th;
+  double* cohpart;
+  float* z;
+  int32_t* j;
+  float* r;
+};
+int rm_row_waves(int64_t N);
+void launch_rm_rows(const RmRowsArgs& a, hipStream_t s);
+
+// zt[q * N + a] = z[dev(a) * qs + q]: per query, API row order (inv = API row -> device row, nullptr = identity)
+void launch_rm_transpose(const float* z, const int32_t* inv, int32_t N, int32_t qs, int32_t nq, float* zt, hipStream_t s);
+// total[q] = number of null points of query q
+void launch_rm_null_count(const float* zt, int32_t N, int32_t nq, int32_t* total, hipStream_t s);
+// per query the kept records at out + off[q]: the cap highest z (ties in API row order) in that order when sel[q] != 0
+// (total > cap, cap <= kRmSelectMax), else every null point in API row order
+struct RmSelectArgs {
+  const float* zt;
+  const int32_t* j;     // N x qs
+  const float* r;       // N x qs
+  const int32_t* inv;   // nullptr = identity
+  const int64_t* off;   // [nq]
+  const int32_t* sel;   // [nq]
+  int32_t N, qs, nq, cap;
+  int32_t* oi;
+  int32_t* oj;
+  float* oz;
+  float* orr;
+};
+void launch_rm_null_select(const RmSelectArgs& a, hipStream_t s);
+
+}  // namespace osc

@@ -814,6 +814,138 @@ class OscillinkLattice:
         return [[{"id": int(i), "score": float(s), "align": float(a)} for i, s, a in zip(ids[q].tolist(), score[q].tolist(),
                                                                                     align[q].tolist())] for q in range(Q)]
 
+    def receipt_many(self, psis: np.ndarray, *, tol: float = 1e-4, max_iters: int = 256, as_arrays: bool = False):
+        """`receipt()` for each row of `psis` (Q x D), as if `set_query(psis[q]); receipt()` had run with the current U,
+        gates, chain, lambdas and receipt / signature settings held fixed, without touching the lattice's state.  U*(psi_q)
+        comes from the query basis `bundle_many` uses (same key, cache and tolerance contract): every
+        energy is a quadratic in psi over per-basis and per-call terms, and full detail adds one GEMM and one graph pass per
+        256 queries.  The meta's ustar_* fields describe the basis (`"ustar_source": "query_basis"`).
+
+        Full detail at a large N reports a null point on most rows (about N per query): set OSCILLINK_RECEIPT_NULL_CAP
+        (the cap is selected on the device) or use `as_arrays=True`, which returns a dict of NumPy arrays instead of dicts:
+        deltaH, coh_drop_sum, anchor_pen_sum, query_term_sum, null_total (Q each), null_offsets (Q + 1) and the kept null
+        points null_i / null_j / null_z / null_r of every query, concatenated."""
+        if self._has_comm:
+            raise NotImplementedError("receipt_many: lattices with a communicator (sharded / multi-rank) are not supported")
+        P = np.asarray(psis)
+        if P.ndim != 2 or P.shape[1] != self.D:
+            raise ValueError(f"psis must be a (Q, {self.D}) array, got shape {P.shape}")
+        P = np.ascontiguousarray(P, dtype=np.float32)
+        bad = np.nonzero(~np.all(np.isfinite(P), axis=1))[0]
+        if bad.size:
+            raise ValueError(f"psis row {int(bad[0])} is not finite")
+        Q = int(P.shape[0])
+        full = self._receipt_detail != "light"
+        try:
+            cap_val = int(os.getenv("OSCILLINK_RECEIPT_NULL_CAP", "0").strip())
+        except ValueError:
+            cap_val = 0
+        sums = np.zeros((4, Q), dtype=np.float64)  # deltaH, coh, anchor, query
+        total = np.zeros(Q, dtype=np.int32)
+        offsets = np.zeros(Q + 1, dtype=np.int64)
+        capacity = Q * (min(cap_val, self.N) if cap_val > 0 else self.N) if full else 0
+        ni = np.zeros(max(capacity, 1), dtype=np.int32)
+        nj = np.zeros(max(capacity, 1), dtype=np.int32)
+        nz = np.zeros(max(capacity, 1), dtype=np.float32)
+        nr = np.zeros(max(capacity, 1), dtype=np.float32)
+        solved = False
+        if Q > 0:
+            n0 = self.stats["query_basis_solves"]
+            self._ensure_query_basis(tol, max_iters, float(np.max(np.abs(P))))
+            solved = self.stats["query_basis_solves"] != n0
+            self._call("osc_receipt_many", nat.f32(P), Q, int(full), 3.0, max(cap_val, 0),
+                       *[sums[t].ctypes.data_as(nat.c_f64p) for t in range(4)], nat.i32(total), nat.i64(offsets),
+                       nat.i32(ni), nat.i32(nj), nat.f32(nz), nat.f32(nr), int(capacity))
+        # the float32 rounding receipt() gives its energies (a float32 dH / np.sum over float32 rows)
+        sums = sums.astype(np.float32).astype(np.float64)
+        kept = int(offsets[-1])
+        self._log("receipt_many", {"Q": Q, "receipt_detail": self._receipt_detail, "basis_solved": solved,
+                                   "null_points": kept})
+        if as_arrays:
+            return {"deltaH": sums[0], "coh_drop_sum": sums[1], "anchor_pen_sum": sums[2], "query_term_sum": sums[3],
+                    "null_total": total.astype(np.int64), "null_offsets": offsets, "null_i": ni[:kept].copy(),
+                    "null_j": nj[:kept].copy(), "null_z": nz[:kept].copy(), "null_r": nr[:kept].copy()}
+        if Q == 0:
+            return []
+        # everything but psi, the energies, the null points and the ustar fields is shared by the batch
+        nnz, _, _ = self.graph_stats()
+        qb = self.last_query_basis
+        res_X, res_x = float(qb["res"]["X"]), float(qb["res"]["x"])
+        adj_sig = hashlib.sha256(np.ascontiguousarray(self._edge_prefix()).tobytes()).hexdigest()
+        sig_rest = {"lam": [self.lamG, self.lamC, self.lamQ, self.lamP], "chain_present": self._chain_nodes is not None,
+                    "chain_len": len(self._chain_nodes) if self._chain_nodes else 0, "k": self._kneighbors,
+                    "detk": self._deterministic_k, "adj": adj_sig}
+        common = {
+            "graph_build_ms": float(self._graph_build_ms),
+            "last_settle_ms": float(self.last.get("t_ms") or 0.0),
+            "avg_degree": float(nnz / max(self.N, 1)),
+            "edge_density": float(nnz / max(self.N * (self.N - 1), 1)),
+            "gates_min": float(np.min(self._B)),
+            "gates_max": float(np.max(self._B)),
+            "gates_mean": float(np.mean(self._B)),
+            "gates_uniform": bool(np.allclose(self._B, self._B[0])),
+        }
+        dyn = self._last_dynamics if os.getenv("OSCILLINK_RECEIPT_DYNAMICS", "0").strip().lower() in {"1", "true", "yes"} \
+            else None
+        psi_inf = np.max(np.abs(P), axis=1) if self.D else np.zeros(Q)
+        out = []
+        for q in range(Q):
+            sig = self._signature_digest({"psi": np.round(P[q], 6).tolist(), **sig_rest}, self._B)
+            dH = float(sums[0, q])
+            res_q = res_X + float(psi_inf[q]) * res_x
+            ustar = {"ustar_iters": int(qb["iters"]["X"]), "ustar_res": float(res_q), "ustar_converged": bool(res_q <= tol)}
+            if full:
+                s, e = int(offsets[q]), int(offsets[q + 1])
+                nulls = self._null_dicts(ni[s:e], nj[s:e], nz[s:e], nr[s:e], e - s)
+                tot = int(total[q])
+            else:
+                nulls, tot = [], 0
+            capped = cap_val > 0 and tot > cap_val
+            meta: dict[str, Any] = {
+                "ustar_cached": not solved,
+                "ustar_solves": int(self.stats["ustar_solves"]),
+                "ustar_cache_hits": int(self.stats["ustar_cache_hits"]),
+                "ustar_converged": ustar["ustar_converged"],
+                "ustar_res": ustar["ustar_res"],
+                "ustar_iters": ustar["ustar_iters"],
+                "ustar_solve_ms": float(qb["solve_ms"]) if solved else 0.0,
+                "ustar_source": "query_basis",
+                **common,
+                "state_sig": sig,
+                "receipt_detail": self._receipt_detail,
+                "null_points_summary": {"total_null_points": tot, "returned_null_points": cap_val if capped else tot,
+                                        "null_cap_applied": bool(capped)},
+            }
+            if self._receipt_secret is not None:
+                if self._signature_mode == "extended":
+                    payload = {
+                        "sig_v": 1, "mode": "extended", "state_sig": sig, "deltaH_total": dH, **ustar,
+                        "params": {"lamG": self.lamG, "lamC": self.lamC, "lamQ": self.lamQ, "lamP": self.lamP},
+                        "graph": {"k": self._kneighbors, "deterministic_k": self._deterministic_k,
+                                  "neighbor_seed": self._neighbor_seed},
+                    }
+                else:
+                    payload = {"sig_v": 1, "mode": "minimal", "state_sig": sig, "deltaH_total": dH}
+                raw = json.dumps(payload, sort_keys=True).encode("utf-8")
+                meta["signature"] = {"algorithm": "HMAC-SHA256", "payload": payload,
+                                     "signature": hmac.new(self._receipt_secret, raw, hashlib.sha256).hexdigest()}
+            rec = {
+                "version": str(__version__),
+                "deltaH_total": dH,
+                "coh_drop_sum": float(sums[1, q]),
+                "anchor_pen_sum": float(sums[2, q]),
+                "query_term_sum": float(sums[3, q]),
+                "cg_iters": int(self.last.get("iters") or 0),
+                "residual": float(self.last.get("res") or 0.0),
+                "t_ms": float(self.last.get("t_ms") or 0.0),
+                "null_points": nulls,
+                "meta": meta,
+            }
+            if dyn:
+                meta["dynamics"] = dyn
+            out.append(rec)
+        return out
+
     def query_basis(self, tol: float = 1e-4, max_iters: int = 256) -> tuple[np.ndarray, np.ndarray]:
         """The query basis (X N x D, x N) in API row order: U*(psi) = X + x psi^T (diagnostic; not in the reference).
         Solved for the current psi's |psi|_inf unless a basis of the same graph, gates, chain, lambdas and tolerance is
