@@ -222,6 +222,36 @@ int osc_receipt_many(osc_handle h, const float* psis, int32_t Q, int32_t detail,
  * out_idx Q x min(k, N) API ids, the same picks as osc_mmr per column up to rounding of the similarities. */
 int osc_mmr_many(osc_handle h, const float* scores, int32_t Q, int32_t k, float lambda_div, int32_t* out_idx);
 
+/* ---- corpus refine (not in the reference) ------------------------------------------------------
+ * A corpus Y (N x D, D <= 1536) resident on the device as Y and Yn = Y / (|Y_i| + 1e-12) (osc_create's normalisation), both
+ * at a row pitch of D rounded up to 32 floats, and nothing else: 8 N ldn bytes.  Queries run OSC_CORPUS_CHUNK (read at
+ * creation, default 256) at a time, fewer when one chunk's scratch would pass 1 GiB. */
+typedef struct osc_corpus* osc_corpus_handle;
+int osc_corpus_create(const float* Y, int64_t N, int32_t D, int32_t device, osc_corpus_handle* out);
+int osc_corpus_destroy(osc_corpus_handle h);
+const char* osc_corpus_last_error(osc_corpus_handle h);  /* h may be NULL: error of the last failed osc_corpus_create */
+/* queries per chunk and one chunk's scratch bytes for a refine of these settings (measurement aid) */
+int osc_corpus_info(osc_corpus_handle h, int32_t top_k, int32_t kneighbors, int32_t k, int32_t* chunk, int64_t* bytes);
+/* The candidate step of the reference's retrieval loop (scripts/bench_beir.py:84-94 `argpartition` top-K of D @ psi;
+ * scripts/real_benchmark.py:328-343, examples/rag_replacement.py:48-66): per query the K = min(top_k, N) corpus rows of the
+ * largest cosine Yn_i . psi / (|psi| + 1e-12), ties to the smaller id, in that order.  ids / cos: Q x K.  top_k <= 1024. */
+int osc_corpus_search(osc_corpus_handle h, const float* psis, int32_t Q, int32_t top_k, int32_t* ids, float* cos);
+/* The whole loop body for Q queries (scripts/bench_beir.py:84-94, scripts/competitor_benchmark.py:236-247):
+ * `Oscillink(Y[cand], kneighbors, row_cap, lamG, lamC, lamQ); set_query(psi); bundle(k, alpha)` with U* solved from x0 = Y
+ * (lattice.py:245-263; tol / max_iters as solve_Ustar) and mmr lambda 0.5.  cand_in (Q x K) replaces the search when not
+ * NULL.  min(kneighbors, K - 1) <= 128 (the dense build route).  Out: cand_out Q x K; local / score / align Q x min(k, K),
+ * local = the pick's row in its candidate lattice; iters / res per query (the U* solve's). */
+int osc_corpus_refine(osc_corpus_handle h, const float* psis, int32_t Q, int32_t top_k, const int32_t* cand_in,
+                      int32_t kneighbors, float row_cap, float lamG, float lamC, float lamQ, float tol, int32_t max_iters,
+                      int32_t k, float alpha, int32_t* cand_out, int32_t* local, float* score, float* align, int32_t* iters,
+                      float* res);
+/* The candidate lattice's graph of one query (mutual_knn_adj + row_sum_cap + normalized_laplacian, graph.py:8-93) as
+ * osc_get_csr gives it for `Oscillink(Y[cand])`: rowptr K + 1, col / a / w nnz (<= capacity), sqrt_deg K; local row ids.
+ * Test / diagnostic aid. */
+int osc_corpus_graph(osc_corpus_handle h, const float* psi, const int32_t* cand_in, int32_t top_k, int32_t kneighbors,
+                     float row_cap, int32_t* cand_out, int64_t* rowptr, int32_t* col, float* a, float* w, float* sqrt_deg,
+                     int64_t capacity, int64_t* nnz);
+
 /* ---- receipts ------------------------------------------------------------------------------- */
 /* deltaH_trace (receipts.py:10-25) on the resident U and U* */
 int osc_deltaH(osc_handle h, double* dH);

@@ -71,6 +71,16 @@ SIGNATURES = {
     "osc_mmr_many": (C.c_int, [Handle, c_f32p, C.c_int32, C.c_int32, C.c_float, c_i32p]),
     "osc_receipt_many": (C.c_int, [Handle, c_f32p, C.c_int32, C.c_int32, C.c_float, C.c_int32, c_f64p, c_f64p, c_f64p, c_f64p,
                                    c_i32p, c_i64p, c_i32p, c_i32p, c_f32p, c_f32p, C.c_int64]),
+    "osc_corpus_create": (C.c_int, [c_f32p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(Handle)]),
+    "osc_corpus_destroy": (C.c_int, [Handle]),
+    "osc_corpus_last_error": (C.c_char_p, [Handle]),
+    "osc_corpus_info": (C.c_int, [Handle, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_i64p]),
+    "osc_corpus_search": (C.c_int, [Handle, c_f32p, C.c_int32, C.c_int32, c_i32p, c_f32p]),
+    "osc_corpus_refine": (C.c_int, [Handle, c_f32p, C.c_int32, C.c_int32, c_i32p, C.c_int32, C.c_float, C.c_float, C.c_float,
+                                    C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_float, c_i32p, c_i32p, c_f32p, c_f32p,
+                                    c_i32p, c_f32p]),
+    "osc_corpus_graph": (C.c_int, [Handle, c_f32p, c_i32p, C.c_int32, C.c_int32, C.c_float, c_i32p, c_i64p, c_i32p, c_f32p,
+                                   c_f32p, c_f32p, C.c_int64, c_i64p]),
     "osc_deltaH": (C.c_int, [Handle, c_f64p]),
     "osc_receipt_components": (C.c_int, [Handle, c_f32p, c_f32p, c_f32p]),
     "osc_null_points": (C.c_int, [Handle, C.c_float, c_i32p, c_i32p, c_f32p, c_f32p, c_i32p]),

@@ -1,0 +1,219 @@
+"""`Corpus` -- the reference's retrieval loop (scripts/bench_beir.py:84-94, examples/rag_replacement.py:48-66) as one
+batched device call per chunk of queries.
+
+For each query the loop takes the top-K cosine candidates of a corpus, builds `Oscillink(Y[cand], ...)`, sets the query
+and asks for `bundle(k, alpha)`.  Every query has its own K-row graph, so the shared-graph batching of `bundle_many`
+does not apply; here every lattice of a chunk is built, solved and bundled by the same few launches.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from typing import Any, Optional
+
+import numpy as np
+
+from . import _native as nat
+
+MAX_TOP_K = 1024  # one key per thread of the per-query select (include/oscillink_hip.h)
+MAX_KNEIGHBORS = 128  # the dense build route's per-row list (k_knn_select)
+MAX_D = 1536  # the bundle kernel keeps the normalised query in LDS
+USTAR_TOL, USTAR_MAX_ITERS = 1e-4, 64  # _ensure_device_ustar's settings
+
+
+class Corpus:
+    """A corpus Y (N x D, finite) resident on the device as Y and its row-normalised copy Yn (osc_create's arithmetic),
+    both at a row pitch of D rounded up to 32 floats: 8 N ceil32(D) bytes, no lattice solver arrays.  Per call, queries
+    run in chunks whose scratch stays under 1 GiB (OSC_CORPUS_CHUNK, read at creation, caps the queries per chunk)."""
+
+    def __init__(self, Y: np.ndarray, *, device: Optional[int] = None):
+        if not isinstance(Y, np.ndarray) or Y.ndim != 2 or Y.shape[0] < 1 or Y.shape[1] < 1:
+            raise ValueError("Y must be a non-empty 2D numpy array")
+        Yc = np.ascontiguousarray(Y, dtype=np.float32)
+        if not np.all(np.isfinite(Yc)):
+            raise ValueError("Y must be finite")
+        self.N, self.D = Yc.shape
+        if self.D > MAX_D:
+            raise ValueError(f"Corpus supports D <= {MAX_D}, got {self.D}")
+        if device is None:
+            device = int(os.environ.get("OSCILLINK_DEVICE", os.environ.get("LOCAL_RANK", "0")))
+        self._h = None
+        L = nat.lib()
+        if nat.device_count() < 1:
+            raise nat.NativeError("no HIP device visible: oscillink_amd runs on MI355X (gfx950) only, no CPU fallback")
+        h = nat.Handle()
+        rc = L.osc_corpus_create(nat.f32(Yc), self.N, self.D, int(device), C.byref(h))
+        if rc != nat.OSC_OK:
+            msg = L.osc_corpus_last_error(None)
+            text = msg.decode("utf-8", "replace") if msg else "osc_corpus_create"
+            if rc == nat.OSC_E_INVALID:
+                raise ValueError(text)
+            raise nat.NativeError(f"osc_corpus_create failed ({rc}): {text}")
+        self._h = h
+
+    # ------------------------------------------------------------------ lifetime
+    def close(self) -> None:
+        h = getattr(self, "_h", None)
+        if h is not None:
+            try:
+                nat.lib().osc_corpus_destroy(h)
+            finally:
+                self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self) -> "Corpus":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def _call(self, name: str, *args) -> None:
+        if self._h is None:
+            raise ValueError("Corpus is closed")
+        rc = getattr(nat.lib(), name)(self._h, *args)
+        if rc == nat.OSC_OK:
+            return
+        msg = nat.lib().osc_corpus_last_error(self._h)
+        text = (msg.decode("utf-8", "replace") if msg else "") or name
+        if rc == nat.OSC_E_INVALID:
+            raise ValueError(text)
+        raise nat.NativeError(f"{name} failed ({rc}): {text}")
+
+    # ------------------------------------------------------------------ validation
+    def _queries(self, psis) -> np.ndarray:
+        if self._h is None:
+            raise ValueError("Corpus is closed")
+        P = np.asarray(psis)
+        if P.ndim != 2 or P.shape[1] != self.D:
+            raise ValueError(f"psis must be a (Q, {self.D}) array, got shape {P.shape}")
+        P = np.ascontiguousarray(P, dtype=np.float32)
+        bad = np.nonzero(~np.all(np.isfinite(P), axis=1))[0]
+        if bad.size:
+            raise ValueError(f"psis row {int(bad[0])} is not finite")
+        return P
+
+    def _top_k(self, top_k: int) -> int:
+        if int(top_k) < 1 or int(top_k) > MAX_TOP_K:
+            raise ValueError(f"top_k must be between 1 and {MAX_TOP_K}, got {top_k}")
+        return min(int(top_k), self.N)
+
+    @staticmethod
+    def _knn(kneighbors: int, K: int) -> int:
+        if int(kneighbors) < 1:
+            raise ValueError("kneighbors must be >= 1")
+        eff = min(int(kneighbors), max(1, K - 1))
+        if eff > MAX_KNEIGHBORS:
+            raise ValueError(f"min(kneighbors, K - 1) = {eff} exceeds the limit of {MAX_KNEIGHBORS} (the dense route)")
+        return eff
+
+    def _candidates(self, candidates, Q: int, K: int) -> np.ndarray:
+        cand = np.asarray(candidates)
+        if cand.shape != (Q, K):
+            raise ValueError(f"candidates must be a ({Q}, {K}) array, got shape {cand.shape}")
+        if cand.size and (not np.issubdtype(cand.dtype, np.integer)):
+            raise ValueError("candidates must hold integer corpus ids")
+        cand = np.ascontiguousarray(cand, dtype=np.int64)
+        if cand.size and (cand.min() < 0 or cand.max() >= self.N):
+            raise ValueError(f"candidates: corpus ids must lie in [0, {self.N})")
+        if cand.size and np.any(np.diff(np.sort(cand, axis=1), axis=1) == 0):
+            raise ValueError("candidates: repeated id within a row")
+        return cand.astype(np.int32)
+
+    # ------------------------------------------------------------------ public API
+    def search(self, psis, top_k: int):
+        """Per query the K = min(top_k, N) corpus ids of the largest cosine Yn_i . psi / (|psi| + 1e-12) (fp32 on the
+        device), ties to the smaller id, in that order.  Returns (ids int32 (Q, K), cos float32 (Q, K))."""
+        P = self._queries(psis)
+        K = self._top_k(top_k)
+        Q = P.shape[0]
+        ids = np.zeros((Q, K), dtype=np.int32)
+        cos = np.zeros((Q, K), dtype=np.float32)
+        if Q:
+            self._call("osc_corpus_search", nat.f32(P), Q, int(top_k), nat.i32(ids), nat.f32(cos))
+        return ids, cos
+
+    def refine_many(self, psis, top_k: int, k: int = 8, alpha: float = 0.5, *, kneighbors: int = 6,
+                    row_cap_val: float = 1.0, lamG: float = 1.0, lamC: float = 0.5, lamQ: float = 4.0,
+                    deterministic_k: bool = False, neighbor_seed: Optional[int] = None, candidates=None,
+                    as_arrays: bool = False):
+        """For each query q, what the reference's loop returns with `cand = search(psis, top_k)[0][q]` (or
+        `candidates[q]`):
+
+            lat = Oscillink(Y[cand], kneighbors, row_cap_val, lamG, lamC, lamQ, deterministic_k, neighbor_seed)
+            lat.set_query(psis[q]); lat.bundle(k, alpha)   # with "id" mapped back to corpus ids
+
+        `settle()` is not run and cannot change the answer: bundle() reads only U*, which is solved from x0 = Y
+        (reference lattice.py:245-263) with _ensure_device_ustar's settings (tol 1e-4, 64 iterations, Jacobi).
+        `deterministic_k` / `neighbor_seed` mean what they mean for Oscillink: the device uses one total order
+        (similarity desc, index asc) either way.  Limits: 1 <= top_k <= 1024, min(kneighbors, K - 1) <= 128.
+
+        Returns Q lists of {"id", "score", "align"}, or with `as_arrays=True` a dict of `ids`, `local`, `score`, `align`
+        (Q, min(k, K)), `candidates` (Q, K), `ustar_iters` and `ustar_res` (Q,)."""
+        P = self._queries(psis)
+        K = self._top_k(top_k)
+        knn = self._knn(kneighbors, K)  # noqa: F841 (validation)
+        if float(lamG) <= 0:
+            raise ValueError("lamG must be > 0 for SPD")
+        for name, val in (("lamC", lamC), ("lamQ", lamQ)):
+            if float(val) < 0:
+                raise ValueError(f"{name} must be >= 0")
+        Q = P.shape[0]
+        cand_in = None if candidates is None else self._candidates(candidates, Q, K)
+        kk = min(max(int(k), 0), K)
+        cand = np.zeros((Q, K), dtype=np.int32)
+        local = np.zeros((Q, kk), dtype=np.int32)
+        score = np.zeros((Q, kk), dtype=np.float32)
+        align = np.zeros((Q, kk), dtype=np.float32)
+        iters = np.zeros(Q, dtype=np.int32)
+        res = np.zeros(Q, dtype=np.float32)
+        if Q:
+            self._call("osc_corpus_refine", nat.f32(P), Q, int(top_k), None if cand_in is None else nat.i32(cand_in),
+                       int(kneighbors), float(row_cap_val), float(lamG), float(lamC), float(lamQ), USTAR_TOL,
+                       USTAR_MAX_ITERS, kk, float(alpha), nat.i32(cand), nat.i32(local), nat.f32(score), nat.f32(align),
+                       nat.i32(iters), nat.f32(res))
+        ids = np.take_along_axis(cand, local, axis=1) if kk else np.zeros((Q, 0), dtype=np.int32)
+        if as_arrays:
+            return {"ids": ids, "local": local, "score": score, "align": align, "candidates": cand,
+                    "ustar_iters": iters, "ustar_res": res}
+        return [[{"id": int(i), "score": float(s), "align": float(a)} for i, s, a in
+                 zip(ids[q].tolist(), score[q].tolist(), align[q].tolist())] for q in range(Q)]
+
+    def info(self, top_k: int, kneighbors: int = 6, k: int = 8) -> dict[str, Any]:
+        """Queries per chunk and one chunk's device scratch for a refine with these settings."""
+        K = self._top_k(top_k)
+        self._knn(kneighbors, K)
+        chunk, nbytes = C.c_int32(0), C.c_int64(0)
+        self._call("osc_corpus_info", int(top_k), int(kneighbors), int(k), C.byref(chunk), C.byref(nbytes))
+        return {"chunk": int(chunk.value), "scratch_bytes": int(nbytes.value)}
+
+    # ------------------------------------------------------------------ test diagnostics
+    def _candidate_graph(self, psi_or_candidates, top_k: int, kneighbors: int = 6, row_cap_val: float = 1.0):
+        """The candidate lattice's graph (rowptr, col, a, w, sqrt_deg) in local order, in the form of graph_csr().
+        A float vector of D entries is a query (its search gives the candidates); an integer vector is the candidates."""
+        K = self._top_k(top_k)
+        kn = self._knn(kneighbors, K)
+        v = np.asarray(psi_or_candidates)
+        psi = np.zeros((1, self.D), dtype=np.float32)
+        cand_in = None
+        if np.issubdtype(v.dtype, np.integer):
+            cand_in = self._candidates(v.reshape(1, -1), 1, K)
+        else:
+            psi = self._queries(v.reshape(1, -1))
+        cap = max(1, K * max(1, kn))
+        cand = np.zeros(K, dtype=np.int32)
+        rowptr = np.zeros(K + 1, dtype=np.int64)
+        col = np.zeros(cap, dtype=np.int32)
+        a = np.zeros(cap, dtype=np.float32)
+        w = np.zeros(cap, dtype=np.float32)
+        sd = np.zeros(K, dtype=np.float32)
+        nnz = C.c_int64(0)
+        self._call("osc_corpus_graph", nat.f32(psi), None if cand_in is None else nat.i32(cand_in), int(top_k),
+                   int(kneighbors), float(row_cap_val), nat.i32(cand), nat.i64(rowptr), nat.i32(col), nat.f32(a),
+                   nat.f32(w), nat.f32(sd), cap, C.byref(nnz))
+        n = int(nnz.value)
+        return rowptr, col[:n].copy(), a[:n].copy(), w[:n].copy(), sd

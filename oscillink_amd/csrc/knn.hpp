@@ -16,6 +16,10 @@ void launch_knn_topk(const KnnPlan& p, const float* Yop, int32_t ld, int32_t N, 
 // small lattices (N <= 4096): dense similarity matrix Sm (N x lds_ floats of scratch) + per-row selection of the k best
 void launch_knn_dense(const float* Yn, int32_t ldn, int32_t N, int32_t k, float* Sm, int32_t lds_, float* out_val,
                       int32_t* out_idx, hipStream_t s);
+// the same for nlat lattices of N rows each stored back to back (Yn: nlat x N rows of ldn, Sm: nlat x N rows of lds_): the
+// lists are the union's (nlat x N rows, column ids offset by the lattice's first row), bit-identical per lattice
+void launch_knn_dense_many(const float* Yn, int32_t ldn, int32_t N, int32_t nlat, int32_t k, float* Sm, int32_t lds_,
+                           float* out_val, int32_t* out_idx, hipStream_t s);
 // any k (the k > 128 route): rows [row_begin, row_begin + rows) of the dense similarity matrix into the scratch Sm
 // (rows_cap x lds_ floats, rows <= rows_cap, lds_ >= N) and a radix select of each row's k best columns; row_begin must
 // be a multiple of 128.  out_val / out_idx are the full N x k lists.

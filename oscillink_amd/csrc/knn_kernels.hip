@@ -365,9 +365,14 @@ __global__ __launch_bounds__(256, 2) void k_knn_topk(const float* __restrict__ Y
 // lists (N = 1200: 374 us of a 0.5 ms build).  Here one workgroup per (row block, column tile) writes its 128 x 128
 // tile of S = Yn Yn^T (same staging, fragment order and MFMA sequence as knn_topk_body, so S is bitwise symmetric and
 // bit-identical to what the streaming kernel scores), and one wave per row then picks the k best by repeated argmax.
+// (blockIdx.z = lattice of a batch of equal-sized lattices stored back to back: rows lat_yn floats apart in Yn, lat_sm in Sm;
+// single-lattice launches pass 0 and one z)
 __global__ __launch_bounds__(256, 2) void k_knn_dense(const float* __restrict__ Yn, int32_t ldn, int32_t N,
-                                                      float* __restrict__ Sm, int32_t lds_, int32_t row_base) {
+                                                      float* __restrict__ Sm, int32_t lds_, int32_t row_base,
+                                                      int64_t lat_yn, int64_t lat_sm) {
   __shared__ __attribute__((aligned(16))) float lds[2 * BM * LDT];
+  Yn += blockIdx.z * lat_yn;
+  Sm += blockIdx.z * lat_sm;
   float* As = lds;
   float* Bs = lds + BM * LDT;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -445,12 +450,17 @@ __global__ __launch_bounds__(256, 2) void k_knn_dense(const float* __restrict__ 
 
 // one wave per row: the k best columns by (similarity desc, index asc), diagonal excluded (graph.py:37, 46-49), values
 // clipped at 0 (graph.py:62).  M = registers per lane (64 M >= N).
+// (blockIdx.y = lattice of a batch as in k_knn_dense: its rows and column ids are offset by blockIdx.y * N in the lists)
 template <int M>
 __global__ __launch_bounds__(256) void k_knn_select(const float* __restrict__ Sm, int32_t lds_, int32_t N, int32_t k,
-                                                    float* out_val, int32_t* out_idx) {
+                                                    float* out_val, int32_t* out_idx, int64_t lat_sm) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= N) return;
+  Sm += blockIdx.y * lat_sm;
+  out_val += (size_t)blockIdx.y * N * k;
+  out_idx += (size_t)blockIdx.y * N * k;
+  const int id0 = (int)blockIdx.y * N;
   float v[M];
 #pragma unroll
   for (int m = 0; m < M; ++m) {
@@ -486,7 +496,7 @@ __global__ __launch_bounds__(256) void k_knn_select(const float* __restrict__ Sm
     }
     if (lane == 0) {
       out_val[(size_t)row * k + r] = fmaxf(wv, 0.f);
-      out_idx[(size_t)row * k + r] = wi;
+      out_idx[(size_t)row * k + r] = id0 + wi;
     }
   }
 }
@@ -1363,12 +1373,19 @@ void launch_knn_topk(const KnnPlan& p, const float* Yop, int32_t ld, int32_t N, 
 
 void launch_knn_dense(const float* Yn, int32_t ldn, int32_t N, int32_t k, float* Sm, int32_t lds_, float* out_val,
                       int32_t* out_idx, hipStream_t s) {
+  launch_knn_dense_many(Yn, ldn, N, 1, k, Sm, lds_, out_val, out_idx, s);
+}
+
+void launch_knn_dense_many(const float* Yn, int32_t ldn, int32_t N, int32_t nlat, int32_t k, float* Sm, int32_t lds_,
+                           float* out_val, int32_t* out_idx, hipStream_t s) {
   if (N > 8192) throw std::runtime_error("launch_knn_dense: N > 8192");
+  if (nlat < 1) return;
   const int nb = (N + BM - 1) / BM;
-  hipLaunchKernelGGL(k_knn_dense, dim3(nb, nb), dim3(256), 0, s, Yn, ldn, N, Sm, lds_, 0);
-  const dim3 grid((unsigned)((N + 3) / 4)), block(256);
+  const int64_t lat_yn = (int64_t)N * ldn, lat_sm = (int64_t)N * lds_;
+  hipLaunchKernelGGL(k_knn_dense, dim3(nb, nb, nlat), dim3(256), 0, s, Yn, ldn, N, Sm, lds_, 0, lat_yn, lat_sm);
+  const dim3 grid((unsigned)((N + 3) / 4), (unsigned)nlat), block(256);
   const int m = (N + 63) / 64;
-#define OSC_SEL(MM) hipLaunchKernelGGL(k_knn_select<MM>, grid, block, 0, s, Sm, lds_, N, k, out_val, out_idx)
+#define OSC_SEL(MM) hipLaunchKernelGGL(k_knn_select<MM>, grid, block, 0, s, Sm, lds_, N, k, out_val, out_idx, lat_sm)
   if (m <= 4) OSC_SEL(4);
   else if (m <= 8) OSC_SEL(8);
   else if (m <= 16) OSC_SEL(16);
@@ -1389,7 +1406,7 @@ void launch_knn_rows_any(const float* Yn, int32_t ldn, int32_t N, int32_t k, int
   if (rows <= 0) return;
   if (row_begin % BM != 0) throw std::runtime_error("launch_knn_rows_any: row_begin must be a multiple of 128");
   hipLaunchKernelGGL(k_knn_dense, dim3((N + BN - 1) / BN, (rows + BM - 1) / BM), dim3(256), 0, s, Yn, ldn, N, Sm, lds_,
-                     row_begin);
+                     row_begin, (int64_t)0, (int64_t)0);
   hipLaunchKernelGGL(k_knn_select_any<256>, dim3((unsigned)rows), dim3(256), 0, s, Sm, lds_, N, k, row_begin, rows, out_val,
                      out_idx, nullptr);
   HIP_CHECK(hipGetLastError());

@@ -1,0 +1,892 @@
+// Corpus refine: for each query the top-K cosine candidates of a resident corpus, a K-row lattice
+// over them, its U* and its bundle -- the reference's retrieval loop (scripts/bench_beir.py:84-94) for a whole batch at
+// once.  A chunk of queries runs as:
+//
+//   k_cq_prep    : |psi_q| + 1e-12                                             one wave per query
+//   k_cq_gemm    : dots = Yn psi^T / (|psi| + 1e-12), fp32 MFMA, one fixed K order (k_query_gemm's tile)
+//   k_cq_select  : per query the K largest (ties to the smaller corpus id), sorted: radix select + bitonic sort
+//   k_cq_gather  : the candidates' rows of Y and Yn, back to back (lattice q = union rows [q K, q K + K))
+//   k_knn_dense / k_knn_select (batched over the lattices), k_mutual_ell, cap and normalise over the block-diagonal union
+//   k_cq_solve   : Jacobi-PCG for U*, one workgroup per lattice, a thread per column (the columns are independent
+//                  recurrences; only the stop test max_c |r_c| <= tol couples them, inside the workgroup)
+//   k_cq_bundle  : coherence drop, alignment, fp64 z-score and MMR over S, one workgroup per lattice
+//
+// No workgroup waits on another: every kernel's workgroups are independent.
+#include "osc_internal.hpp"
+#include "knn.hpp"
+#include "corpus_plan.hpp"
+
+#include <cmath>
+#include <vector>
+
+struct osc_corpus {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  int64_t N = 0;
+  int32_t D = 0, ldn = 0;
+  int32_t chunk_req = osc::host::kCorpusDefaultChunk;  // OSC_CORPUS_CHUNK, read at creation
+  osc::DevBuf<float> Y, Yn;
+  osc::DevBuf<unsigned char> scratch;
+  std::string err;
+  ~osc_corpus() {
+    Y.release();
+    Yn.release();
+    scratch.release();
+    if (stream) release_stream(device, stream);
+  }
+};
+
+namespace osc {
+namespace {
+
+using f32x16 = __attribute__((ext_vector_type(16))) float;
+constexpr int kTM = 128, kTQ = 128, kTK = 32, kTS = kTK + 4;
+
+__device__ __forceinline__ float wave_sum_f(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ double wave_sum_d2(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// qnorm[q] = |psi_q| + 1e-12 (psi: nq rows of ldn, pad columns zero)
+__global__ __launch_bounds__(256) void k_cq_prep(const float* psi, int32_t ldn, int32_t nq, float* qnorm) {
+  const int lane = threadIdx.x & 63;
+  const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (q >= nq) return;
+  const float* p = psi + (size_t)q * ldn;
+  float ss = 0.f;
+  for (int c = lane; c < ldn; c += 64) ss = fmaf(p[c], p[c], ss);
+  ss = wave_sum_f(ss);
+  if (lane == 0) qnorm[q] = sqrtf(ss) + 1e-12f;
+}
+
+// dots[q][i] = <Yn_i, psi_q> / qnorm[q]: 128 x 128 outputs per workgroup, k = 0 .. ldn - 1 in that order for every output
+__global__ __launch_bounds__(256) void k_cq_gemm(const float* __restrict__ Yn, int64_t N, int32_t ldn,
+                                                 const float* __restrict__ psi, int32_t nq, const float* qnorm,
+                                                 float* __restrict__ dots) {
+  __shared__ __attribute__((aligned(16))) float As[kTM * kTS];
+  __shared__ __attribute__((aligned(16))) float Bs[kTQ * kTS];
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int wr = w & 1, wc = w >> 1;
+  const int64_t row0 = (int64_t)blockIdx.x * kTM;
+  const int q0 = blockIdx.y * kTQ;
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  const int kq = (t & 7) * 4;
+  for (int k0 = 0; k0 < ldn; k0 += kTK) {
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+      const int r = (t >> 3) + 32 * it;
+      const int64_t gr = row0 + r;
+      const int k = k0 + kq;
+      float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
+      if (gr < N) a = *reinterpret_cast<const float4*>(Yn + gr * ldn + k);
+      if (q0 + r < nq) b = *reinterpret_cast<const float4*>(psi + (size_t)(q0 + r) * ldn + k);
+      *reinterpret_cast<float4*>(&As[r * kTS + kq]) = a;
+      *reinterpret_cast<float4*>(&Bs[r * kTS + kq]) = b;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < kTK; kk += 2) {
+      const int kl = kk + (lane >> 5);
+      float av[2], bv[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) av[i] = As[(wr * 64 + i * 32 + (lane & 31)) * kTS + kl];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) bv[j] = Bs[(wc * 64 + j * 32 + (lane & 31)) * kTS + kl];
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[j], acc[i][j], 0, 0, 0);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int64_t row = row0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+      if (row >= N) continue;
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int q = q0 + wc * 64 + j * 32 + (lane & 31);
+        if (q < nq) dots[(size_t)q * N + row] = acc[i][j][r] / qnorm[q];
+      }
+    }
+}
+
+// ---- per-query top K: 1024 threads, radix select of the K-th key, then a bitonic sort (k_rm_null_select's pattern) -----
+constexpr int kSelT = host::kCorpusMaxTopK;
+
+__device__ __forceinline__ uint32_t fkey(float v) {  // ascending float order == ascending key order; finite keys are > 0
+  const uint32_t u = v == 0.f ? 0u : __float_as_uint(v);  // (-0 and +0 are one value)
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ int block_scan(bool flag, int* wsum, int* total) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const unsigned long long m = __ballot(flag);
+  const int pre = __popcll(m & ((1ull << lane) - 1ull));
+  if (lane == 0) wsum[w] = __popcll(m);
+  __syncthreads();
+  int wpre = 0, tot = 0;
+#pragma unroll
+  for (int t = 0; t < kSelT / 64; ++t) {
+    const int v = wsum[t];
+    wpre += t < w ? v : 0;
+    tot += v;
+  }
+  __syncthreads();
+  *total = tot;
+  return wpre + pre;
+}
+
+__global__ __launch_bounds__(kSelT) void k_cq_select(const float* dots, int64_t N, int32_t K, int32_t* cand, float* ccos) {
+  __shared__ uint32_t hist[256];
+  __shared__ uint32_t skey[kSelT];
+  __shared__ int32_t sid[kSelT];
+  __shared__ int wsum[kSelT / 64];
+  __shared__ uint32_t st_prefix, st_mask, st_k;
+  __shared__ int st_n;
+  const int q = blockIdx.x, tid = threadIdx.x;
+  const float* d = dots + (size_t)q * N;
+  uint32_t prefix = 0u, mask = 0u, k = (uint32_t)K;
+  for (int pass = 0; pass < 4; ++pass) {
+    const int shift = 24 - 8 * pass;
+    if (tid < 256) hist[tid] = 0u;
+    __syncthreads();
+    for (int64_t i = tid; i < N; i += kSelT) {
+      const uint32_t kk = fkey(d[i]);
+      if ((kk & mask) == prefix) atomicAdd(&hist[(kk >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    if (tid == 0) {
+      uint32_t cum = 0u;
+      for (int b = 255; b >= 0; --b) {
+        const uint32_t h = hist[b];
+        if (cum + h >= k) {
+          prefix |= (uint32_t)b << shift;
+          k -= cum;
+          break;
+        }
+        cum += h;
+      }
+      mask |= 255u << shift;
+      st_prefix = prefix;
+      st_mask = mask;
+      st_k = k;
+    }
+    __syncthreads();
+    prefix = st_prefix;
+    mask = st_mask;
+    k = st_k;
+  }
+  const uint32_t T = prefix;  // the K-th largest key; k = how many keys equal to T are kept (the smallest ids)
+  if (tid == 0) st_n = 0;
+  sid[tid] = 0x7fffffff;
+  skey[tid] = 0u;
+  __syncthreads();
+  int eqrun = 0;
+  for (int64_t i0 = 0; i0 < N; i0 += kSelT) {
+    const int64_t i = i0 + tid;
+    const uint32_t kk = i < N ? fkey(d[i]) : 0u;
+    int tot = 0;
+    const int eqpos = eqrun + block_scan(i < N && kk == T, wsum, &tot);
+    if (i < N && (kk > T || (kk == T && eqpos < (int)k))) {
+      const int slot = atomicAdd(&st_n, 1);
+      if (slot < kSelT) {
+        skey[slot] = kk;
+        sid[slot] = (int32_t)i;
+      }
+    }
+    eqrun += tot;
+  }
+  __syncthreads();
+  for (int size = 2; size <= kSelT; size <<= 1) {  // key descending, then id ascending
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      const int l = tid ^ stride;
+      if (l > tid) {
+        const uint32_t ki = skey[tid], kl = skey[l];
+        const int ai = sid[tid], al = sid[l];
+        const bool l_first = kl > ki || (kl == ki && al < ai);
+        const bool i_first = ki > kl || (ki == kl && ai < al);
+        if ((tid & size) == 0 ? l_first : i_first) {
+          skey[tid] = kl;
+          skey[l] = ki;
+          sid[tid] = al;
+          sid[l] = ai;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  if (tid < K) {
+    const int32_t i = sid[tid];
+    cand[(size_t)q * K + tid] = i;
+    ccos[(size_t)q * K + tid] = d[i];
+  }
+}
+
+// union row g = q K + r <- corpus row cand[q][r]: Y, Yn and the solve's x0 = Y (lattice.py:245-263)
+__global__ __launch_bounds__(256) void k_cq_gather(const float* Y, const float* Yn, int32_t ldn, const int32_t* cand,
+                                                   int64_t rows, float* Yc, float* Ync, float* X) {
+  const int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (g >= rows) return;
+  const int lane = threadIdx.x & 63;
+  const size_t src = (size_t)cand[g] * ldn, dst = (size_t)g * ldn;
+  for (int c = lane * 4; c < ldn; c += 256) {
+    const float4 y = *reinterpret_cast<const float4*>(Y + src + c);
+    *reinterpret_cast<float4*>(Yc + dst + c) = y;
+    *reinterpret_cast<float4*>(X + dst + c) = y;
+    *reinterpret_cast<float4*>(Ync + dst + c) = *reinterpret_cast<const float4*>(Yn + src + c);
+  }
+}
+
+struct SolveArgs {
+  const float* Y;     // union rows x ldn
+  const float* psi;   // nq x ldn
+  const int32_t* col;  // union ELL (width k, union row ids)
+  const float* w;
+  const int32_t* deg;
+  float* X;
+  float* R;
+  float* P;
+  float* AP;
+  int32_t* iters;
+  float* res;
+  int32_t K, k, ldn, max_iters;
+  float lamG, lamC, lamQ, tol;
+};
+
+// Jacobi-PCG for M U* = lamG Y + lamQ 1 psi^T from x0 = Y (the U* operator of osc_solve_ustar with B = 1, no chain):
+// M v = (lamG + lamC + lamQ) v - lamC W v, Jacobi diagonal lamG + lamQ.  One workgroup per lattice; thread t owns the
+// columns t + 256 m and runs their recurrences over the lattice's rows in row order (fp64 column sums), so only the stop
+// test crosses threads.  Same iteration structure as k_settle_small: stop test after the x / r update, before beta.
+template <int NC>
+__global__ __launch_bounds__(256) void k_cq_solve(const SolveArgs a) {
+  __shared__ float red[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int lat = blockIdx.x;
+  const int64_t r0 = (int64_t)lat * a.K, r1 = r0 + a.K;
+  const float* psi = a.psi + (size_t)lat * a.ldn;
+  const float cs = fmaf(a.lamQ, 1.0f, a.lamG + a.lamC);
+  const float invMd = 1.f / (fmaf(a.lamQ, 1.0f, a.lamG) + 1e-12f);
+  const float cW = a.lamC, qb = a.lamQ;
+  int cidx[NC];
+  bool on[NC];
+#pragma unroll
+  for (int m = 0; m < NC; ++m) {
+    cidx[m] = tid + 256 * m;
+    on[m] = cidx[m] < a.ldn;
+    if (!on[m]) cidx[m] = 0;
+  }
+  auto apply = [&](const float* v, int64_t i, float (&out)[NC]) {
+    float acc[NC];
+#pragma unroll
+    for (int m = 0; m < NC; ++m) acc[m] = 0.f;
+    const int d = a.deg[i];
+    for (int e = 0; e < d; ++e) {
+      const int64_t j = a.col[i * a.k + e];
+      const float wij = a.w[i * a.k + e];
+#pragma unroll
+      for (int m = 0; m < NC; ++m) acc[m] = fmaf(wij, v[j * a.ldn + cidx[m]], acc[m]);
+    }
+#pragma unroll
+    for (int m = 0; m < NC; ++m) out[m] = cs * v[i * a.ldn + cidx[m]] - cW * acc[m];
+  };
+  double rz[NC], t1[NC], t2[NC];
+#pragma unroll
+  for (int m = 0; m < NC; ++m) rz[m] = 0.0;
+  for (int64_t i = r0; i < r1; ++i) {  // r = b - M x0, p = z = r / diag
+    float o[NC];
+    apply(a.X, i, o);
+#pragma unroll
+    for (int m = 0; m < NC; ++m) {
+      if (!on[m]) continue;
+      const size_t off = (size_t)i * a.ldn + cidx[m];
+      const float rr = (a.lamG * a.Y[off] + qb * psi[cidx[m]]) - o[m];
+      const float z = rr * invMd;
+      a.R[off] = rr;
+      a.P[off] = z;
+      rz[m] += (double)rr * (double)z;
+    }
+  }
+  int it = 1;
+  float resv = 0.f;
+  for (; it <= a.max_iters; ++it) {
+#pragma unroll
+    for (int m = 0; m < NC; ++m) t1[m] = 0.0;
+    for (int64_t i = r0; i < r1; ++i) {
+      float o[NC];
+      apply(a.P, i, o);
+#pragma unroll
+      for (int m = 0; m < NC; ++m) {
+        if (!on[m]) continue;
+        const size_t off = (size_t)i * a.ldn + cidx[m];
+        a.AP[off] = o[m];
+        t1[m] += (double)a.P[off] * (double)o[m];
+      }
+    }
+    float alpha[NC];
+#pragma unroll
+    for (int m = 0; m < NC; ++m) {
+      alpha[m] = (float)(rz[m] / (t1[m] + 1e-18));  // solver.py:25-26
+      t1[m] = t2[m] = 0.0;
+    }
+    for (int64_t i = r0; i < r1; ++i) {
+#pragma unroll
+      for (int m = 0; m < NC; ++m) {
+        if (!on[m]) continue;
+        const size_t off = (size_t)i * a.ldn + cidx[m];
+        a.X[off] = fmaf(a.P[off], alpha[m], a.X[off]);
+        const float rr = fmaf(-a.AP[off], alpha[m], a.R[off]);
+        a.R[off] = rr;
+        t1[m] += (double)rr * (double)rr;
+        t2[m] += (double)rr * (double)(rr * invMd);
+      }
+    }
+    float mx = 0.f;
+#pragma unroll
+    for (int m = 0; m < NC; ++m) {  // NaN propagates (solver.py:29 reports NaN for a diverged column)
+      const float v = on[m] ? (float)sqrt(t1[m]) : 0.f;
+      mx = (v != v || mx != mx) ? __uint_as_float(0x7FC00000u) : fmaxf(mx, v);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float v = __shfl_xor(mx, o, 64);
+      mx = (v != v || mx != mx) ? __uint_as_float(0x7FC00000u) : fmaxf(mx, v);
+    }
+    if (lane == 0) red[wave] = mx;
+    __syncthreads();
+    resv = red[0];
+#pragma unroll
+    for (int u = 1; u < 4; ++u) resv = (red[u] != red[u] || resv != resv) ? __uint_as_float(0x7FC00000u) : fmaxf(resv, red[u]);
+    __syncthreads();
+    if (resv <= a.tol) break;  // solver.py:30-31, before the beta / p update
+    if (it == a.max_iters) break;
+    for (int64_t i = r0; i < r1; ++i) {
+#pragma unroll
+      for (int m = 0; m < NC; ++m) {
+        if (!on[m]) continue;
+        const size_t off = (size_t)i * a.ldn + cidx[m];
+        const float beta = (float)(t2[m] / (rz[m] + 1e-18));  // solver.py:33-34
+        a.P[off] = fmaf(a.P[off], beta, a.R[off] * invMd);
+      }
+    }
+#pragma unroll
+    for (int m = 0; m < NC; ++m) rz[m] = t2[m];
+  }
+  if (tid == 0) {
+    a.iters[lat] = it > a.max_iters ? a.max_iters : it;
+    a.res[lat] = resv;
+  }
+}
+
+struct BundleArgs {
+  const float* Y;       // union rows x ldn
+  const float* U;       // U* (union rows x ldn)
+  const float* psi;     // nq x ldn
+  const float* qnorm;   // nq
+  const int32_t* col;
+  const float* adj;     // capped adjacency
+  const int32_t* deg;
+  const float* sd;
+  const float* Sm;      // per lattice K x lds similarity matrix
+  int32_t K, k, ldn, lds, kk;
+  float lamC;
+  double alpha, lambda;
+  int32_t* o_local;
+  float* o_score;
+  float* o_align;
+};
+
+constexpr int kBundleRows = host::kCorpusMaxTopK;
+constexpr int kBundleCols = 1536;
+
+// bundle(kk, alpha) of one lattice per workgroup (lattice.py:530-568): align_i = cos(U*_i, psi), coh_i (receipts.py:28-38,
+// the receipt kernel's per-edge arithmetic), z-scored with fp64 mean / std, score = alpha z + (1 - alpha) align, then
+// greedy MMR (graph.py:114-133, lambda 0.5) over the lattice's similarity matrix under osc_mmr's order (value, then the
+// smaller local id)
+__global__ __launch_bounds__(256) void k_cq_bundle(const BundleArgs a) {
+  __shared__ float qn[kBundleCols];
+  __shared__ float s_coh[kBundleRows], s_align[kBundleRows];
+  __shared__ double s_base[kBundleRows], s_max[kBundleRows];
+  __shared__ double s_red[4];
+  __shared__ double s_bv[4];
+  __shared__ int s_bi[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int lat = blockIdx.x, K = a.K;
+  const int64_t r0 = (int64_t)lat * K;
+  const float* psi = a.psi + (size_t)lat * a.ldn;
+  const float qinv = 1.0f / a.qnorm[lat];
+  for (int c = tid; c < a.ldn; c += 256) qn[c] = psi[c] * qinv;
+  __syncthreads();
+  for (int r = wave; r < K; r += 4) {
+    const int64_t i = r0 + r;
+    const float* ui = a.U + (size_t)i * a.ldn;
+    const float* yi = a.Y + (size_t)i * a.ldn;
+    float s = 0.f, n2 = 0.f;
+    for (int c = lane; c < a.ldn; c += 64) {
+      s = fmaf(ui[c], qn[c], s);
+      n2 = fmaf(ui[c], ui[c], n2);
+    }
+    s = wave_sum_f(s);
+    n2 = wave_sum_f(n2);
+    const float inv_i = 1.0f / (a.sd[i] + 1e-12f);
+    float coh = 0.f;
+    const int d = a.deg[i];
+    for (int e = 0; e < d; ++e) {
+      const int64_t j = a.col[i * a.k + e];
+      const float wij = a.adj[i * a.k + e];
+      const float inv_j = 1.0f / (a.sd[j] + 1e-12f);
+      const float* uj = a.U + (size_t)j * a.ldn;
+      const float* yj = a.Y + (size_t)j * a.ldn;
+      float dy = 0.f, du = 0.f;
+      for (int c = lane; c < a.ldn; c += 64) {
+        const float y = yi[c] * inv_i - yj[c] * inv_j;
+        const float u = ui[c] * inv_i - uj[c] * inv_j;
+        dy = fmaf(y, y, dy);
+        du = fmaf(u, u, du);
+      }
+      dy = wave_sum_f(dy);
+      du = wave_sum_f(du);
+      if (wij > 0.f) coh += 0.5f * a.lamC * wij * (dy - du);
+    }
+    if (lane == 0) {
+      s_coh[r] = coh;
+      s_align[r] = s / (sqrtf(n2) + 1e-12f);
+    }
+  }
+  __syncthreads();
+  // fp64 mean and (population) std of coh, fixed reduction order
+  auto block_sum = [&](double v) {
+    v = wave_sum_d2(v);
+    if (lane == 0) s_red[wave] = v;
+    __syncthreads();
+    const double t = ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
+    __syncthreads();
+    return t;
+  };
+  double part = 0.0;
+  for (int r = tid; r < K; r += 256) part += (double)s_coh[r];
+  const double mu = block_sum(part) / (double)K;
+  part = 0.0;
+  for (int r = tid; r < K; r += 256) {
+    const double dv = (double)s_coh[r] - mu;
+    part += dv * dv;
+  }
+  const double sigma = sqrt(block_sum(part) / (double)K) + 1e-12;
+  for (int r = tid; r < K; r += 256) {
+    const double z = sigma > 0.0 ? ((double)s_coh[r] - mu) / sigma : 0.0;
+    const float score = (float)(a.alpha * z + (1.0 - a.alpha) * (double)s_align[r]);
+    s_coh[r] = score;  // (coh is not needed any more)
+    s_base[r] = (1.0 - a.lambda) * (double)score;
+    s_max[r] = 0.0;
+  }
+  __syncthreads();
+  const float* S = a.Sm + (size_t)lat * K * a.lds;
+  for (int t = 0; t < a.kk; ++t) {
+    double bv = -1.0e300;
+    int bi = 0x7fffffff;
+    for (int r = tid; r < K; r += 256) {
+      if (s_base[r] == -INFINITY) continue;  // taken
+      const double v = s_base[r] - (t == 0 ? 0.0 : a.lambda * s_max[r]);
+      if (bi == 0x7fffffff || v > bv || (v == bv && r < bi)) {
+        bv = v;
+        bi = r;
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const double ov = __shfl_xor(bv, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      if (oi != 0x7fffffff && (bi == 0x7fffffff || ov > bv || (ov == bv && oi < bi))) {
+        bv = ov;
+        bi = oi;
+      }
+    }
+    if (lane == 0) {
+      s_bv[wave] = bv;
+      s_bi[wave] = bi;
+    }
+    __syncthreads();
+    bv = s_bv[0];
+    bi = s_bi[0];
+#pragma unroll
+    for (int u = 1; u < 4; ++u)
+      if (s_bi[u] != 0x7fffffff && (bi == 0x7fffffff || s_bv[u] > bv || (s_bv[u] == bv && s_bi[u] < bi))) {
+        bv = s_bv[u];
+        bi = s_bi[u];
+      }
+    __syncthreads();
+    if (bi == 0x7fffffff) break;  // (cannot happen for kk <= K)
+    if (tid == 0) {
+      a.o_local[(size_t)lat * a.kk + t] = bi;
+      a.o_score[(size_t)lat * a.kk + t] = s_coh[bi];
+      a.o_align[(size_t)lat * a.kk + t] = s_align[bi];
+      s_base[bi] = -INFINITY;
+    }
+    if (t + 1 < a.kk) {
+      const float* srow = S + (size_t)bi * a.lds;
+      for (int r = tid; r < K; r += 256) {
+        const double sv = (double)srow[r];
+        s_max[r] = t == 0 ? sv : fmax(s_max[r], sv);
+      }
+    }
+    __syncthreads();
+  }
+}
+
+}  // namespace
+}  // namespace osc
+
+using namespace osc;
+
+namespace {
+
+thread_local std::string g_corpus_error;
+
+template <class F>
+int corpus_guarded(osc_corpus* h, F&& f) {
+  if (!h) return OSC_E_INVALID;
+  try {
+    HIP_CHECK(hipSetDevice(h->device));
+    alloc_ctx() = AllocCtx{h->device, h->stream};
+    f(*h);
+    return OSC_OK;
+  } catch (const Invalid& e) {
+    h->err = e.what();
+    return OSC_E_INVALID;
+  } catch (const Unsupported& e) {
+    h->err = e.what();
+    return OSC_E_UNSUPPORTED;
+  } catch (const std::exception& e) {
+    h->err = e.what();
+    return OSC_E_HIP;
+  }
+}
+
+template <class T>
+T* at(osc_corpus& c, int64_t off) {
+  return reinterpret_cast<T*>(c.scratch.p + off);
+}
+
+struct RefineReq {
+  const float* psis;
+  int32_t Q, K;
+  const int32_t* cand_in;  // Q x K or nullptr (search)
+  int32_t knn;             // effective list length (0: K == 1, no edges)
+  float row_cap, lamG, lamC, lamQ, tol;
+  int32_t max_iters, kk;
+  float alpha;
+  int32_t stage;           // 0 = search only, 1 = graph only, 2 = everything
+};
+
+// one chunk [q0, q0 + nq): psi upload, candidates, and the requested stages; returns the layout used
+host::CorpusLayout run_chunk(osc_corpus& c, const RefineReq& rq, int32_t q0, int32_t nq, int32_t cap_nq) {
+  const int32_t K = rq.K, ldn = c.ldn, k = std::max(1, rq.knn), kk = std::max(1, rq.kk);
+  const host::CorpusLayout L = host::corpus_layout(c.N, ldn, K, k, kk, cap_nq);
+  if ((int64_t)c.scratch.n < L.total) c.scratch.alloc((size_t)L.total);
+  hipStream_t s = c.stream;
+  std::vector<float> hp((size_t)nq * ldn, 0.f);
+  for (int32_t q = 0; q < nq; ++q)
+    std::copy(rq.psis + (size_t)(q0 + q) * c.D, rq.psis + (size_t)(q0 + q + 1) * c.D, hp.begin() + (size_t)q * ldn);
+  float* psi = at<float>(c, L.psi);
+  float* qnorm = at<float>(c, L.qnorm);
+  int32_t* cand = at<int32_t>(c, L.cand);
+  HIP_CHECK(hipMemcpyAsync(psi, hp.data(), hp.size() * 4, hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_cq_prep, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, s, psi, ldn, nq, qnorm);
+  if (rq.cand_in) {
+    HIP_CHECK(hipMemcpyAsync(cand, rq.cand_in + (size_t)q0 * K, (size_t)nq * K * 4, hipMemcpyHostToDevice, s));
+  } else {
+    float* dots = at<float>(c, L.dots);
+    const dim3 grid((unsigned)((c.N + kTM - 1) / kTM), (unsigned)((nq + kTQ - 1) / kTQ));
+    hipLaunchKernelGGL(k_cq_gemm, grid, dim3(256), 0, s, c.Yn.p, c.N, ldn, psi, nq, qnorm, dots);
+    hipLaunchKernelGGL(k_cq_select, dim3((unsigned)nq), dim3(kSelT), 0, s, dots, c.N, K, cand, at<float>(c, L.ccos));
+  }
+  HIP_CHECK(hipGetLastError());
+  if (rq.stage == 0) return L;
+  const int64_t rows = (int64_t)nq * K;
+  float* Yc = at<float>(c, L.Y);
+  float* Ync = at<float>(c, L.Yn);
+  float* X = at<float>(c, L.X);
+  hipLaunchKernelGGL(k_cq_gather, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, c.Y.p, c.Yn.p, ldn, cand, rows, Yc,
+                     Ync, X);
+  HIP_CHECK(hipGetLastError());
+  const int32_t lds = host::corpus_lds(K);
+  int32_t* col = at<int32_t>(c, L.col);
+  float* adj = at<float>(c, L.adj);
+  float* w = at<float>(c, L.w);
+  int32_t* deg = at<int32_t>(c, L.deg);
+  float* sd = at<float>(c, L.sd);
+  float* Sm = at<float>(c, L.Sm);
+  if (rq.knn > 0) {  // the dense route of the lattice build (osc_graph.hip, KnnRoute::dense), every lattice at once
+    launch_knn_dense_many(Ync, ldn, K, nq, k, Sm, lds, at<float>(c, L.kval), at<int32_t>(c, L.kidx), s);
+    launch_mutual_ell(at<float>(c, L.kval), at<int32_t>(c, L.kidx), (int32_t)rows, k, k, col, adj, deg, s);
+  } else {  // one-row lattices have no edges (graph.py:30-32)
+    HIP_CHECK(hipMemsetAsync(deg, 0, (size_t)rows * 4, s));
+  }
+  launch_cap_and_normalize(adj, w, col, deg, k, (int32_t)rows, rq.row_cap, 1, at<float>(c, L.scale), sd, s);
+  if (rq.stage == 1) return L;
+  SolveArgs sa{};
+  sa.Y = Yc;
+  sa.psi = psi;
+  sa.col = col;
+  sa.w = w;
+  sa.deg = deg;
+  sa.X = X;
+  sa.R = at<float>(c, L.R);
+  sa.P = at<float>(c, L.P);
+  sa.AP = at<float>(c, L.AP);
+  sa.iters = at<int32_t>(c, L.iters);
+  sa.res = at<float>(c, L.res);
+  sa.K = K;
+  sa.k = k;
+  sa.ldn = ldn;
+  sa.max_iters = rq.max_iters;
+  sa.lamG = rq.lamG;
+  sa.lamC = rq.lamC;
+  sa.lamQ = rq.lamQ;
+  sa.tol = rq.tol;
+  const int nc = (ldn + 255) / 256;
+  if (nc <= 1) hipLaunchKernelGGL(k_cq_solve<1>, dim3((unsigned)nq), dim3(256), 0, s, sa);
+  else if (nc == 2) hipLaunchKernelGGL(k_cq_solve<2>, dim3((unsigned)nq), dim3(256), 0, s, sa);
+  else if (nc == 3) hipLaunchKernelGGL(k_cq_solve<3>, dim3((unsigned)nq), dim3(256), 0, s, sa);
+  else if (nc == 4) hipLaunchKernelGGL(k_cq_solve<4>, dim3((unsigned)nq), dim3(256), 0, s, sa);
+  else hipLaunchKernelGGL(k_cq_solve<6>, dim3((unsigned)nq), dim3(256), 0, s, sa);
+  HIP_CHECK(hipGetLastError());
+  if (rq.kk > 0) {
+    BundleArgs ba{};
+    ba.Y = Yc;
+    ba.U = X;
+    ba.psi = psi;
+    ba.qnorm = qnorm;
+    ba.col = col;
+    ba.adj = adj;
+    ba.deg = deg;
+    ba.sd = sd;
+    ba.Sm = Sm;
+    ba.K = K;
+    ba.k = k;
+    ba.ldn = ldn;
+    ba.lds = lds;
+    ba.kk = rq.kk;
+    ba.lamC = rq.lamC;
+    ba.alpha = (double)rq.alpha;
+    ba.lambda = 0.5;
+    ba.o_local = at<int32_t>(c, L.o_local);
+    ba.o_score = at<float>(c, L.o_score);
+    ba.o_align = at<float>(c, L.o_align);
+    hipLaunchKernelGGL(k_cq_bundle, dim3((unsigned)nq), dim3(256), 0, s, ba);
+    HIP_CHECK(hipGetLastError());
+  }
+  return L;
+}
+
+void check_queries(const osc_corpus& c, const float* psis, int32_t Q, int32_t top_k) {
+  if (Q < 0 || (Q > 0 && !psis)) throw Invalid("psis must be a (Q, D) array");
+  if (top_k < 1 || top_k > host::kCorpusMaxTopK) throw Invalid("top_k must be between 1 and 1024");
+  for (int64_t i = 0; i < (int64_t)Q * c.D; ++i)
+    if (!std::isfinite(psis[i])) throw Invalid("psis must be finite");
+}
+
+void check_candidates(const osc_corpus& c, const int32_t* cand, int32_t Q, int32_t K) {
+  for (int64_t i = 0; i < (int64_t)Q * K; ++i)
+    if (cand[i] < 0 || cand[i] >= c.N) throw Invalid("candidates: corpus id out of range");
+}
+
+int32_t chunk_for(const osc_corpus& c, int32_t K, int32_t knn, int32_t kk) {
+  return host::corpus_chunk(c.N, c.ldn, K, std::max(1, knn), std::max(1, kk), c.chunk_req, host::kCorpusBudgetBytes);
+}
+
+}  // namespace
+
+extern "C" {
+
+int osc_corpus_create(const float* Y, int64_t N, int32_t D, int32_t device, osc_corpus_handle* out) {
+  if (!out) return OSC_E_INVALID;
+  *out = nullptr;
+  if (!Y || N < 1 || D < 1 || N >= (int64_t)1 << 31 || D > osc::kBundleCols) {
+    g_corpus_error = "osc_corpus_create: need Y != NULL, 1 <= N < 2^31, 1 <= D <= 1536";
+    return OSC_E_INVALID;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || device < 0 || device >= ndev) {
+    g_corpus_error = "osc_corpus_create: no usable HIP device (this library has no CPU fallback)";
+    return OSC_E_NODEVICE;
+  }
+  std::unique_ptr<osc_corpus> h(new osc_corpus());
+  try {
+    h->device = device;
+    HIP_CHECK(hipSetDevice(device));
+    h->stream = acquire_stream(device);
+    alloc_ctx() = AllocCtx{device, h->stream};
+    h->N = N;
+    h->D = D;
+    h->ldn = host::corpus_ldn(D);
+    if (const char* e = getenv("OSC_CORPUS_CHUNK")) {  // queries per chunk (read once, like read_env's switches)
+      const int v = atoi(e);
+      if (v >= 1) h->chunk_req = v;
+    }
+    h->Y.alloc((size_t)N * h->ldn);
+    h->Yn.alloc((size_t)N * h->ldn);
+    HIP_CHECK(hipMemsetAsync(h->Y.p, 0, (size_t)N * h->ldn * 4, h->stream));
+    HIP_CHECK(hipMemcpy2DAsync(h->Y.p, (size_t)h->ldn * 4, Y, (size_t)D * 4, (size_t)D * 4, (size_t)N,
+                               hipMemcpyHostToDevice, h->stream));
+    launch_normalize_rows(h->Y.p, h->ldn, h->Yn.p, h->ldn, N, D, h->stream);  // osc_create's row normalisation
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+  } catch (const std::exception& e) {
+    g_corpus_error = e.what();
+    return OSC_E_HIP;
+  }
+  *out = h.release();
+  return OSC_OK;
+}
+
+int osc_corpus_destroy(osc_corpus_handle h) {
+  if (!h) return OSC_OK;
+  (void)hipSetDevice(h->device);
+  if (h->stream) (void)hipStreamSynchronize(h->stream);
+  alloc_ctx() = AllocCtx{h->device, nullptr};
+  delete h;
+  return OSC_OK;
+}
+
+const char* osc_corpus_last_error(osc_corpus_handle h) { return h ? h->err.c_str() : g_corpus_error.c_str(); }
+
+int osc_corpus_info(osc_corpus_handle h, int32_t top_k, int32_t kneighbors, int32_t k, int32_t* chunk, int64_t* bytes) {
+  return corpus_guarded(h, [&](osc_corpus& c) {
+    const int32_t K = (int32_t)std::min<int64_t>(std::max(1, top_k), c.N);
+    const int32_t knn = K > 1 ? host::corpus_knn(kneighbors, K) : 0;
+    const int32_t kk = std::min(std::max(k, 0), K);
+    const int32_t nq = chunk_for(c, K, knn, kk);
+    if (chunk) *chunk = nq;
+    if (bytes) *bytes = host::corpus_layout(c.N, c.ldn, K, std::max(1, knn), std::max(1, kk), nq).total;
+  });
+}
+
+int osc_corpus_search(osc_corpus_handle h, const float* psis, int32_t Q, int32_t top_k, int32_t* ids, float* cos) {
+  return corpus_guarded(h, [&](osc_corpus& c) {
+    check_queries(c, psis, Q, top_k);
+    if (Q == 0) return;
+    if (!ids || !cos) throw Invalid("osc_corpus_search: NULL buffer");
+    RefineReq rq{};
+    rq.psis = psis;
+    rq.Q = Q;
+    rq.K = (int32_t)std::min<int64_t>(top_k, c.N);
+    rq.stage = 0;
+    const int32_t nq = chunk_for(c, rq.K, 0, 0);
+    for (int32_t ch = 0; ch < host::chunk_count(Q, nq); ++ch) {
+      const int32_t q0 = host::chunk_begin(ch, nq), n = host::chunk_size(Q, ch, nq);
+      const host::CorpusLayout L = run_chunk(c, rq, q0, n, nq);
+      HIP_CHECK(hipMemcpyAsync(ids + (size_t)q0 * rq.K, at<int32_t>(c, L.cand), (size_t)n * rq.K * 4, hipMemcpyDeviceToHost,
+                               c.stream));
+      HIP_CHECK(hipMemcpyAsync(cos + (size_t)q0 * rq.K, at<float>(c, L.ccos), (size_t)n * rq.K * 4, hipMemcpyDeviceToHost,
+                               c.stream));
+      HIP_CHECK(hipStreamSynchronize(c.stream));
+    }
+  });
+}
+
+int osc_corpus_refine(osc_corpus_handle h, const float* psis, int32_t Q, int32_t top_k, const int32_t* cand_in,
+                      int32_t kneighbors, float row_cap, float lamG, float lamC, float lamQ, float tol, int32_t max_iters,
+                      int32_t k, float alpha, int32_t* cand_out, int32_t* local, float* score, float* align, int32_t* iters,
+                      float* res) {
+  return corpus_guarded(h, [&](osc_corpus& c) {
+    check_queries(c, psis, Q, top_k);
+    if (kneighbors < 1) throw Invalid("kneighbors must be >= 1");
+    if (!(lamG > 0.f) || lamC < 0.f || lamQ < 0.f) throw Invalid("need lamG > 0, lamC >= 0, lamQ >= 0");
+    RefineReq rq{};
+    rq.psis = psis;
+    rq.Q = Q;
+    rq.K = (int32_t)std::min<int64_t>(top_k, c.N);
+    rq.knn = rq.K > 1 ? host::corpus_knn(kneighbors, rq.K) : 0;
+    if (rq.knn > host::kCorpusMaxKnn) throw Invalid("min(kneighbors, K - 1) must be at most 128");
+    rq.kk = std::min(std::max(k, 0), rq.K);
+    if (cand_in) check_candidates(c, cand_in, Q, rq.K);
+    if (Q == 0) return;
+    if (!cand_out || !iters || !res || (rq.kk > 0 && (!local || !score || !align))) throw Invalid("osc_corpus_refine: NULL buffer");
+    rq.cand_in = cand_in;
+    rq.row_cap = row_cap;
+    rq.lamG = lamG;
+    rq.lamC = lamC;
+    rq.lamQ = lamQ;
+    rq.tol = tol;
+    rq.max_iters = std::max(1, max_iters);
+    rq.alpha = alpha;
+    rq.stage = 2;
+    const int32_t nq = chunk_for(c, rq.K, rq.knn, rq.kk);
+    for (int32_t ch = 0; ch < host::chunk_count(Q, nq); ++ch) {
+      const int32_t q0 = host::chunk_begin(ch, nq), n = host::chunk_size(Q, ch, nq);
+      const host::CorpusLayout L = run_chunk(c, rq, q0, n, nq);
+      auto down = [&](void* dst, int64_t off, size_t bytes) {
+        HIP_CHECK(hipMemcpyAsync(dst, c.scratch.p + off, bytes, hipMemcpyDeviceToHost, c.stream));
+      };
+      down(cand_out + (size_t)q0 * rq.K, L.cand, (size_t)n * rq.K * 4);
+      down(iters + q0, L.iters, (size_t)n * 4);
+      down(res + q0, L.res, (size_t)n * 4);
+      if (rq.kk > 0) {
+        down(local + (size_t)q0 * rq.kk, L.o_local, (size_t)n * rq.kk * 4);
+        down(score + (size_t)q0 * rq.kk, L.o_score, (size_t)n * rq.kk * 4);
+        down(align + (size_t)q0 * rq.kk, L.o_align, (size_t)n * rq.kk * 4);
+      }
+      HIP_CHECK(hipStreamSynchronize(c.stream));
+    }
+  });
+}
+
+int osc_corpus_graph(osc_corpus_handle h, const float* psi, const int32_t* cand_in, int32_t top_k, int32_t kneighbors,
+                     float row_cap, int32_t* cand_out, int64_t* rowptr, int32_t* col, float* a, float* w, float* sqrt_deg,
+                     int64_t capacity, int64_t* nnz) {
+  return corpus_guarded(h, [&](osc_corpus& c) {
+    check_queries(c, psi, 1, top_k);
+    if (kneighbors < 1) throw Invalid("kneighbors must be >= 1");
+    RefineReq rq{};
+    rq.psis = psi;
+    rq.Q = 1;
+    rq.K = (int32_t)std::min<int64_t>(top_k, c.N);
+    rq.knn = rq.K > 1 ? host::corpus_knn(kneighbors, rq.K) : 0;
+    if (rq.knn > host::kCorpusMaxKnn) throw Invalid("min(kneighbors, K - 1) must be at most 128");
+    if (cand_in) check_candidates(c, cand_in, 1, rq.K);
+    if (!cand_out || !rowptr || !col || !a || !w || !sqrt_deg || !nnz) throw Invalid("osc_corpus_graph: NULL buffer");
+    rq.cand_in = cand_in;
+    rq.row_cap = row_cap;
+    rq.stage = 1;
+    const int32_t K = rq.K, k = std::max(1, rq.knn);
+    const host::CorpusLayout L = run_chunk(c, rq, 0, 1, 1);
+    std::vector<int32_t> hc((size_t)K * k), hd((size_t)K);
+    std::vector<float> ha((size_t)K * k), hw((size_t)K * k);
+    HIP_CHECK(hipMemcpyAsync(cand_out, c.scratch.p + L.cand, (size_t)K * 4, hipMemcpyDeviceToHost, c.stream));
+    HIP_CHECK(hipMemcpyAsync(hd.data(), c.scratch.p + L.deg, (size_t)K * 4, hipMemcpyDeviceToHost, c.stream));
+    HIP_CHECK(hipMemcpyAsync(hc.data(), c.scratch.p + L.col, hc.size() * 4, hipMemcpyDeviceToHost, c.stream));
+    HIP_CHECK(hipMemcpyAsync(ha.data(), c.scratch.p + L.adj, ha.size() * 4, hipMemcpyDeviceToHost, c.stream));
+    HIP_CHECK(hipMemcpyAsync(hw.data(), c.scratch.p + L.w, hw.size() * 4, hipMemcpyDeviceToHost, c.stream));
+    HIP_CHECK(hipMemcpyAsync(sqrt_deg, c.scratch.p + L.sd, (size_t)K * 4, hipMemcpyDeviceToHost, c.stream));
+    HIP_CHECK(hipStreamSynchronize(c.stream));
+    int64_t n = 0;
+    rowptr[0] = 0;
+    for (int32_t i = 0; i < K; ++i) {
+      for (int32_t e = 0; e < hd[(size_t)i]; ++e) {
+        if (n >= capacity) throw Invalid("osc_corpus_graph: capacity too small");
+        col[n] = hc[(size_t)i * k + e];
+        a[n] = ha[(size_t)i * k + e];
+        w[n] = hw[(size_t)i * k + e];
+        ++n;
+      }
+      rowptr[i + 1] = n;
+    }
+    *nnz = n;
+  });
+}
+
+}  // extern "C"
