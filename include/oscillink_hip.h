@@ -245,6 +245,29 @@ int osc_corpus_refine(osc_corpus_handle h, const float* psis, int32_t Q, int32_t
                       int32_t kneighbors, float row_cap, float lamG, float lamC, float lamQ, float tol, int32_t max_iters,
                       int32_t k, float alpha, int32_t* cand_out, int32_t* local, float* score, float* align, int32_t* iters,
                       float* res);
+/* The gates of the reference's hallucination-control loop (examples/rag_replacement.py:159-177, examples/diffusion_gated.py:
+ * `compute_diffusion_gates(Y[cand], psi, kneighbors, row_cap_val, beta, gamma, method, tol, max_iters)`,
+ * preprocess/diffusion.py:35-124) for Q queries, one single-right-hand-side solve per candidate lattice on the device:
+ * s_i = beta max(0, cos(Y_i, psi)), (L_sym + gamma I) h = s by Jacobi-PCG from x0 = 0, min-max to [0, 1] (ones when
+ * max h - min h < 1e-12).  method 0 = "direct" (the CG run to 1e-7 max(1, |s|), at most 2048 iterations; tol / max_iters
+ * unused), 1 = "cg" (tol / max_iters under solver.py's stop rule).  clamp = 0: the solve's h itself, not normalised and
+ * not clipped.  cand_in (Q x K) replaces the search when not NULL.  Out: cand_out / gates_out Q x K (candidate order);
+ * iters / res per query. */
+int osc_corpus_gates(osc_corpus_handle h, const float* psis, int32_t Q, int32_t top_k, const int32_t* cand_in,
+                     int32_t kneighbors, float row_cap, float beta, float gamma, int32_t method, float tol,
+                     int32_t max_iters, int32_t clamp, int32_t* cand_out, float* gates_out, int32_t* iters, float* res);
+/* osc_corpus_refine with gates (examples/rag_replacement.py:159-177, scripts/benchmark_gating_compare.py:
+ * `lat = Oscillink(Y[cand], ...); lat.set_query(psi, gates=g); lat.bundle(k, alpha)`): U* of
+ * M = lamG I + lamC L_sym + lamQ diag(g) with right-hand side lamG Y + lamQ g psi^T (lattice.py:245-263).  gates_in (Q x K,
+ * finite and >= 0) are used as given; NULL = the diffusion gates of osc_corpus_gates (beta, gamma, method, gate_tol,
+ * gate_max_iters; clamped) computed per lattice.  Out as osc_corpus_refine, plus gates_out Q x K (the gates used) and
+ * gate_iters / gate_res per query (zeros for given gates).  Gates of exactly 1 give osc_corpus_refine's results bit for bit. */
+int osc_corpus_refine_gated(osc_corpus_handle h, const float* psis, int32_t Q, int32_t top_k, const int32_t* cand_in,
+                            const float* gates_in, float beta, float gamma, int32_t method, float gate_tol,
+                            int32_t gate_max_iters, int32_t kneighbors, float row_cap, float lamG, float lamC, float lamQ,
+                            float tol, int32_t max_iters, int32_t k, float alpha, int32_t* cand_out, float* gates_out,
+                            int32_t* local, float* score, float* align, int32_t* iters, float* res, int32_t* gate_iters,
+                            float* gate_res);
 /* The candidate lattice's graph of one query (mutual_knn_adj + row_sum_cap + normalized_laplacian, graph.py:8-93) as
  * osc_get_csr gives it for `Oscillink(Y[cand])`: rowptr K + 1, col / a / w nnz (<= capacity), sqrt_deg K; local row ids.
  * Test / diagnostic aid. */

@@ -19,6 +19,7 @@ MAX_TOP_K = 1024  # one key per thread of the per-query select (include/oscillin
 MAX_KNEIGHBORS = 128  # the dense build route's per-row list (k_knn_select)
 MAX_D = 1536  # the bundle kernel keeps the normalised query in LDS
 USTAR_TOL, USTAR_MAX_ITERS = 1e-4, 64  # _ensure_device_ustar's settings
+GATE_METHODS = {"direct": 0, "cg": 1}  # osc_corpus_gates' method codes
 
 
 class Corpus:
@@ -124,6 +125,31 @@ class Corpus:
             raise ValueError("candidates: repeated id within a row")
         return cand.astype(np.int32)
 
+    @staticmethod
+    def _gate_settings(beta, gamma, method, max_iters, prefix: str = ""):
+        """(beta, gamma, method code, max_iters) of a diffusion-gate solve, checked as compute_diffusion_gates checks
+        them; `prefix` turns the names into refine_many's (gate_gamma, ...)."""
+        if not float(gamma) > 0 or not np.isfinite(float(gamma)):
+            raise ValueError(f"{prefix}gamma must be > 0 for SPD")
+        if not np.isfinite(float(beta)):
+            raise ValueError(f"{prefix}beta must be finite")
+        if method not in GATE_METHODS:
+            raise ValueError(f"{prefix}method must be 'direct' or 'cg', got {method!r}")
+        if int(max_iters) < 1:
+            raise ValueError(f"{prefix}max_iters must be >= 1")
+        return float(beta), float(gamma), GATE_METHODS[method], int(max_iters)
+
+    @staticmethod
+    def _warn_non_finite(gates: np.ndarray, iters: np.ndarray, res: np.ndarray, what: str) -> None:
+        bad = np.nonzero(~np.all(np.isfinite(gates), axis=1))[0]
+        if bad.size:  # compute_diffusion_gates hands such gates back with a warning as well
+            import warnings
+
+            q = int(bad[0])
+            warnings.warn(f"{what}: the screened-diffusion solve of query {q} produced non-finite values "
+                          f"(iters={int(iters[q])}, res={float(res[q])!r}; {bad.size} queries in all); returned as "
+                          "computed, like the reference's cg path", RuntimeWarning, stacklevel=3)
+
     # ------------------------------------------------------------------ public API
     def search(self, psis, top_k: int):
         """Per query the K = min(top_k, N) corpus ids of the largest cosine Yn_i . psi / (|psi| + 1e-12) (fp32 on the
@@ -140,7 +166,8 @@ class Corpus:
     def refine_many(self, psis, top_k: int, k: int = 8, alpha: float = 0.5, *, kneighbors: int = 6,
                     row_cap_val: float = 1.0, lamG: float = 1.0, lamC: float = 0.5, lamQ: float = 4.0,
                     deterministic_k: bool = False, neighbor_seed: Optional[int] = None, candidates=None,
-                    as_arrays: bool = False):
+                    as_arrays: bool = False, gates=None, gate_beta: float = 1.0, gate_gamma: float = 0.1,
+                    gate_method: str = "direct", gate_tol: float = 1e-4, gate_max_iters: int = 256):
         """For each query q, what the reference's loop returns with `cand = search(psis, top_k)[0][q]` (or
         `candidates[q]`):
 
@@ -152,8 +179,16 @@ class Corpus:
         `deterministic_k` / `neighbor_seed` mean what they mean for Oscillink: the device uses one total order
         (similarity desc, index asc) either way.  Limits: 1 <= top_k <= 1024, min(kneighbors, K - 1) <= 128.
 
+        `gates` selects the reference's second, "hallucination control" form of the loop (examples/rag_replacement.py:
+        159-177), `lat.set_query(psis[q], gates=g)`:  None -- no gates (B = 1);  "diffusion" -- per lattice
+        g = compute_diffusion_gates(Y[cand], psis[q], kneighbors=..., row_cap_val=..., beta=gate_beta, gamma=gate_gamma,
+        method=gate_method, tol=gate_tol, max_iters=gate_max_iters), solved on the device on the lattice's own graph;
+        a (Q, K) array -- used as given, in candidate order (finite and >= 0: a batch cannot surface one lattice's
+        breakdown the way set_query's caller can).  Gates of exactly 1 give the ungated answer bit for bit.
+
         Returns Q lists of {"id", "score", "align"}, or with `as_arrays=True` a dict of `ids`, `local`, `score`, `align`
-        (Q, min(k, K)), `candidates` (Q, K), `ustar_iters` and `ustar_res` (Q,)."""
+        (Q, min(k, K)), `candidates` (Q, K), `ustar_iters` and `ustar_res` (Q,); with gates also `gates` (Q, K) float32 and
+        `gate_iters`, `gate_res` (Q,; zeros for given gates)."""
         P = self._queries(psis)
         K = self._top_k(top_k)
         knn = self._knn(kneighbors, K)  # noqa: F841 (validation)
@@ -165,23 +200,86 @@ class Corpus:
         Q = P.shape[0]
         cand_in = None if candidates is None else self._candidates(candidates, Q, K)
         kk = min(max(int(k), 0), K)
+        gates_in, gate_set = None, None
+        if isinstance(gates, str):
+            if gates != "diffusion":
+                raise ValueError(f"gates must be None, 'diffusion' or a ({Q}, {K}) array, got {gates!r}")
+            gate_set = self._gate_settings(gate_beta, gate_gamma, gate_method, gate_max_iters, prefix="gate_")
+        elif gates is not None:
+            gates_in = np.asarray(gates)
+            if gates_in.shape != (Q, K):
+                raise ValueError(f"gates must be a ({Q}, {K}) array, got shape {gates_in.shape}")
+            gates_in = np.ascontiguousarray(gates_in, dtype=np.float32)
+            if not np.all(np.isfinite(gates_in)):
+                raise ValueError("gates must be finite")
+            if np.any(gates_in < 0):
+                raise ValueError("gates must be >= 0")
         cand = np.zeros((Q, K), dtype=np.int32)
         local = np.zeros((Q, kk), dtype=np.int32)
         score = np.zeros((Q, kk), dtype=np.float32)
         align = np.zeros((Q, kk), dtype=np.float32)
         iters = np.zeros(Q, dtype=np.int32)
         res = np.zeros(Q, dtype=np.float32)
-        if Q:
+        gated = gates is not None
+        g = np.zeros((Q, K), dtype=np.float32)
+        g_iters = np.zeros(Q, dtype=np.int32)
+        g_res = np.zeros(Q, dtype=np.float32)
+        if Q and not gated:
             self._call("osc_corpus_refine", nat.f32(P), Q, int(top_k), None if cand_in is None else nat.i32(cand_in),
                        int(kneighbors), float(row_cap_val), float(lamG), float(lamC), float(lamQ), USTAR_TOL,
                        USTAR_MAX_ITERS, kk, float(alpha), nat.i32(cand), nat.i32(local), nat.f32(score), nat.f32(align),
                        nat.i32(iters), nat.f32(res))
+        elif Q:
+            beta, gamma, method, g_max = gate_set if gate_set is not None else (1.0, 0.1, 0, 1)
+            self._call("osc_corpus_refine_gated", nat.f32(P), Q, int(top_k),
+                       None if cand_in is None else nat.i32(cand_in), None if gates_in is None else nat.f32(gates_in),
+                       beta, gamma, method, float(gate_tol), g_max, int(kneighbors), float(row_cap_val), float(lamG),
+                       float(lamC), float(lamQ), USTAR_TOL, USTAR_MAX_ITERS, kk, float(alpha), nat.i32(cand), nat.f32(g),
+                       nat.i32(local), nat.f32(score), nat.f32(align), nat.i32(iters), nat.f32(res), nat.i32(g_iters),
+                       nat.f32(g_res))
+            if gates_in is None:
+                self._warn_non_finite(g, g_iters, g_res, "refine_many")
         ids = np.take_along_axis(cand, local, axis=1) if kk else np.zeros((Q, 0), dtype=np.int32)
         if as_arrays:
-            return {"ids": ids, "local": local, "score": score, "align": align, "candidates": cand,
-                    "ustar_iters": iters, "ustar_res": res}
+            out = {"ids": ids, "local": local, "score": score, "align": align, "candidates": cand,
+                   "ustar_iters": iters, "ustar_res": res}
+            if gated:
+                out.update(gates=g, gate_iters=g_iters, gate_res=g_res)
+            return out
         return [[{"id": int(i), "score": float(s), "align": float(a)} for i, s, a in
                  zip(ids[q].tolist(), score[q].tolist(), align[q].tolist())] for q in range(Q)]
+
+    def diffusion_gates_many(self, psis, top_k: int, *, kneighbors: int = 6, row_cap_val: float = 1.0, beta: float = 1.0,
+                             gamma: float = 0.1, method: str = "direct", tol: float = 1e-4, max_iters: int = 256,
+                             clamp: bool = True, candidates=None) -> dict[str, Any]:
+        """For each query q, with `cand` its candidates (searched, or `candidates[q]`),
+
+            compute_diffusion_gates(Y[cand], psis[q], kneighbors=..., row_cap_val=..., beta=..., gamma=..., method=...,
+                                    tol=..., max_iters=..., clamp=...)
+
+        with every lattice's graph and single-right-hand-side solve on the device (no U*) -- for `clamp=True`; with
+        `clamp=False` the result is the solve's h itself, NOT clipped, whereas compute_diffusion_gates (like the reference,
+        diffusion.py:123) still clips h to [0, 1]: `np.clip(out["gates"], 0, 1)` gives its answer.  method="direct" is
+        served, as in compute_diffusion_gates, by the CG run to 1e-7 max(1, |s|) with at most 2048 iterations.  Non-finite
+        gates come back as computed, with a RuntimeWarning naming the first such query.
+
+        Returns a dict of `gates` (Q, K) float32 in candidate order, `candidates` (Q, K), `iters` and `res` (Q,)."""
+        P = self._queries(psis)
+        K = self._top_k(top_k)
+        self._knn(kneighbors, K)
+        b, g, m, mi = self._gate_settings(beta, gamma, method, max_iters)
+        Q = P.shape[0]
+        cand_in = None if candidates is None else self._candidates(candidates, Q, K)
+        cand = np.zeros((Q, K), dtype=np.int32)
+        gates = np.zeros((Q, K), dtype=np.float32)
+        iters = np.zeros(Q, dtype=np.int32)
+        res = np.zeros(Q, dtype=np.float32)
+        if Q:
+            self._call("osc_corpus_gates", nat.f32(P), Q, int(top_k), None if cand_in is None else nat.i32(cand_in),
+                       int(kneighbors), float(row_cap_val), b, g, m, float(tol), mi, int(bool(clamp)), nat.i32(cand),
+                       nat.f32(gates), nat.i32(iters), nat.f32(res))
+            self._warn_non_finite(gates, iters, res, "diffusion_gates_many")
+        return {"gates": gates, "candidates": cand, "iters": iters, "res": res}
 
     def info(self, top_k: int, kneighbors: int = 6, k: int = 8) -> dict[str, Any]:
         """Queries per chunk and one chunk's device scratch for a refine with these settings."""

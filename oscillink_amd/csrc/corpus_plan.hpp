@@ -37,6 +37,8 @@ struct CorpusLayout {
   int64_t qnorm;             // float  [nq]
   int64_t iters, res;        // int32 / float [nq]
   int64_t o_local, o_score, o_align;  // int32 / float / float [nq][kk]
+  int64_t gates;             // float  [nq][K]     diffusion gates B (computed or given); after every older block, so
+  int64_t g_iters, g_res;    // int32 / float [nq]  that those keep the offsets they had before gates existed
   int64_t total;
 };
 
@@ -74,6 +76,9 @@ inline CorpusLayout corpus_layout(int64_t N, int32_t ldn, int32_t K, int32_t k, 
   L.o_local = take((int64_t)nq * kk * 4);
   L.o_score = take((int64_t)nq * kk * 4);
   L.o_align = take((int64_t)nq * kk * 4);
+  L.gates = take((int64_t)nq * K * 4);
+  L.g_iters = take((int64_t)nq * 4);
+  L.g_res = take((int64_t)nq * 4);
   L.total = o;
   return L;
 }

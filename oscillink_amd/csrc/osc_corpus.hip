@@ -7,8 +7,11 @@
 //   k_cq_select  : per query the K largest (ties to the smaller corpus id), sorted: radix select + bitonic sort
 //   k_cq_gather  : the candidates' rows of Y and Yn, back to back (lattice q = union rows [q K, q K + K))
 //   k_knn_dense / k_knn_select (batched over the lattices), k_mutual_ell, cap and normalise over the block-diagonal union
+//   k_cq_gates   : (gated form only) screened-diffusion gates B of every lattice: s = beta max(0, Yn psi / |psi|), one
+//                  single-right-hand-side Jacobi-PCG of (L_sym + gamma I) h = s per workgroup, min-max to [0, 1]
 //   k_cq_solve   : Jacobi-PCG for U*, one workgroup per lattice, a thread per column (the columns are independent
-//                  recurrences; only the stop test max_c |r_c| <= tol couples them, inside the workgroup)
+//                  recurrences; only the stop test max_c |r_c| <= tol couples them, inside the workgroup); its GATED
+//                  instance reads B per row, the other one has B = 1 folded in
 //   k_cq_bundle  : coherence drop, alignment, fp64 z-score and MMR over S, one workgroup per lattice
 //
 // No workgroup waits on another: every kernel's workgroups are independent.
@@ -266,13 +269,17 @@ struct SolveArgs {
   float* res;
   int32_t K, k, ldn, max_iters;
   float lamG, lamC, lamQ, tol;
+  const float* B;     // union rows: the gates (GATED instances only; last, so the ungated instances' arguments stay put)
 };
 
 // Jacobi-PCG for M U* = lamG Y + lamQ 1 psi^T from x0 = Y (the U* operator of osc_solve_ustar with B = 1, no chain):
 // M v = (lamG + lamC + lamQ) v - lamC W v, Jacobi diagonal lamG + lamQ.  One workgroup per lattice; thread t owns the
 // columns t + 256 m and runs their recurrences over the lattice's rows in row order (fp64 column sums), so only the stop
 // test crosses threads.  Same iteration structure as k_settle_small: stop test after the x / r update, before beta.
-template <int NC>
+// GATED: B_i comes from a.B (set_query(psi, gates=B), lattice.py:245-263): row i has the operator constant
+// lamG + lamC + lamQ B_i, the Jacobi diagonal lamG + lamQ B_i and the right-hand side lamG Y_i + (lamQ B_i) psi, each formed
+// so that B_i = 1.0f gives the ungated instance's arithmetic operation for operation.
+template <int NC, bool GATED>
 __global__ __launch_bounds__(256) void k_cq_solve(const SolveArgs a) {
   __shared__ float red[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -282,6 +289,22 @@ __global__ __launch_bounds__(256) void k_cq_solve(const SolveArgs a) {
   const float cs = fmaf(a.lamQ, 1.0f, a.lamG + a.lamC);
   const float invMd = 1.f / (fmaf(a.lamQ, 1.0f, a.lamG) + 1e-12f);
   const float cW = a.lamC, qb = a.lamQ;
+  const float* g_cs = nullptr;   // GATED: the rows' operator constants and inverse Jacobi diagonals, formed once in LDS (every
+  const float* g_inv = nullptr;  // thread walks all rows in every pass; a reciprocal per row and pass is on its critical path)
+  if constexpr (GATED) {
+    __shared__ float s_cs[host::kCorpusMaxTopK], s_inv[host::kCorpusMaxTopK];
+    for (int r = tid; r < a.K; r += 256) {
+      const float Bi = a.B[r0 + r];
+      s_cs[r] = fmaf(a.lamQ, Bi, a.lamG + a.lamC);
+      s_inv[r] = 1.f / (fmaf(a.lamQ, Bi, a.lamG) + 1e-12f);
+    }
+    __syncthreads();
+    g_cs = s_cs;
+    g_inv = s_inv;
+  }
+  auto row_cs = [&](int64_t i) { return GATED ? g_cs[i - r0] : cs; };
+  auto row_invMd = [&](int64_t i) { return GATED ? g_inv[i - r0] : invMd; };
+  auto row_qb = [&](int64_t i) { return GATED ? a.lamQ * a.B[i] : qb; };
   int cidx[NC];
   bool on[NC];
 #pragma unroll
@@ -301,8 +324,9 @@ __global__ __launch_bounds__(256) void k_cq_solve(const SolveArgs a) {
 #pragma unroll
       for (int m = 0; m < NC; ++m) acc[m] = fmaf(wij, v[j * a.ldn + cidx[m]], acc[m]);
     }
+    const float csi = row_cs(i);
 #pragma unroll
-    for (int m = 0; m < NC; ++m) out[m] = cs * v[i * a.ldn + cidx[m]] - cW * acc[m];
+    for (int m = 0; m < NC; ++m) out[m] = csi * v[i * a.ldn + cidx[m]] - cW * acc[m];
   };
   double rz[NC], t1[NC], t2[NC];
 #pragma unroll
@@ -310,12 +334,13 @@ __global__ __launch_bounds__(256) void k_cq_solve(const SolveArgs a) {
   for (int64_t i = r0; i < r1; ++i) {  // r = b - M x0, p = z = r / diag
     float o[NC];
     apply(a.X, i, o);
+    const float qbi = row_qb(i), invMdi = row_invMd(i);
 #pragma unroll
     for (int m = 0; m < NC; ++m) {
       if (!on[m]) continue;
       const size_t off = (size_t)i * a.ldn + cidx[m];
-      const float rr = (a.lamG * a.Y[off] + qb * psi[cidx[m]]) - o[m];
-      const float z = rr * invMd;
+      const float rr = (a.lamG * a.Y[off] + qbi * psi[cidx[m]]) - o[m];
+      const float z = rr * invMdi;
       a.R[off] = rr;
       a.P[off] = z;
       rz[m] += (double)rr * (double)z;
@@ -344,6 +369,7 @@ __global__ __launch_bounds__(256) void k_cq_solve(const SolveArgs a) {
       t1[m] = t2[m] = 0.0;
     }
     for (int64_t i = r0; i < r1; ++i) {
+      const float invMdi = row_invMd(i);
 #pragma unroll
       for (int m = 0; m < NC; ++m) {
         if (!on[m]) continue;
@@ -352,7 +378,7 @@ __global__ __launch_bounds__(256) void k_cq_solve(const SolveArgs a) {
         const float rr = fmaf(-a.AP[off], alpha[m], a.R[off]);
         a.R[off] = rr;
         t1[m] += (double)rr * (double)rr;
-        t2[m] += (double)rr * (double)(rr * invMd);
+        t2[m] += (double)rr * (double)(rr * invMdi);
       }
     }
     float mx = 0.f;
@@ -375,12 +401,13 @@ __global__ __launch_bounds__(256) void k_cq_solve(const SolveArgs a) {
     if (resv <= a.tol) break;  // solver.py:30-31, before the beta / p update
     if (it == a.max_iters) break;
     for (int64_t i = r0; i < r1; ++i) {
+      const float invMdi = row_invMd(i);
 #pragma unroll
       for (int m = 0; m < NC; ++m) {
         if (!on[m]) continue;
         const size_t off = (size_t)i * a.ldn + cidx[m];
         const float beta = (float)(t2[m] / (rz[m] + 1e-18));  // solver.py:33-34
-        a.P[off] = fmaf(a.P[off], beta, a.R[off] * invMd);
+        a.P[off] = fmaf(a.P[off], beta, a.R[off] * invMdi);
       }
     }
 #pragma unroll
@@ -547,6 +574,174 @@ __global__ __launch_bounds__(256) void k_cq_bundle(const BundleArgs a) {
   }
 }
 
+struct GateArgs {
+  const float* Yn;      // union rows x ldn, row-normalised
+  const float* psi;     // nq x ldn
+  const float* qnorm;   // nq
+  const int32_t* col;   // union ELL (width k, union row ids)
+  const float* w;       // normalised weights
+  const int32_t* deg;
+  float* gates;         // union rows
+  int32_t* iters;       // nq
+  float* res;           // nq
+  int32_t K, k, ldn, max_iters, direct, clamp;
+  float beta, gamma, tol;
+};
+
+constexpr int kGateOwn = host::kCorpusMaxTopK / 256;  // rows per thread: row = tid + 256 m
+
+// compute_diffusion_gates (preprocess/diffusion.py:35-124) of one lattice per workgroup, the whole solve in one launch:
+// s_i = beta max(0, <Yn_i, psi / (|psi| + 1e-12)>), Jacobi-PCG of (L_sym + gamma I) h = s from x0 = 0 under solver.py's
+// stop rule (operator (1 + gamma) v_i - sum_e w_ie v_col(ie), diagonal 1 + gamma), then min-max to [0, 1].  direct != 0
+// stands for the reference's dense solve: tol = 1e-7 max(1, |s|) formed here, max_iters from the host (2048).
+// Thread t owns rows t + 256 m: their h, r and A p live in its registers, p in LDS (the only vector other threads read).
+// Every dot product is fp64: per-thread partials in row order, the wave's butterfly, then the four waves in order -- a
+// lattice's gates depend on nothing but the lattice.  Every thread reads the reduced sums from LDS after a barrier, so the
+// stop decision is uniform and nobody is left behind a __syncthreads().
+__global__ __launch_bounds__(256) void k_cq_gates(const GateArgs a) {
+  __shared__ float qn[kBundleCols];
+  __shared__ float sp[host::kCorpusMaxTopK];
+  __shared__ double s_red[2][4];
+  __shared__ float s_mm[2][4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int lat = blockIdx.x, K = a.K;
+  const int64_t r0 = (int64_t)lat * K;
+  const float* psi = a.psi + (size_t)lat * a.ldn;
+  const float qinv = 1.0f / a.qnorm[lat];
+  for (int c = tid; c < a.ldn; c += 256) qn[c] = psi[c] * qinv;
+  __syncthreads();
+  for (int r = wave; r < K; r += 4) {  // a wave per row
+    const float* yi = a.Yn + (size_t)(r0 + r) * a.ldn;
+    float s = 0.f;
+    for (int c = lane; c < a.ldn; c += 64) s = fmaf(yi[c], qn[c], s);
+    s = wave_sum_f(s);
+    if (lane == 0) sp[r] = a.beta * fmaxf(0.f, s);
+  }
+  __syncthreads();
+  auto block_sum2 = [&](double u, double v, double& U, double& V) {
+    u = wave_sum_d2(u);
+    v = wave_sum_d2(v);
+    if (lane == 0) {
+      s_red[0][wave] = u;
+      s_red[1][wave] = v;
+    }
+    __syncthreads();
+    U = ((s_red[0][0] + s_red[0][1]) + s_red[0][2]) + s_red[0][3];
+    V = ((s_red[1][0] + s_red[1][1]) + s_red[1][2]) + s_red[1][3];
+    __syncthreads();
+  };
+  auto block_sum = [&](double u) {
+    u = wave_sum_d2(u);
+    if (lane == 0) s_red[0][wave] = u;
+    __syncthreads();
+    const double U = ((s_red[0][0] + s_red[0][1]) + s_red[0][2]) + s_red[0][3];
+    __syncthreads();
+    return U;
+  };
+  const float cs = 1.0f + a.gamma;
+  const float invMd = 1.f / ((1.0f + a.gamma) + 1e-12f);
+  float h[kGateOwn], r[kGateOwn], ap[kGateOwn];
+  double t1 = 0.0, t2 = 0.0, ss, rz;
+#pragma unroll
+  for (int m = 0; m < kGateOwn; ++m) {  // x0 = 0: r = s, p = z = r / diag
+    const int row = tid + 256 * m;
+    h[m] = r[m] = ap[m] = 0.f;
+    if (row < K) {
+      const float sv = sp[row];
+      const float z = sv * invMd;
+      r[m] = sv;
+      sp[row] = z;
+      t1 += (double)sv * (double)sv;
+      t2 += (double)sv * (double)z;
+    }
+  }
+  block_sum2(t1, t2, ss, rz);  // (its barriers also publish p)
+  const float tol = a.direct ? 1e-7f * fmaxf(1.0f, (float)sqrt(ss)) : a.tol;
+  int it = 1;
+  float resv = 0.f;
+  for (; it <= a.max_iters; ++it) {
+    double pap = 0.0, T1, T2;
+#pragma unroll
+    for (int m = 0; m < kGateOwn; ++m) {
+      const int row = tid + 256 * m;
+      if (row < K) {
+        const int64_t i = r0 + row;
+        const int d = a.deg[i];
+        float acc = 0.f;
+        for (int e = 0; e < d; ++e) acc = fmaf(a.w[i * a.k + e], sp[a.col[i * a.k + e] - r0], acc);
+        const float pv = sp[row];
+        ap[m] = cs * pv - acc;
+        pap += (double)pv * (double)ap[m];
+      }
+    }
+    const float alpha = (float)(rz / (block_sum(pap) + 1e-18));  // solver.py:25-26
+    t1 = t2 = 0.0;
+#pragma unroll
+    for (int m = 0; m < kGateOwn; ++m) {
+      const int row = tid + 256 * m;
+      if (row < K) {
+        h[m] = fmaf(sp[row], alpha, h[m]);
+        const float rr = fmaf(-ap[m], alpha, r[m]);
+        r[m] = rr;
+        t1 += (double)rr * (double)rr;
+        t2 += (double)rr * (double)(rr * invMd);
+      }
+    }
+    block_sum2(t1, t2, T1, T2);
+    resv = (float)sqrt(T1);
+    if (resv <= tol) break;  // solver.py:30-31, before the beta / p update (uniform: T1 comes from LDS)
+    if (it == a.max_iters) break;
+    const float beta = (float)(T2 / (rz + 1e-18));  // solver.py:33-34
+#pragma unroll
+    for (int m = 0; m < kGateOwn; ++m) {
+      const int row = tid + 256 * m;
+      if (row < K) sp[row] = fmaf(sp[row], beta, r[m] * invMd);
+    }
+    rz = T2;
+    __syncthreads();
+  }
+  const float qnan = __uint_as_float(0x7FC00000u);
+  auto nmin = [&](float x, float y) { return (x != x || y != y) ? qnan : fminf(x, y); };  // np.min / np.max keep a NaN
+  auto nmax = [&](float x, float y) { return (x != x || y != y) ? qnan : fmaxf(x, y); };
+  float lo = INFINITY, hi = -INFINITY;
+#pragma unroll
+  for (int m = 0; m < kGateOwn; ++m)
+    if (tid + 256 * m < K) {
+      lo = nmin(lo, h[m]);
+      hi = nmax(hi, h[m]);
+    }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    lo = nmin(lo, __shfl_xor(lo, o, 64));
+    hi = nmax(hi, __shfl_xor(hi, o, 64));
+  }
+  if (lane == 0) {
+    s_mm[0][wave] = lo;
+    s_mm[1][wave] = hi;
+  }
+  __syncthreads();
+  lo = nmin(nmin(s_mm[0][0], s_mm[0][1]), nmin(s_mm[0][2], s_mm[0][3]));
+  hi = nmax(nmax(s_mm[1][0], s_mm[1][1]), nmax(s_mm[1][2], s_mm[1][3]));
+  const bool flat = (double)hi - (double)lo < 1e-12;  // diffusion.py:119-122; false for a NaN, which then spreads
+  const float span = hi - lo;
+#pragma unroll
+  for (int m = 0; m < kGateOwn; ++m) {
+    const int row = tid + 256 * m;
+    if (row < K) {
+      float g = h[m];
+      if (a.clamp) {
+        g = flat ? 1.0f : __fdiv_rn(g - lo, span);
+        g = g < 0.f ? 0.f : (g > 1.f ? 1.f : g);  // np.clip: a NaN stays
+      }
+      a.gates[r0 + row] = g;
+    }
+  }
+  if (tid == 0) {
+    a.iters[lat] = it > a.max_iters ? a.max_iters : it;
+    a.res[lat] = resv;
+  }
+}
+
 }  // namespace
 }  // namespace osc
 
@@ -589,7 +784,11 @@ struct RefineReq {
   float row_cap, lamG, lamC, lamQ, tol;
   int32_t max_iters, kk;
   float alpha;
-  int32_t stage;           // 0 = search only, 1 = graph only, 2 = everything
+  int32_t stage;           // 0 = search only, 1 = up to the graph (and the gates, if asked for), 2 = everything
+  int32_t gate = 0;        // 0 = none (B = 1), 1 = diffusion gates computed per lattice, 2 = gates_in
+  const float* gates_in = nullptr;  // Q x K
+  float g_beta = 1.f, g_gamma = 0.1f, g_tol = 1e-4f;
+  int32_t g_direct = 1, g_max_iters = 2048, g_clamp = 1;
 };
 
 // one chunk [q0, q0 + nq): psi upload, candidates, and the requested stages; returns the layout used
@@ -637,6 +836,32 @@ host::CorpusLayout run_chunk(osc_corpus& c, const RefineReq& rq, int32_t q0, int
     HIP_CHECK(hipMemsetAsync(deg, 0, (size_t)rows * 4, s));
   }
   launch_cap_and_normalize(adj, w, col, deg, k, (int32_t)rows, rq.row_cap, 1, at<float>(c, L.scale), sd, s);
+  float* gates = at<float>(c, L.gates);
+  if (rq.gate == 1) {
+    GateArgs ga{};
+    ga.Yn = Ync;
+    ga.psi = psi;
+    ga.qnorm = qnorm;
+    ga.col = col;
+    ga.w = w;
+    ga.deg = deg;
+    ga.gates = gates;
+    ga.iters = at<int32_t>(c, L.g_iters);
+    ga.res = at<float>(c, L.g_res);
+    ga.K = K;
+    ga.k = k;
+    ga.ldn = ldn;
+    ga.max_iters = rq.g_max_iters;
+    ga.direct = rq.g_direct;
+    ga.clamp = rq.g_clamp;
+    ga.beta = rq.g_beta;
+    ga.gamma = rq.g_gamma;
+    ga.tol = rq.g_tol;
+    hipLaunchKernelGGL(k_cq_gates, dim3((unsigned)nq), dim3(256), 0, s, ga);
+    HIP_CHECK(hipGetLastError());
+  } else if (rq.gate == 2) {
+    HIP_CHECK(hipMemcpyAsync(gates, rq.gates_in + (size_t)q0 * K, (size_t)rows * 4, hipMemcpyHostToDevice, s));
+  }
   if (rq.stage == 1) return L;
   SolveArgs sa{};
   sa.Y = Yc;
@@ -658,12 +883,22 @@ host::CorpusLayout run_chunk(osc_corpus& c, const RefineReq& rq, int32_t q0, int
   sa.lamC = rq.lamC;
   sa.lamQ = rq.lamQ;
   sa.tol = rq.tol;
+  sa.B = rq.gate ? gates : nullptr;
   const int nc = (ldn + 255) / 256;
-  if (nc <= 1) hipLaunchKernelGGL(k_cq_solve<1>, dim3((unsigned)nq), dim3(256), 0, s, sa);
-  else if (nc == 2) hipLaunchKernelGGL(k_cq_solve<2>, dim3((unsigned)nq), dim3(256), 0, s, sa);
-  else if (nc == 3) hipLaunchKernelGGL(k_cq_solve<3>, dim3((unsigned)nq), dim3(256), 0, s, sa);
-  else if (nc == 4) hipLaunchKernelGGL(k_cq_solve<4>, dim3((unsigned)nq), dim3(256), 0, s, sa);
-  else hipLaunchKernelGGL(k_cq_solve<6>, dim3((unsigned)nq), dim3(256), 0, s, sa);
+  const dim3 sg((unsigned)nq), sb(256);
+  if (!rq.gate) {
+    if (nc <= 1) hipLaunchKernelGGL((k_cq_solve<1, false>), sg, sb, 0, s, sa);
+    else if (nc == 2) hipLaunchKernelGGL((k_cq_solve<2, false>), sg, sb, 0, s, sa);
+    else if (nc == 3) hipLaunchKernelGGL((k_cq_solve<3, false>), sg, sb, 0, s, sa);
+    else if (nc == 4) hipLaunchKernelGGL((k_cq_solve<4, false>), sg, sb, 0, s, sa);
+    else hipLaunchKernelGGL((k_cq_solve<6, false>), sg, sb, 0, s, sa);
+  } else {
+    if (nc <= 1) hipLaunchKernelGGL((k_cq_solve<1, true>), sg, sb, 0, s, sa);
+    else if (nc == 2) hipLaunchKernelGGL((k_cq_solve<2, true>), sg, sb, 0, s, sa);
+    else if (nc == 3) hipLaunchKernelGGL((k_cq_solve<3, true>), sg, sb, 0, s, sa);
+    else if (nc == 4) hipLaunchKernelGGL((k_cq_solve<4, true>), sg, sb, 0, s, sa);
+    else hipLaunchKernelGGL((k_cq_solve<6, true>), sg, sb, 0, s, sa);
+  }
   HIP_CHECK(hipGetLastError());
   if (rq.kk > 0) {
     BundleArgs ba{};
@@ -707,6 +942,100 @@ void check_candidates(const osc_corpus& c, const int32_t* cand, int32_t Q, int32
 
 int32_t chunk_for(const osc_corpus& c, int32_t K, int32_t knn, int32_t kk) {
   return host::corpus_chunk(c.N, c.ldn, K, std::max(1, knn), std::max(1, kk), c.chunk_req, host::kCorpusBudgetBytes);
+}
+
+struct RefineOut {
+  int32_t* cand;
+  int32_t* local;
+  float* score;
+  float* align;
+  int32_t* iters;
+  float* res;
+  float* gates = nullptr;     // the three below: gated calls only
+  int32_t* g_iters = nullptr;
+  float* g_res = nullptr;
+};
+
+void check_gate_settings(float beta, float gamma, int32_t method, int32_t max_iters) {
+  if (!(gamma > 0.f) || !std::isfinite(gamma)) throw Invalid("gamma must be > 0 for SPD");
+  if (!std::isfinite(beta)) throw Invalid("beta must be finite");
+  if (method != 0 && method != 1) throw Invalid("method must be 0 (direct) or 1 (cg)");
+  if (max_iters < 1) throw Invalid("max_iters must be >= 1");
+}
+
+// rq.psis / Q / gate fields set by the caller; the rest of the request is validated and filled here
+// what every per-lattice entry point checks first, in this order
+void check_request(const osc_corpus& c, const float* psis, int32_t Q, int32_t top_k, int32_t kneighbors) {
+  check_queries(c, psis, Q, top_k);
+  if (kneighbors < 1) throw Invalid("kneighbors must be >= 1");
+}
+
+// K and the list length of the request's lattices, and its candidates if given
+void set_shape(const osc_corpus& c, RefineReq& rq, int32_t top_k, int32_t kneighbors, const int32_t* cand_in) {
+  rq.K = (int32_t)std::min<int64_t>(top_k, c.N);
+  rq.knn = rq.K > 1 ? host::corpus_knn(kneighbors, rq.K) : 0;
+  if (rq.knn > host::kCorpusMaxKnn) throw Invalid("min(kneighbors, K - 1) must be at most 128");
+  if (cand_in) check_candidates(c, cand_in, rq.Q, rq.K);
+  rq.cand_in = cand_in;
+}
+
+// runs the request chunk by chunk; fetch(L, q0, n, down) queues the chunk's downloads, then the stream is drained
+template <class F>
+void for_each_chunk(osc_corpus& c, const RefineReq& rq, F&& fetch) {
+  const int32_t nq = chunk_for(c, rq.K, rq.knn, rq.kk);
+  auto down = [&](void* dst, int64_t off, size_t bytes) {
+    HIP_CHECK(hipMemcpyAsync(dst, c.scratch.p + off, bytes, hipMemcpyDeviceToHost, c.stream));
+  };
+  for (int32_t ch = 0; ch < host::chunk_count(rq.Q, nq); ++ch) {
+    const int32_t q0 = host::chunk_begin(ch, nq), n = host::chunk_size(rq.Q, ch, nq);
+    const host::CorpusLayout L = run_chunk(c, rq, q0, n, nq);
+    fetch(L, q0, n, down);
+    HIP_CHECK(hipStreamSynchronize(c.stream));
+  }
+}
+
+void refine_body(osc_corpus& c, RefineReq rq, int32_t top_k, const int32_t* cand_in, int32_t kneighbors, float row_cap,
+                 float lamG, float lamC, float lamQ, float tol, int32_t max_iters, int32_t k, float alpha,
+                 const RefineOut& o, const char* null_msg) {
+  const int32_t Q = rq.Q;
+  check_request(c, rq.psis, Q, top_k, kneighbors);
+  if (!(lamG > 0.f) || lamC < 0.f || lamQ < 0.f) throw Invalid("need lamG > 0, lamC >= 0, lamQ >= 0");
+  set_shape(c, rq, top_k, kneighbors, cand_in);
+  rq.kk = std::min(std::max(k, 0), rq.K);
+  if (rq.gate == 2)
+    for (int64_t i = 0; i < (int64_t)Q * rq.K; ++i)
+      if (!std::isfinite(rq.gates_in[i]) || rq.gates_in[i] < 0.f) throw Invalid("gates must be finite and >= 0");
+  if (Q == 0) return;
+  if (!o.cand || !o.iters || !o.res || (rq.kk > 0 && (!o.local || !o.score || !o.align)) ||
+      (rq.gate && (!o.gates || !o.g_iters || !o.g_res)))
+    throw Invalid(null_msg);
+  rq.row_cap = row_cap;
+  rq.lamG = lamG;
+  rq.lamC = lamC;
+  rq.lamQ = lamQ;
+  rq.tol = tol;
+  rq.max_iters = std::max(1, max_iters);
+  rq.alpha = alpha;
+  rq.stage = 2;
+  for_each_chunk(c, rq, [&](const host::CorpusLayout& L, int32_t q0, int32_t n, auto& down) {
+    down(o.cand + (size_t)q0 * rq.K, L.cand, (size_t)n * rq.K * 4);
+    down(o.iters + q0, L.iters, (size_t)n * 4);
+    down(o.res + q0, L.res, (size_t)n * 4);
+    if (rq.kk > 0) {
+      down(o.local + (size_t)q0 * rq.kk, L.o_local, (size_t)n * rq.kk * 4);
+      down(o.score + (size_t)q0 * rq.kk, L.o_score, (size_t)n * rq.kk * 4);
+      down(o.align + (size_t)q0 * rq.kk, L.o_align, (size_t)n * rq.kk * 4);
+    }
+    if (rq.gate) down(o.gates + (size_t)q0 * rq.K, L.gates, (size_t)n * rq.K * 4);
+    if (rq.gate == 1) {
+      down(o.g_iters + q0, L.g_iters, (size_t)n * 4);
+      down(o.g_res + q0, L.g_res, (size_t)n * 4);
+    }
+  });
+  if (rq.gate == 2) {  // nothing was solved for given gates
+    std::fill(o.g_iters, o.g_iters + Q, 0);
+    std::fill(o.g_res, o.g_res + Q, 0.f);
+  }
 }
 
 }  // namespace
@@ -803,45 +1132,72 @@ int osc_corpus_refine(osc_corpus_handle h, const float* psis, int32_t Q, int32_t
                       int32_t k, float alpha, int32_t* cand_out, int32_t* local, float* score, float* align, int32_t* iters,
                       float* res) {
   return corpus_guarded(h, [&](osc_corpus& c) {
-    check_queries(c, psis, Q, top_k);
-    if (kneighbors < 1) throw Invalid("kneighbors must be >= 1");
-    if (!(lamG > 0.f) || lamC < 0.f || lamQ < 0.f) throw Invalid("need lamG > 0, lamC >= 0, lamQ >= 0");
     RefineReq rq{};
     rq.psis = psis;
     rq.Q = Q;
-    rq.K = (int32_t)std::min<int64_t>(top_k, c.N);
-    rq.knn = rq.K > 1 ? host::corpus_knn(kneighbors, rq.K) : 0;
-    if (rq.knn > host::kCorpusMaxKnn) throw Invalid("min(kneighbors, K - 1) must be at most 128");
-    rq.kk = std::min(std::max(k, 0), rq.K);
-    if (cand_in) check_candidates(c, cand_in, Q, rq.K);
-    if (Q == 0) return;
-    if (!cand_out || !iters || !res || (rq.kk > 0 && (!local || !score || !align))) throw Invalid("osc_corpus_refine: NULL buffer");
-    rq.cand_in = cand_in;
-    rq.row_cap = row_cap;
-    rq.lamG = lamG;
-    rq.lamC = lamC;
-    rq.lamQ = lamQ;
-    rq.tol = tol;
-    rq.max_iters = std::max(1, max_iters);
-    rq.alpha = alpha;
-    rq.stage = 2;
-    const int32_t nq = chunk_for(c, rq.K, rq.knn, rq.kk);
-    for (int32_t ch = 0; ch < host::chunk_count(Q, nq); ++ch) {
-      const int32_t q0 = host::chunk_begin(ch, nq), n = host::chunk_size(Q, ch, nq);
-      const host::CorpusLayout L = run_chunk(c, rq, q0, n, nq);
-      auto down = [&](void* dst, int64_t off, size_t bytes) {
-        HIP_CHECK(hipMemcpyAsync(dst, c.scratch.p + off, bytes, hipMemcpyDeviceToHost, c.stream));
-      };
-      down(cand_out + (size_t)q0 * rq.K, L.cand, (size_t)n * rq.K * 4);
-      down(iters + q0, L.iters, (size_t)n * 4);
-      down(res + q0, L.res, (size_t)n * 4);
-      if (rq.kk > 0) {
-        down(local + (size_t)q0 * rq.kk, L.o_local, (size_t)n * rq.kk * 4);
-        down(score + (size_t)q0 * rq.kk, L.o_score, (size_t)n * rq.kk * 4);
-        down(align + (size_t)q0 * rq.kk, L.o_align, (size_t)n * rq.kk * 4);
-      }
-      HIP_CHECK(hipStreamSynchronize(c.stream));
+    refine_body(c, rq, top_k, cand_in, kneighbors, row_cap, lamG, lamC, lamQ, tol, max_iters, k, alpha,
+                RefineOut{cand_out, local, score, align, iters, res}, "osc_corpus_refine: NULL buffer");
+  });
+}
+
+int osc_corpus_refine_gated(osc_corpus_handle h, const float* psis, int32_t Q, int32_t top_k, const int32_t* cand_in,
+                            const float* gates_in, float beta, float gamma, int32_t method, float gate_tol,
+                            int32_t gate_max_iters, int32_t kneighbors, float row_cap, float lamG, float lamC, float lamQ,
+                            float tol, int32_t max_iters, int32_t k, float alpha, int32_t* cand_out, float* gates_out,
+                            int32_t* local, float* score, float* align, int32_t* iters, float* res, int32_t* gate_iters,
+                            float* gate_res) {
+  return corpus_guarded(h, [&](osc_corpus& c) {
+    RefineReq rq{};
+    rq.psis = psis;
+    rq.Q = Q;
+    if (gates_in) {
+      rq.gate = 2;
+      rq.gates_in = gates_in;
+    } else {
+      check_gate_settings(beta, gamma, method, gate_max_iters);
+      rq.gate = 1;
+      rq.g_beta = beta;
+      rq.g_gamma = gamma;
+      rq.g_direct = method == 0;
+      rq.g_tol = gate_tol;
+      rq.g_max_iters = method == 0 ? 2048 : gate_max_iters;
     }
+    RefineOut o{cand_out, local, score, align, iters, res};
+    o.gates = gates_out;
+    o.g_iters = gate_iters;
+    o.g_res = gate_res;
+    refine_body(c, rq, top_k, cand_in, kneighbors, row_cap, lamG, lamC, lamQ, tol, max_iters, k, alpha, o,
+                "osc_corpus_refine_gated: NULL buffer");
+  });
+}
+
+int osc_corpus_gates(osc_corpus_handle h, const float* psis, int32_t Q, int32_t top_k, const int32_t* cand_in,
+                     int32_t kneighbors, float row_cap, float beta, float gamma, int32_t method, float tol,
+                     int32_t max_iters, int32_t clamp, int32_t* cand_out, float* gates_out, int32_t* iters, float* res) {
+  return corpus_guarded(h, [&](osc_corpus& c) {
+    check_request(c, psis, Q, top_k, kneighbors);
+    check_gate_settings(beta, gamma, method, max_iters);
+    RefineReq rq{};
+    rq.psis = psis;
+    rq.Q = Q;
+    set_shape(c, rq, top_k, kneighbors, cand_in);
+    if (Q == 0) return;
+    if (!cand_out || !gates_out || !iters || !res) throw Invalid("osc_corpus_gates: NULL buffer");
+    rq.row_cap = row_cap;
+    rq.stage = 1;
+    rq.gate = 1;
+    rq.g_beta = beta;
+    rq.g_gamma = gamma;
+    rq.g_direct = method == 0;
+    rq.g_tol = tol;
+    rq.g_max_iters = method == 0 ? 2048 : max_iters;
+    rq.g_clamp = clamp != 0;
+    for_each_chunk(c, rq, [&](const host::CorpusLayout& L, int32_t q0, int32_t n, auto& down) {
+      down(cand_out + (size_t)q0 * rq.K, L.cand, (size_t)n * rq.K * 4);
+      down(gates_out + (size_t)q0 * rq.K, L.gates, (size_t)n * rq.K * 4);
+      down(iters + q0, L.g_iters, (size_t)n * 4);
+      down(res + q0, L.g_res, (size_t)n * 4);
+    });
   });
 }
 
