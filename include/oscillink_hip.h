@@ -268,6 +268,31 @@ int osc_corpus_refine_gated(osc_corpus_handle h, const float* psis, int32_t Q, i
                             float tol, int32_t max_iters, int32_t k, float alpha, int32_t* cand_out, float* gates_out,
                             int32_t* local, float* score, float* align, int32_t* iters, float* res, int32_t* gate_iters,
                             float* gate_res);
+/* The loop body the reference ships with its energy receipt (examples/rag_replacement.py:48-73 and 159-184,
+ * examples/diffusion_gated.py, cloud/app/main.py:1043-1063), for Q queries:
+ * `lat = Oscillink(Y[cand], ...); lat.set_query(psi[, gates=g]); lat.settle(dt, settle_max_iters, settle_tol);
+ *  lat.bundle(k, alpha); lat.receipt()`.  Everything osc_corpus_refine_gated takes and returns, with gate_mode 0 = no gates
+ * (gates_out / gate_iters / gate_res may be NULL), 1 = diffusion gates computed per lattice, 2 = gates_in; behind the bundle
+ * every lattice is settled (one implicit-Euler step from U = Y, Jacobi-PCG, each lattice stopping on its own) and its
+ * receipt is taken on the device.  detail 0 = light (deltaH only; the three sums are zero, no null points), 1 = full.
+ * Out per query: settle_iters / settle_res; dH, coh_sum, anchor_sum, query_sum (fp64 sums in row order, not yet rounded to
+ * float32 as receipt() reports them); null_total (found) and null_offsets (Q + 1): the kept null points of query q are
+ * null_i / null_j / null_z / null_r [null_offsets[q], null_offsets[q + 1]), local row ids of the candidate lattice, in row
+ * order -- or, with null_cap > 0 and more found, the null_cap highest z (z descending, then row ascending; selected on the
+ * device).  null_capacity >= Q * (null_cap > 0 ? min(null_cap, K) : K) entries in full detail.  z_th: 3.0 in receipt().
+ * Optional (NULL skips the download of the chunk's degree and column arrays): nnz_out (Q) the lattice's stored edges,
+ * edge_prefix (Q x edge_prefix_cap x 2, int64) its first (i, j) pairs in local ids, row-major, edge_prefix_n (Q) how many. */
+int osc_corpus_refine_receipts(osc_corpus_handle h, const float* psis, int32_t Q, int32_t top_k, const int32_t* cand_in,
+                               int32_t gate_mode, const float* gates_in, float beta, float gamma, int32_t method,
+                               float gate_tol, int32_t gate_max_iters, int32_t kneighbors, float row_cap, float lamG,
+                               float lamC, float lamQ, float tol, int32_t max_iters, int32_t k, float alpha, float dt,
+                               int32_t settle_max_iters, float settle_tol, int32_t detail, float z_th, int32_t null_cap,
+                               int32_t* cand_out, float* gates_out, int32_t* local, float* score, float* align,
+                               int32_t* iters, float* res, int32_t* gate_iters, float* gate_res, int32_t* settle_iters,
+                               float* settle_res, double* dH, double* coh_sum, double* anchor_sum, double* query_sum,
+                               int32_t* null_total, int64_t* null_offsets, int32_t* null_i, int32_t* null_j, float* null_z,
+                               float* null_r, int64_t null_capacity, int64_t* nnz_out, int64_t* edge_prefix,
+                               int32_t* edge_prefix_n, int32_t edge_prefix_cap);
 /* The candidate lattice's graph of one query (mutual_knn_adj + row_sum_cap + normalized_laplacian, graph.py:8-93) as
  * osc_get_csr gives it for `Oscillink(Y[cand])`: rowptr K + 1, col / a / w nnz (<= capacity), sqrt_deg K; local row ids.
  * Test / diagnostic aid. */

@@ -8,6 +8,7 @@ does not apply; here every lattice of a chunk is built, solved and bundled by th
 from __future__ import annotations
 
 import ctypes as C
+import hashlib
 import os
 from typing import Any, Optional
 
@@ -20,6 +21,9 @@ MAX_KNEIGHBORS = 128  # the dense build route's per-row list (k_knn_select)
 MAX_D = 1536  # the bundle kernel keeps the normalised query in LDS
 USTAR_TOL, USTAR_MAX_ITERS = 1e-4, 64  # _ensure_device_ustar's settings
 GATE_METHODS = {"direct": 0, "cg": 1}  # osc_corpus_gates' method codes
+RECEIPT_DETAILS = {"light": 0, "full": 1}  # osc_corpus_refine_receipts' detail codes (set_receipt_detail's words)
+RECEIPT_Z_TH = 3.0  # receipt()'s null-point threshold
+EDGE_PREFIX = 2048  # edges under the state signature (OscillinkLattice._edge_prefix)
 
 
 class Corpus:
@@ -140,6 +144,20 @@ class Corpus:
         return float(beta), float(gamma), GATE_METHODS[method], int(max_iters)
 
     @staticmethod
+    def _receipt_settings(receipts, settle_dt, settle_max_iters, settle_tol):
+        """(detail code or None, dt, max_iters, tol) of refine_many's receipts arguments, checked before any native call."""
+        if receipts is not None and (not isinstance(receipts, str) or receipts not in RECEIPT_DETAILS):
+            raise ValueError(f"receipts must be None, 'light' or 'full', got {receipts!r}")
+        if not np.isfinite(float(settle_dt)) or not float(settle_dt) > 0:
+            raise ValueError("settle_dt must be finite and > 0")
+        if int(settle_max_iters) < 1:
+            raise ValueError("settle_max_iters must be >= 1")
+        if not np.isfinite(float(settle_tol)):
+            raise ValueError("settle_tol must be finite")
+        return (None if receipts is None else RECEIPT_DETAILS[receipts], float(settle_dt), int(settle_max_iters),
+                float(settle_tol))
+
+    @staticmethod
     def _warn_non_finite(gates: np.ndarray, iters: np.ndarray, res: np.ndarray, what: str) -> None:
         bad = np.nonzero(~np.all(np.isfinite(gates), axis=1))[0]
         if bad.size:  # compute_diffusion_gates hands such gates back with a warning as well
@@ -167,7 +185,9 @@ class Corpus:
                     row_cap_val: float = 1.0, lamG: float = 1.0, lamC: float = 0.5, lamQ: float = 4.0,
                     deterministic_k: bool = False, neighbor_seed: Optional[int] = None, candidates=None,
                     as_arrays: bool = False, gates=None, gate_beta: float = 1.0, gate_gamma: float = 0.1,
-                    gate_method: str = "direct", gate_tol: float = 1e-4, gate_max_iters: int = 256):
+                    gate_method: str = "direct", gate_tol: float = 1e-4, gate_max_iters: int = 256,
+                    receipts: Optional[str] = None, settle_dt: float = 1.0, settle_max_iters: int = 12,
+                    settle_tol: float = 1e-3):
         """For each query q, what the reference's loop returns with `cand = search(psis, top_k)[0][q]` (or
         `candidates[q]`):
 
@@ -188,10 +208,27 @@ class Corpus:
 
         Returns Q lists of {"id", "score", "align"}, or with `as_arrays=True` a dict of `ids`, `local`, `score`, `align`
         (Q, min(k, K)), `candidates` (Q, K), `ustar_iters` and `ustar_res` (Q,); with gates also `gates` (Q, K) float32 and
-        `gate_iters`, `gate_res` (Q,; zeros for given gates)."""
+        `gate_iters`, `gate_res` (Q,; zeros for given gates).
+
+        `receipts="light"` or `"full"` (set_receipt_detail's words) runs the loop the reference ships with its audit trail
+        (examples/rag_replacement.py:48-73): per query additionally `s = lat.settle(settle_dt, settle_max_iters, settle_tol)`
+        before the bundle and `rec = lat.receipt()` after it, for the same lattice, query and gates, on the device -- a
+        fresh lattice (U = Y; warm_start / inertia have nothing to act on), Jacobi preconditioning; a settle that does not
+        converge does not raise.  With `as_arrays=True` the dict gains `settle_iters` int32, `settle_res` float32, `deltaH`,
+        `coh_drop_sum`, `anchor_pen_sum`, `query_term_sum` float64 (Q,) with receipt()'s float32 rounding (the three sums are
+        zero in light detail) and, in full detail, `null_total` (Q,), `null_offsets` (Q + 1,), `null_i`, `null_j` (local row
+        ids of the candidate lattice), `null_z`, `null_r`: receipt_many's layout.  OSCILLINK_RECEIPT_NULL_CAP means what it
+        means for receipt() (highest z kept, stable), applied on the device.  Otherwise Q dicts {"bundle": [...], "settle":
+        {"iters", "res"}, "receipt": {...}}; "receipt" has receipt()'s keys, `state_sig` equal to the loop's, cg_iters /
+        residual from the settle, ustar_* from the U* solve and meta["ustar_source"] = "corpus_batch".  Fields that describe
+        one handle's clock or cache have no per-lattice meaning in a batch and are fixed: t_ms, ustar_solve_ms,
+        graph_build_ms, last_settle_ms = 0.0, ustar_cached False, ustar_solves 1, ustar_cache_hits 0.  Not covered:
+        HMAC-signed receipts (a Corpus has no secret), chains on candidate lattices, OSCILLINK_RECEIPT_DYNAMICS, and
+        preconditioners other than "jacobi".  `receipts=None` is the call as it was."""
         P = self._queries(psis)
         K = self._top_k(top_k)
-        knn = self._knn(kneighbors, K)  # noqa: F841 (validation)
+        knn = self._knn(kneighbors, K)
+        detail, s_dt, s_max, s_tol = self._receipt_settings(receipts, settle_dt, settle_max_iters, settle_tol)
         if float(lamG) <= 0:
             raise ValueError("lamG must be > 0 for SPD")
         for name, val in (("lamC", lamC), ("lamQ", lamQ)):
@@ -224,6 +261,10 @@ class Corpus:
         g = np.zeros((Q, K), dtype=np.float32)
         g_iters = np.zeros(Q, dtype=np.int32)
         g_res = np.zeros(Q, dtype=np.float32)
+        if detail is not None:
+            return self._refine_receipts(P, K, knn, kk, cand_in, gates, gates_in, gate_set, (detail, s_dt, s_max, s_tol),
+                                         (top_k, kneighbors, row_cap_val, lamG, lamC, lamQ, deterministic_k, alpha, gate_tol),
+                                         (cand, local, score, align, iters, res, g, g_iters, g_res), as_arrays)
         if Q and not gated:
             self._call("osc_corpus_refine", nat.f32(P), Q, int(top_k), None if cand_in is None else nat.i32(cand_in),
                        int(kneighbors), float(row_cap_val), float(lamG), float(lamC), float(lamQ), USTAR_TOL,
@@ -248,6 +289,124 @@ class Corpus:
             return out
         return [[{"id": int(i), "score": float(s), "align": float(a)} for i, s, a in
                  zip(ids[q].tolist(), score[q].tolist(), align[q].tolist())] for q in range(Q)]
+
+    def _refine_receipts(self, P, K, knn, kk, cand_in, gates, gates_in, gate_set, settle, settings, outputs, as_arrays):
+        """refine_many with receipts, behind its validation: one osc_corpus_refine_receipts call, then the arrays or the
+        loop's dicts.  settle = (detail code, dt, max_iters, tol); settings = refine_many's lattice arguments; outputs =
+        the result arrays it has allocated."""
+        from .lattice import OscillinkLattice, __version__
+
+        detail, s_dt, s_max, s_tol = settle
+        top_k, kneighbors, row_cap_val, lamG, lamC, lamQ, deterministic_k, alpha, gate_tol = settings
+        cand, local, score, align, iters, res, g, g_iters, g_res = outputs
+        Q = P.shape[0]
+        full = detail == 1
+        gated = gates is not None
+        mode = 0 if not gated else (2 if gates_in is not None else 1)
+        try:
+            cap_val = int(os.getenv("OSCILLINK_RECEIPT_NULL_CAP", "0").strip())
+        except ValueError:
+            cap_val = 0
+        cap_val = max(cap_val, 0)
+        slots = (min(cap_val, K) if cap_val > 0 else K) if full else 0
+        capacity = Q * slots
+        s_iters = np.zeros(Q, dtype=np.int32)
+        s_res = np.zeros(Q, dtype=np.float32)
+        sums = np.zeros((4, Q), dtype=np.float64)  # deltaH, coh, anchor, query
+        total = np.zeros(Q, dtype=np.int32)
+        offsets = np.zeros(Q + 1, dtype=np.int64)
+        ni = np.zeros(max(capacity, 1), dtype=np.int32)
+        nj = np.zeros(max(capacity, 1), dtype=np.int32)
+        nz = np.zeros(max(capacity, 1), dtype=np.float32)
+        nr = np.zeros(max(capacity, 1), dtype=np.float32)
+        dicts = not as_arrays
+        nnz = np.zeros(Q, dtype=np.int64)
+        pairs = np.zeros((Q if dicts else 0, EDGE_PREFIX, 2), dtype=np.int64)
+        pairs_n = np.zeros(Q, dtype=np.int32)
+        if Q:
+            beta, gamma, method, g_max = gate_set if gate_set is not None else (1.0, 0.1, 0, 1)
+            self._call("osc_corpus_refine_receipts", nat.f32(P), Q, int(top_k),
+                       None if cand_in is None else nat.i32(cand_in), mode, None if gates_in is None else nat.f32(gates_in),
+                       beta, gamma, method, float(gate_tol), g_max, int(kneighbors), float(row_cap_val), float(lamG),
+                       float(lamC), float(lamQ), USTAR_TOL, USTAR_MAX_ITERS, kk, float(alpha), s_dt, s_max, s_tol, detail,
+                       RECEIPT_Z_TH, cap_val, nat.i32(cand), nat.f32(g), nat.i32(local), nat.f32(score), nat.f32(align),
+                       nat.i32(iters), nat.f32(res), nat.i32(g_iters), nat.f32(g_res), nat.i32(s_iters), nat.f32(s_res),
+                       *[sums[t].ctypes.data_as(nat.c_f64p) for t in range(4)], nat.i32(total), nat.i64(offsets),
+                       nat.i32(ni), nat.i32(nj), nat.f32(nz), nat.f32(nr), int(capacity),
+                       nat.i64(nnz) if dicts else None, nat.i64(pairs) if dicts else None,
+                       nat.i32(pairs_n) if dicts else None, EDGE_PREFIX)
+            if mode == 1:
+                self._warn_non_finite(g, g_iters, g_res, "refine_many")
+        # the float32 rounding receipt() gives its energies (a float32 dH / np.sum over float32 rows)
+        sums = sums.astype(np.float32).astype(np.float64)
+        kept = int(offsets[-1])
+        ids = np.take_along_axis(cand, local, axis=1) if kk else np.zeros((Q, 0), dtype=np.int32)
+        if as_arrays:
+            out = {"ids": ids, "local": local, "score": score, "align": align, "candidates": cand,
+                   "ustar_iters": iters, "ustar_res": res}
+            if gated:
+                out.update(gates=g, gate_iters=g_iters, gate_res=g_res)
+            out.update(settle_iters=s_iters, settle_res=s_res, deltaH=sums[0], coh_drop_sum=sums[1],
+                       anchor_pen_sum=sums[2], query_term_sum=sums[3])
+            if full:
+                out.update(null_total=total.astype(np.int64), null_offsets=offsets, null_i=ni[:kept].copy(),
+                           null_j=nj[:kept].copy(), null_z=nz[:kept].copy(), null_r=nr[:kept].copy())
+            return out
+        detail_name = "full" if full else "light"
+        ones = np.ones(K, dtype=np.float32)
+        out = []
+        for q in range(Q):
+            B = g[q] if gated else ones
+            adj_sig = hashlib.sha256(np.ascontiguousarray(pairs[q, :int(pairs_n[q])]).tobytes()).hexdigest()
+            sig = OscillinkLattice._signature_digest(
+                {"psi": np.round(P[q], 6).tolist(), "lam": [lamG, lamC, lamQ, 0.0], "chain_present": False, "chain_len": 0,
+                 "k": knn, "detk": bool(deterministic_k), "adj": adj_sig}, B)
+            if full:
+                s, e = int(offsets[q]), int(offsets[q + 1])
+                nulls = OscillinkLattice._null_dicts(ni[s:e], nj[s:e], nz[s:e], nr[s:e], e - s)
+                tot = int(total[q])
+            else:
+                nulls, tot = [], 0
+            capped = cap_val > 0 and tot > cap_val
+            n_edges = int(nnz[q])
+            meta: dict[str, Any] = {
+                "ustar_cached": False,
+                "ustar_solves": 1,
+                "ustar_cache_hits": 0,
+                "ustar_converged": bool(float(res[q]) <= USTAR_TOL),
+                "ustar_res": float(res[q]),
+                "ustar_iters": int(iters[q]),
+                "ustar_solve_ms": 0.0,
+                "ustar_source": "corpus_batch",
+                "graph_build_ms": 0.0,
+                "last_settle_ms": 0.0,
+                "avg_degree": float(n_edges / max(K, 1)),
+                "edge_density": float(n_edges / max(K * (K - 1), 1)),
+                "gates_min": float(np.min(B)),
+                "gates_max": float(np.max(B)),
+                "gates_mean": float(np.mean(B)),
+                "gates_uniform": bool(np.allclose(B, B[0])),
+                "state_sig": sig,
+                "receipt_detail": detail_name,
+                "null_points_summary": {"total_null_points": tot, "returned_null_points": cap_val if capped else tot,
+                                        "null_cap_applied": bool(capped)},
+            }
+            rec = {
+                "version": str(__version__),
+                "deltaH_total": float(sums[0, q]),
+                "coh_drop_sum": float(sums[1, q]),
+                "anchor_pen_sum": float(sums[2, q]),
+                "query_term_sum": float(sums[3, q]),
+                "cg_iters": int(s_iters[q]),
+                "residual": float(s_res[q]),
+                "t_ms": 0.0,
+                "null_points": nulls,
+                "meta": meta,
+            }
+            bundle = [{"id": int(i), "score": float(sc), "align": float(a)} for i, sc, a in
+                      zip(ids[q].tolist(), score[q].tolist(), align[q].tolist())]
+            out.append({"bundle": bundle, "settle": {"iters": int(s_iters[q]), "res": float(s_res[q])}, "receipt": rec})
+        return out
 
     def diffusion_gates_many(self, psis, top_k: int, *, kneighbors: int = 6, row_cap_val: float = 1.0, beta: float = 1.0,
                              gamma: float = 0.1, method: str = "direct", tol: float = 1e-4, max_iters: int = 256,

@@ -40,9 +40,22 @@ struct CorpusLayout {
   int64_t gates;             // float  [nq][K]     diffusion gates B (computed or given); after every older block, so
   int64_t g_iters, g_res;    // int32 / float [nq]  that those keep the offsets they had before gates existed
   int64_t total;
+  // receipts (settle + receipt per lattice): behind g_res, and only when asked for -- all zero otherwise, total unchanged
+  int64_t s_iters, s_res;    // int32 / float [nq]  the settle's iterations and residual
+  int64_t r_sums;            // double [nq][4]      deltaH, coh_drop, anchor_pen, query_term
+  int64_t n_total, n_kept;   // int32  [nq]         null points found / written (the cap)
+  int64_t n_i, n_j, n_z, n_r;  // int32 / int32 / float / float [nq][null_slots] the kept null points, local ids
 };
 
-inline CorpusLayout corpus_layout(int64_t N, int32_t ldn, int32_t K, int32_t k, int32_t kk, int32_t nq) {
+// null-point slots per query of a receipts call: none in light detail, else K, or the cap when one is set
+inline int32_t corpus_null_slots(int32_t K, bool full, int32_t null_cap) {
+  if (!full) return 0;
+  return null_cap > 0 ? std::min(null_cap, K) : K;
+}
+
+// receipts = false: the layout of a plain / gated refine (null_slots ignored).  receipts = true adds the blocks above.
+inline CorpusLayout corpus_layout(int64_t N, int32_t ldn, int32_t K, int32_t k, int32_t kk, int32_t nq, bool receipts = false,
+                                  int32_t null_slots = 0) {
   CorpusLayout L{};
   const int64_t rows = (int64_t)nq * K, lds = corpus_lds(K);
   int64_t o = 0;
@@ -79,18 +92,31 @@ inline CorpusLayout corpus_layout(int64_t N, int32_t ldn, int32_t K, int32_t k, 
   L.gates = take((int64_t)nq * K * 4);
   L.g_iters = take((int64_t)nq * 4);
   L.g_res = take((int64_t)nq * 4);
+  if (receipts) {
+    const int64_t slots = std::max<int64_t>(0, null_slots);
+    L.s_iters = take((int64_t)nq * 4);
+    L.s_res = take((int64_t)nq * 4);
+    L.r_sums = take((int64_t)nq * 4 * 8);
+    L.n_total = take((int64_t)nq * 4);
+    L.n_kept = take((int64_t)nq * 4);
+    L.n_i = take((int64_t)nq * slots * 4);
+    L.n_j = take((int64_t)nq * slots * 4);
+    L.n_z = take((int64_t)nq * slots * 4);
+    L.n_r = take((int64_t)nq * slots * 4);
+  }
   L.total = o;
   return L;
 }
 
 // queries per chunk: the requested count (OSC_CORPUS_CHUNK, else kCorpusDefaultChunk), lowered until one chunk's scratch
 // fits the budget; at least 1 (a single query over budget still runs: its scratch is what it is)
-inline int32_t corpus_chunk(int64_t N, int32_t ldn, int32_t K, int32_t k, int32_t kk, int32_t requested, int64_t budget) {
+inline int32_t corpus_chunk(int64_t N, int32_t ldn, int32_t K, int32_t k, int32_t kk, int32_t requested, int64_t budget,
+                            bool receipts = false, int32_t null_slots = 0) {
   int32_t nq = std::max<int32_t>(1, requested);
-  const int64_t one = corpus_layout(N, ldn, K, k, kk, 1).total;
+  const int64_t one = corpus_layout(N, ldn, K, k, kk, 1, receipts, null_slots).total;
   const int64_t fit = std::max<int64_t>(1, budget / std::max<int64_t>(1, one));
   nq = (int32_t)std::min<int64_t>(nq, fit);
-  while (nq > 1 && corpus_layout(N, ldn, K, k, kk, nq).total > budget) --nq;
+  while (nq > 1 && corpus_layout(N, ldn, K, k, kk, nq, receipts, null_slots).total > budget) --nq;
   return nq;
 }
 

@@ -13,11 +13,17 @@
 //                  recurrences; only the stop test max_c |r_c| <= tol couples them, inside the workgroup); its GATED
 //                  instance reads B per row, the other one has B = 1 folded in
 //   k_cq_bundle  : coherence drop, alignment, fp64 z-score and MMR over S, one workgroup per lattice
+//   (corpus_receipt_kernels.hip)
+//   k_cq_settle  : (receipts only) settle() of the fresh lattice: one implicit-Euler step from U = Y by Jacobi-PCG, one
+//                  workgroup per lattice; its state takes the gathered Yn block, which nothing reads after the bundle
+//   k_cq_receipt : (receipts only) deltaH of the settled state against U*, and in full detail the three component sums and
+//                  the null points (cap applied in the workgroup), one workgroup per lattice
 //
 // No workgroup waits on another: every kernel's workgroups are independent.
 #include "osc_internal.hpp"
 #include "knn.hpp"
 #include "corpus_plan.hpp"
+#include "corpus_receipts.hpp"
 
 #include <cmath>
 #include <vector>
@@ -439,6 +445,7 @@ struct BundleArgs {
 
 constexpr int kBundleRows = host::kCorpusMaxTopK;
 constexpr int kBundleCols = 1536;
+static_assert(kBundleCols == kCqMaxCols && kBundleRows == kCqMaxRows, "the receipt kernel keeps the same rows and columns in LDS");
 
 // bundle(kk, alpha) of one lattice per workgroup (lattice.py:530-568): align_i = cos(U*_i, psi), coh_i (receipts.py:28-38,
 // the receipt kernel's per-edge arithmetic), z-scored with fp64 mean / std, score = alpha z + (1 - alpha) align, then
@@ -789,12 +796,15 @@ struct RefineReq {
   const float* gates_in = nullptr;  // Q x K
   float g_beta = 1.f, g_gamma = 0.1f, g_tol = 1e-4f;
   int32_t g_direct = 1, g_max_iters = 2048, g_clamp = 1;
+  int32_t receipts = 0;    // 0 = none, 1 = light, 2 = full: settle + receipt behind the bundle (stage 2 only)
+  float s_dt = 1.f, s_tol = 1e-3f, z_th = 3.f;
+  int32_t s_max_iters = 12, null_cap = 0, null_slots = 0;
 };
 
 // one chunk [q0, q0 + nq): psi upload, candidates, and the requested stages; returns the layout used
 host::CorpusLayout run_chunk(osc_corpus& c, const RefineReq& rq, int32_t q0, int32_t nq, int32_t cap_nq) {
   const int32_t K = rq.K, ldn = c.ldn, k = std::max(1, rq.knn), kk = std::max(1, rq.kk);
-  const host::CorpusLayout L = host::corpus_layout(c.N, ldn, K, k, kk, cap_nq);
+  const host::CorpusLayout L = host::corpus_layout(c.N, ldn, K, k, kk, cap_nq, rq.receipts != 0, rq.null_slots);
   if ((int64_t)c.scratch.n < L.total) c.scratch.alloc((size_t)L.total);
   hipStream_t s = c.stream;
   std::vector<float> hp((size_t)nq * ldn, 0.f);
@@ -925,6 +935,59 @@ host::CorpusLayout run_chunk(osc_corpus& c, const RefineReq& rq, int32_t q0, int
     hipLaunchKernelGGL(k_cq_bundle, dim3((unsigned)nq), dim3(256), 0, s, ba);
     HIP_CHECK(hipGetLastError());
   }
+  if (!rq.receipts) return L;
+  CqSettleArgs ta{};
+  ta.Y = Yc;
+  ta.psi = psi;
+  ta.col = col;
+  ta.w = w;
+  ta.deg = deg;
+  ta.X = Ync;  // dead since the graph, the gates and the bundle: the settled state lives there, U* stays in X
+  ta.R = sa.R;
+  ta.P = sa.P;
+  ta.AP = sa.AP;
+  ta.iters = at<int32_t>(c, L.s_iters);
+  ta.res = at<float>(c, L.s_res);
+  ta.K = K;
+  ta.k = k;
+  ta.ldn = ldn;
+  ta.max_iters = rq.s_max_iters;
+  ta.lamG = rq.lamG;
+  ta.lamC = rq.lamC;
+  ta.lamQ = rq.lamQ;
+  ta.dt = rq.s_dt;
+  ta.tol = rq.s_tol;
+  ta.B = rq.gate ? gates : nullptr;
+  launch_cq_settle(ta, nq, s);
+  CqReceiptArgs ra{};
+  ra.Y = Yc;
+  ra.Us = X;
+  ra.Up = Ync;
+  ra.psi = psi;
+  ra.col = col;
+  ra.w = w;
+  ra.adj = adj;
+  ra.deg = deg;
+  ra.sd = sd;
+  ra.B = rq.gate ? gates : nullptr;
+  ra.K = K;
+  ra.k = k;
+  ra.ldn = ldn;
+  ra.full = rq.receipts == 2;
+  ra.cap = rq.null_cap;
+  ra.slots = rq.null_slots;
+  ra.lamG = rq.lamG;
+  ra.lamC = rq.lamC;
+  ra.lamQ = rq.lamQ;
+  ra.z_th = rq.z_th;
+  ra.sums = at<double>(c, L.r_sums);
+  ra.n_total = at<int32_t>(c, L.n_total);
+  ra.n_kept = at<int32_t>(c, L.n_kept);
+  ra.n_i = at<int32_t>(c, L.n_i);
+  ra.n_j = at<int32_t>(c, L.n_j);
+  ra.n_z = at<float>(c, L.n_z);
+  ra.n_r = at<float>(c, L.n_r);
+  launch_cq_receipt(ra, nq, s);
   return L;
 }
 
@@ -940,8 +1003,9 @@ void check_candidates(const osc_corpus& c, const int32_t* cand, int32_t Q, int32
     if (cand[i] < 0 || cand[i] >= c.N) throw Invalid("candidates: corpus id out of range");
 }
 
-int32_t chunk_for(const osc_corpus& c, int32_t K, int32_t knn, int32_t kk) {
-  return host::corpus_chunk(c.N, c.ldn, K, std::max(1, knn), std::max(1, kk), c.chunk_req, host::kCorpusBudgetBytes);
+int32_t chunk_for(const osc_corpus& c, int32_t K, int32_t knn, int32_t kk, bool receipts = false, int32_t null_slots = 0) {
+  return host::corpus_chunk(c.N, c.ldn, K, std::max(1, knn), std::max(1, kk), c.chunk_req, host::kCorpusBudgetBytes, receipts,
+                            null_slots);
 }
 
 struct RefineOut {
@@ -954,6 +1018,24 @@ struct RefineOut {
   float* gates = nullptr;     // the three below: gated calls only
   int32_t* g_iters = nullptr;
   float* g_res = nullptr;
+};
+
+// what a receipts call returns on top of RefineOut (osc_corpus_refine_receipts)
+struct ReceiptOut {
+  int32_t* s_iters;
+  float* s_res;
+  double* sums[4];          // deltaH, coh_drop, anchor_pen, query_term
+  int32_t* null_total;
+  int64_t* null_offsets;    // Q + 1
+  int32_t* null_i;
+  int32_t* null_j;
+  float* null_z;
+  float* null_r;
+  int64_t capacity;
+  int64_t* nnz;             // the three below: optional (state signature / degree fields of the dict form)
+  int64_t* edge_prefix;     // Q x prefix_cap x 2
+  int32_t* edge_prefix_n;
+  int32_t prefix_cap;
 };
 
 void check_gate_settings(float beta, float gamma, int32_t method, int32_t max_iters) {
@@ -982,7 +1064,7 @@ void set_shape(const osc_corpus& c, RefineReq& rq, int32_t top_k, int32_t kneigh
 // runs the request chunk by chunk; fetch(L, q0, n, down) queues the chunk's downloads, then the stream is drained
 template <class F>
 void for_each_chunk(osc_corpus& c, const RefineReq& rq, F&& fetch) {
-  const int32_t nq = chunk_for(c, rq.K, rq.knn, rq.kk);
+  const int32_t nq = chunk_for(c, rq.K, rq.knn, rq.kk, rq.receipts != 0, rq.null_slots);
   auto down = [&](void* dst, int64_t off, size_t bytes) {
     HIP_CHECK(hipMemcpyAsync(dst, c.scratch.p + off, bytes, hipMemcpyDeviceToHost, c.stream));
   };
@@ -996,7 +1078,7 @@ void for_each_chunk(osc_corpus& c, const RefineReq& rq, F&& fetch) {
 
 void refine_body(osc_corpus& c, RefineReq rq, int32_t top_k, const int32_t* cand_in, int32_t kneighbors, float row_cap,
                  float lamG, float lamC, float lamQ, float tol, int32_t max_iters, int32_t k, float alpha,
-                 const RefineOut& o, const char* null_msg) {
+                 const RefineOut& o, const char* null_msg, const ReceiptOut* ro = nullptr) {
   const int32_t Q = rq.Q;
   check_request(c, rq.psis, Q, top_k, kneighbors);
   if (!(lamG > 0.f) || lamC < 0.f || lamQ < 0.f) throw Invalid("need lamG > 0, lamC >= 0, lamQ >= 0");
@@ -1005,10 +1087,23 @@ void refine_body(osc_corpus& c, RefineReq rq, int32_t top_k, const int32_t* cand
   if (rq.gate == 2)
     for (int64_t i = 0; i < (int64_t)Q * rq.K; ++i)
       if (!std::isfinite(rq.gates_in[i]) || rq.gates_in[i] < 0.f) throw Invalid("gates must be finite and >= 0");
+  if (ro) {
+    if (!ro->null_offsets) throw Invalid(null_msg);
+    ro->null_offsets[0] = 0;
+  }
   if (Q == 0) return;
   if (!o.cand || !o.iters || !o.res || (rq.kk > 0 && (!o.local || !o.score || !o.align)) ||
       (rq.gate && (!o.gates || !o.g_iters || !o.g_res)))
     throw Invalid(null_msg);
+  const bool full = rq.receipts == 2;
+  if (ro) {
+    if (!ro->s_iters || !ro->s_res || !ro->sums[0] || !ro->sums[1] || !ro->sums[2] || !ro->sums[3] || !ro->null_total ||
+        (full && (!ro->null_i || !ro->null_j || !ro->null_z || !ro->null_r)) ||
+        (ro->edge_prefix && (!ro->edge_prefix_n || ro->prefix_cap < 0)))
+      throw Invalid(null_msg);
+    rq.null_slots = host::corpus_null_slots(rq.K, full, rq.null_cap);
+    if (full && ro->capacity < (int64_t)Q * rq.null_slots) throw Invalid("null point capacity too small");
+  }
   rq.row_cap = row_cap;
   rq.lamG = lamG;
   rq.lamC = lamC;
@@ -1030,6 +1125,59 @@ void refine_body(osc_corpus& c, RefineReq rq, int32_t top_k, const int32_t* cand
     if (rq.gate == 1) {
       down(o.g_iters + q0, L.g_iters, (size_t)n * 4);
       down(o.g_res + q0, L.g_res, (size_t)n * 4);
+    }
+    if (!ro) return;
+    // receipts: per-query scalars and the slabs of kept null points (null_slots per query), packed back to back on the host
+    // once the chunk's copies have landed (the stream is drained here: the staging vectors live in this call)
+    const int32_t slots = rq.null_slots, kw = std::max(1, rq.knn);
+    std::vector<double> hs((size_t)n * 4);
+    std::vector<int32_t> hk((size_t)n), hi((size_t)n * slots), hj((size_t)n * slots), hd, hc;
+    std::vector<float> hz((size_t)n * slots), hr((size_t)n * slots);
+    down(ro->s_iters + q0, L.s_iters, (size_t)n * 4);
+    down(ro->s_res + q0, L.s_res, (size_t)n * 4);
+    down(hs.data(), L.r_sums, hs.size() * 8);
+    down(ro->null_total + q0, L.n_total, (size_t)n * 4);
+    down(hk.data(), L.n_kept, (size_t)n * 4);
+    if (full && slots > 0) {
+      down(hi.data(), L.n_i, hi.size() * 4);
+      down(hj.data(), L.n_j, hj.size() * 4);
+      down(hz.data(), L.n_z, hz.size() * 4);
+      down(hr.data(), L.n_r, hr.size() * 4);
+    }
+    const bool want_graph = ro->nnz || ro->edge_prefix;
+    if (want_graph) {
+      hd.resize((size_t)n * rq.K);
+      hc.resize((size_t)n * rq.K * kw);
+      down(hd.data(), L.deg, hd.size() * 4);
+      down(hc.data(), L.col, hc.size() * 4);
+    }
+    HIP_CHECK(hipStreamSynchronize(c.stream));
+    for (int32_t q = 0; q < n; ++q) {
+      for (int t = 0; t < 4; ++t) ro->sums[t][q0 + q] = hs[(size_t)q * 4 + t];
+      int64_t at0 = ro->null_offsets[q0 + q];
+      const int32_t kept = full ? std::min(std::max(hk[(size_t)q], 0), slots) : 0;
+      for (int32_t t = 0; t < kept; ++t) {
+        const size_t sidx = (size_t)q * slots + t;
+        ro->null_i[at0 + t] = hi[sidx];
+        ro->null_j[at0 + t] = hj[sidx];
+        ro->null_z[at0 + t] = hz[sidx];
+        ro->null_r[at0 + t] = hr[sidx];
+      }
+      ro->null_offsets[q0 + q + 1] = at0 + kept;
+      if (!want_graph) continue;
+      int64_t nnz = 0, np = 0;
+      const int64_t r0 = (int64_t)q * rq.K;
+      int64_t* pairs = ro->edge_prefix ? ro->edge_prefix + (size_t)(q0 + q) * ro->prefix_cap * 2 : nullptr;
+      for (int32_t i = 0; i < rq.K; ++i) {
+        const int32_t d = rq.knn > 0 ? hd[(size_t)(r0 + i)] : 0;
+        for (int32_t e = 0; e < d && pairs && np < ro->prefix_cap; ++e, ++np) {
+          pairs[np * 2] = i;
+          pairs[np * 2 + 1] = (int64_t)hc[(size_t)(r0 + i) * kw + e] - r0;
+        }
+        nnz += d;
+      }
+      if (ro->nnz) ro->nnz[q0 + q] = nnz;
+      if (ro->edge_prefix_n) ro->edge_prefix_n[q0 + q] = (int32_t)np;
     }
   });
   if (rq.gate == 2) {  // nothing was solved for given gates
@@ -1168,6 +1316,56 @@ int osc_corpus_refine_gated(osc_corpus_handle h, const float* psis, int32_t Q, i
     o.g_res = gate_res;
     refine_body(c, rq, top_k, cand_in, kneighbors, row_cap, lamG, lamC, lamQ, tol, max_iters, k, alpha, o,
                 "osc_corpus_refine_gated: NULL buffer");
+  });
+}
+
+int osc_corpus_refine_receipts(osc_corpus_handle h, const float* psis, int32_t Q, int32_t top_k, const int32_t* cand_in,
+                               int32_t gate_mode, const float* gates_in, float beta, float gamma, int32_t method,
+                               float gate_tol, int32_t gate_max_iters, int32_t kneighbors, float row_cap, float lamG,
+                               float lamC, float lamQ, float tol, int32_t max_iters, int32_t k, float alpha, float dt,
+                               int32_t settle_max_iters, float settle_tol, int32_t detail, float z_th, int32_t null_cap,
+                               int32_t* cand_out, float* gates_out, int32_t* local, float* score, float* align,
+                               int32_t* iters, float* res, int32_t* gate_iters, float* gate_res, int32_t* settle_iters,
+                               float* settle_res, double* dH, double* coh_sum, double* anchor_sum, double* query_sum,
+                               int32_t* null_total, int64_t* null_offsets, int32_t* null_i, int32_t* null_j, float* null_z,
+                               float* null_r, int64_t null_capacity, int64_t* nnz_out, int64_t* edge_prefix,
+                               int32_t* edge_prefix_n, int32_t edge_prefix_cap) {
+  return corpus_guarded(h, [&](osc_corpus& c) {
+    if (gate_mode < 0 || gate_mode > 2) throw Invalid("gate_mode must be 0 (none), 1 (diffusion) or 2 (given)");
+    if (gate_mode == 2 && !gates_in && Q > 0) throw Invalid("gate_mode 2 needs gates_in");
+    if (detail != 0 && detail != 1) throw Invalid("detail must be 0 (light) or 1 (full)");
+    if (!(dt > 0.f) || !std::isfinite(dt)) throw Invalid("dt must be finite and > 0");
+    if (settle_max_iters < 1) throw Invalid("settle_max_iters must be >= 1");
+    if (!std::isfinite(settle_tol)) throw Invalid("settle_tol must be finite");
+    if (!std::isfinite(z_th)) throw Invalid("z_th must be finite");
+    RefineReq rq{};
+    rq.psis = psis;
+    rq.Q = Q;
+    rq.gate = gate_mode;
+    if (gate_mode == 2) {
+      rq.gates_in = gates_in;
+    } else if (gate_mode == 1) {
+      check_gate_settings(beta, gamma, method, gate_max_iters);
+      rq.g_beta = beta;
+      rq.g_gamma = gamma;
+      rq.g_direct = method == 0;
+      rq.g_tol = gate_tol;
+      rq.g_max_iters = method == 0 ? 2048 : gate_max_iters;
+    }
+    rq.receipts = detail ? 2 : 1;
+    rq.s_dt = dt;
+    rq.s_max_iters = settle_max_iters;
+    rq.s_tol = settle_tol;
+    rq.z_th = z_th;
+    rq.null_cap = std::max(0, null_cap);
+    RefineOut o{cand_out, local, score, align, iters, res};
+    o.gates = gates_out;
+    o.g_iters = gate_iters;
+    o.g_res = gate_res;
+    ReceiptOut ro{settle_iters, settle_res, {dH, coh_sum, anchor_sum, query_sum}, null_total, null_offsets, null_i, null_j,
+                  null_z, null_r, null_capacity, nnz_out, edge_prefix, edge_prefix_n, edge_prefix_cap};
+    refine_body(c, rq, top_k, cand_in, kneighbors, row_cap, lamG, lamC, lamQ, tol, max_iters, k, alpha, o,
+                "osc_corpus_refine_receipts: NULL buffer", &ro);
   });
 }
 
