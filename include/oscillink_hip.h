@@ -344,7 +344,9 @@ int osc_dynamics(osc_handle h, const float* U_prev_or_null, const float* U_next_
  * gave up on overflowing hit lists and the whole-array build ran instead), *total_ms = 0.  which = 16: *launches = the main
  * sweep of the last build's thresholds-and-hits prefilter (0: another route built the lists; 1: every rank swept every column
  * tile for its row blocks; 2: the symmetric half sweep, ONE per build whatever the world size -- the ranks of a sharded build
- * split its work items), *total_ms = 0. */
+ * split its work items), *total_ms = 0.  which = 17 / 18 / 19: *launches = the whole-array Y -> U copies made for this
+ * handle since creation (none on one GPU: U aliases Y until a settle writes it), the rows -> slab-major transposes launched
+ * (k_rows_to_slab), the bytes the slab-major image of the anchors holds (0: not built; OSC_ANCHOR_SLAB=0: never), *total_ms = 0. */
 int osc_profile_enable(osc_handle h, int32_t on);
 int osc_profile_reset(osc_handle h);
 int osc_profile_get(osc_handle h, int32_t which, int64_t* launches, double* total_ms);

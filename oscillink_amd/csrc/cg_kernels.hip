@@ -826,6 +826,7 @@ __global__ __launch_bounds__(256) void k_update_xr(const UpdateArgs a) {
   const int sub = lane / LPR, lr = lane % LPR;
   const int32_t ld = a.ld;
   const bool tmp = a.temporal != 0;
+  [[maybe_unused]] const float* const xin = a.Xin != nullptr ? a.Xin : a.X;  // (UpdateArgs::Xin: iteration 1 of an anchor-start settle)
   int coff[NCH];
   bool cok[NCH];
   float4 al[NCH], rr[NCH], rz[NCH];
@@ -850,7 +851,7 @@ __global__ __launch_bounds__(256) void k_update_xr(const UpdateArgs a) {
       float4 r = ld4_sel(a.R + off, tmp);
       const float4 ap = ld4_sel(a.AP + off, tmp);
       if constexpr (WITHX) {
-        float4 x = ld4_sel(a.X + off, tmp);
+        float4 x = ld4_sel(xin + off, tmp);
         const float4 p = ld4_sel(a.P + p_off(a, row, coff[ch]), tmp);
         x.x = fmaf(p.x, al[ch].x, x.x); x.y = fmaf(p.y, al[ch].y, x.y);
         x.z = fmaf(p.z, al[ch].z, x.z); x.w = fmaf(p.w, al[ch].w, x.w);
@@ -879,6 +880,7 @@ __global__ __launch_bounds__(256) void k_update_p(const UpdateArgs a) {
   const int sub = lane / LPR, lr = lane % LPR;
   const int32_t ld = a.ld;
   const bool tmp = a.temporal != 0;
+  [[maybe_unused]] const float* const xin = a.Xin != nullptr ? a.Xin : a.X;  // (UpdateArgs::Xin)
   int coff[NCH];
   bool cok[NCH];
   float4 be[NCH], al[NCH];
@@ -902,7 +904,7 @@ __global__ __launch_bounds__(256) void k_update_p(const UpdateArgs a) {
       const size_t poff = p_off(a, row, coff[ch]);
       float4 p = ld4_sel(a.P + poff, tmp);
       if constexpr (WITHX) {
-        float4 x = ld4_sel(a.X + off, tmp);
+        float4 x = ld4_sel(xin + off, tmp);
         x.x = fmaf(p.x, al[ch].x, x.x); x.y = fmaf(p.y, al[ch].y, x.y);
         x.z = fmaf(p.z, al[ch].z, x.z); x.w = fmaf(p.w, al[ch].w, x.w);
         st4_sel(a.X + off, x, tmp);

@@ -197,6 +197,9 @@ struct UpdateArgs {
   // hand (launch_update_x behind the last iteration) -- one array pass less per iteration; OSC_XMODE_XR_LAST: k_update_xr
   // in the form for the expected last iteration (x finished there, the new r not stored)
   int32_t xmode;
+  // the x an x update READS (nullptr: X itself).  The settle that starts from the anchors without copying them: the one
+  // launch that applies iteration 1's update reads x0 from the anchors and writes x into X (run_cg)
+  const float* Xin;
 };
 constexpr int32_t OSC_XMODE_XR_SKIPS_X = 1, OSC_XMODE_P_APPLIES_X = 2, OSC_XMODE_XR_LAST = 4;
 

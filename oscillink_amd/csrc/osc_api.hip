@@ -31,6 +31,7 @@ void read_env_solver(L& h) {
     h.x_last_form = v == 1;
   }
   if (num("OSC_SMALL_PATH", v)) h.small_path = v != 0;
+  if (num("OSC_ANCHOR_SLAB", v)) h.anchor_slab = v != 0;
   if (num("OSC_RECEIPT_PAIR", v)) h.receipt_pair = v != 0;
   if (const char* e = getenv("OSC_SHARD")) h.shard_mode = !strcmp(e, "row") ? 1 : 0;
   if (num("OSC_ROW_FAKE_SHARDS", v)) h.fake_row_shards = std::max(0, v);
@@ -76,6 +77,29 @@ void read_env_build(L& h) {
 void read_env(L& h) {
   read_env_solver(h);
   read_env_build(h);
+}
+
+// U = Y without the copy where a solve owns all of U: one process, the full column window, no row shards.  A windowed
+// handle's or a rank's U keeps columns or rows its solves do not write, so those keep the eager copy (and are not what the
+// alias is for: the first settle of a fresh lattice on one GPU).
+bool u_alias_ok(const L& h) { return h.comm == nullptr && h.c0 == 0 && h.c1 == h.dcols && !row_mode(h); }
+
+void reset_u_to_y(L& h) {
+  if (u_alias_ok(h)) {
+    h.u_is_y = true;
+    return;
+  }
+  HIP_CHECK(hipMemcpyAsync(h.U.p, h.Y.p, (size_t)h.N * h.ld * 4, hipMemcpyDeviceToDevice, h.stream));
+  h.u_is_y = false;
+  h.yu_copies += 1;
+}
+
+// U's buffer takes the state it stands for (before something that needs U and Y in two arrays)
+void materialise_u(L& h) {
+  if (!h.u_is_y) return;
+  HIP_CHECK(hipMemcpyAsync(h.U.p, h.Y.p, (size_t)h.N * h.ld * 4, hipMemcpyDeviceToDevice, h.stream));
+  h.u_is_y = false;
+  h.yu_copies += 1;
 }
 
 void require_graph(L& h) {
@@ -205,7 +229,8 @@ int osc_create(const float* Y, int64_t N, int32_t D, int32_t k, float row_cap, i
     const size_t n = (size_t)N * h->ld;
     for (DevBuf<float>* b : {&h->Y, &h->U, &h->X, &h->R, &h->P, &h->AP, &h->Ustar}) b->alloc(n);
     if (h->ld != D) HIP_CHECK(hipMemsetAsync(h->Y.p, 0, n * 4, h->stream));  // (the padding columns; the anchors follow below)
-    for (DevBuf<float>* b : {&h->X, &h->R, &h->P, &h->AP, &h->Ustar}) HIP_CHECK(hipMemsetAsync(b->p, 0, n * 4, h->stream));
+    // (U too: while it aliases Y nothing initialises its padding columns, and a solve writes [c0, c1) only)
+    for (DevBuf<float>* b : {&h->U, &h->X, &h->R, &h->P, &h->AP, &h->Ustar}) HIP_CHECK(hipMemsetAsync(b->p, 0, n * 4, h->stream));
     h->B.alloc((size_t)N);
     std::vector<float> ones((size_t)N, 1.0f);
     HIP_CHECK(hipMemcpyAsync(h->B.p, ones.data(), (size_t)N * 4, hipMemcpyHostToDevice, h->stream));
@@ -217,7 +242,7 @@ int osc_create(const float* Y, int64_t N, int32_t D, int32_t k, float row_cap, i
       build_graph(*h, Y);
     } else {
       upload_rows(*h, h->Y.p, Y);
-      HIP_CHECK(hipMemcpyAsync(h->U.p, h->Y.p, n * 4, hipMemcpyDeviceToDevice, h->stream));
+      reset_u_to_y(*h);
     }
     sync(*h);
   } catch (const Unsupported& e) {
@@ -525,7 +550,7 @@ int osc_get_U(osc_handle h, float* out) {
       gather_columns(l, l.U.p);
       l.u_sharded = false;
     }
-    download_api_order(l, out, l.U.p);
+    download_api_order(l, out, u_read(l));
   });
 }
 
@@ -546,12 +571,13 @@ int osc_set_U(osc_handle h, const float* U) {
         upload_rows(l, l.U.p, U);
       }
       l.u_sharded = false;
+      l.u_is_y = false;
     } else if (l.comm && l.world > 1 && l.shard_mode == 0) {  // column-sharded: only this rank's slab is needed
       HIP_CHECK(hipMemcpy2DAsync(l.U.p + l.c0, (size_t)l.ld * 4, l.Y.p + l.c0, (size_t)l.ld * 4,
                                  (size_t)(l.c1 - l.c0) * 4, (size_t)l.N, hipMemcpyDeviceToDevice, l.stream));
       l.u_sharded = true;
     } else {
-      HIP_CHECK(hipMemcpyAsync(l.U.p, l.Y.p, (size_t)l.N * l.ld * 4, hipMemcpyDeviceToDevice, l.stream));
+      reset_u_to_y(l);  // (no copy where U may alias Y)
       l.u_sharded = false;
     }
     if (U) sync(l);  // (the caller's buffer is free on return; the device-side reset is ordered by the stream)
@@ -568,24 +594,33 @@ int osc_settle(osc_handle h, float dt, int32_t max_iters, float tol, int32_t pre
     sync(l);
     const double t0 = now_ms();
     // x0 (lattice.py:751-758)
-    const float* x0 = l.U.p;
+    // (a cold start from an aliased U: the state term U and the start Y would be one array where they are two today, which
+    // changes the form of the INIT pass -- that rare call gets its U in place first)
+    if (!warm_start) materialise_u(l);
+    const float* const u = u_read(l);
+    const float* x0 = u;
     if (!warm_start) {
       x0 = l.Y.p;
     } else {
       const float w = std::max(0.0f, std::min(1.0f, inertia));
       if (w > 0.0f) {
-        launch_axpby(l.AP.p, l.Y.p, 1.0f - w, l.U.p, w, (int64_t)l.N * l.ld, l.stream);
+        launch_axpby(l.AP.p, l.Y.p, 1.0f - w, u, w, (int64_t)l.N * l.ld, l.stream);
         x0 = l.AP.p;  // AP is free until the first operator apply overwrites it (INIT gathers x0 before that)
       }
     }
     // Warm start from U itself (the default): the CG runs in place on U -- the old state is only read by the INIT pass
     // (as x0 and as the rhs term), which then has no x0 copy to write, and there is nothing to swap afterwards.
-    const bool in_place = x0 == l.U.p && !row_mode(l);
-    CgBuffers b{x0, in_place ? l.U.p : l.X.p, l.R.p, l.P.p, l.AP.p, l.U.p, l.Y.p, l.B.p, l.psi.p, l.ld, l.c0, l.c1};
-    if (in_place) b.Xalt = l.X.p;  // free in an in-place solve
+    // From an aliased U: x0 and the state term are the anchors, the solution goes into U's (empty) buffer; the INIT pass
+    // writes no x0 copy there, iteration 1's x update reads x0 from the anchors (CgBuffers::defer_x0).
+    const bool from_anchors = l.u_is_y && x0 == u;
+    const bool in_place = (x0 == l.U.p || from_anchors) && !row_mode(l);
+    CgBuffers b{x0, in_place ? l.U.p : l.X.p, l.R.p, l.P.p, l.AP.p, u, l.Y.p, l.B.p, l.psi.p, l.ld, l.c0, l.c1};
+    if (in_place && !from_anchors) b.Xalt = l.X.p;  // free in an in-place solve
+    b.defer_x0 = from_anchors;
     // when x0 aliases AP the INIT pass reads it completely before the first SPMM_AP launch writes AP: same stream
     const CgResult r = run_cg(l, op, b, path_active(l), max_iters, tol);
     if (r.sol == l.X.p) l.U.swap(l.X);  // U <- U+ (lattice.py:206); an in-place solve left it in U already
+    l.u_is_y = false;  // (a solve that threw left the flag set: readers then still see Y, not a half-written U)
     if (l.comm && l.world > 1 && l.shard_mode == 0) {
       // the swapped-in buffer only holds this rank's columns; the others are refreshed lazily by osc_get_U.
       l.u_sharded = true;
@@ -605,7 +640,7 @@ int osc_solve_ustar(osc_handle h, float tol, int32_t max_iters, float* Ustar_out
     const OpParams op = ustar_op(l);
     sync(l);
     const double t0 = now_ms();
-    CgBuffers b{l.Y.p, l.X.p, l.R.p, l.P.p, l.AP.p, l.U.p, l.Y.p, l.B.p, l.psi.p, l.ld, l.c0, l.c1};
+    CgBuffers b{l.Y.p, l.X.p, l.R.p, l.P.p, l.AP.p, u_read(l), l.Y.p, l.B.p, l.psi.p, l.ld, l.c0, l.c1};
     b.kind = 1;
     const CgResult r = run_cg(l, op, b, path_active(l), max_iters, tol);
     l.Ustar.swap(l.X);
@@ -635,7 +670,7 @@ int osc_get_ustar(osc_handle h, float* out) {
 int osc_get_rows(osc_handle h, int32_t which, const int32_t* rows, int32_t n, float* out) {
   return guarded(h, [&](L& l) {
     if (n < 0 || (n > 0 && (!rows || !out))) throw Invalid("osc_get_rows: bad arguments");
-    const float* src = which == 0 ? l.Y.p : which == 1 ? l.U.p : which == 2 ? l.Ustar.p : nullptr;
+    const float* src = which == 0 ? l.Y.p : which == 1 ? u_read(l) : which == 2 ? l.Ustar.p : nullptr;
     if (!src) throw Invalid("osc_get_rows: which must be 0 (Y), 1 (U) or 2 (U*)");
     if (which == 2 && !l.have_ustar) throw StateError("osc_get_rows: no resident U* (call osc_solve_ustar first)");
     if (which == 1 && l.u_sharded) {  // collective in column-sharded runs, like osc_get_U
@@ -945,7 +980,7 @@ int osc_deltaH(osc_handle h, double* dH) {
     require_graph(l);
     if (!l.have_ustar) throw StateError("osc_deltaH: no resident U* (call osc_solve_ustar first)");
     if (!dH) throw Invalid("osc_deltaH: dH is NULL");
-    *dH = quad_form_of_difference(l, l.U.p, l.Ustar.p);  // diff = U - U*
+    *dH = quad_form_of_difference(l, u_read(l), l.Ustar.p);  // diff = U - U*
   });
 }
 
@@ -966,7 +1001,7 @@ int osc_dynamics_snapshot(osc_handle h) {
       l.u_sharded = false;
     }
     l.Uprev.alloc((size_t)l.N * l.ld);
-    HIP_CHECK(hipMemcpyAsync(l.Uprev.p, l.U.p, (size_t)l.N * l.ld * 4, hipMemcpyDeviceToDevice, l.stream));
+    HIP_CHECK(hipMemcpyAsync(l.Uprev.p, u_read(l), (size_t)l.N * l.ld * 4, hipMemcpyDeviceToDevice, l.stream));
     l.have_uprev = true;
   });
 }
@@ -990,7 +1025,7 @@ int osc_dynamics(osc_handle h, const float* U_prev, const float* U_next, double*
       gather_columns(l, l.U.p);
       l.u_sharded = false;
     }
-    const float* next = l.U.p;
+    const float* next = u_read(l);
     DevBuf<float> next_buf;
     if (U_next) {
       next_buf.alloc(n);
@@ -1294,12 +1329,18 @@ int osc_profile_get(osc_handle h, int32_t which, int64_t* launches, double* tota
       if (total_ms) *total_ms = 0.0;
       return;
     }
+    if (which >= 17 && which <= 19) {  // work an anchor start does without: counted, so that its absence can be asserted
+      // 17: whole-array Y -> U copies made for this handle; 18: k_rows_to_slab launches; 19: bytes the anchors' slab-major image holds
+      if (launches) *launches = which == 17 ? l.yu_copies : which == 18 ? l.slab_launches : (int64_t)(l.ys_ready ? l.Ys.n * 4 : 0);
+      if (total_ms) *total_ms = 0.0;
+      return;
+    }
     if (which == 14) {  // the kernel shape of the last blocked matvec
       if (launches) *launches = l.last_plan.shape;
       if (total_ms) *total_ms = 0.0;
       return;
     }
-    if (which < 0 || which > 4) throw Invalid("osc_profile_get: which must be 0..4 or 14..16");
+    if (which < 0 || which > 4) throw Invalid("osc_profile_get: which must be 0..4 or 14..19");
     prof_drain(l);
     if (launches) *launches = l.prof_count[which];
     if (total_ms) *total_ms = l.prof_ms[which];
@@ -1330,6 +1371,7 @@ int osc_comm_init(osc_handle h, const char id[128], int32_t rank, int32_t world)
   return guarded(h, [&](L& l) {
     if (world < 1 || rank < 0 || rank >= world) throw Invalid("osc_comm_init: bad rank/world");
     drain_comm_stream(l);
+    materialise_u(l);  // (a rank's U holds columns or rows its solves do not own: no alias under a communicator)
     l.comm.reset();
     l.rank = rank;
     l.world = world;

@@ -96,6 +96,7 @@ void install_chain(L& l) {
 void move_state(L& l, const int32_t* from_d, const int32_t* relabel_d) {
   const size_t n = (size_t)l.N * l.ld;
   for (DevBuf<float>* b : {&l.Y, &l.U}) {  // AP is scratch between solves
+    if (b == &l.U && l.u_is_y) continue;  // (U aliases Y: its buffer holds nothing to move)
     launch_move_rows(l.AP.p, b->p, from_d, l.N, l.ld, false, l.stream);
     HIP_CHECK(hipMemcpyAsync(b->p, l.AP.p, n * 4, hipMemcpyDeviceToDevice, l.stream));
   }
@@ -121,6 +122,7 @@ void move_state(L& l, const int32_t* from_d, const int32_t* relabel_d) {
   l.deg.swap(deg2);
   l.ell_t_ready = false;
   l.blk_nb = 0;
+  l.ys_ready = false;  // (the anchors' slab-major image is in the old row order)
   l.have_ustar = false;
   l.u_sharded = false;
   ++l.graph_epoch;
@@ -300,6 +302,7 @@ void stream_pieces(L& h, const float* host_Y, const std::vector<int32_t>& starts
                    DevBuf<float>& smp_n) {
   const int32_t N = (int32_t)h.N, D = h.D;
   const int pieces = (int)starts.size();
+  const bool alias_u = u_alias_ok(h);  // U = Y by alias instead of by a copy per piece (osc_api.hip: reset_u_to_y)
   if (pieces < 1 || pieces > 16) throw std::runtime_error("streamed create: 1 to 16 pieces");  // (p_queue: four counters per piece)
   auto row0 = [&](int j) { return j < pieces ? starts[(size_t)j] : N; };
   const int32_t m_s = pp.sample_tiles * 128, chunk_rows = pp.T * 128;
@@ -394,12 +397,12 @@ void stream_pieces(L& h, const float* host_Y, const std::vector<int32_t>& starts
       HIP_CHECK(hipMemcpyAsync(h.Y.p + (size_t)r0 * h.ld, host_Y + (size_t)r0 * D, (size_t)(r1 - r0) * row_bytes, hipMemcpyHostToDevice, up));
       HIP_CHECK(hipEventRecord(E(ev[(size_t)j]), up));
     };
-    // behind piece j's arrival: U's rows, unit rows, image rows
+    // behind piece j's arrival: U's rows (where U may not alias Y), unit rows, image rows
     auto queue_rows = [&](int j) {
       hipStream_t s = cs[j & 1];
       const int32_t r0 = row0(j), r1 = row0(j + 1);
       HIP_CHECK(hipStreamWaitEvent(s, E(ev[(size_t)j]), 0));
-      HIP_CHECK(hipMemcpyAsync(h.U.p + (size_t)r0 * h.ld, h.Y.p + (size_t)r0 * h.ld, (size_t)(r1 - r0) * h.ld * 4, hipMemcpyDeviceToDevice, s));
+      if (!alias_u) HIP_CHECK(hipMemcpyAsync(h.U.p + (size_t)r0 * h.ld, h.Y.p + (size_t)r0 * h.ld, (size_t)(r1 - r0) * h.ld * 4, hipMemcpyDeviceToDevice, s));
       launch_normalize_rows(h.Y.p + (size_t)r0 * h.ld, h.ld, Yn + (size_t)r0 * ldn, ldn, r1 - r0, D, s);
       launch_panel_image(Yn, ldn, p_img, pp, N, D, s, r0, j + 1 == pieces ? pp.npad : r1);
     };
@@ -480,6 +483,9 @@ void stream_pieces(L& h, const float* host_Y, const std::vector<int32_t>& starts
   }
   cleanup(false);
   h.create_pieces = pieces;
+  h.ys_ready = false;
+  h.u_is_y = alias_u;
+  if (!alias_u) h.yu_copies += 1;
 }
 
 // host_Y (osc_create only): the caller's anchors, not on the device yet -- the build brings them there, either whole before
@@ -504,7 +510,8 @@ void build_graph(L& h, const float* host_Y) {
 static void upload_anchors(L& h, const float*& host_Y) {
   if (host_Y == nullptr) return;
   upload_rows(h, h.Y.p, host_Y);
-  HIP_CHECK(hipMemcpyAsync(h.U.p, h.Y.p, (size_t)h.N * h.ld * 4, hipMemcpyDeviceToDevice, h.stream));
+  h.ys_ready = false;
+  reset_u_to_y(h);
   host_Y = nullptr;
 }
 

@@ -69,6 +69,16 @@ struct osc_lattice {
   int32_t D = 0, ld = 0;
   // state (N x ld, row-major)
   DevBuf<float> Y, U, X, R, P, AP, Ustar;
+  // U is bit-for-bit Y and U's buffer holds nothing yet (the state right after construction and after osc_set_U(NULL)):
+  // readers go through u_read(), the first settle writes U.  Cleared by osc_set_U(ptr) and at the successful end of a settle.
+  bool u_is_y = false;
+  // slab-major image of the anchors over the handle's window (the layout launch_rows_to_slab writes), built on first use
+  // by a blocked INIT pass that starts from Y and kept until Y's device copy changes (OSC_ANCHOR_SLAB=0: never built)
+  DevBuf<float> Ys;
+  bool ys_ready = false;
+  bool anchor_slab = true;
+  int64_t yu_copies = 0;     // whole-array Y -> U copies made for this handle (osc_profile_get slot 17)
+  int64_t slab_launches = 0;  // k_rows_to_slab launches (slot 18)
   bool have_ustar = false;
   DevBuf<float> Uprev;  // state before the last settle (dynamics snapshot, lattice.py:825-927); allocated on first use
   bool have_uprev = false;
@@ -260,6 +270,9 @@ struct CgBuffers {  // the arrays one solve works on (all N x ld)
   // one-launch small kernel may give up at its barrier -- writes here instead and reports it in CgResult::sol, so a
   // failed attempt never leaves the caller's state partly advanced.  nullptr: X is never aliased.
   float* Xalt = nullptr;
+  // x0 is the anchors and X holds nothing yet (the settle from an aliased U): the INIT pass of the general path writes
+  // no copy of x0 into X; the launch that applies iteration 1's x update reads x from x0 instead (run_cg)
+  bool defer_x0 = false;
   int kind = 0;  // 0 settle, 1 U*, 2 single right-hand side: repeated solves of one kind take the same iteration count
 };
 
@@ -324,6 +337,12 @@ void build_halo_plan(L& h);
 void halo_exchange(L& h, float* arr, int32_t ld);
 CgResult run_cg_rows(L& h, const OpParams& op, const CgBuffers& b, bool with_path, int max_iters, float tol);
 bool row_mode(const L& h);
+// U as readers see it: the anchors while U aliases them
+inline const float* u_read(const L& h) { return h.u_is_y ? h.Y.p : h.U.p; }
+bool u_alias_ok(const L& h);
+void reset_u_to_y(L& h);
+void materialise_u(L& h);
+void rows_to_slab(L& h, const float* src, float* dst, int32_t ld, int32_t c0, int32_t c1, int grid, const float* sub = nullptr);
 bool env_num(const char* name, int& out);
 void read_env_solver(L& h);
 void read_env_build(L& h);

@@ -98,7 +98,7 @@ void query_basis_solve(L& l, float tol, int32_t max_iters, float scale, bool fre
     q.X.alloc(n * l.ld);
     q.zero_psi.alloc((size_t)l.ld);
     HIP_CHECK(hipMemsetAsync(q.zero_psi.p, 0, (size_t)l.ld * 4, l.stream));
-    CgBuffers b{l.Y.p, q.X.p, l.R.p, l.P.p, l.AP.p, l.U.p, l.Y.p, l.B.p, q.zero_psi.p, l.ld, l.c0, l.c1};
+    CgBuffers b{l.Y.p, q.X.p, l.R.p, l.P.p, l.AP.p, u_read(l), l.Y.p, l.B.p, q.zero_psi.p, l.ld, l.c0, l.c1};
     b.kind = 1;
     const CgResult r = run_cg(l, op, b, path_active(l), max_iters, 0.5f * tol);
     if (r.sol != q.X.p) HIP_CHECK(hipMemcpyAsync(q.X.p, r.sol, n * l.ld * 4, hipMemcpyDeviceToDevice, l.stream));
@@ -369,7 +369,7 @@ void query_receipt_many(L& l, const float* psis, int32_t Q, int32_t detail, floa
   c.X = q.X.p;
   c.x4 = q.x4.p;
   c.Mx = q.Mx.p;
-  c.U = l.U.p;
+  c.U = u_read(l);
   c.psi0 = l.psi.p;
   q.U0.alloc(n * l.ld);
   c.U0 = q.U0.p;
@@ -386,7 +386,7 @@ void query_receipt_many(L& l, const float* psis, int32_t Q, int32_t detail, floa
   std::vector<double> h1((size_t)l.ld);
   HIP_CHECK(hipMemcpyAsync(h1.data(), q.rsum.p, h1.size() * 8, hipMemcpyDeviceToHost, l.stream));
   sync(l);
-  const double h0 = quad_form_of_difference(l, l.U.p, q.U0.p);
+  const double h0 = quad_form_of_difference(l, u_read(l), q.U0.p);
   const double* a1 = q.rm_vec.data();
   const double* b1 = a1 + D;
   for (int32_t t = 0; t < Q; ++t) {

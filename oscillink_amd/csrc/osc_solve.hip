@@ -226,6 +226,28 @@ bool run_cg_small(L& h, const OpParams& op, const CgBuffers& b, bool with_path, 
 CgResult run_cg_rows(L& h, const OpParams& op, const CgBuffers& b, bool with_path, int max_iters, float tol);
 bool row_mode(const L& h);
 
+// rows -> slab-major over [c0, c1) (k_rows_to_slab), counted per handle (osc_profile_get slot 18)
+void rows_to_slab(L& h, const float* src, float* dst, int32_t ld, int32_t c0, int32_t c1, int grid, const float* sub) {
+  launch_rows_to_slab(src, dst, h.N, ld, c0, c1, grid, h.stream, sub);
+  h.slab_launches += (c1 - c0 + 2047) / 2048;
+}
+
+// The slab-major operand of a blocked INIT pass that starts from x0: the anchors' image where x0 IS the anchors (built on
+// first use, the same bits for every solve that starts from Y: the first settle of a lattice, every settle after a reset,
+// the U* solve, the query basis), else x0 transposed into `scratch`.
+static const float* init_operand(L& h, const CgBuffers& b, float* scratch, int grid) {
+  if (h.anchor_slab && b.x0 == h.Y.p && b.ld == h.ld && b.c0 == h.c0 && b.c1 == h.c1) {
+    if (!h.ys_ready) {
+      h.Ys.alloc((size_t)h.N * h.ld);
+      rows_to_slab(h, h.Y.p, h.Ys.p, h.ld, h.c0, h.c1, grid);
+      h.ys_ready = true;
+    }
+    return h.Ys.p;
+  }
+  rows_to_slab(h, b.x0, scratch, b.ld, b.c0, b.c1, grid);
+  return scratch;
+}
+
 // Arguments of the source-blocked matvec (k_apply_blocked) for the handle's whole column window: X = slab-major input, OUT =
 // row-major output, column sums of X . OUT into h.part0 (grid rows, + the chain fix-up's chunks behind them).  For a plan
 // with source blocks.
@@ -284,7 +306,7 @@ int blocked_quad_form(L& h, const host::ApplyPlan& plan, const OpParams& op, con
   BlkArgs ba{};
   ChainFixArgs cf{};
   blocked_setup(h, plan, op, scratch_slab, scratch_out, h.B.p, h.ld, with_path, grid, ba, cf);
-  launch_rows_to_slab(x_rows, scratch_slab, h.N, h.ld, h.c0, h.c1, grid, h.stream, x_sub);
+  rows_to_slab(h, x_rows, scratch_slab, h.ld, h.c0, h.c1, grid, x_sub);
   ba.gate = nullptr;
   launch_apply_blocked(ba, grid, h.stream, nullptr, plan.shape);
   h.blk_applies += 1;
@@ -350,9 +372,14 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
   sa.c0 = b.c0;
   sa.c1 = b.c1;
   sa.part = h.part0.p;
+  // The settle from an aliased U (b.defer_x0: x0 = the anchors, X = U's empty buffer): no INIT form writes a copy of x0
+  // into X -- each is told that x0 IS its solution array, as in an in-place solve -- and the one launch that applies
+  // iteration 1's x update reads x from x0 and writes it to X (UpdateArgs::Xin below).
+  const float* const x1_in = b.defer_x0 && b.X != b.x0 && !overlap ? b.x0 : nullptr;
+  float* const x_init = x1_in != nullptr ? const_cast<float*>(b.x0) : b.X;  // (only compared with x0, never written, then)
   // r = b - A x0 ; z ; p ; rz
   sa.X = b.x0;
-  sa.OUT = b.X;
+  sa.OUT = x_init;
   sa.R = b.R;
   sa.P = b.P;
   sa.U = b.rhsU;
@@ -374,16 +401,17 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
   // (the rhs rows the fused pass can take besides x0 itself: one -- the state term must be x0 or absent, and if y is a
   // third array the solution array must be x0)
   const bool fuse_u = b.rhsU == b.x0 || op.rbU == 0.f;
-  const bool fuse_y = b.rhsY == b.x0 || b.X == b.x0;
+  const bool fuse_y = b.rhsY == b.x0 || x_init == b.x0;
   if (ba.nb > 0 && h.blk_init && h.blk_init_fused && fuse_u && fuse_y && b.x0 != b.AP) {
     // r = b - A x0 INSIDE the blocked matvec (the in-place warm-started settle: x0 is also the rhs state term and the
-    // solution array; the U* solve: x0 is Y, no state term): x0 -> slab-major (into P), then one launch gathers A x0 and
-    // leaves r, z (slab-major, in the AP array), x0 in the solution array and the r . z column sums
+    // solution array; the U* solve: x0 is Y, no state term): x0 slab-major (into P, or the anchors' image), then one launch
+    // gathers A x0 and leaves r, z (slab-major, in the AP array), x0 in the solution array and the r . z column sums.
     ProfScope ps(h, 4, 0);
-    launch_rows_to_slab(b.x0, b.P, h.N, b.ld, b.c0, b.c1, grid, h.stream);
+    ba.X = init_operand(h, b, b.P, grid);
+    cf.X = ba.X;
     BlkInit bi{};
     bi.Y = b.rhsY == b.x0 ? nullptr : b.rhsY;
-    bi.Xcopy = b.X == b.x0 ? nullptr : b.X;
+    bi.Xcopy = x_init == b.x0 ? nullptr : b.X;
     bi.R = b.R;
     bi.Z = b.AP;
     bi.psi = b.psi;
@@ -412,19 +440,22 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
     cf.X = Pbuf;
     cf.OUT = APbuf;
   } else if (ba.nb > 0 && h.blk_init && b.x0 != b.AP) {
-    // r = b - A x0 around the blocked matvec: x0 -> slab-major (into P), A x0 -> AP, then r, z, p = z, r . z
+    // r = b - A x0 around the blocked matvec: x0 slab-major (into P, or the anchors' image), A x0 -> AP, then r, z, p = z, r . z
     ProfScope ps(h, 4, 0);
-    launch_rows_to_slab(b.x0, b.P, h.N, b.ld, b.c0, b.c1, grid, h.stream);
+    ba.X = init_operand(h, b, b.P, grid);
+    cf.X = ba.X;
     ba.gate = nullptr;
     launch_apply_blocked(ba, grid, h.stream, nullptr, plan.shape);
     if (cf.chunks > 0) {
       cf.gate = nullptr;
       launch_chain_fix(cf, h.stream);
     }
+    ba.X = b.P;
+    cf.X = b.P;
     InitFinishArgs fa{};
     fa.AP = b.AP;
     fa.X0 = b.x0;
-    fa.X = b.X;
+    fa.X = x_init;
     fa.R = b.R;
     fa.P = b.P;
     fa.U = b.rhsU;
@@ -484,6 +515,7 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
   auto finish_x = [&](int it) {
     ua.gate = nullptr;
     ua.xmode = OSC_XMODE_XR_SKIPS_X | OSC_XMODE_P_APPLIES_X;
+    ua.Xin = it == 1 ? x1_in : nullptr;
     for_windows(ua, [&](const UpdateArgs& w) { launch_update_x(w, grid, h.stream); });
     xs.finished(it);
   };
@@ -499,6 +531,7 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
       ProfScope ps(h, 2, it);
       // p = z + beta p (solver.py:32-36), and iteration it - 1's x += alpha p (solver.py:27) with the p it replaces
       ua.xmode = form.p_applies_x ? OSC_XMODE_P_APPLIES_X : 0;
+      ua.Xin = it == 2 ? x1_in : nullptr;  // (this launch applies iteration it - 1's x update)
       for_windows(ua, [&](const UpdateArgs& w) { launch_update_p(w, grid, h.stream); });
     }
     if (ba.nb > 0) {  // Ap and column sums of p.Ap
@@ -519,6 +552,7 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
     {
       ProfScope ps(h, 1, it);
       ua.xmode = form.xr == host::CgXSchedule::XR_LAST ? OSC_XMODE_XR_LAST : form.xr == host::CgXSchedule::XR_SKIPS_X ? OSC_XMODE_XR_SKIPS_X : 0;
+      ua.Xin = it == 1 ? x1_in : nullptr;  // (the forms that carry an x update here carry iteration it's)
       for_windows(ua, [&](const UpdateArgs& w) { launch_update_xr(w, grid, h.stream); });
     }
     if (mapped) {
@@ -594,6 +628,7 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
       if (xs.restore_r(it)) {  // ... from the r this iteration computed but did not keep
         ua.gate = nullptr;
         ua.xmode = OSC_XMODE_XR_SKIPS_X;
+        ua.Xin = nullptr;
         for_windows(ua, [&](const UpdateArgs& w) { launch_update_xr(w, grid, h.stream); });
       }
       enqueue_iter(++enqueued, false);

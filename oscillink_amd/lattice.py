@@ -170,9 +170,10 @@ class OscillinkLattice:
         self._U_host = v.copy()
 
     def reset_U(self, wait: bool = True) -> None:
-        """U <- Y on the device (the state right after construction); used by benchmark loops.  The copy is ordered by
-        the handle's stream, so whatever follows sees the reset state either way; `wait=False` returns without waiting
-        for it (a timing loop that wants the reset outside its clock keeps the default)."""
+        """U <- Y on the device (the state right after construction); used by benchmark loops.  On one GPU nothing is
+        copied: U aliases Y until the next settle writes it (`build_info()["y_to_u_copies"]` counts the copies a windowed
+        or multi-rank handle still makes, ordered by the handle's stream).  Whatever follows sees the reset state either
+        way; `wait=True` still synchronises the device, `wait=False` returns at once."""
         self._call("osc_set_U", None)
         self._U_host = None
         if wait:
@@ -243,11 +244,17 @@ class OscillinkLattice:
         self._call("osc_profile_get", 15, C.byref(pieces), C.byref(unused))
         sweep = C.c_int64(0)
         self._call("osc_profile_get", 16, C.byref(sweep), C.byref(unused))
+        copies, slabs, ys = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._call("osc_profile_get", 17, C.byref(copies), C.byref(unused))
+        self._call("osc_profile_get", 18, C.byref(slabs), C.byref(unused))
+        self._call("osc_profile_get", 19, C.byref(ys), C.byref(unused))
         return {"prefilter": int(pf.value), "fallback_rows": int(fb.value), "small_solves": int(ss.value),
                 "reordered": int(ro.value), "clustering": float(cc.value), "apply_launches": int(ln.value),
                 "apply_slab_cols": int(sc.value), "apply_xs_workgroups": int(xw.value),
                 "apply_src_blocks": int(sb.value), "blocked_applies": int(ba.value), "apply_blocked_shape": int(shape.value),
-                "create_pieces": int(pieces.value), "knn_sweep": int(sweep.value)}
+                "create_pieces": int(pieces.value), "knn_sweep": int(sweep.value),
+                "y_to_u_copies": int(copies.value), "rows_to_slab_launches": int(slabs.value),
+                "anchor_slab_bytes": int(ys.value)}
 
     def halo_info(self) -> dict[str, int]:
         """Row-sharded runs (OSC_SHARD=row under a communicator): the rows of the search direction this rank receives
