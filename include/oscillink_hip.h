@@ -346,7 +346,10 @@ int osc_dynamics(osc_handle h, const float* U_prev_or_null, const float* U_next_
  * tile for its row blocks; 2: the symmetric half sweep, ONE per build whatever the world size -- the ranks of a sharded build
  * split its work items), *total_ms = 0.  which = 17 / 18 / 19: *launches = the whole-array Y -> U copies made for this
  * handle since creation (none on one GPU: U aliases Y until a settle writes it), the rows -> slab-major transposes launched
- * (k_rows_to_slab), the bytes the slab-major image of the anchors holds (0: not built; OSC_ANCHOR_SLAB=0: never), *total_ms = 0. */
+ * (k_rows_to_slab), the bytes the slab-major image of the anchors holds (0: not built; OSC_ANCHOR_SLAB=0: never), *total_ms = 0.
+ * which = 20 / 21: *launches = the bytes the anchors' cached row sums W.Y hold (as many as the image once built; 0: not built
+ * or dropped with the graph; OSC_ANCHOR_WY=0 or OSC_ANCHOR_SLAB=0: never), the INIT passes of solves from the anchors that
+ * streamed those sums instead of gathering them, *total_ms = 0. */
 int osc_profile_enable(osc_handle h, int32_t on);
 int osc_profile_reset(osc_handle h);
 int osc_profile_get(osc_handle h, int32_t which, int64_t* launches, double* total_ms);

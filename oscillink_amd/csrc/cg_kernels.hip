@@ -37,6 +37,11 @@ __device__ __forceinline__ void st4_stream(float* p, float4 v) {
   const v4f t = {v.x, v.y, v.z, v.w};
   __builtin_nontemporal_store(t, reinterpret_cast<v4f*>(p));
 }
+using v2f = __attribute__((ext_vector_type(2))) float;
+__device__ __forceinline__ void st2_stream(float* p, float a, float b) {
+  const v2f t = {a, b};
+  __builtin_nontemporal_store(t, reinterpret_cast<v2f*>(p));
+}
 // streaming load (read once per kernel)
 __device__ __forceinline__ float4 ld4_stream(const float* p) {
   const v4f t = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(p));
@@ -368,6 +373,53 @@ __device__ __forceinline__ void blk_fold(float4 dot, float (&red)[NW][32], float
   }
 }
 
+// What one workgroup of a blocked launch works on (BlkArgs' geometry): k_init_cached must hand every row to the same
+// workgroup, wave and lane as k_apply_blocked does, or its r . z partials would be other sums.  k_apply_blocked keeps the
+// same lines in its own prologue: going through this struct there moves its scalar registers about (the loop form's code
+// is to stay what three rounds of tuning left).  Change the two together.
+struct BlkWork {
+  int wgx;              // workgroup within its XCD
+  int xgroups, xgrp;    // slab groups, this XCD's: it owns the slabs xgrp, xgrp + xgroups, ...
+  int rlo, rhi;         // ... and of those the rows [rlo, rhi)
+  int W8;               // rows one "deal" of groups covers (8 per gathering wave of the XCD)
+  int slice_rows;       // rows of a destination slice
+  int nslab;            // slabs of this XCD
+};
+template <int CW>
+__device__ __forceinline__ BlkWork blk_work(const BlkArgs& a) {
+  BlkWork k;
+  const int xcd = (int)(blockIdx.x & 7);
+  k.wgx = (int)(blockIdx.x >> 3);
+  k.xgroups = a.xs_groups;
+  k.xgrp = xcd % k.xgroups;
+  const int xpart = xcd / k.xgroups, parts = 8 / k.xgroups;
+  k.rlo = (int)((int64_t)a.N * xpart / parts);
+  k.rhi = (int)((int64_t)a.N * (xpart + 1) / parts);
+  k.W8 = a.xs * CW * 8;
+  k.slice_rows = k.W8 * a.groups;
+  k.nslab = a.c1 - a.c0 > k.xgrp * 32 ? ((a.c1 - a.c0 - k.xgrp * 32 + k.xgroups * 32 - 1) / (k.xgroups * 32)) : 0;
+  return k;
+}
+
+// One float4 of the INIT pass: from x0's, the rhs anchor term's and the row sum's (acc = sum_j W_ij x0_j) values to
+// r = rhs - A x0 and z = M^-1 r (k_init_finish's expressions).  Every product and sum is spelled out in the one form the
+// compiler chose for the gathering kernel when the expressions were written infix (a x b - c x d contracts per call site):
+// the gathering and the cached INIT pass must agree to the bit.
+__device__ __forceinline__ void blk_init_row(const BlkArgs& a, const BlkInit& ii, float b, float4 x, float4 y, float4 acc,
+                                             float4 psi4, float4& r, float4& z) {
+  const float cs = fmaf(a.cs_B, b, a.cs_const);
+  const float qb = __fmul_rn(ii.rbB, b);
+  const float invMd = 1.f / (fmaf(ii.md_B, b, ii.md_const) + 1e-12f);  // (no preconditioner: md_B = 0, md_const = 1)
+  auto one = [&](float xv, float yv, float av, float pv) {
+    const float o = fmaf(cs, xv, -__fmul_rn(a.cW, av));                                  // (cs + ...) x - cW sum W x
+    const float rhs = fmaf(pv, qb, fmaf(ii.rbU, xv, __fmul_rn(ii.rbY, yv)));             // rbU x + rbY y + rbB B psi
+    return __fsub_rn(rhs, o);
+  };
+  r = make_float4(one(x.x, y.x, acc.x, psi4.x), one(x.y, y.y, acc.y, psi4.y), one(x.z, y.z, acc.z, psi4.z),
+                  one(x.w, y.w, acc.w, psi4.w));
+  z = make_float4(__fmul_rn(invMd, r.x), __fmul_rn(invMd, r.y), __fmul_rn(invMd, r.z), __fmul_rn(invMd, r.w));
+}
+
 // INIT (BlkInit): the solve's initial residual in the same launch.  X holds x0 slab-major, and where a row's sums are
 // complete the epilogue forms r = rhs - A x0 with rhs = rbU x0 + rbY y + rbB B psi (y = ii.Y's row, or x0 itself: the
 // warm-started settle, whose rhs state term IS x0, and the U* solve, which starts from Y and has no state term),
@@ -379,9 +431,13 @@ __device__ __forceinline__ void blk_fold(float4 dot, float (&red)[NW][32], float
 // miss the L2, so a round of 32 lines practically always waits for one fabric round trip: with one round in flight the
 // kernel is bound by bytes in flight / miss latency.  PD > 1 issues round g + PD - 1 before it consumes round g (the
 // slots' weights and the gathered rows of PD rounds in registers).  WPE: waves per SIMD the register budget is set for.
-template <int GM, int CW, bool INIT = false, int PD = 1, int WPE = 4>
+// WY (INIT only): the pass also stores every row's sum (acc, as it enters the epilogue's arithmetic) slab-major into ii.WY:
+// the operand of k_init_cached, which serves the later solves from the same x0 on the same graph copy.  That form takes
+// no separate rhs term (ii.Y == nullptr: y is x0), so the y rows' registers pay for the store.
+template <int GM, int CW, bool INIT = false, int PD = 1, int WPE = 4, bool WY = false>
 __global__ __launch_bounds__((CW + 1) * 64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_apply_blocked(const BlkArgs a,
                                                                                                                 const BlkInit ii) {
+  static_assert(INIT || !WY, "only the INIT pass stores the row sums");
   constexpr int SL = OSC_BLK_SLOTS, NT = (CW + 1) * 64;
   __shared__ __attribute__((aligned(16))) float red[CW + 1][32];
   // per gathering wave: the slots of each of its rows in the current block, and (other half) in the next one
@@ -394,7 +450,7 @@ __global__ __launch_bounds__((CW + 1) * 64) __attribute__((amdgpu_waves_per_eu(W
   const int32_t ld = a.ld;
   for (int c = a.c0 + threadIdx.x; c < a.c1; c += NT) a.part[(size_t)blockIdx.x * ld + c] = 0.f;
   if ((int)(blockIdx.x >> 3) >= a.xs) return;
-  const int xcd = (int)(blockIdx.x & 7), wgx = (int)(blockIdx.x >> 3);
+  const int xcd = (int)(blockIdx.x & 7), wgx = (int)(blockIdx.x >> 3);  // (blk_work's arithmetic, spelled out: see there)
   const int xgroups = a.xs_groups, xgrp = xcd % xgroups, xpart = xcd / xgroups, parts = 8 / xgroups;
   const int rlo = (int)((int64_t)a.N * xpart / parts), rhi = (int)((int64_t)a.N * (xpart + 1) / parts);
   const int nb = a.nb, ng = a.groups;
@@ -542,31 +598,33 @@ __global__ __launch_bounds__((CW + 1) * 64) __attribute__((amdgpu_waves_per_eu(W
       // also wait for the previous batch's stores to be acknowledged.
       constexpr int EC = WPE <= 2 ? 4 : INIT ? 1 : 2, NBATCH = (GM + EC - 1) / EC;  // (INIT: the y rows take the second group's registers; two groups: 72 spills)
       float4 xs[2][EC];
-      float4 ys[2][INIT ? EC : 1];
+      float4 ys[2][INIT && !WY ? EC : 1];
       int2 rr[2][EC];
       float bv[2][EC];
       float4 psi4 = f4(0.f);
       float* zbase = nullptr;
+      float* wybase = nullptr;
       const uint32_t ldb = (uint32_t)ld * 4u, cb = (uint32_t)(p.sc0 + lr * 4) * 4u;
       // (INIT: the 14 dwords of `ii` cost the kernel 22 scalar-register spills into vector lanes; reading them from the
       // kernel-argument segment here, per closing sub-phase, was tried -- 12 spills, the same 700 us at config 3)
       if constexpr (INIT) {
         if (cok) psi4 = ld4(ii.psi + p.sc0 + lr * 4);
         zbase = ii.Z + (size_t)(p.sc0 >> 5) * (size_t)a.N * 32;
+        if constexpr (WY) wybase = ii.WY + (size_t)(p.sc0 >> 5) * (size_t)a.N * 32;
       }
-      auto fetch = [&](int k, float4 (&x)[EC], float4 (&y)[INIT ? EC : 1], int2 (&r)[EC], float (&bb)[EC]) {
+      auto fetch = [&](int k, float4 (&x)[EC], float4 (&y)[INIT && !WY ? EC : 1], int2 (&r)[EC], float (&bb)[EC]) {
 #pragma unroll
         for (int i = 0; i < EC; ++i) {
           const int g = k * EC + i, row = row_first + g * w8;
           x[i] = f4(0.f);
           r[i] = make_int2(0, 0);
           bb[i] = 0.f;
-          if constexpr (INIT) y[i] = f4(0.f);
+          if constexpr (INIT && !WY) y[i] = f4(0.f);
           if (g < GM && g < ng && row < rhi && cok) {
             x[i] = ld4_at(xbase, (uint32_t)row * 128u + lr16);
             r[i] = ld2_at(a.rest, (uint32_t)row * 8u);  // edges beyond SL per block: {first, count}, ascending columns
             bb[i] = ld1_at(a.B, (uint32_t)row * 4u);
-            if constexpr (INIT) {  // (byte offsets of a row-major array fit 32 bits: launch_apply_blocked checks N * ld)
+            if constexpr (INIT && !WY) {  // (byte offsets of a row-major array fit 32 bits: launch_apply_blocked checks N * ld)
               if (ii.Y != nullptr) y[i] = ld4_stream(reinterpret_cast<const float*>(reinterpret_cast<const char*>(ii.Y) + ((uint32_t)row * ldb + cb)));
             }
           }
@@ -585,27 +643,31 @@ __global__ __launch_bounds__((CW + 1) * 64) __attribute__((amdgpu_waves_per_eu(W
             const int2 en = ld2_at(a.over, (uint32_t)(rr[k & 1][i].x + e) * 8u);
             acc[g] = fma4(__int_as_float(en.y), ld4_at(xbase, (uint32_t)en.x * 128u + lr16), acc[g]);
           }
-          const float cs = fmaf(a.cs_B, bv[k & 1][i], a.cs_const);
-          float4 o;
-          o.x = cs * xs[k & 1][i].x - a.cW * acc[g].x;
-          o.y = cs * xs[k & 1][i].y - a.cW * acc[g].y;
-          o.z = cs * xs[k & 1][i].z - a.cW * acc[g].z;
-          o.w = cs * xs[k & 1][i].w - a.cW * acc[g].w;
           if constexpr (INIT) {
-            const float4 x = xs[k & 1][i], y = ii.Y != nullptr ? ys[k & 1][i] : x;
-            const float qb = ii.rbB * bv[k & 1][i];
-            const float invMd = 1.f / (fmaf(ii.md_B, bv[k & 1][i], ii.md_const) + 1e-12f);  // (no preconditioner: md_B = 0, md_const = 1)
-            float4 r, z;  // (k_init_finish's expressions)
-            r.x = (ii.rbU * x.x + ii.rbY * y.x + qb * psi4.x) - o.x;
-            r.y = (ii.rbU * x.y + ii.rbY * y.y + qb * psi4.y) - o.y;
-            r.z = (ii.rbU * x.z + ii.rbY * y.z + qb * psi4.z) - o.z;
-            r.w = (ii.rbU * x.w + ii.rbY * y.w + qb * psi4.w) - o.w;
-            z = make_float4(r.x * invMd, r.y * invMd, r.z * invMd, r.w * invMd);
+            const float4 x = xs[k & 1][i];
+            float4 y = x;
+            if constexpr (!WY) y = ii.Y != nullptr ? ys[k & 1][i] : x;
+            if constexpr (WY) {
+              // in two halves: the sums live in register pairs, and one 16-byte store wants every group's moved into a quad first
+              // (20+ registers, spills in the widest shapes).  The second offset is opaque so that the halves are not merged again.
+              uint32_t lo = (uint32_t)row * 128u + lr16, hi = lo + 8u;
+              asm volatile("" : "+v"(hi));
+              st2_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(wybase) + lo), acc[g].x, acc[g].y);
+              st2_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(wybase) + hi), acc[g].z, acc[g].w);
+            }
+            float4 r, z;
+            blk_init_row(a, ii, bv[k & 1][i], x, y, acc[g], psi4, r, z);
             st4_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(ii.R) + ((uint32_t)row * ldb + cb)), r);
             if (ii.Xcopy != nullptr) st4_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(ii.Xcopy) + ((uint32_t)row * ldb + cb)), x);
             st4(reinterpret_cast<float*>(reinterpret_cast<char*>(zbase) + ((uint32_t)row * 128u + lr16)), z);
             dot[0] = mulacc4(r, z, dot[0]);
           } else {
+            const float cs = fmaf(a.cs_B, bv[k & 1][i], a.cs_const);
+            float4 o;
+            o.x = cs * xs[k & 1][i].x - a.cW * acc[g].x;
+            o.y = cs * xs[k & 1][i].y - a.cW * acc[g].y;
+            o.z = cs * xs[k & 1][i].z - a.cW * acc[g].z;
+            o.w = cs * xs[k & 1][i].w - a.cW * acc[g].w;
             st4_stream(a.OUT + ((size_t)(uint32_t)row * (uint32_t)ld + (uint32_t)(p.sc0 + lr * 4)), o);
             dot[0] = mulacc4(xs[k & 1][i], o, dot[0]);
           }
@@ -617,6 +679,91 @@ __global__ __launch_bounds__((CW + 1) * 64) __attribute__((amdgpu_waves_per_eu(W
       blk_fold<CW + 1>(dot[0], red, a.part, ld, p.sc0, min(a.c1, p.sc0 + 32), wave, lane);
       dot[0] = f4(0.f);
     }
+  }
+}
+
+// The INIT pass of a solve whose x0 has its row sums cached (BlkInit::WY, left by the storing form of
+// k_apply_blocked<.., INIT> for the same x0, graph copy and block count): that kernel's epilogue with acc streamed in
+// instead of gathered.  Same r, z, x0 copy and r . z partials to the bit, which takes the same arithmetic (blk_init_row),
+// the same row -> (workgroup, wave, lane) mapping (blk_work) and the same order of every lane's sum: per slab its rows
+// ascending -- the slices' groups are one arithmetic sequence of rows, slice_rows = W8 x groups, so slices and groups
+// fold into one index here -- then blk_fold over the workgroup's waves.  The last wave, the gathering kernel's list
+// wave, only takes part in the fold (with zeros, as there).  No x0 other than the rhs anchor term (ii.Y == nullptr).
+// Every stream is read once: batches of EC groups per wave (EC KB each of x0 and of the sums), the next batch requested
+// before the current one is consumed.
+__device__ __forceinline__ float4 ld4_stream_at(const float* base, uint32_t byte_off) {
+  return ld4_stream(reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off));
+}
+template <int CW>
+__global__ __launch_bounds__((CW + 1) * 64) void k_init_cached(const BlkArgs a, const BlkInit ii) {
+  constexpr int NT = (CW + 1) * 64, EC = 4;
+  __shared__ __attribute__((aligned(16))) float red[CW + 1][32];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int sub = lane >> 3, lr = lane & 7;
+  const int32_t ld = a.ld;
+  for (int c = a.c0 + threadIdx.x; c < a.c1; c += NT) a.part[(size_t)blockIdx.x * ld + c] = 0.f;
+  if ((int)(blockIdx.x >> 3) >= a.xs) return;
+  const BlkWork wk = blk_work<CW>(a);
+  const uint32_t lr16 = (uint32_t)lr * 16u, ldb = (uint32_t)ld * 4u;
+  const int ngall = a.slices * a.groups, nbatch = (ngall + EC - 1) / EC;
+  const int row_first = wk.rlo + ((wk.wgx * CW + wave) << 3) + sub;
+  for (int q = 0; q < wk.nslab; ++q) {
+    const int sc0 = a.c0 + (wk.xgrp + q * wk.xgroups) * 32;
+    float4 dot = f4(0.f);
+    if (wave < CW) {
+      const bool cok = sc0 + lr * 4 < a.c1;
+      const size_t slab = (size_t)(sc0 >> 5) * (size_t)a.N * 32;
+      const float* xbase = a.X + slab;
+      const float* wybase = ii.WY + slab;
+      float* zbase = ii.Z + slab;
+      const uint32_t cb = (uint32_t)(sc0 + lr * 4) * 4u;
+      const float4 psi4 = cok ? ld4(ii.psi + sc0 + lr * 4) : f4(0.f);
+      float4 xs[2][EC], ws[2][EC];
+      float bv[2][EC];
+      // No test around the loads: a lane without a row (past the part's rows, or a column past c1) reads the part's last row,
+      // resp. the slab's first columns, and consume() drops what it got.  With the loads in straight-line code the compiler's
+      // waits are counted ones and batch k + 1 stays in flight while batch k is consumed; under a test every wait is for all.
+      const uint32_t lrc = cok ? lr16 : 0u;
+      const int row_last = max(wk.rhi - 1, 0);
+      auto fetch = [&](int k, float4 (&x)[EC], float4 (&w)[EC], float (&bb)[EC]) {
+#pragma unroll
+        for (int i = 0; i < EC; ++i) {  // (byte offsets fit 32 bits: launch_init_cached checks as launch_apply_blocked does)
+          const uint32_t row = (uint32_t)min(row_first + (k * EC + i) * wk.W8, row_last);
+          x[i] = ld4_stream_at(xbase, row * 128u + lrc);
+          w[i] = ld4_stream_at(wybase, row * 128u + lrc);
+          bb[i] = ld1_at(a.B, row * 4u);
+        }
+      };
+      auto consume = [&](int k, const float4 (&x)[EC], const float4 (&w)[EC], const float (&bb)[EC]) {
+#pragma unroll
+        for (int i = 0; i < EC; ++i) {
+          const int g = k * EC + i, row = row_first + g * wk.W8;
+          if (g >= ngall || row >= wk.rhi || !cok) continue;
+          float4 r, z;
+          blk_init_row(a, ii, bb[i], x[i], x[i], w[i], psi4, r, z);
+          st4_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(ii.R) + ((uint32_t)row * ldb + cb)), r);
+          if (ii.Xcopy != nullptr) st4_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(ii.Xcopy) + ((uint32_t)row * ldb + cb)), x[i]);
+          st4(reinterpret_cast<float*>(reinterpret_cast<char*>(zbase) + ((uint32_t)row * 128u + lr16)), z);
+          dot = mulacc4(r, z, dot);
+        }
+      };
+      fetch(0, xs[0], ws[0], bv[0]);
+      int k = 0;
+      for (; k + 2 < nbatch; k += 2) {  // two batches per trip (the buffers keep their registers), no test around a fetch
+        fetch(k + 1, xs[1], ws[1], bv[1]);
+        consume(k, xs[0], ws[0], bv[0]);
+        fetch(k + 2, xs[0], ws[0], bv[0]);
+        consume(k + 1, xs[1], ws[1], bv[1]);
+      }
+      if (k + 1 < nbatch) {  // the last one or two batches (batch k is in xs[0])
+        fetch(k + 1, xs[1], ws[1], bv[1]);
+        consume(k, xs[0], ws[0], bv[0]);
+        consume(k + 1, xs[1], ws[1], bv[1]);
+      } else {
+        consume(k, xs[0], ws[0], bv[0]);
+      }
+    }
+    blk_fold<CW + 1>(dot, red, a.part, ld, sc0, min(a.c1, sc0 + 32), wave, lane);
   }
 }
 
@@ -1169,14 +1316,35 @@ int blocked_resident_per_cu(int variant) {
   return n;
 }
 
-void launch_apply_blocked(const BlkArgs& a, int grid, hipStream_t s, const BlkInit* init, int variant) {
+static void blocked_args_check(const BlkArgs& a, int grid, int variant) {
   if (variant < 0 || variant >= kBlkShapeCount) throw std::runtime_error("blocked apply: unknown kernel shape");
   const BlkShape& sh = kBlkShapes[variant];
   if (grid < 8 || (grid & 7) != 0 || a.xs < 1 || a.xs > grid / 8 || a.xs_groups < 1 || 8 % a.xs_groups != 0 || a.groups < 1 ||
       a.groups > sh.gm || a.slices < 1 || a.nb < 1 || a.nb > OSC_MAX_SRC_BLOCKS || !a.slots || !a.rest ||
       (int64_t)a.N * a.ld * 4 >= ((int64_t)1 << 32) || (a.c0 & 31) != 0)
     throw std::runtime_error("blocked apply: unsupported arguments");
-  if (init != nullptr) {
+}
+
+// the cached INIT pass in the geometry of kernel shape `variant` (the shape fixes the gathering waves per workgroup)
+void launch_init_cached(const BlkArgs& a, int grid, hipStream_t s, const BlkInit& init, int variant) {
+  blocked_args_check(a, grid, variant);
+  if (!init.R || !init.Z || !init.psi || !init.WY || init.Y != nullptr || init.Z == a.X || init.Z == init.WY)
+    throw std::runtime_error("cached INIT pass: bad arguments");
+#define CALL(G, W, P, E) hipLaunchKernelGGL((k_init_cached<W>), dim3(grid), dim3((W + 1) * 64), 0, s, a, init)
+  OSC_BLK_SHAPE_SWITCH(variant, CALL);
+#undef CALL
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_apply_blocked(const BlkArgs& a, int grid, hipStream_t s, const BlkInit* init, int variant, bool store_wy) {
+  blocked_args_check(a, grid, variant);
+  if (store_wy) {
+    if (init == nullptr || !init->R || !init->Z || !init->psi || !init->WY || init->Y != nullptr || init->Z == a.X || init->WY == a.X || init->WY == init->Z)
+      throw std::runtime_error("blocked apply: bad INIT arguments");
+#define CALL(G, W, P, E) hipLaunchKernelGGL((k_apply_blocked<G, W, true, P, E, true>), dim3(grid), dim3((W + 1) * 64), 0, s, a, *init)
+    OSC_BLK_SHAPE_SWITCH(variant, CALL);
+#undef CALL
+  } else if (init != nullptr) {
     if (!init->R || !init->Z || !init->psi || init->Z == a.X) throw std::runtime_error("blocked apply: bad INIT arguments");
 #define CALL(G, W, P, E) hipLaunchKernelGGL((k_apply_blocked<G, W, true, P, E>), dim3(grid), dim3((W + 1) * 64), 0, s, a, *init)
     OSC_BLK_SHAPE_SWITCH(variant, CALL);

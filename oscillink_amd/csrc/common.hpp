@@ -131,6 +131,9 @@ struct BlkInit {
   float* Z;          // z = M^-1 r out, SLAB-major like BlkArgs::X (must not be that array)
   const float* psi;  // [ld]
   float rbU, rbY, rbB, md_B, md_const;  // no preconditioner: md_B = 0, md_const = 1
+  // the row sums sum_j W_ij x0_j, slab-major like BlkArgs::X (the anchors' cached W.Y, L::WYs): written by the gathering pass
+  // in its storing form (launch_apply_blocked, store_wy), read in place of the gather by k_init_cached; nullptr otherwise
+  float* WY;
 };
 
 enum SpmmMode { SPMM_AP = 0, SPMM_INIT = 1, SPMM_DOT = 2 };
@@ -260,7 +263,11 @@ void launch_rows_to_slab(const float* src, float* dst, int64_t N, int32_t ld, in
 void launch_init_finish(const InitFinishArgs& a, int grid, hipStream_t s);
 int chain_fix_chunks(int32_t prows);
 void launch_chain_fix(const ChainFixArgs& a, hipStream_t s);
-void launch_apply_blocked(const BlkArgs& a, int grid, hipStream_t s, const BlkInit* init = nullptr, int variant = 0);
+// store_wy: the INIT pass (init != nullptr) also writes its row sums to init->WY
+void launch_apply_blocked(const BlkArgs& a, int grid, hipStream_t s, const BlkInit* init = nullptr, int variant = 0,
+                          bool store_wy = false);
+// the same INIT pass with the row sums read from init.WY instead of gathered (k_init_cached): same results to the bit
+void launch_init_cached(const BlkArgs& a, int grid, hipStream_t s, const BlkInit& init, int variant);
 int blocked_resident_per_cu(int variant);  // workgroups per CU a kernel shape (kBlkShapes) gets resident
 void launch_spmm(int mode, const SpmmArgs& a, int grid, hipStream_t s);
 void launch_update_xr(const UpdateArgs& a, int grid, hipStream_t s);

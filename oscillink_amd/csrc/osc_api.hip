@@ -32,6 +32,7 @@ void read_env_solver(L& h) {
   }
   if (num("OSC_SMALL_PATH", v)) h.small_path = v != 0;
   if (num("OSC_ANCHOR_SLAB", v)) h.anchor_slab = v != 0;
+  if (num("OSC_ANCHOR_WY", v)) h.anchor_wy = v != 0;  // (needs the anchors' image: OSC_ANCHOR_SLAB=0 switches it off too, run_cg)
   if (num("OSC_RECEIPT_PAIR", v)) h.receipt_pair = v != 0;
   if (const char* e = getenv("OSC_SHARD")) h.shard_mode = !strcmp(e, "row") ? 1 : 0;
   if (num("OSC_ROW_FAKE_SHARDS", v)) h.fake_row_shards = std::max(0, v);
@@ -642,6 +643,7 @@ int osc_solve_ustar(osc_handle h, float tol, int32_t max_iters, float* Ustar_out
     const double t0 = now_ms();
     CgBuffers b{l.Y.p, l.X.p, l.R.p, l.P.p, l.AP.p, u_read(l), l.Y.p, l.B.p, l.psi.p, l.ld, l.c0, l.c1};
     b.kind = 1;
+    b.defer_x0 = l.comm == nullptr;  // (x0 is the anchors: no copy of them into X, iteration 1's x update reads them in place)
     const CgResult r = run_cg(l, op, b, path_active(l), max_iters, tol);
     l.Ustar.swap(l.X);
     if (l.shard_mode == 0) gather_columns(l, l.Ustar.p);  // receipts read whole rows of U* (row mode: already whole)
@@ -1335,12 +1337,17 @@ int osc_profile_get(osc_handle h, int32_t which, int64_t* launches, double* tota
       if (total_ms) *total_ms = 0.0;
       return;
     }
+    if (which == 20 || which == 21) {  // 20: bytes the anchors' cached row sums W.Y hold; 21: INIT passes served from them
+      if (launches) *launches = which == 20 ? (int64_t)(l.wy_nb > 0 ? l.WYs.n * 4 : 0) : l.cached_inits;
+      if (total_ms) *total_ms = 0.0;
+      return;
+    }
     if (which == 14) {  // the kernel shape of the last blocked matvec
       if (launches) *launches = l.last_plan.shape;
       if (total_ms) *total_ms = 0.0;
       return;
     }
-    if (which < 0 || which > 4) throw Invalid("osc_profile_get: which must be 0..4 or 14..19");
+    if (which < 0 || which > 4) throw Invalid("osc_profile_get: which must be 0..4 or 14..21");
     prof_drain(l);
     if (launches) *launches = l.prof_count[which];
     if (total_ms) *total_ms = l.prof_ms[which];

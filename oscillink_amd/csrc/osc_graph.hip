@@ -19,6 +19,7 @@ void graph_counts(L& h) {
 void alloc_ell(L& h, int32_t width) {
   h.ell_t_ready = false;
   h.blk_nb = 0;
+  h.wy_nb = 0;
   ++h.graph_epoch;
   h.width = std::max<int32_t>(1, width);
   const size_t n = (size_t)h.N * h.width;
@@ -122,6 +123,7 @@ void move_state(L& l, const int32_t* from_d, const int32_t* relabel_d) {
   l.deg.swap(deg2);
   l.ell_t_ready = false;
   l.blk_nb = 0;
+  l.wy_nb = 0;
   l.ys_ready = false;  // (the anchors' slab-major image is in the old row order)
   l.have_ustar = false;
   l.u_sharded = false;
@@ -484,6 +486,7 @@ void stream_pieces(L& h, const float* host_Y, const std::vector<int32_t>& starts
   cleanup(false);
   h.create_pieces = pieces;
   h.ys_ready = false;
+  h.wy_nb = 0;
   h.u_is_y = alias_u;
   if (!alias_u) h.yu_copies += 1;
 }
@@ -511,6 +514,7 @@ static void upload_anchors(L& h, const float*& host_Y) {
   if (host_Y == nullptr) return;
   upload_rows(h, h.Y.p, host_Y);
   h.ys_ready = false;
+  h.wy_nb = 0;
   reset_u_to_y(h);
   host_Y = nullptr;
 }

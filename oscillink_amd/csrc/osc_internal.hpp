@@ -77,6 +77,15 @@ struct osc_lattice {
   DevBuf<float> Ys;
   bool ys_ready = false;
   bool anchor_slab = true;
+  // The anchors' row sums W.Y, slab-major like Ys: exactly what the gathering INIT pass of a solve that starts from Y has in
+  // hand when its rows are complete.  Written by that pass as a by-product (run_cg), then every later anchor start on this
+  // graph copy streams its INIT pass (k_init_cached) instead of gathering.  The sums depend on Y, the graph and the slot
+  // placement of the block-major copy: wy_nb is the block count they were formed with (0: none held), dropped with blk_nb
+  // and with ys_ready.  OSC_ANCHOR_WY=0 or OSC_ANCHOR_SLAB=0: never built.
+  DevBuf<float> WYs;
+  int wy_nb = 0;
+  bool anchor_wy = true;
+  int64_t cached_inits = 0;  // INIT passes served from WYs (osc_profile_get slot 21; slot 20: the bytes WYs holds)
   int64_t yu_copies = 0;     // whole-array Y -> U copies made for this handle (osc_profile_get slot 17)
   int64_t slab_launches = 0;  // k_rows_to_slab launches (slot 18)
   bool have_ustar = false;

@@ -100,6 +100,7 @@ void query_basis_solve(L& l, float tol, int32_t max_iters, float scale, bool fre
     HIP_CHECK(hipMemsetAsync(q.zero_psi.p, 0, (size_t)l.ld * 4, l.stream));
     CgBuffers b{l.Y.p, q.X.p, l.R.p, l.P.p, l.AP.p, u_read(l), l.Y.p, l.B.p, q.zero_psi.p, l.ld, l.c0, l.c1};
     b.kind = 1;
+    b.defer_x0 = true;  // (as in osc_solve_ustar: x0 is the anchors, nothing copies them into q.X first)
     const CgResult r = run_cg(l, op, b, path_active(l), max_iters, 0.5f * tol);
     if (r.sol != q.X.p) HIP_CHECK(hipMemcpyAsync(q.X.p, r.sol, n * l.ld * 4, hipMemcpyDeviceToDevice, l.stream));
     iters[0] = r.iters;

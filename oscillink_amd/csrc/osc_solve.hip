@@ -422,7 +422,23 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
     bi.md_const = op.precond ? op.md_const : 1.f;
     ba.gate = nullptr;
     ba.OUT = nullptr;
-    launch_apply_blocked(ba, grid, h.stream, &bi, plan.shape);
+    // From the anchors' resident image: their row sums W.Y are the same for every such solve on this graph copy.  The first
+    // one gathers them and leaves them behind (one more store per row), the later ones stream them (k_init_cached: the
+    // same r, z and r . z sums to the bit).
+    const bool wy_route = h.anchor_wy && h.anchor_slab && ba.X == h.Ys.p && bi.Y == nullptr;
+    if (wy_route && h.wy_nb == ba.nb) {
+      bi.WY = h.WYs.p;
+      launch_init_cached(ba, grid, h.stream, bi, plan.shape);
+      h.cached_inits += 1;
+    } else if (wy_route) {
+      h.wy_nb = 0;
+      h.WYs.alloc((size_t)h.N * h.ld);
+      bi.WY = h.WYs.p;
+      launch_apply_blocked(ba, grid, h.stream, &bi, plan.shape, true);
+      h.wy_nb = ba.nb;
+    } else {
+      launch_apply_blocked(ba, grid, h.stream, &bi, plan.shape);
+    }
     if (cf.chunks > 0) {  // the chain prior's rows: their r, z and r . z still lack the chain term
       ChainFixArgs ci = cf;
       ci.gate = nullptr;
