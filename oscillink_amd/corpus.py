@@ -26,6 +26,43 @@ RECEIPT_Z_TH = 3.0  # receipt()'s null-point threshold
 EDGE_PREFIX = 2048  # edges under the state signature (OscillinkLattice._edge_prefix)
 
 
+class _RefineOut:
+    """The result arrays of one refine_many call, zeroed, and the two forms every path hands them back in."""
+
+    def __init__(self, Q: int, K: int, kk: int, gated: bool):
+        self.gated = gated
+        self.cand = np.zeros((Q, K), dtype=np.int32)
+        self.local = np.zeros((Q, kk), dtype=np.int32)
+        self.score = np.zeros((Q, kk), dtype=np.float32)
+        self.align = np.zeros((Q, kk), dtype=np.float32)
+        self.iters = np.zeros(Q, dtype=np.int32)
+        self.res = np.zeros(Q, dtype=np.float32)
+        self.g = np.zeros((Q, K), dtype=np.float32)
+        self.g_iters = np.zeros(Q, dtype=np.int32)
+        self.g_res = np.zeros(Q, dtype=np.float32)
+
+    def pointers(self, gated: bool):
+        """The arrays in the entry points' order: the gated ones take the gates second and the gate solves' report last."""
+        p = [nat.i32(self.cand), nat.i32(self.local), nat.f32(self.score), nat.f32(self.align), nat.i32(self.iters),
+             nat.f32(self.res)]
+        return p if not gated else [p[0], nat.f32(self.g), *p[1:], nat.i32(self.g_iters), nat.f32(self.g_res)]
+
+    def ids_and_arrays(self):
+        """(ids, the `as_arrays` dict without receipts) once the native call has filled the arrays."""
+        Q, kk = self.local.shape
+        ids = np.take_along_axis(self.cand, self.local, axis=1) if kk else np.zeros((Q, 0), dtype=np.int32)
+        out = {"ids": ids, "local": self.local, "score": self.score, "align": self.align, "candidates": self.cand,
+               "ustar_iters": self.iters, "ustar_res": self.res}
+        if self.gated:
+            out.update(gates=self.g, gate_iters=self.g_iters, gate_res=self.g_res)
+        return ids, out
+
+    def bundles(self, ids):
+        """Per query the list of {"id", "score", "align"} that bundle() returns."""
+        return [[{"id": int(i), "score": float(s), "align": float(a)} for i, s, a in
+                 zip(ids[q].tolist(), self.score[q].tolist(), self.align[q].tolist())] for q in range(ids.shape[0])]
+
+
 class Corpus:
     """A corpus Y (N x D, finite) resident on the device as Y and its row-normalised copy Yn (osc_create's arithmetic),
     both at a row pitch of D rounded up to 32 floats: 8 N ceil32(D) bytes, no lattice solver arrays.  Per call, queries
@@ -251,58 +288,41 @@ class Corpus:
                 raise ValueError("gates must be finite")
             if np.any(gates_in < 0):
                 raise ValueError("gates must be >= 0")
-        cand = np.zeros((Q, K), dtype=np.int32)
-        local = np.zeros((Q, kk), dtype=np.int32)
-        score = np.zeros((Q, kk), dtype=np.float32)
-        align = np.zeros((Q, kk), dtype=np.float32)
-        iters = np.zeros(Q, dtype=np.int32)
-        res = np.zeros(Q, dtype=np.float32)
         gated = gates is not None
-        g = np.zeros((Q, K), dtype=np.float32)
-        g_iters = np.zeros(Q, dtype=np.int32)
-        g_res = np.zeros(Q, dtype=np.float32)
+        o = _RefineOut(Q, K, kk, gated)
+        cand_arg = None if cand_in is None else nat.i32(cand_in)
+        gates_arg = None if gates_in is None else nat.f32(gates_in)
+        beta, gamma, method, g_max = gate_set if gate_set is not None else (1.0, 0.1, 0, 1)
+        gate_args = (beta, gamma, method, float(gate_tol), g_max)
+        solve_args = (int(kneighbors), float(row_cap_val), float(lamG), float(lamC), float(lamQ), USTAR_TOL,
+                      USTAR_MAX_ITERS, kk, float(alpha))
         if detail is not None:
-            return self._refine_receipts(P, K, knn, kk, cand_in, gates, gates_in, gate_set, (detail, s_dt, s_max, s_tol),
-                                         (top_k, kneighbors, row_cap_val, lamG, lamC, lamQ, deterministic_k, alpha, gate_tol),
-                                         (cand, local, score, align, iters, res, g, g_iters, g_res), as_arrays)
+            return self._refine_receipts(P, o, top_k=top_k, knn=knn, cand_arg=cand_arg,
+                                         mode=0 if not gated else (2 if gates_in is not None else 1), gates_arg=gates_arg,
+                                         gate_args=gate_args, solve_args=solve_args, detail=detail,
+                                         settle_args=(s_dt, s_max, s_tol), lam=[lamG, lamC, lamQ, 0.0],
+                                         deterministic_k=deterministic_k, as_arrays=as_arrays)
         if Q and not gated:
-            self._call("osc_corpus_refine", nat.f32(P), Q, int(top_k), None if cand_in is None else nat.i32(cand_in),
-                       int(kneighbors), float(row_cap_val), float(lamG), float(lamC), float(lamQ), USTAR_TOL,
-                       USTAR_MAX_ITERS, kk, float(alpha), nat.i32(cand), nat.i32(local), nat.f32(score), nat.f32(align),
-                       nat.i32(iters), nat.f32(res))
+            self._call("osc_corpus_refine", nat.f32(P), Q, int(top_k), cand_arg, *solve_args, *o.pointers(False))
         elif Q:
-            beta, gamma, method, g_max = gate_set if gate_set is not None else (1.0, 0.1, 0, 1)
-            self._call("osc_corpus_refine_gated", nat.f32(P), Q, int(top_k),
-                       None if cand_in is None else nat.i32(cand_in), None if gates_in is None else nat.f32(gates_in),
-                       beta, gamma, method, float(gate_tol), g_max, int(kneighbors), float(row_cap_val), float(lamG),
-                       float(lamC), float(lamQ), USTAR_TOL, USTAR_MAX_ITERS, kk, float(alpha), nat.i32(cand), nat.f32(g),
-                       nat.i32(local), nat.f32(score), nat.f32(align), nat.i32(iters), nat.f32(res), nat.i32(g_iters),
-                       nat.f32(g_res))
+            self._call("osc_corpus_refine_gated", nat.f32(P), Q, int(top_k), cand_arg, gates_arg, *gate_args, *solve_args,
+                       *o.pointers(True))
             if gates_in is None:
-                self._warn_non_finite(g, g_iters, g_res, "refine_many")
-        ids = np.take_along_axis(cand, local, axis=1) if kk else np.zeros((Q, 0), dtype=np.int32)
-        if as_arrays:
-            out = {"ids": ids, "local": local, "score": score, "align": align, "candidates": cand,
-                   "ustar_iters": iters, "ustar_res": res}
-            if gated:
-                out.update(gates=g, gate_iters=g_iters, gate_res=g_res)
-            return out
-        return [[{"id": int(i), "score": float(s), "align": float(a)} for i, s, a in
-                 zip(ids[q].tolist(), score[q].tolist(), align[q].tolist())] for q in range(Q)]
+                self._warn_non_finite(o.g, o.g_iters, o.g_res, "refine_many")
+        ids, arrays = o.ids_and_arrays()
+        return arrays if as_arrays else o.bundles(ids)
 
-    def _refine_receipts(self, P, K, knn, kk, cand_in, gates, gates_in, gate_set, settle, settings, outputs, as_arrays):
+    def _refine_receipts(self, P, o, *, top_k, knn, cand_arg, mode, gates_arg, gate_args, solve_args, detail,
+                         settle_args, lam, deterministic_k, as_arrays):
         """refine_many with receipts, behind its validation: one osc_corpus_refine_receipts call, then the arrays or the
-        loop's dicts.  settle = (detail code, dt, max_iters, tol); settings = refine_many's lattice arguments; outputs =
-        the result arrays it has allocated."""
+        loop's dicts.  o = the result arrays; mode = the entry point's gate_mode; gate_args, solve_args and settle_args
+        (dt, max_iters, tol) = its argument runs of those names; lam = the state signature's lambdas, as given."""
         from .lattice import OscillinkLattice, __version__
 
-        detail, s_dt, s_max, s_tol = settle
-        top_k, kneighbors, row_cap_val, lamG, lamC, lamQ, deterministic_k, alpha, gate_tol = settings
-        cand, local, score, align, iters, res, g, g_iters, g_res = outputs
-        Q = P.shape[0]
+        Q, K = o.cand.shape
         full = detail == 1
-        gated = gates is not None
-        mode = 0 if not gated else (2 if gates_in is not None else 1)
+        gated = o.gated
+        iters, res, g, g_iters, g_res = o.iters, o.res, o.g, o.g_iters, o.g_res
         try:
             cap_val = int(os.getenv("OSCILLINK_RECEIPT_NULL_CAP", "0").strip())
         except ValueError:
@@ -324,13 +344,9 @@ class Corpus:
         pairs = np.zeros((Q if dicts else 0, EDGE_PREFIX, 2), dtype=np.int64)
         pairs_n = np.zeros(Q, dtype=np.int32)
         if Q:
-            beta, gamma, method, g_max = gate_set if gate_set is not None else (1.0, 0.1, 0, 1)
-            self._call("osc_corpus_refine_receipts", nat.f32(P), Q, int(top_k),
-                       None if cand_in is None else nat.i32(cand_in), mode, None if gates_in is None else nat.f32(gates_in),
-                       beta, gamma, method, float(gate_tol), g_max, int(kneighbors), float(row_cap_val), float(lamG),
-                       float(lamC), float(lamQ), USTAR_TOL, USTAR_MAX_ITERS, kk, float(alpha), s_dt, s_max, s_tol, detail,
-                       RECEIPT_Z_TH, cap_val, nat.i32(cand), nat.f32(g), nat.i32(local), nat.f32(score), nat.f32(align),
-                       nat.i32(iters), nat.f32(res), nat.i32(g_iters), nat.f32(g_res), nat.i32(s_iters), nat.f32(s_res),
+            self._call("osc_corpus_refine_receipts", nat.f32(P), Q, int(top_k), cand_arg, mode, gates_arg, *gate_args,
+                       *solve_args, *settle_args, detail, RECEIPT_Z_TH, cap_val, *o.pointers(True), nat.i32(s_iters),
+                       nat.f32(s_res),
                        *[sums[t].ctypes.data_as(nat.c_f64p) for t in range(4)], nat.i32(total), nat.i64(offsets),
                        nat.i32(ni), nat.i32(nj), nat.f32(nz), nat.f32(nr), int(capacity),
                        nat.i64(nnz) if dicts else None, nat.i64(pairs) if dicts else None,
@@ -340,12 +356,8 @@ class Corpus:
         # the float32 rounding receipt() gives its energies (a float32 dH / np.sum over float32 rows)
         sums = sums.astype(np.float32).astype(np.float64)
         kept = int(offsets[-1])
-        ids = np.take_along_axis(cand, local, axis=1) if kk else np.zeros((Q, 0), dtype=np.int32)
+        ids, out = o.ids_and_arrays()
         if as_arrays:
-            out = {"ids": ids, "local": local, "score": score, "align": align, "candidates": cand,
-                   "ustar_iters": iters, "ustar_res": res}
-            if gated:
-                out.update(gates=g, gate_iters=g_iters, gate_res=g_res)
             out.update(settle_iters=s_iters, settle_res=s_res, deltaH=sums[0], coh_drop_sum=sums[1],
                        anchor_pen_sum=sums[2], query_term_sum=sums[3])
             if full:
@@ -354,12 +366,13 @@ class Corpus:
             return out
         detail_name = "full" if full else "light"
         ones = np.ones(K, dtype=np.float32)
+        bundles = o.bundles(ids)
         out = []
         for q in range(Q):
             B = g[q] if gated else ones
             adj_sig = hashlib.sha256(np.ascontiguousarray(pairs[q, :int(pairs_n[q])]).tobytes()).hexdigest()
             sig = OscillinkLattice._signature_digest(
-                {"psi": np.round(P[q], 6).tolist(), "lam": [lamG, lamC, lamQ, 0.0], "chain_present": False, "chain_len": 0,
+                {"psi": np.round(P[q], 6).tolist(), "lam": lam, "chain_present": False, "chain_len": 0,
                  "k": knn, "detk": bool(deterministic_k), "adj": adj_sig}, B)
             if full:
                 s, e = int(offsets[q]), int(offsets[q + 1])
@@ -403,9 +416,7 @@ class Corpus:
                 "null_points": nulls,
                 "meta": meta,
             }
-            bundle = [{"id": int(i), "score": float(sc), "align": float(a)} for i, sc, a in
-                      zip(ids[q].tolist(), score[q].tolist(), align[q].tolist())]
-            out.append({"bundle": bundle, "settle": {"iters": int(s_iters[q]), "res": float(s_res[q])}, "receipt": rec})
+            out.append({"bundle": bundles[q], "settle": {"iters": int(s_iters[q]), "res": float(s_res[q])}, "receipt": rec})
         return out
 
     def diffusion_gates_many(self, psis, top_k: int, *, kneighbors: int = 6, row_cap_val: float = 1.0, beta: float = 1.0,

@@ -11,15 +11,16 @@
 //                  single-right-hand-side Jacobi-PCG of (L_sym + gamma I) h = s per workgroup, min-max to [0, 1]
 //   k_cq_solve   : Jacobi-PCG for U*, one workgroup per lattice, a thread per column (the columns are independent
 //                  recurrences; only the stop test max_c |r_c| <= tol couples them, inside the workgroup); its GATED
-//                  instance reads B per row, the other one has B = 1 folded in
+//                  instance reads B per row, the other one has B = 1 folded in.  The iteration is cq_pcg (corpus_pcg.hpp)
 //   k_cq_bundle  : coherence drop, alignment, fp64 z-score and MMR over S, one workgroup per lattice
 //   (corpus_receipt_kernels.hip)
-//   k_cq_settle  : (receipts only) settle() of the fresh lattice: one implicit-Euler step from U = Y by Jacobi-PCG, one
+//   k_cq_settle  : (receipts only) settle() of the fresh lattice: one implicit-Euler step from U = Y by the same cq_pcg, one
 //                  workgroup per lattice; its state takes the gathered Yn block, which nothing reads after the bundle
 //   k_cq_receipt : (receipts only) deltaH of the settled state against U*, and in full detail the three component sums and
 //                  the null points (cap applied in the workgroup), one workgroup per lattice
 //
-// No workgroup waits on another: every kernel's workgroups are independent.
+// No workgroup waits on another: every kernel's workgroups are independent.  Every per-lattice kernel's arguments begin with
+// the same CqLattice block (corpus_pcg.hpp), which run_chunk fills once.
 #include "osc_internal.hpp"
 #include "knn.hpp"
 #include "corpus_plan.hpp"
@@ -50,17 +51,6 @@ namespace {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 constexpr int kTM = 128, kTQ = 128, kTK = 32, kTS = kTK + 4;
-
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_sum_d2(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // qnorm[q] = |psi_q| + 1e-12 (psi: nq rows of ldn, pad columns zero)
 __global__ __launch_bounds__(256) void k_cq_prep(const float* psi, int32_t ldn, int32_t nq, float* qnorm) {
@@ -261,182 +251,64 @@ __global__ __launch_bounds__(256) void k_cq_gather(const float* Y, const float* 
   }
 }
 
-struct SolveArgs {
-  const float* Y;     // union rows x ldn
-  const float* psi;   // nq x ldn
-  const int32_t* col;  // union ELL (width k, union row ids)
-  const float* w;
-  const int32_t* deg;
-  float* X;
-  float* R;
-  float* P;
-  float* AP;
-  int32_t* iters;
-  float* res;
-  int32_t K, k, ldn, max_iters;
-  float lamG, lamC, lamQ, tol;
-  const float* B;     // union rows: the gates (GATED instances only; last, so the ungated instances' arguments stay put)
+// the U* operator as cq_pcg's operator, B = 1 folded in: one constant, one inverse diagonal and lamQ for every row
+struct CqSolveOp {
+  float cs_, inv_, cW, lamG, lamQ;
+  static constexpr bool kFromY = false;
+  __device__ __forceinline__ float cs(int64_t) const { return cs_; }
+  __device__ __forceinline__ float inv_diag(int64_t) const { return inv_; }
+  __device__ __forceinline__ float qb(int64_t) const { return lamQ; }
+  __device__ __forceinline__ float rhs(float y, float qbi, float p) const { return lamG * y + qbi * p; }
+};
+
+// the same with gates: the rows' operator constants and inverse Jacobi diagonals formed once in LDS (every thread walks all
+// rows in every pass; a reciprocal per row and pass is on its critical path), lamQ B_i from global memory
+struct CqGatedSolveOp {
+  const float* s_cs;
+  const float* s_inv;
+  const float* B;
+  int64_t r0;
+  float cW, lamG, lamQ;
+  static constexpr bool kFromY = false;
+  __device__ __forceinline__ float cs(int64_t i) const { return s_cs[i - r0]; }
+  __device__ __forceinline__ float inv_diag(int64_t i) const { return s_inv[i - r0]; }
+  __device__ __forceinline__ float qb(int64_t i) const { return lamQ * B[i]; }
+  __device__ __forceinline__ float rhs(float y, float qbi, float p) const { return lamG * y + qbi * p; }
 };
 
 // Jacobi-PCG for M U* = lamG Y + lamQ 1 psi^T from x0 = Y (the U* operator of osc_solve_ustar with B = 1, no chain):
-// M v = (lamG + lamC + lamQ) v - lamC W v, Jacobi diagonal lamG + lamQ.  One workgroup per lattice; thread t owns the
-// columns t + 256 m and runs their recurrences over the lattice's rows in row order (fp64 column sums), so only the stop
-// test crosses threads.  Same iteration structure as k_settle_small: stop test after the x / r update, before beta.
-// GATED: B_i comes from a.B (set_query(psi, gates=B), lattice.py:245-263): row i has the operator constant
+// M v = (lamG + lamC + lamQ) v - lamC W v, Jacobi diagonal lamG + lamQ.  One workgroup per lattice; the iteration is
+// cq_pcg (corpus_pcg.hpp), which k_cq_settle runs too.
+// GATED: B_i comes from the lattice block (set_query(psi, gates=B), lattice.py:245-263): row i has the operator constant
 // lamG + lamC + lamQ B_i, the Jacobi diagonal lamG + lamQ B_i and the right-hand side lamG Y_i + (lamQ B_i) psi, each formed
 // so that B_i = 1.0f gives the ungated instance's arithmetic operation for operation.
 template <int NC, bool GATED>
-__global__ __launch_bounds__(256) void k_cq_solve(const SolveArgs a) {
+__global__ __launch_bounds__(256) void k_cq_solve(const CqPcgArgs a) {
   __shared__ float red[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int lat = blockIdx.x;
-  const int64_t r0 = (int64_t)lat * a.K, r1 = r0 + a.K;
-  const float* psi = a.psi + (size_t)lat * a.ldn;
-  const float cs = fmaf(a.lamQ, 1.0f, a.lamG + a.lamC);
-  const float invMd = 1.f / (fmaf(a.lamQ, 1.0f, a.lamG) + 1e-12f);
-  const float cW = a.lamC, qb = a.lamQ;
-  const float* g_cs = nullptr;   // GATED: the rows' operator constants and inverse Jacobi diagonals, formed once in LDS (every
-  const float* g_inv = nullptr;  // thread walks all rows in every pass; a reciprocal per row and pass is on its critical path)
+  const CqLattice& g = a.lat;
   if constexpr (GATED) {
     __shared__ float s_cs[host::kCorpusMaxTopK], s_inv[host::kCorpusMaxTopK];
-    for (int r = tid; r < a.K; r += 256) {
-      const float Bi = a.B[r0 + r];
-      s_cs[r] = fmaf(a.lamQ, Bi, a.lamG + a.lamC);
-      s_inv[r] = 1.f / (fmaf(a.lamQ, Bi, a.lamG) + 1e-12f);
+    const int tid = threadIdx.x, lat = blockIdx.x;
+    const int64_t r0 = (int64_t)lat * g.K;
+    for (int r = tid; r < g.K; r += 256) {
+      const float Bi = g.B[r0 + r];
+      s_cs[r] = fmaf(g.lamQ, Bi, g.lamG + g.lamC);
+      s_inv[r] = 1.f / (fmaf(g.lamQ, Bi, g.lamG) + 1e-12f);
     }
     __syncthreads();
-    g_cs = s_cs;
-    g_inv = s_inv;
-  }
-  auto row_cs = [&](int64_t i) { return GATED ? g_cs[i - r0] : cs; };
-  auto row_invMd = [&](int64_t i) { return GATED ? g_inv[i - r0] : invMd; };
-  auto row_qb = [&](int64_t i) { return GATED ? a.lamQ * a.B[i] : qb; };
-  int cidx[NC];
-  bool on[NC];
-#pragma unroll
-  for (int m = 0; m < NC; ++m) {
-    cidx[m] = tid + 256 * m;
-    on[m] = cidx[m] < a.ldn;
-    if (!on[m]) cidx[m] = 0;
-  }
-  auto apply = [&](const float* v, int64_t i, float (&out)[NC]) {
-    float acc[NC];
-#pragma unroll
-    for (int m = 0; m < NC; ++m) acc[m] = 0.f;
-    const int d = a.deg[i];
-    for (int e = 0; e < d; ++e) {
-      const int64_t j = a.col[i * a.k + e];
-      const float wij = a.w[i * a.k + e];
-#pragma unroll
-      for (int m = 0; m < NC; ++m) acc[m] = fmaf(wij, v[j * a.ldn + cidx[m]], acc[m]);
-    }
-    const float csi = row_cs(i);
-#pragma unroll
-    for (int m = 0; m < NC; ++m) out[m] = csi * v[i * a.ldn + cidx[m]] - cW * acc[m];
-  };
-  double rz[NC], t1[NC], t2[NC];
-#pragma unroll
-  for (int m = 0; m < NC; ++m) rz[m] = 0.0;
-  for (int64_t i = r0; i < r1; ++i) {  // r = b - M x0, p = z = r / diag
-    float o[NC];
-    apply(a.X, i, o);
-    const float qbi = row_qb(i), invMdi = row_invMd(i);
-#pragma unroll
-    for (int m = 0; m < NC; ++m) {
-      if (!on[m]) continue;
-      const size_t off = (size_t)i * a.ldn + cidx[m];
-      const float rr = (a.lamG * a.Y[off] + qbi * psi[cidx[m]]) - o[m];
-      const float z = rr * invMdi;
-      a.R[off] = rr;
-      a.P[off] = z;
-      rz[m] += (double)rr * (double)z;
-    }
-  }
-  int it = 1;
-  float resv = 0.f;
-  for (; it <= a.max_iters; ++it) {
-#pragma unroll
-    for (int m = 0; m < NC; ++m) t1[m] = 0.0;
-    for (int64_t i = r0; i < r1; ++i) {
-      float o[NC];
-      apply(a.P, i, o);
-#pragma unroll
-      for (int m = 0; m < NC; ++m) {
-        if (!on[m]) continue;
-        const size_t off = (size_t)i * a.ldn + cidx[m];
-        a.AP[off] = o[m];
-        t1[m] += (double)a.P[off] * (double)o[m];
-      }
-    }
-    float alpha[NC];
-#pragma unroll
-    for (int m = 0; m < NC; ++m) {
-      alpha[m] = (float)(rz[m] / (t1[m] + 1e-18));  // solver.py:25-26
-      t1[m] = t2[m] = 0.0;
-    }
-    for (int64_t i = r0; i < r1; ++i) {
-      const float invMdi = row_invMd(i);
-#pragma unroll
-      for (int m = 0; m < NC; ++m) {
-        if (!on[m]) continue;
-        const size_t off = (size_t)i * a.ldn + cidx[m];
-        a.X[off] = fmaf(a.P[off], alpha[m], a.X[off]);
-        const float rr = fmaf(-a.AP[off], alpha[m], a.R[off]);
-        a.R[off] = rr;
-        t1[m] += (double)rr * (double)rr;
-        t2[m] += (double)rr * (double)(rr * invMdi);
-      }
-    }
-    float mx = 0.f;
-#pragma unroll
-    for (int m = 0; m < NC; ++m) {  // NaN propagates (solver.py:29 reports NaN for a diverged column)
-      const float v = on[m] ? (float)sqrt(t1[m]) : 0.f;
-      mx = (v != v || mx != mx) ? __uint_as_float(0x7FC00000u) : fmaxf(mx, v);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float v = __shfl_xor(mx, o, 64);
-      mx = (v != v || mx != mx) ? __uint_as_float(0x7FC00000u) : fmaxf(mx, v);
-    }
-    if (lane == 0) red[wave] = mx;
-    __syncthreads();
-    resv = red[0];
-#pragma unroll
-    for (int u = 1; u < 4; ++u) resv = (red[u] != red[u] || resv != resv) ? __uint_as_float(0x7FC00000u) : fmaxf(resv, red[u]);
-    __syncthreads();
-    if (resv <= a.tol) break;  // solver.py:30-31, before the beta / p update
-    if (it == a.max_iters) break;
-    for (int64_t i = r0; i < r1; ++i) {
-      const float invMdi = row_invMd(i);
-#pragma unroll
-      for (int m = 0; m < NC; ++m) {
-        if (!on[m]) continue;
-        const size_t off = (size_t)i * a.ldn + cidx[m];
-        const float beta = (float)(t2[m] / (rz[m] + 1e-18));  // solver.py:33-34
-        a.P[off] = fmaf(a.P[off], beta, a.R[off] * invMdi);
-      }
-    }
-#pragma unroll
-    for (int m = 0; m < NC; ++m) rz[m] = t2[m];
-  }
-  if (tid == 0) {
-    a.iters[lat] = it > a.max_iters ? a.max_iters : it;
-    a.res[lat] = resv;
+    cq_pcg<NC>(a, CqGatedSolveOp{s_cs, s_inv, g.B, r0, g.lamC, g.lamG, g.lamQ}, red);
+  } else {
+    const float cs = fmaf(g.lamQ, 1.0f, g.lamG + g.lamC);
+    const float invMd = 1.f / (fmaf(g.lamQ, 1.0f, g.lamG) + 1e-12f);
+    cq_pcg<NC>(a, CqSolveOp{cs, invMd, g.lamC, g.lamG, g.lamQ}, red);
   }
 }
 
 struct BundleArgs {
-  const float* Y;       // union rows x ldn
+  CqLattice lat;
   const float* U;       // U* (union rows x ldn)
-  const float* psi;     // nq x ldn
-  const float* qnorm;   // nq
-  const int32_t* col;
-  const float* adj;     // capped adjacency
-  const int32_t* deg;
-  const float* sd;
   const float* Sm;      // per lattice K x lds similarity matrix
-  int32_t K, k, ldn, lds, kk;
-  float lamC;
+  int32_t lds, kk;
   double alpha, lambda;
   int32_t* o_local;
   float* o_score;
@@ -459,34 +331,35 @@ __global__ __launch_bounds__(256) void k_cq_bundle(const BundleArgs a) {
   __shared__ double s_bv[4];
   __shared__ int s_bi[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int lat = blockIdx.x, K = a.K;
+  const CqLattice& g = a.lat;
+  const int lat = blockIdx.x, K = g.K;
   const int64_t r0 = (int64_t)lat * K;
-  const float* psi = a.psi + (size_t)lat * a.ldn;
-  const float qinv = 1.0f / a.qnorm[lat];
-  for (int c = tid; c < a.ldn; c += 256) qn[c] = psi[c] * qinv;
+  const float* psi = g.psi + (size_t)lat * g.ldn;
+  const float qinv = 1.0f / g.qnorm[lat];
+  for (int c = tid; c < g.ldn; c += 256) qn[c] = psi[c] * qinv;
   __syncthreads();
   for (int r = wave; r < K; r += 4) {
     const int64_t i = r0 + r;
-    const float* ui = a.U + (size_t)i * a.ldn;
-    const float* yi = a.Y + (size_t)i * a.ldn;
+    const float* ui = a.U + (size_t)i * g.ldn;
+    const float* yi = g.Y + (size_t)i * g.ldn;
     float s = 0.f, n2 = 0.f;
-    for (int c = lane; c < a.ldn; c += 64) {
+    for (int c = lane; c < g.ldn; c += 64) {
       s = fmaf(ui[c], qn[c], s);
       n2 = fmaf(ui[c], ui[c], n2);
     }
     s = wave_sum_f(s);
     n2 = wave_sum_f(n2);
-    const float inv_i = 1.0f / (a.sd[i] + 1e-12f);
+    const float inv_i = 1.0f / (g.sd[i] + 1e-12f);
     float coh = 0.f;
-    const int d = a.deg[i];
+    const int d = g.deg[i];
     for (int e = 0; e < d; ++e) {
-      const int64_t j = a.col[i * a.k + e];
-      const float wij = a.adj[i * a.k + e];
-      const float inv_j = 1.0f / (a.sd[j] + 1e-12f);
-      const float* uj = a.U + (size_t)j * a.ldn;
-      const float* yj = a.Y + (size_t)j * a.ldn;
+      const int64_t j = g.col[i * g.k + e];
+      const float wij = g.adj[i * g.k + e];
+      const float inv_j = 1.0f / (g.sd[j] + 1e-12f);
+      const float* uj = a.U + (size_t)j * g.ldn;
+      const float* yj = g.Y + (size_t)j * g.ldn;
       float dy = 0.f, du = 0.f;
-      for (int c = lane; c < a.ldn; c += 64) {
+      for (int c = lane; c < g.ldn; c += 64) {
         const float y = yi[c] * inv_i - yj[c] * inv_j;
         const float u = ui[c] * inv_i - uj[c] * inv_j;
         dy = fmaf(y, y, dy);
@@ -494,7 +367,7 @@ __global__ __launch_bounds__(256) void k_cq_bundle(const BundleArgs a) {
       }
       dy = wave_sum_f(dy);
       du = wave_sum_f(du);
-      if (wij > 0.f) coh += 0.5f * a.lamC * wij * (dy - du);
+      if (wij > 0.f) coh += 0.5f * g.lamC * wij * (dy - du);
     }
     if (lane == 0) {
       s_coh[r] = coh;
@@ -504,7 +377,7 @@ __global__ __launch_bounds__(256) void k_cq_bundle(const BundleArgs a) {
   __syncthreads();
   // fp64 mean and (population) std of coh, fixed reduction order
   auto block_sum = [&](double v) {
-    v = wave_sum_d2(v);
+    v = wave_sum_d(v);
     if (lane == 0) s_red[wave] = v;
     __syncthreads();
     const double t = ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
@@ -582,16 +455,12 @@ __global__ __launch_bounds__(256) void k_cq_bundle(const BundleArgs a) {
 }
 
 struct GateArgs {
+  CqLattice lat;
   const float* Yn;      // union rows x ldn, row-normalised
-  const float* psi;     // nq x ldn
-  const float* qnorm;   // nq
-  const int32_t* col;   // union ELL (width k, union row ids)
-  const float* w;       // normalised weights
-  const int32_t* deg;
   float* gates;         // union rows
   int32_t* iters;       // nq
   float* res;           // nq
-  int32_t K, k, ldn, max_iters, direct, clamp;
+  int32_t max_iters, direct, clamp;
   float beta, gamma, tol;
 };
 
@@ -611,23 +480,24 @@ __global__ __launch_bounds__(256) void k_cq_gates(const GateArgs a) {
   __shared__ double s_red[2][4];
   __shared__ float s_mm[2][4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int lat = blockIdx.x, K = a.K;
+  const CqLattice& g = a.lat;
+  const int lat = blockIdx.x, K = g.K;
   const int64_t r0 = (int64_t)lat * K;
-  const float* psi = a.psi + (size_t)lat * a.ldn;
-  const float qinv = 1.0f / a.qnorm[lat];
-  for (int c = tid; c < a.ldn; c += 256) qn[c] = psi[c] * qinv;
+  const float* psi = g.psi + (size_t)lat * g.ldn;
+  const float qinv = 1.0f / g.qnorm[lat];
+  for (int c = tid; c < g.ldn; c += 256) qn[c] = psi[c] * qinv;
   __syncthreads();
   for (int r = wave; r < K; r += 4) {  // a wave per row
-    const float* yi = a.Yn + (size_t)(r0 + r) * a.ldn;
+    const float* yi = a.Yn + (size_t)(r0 + r) * g.ldn;
     float s = 0.f;
-    for (int c = lane; c < a.ldn; c += 64) s = fmaf(yi[c], qn[c], s);
+    for (int c = lane; c < g.ldn; c += 64) s = fmaf(yi[c], qn[c], s);
     s = wave_sum_f(s);
     if (lane == 0) sp[r] = a.beta * fmaxf(0.f, s);
   }
   __syncthreads();
   auto block_sum2 = [&](double u, double v, double& U, double& V) {
-    u = wave_sum_d2(u);
-    v = wave_sum_d2(v);
+    u = wave_sum_d(u);
+    v = wave_sum_d(v);
     if (lane == 0) {
       s_red[0][wave] = u;
       s_red[1][wave] = v;
@@ -638,7 +508,7 @@ __global__ __launch_bounds__(256) void k_cq_gates(const GateArgs a) {
     __syncthreads();
   };
   auto block_sum = [&](double u) {
-    u = wave_sum_d2(u);
+    u = wave_sum_d(u);
     if (lane == 0) s_red[0][wave] = u;
     __syncthreads();
     const double U = ((s_red[0][0] + s_red[0][1]) + s_red[0][2]) + s_red[0][3];
@@ -673,9 +543,9 @@ __global__ __launch_bounds__(256) void k_cq_gates(const GateArgs a) {
       const int row = tid + 256 * m;
       if (row < K) {
         const int64_t i = r0 + row;
-        const int d = a.deg[i];
+        const int d = g.deg[i];
         float acc = 0.f;
-        for (int e = 0; e < d; ++e) acc = fmaf(a.w[i * a.k + e], sp[a.col[i * a.k + e] - r0], acc);
+        for (int e = 0; e < d; ++e) acc = fmaf(g.w[i * g.k + e], sp[g.col[i * g.k + e] - r0], acc);
         const float pv = sp[row];
         ap[m] = cs * pv - acc;
         pap += (double)pv * (double)ap[m];
@@ -707,28 +577,25 @@ __global__ __launch_bounds__(256) void k_cq_gates(const GateArgs a) {
     rz = T2;
     __syncthreads();
   }
-  const float qnan = __uint_as_float(0x7FC00000u);
-  auto nmin = [&](float x, float y) { return (x != x || y != y) ? qnan : fminf(x, y); };  // np.min / np.max keep a NaN
-  auto nmax = [&](float x, float y) { return (x != x || y != y) ? qnan : fmaxf(x, y); };
   float lo = INFINITY, hi = -INFINITY;
 #pragma unroll
   for (int m = 0; m < kGateOwn; ++m)
     if (tid + 256 * m < K) {
-      lo = nmin(lo, h[m]);
-      hi = nmax(hi, h[m]);
+      lo = nan_min(lo, h[m]);
+      hi = nan_max(hi, h[m]);
     }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
-    lo = nmin(lo, __shfl_xor(lo, o, 64));
-    hi = nmax(hi, __shfl_xor(hi, o, 64));
+    lo = nan_min(lo, __shfl_xor(lo, o, 64));
+    hi = nan_max(hi, __shfl_xor(hi, o, 64));
   }
   if (lane == 0) {
     s_mm[0][wave] = lo;
     s_mm[1][wave] = hi;
   }
   __syncthreads();
-  lo = nmin(nmin(s_mm[0][0], s_mm[0][1]), nmin(s_mm[0][2], s_mm[0][3]));
-  hi = nmax(nmax(s_mm[1][0], s_mm[1][1]), nmax(s_mm[1][2], s_mm[1][3]));
+  lo = nan_min(nan_min(s_mm[0][0], s_mm[0][1]), nan_min(s_mm[0][2], s_mm[0][3]));
+  hi = nan_max(nan_max(s_mm[1][0], s_mm[1][1]), nan_max(s_mm[1][2], s_mm[1][3]));
   const bool flat = (double)hi - (double)lo < 1e-12;  // diffusion.py:119-122; false for a NaN, which then spreads
   const float span = hi - lo;
 #pragma unroll
@@ -785,8 +652,10 @@ T* at(osc_corpus& c, int64_t off) {
 
 struct RefineReq {
   const float* psis;
-  int32_t Q, K;
+  int32_t Q;
+  int32_t top_k, kneighbors;  // as given; set_shape turns them into K and knn
   const int32_t* cand_in;  // Q x K or nullptr (search)
+  int32_t K;
   int32_t knn;             // effective list length (0: K == 1, no edges)
   float row_cap, lamG, lamC, lamQ, tol;
   int32_t max_iters, kk;
@@ -801,37 +670,41 @@ struct RefineReq {
   int32_t s_max_iters = 12, null_cap = 0, null_slots = 0;
 };
 
-// one chunk [q0, q0 + nq): psi upload, candidates, and the requested stages; returns the layout used
+// one chunk [q0, q0 + nq): psi upload, candidates, and the requested stages in the order of the list at the top of this
+// file; returns the layout used
 host::CorpusLayout run_chunk(osc_corpus& c, const RefineReq& rq, int32_t q0, int32_t nq, int32_t cap_nq) {
   const int32_t K = rq.K, ldn = c.ldn, k = std::max(1, rq.knn), kk = std::max(1, rq.kk);
   const host::CorpusLayout L = host::corpus_layout(c.N, ldn, K, k, kk, cap_nq, rq.receipts != 0, rq.null_slots);
   if ((int64_t)c.scratch.n < L.total) c.scratch.alloc((size_t)L.total);
   hipStream_t s = c.stream;
+  const dim3 per_lattice((unsigned)nq), wg(256);
   std::vector<float> hp((size_t)nq * ldn, 0.f);
   for (int32_t q = 0; q < nq; ++q)
     std::copy(rq.psis + (size_t)(q0 + q) * c.D, rq.psis + (size_t)(q0 + q + 1) * c.D, hp.begin() + (size_t)q * ldn);
   float* psi = at<float>(c, L.psi);
   float* qnorm = at<float>(c, L.qnorm);
   int32_t* cand = at<int32_t>(c, L.cand);
+  // prep, and the candidates: given, or gemm + select
   HIP_CHECK(hipMemcpyAsync(psi, hp.data(), hp.size() * 4, hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_cq_prep, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, s, psi, ldn, nq, qnorm);
+  hipLaunchKernelGGL(k_cq_prep, dim3((unsigned)((nq + 3) / 4)), wg, 0, s, psi, ldn, nq, qnorm);
   if (rq.cand_in) {
     HIP_CHECK(hipMemcpyAsync(cand, rq.cand_in + (size_t)q0 * K, (size_t)nq * K * 4, hipMemcpyHostToDevice, s));
   } else {
     float* dots = at<float>(c, L.dots);
     const dim3 grid((unsigned)((c.N + kTM - 1) / kTM), (unsigned)((nq + kTQ - 1) / kTQ));
-    hipLaunchKernelGGL(k_cq_gemm, grid, dim3(256), 0, s, c.Yn.p, c.N, ldn, psi, nq, qnorm, dots);
-    hipLaunchKernelGGL(k_cq_select, dim3((unsigned)nq), dim3(kSelT), 0, s, dots, c.N, K, cand, at<float>(c, L.ccos));
+    hipLaunchKernelGGL(k_cq_gemm, grid, wg, 0, s, c.Yn.p, c.N, ldn, psi, nq, qnorm, dots);
+    hipLaunchKernelGGL(k_cq_select, per_lattice, dim3(kSelT), 0, s, dots, c.N, K, cand, at<float>(c, L.ccos));
   }
   HIP_CHECK(hipGetLastError());
   if (rq.stage == 0) return L;
+  // gather
   const int64_t rows = (int64_t)nq * K;
   float* Yc = at<float>(c, L.Y);
   float* Ync = at<float>(c, L.Yn);
   float* X = at<float>(c, L.X);
-  hipLaunchKernelGGL(k_cq_gather, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, c.Y.p, c.Yn.p, ldn, cand, rows, Yc,
-                     Ync, X);
+  hipLaunchKernelGGL(k_cq_gather, dim3((unsigned)((rows + 3) / 4)), wg, 0, s, c.Y.p, c.Yn.p, ldn, cand, rows, Yc, Ync, X);
   HIP_CHECK(hipGetLastError());
+  // the graph of every lattice
   const int32_t lds = host::corpus_lds(K);
   int32_t* col = at<int32_t>(c, L.col);
   float* adj = at<float>(c, L.adj);
@@ -847,146 +720,48 @@ host::CorpusLayout run_chunk(osc_corpus& c, const RefineReq& rq, int32_t q0, int
   }
   launch_cap_and_normalize(adj, w, col, deg, k, (int32_t)rows, rq.row_cap, 1, at<float>(c, L.scale), sd, s);
   float* gates = at<float>(c, L.gates);
+  const CqLattice lat{Yc, psi, qnorm, col, w, adj, deg, sd, rq.gate ? gates : nullptr, K, k, ldn, rq.lamG, rq.lamC, rq.lamQ};
+  // gates: solved per lattice, or given
   if (rq.gate == 1) {
-    GateArgs ga{};
-    ga.Yn = Ync;
-    ga.psi = psi;
-    ga.qnorm = qnorm;
-    ga.col = col;
-    ga.w = w;
-    ga.deg = deg;
-    ga.gates = gates;
-    ga.iters = at<int32_t>(c, L.g_iters);
-    ga.res = at<float>(c, L.g_res);
-    ga.K = K;
-    ga.k = k;
-    ga.ldn = ldn;
-    ga.max_iters = rq.g_max_iters;
-    ga.direct = rq.g_direct;
-    ga.clamp = rq.g_clamp;
-    ga.beta = rq.g_beta;
-    ga.gamma = rq.g_gamma;
-    ga.tol = rq.g_tol;
-    hipLaunchKernelGGL(k_cq_gates, dim3((unsigned)nq), dim3(256), 0, s, ga);
+    const GateArgs ga{lat, Ync, gates, at<int32_t>(c, L.g_iters), at<float>(c, L.g_res), rq.g_max_iters, rq.g_direct,
+                      rq.g_clamp, rq.g_beta, rq.g_gamma, rq.g_tol};
+    hipLaunchKernelGGL(k_cq_gates, per_lattice, wg, 0, s, ga);
     HIP_CHECK(hipGetLastError());
   } else if (rq.gate == 2) {
     HIP_CHECK(hipMemcpyAsync(gates, rq.gates_in + (size_t)q0 * K, (size_t)rows * 4, hipMemcpyHostToDevice, s));
   }
   if (rq.stage == 1) return L;
-  SolveArgs sa{};
-  sa.Y = Yc;
-  sa.psi = psi;
-  sa.col = col;
-  sa.w = w;
-  sa.deg = deg;
-  sa.X = X;
-  sa.R = at<float>(c, L.R);
-  sa.P = at<float>(c, L.P);
-  sa.AP = at<float>(c, L.AP);
-  sa.iters = at<int32_t>(c, L.iters);
-  sa.res = at<float>(c, L.res);
-  sa.K = K;
-  sa.k = k;
-  sa.ldn = ldn;
-  sa.max_iters = rq.max_iters;
-  sa.lamG = rq.lamG;
-  sa.lamC = rq.lamC;
-  sa.lamQ = rq.lamQ;
-  sa.tol = rq.tol;
-  sa.B = rq.gate ? gates : nullptr;
-  const int nc = (ldn + 255) / 256;
-  const dim3 sg((unsigned)nq), sb(256);
-  if (!rq.gate) {
-    if (nc <= 1) hipLaunchKernelGGL((k_cq_solve<1, false>), sg, sb, 0, s, sa);
-    else if (nc == 2) hipLaunchKernelGGL((k_cq_solve<2, false>), sg, sb, 0, s, sa);
-    else if (nc == 3) hipLaunchKernelGGL((k_cq_solve<3, false>), sg, sb, 0, s, sa);
-    else if (nc == 4) hipLaunchKernelGGL((k_cq_solve<4, false>), sg, sb, 0, s, sa);
-    else hipLaunchKernelGGL((k_cq_solve<6, false>), sg, sb, 0, s, sa);
-  } else {
-    if (nc <= 1) hipLaunchKernelGGL((k_cq_solve<1, true>), sg, sb, 0, s, sa);
-    else if (nc == 2) hipLaunchKernelGGL((k_cq_solve<2, true>), sg, sb, 0, s, sa);
-    else if (nc == 3) hipLaunchKernelGGL((k_cq_solve<3, true>), sg, sb, 0, s, sa);
-    else if (nc == 4) hipLaunchKernelGGL((k_cq_solve<4, true>), sg, sb, 0, s, sa);
-    else hipLaunchKernelGGL((k_cq_solve<6, true>), sg, sb, 0, s, sa);
-  }
+  // solve: U* into X
+  const CqPcgArgs sa{lat, X, at<float>(c, L.R), at<float>(c, L.P), at<float>(c, L.AP), at<int32_t>(c, L.iters),
+                     at<float>(c, L.res), rq.max_iters, rq.tol, 0.f};
+  cq_with_nc(ldn, [&](auto nc) {
+    constexpr int NC = decltype(nc)::value;
+    if (rq.gate) hipLaunchKernelGGL((k_cq_solve<NC, true>), per_lattice, wg, 0, s, sa);
+    else hipLaunchKernelGGL((k_cq_solve<NC, false>), per_lattice, wg, 0, s, sa);
+  });
   HIP_CHECK(hipGetLastError());
+  // bundle
   if (rq.kk > 0) {
-    BundleArgs ba{};
-    ba.Y = Yc;
-    ba.U = X;
-    ba.psi = psi;
-    ba.qnorm = qnorm;
-    ba.col = col;
-    ba.adj = adj;
-    ba.deg = deg;
-    ba.sd = sd;
-    ba.Sm = Sm;
-    ba.K = K;
-    ba.k = k;
-    ba.ldn = ldn;
-    ba.lds = lds;
-    ba.kk = rq.kk;
-    ba.lamC = rq.lamC;
-    ba.alpha = (double)rq.alpha;
-    ba.lambda = 0.5;
-    ba.o_local = at<int32_t>(c, L.o_local);
-    ba.o_score = at<float>(c, L.o_score);
-    ba.o_align = at<float>(c, L.o_align);
-    hipLaunchKernelGGL(k_cq_bundle, dim3((unsigned)nq), dim3(256), 0, s, ba);
+    const BundleArgs ba{lat, X, Sm, lds, rq.kk, (double)rq.alpha, 0.5, at<int32_t>(c, L.o_local), at<float>(c, L.o_score),
+                        at<float>(c, L.o_align)};
+    hipLaunchKernelGGL(k_cq_bundle, per_lattice, wg, 0, s, ba);
     HIP_CHECK(hipGetLastError());
   }
   if (!rq.receipts) return L;
-  CqSettleArgs ta{};
-  ta.Y = Yc;
-  ta.psi = psi;
-  ta.col = col;
-  ta.w = w;
-  ta.deg = deg;
-  ta.X = Ync;  // dead since the graph, the gates and the bundle: the settled state lives there, U* stays in X
-  ta.R = sa.R;
-  ta.P = sa.P;
-  ta.AP = sa.AP;
+  // settle: the solve's R, P and AP again; the settled state takes Ync, dead since the graph, the gates and the bundle, and
+  // U* stays in X
+  CqPcgArgs ta = sa;
+  ta.X = Ync;
   ta.iters = at<int32_t>(c, L.s_iters);
   ta.res = at<float>(c, L.s_res);
-  ta.K = K;
-  ta.k = k;
-  ta.ldn = ldn;
   ta.max_iters = rq.s_max_iters;
-  ta.lamG = rq.lamG;
-  ta.lamC = rq.lamC;
-  ta.lamQ = rq.lamQ;
-  ta.dt = rq.s_dt;
   ta.tol = rq.s_tol;
-  ta.B = rq.gate ? gates : nullptr;
+  ta.dt = rq.s_dt;
   launch_cq_settle(ta, nq, s);
-  CqReceiptArgs ra{};
-  ra.Y = Yc;
-  ra.Us = X;
-  ra.Up = Ync;
-  ra.psi = psi;
-  ra.col = col;
-  ra.w = w;
-  ra.adj = adj;
-  ra.deg = deg;
-  ra.sd = sd;
-  ra.B = rq.gate ? gates : nullptr;
-  ra.K = K;
-  ra.k = k;
-  ra.ldn = ldn;
-  ra.full = rq.receipts == 2;
-  ra.cap = rq.null_cap;
-  ra.slots = rq.null_slots;
-  ra.lamG = rq.lamG;
-  ra.lamC = rq.lamC;
-  ra.lamQ = rq.lamQ;
-  ra.z_th = rq.z_th;
-  ra.sums = at<double>(c, L.r_sums);
-  ra.n_total = at<int32_t>(c, L.n_total);
-  ra.n_kept = at<int32_t>(c, L.n_kept);
-  ra.n_i = at<int32_t>(c, L.n_i);
-  ra.n_j = at<int32_t>(c, L.n_j);
-  ra.n_z = at<float>(c, L.n_z);
-  ra.n_r = at<float>(c, L.n_r);
+  // receipt
+  const CqReceiptArgs ra{lat, X, Ync, rq.receipts == 2, rq.null_cap, rq.null_slots, rq.z_th, at<double>(c, L.r_sums),
+                         at<int32_t>(c, L.n_total), at<int32_t>(c, L.n_kept), at<int32_t>(c, L.n_i), at<int32_t>(c, L.n_j),
+                         at<float>(c, L.n_z), at<float>(c, L.n_r)};
   launch_cq_receipt(ra, nq, s);
   return L;
 }
@@ -1045,20 +820,60 @@ void check_gate_settings(float beta, float gamma, int32_t method, int32_t max_it
   if (max_iters < 1) throw Invalid("max_iters must be >= 1");
 }
 
-// rq.psis / Q / gate fields set by the caller; the rest of the request is validated and filled here
-// what every per-lattice entry point checks first, in this order
-void check_request(const osc_corpus& c, const float* psis, int32_t Q, int32_t top_k, int32_t kneighbors) {
-  check_queries(c, psis, Q, top_k);
-  if (kneighbors < 1) throw Invalid("kneighbors must be >= 1");
+// the gates of a request: mode 0 = none, 1 = diffusion gates under these (checked) settings, 2 = gates_in
+void set_gate_request(RefineReq& rq, int32_t mode, const float* gates_in, float beta, float gamma, int32_t method, float tol,
+                      int32_t max_iters) {
+  rq.gate = mode;
+  if (mode == 2) rq.gates_in = gates_in;
+  if (mode != 1) return;
+  check_gate_settings(beta, gamma, method, max_iters);
+  rq.g_beta = beta;
+  rq.g_gamma = gamma;
+  rq.g_direct = method == 0;
+  rq.g_tol = tol;
+  rq.g_max_iters = method == 0 ? 2048 : max_iters;  // direct: the reference's dense solve, served by a long CG
 }
 
-// K and the list length of the request's lattices, and its candidates if given
-void set_shape(const osc_corpus& c, RefineReq& rq, int32_t top_k, int32_t kneighbors, const int32_t* cand_in) {
-  rq.K = (int32_t)std::min<int64_t>(top_k, c.N);
-  rq.knn = rq.K > 1 ? host::corpus_knn(kneighbors, rq.K) : 0;
-  if (rq.knn > host::kCorpusMaxKnn) throw Invalid("min(kneighbors, K - 1) must be at most 128");
-  if (cand_in) check_candidates(c, cand_in, rq.Q, rq.K);
+// the queries, top_k, kneighbors and candidates of a request (checked by check_request and set_shape)
+RefineReq lattice_request(const float* psis, int32_t Q, int32_t top_k, int32_t kneighbors, const int32_t* cand_in) {
+  RefineReq rq{};
+  rq.psis = psis;
+  rq.Q = Q;
+  rq.top_k = top_k;
+  rq.kneighbors = kneighbors;
   rq.cand_in = cand_in;
+  return rq;
+}
+
+// a full refine: the lattices, the U* solve's settings and the bundle's
+RefineReq refine_request(const float* psis, int32_t Q, int32_t top_k, const int32_t* cand_in, int32_t kneighbors,
+                         float row_cap, float lamG, float lamC, float lamQ, float tol, int32_t max_iters, int32_t k,
+                         float alpha) {
+  RefineReq rq = lattice_request(psis, Q, top_k, kneighbors, cand_in);
+  rq.row_cap = row_cap;
+  rq.lamG = lamG;
+  rq.lamC = lamC;
+  rq.lamQ = lamQ;
+  rq.tol = tol;
+  rq.max_iters = std::max(1, max_iters);
+  rq.kk = k;  // as given; refine_body clamps it to [0, K]
+  rq.alpha = alpha;
+  rq.stage = 2;
+  return rq;
+}
+
+// what every per-lattice entry point checks first, in this order
+void check_request(const osc_corpus& c, const RefineReq& rq) {
+  check_queries(c, rq.psis, rq.Q, rq.top_k);
+  if (rq.kneighbors < 1) throw Invalid("kneighbors must be >= 1");
+}
+
+// K and the list length of the request's lattices, and its candidates checked if given
+void set_shape(const osc_corpus& c, RefineReq& rq) {
+  rq.K = (int32_t)std::min<int64_t>(rq.top_k, c.N);
+  rq.knn = rq.K > 1 ? host::corpus_knn(rq.kneighbors, rq.K) : 0;
+  if (rq.knn > host::kCorpusMaxKnn) throw Invalid("min(kneighbors, K - 1) must be at most 128");
+  if (rq.cand_in) check_candidates(c, rq.cand_in, rq.Q, rq.K);
 }
 
 // runs the request chunk by chunk; fetch(L, q0, n, down) queues the chunk's downloads, then the stream is drained
@@ -1076,14 +891,72 @@ void for_each_chunk(osc_corpus& c, const RefineReq& rq, F&& fetch) {
   }
 }
 
-void refine_body(osc_corpus& c, RefineReq rq, int32_t top_k, const int32_t* cand_in, int32_t kneighbors, float row_cap,
-                 float lamG, float lamC, float lamQ, float tol, int32_t max_iters, int32_t k, float alpha,
-                 const RefineOut& o, const char* null_msg, const ReceiptOut* ro = nullptr) {
+// a chunk's receipts: per-query scalars and the slabs of kept null points (null_slots per query), packed back to back on the
+// host once the chunk's copies have landed (the stream is drained here: the staging vectors live in this call)
+template <class Down>
+void fetch_receipts(osc_corpus& c, const RefineReq& rq, const ReceiptOut& ro, const host::CorpusLayout& L, int32_t q0,
+                    int32_t n, Down& down) {
+  const bool full = rq.receipts == 2;
+  const int32_t slots = rq.null_slots, kw = std::max(1, rq.knn);
+  std::vector<double> hs((size_t)n * 4);
+  std::vector<int32_t> hk((size_t)n), hi((size_t)n * slots), hj((size_t)n * slots), hd, hc;
+  std::vector<float> hz((size_t)n * slots), hr((size_t)n * slots);
+  down(ro.s_iters + q0, L.s_iters, (size_t)n * 4);
+  down(ro.s_res + q0, L.s_res, (size_t)n * 4);
+  down(hs.data(), L.r_sums, hs.size() * 8);
+  down(ro.null_total + q0, L.n_total, (size_t)n * 4);
+  down(hk.data(), L.n_kept, (size_t)n * 4);
+  if (full && slots > 0) {
+    down(hi.data(), L.n_i, hi.size() * 4);
+    down(hj.data(), L.n_j, hj.size() * 4);
+    down(hz.data(), L.n_z, hz.size() * 4);
+    down(hr.data(), L.n_r, hr.size() * 4);
+  }
+  const bool want_graph = ro.nnz || ro.edge_prefix;
+  if (want_graph) {
+    hd.resize((size_t)n * rq.K);
+    hc.resize((size_t)n * rq.K * kw);
+    down(hd.data(), L.deg, hd.size() * 4);
+    down(hc.data(), L.col, hc.size() * 4);
+  }
+  HIP_CHECK(hipStreamSynchronize(c.stream));
+  for (int32_t q = 0; q < n; ++q) {
+    for (int t = 0; t < 4; ++t) ro.sums[t][q0 + q] = hs[(size_t)q * 4 + t];
+    int64_t at0 = ro.null_offsets[q0 + q];
+    const int32_t kept = full ? std::min(std::max(hk[(size_t)q], 0), slots) : 0;
+    for (int32_t t = 0; t < kept; ++t) {
+      const size_t sidx = (size_t)q * slots + t;
+      ro.null_i[at0 + t] = hi[sidx];
+      ro.null_j[at0 + t] = hj[sidx];
+      ro.null_z[at0 + t] = hz[sidx];
+      ro.null_r[at0 + t] = hr[sidx];
+    }
+    ro.null_offsets[q0 + q + 1] = at0 + kept;
+    if (!want_graph) continue;
+    int64_t nnz = 0, np = 0;
+    const int64_t r0 = (int64_t)q * rq.K;
+    int64_t* pairs = ro.edge_prefix ? ro.edge_prefix + (size_t)(q0 + q) * ro.prefix_cap * 2 : nullptr;
+    for (int32_t i = 0; i < rq.K; ++i) {
+      const int32_t d = rq.knn > 0 ? hd[(size_t)(r0 + i)] : 0;
+      for (int32_t e = 0; e < d && pairs && np < ro.prefix_cap; ++e, ++np) {
+        pairs[np * 2] = i;
+        pairs[np * 2 + 1] = (int64_t)hc[(size_t)(r0 + i) * kw + e] - r0;
+      }
+      nnz += d;
+    }
+    if (ro.nnz) ro.nnz[q0 + q] = nnz;
+    if (ro.edge_prefix_n) ro.edge_prefix_n[q0 + q] = (int32_t)np;
+  }
+}
+
+// validates a refine_request (with its gates and receipts set) and its buffers, in the order the messages are documented
+// in, and runs it
+void refine_body(osc_corpus& c, RefineReq rq, const RefineOut& o, const char* null_msg, const ReceiptOut* ro = nullptr) {
   const int32_t Q = rq.Q;
-  check_request(c, rq.psis, Q, top_k, kneighbors);
-  if (!(lamG > 0.f) || lamC < 0.f || lamQ < 0.f) throw Invalid("need lamG > 0, lamC >= 0, lamQ >= 0");
-  set_shape(c, rq, top_k, kneighbors, cand_in);
-  rq.kk = std::min(std::max(k, 0), rq.K);
+  check_request(c, rq);
+  if (!(rq.lamG > 0.f) || rq.lamC < 0.f || rq.lamQ < 0.f) throw Invalid("need lamG > 0, lamC >= 0, lamQ >= 0");
+  set_shape(c, rq);
+  rq.kk = std::min(std::max(rq.kk, 0), rq.K);
   if (rq.gate == 2)
     for (int64_t i = 0; i < (int64_t)Q * rq.K; ++i)
       if (!std::isfinite(rq.gates_in[i]) || rq.gates_in[i] < 0.f) throw Invalid("gates must be finite and >= 0");
@@ -1095,8 +968,8 @@ void refine_body(osc_corpus& c, RefineReq rq, int32_t top_k, const int32_t* cand
   if (!o.cand || !o.iters || !o.res || (rq.kk > 0 && (!o.local || !o.score || !o.align)) ||
       (rq.gate && (!o.gates || !o.g_iters || !o.g_res)))
     throw Invalid(null_msg);
-  const bool full = rq.receipts == 2;
   if (ro) {
+    const bool full = rq.receipts == 2;
     if (!ro->s_iters || !ro->s_res || !ro->sums[0] || !ro->sums[1] || !ro->sums[2] || !ro->sums[3] || !ro->null_total ||
         (full && (!ro->null_i || !ro->null_j || !ro->null_z || !ro->null_r)) ||
         (ro->edge_prefix && (!ro->edge_prefix_n || ro->prefix_cap < 0)))
@@ -1104,14 +977,6 @@ void refine_body(osc_corpus& c, RefineReq rq, int32_t top_k, const int32_t* cand
     rq.null_slots = host::corpus_null_slots(rq.K, full, rq.null_cap);
     if (full && ro->capacity < (int64_t)Q * rq.null_slots) throw Invalid("null point capacity too small");
   }
-  rq.row_cap = row_cap;
-  rq.lamG = lamG;
-  rq.lamC = lamC;
-  rq.lamQ = lamQ;
-  rq.tol = tol;
-  rq.max_iters = std::max(1, max_iters);
-  rq.alpha = alpha;
-  rq.stage = 2;
   for_each_chunk(c, rq, [&](const host::CorpusLayout& L, int32_t q0, int32_t n, auto& down) {
     down(o.cand + (size_t)q0 * rq.K, L.cand, (size_t)n * rq.K * 4);
     down(o.iters + q0, L.iters, (size_t)n * 4);
@@ -1126,59 +991,7 @@ void refine_body(osc_corpus& c, RefineReq rq, int32_t top_k, const int32_t* cand
       down(o.g_iters + q0, L.g_iters, (size_t)n * 4);
       down(o.g_res + q0, L.g_res, (size_t)n * 4);
     }
-    if (!ro) return;
-    // receipts: per-query scalars and the slabs of kept null points (null_slots per query), packed back to back on the host
-    // once the chunk's copies have landed (the stream is drained here: the staging vectors live in this call)
-    const int32_t slots = rq.null_slots, kw = std::max(1, rq.knn);
-    std::vector<double> hs((size_t)n * 4);
-    std::vector<int32_t> hk((size_t)n), hi((size_t)n * slots), hj((size_t)n * slots), hd, hc;
-    std::vector<float> hz((size_t)n * slots), hr((size_t)n * slots);
-    down(ro->s_iters + q0, L.s_iters, (size_t)n * 4);
-    down(ro->s_res + q0, L.s_res, (size_t)n * 4);
-    down(hs.data(), L.r_sums, hs.size() * 8);
-    down(ro->null_total + q0, L.n_total, (size_t)n * 4);
-    down(hk.data(), L.n_kept, (size_t)n * 4);
-    if (full && slots > 0) {
-      down(hi.data(), L.n_i, hi.size() * 4);
-      down(hj.data(), L.n_j, hj.size() * 4);
-      down(hz.data(), L.n_z, hz.size() * 4);
-      down(hr.data(), L.n_r, hr.size() * 4);
-    }
-    const bool want_graph = ro->nnz || ro->edge_prefix;
-    if (want_graph) {
-      hd.resize((size_t)n * rq.K);
-      hc.resize((size_t)n * rq.K * kw);
-      down(hd.data(), L.deg, hd.size() * 4);
-      down(hc.data(), L.col, hc.size() * 4);
-    }
-    HIP_CHECK(hipStreamSynchronize(c.stream));
-    for (int32_t q = 0; q < n; ++q) {
-      for (int t = 0; t < 4; ++t) ro->sums[t][q0 + q] = hs[(size_t)q * 4 + t];
-      int64_t at0 = ro->null_offsets[q0 + q];
-      const int32_t kept = full ? std::min(std::max(hk[(size_t)q], 0), slots) : 0;
-      for (int32_t t = 0; t < kept; ++t) {
-        const size_t sidx = (size_t)q * slots + t;
-        ro->null_i[at0 + t] = hi[sidx];
-        ro->null_j[at0 + t] = hj[sidx];
-        ro->null_z[at0 + t] = hz[sidx];
-        ro->null_r[at0 + t] = hr[sidx];
-      }
-      ro->null_offsets[q0 + q + 1] = at0 + kept;
-      if (!want_graph) continue;
-      int64_t nnz = 0, np = 0;
-      const int64_t r0 = (int64_t)q * rq.K;
-      int64_t* pairs = ro->edge_prefix ? ro->edge_prefix + (size_t)(q0 + q) * ro->prefix_cap * 2 : nullptr;
-      for (int32_t i = 0; i < rq.K; ++i) {
-        const int32_t d = rq.knn > 0 ? hd[(size_t)(r0 + i)] : 0;
-        for (int32_t e = 0; e < d && pairs && np < ro->prefix_cap; ++e, ++np) {
-          pairs[np * 2] = i;
-          pairs[np * 2 + 1] = (int64_t)hc[(size_t)(r0 + i) * kw + e] - r0;
-        }
-        nnz += d;
-      }
-      if (ro->nnz) ro->nnz[q0 + q] = nnz;
-      if (ro->edge_prefix_n) ro->edge_prefix_n[q0 + q] = (int32_t)np;
-    }
+    if (ro) fetch_receipts(c, rq, *ro, L, q0, n, down);
   });
   if (rq.gate == 2) {  // nothing was solved for given gates
     std::fill(o.g_iters, o.g_iters + Q, 0);
@@ -1262,16 +1075,10 @@ int osc_corpus_search(osc_corpus_handle h, const float* psis, int32_t Q, int32_t
     rq.Q = Q;
     rq.K = (int32_t)std::min<int64_t>(top_k, c.N);
     rq.stage = 0;
-    const int32_t nq = chunk_for(c, rq.K, 0, 0);
-    for (int32_t ch = 0; ch < host::chunk_count(Q, nq); ++ch) {
-      const int32_t q0 = host::chunk_begin(ch, nq), n = host::chunk_size(Q, ch, nq);
-      const host::CorpusLayout L = run_chunk(c, rq, q0, n, nq);
-      HIP_CHECK(hipMemcpyAsync(ids + (size_t)q0 * rq.K, at<int32_t>(c, L.cand), (size_t)n * rq.K * 4, hipMemcpyDeviceToHost,
-                               c.stream));
-      HIP_CHECK(hipMemcpyAsync(cos + (size_t)q0 * rq.K, at<float>(c, L.ccos), (size_t)n * rq.K * 4, hipMemcpyDeviceToHost,
-                               c.stream));
-      HIP_CHECK(hipStreamSynchronize(c.stream));
-    }
+    for_each_chunk(c, rq, [&](const host::CorpusLayout& L, int32_t q0, int32_t n, auto& down) {
+      down(ids + (size_t)q0 * rq.K, L.cand, (size_t)n * rq.K * 4);
+      down(cos + (size_t)q0 * rq.K, L.ccos, (size_t)n * rq.K * 4);
+    });
   });
 }
 
@@ -1280,10 +1087,7 @@ int osc_corpus_refine(osc_corpus_handle h, const float* psis, int32_t Q, int32_t
                       int32_t k, float alpha, int32_t* cand_out, int32_t* local, float* score, float* align, int32_t* iters,
                       float* res) {
   return corpus_guarded(h, [&](osc_corpus& c) {
-    RefineReq rq{};
-    rq.psis = psis;
-    rq.Q = Q;
-    refine_body(c, rq, top_k, cand_in, kneighbors, row_cap, lamG, lamC, lamQ, tol, max_iters, k, alpha,
+    refine_body(c, refine_request(psis, Q, top_k, cand_in, kneighbors, row_cap, lamG, lamC, lamQ, tol, max_iters, k, alpha),
                 RefineOut{cand_out, local, score, align, iters, res}, "osc_corpus_refine: NULL buffer");
   });
 }
@@ -1295,26 +1099,9 @@ int osc_corpus_refine_gated(osc_corpus_handle h, const float* psis, int32_t Q, i
                             int32_t* local, float* score, float* align, int32_t* iters, float* res, int32_t* gate_iters,
                             float* gate_res) {
   return corpus_guarded(h, [&](osc_corpus& c) {
-    RefineReq rq{};
-    rq.psis = psis;
-    rq.Q = Q;
-    if (gates_in) {
-      rq.gate = 2;
-      rq.gates_in = gates_in;
-    } else {
-      check_gate_settings(beta, gamma, method, gate_max_iters);
-      rq.gate = 1;
-      rq.g_beta = beta;
-      rq.g_gamma = gamma;
-      rq.g_direct = method == 0;
-      rq.g_tol = gate_tol;
-      rq.g_max_iters = method == 0 ? 2048 : gate_max_iters;
-    }
-    RefineOut o{cand_out, local, score, align, iters, res};
-    o.gates = gates_out;
-    o.g_iters = gate_iters;
-    o.g_res = gate_res;
-    refine_body(c, rq, top_k, cand_in, kneighbors, row_cap, lamG, lamC, lamQ, tol, max_iters, k, alpha, o,
+    RefineReq rq = refine_request(psis, Q, top_k, cand_in, kneighbors, row_cap, lamG, lamC, lamQ, tol, max_iters, k, alpha);
+    set_gate_request(rq, gates_in ? 2 : 1, gates_in, beta, gamma, method, gate_tol, gate_max_iters);
+    refine_body(c, rq, RefineOut{cand_out, local, score, align, iters, res, gates_out, gate_iters, gate_res},
                 "osc_corpus_refine_gated: NULL buffer");
   });
 }
@@ -1338,33 +1125,17 @@ int osc_corpus_refine_receipts(osc_corpus_handle h, const float* psis, int32_t Q
     if (settle_max_iters < 1) throw Invalid("settle_max_iters must be >= 1");
     if (!std::isfinite(settle_tol)) throw Invalid("settle_tol must be finite");
     if (!std::isfinite(z_th)) throw Invalid("z_th must be finite");
-    RefineReq rq{};
-    rq.psis = psis;
-    rq.Q = Q;
-    rq.gate = gate_mode;
-    if (gate_mode == 2) {
-      rq.gates_in = gates_in;
-    } else if (gate_mode == 1) {
-      check_gate_settings(beta, gamma, method, gate_max_iters);
-      rq.g_beta = beta;
-      rq.g_gamma = gamma;
-      rq.g_direct = method == 0;
-      rq.g_tol = gate_tol;
-      rq.g_max_iters = method == 0 ? 2048 : gate_max_iters;
-    }
+    RefineReq rq = refine_request(psis, Q, top_k, cand_in, kneighbors, row_cap, lamG, lamC, lamQ, tol, max_iters, k, alpha);
+    set_gate_request(rq, gate_mode, gates_in, beta, gamma, method, gate_tol, gate_max_iters);
     rq.receipts = detail ? 2 : 1;
     rq.s_dt = dt;
     rq.s_max_iters = settle_max_iters;
     rq.s_tol = settle_tol;
     rq.z_th = z_th;
     rq.null_cap = std::max(0, null_cap);
-    RefineOut o{cand_out, local, score, align, iters, res};
-    o.gates = gates_out;
-    o.g_iters = gate_iters;
-    o.g_res = gate_res;
-    ReceiptOut ro{settle_iters, settle_res, {dH, coh_sum, anchor_sum, query_sum}, null_total, null_offsets, null_i, null_j,
-                  null_z, null_r, null_capacity, nnz_out, edge_prefix, edge_prefix_n, edge_prefix_cap};
-    refine_body(c, rq, top_k, cand_in, kneighbors, row_cap, lamG, lamC, lamQ, tol, max_iters, k, alpha, o,
+    const ReceiptOut ro{settle_iters, settle_res, {dH, coh_sum, anchor_sum, query_sum}, null_total, null_offsets, null_i,
+                        null_j, null_z, null_r, null_capacity, nnz_out, edge_prefix, edge_prefix_n, edge_prefix_cap};
+    refine_body(c, rq, RefineOut{cand_out, local, score, align, iters, res, gates_out, gate_iters, gate_res},
                 "osc_corpus_refine_receipts: NULL buffer", &ro);
   });
 }
@@ -1373,22 +1144,14 @@ int osc_corpus_gates(osc_corpus_handle h, const float* psis, int32_t Q, int32_t 
                      int32_t kneighbors, float row_cap, float beta, float gamma, int32_t method, float tol,
                      int32_t max_iters, int32_t clamp, int32_t* cand_out, float* gates_out, int32_t* iters, float* res) {
   return corpus_guarded(h, [&](osc_corpus& c) {
-    check_request(c, psis, Q, top_k, kneighbors);
-    check_gate_settings(beta, gamma, method, max_iters);
-    RefineReq rq{};
-    rq.psis = psis;
-    rq.Q = Q;
-    set_shape(c, rq, top_k, kneighbors, cand_in);
+    RefineReq rq = lattice_request(psis, Q, top_k, kneighbors, cand_in);
+    check_request(c, rq);
+    set_gate_request(rq, 1, nullptr, beta, gamma, method, tol, max_iters);
+    set_shape(c, rq);
     if (Q == 0) return;
     if (!cand_out || !gates_out || !iters || !res) throw Invalid("osc_corpus_gates: NULL buffer");
     rq.row_cap = row_cap;
     rq.stage = 1;
-    rq.gate = 1;
-    rq.g_beta = beta;
-    rq.g_gamma = gamma;
-    rq.g_direct = method == 0;
-    rq.g_tol = tol;
-    rq.g_max_iters = method == 0 ? 2048 : max_iters;
     rq.g_clamp = clamp != 0;
     for_each_chunk(c, rq, [&](const host::CorpusLayout& L, int32_t q0, int32_t n, auto& down) {
       down(cand_out + (size_t)q0 * rq.K, L.cand, (size_t)n * rq.K * 4);
@@ -1403,17 +1166,10 @@ int osc_corpus_graph(osc_corpus_handle h, const float* psi, const int32_t* cand_
                      float row_cap, int32_t* cand_out, int64_t* rowptr, int32_t* col, float* a, float* w, float* sqrt_deg,
                      int64_t capacity, int64_t* nnz) {
   return corpus_guarded(h, [&](osc_corpus& c) {
-    check_queries(c, psi, 1, top_k);
-    if (kneighbors < 1) throw Invalid("kneighbors must be >= 1");
-    RefineReq rq{};
-    rq.psis = psi;
-    rq.Q = 1;
-    rq.K = (int32_t)std::min<int64_t>(top_k, c.N);
-    rq.knn = rq.K > 1 ? host::corpus_knn(kneighbors, rq.K) : 0;
-    if (rq.knn > host::kCorpusMaxKnn) throw Invalid("min(kneighbors, K - 1) must be at most 128");
-    if (cand_in) check_candidates(c, cand_in, 1, rq.K);
+    RefineReq rq = lattice_request(psi, 1, top_k, kneighbors, cand_in);
+    check_request(c, rq);
+    set_shape(c, rq);
     if (!cand_out || !rowptr || !col || !a || !w || !sqrt_deg || !nnz) throw Invalid("osc_corpus_graph: NULL buffer");
-    rq.cand_in = cand_in;
     rq.row_cap = row_cap;
     rq.stage = 1;
     const int32_t K = rq.K, k = std::max(1, rq.knn);

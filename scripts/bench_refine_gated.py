@@ -6,8 +6,8 @@ stream synchronisation before it returns, so each clock read follows a synchroni
 the figures are the median of --reps calls with min and max.  Writes profiles/refine_gated_bench.json.
 
     python scripts/bench_refine_gated.py [--N 100000 --D 768 --reps 5 --loop 32]
-    python scripts/bench_refine_gated.py --parent-lib PATH   # also: ungated refine, this build against the library
-                                                             # built from the parent commit, alternating in one process
+    python scripts/bench_refine_gated.py --parent-lib PATH   # also: the ungated and the gated refine, this build against the
+                                                             # library built from the parent commit, alternating in one process
     python scripts/bench_refine_gated.py --profile --reps 3  # the run to put under rocprofv3 --kernel-trace --stats"""
 import argparse
 import ctypes as C
@@ -39,41 +39,61 @@ def timed(fn, reps):
     return ts
 
 
-def raw_refine(lib, Y, P):
-    """The ungated osc_corpus_refine of a library through ctypes alone (its signature is the same in both builds)."""
+AB_ENTRY = {"ungated": "osc_corpus_refine", "gated": "osc_corpus_refine_gated", "receipts": "osc_corpus_refine_receipts"}
+
+
+def raw_refine(lib, Y, P, kind="ungated"):
+    """One refine entry point of a library through ctypes alone (the signatures are the same in both builds): "ungated" is
+    osc_corpus_refine, "gated" osc_corpus_refine_gated with diffusion gates, "receipts" osc_corpus_refine_receipts without
+    gates in full detail -- each with refine_many's arguments.  call() returns copies of every array the call fills."""
     from oscillink_amd import _native as nat
 
-    res, args = nat.SIGNATURES["osc_corpus_refine"]
-    for name in ("osc_corpus_create", "osc_corpus_destroy", "osc_corpus_refine"):
+    for name in ("osc_corpus_create", "osc_corpus_destroy", AB_ENTRY[kind]):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = nat.SIGNATURES[name]
     h = nat.Handle()
     assert lib.osc_corpus_create(nat.f32(Y), Y.shape[0], Y.shape[1], 0, C.byref(h)) == 0
     Q = P.shape[0]
-    cand = np.zeros((Q, TOP_K), np.int32)
-    local = np.zeros((Q, K_PICK), np.int32)
-    score = np.zeros((Q, K_PICK), np.float32)
-    align = np.zeros((Q, K_PICK), np.float32)
-    iters = np.zeros(Q, np.int32)
-    rs = np.zeros(Q, np.float32)
+    cand, g = np.zeros((Q, TOP_K), np.int32), np.zeros((Q, TOP_K), np.float32)
+    local, score, align = np.zeros((Q, K_PICK), np.int32), np.zeros((Q, K_PICK), np.float32), np.zeros((Q, K_PICK), np.float32)
+    iters, g_iters, s_iters, total = (np.zeros(Q, np.int32) for _ in range(4))
+    rs, g_res, s_res = (np.zeros(Q, np.float32) for _ in range(3))
+    sums, offsets = np.zeros((4, Q), np.float64), np.zeros(Q + 1, np.int64)
+    ni, nj = np.zeros(Q * TOP_K, np.int32), np.zeros(Q * TOP_K, np.int32)
+    nz, nr = np.zeros(Q * TOP_K, np.float32), np.zeros(Q * TOP_K, np.float32)
+    ptr = {np.dtype(np.int32): nat.i32, np.dtype(np.float32): nat.f32, np.dtype(np.int64): nat.i64,
+           np.dtype(np.float64): lambda v: v.ctypes.data_as(nat.c_f64p)}
+    solve = (6, 1.0, 1.0, 0.5, 4.0, 1e-4, 64, K_PICK, 0.5)  # kneighbors, row cap, lambdas, U* settings, k, alpha
+    gate = (BETA, GAMMA, 0, 1e-4, 256)  # method "direct"
+    gated_outs = [cand, g, local, score, align, iters, rs, g_iters, g_res]
+    if kind == "ungated":
+        outs = [cand, local, score, align, iters, rs]
+        args = [nat.f32(P), Q, TOP_K, None, *solve, *outs]
+    elif kind == "gated":
+        outs = gated_outs
+        args = [nat.f32(P), Q, TOP_K, None, None, *gate, *solve, *outs]
+    else:  # gate_mode 0; settle(1.0, 12, 1e-3), full detail, z_th 3, no cap; no graph fields
+        outs = gated_outs + [s_iters, s_res, *sums, total, offsets, ni, nj, nz, nr]
+        args = [nat.f32(P), Q, TOP_K, None, 0, None, *gate, *solve, 1.0, 12, 1e-3, 1, 3.0, 0, *outs, Q * TOP_K, None, None,
+                None, 2048]
+    args = [ptr[a.dtype](a) if isinstance(a, np.ndarray) else a for a in args]
+    fn = getattr(lib, AB_ENTRY[kind])
 
     def call():
-        rc = lib.osc_corpus_refine(h, nat.f32(P), Q, TOP_K, None, 6, 1.0, 1.0, 0.5, 4.0, 1e-4, 64, K_PICK, 0.5, nat.i32(cand),
-                                   nat.i32(local), nat.f32(score), nat.f32(align), nat.i32(iters), nat.f32(rs))
-        assert rc == 0
-        return local.copy(), score.copy()
+        assert fn(h, *args) == 0
+        return [o.copy() for o in outs]
 
     return call, lambda: lib.osc_corpus_destroy(h)
 
 
-def ungated_ab(parent_path, Y, P, reps):
-    """Parent build and this build, the same ungated call, alternating (so drift hits both alike)."""
+def parent_ab(parent_path, Y, P, reps, kind="ungated"):
+    """Parent build and this build, the same call (raw_refine's kind), alternating (so drift hits both alike)."""
     from oscillink_amd import _native as nat
 
-    mine, close_mine = raw_refine(C.CDLL(nat.LIB_PATH), Y, P)
-    theirs, close_theirs = raw_refine(C.CDLL(parent_path), Y, P)
+    mine, close_mine = raw_refine(C.CDLL(nat.LIB_PATH), Y, P, kind)
+    theirs, close_theirs = raw_refine(C.CDLL(parent_path), Y, P, kind)
     a, b = mine(), theirs()  # warm-up, and the answers are the same bytes
-    same = bool(np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]))
+    same = all(x.tobytes() == y.tobytes() for x, y in zip(a, b))
     tm, tp = [], []
     for _ in range(reps):
         t = time.perf_counter()
@@ -85,7 +105,7 @@ def ungated_ab(parent_path, Y, P, reps):
     close_mine()
     close_theirs()
     Q = P.shape[0]
-    out = {"parent": stats(tp, Q), "this": stats(tm, Q), "same_bytes": same, "reps": reps}
+    out = {"entry": AB_ENTRY[kind], "parent": stats(tp, Q), "this": stats(tm, Q), "same_bytes": same, "reps": reps}
     spread = out["parent"]["max_ms"] - out["parent"]["min_ms"]
     out["parent_spread_ms"] = spread
     out["not_slower"] = bool(out["this"]["batch_ms"] <= out["parent"]["batch_ms"] + spread)
@@ -99,7 +119,7 @@ def main():
     ap.add_argument("--Q", type=int, default=256)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--loop", type=int, default=32)
-    ap.add_argument("--parent-lib", default=None, help="liboscillink_hip.so built from the parent commit (ungated A/B)")
+    ap.add_argument("--parent-lib", default=None, help="liboscillink_hip.so built from the parent commit (ungated and gated A/B)")
     ap.add_argument("--profile", action="store_true", help="only the gated and the ungated batch (profiler run)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "refine_gated_bench.json"))
     a = ap.parse_args()
@@ -144,7 +164,8 @@ def main():
         rec["target_ratio"] = 1.0 / 20.0
     c.close()
     if a.parent_lib and not a.profile:
-        rec["ungated_ab"] = ungated_ab(a.parent_lib, Y, P, max(5, a.reps))
+        rec["ungated_ab"] = parent_ab(a.parent_lib, Y, P, max(5, a.reps))
+        rec["gated_ab"] = parent_ab(a.parent_lib, Y, P, max(5, a.reps), "gated")
     line = json.dumps(rec)
     print(line)
     if not a.profile:

@@ -6,8 +6,8 @@ library's own stream synchronisation before it returns, so each clock read follo
 warmed up once; the figures are the median of --reps calls with min and max.  Writes profiles/refine_receipts_bench.json.
 
     python scripts/bench_refine_receipts.py [--N 100000 --D 768 --reps 5 --loop 32]
-    python scripts/bench_refine_receipts.py --parent-lib PATH   # also: receipts=None, this build against the library built
-                                                                # from the parent commit, alternating in one process
+    python scripts/bench_refine_receipts.py --parent-lib PATH   # also: receipts=None and "full", this build against the library
+                                                                # built from the parent commit, alternating in one process
     python scripts/bench_refine_receipts.py --profile --reps 3  # the run to put under rocprofv3 --kernel-trace --stats"""
 import argparse
 import json
@@ -21,7 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
 
-from bench_refine_gated import BETA, GAMMA, K_PICK, TOP_K, stats, timed, ungated_ab  # noqa: E402
+from bench_refine_gated import BETA, GAMMA, K_PICK, TOP_K, parent_ab, stats, timed  # noqa: E402
 
 
 def main():
@@ -31,7 +31,7 @@ def main():
     ap.add_argument("--Q", type=int, default=256)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--loop", type=int, default=32)
-    ap.add_argument("--parent-lib", default=None, help="liboscillink_hip.so built from the parent commit (receipts=None A/B)")
+    ap.add_argument("--parent-lib", default=None, help="liboscillink_hip.so built from the parent commit (receipts=None and \"full\" A/B)")
     ap.add_argument("--profile", action="store_true", help="only the batches (profiler run)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "refine_receipts_bench.json"))
     a = ap.parse_args()
@@ -88,7 +88,8 @@ def main():
         rec["target_ratio"] = 1.0 / 20.0
     c.close()
     if a.parent_lib and not a.profile:
-        rec["plain_ab"] = ungated_ab(a.parent_lib, Y, P, max(5, a.reps))
+        rec["plain_ab"] = parent_ab(a.parent_lib, Y, P, max(5, a.reps))
+        rec["full_ab"] = parent_ab(a.parent_lib, Y, P, max(5, a.reps), "receipts")
     line = json.dumps(rec)
     print(line)
     if not a.profile:
