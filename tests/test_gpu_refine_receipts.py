@@ -161,13 +161,14 @@ def rounding_floor(Yc, psi, kw):
 
 
 def check_against_loop(amd, Y, P, top_k, k, alpha, kw, gate_kw, tag, queries=None, exact_zero=False,
-                       allow_iter_exception=False):
-    """Check 5 for one case.  gate_kw: {} or refine_many's gates arguments; in gated cases the loop gets the batch's gates."""
+                       allow_iter_exception=False, settle_dt=1.0):
+    """Check 5 for one case.  gate_kw: {} or refine_many's gates arguments; in gated cases the loop gets the batch's gates.
+    settle_dt: the step of both the batch's settle and the loop's."""
     with amd.Corpus(Y) as c:
         info = c.info(top_k, kw.get("kneighbors", 6), k)
         plain = c.refine_many(P, top_k, k, alpha, as_arrays=True, **kw, **gate_kw)
-        arr = c.refine_many(P, top_k, k, alpha, as_arrays=True, receipts="full", **kw, **gate_kw)
-        dcts = c.refine_many(P, top_k, k, alpha, receipts="full", **kw, **gate_kw)
+        arr = c.refine_many(P, top_k, k, alpha, as_arrays=True, receipts="full", settle_dt=settle_dt, **kw, **gate_kw)
+        dcts = c.refine_many(P, top_k, k, alpha, receipts="full", settle_dt=settle_dt, **kw, **gate_kw)
         assert c.info(top_k, kw.get("kneighbors", 6), k) == info
         again = c.refine_many(P, top_k, k, alpha, as_arrays=True, **kw, **gate_kw)
     for key in plain:  # receipts=None after a receipts call: the same bytes as before it
@@ -181,7 +182,7 @@ def check_against_loop(amd, Y, P, top_k, k, alpha, kw, gate_kw, tag, queries=Non
     for q in (range(P.shape[0]) if queries is None else queries):
         cand = arr["candidates"][q]
         gates = arr["gates"][q] if gate_kw else None
-        lp = loop(amd, Y[cand], P[q], k, alpha, kw, gates=gates)
+        lp = loop(amd, Y[cand], P[q], k, alpha, kw, gates=gates, settle=(settle_dt, 12, 1e-3))
         n, t = check_query(tag, q, arr, dcts[q], lp, exact_zero=exact_zero, allow_iter_exception=allow_iter_exception)
         rows += n
         near += t
@@ -209,14 +210,14 @@ def test_receipts_against_loop_gated(amd, top_k, k, kw, beta, gamma):
         assert given[key].tobytes() == first[key].tobytes(), key
 
 
-def oracle_receipt(Yc, psi, kw, gates, graph):
+def oracle_receipt(Yc, psi, kw, gates, graph, settle_dt=1.0):
     """The oracle's settle / U* / deltaH / components / nulls on the device's candidate graph."""
     from oracle import oscillink_oracle as orc
 
     lk = yg.lattice_kw(kw)
     ref = orc.OracleLattice(Yc, graph=yg.dense_adj(graph, Yc.shape[0]).astype(np.float32), **lk)
     ref.set_query(psi, gates=gates)
-    s = dict(ref.settle(dt=1.0, max_iters=12, tol=1e-3))
+    s = dict(ref.settle(dt=settle_dt, max_iters=12, tol=1e-3))
     Us = ref.solve_Ustar()
     dH = float(ref.deltaH(Us))
     coh, anc, qry = ref.components(Us)
