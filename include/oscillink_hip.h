@@ -293,6 +293,35 @@ int osc_corpus_refine_receipts(osc_corpus_handle h, const float* psis, int32_t Q
                                int32_t* null_total, int64_t* null_offsets, int32_t* null_i, int32_t* null_j, float* null_z,
                                float* null_r, int64_t null_capacity, int64_t* nnz_out, int64_t* edge_prefix,
                                int32_t* edge_prefix_n, int32_t edge_prefix_cap);
+/* osc_corpus_refine_receipts with a chain prior on the candidate lattices -- the loop with
+ * `lat.add_chain(chain, lamP, weights)` after construction and `lat.chain_receipt(chain, chain_z_th)` appended
+ * (lattice.py:129-149, 466-528; graph.py:96-111; examples/quickstart.py:14-23, scripts/benchmark.py:60-83).  The superset of
+ * the three refine entries: everything osc_corpus_refine_receipts takes and returns, with detail -1 = no settle and no
+ * receipt (their outputs may be NULL), and the chain block: query q's chain is chain_nodes[chain_offsets[q],
+ * chain_offsets[q + 1]) (chain_offsets Q + 1, from 0), local row ids of its candidate lattice, 2 .. 1024 of them, or an empty
+ * range for a lattice without a chain; chain_weights NULL (ones) or one finite weight per chain edge, flat in query order
+ * (query q's start at chain_offsets[q] - the number of chains before q).  Repeated nodes, revisited edges (the largest weight
+ * is kept) and self-steps mean what they mean in build_path_laplacian.  One lamP >= 0 for the call.  For a lattice with a
+ * chain the U* and settle operators gain lamP L_path (while lamP > 0), the Jacobi diagonal gains lamP, deltaH the path term.
+ * A lattice without a chain, and one with a chain at lamP = 0, return what osc_corpus_refine_receipts returns, bit for bit.
+ * Out, chain receipt from U*: chain_z_struct / chain_z_path / chain_r_struct / chain_r_path per chain edge (flat, laid out as
+ * chain_weights); per query chain_gain (fp64, edge order), chain_verdict (all max(z) <= chain_z_th), chain_weakest_k (first
+ * edge whose max(z) exceeds every earlier one, from -1; unwritten for a lattice without a chain when no query has one) and
+ * chain_weakest_z.  If no query has a chain, the kernels of osc_corpus_refine_receipts run and no chain output is written. */
+int osc_corpus_refine_chains(osc_corpus_handle h, const float* psis, int32_t Q, int32_t top_k, const int32_t* cand_in,
+                             int32_t gate_mode, const float* gates_in, float beta, float gamma, int32_t method,
+                             float gate_tol, int32_t gate_max_iters, int32_t kneighbors, float row_cap, float lamG, float lamC,
+                             float lamQ, float tol, int32_t max_iters, int32_t k, float alpha, float dt,
+                             int32_t settle_max_iters, float settle_tol, int32_t detail, float z_th, int32_t null_cap,
+                             const int64_t* chain_offsets, const int32_t* chain_nodes, const float* chain_weights, float lamP,
+                             float chain_z_th, int32_t* cand_out, float* gates_out, int32_t* local, float* score,
+                             float* align, int32_t* iters, float* res, int32_t* gate_iters, float* gate_res,
+                             int32_t* settle_iters, float* settle_res, double* dH, double* coh_sum, double* anchor_sum,
+                             double* query_sum, int32_t* null_total, int64_t* null_offsets, int32_t* null_i, int32_t* null_j,
+                             float* null_z, float* null_r, int64_t null_capacity, int64_t* nnz_out, int64_t* edge_prefix,
+                             int32_t* edge_prefix_n, int32_t edge_prefix_cap, float* chain_z_struct, float* chain_z_path,
+                             float* chain_r_struct, float* chain_r_path, double* chain_gain, int32_t* chain_verdict,
+                             int32_t* chain_weakest_k, float* chain_weakest_z);
 /* The candidate lattice's graph of one query (mutual_knn_adj + row_sum_cap + normalized_laplacian, graph.py:8-93) as
  * osc_get_csr gives it for `Oscillink(Y[cand])`: rowptr K + 1, col / a / w nnz (<= capacity), sqrt_deg K; local row ids.
  * Test / diagnostic aid. */

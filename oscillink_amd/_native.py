@@ -92,6 +92,14 @@ SIGNATURES = {
                                              c_f32p, c_f32p, c_i32p, c_f32p, c_i32p, c_f32p, c_i32p, c_f32p, c_f64p, c_f64p,
                                              c_f64p, c_f64p, c_i32p, c_i64p, c_i32p, c_i32p, c_f32p, c_f32p, C.c_int64,
                                              c_i64p, c_i64p, c_i32p, C.c_int32]),
+    "osc_corpus_refine_chains": (C.c_int, [Handle, c_f32p, C.c_int32, C.c_int32, c_i32p, C.c_int32, c_f32p, C.c_float,
+                                           C.c_float, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_float, C.c_float,
+                                           C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_float, C.c_float,
+                                           C.c_int32, C.c_float, C.c_int32, C.c_float, C.c_int32, c_i64p, c_i32p, c_f32p,
+                                           C.c_float, C.c_float, c_i32p, c_f32p, c_i32p, c_f32p, c_f32p, c_i32p, c_f32p,
+                                           c_i32p, c_f32p, c_i32p, c_f32p, c_f64p, c_f64p, c_f64p, c_f64p, c_i32p, c_i64p,
+                                           c_i32p, c_i32p, c_f32p, c_f32p, C.c_int64, c_i64p, c_i64p, c_i32p, C.c_int32,
+                                           c_f32p, c_f32p, c_f32p, c_f32p, c_f64p, c_i32p, c_i32p, c_f32p]),
     "osc_corpus_graph": (C.c_int, [Handle, c_f32p, c_i32p, C.c_int32, C.c_int32, C.c_float, c_i32p, c_i64p, c_i32p, c_f32p,
                                    c_f32p, c_f32p, C.c_int64, c_i64p]),
     "osc_deltaH": (C.c_int, [Handle, c_f64p]),

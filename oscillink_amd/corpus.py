@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import hashlib
+import operator
 import os
 from typing import Any, Optional
 
@@ -24,6 +25,7 @@ GATE_METHODS = {"direct": 0, "cg": 1}  # osc_corpus_gates' method codes
 RECEIPT_DETAILS = {"light": 0, "full": 1}  # osc_corpus_refine_receipts' detail codes (set_receipt_detail's words)
 RECEIPT_Z_TH = 3.0  # receipt()'s null-point threshold
 EDGE_PREFIX = 2048  # edges under the state signature (OscillinkLattice._edge_prefix)
+MAX_CHAIN = 1024  # nodes of one query's chain (include/oscillink_hip.h)
 
 
 class _RefineOut:
@@ -195,6 +197,77 @@ class Corpus:
                 float(settle_tol))
 
     @staticmethod
+    def _chains(chains, chain_weights, lamP, chain_z_th, Q: int, K: int):
+        """refine_many's chain arguments, checked as add_chain checks them (with the query index in front), as the entry
+        point's chain block: None without chains, else a dict of `offsets` int64 (Q + 1, over nodes), `nodes` int32,
+        `weights` float32 per chain edge or None, `edge_offsets` int64 (Q + 1), `lists` (per query the chain or None),
+        `lamP` and `z_th`."""
+        if chains is None:
+            if chain_weights is not None:
+                raise ValueError("chain_weights given without chains")
+            return None
+        if float(lamP) < 0 or not np.isfinite(float(lamP)):
+            raise ValueError("lamP must be >= 0")
+        if not np.isfinite(float(chain_z_th)):
+            raise ValueError("chain_z_th must be finite")
+        if isinstance(chains, np.ndarray) and chains.ndim == 2:
+            if chains.shape[0] != Q or (chains.size and not np.issubdtype(chains.dtype, np.integer)):
+                raise ValueError(f"chains must hold {Q} entries (None or a sequence of integers each), or be a ({Q}, L) "
+                                 f"integer array; got an array of shape {chains.shape}, dtype {chains.dtype}")
+            chains = list(chains)
+        try:
+            n = len(chains)
+        except TypeError:
+            n = -1
+        if n != Q:
+            raise ValueError(f"chains must hold {Q} entries (None or a sequence of integers each), or be a ({Q}, L) integer "
+                             f"array; got {n if n >= 0 else type(chains).__name__}")
+        if chain_weights is not None and len(chain_weights) != Q:
+            raise ValueError(f"chain_weights must be None or hold {Q} entries parallel to chains, got {len(chain_weights)}")
+        lists, wlists = [], []
+        for q in range(Q):
+            ch = chains[q]
+            w = None if chain_weights is None else chain_weights[q]
+            if ch is None:
+                if w is not None:
+                    raise ValueError(f"query {q}: weights given without a chain")
+                lists.append(None)
+                wlists.append(None)
+                continue
+            try:
+                ch = [int(operator.index(c)) for c in ch]
+            except TypeError:
+                raise ValueError(f"query {q}: chain must be None or a sequence of integers") from None
+            if any((c < 0 or c >= K) for c in ch):
+                raise ValueError(f"query {q}: chain indices out of bounds")
+            if len(ch) < 2:
+                raise ValueError(f"query {q}: chain must contain at least two indices")
+            if len(ch) > MAX_CHAIN:
+                raise ValueError(f"query {q}: a chain has at most {MAX_CHAIN} indices, got {len(ch)}")
+            if w is not None:
+                w = np.asarray(w, dtype=np.float32).reshape(-1)
+                if w.size != len(ch) - 1:
+                    raise ValueError(f"query {q}: weights length must equal len(chain)-1")
+                if not np.all(np.isfinite(w)):
+                    raise ValueError(f"query {q}: chain weights must be finite")
+            lists.append(ch)
+            wlists.append(w)
+        lens = np.array([0 if ch is None else len(ch) for ch in lists], dtype=np.int64)
+        offsets = np.zeros(Q + 1, dtype=np.int64)
+        np.cumsum(lens, out=offsets[1:])
+        edge_offsets = np.zeros(Q + 1, dtype=np.int64)
+        np.cumsum(np.maximum(lens - 1, 0), out=edge_offsets[1:])
+        nodes = np.array([c for ch in lists if ch is not None for c in ch], dtype=np.int32)
+        weights = None
+        if any(w is not None for w in wlists):
+            weights = np.ones(max(int(edge_offsets[-1]), 1), dtype=np.float32)  # None beside given weights: ones
+            for q, w in enumerate(wlists):
+                if w is not None:
+                    weights[int(edge_offsets[q]):int(edge_offsets[q + 1])] = w
+        return {"offsets": offsets, "nodes": nodes if nodes.size else np.zeros(1, dtype=np.int32), "weights": weights,
+                "edge_offsets": edge_offsets, "lists": lists, "lamP": float(lamP), "z_th": float(chain_z_th)}
+
+    @staticmethod
     def _warn_non_finite(gates: np.ndarray, iters: np.ndarray, res: np.ndarray, what: str) -> None:
         bad = np.nonzero(~np.all(np.isfinite(gates), axis=1))[0]
         if bad.size:  # compute_diffusion_gates hands such gates back with a warning as well
@@ -224,7 +297,8 @@ class Corpus:
                     as_arrays: bool = False, gates=None, gate_beta: float = 1.0, gate_gamma: float = 0.1,
                     gate_method: str = "direct", gate_tol: float = 1e-4, gate_max_iters: int = 256,
                     receipts: Optional[str] = None, settle_dt: float = 1.0, settle_max_iters: int = 12,
-                    settle_tol: float = 1e-3):
+                    settle_tol: float = 1e-3, chains=None, lamP: float = 0.2, chain_weights=None,
+                    chain_z_th: float = 2.5):
         """For each query q, what the reference's loop returns with `cand = search(psis, top_k)[0][q]` (or
         `candidates[q]`):
 
@@ -260,8 +334,23 @@ class Corpus:
         residual from the settle, ustar_* from the U* solve and meta["ustar_source"] = "corpus_batch".  Fields that describe
         one handle's clock or cache have no per-lattice meaning in a batch and are fixed: t_ms, ustar_solve_ms,
         graph_build_ms, last_settle_ms = 0.0, ustar_cached False, ustar_solves 1, ustar_cache_hits 0.  Not covered:
-        HMAC-signed receipts (a Corpus has no secret), chains on candidate lattices, OSCILLINK_RECEIPT_DYNAMICS, and
-        preconditioners other than "jacobi".  `receipts=None` is the call as it was."""
+        HMAC-signed receipts (a Corpus has no secret), OSCILLINK_RECEIPT_DYNAMICS, and preconditioners other than "jacobi".
+        `receipts=None` is the call as it was.
+
+        `chains` puts a chain prior on the candidate lattices (examples/quickstart.py:14-23, scripts/benchmark.py:60-83):
+        Q entries, each None or a sequence of 2 .. 1024 local row ids of the query's lattice -- positions in `candidates[q]`,
+        the search order -- or a (Q, L) integer array.  For a query with a chain everything returned is what the loop returns
+        with `lat.add_chain(chains[q], lamP=lamP, weights=chain_weights[q])` after construction (one `lamP` >= 0 for the
+        call; `chain_weights` None, or parallel to `chains` with None or len(chain) - 1 finite floats each), with or without
+        gates and receipts: U* and the settle gain lamP L_path, the Jacobi diagonal lamP, deltaH the path term, and
+        `state_sig` carries lamP, chain_present and chain_len.  A query whose entry is None is a lattice without a chain.
+        Per query with a chain `lat.chain_receipt(chains[q], z_th=chain_z_th)` is computed on the device from U*: with
+        `as_arrays=True` the dict gains `chain_offsets` int64 (Q + 1, over chain edges), `chain_z_struct`, `chain_z_path`,
+        `chain_r_struct`, `chain_r_path` float32 (flat), `chain_gain` float64, `chain_verdict` bool, `chain_weakest_k` int32
+        (-1 without a chain) and `chain_weakest_z` float32 (Q,); with `receipts` set and the dict form each query's dict
+        gains "chain_receipt" (chain_receipt()'s keys, local ids; None without a chain).  With `receipts=None` and the list
+        form the return value stays Q bundles: the chain acts through U* only.  `chains=None` adds no key and calls the
+        entry points called without it."""
         P = self._queries(psis)
         K = self._top_k(top_k)
         knn = self._knn(kneighbors, K)
@@ -288,6 +377,7 @@ class Corpus:
                 raise ValueError("gates must be finite")
             if np.any(gates_in < 0):
                 raise ValueError("gates must be >= 0")
+        chain = self._chains(chains, chain_weights, lamP, chain_z_th, Q, K)
         gated = gates is not None
         o = _RefineOut(Q, K, kk, gated)
         cand_arg = None if cand_in is None else nat.i32(cand_in)
@@ -296,12 +386,12 @@ class Corpus:
         gate_args = (beta, gamma, method, float(gate_tol), g_max)
         solve_args = (int(kneighbors), float(row_cap_val), float(lamG), float(lamC), float(lamQ), USTAR_TOL,
                       USTAR_MAX_ITERS, kk, float(alpha))
-        if detail is not None:
+        if detail is not None or chain is not None:
             return self._refine_receipts(P, o, top_k=top_k, knn=knn, cand_arg=cand_arg,
                                          mode=0 if not gated else (2 if gates_in is not None else 1), gates_arg=gates_arg,
                                          gate_args=gate_args, solve_args=solve_args, detail=detail,
                                          settle_args=(s_dt, s_max, s_tol), lam=[lamG, lamC, lamQ, 0.0],
-                                         deterministic_k=deterministic_k, as_arrays=as_arrays)
+                                         deterministic_k=deterministic_k, as_arrays=as_arrays, chain=chain)
         if Q and not gated:
             self._call("osc_corpus_refine", nat.f32(P), Q, int(top_k), cand_arg, *solve_args, *o.pointers(False))
         elif Q:
@@ -313,10 +403,12 @@ class Corpus:
         return arrays if as_arrays else o.bundles(ids)
 
     def _refine_receipts(self, P, o, *, top_k, knn, cand_arg, mode, gates_arg, gate_args, solve_args, detail,
-                         settle_args, lam, deterministic_k, as_arrays):
-        """refine_many with receipts, behind its validation: one osc_corpus_refine_receipts call, then the arrays or the
-        loop's dicts.  o = the result arrays; mode = the entry point's gate_mode; gate_args, solve_args and settle_args
-        (dt, max_iters, tol) = its argument runs of those names; lam = the state signature's lambdas, as given."""
+                         settle_args, lam, deterministic_k, as_arrays, chain=None):
+        """refine_many with receipts or chains, behind its validation: one osc_corpus_refine_receipts call (or, with
+        chains, one osc_corpus_refine_chains call), then the arrays or the loop's dicts.  o = the result arrays; mode = the
+        entry point's gate_mode; gate_args, solve_args and settle_args (dt, max_iters, tol) = its argument runs of those
+        names; detail = None (chains only: no settle, no receipt), 0 or 1; lam = the state signature's lambdas, as given;
+        chain = _chains' block or None."""
         from .lattice import OscillinkLattice, __version__
 
         Q, K = o.cand.shape
@@ -339,18 +431,32 @@ class Corpus:
         nj = np.zeros(max(capacity, 1), dtype=np.int32)
         nz = np.zeros(max(capacity, 1), dtype=np.float32)
         nr = np.zeros(max(capacity, 1), dtype=np.float32)
-        dicts = not as_arrays
+        dicts = not as_arrays and detail is not None
         nnz = np.zeros(Q, dtype=np.int64)
         pairs = np.zeros((Q if dicts else 0, EDGE_PREFIX, 2), dtype=np.int64)
         pairs_n = np.zeros(Q, dtype=np.int32)
-        if Q:
-            self._call("osc_corpus_refine_receipts", nat.f32(P), Q, int(top_k), cand_arg, mode, gates_arg, *gate_args,
-                       *solve_args, *settle_args, detail, RECEIPT_Z_TH, cap_val, *o.pointers(True), nat.i32(s_iters),
-                       nat.f32(s_res),
-                       *[sums[t].ctypes.data_as(nat.c_f64p) for t in range(4)], nat.i32(total), nat.i64(offsets),
-                       nat.i32(ni), nat.i32(nj), nat.f32(nz), nat.f32(nr), int(capacity),
+        receipt_out = (nat.i32(s_iters), nat.f32(s_res), *[sums[t].ctypes.data_as(nat.c_f64p) for t in range(4)],
+                       nat.i32(total), nat.i64(offsets), nat.i32(ni), nat.i32(nj), nat.f32(nz), nat.f32(nr), int(capacity),
                        nat.i64(nnz) if dicts else None, nat.i64(pairs) if dicts else None,
                        nat.i32(pairs_n) if dicts else None, EDGE_PREFIX)
+        if chain is not None:
+            n_edges = int(chain["edge_offsets"][-1])
+            c_edge = np.zeros((4, max(n_edges, 1)), dtype=np.float32)  # z_struct, z_path, r_struct, r_path
+            c_gain = np.zeros(Q, dtype=np.float64)
+            c_verdict = np.zeros(Q, dtype=np.int32)
+            c_weak_k = np.full(Q, -1, dtype=np.int32)
+            c_weak_z = np.zeros(Q, dtype=np.float32)
+        if Q and chain is not None:
+            self._call("osc_corpus_refine_chains", nat.f32(P), Q, int(top_k), cand_arg, mode, gates_arg, *gate_args,
+                       *solve_args, *settle_args, -1 if detail is None else detail, RECEIPT_Z_TH, cap_val,
+                       nat.i64(chain["offsets"]), nat.i32(chain["nodes"]),
+                       None if chain["weights"] is None else nat.f32(chain["weights"]), chain["lamP"], chain["z_th"],
+                       *o.pointers(True), *receipt_out, *[nat.f32(c_edge[t]) for t in range(4)],
+                       c_gain.ctypes.data_as(nat.c_f64p), nat.i32(c_verdict), nat.i32(c_weak_k), nat.f32(c_weak_z))
+        elif Q:
+            self._call("osc_corpus_refine_receipts", nat.f32(P), Q, int(top_k), cand_arg, mode, gates_arg, *gate_args,
+                       *solve_args, *settle_args, detail, RECEIPT_Z_TH, cap_val, *o.pointers(True), *receipt_out)
+        if Q:
             if mode == 1:
                 self._warn_non_finite(g, g_iters, g_res, "refine_many")
         # the float32 rounding receipt() gives its energies (a float32 dH / np.sum over float32 rows)
@@ -358,12 +464,20 @@ class Corpus:
         kept = int(offsets[-1])
         ids, out = o.ids_and_arrays()
         if as_arrays:
-            out.update(settle_iters=s_iters, settle_res=s_res, deltaH=sums[0], coh_drop_sum=sums[1],
-                       anchor_pen_sum=sums[2], query_term_sum=sums[3])
+            if detail is not None:
+                out.update(settle_iters=s_iters, settle_res=s_res, deltaH=sums[0], coh_drop_sum=sums[1],
+                           anchor_pen_sum=sums[2], query_term_sum=sums[3])
             if full:
                 out.update(null_total=total.astype(np.int64), null_offsets=offsets, null_i=ni[:kept].copy(),
                            null_j=nj[:kept].copy(), null_z=nz[:kept].copy(), null_r=nr[:kept].copy())
+            if chain is not None:
+                out.update(chain_offsets=chain["edge_offsets"], chain_z_struct=c_edge[0, :n_edges].copy(),
+                           chain_z_path=c_edge[1, :n_edges].copy(), chain_r_struct=c_edge[2, :n_edges].copy(),
+                           chain_r_path=c_edge[3, :n_edges].copy(), chain_gain=c_gain, chain_verdict=c_verdict != 0,
+                           chain_weakest_k=c_weak_k, chain_weakest_z=c_weak_z)
             return out
+        if detail is None:  # chains without receipts, list form: the chain acts through U* only
+            return o.bundles(ids)
         detail_name = "full" if full else "light"
         ones = np.ones(K, dtype=np.float32)
         bundles = o.bundles(ids)
@@ -371,8 +485,10 @@ class Corpus:
         for q in range(Q):
             B = g[q] if gated else ones
             adj_sig = hashlib.sha256(np.ascontiguousarray(pairs[q, :int(pairs_n[q])]).tobytes()).hexdigest()
+            ch = None if chain is None else chain["lists"][q]
             sig = OscillinkLattice._signature_digest(
-                {"psi": np.round(P[q], 6).tolist(), "lam": lam, "chain_present": False, "chain_len": 0,
+                {"psi": np.round(P[q], 6).tolist(), "lam": lam if ch is None else [*lam[:3], chain["lamP"]],
+                 "chain_present": ch is not None, "chain_len": 0 if ch is None else len(ch),
                  "k": knn, "detk": bool(deterministic_k), "adj": adj_sig}, B)
             if full:
                 s, e = int(offsets[q]), int(offsets[q + 1])
@@ -417,6 +533,20 @@ class Corpus:
                 "meta": meta,
             }
             out.append({"bundle": bundles[q], "settle": {"iters": int(s_iters[q]), "res": float(s_res[q])}, "receipt": rec})
+            if chain is not None:
+                out[-1]["chain_receipt"] = None
+            if ch is not None:
+                e0 = int(chain["edge_offsets"][q])
+                wk = int(c_weak_k[q])
+                out[-1]["chain_receipt"] = {
+                    "verdict": bool(c_verdict[q]),
+                    "weakest_link": {"k": wk, "edge": [ch[wk], ch[wk + 1]] if wk >= 0 else [-1, -1],
+                                     "zscore": float(c_weak_z[q])},
+                    "coherence_gain": float(c_gain[q]),
+                    "edges": [{"k": t, "edge": [ch[t], ch[t + 1]], "z_struct": float(c_edge[0, e0 + t]),
+                               "z_path": float(c_edge[1, e0 + t]), "r_struct": float(c_edge[2, e0 + t]),
+                               "r_path": float(c_edge[3, e0 + t])} for t in range(len(ch) - 1)],
+                }
         return out
 
     def diffusion_gates_many(self, psis, top_k: int, *, kneighbors: int = 6, row_cap_val: float = 1.0, beta: float = 1.0,

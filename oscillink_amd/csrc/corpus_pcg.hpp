@@ -45,6 +45,50 @@ struct CqPcgArgs {
   float dt;           // the settle's step (the solve ignores it)
 };
 
+// the chain priors of one chunk: per lattice the int and float records host::pack_chain fills
+// (corpus_chain.hpp).  n_edges = 0: the lattice has no chain
+struct CqChain {
+  const int32_t* ints;  // nq x int_words: [n_edges, n_rows, nodes[cap + 1], rows[R], ptr[R + 1], col[2 cap]], local ids
+  const float* flts;    // nq x 4 cap: [a[2 cap], w[2 cap]]
+  int32_t int_words, cap, rows_at, ptr_at, col_at;
+  float lamP;
+  __device__ __forceinline__ const int32_t* rec(int lat) const { return ints + (size_t)lat * int_words; }
+  __device__ __forceinline__ const float* a(int lat) const { return flts + (size_t)lat * 4 * cap; }
+  __device__ __forceinline__ const float* w(int lat) const { return flts + (size_t)lat * 4 * cap + 2 * cap; }
+};
+
+// what cq_pcg's path hook reads: (L_path v)_i = v_i - sum_p w_p v_col(p) over row i's path entries; the v_i part is in the
+// policy's cs(i), this is the sum.  s_slot (LDS): local row -> its path row, or -1 (every row when the hook is inactive)
+struct CqPathRows {
+  const int32_t* s_slot;
+  const int32_t* ptr;
+  const int32_t* col;  // local ids
+  const float* w;
+  float cP;            // lamP for the solve, dt lamP for the settle
+};
+
+// fills s_slot for one lattice (the caller's barrier publishes it); active = the lattice has a chain and lamP > 0
+__device__ __forceinline__ void cq_path_slots(const CqChain& c, int lat, int K, bool active, int32_t* s_slot) {
+  const int32_t* rec = c.rec(lat);
+  for (int r = threadIdx.x; r < K; r += 256) s_slot[r] = -1;
+  __syncthreads();
+  if (active)
+    for (int t = threadIdx.x; t < rec[1]; t += 256) s_slot[rec[c.rows_at + t]] = t;
+}
+__device__ __forceinline__ CqPathRows cq_path_rows(const CqChain& c, int lat, const int32_t* s_slot, float cP) {
+  const int32_t* rec = c.rec(lat);
+  return CqPathRows{s_slot, rec + c.ptr_at, rec + c.col_at, c.w(lat), cP};
+}
+
+// a sa - b sb with both products rounded on their own (receipt_kernels.hip's sdiff), so that edge (i, j) and edge (j, i)
+// get bit-identical energies
+__device__ __forceinline__ float cq_sdiff(float a, float sa, float b, float sb) {
+#pragma clang fp contract(off)
+  const float p = a * sa;
+  const float q = b * sb;
+  return p - q;
+}
+
 __device__ __forceinline__ float wave_sum_f(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -85,6 +129,9 @@ void cq_with_nc(int32_t ldn, F&& f) {
 //   kFromY                      false: x0 is in a.X already; true: x0 = Y, read from there and stored to a.X by INIT
 //   rhs(y, qb_i, psi_c)         the right-hand side from the anchor entry, written out by the policy so that its operands
 //                               and association are its own
+//   kPath                       true: the policy has a CqPathRows `path`, and rows with path entries get
+//                               - path.cP sum_p w_p v_col(p) on top (a chain prior; its diagonal part is in cs(i)).  A
+//                               compile-time switch: the kPath = false instantiations hold no trace of it
 // red: four floats of LDS.  Writes a.X, a.R, a.P, a.AP and, from thread 0, a.iters / a.res of the lattice.
 template <int NC, class Op>
 __device__ __forceinline__ void cq_pcg(const CqPcgArgs& a, const Op& op, float* red) {
@@ -115,6 +162,22 @@ __device__ __forceinline__ void cq_pcg(const CqPcgArgs& a, const Op& op, float* 
     const float csi = op.cs(i);
 #pragma unroll
     for (int m = 0; m < NC; ++m) out[m] = csi * v[i * g.ldn + cidx[m]] - op.cW * acc[m];
+    if constexpr (Op::kPath) {
+      const int ps = op.path.s_slot[i - r0];
+      if (ps >= 0) {
+        float accp[NC];
+#pragma unroll
+        for (int m = 0; m < NC; ++m) accp[m] = 0.f;
+        for (int e = op.path.ptr[ps]; e < op.path.ptr[ps + 1]; ++e) {
+          const int64_t j = r0 + op.path.col[e];
+          const float wp = op.path.w[e];
+#pragma unroll
+          for (int m = 0; m < NC; ++m) accp[m] = fmaf(wp, v[j * g.ldn + cidx[m]], accp[m]);
+        }
+#pragma unroll
+        for (int m = 0; m < NC; ++m) out[m] = fmaf(-op.path.cP, accp[m], out[m]);
+      }
+    }
   };
   double rz[NC], t1[NC], t2[NC];
 #pragma unroll

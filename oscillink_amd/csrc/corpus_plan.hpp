@@ -45,7 +45,20 @@ struct CorpusLayout {
   int64_t r_sums;            // double [nq][4]      deltaH, coh_drop, anchor_pen, query_term
   int64_t n_total, n_kept;   // int32  [nq]         null points found / written (the cap)
   int64_t n_i, n_j, n_z, n_r;  // int32 / int32 / float / float [nq][null_slots] the kept null points, local ids
+  // chains (a path prior and a chain receipt per lattice): behind everything above, and only when the call has chains --
+  // all zero otherwise, total unchanged.  E = chain_cap, the largest edge count of the call's chains
+  int64_t c_int;             // int32  [nq][chain_int_words(K, E)]  corpus_chain.hpp's int record
+  int64_t c_flt;             // float  [nq][4 E]                    its float record
+  int64_t c_edge;            // float  [nq][4][E]                   z_struct, z_path, r_struct, r_path per chain edge
+  int64_t c_gain;            // double [nq]                         coherence gain
+  int64_t c_verdict, c_weak_k;  // int32 [nq]
+  int64_t c_weak_z;          // float  [nq]
 };
+
+// words of one query's chain records (corpus_chain.hpp packs them)
+inline int64_t corpus_chain_int_words(int32_t K, int32_t cap) {
+  return 2 + ((int64_t)cap + 1) + 2 * (int64_t)std::min(K, cap + 1) + 1 + 2 * (int64_t)cap;
+}
 
 // null-point slots per query of a receipts call: none in light detail, else K, or the cap when one is set
 inline int32_t corpus_null_slots(int32_t K, bool full, int32_t null_cap) {
@@ -53,9 +66,10 @@ inline int32_t corpus_null_slots(int32_t K, bool full, int32_t null_cap) {
   return null_cap > 0 ? std::min(null_cap, K) : K;
 }
 
-// receipts = false: the layout of a plain / gated refine (null_slots ignored).  receipts = true adds the blocks above.
+// receipts = false: the layout of a plain / gated refine (null_slots ignored).  receipts = true adds the receipts blocks,
+// chain_cap > 0 the chain blocks.
 inline CorpusLayout corpus_layout(int64_t N, int32_t ldn, int32_t K, int32_t k, int32_t kk, int32_t nq, bool receipts = false,
-                                  int32_t null_slots = 0) {
+                                  int32_t null_slots = 0, int32_t chain_cap = 0) {
   CorpusLayout L{};
   const int64_t rows = (int64_t)nq * K, lds = corpus_lds(K);
   int64_t o = 0;
@@ -104,6 +118,15 @@ inline CorpusLayout corpus_layout(int64_t N, int32_t ldn, int32_t K, int32_t k, 
     L.n_z = take((int64_t)nq * slots * 4);
     L.n_r = take((int64_t)nq * slots * 4);
   }
+  if (chain_cap > 0) {
+    L.c_int = take((int64_t)nq * corpus_chain_int_words(K, chain_cap) * 4);
+    L.c_flt = take((int64_t)nq * 4 * chain_cap * 4);
+    L.c_edge = take((int64_t)nq * 4 * chain_cap * 4);
+    L.c_gain = take((int64_t)nq * 8);
+    L.c_verdict = take((int64_t)nq * 4);
+    L.c_weak_k = take((int64_t)nq * 4);
+    L.c_weak_z = take((int64_t)nq * 4);
+  }
   L.total = o;
   return L;
 }
@@ -111,12 +134,12 @@ inline CorpusLayout corpus_layout(int64_t N, int32_t ldn, int32_t K, int32_t k, 
 // queries per chunk: the requested count (OSC_CORPUS_CHUNK, else kCorpusDefaultChunk), lowered until one chunk's scratch
 // fits the budget; at least 1 (a single query over budget still runs: its scratch is what it is)
 inline int32_t corpus_chunk(int64_t N, int32_t ldn, int32_t K, int32_t k, int32_t kk, int32_t requested, int64_t budget,
-                            bool receipts = false, int32_t null_slots = 0) {
+                            bool receipts = false, int32_t null_slots = 0, int32_t chain_cap = 0) {
   int32_t nq = std::max<int32_t>(1, requested);
-  const int64_t one = corpus_layout(N, ldn, K, k, kk, 1, receipts, null_slots).total;
+  const int64_t one = corpus_layout(N, ldn, K, k, kk, 1, receipts, null_slots, chain_cap).total;
   const int64_t fit = std::max<int64_t>(1, budget / std::max<int64_t>(1, one));
   nq = (int32_t)std::min<int64_t>(nq, fit);
-  while (nq > 1 && corpus_layout(N, ldn, K, k, kk, nq, receipts, null_slots).total > budget) --nq;
+  while (nq > 1 && corpus_layout(N, ldn, K, k, kk, nq, receipts, null_slots, chain_cap).total > budget) --nq;
   return nq;
 }
 

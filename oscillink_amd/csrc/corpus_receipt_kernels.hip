@@ -1,6 +1,8 @@
 // Settle and receipt of every candidate lattice of a corpus refine chunk, behind the U* solve and
 // the bundle of osc_corpus.hip: k_cq_settle (one implicit-Euler step from U = Y) and k_cq_receipt (deltaH, the component
 // sums, the null points), one workgroup per lattice each.  No workgroup waits on another.
+// k_cq_settle_chain and k_cq_receipt<true> are the same two for a call with chains: lamP L_path in
+// the operator.  A call without chains launches k_cq_settle and k_cq_receipt<false> only.
 #include "common.hpp"
 #include "corpus_receipts.hpp"
 
@@ -14,7 +16,7 @@ struct CqSettleOp {
   const float* s_qb;
   int64_t r0;
   float cW, rbY;
-  static constexpr bool kFromY = true;
+  static constexpr bool kFromY = true, kPath = false;
   __device__ __forceinline__ float cs(int64_t i) const { return s_cs[i - r0]; }
   __device__ __forceinline__ float inv_diag(int64_t i) const { return s_inv[i - r0]; }
   __device__ __forceinline__ float qb(int64_t i) const { return s_qb[i - r0]; }
@@ -53,14 +55,42 @@ __global__ __launch_bounds__(256) void k_cq_settle(const CqPcgArgs a) {
   cq_pcg<NC>(a, CqSettleOp{s_cs, s_inv, s_qb, r0, cW, rbY}, red);
 }
 
-// receipt_kernels.hip's sdiff: a sa - b sb with both products rounded on their own, so that edge (i, j) and edge (j, i) get
-// bit-identical energies
-__device__ __forceinline__ float cq_sdiff(float a, float sa, float b, float sb) {
-#pragma clang fp contract(off)
-  const float p = a * sa;
-  const float q = b * sb;
-  return p - q;
+// the same step of a lattice with a chain prior (lattice.py:180-181, 187-191): the operator gains dt lamP L_path while
+// lamP > 0 -- its diagonal part in the rows' constants, the rest through cq_pcg's path hook -- and the Jacobi diagonal gains
+// dt lamP whenever a chain is present.  Each is added to the chainless expression, so a lattice without a chain, or with one
+// at lamP = 0, gets k_cq_settle's bytes.
+struct CqChainSettleOp : CqSettleOp {
+  static constexpr bool kPath = true;
+  CqPathRows path;
+};
+
+template <int NC>
+__global__ __launch_bounds__(256) void k_cq_settle_chain(const CqChainPcgArgs ca) {
+  __shared__ float red[4];
+  __shared__ float s_cs[host::kCorpusMaxTopK], s_inv[host::kCorpusMaxTopK], s_qb[host::kCorpusMaxTopK];
+  __shared__ int32_t s_slot[host::kCorpusMaxTopK];
+  const CqPcgArgs& a = ca.pcg;
+  const CqLattice& g = a.lat;
+  const int tid = threadIdx.x, lat = blockIdx.x;
+  const int64_t r0 = (int64_t)lat * g.K;
+  const bool present = ca.chain.rec(lat)[0] > 0, active = present && ca.chain.lamP > 0.f;
+  const float cW = a.dt * g.lamC, rbY = cq_rounded_mul(a.dt, g.lamG), cQ = a.dt * g.lamQ;
+  const float cP = active ? cq_rounded_mul(a.dt, ca.chain.lamP) : 0.f;
+  const float dP = present ? cq_rounded_mul(a.dt, ca.chain.lamP) : 0.f;
+  cq_path_slots(ca.chain, lat, g.K, active, s_slot);
+  for (int r = tid; r < g.K; r += 256) {
+    const float Bi = g.B ? g.B[r0 + r] : 1.0f;
+    const float cs = fmaf(cQ, Bi, 1.0f + a.dt * (g.lamG + g.lamC));
+    s_cs[r] = active ? cs + cP : cs;
+    s_inv[r] = 1.f / (fmaf(cQ, Bi, present ? (1.0f + rbY) + dP : 1.0f + rbY) + 1e-12f);
+    s_qb[r] = cQ * Bi;
+  }
+  __syncthreads();
+  cq_pcg<NC>(a, CqChainSettleOp{{s_cs, s_inv, s_qb, r0, cW, rbY}, cq_path_rows(ca.chain, lat, s_slot, cP)}, red);
 }
+
+__device__ __forceinline__ const CqReceiptArgs& cq_receipt_args(const CqReceiptArgs& a) { return a; }
+__device__ __forceinline__ const CqReceiptArgs& cq_receipt_args(const CqChainReceiptArgs& a) { return a.rec; }
 
 // receipt() of one lattice per workgroup (lattice.py receipt(), receipts.py:10-83), a wave per row:
 //   deltaH   = sum_i E_i . (M E)_i, E = U+ - U*, M the U* operator (lamG + lamC + lamQ B_i on the diagonal, -lamC W off it)
@@ -70,7 +100,11 @@ __device__ __forceinline__ float cq_sdiff(float a, float sa, float b, float sb) 
 // The per-row values meet in LDS; each of the four sums is then added up in fp64 in row order by one thread, and the null
 // points are written in local row order -- or, when there are more than the cap, the cap highest z in receipt()'s order (z
 // descending, then row ascending: a rank count over the at most 1024 rows in LDS).  Nothing but the lattice enters.
-__global__ __launch_bounds__(256) void k_cq_receipt(const CqReceiptArgs a) {
+// CHAIN (a call with chains): M gains lamP L_path for a lattice whose chain is active (lamP > 0) -- lamP on the diagonal and
+// the row's path entries in the deltaH pass; everything else reads U* alone and stays as it is.
+template <bool CHAIN>
+__global__ __launch_bounds__(256) void k_cq_receipt(const std::conditional_t<CHAIN, CqChainReceiptArgs, CqReceiptArgs> args) {
+  const CqReceiptArgs& a = cq_receipt_args(args);
   __shared__ float s_psi[kCqMaxCols];
   __shared__ double s_dh[kCqMaxRows];
   __shared__ float s_coh[kCqMaxRows], s_anc[kCqMaxRows], s_qry[kCqMaxRows], s_nz[kCqMaxRows], s_nr[kCqMaxRows];
@@ -82,12 +116,26 @@ __global__ __launch_bounds__(256) void k_cq_receipt(const CqReceiptArgs a) {
   const int64_t r0 = (int64_t)lat * K;
   const float* psi = g.psi + (size_t)lat * g.ldn;
   for (int c = tid; c < g.ldn; c += 256) s_psi[c] = psi[c];
+  [[maybe_unused]] CqPathRows path{};
+  [[maybe_unused]] bool active = false;
+  if constexpr (CHAIN) {
+    __shared__ int32_t s_slot[kCqMaxRows];
+    const CqChain& ch = args.chain;
+    active = ch.rec(lat)[0] > 0 && ch.lamP > 0.f;
+    cq_path_slots(ch, lat, K, active, s_slot);
+    path = cq_path_rows(ch, lat, s_slot, active ? ch.lamP : 0.f);
+  }
   __syncthreads();
   for (int r = wave; r < K; r += 4) {
     const int64_t i = r0 + r;
     const size_t io = (size_t)i * g.ldn;
     const float Bi = g.B ? g.B[i] : 1.0f;
-    const float cs = fmaf(g.lamQ, Bi, g.lamG + g.lamC);
+    float cs = fmaf(g.lamQ, Bi, g.lamG + g.lamC);
+    [[maybe_unused]] int ps = -1;
+    if constexpr (CHAIN) {
+      if (active) cs = cs + path.cP;
+      ps = path.s_slot[r];
+    }
     const int d = g.deg[i];
     const int32_t* crow = g.col + i * g.k;
     double dh = 0.0;
@@ -98,7 +146,17 @@ __global__ __launch_bounds__(256) void k_cq_receipt(const CqReceiptArgs a) {
         const size_t jo = (size_t)crow[e] * g.ldn + c;
         acc = fmaf(g.w[i * g.k + e], a.Up[jo] - a.Us[jo], acc);
       }
-      const float me = cs * ei - g.lamC * acc;
+      float me = cs * ei - g.lamC * acc;
+      if constexpr (CHAIN) {
+        if (ps >= 0) {
+          float accp = 0.f;
+          for (int e = path.ptr[ps]; e < path.ptr[ps + 1]; ++e) {
+            const size_t jo = (size_t)(r0 + path.col[e]) * g.ldn + c;
+            accp = fmaf(path.w[e], a.Up[jo] - a.Us[jo], accp);
+          }
+          me = fmaf(-path.cP, accp, me);
+        }
+      }
       dh += (double)ei * (double)me;
     }
     dh = wave_sum_d(dh);
@@ -231,7 +289,19 @@ void launch_cq_settle(const CqPcgArgs& a, int32_t nq, hipStream_t s) {
 }
 
 void launch_cq_receipt(const CqReceiptArgs& a, int32_t nq, hipStream_t s) {
-  hipLaunchKernelGGL(k_cq_receipt, dim3((unsigned)nq), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_cq_receipt<false>, dim3((unsigned)nq), dim3(256), 0, s, a);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_cq_settle_chain(const CqChainPcgArgs& a, int32_t nq, hipStream_t s) {
+  cq_with_nc(a.pcg.lat.ldn, [&](auto nc) {
+    hipLaunchKernelGGL((k_cq_settle_chain<decltype(nc)::value>), dim3((unsigned)nq), dim3(256), 0, s, a);
+  });
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_cq_receipt_chain(const CqChainReceiptArgs& a, int32_t nq, hipStream_t s) {
+  hipLaunchKernelGGL(k_cq_receipt<true>, dim3((unsigned)nq), dim3(256), 0, s, a);
   HIP_CHECK(hipGetLastError());
 }
 

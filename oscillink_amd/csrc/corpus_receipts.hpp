@@ -21,8 +21,38 @@ struct CqReceiptArgs {
   float* n_r;
 };
 
+// a call with chains (osc_corpus_refine_chains): the same blocks with the chunk's chain records
+struct CqChainPcgArgs {
+  CqPcgArgs pcg;
+  CqChain chain;
+};
+struct CqChainReceiptArgs {
+  CqReceiptArgs rec;
+  CqChain chain;
+};
+
+constexpr int kCqMaxChainEdges = 1023;  // a chain has at most 1024 nodes
+
+// k_cq_chain_receipt: chain_receipt() of the lattice's own chain from U*
+struct CqChainEdgesArgs {
+  CqLattice lat;
+  CqChain chain;
+  const float* Us;      // U* (union rows x ldn)
+  float z_th;
+  float* edge;          // nq x 4 x cap: z_struct, z_path, r_struct, r_path per chain edge
+  double* gain;         // nq
+  int32_t* verdict;     // nq
+  int32_t* weak_k;      // nq: -1 without a chain (or when no edge's z exceeds -1: lattice.py:489)
+  float* weak_z;        // nq
+};
+
 // one workgroup per lattice, nq lattices
 void launch_cq_settle(const CqPcgArgs& a, int32_t nq, hipStream_t s);
 void launch_cq_receipt(const CqReceiptArgs& a, int32_t nq, hipStream_t s);
+// the chain instantiations (corpus_chain_kernels.hip, corpus_receipt_kernels.hip); only calls with chains launch them
+void launch_cq_solve_chain(const CqChainPcgArgs& a, int32_t nq, hipStream_t s);
+void launch_cq_settle_chain(const CqChainPcgArgs& a, int32_t nq, hipStream_t s);
+void launch_cq_receipt_chain(const CqChainReceiptArgs& a, int32_t nq, hipStream_t s);
+void launch_cq_chain_receipt(const CqChainEdgesArgs& a, int32_t nq, hipStream_t s);
 
 }  // namespace osc

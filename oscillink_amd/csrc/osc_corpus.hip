@@ -18,6 +18,9 @@
 //                  workgroup per lattice; its state takes the gathered Yn block, which nothing reads after the bundle
 //   k_cq_receipt : (receipts only) deltaH of the settled state against U*, and in full detail the three component sums and
 //                  the null points (cap applied in the workgroup), one workgroup per lattice
+//   (calls with chains only, DESIGN.md section 13.4: corpus_chain_kernels.hip)
+//   k_cq_solve_chain / k_cq_settle_chain / k_cq_receipt_chain : the three above with lamP L_path in the operator
+//   k_cq_chain_receipt : chain_receipt() of every lattice's own chain from U*, behind the bundle
 //
 // No workgroup waits on another: every kernel's workgroups are independent.  Every per-lattice kernel's arguments begin with
 // the same CqLattice block (corpus_pcg.hpp), which run_chunk fills once.
@@ -25,6 +28,7 @@
 #include "knn.hpp"
 #include "corpus_plan.hpp"
 #include "corpus_receipts.hpp"
+#include "corpus_chain.hpp"
 
 #include <cmath>
 #include <vector>
@@ -271,7 +275,7 @@ __global__ __launch_bounds__(256) void k_cq_gather(const float* Y, const float* 
 // the U* operator as cq_pcg's operator, B = 1 folded in: one constant, one inverse diagonal and lamQ for every row
 struct CqSolveOp {
   float cs_, inv_, cW, lamG, lamQ;
-  static constexpr bool kFromY = false;
+  static constexpr bool kFromY = false, kPath = false;
   __device__ __forceinline__ float cs(int64_t) const { return cs_; }
   __device__ __forceinline__ float inv_diag(int64_t) const { return inv_; }
   __device__ __forceinline__ float qb(int64_t) const { return lamQ; }
@@ -286,7 +290,7 @@ struct CqGatedSolveOp {
   const float* B;
   int64_t r0;
   float cW, lamG, lamQ;
-  static constexpr bool kFromY = false;
+  static constexpr bool kFromY = false, kPath = false;
   __device__ __forceinline__ float cs(int64_t i) const { return s_cs[i - r0]; }
   __device__ __forceinline__ float inv_diag(int64_t i) const { return s_inv[i - r0]; }
   __device__ __forceinline__ float qb(int64_t i) const { return lamQ * B[i]; }
@@ -685,13 +689,20 @@ struct RefineReq {
   int32_t receipts = 0;    // 0 = none, 1 = light, 2 = full: settle + receipt behind the bundle (stage 2 only)
   float s_dt = 1.f, s_tol = 1e-3f, z_th = 3.f;
   int32_t s_max_iters = 12, null_cap = 0, null_slots = 0;
+  // chains (osc_corpus_refine_chains): chain_cap = the largest edge count of the call's chains, 0 = a call without chains
+  int32_t chain_cap = 0;
+  const int64_t* c_off = nullptr;    // Q + 1 offsets into c_nodes; an empty range = no chain
+  const int32_t* c_nodes = nullptr;  // local row ids
+  const float* c_w = nullptr;        // per chain edge, at c_eoff, or nullptr (ones)
+  const int64_t* c_eoff = nullptr;   // Q + 1 offsets over chain edges
+  float lamP = 0.f, c_zth = 2.5f;
 };
 
 // one chunk [q0, q0 + nq): psi upload, candidates, and the requested stages in the order of the list at the top of this
 // file; returns the layout used
 host::CorpusLayout run_chunk(osc_corpus& c, const RefineReq& rq, int32_t q0, int32_t nq, int32_t cap_nq) {
   const int32_t K = rq.K, ldn = c.ldn, k = std::max(1, rq.knn), kk = std::max(1, rq.kk);
-  const host::CorpusLayout L = host::corpus_layout(c.N, ldn, K, k, kk, cap_nq, rq.receipts != 0, rq.null_slots);
+  const host::CorpusLayout L = host::corpus_layout(c.N, ldn, K, k, kk, cap_nq, rq.receipts != 0, rq.null_slots, rq.chain_cap);
   if ((int64_t)c.scratch.n < L.total) c.scratch.alloc((size_t)L.total);
   hipStream_t s = c.stream;
   const dim3 per_lattice((unsigned)nq), wg(256);
@@ -748,15 +759,37 @@ host::CorpusLayout run_chunk(osc_corpus& c, const RefineReq& rq, int32_t q0, int
     HIP_CHECK(hipMemcpyAsync(gates, rq.gates_in + (size_t)q0 * K, (size_t)rows * 4, hipMemcpyHostToDevice, s));
   }
   if (rq.stage == 1) return L;
+  // the chunk's chain records (a call with chains only)
+  const bool chains = rq.chain_cap > 0;
+  CqChain chain{};
+  if (chains) {
+    const int32_t cap = rq.chain_cap;
+    const int64_t iw = host::chain_int_words(K, cap), fw = host::chain_flt_words(cap);
+    std::vector<int32_t> hi((size_t)(nq * iw), 0);
+    std::vector<float> hf((size_t)(nq * fw), 0.f);
+    for (int32_t q = 0; q < nq; ++q) {
+      const int64_t b = rq.c_off[q0 + q], len = rq.c_off[q0 + q + 1] - b;
+      host::pack_chain(rq.c_nodes + b, rq.c_w ? rq.c_w + rq.c_eoff[q0 + q] : nullptr, (int32_t)len, K, cap,
+                       hi.data() + (size_t)(q * iw), hf.data() + (size_t)(q * fw));
+    }
+    HIP_CHECK(hipMemcpyAsync(at<int32_t>(c, L.c_int), hi.data(), hi.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(at<float>(c, L.c_flt), hf.data(), hf.size() * 4, hipMemcpyHostToDevice, s));
+    chain = CqChain{at<int32_t>(c, L.c_int), at<float>(c, L.c_flt), (int32_t)iw, cap, (int32_t)host::chain_rows_at(cap),
+                    (int32_t)host::chain_ptr_at(K, cap), (int32_t)host::chain_col_at(K, cap), rq.lamP};
+  }
   // solve: U* into X
   const CqPcgArgs sa{lat, X, at<float>(c, L.R), at<float>(c, L.P), at<float>(c, L.AP), at<int32_t>(c, L.iters),
                      at<float>(c, L.res), rq.max_iters, rq.tol, 0.f};
-  cq_with_nc(ldn, [&](auto nc) {
-    constexpr int NC = decltype(nc)::value;
-    if (rq.gate) hipLaunchKernelGGL((k_cq_solve<NC, true>), per_lattice, wg, 0, s, sa);
-    else hipLaunchKernelGGL((k_cq_solve<NC, false>), per_lattice, wg, 0, s, sa);
-  });
-  HIP_CHECK(hipGetLastError());
+  if (chains) {
+    launch_cq_solve_chain(CqChainPcgArgs{sa, chain}, nq, s);
+  } else {
+    cq_with_nc(ldn, [&](auto nc) {
+      constexpr int NC = decltype(nc)::value;
+      if (rq.gate) hipLaunchKernelGGL((k_cq_solve<NC, true>), per_lattice, wg, 0, s, sa);
+      else hipLaunchKernelGGL((k_cq_solve<NC, false>), per_lattice, wg, 0, s, sa);
+    });
+    HIP_CHECK(hipGetLastError());
+  }
   // bundle
   if (rq.kk > 0) {
     const BundleArgs ba{lat, X, Sm, lds, rq.kk, (double)rq.alpha, 0.5, at<int32_t>(c, L.o_local), at<float>(c, L.o_score),
@@ -764,6 +797,10 @@ host::CorpusLayout run_chunk(osc_corpus& c, const RefineReq& rq, int32_t q0, int
     hipLaunchKernelGGL(k_cq_bundle, per_lattice, wg, 0, s, ba);
     HIP_CHECK(hipGetLastError());
   }
+  if (chains)  // chain_receipt(): U* alone, no settle needed
+    launch_cq_chain_receipt(CqChainEdgesArgs{lat, chain, X, rq.c_zth, at<float>(c, L.c_edge), at<double>(c, L.c_gain),
+                                             at<int32_t>(c, L.c_verdict), at<int32_t>(c, L.c_weak_k),
+                                             at<float>(c, L.c_weak_z)}, nq, s);
   if (!rq.receipts) return L;
   // settle: the solve's R, P and AP again; the settled state takes Ync, dead since the graph, the gates and the bundle, and
   // U* stays in X
@@ -774,12 +811,14 @@ host::CorpusLayout run_chunk(osc_corpus& c, const RefineReq& rq, int32_t q0, int
   ta.max_iters = rq.s_max_iters;
   ta.tol = rq.s_tol;
   ta.dt = rq.s_dt;
-  launch_cq_settle(ta, nq, s);
+  if (chains) launch_cq_settle_chain(CqChainPcgArgs{ta, chain}, nq, s);
+  else launch_cq_settle(ta, nq, s);
   // receipt
   const CqReceiptArgs ra{lat, X, Ync, rq.receipts == 2, rq.null_cap, rq.null_slots, rq.z_th, at<double>(c, L.r_sums),
                          at<int32_t>(c, L.n_total), at<int32_t>(c, L.n_kept), at<int32_t>(c, L.n_i), at<int32_t>(c, L.n_j),
                          at<float>(c, L.n_z), at<float>(c, L.n_r)};
-  launch_cq_receipt(ra, nq, s);
+  if (chains) launch_cq_receipt_chain(CqChainReceiptArgs{ra, chain}, nq, s);
+  else launch_cq_receipt(ra, nq, s);
   return L;
 }
 
@@ -795,9 +834,10 @@ void check_candidates(const osc_corpus& c, const int32_t* cand, int32_t Q, int32
     if (cand[i] < 0 || cand[i] >= c.N) throw Invalid("candidates: corpus id out of range");
 }
 
-int32_t chunk_for(const osc_corpus& c, int32_t K, int32_t knn, int32_t kk, bool receipts = false, int32_t null_slots = 0) {
+int32_t chunk_for(const osc_corpus& c, int32_t K, int32_t knn, int32_t kk, bool receipts = false, int32_t null_slots = 0,
+                  int32_t chain_cap = 0) {
   return host::corpus_chunk(c.N, c.ldn, K, std::max(1, knn), std::max(1, kk), c.chunk_req, host::kCorpusBudgetBytes, receipts,
-                            null_slots);
+                            null_slots, chain_cap);
 }
 
 struct RefineOut {
@@ -828,6 +868,19 @@ struct ReceiptOut {
   int64_t* edge_prefix;     // Q x prefix_cap x 2
   int32_t* edge_prefix_n;
   int32_t prefix_cap;
+};
+
+// what a call with chains returns on top of that (osc_corpus_refine_chains); the four edge arrays are flat over the chain
+// edges of all queries, in query order
+struct ChainOut {
+  float* z_struct;
+  float* z_path;
+  float* r_struct;
+  float* r_path;
+  double* gain;
+  int32_t* verdict;
+  int32_t* weak_k;
+  float* weak_z;
 };
 
 void check_gate_settings(float beta, float gamma, int32_t method, int32_t max_iters) {
@@ -896,7 +949,7 @@ void set_shape(const osc_corpus& c, RefineReq& rq) {
 // runs the request chunk by chunk; fetch(L, q0, n, down) queues the chunk's downloads, then the stream is drained
 template <class F>
 void for_each_chunk(osc_corpus& c, const RefineReq& rq, F&& fetch) {
-  const int32_t nq = chunk_for(c, rq.K, rq.knn, rq.kk, rq.receipts != 0, rq.null_slots);
+  const int32_t nq = chunk_for(c, rq.K, rq.knn, rq.kk, rq.receipts != 0, rq.null_slots, rq.chain_cap);
   auto down = [&](void* dst, int64_t off, size_t bytes) {
     HIP_CHECK(hipMemcpyAsync(dst, c.scratch.p + off, bytes, hipMemcpyDeviceToHost, c.stream));
   };
@@ -966,9 +1019,30 @@ void fetch_receipts(osc_corpus& c, const RefineReq& rq, const ReceiptOut& ro, co
   }
 }
 
-// validates a refine_request (with its gates and receipts set) and its buffers, in the order the messages are documented
-// in, and runs it
-void refine_body(osc_corpus& c, RefineReq rq, const RefineOut& o, const char* null_msg, const ReceiptOut* ro = nullptr) {
+// a chunk's chain receipts: the edge slabs (chain_cap per query) packed to the queries' edge ranges, and the per-query scalars
+template <class Down>
+void fetch_chains(osc_corpus& c, const RefineReq& rq, const ChainOut& co, const host::CorpusLayout& L, int32_t q0, int32_t n,
+                  Down& down) {
+  const int32_t cap = rq.chain_cap;
+  std::vector<float> he((size_t)n * 4 * cap);
+  down(he.data(), L.c_edge, he.size() * 4);
+  down(co.gain + q0, L.c_gain, (size_t)n * 8);
+  down(co.verdict + q0, L.c_verdict, (size_t)n * 4);
+  down(co.weak_k + q0, L.c_weak_k, (size_t)n * 4);
+  down(co.weak_z + q0, L.c_weak_z, (size_t)n * 4);
+  HIP_CHECK(hipStreamSynchronize(c.stream));
+  float* dst[4] = {co.z_struct, co.z_path, co.r_struct, co.r_path};
+  for (int32_t q = 0; q < n; ++q) {
+    const int64_t e0 = rq.c_eoff[q0 + q], ne = rq.c_eoff[q0 + q + 1] - e0;
+    for (int t = 0; t < 4; ++t)
+      std::copy(he.begin() + ((size_t)q * 4 + t) * cap, he.begin() + ((size_t)q * 4 + t) * cap + ne, dst[t] + e0);
+  }
+}
+
+// validates a refine_request (with its gates, receipts and chains set) and its buffers, in the order the messages are
+// documented in, and runs it
+void refine_body(osc_corpus& c, RefineReq rq, const RefineOut& o, const char* null_msg, const ReceiptOut* ro = nullptr,
+                 const ChainOut* co = nullptr) {
   const int32_t Q = rq.Q;
   check_request(c, rq);
   if (!(rq.lamG > 0.f) || rq.lamC < 0.f || rq.lamQ < 0.f) throw Invalid("need lamG > 0, lamC >= 0, lamQ >= 0");
@@ -981,7 +1055,33 @@ void refine_body(osc_corpus& c, RefineReq rq, const RefineOut& o, const char* nu
     if (!ro->null_offsets) throw Invalid(null_msg);
     ro->null_offsets[0] = 0;
   }
+  std::vector<int64_t> eoff;  // the chains: checked as add_chain checks them (lattice.py:129-142), edge offsets formed
+  if (co) {
+    if (!(rq.lamP >= 0.f) || !std::isfinite(rq.lamP)) throw Invalid("lamP must be >= 0");
+    if (!std::isfinite(rq.c_zth)) throw Invalid("chain_z_th must be finite");
+    if (!rq.c_off || rq.c_off[0] != 0) throw Invalid("chain_offsets must start at 0");
+    eoff.assign((size_t)Q + 1, 0);
+    for (int32_t q = 0; q < Q; ++q) {
+      const int64_t len = rq.c_off[q + 1] - rq.c_off[q];
+      if (len < 0) throw Invalid("chain_offsets must not decrease");
+      if (len == 1) throw Invalid("chain must contain at least two indices");
+      if (len > host::kCorpusMaxChain) throw Invalid("a chain has at most 1024 indices");
+      if (len > 0 && !rq.c_nodes) throw Invalid(null_msg);
+      for (int64_t t = rq.c_off[q]; t < rq.c_off[q + 1]; ++t)
+        if (rq.c_nodes[t] < 0 || rq.c_nodes[t] >= rq.K) throw Invalid("chain indices out of bounds");
+      eoff[(size_t)q + 1] = eoff[(size_t)q] + std::max<int64_t>(0, len - 1);
+      rq.chain_cap = std::max(rq.chain_cap, (int32_t)std::max<int64_t>(0, len - 1));
+    }
+    if (rq.c_w)
+      for (int64_t t = 0; t < eoff[(size_t)Q]; ++t)
+        if (!std::isfinite(rq.c_w[t])) throw Invalid("chain weights must be finite");
+    rq.c_eoff = eoff.data();
+    if (rq.chain_cap == 0) co = nullptr;  // no query has a chain: the call without chains
+  }
   if (Q == 0) return;
+  if (co && (!co->z_struct || !co->z_path || !co->r_struct || !co->r_path || !co->gain || !co->verdict || !co->weak_k ||
+             !co->weak_z))
+    throw Invalid(null_msg);
   if (!o.cand || !o.iters || !o.res || (rq.kk > 0 && (!o.local || !o.score || !o.align)) ||
       (rq.gate && (!o.gates || !o.g_iters || !o.g_res)))
     throw Invalid(null_msg);
@@ -1009,6 +1109,7 @@ void refine_body(osc_corpus& c, RefineReq rq, const RefineOut& o, const char* nu
       down(o.g_res + q0, L.g_res, (size_t)n * 4);
     }
     if (ro) fetch_receipts(c, rq, *ro, L, q0, n, down);
+    if (co) fetch_chains(c, rq, *co, L, q0, n, down);
   });
   if (rq.gate == 2) {  // nothing was solved for given gates
     std::fill(o.g_iters, o.g_iters + Q, 0);
@@ -1154,6 +1255,53 @@ int osc_corpus_refine_receipts(osc_corpus_handle h, const float* psis, int32_t Q
                         null_j, null_z, null_r, null_capacity, nnz_out, edge_prefix, edge_prefix_n, edge_prefix_cap};
     refine_body(c, rq, RefineOut{cand_out, local, score, align, iters, res, gates_out, gate_iters, gate_res},
                 "osc_corpus_refine_receipts: NULL buffer", &ro);
+  });
+}
+
+int osc_corpus_refine_chains(osc_corpus_handle h, const float* psis, int32_t Q, int32_t top_k, const int32_t* cand_in,
+                             int32_t gate_mode, const float* gates_in, float beta, float gamma, int32_t method,
+                             float gate_tol, int32_t gate_max_iters, int32_t kneighbors, float row_cap, float lamG, float lamC,
+                             float lamQ, float tol, int32_t max_iters, int32_t k, float alpha, float dt,
+                             int32_t settle_max_iters, float settle_tol, int32_t detail, float z_th, int32_t null_cap,
+                             const int64_t* chain_offsets, const int32_t* chain_nodes, const float* chain_weights, float lamP,
+                             float chain_z_th, int32_t* cand_out, float* gates_out, int32_t* local, float* score,
+                             float* align, int32_t* iters, float* res, int32_t* gate_iters, float* gate_res,
+                             int32_t* settle_iters, float* settle_res, double* dH, double* coh_sum, double* anchor_sum,
+                             double* query_sum, int32_t* null_total, int64_t* null_offsets, int32_t* null_i, int32_t* null_j,
+                             float* null_z, float* null_r, int64_t null_capacity, int64_t* nnz_out, int64_t* edge_prefix,
+                             int32_t* edge_prefix_n, int32_t edge_prefix_cap, float* chain_z_struct, float* chain_z_path,
+                             float* chain_r_struct, float* chain_r_path, double* chain_gain, int32_t* chain_verdict,
+                             int32_t* chain_weakest_k, float* chain_weakest_z) {
+  return corpus_guarded(h, [&](osc_corpus& c) {
+    if (gate_mode < 0 || gate_mode > 2) throw Invalid("gate_mode must be 0 (none), 1 (diffusion) or 2 (given)");
+    if (gate_mode == 2 && !gates_in && Q > 0) throw Invalid("gate_mode 2 needs gates_in");
+    if (detail < -1 || detail > 1) throw Invalid("detail must be -1 (no receipts), 0 (light) or 1 (full)");
+    RefineReq rq = refine_request(psis, Q, top_k, cand_in, kneighbors, row_cap, lamG, lamC, lamQ, tol, max_iters, k, alpha);
+    set_gate_request(rq, gate_mode, gates_in, beta, gamma, method, gate_tol, gate_max_iters);
+    if (detail >= 0) {
+      if (!(dt > 0.f) || !std::isfinite(dt)) throw Invalid("dt must be finite and > 0");
+      if (settle_max_iters < 1) throw Invalid("settle_max_iters must be >= 1");
+      if (!std::isfinite(settle_tol)) throw Invalid("settle_tol must be finite");
+      if (!std::isfinite(z_th)) throw Invalid("z_th must be finite");
+      rq.receipts = detail ? 2 : 1;
+      rq.s_dt = dt;
+      rq.s_max_iters = settle_max_iters;
+      rq.s_tol = settle_tol;
+      rq.z_th = z_th;
+      rq.null_cap = std::max(0, null_cap);
+    }
+    rq.c_off = chain_offsets;
+    rq.c_nodes = chain_nodes;
+    rq.c_w = chain_weights;
+    rq.lamP = lamP;
+    rq.c_zth = chain_z_th;
+    const ReceiptOut ro{settle_iters, settle_res, {dH, coh_sum, anchor_sum, query_sum}, null_total, null_offsets, null_i,
+                        null_j, null_z, null_r, null_capacity, nnz_out, edge_prefix, edge_prefix_n, edge_prefix_cap};
+    const ChainOut co{chain_z_struct, chain_z_path, chain_r_struct, chain_r_path, chain_gain, chain_verdict, chain_weakest_k,
+                      chain_weakest_z};
+    if (!chain_offsets) throw Invalid("osc_corpus_refine_chains: NULL buffer");
+    refine_body(c, rq, RefineOut{cand_out, local, score, align, iters, res, gates_out, gate_iters, gate_res},
+                "osc_corpus_refine_chains: NULL buffer", detail >= 0 ? &ro : nullptr, &co);
   });
 }
 
