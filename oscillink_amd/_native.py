@@ -24,6 +24,23 @@ c_i64p = C.POINTER(C.c_int64)
 c_f64p = C.POINTER(C.c_double)
 Handle = C.c_void_p
 
+_i32, _i64, _f32 = C.c_int32, C.c_int64, C.c_float
+# The argument runs of the Corpus refine entry points, in the header's order (corpus.py passes the same runs by name).
+_QUERIES = [Handle, c_f32p, _i32, _i32, c_i32p]  # h, psis, Q, top_k, cand_in
+_GATE_SET = [_f32, _f32, _i32, _f32, _i32]  # beta, gamma, method, gate_tol, gate_max_iters
+# kneighbors, row_cap, lamG, lamC, lamQ, tol, max_iters, k, alpha
+_SOLVE_SET = [_i32, _f32, _f32, _f32, _f32, _f32, _i32, _i32, _f32]
+_RECEIPT_SET = [_f32, _i32, _f32, _i32, _f32, _i32]  # dt, settle_max_iters, settle_tol, detail, z_th, null_cap
+_CHAIN_IN = [c_i64p, c_i32p, c_f32p, _f32, _f32]  # chain_offsets, chain_nodes, chain_weights, lamP, chain_z_th
+_REFINE_OUT = [c_i32p, c_i32p, c_f32p, c_f32p, c_i32p, c_f32p]  # cand, local, score, align, iters, res
+_REFINE_OUT_GATED = [c_i32p, c_f32p, *_REFINE_OUT[1:], c_i32p, c_f32p]  # gates second, gate_iters and gate_res last
+# dH, coh, anchor, query sums, null_total, null_offsets, null_i, null_j, null_z, null_r, null_capacity
+_RECEIPT_MANY_OUT = [c_f64p, c_f64p, c_f64p, c_f64p, c_i32p, c_i64p, c_i32p, c_i32p, c_f32p, c_f32p, _i64]
+# settle_iters, settle_res in front; nnz, edge_prefix, edge_prefix_n, edge_prefix_cap behind
+_RECEIPT_OUT = [c_i32p, c_f32p, *_RECEIPT_MANY_OUT, c_i64p, c_i64p, c_i32p, _i32]
+_CHAIN_OUT = [c_f32p, c_f32p, c_f32p, c_f32p, c_f64p, c_i32p, c_i32p, c_f32p]  # z_struct .. r_path, gain, verdict, weakest k, z
+_GATED_REQUEST = [*_QUERIES, _i32, c_f32p, *_GATE_SET, *_SOLVE_SET, *_RECEIPT_SET]  # + gate_mode, gates_in
+
 # name -> (restype, argtypes): exactly the declarations of include/oscillink_hip.h
 SIGNATURES = {
     "osc_version": (C.c_char_p, []),
@@ -69,37 +86,18 @@ SIGNATURES = {
     "osc_get_query_basis": (C.c_int, [Handle, c_f32p, c_f32p]),
     "osc_bundle_many": (C.c_int, [Handle, c_f32p, C.c_int32, C.c_int32, C.c_float, C.c_float, c_i32p, c_f32p, c_f32p]),
     "osc_mmr_many": (C.c_int, [Handle, c_f32p, C.c_int32, C.c_int32, C.c_float, c_i32p]),
-    "osc_receipt_many": (C.c_int, [Handle, c_f32p, C.c_int32, C.c_int32, C.c_float, C.c_int32, c_f64p, c_f64p, c_f64p, c_f64p,
-                                   c_i32p, c_i64p, c_i32p, c_i32p, c_f32p, c_f32p, C.c_int64]),
+    "osc_receipt_many": (C.c_int, [Handle, c_f32p, C.c_int32, C.c_int32, C.c_float, C.c_int32, *_RECEIPT_MANY_OUT]),
     "osc_corpus_create": (C.c_int, [c_f32p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(Handle)]),
     "osc_corpus_destroy": (C.c_int, [Handle]),
     "osc_corpus_last_error": (C.c_char_p, [Handle]),
     "osc_corpus_info": (C.c_int, [Handle, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_i64p]),
     "osc_corpus_search": (C.c_int, [Handle, c_f32p, C.c_int32, C.c_int32, c_i32p, c_f32p]),
-    "osc_corpus_refine": (C.c_int, [Handle, c_f32p, C.c_int32, C.c_int32, c_i32p, C.c_int32, C.c_float, C.c_float, C.c_float,
-                                    C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_float, c_i32p, c_i32p, c_f32p, c_f32p,
-                                    c_i32p, c_f32p]),
+    "osc_corpus_refine": (C.c_int, [*_QUERIES, *_SOLVE_SET, *_REFINE_OUT]),
     "osc_corpus_gates": (C.c_int, [Handle, c_f32p, C.c_int32, C.c_int32, c_i32p, C.c_int32, C.c_float, C.c_float, C.c_float,
                                    C.c_int32, C.c_float, C.c_int32, C.c_int32, c_i32p, c_f32p, c_i32p, c_f32p]),
-    "osc_corpus_refine_gated": (C.c_int, [Handle, c_f32p, C.c_int32, C.c_int32, c_i32p, c_f32p, C.c_float, C.c_float,
-                                          C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float,
-                                          C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_float, c_i32p, c_f32p, c_i32p,
-                                          c_f32p, c_f32p, c_i32p, c_f32p, c_i32p, c_f32p]),
-    "osc_corpus_refine_receipts": (C.c_int, [Handle, c_f32p, C.c_int32, C.c_int32, c_i32p, C.c_int32, c_f32p, C.c_float,
-                                             C.c_float, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_float, C.c_float,
-                                             C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_float, C.c_float,
-                                             C.c_int32, C.c_float, C.c_int32, C.c_float, C.c_int32, c_i32p, c_f32p, c_i32p,
-                                             c_f32p, c_f32p, c_i32p, c_f32p, c_i32p, c_f32p, c_i32p, c_f32p, c_f64p, c_f64p,
-                                             c_f64p, c_f64p, c_i32p, c_i64p, c_i32p, c_i32p, c_f32p, c_f32p, C.c_int64,
-                                             c_i64p, c_i64p, c_i32p, C.c_int32]),
-    "osc_corpus_refine_chains": (C.c_int, [Handle, c_f32p, C.c_int32, C.c_int32, c_i32p, C.c_int32, c_f32p, C.c_float,
-                                           C.c_float, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_float, C.c_float,
-                                           C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_float, C.c_float,
-                                           C.c_int32, C.c_float, C.c_int32, C.c_float, C.c_int32, c_i64p, c_i32p, c_f32p,
-                                           C.c_float, C.c_float, c_i32p, c_f32p, c_i32p, c_f32p, c_f32p, c_i32p, c_f32p,
-                                           c_i32p, c_f32p, c_i32p, c_f32p, c_f64p, c_f64p, c_f64p, c_f64p, c_i32p, c_i64p,
-                                           c_i32p, c_i32p, c_f32p, c_f32p, C.c_int64, c_i64p, c_i64p, c_i32p, C.c_int32,
-                                           c_f32p, c_f32p, c_f32p, c_f32p, c_f64p, c_i32p, c_i32p, c_f32p]),
+    "osc_corpus_refine_gated": (C.c_int, [*_QUERIES, c_f32p, *_GATE_SET, *_SOLVE_SET, *_REFINE_OUT_GATED]),
+    "osc_corpus_refine_receipts": (C.c_int, [*_GATED_REQUEST, *_REFINE_OUT_GATED, *_RECEIPT_OUT]),
+    "osc_corpus_refine_chains": (C.c_int, [*_GATED_REQUEST, *_CHAIN_IN, *_REFINE_OUT_GATED, *_RECEIPT_OUT, *_CHAIN_OUT]),
     "osc_corpus_graph": (C.c_int, [Handle, c_f32p, c_i32p, C.c_int32, C.c_int32, C.c_float, c_i32p, c_i64p, c_i32p, c_f32p,
                                    c_f32p, c_f32p, C.c_int64, c_i64p]),
     "osc_deltaH": (C.c_int, [Handle, c_f64p]),

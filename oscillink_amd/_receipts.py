@@ -1,0 +1,188 @@
+"""The host side of a receipt, once: what `OscillinkLattice.receipt`, `receipt_many` and `Corpus.refine_many(receipts=...)`
+share when they turn device numbers into the reference's receipt dict (oscillink/core/lattice.py:298-455, receipts.py).
+The callers differ in where the `ustar_*` values, the clocks and the gates come from; they pass values, never a lattice.
+Key order is the reference's and is part of the contract (tests/test_receipt_records_host.py).  NumPy and the standard
+library only.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import gc
+import hashlib
+import hmac
+import json
+import os
+from typing import Any, Optional
+
+import numpy as np
+
+
+def null_cap() -> int:
+    """OSCILLINK_RECEIPT_NULL_CAP as an int >= 0; unset, garbage or negative: 0 (no cap)."""
+    try:
+        return max(int(os.getenv("OSCILLINK_RECEIPT_NULL_CAP", "0").strip()), 0)
+    except ValueError:
+        return 0
+
+
+def null_summary(total: int, cap: int) -> dict[str, Any]:
+    capped = cap > 0 and total > cap
+    return {"total_null_points": total, "returned_null_points": cap if capped else total, "null_cap_applied": bool(capped)}
+
+
+def null_dicts(i, j, z, r, n):
+    """The reference's list of {"edge": [i, j], "z": .., "residual": ..} (receipts.py:63-83).  At config 3 every row has a
+    null point (a dense residual row is 29 values among 100 000 zeros), so this makes 100 000 dicts + 100 000 lists: the
+    cyclic collector, which wakes up every 700 new containers and re-walks the young ones, was two thirds of the 47 ms the
+    list took -- nothing built here can be part of a cycle, so it is paused for the construction."""
+    il, jl, zl, rl = i[:n].tolist(), j[:n].tolist(), z[:n].astype(float).tolist(), r[:n].astype(float).tolist()
+    paused = n > 2000 and gc.isenabled()
+    if paused:
+        gc.disable()
+    try:
+        return [{"edge": [a, b], "z": c, "residual": d} for a, b, c, d in zip(il, jl, zl, rl)]
+    finally:
+        if paused:
+            gc.enable()
+
+
+def check_queries(psis, D: int) -> np.ndarray:
+    """`psis` as a contiguous float32 (Q, D) array with finite rows, or the ValueError every batched call raises."""
+    P = np.asarray(psis)
+    if P.ndim != 2 or P.shape[1] != D:
+        raise ValueError(f"psis must be a (Q, {D}) array, got shape {P.shape}")
+    P = np.ascontiguousarray(P, dtype=np.float32)
+    bad = np.nonzero(~np.all(np.isfinite(P), axis=1))[0]
+    if bad.size:
+        raise ValueError(f"psis row {int(bad[0])} is not finite")
+    return P
+
+
+def bundle_dicts(ids, score, align) -> list[dict[str, Any]]:
+    """One query's bundle, the list of {"id", "score", "align"} that bundle() returns, from three parallel 1-D arrays."""
+    return [{"id": int(i), "score": float(s), "align": float(a)}
+            for i, s, a in zip(ids.tolist(), score.tolist(), align.tolist())]
+
+
+def _ptr(a: np.ndarray, ctype):
+    return a.ctypes.data_as(C.POINTER(ctype))
+
+
+class ReceiptArrays:
+    """The receipt buffers of a batch of Q queries, as osc_receipt_many and osc_corpus_refine_receipts fill them: the
+    (4, Q) float64 sums (deltaH, coh, anchor, query), the null totals, the offsets of the kept null points and those
+    points, `slots` per query at most (0 = light detail: none).  `settle=True` adds the per-query settle report that the
+    Corpus entry points write in front."""
+
+    def __init__(self, Q: int, slots: int, settle: bool = False):
+        self.full = slots > 0
+        self.capacity = Q * slots
+        self.settle = (np.zeros(Q, dtype=np.int32), np.zeros(Q, dtype=np.float32)) if settle else None
+        self.sums = np.zeros((4, Q), dtype=np.float64)
+        self.total = np.zeros(Q, dtype=np.int32)
+        self.offsets = np.zeros(Q + 1, dtype=np.int64)
+        n = max(self.capacity, 1)
+        self.i, self.j = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        self.z, self.r = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.float32)
+
+    def pointers(self) -> list:
+        """The arrays in the entry points' order, the capacity last."""
+        head = [] if self.settle is None else [_ptr(self.settle[0], C.c_int32), _ptr(self.settle[1], C.c_float)]
+        return [*head, *[_ptr(self.sums[t], C.c_double) for t in range(4)], _ptr(self.total, C.c_int32),
+                _ptr(self.offsets, C.c_int64), _ptr(self.i, C.c_int32), _ptr(self.j, C.c_int32), _ptr(self.z, C.c_float),
+                _ptr(self.r, C.c_float), int(self.capacity)]
+
+    def round_sums(self) -> None:
+        """Once the native call has returned: the float32 rounding receipt() gives its energies (a float32 dH / np.sum
+        over float32 rows)."""
+        self.sums = self.sums.astype(np.float32).astype(np.float64)
+
+    @property
+    def kept(self) -> int:
+        return int(self.offsets[-1])
+
+    def scalar_arrays(self) -> dict[str, np.ndarray]:
+        """The per-query scalars of the `as_arrays` form."""
+        head = {} if self.settle is None else dict(settle_iters=self.settle[0], settle_res=self.settle[1])
+        return dict(head, deltaH=self.sums[0], coh_drop_sum=self.sums[1], anchor_pen_sum=self.sums[2],
+                    query_term_sum=self.sums[3])
+
+    def null_arrays(self) -> dict[str, np.ndarray]:
+        """The null points of the `as_arrays` form (full detail): every query's kept points, concatenated."""
+        n = self.kept
+        return dict(null_total=self.total.astype(np.int64), null_offsets=self.offsets, null_i=self.i[:n].copy(),
+                    null_j=self.j[:n].copy(), null_z=self.z[:n].copy(), null_r=self.r[:n].copy())
+
+    def nulls(self, q: int):
+        """(query q's null point dicts, its total before the cap); ([], 0) in light detail."""
+        if not self.full:
+            return [], 0
+        s, e = int(self.offsets[q]), int(self.offsets[q + 1])
+        return null_dicts(self.i[s:e], self.j[s:e], self.z[s:e], self.r[s:e], e - s), int(self.total[q])
+
+
+def degree_stats(nnz: int, n: int) -> dict[str, float]:
+    return {"avg_degree": float(nnz / max(n, 1)), "edge_density": float(nnz / max(n * (n - 1), 1))}
+
+
+def gate_stats(B: np.ndarray) -> dict[str, Any]:
+    return {"gates_min": float(np.min(B)), "gates_max": float(np.max(B)), "gates_mean": float(np.mean(B)),
+            "gates_uniform": bool(np.allclose(B, B[0]))}
+
+
+def meta(*, ustar_cached, ustar_solves, ustar_cache_hits, ustar: dict, ustar_solve_ms, ustar_source: Optional[str] = None,
+         graph_build_ms, last_settle_ms, degree: dict, gates: dict, state_sig: str, receipt_detail: str,
+         null_points_summary: dict) -> dict[str, Any]:
+    """A receipt's `meta`.  ustar = {"ustar_iters", "ustar_res", "ustar_converged"} (what sign() signs in extended mode);
+    degree, gates = degree_stats() / gate_stats(), which a batch on one graph forms once; `ustar_source` only if given."""
+    m = {
+        "ustar_cached": bool(ustar_cached),
+        "ustar_solves": int(ustar_solves),
+        "ustar_cache_hits": int(ustar_cache_hits),
+        "ustar_converged": ustar["ustar_converged"],
+        "ustar_res": ustar["ustar_res"],
+        "ustar_iters": ustar["ustar_iters"],
+        "ustar_solve_ms": float(ustar_solve_ms),
+        "ustar_source": ustar_source,
+        "graph_build_ms": float(graph_build_ms),
+        "last_settle_ms": float(last_settle_ms),
+        **degree,
+        **gates,
+        "state_sig": state_sig,
+        "receipt_detail": receipt_detail,
+        "null_points_summary": null_points_summary,
+    }
+    if ustar_source is None:  # receipt(): the reference's keys and no more
+        del m["ustar_source"]
+    return m
+
+
+def sign(meta: dict, secret: Optional[bytes], mode: str, *, state_sig: str, deltaH: float, ustar: dict, params: dict,
+         graph: dict) -> None:
+    """meta["signature"] = the HMAC-SHA256 block over the minimal or extended payload (lattice.py:380-418); nothing
+    without a secret."""
+    if secret is None:
+        return
+    payload = {"sig_v": 1, "mode": "minimal", "state_sig": state_sig, "deltaH_total": float(deltaH)}
+    if mode == "extended":
+        payload = {**payload, "mode": "extended", **ustar, "params": params, "graph": graph}
+    raw = json.dumps(payload, sort_keys=True).encode("utf-8")
+    meta["signature"] = {"algorithm": "HMAC-SHA256", "payload": payload,
+                         "signature": hmac.new(secret, raw, hashlib.sha256).hexdigest()}
+
+
+def record(*, version, deltaH, coh_drop_sum, anchor_pen_sum, query_term_sum, cg_iters, residual, t_ms, null_points,
+           meta: dict) -> dict[str, Any]:
+    """The receipt itself; callers append meta["dynamics"] afterwards."""
+    return {
+        "version": str(version),
+        "deltaH_total": float(deltaH),
+        "coh_drop_sum": float(coh_drop_sum),
+        "anchor_pen_sum": float(anchor_pen_sum),
+        "query_term_sum": float(query_term_sum),
+        "cg_iters": int(cg_iters),
+        "residual": float(residual),
+        "t_ms": float(t_ms),
+        "null_points": null_points,
+        "meta": meta,
+    }

@@ -16,6 +16,7 @@ from typing import Any, Optional
 import numpy as np
 
 from . import _native as nat
+from . import _receipts as rc
 
 MAX_TOP_K = 1024  # one key per thread of the per-query select (include/oscillink_hip.h)
 MAX_KNEIGHBORS = 128  # the dense build route's per-row list (k_knn_select)
@@ -61,8 +62,7 @@ class _RefineOut:
 
     def bundles(self, ids):
         """Per query the list of {"id", "score", "align"} that bundle() returns."""
-        return [[{"id": int(i), "score": float(s), "align": float(a)} for i, s, a in
-                 zip(ids[q].tolist(), self.score[q].tolist(), self.align[q].tolist())] for q in range(ids.shape[0])]
+        return [rc.bundle_dicts(ids[q], self.score[q], self.align[q]) for q in range(ids.shape[0])]
 
 
 class Corpus:
@@ -132,14 +132,7 @@ class Corpus:
     def _queries(self, psis) -> np.ndarray:
         if self._h is None:
             raise ValueError("Corpus is closed")
-        P = np.asarray(psis)
-        if P.ndim != 2 or P.shape[1] != self.D:
-            raise ValueError(f"psis must be a (Q, {self.D}) array, got shape {P.shape}")
-        P = np.ascontiguousarray(P, dtype=np.float32)
-        bad = np.nonzero(~np.all(np.isfinite(P), axis=1))[0]
-        if bad.size:
-            raise ValueError(f"psis row {int(bad[0])} is not finite")
-        return P
+        return rc.check_queries(psis, self.D)
 
     def _top_k(self, top_k: int) -> int:
         if int(top_k) < 1 or int(top_k) > MAX_TOP_K:
@@ -415,29 +408,14 @@ class Corpus:
         full = detail == 1
         gated = o.gated
         iters, res, g, g_iters, g_res = o.iters, o.res, o.g, o.g_iters, o.g_res
-        try:
-            cap_val = int(os.getenv("OSCILLINK_RECEIPT_NULL_CAP", "0").strip())
-        except ValueError:
-            cap_val = 0
-        cap_val = max(cap_val, 0)
-        slots = (min(cap_val, K) if cap_val > 0 else K) if full else 0
-        capacity = Q * slots
-        s_iters = np.zeros(Q, dtype=np.int32)
-        s_res = np.zeros(Q, dtype=np.float32)
-        sums = np.zeros((4, Q), dtype=np.float64)  # deltaH, coh, anchor, query
-        total = np.zeros(Q, dtype=np.int32)
-        offsets = np.zeros(Q + 1, dtype=np.int64)
-        ni = np.zeros(max(capacity, 1), dtype=np.int32)
-        nj = np.zeros(max(capacity, 1), dtype=np.int32)
-        nz = np.zeros(max(capacity, 1), dtype=np.float32)
-        nr = np.zeros(max(capacity, 1), dtype=np.float32)
+        cap_val = rc.null_cap()
+        ra = rc.ReceiptArrays(Q, (min(cap_val, K) if cap_val > 0 else K) if full else 0, settle=True)
+        s_iters, s_res = ra.settle
         dicts = not as_arrays and detail is not None
         nnz = np.zeros(Q, dtype=np.int64)
         pairs = np.zeros((Q if dicts else 0, EDGE_PREFIX, 2), dtype=np.int64)
         pairs_n = np.zeros(Q, dtype=np.int32)
-        receipt_out = (nat.i32(s_iters), nat.f32(s_res), *[sums[t].ctypes.data_as(nat.c_f64p) for t in range(4)],
-                       nat.i32(total), nat.i64(offsets), nat.i32(ni), nat.i32(nj), nat.f32(nz), nat.f32(nr), int(capacity),
-                       nat.i64(nnz) if dicts else None, nat.i64(pairs) if dicts else None,
+        receipt_out = (*ra.pointers(), nat.i64(nnz) if dicts else None, nat.i64(pairs) if dicts else None,
                        nat.i32(pairs_n) if dicts else None, EDGE_PREFIX)
         if chain is not None:
             n_edges = int(chain["edge_offsets"][-1])
@@ -459,17 +437,13 @@ class Corpus:
         if Q:
             if mode == 1:
                 self._warn_non_finite(g, g_iters, g_res, "refine_many")
-        # the float32 rounding receipt() gives its energies (a float32 dH / np.sum over float32 rows)
-        sums = sums.astype(np.float32).astype(np.float64)
-        kept = int(offsets[-1])
+        ra.round_sums()
         ids, out = o.ids_and_arrays()
         if as_arrays:
             if detail is not None:
-                out.update(settle_iters=s_iters, settle_res=s_res, deltaH=sums[0], coh_drop_sum=sums[1],
-                           anchor_pen_sum=sums[2], query_term_sum=sums[3])
+                out.update(ra.scalar_arrays())
             if full:
-                out.update(null_total=total.astype(np.int64), null_offsets=offsets, null_i=ni[:kept].copy(),
-                           null_j=nj[:kept].copy(), null_z=nz[:kept].copy(), null_r=nr[:kept].copy())
+                out.update(ra.null_arrays())
             if chain is not None:
                 out.update(chain_offsets=chain["edge_offsets"], chain_z_struct=c_edge[0, :n_edges].copy(),
                            chain_z_path=c_edge[1, :n_edges].copy(), chain_r_struct=c_edge[2, :n_edges].copy(),
@@ -490,48 +464,16 @@ class Corpus:
                 {"psi": np.round(P[q], 6).tolist(), "lam": lam if ch is None else [*lam[:3], chain["lamP"]],
                  "chain_present": ch is not None, "chain_len": 0 if ch is None else len(ch),
                  "k": knn, "detk": bool(deterministic_k), "adj": adj_sig}, B)
-            if full:
-                s, e = int(offsets[q]), int(offsets[q + 1])
-                nulls = OscillinkLattice._null_dicts(ni[s:e], nj[s:e], nz[s:e], nr[s:e], e - s)
-                tot = int(total[q])
-            else:
-                nulls, tot = [], 0
-            capped = cap_val > 0 and tot > cap_val
-            n_edges = int(nnz[q])
-            meta: dict[str, Any] = {
-                "ustar_cached": False,
-                "ustar_solves": 1,
-                "ustar_cache_hits": 0,
-                "ustar_converged": bool(float(res[q]) <= USTAR_TOL),
-                "ustar_res": float(res[q]),
-                "ustar_iters": int(iters[q]),
-                "ustar_solve_ms": 0.0,
-                "ustar_source": "corpus_batch",
-                "graph_build_ms": 0.0,
-                "last_settle_ms": 0.0,
-                "avg_degree": float(n_edges / max(K, 1)),
-                "edge_density": float(n_edges / max(K * (K - 1), 1)),
-                "gates_min": float(np.min(B)),
-                "gates_max": float(np.max(B)),
-                "gates_mean": float(np.mean(B)),
-                "gates_uniform": bool(np.allclose(B, B[0])),
-                "state_sig": sig,
-                "receipt_detail": detail_name,
-                "null_points_summary": {"total_null_points": tot, "returned_null_points": cap_val if capped else tot,
-                                        "null_cap_applied": bool(capped)},
-            }
-            rec = {
-                "version": str(__version__),
-                "deltaH_total": float(sums[0, q]),
-                "coh_drop_sum": float(sums[1, q]),
-                "anchor_pen_sum": float(sums[2, q]),
-                "query_term_sum": float(sums[3, q]),
-                "cg_iters": int(s_iters[q]),
-                "residual": float(s_res[q]),
-                "t_ms": 0.0,
-                "null_points": nulls,
-                "meta": meta,
-            }
+            nulls, tot = ra.nulls(q)
+            meta = rc.meta(ustar_cached=False, ustar_solves=1, ustar_cache_hits=0,
+                           ustar={"ustar_iters": int(iters[q]), "ustar_res": float(res[q]),
+                                  "ustar_converged": bool(float(res[q]) <= USTAR_TOL)},
+                           ustar_solve_ms=0.0, ustar_source="corpus_batch", graph_build_ms=0.0, last_settle_ms=0.0,
+                           degree=rc.degree_stats(int(nnz[q]), K), gates=rc.gate_stats(B), state_sig=sig,
+                           receipt_detail=detail_name, null_points_summary=rc.null_summary(tot, cap_val))
+            rec = rc.record(version=__version__, deltaH=ra.sums[0, q], coh_drop_sum=ra.sums[1, q],
+                            anchor_pen_sum=ra.sums[2, q], query_term_sum=ra.sums[3, q], cg_iters=s_iters[q],
+                            residual=s_res[q], t_ms=0.0, null_points=nulls, meta=meta)
             out.append({"bundle": bundles[q], "settle": {"iters": int(s_iters[q]), "res": float(s_res[q])}, "receipt": rec})
             if chain is not None:
                 out[-1]["chain_receipt"] = None

@@ -904,6 +904,35 @@ void set_gate_request(RefineReq& rq, int32_t mode, const float* gates_in, float 
   rq.g_max_iters = method == 0 ? 2048 : max_iters;  // direct: the reference's dense solve, served by a long CG
 }
 
+// the gate_mode argument of the entry points that take one
+void check_gate_mode(int32_t gate_mode, const float* gates_in, int32_t Q) {
+  if (gate_mode < 0 || gate_mode > 2) throw Invalid("gate_mode must be 0 (none), 1 (diffusion) or 2 (given)");
+  if (gate_mode == 2 && !gates_in && Q > 0) throw Invalid("gate_mode 2 needs gates_in");
+}
+
+// the settle and the receipt of a request, under these (checked) settings; detail 0 = light, 1 = full
+void set_receipt_request(RefineReq& rq, int32_t detail, float dt, int32_t settle_max_iters, float settle_tol, float z_th,
+                         int32_t null_cap) {
+  if (!(dt > 0.f) || !std::isfinite(dt)) throw Invalid("dt must be finite and > 0");
+  if (settle_max_iters < 1) throw Invalid("settle_max_iters must be >= 1");
+  if (!std::isfinite(settle_tol)) throw Invalid("settle_tol must be finite");
+  if (!std::isfinite(z_th)) throw Invalid("z_th must be finite");
+  rq.receipts = detail ? 2 : 1;
+  rq.s_dt = dt;
+  rq.s_max_iters = settle_max_iters;
+  rq.s_tol = settle_tol;
+  rq.z_th = z_th;
+  rq.null_cap = std::max(0, null_cap);
+}
+
+ReceiptOut receipt_out(int32_t* settle_iters, float* settle_res, double* dH, double* coh_sum, double* anchor_sum,
+                       double* query_sum, int32_t* null_total, int64_t* null_offsets, int32_t* null_i, int32_t* null_j,
+                       float* null_z, float* null_r, int64_t null_capacity, int64_t* nnz_out, int64_t* edge_prefix,
+                       int32_t* edge_prefix_n, int32_t edge_prefix_cap) {
+  return ReceiptOut{settle_iters, settle_res, {dH, coh_sum, anchor_sum, query_sum}, null_total, null_offsets, null_i,
+                    null_j, null_z, null_r, null_capacity, nnz_out, edge_prefix, edge_prefix_n, edge_prefix_cap};
+}
+
 // the queries, top_k, kneighbors and candidates of a request (checked by check_request and set_shape)
 RefineReq lattice_request(const float* psis, int32_t Q, int32_t top_k, int32_t kneighbors, const int32_t* cand_in) {
   RefineReq rq{};
@@ -1236,23 +1265,14 @@ int osc_corpus_refine_receipts(osc_corpus_handle h, const float* psis, int32_t Q
                                float* null_r, int64_t null_capacity, int64_t* nnz_out, int64_t* edge_prefix,
                                int32_t* edge_prefix_n, int32_t edge_prefix_cap) {
   return corpus_guarded(h, [&](osc_corpus& c) {
-    if (gate_mode < 0 || gate_mode > 2) throw Invalid("gate_mode must be 0 (none), 1 (diffusion) or 2 (given)");
-    if (gate_mode == 2 && !gates_in && Q > 0) throw Invalid("gate_mode 2 needs gates_in");
+    check_gate_mode(gate_mode, gates_in, Q);
     if (detail != 0 && detail != 1) throw Invalid("detail must be 0 (light) or 1 (full)");
-    if (!(dt > 0.f) || !std::isfinite(dt)) throw Invalid("dt must be finite and > 0");
-    if (settle_max_iters < 1) throw Invalid("settle_max_iters must be >= 1");
-    if (!std::isfinite(settle_tol)) throw Invalid("settle_tol must be finite");
-    if (!std::isfinite(z_th)) throw Invalid("z_th must be finite");
     RefineReq rq = refine_request(psis, Q, top_k, cand_in, kneighbors, row_cap, lamG, lamC, lamQ, tol, max_iters, k, alpha);
+    set_receipt_request(rq, detail, dt, settle_max_iters, settle_tol, z_th, null_cap);  // checked ahead of the gates' settings
     set_gate_request(rq, gate_mode, gates_in, beta, gamma, method, gate_tol, gate_max_iters);
-    rq.receipts = detail ? 2 : 1;
-    rq.s_dt = dt;
-    rq.s_max_iters = settle_max_iters;
-    rq.s_tol = settle_tol;
-    rq.z_th = z_th;
-    rq.null_cap = std::max(0, null_cap);
-    const ReceiptOut ro{settle_iters, settle_res, {dH, coh_sum, anchor_sum, query_sum}, null_total, null_offsets, null_i,
-                        null_j, null_z, null_r, null_capacity, nnz_out, edge_prefix, edge_prefix_n, edge_prefix_cap};
+    const ReceiptOut ro = receipt_out(settle_iters, settle_res, dH, coh_sum, anchor_sum, query_sum, null_total, null_offsets,
+                                      null_i, null_j, null_z, null_r, null_capacity, nnz_out, edge_prefix, edge_prefix_n,
+                                      edge_prefix_cap);
     refine_body(c, rq, RefineOut{cand_out, local, score, align, iters, res, gates_out, gate_iters, gate_res},
                 "osc_corpus_refine_receipts: NULL buffer", &ro);
   });
@@ -1273,30 +1293,19 @@ int osc_corpus_refine_chains(osc_corpus_handle h, const float* psis, int32_t Q, 
                              float* chain_r_struct, float* chain_r_path, double* chain_gain, int32_t* chain_verdict,
                              int32_t* chain_weakest_k, float* chain_weakest_z) {
   return corpus_guarded(h, [&](osc_corpus& c) {
-    if (gate_mode < 0 || gate_mode > 2) throw Invalid("gate_mode must be 0 (none), 1 (diffusion) or 2 (given)");
-    if (gate_mode == 2 && !gates_in && Q > 0) throw Invalid("gate_mode 2 needs gates_in");
+    check_gate_mode(gate_mode, gates_in, Q);
     if (detail < -1 || detail > 1) throw Invalid("detail must be -1 (no receipts), 0 (light) or 1 (full)");
     RefineReq rq = refine_request(psis, Q, top_k, cand_in, kneighbors, row_cap, lamG, lamC, lamQ, tol, max_iters, k, alpha);
     set_gate_request(rq, gate_mode, gates_in, beta, gamma, method, gate_tol, gate_max_iters);
-    if (detail >= 0) {
-      if (!(dt > 0.f) || !std::isfinite(dt)) throw Invalid("dt must be finite and > 0");
-      if (settle_max_iters < 1) throw Invalid("settle_max_iters must be >= 1");
-      if (!std::isfinite(settle_tol)) throw Invalid("settle_tol must be finite");
-      if (!std::isfinite(z_th)) throw Invalid("z_th must be finite");
-      rq.receipts = detail ? 2 : 1;
-      rq.s_dt = dt;
-      rq.s_max_iters = settle_max_iters;
-      rq.s_tol = settle_tol;
-      rq.z_th = z_th;
-      rq.null_cap = std::max(0, null_cap);
-    }
+    if (detail >= 0) set_receipt_request(rq, detail, dt, settle_max_iters, settle_tol, z_th, null_cap);
     rq.c_off = chain_offsets;
     rq.c_nodes = chain_nodes;
     rq.c_w = chain_weights;
     rq.lamP = lamP;
     rq.c_zth = chain_z_th;
-    const ReceiptOut ro{settle_iters, settle_res, {dH, coh_sum, anchor_sum, query_sum}, null_total, null_offsets, null_i,
-                        null_j, null_z, null_r, null_capacity, nnz_out, edge_prefix, edge_prefix_n, edge_prefix_cap};
+    const ReceiptOut ro = receipt_out(settle_iters, settle_res, dH, coh_sum, anchor_sum, query_sum, null_total, null_offsets,
+                                      null_i, null_j, null_z, null_r, null_capacity, nnz_out, edge_prefix, edge_prefix_n,
+                                      edge_prefix_cap);
     const ChainOut co{chain_z_struct, chain_z_path, chain_r_struct, chain_r_path, chain_gain, chain_verdict, chain_weakest_k,
                       chain_weakest_z};
     if (!chain_offsets) throw Invalid("osc_corpus_refine_chains: NULL buffer");

@@ -12,9 +12,7 @@ receipt assembly + HMAC signing, persistence.
 from __future__ import annotations
 
 import ctypes as C
-import gc
 import hashlib
-import hmac
 import json
 import os
 import time
@@ -23,6 +21,7 @@ from typing import Any, Optional
 import numpy as np
 
 from . import _native as nat
+from . import _receipts as rc
 
 __version__ = "0.1.13+mi355x.1"
 
@@ -534,81 +533,49 @@ class OscillinkLattice:
         dH = C.c_double(0.0)
         self._call("osc_deltaH", C.byref(dH))
         dH = float(np.float32(dH.value))
+        cap_val = rc.null_cap()
         if self._receipt_detail == "light":
             coh_sum = anchor_sum = query_sum = 0.0
-        else:
-            coh, anc, qry, null_arrays = self._receipt_rows(3.0)
-            coh_sum, anchor_sum, query_sum = float(np.sum(coh)), float(np.sum(anc)), float(np.sum(qry))
-        try:
-            cap_val = int(os.getenv("OSCILLINK_RECEIPT_NULL_CAP", "0").strip())
-        except ValueError:
-            cap_val = 0
-        if self._receipt_detail == "light":
             nulls, total = [], 0
         else:
-            i, j, z, r, total = null_arrays
+            coh, anc, qry, (i, j, z, r, total) = self._receipt_rows(3.0)
+            coh_sum, anchor_sum, query_sum = float(np.sum(coh)), float(np.sum(anc)), float(np.sum(qry))
             if cap_val > 0 and total > cap_val:  # keep the highest z (lattice.py:341-349); stable like sorted()
                 keep = np.argsort(-z[:total], kind="stable")[:cap_val]
-                nulls = self._null_dicts(i[keep], j[keep], z[keep], r[keep], cap_val)
+                nulls = rc.null_dicts(i[keep], j[keep], z[keep], r[keep], cap_val)
             else:
-                nulls = self._null_dicts(i, j, z, r, total)
-        capped = cap_val > 0 and total > cap_val
-        null_meta = {"total_null_points": total, "returned_null_points": cap_val if capped else total,
-                     "null_cap_applied": bool(capped)}
+                nulls = rc.null_dicts(i, j, z, r, total)
         nnz, _, _ = self.graph_stats()
         lu = getattr(self, "last_ustar", {})
         sig = self._signature()
-        meta: dict[str, Any] = {
-            "ustar_cached": bool(self._Ustar_sig is not None and self._Ustar_sig == sig),
-            "ustar_solves": int(self.stats["ustar_solves"]),
-            "ustar_cache_hits": int(self.stats["ustar_cache_hits"]),
-            "ustar_converged": bool(lu.get("converged", True)),
-            "ustar_res": float(lu.get("res", 0.0)),
-            "ustar_iters": int(lu.get("iters", 0)),
-            "ustar_solve_ms": float(lu.get("solve_ms", 0.0)),
-            "graph_build_ms": float(self._graph_build_ms),
-            "last_settle_ms": float(self.last.get("t_ms") or 0.0),
-            "avg_degree": float(nnz / max(self.N, 1)),
-            "edge_density": float(nnz / max(self.N * (self.N - 1), 1)),
-            "gates_min": float(np.min(self._B)),
-            "gates_max": float(np.max(self._B)),
-            "gates_mean": float(np.mean(self._B)),
-            "gates_uniform": bool(np.allclose(self._B, self._B[0])),
-            "state_sig": sig,
-            "receipt_detail": self._receipt_detail,
-            "null_points_summary": null_meta,
-        }
-        if self._receipt_secret is not None:
-            if self._signature_mode == "extended":
-                payload = {
-                    "sig_v": 1, "mode": "extended", "state_sig": sig, "deltaH_total": float(dH),
-                    "ustar_iters": int(lu.get("iters", 0)), "ustar_res": float(lu.get("res", 0.0)),
-                    "ustar_converged": bool(lu.get("converged", True)),
-                    "params": {"lamG": self.lamG, "lamC": self.lamC, "lamQ": self.lamQ, "lamP": self.lamP},
-                    "graph": {"k": self._kneighbors, "deterministic_k": self._deterministic_k,
-                              "neighbor_seed": self._neighbor_seed},
-                }
-            else:
-                payload = {"sig_v": 1, "mode": "minimal", "state_sig": sig, "deltaH_total": float(dH)}
-            raw = json.dumps(payload, sort_keys=True).encode("utf-8")
-            meta["signature"] = {"algorithm": "HMAC-SHA256", "payload": payload,
-                                 "signature": hmac.new(self._receipt_secret, raw, hashlib.sha256).hexdigest()}
-        out = {
-            "version": str(__version__),
-            "deltaH_total": float(dH),
-            "coh_drop_sum": coh_sum,
-            "anchor_pen_sum": anchor_sum,
-            "query_term_sum": query_sum,
-            "cg_iters": int(self.last.get("iters") or 0),
-            "residual": float(self.last.get("res") or 0.0),
-            "t_ms": float(self.last.get("t_ms") or 0.0),
-            "null_points": nulls,
-            "meta": meta,
-        }
+        ustar = {"ustar_iters": int(lu.get("iters", 0)), "ustar_res": float(lu.get("res", 0.0)),
+                 "ustar_converged": bool(lu.get("converged", True))}
+        settle = self._last_settle_fields()
+        meta = rc.meta(ustar_cached=self._Ustar_sig is not None and self._Ustar_sig == sig,
+                       ustar_solves=self.stats["ustar_solves"], ustar_cache_hits=self.stats["ustar_cache_hits"], ustar=ustar,
+                       ustar_solve_ms=lu.get("solve_ms", 0.0), graph_build_ms=self._graph_build_ms,
+                       last_settle_ms=settle["t_ms"], degree=rc.degree_stats(nnz, self.N), gates=rc.gate_stats(self._B),
+                       state_sig=sig, receipt_detail=self._receipt_detail,
+                       null_points_summary=rc.null_summary(total, cap_val))
+        rc.sign(meta, self._receipt_secret, self._signature_mode, state_sig=sig, deltaH=dH, ustar=ustar,
+                **self._signed_settings())
+        out = rc.record(version=__version__, deltaH=dH, coh_drop_sum=coh_sum, anchor_pen_sum=anchor_sum,
+                        query_term_sum=query_sum, **settle, null_points=nulls, meta=meta)
         if os.getenv("OSCILLINK_RECEIPT_DYNAMICS", "0").strip().lower() in {"1", "true", "yes"} and self._last_dynamics:
             meta["dynamics"] = self._last_dynamics
         self._log("receipt", {"deltaH_total": out["deltaH_total"], "ustar_cached": meta["ustar_cached"]})
         return out
+
+    def _last_settle_fields(self) -> dict[str, Any]:
+        """The last settle as a receipt reports it (record()'s cg_iters / residual / t_ms)."""
+        return {"cg_iters": int(self.last.get("iters") or 0), "residual": float(self.last.get("res") or 0.0),
+                "t_ms": float(self.last.get("t_ms") or 0.0)}
+
+    def _signed_settings(self) -> dict[str, Any]:
+        """The `params` and `graph` blocks of the extended signature payload."""
+        return {"params": {"lamG": self.lamG, "lamC": self.lamC, "lamQ": self.lamQ, "lamP": self.lamP},
+                "graph": {"k": self._kneighbors, "deterministic_k": self._deterministic_k,
+                          "neighbor_seed": self._neighbor_seed}}
 
     def _components(self):
         coh = np.zeros(self.N, dtype=np.float32)
@@ -630,22 +597,6 @@ class OscillinkLattice:
                    nat.f32(z), nat.f32(r), C.byref(n))
         return coh, anc, qry, (i, j, z, r, int(n.value))
 
-    @staticmethod
-    def _null_dicts(i, j, z, r, n):
-        """The reference's list of {"edge": [i, j], "z": .., "residual": ..} (receipts.py:63-83).  At config 3 every row has a
-        null point (a dense residual row is 29 values among 100 000 zeros), so this makes 100 000 dicts + 100 000 lists: the
-        cyclic collector, which wakes up every 700 new containers and re-walks the young ones, was two thirds of the 47 ms the
-        list took -- nothing built here can be part of a cycle, so it is paused for the construction."""
-        il, jl, zl, rl = i[:n].tolist(), j[:n].tolist(), z[:n].astype(float).tolist(), r[:n].astype(float).tolist()
-        paused = n > 2000 and gc.isenabled()
-        if paused:
-            gc.disable()
-        try:
-            return [{"edge": [a, b], "z": c, "residual": d} for a, b, c, d in zip(il, jl, zl, rl)]
-        finally:
-            if paused:
-                gc.enable()
-
     def _coherence_drop(self, Ustar: Optional[np.ndarray] = None) -> np.ndarray:
         self._ensure_device_ustar()
         return self._components()[0]
@@ -657,7 +608,7 @@ class OscillinkLattice:
         r = np.zeros(self.N, dtype=np.float32)
         n = C.c_int32(0)
         self._call("osc_null_points", float(z_th), nat.i32(i), nat.i32(j), nat.f32(z), nat.f32(r), C.byref(n))
-        return self._null_dicts(i, j, z, r, n.value)
+        return rc.null_dicts(i, j, z, r, n.value)
 
     def verify_current_receipt(self, secret) -> bool:
         from .receipts import verify_receipt
@@ -777,8 +728,8 @@ class OscillinkLattice:
         mu, sigma = float(np.mean(coh)), float(np.std(coh) + 1e-12)
         z = (coh - mu) / sigma if sigma > 0 else np.zeros_like(coh)
         score = alpha * z + (1 - alpha) * align.squeeze()
-        order = self._mmr(score, k, 0.5)
-        return [{"id": int(i), "score": float(score[i]), "align": float(align[i])} for i in order]
+        order = np.asarray(self._mmr(score, k, 0.5), dtype=np.intp)
+        return rc.bundle_dicts(order, score[order], align[order])
 
     def _mmr(self, scores: np.ndarray, k: int, lambda_div: float) -> list[int]:
         """Greedy MMR over cosine similarity of Y (graph.py:114-133) as ONE device call: per step an argmax over the
@@ -802,13 +753,7 @@ class OscillinkLattice:
         (ids, score, align), each Q x min(k, N)."""
         if self._has_comm:
             raise NotImplementedError("bundle_many: lattices with a communicator (sharded / multi-rank) are not supported")
-        P = np.asarray(psis)
-        if P.ndim != 2 or P.shape[1] != self.D:
-            raise ValueError(f"psis must be a (Q, {self.D}) array, got shape {P.shape}")
-        P = np.ascontiguousarray(P, dtype=np.float32)
-        bad = np.nonzero(~np.all(np.isfinite(P), axis=1))[0]
-        if bad.size:
-            raise ValueError(f"psis row {int(bad[0])} is not finite")
+        P = rc.check_queries(psis, self.D)
         Q = int(P.shape[0])
         kk = min(int(k), self.N) if k > 0 else 0
         ids = np.zeros((Q, kk), dtype=np.int32)
@@ -821,8 +766,7 @@ class OscillinkLattice:
             return ids, score, align
         if Q == 0:
             return []
-        return [[{"id": int(i), "score": float(s), "align": float(a)} for i, s, a in zip(ids[q].tolist(), score[q].tolist(),
-                                                                                    align[q].tolist())] for q in range(Q)]
+        return [rc.bundle_dicts(ids[q], score[q], align[q]) for q in range(Q)]
 
     def receipt_many(self, psis: np.ndarray, *, tol: float = 1e-4, max_iters: int = 256, as_arrays: bool = False):
         """`receipt()` for each row of `psis` (Q x D), as if `set_query(psis[q]); receipt()` had run with the current U,
@@ -837,44 +781,22 @@ class OscillinkLattice:
         points null_i / null_j / null_z / null_r of every query, concatenated."""
         if self._has_comm:
             raise NotImplementedError("receipt_many: lattices with a communicator (sharded / multi-rank) are not supported")
-        P = np.asarray(psis)
-        if P.ndim != 2 or P.shape[1] != self.D:
-            raise ValueError(f"psis must be a (Q, {self.D}) array, got shape {P.shape}")
-        P = np.ascontiguousarray(P, dtype=np.float32)
-        bad = np.nonzero(~np.all(np.isfinite(P), axis=1))[0]
-        if bad.size:
-            raise ValueError(f"psis row {int(bad[0])} is not finite")
+        P = rc.check_queries(psis, self.D)
         Q = int(P.shape[0])
         full = self._receipt_detail != "light"
-        try:
-            cap_val = int(os.getenv("OSCILLINK_RECEIPT_NULL_CAP", "0").strip())
-        except ValueError:
-            cap_val = 0
-        sums = np.zeros((4, Q), dtype=np.float64)  # deltaH, coh, anchor, query
-        total = np.zeros(Q, dtype=np.int32)
-        offsets = np.zeros(Q + 1, dtype=np.int64)
-        capacity = Q * (min(cap_val, self.N) if cap_val > 0 else self.N) if full else 0
-        ni = np.zeros(max(capacity, 1), dtype=np.int32)
-        nj = np.zeros(max(capacity, 1), dtype=np.int32)
-        nz = np.zeros(max(capacity, 1), dtype=np.float32)
-        nr = np.zeros(max(capacity, 1), dtype=np.float32)
+        cap_val = rc.null_cap()
+        ra = rc.ReceiptArrays(Q, (min(cap_val, self.N) if cap_val > 0 else self.N) if full else 0)
         solved = False
         if Q > 0:
             n0 = self.stats["query_basis_solves"]
             self._ensure_query_basis(tol, max_iters, float(np.max(np.abs(P))))
             solved = self.stats["query_basis_solves"] != n0
-            self._call("osc_receipt_many", nat.f32(P), Q, int(full), 3.0, max(cap_val, 0),
-                       *[sums[t].ctypes.data_as(nat.c_f64p) for t in range(4)], nat.i32(total), nat.i64(offsets),
-                       nat.i32(ni), nat.i32(nj), nat.f32(nz), nat.f32(nr), int(capacity))
-        # the float32 rounding receipt() gives its energies (a float32 dH / np.sum over float32 rows)
-        sums = sums.astype(np.float32).astype(np.float64)
-        kept = int(offsets[-1])
+            self._call("osc_receipt_many", nat.f32(P), Q, int(full), 3.0, cap_val, *ra.pointers())
+        ra.round_sums()
         self._log("receipt_many", {"Q": Q, "receipt_detail": self._receipt_detail, "basis_solved": solved,
-                                   "null_points": kept})
+                                   "null_points": ra.kept})
         if as_arrays:
-            return {"deltaH": sums[0], "coh_drop_sum": sums[1], "anchor_pen_sum": sums[2], "query_term_sum": sums[3],
-                    "null_total": total.astype(np.int64), "null_offsets": offsets, "null_i": ni[:kept].copy(),
-                    "null_j": nj[:kept].copy(), "null_z": nz[:kept].copy(), "null_r": nr[:kept].copy()}
+            return {**ra.scalar_arrays(), **ra.null_arrays()}
         if Q == 0:
             return []
         # everything but psi, the energies, the null points and the ustar fields is shared by the batch
@@ -885,72 +807,27 @@ class OscillinkLattice:
         sig_rest = {"lam": [self.lamG, self.lamC, self.lamQ, self.lamP], "chain_present": self._chain_nodes is not None,
                     "chain_len": len(self._chain_nodes) if self._chain_nodes else 0, "k": self._kneighbors,
                     "detk": self._deterministic_k, "adj": adj_sig}
-        common = {
-            "graph_build_ms": float(self._graph_build_ms),
-            "last_settle_ms": float(self.last.get("t_ms") or 0.0),
-            "avg_degree": float(nnz / max(self.N, 1)),
-            "edge_density": float(nnz / max(self.N * (self.N - 1), 1)),
-            "gates_min": float(np.min(self._B)),
-            "gates_max": float(np.max(self._B)),
-            "gates_mean": float(np.mean(self._B)),
-            "gates_uniform": bool(np.allclose(self._B, self._B[0])),
-        }
+        degree, gates = rc.degree_stats(nnz, self.N), rc.gate_stats(self._B)
+        settle, signed = self._last_settle_fields(), self._signed_settings()
         dyn = self._last_dynamics if os.getenv("OSCILLINK_RECEIPT_DYNAMICS", "0").strip().lower() in {"1", "true", "yes"} \
             else None
         psi_inf = np.max(np.abs(P), axis=1) if self.D else np.zeros(Q)
         out = []
         for q in range(Q):
             sig = self._signature_digest({"psi": np.round(P[q], 6).tolist(), **sig_rest}, self._B)
-            dH = float(sums[0, q])
+            dH = float(ra.sums[0, q])
             res_q = res_X + float(psi_inf[q]) * res_x
             ustar = {"ustar_iters": int(qb["iters"]["X"]), "ustar_res": float(res_q), "ustar_converged": bool(res_q <= tol)}
-            if full:
-                s, e = int(offsets[q]), int(offsets[q + 1])
-                nulls = self._null_dicts(ni[s:e], nj[s:e], nz[s:e], nr[s:e], e - s)
-                tot = int(total[q])
-            else:
-                nulls, tot = [], 0
-            capped = cap_val > 0 and tot > cap_val
-            meta: dict[str, Any] = {
-                "ustar_cached": not solved,
-                "ustar_solves": int(self.stats["ustar_solves"]),
-                "ustar_cache_hits": int(self.stats["ustar_cache_hits"]),
-                "ustar_converged": ustar["ustar_converged"],
-                "ustar_res": ustar["ustar_res"],
-                "ustar_iters": ustar["ustar_iters"],
-                "ustar_solve_ms": float(qb["solve_ms"]) if solved else 0.0,
-                "ustar_source": "query_basis",
-                **common,
-                "state_sig": sig,
-                "receipt_detail": self._receipt_detail,
-                "null_points_summary": {"total_null_points": tot, "returned_null_points": cap_val if capped else tot,
-                                        "null_cap_applied": bool(capped)},
-            }
-            if self._receipt_secret is not None:
-                if self._signature_mode == "extended":
-                    payload = {
-                        "sig_v": 1, "mode": "extended", "state_sig": sig, "deltaH_total": dH, **ustar,
-                        "params": {"lamG": self.lamG, "lamC": self.lamC, "lamQ": self.lamQ, "lamP": self.lamP},
-                        "graph": {"k": self._kneighbors, "deterministic_k": self._deterministic_k,
-                                  "neighbor_seed": self._neighbor_seed},
-                    }
-                else:
-                    payload = {"sig_v": 1, "mode": "minimal", "state_sig": sig, "deltaH_total": dH}
-                raw = json.dumps(payload, sort_keys=True).encode("utf-8")
-                meta["signature"] = {"algorithm": "HMAC-SHA256", "payload": payload,
-                                     "signature": hmac.new(self._receipt_secret, raw, hashlib.sha256).hexdigest()}
-            rec = {
-                "version": str(__version__),
-                "deltaH_total": dH,
-                "coh_drop_sum": float(sums[1, q]),
-                "anchor_pen_sum": float(sums[2, q]),
-                "query_term_sum": float(sums[3, q]),
-                "cg_iters": int(self.last.get("iters") or 0),
-                "residual": float(self.last.get("res") or 0.0),
-                "t_ms": float(self.last.get("t_ms") or 0.0),
-                "null_points": nulls,
-                "meta": meta,
-            }
+            nulls, tot = ra.nulls(q)
+            meta = rc.meta(ustar_cached=not solved, ustar_solves=self.stats["ustar_solves"],
+                           ustar_cache_hits=self.stats["ustar_cache_hits"], ustar=ustar,
+                           ustar_solve_ms=float(qb["solve_ms"]) if solved else 0.0, ustar_source="query_basis",
+                           graph_build_ms=self._graph_build_ms, last_settle_ms=settle["t_ms"], degree=degree, gates=gates,
+                           state_sig=sig, receipt_detail=self._receipt_detail,
+                           null_points_summary=rc.null_summary(tot, cap_val))
+            rc.sign(meta, self._receipt_secret, self._signature_mode, state_sig=sig, deltaH=dH, ustar=ustar, **signed)
+            rec = rc.record(version=__version__, deltaH=dH, coh_drop_sum=ra.sums[1, q], anchor_pen_sum=ra.sums[2, q],
+                            query_term_sum=ra.sums[3, q], **settle, null_points=nulls, meta=meta)
             if dyn:
                 meta["dynamics"] = dyn
             out.append(rec)
