@@ -841,11 +841,12 @@ def _knn_sets(lat, N, k):
                                         (16400, 130, 24, "dups")])
 def test_panel_prefilter_route_gives_the_exact_lists(amd, N, D, k, kind, monkeypatch):
     """The three device routes to the per-row top-k lists -- panel prefilter (register-resident query panel, sampled
-    thresholds, appended hits; the default from N = 16384 at D <= 768), tile prefilter (in-kernel sorted lists) and the
-    all-fp32 kernel -- on inputs that stress the panel route's assumptions: ragged N and D (both K depths, 6 and 12
-    steps), k up to 64 (keep 96: narrower sub-ranges in the select), tight clusters (thresholds near the top of the
-    range, most rows fail the proof and are redone exactly) and exact duplicates (ties at the threshold).  A row may
-    differ between routes only by a rank-k near-tie (gap below fp32 summation noise)."""
+    thresholds, appended hits; the planner's own choice from 6144 rows at D >= 512, 7168 at D >= 320 and 8193 otherwise;
+    forced here), tile prefilter (in-kernel sorted lists) and the all-fp32 kernel -- on inputs that stress the panel
+    route's assumptions: ragged N and D (both K depths, 6 and 12 steps), k up to 64 (keep 96: narrower sub-ranges in the
+    select), tight clusters (thresholds near the top of the range, most rows fail the proof and are redone exactly) and
+    exact duplicates (ties at the threshold).  A row may differ between routes only by a rank-k near-tie (gap below
+    fp32 summation noise)."""
     rng = np.random.default_rng(N + D + k)
     if kind == "iid":
         Y = rng.standard_normal((N, D), dtype=np.float32)
