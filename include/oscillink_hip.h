@@ -365,23 +365,40 @@ int osc_dynamics(osc_handle h, const float* U_prev_or_null, const float* U_next_
 /* Per-kernel HIP-event timing on the handle's own stream.  which: 0 = operator apply inside the CG loop (SpMM, the
  * CG matvec; one sample per apply = all its launches), 1 = fused x/r update, 2 = p update, 3 = kNN GEMM+top-k,
  * 4 = the initial-residual apply of a solve (same gather plus the rhs / r / p streams).  Returns samples and the
- * summed device time since the last reset.  Enabling adds two event records per sample.
- * which = 14: *launches = the kernel shape the last blocked matvec ran with
- * (0 = two 8-wave workgroups per CU, one gather round in flight; 1..6 = one workgroup per CU, four rounds in flight,
- * 8 / 12 / 16 / 20 / 24 / 28 row groups per wave; OSC_BLK_VARIANT forces one), *total_ms = 0.  which = 15: *launches = the
- * pieces the last graph build received its anchors in (0: they were resident before it started; negative: a streamed build
- * gave up on overflowing hit lists and the whole-array build ran instead), *total_ms = 0.  which = 16: *launches = the main
- * sweep of the last build's thresholds-and-hits prefilter (0: another route built the lists; 1: every rank swept every column
- * tile for its row blocks; 2: the symmetric half sweep, ONE per build whatever the world size -- the ranks of a sharded build
- * split its work items), *total_ms = 0.  which = 17 / 18 / 19: *launches = the whole-array Y -> U copies made for this
- * handle since creation (none on one GPU: U aliases Y until a settle writes it), the rows -> slab-major transposes launched
- * (k_rows_to_slab), the bytes the slab-major image of the anchors holds (0: not built; OSC_ANCHOR_SLAB=0: never), *total_ms = 0.
- * which = 20 / 21: *launches = the bytes the anchors' cached row sums W.Y hold (as many as the image once built; 0: not built
- * or dropped with the graph; OSC_ANCHOR_WY=0 or OSC_ANCHOR_SLAB=0: never), the INIT passes of solves from the anchors that
- * streamed those sums instead of gathering them, *total_ms = 0. */
+ * summed device time since the last reset.  Enabling adds two event records per sample. */
 int osc_profile_enable(osc_handle h, int32_t on);
 int osc_profile_reset(osc_handle h);
 int osc_profile_get(osc_handle h, int32_t which, int64_t* launches, double* total_ms);
+
+/* Counters of the handle's device paths (not timings): what the last build and the solves so far did, so that tests can
+ * assert the presence or the absence of a piece of work. */
+typedef struct osc_counters {
+  /* the kernel shape the last blocked matvec ran with (0 = two 8-wave workgroups per CU, one gather round in flight;
+   * 1..6 = one workgroup per CU, four rounds in flight, 8 / 12 / 16 / 20 / 24 / 28 row groups per wave; OSC_BLK_VARIANT
+   * forces one) */
+  int64_t blocked_shape;
+  /* the pieces the last graph build received its anchors in (0: they were resident before it started; negative: a
+   * streamed build gave up on overflowing hit lists and the whole-array build ran instead) */
+  int64_t create_pieces;
+  /* the main sweep of the last build's thresholds-and-hits prefilter (0: another route built the lists; 1: every rank
+   * swept every column tile for its row blocks; 2: the symmetric half sweep, ONE per build whatever the world size -- the
+   * ranks of a sharded build split its work items) */
+  int64_t knn_sweep;
+  /* the whole-array Y -> U copies made for this handle since creation (none on one GPU: U aliases Y until a settle
+   * writes it) */
+  int64_t y_to_u_copies;
+  /* the rows -> slab-major transposes launched (k_rows_to_slab) */
+  int64_t rows_to_slab_launches;
+  /* the bytes the slab-major image of the anchors holds (0: not built, or dropped with the anchors, the row order or the
+   * column window; OSC_ANCHOR_SLAB=0: never) */
+  int64_t anchor_slab_bytes;
+  /* the bytes the anchors' cached row sums W.Y hold (as many as the image once built; 0: not built, or dropped with the
+   * image or the graph; OSC_ANCHOR_WY=0 or OSC_ANCHOR_SLAB=0: never) */
+  int64_t anchor_wy_bytes;
+  /* the INIT passes of solves from the anchors that streamed those sums instead of gathering them */
+  int64_t cached_inits;
+} osc_counters;
+int osc_counters_get(osc_handle h, osc_counters* out);
 
 /* ---- multi-GPU (one process per GPU, RCCL over xGMI) ---------------------------------------- */
 /* Column-sharded CG: every rank holds the whole graph and the column slab [c0, c1) of the N x D state;

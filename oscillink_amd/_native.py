@@ -41,6 +41,14 @@ _RECEIPT_OUT = [c_i32p, c_f32p, *_RECEIPT_MANY_OUT, c_i64p, c_i64p, c_i32p, _i32
 _CHAIN_OUT = [c_f32p, c_f32p, c_f32p, c_f32p, c_f64p, c_i32p, c_i32p, c_f32p]  # z_struct .. r_path, gain, verdict, weakest k, z
 _GATED_REQUEST = [*_QUERIES, _i32, c_f32p, *_GATE_SET, *_SOLVE_SET, *_RECEIPT_SET]  # + gate_mode, gates_in
 
+
+class Counters(C.Structure):
+    """struct osc_counters of include/oscillink_hip.h (the fields' meanings are there)."""
+    _fields_ = [(name, C.c_int64) for name in (
+        "blocked_shape", "create_pieces", "knn_sweep", "y_to_u_copies", "rows_to_slab_launches", "anchor_slab_bytes",
+        "anchor_wy_bytes", "cached_inits")]
+
+
 # name -> (restype, argtypes): exactly the declarations of include/oscillink_hip.h
 SIGNATURES = {
     "osc_version": (C.c_char_p, []),
@@ -110,6 +118,7 @@ SIGNATURES = {
     "osc_profile_enable": (C.c_int, [Handle, C.c_int32]),
     "osc_profile_reset": (C.c_int, [Handle]),
     "osc_profile_get": (C.c_int, [Handle, C.c_int32, c_i64p, c_f64p]),
+    "osc_counters_get": (C.c_int, [Handle, C.POINTER(Counters)]),
     "osc_apply_info": (C.c_int, [Handle, c_i32p, c_i64p]),
     "osc_get_blocked_copy": (C.c_int, [Handle, C.c_int32, c_i32p, c_f32p, c_i32p, c_i32p, c_i32p, c_f32p, C.c_int32]),
     "osc_comm_unique_id": (C.c_int, [C.c_char_p]),

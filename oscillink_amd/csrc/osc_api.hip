@@ -472,7 +472,7 @@ int osc_set_csr(osc_handle h, const int64_t* rowptr, const int32_t* col, const f
                              l.sqrt_deg.p, l.stream);
     graph_counts(l);
     l.have_graph = true;
-    l.have_ustar = false;
+    host::changed(l.derived, host::Input::graph);
     l.knn_k = 0;
     maybe_reorder(l);
   });
@@ -503,7 +503,7 @@ int osc_set_query(osc_handle h, const float* psi, const float* gates) {
     }
     if (gates) HIP_CHECK(hipMemcpyAsync(l.B.p, gates, (size_t)l.N * 4, hipMemcpyHostToDevice, l.stream));
     sync(l);
-    l.have_ustar = false;
+    host::changed(l.derived, host::Input::query);
   });
 }
 
@@ -519,7 +519,7 @@ int osc_set_chain(osc_handle h, const int32_t* chain, const float* weights, int3
     l.chain_present = true;
     install_chain(l);
     l.lamP = lamP;
-    l.have_ustar = false;
+    host::changed(l.derived, host::Input::chain);
   });
 }
 
@@ -527,8 +527,7 @@ int osc_clear_chain(osc_handle h) {
   return guarded(h, [&](L& l) {
     l.chain_present = false;
     l.lamP = 0.0f;
-    l.have_ustar = false;
-    ++l.graph_epoch;
+    host::changed(l.derived, host::Input::chain);
   });
 }
 
@@ -537,7 +536,7 @@ int osc_set_lams(osc_handle h, float lamG, float lamC, float lamQ) {
     if (!(lamG > 0)) throw Invalid("lamG must be > 0 for SPD");
     if (lamC < 0) throw Invalid("lamC must be >= 0");
     if (lamQ < 0) throw Invalid("lamQ must be >= 0");
-    if (l.lamG != lamG || l.lamC != lamC || l.lamQ != lamQ) l.have_ustar = false;  // U* belongs to the old lams
+    if (l.lamG != lamG || l.lamC != lamC || l.lamQ != lamQ) host::changed(l.derived, host::Input::lams);
     l.lamG = lamG;
     l.lamC = lamC;
     l.lamQ = lamQ;
@@ -647,7 +646,7 @@ int osc_solve_ustar(osc_handle h, float tol, int32_t max_iters, float* Ustar_out
     const CgResult r = run_cg(l, op, b, path_active(l), max_iters, tol);
     l.Ustar.swap(l.X);
     if (l.shard_mode == 0) gather_columns(l, l.Ustar.p);  // receipts read whole rows of U* (row mode: already whole)
-    l.have_ustar = true;
+    l.derived.ustar = true;
     if (ms) *ms = now_ms() - t0;
     if (iters) *iters = r.iters;
     if (res) *res = r.res;
@@ -657,14 +656,14 @@ int osc_solve_ustar(osc_handle h, float tol, int32_t max_iters, float* Ustar_out
 
 int osc_has_ustar(osc_handle h, int32_t* yes) {
   return guarded(h, [&](L& l) {
-    if (yes) *yes = l.have_ustar ? 1 : 0;
+    if (yes) *yes = l.derived.ustar ? 1 : 0;
   });
 }
 
 int osc_get_ustar(osc_handle h, float* out) {
   return guarded(h, [&](L& l) {
     if (!out) throw Invalid("osc_get_ustar: out is NULL");
-    if (!l.have_ustar) throw StateError("osc_get_ustar: no resident U* (call osc_solve_ustar first)");
+    if (!l.derived.ustar) throw StateError("osc_get_ustar: no resident U* (call osc_solve_ustar first)");
     download_api_order(l, out, l.Ustar.p);
   });
 }
@@ -674,7 +673,7 @@ int osc_get_rows(osc_handle h, int32_t which, const int32_t* rows, int32_t n, fl
     if (n < 0 || (n > 0 && (!rows || !out))) throw Invalid("osc_get_rows: bad arguments");
     const float* src = which == 0 ? l.Y.p : which == 1 ? u_read(l) : which == 2 ? l.Ustar.p : nullptr;
     if (!src) throw Invalid("osc_get_rows: which must be 0 (Y), 1 (U) or 2 (U*)");
-    if (which == 2 && !l.have_ustar) throw StateError("osc_get_rows: no resident U* (call osc_solve_ustar first)");
+    if (which == 2 && !l.derived.ustar) throw StateError("osc_get_rows: no resident U* (call osc_solve_ustar first)");
     if (which == 1 && l.u_sharded) {  // collective in column-sharded runs, like osc_get_U
       gather_columns(l, l.U.p);
       l.u_sharded = false;
@@ -905,7 +904,7 @@ int osc_mmr_many(osc_handle h, const float* scores, int32_t Q, int32_t k, float 
 int osc_ustar_cosine_to(osc_handle h, const float* psi, float* out) {
   return guarded(h, [&](L& l) {
     if (!psi || !out) throw Invalid("osc_ustar_cosine_to: NULL buffer");
-    if (!l.have_ustar) throw StateError("osc_ustar_cosine_to: no resident U* (call osc_solve_ustar first)");
+    if (!l.derived.ustar) throw StateError("osc_ustar_cosine_to: no resident U* (call osc_solve_ustar first)");
     rows_cosine_to(l, l.Ustar.p, psi, out);
   });
 }
@@ -980,7 +979,7 @@ extern "C++" double quad_form_of_difference(L& l, const float* A, const float* B
 int osc_deltaH(osc_handle h, double* dH) {
   return guarded(h, [&](L& l) {
     require_graph(l);
-    if (!l.have_ustar) throw StateError("osc_deltaH: no resident U* (call osc_solve_ustar first)");
+    if (!l.derived.ustar) throw StateError("osc_deltaH: no resident U* (call osc_solve_ustar first)");
     if (!dH) throw Invalid("osc_deltaH: dH is NULL");
     *dH = quad_form_of_difference(l, u_read(l), l.Ustar.p);  // diff = U - U*
   });
@@ -1246,7 +1245,7 @@ static void receipt_rows(L& l, float z_th, DevBuf<float>& coh, DevBuf<float>& an
 int osc_receipt_components(osc_handle h, float* coh, float* anchor, float* query) {
   return guarded(h, [&](L& l) {
     require_graph(l);
-    if (!l.have_ustar) throw StateError("osc_receipt_components: no resident U*");
+    if (!l.derived.ustar) throw StateError("osc_receipt_components: no resident U*");
     DevBuf<float> c, a, q, nz, nr;
     DevBuf<int32_t> nj;
     receipt_rows(l, 3.0f, c, a, q, nj, nz, nr, true, false);
@@ -1264,7 +1263,7 @@ int osc_null_points(osc_handle h, float z_th, int32_t* i_out, int32_t* j_out, fl
                     int32_t* count) {
   return guarded(h, [&](L& l) {
     require_graph(l);
-    if (!l.have_ustar) throw StateError("osc_null_points: no resident U*");
+    if (!l.derived.ustar) throw StateError("osc_null_points: no resident U*");
     if (!count) throw Invalid("osc_null_points: count is NULL");
     DevBuf<float> c, a, q, nz, nr;
     DevBuf<int32_t> nj;
@@ -1283,7 +1282,7 @@ int osc_receipt_rows(osc_handle h, float z_th, float* coh, float* anchor, float*
                      float* z_out, float* r_out, int32_t* count) {
   return guarded(h, [&](L& l) {
     require_graph(l);
-    if (!l.have_ustar) throw StateError("osc_receipt_rows: no resident U*");
+    if (!l.derived.ustar) throw StateError("osc_receipt_rows: no resident U*");
     if (!count) throw Invalid("osc_receipt_rows: count is NULL");
     DevBuf<float> c, a, q, nz, nr;
     DevBuf<int32_t> nj;
@@ -1321,36 +1320,24 @@ int osc_profile_reset(osc_handle h) {
 }
 int osc_profile_get(osc_handle h, int32_t which, int64_t* launches, double* total_ms) {
   return guarded(h, [&](L& l) {
-    if (which == 16) {  // main sweep of the last build's prefilter: 0 none, 1 full (per rank), 2 half (one per build)
-      if (launches) *launches = l.knn_last.sweep();
-      if (total_ms) *total_ms = 0.0;
-      return;
-    }
-    if (which == 15) {  // pieces the last build received its anchors in (0: they were on the device before it started)
-      if (launches) *launches = l.create_pieces;
-      if (total_ms) *total_ms = 0.0;
-      return;
-    }
-    if (which >= 17 && which <= 19) {  // work an anchor start does without: counted, so that its absence can be asserted
-      // 17: whole-array Y -> U copies made for this handle; 18: k_rows_to_slab launches; 19: bytes the anchors' slab-major image holds
-      if (launches) *launches = which == 17 ? l.yu_copies : which == 18 ? l.slab_launches : (int64_t)(l.ys_ready ? l.Ys.n * 4 : 0);
-      if (total_ms) *total_ms = 0.0;
-      return;
-    }
-    if (which == 20 || which == 21) {  // 20: bytes the anchors' cached row sums W.Y hold; 21: INIT passes served from them
-      if (launches) *launches = which == 20 ? (int64_t)(l.wy_nb > 0 ? l.WYs.n * 4 : 0) : l.cached_inits;
-      if (total_ms) *total_ms = 0.0;
-      return;
-    }
-    if (which == 14) {  // the kernel shape of the last blocked matvec
-      if (launches) *launches = l.last_plan.shape;
-      if (total_ms) *total_ms = 0.0;
-      return;
-    }
-    if (which < 0 || which > 4) throw Invalid("osc_profile_get: which must be 0..4 or 14..21");
+    if (which < 0 || which > 4) throw Invalid("osc_profile_get: which must be 0..4");
     prof_drain(l);
     if (launches) *launches = l.prof_count[which];
     if (total_ms) *total_ms = l.prof_ms[which];
+  });
+}
+
+int osc_counters_get(osc_handle h, osc_counters* out) {
+  return guarded(h, [&](L& l) {
+    if (!out) throw Invalid("osc_counters_get: out is NULL");
+    out->blocked_shape = l.last_plan.shape;
+    out->create_pieces = l.create_pieces;
+    out->knn_sweep = l.knn_last.sweep();
+    out->y_to_u_copies = l.yu_copies;
+    out->rows_to_slab_launches = l.slab_launches;
+    out->anchor_slab_bytes = l.derived.ys ? (int64_t)l.Ys.n * 4 : 0;
+    out->anchor_wy_bytes = l.derived.wy_nb > 0 ? (int64_t)l.WYs.n * 4 : 0;
+    out->cached_inits = l.cached_inits;
   });
 }
 
@@ -1394,8 +1381,8 @@ int osc_comm_init(osc_handle h, const char id[128], int32_t rank, int32_t world)
     }
     if (l.c1 <= l.c0) throw Invalid("osc_comm_init: more ranks than 4-column groups");
     l.comm = comm_create(id, rank, world, l.device);
-    ++l.graph_epoch;
-    l.have_ustar = false;
+    host::changed(l.derived, host::Input::window);  // (the anchors' slab-major image is laid out over the old window)
+    host::changed(l.derived, host::Input::comm);
   });
 }
 
@@ -1437,7 +1424,7 @@ int osc_halo_info(osc_handle h, int64_t* need_rows, int64_t* need_rows_max, int6
   return guarded(h, [&](L& l) {
     if (!l.comm || l.shard_mode != 1) throw StateError("osc_halo_info: no row-sharded communicator on this handle");
     require_graph(l);
-    if (l.halo.epoch != l.graph_epoch) build_halo_plan(l);
+    if (l.halo.epoch != l.derived.epoch) build_halo_plan(l);
     const int64_t own = l.N * (l.rank + 1) / l.world - l.N * l.rank / l.world;
     if (need_rows) *need_rows = l.halo.need_rows;
     if (need_rows_max) *need_rows_max = l.halo.need_rows_max;

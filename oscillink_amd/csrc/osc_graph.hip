@@ -17,10 +17,7 @@ void graph_counts(L& h) {
 }
 
 void alloc_ell(L& h, int32_t width) {
-  h.ell_t_ready = false;
-  h.blk_nb = 0;
-  h.wy_nb = 0;
-  ++h.graph_epoch;
+  host::changed(h.derived, host::Input::graph);
   h.width = std::max<int32_t>(1, width);
   const size_t n = (size_t)h.N * h.width;
   h.ell_col.alloc(n);
@@ -38,7 +35,7 @@ bool permuted(const L& h) { return !h.perm_h.empty(); }
 
 // path Laplacian structures from the stored chain (graph.py:96-111), in the handle's current row order
 void install_chain(L& l) {
-  ++l.graph_epoch;
+  host::changed(l.derived, host::Input::chain);
   if (!l.chain_present) return;
   const int32_t len = (int32_t)l.chain_nodes.size();
   auto id = [&](int32_t v) { return permuted(l) ? l.inv_h[(size_t)v] : v; };
@@ -121,13 +118,8 @@ void move_state(L& l, const int32_t* from_d, const int32_t* relabel_d) {
   l.ell_a.swap(a2);
   l.ell_w.swap(w2);
   l.deg.swap(deg2);
-  l.ell_t_ready = false;
-  l.blk_nb = 0;
-  l.wy_nb = 0;
-  l.ys_ready = false;  // (the anchors' slab-major image is in the old row order)
-  l.have_ustar = false;
+  host::changed(l.derived, host::Input::row_order);  // (the anchors' slab-major image is in the old row order as well)
   l.u_sharded = false;
-  ++l.graph_epoch;
 }
 
 void drop_order(L& l) {  // back to the API's row order
@@ -485,8 +477,7 @@ void stream_pieces(L& h, const float* host_Y, const std::vector<int32_t>& starts
   }
   cleanup(false);
   h.create_pieces = pieces;
-  h.ys_ready = false;
-  h.wy_nb = 0;
+  host::changed(h.derived, host::Input::anchors);
   h.u_is_y = alias_u;
   if (!alias_u) h.yu_copies += 1;
 }
@@ -513,8 +504,7 @@ void build_graph(L& h, const float* host_Y) {
 static void upload_anchors(L& h, const float*& host_Y) {
   if (host_Y == nullptr) return;
   upload_rows(h, h.Y.p, host_Y);
-  h.ys_ready = false;
-  h.wy_nb = 0;
+  host::changed(h.derived, host::Input::anchors);
   reset_u_to_y(h);
   host_Y = nullptr;
 }
@@ -800,7 +790,7 @@ static bool build_graph_once(L& h, const float* host_Y) {
   drop_order(h);  // the build works on the API's row order
   const int32_t N = (int32_t)h.N;
   h.k_eff = std::min<int32_t>(h.k_eff, std::max<int32_t>(1, N - 1));  // lattice.py:60
-  h.have_ustar = false;
+  host::changed(h.derived, host::Input::graph);  // (the lists below already replace the old graph's)
   if (N <= 1) {  // graph.py:30-32
     upload_anchors(h, host_Y);
     alloc_ell(h, 1);

@@ -21,6 +21,7 @@
 #include "../../include/oscillink_hip.h"
 #include "common.hpp"
 #include "host_logic.hpp"
+#include "derived_state.hpp"
 #include "comm.hpp"
 #include "knn.hpp"
 #include "knn_gemm.hpp"
@@ -29,9 +30,6 @@
 #include "dynamics.hpp"
 #include "small.hpp"
 #include "query.hpp"
-
-using namespace osc;
-
 
 using namespace osc;
 
@@ -73,22 +71,21 @@ struct osc_lattice {
   // readers go through u_read(), the first settle writes U.  Cleared by osc_set_U(ptr) and at the successful end of a settle.
   bool u_is_y = false;
   // slab-major image of the anchors over the handle's window (the layout launch_rows_to_slab writes), built on first use
-  // by a blocked INIT pass that starts from Y and kept until Y's device copy changes (OSC_ANCHOR_SLAB=0: never built)
+  // by a blocked INIT pass that starts from Y and kept until Y's device copy, the row order or the window changes (OSC_ANCHOR_SLAB=0: never built)
   DevBuf<float> Ys;
-  bool ys_ready = false;
   bool anchor_slab = true;
   // The anchors' row sums W.Y, slab-major like Ys: exactly what the gathering INIT pass of a solve that starts from Y has in
   // hand when its rows are complete.  Written by that pass as a by-product (run_cg), then every later anchor start on this
   // graph copy streams its INIT pass (k_init_cached) instead of gathering.  The sums depend on Y, the graph and the slot
-  // placement of the block-major copy: wy_nb is the block count they were formed with (0: none held), dropped with blk_nb
-  // and with ys_ready.  OSC_ANCHOR_WY=0 or OSC_ANCHOR_SLAB=0: never built.
+  // placement of the block-major copy (derived_state.hpp: anchor_wy).  OSC_ANCHOR_WY=0 or OSC_ANCHOR_SLAB=0: never built.
   DevBuf<float> WYs;
-  int wy_nb = 0;
   bool anchor_wy = true;
-  int64_t cached_inits = 0;  // INIT passes served from WYs (osc_profile_get slot 21; slot 20: the bytes WYs holds)
-  int64_t yu_copies = 0;     // whole-array Y -> U copies made for this handle (osc_profile_get slot 17)
-  int64_t slab_launches = 0;  // k_rows_to_slab launches (slot 18)
-  bool have_ustar = false;
+  int64_t cached_inits = 0;  // INIT passes served from WYs (osc_counters::cached_inits)
+  int64_t yu_copies = 0;     // whole-array Y -> U copies made for this handle (osc_counters::y_to_u_copies)
+  int64_t slab_launches = 0;  // k_rows_to_slab launches (osc_counters::rows_to_slab_launches)
+  // Which of the arrays computed from other state (ell_col_t / ell_w_t, blk_*, Ys, WYs, Ustar; by epoch: halo, query) are
+  // current.  Dropped by host::changed(derived, <what changed>) alone (derived_state.hpp has the dependency table).
+  host::Derived derived;
   DevBuf<float> Uprev;  // state before the last settle (dynamics snapshot, lattice.py:825-927); allocated on first use
   bool have_uprev = false;
   DevBuf<float> B, psi;
@@ -156,14 +153,12 @@ struct osc_lattice {
   bool x_last_form = true;            // ... and the expected last iteration finishes x itself without storing r (OSC_X_DEFER=2: off)
   DevBuf<int32_t> ell_col_t;          // transposed ELL for the one-launch path (built on first use per graph)
   DevBuf<float> ell_w_t;
-  bool ell_t_ready = false;
   // block-major copy of the graph for the source-blocked CG matvec (k_spmm_blocked), built on first use per graph
   DevBuf<int2> blk_slots, blk_rest, blk_over;
-  int blk_nb = 0;          // blocks of the copy held (0 = none / stale)
   int spmm_blocked = -1;   // < 0 by lattice size, 0 off, > 0 = that many source blocks (OSC_SPMM_BLOCKED)
   int blk_variant = -1;    // kernel shape of the blocked matvec (kBlkShapes); -1 = by geometry, OSC_BLK_VARIANT forces one
   mutable int blk_resident[kBlkShapeCount] = {-1};  // workgroups per XCD each shape gets resident ([0] < 0: not queried yet)
-  host::ApplyPlan last_plan;  // the apply plan of the last general-path solve (osc_apply_info, osc_profile_get slot 14)
+  host::ApplyPlan last_plan;  // the apply plan of the last general-path solve (osc_apply_info, osc_counters::blocked_shape)
   double temporal_mb = 200.0;  // largest solve (5 arrays x N x window) whose update kernels use ordinary instead of nontemporal accesses
   bool spmm_deep = true;   // re-ordered lattices: the operator apply with 8 gathers in flight per row (OSC_SPMM_DEEP=0: the usual 2)
   bool blk_init = true;    // the initial residual goes through the blocked matvec as well (OSC_BLK_INIT=0: plain INIT apply)
@@ -191,10 +186,9 @@ struct osc_lattice {
   int fake_row_shards = 0; // test hook (OSC_ROW_FAKE_SHARDS=V): V row shards on this one GPU, collectives local
   DevBuf<double> sums;     // [2][ld] completed column sums of the row-sharded CG
   DevBuf<float> comm_buf;
-  // halo plan of the row-sharded CG (built on first use per graph / chain / communicator: graph_epoch)
-  uint64_t graph_epoch = 1;
+  // halo plan of the row-sharded CG (built on first use per graph / chain / communicator: derived.epoch)
   struct HaloPlan {
-    uint64_t epoch = 0;                      // graph_epoch it was built for (0 = none)
+    uint64_t epoch = 0;                      // derived.epoch it was built for (0 = none)
     bool full = false;                       // halo ~ everything: exchange whole row blocks instead (all-gather)
     std::vector<int64_t> give_off, need_off; // [world + 1] offsets of each peer's slice in give_idx / need_idx
     DevBuf<int32_t> give_idx, need_idx;      // my rows each peer needs (sorted) / the peers' rows I need (sorted)
@@ -209,10 +203,10 @@ struct osc_lattice {
   int64_t prof_count[5] = {0, 0, 0, 0, 0};
   double prof_ms[5] = {0, 0, 0, 0, 0};
   // multi-query bundles (osc_query.hip): the query basis M X = lamG Y, M x = lamQ B of the graph / gates / chain / lams it
-  // was solved for (the caller keys it; a new graph_epoch drops it), its per-row constants and the batch scratch
+  // was solved for (the caller keys it; a new derived.epoch drops it), its per-row constants and the batch scratch
   struct QueryState {
     bool have = false;
-    uint64_t epoch = 0;        // graph_epoch of the basis
+    uint64_t epoch = 0;        // derived.epoch of the basis
     float scale = 0.f;         // |psi|_inf the x part was solved for (its residual target is tol / (2 scale))
     DevBuf<float> X, x4;       // N x ld, N x 4 (column 0 = x)
     DevBuf<float> s;           // [N] x / (sd + 1e-12)

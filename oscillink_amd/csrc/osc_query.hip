@@ -11,14 +11,14 @@ namespace {
 
 void ensure_yn(L& l) {
   auto& q = l.query;
-  if (q.yn_epoch == l.graph_epoch && q.Yn.p) return;
+  if (q.yn_epoch == l.derived.epoch && q.Yn.p) return;
   q.Yn.alloc((size_t)l.N * l.ld);
   launch_rows_normalise(l.Y.p, q.Yn.p, (int32_t)l.N, l.D, l.ld, l.stream);
-  q.yn_epoch = l.graph_epoch;
+  q.yn_epoch = l.derived.epoch;
 }
 
 void require_basis(const L& l) {
-  if (!l.query.have || l.query.epoch != l.graph_epoch)
+  if (!l.query.have || l.query.epoch != l.derived.epoch)
     throw StateError("no query basis for the current graph (call osc_query_basis first)");
 }
 
@@ -82,7 +82,7 @@ void query_basis_solve(L& l, float tol, int32_t max_iters, float scale, bool fre
   if (!(tol > 0.f) || !std::isfinite(tol)) throw Invalid("osc_query_basis: tol must be > 0");
   if (!(scale > 0.f) || !std::isfinite(scale)) throw Invalid("osc_query_basis: scale must be a finite value > 0");
   auto& q = l.query;
-  if (!q.have || q.epoch != l.graph_epoch) fresh = true;
+  if (!q.have || q.epoch != l.derived.epoch) fresh = true;
   ensure_cg_scratch(l, max_iters);
   // the lattice's own solves keep their iteration predictions and residual history
   int saved_pred[3];
@@ -157,7 +157,7 @@ void query_basis_solve(L& l, float tol, int32_t max_iters, float scale, bool fre
   l.history = std::move(saved_hist);
   q.have = true;
   ++q.gen;
-  q.epoch = l.graph_epoch;
+  q.epoch = l.derived.epoch;
   q.scale = scale;
   if (ms) *ms = now_ms() - t0;
 }

@@ -67,7 +67,7 @@ host::ApplyPlan apply_plan(const L& h, int32_t c0, int32_t c1, int32_t ld, bool 
 }
 
 BlockedView blocked_view(L& h, int nb) {
-  if (h.blk_nb != nb) {
+  if (h.derived.blk_nb != nb) {
     DevBuf<unsigned> cnt;
     cnt.alloc(1);
     HIP_CHECK(hipMemsetAsync(cnt.p, 0, 4, h.stream));
@@ -89,7 +89,7 @@ BlockedView blocked_view(L& h, int nb) {
     launch_blocked_fill(h.ell_col.p, h.ell_w.p, h.deg.p, h.width, (int32_t)h.N, nb, h.blk_slots.p, h.blk_rest.p, h.blk_over.p, cnt.p,
                         h.stream);
     sync(h);  // cnt goes out of scope
-    h.blk_nb = nb;
+    h.derived.blk_nb = nb;
   }
   BlockedView v{};
   v.slots = h.blk_slots.p;
@@ -155,11 +155,11 @@ bool run_cg_small(L& h, const OpParams& op, const CgBuffers& b, bool with_path, 
   volatile uint32_t* host_words = reinterpret_cast<volatile uint32_t*>(h.res_host);
   if (polled) host_words[nslots] = kPending;
   SmallArgs a{};
-  if (!h.ell_t_ready) {
+  if (!h.derived.ell_t) {
     h.ell_col_t.alloc((size_t)h.N * h.width);
     h.ell_w_t.alloc((size_t)h.N * h.width);
     launch_transpose_ell(h.ell_col.p, h.ell_w.p, (int32_t)h.N, h.width, h.ell_col_t.p, h.ell_w_t.p, h.stream);
-    h.ell_t_ready = true;
+    h.derived.ell_t = true;
   }
   a.g = graph_view(h, with_path);
   a.col_t = h.ell_col_t.p;
@@ -226,7 +226,7 @@ bool run_cg_small(L& h, const OpParams& op, const CgBuffers& b, bool with_path, 
 CgResult run_cg_rows(L& h, const OpParams& op, const CgBuffers& b, bool with_path, int max_iters, float tol);
 bool row_mode(const L& h);
 
-// rows -> slab-major over [c0, c1) (k_rows_to_slab), counted per handle (osc_profile_get slot 18)
+// rows -> slab-major over [c0, c1) (k_rows_to_slab), counted per handle (osc_counters::rows_to_slab_launches)
 void rows_to_slab(L& h, const float* src, float* dst, int32_t ld, int32_t c0, int32_t c1, int grid, const float* sub) {
   launch_rows_to_slab(src, dst, h.N, ld, c0, c1, grid, h.stream, sub);
   h.slab_launches += (c1 - c0 + 2047) / 2048;
@@ -237,10 +237,10 @@ void rows_to_slab(L& h, const float* src, float* dst, int32_t ld, int32_t c0, in
 // the U* solve, the query basis), else x0 transposed into `scratch`.
 static const float* init_operand(L& h, const CgBuffers& b, float* scratch, int grid) {
   if (h.anchor_slab && b.x0 == h.Y.p && b.ld == h.ld && b.c0 == h.c0 && b.c1 == h.c1) {
-    if (!h.ys_ready) {
+    if (!h.derived.ys) {
       h.Ys.alloc((size_t)h.N * h.ld);
       rows_to_slab(h, h.Y.p, h.Ys.p, h.ld, h.c0, h.c1, grid);
-      h.ys_ready = true;
+      h.derived.ys = true;
     }
     return h.Ys.p;
   }
@@ -426,16 +426,16 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
     // one gathers them and leaves them behind (one more store per row), the later ones stream them (k_init_cached: the
     // same r, z and r . z sums to the bit).
     const bool wy_route = h.anchor_wy && h.anchor_slab && ba.X == h.Ys.p && bi.Y == nullptr;
-    if (wy_route && h.wy_nb == ba.nb) {
+    if (wy_route && h.derived.wy_nb == ba.nb) {
       bi.WY = h.WYs.p;
       launch_init_cached(ba, grid, h.stream, bi, plan.shape);
       h.cached_inits += 1;
     } else if (wy_route) {
-      h.wy_nb = 0;
+      h.derived.wy_nb = 0;  // (not current while this launch rewrites them)
       h.WYs.alloc((size_t)h.N * h.ld);
       bi.WY = h.WYs.p;
       launch_apply_blocked(ba, grid, h.stream, &bi, plan.shape, true);
-      h.wy_nb = ba.nb;
+      h.derived.wy_nb = ba.nb;
     } else {
       launch_apply_blocked(ba, grid, h.stream, &bi, plan.shape);
     }
@@ -778,14 +778,14 @@ void build_halo_plan(L& h) {
     hp.recv.alloc(std::max<size_t>(1, ni.size() * (size_t)h.ld));
   }
   sync(h);
-  hp.epoch = h.graph_epoch;
+  hp.epoch = h.derived.epoch;
 }
 
 // the per-iteration halo exchange of `arr` (N x ld, every rank's own row block current): afterwards the rows this
 // rank's operator gathers from are current too
 void halo_exchange(L& h, float* arr, int32_t ld) {
   if (!h.comm) return;
-  if (h.halo.epoch != h.graph_epoch) build_halo_plan(h);
+  if (h.halo.epoch != h.derived.epoch) build_halo_plan(h);
   L::HaloPlan& hp = h.halo;
   if (hp.full || ld != h.ld) {
     exchange_rows(h, arr, ld);

@@ -238,25 +238,14 @@ class OscillinkLattice:
         self._call("osc_spmm_plan", C.byref(ln), C.byref(sc), C.byref(xw))
         sb, ba = C.c_int32(0), C.c_int64(0)
         self._call("osc_apply_info", C.byref(sb), C.byref(ba))
-        shape, pieces, unused = C.c_int64(0), C.c_int64(0), C.c_double(0.0)
-        self._call("osc_profile_get", 14, C.byref(shape), C.byref(unused))
-        self._call("osc_profile_get", 15, C.byref(pieces), C.byref(unused))
-        sweep = C.c_int64(0)
-        self._call("osc_profile_get", 16, C.byref(sweep), C.byref(unused))
-        copies, slabs, ys = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        self._call("osc_profile_get", 17, C.byref(copies), C.byref(unused))
-        self._call("osc_profile_get", 18, C.byref(slabs), C.byref(unused))
-        self._call("osc_profile_get", 19, C.byref(ys), C.byref(unused))
-        wy, cached = C.c_int64(0), C.c_int64(0)
-        self._call("osc_profile_get", 20, C.byref(wy), C.byref(unused))
-        self._call("osc_profile_get", 21, C.byref(cached), C.byref(unused))
+        counters = nat.Counters()
+        self._call("osc_counters_get", C.byref(counters))
         return {"prefilter": int(pf.value), "fallback_rows": int(fb.value), "small_solves": int(ss.value),
                 "reordered": int(ro.value), "clustering": float(cc.value), "apply_launches": int(ln.value),
                 "apply_slab_cols": int(sc.value), "apply_xs_workgroups": int(xw.value),
-                "apply_src_blocks": int(sb.value), "blocked_applies": int(ba.value), "apply_blocked_shape": int(shape.value),
-                "create_pieces": int(pieces.value), "knn_sweep": int(sweep.value),
-                "y_to_u_copies": int(copies.value), "rows_to_slab_launches": int(slabs.value),
-                "anchor_slab_bytes": int(ys.value), "anchor_wy_bytes": int(wy.value), "cached_inits": int(cached.value)}
+                "apply_src_blocks": int(sb.value), "blocked_applies": int(ba.value),
+                "apply_blocked_shape": int(counters.blocked_shape),
+                **{name: int(getattr(counters, name)) for name, _ in nat.Counters._fields_[1:]}}
 
     def halo_info(self) -> dict[str, int]:
         """Row-sharded runs (OSC_SHARD=row under a communicator): the rows of the search direction this rank receives

@@ -232,3 +232,47 @@ def test_counters(amd, switch, monkeypatch):
             assert info["rows_to_slab_launches"] == (3 if switch == "OSC_ANCHOR_SLAB" else 1), info
     finally:
         lat.close()
+
+
+def test_joining_a_communicator_drops_the_image_and_the_sums(amd, monkeypatch):
+    """`osc_comm_init` gives the handle another column window, and `Ys` / `WYs` are laid out over the window.  Per rank of a
+    two-rank loopback group: handle A solves on the full window first and joins then, handle B joins before it has solved
+    anything.  A's image and sums are gone after the call, and its next solve equals B's to the bit."""
+    from oscillink_amd import _native as nat
+    from oscillink_amd import sharding
+
+    _clean_env(monkeypatch)
+    N, D, ld = 20000, 256, 256
+    Y, psi, _, _ = _inputs(N, D, seed=11)
+    uid_b = sharding.loopback_id()
+
+    def join(lat, uid, rank, world):
+        nat.check(nat.lib().osc_comm_init(lat._h, bytes(uid), int(rank), int(world)), lat._h, "osc_comm_init")
+
+    def rank_fn(rank, comm):
+        uid_a, _, world = comm
+        a, b = amd.Oscillink(Y, kneighbors=16), amd.Oscillink(Y, kneighbors=16)
+        try:
+            for lat in (a, b):
+                lat.set_query(psi)
+            a.solve_Ustar(use_cache=False)
+            info = a.build_info()
+            assert info["anchor_slab_bytes"] == N * ld * 4 == info["anchor_wy_bytes"], info
+            join(a, uid_a, rank, world)
+            info = a.build_info()
+            assert info["anchor_slab_bytes"] == 0 and info["anchor_wy_bytes"] == 0, info
+            join(b, uid_b, rank, world)
+            out = []
+            for lat in (a, b):
+                us = lat.solve_Ustar(use_cache=False).copy()
+                info = lat.build_info()
+                assert info["apply_src_blocks"] > 0 and info["anchor_slab_bytes"] > 0, info
+                out.append((us, lat.residual_history()))
+            return out
+        finally:
+            a.close()
+            b.close()
+
+    for rank, ((ua, ha), (ub, hb)) in enumerate(sharding.run_loopback_ranks(2, rank_fn, timeout_s=120.0)):
+        assert np.array_equal(ua, ub), (rank, float(np.abs(ua - ub).max()))
+        assert ha == hb, (rank, ha, hb)

@@ -38,6 +38,18 @@ def test_library_exports_every_declared_symbol(lib):
     assert lib.osc_device_count(ctypes.byref(n)) == 0 and n.value >= 0
 
 
+def test_counters_struct_matches_the_header():
+    from oscillink_amd import _native
+
+    txt = open(os.path.join(ROOT, "include", "oscillink_hip.h")).read()
+    body = re.search(r"typedef struct osc_counters \{(.*?)\} osc_counters;", txt, re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    fields = [m for decl in re.findall(r"int64_t\s+([^;]+);", body) for m in re.findall(r"\w+", decl)]
+    assert len(fields) == 8 and not re.sub(r"int64_t\s+[^;]+;", "", body).strip()  # nothing but int64_t fields
+    assert [(n, ctypes.c_int64) for n in fields] == list(_native.Counters._fields_)
+    assert ctypes.sizeof(_native.Counters) == 8 * len(fields)
+
+
 def test_validation_precedes_device_and_missing_gpu_fails_loudly(lib):
     import oscillink_amd
     from oscillink_amd import _native
