@@ -111,6 +111,13 @@ int osc_spmm_plan(osc_handle h, int32_t* launches, int32_t* slab_cols, int32_t* 
  * aid) */
 int osc_apply_info(osc_handle h, int32_t* src_blocks, int64_t* blocked_applies);
 
+/* the ring of kept search directions of the last general-path solve: slots = K (1: no ring -- x was updated every
+ * iteration; 2..4: the last K directions were kept and x was written by whole passes over them only; OSC_X_RING = 0 off /
+ * 2..4 forces K, capped by max_iters), flushes = its passes that ran inside an iteration because a slot was about to be
+ * overwritten, passes = all its x passes (one where the solve took at most K iterations), bytes = device memory the
+ * handle holds for the ring (measurement aid) */
+int osc_x_ring_info(osc_handle h, int32_t* slots, int64_t* flushes, int64_t* passes, int64_t* bytes);
+
 /* the block-major copy of the graph the blocked matvec walks, built for `nb` source blocks (test / diagnostic aid; no
  * reference counterpart): slot_col / slot_w [nb][N][4] = {neighbour row, W_ij} per (source block, row, slot), unused slots
  * {first row of the block, 0}; rows whose edges exceed 4 nb slots list the rest in over_col / over_w[over_first[i] ..

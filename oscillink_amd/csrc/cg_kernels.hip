@@ -5,6 +5,8 @@
 //                 with the right-hand side, residual, Jacobi scaling and first search direction (solver.py:19-22).
 //   k_update_xr : x += alpha p ; r -= alpha Ap ; column sums of r.r and r.z   (solver.py:27-29, 32-33)
 //   k_update_p  : p = z + beta p with z = r / (Md + 1e-12) recomputed          (solver.py:32, 35)
+//   k_update_x_ring : x += alpha_1 p_1 + ... + alpha_M p_M from a ring of kept directions, the x update of the solves that
+//                 keep one (solver.py:27 applied M iterations at a time, same roundings)
 //   k_reduce_*  : deterministic second stage of the column reductions -> alpha, beta, residual
 //
 // Layout: every N x D array is row-major with pitch ld (multiple of 4 floats) so one wave reads a row as
@@ -963,6 +965,8 @@ __global__ __launch_bounds__(256) void k_init_finish(const InitFinishArgs a) {
 // last one): this kernel then moves r and Ap only (run_cg).
 // STORE_R = false (with WITHX): the form for an iteration expected to be the solve's last -- x is finished here and the new
 // r only feeds the two column sums; should the solve go on after all, the host has the r update redone with a store.
+// WITHX = false, STORE_R = false: the expected last iteration of a solve that keeps its directions in a ring (run_cg) -- r
+// and Ap are read, nothing but the two column sums is written.
 template <int LPR, int NCH, bool WITHX, bool STORE_R = true>
 __global__ __launch_bounds__(256) void k_update_xr(const UpdateArgs a) {
   constexpr int RPW = 64 / LPR;
@@ -1028,6 +1032,7 @@ __global__ __launch_bounds__(256) void k_update_p(const UpdateArgs a) {
   const int32_t ld = a.ld;
   const bool tmp = a.temporal != 0;
   [[maybe_unused]] const float* const xin = a.Xin != nullptr ? a.Xin : a.X;  // (UpdateArgs::Xin)
+  float* const pout = a.Pout != nullptr ? a.Pout : a.P;                       // (UpdateArgs::Pout)
   int coff[NCH];
   bool cok[NCH];
   float4 be[NCH], al[NCH];
@@ -1060,8 +1065,53 @@ __global__ __launch_bounds__(256) void k_update_p(const UpdateArgs a) {
         const float4 r = ld4_sel(a.R + off, tmp);
         p.x = fmaf(p.x, be[ch].x, r.x * invMd); p.y = fmaf(p.y, be[ch].y, r.y * invMd);
         p.z = fmaf(p.z, be[ch].z, r.z * invMd); p.w = fmaf(p.w, be[ch].w, r.w * invMd);
-        st4(a.P + poff, p);
+        st4(pout + poff, p);
       }
+    }
+  }
+}
+
+// x = xin + alpha_1 p_1 + ... + alpha_M p_M from a ring of kept directions (XRingArgs), oldest first: the only kernel of such
+// a solve that touches x.  All M + 1 loads of a chunk are issued before the first fmaf.  In place (xin == X): a thread reads
+// and writes the same element.
+template <int LPR, int NCH, int M>
+__global__ __launch_bounds__(256) void k_update_x_ring(const XRingArgs a) {
+  constexpr int RPW = 64 / LPR;
+  if (a.gate != nullptr && *a.gate <= a.gate_tol) return;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int sub = lane / LPR, lr = lane % LPR;
+  const int32_t ld = a.ld;
+  const bool tmp = a.temporal != 0;
+  const float* const xin = a.Xin != nullptr ? a.Xin : a.X;
+  int coff[NCH];
+  bool cok[NCH];
+  float4 al[M][NCH];
+#pragma unroll
+  for (int ch = 0; ch < NCH; ++ch) {
+    coff[ch] = a.c0 + (ch * LPR + lr) * 4;
+    cok[ch] = coff[ch] < a.c1;
+#pragma unroll
+    for (int m = 0; m < M; ++m) al[m][ch] = cok[ch] ? ld4(a.alpha[m] + coff[ch]) : f4(0.f);
+  }
+  const int64_t rend = a.N;  // streaming kernels: plain grid-stride over the row range
+  for (int64_t rb = a.row0 + ((int64_t)blockIdx.x * 4 + wave) * RPW; rb < rend; rb += (int64_t)gridDim.x * 4 * RPW) {
+    const int row = (int)rb + sub;
+    if (row >= rend) continue;
+#pragma unroll
+    for (int ch = 0; ch < NCH; ++ch) {
+      if (!cok[ch]) continue;
+      const size_t off = (size_t)row * ld + coff[ch];
+      const size_t poff = a.pblk ? blk_off(a.pblk, row, coff[ch]) : off;
+      float4 x = ld4_sel(xin + off, tmp);
+      float4 p[M];
+#pragma unroll
+      for (int m = 0; m < M; ++m) p[m] = ld4_sel(a.P[m] + poff, tmp);
+#pragma unroll
+      for (int m = 0; m < M; ++m) {
+        x.x = fmaf(p[m].x, al[m][ch].x, x.x); x.y = fmaf(p[m].y, al[m][ch].y, x.y);
+        x.z = fmaf(p[m].z, al[m][ch].z, x.z); x.w = fmaf(p[m].w, al[m][ch].w, x.w);
+      }
+      st4_sel(a.X + off, x, tmp);
     }
   }
 }
@@ -1395,8 +1445,11 @@ void launch_update_xr(const UpdateArgs& a, int grid, hipStream_t s) {
 #define CALL(L, C) hipLaunchKernelGGL((k_update_xr<L, C, true>), dim3(grid), dim3(256), 0, s, a)
 #define CALL_NOX(L, C) hipLaunchKernelGGL((k_update_xr<L, C, false>), dim3(grid), dim3(256), 0, s, a)
 #define CALL_LAST(L, C) hipLaunchKernelGGL((k_update_xr<L, C, true, false>), dim3(grid), dim3(256), 0, s, a)
+#define CALL_BARE(L, C) hipLaunchKernelGGL((k_update_xr<L, C, false, false>), dim3(grid), dim3(256), 0, s, a)
   if (a.xmode & OSC_XMODE_XR_LAST) {
     OSC_SHAPE_SWITCH(sh, CALL_LAST);
+  } else if (a.xmode & OSC_XMODE_XR_BARE) {
+    OSC_SHAPE_SWITCH(sh, CALL_BARE);
   } else if (a.xmode & OSC_XMODE_XR_SKIPS_X) {
     OSC_SHAPE_SWITCH(sh, CALL_NOX);
   } else {
@@ -1405,6 +1458,7 @@ void launch_update_xr(const UpdateArgs& a, int grid, hipStream_t s) {
 #undef CALL
 #undef CALL_NOX
 #undef CALL_LAST
+#undef CALL_BARE
   HIP_CHECK(hipGetLastError());
 }
 
@@ -1427,6 +1481,26 @@ void launch_update_x(const UpdateArgs& a, int grid, hipStream_t s) {  // x += al
 #define CALL(L, C) hipLaunchKernelGGL((k_update_p<L, C, true, false>), dim3(grid), dim3(256), 0, s, a)
   OSC_SHAPE_SWITCH(sh, CALL);
 #undef CALL
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_update_x_ring(const XRingArgs& a, int grid, hipStream_t s) {
+  const Shape sh = pick_shape(a.c1 - a.c0);
+#define CALL1(L, C) hipLaunchKernelGGL((k_update_x_ring<L, C, 1>), dim3(grid), dim3(256), 0, s, a)
+#define CALL2(L, C) hipLaunchKernelGGL((k_update_x_ring<L, C, 2>), dim3(grid), dim3(256), 0, s, a)
+#define CALL3(L, C) hipLaunchKernelGGL((k_update_x_ring<L, C, 3>), dim3(grid), dim3(256), 0, s, a)
+#define CALL4(L, C) hipLaunchKernelGGL((k_update_x_ring<L, C, 4>), dim3(grid), dim3(256), 0, s, a)
+  switch (a.M) {
+    case 1: OSC_SHAPE_SWITCH(sh, CALL1); break;
+    case 2: OSC_SHAPE_SWITCH(sh, CALL2); break;
+    case 3: OSC_SHAPE_SWITCH(sh, CALL3); break;
+    case 4: OSC_SHAPE_SWITCH(sh, CALL4); break;
+    default: throw std::runtime_error("x ring pass: 1 to 4 directions");
+  }
+#undef CALL1
+#undef CALL2
+#undef CALL3
+#undef CALL4
   HIP_CHECK(hipGetLastError());
 }
 

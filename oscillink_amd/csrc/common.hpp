@@ -203,8 +203,30 @@ struct UpdateArgs {
   // the x an x update READS (nullptr: X itself).  The settle that starts from the anchors without copying them: the one
   // launch that applies iteration 1's update reads x0 from the anchors and writes x into X (run_cg)
   const float* Xin;
+  // where k_update_p writes the new direction (nullptr: over P).  A solve that keeps its directions in a ring (run_cg) reads
+  // the previous one from P and writes the next slot; no kernel of such a solve touches x but k_update_x_ring
+  float* Pout;
 };
-constexpr int32_t OSC_XMODE_XR_SKIPS_X = 1, OSC_XMODE_P_APPLIES_X = 2, OSC_XMODE_XR_LAST = 4;
+// OSC_XMODE_XR_BARE (with XR_SKIPS_X): the x-r kernel of the expected last iteration of a ring solve -- x left alone, the new
+// r not stored
+constexpr int32_t OSC_XMODE_XR_SKIPS_X = 1, OSC_XMODE_P_APPLIES_X = 2, OSC_XMODE_XR_LAST = 4, OSC_XMODE_XR_BARE = 8;
+
+// k_update_x_ring: x = Xin (nullptr: X) + sum over m < M of alpha[m] * P[m], applied in ascending m with one fmaf each --
+// the roundings the per-iteration x updates perform through memory
+constexpr int OSC_X_RING_MAX = 4;
+struct XRingArgs {
+  float* X;
+  const float* Xin;
+  const float* P[OSC_X_RING_MAX];      // kept directions, oldest first (layout: pblk)
+  const float* alpha[OSC_X_RING_MAX];  // [ld] each
+  int32_t M;
+  int64_t N, row0;
+  int32_t ld, c0, c1;
+  const float* gate;
+  float gate_tol;
+  int64_t pblk;
+  int32_t temporal;
+};
 
 struct Gate {
   const float* p;
@@ -273,6 +295,7 @@ void launch_spmm(int mode, const SpmmArgs& a, int grid, hipStream_t s);
 void launch_update_xr(const UpdateArgs& a, int grid, hipStream_t s);
 void launch_update_p(const UpdateArgs& a, int grid, hipStream_t s);
 void launch_update_x(const UpdateArgs& a, int grid, hipStream_t s);  // x += alpha p (UpdateArgs::xmode)
+void launch_update_x_ring(const XRingArgs& a, int grid, hipStream_t s);
 // column reductions over `nb` partial rows
 void launch_reduce_init(const float* part, int nb, int32_t ld, int32_t c0, int32_t c1, double* rz, hipStream_t s);
 void launch_reduce_alpha(const float* part, int nb, int32_t ld, int32_t c0, int32_t c1, const double* rz,

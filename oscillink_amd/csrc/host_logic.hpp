@@ -10,6 +10,8 @@
 //   plan_apply                        : how a CG solve launches its operator apply (the one place that decides it)
 //   blk_place_row                     : host model of k_blk_count / k_blk_fill (one row of the block-major graph copy)
 //   CgXSchedule                       : which launch of a CG solve carries which iteration's x update (run_cg)
+//   plan_x_ring / CgXRing             : how many search directions a solve keeps, and when a pass applies them to x (swept by
+//                                       tests/host_logic/sweep_x_ring.cpp)
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -544,6 +546,99 @@ struct CgXSchedule {
   // the solve stopped in `iters`: apply its x update now (it rode in a gated p update that did not run)?
   bool finish_at_end(int iters) const { return xdefer && x_rides_gated == iters; }
   void finished(int it) { x_done = it, x_rides_gated = 0; }  // after the x update of `it` was launched on its own
+};
+
+// ---- the ring of kept search directions (run_cg) ----------------------------------------------------------------------
+// x is an output of the recurrence only: x = x0 + sum alpha_it p_it.  With the last K directions (and their alpha vectors)
+// kept -- direction `it` in slot it % K -- no p update and no x-r kernel touches x; one pass (k_update_x_ring) applies up
+// to K pending directions at once, in ascending iteration order, with the fmaf the per-iteration updates perform.
+// plan_x_ring picks K (1 = off: the paths CgXSchedule serves); CgXRing says when a pass goes out.
+struct XRingInputs {
+  int predicted = 0;        // iterations the handle's previous solve of this kind took (0: unknown)
+  int max_iters = 1;
+  int64_t array_bytes = 0;  // one N x ld array
+  int64_t free_bytes = 0;   // device memory a new slot could come from (the slots already held count as free)
+  bool ungated = false;     // sharded solve whose stop test runs beside it: its speculative launches carry no gate
+  bool xdefer = true;       // (OSC_X_DEFER=0: x is updated beside r, every iteration)
+  int forced = -1;          // OSC_X_RING: 0 off, 2..4 that K, < 0 by the rules below
+};
+constexpr int kXRingMax = 4;
+inline int plan_x_ring(const XRingInputs& in) {
+  if (in.ungated || !in.xdefer || in.forced == 0) return 1;  // a flush needs the gate of the iteration it belongs to
+  int K;
+  if (in.forced > 0) {
+    K = std::min(in.forced, kXRingMax);
+  } else {
+    if (in.predicted <= 0) return 1;  // without a prediction the solve cannot tell one pass from many
+    // (The cache-resident regime, UpdateArgs::temporal, is no input: K - 1 more arrays were expected to cost there, and
+    // measured the ring pays at every size tried, K = 4 most -- reset_U + settle of 4 iterations at 20 000 x 128 226 -> 218 us,
+    // 20 000 x 256 313 -> 299, 30 000 x 256 389 -> 375, 38 000 x 256 470 -> 450, 40 000 x 256 479 -> 462, p10-p90 bands apart:
+    // DESIGN.md section 3.)
+    K = std::min(in.predicted, kXRingMax);
+  }
+  K = std::min(K, in.max_iters);  // (more slots than iterations are never written)
+  while (K > 1 && (int64_t)(K - 1) * in.array_bytes > in.free_bytes / 4) --K;
+  return std::max(K, 1);
+}
+
+// Which x passes a solve with K >= 2 slots launches.  Every flush belongs to the iteration being enqueued and carries its
+// gate (it ran iff that iteration was a real one; the host reads the residuals in order, so it knows); the passes the host
+// launches when nothing is enqueued behind an iteration it knows to be real, and the one at the end, carry none.
+struct CgXRing {
+  int K = 2;
+  bool last_form = true;
+  int stop_guess = 0, max_iters = 1;
+  int applied = 0;                      // directions 1 .. applied are in x (their pass ran, or is enqueued ungated)
+  int flush_iter = 0, flush_upto = 0;   // the gated flush not yet known to have run: of iteration flush_iter, up to flush_upto
+  int r_unstored = 0;                   // the iteration whose x-r kernel did not store r (0: none)
+  int flushes = 0, passes = 0;          // gated flushes / all x passes launched
+  struct Pass {
+    int first, count;  // directions first .. first + count - 1 (count 0: no launch)
+  };
+  // the host knows that iterations up to `real` are real ones: a flush that belongs to one of them has run
+  void settle(int real) {
+    if (flush_iter != 0 && flush_iter <= real) applied = flush_upto, flush_iter = 0;
+  }
+  // Iteration it >= 2 is being enqueued (its predecessor is known to be real or is what its gate tests): the pass to launch,
+  // gated like it, before its p update overwrites slot it % K, which holds direction it - K.
+  Pass flush_before_p(int it) {
+    settle(it - 1);
+    const int pending = it - 1 - applied;
+    if (pending < K) return Pass{0, 0};
+    const Pass p{applied + 1, pending};
+    flush_iter = it, flush_upto = it - 1;
+    ++flushes, ++passes;
+    return p;
+  }
+  // the expected last iteration's x-r kernel neither touches x nor stores r
+  bool xr_last(int it) {
+    const bool last = last_form && (it == stop_guess || it == max_iters);
+    if (last) r_unstored = it;
+    return last;
+  }
+  bool restore_r(int it) {
+    if (r_unstored != it) return false;
+    r_unstored = 0;
+    return true;
+  }
+  // nothing is enqueued behind `it` for now and the host has seen its predecessor unconverged: the ungated pass for the
+  // pending directions up to `it`, behind its x-r kernel
+  Pass pass_before_wait(int it) {
+    settle(it);
+    const Pass p{applied + 1, it - applied};
+    applied = it;
+    if (p.count > 0) ++passes;
+    return p;
+  }
+  // the solve stopped in `iters`: the ungated pass for what is still pending
+  Pass final_pass(int iters) {
+    settle(iters);
+    flush_iter = 0;  // (a flush of iteration iters + 1 was gated off)
+    const Pass p{applied + 1, iters - applied};
+    applied = iters;
+    if (p.count > 0) ++passes;
+    return p;
+  }
 };
 
 }  // namespace host

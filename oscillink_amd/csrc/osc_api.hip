@@ -30,6 +30,7 @@ void read_env_solver(L& h) {
     h.x_defer = v != 0;
     h.x_last_form = v == 1;
   }
+  if (num("OSC_X_RING", v)) h.x_ring_force = v <= 0 ? 0 : std::max(2, std::min(v, host::kXRingMax));
   if (num("OSC_SMALL_PATH", v)) h.small_path = v != 0;
   if (num("OSC_ANCHOR_SLAB", v)) h.anchor_slab = v != 0;
   if (num("OSC_ANCHOR_WY", v)) h.anchor_wy = v != 0;  // (needs the anchors' image: OSC_ANCHOR_SLAB=0 switches it off too, run_cg)
@@ -310,6 +311,18 @@ int osc_apply_info(osc_handle h, int32_t* src_blocks, int64_t* blocked_applies) 
   return guarded(h, [&](L& l) {
     if (src_blocks) *src_blocks = l.last_plan.src_blocks;
     if (blocked_applies) *blocked_applies = l.blk_applies;
+  });
+}
+
+int osc_x_ring_info(osc_handle h, int32_t* slots, int64_t* flushes, int64_t* passes, int64_t* bytes) {
+  return guarded(h, [&](L& l) {
+    if (slots) *slots = l.x_ring_k;
+    if (flushes) *flushes = l.x_ring_flushes;
+    if (passes) *passes = l.x_ring_passes;
+    if (bytes) {
+      *bytes = (int64_t)l.alpha_ring.n * 4;
+      for (const DevBuf<float>& r : l.xring) *bytes += (int64_t)r.n * 4;
+    }
   });
 }
 

@@ -151,6 +151,12 @@ struct osc_lattice {
   int predicted_iters[3] = {0, 0, 0};  // iterations the last general-path solve of each kind (CgBuffers::kind) took (0 = unknown)
   bool x_defer = true;                // the x update rides in the next iteration's p update (run_cg; OSC_X_DEFER=0: beside the r update)
   bool x_last_form = true;            // ... and the expected last iteration finishes x itself without storing r (OSC_X_DEFER=2: off)
+  // The ring of kept search directions (run_cg; host_logic.hpp: plan_x_ring): up to three arrays beside P, and the alpha
+  // vectors of the kept iterations.  Scratch like P and AP: nothing in them outlives a solve, they stay with the handle.
+  DevBuf<float> xring[3], alpha_ring;
+  int x_ring_force = -1;              // OSC_X_RING: 0 off, 2..4 that many slots, unset: by the planner
+  int x_ring_k = 1;                   // slots of the last general-path solve (1: no ring), its gated flushes and all its x passes
+  int64_t x_ring_flushes = 0, x_ring_passes = 0;
   DevBuf<int32_t> ell_col_t;          // transposed ELL for the one-launch path (built on first use per graph)
   DevBuf<float> ell_w_t;
   // block-major copy of the graph for the source-blocked CG matvec (k_spmm_blocked), built on first use per graph

@@ -1,6 +1,8 @@
 // Operator parameters, apply plans and the CG drivers of liboscillink_hip.so (see osc_internal.hpp).
 #include "osc_internal.hpp"
 
+#include <limits>
+
 // ---- operators ------------------------------------------------------------------------------------
 bool path_active(const L& h) { return h.chain_present && h.lamP > 0.0f; }
 
@@ -528,6 +530,75 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
   xs.ungated = overlap;
   xs.stop_guess = stop_guess;
   xs.max_iters = max_iters;
+  // The ring of kept directions (host_logic.hpp: plan_x_ring, CgXRing): K >= 2 slots -- direction `it` in slot it % K, its
+  // alpha in the same slot of h.alpha_ring -- and x is written by k_update_x_ring alone: once per solve where the solve
+  // takes at most K iterations.  K = 1: everything below runs as CgXSchedule says.
+  host::XRingInputs ri;
+  ri.predicted = stop_guess;
+  ri.max_iters = max_iters;
+  ri.array_bytes = (int64_t)h.N * b.ld * 4;
+  ri.ungated = overlap;
+  ri.xdefer = xdefer;
+  ri.forced = h.x_ring_force;
+  const size_t ring_n = (size_t)h.N * b.ld;
+  int held = 0;  // slots the handle holds at this size: only a solve that wants more asks the device what is free
+  while (held < host::kXRingMax - 1 && h.xring[held].n >= ring_n) ++held;
+  ri.free_bytes = std::numeric_limits<int64_t>::max();
+  if (host::plan_x_ring(ri) - 1 > held) {
+    size_t free_b = 0, total_b = 0;
+    HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+    ri.free_bytes = (int64_t)free_b + ri.array_bytes * held;
+  }
+  host::CgXRing ring;
+  ring.K = host::plan_x_ring(ri);
+  ring.last_form = h.x_last_form;
+  ring.stop_guess = stop_guess;
+  ring.max_iters = max_iters;
+  float* slot[host::kXRingMax] = {nullptr, nullptr, nullptr, nullptr};
+  float* aslot[host::kXRingMax] = {nullptr, nullptr, nullptr, nullptr};
+  if (ring.K > 1) {
+    try {
+      for (int j = 0; j < ring.K - 1; ++j)
+        if (h.xring[j].n < ring_n) h.xring[j].alloc(ring_n);
+      const size_t an = (size_t)std::max(h.ld, b.ld);
+      if (h.alpha_ring.n < an * host::kXRingMax) h.alpha_ring.alloc(an * host::kXRingMax);
+      for (int i = 0; i < ring.K; ++i) aslot[i] = h.alpha_ring.p + (size_t)i * an;
+    } catch (const HipError&) {  // no solve fails over its ring
+      (void)hipGetLastError();
+      for (DevBuf<float>& r : h.xring) r.release();
+      ring.K = 1;
+    }
+  }
+  const bool ringed = ring.K > 1;
+  if (ringed) {
+    slot[1 % ring.K] = Pbuf;  // direction 1 is where the INIT pass left z
+    for (int i = 0, j = 0; i < ring.K; ++i)
+      if (i != 1 % ring.K) slot[i] = h.xring[j++].p;
+  }
+  auto dir = [&](int it) { return slot[it % ring.K]; };
+  auto alpha_of = [&](int it) { return ringed ? aslot[it % ring.K] : h.alpha.p; };
+  auto ring_pass = [&](host::CgXRing::Pass ps, const float* gate) {
+    if (ps.count <= 0) return;
+    XRingArgs xa{};
+    xa.X = b.X;
+    xa.Xin = ps.first == 1 ? x1_in : nullptr;  // (nothing applied yet: x is still x0, the anchors of an aliased start)
+    xa.M = ps.count;
+    for (int m = 0; m < ps.count; ++m) {
+      xa.P[m] = dir(ps.first + m);
+      xa.alpha[m] = alpha_of(ps.first + m);
+    }
+    xa.N = h.N;
+    xa.ld = b.ld;
+    xa.gate = gate;
+    xa.gate_tol = tol;
+    xa.pblk = ua.pblk;
+    xa.temporal = ua.temporal;
+    for (int32_t s0 = b.c0; s0 < b.c1; s0 += 2048) {
+      xa.c0 = s0;
+      xa.c1 = std::min(b.c1, s0 + 2048);
+      launch_update_x_ring(xa, grid, h.stream);
+    }
+  };
   auto finish_x = [&](int it) {
     ua.gate = nullptr;
     ua.xmode = OSC_XMODE_XR_SKIPS_X | OSC_XMODE_P_APPLIES_X;
@@ -542,8 +613,22 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
     sa.gate_tol = tol;
     ua.gate = g.p;
     ua.gate_tol = tol;
-    const host::CgXSchedule::IterForm form = xs.enqueue(it, speculative);
-    if (it > 1) {
+    host::CgXSchedule::IterForm form{false, host::CgXSchedule::XR_SKIPS_X};
+    if (!ringed) form = xs.enqueue(it, speculative);
+    if (ringed && it > 1) {
+      ProfScope ps(h, 2, it);
+      // the slot p_it goes to still holds a direction x lacks: this iteration's flush, then p_it = z + beta p_{it-1}
+      const host::CgXRing::Pass fl = ring.flush_before_p(it);
+      ring_pass(fl, g.p);
+      ua.xmode = 0;
+      ua.Xin = nullptr;
+      ua.P = dir(it - 1);
+      ua.Pout = dir(it);
+      for_windows(ua, [&](const UpdateArgs& w) { launch_update_p(w, grid, h.stream); });
+      ba.X = dir(it);
+      cf.X = dir(it);
+      sa.X = dir(it);
+    } else if (it > 1) {
       ProfScope ps(h, 2, it);
       // p = z + beta p (solver.py:32-36), and iteration it - 1's x += alpha p (solver.py:27) with the p it replaces
       ua.xmode = form.p_applies_x ? OSC_XMODE_P_APPLIES_X : 0;
@@ -564,8 +649,14 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
     } else {
       spmm_slabbed(h, plan, SPMM_AP, sa, grid, it);
     }
-    launch_reduce_alpha(h.part0.p, grid + (ba.nb > 0 ? cf.chunks : 0), b.ld, b.c0, b.c1, h.rz.p, h.alpha.p, g, h.stream);
-    {
+    launch_reduce_alpha(h.part0.p, grid + (ba.nb > 0 ? cf.chunks : 0), b.ld, b.c0, b.c1, h.rz.p, alpha_of(it), g, h.stream);
+    if (ringed) {
+      ProfScope ps(h, 1, it);
+      ua.alpha = alpha_of(it);
+      ua.xmode = OSC_XMODE_XR_SKIPS_X | (ring.xr_last(it) ? OSC_XMODE_XR_BARE : 0);
+      ua.Xin = nullptr;
+      for_windows(ua, [&](const UpdateArgs& w) { launch_update_xr(w, grid, h.stream); });
+    } else {
       ProfScope ps(h, 1, it);
       ua.xmode = form.xr == host::CgXSchedule::XR_LAST ? OSC_XMODE_XR_LAST : form.xr == host::CgXSchedule::XR_SKIPS_X ? OSC_XMODE_XR_SKIPS_X : 0;
       ua.Xin = it == 1 ? x1_in : nullptr;  // (the forms that carry an x update here carry iteration it's)
@@ -628,6 +719,10 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
   for (int it = 1; it <= max_iters; ++it) {
     if (it < max_iters && it != stop_guess && enqueued == it) {
       enqueue_iter(++enqueued, true);  // speculative: no-ops if `it` converged (overlap: ungated, scratch arrays only)
+    } else if (ringed) {
+      // nothing is enqueued behind this iteration for now and it is a real one: the pending directions up to it go into x
+      // behind its x-r kernel, while the host waits for its residual
+      ring_pass(ring.pass_before_wait(it), nullptr);
     } else if (xs.finish_before_wait(it)) {
       // nothing is enqueued behind this iteration for now (the expected last one): its x update goes out at once.  The
       // host has seen iteration it - 1 unconverged, so iteration `it` is a real one whatever its residual will say.
@@ -641,8 +736,9 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
       break;
     }
     if (it < max_iters && enqueued == it) {  // the guess was wrong: go on
-      if (xs.restore_r(it)) {  // ... from the r this iteration computed but did not keep
+      if (ringed ? ring.restore_r(it) : xs.restore_r(it)) {  // ... from the r this iteration computed but did not keep
         ua.gate = nullptr;
+        ua.alpha = alpha_of(it);
         ua.xmode = OSC_XMODE_XR_SKIPS_X;
         ua.Xin = nullptr;
         for_windows(ua, [&](const UpdateArgs& w) { launch_update_xr(w, grid, h.stream); });
@@ -653,7 +749,14 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
   h.predicted_iters[b.kind] = out.iters;
   // the last iteration's x update rode in a gated p update that did not run (the solve converged under a speculative
   // iteration): alpha and p are still that iteration's
-  if (xs.finish_at_end(out.iters)) finish_x(out.iters);
+  if (ringed) {  // what the ring still holds for x: with at most K iterations the solve's only x pass
+    ring_pass(ring.final_pass(out.iters), nullptr);
+  } else if (xs.finish_at_end(out.iters)) {
+    finish_x(out.iters);
+  }
+  h.x_ring_k = ring.K;
+  h.x_ring_flushes = ringed ? ring.flushes : 0;
+  h.x_ring_passes = ringed ? ring.passes : 0;
   // The solution is complete once the last residual is out; what may still be queued are the gated-off launches of
   // the speculative iteration (they return at once and write nothing).  With the mapped read-back the stream is left
   // to drain on its own -- later calls are ordered behind it anyway; the copy + event path keeps its full wait.

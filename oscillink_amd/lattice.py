@@ -238,6 +238,8 @@ class OscillinkLattice:
         self._call("osc_spmm_plan", C.byref(ln), C.byref(sc), C.byref(xw))
         sb, ba = C.c_int32(0), C.c_int64(0)
         self._call("osc_apply_info", C.byref(sb), C.byref(ba))
+        xk, xf, xp, xb = C.c_int32(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._call("osc_x_ring_info", C.byref(xk), C.byref(xf), C.byref(xp), C.byref(xb))
         counters = nat.Counters()
         self._call("osc_counters_get", C.byref(counters))
         return {"prefilter": int(pf.value), "fallback_rows": int(fb.value), "small_solves": int(ss.value),
@@ -245,6 +247,8 @@ class OscillinkLattice:
                 "apply_slab_cols": int(sc.value), "apply_xs_workgroups": int(xw.value),
                 "apply_src_blocks": int(sb.value), "blocked_applies": int(ba.value),
                 "apply_blocked_shape": int(counters.blocked_shape),
+                "x_ring_slots": int(xk.value), "x_ring_flushes": int(xf.value), "x_ring_passes": int(xp.value),
+                "x_ring_bytes": int(xb.value),
                 **{name: int(getattr(counters, name)) for name, _ in nat.Counters._fields_[1:]}}
 
     def halo_info(self) -> dict[str, int]:
