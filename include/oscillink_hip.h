@@ -225,6 +225,20 @@ int osc_bundle_many(osc_handle h, const float* psis, int32_t Q, int32_t k, float
 int osc_receipt_many(osc_handle h, const float* psis, int32_t Q, int32_t detail, float z_th, int32_t null_cap, double* dH,
                      double* coh_sum, double* anchor_sum, double* query_sum, int32_t* null_total, int64_t* null_offsets,
                      int32_t* i_out, int32_t* j_out, float* z_out, float* r_out, int64_t capacity);
+/* Not in the reference: chain_receipt(chain, z_th) (lattice.py:466-528) for Q (query, chain) pairs with the current graph,
+ * gates, own chain and lambdas held fixed, U*(psi_q) from the resident basis.  psis is Q x D.
+ * chain_offsets holds Q + 1 node offsets from 0 into chain_nodes (API row ids); a chain has 2 to 1024 nodes, repeats allowed.
+ * The path residuals use the lattice's own chain (osc_set_chain) with its weights when it has one, else the unit-weight path
+ * of the argument (lattice.py:479-483).  A chain of L nodes has L - 1 edges: query q's edge t is entry
+ * chain_offsets[q] - q + t of z_struct / z_path / r_struct / r_path (chain_offsets[Q] - Q entries each).  Per query: gain
+ * (coherence_gain, added in fp64 in edge order), verdict (1: every edge's max(z_struct, z_path) <= z_th), weakest_k (the
+ * first edge whose max(z) is strictly greater than every earlier one, from -1.0; -1 when none is) and weakest_z (that
+ * maximum, -1.0 with weakest_k = -1).  A non-finite query gives non-finite answers for that query alone.
+ * OSC_E_STATE without a basis, OSC_E_UNSUPPORTED with a communicator, OSC_E_INVALID for a node outside [0, N) or a chain
+ * outside 2..1024 nodes. */
+int osc_chain_receipt_many(osc_handle h, const float* psis, int32_t Q, const int64_t* chain_offsets,
+                           const int32_t* chain_nodes, float z_th, float* z_struct, float* z_path, float* r_struct,
+                           float* r_path, double* gain, int32_t* verdict, int32_t* weakest_k, float* weakest_z);
 /* mmr_diversify (graph.py:114-133) for Q score columns at once: scores N x Q (API row order, queries contiguous per row);
  * out_idx Q x min(k, N) API ids, the same picks as osc_mmr per column up to rounding of the similarities. */
 int osc_mmr_many(osc_handle h, const float* scores, int32_t Q, int32_t k, float lambda_div, int32_t* out_idx);

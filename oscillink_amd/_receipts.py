@@ -46,16 +46,83 @@ def null_dicts(i, j, z, r, n):
             gc.enable()
 
 
-def check_queries(psis, D: int) -> np.ndarray:
-    """`psis` as a contiguous float32 (Q, D) array with finite rows, or the ValueError every batched call raises."""
+def check_queries(psis, D: int, finite: bool = True) -> np.ndarray:
+    """`psis` as a contiguous float32 (Q, D) array with finite rows, or the ValueError every batched call raises.
+    finite=False lets non-finite rows through (chain_receipt_many: such a query gets non-finite answers, as in the loop)."""
     P = np.asarray(psis)
     if P.ndim != 2 or P.shape[1] != D:
         raise ValueError(f"psis must be a (Q, {D}) array, got shape {P.shape}")
     P = np.ascontiguousarray(P, dtype=np.float32)
     bad = np.nonzero(~np.all(np.isfinite(P), axis=1))[0]
-    if bad.size:
+    if bad.size and finite:
         raise ValueError(f"psis row {int(bad[0])} is not finite")
     return P
+
+
+MAX_CHAIN = 1024  # nodes of one query's chain (include/oscillink_hip.h)
+CHAIN_EDGE_KEYS = ("chain_z_struct", "chain_z_path", "chain_r_struct", "chain_r_path")
+
+
+def chain_block(chains, Q: int, N: int):
+    """chain_receipt_many's `chains` -- one chain (a sequence of ints, shared by every query) or a sequence of Q chains --
+    as (lists, offsets, nodes): per query the chain as a list of ints, the Q + 1 int64 node offsets and the int32 nodes of
+    osc_chain_receipt_many.  ValueError for a chain count other than Q, a chain outside 2..MAX_CHAIN nodes, a node that is
+    no integer or lies outside [0, N)."""
+    def one(ch, who):
+        try:
+            arr = np.asarray(ch)
+            if arr.ndim != 1 or (arr.size and not np.issubdtype(arr.dtype, np.integer)):
+                raise TypeError
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: a chain must be a sequence of integers") from None
+        if arr.size < 2:
+            raise ValueError(f"{who}: chain must contain at least two indices")
+        if arr.size > MAX_CHAIN:
+            raise ValueError(f"{who}: a chain has at most {MAX_CHAIN} indices, got {arr.size}")
+        if arr.min() < 0 or arr.max() >= N:
+            raise ValueError(f"{who}: chain indices out of bounds")
+        return [int(c) for c in arr]
+
+    try:
+        n = len(chains)
+    except TypeError:
+        raise ValueError("chains must be one chain (a sequence of integers) or a sequence of Q chains") from None
+    first = chains[0] if n else None
+    if n and (isinstance(first, (int, np.integer)) or (isinstance(chains, np.ndarray) and chains.ndim == 1)):
+        lists = [one(chains, "chain")] * Q
+    else:
+        if n != Q:
+            raise ValueError(f"chains must be one chain or hold {Q} chains, got {n}")
+        lists = [one(chains[q], f"query {q}") for q in range(Q)]
+    offsets = np.zeros(Q + 1, dtype=np.int64)
+    np.cumsum([len(ch) for ch in lists], out=offsets[1:])
+    nodes = np.array([c for ch in lists for c in ch], dtype=np.int32)
+    return lists, offsets, nodes
+
+
+def chain_receipt_dict(chain, *, weakest_k, weakest_z, gain, verdict, z_struct, z_path, r_struct, r_path) -> dict[str, Any]:
+    """chain_receipt()'s dict (lattice.py:466-528) for one chain from the device's numbers: the per-edge arrays hold the
+    chain's len(chain) - 1 edges; weakest_k = -1 (no edge's max(z) exceeds -1) reads edge [-1, -1]."""
+    wk = int(weakest_k)
+    return {
+        "verdict": bool(verdict),
+        "weakest_link": {"k": wk, "edge": [chain[wk], chain[wk + 1]] if wk >= 0 else [-1, -1], "zscore": float(weakest_z)},
+        "coherence_gain": float(gain),
+        "edges": [{"k": t, "edge": [chain[t], chain[t + 1]], "z_struct": float(z_struct[t]), "z_path": float(z_path[t]),
+                   "r_struct": float(r_struct[t]), "r_path": float(r_path[t])} for t in range(len(chain) - 1)],
+    }
+
+
+def chain_receipt_dicts(chains, arr: dict) -> list[dict[str, Any]]:
+    """Q chain receipts from the `as_arrays` form (chain_offsets over edges, the flat per-edge arrays, the per-query
+    scalars); chains: per query the chain as a list of ints."""
+    out = []
+    for q, ch in enumerate(chains):
+        s, e = int(arr["chain_offsets"][q]), int(arr["chain_offsets"][q + 1])
+        out.append(chain_receipt_dict(ch, weakest_k=arr["chain_weakest_k"][q], weakest_z=arr["chain_weakest_z"][q],
+                                      gain=arr["chain_gain"][q], verdict=arr["chain_verdict"][q],
+                                      **{k[len("chain_"):]: arr[k][s:e] for k in CHAIN_EDGE_KEYS}))
+    return out
 
 
 def bundle_dicts(ids, score, align) -> list[dict[str, Any]]:

@@ -26,7 +26,7 @@ GATE_METHODS = {"direct": 0, "cg": 1}  # osc_corpus_gates' method codes
 RECEIPT_DETAILS = {"light": 0, "full": 1}  # osc_corpus_refine_receipts' detail codes (set_receipt_detail's words)
 RECEIPT_Z_TH = 3.0  # receipt()'s null-point threshold
 EDGE_PREFIX = 2048  # edges under the state signature (OscillinkLattice._edge_prefix)
-MAX_CHAIN = 1024  # nodes of one query's chain (include/oscillink_hip.h)
+MAX_CHAIN = rc.MAX_CHAIN
 
 
 class _RefineOut:
@@ -479,16 +479,9 @@ class Corpus:
                 out[-1]["chain_receipt"] = None
             if ch is not None:
                 e0 = int(chain["edge_offsets"][q])
-                wk = int(c_weak_k[q])
-                out[-1]["chain_receipt"] = {
-                    "verdict": bool(c_verdict[q]),
-                    "weakest_link": {"k": wk, "edge": [ch[wk], ch[wk + 1]] if wk >= 0 else [-1, -1],
-                                     "zscore": float(c_weak_z[q])},
-                    "coherence_gain": float(c_gain[q]),
-                    "edges": [{"k": t, "edge": [ch[t], ch[t + 1]], "z_struct": float(c_edge[0, e0 + t]),
-                               "z_path": float(c_edge[1, e0 + t]), "r_struct": float(c_edge[2, e0 + t]),
-                               "r_path": float(c_edge[3, e0 + t])} for t in range(len(ch) - 1)],
-                }
+                out[-1]["chain_receipt"] = rc.chain_receipt_dict(
+                    ch, weakest_k=c_weak_k[q], weakest_z=c_weak_z[q], gain=c_gain[q], verdict=c_verdict[q],
+                    z_struct=c_edge[0, e0:], z_path=c_edge[1, e0:], r_struct=c_edge[2, e0:], r_path=c_edge[3, e0:])
         return out
 
     def diffusion_gates_many(self, psis, top_k: int, *, kneighbors: int = 6, row_cap_val: float = 1.0, beta: float = 1.0,

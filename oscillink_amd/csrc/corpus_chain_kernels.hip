@@ -2,6 +2,7 @@
 // solve with lamP L_path (k_cq_solve_chain) and chain_receipt() of every lattice's own chain (k_cq_chain_receipt), one
 // workgroup per lattice each.  The settle and the receipt of such a call are corpus_receipt_kernels.hip's chain instances.
 // Only a call with chains launches any of them; no workgroup waits on another.
+#include "chain_receipt_dev.hpp"
 #include "common.hpp"
 #include "corpus_receipts.hpp"
 
@@ -56,7 +57,8 @@ __global__ __launch_bounds__(256) void k_cq_solve_chain(const CqChainPcgArgs ca)
 //   path entries; mu = sum R / K, sigma = sqrt(sum R^2 / K - mu^2) + 1e-12; z = (R_ij - mu) / sigma with R_ij = 0 when j is not
 //   an entry of the row; gain term 0.5 lamC max(a_ij, 0) (|Yn_i - Yn_j|^2 - |Un_i - Un_j|^2).
 // One thread then adds the gain in fp64 in edge order, takes the first edge whose max(z) is strictly greater than every
-// earlier one, from -1 (lattice.py:489, 506), and forms the verdict all(max(z) <= z_th).
+// earlier one, from -1 (lattice.py:489, 506), and forms the verdict all(max(z) <= z_th): chain_receipt_dev.hpp's rules, which
+// the built lattice's batched call (chain_many_kernels.hip) runs as well.
 __global__ __launch_bounds__(256) void k_cq_chain_receipt(const CqChainEdgesArgs a) {
   __shared__ double s_term[kCqMaxChainEdges], s_zmax[kCqMaxChainEdges];
   __shared__ int32_t s_slot[kCqMaxRows];
@@ -122,9 +124,7 @@ __global__ __launch_bounds__(256) void k_cq_chain_receipt(const CqChainEdgesArgs
       dy = wave_sum_f(dy);
       term = 0.5 * (double)g.lamC * (double)wij * ((double)dy - (double)du);
     }
-    const double mu_s = s1 / (double)K;
-    const double var_s = fmax(s2 / (double)K - mu_s * mu_s, 0.0);
-    const double z_s = ((double)rs - mu_s) / (sqrt(var_s) + 1e-12);
+    const double z_s = chain_row_z(s1, s2, rs, (double)K);
     // path row i (every chain node owns one)
     s1 = s2 = 0.0;
     const int ps = s_slot[li];
@@ -135,34 +135,23 @@ __global__ __launch_bounds__(256) void k_cq_chain_receipt(const CqChainEdgesArgs
         s2 += (double)R * (double)R;
         if (pcol[e] == lj) rp = R;
       }
-    const double mu_p = s1 / (double)K;
-    const double var_p = fmax(s2 / (double)K - mu_p * mu_p, 0.0);
-    const double z_p = ((double)rp - mu_p) / (sqrt(var_p) + 1e-12);
+    const double z_p = chain_row_z(s1, s2, rp, (double)K);
     if (lane == 0) {
       out[t] = (float)z_s;
       out[a.chain.cap + t] = (float)z_p;
       out[2 * a.chain.cap + t] = rs;
       out[3 * a.chain.cap + t] = rp;
       s_term[t] = term;
-      s_zmax[t] = z_p > z_s ? z_p : z_s;  // Python's max(z_struct, z_path)
+      s_zmax[t] = chain_zmax(z_s, z_p);
     }
   }
   __syncthreads();
   if (tid == 0) {
-    double gain = 0.0, worst = -1.0;
-    int wk = -1, ok = 1;
-    for (int t = 0; t < E; ++t) {
-      gain += s_term[t];
-      if (s_zmax[t] > worst) {
-        worst = s_zmax[t];
-        wk = t;
-      }
-      if (!(s_zmax[t] <= (double)a.z_th)) ok = 0;
-    }
-    a.gain[lat] = gain;
-    a.verdict[lat] = ok;
-    a.weak_k[lat] = wk;
-    a.weak_z[lat] = (float)worst;
+    const ChainVerdict v = chain_finish(s_term, s_zmax, E, a.z_th);
+    a.gain[lat] = v.gain;
+    a.verdict[lat] = v.ok;
+    a.weak_k[lat] = v.weak_k;
+    a.weak_z[lat] = (float)v.worst;
   }
 }
 

@@ -906,6 +906,19 @@ int osc_receipt_many(osc_handle h, const float* psis, int32_t Q, int32_t detail,
   });
 }
 
+int osc_chain_receipt_many(osc_handle h, const float* psis, int32_t Q, const int64_t* chain_offsets,
+                           const int32_t* chain_nodes, float z_th, float* z_struct, float* z_path, float* r_struct,
+                           float* r_path, double* gain, int32_t* verdict, int32_t* weakest_k, float* weakest_z) {
+  return guarded(h, [&](L& l) {
+    if (Q < 0) throw Invalid("osc_chain_receipt_many: Q must be >= 0");
+    if (Q > 0 && (!psis || !chain_offsets || !chain_nodes || !z_struct || !z_path || !r_struct || !r_path || !gain ||
+                  !verdict || !weakest_k || !weakest_z))
+      throw Invalid("osc_chain_receipt_many: NULL buffer");
+    query_chain_receipt_many(l, psis, Q, chain_offsets, chain_nodes, z_th, z_struct, z_path, r_struct, r_path, gain, verdict,
+                             weakest_k, weakest_z);
+  });
+}
+
 int osc_mmr_many(osc_handle h, const float* scores, int32_t Q, int32_t k, float lambda_div, int32_t* out_idx) {
   return guarded(h, [&](L& l) {
     if (Q < 0) throw Invalid("osc_mmr_many: Q must be >= 0");

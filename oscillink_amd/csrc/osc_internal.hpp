@@ -238,6 +238,11 @@ struct osc_lattice {
     DevBuf<float> U0, rz, rr, zt, roz, ror;  // U0: X + x psi0^T; rz / rj / rr: N x qs candidates; zt: qs x N
     DevBuf<int32_t> rj, rtot, rsel, roi, roj;
     DevBuf<int64_t> roff;
+    // chain_receipt_many: one chunk's queries, units, path entries and results; nothing is kept
+    DevBuf<float> cm_psi, cm_pa, cm_edge, cm_wz;
+    DevBuf<host::ChainManyUnit> cm_units;
+    DevBuf<int32_t> cm_pcol, cm_eoff, cm_verdict, cm_wk;
+    DevBuf<double> cm_term, cm_gain;
   } query;
   std::string err;
 
@@ -363,6 +368,9 @@ void query_basis_download(L& l, float* X_out, float* x_out);
 void query_receipt_many(L& l, const float* psis, int32_t Q, int32_t detail, float z_th, int32_t null_cap, double* dH,
                         double* coh_sum, double* anchor_sum, double* query_sum, int32_t* null_total, int64_t* null_offsets,
                         int32_t* i_out, int32_t* j_out, float* z_out, float* r_out, int64_t capacity);
+void query_chain_receipt_many(L& l, const float* psis, int32_t Q, const int64_t* chain_offsets, const int32_t* chain_nodes,
+                              float z_th, float* z_struct, float* z_path, float* r_struct, float* r_path, double* gain,
+                              int32_t* verdict, int32_t* weakest_k, float* weakest_z);
 // sum (A - B) . M (A - B) with the stationary operator (osc_api.hip; receipts.py:21-25)
 double quad_form_of_difference(L& l, const float* A, const float* B);
 void query_bundle_many(L& l, const float* psis, int32_t Q, int32_t k, float alpha, float lambda_div, int32_t* ids,

@@ -567,3 +567,113 @@ void query_receipt_many(L& l, const float* psis, int32_t Q, int32_t detail, floa
     }
   }
 }
+
+// ---- chain receipts -------------------------------------------------------------------------
+// chain_receipt(chain_q, z_th) of U*(psi_q) for Q (query, chain) pairs: per chunk the path structures (the lattice's own
+// chain once per call, else once per distinct chain of the chunk), the (query, edge) units, one gather kernel over them and
+// one finish kernel over the queries.  Nothing outlives the call but the scratch's allocation.
+void query_chain_receipt_many(L& l, const float* psis, int32_t Q, const int64_t* chain_offsets, const int32_t* chain_nodes,
+                              float z_th, float* z_struct, float* z_path, float* r_struct, float* r_path, double* gain,
+                              int32_t* verdict, int32_t* weakest_k, float* weakest_z) {
+  if (l.comm) throw Unsupported("osc_chain_receipt_many: lattices with a communicator are not supported");
+  require_basis(l);
+  if (Q <= 0) return;
+  int32_t where = 0;
+  switch (host::chain_many_check(chain_offsets, chain_nodes, Q, l.N, &where)) {
+    case 1:
+      throw Invalid("osc_chain_receipt_many: query " + std::to_string(where) + ": a chain has 2 to " +
+                    std::to_string(host::kCorpusMaxChain) + " nodes, at offsets that start from 0");
+    case 2:
+      throw Invalid("osc_chain_receipt_many: query " + std::to_string(where) + ": chain indices out of bounds");
+  }
+  auto& q = l.query;
+  const int32_t N = (int32_t)l.N, D = l.D;
+  const int32_t* dev = permuted(l) ? l.inv_h.data() : nullptr;
+  host::ChainManyPaths paths;
+  int32_t own = -1;
+  if (l.chain_present) {  // lattice.py:479-483: the lattice's own A_path, weights included, whatever the argument is
+    std::vector<int32_t> rows(l.chain_nodes);
+    if (dev)
+      for (int32_t& v : rows) v = dev[v];
+    own = paths.add(rows.data(), l.chain_w.empty() ? nullptr : l.chain_w.data(), (int32_t)rows.size(), N);
+  }
+  auto upload_paths = [&]() {
+    q.cm_pcol.alloc(std::max<size_t>(paths.pcol.size(), 1));
+    q.cm_pa.alloc(std::max<size_t>(paths.pa.size(), 1));
+    if (paths.pcol.empty()) return;
+    HIP_CHECK(hipMemcpyAsync(q.cm_pcol.p, paths.pcol.data(), paths.pcol.size() * 4, hipMemcpyHostToDevice, l.stream));
+    HIP_CHECK(hipMemcpyAsync(q.cm_pa.p, paths.pa.data(), paths.pa.size() * 4, hipMemcpyHostToDevice, l.stream));
+  };
+  if (own >= 0) upload_paths();
+  q.cm_eoff.alloc((size_t)kQueryChunk + 1);
+  q.cm_gain.alloc(kQueryChunk);
+  q.cm_verdict.alloc(kQueryChunk);
+  q.cm_wk.alloc(kQueryChunk);
+  q.cm_wz.alloc(kQueryChunk);
+  std::vector<host::ChainManyUnit> units;
+  std::vector<int32_t> eoff;
+  std::vector<float> hpsi;
+  for (int32_t c0 = 0; c0 < Q; c0 += kQueryChunk) {
+    const int32_t nq = std::min<int32_t>(kQueryChunk, Q - c0);
+    if (own < 0) paths.clear();
+    host::chain_many_units(chain_offsets, chain_nodes, c0, nq, dev, N, own, paths, units, eoff);
+    if (own < 0) upload_paths();
+    const size_t nu = units.size();
+    hpsi.assign((size_t)nq * l.ld, 0.f);
+    for (int32_t t = 0; t < nq; ++t)
+      std::copy(psis + (size_t)(c0 + t) * D, psis + (size_t)(c0 + t + 1) * D, hpsi.data() + (size_t)t * l.ld);
+    q.cm_psi.alloc(hpsi.size());
+    q.cm_units.alloc(nu);
+    q.cm_edge.alloc(4 * nu);
+    q.cm_term.alloc(2 * nu);
+    HIP_CHECK(hipMemcpyAsync(q.cm_psi.p, hpsi.data(), hpsi.size() * 4, hipMemcpyHostToDevice, l.stream));
+    HIP_CHECK(hipMemcpyAsync(q.cm_units.p, units.data(), nu * sizeof(host::ChainManyUnit), hipMemcpyHostToDevice, l.stream));
+    HIP_CHECK(hipMemcpyAsync(q.cm_eoff.p, eoff.data(), eoff.size() * 4, hipMemcpyHostToDevice, l.stream));
+    CmEdgesArgs e{};
+    e.X = q.X.p;
+    e.x4 = q.x4.p;
+    e.Y = l.Y.p;
+    e.sqrt_deg = l.sqrt_deg.p;
+    e.col = l.ell_col.p;
+    e.adj = l.ell_a.p;
+    e.deg = l.deg.p;
+    e.psi = q.cm_psi.p;
+    e.units = q.cm_units.p;
+    e.pcol = q.cm_pcol.p;
+    e.pa = q.cm_pa.p;
+    e.width = l.width;
+    e.N = N;
+    e.D = D;
+    e.ld = l.ld;
+    e.n_units = (int64_t)nu;
+    e.lamC = l.lamC;
+    e.z_struct = q.cm_edge.p;
+    e.z_path = q.cm_edge.p + nu;
+    e.r_struct = q.cm_edge.p + 2 * nu;
+    e.r_path = q.cm_edge.p + 3 * nu;
+    e.term = q.cm_term.p;
+    e.zmax = q.cm_term.p + nu;
+    launch_cm_edges(e, l.stream);
+    CmFinishArgs f{};
+    f.eoff = q.cm_eoff.p;
+    f.term = e.term;
+    f.zmax = e.zmax;
+    f.nq = nq;
+    f.z_th = z_th;
+    f.gain = q.cm_gain.p;
+    f.verdict = q.cm_verdict.p;
+    f.weak_k = q.cm_wk.p;
+    f.weak_z = q.cm_wz.p;
+    launch_cm_finish(f, l.stream);
+    const int64_t at = host::chain_many_edge_at(chain_offsets, c0);  // the chunk's units are its queries' edges, in order
+    HIP_CHECK(hipMemcpyAsync(z_struct + at, e.z_struct, nu * 4, hipMemcpyDeviceToHost, l.stream));
+    HIP_CHECK(hipMemcpyAsync(z_path + at, e.z_path, nu * 4, hipMemcpyDeviceToHost, l.stream));
+    HIP_CHECK(hipMemcpyAsync(r_struct + at, e.r_struct, nu * 4, hipMemcpyDeviceToHost, l.stream));
+    HIP_CHECK(hipMemcpyAsync(r_path + at, e.r_path, nu * 4, hipMemcpyDeviceToHost, l.stream));
+    HIP_CHECK(hipMemcpyAsync(gain + c0, q.cm_gain.p, (size_t)nq * 8, hipMemcpyDeviceToHost, l.stream));
+    HIP_CHECK(hipMemcpyAsync(verdict + c0, q.cm_verdict.p, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
+    HIP_CHECK(hipMemcpyAsync(weakest_k + c0, q.cm_wk.p, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
+    HIP_CHECK(hipMemcpyAsync(weakest_z + c0, q.cm_wz.p, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
+    sync(l);  // (the host vectors above are reused by the next chunk)
+  }
+}

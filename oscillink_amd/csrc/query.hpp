@@ -184,3 +184,55 @@ struct RmSelectArgs {
 void launch_rm_null_select(const RmSelectArgs& a, hipStream_t s);
 
 }  // namespace osc
+
+// ---- multi-query chain receipts: chain_many_kernels.hip -------------------------------------
+#include "chain_many.hpp"
+
+namespace osc {
+
+constexpr int kCmMaxBlocks = 4096;  // k_cm_edges' grid: 4 waves a workgroup, grid-stride over the units beyond it
+
+// per (query, chain edge) unit u = (q, i, j) of a chunk, on U*(psi_q) = X + x psi_q^T with Un = U* / (sd + 1e-12):
+//   R_s = lamC a_ic |Un_i - Un_c|^2 over row i's ELL slots with a_ic > 0, R_p = max(lamC, 1e-6) A_path[i][c] |Un_i - Un_c|^2
+//   over its path entries [pb, pe); per row mu = sum R / N, sigma = sqrt(sum R^2 / N - mu^2) + 1e-12 in fp64, slot order;
+//   z = (R_ij - mu) / sigma with R_ij = 0 when j is not an entry; term = 0.5 lamC a_ij (|Yn_i - Yn_j|^2 - |Un_i - Un_j|^2)
+struct CmEdgesArgs {
+  const float* X;        // N x ld
+  const float* x4;       // N x 4, column 0 = x
+  const float* Y;        // N x ld
+  const float* sqrt_deg;
+  const int32_t* col;    // ELL, device rows
+  const float* adj;      // capped adjacency
+  const int32_t* deg;
+  const float* psi;      // nq x ld, pad columns zero
+  const host::ChainManyUnit* units;
+  const int32_t* pcol;   // the chunk's path entries, device rows
+  const float* pa;       // A_path
+  int32_t width, N, D, ld;
+  int64_t n_units;
+  float lamC;
+  float* z_struct;       // [n_units] each
+  float* z_path;
+  float* r_struct;
+  float* r_path;
+  double* term;
+  double* zmax;          // max(z_struct, z_path) in fp64
+};
+int cm_edge_blocks(int64_t n_units);
+void launch_cm_edges(const CmEdgesArgs& a, hipStream_t s);
+
+// per query of the chunk over its units [eoff[q], eoff[q + 1]): the gain, the verdict, the weakest link
+struct CmFinishArgs {
+  const int32_t* eoff;   // [nq + 1]
+  const double* term;
+  const double* zmax;
+  int32_t nq;
+  float z_th;
+  double* gain;
+  int32_t* verdict;
+  int32_t* weak_k;       // -1: no edge's max(z) exceeds -1
+  float* weak_z;
+};
+void launch_cm_finish(const CmFinishArgs& a, hipStream_t s);
+
+}  // namespace osc

@@ -826,6 +826,47 @@ class OscillinkLattice:
             out.append(rec)
         return out
 
+    def chain_receipt_many(self, psis: np.ndarray, chains, z_th: float = 2.5, *, tol: float = 1e-4, max_iters: int = 256,
+                           as_arrays: bool = False):
+        """`chain_receipt(chains[q], z_th)` for each row of `psis` (Q x D), as if `set_query(psis[q])` had been called, with
+        the current graph, gates, own chain (add_chain), lambdas and U held fixed and without touching the lattice's state.
+        `chains` is one chain (a sequence of API row ids, shared by every query) or a sequence of Q chains, 2 to 1024 nodes
+        each; repeated nodes, self-steps and revisited edges behave as in chain_receipt.  The path residuals use the
+        lattice's own chain with its weights when it has one, else the unit-weight path of the argument.  U*(psi_q) comes
+        from the query basis `bundle_many` / `receipt_many` use (same key, cache and tolerance contract); only the rows of
+        the chain nodes and their graph and path neighbours are read.  A non-finite query row gets
+        non-finite answers and changes no other query's.
+
+        Returns Q dicts with chain_receipt's keys, or with `as_arrays=True` the arrays they are assembled from, under
+        `Corpus.refine_many`'s names: `chain_offsets` int64 (Q + 1, over chain edges), `chain_z_struct`, `chain_z_path`,
+        `chain_r_struct`, `chain_r_path` float32 (flat), `chain_gain` float64, `chain_verdict` bool, `chain_weakest_k` int32
+        (-1 when no edge's max(z) exceeds -1) and `chain_weakest_z` float32."""
+        if self._has_comm:
+            raise NotImplementedError("chain_receipt_many: lattices with a communicator (sharded / multi-rank) are not "
+                                      "supported")
+        P = rc.check_queries(psis, self.D, finite=False)
+        Q = int(P.shape[0])
+        lists, offsets, nodes = rc.chain_block(chains, Q, self.N)
+        edge_offsets = offsets - np.arange(Q + 1, dtype=np.int64)
+        n_edges = int(edge_offsets[-1])
+        edge = np.zeros((4, max(n_edges, 1)), dtype=np.float32)
+        gain = np.zeros(Q, dtype=np.float64)
+        verdict, weak_k = np.zeros(Q, dtype=np.int32), np.zeros(Q, dtype=np.int32)
+        weak_z = np.zeros(Q, dtype=np.float32)
+        solved = False
+        if Q > 0:
+            n0 = self.stats["query_basis_solves"]
+            self._ensure_query_basis(tol, max_iters, float(np.max(np.abs(P), where=np.isfinite(P), initial=0.0)))
+            solved = self.stats["query_basis_solves"] != n0
+            self._call("osc_chain_receipt_many", nat.f32(P), Q, nat.i64(offsets), nat.i32(nodes), float(z_th),
+                       *[nat.f32(edge[t]) for t in range(4)], gain.ctypes.data_as(C.POINTER(C.c_double)), nat.i32(verdict),
+                       nat.i32(weak_k), nat.f32(weak_z))
+        self._log("chain_receipt_many", {"Q": Q, "edges": n_edges, "basis_solved": solved})
+        arr = dict(chain_offsets=edge_offsets, chain_z_struct=edge[0, :n_edges].copy(), chain_z_path=edge[1, :n_edges].copy(),
+                   chain_r_struct=edge[2, :n_edges].copy(), chain_r_path=edge[3, :n_edges].copy(), chain_gain=gain,
+                   chain_verdict=verdict != 0, chain_weakest_k=weak_k, chain_weakest_z=weak_z)
+        return arr if as_arrays else rc.chain_receipt_dicts(lists, arr)
+
     def query_basis(self, tol: float = 1e-4, max_iters: int = 256) -> tuple[np.ndarray, np.ndarray]:
         """The query basis (X N x D, x N) in API row order: U*(psi) = X + x psi^T (diagnostic; not in the reference).
         Solved for the current psi's |psi|_inf unless a basis of the same graph, gates, chain, lambdas and tolerance is
