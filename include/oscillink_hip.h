@@ -98,6 +98,17 @@ int osc_order_info(osc_handle h, int32_t* reordered, double* clustering);
 /* the internal row order itself (test / diagnostic aid): perm[new] = caller's row id, N entries; the identity when the
  * rows are stored in the caller's order */
 int osc_get_row_order(osc_handle h, int32_t* perm);
+/* which order the rows are stored in: order_kind 0 = the caller's, 1 = BFS (osc_order_info's reordered), 2 = balanced
+ * source blocks -- an unstructured lattice's rows ordered so that every row's neighbours spread over the src_blocks
+ * source blocks of the blocked CG matvec with at most 4 in each (chosen without a communicator where the apply plan has
+ * source blocks in the wide kernel shapes; OSC_BALANCE=0 never, 1 wherever the plan has source blocks; OSC_REORDER=0
+ * keeps the caller's order; OSC_BALANCE_HOST=1 computes the same order on the host).  For order_kind 2: displaced_before /
+ * displaced_after = edges beyond the 4 slots a row has per source block in the caller's order / the stored order, rounds =
+ * rounds of the search, ms = search + state move, on_device = 1 when the device kernels computed the order, 0 when the host
+ * reference did (OSC_BALANCE_HOST=1, or an ELL wider than 255 / lists too large for the device form); 0 otherwise
+ * (measurement aid) */
+int osc_balance_info(osc_handle h, int32_t* order_kind, int64_t* displaced_before, int64_t* displaced_after, int32_t* rounds,
+                     int32_t* src_blocks, double* ms, int32_t* on_device);
 
 /* how one operator apply (the CG matvec over this handle's column window) is launched: launches = kernel launches per
  * apply, slab_cols = columns each launch covers, xs_workgroups = 0 for sequential column slabs swept by the whole

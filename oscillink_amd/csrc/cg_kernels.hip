@@ -1305,14 +1305,14 @@ static void blocked_check(int32_t N, int32_t width, int32_t nb) {
 void launch_blocked_count(const int32_t* col, const int32_t* deg, int32_t width, int32_t N, int32_t nb,
                           unsigned* over_count, hipStream_t s) {
   blocked_check(N, width, nb);
-  hipLaunchKernelGGL(k_blk_count, dim3((N + 255) / 256), dim3(256), 0, s, col, deg, width, N, nb, (N + nb - 1) / nb,
+  hipLaunchKernelGGL(k_blk_count, dim3((N + 255) / 256), dim3(256), 0, s, col, deg, width, N, nb, host::blocked_rows_per_block(N, nb),
                      over_count);
   HIP_CHECK(hipGetLastError());
 }
 void launch_blocked_fill(const int32_t* col, const float* w, const int32_t* deg, int32_t width, int32_t N, int32_t nb,
                          int2* slots, int2* rest, int2* over, unsigned* over_count, hipStream_t s) {
   blocked_check(N, width, nb);
-  hipLaunchKernelGGL(k_blk_fill, dim3((N + 255) / 256), dim3(256), 0, s, col, w, deg, width, N, nb, (N + nb - 1) / nb,
+  hipLaunchKernelGGL(k_blk_fill, dim3((N + 255) / 256), dim3(256), 0, s, col, w, deg, width, N, nb, host::blocked_rows_per_block(N, nb),
                      slots, rest, over, over_count);
   HIP_CHECK(hipGetLastError());
 }

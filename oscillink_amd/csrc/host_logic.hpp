@@ -291,6 +291,8 @@ inline int blocked_block_count(double mean_deg, double edges_per_block, int max_
   const int nb = (int)std::max(2.0, std::floor(mean_deg / edges_per_block + 0.5));
   return std::min(nb, max_blocks);
 }
+// rows per source block: block b is the stored rows [b rpb, (b + 1) rpb) (k_blk_count / k_blk_fill, block_balance.hpp)
+inline int32_t blocked_rows_per_block(int64_t N, int nb) { return (int32_t)std::max<int64_t>(1, (N + nb - 1) / std::max(1, nb)); }
 inline int blk_of(int col, int rpb, int nb) { return std::min(nb - 1, col / rpb); }
 // Host model of k_blk_count / k_blk_fill for ONE row (cols ascending, deg entries): an edge goes into the slot row of its
 // own block while that has room (slots 0 .. c - 1 for the block's c <= SL own edges); an edge that finds its block full
@@ -302,7 +304,7 @@ struct BlkEntry {
 };
 inline void blk_place_row(const int32_t* cols, const float* w, int deg, int32_t N, int nb, int SL, std::vector<BlkEntry>& slots,
                           std::vector<BlkEntry>& over) {
-  const int rpb = (N + nb - 1) / nb;
+  const int rpb = blocked_rows_per_block(N, nb);
   std::vector<int> c((size_t)nb, 0), k((size_t)nb, 0), tail((size_t)nb, 0);
   for (int e = 0; e < deg; ++e) {
     if (cols[e] < 0 || cols[e] >= N) throw InvalidArg("blk_place_row: column out of range");

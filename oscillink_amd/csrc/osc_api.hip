@@ -72,6 +72,8 @@ void read_env_build(L& h) {
   if (num("OSC_KNN_TILE_WIDE", v)) kb.tune.tile_wide = v != 0 ? 1 : 0;
   kb.force_exchange = num("OSC_KNN_FORCE_EXCHANGE", v) && v != 0;
   h.bfs_host = num("OSC_BFS_HOST", v) && v != 0;
+  h.balance = num("OSC_BALANCE", v) ? (v != 0 ? 1 : 0) : -1;
+  h.balance_host = num("OSC_BALANCE_HOST", v) && v != 0;
   h.halo_force = 0;
   if (const char* e = getenv("OSC_HALO")) h.halo_force = !strcmp(e, "full") ? 1 : !strcmp(e, "lists") ? 2 : 0;
 }
@@ -365,6 +367,20 @@ int osc_order_info(osc_handle h, int32_t* reordered, double* clustering) {
   return guarded(h, [&](L& l) {
     if (reordered) *reordered = l.reordered ? 1 : 0;
     if (clustering) *clustering = l.clustering;
+  });
+}
+
+int osc_balance_info(osc_handle h, int32_t* order_kind, int64_t* displaced_before, int64_t* displaced_after, int32_t* rounds,
+                     int32_t* src_blocks, double* ms, int32_t* on_device) {
+  return guarded(h, [&](L& l) {
+    const bool bal = l.order_kind == 2;
+    if (order_kind) *order_kind = l.order_kind;
+    if (displaced_before) *displaced_before = bal ? l.displaced_before : 0;
+    if (displaced_after) *displaced_after = bal ? l.displaced_after : 0;
+    if (rounds) *rounds = bal ? l.balance_rounds : 0;
+    if (src_blocks) *src_blocks = bal ? l.balance_nb : 0;
+    if (ms) *ms = bal ? l.balance_ms : 0.0;
+    if (on_device) *on_device = bal && l.balance_on_device ? 1 : 0;
   });
 }
 
@@ -1393,6 +1409,7 @@ int osc_comm_init(osc_handle h, const char id[128], int32_t rank, int32_t world)
     drain_comm_stream(l);
     materialise_u(l);  // (a rank's U holds columns or rows its solves do not own: no alias under a communicator)
     l.comm.reset();
+    if (l.order_kind == 2) drop_order(l);  // balanced source blocks are a one-process order (maybe_reorder): back to the API's
     l.rank = rank;
     l.world = world;
     l.fake_window = false;

@@ -127,6 +127,8 @@ void drop_order(L& l) {  // back to the API's row order
   move_state(l, l.inv_d.p, l.perm_d.p);
   l.perm_h.clear();
   l.inv_h.clear();
+  l.reordered = false;
+  l.order_kind = 0;
   install_chain(l);
 }
 
@@ -173,16 +175,59 @@ std::vector<int32_t> bfs_order(L& l) {
   return order;
 }
 
+// Balanced source blocks (block_balance.hpp) for a lattice whose graph has no locality to order by: applies where the
+// handle's apply plan has source blocks, with the plan's block count and OSC_BLK_SLOTS.  OSC_BALANCE=1: wherever it has;
+// auto: where the planner itself picks a wide kernel shape (one forced by OSC_BLK_VARIANT does not count), up to the slab
+// mode's Infinity-Cache budget -- beyond it a source block is far from L2-resident and a displaced edge misses no more
+// than any other (config 4, 1M x 384: 4.3 % -> 0.1 % displaced, settle 25.96 -> 26.04 ms for 21.8 ms of search).  The plan is
+// that of a handle in API order and stays it: l.reordered is the BFS flag and is not set here.  The rounds run on the
+// device (balance_kernels.hip; OSC_BALANCE_HOST=1 or a shape the device form does not cover: the host reference, the same
+// order).  DESIGN.md section 4 has the cost: 5 ms at config 3, paid back after 66 settles.
+static bool maybe_balance(L& l) {
+  if (l.balance == 0 || l.comm != nullptr || row_mode(l) || l.N < 2 || l.nnz == 0) return false;  // (sharded runs keep their order)
+  const host::ApplyPlan plan = apply_plan(l, l.c0, l.c1, l.ld, false);
+  const bool wide_by_plan = plan.shape > 0 && l.blk_variant < 0 && l.N <= host::kXsBudgetRows;
+  if (plan.src_blocks < 2 || !(l.balance == 1 || wide_by_plan)) return false;
+  const double t0 = now_ms();
+  const int nb = plan.src_blocks;
+  std::vector<int32_t> pos;
+  host::BalanceStats st;
+  l.balance_on_device = !l.balance_host && device_balance_assign(l.ell_col.p, l.deg.p, l.width, (int32_t)l.N, nb, OSC_BLK_SLOTS, pos, st, l.stream);
+  if (!l.balance_on_device) {
+    const size_t ne = (size_t)l.N * l.width;
+    std::vector<int32_t> col(ne), deg((size_t)l.N);
+    HIP_CHECK(hipMemcpyAsync(col.data(), l.ell_col.p, ne * 4, hipMemcpyDeviceToHost, l.stream));
+    HIP_CHECK(hipMemcpyAsync(deg.data(), l.deg.p, (size_t)l.N * 4, hipMemcpyDeviceToHost, l.stream));
+    sync(l);
+    host::balance_assign(col.data(), deg.data(), l.width, (int32_t)l.N, nb, OSC_BLK_SLOTS, pos, &st);
+  }
+  l.displaced_before = st.displaced_before;
+  l.displaced_after = st.displaced_after;
+  l.balance_rounds = st.rounds;
+  l.balance_nb = nb;
+  if (st.displaced_after < st.displaced_before) {  // (an order that displaces no fewer edges is not worth the state move)
+    apply_order(l, host::balance_order(pos.data(), (int32_t)l.N, nb));
+    l.order_kind = 2;
+  }
+  sync(l);
+  l.balance_ms = now_ms() - t0;
+  return l.order_kind == 2;
+}
+
 // Re-order the rows when it pays: the BFS + state move cost a few ms at N = 100k and buy ~1.5x on the operator apply
 // of a clustered lattice, nothing on an unstructured one.  Auto mode decides on a sampled clustering coefficient.
 void maybe_reorder(L& l) {
   l.reordered = false;
+  l.order_kind = 0;
   l.clustering = 0.0;
   // under a communicator only the row-sharded CG re-orders (every rank holds the same graph and takes the same
   // deterministic decision and order; the halo lists shrink with locality); the column-sharded default keeps API order
   if (l.reorder == 0 || (l.comm != nullptr && l.shard_mode != 1) || l.N < 2) return;
   if (l.reorder < 0) {
-    if (l.N < 8192 || l.nnz == 0) return;  // small lattices run out of LDS / L2 anyway
+    if (l.N < 8192 || l.nnz == 0) {  // small lattices run out of LDS / L2 anyway
+      if (l.balance == 1) maybe_balance(l);
+      return;
+    }
     constexpr int kSample = 1024;
     DevBuf<unsigned long long> cnt;
     cnt.alloc(2 * kSample);  // (every sampled row writes its own two words: perm_kernels.hip)
@@ -193,7 +238,10 @@ void maybe_reorder(L& l) {
     unsigned long long hc[2] = {0, 0};
     for (int s2 = 0; s2 < kSample; ++s2) hc[0] += per_row[(size_t)2 * s2], hc[1] += per_row[(size_t)2 * s2 + 1];
     l.clustering = hc[1] ? (double)hc[0] / (double)hc[1] : 0.0;
-    if (l.clustering < 0.05) return;
+    if (l.clustering < 0.05) {  // unstructured: no order gives it locality, one can still give it balance
+      maybe_balance(l);
+      return;
+    }
   }
   // the order itself: on the device (bfs_order.hip; the same order as the host walk below it, OSC_BFS_HOST=1 forces that)
   bool on_device = false;
@@ -210,6 +258,7 @@ void maybe_reorder(L& l) {
   }
   if (!on_device) apply_order(l, bfs_order(l));
   l.reordered = true;
+  l.order_kind = 1;
 }
 
 // Sharded half sweep: every rank holds partial buckets of ALL rows; rank q needs the other ranks' entries of the buckets of

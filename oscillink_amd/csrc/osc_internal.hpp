@@ -110,7 +110,16 @@ struct osc_lattice {
   // internal row order (empty = identity): API row i lives at device row inv_h[i]; perm_h[new] = old
   int reorder = -1;        // OSC_REORDER: 0 never, 1 always, unset = auto (when the graph is clustered enough to pay)
   double clustering = 0.0;  // sampled local clustering coefficient of the last graph
-  bool reordered = false;
+  bool reordered = false;   // the stored order is the BFS order (selects the deep kernels and the BFS block rule; order_kind == 1)
+  // Which order the rows are stored in: 0 the API's, 1 BFS, 2 balanced source blocks (block_balance.hpp: every row's
+  // neighbours spread over the blocked matvec's source blocks; the graph keeps no locality, so nothing BFS-specific applies).
+  int order_kind = 0;
+  int balance = -1;         // OSC_BALANCE: 0 never, 1 wherever the apply plan has source blocks, unset = auto (maybe_reorder)
+  bool balance_host = false;  // OSC_BALANCE_HOST=1: the host reference computes the order (A/B, tests)
+  int64_t displaced_before = 0, displaced_after = 0;  // displaced edges of the last balanced order: API order / stored order
+  int32_t balance_rounds = 0, balance_nb = 0;
+  bool balance_on_device = false;  // the device kernels computed the last balanced order (false: the host reference did)
+  double balance_ms = 0.0;  // search + state move of the last balanced order
   std::vector<int32_t> perm_h, inv_h;
   DevBuf<int32_t> perm_d, inv_d;
   // chain prior (kept in API ids on the host so it can be re-installed after a re-order)

@@ -1,4 +1,7 @@
 #pragma once
+#include <vector>
+
+#include "block_balance.hpp"
 #include "common.hpp"
 
 namespace osc {
@@ -15,6 +18,12 @@ void launch_permute_ell(const int32_t* col_in, const float* a_in, const float* w
 // the host's queue BFS (components by smallest row id, neighbours in slot order).  false: graph too deep / too large for
 // the device form -- walk it on the host.
 bool device_bfs_order(const int32_t* col, const int32_t* deg, int32_t width, int32_t N, int32_t* perm_out, hipStream_t s);
+
+// The balanced source-block assignment computed on the device (balance_kernels.hip): pos_out[r] = stored position of API row r,
+// identical to host::balance_assign (block_balance.hpp).  false: not a shape the device form covers (ELL width above 255, lists
+// too large) -- run the host reference.
+bool device_balance_assign(const int32_t* col, const int32_t* deg, int32_t width, int32_t N, int32_t nb, int32_t slots,
+                           std::vector<int32_t>& pos_out, host::BalanceStats& st, hipStream_t s);
 
 // exclusive prefix sum of n int32 on the device (bfs_order.hip; out may alias in; sums: scan_blocks(n) int32 of scratch)
 size_t scan_blocks(int64_t n);

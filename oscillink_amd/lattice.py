@@ -240,9 +240,15 @@ class OscillinkLattice:
         self._call("osc_apply_info", C.byref(sb), C.byref(ba))
         xk, xf, xp, xb = C.c_int32(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
         self._call("osc_x_ring_info", C.byref(xk), C.byref(xf), C.byref(xp), C.byref(xb))
+        ok, db, da, br, bn, bm = C.c_int32(0), C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int32(0), C.c_double(0.0)
+        bd = C.c_int32(0)
+        self._call("osc_balance_info", C.byref(ok), C.byref(db), C.byref(da), C.byref(br), C.byref(bn), C.byref(bm), C.byref(bd))
         counters = nat.Counters()
         self._call("osc_counters_get", C.byref(counters))
-        return {"prefilter": int(pf.value), "fallback_rows": int(fb.value), "small_solves": int(ss.value),
+        return {"order_kind": ("none", "bfs", "balanced")[int(ok.value)], "displaced_edges_before": int(db.value),
+                "displaced_edges_after": int(da.value), "balance_rounds": int(br.value), "balance_src_blocks": int(bn.value),
+                "balance_ms": float(bm.value), "balance_on_device": int(bd.value),
+                "prefilter": int(pf.value), "fallback_rows": int(fb.value), "small_solves": int(ss.value),
                 "reordered": int(ro.value), "clustering": float(cc.value), "apply_launches": int(ln.value),
                 "apply_slab_cols": int(sc.value), "apply_xs_workgroups": int(xw.value),
                 "apply_src_blocks": int(sb.value), "blocked_applies": int(ba.value),
