@@ -1,5 +1,5 @@
 // Host-side index arithmetic and list building of liboscillink_hip.so, kept free of every HIP type: the functions the
-// library itself runs (osc_api.hip includes this header) also compile with a plain host compiler, and
+// library itself runs (osc_internal.hpp includes this header) also compile with a plain host compiler, and
 // tests/host_logic/sweep_host_logic.cpp sweeps them over N x k x world under -fsanitize=address,undefined on the CPU box
 // (sanitizers belong on the CPU build; GPU AddressSanitizer is not available on the pool).
 //   column_shard / row_lo / row_owner : the partitions of the sharded solves (column windows, row blocks)
@@ -12,6 +12,8 @@
 //   CgXSchedule                       : which launch of a CG solve carries which iteration's x update (run_cg)
 //   plan_x_ring / CgXRing             : how many search directions a solve keeps, and when a pass applies them to x (swept by
 //                                       tests/host_logic/sweep_x_ring.cpp)
+//   cg_host_loop                      : the host loop of a CG solve -- which iteration is enqueued when (run_cg in
+//                                       osc_solve.hip and both sweeps run this one function)
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -500,7 +502,7 @@ inline ApplyPlan plan_apply(const ApplyInputs& in) {
   return p;
 }
 
-// ---- where the x update of a CG iteration happens (run_cg in osc_api.hip) ---------------------------------------------
+// ---- where the x update of a CG iteration happens (run_cg in osc_solve.hip) -------------------------------------------
 // The solve's host loop enqueues iteration it + 1 before it has read iteration it's residual, so a launch may belong to
 // an iteration that never was one.  With the x update deferred (x += alpha p of iteration it is applied by iteration
 // it + 1's p update, which reads p anyway) this object decides, launch by launch, which kernel carries which x update,
@@ -642,6 +644,38 @@ struct CgXRing {
     return p;
   }
 };
+
+// ---- the host loop of a CG solve (run_cg in osc_solve.hip) --------------------------------------------------------------
+// Iteration it + 1 is enqueued before iteration it's residual is read -- except behind the iteration the previous solve of
+// this kind converged in (stop_guess; 0: unknown): repeated settles of one lattice take the same count, and the five
+// gated-off launches of a needless speculative iteration cost ~22 us (8 % of a settle at N = 20000, D = 128; ungated under
+// a communicator: a whole iteration).  A wrong guess the other way costs one host round trip: the iteration is then
+// enqueued after its predecessor's residual has been read.  (Every rank of a sharded solve sees the same residuals, hence
+// takes the same decisions.)
+// Ops: enqueue(it, speculative) -- everything of iteration `it` up to its residual; idle_before_wait(it) -- nothing is
+// enqueued behind `it` for now, and the host has seen its predecessor unconverged, so `it` is a real iteration whatever its
+// residual will say; float wait(it) -- its residual; go_on(it) -- the guess was wrong and iteration it + 1 follows
+// unspeculatively (the r that `it` computed but did not keep is restored here).  What x policy these follow (CgXSchedule,
+// CgXRing) is the ops' business.  Returns the iteration the solve stopped in (max_iters if in none).
+template <class Ops>
+int cg_host_loop(int max_iters, int stop_guess, double tol, Ops& ops) {
+  int enqueued = 1;
+  ops.enqueue(1, false);
+  for (int it = 1; it <= max_iters; ++it) {
+    if (it < max_iters && it != stop_guess && enqueued == it) {
+      ops.enqueue(++enqueued, true);  // speculative: no-ops if `it` converged (ungated: scratch arrays only)
+    } else {
+      ops.idle_before_wait(it);
+    }
+    const float res = ops.wait(it);
+    if ((double)res <= tol) return it;
+    if (it < max_iters && enqueued == it) {  // the guess was wrong: go on
+      ops.go_on(it);
+      ops.enqueue(++enqueued, false);
+    }
+  }
+  return max_iters;
+}
 
 }  // namespace host
 }  // namespace osc

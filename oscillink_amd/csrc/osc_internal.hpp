@@ -183,7 +183,6 @@ struct osc_lattice {
   float* res_host = nullptr;  // pinned, host-mapped mirror of res_bits for the per-iteration read-back
   float* res_host_dev = nullptr;  // the device's address of it
   size_t res_host_n = 0;
-  bool mapped_residual = true;  // residuals published into host-mapped memory (false: copy + event per iteration)
   std::vector<hipEvent_t> iter_events;
   // sharded solves: the stop test's all-reduce runs on a second stream beside the next iteration's p update and matvec
   // (run_cg); step_events[it] = "iteration it's local residual is out" (OSC_COMM_OVERLAP=0: all-reduce in the solve's stream)
@@ -327,6 +326,12 @@ void download_api_order(L& h, float* dst, const float* src);
 void drain_comm_stream(L& h);
 uint32_t* ctrl_segment(L& h, size_t words);
 void ensure_ctrl(L& h, size_t slots);
+// A word of the host-mapped mirror (L::res_host) the device has yet to publish: never a residual (those are sqrt(...) >= 0
+// or a canonical NaN) nor a status.  poll_host_word spins on such a word and returns its first other value; `second`:
+// nullptr, or the stream the word comes out of where that is not the handle's (queried as well); `what` names the word in
+// the errors (HipError: the streams finished without publishing it, or 120 s passed).
+constexpr uint32_t kCtrlPending = 0xFFFFFFFFu;
+uint32_t poll_host_word(L& h, volatile uint32_t* word, hipStream_t second, const char* what);
 void ensure_cg_scratch(L& h, int max_iters);
 int cg_grid(const L& h);
 int blocked_quad_form(L& h, const host::ApplyPlan& plan, const OpParams& op, const float* x_rows, float* scratch_slab,

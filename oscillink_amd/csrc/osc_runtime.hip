@@ -433,6 +433,22 @@ void ensure_ctrl(L& h, size_t slots) {
   }
 }
 
+uint32_t poll_host_word(L& h, volatile uint32_t* word, hipStream_t second, const char* what) {
+  const double t_start = now_ms();
+  for (uint64_t spin = 1;; ++spin) {
+    const uint32_t bits = *word;
+    if (bits != kCtrlPending) return bits;
+    if ((spin & 0x3FFF) == 0) {  // every ~16k polls: has the stream died or drained without publishing?
+      hipError_t q = hipStreamQuery(h.stream);
+      if (q == hipSuccess && second != nullptr) q = hipStreamQuery(second);
+      if (q != hipSuccess && q != hipErrorNotReady) hip_check(q, (std::string("hipStreamQuery, waiting for ") + what).c_str(), __FILE__, __LINE__);
+      if (q == hipSuccess && *word == kCtrlPending) throw HipError(std::string("the stream finished without publishing ") + what);
+      if (now_ms() - t_start > 120000.0) throw HipError(std::string("timeout waiting for ") + what);
+    }
+    __builtin_ia32_pause();
+  }
+}
+
 void ensure_cg_scratch(L& h, int max_iters) {
   const size_t pn = (size_t)(h.grid_cap + OSC_CHAIN_FIX_MAX_CHUNKS) * h.ld;  // + the chain fix-up's rows beside the blocked apply
   h.part0.alloc(pn);

@@ -120,23 +120,19 @@ void spmm_slabbed(L& h, const host::ApplyPlan& plan, int mode, SpmmArgs sa, int 
 }
 
 // elementwise CG kernels cover at most 2048 columns per launch: wider states run as several column windows
-template <typename F>
-void for_windows(UpdateArgs ua, F&& launch) {
-  const int32_t c0 = ua.c0, c1 = ua.c1;
+template <typename Args, typename F>
+void for_windows(Args a, F&& launch) {
+  const int32_t c0 = a.c0, c1 = a.c1;
   for (int32_t s0 = c0; s0 < c1; s0 += 2048) {
-    ua.c0 = s0;
-    ua.c1 = std::min(c1, s0 + 2048);
-    launch(ua);
+    a.c0 = s0;
+    a.c1 = std::min(c1, s0 + 2048);
+    launch(a);
   }
 }
 
-
-
-// cg_solve (solver.py:6-37) on the device; returns once the last residual is out (what may still be queued then touches
-// scratch arrays only, and later calls are ordered behind it by the stream).
-// The host enqueues iteration it+1 before it reads iteration it's residual.  On one GPU every kernel of a speculative
-// iteration carries a gate (residual of the previous iteration, tol) and is a no-op once the CG has converged; under
-// a communicator it carries none and writes scratch arrays only (the x update of an iteration is applied by its
+// The CG drivers.  The host enqueues iteration it+1 before it reads iteration it's residual.  On one GPU every kernel of a
+// speculative iteration carries a gate (residual of the previous iteration, tol) and is a no-op once the CG has converged;
+// under a communicator it carries none and writes scratch arrays only (the x update of an iteration is applied by its
 // successor's p update or by the host's order, never speculatively).  Either way the reference's "stop before the
 // beta/p update" semantics hold exactly while the stream never drains between iterations.
 // Small lattices: the whole solve in ONE launch with the state in LDS (small_kernels.hip).  Returns false when the
@@ -152,10 +148,8 @@ bool run_cg_small(L& h, const OpParams& op, const CgBuffers& b, bool with_path, 
   uint32_t* ctl = ctrl_segment(h, nctl);
   // the kernel's last workgroup publishes residuals + a "done" word into host-mapped memory and the host polls that
   // word
-  const bool polled = h.mapped_residual;
-  constexpr uint32_t kPending = 0xFFFFFFFFu;
   volatile uint32_t* host_words = reinterpret_cast<volatile uint32_t*>(h.res_host);
-  if (polled) host_words[nslots] = kPending;
+  host_words[nslots] = kCtrlPending;
   SmallArgs a{};
   if (!h.derived.ell_t) {
     h.ell_col_t.alloc((size_t)h.N * h.width);
@@ -182,33 +176,15 @@ bool run_cg_small(L& h, const OpParams& op, const CgBuffers& b, bool with_path, 
   a.arrive = ctl + nslots;
   a.status = ctl + 2 * nslots;
   a.finish = ctl + 2 * nslots + 1;
-  a.host_words = polled ? reinterpret_cast<uint32_t*>(h.res_host_dev) : nullptr;
+  a.host_words = reinterpret_cast<uint32_t*>(h.res_host_dev);
   a.N = (int32_t)h.N;
   a.ld = b.ld;
   a.max_iters = max_iters;
   a.tol = tol;
   launch_settle_small(a, C, h.stream);
-  if (polled) {
-    const double t_start = now_ms();
-    for (uint64_t spin = 1; host_words[nslots] == kPending; ++spin) {
-      if ((spin & 0x3FFF) == 0) {  // every ~16k polls: has the stream died or drained without the word?
-        const hipError_t q = hipStreamQuery(h.stream);
-        if (q != hipSuccess && q != hipErrorNotReady) hip_check(q, "hipStreamQuery (one-launch solve)", __FILE__, __LINE__);
-        if (q == hipSuccess && host_words[nslots] == kPending) throw HipError("one-launch solve finished without its done word");
-        if (now_ms() - t_start > 120000.0) throw HipError("timeout waiting for the one-launch solve");
-      }
-      __builtin_ia32_pause();
-    }
-    if (host_words[nslots] != 0u) {
-      sync(h);       // (the kernel's other workgroups are on their way out)
-      return false;  // barrier timeout (GPU shared with other persistent work): take the general path
-    }
-  } else {
-    HIP_CHECK(hipMemcpyAsync(h.res_host, ctl, nctl * 4, hipMemcpyDeviceToHost, h.stream));
-    sync(h);
-    uint32_t st;
-    std::memcpy(&st, h.res_host + 2 * nslots, 4);
-    if (st != 0) return false;  // barrier timeout (GPU shared with other persistent work): take the general path
+  if (poll_host_word(h, host_words + nslots, nullptr, "the one-launch solve's done word") != 0u) {
+    sync(h);       // (the kernel's other workgroups are on their way out)
+    return false;  // barrier timeout (GPU shared with other persistent work): take the general path
   }
   h.history.clear();
   out = CgResult{max_iters, 0.f, xout};
@@ -224,9 +200,6 @@ bool run_cg_small(L& h, const OpParams& op, const CgBuffers& b, bool with_path, 
   h.small_solves += 1;
   return true;
 }
-
-CgResult run_cg_rows(L& h, const OpParams& op, const CgBuffers& b, bool with_path, int max_iters, float tol);
-bool row_mode(const L& h);
 
 // rows -> slab-major over [c0, c1) (k_rows_to_slab), counted per handle (osc_counters::rows_to_slab_launches)
 void rows_to_slab(L& h, const float* src, float* dst, int32_t ld, int32_t c0, int32_t c1, int grid, const float* sub) {
@@ -297,6 +270,25 @@ void blocked_setup(L& h, const host::ApplyPlan& plan, const OpParams& op, const 
   }
 }
 
+// k_apply_blocked over ba and, where the lattice has a chain prior (cf.chunks > 0), the chain fix-up behind it, both under the
+// gate g.  The caller counts the launch where osc_counters::blocked_applies counts it (the INIT passes of a solve do not).
+static void apply_blocked(L& h, const host::ApplyPlan& plan, BlkArgs& ba, ChainFixArgs& cf, int grid, Gate g) {
+  ba.gate = g.p;
+  ba.gate_tol = g.tol;
+  launch_apply_blocked(ba, grid, h.stream, nullptr, plan.shape);
+  if (cf.chunks > 0) {
+    cf.gate = g.p;
+    cf.gate_tol = g.tol;
+    launch_chain_fix(cf, h.stream);
+  }
+}
+
+// launches of iterations behind the one a solve stopped in (speculative, gated off) are not profile samples
+static void drop_speculative_samples(L& h, size_t mark, int iters) {
+  for (size_t i = mark; i < h.prof_pending.size(); ++i)
+    if (h.prof_pending[i].iter > iters) h.prof_pending[i].which = -1;
+}
+
 // x . (op x) summed per column into h.part0 for a ROW-major x (N x ld, the handle's whole window) through the blocked matvec:
 // x -> slab-major (scratch_slab), one launch (+ the chain fix-up), op x -> scratch_out.  Returns the rows of partial sums
 // h.part0 holds, 0 where the blocked matvec does not serve this lattice (the caller takes the plain apply's DOT form).
@@ -309,108 +301,205 @@ int blocked_quad_form(L& h, const host::ApplyPlan& plan, const OpParams& op, con
   ChainFixArgs cf{};
   blocked_setup(h, plan, op, scratch_slab, scratch_out, h.B.p, h.ld, with_path, grid, ba, cf);
   rows_to_slab(h, x_rows, scratch_slab, h.ld, h.c0, h.c1, grid, x_sub);
-  ba.gate = nullptr;
-  launch_apply_blocked(ba, grid, h.stream, nullptr, plan.shape);
+  apply_blocked(h, plan, ba, cf, grid, Gate{nullptr, 0.f});
   h.blk_applies += 1;
-  if (cf.chunks > 0) {
-    cf.gate = nullptr;
-    launch_chain_fix(cf, h.stream);
-  }
   return grid + cf.chunks;
 }
 
-CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, int max_iters, float tol) {
-  if (row_mode(h) && b.ld == h.ld) return run_cg_rows(h, op, b, with_path, max_iters, tol);
-  {
-    CgResult one{};
-    if (run_cg_small(h, op, b, with_path, max_iters, tol, one)) return one;
-  }
-  const int grid = cg_grid(h);
-  const host::ApplyPlan plan = apply_plan(h, b.c0, b.c1, b.ld, with_path);
-  const size_t nslots = (size_t)max_iters + 2;
-  ensure_ctrl(h, nslots);
-  uint32_t* const res_slots = ctrl_segment(h, 2 * nslots);  // zeroed: [residual per iteration | arrival counter per iteration]
-  uint32_t* done_ctr = res_slots + nslots;
+namespace {
+
+// One general-path solve: the host side of cg_solve (solver.py:6-37) as run_cg stages it -- construction (control words, stop
+// test route, the arguments that hold for the whole solve), init() (r = b - A x0, z, p, r . z), plan_ring(), the loop methods
+// host::cg_host_loop drives (host_logic.hpp), finish().
+struct CgSolve {
+  // ---- fixed for the solve ------------------------------------------------------------------------------------------
+  L& h;
+  const OpParams& op;
+  const CgBuffers& b;
+  const bool with_path;
+  const int max_iters;
+  const float tol;
+  const int grid;
+  const host::ApplyPlan plan;
+  const size_t nslots;
   // Single GPU: the last workgroup of each iteration's beta reduction writes the residual into host-mapped memory and
   // the host polls that word (no 4-byte copy, event record and event wait per iteration).  Under a communicator the
-  // residual first goes through the all-reduce (below; OSC_COMM_OVERLAP=0: in the solve's stream,
-  // read back by copy + event).
-  const bool mapped = h.comm == nullptr && h.mapped_residual;
+  // residual first goes through the all-reduce (publish_residual; OSC_COMM_OVERLAP=0: in the solve's stream, read back by
+  // copy + event).
+  const bool mapped;
   // Sharded (column windows): the stop test needs max over the ranks of the residual -- a 4-byte all-reduce per iteration,
   // tens of microseconds of latency on xGMI next to ~180 us of kernels per iteration in an 8-rank window of config 3.
-  // With the x update deferred (below) a speculative iteration writes scratch arrays only (r, p, Ap, alpha, beta), so it
-  // needs no gate and the solve's stream never waits for the all-reduce: that goes to a second stream behind an event
-  // per iteration, followed by a one-thread kernel that publishes the reduced word into the host-mapped slot the host
-  // polls, as on one GPU.  The host alone decides when to stop; a wrong guess of the last iteration costs one iteration
-  // of device time instead of five gated-off launches.
-  const bool xdefer = h.x_defer;
-  // What it costs (one-rank RCCL communicator, all-reduce latency ~0: docs/DESIGN_HISTORY.md section 6): ~17 us once per solve for the
-  // second stream's hand-over at the last iteration, and the expected last iteration's own form (an ungated speculative
-  // iteration must not touch x): 47 us at 768 columns, 6 at 96.  What it saves: every all-reduce latency but the last.
-  // Hence by default from four ranks on (narrow windows, 15-30 us per all-reduce); OSC_COMM_OVERLAP=1 / 0 force it.
-  const bool want_overlap = h.comm_overlap == 1 || (h.comm_overlap < 0 && h.world >= 4);
-  const bool overlap = h.comm != nullptr && want_overlap && h.mapped_residual && xdefer;
-  if (overlap) {
-    if (!h.comm_stream) h.comm_stream = acquire_stream(h.device);
-    while (h.step_events.size() < nslots) {
-      hipEvent_t e;
-      HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      h.step_events.push_back(e);
-    }
-    h.comm_stream_busy = true;  // from here on (also if the solve is abandoned half way): drained before the slots are reused
-  }
-  const bool polled = mapped || overlap;
-  constexpr uint32_t kPending = 0xFFFFFFFFu;  // never a residual (those are sqrt(...) >= 0 or a canonical NaN)
-  if (polled)
-    for (size_t i = 0; i < nslots; ++i) reinterpret_cast<volatile uint32_t*>(h.res_host)[i] = kPending;
-  const float* res_dev = reinterpret_cast<const float*>(res_slots);
-  SpmmArgs sa{};
-  sa.g = graph_view(h, with_path);
-  sa.op = op;
-  sa.B = b.B;
-  sa.psi = b.psi;
-  sa.N = h.N;
-  sa.ld = b.ld;
-  sa.c0 = b.c0;
-  sa.c1 = b.c1;
-  sa.part = h.part0.p;
+  // With the x update deferred a speculative iteration writes scratch arrays only (r, p, Ap, alpha, beta), so it needs no
+  // gate and the solve's stream never waits for the all-reduce: that goes to a second stream behind an event per iteration,
+  // followed by a one-thread kernel that publishes the reduced word into the host-mapped slot the host polls, as on one
+  // GPU.  The host alone decides when to stop; a wrong guess of the last iteration costs one iteration of device time
+  // instead of five gated-off launches.
+  // What it costs (one-rank RCCL communicator, all-reduce latency ~0: docs/DESIGN_HISTORY.md section 6): ~17 us once per
+  // solve for the second stream's hand-over at the last iteration, and the expected last iteration's own form (an ungated
+  // speculative iteration must not touch x): 47 us at 768 columns, 6 at 96.  What it saves: every all-reduce latency but
+  // the last.  Hence by default from four ranks on (narrow windows, 15-30 us per all-reduce); OSC_COMM_OVERLAP=1 / 0 force it.
+  const bool overlap;
+  const bool polled;  // the host reads residuals from the host-mapped words (false: copy + event per iteration)
+  uint32_t* res_slots = nullptr;  // zeroed: [residual per iteration | arrival counter per iteration]
+  uint32_t* done_ctr = nullptr;
   // The settle from an aliased U (b.defer_x0: x0 = the anchors, X = U's empty buffer): no INIT form writes a copy of x0
   // into X -- each is told that x0 IS its solution array, as in an in-place solve -- and the one launch that applies
-  // iteration 1's x update reads x from x0 and writes it to X (UpdateArgs::Xin below).
-  const float* const x1_in = b.defer_x0 && b.X != b.x0 && !overlap ? b.x0 : nullptr;
-  float* const x_init = x1_in != nullptr ? const_cast<float*>(b.x0) : b.X;  // (only compared with x0, never written, then)
-  // r = b - A x0 ; z ; p ; rz
-  sa.X = b.x0;
-  sa.OUT = x_init;
-  sa.R = b.R;
-  sa.P = b.P;
-  sa.U = b.rhsU;
-  sa.Y = b.rhsY;
-  sa.gate = nullptr;
-  // slab-major search direction: only where the XCD-affine slab apply runs (its gathers then read contiguous slabs)
-  const bool pblk = plan.pblk;
-  sa.pblk = pblk ? h.N : 0;
-  // source-blocked CG matvec (k_apply_blocked) where the slab an XCD gathers from is far larger than its L2
+  // iteration 1's x update reads x from x0 and writes it to X (UpdateArgs::Xin).
+  const float* const x1_in;
+  float* const x_init;  // (only compared with x0, never written, then)
+  const int stop_guess;  // the count of the handle's previous solve of this kind (0: unknown)
+  float* Pbuf;   // search direction / operator output: the fused INIT pass leaves p in the AP array and swaps the two for
+  float* APbuf;  // the rest of the solve (init() alone changes them)
+  size_t prof_mark = 0;  // the handle's pending profile samples when the loop started
+
+  // ---- where x is updated ---------------------------------------------------------------------------------------------
+  // Deferred x update: iteration it's x += alpha p is applied by iteration it + 1's p update, which reads p anyway (x, r,
+  // p in / x, p out there, r, Ap in / r out in the x-r kernel: 8 array passes per iteration instead of 9), or by
+  // finish_x behind an iteration that has no successor enqueued.  The iteration expected to be the last (stop_guess, or
+  // max_iters) takes k_update_xr's "last" form instead: x finished next to the r update, the new r not stored (five passes
+  // instead of three there and three in finish_x).  Which launch carries which update is decided by host::CgXSchedule
+  // (host_logic.hpp; swept against a model of the device's gating on the CPU box, tests/host_logic/sweep_host_logic.cpp).
+  host::CgXSchedule xs;
+  // The ring of kept directions (host_logic.hpp: plan_x_ring, CgXRing): K >= 2 slots -- direction `it` in slot it % K, its
+  // alpha in the same slot of h.alpha_ring -- and x is written by k_update_x_ring alone: once per solve where the solve
+  // takes at most K iterations.  K = 1: everything runs as CgXSchedule says.
+  host::CgXRing ring;
+  float* slot[host::kXRingMax] = {nullptr, nullptr, nullptr, nullptr};
+  float* aslot[host::kXRingMax] = {nullptr, nullptr, nullptr, nullptr};
+
+  // ---- kernel arguments: members, edited launch by launch --------------------------------------------------------------
+  // Every launch site sets each field that differs between launch kinds; the rest is set once, here said where.
+  // sa (k_spmm): the constructor sets g, op, B, psi, N, ld, c0, c1, part, R, P, U, Y (the INIT outputs and rhs: the AP mode
+  //   reads none of them); per launch: X, OUT, xblk, pblk, gate, gate_tol (spmm_slabbed sets deep, xs, xs_groups and the slab).
+  // ua (k_update_p / _xr / _x): the constructor sets X, R, B, beta, part_rr, part_rz, op, N, ld, c0, c1, pblk, temporal,
+  //   init() sets AP; per launch (set_update): gate, gate_tol, xmode, Xin, alpha, P, Pout (for_windows sets the window).
+  // ba (k_apply_blocked), cf (k_chain_fix): blocked_setup sets everything but X, OUT, gate, gate_tol, which are per launch.
+  SpmmArgs sa{};
+  UpdateArgs ua{};
   BlkArgs ba{};
   ChainFixArgs cf{};
-  if (plan.src_blocks > 0) blocked_setup(h, plan, op, b.P, b.AP, b.B, b.ld, with_path, grid, ba, cf);
 
-  // (an inertia start hands over x0 IN the AP array, which the blocked matvec would overwrite with A x0 before
-  // init_finish has read x0: such a solve keeps the gathering INIT kernel, which reads x0 completely first)
-  int init_part_rows = grid;  // rows of r . z partials the INIT pass leaves (+ the chain fix-up's behind the fused pass)
-  float* Pbuf = b.P;   // search direction / operator output: the fused INIT pass below leaves p in the AP array and
-  float* APbuf = b.AP;  // swaps the two for the rest of the solve
-  // (the rhs rows the fused pass can take besides x0 itself: one -- the state term must be x0 or absent, and if y is a
-  // third array the solution array must be x0)
-  const bool fuse_u = b.rhsU == b.x0 || op.rbU == 0.f;
-  const bool fuse_y = b.rhsY == b.x0 || x_init == b.x0;
-  if (ba.nb > 0 && h.blk_init && h.blk_init_fused && fuse_u && fuse_y && b.x0 != b.AP) {
-    // r = b - A x0 INSIDE the blocked matvec (the in-place warm-started settle: x0 is also the rhs state term and the
-    // solution array; the U* solve: x0 is Y, no state term): x0 slab-major (into P, or the anchors' image), then one launch
-    // gathers A x0 and leaves r, z (slab-major, in the AP array), x0 in the solution array and the r . z column sums.
+  CgSolve(L& h_, const OpParams& op_, const CgBuffers& b_, bool with_path_, int max_iters_, float tol_)
+      : h(h_), op(op_), b(b_), with_path(with_path_), max_iters(max_iters_), tol(tol_), grid(cg_grid(h_)),
+        plan(apply_plan(h_, b_.c0, b_.c1, b_.ld, with_path_)), nslots((size_t)max_iters_ + 2), mapped(h_.comm == nullptr),
+        overlap(h_.comm != nullptr && (h_.comm_overlap == 1 || (h_.comm_overlap < 0 && h_.world >= 4)) && h_.x_defer),
+        polled(mapped || overlap), x1_in(b_.defer_x0 && b_.X != b_.x0 && !overlap ? b_.x0 : nullptr),
+        x_init(x1_in != nullptr ? const_cast<float*>(b_.x0) : b_.X), stop_guess(h_.predicted_iters[b_.kind]), Pbuf(b_.P),
+        APbuf(b_.AP) {
+    ensure_ctrl(h, nslots);
+    res_slots = ctrl_segment(h, 2 * nslots);
+    done_ctr = res_slots + nslots;
+    if (overlap) {
+      if (!h.comm_stream) h.comm_stream = acquire_stream(h.device);
+      while (h.step_events.size() < nslots) {
+        hipEvent_t e;
+        HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        h.step_events.push_back(e);
+      }
+      h.comm_stream_busy = true;  // from here on (also if the solve is abandoned half way): drained before the slots are reused
+    }
+    if (polled)  // (kCtrlPending is never a residual: those are sqrt(...) >= 0 or a canonical NaN)
+      for (size_t i = 0; i < nslots; ++i) reinterpret_cast<volatile uint32_t*>(h.res_host)[i] = kCtrlPending;
+    sa.g = graph_view(h, with_path);
+    sa.op = op;
+    sa.B = b.B;
+    sa.psi = b.psi;
+    sa.N = h.N;
+    sa.ld = b.ld;
+    sa.c0 = b.c0;
+    sa.c1 = b.c1;
+    sa.part = h.part0.p;
+    sa.R = b.R;
+    sa.P = b.P;
+    sa.U = b.rhsU;
+    sa.Y = b.rhsY;
+    // source-blocked CG matvec (k_apply_blocked) where the slab an XCD gathers from is far larger than its L2
+    if (plan.src_blocks > 0) blocked_setup(h, plan, op, b.P, b.AP, b.B, b.ld, with_path, grid, ba, cf);
+    // slab-major search direction: only where the XCD-affine slab apply runs (its gathers then read contiguous slabs)
+    ua.pblk = plan.pblk ? h.N : 0;
+    ua.temporal = 5.0 * (double)h.N * (double)(b.c1 - b.c0) * 4.0 <= h.temporal_mb * 1048576.0;
+    ua.X = b.X;
+    ua.R = b.R;
+    ua.B = b.B;
+    ua.beta = h.beta.p;
+    ua.part_rr = h.part0.p;
+    ua.part_rz = h.part1.p;
+    ua.op = op;
+    ua.N = h.N;
+    ua.ld = b.ld;
+    ua.c0 = b.c0;
+    ua.c1 = b.c1;
+    xs.xdefer = h.x_defer;
+    xs.last_form = h.x_last_form;
+    xs.ungated = overlap;
+    xs.stop_guess = stop_guess;
+    xs.max_iters = max_iters;
+    ring.K = 1;  // (until plan_ring)
+  }
+
+  bool ringed() const { return ring.K > 1; }
+  float* dir(int it) const { return ringed() ? slot[it % ring.K] : Pbuf; }  // where direction `it` lives
+  float* alpha_of(int it) const { return ringed() ? aslot[it % ring.K] : h.alpha.p; }
+
+  // r = b - A x0 ; z ; p ; rz.  Returns the rows of r . z partials the pass left (+ the chain fix-up's behind the fused pass).
+  int init() {
+    int part_rows = grid;
+    // (the rhs rows the fused pass can take besides x0 itself: one -- the state term must be x0 or absent, and if y is a
+    // third array the solution array must be x0)
+    const bool fuse_u = b.rhsU == b.x0 || op.rbU == 0.f;
+    const bool fuse_y = b.rhsY == b.x0 || x_init == b.x0;
+    // (an inertia start hands over x0 IN the AP array, which the blocked matvec would overwrite with A x0 before
+    // init_finish has read x0: such a solve keeps the gathering INIT kernel, which reads x0 completely first)
+    if (ba.nb > 0 && h.blk_init && h.blk_init_fused && fuse_u && fuse_y && b.x0 != b.AP) {
+      part_rows = init_fused();
+    } else if (ba.nb > 0 && h.blk_init && b.x0 != b.AP) {
+      // r = b - A x0 around the blocked matvec: x0 slab-major (into P, or the anchors' image), A x0 -> AP, then r, z, p = z, r . z
+      ProfScope ps(h, 4, 0);
+      ba.X = cf.X = init_operand(h, b, b.P, grid);
+      ba.OUT = cf.OUT = b.AP;
+      apply_blocked(h, plan, ba, cf, grid, Gate{nullptr, 0.f});  // (an INIT pass: not counted in blk_applies)
+      InitFinishArgs fa{};
+      fa.AP = b.AP;
+      fa.X0 = b.x0;
+      fa.X = x_init;
+      fa.R = b.R;
+      fa.P = b.P;
+      fa.U = b.rhsU;
+      fa.Y = b.rhsY;
+      fa.B = b.B;
+      fa.psi = b.psi;
+      fa.part = h.part0.p;
+      fa.op = op;
+      fa.N = h.N;
+      fa.pblk = h.N;
+      fa.ld = b.ld;
+      fa.c0 = b.c0;
+      fa.c1 = b.c1;
+      for_windows(fa, [&](const InitFinishArgs& w) { launch_init_finish(w, grid, h.stream); });
+    } else {
+      sa.X = b.x0;
+      sa.OUT = x_init;
+      sa.xblk = 0;
+      sa.pblk = plan.pblk ? h.N : 0;
+      sa.gate = nullptr;
+      sa.gate_tol = 0.f;
+      spmm_slabbed(h, plan, SPMM_INIT, sa, grid);
+    }
+    launch_reduce_init(h.part0.p, part_rows, b.ld, b.c0, b.c1, h.rz.p, h.stream);
+    ua.AP = APbuf;
+    h.last_plan = plan;
+    return part_rows;
+  }
+
+  // r = b - A x0 INSIDE the blocked matvec (the in-place warm-started settle: x0 is also the rhs state term and the
+  // solution array; the U* solve: x0 is Y, no state term): x0 slab-major (into P, or the anchors' image), then one launch
+  // gathers A x0 and leaves r, z (slab-major, in the AP array), x0 in the solution array and the r . z column sums.
+  int init_fused() {
     ProfScope ps(h, 4, 0);
-    ba.X = init_operand(h, b, b.P, grid);
-    cf.X = ba.X;
+    ba.X = cf.X = init_operand(h, b, b.P, grid);
+    ba.OUT = nullptr;
+    ba.gate = nullptr;
+    ba.gate_tol = 0.f;
     BlkInit bi{};
     bi.Y = b.rhsY == b.x0 ? nullptr : b.rhsY;
     bi.Xcopy = x_init == b.x0 ? nullptr : b.X;
@@ -422,11 +511,9 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
     bi.rbB = op.rbB;
     bi.md_B = op.precond ? op.md_B : 0.f;
     bi.md_const = op.precond ? op.md_const : 1.f;
-    ba.gate = nullptr;
-    ba.OUT = nullptr;
     // From the anchors' resident image: their row sums W.Y are the same for every such solve on this graph copy.  The first
     // one gathers them and leaves them behind (one more store per row), the later ones stream them (k_init_cached: the
-    // same r, z and r . z sums to the bit).
+    // same r, z and r . z sums to the bit).  (INIT passes are not counted in blk_applies.)
     const bool wy_route = h.anchor_wy && h.anchor_slab && ba.X == h.Ys.p && bi.Y == nullptr;
     if (wy_route && h.derived.wy_nb == ba.nb) {
       bi.WY = h.WYs.p;
@@ -441,143 +528,85 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
     } else {
       launch_apply_blocked(ba, grid, h.stream, &bi, plan.shape);
     }
+    int part_rows = grid;
     if (cf.chunks > 0) {  // the chain prior's rows: their r, z and r . z still lack the chain term
       ChainFixArgs ci = cf;
+      ci.OUT = b.AP;  // (not written in this form: what blocked_setup left there)
       ci.gate = nullptr;
+      ci.gate_tol = 0.f;
       ci.initR = b.R;
       ci.initZ = b.AP;
       ci.B = b.B;
       ci.md_B = bi.md_B;
       ci.md_const = bi.md_const;
       launch_chain_fix(ci, h.stream);
-      init_part_rows = grid + cf.chunks;
+      part_rows = grid + cf.chunks;
     }
-    std::swap(Pbuf, APbuf);
-    ba.X = Pbuf;
-    ba.OUT = APbuf;
-    cf.X = Pbuf;
-    cf.OUT = APbuf;
-  } else if (ba.nb > 0 && h.blk_init && b.x0 != b.AP) {
-    // r = b - A x0 around the blocked matvec: x0 slab-major (into P, or the anchors' image), A x0 -> AP, then r, z, p = z, r . z
-    ProfScope ps(h, 4, 0);
-    ba.X = init_operand(h, b, b.P, grid);
-    cf.X = ba.X;
-    ba.gate = nullptr;
-    launch_apply_blocked(ba, grid, h.stream, nullptr, plan.shape);
-    if (cf.chunks > 0) {
-      cf.gate = nullptr;
-      launch_chain_fix(cf, h.stream);
-    }
-    ba.X = b.P;
-    cf.X = b.P;
-    InitFinishArgs fa{};
-    fa.AP = b.AP;
-    fa.X0 = b.x0;
-    fa.X = x_init;
-    fa.R = b.R;
-    fa.P = b.P;
-    fa.U = b.rhsU;
-    fa.Y = b.rhsY;
-    fa.B = b.B;
-    fa.psi = b.psi;
-    fa.part = h.part0.p;
-    fa.op = op;
-    fa.N = h.N;
-    fa.pblk = h.N;
-    fa.ld = b.ld;
-    for (int32_t s0 = b.c0; s0 < b.c1; s0 += 2048) {
-      fa.c0 = s0;
-      fa.c1 = std::min(b.c1, s0 + 2048);
-      launch_init_finish(fa, grid, h.stream);
-    }
-  } else {
-    spmm_slabbed(h, plan, SPMM_INIT, sa, grid);
+    std::swap(Pbuf, APbuf);  // z, the first direction, lies in the AP array
+    return part_rows;
   }
-  launch_reduce_init(h.part0.p, init_part_rows, b.ld, b.c0, b.c1, h.rz.p, h.stream);
-  UpdateArgs ua{};
-  ua.pblk = pblk ? h.N : 0;
-  ua.temporal = 5.0 * (double)h.N * (double)(b.c1 - b.c0) * 4.0 <= h.temporal_mb * 1048576.0;
-  ua.X = b.X;
-  ua.R = b.R;
-  ua.P = Pbuf;
-  ua.AP = APbuf;
-  ua.B = b.B;
-  ua.alpha = h.alpha.p;
-  ua.beta = h.beta.p;
-  ua.part_rr = h.part0.p;
-  ua.part_rz = h.part1.p;
-  ua.op = op;
-  ua.N = h.N;
-  ua.ld = b.ld;
-  ua.c0 = b.c0;
-  ua.c1 = b.c1;
-  sa.X = Pbuf;
-  sa.OUT = APbuf;
-  sa.xblk = pblk ? h.N : 0;
-  sa.pblk = 0;
-  h.last_plan = plan;
-  // Deferred x update: iteration it's x += alpha p is applied by iteration it + 1's p update, which reads p anyway (x, r,
-  // p in / x, p out there, r, Ap in / r out in the x-r kernel: 8 array passes per iteration instead of 9), or by
-  // finish_x behind an iteration that has no successor enqueued.  The iteration expected to be the last (the count of
-  // the handle's previous solve of this kind, or max_iters) takes k_update_xr's "last" form instead: x finished next
-  // to the r update, the new r not stored (five passes instead of three there and three in finish_x).  Which launch
-  // carries which update is decided by host::CgXSchedule (host_logic.hpp; swept against a model of the device's
-  // gating on the CPU box, tests/host_logic/sweep_host_logic.cpp).
-  const int stop_guess = h.predicted_iters[b.kind];
-  host::CgXSchedule xs;
-  xs.xdefer = xdefer;
-  xs.last_form = h.x_last_form;
-  xs.ungated = overlap;
-  xs.stop_guess = stop_guess;
-  xs.max_iters = max_iters;
-  // The ring of kept directions (host_logic.hpp: plan_x_ring, CgXRing): K >= 2 slots -- direction `it` in slot it % K, its
-  // alpha in the same slot of h.alpha_ring -- and x is written by k_update_x_ring alone: once per solve where the solve
-  // takes at most K iterations.  K = 1: everything below runs as CgXSchedule says.
-  host::XRingInputs ri;
-  ri.predicted = stop_guess;
-  ri.max_iters = max_iters;
-  ri.array_bytes = (int64_t)h.N * b.ld * 4;
-  ri.ungated = overlap;
-  ri.xdefer = xdefer;
-  ri.forced = h.x_ring_force;
-  const size_t ring_n = (size_t)h.N * b.ld;
-  int held = 0;  // slots the handle holds at this size: only a solve that wants more asks the device what is free
-  while (held < host::kXRingMax - 1 && h.xring[held].n >= ring_n) ++held;
-  ri.free_bytes = std::numeric_limits<int64_t>::max();
-  if (host::plan_x_ring(ri) - 1 > held) {
-    size_t free_b = 0, total_b = 0;
-    HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-    ri.free_bytes = (int64_t)free_b + ri.array_bytes * held;
-  }
-  host::CgXRing ring;
-  ring.K = host::plan_x_ring(ri);
-  ring.last_form = h.x_last_form;
-  ring.stop_guess = stop_guess;
-  ring.max_iters = max_iters;
-  float* slot[host::kXRingMax] = {nullptr, nullptr, nullptr, nullptr};
-  float* aslot[host::kXRingMax] = {nullptr, nullptr, nullptr, nullptr};
-  if (ring.K > 1) {
-    try {
-      for (int j = 0; j < ring.K - 1; ++j)
-        if (h.xring[j].n < ring_n) h.xring[j].alloc(ring_n);
-      const size_t an = (size_t)std::max(h.ld, b.ld);
-      if (h.alpha_ring.n < an * host::kXRingMax) h.alpha_ring.alloc(an * host::kXRingMax);
-      for (int i = 0; i < ring.K; ++i) aslot[i] = h.alpha_ring.p + (size_t)i * an;
-    } catch (const HipError&) {  // no solve fails over its ring
-      (void)hipGetLastError();
-      for (DevBuf<float>& r : h.xring) r.release();
-      ring.K = 1;
+
+  // How many directions the solve keeps (plan_x_ring) and where: only a solve that wants more slots than the handle holds at
+  // this size asks the device what is free; no solve fails over its ring.
+  void plan_ring() {
+    host::XRingInputs ri;
+    ri.predicted = stop_guess;
+    ri.max_iters = max_iters;
+    ri.array_bytes = (int64_t)h.N * b.ld * 4;
+    ri.ungated = overlap;
+    ri.xdefer = h.x_defer;
+    ri.forced = h.x_ring_force;
+    const size_t ring_n = (size_t)h.N * b.ld;
+    int held = 0;
+    while (held < host::kXRingMax - 1 && h.xring[held].n >= ring_n) ++held;
+    ri.free_bytes = std::numeric_limits<int64_t>::max();
+    if (host::plan_x_ring(ri) - 1 > held) {
+      size_t free_b = 0, total_b = 0;
+      HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+      ri.free_bytes = (int64_t)free_b + ri.array_bytes * held;
+    }
+    ring.K = host::plan_x_ring(ri);
+    ring.last_form = h.x_last_form;
+    ring.stop_guess = stop_guess;
+    ring.max_iters = max_iters;
+    if (ring.K > 1) {
+      try {
+        for (int j = 0; j < ring.K - 1; ++j)
+          if (h.xring[j].n < ring_n) h.xring[j].alloc(ring_n);
+        const size_t an = (size_t)std::max(h.ld, b.ld);
+        if (h.alpha_ring.n < an * host::kXRingMax) h.alpha_ring.alloc(an * host::kXRingMax);
+        for (int i = 0; i < ring.K; ++i) aslot[i] = h.alpha_ring.p + (size_t)i * an;
+      } catch (const HipError&) {
+        (void)hipGetLastError();
+        for (DevBuf<float>& r : h.xring) r.release();
+        ring.K = 1;
+      }
+    }
+    if (ring.K > 1) {
+      slot[1 % ring.K] = Pbuf;  // direction 1 is where the INIT pass left z (behind the fused pass: the AP array)
+      for (int i = 0, j = 0; i < ring.K; ++i)
+        if (i != 1 % ring.K) slot[i] = h.xring[j++].p;
     }
   }
-  const bool ringed = ring.K > 1;
-  if (ringed) {
-    slot[1 % ring.K] = Pbuf;  // direction 1 is where the INIT pass left z
-    for (int i = 0, j = 0; i < ring.K; ++i)
-      if (i != 1 % ring.K) slot[i] = h.xring[j++].p;
+
+  // the per-launch fields of ua, all of them
+  void set_update(const float* gate, int32_t xmode, const float* Xin, const float* alpha, float* P, float* Pout) {
+    ua.gate = gate;
+    ua.gate_tol = tol;
+    ua.xmode = xmode;
+    ua.Xin = Xin;
+    ua.alpha = alpha;
+    ua.P = P;
+    ua.Pout = Pout;
   }
-  auto dir = [&](int it) { return slot[it % ring.K]; };
-  auto alpha_of = [&](int it) { return ringed ? aslot[it % ring.K] : h.alpha.p; };
-  auto ring_pass = [&](host::CgXRing::Pass ps, const float* gate) {
+  void update_p() { for_windows(ua, [&](const UpdateArgs& w) { launch_update_p(w, grid, h.stream); }); }
+  void update_xr() { for_windows(ua, [&](const UpdateArgs& w) { launch_update_xr(w, grid, h.stream); }); }
+  // P / Pout of iteration it's x-r kernel and of the redone r update behind it: what that iteration's p update left there.
+  // No form of k_update_xr a ring solve launches reads them (x is left alone); they keep the values they always had.
+  float* xr_p(int it) const { return dir(std::max(it - 1, 1)); }
+  float* xr_pout(int it) const { return ringed() && it > 1 ? dir(it) : nullptr; }
+
+  void ring_pass(host::CgXRing::Pass ps, const float* gate) {
     if (ps.count <= 0) return;
     XRingArgs xa{};
     xa.X = b.X;
@@ -593,75 +622,67 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
     xa.gate_tol = tol;
     xa.pblk = ua.pblk;
     xa.temporal = ua.temporal;
-    for (int32_t s0 = b.c0; s0 < b.c1; s0 += 2048) {
-      xa.c0 = s0;
-      xa.c1 = std::min(b.c1, s0 + 2048);
-      launch_update_x_ring(xa, grid, h.stream);
-    }
-  };
-  auto finish_x = [&](int it) {
-    ua.gate = nullptr;
-    ua.xmode = OSC_XMODE_XR_SKIPS_X | OSC_XMODE_P_APPLIES_X;
-    ua.Xin = it == 1 ? x1_in : nullptr;
+    xa.c0 = b.c0;
+    xa.c1 = b.c1;
+    for_windows(xa, [&](const XRingArgs& w) { launch_update_x_ring(w, grid, h.stream); });
+  }
+  void finish_x(int it) {  // iteration it's x += alpha p on its own, ungated (not in a ring solve)
+    set_update(nullptr, OSC_XMODE_XR_SKIPS_X | OSC_XMODE_P_APPLIES_X, it == 1 ? x1_in : nullptr, h.alpha.p, Pbuf, nullptr);
     for_windows(ua, [&](const UpdateArgs& w) { launch_update_x(w, grid, h.stream); });
     xs.finished(it);
-  };
-  auto enqueue_iter = [&](int it, bool speculative) {  // everything of iteration `it` up to its residual, gated on iteration it-1
-    // (overlap: no gates -- an iteration writes scratch arrays only until the host has seen its predecessor unconverged)
-    const Gate g{it > 1 && !overlap ? res_dev + (it - 1) : nullptr, tol};
-    sa.gate = g.p;
-    sa.gate_tol = tol;
-    ua.gate = g.p;
-    ua.gate_tol = tol;
+  }
+
+  // everything of iteration `it` up to its residual, gated on iteration it - 1
+  // (overlap: no gates -- an iteration writes scratch arrays only until the host has seen its predecessor unconverged)
+  void enqueue(int it, bool speculative) {
+    const Gate g{it > 1 && !overlap ? reinterpret_cast<const float*>(res_slots) + (it - 1) : nullptr, tol};
     host::CgXSchedule::IterForm form{false, host::CgXSchedule::XR_SKIPS_X};
-    if (!ringed) form = xs.enqueue(it, speculative);
-    if (ringed && it > 1) {
+    if (!ringed()) form = xs.enqueue(it, speculative);
+    if (it > 1) {
       ProfScope ps(h, 2, it);
-      // the slot p_it goes to still holds a direction x lacks: this iteration's flush, then p_it = z + beta p_{it-1}
-      const host::CgXRing::Pass fl = ring.flush_before_p(it);
-      ring_pass(fl, g.p);
-      ua.xmode = 0;
-      ua.Xin = nullptr;
-      ua.P = dir(it - 1);
-      ua.Pout = dir(it);
-      for_windows(ua, [&](const UpdateArgs& w) { launch_update_p(w, grid, h.stream); });
-      ba.X = dir(it);
-      cf.X = dir(it);
-      sa.X = dir(it);
-    } else if (it > 1) {
-      ProfScope ps(h, 2, it);
-      // p = z + beta p (solver.py:32-36), and iteration it - 1's x += alpha p (solver.py:27) with the p it replaces
-      ua.xmode = form.p_applies_x ? OSC_XMODE_P_APPLIES_X : 0;
-      ua.Xin = it == 2 ? x1_in : nullptr;  // (this launch applies iteration it - 1's x update)
-      for_windows(ua, [&](const UpdateArgs& w) { launch_update_p(w, grid, h.stream); });
+      if (ringed()) {
+        // the slot p_it goes to still holds a direction x lacks: this iteration's flush, then p_it = z + beta p_{it-1}
+        // (alpha: iteration it - 1's, as its x-r kernel left it; a p update that applies no x update does not read it)
+        ring_pass(ring.flush_before_p(it), g.p);
+        set_update(g.p, 0, nullptr, alpha_of(it - 1), dir(it - 1), dir(it));
+      } else {
+        // p = z + beta p (solver.py:32-36), and iteration it - 1's x += alpha p (solver.py:27) with the p it replaces
+        // (Xin: this launch applies iteration it - 1's x update)
+        set_update(g.p, form.p_applies_x ? OSC_XMODE_P_APPLIES_X : 0, it == 2 ? x1_in : nullptr, h.alpha.p, Pbuf, nullptr);
+      }
+      update_p();
     }
     if (ba.nb > 0) {  // Ap and column sums of p.Ap
       ProfScope ps(h, 0, it);
-      ba.gate = g.p;
-      ba.gate_tol = tol;
-      launch_apply_blocked(ba, grid, h.stream, nullptr, plan.shape);
-      if (cf.chunks > 0) {
-        cf.gate = g.p;
-        cf.gate_tol = tol;
-        launch_chain_fix(cf, h.stream);
-      }
+      ba.X = cf.X = dir(it);
+      ba.OUT = cf.OUT = APbuf;
+      apply_blocked(h, plan, ba, cf, grid, g);
       h.blk_applies += 1;
     } else {
+      sa.X = dir(it);
+      sa.OUT = APbuf;
+      sa.xblk = plan.pblk ? h.N : 0;
+      sa.pblk = 0;
+      sa.gate = g.p;
+      sa.gate_tol = tol;
       spmm_slabbed(h, plan, SPMM_AP, sa, grid, it);
     }
     launch_reduce_alpha(h.part0.p, grid + (ba.nb > 0 ? cf.chunks : 0), b.ld, b.c0, b.c1, h.rz.p, alpha_of(it), g, h.stream);
-    if (ringed) {
+    {
       ProfScope ps(h, 1, it);
-      ua.alpha = alpha_of(it);
-      ua.xmode = OSC_XMODE_XR_SKIPS_X | (ring.xr_last(it) ? OSC_XMODE_XR_BARE : 0);
-      ua.Xin = nullptr;
-      for_windows(ua, [&](const UpdateArgs& w) { launch_update_xr(w, grid, h.stream); });
-    } else {
-      ProfScope ps(h, 1, it);
-      ua.xmode = form.xr == host::CgXSchedule::XR_LAST ? OSC_XMODE_XR_LAST : form.xr == host::CgXSchedule::XR_SKIPS_X ? OSC_XMODE_XR_SKIPS_X : 0;
-      ua.Xin = it == 1 ? x1_in : nullptr;  // (the forms that carry an x update here carry iteration it's)
-      for_windows(ua, [&](const UpdateArgs& w) { launch_update_xr(w, grid, h.stream); });
+      if (ringed()) {
+        set_update(g.p, OSC_XMODE_XR_SKIPS_X | (ring.xr_last(it) ? OSC_XMODE_XR_BARE : 0), nullptr, alpha_of(it), xr_p(it), xr_pout(it));
+      } else {  // (Xin: the forms that carry an x update here carry iteration it's)
+        const int32_t xmode = form.xr == host::CgXSchedule::XR_LAST ? OSC_XMODE_XR_LAST : form.xr == host::CgXSchedule::XR_SKIPS_X ? OSC_XMODE_XR_SKIPS_X : 0;
+        set_update(g.p, xmode, it == 1 ? x1_in : nullptr, h.alpha.p, Pbuf, nullptr);
+      }
+      update_xr();
     }
+    publish_residual(it, g);
+  }
+
+  // beta, the residual of iteration `it` and its way to the host: mapped, overlap via the second stream, copy + event
+  void publish_residual(int it, Gate g) {
     if (mapped) {
       launch_reduce_beta(h.part0.p, h.part1.p, grid, b.ld, b.c0, b.c1, h.rz.p, h.beta.p, res_slots + it, g, h.stream,
                          done_ctr + it, h.res_host_dev + it);
@@ -675,96 +696,81 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
       launch_publish_word(res_slots + it, reinterpret_cast<uint32_t*>(h.res_host_dev + it), h.comm_stream);
       return;
     }
-    // column-sharded: the stop test is the max over all shards (solver.py:29)
-    if (h.comm) h.comm->allreduce(res_slots + it, 1, COMM_F32, COMM_MAX, h.stream);
+    // column-sharded (not mapped: there is a communicator): the stop test is the max over all shards (solver.py:29)
+    h.comm->allreduce(res_slots + it, 1, COMM_F32, COMM_MAX, h.stream);
     HIP_CHECK(hipMemcpyAsync(h.res_host + it, res_slots + it, 4, hipMemcpyDeviceToHost, h.stream));
     HIP_CHECK(hipEventRecord(h.iter_events[(size_t)it], h.stream));
-  };
-  auto wait_residual = [&](int it) -> float {
-    if (!polled) {
-      HIP_CHECK(hipEventSynchronize(h.iter_events[(size_t)it]));
-      return h.res_host[it];
-    }
-    volatile uint32_t* slot = reinterpret_cast<volatile uint32_t*>(h.res_host) + it;
-    const double t_start = now_ms();
-    for (uint64_t spin = 1;; ++spin) {
-      const uint32_t bits = *slot;
-      if (bits != kPending) {
-        float v;
-        std::memcpy(&v, &bits, 4);
-        return v;
-      }
-      if ((spin & 0x3FFF) == 0) {  // every ~16k polls: has the stream died or drained without publishing?
-        hipError_t q = hipStreamQuery(h.stream);
-        if (q == hipSuccess && overlap) q = hipStreamQuery(h.comm_stream);  // the word comes out of the second stream
-        if (q != hipSuccess && q != hipErrorNotReady) hip_check(q, "hipStreamQuery (CG residual wait)", __FILE__, __LINE__);
-        if (q == hipSuccess && *slot == kPending) throw HipError("CG iteration finished without publishing its residual");
-        if (now_ms() - t_start > 120000.0) throw HipError("timeout waiting for a CG residual");
-      }
-      __builtin_ia32_pause();
-    }
-  };
+  }
 
-  h.history.clear();
-  CgResult out{max_iters, 0.f, b.X};
-  const size_t prof_mark = h.prof_pending.size();
-  // Iteration it + 1 is enqueued before iteration it's residual is read -- except behind the iteration the previous
-  // solve of this handle converged in: repeated settles of one lattice take the same count, and the five gated-off
-  // launches of a needless speculative iteration cost ~22 us (8 % of a settle at N = 20000, D = 128; ungated under a
-  // communicator: a whole iteration).  A wrong guess the other way costs one host round trip: the iteration is then
-  // enqueued after its predecessor's residual has been read.
-  // (Every rank of a sharded solve sees the same residuals, hence takes the same decisions.)
-  int enqueued = 1;
-  enqueue_iter(1, false);
-  for (int it = 1; it <= max_iters; ++it) {
-    if (it < max_iters && it != stop_guess && enqueued == it) {
-      enqueue_iter(++enqueued, true);  // speculative: no-ops if `it` converged (overlap: ungated, scratch arrays only)
-    } else if (ringed) {
-      // nothing is enqueued behind this iteration for now and it is a real one: the pending directions up to it go into x
-      // behind its x-r kernel, while the host waits for its residual
+  void idle_before_wait(int it) {
+    if (ringed()) {
+      // the pending directions up to `it` go into x behind its x-r kernel, while the host waits for its residual
       ring_pass(ring.pass_before_wait(it), nullptr);
     } else if (xs.finish_before_wait(it)) {
-      // nothing is enqueued behind this iteration for now (the expected last one): its x update goes out at once.  The
-      // host has seen iteration it - 1 unconverged, so iteration `it` is a real one whatever its residual will say.
-      finish_x(it);
+      finish_x(it);  // (the expected last one): its x update goes out at once
     }
-    const float res = wait_residual(it);
+  }
+  float wait(int it) {  // iteration it's residual, into the handle's history
+    float res;
+    if (polled) {  // (overlap: the word comes out of the second stream)
+      const uint32_t bits = poll_host_word(h, reinterpret_cast<volatile uint32_t*>(h.res_host) + it,
+                                           overlap ? h.comm_stream : nullptr, "a CG iteration's residual");
+      std::memcpy(&res, &bits, 4);
+    } else {
+      HIP_CHECK(hipEventSynchronize(h.iter_events[(size_t)it]));
+      res = h.res_host[it];
+    }
     h.history.push_back(res);
-    out.res = res;
-    if ((double)res <= (double)tol) {
-      out.iters = it;
-      break;
-    }
-    if (it < max_iters && enqueued == it) {  // the guess was wrong: go on
-      if (ringed ? ring.restore_r(it) : xs.restore_r(it)) {  // ... from the r this iteration computed but did not keep
-        ua.gate = nullptr;
-        ua.alpha = alpha_of(it);
-        ua.xmode = OSC_XMODE_XR_SKIPS_X;
-        ua.Xin = nullptr;
-        for_windows(ua, [&](const UpdateArgs& w) { launch_update_xr(w, grid, h.stream); });
-      }
-      enqueue_iter(++enqueued, false);
+    return res;
+  }
+  void go_on(int it) {  // the solve goes on behind `it` ... from the r this iteration computed but did not keep
+    if (ringed() ? ring.restore_r(it) : xs.restore_r(it)) {
+      set_update(nullptr, OSC_XMODE_XR_SKIPS_X, nullptr, alpha_of(it), xr_p(it), xr_pout(it));
+      update_xr();
     }
   }
-  h.predicted_iters[b.kind] = out.iters;
-  // the last iteration's x update rode in a gated p update that did not run (the solve converged under a speculative
-  // iteration): alpha and p are still that iteration's
-  if (ringed) {  // what the ring still holds for x: with at most K iterations the solve's only x pass
-    ring_pass(ring.final_pass(out.iters), nullptr);
-  } else if (xs.finish_at_end(out.iters)) {
-    finish_x(out.iters);
+
+  CgResult finish(int iters) {
+    h.predicted_iters[b.kind] = iters;
+    // the last iteration's x update rode in a gated p update that did not run (the solve converged under a speculative
+    // iteration): alpha and p are still that iteration's
+    if (ringed()) {  // what the ring still holds for x: with at most K iterations the solve's only x pass
+      ring_pass(ring.final_pass(iters), nullptr);
+    } else if (xs.finish_at_end(iters)) {
+      finish_x(iters);
+    }
+    h.x_ring_k = ring.K;
+    h.x_ring_flushes = ringed() ? ring.flushes : 0;
+    h.x_ring_passes = ringed() ? ring.passes : 0;
+    // The solution is complete once the last residual is out; what may still be queued are the gated-off launches of
+    // the speculative iteration (they return at once and write nothing).  With the polled read-back the stream is left
+    // to drain on its own -- later calls are ordered behind it anyway; the copy + event path keeps its full wait.
+    // (overlap: the same; the second stream is drained by whoever next touches the residual slots it writes -- drain_comm_stream)
+    if (!polled || h.prof_on) sync(h);
+    drop_speculative_samples(h, prof_mark, iters);
+    return CgResult{iters, h.history.empty() ? 0.f : h.history.back(), b.X};
   }
-  h.x_ring_k = ring.K;
-  h.x_ring_flushes = ringed ? ring.flushes : 0;
-  h.x_ring_passes = ringed ? ring.passes : 0;
-  // The solution is complete once the last residual is out; what may still be queued are the gated-off launches of
-  // the speculative iteration (they return at once and write nothing).  With the mapped read-back the stream is left
-  // to drain on its own -- later calls are ordered behind it anyway; the copy + event path keeps its full wait.
-  // (overlap: the same; the second stream is drained by whoever next touches the residual slots it writes -- drain_comm_stream)
-  if (!polled || h.prof_on) sync(h);
-  for (size_t i = prof_mark; i < h.prof_pending.size(); ++i)  // speculative (gated-off) launches are not samples
-    if (h.prof_pending[i].iter > out.iters) h.prof_pending[i].which = -1;
-  return out;
+};
+
+}  // namespace
+
+// cg_solve (solver.py:6-37) on the device; returns once the last residual is out (what may still be queued then touches
+// scratch arrays only, and later calls are ordered behind it by the stream).  Which iteration is enqueued when is
+// host::cg_host_loop's business (host_logic.hpp; the sweeps under tests/host_logic run that same function against a model
+// of the device's gating); CgSolve is what it drives.
+CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, int max_iters, float tol) {
+  if (row_mode(h) && b.ld == h.ld) return run_cg_rows(h, op, b, with_path, max_iters, tol);
+  {
+    CgResult one{};
+    if (run_cg_small(h, op, b, with_path, max_iters, tol, one)) return one;
+  }
+  CgSolve s(h, op, b, with_path, max_iters, tol);
+  s.init();
+  s.plan_ring();
+  h.history.clear();
+  s.prof_mark = h.prof_pending.size();
+  const int iters = host::cg_host_loop(max_iters, s.stop_guess, (double)tol, s);
+  return s.finish(iters);
 }
 
 // Column-sharded runs: every rank owns columns [c0, c1) of an N x ld array.  Make the whole array valid on every
@@ -917,18 +923,8 @@ CgResult run_cg_rows(L& h, const OpParams& op, const CgBuffers& b, bool with_pat
   h.sums.alloc((size_t)2 * b.ld);
   double* s0 = h.sums.p;
   double* s1 = h.sums.p + b.ld;
+  ensure_ctrl(h, (size_t)max_iters + 2);  // (every caller has sized them already, ensure_cg_scratch: nothing grows here)
   HIP_CHECK(hipMemsetAsync(h.res_bits.p, 0, ((size_t)max_iters + 2) * 4, h.stream));
-  if (h.res_host_n < (size_t)max_iters + 2) {
-    if (h.res_host) (void)hipHostFree(h.res_host);
-    h.res_host = nullptr;
-    HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h.res_host), ((size_t)max_iters + 2) * 4, hipHostMallocDefault));
-    h.res_host_n = (size_t)max_iters + 2;
-  }
-  while (h.iter_events.size() < (size_t)max_iters + 2) {
-    hipEvent_t e;
-    HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    h.iter_events.push_back(e);
-  }
   const float* res_dev = reinterpret_cast<const float*>(h.res_bits.p);
   SpmmArgs sa{};
   sa.g = graph_view(h, with_path);
@@ -1026,8 +1022,7 @@ CgResult run_cg_rows(L& h, const OpParams& op, const CgBuffers& b, bool with_pat
   }
   exchange_rows(h, b.X, b.ld);  // every rank leaves with the whole solution
   sync(h);
-  for (size_t i = prof_mark; i < h.prof_pending.size(); ++i)
-    if (h.prof_pending[i].iter > out.iters) h.prof_pending[i].which = -1;
+  drop_speculative_samples(h, prof_mark, out.iters);
   return out;
 }
 

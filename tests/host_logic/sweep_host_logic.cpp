@@ -13,6 +13,7 @@
 #include "../../oscillink_amd/csrc/host_logic.hpp"
 #include "../../oscillink_amd/csrc/knn_plan.hpp"
 #include "../../oscillink_amd/csrc/knn_rowmap.hpp"
+#include "cg_loop_model.hpp"
 
 using namespace osc::host;
 
@@ -576,11 +577,12 @@ static void check_knn_build_plans() {
 }
 
 // ---- CgXSchedule against a model of the device ---------------------------------------------------------------------
-// The host loop of run_cg (osc_api.hip) is replayed here verbatim; the "device" executes the launches in order with the
-// gating rule of the kernels (a gated launch of iteration it runs iff iteration it - 1 did not converge; an ungated
-// one always runs) and tracks which iteration's values p, alpha and r hold.  Checked: every iteration up to the one the
-// solve stopped in has its x update applied exactly once, with its own p and alpha; no other; every kernel that reads
-// r finds the r it expects; the host never launches anything for an iteration it should not.
+// The host loop of run_cg (osc_solve.hip) runs here -- the library's loop, cg_host_loop; the "device" executes the
+// launches in order with the gating rule of the kernels (a gated launch of iteration it runs iff iteration it - 1 did
+// not converge; an ungated one always runs) and tracks which iteration's values p, alpha and r hold.  Checked: every
+// iteration up to the one the solve stopped in has its x update applied exactly once, with its own p and alpha; no
+// other; every kernel that reads r finds the r it expects; the host never launches anything for an iteration it should
+// not.
 static void check_cg_schedule(int max_iters, int stop_guess, int converge_at, bool ungated, bool xdefer, bool last_form) {
   CgXSchedule xs;
   xs.xdefer = xdefer, xs.last_form = last_form, xs.ungated = ungated, xs.stop_guess = stop_guess, xs.max_iters = max_iters;
@@ -616,23 +618,18 @@ static void check_cg_schedule(int max_iters, int stop_guess, int converge_at, bo
     apply_x(it);
     xs.finished(it);
   };
-  int iters = max_iters, enqueued = 1;
-  enqueue_iter(1, false);
-  for (int it = 1; it <= max_iters; ++it) {
-    if (it < max_iters && it != stop_guess && enqueued == it) enqueue_iter(++enqueued, true);
-    else if (xs.finish_before_wait(it)) finish_x(it);
-    if (converged(it)) {
-      iters = it;
-      break;
+  auto idle_before_wait = [&](int it) {
+    if (xs.finish_before_wait(it)) finish_x(it);
+  };
+  auto wait = [&](int it) { return converged(it) ? 0.f : 1.f; };  // (against tol 0.5)
+  auto go_on = [&](int it) {
+    if (xs.restore_r(it)) {
+      CHECK(r_ver == it - 1, "redoing the r update of iteration %d from r of iteration %d", it, r_ver);
+      r_ver = it;
     }
-    if (it < max_iters && enqueued == it) {
-      if (xs.restore_r(it)) {
-        CHECK(r_ver == it - 1, "redoing the r update of iteration %d from r of iteration %d", it, r_ver);
-        r_ver = it;
-      }
-      enqueue_iter(++enqueued, false);
-    }
-  }
+  };
+  auto ops = cg_loop_model(enqueue_iter, idle_before_wait, wait, go_on);
+  const int iters = cg_host_loop(max_iters, stop_guess, 0.5, ops);  // the library's loop
   if (xs.finish_at_end(iters)) finish_x(iters);
   for (int it = 1; it <= max_iters + 1; ++it)
     CHECK(x_applied[(size_t)it] == (it <= iters ? 1 : 0),

@@ -1,12 +1,13 @@
-// Sweep of the direction ring's host logic (oscillink_amd/csrc/host_logic.hpp: plan_x_ring, CgXRing) against a model of the
-// device, built with a plain host compiler by tests/test_x_ring_host.py (once plain, once under
-// -fsanitize=address,undefined).  The host loop of run_cg (osc_solve.hip) is replayed for every (predicted iterations,
-// stopping iteration, max_iters <= 12, K, last-form switch); which iterations are enqueued speculatively follows from the
-// prediction, as in run_cg.  The "device" executes the launches in order with the gating rule of the kernels (a gated
-// launch of iteration it runs iff iteration it - 1 did not converge; an ungated one always runs) and tracks which
-// iteration's direction and alpha each slot holds.  Checked: every real iteration's direction is applied exactly once, in
-// ascending order, with its own alpha, before its slot is overwritten; none behind the stop; a pass holds 1..K
-// directions; the first pass, and only it, starts from x0; every kernel that reads r finds the r it expects.
+// Sweep of the direction ring's host logic (oscillink_amd/csrc/host_logic.hpp: plan_x_ring, CgXRing) against a model of
+// the device, built with a plain host compiler by tests/test_x_ring_host.py (once plain, once under
+// -fsanitize=address,undefined).  The host loop of run_cg (osc_solve.hip) -- the library's loop, cg_host_loop -- runs
+// for every (predicted iterations, stopping iteration, max_iters <= 12, K, last-form switch); which iterations are
+// enqueued speculatively follows from the prediction, as in run_cg.  The "device" executes the launches in order with
+// the gating rule of the kernels (a gated launch of iteration it runs iff iteration it - 1 did not converge; an ungated
+// one always runs) and tracks which iteration's direction and alpha each slot holds.  Checked: every real iteration's
+// direction is applied exactly once, in ascending order, with its own alpha, before its slot is overwritten; none
+// behind the stop; a pass holds 1..K directions; the first pass, and only it, starts from x0; every kernel that reads r
+// finds the r it expects.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -16,6 +17,7 @@
 #include <vector>
 
 #include "../../oscillink_amd/csrc/host_logic.hpp"
+#include "cg_loop_model.hpp"
 
 using namespace osc::host;
 
@@ -61,7 +63,7 @@ static void check_ring(int K, int max_iters, int stop_guess, int converge_at, bo
     }
     x_in_X = true;
   };
-  auto enqueue_iter = [&](int it) {
+  auto enqueue_iter = [&](int it, bool /*speculative*/) {
     if (it > 1) {
       pass(ring.flush_before_p(it), it);
       if (runs(it, true)) {  // p_it = z(r_{it-1}) + beta p_{it-1} into slot it % K
@@ -83,24 +85,17 @@ static void check_ring(int K, int max_iters, int stop_guess, int converge_at, bo
       (void)ring.xr_last(it);  // (the host calls it whether or not the launch runs)
     }
   };
-  int iters = max_iters, enqueued = 1;
-  enqueue_iter(1);
-  for (int it = 1; it <= max_iters; ++it) {
-    if (it < max_iters && it != stop_guess && enqueued == it) enqueue_iter(++enqueued);
-    else pass(ring.pass_before_wait(it), 0);
-    if (converged(it)) {
-      iters = it;
-      break;
+  auto idle_before_wait = [&](int it) { pass(ring.pass_before_wait(it), 0); };
+  auto wait = [&](int it) { return converged(it) ? 0.f : 1.f; };  // (against tol 0.5)
+  auto go_on = [&](int it) {
+    if (ring.restore_r(it)) {
+      CHECK(r_ver == it - 1, "%s: redoing the r update of iteration %d from r of %d", tag(), it, r_ver);
+      CHECK(slot_alpha[(size_t)(it % K)] == it, "%s: redoing the r update of %d with alpha of %d", tag(), it, slot_alpha[(size_t)(it % K)]);
+      r_ver = it;
     }
-    if (it < max_iters && enqueued == it) {
-      if (ring.restore_r(it)) {
-        CHECK(r_ver == it - 1, "%s: redoing the r update of iteration %d from r of %d", tag(), it, r_ver);
-        CHECK(slot_alpha[(size_t)(it % K)] == it, "%s: redoing the r update of %d with alpha of %d", tag(), it, slot_alpha[(size_t)(it % K)]);
-        r_ver = it;
-      }
-      enqueue_iter(++enqueued);
-    }
-  }
+  };
+  auto ops = cg_loop_model(enqueue_iter, idle_before_wait, wait, go_on);
+  const int iters = cg_host_loop(max_iters, stop_guess, 0.5, ops);  // the library's loop
   pass(ring.final_pass(iters), 0);
   for (int it = 1; it <= max_iters + 1; ++it)
     CHECK(applied[(size_t)it] == (it <= iters ? 1 : 0), "%s: direction %d applied %d times (solve stopped in %d)", tag(), it,
