@@ -361,6 +361,37 @@ int osc_corpus_graph(osc_corpus_handle h, const float* psi, const int32_t* cand_
                      float row_cap, int32_t* cand_out, int64_t* rowptr, int32_t* col, float* a, float* w, float* sqrt_deg,
                      int64_t capacity, int64_t* nnz);
 
+/* ---- mutable corpus ------------------------------------------------------------------------
+ * Ids are row positions.  Y / Yn are allocated for `capacity` >= N rows; a bitmap of uint32 words (bit i & 31 of word
+ * i >> 5 for row i, 1 = live, zero bits beyond N) says which rows take part.  A removed row keeps its id (a tombstone) until
+ * osc_corpus_compact.  Everywhere above, K = min(top_k, live rows), a search returns live rows only, cand_in naming a removed
+ * row is OSC_E_INVALID (the message names the query and the id), and a corpus without live rows answers every query call
+ * and osc_corpus_compact with OSC_E_INVALID.  A corpus without tombstones, called without a filter, launches what it
+ * launched before these entry points existed. */
+/* Appends M rows (M x D, row-major) as ids N .. N + M - 1, normalised as osc_corpus_create normalises; *first_id = the first
+ * new id (N for M = 0).  N + M < 2^31.  When N + M passes the capacity, Y / Yn move to max(N + M, capacity * 3 / 2) rows
+ * rounded up to 128; if that allocation fails the corpus is as it was.  Synchronises before it returns. */
+int osc_corpus_append(osc_corpus_handle h, const float* Y, int64_t M, int64_t* first_id);
+/* Tombstones the n rows ids[]: other rows keep their ids, removed ids are not reused.  An id outside [0, N) is OSC_E_INVALID
+ * and nothing changes; an id already removed is ignored.  *newly_removed = how many were live. */
+int osc_corpus_remove(osc_corpus_handle h, const int32_t* ids, int64_t n, int64_t* newly_removed);
+/* Drops the tombstoned rows, keeping the order of the others, and renumbers densely: Y and Yn are gathered (Yn is copied, not
+ * recomputed) into fresh buffers of the live rows rounded up to 128.  new_id_of_old_or_null: N entries, the new id or -1.
+ * *N_new = the new N (= the live rows).  An armed filter is dropped. */
+int osc_corpus_compact(osc_corpus_handle h, int32_t* new_id_of_old_or_null, int64_t* N_new);
+/* rows including tombstones, live rows, rows allocated (any may be NULL) */
+int osc_corpus_rows(osc_corpus_handle h, int64_t* N, int64_t* live, int64_t* capacity);
+/* the live bitmap: ceil(N / 32) words */
+int osc_corpus_get_live(osc_corpus_handle h, uint32_t* words);
+/* Arms a filter for the NEXT osc_corpus_search / _refine* / _gates / _graph call on this handle, which consumes and clears it
+ * whether it succeeds or fails: rows = 0 clears, rows = 1 is one bitmap (the live bitmap's form, words_per_row =
+ * ceil(N / 32)) for every query, otherwise rows must equal that call's Q and query q's bitmap is words[q * words_per_row ..].
+ * A row is eligible iff it is live and its bit is set; the search ranks eligible rows only (cosine descending, ties to the
+ * smaller id).  Every query needs at least K = min(top_k, live rows) eligible rows: otherwise that call returns
+ * OSC_E_INVALID with the first such query and its count in the message, before any device work.  A filter together with
+ * cand_in is OSC_E_INVALID.  A filter of all ones returns what no filter returns, bit for bit. */
+int osc_corpus_filter(osc_corpus_handle h, const uint32_t* words, int32_t rows, int64_t words_per_row);
+
 /* ---- receipts ------------------------------------------------------------------------------- */
 /* deltaH_trace (receipts.py:10-25) on the resident U and U* */
 int osc_deltaH(osc_handle h, double* dH);

@@ -22,6 +22,7 @@ c_f32p = C.POINTER(C.c_float)
 c_i32p = C.POINTER(C.c_int32)
 c_i64p = C.POINTER(C.c_int64)
 c_f64p = C.POINTER(C.c_double)
+c_u32p = C.POINTER(C.c_uint32)
 Handle = C.c_void_p
 
 _i32, _i64, _f32 = C.c_int32, C.c_int64, C.c_float
@@ -110,6 +111,12 @@ SIGNATURES = {
     "osc_corpus_refine_chains": (C.c_int, [*_GATED_REQUEST, *_CHAIN_IN, *_REFINE_OUT_GATED, *_RECEIPT_OUT, *_CHAIN_OUT]),
     "osc_corpus_graph": (C.c_int, [Handle, c_f32p, c_i32p, C.c_int32, C.c_int32, C.c_float, c_i32p, c_i64p, c_i32p, c_f32p,
                                    c_f32p, c_f32p, C.c_int64, c_i64p]),
+    "osc_corpus_append": (C.c_int, [Handle, c_f32p, C.c_int64, c_i64p]),
+    "osc_corpus_remove": (C.c_int, [Handle, c_i32p, C.c_int64, c_i64p]),
+    "osc_corpus_compact": (C.c_int, [Handle, c_i32p, c_i64p]),
+    "osc_corpus_rows": (C.c_int, [Handle, c_i64p, c_i64p, c_i64p]),
+    "osc_corpus_get_live": (C.c_int, [Handle, c_u32p]),
+    "osc_corpus_filter": (C.c_int, [Handle, c_u32p, C.c_int32, C.c_int64]),
     "osc_deltaH": (C.c_int, [Handle, c_f64p]),
     "osc_receipt_components": (C.c_int, [Handle, c_f32p, c_f32p, c_f32p]),
     "osc_null_points": (C.c_int, [Handle, C.c_float, c_i32p, c_i32p, c_f32p, c_f32p, c_i32p]),
@@ -210,6 +217,10 @@ def i32(a: np.ndarray):
 
 def i64(a: np.ndarray):
     return a.ctypes.data_as(c_i64p)
+
+
+def u32(a: np.ndarray):
+    return a.ctypes.data_as(c_u32p)
 
 
 def check(rc: int, handle=None, what: str = "") -> None:

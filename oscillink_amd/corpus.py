@@ -15,6 +15,7 @@ from typing import Any, Optional
 
 import numpy as np
 
+from . import _masks as mk
 from . import _native as nat
 from . import _receipts as rc
 
@@ -68,7 +69,14 @@ class _RefineOut:
 class Corpus:
     """A corpus Y (N x D, finite) resident on the device as Y and its row-normalised copy Yn (osc_create's arithmetic),
     both at a row pitch of D rounded up to 32 floats: 8 N ceil32(D) bytes, no lattice solver arrays.  Per call, queries
-    run in chunks whose scratch stays under 1 GiB (OSC_CORPUS_CHUNK, read at creation, caps the queries per chunk)."""
+    run in chunks whose scratch stays under 1 GiB (OSC_CORPUS_CHUNK, read at creation, caps the queries per chunk).
+
+    The corpus can change: ids are row positions, `append` adds rows at the end, `remove`
+    tombstones rows without moving the others, `compact` drops the tombstones and renumbers.  `N` counts rows including
+    tombstones, `n_live` the others; the very next call sees the change."""
+
+    _n_removed = 0  # tombstones among the N rows (the native handle's N - n_live)
+    _alive = None  # alive()'s array, kept until the next append / remove / compact
 
     def __init__(self, Y: np.ndarray, *, device: Optional[int] = None):
         if not isinstance(Y, np.ndarray) or Y.ndim != 2 or Y.shape[0] < 1 or Y.shape[1] < 1:
@@ -116,6 +124,12 @@ class Corpus:
     def __exit__(self, *exc) -> None:
         self.close()
 
+    def _call_filtered(self, allow: Optional[np.ndarray], name: str, *args) -> None:
+        """_call(name, ...) with `allow` (_allow's words or None) armed as the call's filter: the native call consumes it."""
+        if allow is not None:
+            self._call("osc_corpus_filter", nat.u32(allow), allow.shape[0], allow.shape[1])
+        self._call(name, *args)
+
     def _call(self, name: str, *args) -> None:
         if self._h is None:
             raise ValueError("Corpus is closed")
@@ -137,7 +151,10 @@ class Corpus:
     def _top_k(self, top_k: int) -> int:
         if int(top_k) < 1 or int(top_k) > MAX_TOP_K:
             raise ValueError(f"top_k must be between 1 and {MAX_TOP_K}, got {top_k}")
-        return min(int(top_k), self.N)
+        n_live = self.n_live
+        if n_live == 0:
+            raise ValueError("the corpus has no live rows")
+        return min(int(top_k), n_live)
 
     @staticmethod
     def _knn(kneighbors: int, K: int) -> int:
@@ -157,9 +174,33 @@ class Corpus:
         cand = np.ascontiguousarray(cand, dtype=np.int64)
         if cand.size and (cand.min() < 0 or cand.max() >= self.N):
             raise ValueError(f"candidates: corpus ids must lie in [0, {self.N})")
+        if cand.size and self.n_live < self.N:
+            dead = ~self._alive_mask()[cand]
+            if dead.any():
+                q, j = np.argwhere(dead)[0]
+                raise ValueError(f"candidates: query {int(q)} names removed id {int(cand[q, j])}")
         if cand.size and np.any(np.diff(np.sort(cand, axis=1), axis=1) == 0):
             raise ValueError("candidates: repeated id within a row")
         return cand.astype(np.int32)
+
+    def _allow(self, allow, candidates, Q: int, K: int) -> Optional[np.ndarray]:
+        """The `allow` argument of search / refine_many / diffusion_gates_many as the native filter's words, (1, W) for
+        one filter or (Q, W) for one per query, or None; checked before any device work."""
+        if allow is None:
+            return None
+        if candidates is not None:
+            raise ValueError("allow cannot be combined with candidates")
+        a = np.asarray(allow)
+        if a.dtype != np.bool_:
+            raise ValueError(f"allow must be a bool array, got dtype {a.dtype}")
+        if a.shape != (self.N,) and a.shape != (Q, self.N):
+            raise ValueError(f"allow must have shape ({self.N},) or ({Q}, {self.N}), got {a.shape}")
+        counts = np.atleast_2d(a & self._alive_mask()).sum(axis=1)
+        short = np.flatnonzero(counts < K)
+        if short.size and Q:
+            q = int(short[0])
+            raise ValueError(f"allow: query {q} has {int(counts[q])} eligible rows (live and allowed), fewer than K = {K}")
+        return mk.pack_mask(a)
 
     @staticmethod
     def _gate_settings(beta, gamma, method, max_iters, prefix: str = ""):
@@ -272,17 +313,104 @@ class Corpus:
                           "computed, like the reference's cg path", RuntimeWarning, stacklevel=3)
 
     # ------------------------------------------------------------------ public API
-    def search(self, psis, top_k: int):
-        """Per query the K = min(top_k, N) corpus ids of the largest cosine Yn_i . psi / (|psi| + 1e-12) (fp32 on the
-        device), ties to the smaller id, in that order.  Returns (ids int32 (Q, K), cos float32 (Q, K))."""
+    def search(self, psis, top_k: int, *, allow=None):
+        """Per query the K = min(top_k, n_live) corpus ids of the largest cosine Yn_i . psi / (|psi| + 1e-12) (fp32 on the
+        device), ties to the smaller id, in that order.  Returns (ids int32 (Q, K), cos float32 (Q, K)).
+
+        Removed rows are never returned.  `allow` narrows the search on the device: a bool array (N,) for every query or
+        (Q, N) with one row per query; a row is eligible iff it is live and allowed, and the order within the eligible rows
+        is the same.  Every query needs at least K eligible rows (ValueError naming the first query that has fewer)."""
         P = self._queries(psis)
         K = self._top_k(top_k)
         Q = P.shape[0]
+        words = self._allow(allow, None, Q, K)
         ids = np.zeros((Q, K), dtype=np.int32)
         cos = np.zeros((Q, K), dtype=np.float32)
         if Q:
-            self._call("osc_corpus_search", nat.f32(P), Q, int(top_k), nat.i32(ids), nat.f32(cos))
+            self._call_filtered(words, "osc_corpus_search", nat.f32(P), Q, int(top_k), nat.i32(ids), nat.f32(cos))
         return ids, cos
+
+    # ------------------------------------------------------------------ rows
+    @property
+    def n_live(self) -> int:
+        """Rows that have not been removed."""
+        if self._h is None:
+            raise ValueError("Corpus is closed")
+        return self.N - self._n_removed
+
+    @property
+    def capacity(self) -> int:
+        """Rows the device buffers hold before an append has to move them."""
+        n, live, cap = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._call("osc_corpus_rows", C.byref(n), C.byref(live), C.byref(cap))
+        assert (int(n.value), int(live.value)) == (self.N, self.N - self._n_removed)
+        return int(cap.value)
+
+    def _alive_mask(self) -> np.ndarray:
+        if self._h is None:
+            raise ValueError("Corpus is closed")
+        if self._alive is None and self._n_removed == 0:
+            self._alive = np.ones(self.N, dtype=bool)
+        if self._alive is None:
+            words = np.zeros(mk.words_for(self.N), dtype=np.uint32)
+            self._call("osc_corpus_get_live", nat.u32(words))
+            self._alive = mk.unpack_mask(words, self.N)
+        return self._alive
+
+    def alive(self) -> np.ndarray:
+        """bool (N,): True for the rows that have not been removed."""
+        return self._alive_mask().copy()
+
+    def append(self, Ynew) -> np.ndarray:
+        """Adds the rows of `Ynew` (M, D; finite) as ids N .. N + M - 1 and returns those ids (int64).  The rows are
+        uploaded and normalised on their own; when the device buffers are full they move to max(N + M, 1.5 capacity) rows
+        (rounded up to 128) by a device copy.  If that allocation fails the corpus is as it was."""
+        Yn = np.asarray(Ynew)
+        if Yn.ndim != 2 or Yn.shape[1] != self.D:
+            raise ValueError(f"Ynew must be an (M, {self.D}) array, got shape {Yn.shape}")
+        Yc = np.ascontiguousarray(Yn, dtype=np.float32)
+        if not np.all(np.isfinite(Yc)):
+            raise ValueError("Ynew must be finite")
+        M = Yc.shape[0]
+        if self.N + M >= 2 ** 31:
+            raise ValueError(f"N + M must stay below 2^31, got {self.N} + {M}")
+        first = C.c_int64(0)
+        self._call("osc_corpus_append", nat.f32(Yc) if M else None, M, C.byref(first))
+        if M:
+            self.N += M
+            self._alive = None
+        return np.arange(first.value, first.value + M, dtype=np.int64)
+
+    def remove(self, ids) -> int:
+        """Tombstones the rows `ids`: they leave every later search, the other rows keep their ids, and removed ids are
+        not reused.  An id outside [0, N) raises ValueError before anything changes; an id removed earlier is ignored.
+        Returns the number of rows newly removed."""
+        if self._h is None:
+            raise ValueError("Corpus is closed")
+        r = np.asarray(ids).reshape(-1)
+        if r.size and not np.issubdtype(r.dtype, np.integer):
+            raise ValueError("ids must be integers")
+        r = r.astype(np.int64)
+        if r.size and (r.min() < 0 or r.max() >= self.N):
+            bad = int(r[(r < 0) | (r >= self.N)][0])
+            raise ValueError(f"remove: id {bad} is outside [0, {self.N})")
+        r32 = np.ascontiguousarray(r, dtype=np.int32)
+        gone = C.c_int64(0)
+        self._call("osc_corpus_remove", nat.i32(r32) if r32.size else None, int(r32.size), C.byref(gone))
+        self._n_removed += int(gone.value)
+        self._alive = None
+        return int(gone.value)
+
+    def compact(self) -> np.ndarray:
+        """Drops the removed rows, keeps the order of the others and renumbers them densely (a device gather of Y and Yn
+        into fresh buffers).  Afterwards N == n_live.  Returns new_id_of_old: int64, one entry per old row, -1 for a
+        removed row.  ValueError when every row has been removed."""
+        new_id = mk.compaction_map(self._alive_mask())
+        n_new = C.c_int64(0)
+        self._call("osc_corpus_compact", None, C.byref(n_new))
+        self.N, self._n_removed = int(n_new.value), 0
+        self._alive = None
+        return new_id
 
     def refine_many(self, psis, top_k: int, k: int = 8, alpha: float = 0.5, *, kneighbors: int = 6,
                     row_cap_val: float = 1.0, lamG: float = 1.0, lamC: float = 0.5, lamQ: float = 4.0,
@@ -291,7 +419,7 @@ class Corpus:
                     gate_method: str = "direct", gate_tol: float = 1e-4, gate_max_iters: int = 256,
                     receipts: Optional[str] = None, settle_dt: float = 1.0, settle_max_iters: int = 12,
                     settle_tol: float = 1e-3, chains=None, lamP: float = 0.2, chain_weights=None,
-                    chain_z_th: float = 2.5):
+                    chain_z_th: float = 2.5, allow=None):
         """For each query q, what the reference's loop returns with `cand = search(psis, top_k)[0][q]` (or
         `candidates[q]`):
 
@@ -343,7 +471,14 @@ class Corpus:
         (-1 without a chain) and `chain_weakest_z` float32 (Q,); with `receipts` set and the dict form each query's dict
         gains "chain_receipt" (chain_receipt()'s keys, local ids; None without a chain).  With `receipts=None` and the list
         form the return value stays Q bundles: the chain acts through U* only.  `chains=None` adds no key and calls the
-        entry points called without it."""
+        entry points called without it.
+
+        On a corpus that has changed (`append`, `remove`, `compact`) K = min(top_k, n_live), removed rows are never
+        searched and `candidates` naming one raises ValueError.  `allow` -- a bool array (N,) for every query or (Q, N)
+        with one row per query -- narrows the device search to the rows that are live and allowed, as in `search`; it
+        cannot be combined with `candidates`, and every query needs at least K eligible rows.  Either way the answer is
+        the one a fresh `Corpus` over the eligible rows gives, ids mapped; `allow=None` on a corpus without removed rows is
+        the call as it was."""
         P = self._queries(psis)
         K = self._top_k(top_k)
         knn = self._knn(kneighbors, K)
@@ -355,6 +490,7 @@ class Corpus:
                 raise ValueError(f"{name} must be >= 0")
         Q = P.shape[0]
         cand_in = None if candidates is None else self._candidates(candidates, Q, K)
+        words = self._allow(allow, candidates, Q, K)
         kk = min(max(int(k), 0), K)
         gates_in, gate_set = None, None
         if isinstance(gates, str):
@@ -384,24 +520,25 @@ class Corpus:
                                          mode=0 if not gated else (2 if gates_in is not None else 1), gates_arg=gates_arg,
                                          gate_args=gate_args, solve_args=solve_args, detail=detail,
                                          settle_args=(s_dt, s_max, s_tol), lam=[lamG, lamC, lamQ, 0.0],
-                                         deterministic_k=deterministic_k, as_arrays=as_arrays, chain=chain)
+                                         deterministic_k=deterministic_k, as_arrays=as_arrays, chain=chain, allow=words)
         if Q and not gated:
-            self._call("osc_corpus_refine", nat.f32(P), Q, int(top_k), cand_arg, *solve_args, *o.pointers(False))
+            self._call_filtered(words, "osc_corpus_refine", nat.f32(P), Q, int(top_k), cand_arg, *solve_args,
+                                *o.pointers(False))
         elif Q:
-            self._call("osc_corpus_refine_gated", nat.f32(P), Q, int(top_k), cand_arg, gates_arg, *gate_args, *solve_args,
-                       *o.pointers(True))
+            self._call_filtered(words, "osc_corpus_refine_gated", nat.f32(P), Q, int(top_k), cand_arg, gates_arg, *gate_args,
+                                *solve_args, *o.pointers(True))
             if gates_in is None:
                 self._warn_non_finite(o.g, o.g_iters, o.g_res, "refine_many")
         ids, arrays = o.ids_and_arrays()
         return arrays if as_arrays else o.bundles(ids)
 
     def _refine_receipts(self, P, o, *, top_k, knn, cand_arg, mode, gates_arg, gate_args, solve_args, detail,
-                         settle_args, lam, deterministic_k, as_arrays, chain=None):
+                         settle_args, lam, deterministic_k, as_arrays, chain=None, allow=None):
         """refine_many with receipts or chains, behind its validation: one osc_corpus_refine_receipts call (or, with
         chains, one osc_corpus_refine_chains call), then the arrays or the loop's dicts.  o = the result arrays; mode = the
         entry point's gate_mode; gate_args, solve_args and settle_args (dt, max_iters, tol) = its argument runs of those
         names; detail = None (chains only: no settle, no receipt), 0 or 1; lam = the state signature's lambdas, as given;
-        chain = _chains' block or None."""
+        chain = _chains' block or None; allow = _allow's words or None."""
         from .lattice import OscillinkLattice, __version__
 
         Q, K = o.cand.shape
@@ -425,15 +562,15 @@ class Corpus:
             c_weak_k = np.full(Q, -1, dtype=np.int32)
             c_weak_z = np.zeros(Q, dtype=np.float32)
         if Q and chain is not None:
-            self._call("osc_corpus_refine_chains", nat.f32(P), Q, int(top_k), cand_arg, mode, gates_arg, *gate_args,
-                       *solve_args, *settle_args, -1 if detail is None else detail, RECEIPT_Z_TH, cap_val,
+            self._call_filtered(allow, "osc_corpus_refine_chains", nat.f32(P), Q, int(top_k), cand_arg, mode, gates_arg,
+                       *gate_args, *solve_args, *settle_args, -1 if detail is None else detail, RECEIPT_Z_TH, cap_val,
                        nat.i64(chain["offsets"]), nat.i32(chain["nodes"]),
                        None if chain["weights"] is None else nat.f32(chain["weights"]), chain["lamP"], chain["z_th"],
                        *o.pointers(True), *receipt_out, *[nat.f32(c_edge[t]) for t in range(4)],
                        c_gain.ctypes.data_as(nat.c_f64p), nat.i32(c_verdict), nat.i32(c_weak_k), nat.f32(c_weak_z))
         elif Q:
-            self._call("osc_corpus_refine_receipts", nat.f32(P), Q, int(top_k), cand_arg, mode, gates_arg, *gate_args,
-                       *solve_args, *settle_args, detail, RECEIPT_Z_TH, cap_val, *o.pointers(True), *receipt_out)
+            self._call_filtered(allow, "osc_corpus_refine_receipts", nat.f32(P), Q, int(top_k), cand_arg, mode, gates_arg,
+                       *gate_args, *solve_args, *settle_args, detail, RECEIPT_Z_TH, cap_val, *o.pointers(True), *receipt_out)
         if Q:
             if mode == 1:
                 self._warn_non_finite(g, g_iters, g_res, "refine_many")
@@ -486,7 +623,7 @@ class Corpus:
 
     def diffusion_gates_many(self, psis, top_k: int, *, kneighbors: int = 6, row_cap_val: float = 1.0, beta: float = 1.0,
                              gamma: float = 0.1, method: str = "direct", tol: float = 1e-4, max_iters: int = 256,
-                             clamp: bool = True, candidates=None) -> dict[str, Any]:
+                             clamp: bool = True, candidates=None, allow=None) -> dict[str, Any]:
         """For each query q, with `cand` its candidates (searched, or `candidates[q]`),
 
             compute_diffusion_gates(Y[cand], psis[q], kneighbors=..., row_cap_val=..., beta=..., gamma=..., method=...,
@@ -496,7 +633,8 @@ class Corpus:
         `clamp=False` the result is the solve's h itself, NOT clipped, whereas compute_diffusion_gates (like the reference,
         diffusion.py:123) still clips h to [0, 1]: `np.clip(out["gates"], 0, 1)` gives its answer.  method="direct" is
         served, as in compute_diffusion_gates, by the CG run to 1e-7 max(1, |s|) with at most 2048 iterations.  Non-finite
-        gates come back as computed, with a RuntimeWarning naming the first such query.
+        gates come back as computed, with a RuntimeWarning naming the first such query.  `allow` narrows the search as in
+        `search`.
 
         Returns a dict of `gates` (Q, K) float32 in candidate order, `candidates` (Q, K), `iters` and `res` (Q,)."""
         P = self._queries(psis)
@@ -505,14 +643,16 @@ class Corpus:
         b, g, m, mi = self._gate_settings(beta, gamma, method, max_iters)
         Q = P.shape[0]
         cand_in = None if candidates is None else self._candidates(candidates, Q, K)
+        words = self._allow(allow, candidates, Q, K)
         cand = np.zeros((Q, K), dtype=np.int32)
         gates = np.zeros((Q, K), dtype=np.float32)
         iters = np.zeros(Q, dtype=np.int32)
         res = np.zeros(Q, dtype=np.float32)
         if Q:
-            self._call("osc_corpus_gates", nat.f32(P), Q, int(top_k), None if cand_in is None else nat.i32(cand_in),
-                       int(kneighbors), float(row_cap_val), b, g, m, float(tol), mi, int(bool(clamp)), nat.i32(cand),
-                       nat.f32(gates), nat.i32(iters), nat.f32(res))
+            self._call_filtered(words, "osc_corpus_gates", nat.f32(P), Q, int(top_k),
+                                None if cand_in is None else nat.i32(cand_in), int(kneighbors), float(row_cap_val), b, g, m,
+                                float(tol), mi, int(bool(clamp)), nat.i32(cand), nat.f32(gates), nat.i32(iters),
+                                nat.f32(res))
             self._warn_non_finite(gates, iters, res, "diffusion_gates_many")
         return {"gates": gates, "candidates": cand, "iters": iters, "res": res}
 

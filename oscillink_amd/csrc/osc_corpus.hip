@@ -27,24 +27,42 @@
 #include "osc_internal.hpp"
 #include "knn.hpp"
 #include "corpus_plan.hpp"
+#include "corpus_select.hpp"
+#include "corpus_store.hpp"
 #include "corpus_receipts.hpp"
 #include "corpus_chain.hpp"
 
 #include <cmath>
 #include <vector>
 
+// a filter armed by osc_corpus_filter for the next query call: rows = 0 none, 1 shared, else one row of words per query
+struct CorpusFilter {
+  std::vector<uint32_t> words;
+  int32_t rows = 0;
+  int64_t words_per_row = 0;
+};
+
 struct osc_corpus {
   int device = 0;
   hipStream_t stream = nullptr;
-  int64_t N = 0;
+  int64_t N = 0;        // rows, tombstones included: ids are [0, N)
+  int64_t cap = 0;      // rows allocated in Y / Yn
+  int64_t n_live = 0;
   int32_t D = 0, ldn = 0;
   int32_t chunk_req = osc::host::kCorpusDefaultChunk;  // OSC_CORPUS_CHUNK, read at creation
   osc::DevBuf<float> Y, Yn;
+  std::vector<uint32_t> live;      // corpus_store.hpp's bitmap, store_words(N) words
+  osc::DevBuf<uint32_t> d_live;    // its device copy, brought up to date by the first masked select after a change
+  bool d_live_current = false;
+  CorpusFilter filter;
+  osc::DevBuf<uint32_t> d_filter;  // one chunk's rows of the call's filter
   osc::DevBuf<unsigned char> scratch;
   std::string err;
   ~osc_corpus() {
     Y.release();
     Yn.release();
+    d_live.release();
+    d_filter.release();
     scratch.release();
     if (stream) release_stream(device, stream);
   }
@@ -146,31 +164,6 @@ __global__ __launch_bounds__(256) void k_cq_gemm(const float* __restrict__ Yn, i
 }
 
 // ---- per-query top K: 1024 threads, radix select of the K-th key, then a bitonic sort (k_rm_null_select's pattern) -----
-constexpr int kSelT = host::kCorpusMaxTopK;
-
-__device__ __forceinline__ uint32_t fkey(float v) {  // ascending float order == ascending key order; finite keys are > 0
-  const uint32_t u = v == 0.f ? 0u : __float_as_uint(v);  // (-0 and +0 are one value)
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ int block_scan(bool flag, int* wsum, int* total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const unsigned long long m = __ballot(flag);
-  const int pre = __popcll(m & ((1ull << lane) - 1ull));
-  if (lane == 0) wsum[w] = __popcll(m);
-  __syncthreads();
-  int wpre = 0, tot = 0;
-#pragma unroll
-  for (int t = 0; t < kSelT / 64; ++t) {
-    const int v = wsum[t];
-    wpre += t < w ? v : 0;
-    tot += v;
-  }
-  __syncthreads();
-  *total = tot;
-  return wpre + pre;
-}
-
 __global__ __launch_bounds__(kSelT) void k_cq_select(const float* dots, int64_t N, int32_t K, int32_t* cand, float* ccos) {
   __shared__ uint32_t hist[256];
   __shared__ uint32_t skey[kSelT];
@@ -666,6 +659,14 @@ int corpus_guarded(osc_corpus* h, F&& f) {
   }
 }
 
+// a call that searches or takes candidates: whatever it returns, the filter armed for it is spent
+template <class F>
+int corpus_query(osc_corpus* h, F&& f) {
+  const int rc = corpus_guarded(h, f);
+  if (h) h->filter = CorpusFilter{};
+  return rc;
+}
+
 template <class T>
 T* at(osc_corpus& c, int64_t off) {
   return reinterpret_cast<T*>(c.scratch.p + off);
@@ -696,7 +697,21 @@ struct RefineReq {
   const float* c_w = nullptr;        // per chain edge, at c_eoff, or nullptr (ones)
   const int64_t* c_eoff = nullptr;   // Q + 1 offsets over chain edges
   float lamP = 0.f, c_zth = 2.5f;
+  // the call's filter (osc_corpus_filter), set by set_k_and_filter: rows of store_words(N) words, nullptr = none
+  const uint32_t* allow = nullptr;
+  int64_t allow_stride = 0;  // words from one query's row to the next; 0 = one row for every query
 };
+
+// the device copy of the live bitmap, as of now
+const uint32_t* live_on_device(osc_corpus& c) {
+  const size_t nw = (size_t)host::store_words(c.N);
+  if (c.d_live.n < nw) c.d_live.alloc((size_t)host::store_words(std::max(c.cap, c.N)));
+  if (!c.d_live_current) {
+    HIP_CHECK(hipMemcpyAsync(c.d_live.p, c.live.data(), nw * 4, hipMemcpyHostToDevice, c.stream));
+    c.d_live_current = true;
+  }
+  return c.d_live.p;
+}
 
 // one chunk [q0, q0 + nq): psi upload, candidates, and the requested stages in the order of the list at the top of this
 // file; returns the layout used
@@ -721,7 +736,19 @@ host::CorpusLayout run_chunk(osc_corpus& c, const RefineReq& rq, int32_t q0, int
     float* dots = at<float>(c, L.dots);
     const dim3 grid((unsigned)((c.N + kTM - 1) / kTM), (unsigned)((nq + kTQ - 1) / kTQ));
     hipLaunchKernelGGL(k_cq_gemm, grid, wg, 0, s, c.Yn.p, c.N, ldn, psi, nq, qnorm, dots);
-    hipLaunchKernelGGL(k_cq_select, per_lattice, dim3(kSelT), 0, s, dots, c.N, K, cand, at<float>(c, L.ccos));
+    if (c.n_live == c.N && !rq.allow) {
+      hipLaunchKernelGGL(k_cq_select, per_lattice, dim3(kSelT), 0, s, dots, c.N, K, cand, at<float>(c, L.ccos));
+    } else {  // tombstones or a filter: the chunk's rows of the filter go into a buffer of their own
+      const uint32_t* d_allow = nullptr;
+      if (rq.allow) {
+        const bool shared = rq.allow_stride == 0;
+        const size_t wpr = (size_t)host::store_words(c.N), words = (shared ? 1 : (size_t)nq) * wpr;
+        if (c.d_filter.n < words) c.d_filter.alloc((shared ? 1 : (size_t)cap_nq) * wpr);
+        HIP_CHECK(hipMemcpyAsync(c.d_filter.p, rq.allow + (size_t)q0 * rq.allow_stride, words * 4, hipMemcpyHostToDevice, s));
+        d_allow = c.d_filter.p;
+      }
+      launch_cq_select_masked(dots, c.N, K, live_on_device(c), d_allow, rq.allow_stride, cand, at<float>(c, L.ccos), nq, s);
+    }
   }
   HIP_CHECK(hipGetLastError());
   if (rq.stage == 0) return L;
@@ -830,8 +857,32 @@ void check_queries(const osc_corpus& c, const float* psis, int32_t Q, int32_t to
 }
 
 void check_candidates(const osc_corpus& c, const int32_t* cand, int32_t Q, int32_t K) {
-  for (int64_t i = 0; i < (int64_t)Q * K; ++i)
+  for (int64_t i = 0; i < (int64_t)Q * K; ++i) {
     if (cand[i] < 0 || cand[i] >= c.N) throw Invalid("candidates: corpus id out of range");
+    if (!host::store_get(c.live.data(), cand[i]))
+      throw Invalid("candidates: query " + std::to_string(i / K) + " names removed id " + std::to_string(cand[i]));
+  }
+}
+
+// K of a call, and its filter attached to the request: min(top_k, live rows), of which every query must have K eligible
+// ones (live and allowed).  Before any device work.
+int32_t set_k_and_filter(const osc_corpus& c, RefineReq& rq, int32_t top_k) {
+  if (c.n_live == 0) throw Invalid("the corpus has no live rows");
+  const int32_t K = (int32_t)std::min<int64_t>(top_k, c.n_live);
+  const CorpusFilter& fl = c.filter;
+  if (fl.rows == 0) return K;
+  if (rq.cand_in) throw Invalid("a filter cannot be combined with candidates");
+  if (fl.rows != 1 && fl.rows != rq.Q) throw Invalid("the filter must have 1 row or one row per query");
+  if (fl.words_per_row != host::store_words(c.N)) throw Invalid("the filter was armed for another row count");
+  for (int32_t q = 0; q < (fl.rows == 1 ? std::min(rq.Q, 1) : rq.Q); ++q) {
+    const int64_t n = host::store_count(c.live.data(), fl.words.data() + (size_t)q * fl.words_per_row, c.N);
+    if (n < K)
+      throw Invalid("filter: query " + std::to_string(q) + " has " + std::to_string(n) + " eligible rows, fewer than K = " +
+                    std::to_string(K));
+  }
+  rq.allow = fl.words.data();
+  rq.allow_stride = fl.rows == 1 ? 0 : fl.words_per_row;
+  return K;
 }
 
 int32_t chunk_for(const osc_corpus& c, int32_t K, int32_t knn, int32_t kk, bool receipts = false, int32_t null_slots = 0,
@@ -967,9 +1018,9 @@ void check_request(const osc_corpus& c, const RefineReq& rq) {
   if (rq.kneighbors < 1) throw Invalid("kneighbors must be >= 1");
 }
 
-// K and the list length of the request's lattices, and its candidates checked if given
+// K and the list length of the request's lattices, its filter attached, and its candidates checked if given
 void set_shape(const osc_corpus& c, RefineReq& rq) {
-  rq.K = (int32_t)std::min<int64_t>(rq.top_k, c.N);
+  rq.K = set_k_and_filter(c, rq, rq.top_k);
   rq.knn = rq.K > 1 ? host::corpus_knn(rq.kneighbors, rq.K) : 0;
   if (rq.knn > host::kCorpusMaxKnn) throw Invalid("min(kneighbors, K - 1) must be at most 128");
   if (rq.cand_in) check_candidates(c, rq.cand_in, rq.Q, rq.K);
@@ -1168,7 +1219,9 @@ int osc_corpus_create(const float* Y, int64_t N, int32_t D, int32_t device, osc_
     HIP_CHECK(hipSetDevice(device));
     h->stream = acquire_stream(device);
     alloc_ctx() = AllocCtx{device, h->stream};
-    h->N = N;
+    h->N = h->cap = h->n_live = N;
+    h->live.assign((size_t)host::store_words(N), 0xffffffffu);
+    h->live.back() = host::store_tail_mask(N);
     h->D = D;
     h->ldn = host::corpus_ldn(D);
     if (const char* e = getenv("OSC_CORPUS_CHUNK")) {  // queries per chunk (read once, like read_env's switches)
@@ -1203,7 +1256,8 @@ const char* osc_corpus_last_error(osc_corpus_handle h) { return h ? h->err.c_str
 
 int osc_corpus_info(osc_corpus_handle h, int32_t top_k, int32_t kneighbors, int32_t k, int32_t* chunk, int64_t* bytes) {
   return corpus_guarded(h, [&](osc_corpus& c) {
-    const int32_t K = (int32_t)std::min<int64_t>(std::max(1, top_k), c.N);
+    if (c.n_live == 0) throw Invalid("the corpus has no live rows");
+    const int32_t K = (int32_t)std::min<int64_t>(std::max(1, top_k), c.n_live);
     const int32_t knn = K > 1 ? host::corpus_knn(kneighbors, K) : 0;
     const int32_t kk = std::min(std::max(k, 0), K);
     const int32_t nq = chunk_for(c, K, knn, kk);
@@ -1213,14 +1267,14 @@ int osc_corpus_info(osc_corpus_handle h, int32_t top_k, int32_t kneighbors, int3
 }
 
 int osc_corpus_search(osc_corpus_handle h, const float* psis, int32_t Q, int32_t top_k, int32_t* ids, float* cos) {
-  return corpus_guarded(h, [&](osc_corpus& c) {
+  return corpus_query(h, [&](osc_corpus& c) {
     check_queries(c, psis, Q, top_k);
     if (Q == 0) return;
     if (!ids || !cos) throw Invalid("osc_corpus_search: NULL buffer");
     RefineReq rq{};
     rq.psis = psis;
     rq.Q = Q;
-    rq.K = (int32_t)std::min<int64_t>(top_k, c.N);
+    rq.K = set_k_and_filter(c, rq, top_k);
     rq.stage = 0;
     for_each_chunk(c, rq, [&](const host::CorpusLayout& L, int32_t q0, int32_t n, auto& down) {
       down(ids + (size_t)q0 * rq.K, L.cand, (size_t)n * rq.K * 4);
@@ -1233,7 +1287,7 @@ int osc_corpus_refine(osc_corpus_handle h, const float* psis, int32_t Q, int32_t
                       int32_t kneighbors, float row_cap, float lamG, float lamC, float lamQ, float tol, int32_t max_iters,
                       int32_t k, float alpha, int32_t* cand_out, int32_t* local, float* score, float* align, int32_t* iters,
                       float* res) {
-  return corpus_guarded(h, [&](osc_corpus& c) {
+  return corpus_query(h, [&](osc_corpus& c) {
     refine_body(c, refine_request(psis, Q, top_k, cand_in, kneighbors, row_cap, lamG, lamC, lamQ, tol, max_iters, k, alpha),
                 RefineOut{cand_out, local, score, align, iters, res}, "osc_corpus_refine: NULL buffer");
   });
@@ -1245,7 +1299,7 @@ int osc_corpus_refine_gated(osc_corpus_handle h, const float* psis, int32_t Q, i
                             float tol, int32_t max_iters, int32_t k, float alpha, int32_t* cand_out, float* gates_out,
                             int32_t* local, float* score, float* align, int32_t* iters, float* res, int32_t* gate_iters,
                             float* gate_res) {
-  return corpus_guarded(h, [&](osc_corpus& c) {
+  return corpus_query(h, [&](osc_corpus& c) {
     RefineReq rq = refine_request(psis, Q, top_k, cand_in, kneighbors, row_cap, lamG, lamC, lamQ, tol, max_iters, k, alpha);
     set_gate_request(rq, gates_in ? 2 : 1, gates_in, beta, gamma, method, gate_tol, gate_max_iters);
     refine_body(c, rq, RefineOut{cand_out, local, score, align, iters, res, gates_out, gate_iters, gate_res},
@@ -1264,7 +1318,7 @@ int osc_corpus_refine_receipts(osc_corpus_handle h, const float* psis, int32_t Q
                                int32_t* null_total, int64_t* null_offsets, int32_t* null_i, int32_t* null_j, float* null_z,
                                float* null_r, int64_t null_capacity, int64_t* nnz_out, int64_t* edge_prefix,
                                int32_t* edge_prefix_n, int32_t edge_prefix_cap) {
-  return corpus_guarded(h, [&](osc_corpus& c) {
+  return corpus_query(h, [&](osc_corpus& c) {
     check_gate_mode(gate_mode, gates_in, Q);
     if (detail != 0 && detail != 1) throw Invalid("detail must be 0 (light) or 1 (full)");
     RefineReq rq = refine_request(psis, Q, top_k, cand_in, kneighbors, row_cap, lamG, lamC, lamQ, tol, max_iters, k, alpha);
@@ -1292,7 +1346,7 @@ int osc_corpus_refine_chains(osc_corpus_handle h, const float* psis, int32_t Q, 
                              int32_t* edge_prefix_n, int32_t edge_prefix_cap, float* chain_z_struct, float* chain_z_path,
                              float* chain_r_struct, float* chain_r_path, double* chain_gain, int32_t* chain_verdict,
                              int32_t* chain_weakest_k, float* chain_weakest_z) {
-  return corpus_guarded(h, [&](osc_corpus& c) {
+  return corpus_query(h, [&](osc_corpus& c) {
     check_gate_mode(gate_mode, gates_in, Q);
     if (detail < -1 || detail > 1) throw Invalid("detail must be -1 (no receipts), 0 (light) or 1 (full)");
     RefineReq rq = refine_request(psis, Q, top_k, cand_in, kneighbors, row_cap, lamG, lamC, lamQ, tol, max_iters, k, alpha);
@@ -1317,7 +1371,7 @@ int osc_corpus_refine_chains(osc_corpus_handle h, const float* psis, int32_t Q, 
 int osc_corpus_gates(osc_corpus_handle h, const float* psis, int32_t Q, int32_t top_k, const int32_t* cand_in,
                      int32_t kneighbors, float row_cap, float beta, float gamma, int32_t method, float tol,
                      int32_t max_iters, int32_t clamp, int32_t* cand_out, float* gates_out, int32_t* iters, float* res) {
-  return corpus_guarded(h, [&](osc_corpus& c) {
+  return corpus_query(h, [&](osc_corpus& c) {
     RefineReq rq = lattice_request(psis, Q, top_k, kneighbors, cand_in);
     check_request(c, rq);
     set_gate_request(rq, 1, nullptr, beta, gamma, method, tol, max_iters);
@@ -1339,7 +1393,7 @@ int osc_corpus_gates(osc_corpus_handle h, const float* psis, int32_t Q, int32_t 
 int osc_corpus_graph(osc_corpus_handle h, const float* psi, const int32_t* cand_in, int32_t top_k, int32_t kneighbors,
                      float row_cap, int32_t* cand_out, int64_t* rowptr, int32_t* col, float* a, float* w, float* sqrt_deg,
                      int64_t capacity, int64_t* nnz) {
-  return corpus_guarded(h, [&](osc_corpus& c) {
+  return corpus_query(h, [&](osc_corpus& c) {
     RefineReq rq = lattice_request(psi, 1, top_k, kneighbors, cand_in);
     check_request(c, rq);
     set_shape(c, rq);
@@ -1370,6 +1424,117 @@ int osc_corpus_graph(osc_corpus_handle h, const float* psi, const int32_t* cand_
       rowptr[i + 1] = n;
     }
     *nnz = n;
+  });
+}
+
+int osc_corpus_rows(osc_corpus_handle h, int64_t* N, int64_t* live, int64_t* capacity) {
+  return corpus_guarded(h, [&](osc_corpus& c) {
+    if (N) *N = c.N;
+    if (live) *live = c.n_live;
+    if (capacity) *capacity = c.cap;
+  });
+}
+
+int osc_corpus_get_live(osc_corpus_handle h, uint32_t* words) {
+  return corpus_guarded(h, [&](osc_corpus& c) {
+    if (!words) throw Invalid("osc_corpus_get_live: NULL buffer");
+    std::copy(c.live.begin(), c.live.end(), words);
+  });
+}
+
+int osc_corpus_append(osc_corpus_handle h, const float* Y, int64_t M, int64_t* first_id) {
+  return corpus_guarded(h, [&](osc_corpus& c) {
+    if (M < 0 || (M > 0 && !Y)) throw Invalid("osc_corpus_append: need M >= 0 and Y != NULL");
+    if (M > host::kCorpusMaxRows - c.N) throw Invalid("osc_corpus_append: N + M must stay below 2^31");
+    if (first_id) *first_id = c.N;
+    if (M == 0) return;
+    const int64_t N1 = c.N + M;
+    const size_t ldn = (size_t)c.ldn;
+    std::vector<uint32_t> live = c.live;  // everything that can fail comes before the handle changes
+    live.resize((size_t)host::store_words(N1), 0u);
+    for (int64_t i = c.N; i < N1; ++i) host::store_set(live.data(), i);
+    if (N1 > c.cap) {  // grow: new buffers first, then copy, swap, and the old ones go once the stream has drained
+      const int64_t cap1 = host::store_capacity(c.cap, N1);
+      DevBuf<float> Y1, Yn1;
+      Y1.alloc((size_t)cap1 * ldn);
+      Yn1.alloc((size_t)cap1 * ldn);
+      HIP_CHECK(hipMemcpyAsync(Y1.p, c.Y.p, (size_t)c.N * ldn * 4, hipMemcpyDeviceToDevice, c.stream));
+      HIP_CHECK(hipMemcpyAsync(Yn1.p, c.Yn.p, (size_t)c.N * ldn * 4, hipMemcpyDeviceToDevice, c.stream));
+      c.Y.swap(Y1);
+      c.Yn.swap(Yn1);
+      c.cap = cap1;
+    }  // (Y1 / Yn1 release here: pool_free waits for the stream)
+    float* y = c.Y.p + (size_t)c.N * ldn;
+    HIP_CHECK(hipMemsetAsync(y, 0, (size_t)M * ldn * 4, c.stream));  // the pitch padding: the GEMM reads it
+    HIP_CHECK(hipMemcpy2DAsync(y, ldn * 4, Y, (size_t)c.D * 4, (size_t)c.D * 4, (size_t)M, hipMemcpyHostToDevice, c.stream));
+    launch_normalize_rows(y, c.ldn, c.Yn.p + (size_t)c.N * ldn, c.ldn, M, c.D, c.stream);
+    HIP_CHECK(hipStreamSynchronize(c.stream));
+    c.live.swap(live);
+    c.d_live_current = false;
+    c.n_live += M;
+    c.N = N1;
+  });
+}
+
+int osc_corpus_remove(osc_corpus_handle h, const int32_t* ids, int64_t n, int64_t* newly_removed) {
+  return corpus_guarded(h, [&](osc_corpus& c) {
+    if (n < 0 || (n > 0 && !ids)) throw Invalid("osc_corpus_remove: need n >= 0 and ids != NULL");
+    for (int64_t t = 0; t < n; ++t)
+      if (ids[t] < 0 || ids[t] >= c.N)
+        throw Invalid("osc_corpus_remove: id " + std::to_string(ids[t]) + " is outside [0, " + std::to_string(c.N) + ")");
+    int64_t gone = 0;
+    for (int64_t t = 0; t < n; ++t)
+      if (host::store_get(c.live.data(), ids[t])) {
+        host::store_clear(c.live.data(), ids[t]);
+        ++gone;
+      }
+    c.n_live -= gone;
+    if (gone) c.d_live_current = false;
+    if (newly_removed) *newly_removed = gone;
+  });
+}
+
+int osc_corpus_compact(osc_corpus_handle h, int32_t* new_id_of_old_or_null, int64_t* N_new) {
+  return corpus_guarded(h, [&](osc_corpus& c) {
+    if (c.n_live == 0) throw Invalid("the corpus has no live rows");
+    std::vector<int32_t> kept;
+    const int64_t n = host::store_compact_map(c.live.data(), c.N, new_id_of_old_or_null, kept);
+    if (N_new) *N_new = n;
+    if (n == c.N) return;  // no tombstone: the rows stay where they are
+    const size_t ldn = (size_t)c.ldn;
+    const int64_t cap1 = host::store_capacity(0, n);
+    std::vector<uint32_t> live((size_t)host::store_words(n), 0xffffffffu);
+    live.back() = host::store_tail_mask(n);
+    {
+      DevBuf<float> Y1, Yn1;
+      DevBuf<int32_t> d_kept;
+      Y1.alloc((size_t)cap1 * ldn);
+      Yn1.alloc((size_t)cap1 * ldn);
+      d_kept.alloc((size_t)n);
+      HIP_CHECK(hipMemcpyAsync(d_kept.p, kept.data(), (size_t)n * 4, hipMemcpyHostToDevice, c.stream));
+      launch_cq_compact(c.Y.p, c.Yn.p, c.ldn, d_kept.p, n, Y1.p, Yn1.p, c.stream);
+      HIP_CHECK(hipStreamSynchronize(c.stream));
+      c.Y.swap(Y1);
+      c.Yn.swap(Yn1);
+    }
+    c.cap = cap1;
+    c.live.swap(live);
+    c.d_live_current = false;
+    c.N = c.n_live = n;
+    c.filter = CorpusFilter{};  // (armed for ids that no longer exist)
+  });
+}
+
+int osc_corpus_filter(osc_corpus_handle h, const uint32_t* words, int32_t rows, int64_t words_per_row) {
+  return corpus_guarded(h, [&](osc_corpus& c) {
+    c.filter = CorpusFilter{};
+    if (rows == 0) return;
+    if (rows < 0 || !words) throw Invalid("osc_corpus_filter: need rows >= 0 and words != NULL");
+    if (words_per_row != host::store_words(c.N))
+      throw Invalid("osc_corpus_filter: words_per_row must be ceil(N / 32) = " + std::to_string(host::store_words(c.N)));
+    c.filter.words.assign(words, words + (size_t)rows * words_per_row);
+    c.filter.rows = rows;
+    c.filter.words_per_row = words_per_row;
   });
 }
 
