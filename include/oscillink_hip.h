@@ -129,6 +129,14 @@ int osc_apply_info(osc_handle h, int32_t* src_blocks, int64_t* blocked_applies);
  * handle holds for the ring (measurement aid) */
 int osc_x_ring_info(osc_handle h, int32_t* slots, int64_t* flushes, int64_t* passes, int64_t* bytes);
 
+/* the streamed first apply of anchor starts (a solve that starts from the anchors under uniform gates, without a chain
+ * prior, on the blocked plan: from the lattice's second such solve on, the cached INIT pass also emits iteration 1's A p from
+ * the anchors' second row sums W (W Y) and W 1, and that iteration's gathering matvec is not launched; OSC_ANCHOR_AP = 0 off /
+ * 1 wherever the cached INIT pass runs, unset: lattices of at least 96000 rows): streamed_first_applies = such solves since
+ * creation, bytes = device memory held for the two arrays (0: not built or dropped), last_solve = whether the last
+ * general-path solve took the route, builds = times the arrays were formed (measurement aid) */
+int osc_anchor_ap_info(osc_handle h, int64_t* streamed_first_applies, int64_t* bytes, int32_t* last_solve, int64_t* builds);
+
 /* the block-major copy of the graph the blocked matvec walks, built for `nb` source blocks (test / diagnostic aid; no
  * reference counterpart): slot_col / slot_w [nb][N][4] = {neighbour row, W_ij} per (source block, row, slot), unused slots
  * {first row of the block, 0}; rows whose edges exceed 4 nb slots list the rest in over_col / over_w[over_first[i] ..

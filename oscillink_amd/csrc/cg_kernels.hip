@@ -696,14 +696,23 @@ __global__ __launch_bounds__((CW + 1) * 64) __attribute__((amdgpu_waves_per_eu(W
 __device__ __forceinline__ float4 ld4_stream_at(const float* base, uint32_t byte_off) {
   return ld4_stream(reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off));
 }
-template <int CW>
-__global__ __launch_bounds__((CW + 1) * 64) void k_init_cached(const BlkArgs a, const BlkInit ii) {
+// AP (BlkInitAp, the anchor start under uniform gates): the pass also emits iteration 1's operator output.  The first
+// direction is p1 = z0 = m (qb psi + u Y + cW WY) with per-row scalars m = 1 / Md, qb = rbB b, u = rbU + rbY - cs, so
+// (W p1)_i = m (qb s_i psi + u WY_i + cW WWY_i) with s = W 1 and WWY = W (W Y), both cached (L::Wsum, L::WWs), and
+// A p1 = cs z0 - cW W p1 is streamed here instead of gathered: one more row read (WWY, row-major), one more row written
+// (A p1, row-major), the column sums of p1 . A p1 into ap.part beside those of r . z.  r, z, the x0 copy and the r . z sums
+// are the other form's to the bit; the new products and sums are spelled out so that no call site contracts them its own way.
+template <int CW, bool AP>
+__device__ __forceinline__ void init_cached_body(const BlkArgs& a, const BlkInit& ii, const BlkInitAp& ap) {
   constexpr int NT = (CW + 1) * 64, EC = 4;
   __shared__ __attribute__((aligned(16))) float red[CW + 1][32];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int sub = lane >> 3, lr = lane & 7;
   const int32_t ld = a.ld;
-  for (int c = a.c0 + threadIdx.x; c < a.c1; c += NT) a.part[(size_t)blockIdx.x * ld + c] = 0.f;
+  for (int c = a.c0 + threadIdx.x; c < a.c1; c += NT) {
+    a.part[(size_t)blockIdx.x * ld + c] = 0.f;
+    if constexpr (AP) ap.part[(size_t)blockIdx.x * ld + c] = 0.f;
+  }
   if ((int)(blockIdx.x >> 3) >= a.xs) return;
   const BlkWork wk = blk_work<CW>(a);
   const uint32_t lr16 = (uint32_t)lr * 16u, ldb = (uint32_t)ld * 4u;
@@ -711,7 +720,7 @@ __global__ __launch_bounds__((CW + 1) * 64) void k_init_cached(const BlkArgs a, 
   const int row_first = wk.rlo + ((wk.wgx * CW + wave) << 3) + sub;
   for (int q = 0; q < wk.nslab; ++q) {
     const int sc0 = a.c0 + (wk.xgrp + q * wk.xgroups) * 32;
-    float4 dot = f4(0.f);
+    float4 dot = f4(0.f), dot_ap = f4(0.f);
     if (wave < CW) {
       const bool cok = sc0 + lr * 4 < a.c1;
       const size_t slab = (size_t)(sc0 >> 5) * (size_t)a.N * 32;
@@ -721,22 +730,30 @@ __global__ __launch_bounds__((CW + 1) * 64) void k_init_cached(const BlkArgs a, 
       const uint32_t cb = (uint32_t)(sc0 + lr * 4) * 4u;
       const float4 psi4 = cok ? ld4(ii.psi + sc0 + lr * 4) : f4(0.f);
       float4 xs[2][EC], ws[2][EC];
+      float4 vs[2][AP ? EC : 1];  // (AP: the rows of W W Y and the rows' weight sums)
+      float ss[2][AP ? EC : 1];
       float bv[2][EC];
       // No test around the loads: a lane without a row (past the part's rows, or a column past c1) reads the part's last row,
       // resp. the slab's first columns, and consume() drops what it got.  With the loads in straight-line code the compiler's
       // waits are counted ones and batch k + 1 stays in flight while batch k is consumed; under a test every wait is for all.
       const uint32_t lrc = cok ? lr16 : 0u;
+      const uint32_t cbc = cok ? cb : (uint32_t)sc0 * 4u;
       const int row_last = max(wk.rhi - 1, 0);
-      auto fetch = [&](int k, float4 (&x)[EC], float4 (&w)[EC], float (&bb)[EC]) {
+      auto fetch = [&](int k, float4 (&x)[EC], float4 (&w)[EC], float (&bb)[EC], float4 (&v)[AP ? EC : 1], float (&sm)[AP ? EC : 1]) {
 #pragma unroll
         for (int i = 0; i < EC; ++i) {  // (byte offsets fit 32 bits: launch_init_cached checks as launch_apply_blocked does)
           const uint32_t row = (uint32_t)min(row_first + (k * EC + i) * wk.W8, row_last);
           x[i] = ld4_stream_at(xbase, row * 128u + lrc);
           w[i] = ld4_stream_at(wybase, row * 128u + lrc);
           bb[i] = ld1_at(a.B, row * 4u);
+          if constexpr (AP) {
+            v[i] = ld4_stream_at(ap.WW, row * ldb + cbc);
+            sm[i] = ld1_at(ap.wsum, row * 4u);
+          }
         }
       };
-      auto consume = [&](int k, const float4 (&x)[EC], const float4 (&w)[EC], const float (&bb)[EC]) {
+      auto consume = [&](int k, const float4 (&x)[EC], const float4 (&w)[EC], const float (&bb)[EC], const float4 (&v)[AP ? EC : 1],
+                         const float (&sm)[AP ? EC : 1]) {
 #pragma unroll
         for (int i = 0; i < EC; ++i) {
           const int g = k * EC + i, row = row_first + g * wk.W8;
@@ -747,26 +764,59 @@ __global__ __launch_bounds__((CW + 1) * 64) void k_init_cached(const BlkArgs a, 
           if (ii.Xcopy != nullptr) st4_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(ii.Xcopy) + ((uint32_t)row * ldb + cb)), x[i]);
           st4(reinterpret_cast<float*>(reinterpret_cast<char*>(zbase) + ((uint32_t)row * 128u + lr16)), z);
           dot = mulacc4(r, z, dot);
+          if constexpr (AP) {
+            const float cs = fmaf(a.cs_B, bb[i], a.cs_const);  // (blk_init_row's scalars)
+            const float invMd = 1.f / (fmaf(ii.md_B, bb[i], ii.md_const) + 1e-12f);
+            const float u = __fsub_rn(__fadd_rn(ii.rbU, ii.rbY), cs);
+            const float qs = __fmul_rn(__fmul_rn(ii.rbB, bb[i]), sm[i]);
+            auto one = [&](float zv, float wyv, float wwv, float pv) {
+              const float wz = __fmul_rn(invMd, fmaf(a.cW, wwv, fmaf(u, wyv, __fmul_rn(qs, pv))));  // (W z0)_i
+              return fmaf(cs, zv, -__fmul_rn(a.cW, wz));
+            };
+            const float4 o = make_float4(one(z.x, w[i].x, v[i].x, psi4.x), one(z.y, w[i].y, v[i].y, psi4.y),
+                                         one(z.z, w[i].z, v[i].z, psi4.z), one(z.w, w[i].w, v[i].w, psi4.w));
+            st4_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(ap.AP) + ((uint32_t)row * ldb + cb)), o);
+            dot_ap = mulacc4(z, o, dot_ap);
+          }
         }
       };
-      fetch(0, xs[0], ws[0], bv[0]);
+      fetch(0, xs[0], ws[0], bv[0], vs[0], ss[0]);
       int k = 0;
       for (; k + 2 < nbatch; k += 2) {  // two batches per trip (the buffers keep their registers), no test around a fetch
-        fetch(k + 1, xs[1], ws[1], bv[1]);
-        consume(k, xs[0], ws[0], bv[0]);
-        fetch(k + 2, xs[0], ws[0], bv[0]);
-        consume(k + 1, xs[1], ws[1], bv[1]);
+        fetch(k + 1, xs[1], ws[1], bv[1], vs[1], ss[1]);
+        consume(k, xs[0], ws[0], bv[0], vs[0], ss[0]);
+        fetch(k + 2, xs[0], ws[0], bv[0], vs[0], ss[0]);
+        consume(k + 1, xs[1], ws[1], bv[1], vs[1], ss[1]);
       }
       if (k + 1 < nbatch) {  // the last one or two batches (batch k is in xs[0])
-        fetch(k + 1, xs[1], ws[1], bv[1]);
-        consume(k, xs[0], ws[0], bv[0]);
-        consume(k + 1, xs[1], ws[1], bv[1]);
+        fetch(k + 1, xs[1], ws[1], bv[1], vs[1], ss[1]);
+        consume(k, xs[0], ws[0], bv[0], vs[0], ss[0]);
+        consume(k + 1, xs[1], ws[1], bv[1], vs[1], ss[1]);
       } else {
-        consume(k, xs[0], ws[0], bv[0]);
+        consume(k, xs[0], ws[0], bv[0], vs[0], ss[0]);
       }
     }
     blk_fold<CW + 1>(dot, red, a.part, ld, sc0, min(a.c1, sc0 + 32), wave, lane);
+    if constexpr (AP) blk_fold<CW + 1>(dot_ap, red, ap.part, ld, sc0, min(a.c1, sc0 + 32), wave, lane);
   }
+}
+template <int CW>
+__global__ __launch_bounds__((CW + 1) * 64) void k_init_cached(const BlkArgs a, const BlkInit ii) {
+  init_cached_body<CW, false>(a, ii, BlkInitAp{});
+}
+template <int CW>
+__global__ __launch_bounds__((CW + 1) * 64) void k_init_cached_ap(const BlkArgs a, const BlkInit ii, const BlkInitAp ap) {
+  init_cached_body<CW, true>(a, ii, ap);
+}
+
+// s_i = sum_j W_ij over the ELL row, in stored order: one thread per row (BlkInitAp::wsum)
+__global__ __launch_bounds__(256) void k_row_weight_sums(const float* w, const int32_t* deg, int32_t width, int32_t N, float* out) {
+  const int row = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (row >= N) return;
+  float s = 0.f;
+  const int d = min(deg[row], width);
+  for (int e = 0; e < d; ++e) s = __fadd_rn(s, w[(size_t)row * width + e]);
+  out[row] = s;
 }
 
 // chain prior for k_apply_blocked (ChainFixArgs): one wave per (64 columns, chunk of path rows), one thread per column
@@ -1376,13 +1426,27 @@ static void blocked_args_check(const BlkArgs& a, int grid, int variant) {
 }
 
 // the cached INIT pass in the geometry of kernel shape `variant` (the shape fixes the gathering waves per workgroup)
-void launch_init_cached(const BlkArgs& a, int grid, hipStream_t s, const BlkInit& init, int variant) {
+void launch_init_cached(const BlkArgs& a, int grid, hipStream_t s, const BlkInit& init, int variant, const BlkInitAp* ap) {
   blocked_args_check(a, grid, variant);
   if (!init.R || !init.Z || !init.psi || !init.WY || init.Y != nullptr || init.Z == a.X || init.Z == init.WY)
     throw std::runtime_error("cached INIT pass: bad arguments");
+  if (ap != nullptr) {
+    if (!ap->WW || !ap->wsum || !ap->AP || !ap->part || ap->part == a.part || ap->AP == init.R || ap->AP == init.Z || ap->AP == init.Xcopy ||
+        ap->AP == ap->WW)
+      throw std::runtime_error("cached INIT pass: bad first-apply arguments");
+#define CALL(G, W, P, E) hipLaunchKernelGGL((k_init_cached_ap<W>), dim3(grid), dim3((W + 1) * 64), 0, s, a, init, *ap)
+    OSC_BLK_SHAPE_SWITCH(variant, CALL);
+#undef CALL
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
 #define CALL(G, W, P, E) hipLaunchKernelGGL((k_init_cached<W>), dim3(grid), dim3((W + 1) * 64), 0, s, a, init)
   OSC_BLK_SHAPE_SWITCH(variant, CALL);
 #undef CALL
+  HIP_CHECK(hipGetLastError());
+}
+void launch_row_weight_sums(const float* w, const int32_t* deg, int32_t width, int32_t N, float* out, hipStream_t s) {
+  hipLaunchKernelGGL(k_row_weight_sums, dim3((N + 255) / 256), dim3(256), 0, s, w, deg, width, N, out);
   HIP_CHECK(hipGetLastError());
 }
 

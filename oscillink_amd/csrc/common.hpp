@@ -136,6 +136,15 @@ struct BlkInit {
   float* WY;
 };
 
+// k_init_cached in the form that also emits iteration 1's operator output A p1 (p1 = z0) of an anchor start under uniform
+// gates, from the anchors' cached second row sums (L::WWs, L::Wsum): see the kernel
+struct BlkInitAp {
+  const float* WW;    // W (W Y), row-major with pitch ld
+  const float* wsum;  // [N] s = W 1
+  float* AP;          // A p1 out, row-major
+  float* part;        // [grid][ld] column partial sums of p1 . A p1
+};
+
 enum SpmmMode { SPMM_AP = 0, SPMM_INIT = 1, SPMM_DOT = 2 };
 
 struct SpmmArgs {
@@ -289,7 +298,9 @@ void launch_chain_fix(const ChainFixArgs& a, hipStream_t s);
 void launch_apply_blocked(const BlkArgs& a, int grid, hipStream_t s, const BlkInit* init = nullptr, int variant = 0,
                           bool store_wy = false);
 // the same INIT pass with the row sums read from init.WY instead of gathered (k_init_cached): same results to the bit
-void launch_init_cached(const BlkArgs& a, int grid, hipStream_t s, const BlkInit& init, int variant);
+// ap: the form that also streams iteration 1's A p1 and its p . Ap sums (BlkInitAp)
+void launch_init_cached(const BlkArgs& a, int grid, hipStream_t s, const BlkInit& init, int variant, const BlkInitAp* ap = nullptr);
+void launch_row_weight_sums(const float* w, const int32_t* deg, int32_t width, int32_t N, float* out, hipStream_t s);
 int blocked_resident_per_cu(int variant);  // workgroups per CU a kernel shape (kBlkShapes) gets resident
 void launch_spmm(int mode, const SpmmArgs& a, int grid, hipStream_t s);
 void launch_update_xr(const UpdateArgs& a, int grid, hipStream_t s);

@@ -59,6 +59,7 @@ struct Derived {
   int blk_nb = 0;  // blocks of the copy held (0 = none)
   bool ys = false;
   int wy_nb = 0;  // block count the sums were formed with (0 = none held)
+  int wwy_nb = 0;  // WWs / Wsum (the second row sums W.(W.Y) and W.1, built from WYs): same validity, dropped with anchor_wy
   bool ustar = false;
   uint64_t epoch = 1;  // what an epoch_keyed cache was built for (its own 0 = never built)
 };
@@ -68,7 +69,7 @@ inline void drop(Derived& d, Cache c) {
     case Cache::ell_t: d.ell_t = false; break;
     case Cache::blocked_copy: d.blk_nb = 0; break;
     case Cache::anchor_slab: d.ys = false; break;
-    case Cache::anchor_wy: d.wy_nb = 0; break;
+    case Cache::anchor_wy: d.wy_nb = d.wwy_nb = 0; break;
     case Cache::ustar: d.ustar = false; break;
     case Cache::epoch_keyed: ++d.epoch; break;
     case Cache::count: break;

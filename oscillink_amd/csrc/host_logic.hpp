@@ -12,12 +12,15 @@
 //   CgXSchedule                       : which launch of a CG solve carries which iteration's x update (run_cg)
 //   plan_x_ring / CgXRing             : how many search directions a solve keeps, and when a pass applies them to x (swept by
 //                                       tests/host_logic/sweep_x_ring.cpp)
+//   gates_uniform / anchor_ap_route / anchor_ap_fits : whether an anchor start streams iteration 1's A p from the cached
+//                                       second row sums (swept by tests/host_logic/sweep_anchor_ap.cpp)
 //   cg_host_loop                      : the host loop of a CG solve -- which iteration is enqueued when (run_cg in
 //                                       osc_solve.hip and both sweeps run this one function)
 #pragma once
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <stdexcept>
 #include <utility>
 #include <vector>
@@ -551,6 +554,32 @@ struct CgXSchedule {
   bool finish_at_end(int iters) const { return xdefer && x_rides_gated == iters; }
   void finished(int it) { x_done = it, x_rides_gated = 0; }  // after the x update of `it` was launched on its own
 };
+
+// ---- the streamed first apply of an anchor start (run_cg: CgSolve::init_fused) -------------------------------------------
+// Under uniform gates iteration 1's A p1 is a per-row scalar combination of psi, W Y and W W Y (cg_kernels.hip:
+// k_init_cached_ap), so the cached INIT pass can emit it and the iteration's gathering matvec is not launched.
+// gates_uniform: the gates a query hands over are all the same float (any value: b is then just another scalar).
+inline bool gates_uniform(const float* gates, int64_t n) {
+  for (int64_t i = 1; i < n; ++i)
+    if (std::memcmp(gates + i, gates, sizeof(float)) != 0) return false;
+  return true;
+}
+// Rows from which plan_apply picks the wide kernel shapes on its own: where auto mode serves (smaller lattices keep the
+// gathered first apply until they have a measurement of their own).
+constexpr int64_t kAnchorApAutoRows = 96000;
+struct AnchorApInputs {
+  int mode = -1;               // OSC_ANCHOR_AP: 0 off, 1 wherever the cached INIT runs, < 0 by the lattice's rows
+  int64_t N = 0;
+  bool cached_init = false;    // the cached INIT pass would run (the anchors' row sums are held for this graph copy)
+  bool gates_uniform = false;  // ... and are the handle's own gates
+  bool chain_rows = false;     // a chain prior's rows take part in the operator
+};
+inline bool anchor_ap_route(const AnchorApInputs& in) {
+  if (in.mode == 0 || !in.cached_init || !in.gates_uniform || in.chain_rows) return false;
+  return in.mode > 0 || in.N >= kAnchorApAutoRows;
+}
+// the memory rule of the direction ring: the arrays are only taken from a quarter of what is free
+inline bool anchor_ap_fits(int64_t bytes, int64_t free_bytes) { return bytes >= 0 && bytes <= free_bytes / 4; }
 
 // ---- the ring of kept search directions (run_cg) ----------------------------------------------------------------------
 // x is an output of the recurrence only: x = x0 + sum alpha_it p_it.  With the last K directions (and their alpha vectors)

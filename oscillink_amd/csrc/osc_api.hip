@@ -34,6 +34,7 @@ void read_env_solver(L& h) {
   if (num("OSC_SMALL_PATH", v)) h.small_path = v != 0;
   if (num("OSC_ANCHOR_SLAB", v)) h.anchor_slab = v != 0;
   if (num("OSC_ANCHOR_WY", v)) h.anchor_wy = v != 0;  // (needs the anchors' image: OSC_ANCHOR_SLAB=0 switches it off too, run_cg)
+  if (num("OSC_ANCHOR_AP", v)) h.anchor_ap = v != 0 ? 1 : 0;
   if (num("OSC_RECEIPT_PAIR", v)) h.receipt_pair = v != 0;
   if (const char* e = getenv("OSC_SHARD")) h.shard_mode = !strcmp(e, "row") ? 1 : 0;
   if (num("OSC_ROW_FAKE_SHARDS", v)) h.fake_row_shards = std::max(0, v);
@@ -328,6 +329,15 @@ int osc_x_ring_info(osc_handle h, int32_t* slots, int64_t* flushes, int64_t* pas
   });
 }
 
+int osc_anchor_ap_info(osc_handle h, int64_t* streamed_first_applies, int64_t* bytes, int32_t* last_solve, int64_t* builds) {
+  return guarded(h, [&](L& l) {
+    if (streamed_first_applies) *streamed_first_applies = l.streamed_first_applies;
+    if (bytes) *bytes = l.derived.wwy_nb > 0 ? ((int64_t)l.WWs.n + (int64_t)l.Wsum.n) * 4 : 0;
+    if (last_solve) *last_solve = l.anchor_ap_last ? 1 : 0;
+    if (builds) *builds = l.anchor_ap_builds;
+  });
+}
+
 int osc_get_blocked_copy(osc_handle h, int32_t nb, int32_t* slot_col, float* slot_w, int32_t* over_first, int32_t* over_count,
                          int32_t* over_col, float* over_w, int32_t over_cap) {
   return guarded(h, [&](L& l) {
@@ -530,7 +540,10 @@ int osc_set_query(osc_handle h, const float* psi, const float* gates) {
       for (int64_t i = 0; i < l.N; ++i) gp[(size_t)i] = gates[l.perm_h[(size_t)i]];
       gates = gp.data();
     }
-    if (gates) HIP_CHECK(hipMemcpyAsync(l.B.p, gates, (size_t)l.N * 4, hipMemcpyHostToDevice, l.stream));
+    if (gates) {
+      HIP_CHECK(hipMemcpyAsync(l.B.p, gates, (size_t)l.N * 4, hipMemcpyHostToDevice, l.stream));
+      l.gates_uniform = host::gates_uniform(gates, l.N);
+    }
     sync(l);
     host::changed(l.derived, host::Input::query);
   });

@@ -81,6 +81,17 @@ struct osc_lattice {
   DevBuf<float> WYs;
   bool anchor_wy = true;
   int64_t cached_inits = 0;  // INIT passes served from WYs (osc_counters::cached_inits)
+  // The anchors' second row sums W.(W.Y) (row-major) and the rows' weight sums W.1: with them the cached INIT pass of an anchor
+  // start under uniform gates also emits iteration 1's A p (k_init_cached_ap) and that iteration's gathering matvec is not
+  // launched.  Built from WYs on the first solve that takes the route (a lattice's second anchor start), valid exactly as
+  // long as WYs (Derived::wwy_nb).  OSC_ANCHOR_AP: 0 never, 1 wherever the cached INIT runs, unset: by the lattice's rows
+  // (host_logic.hpp: anchor_ap_route).
+  DevBuf<float> WWs, Wsum;
+  int anchor_ap = -1;
+  bool anchor_ap_denied = false;  // the arrays did not fit (asked again once WYs is formed anew)
+  bool gates_uniform = true;      // B holds one value (osc_set_query scans the gates it is handed)
+  int64_t streamed_first_applies = 0, anchor_ap_builds = 0;
+  bool anchor_ap_last = false;    // the last general-path solve took the route
   int64_t yu_copies = 0;     // whole-array Y -> U copies made for this handle (osc_counters::y_to_u_copies)
   int64_t slab_launches = 0;  // k_rows_to_slab launches (osc_counters::rows_to_slab_launches)
   // Which of the arrays computed from other state (ell_col_t / ell_w_t, blk_*, Ys, WYs, Ustar; by epoch: halo, query) are

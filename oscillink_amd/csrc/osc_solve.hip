@@ -351,6 +351,9 @@ struct CgSolve {
   float* Pbuf;   // search direction / operator output: the fused INIT pass leaves p in the AP array and swaps the two for
   float* APbuf;  // the rest of the solve (init() alone changes them)
   size_t prof_mark = 0;  // the handle's pending profile samples when the loop started
+  // The INIT pass also left iteration 1's A p (in the AP array) and its p . Ap partials (in part1): init_fused, the anchor
+  // start under uniform gates.  enqueue(1) then launches no matvec and forms alpha from those partials.
+  bool first_ap_done = false;
 
   // ---- where x is updated ---------------------------------------------------------------------------------------------
   // Deferred x update: iteration it's x += alpha p is applied by iteration it + 1's p update, which reads p anyway (x, r,
@@ -488,6 +491,7 @@ struct CgSolve {
     launch_reduce_init(h.part0.p, part_rows, b.ld, b.c0, b.c1, h.rz.p, h.stream);
     ua.AP = APbuf;
     h.last_plan = plan;
+    h.anchor_ap_last = first_ap_done;
     return part_rows;
   }
 
@@ -517,10 +521,25 @@ struct CgSolve {
     const bool wy_route = h.anchor_wy && h.anchor_slab && ba.X == h.Ys.p && bi.Y == nullptr;
     if (wy_route && h.derived.wy_nb == ba.nb) {
       bi.WY = h.WYs.p;
-      launch_init_cached(ba, grid, h.stream, bi, plan.shape);
+      host::AnchorApInputs ai;
+      ai.mode = h.anchor_ap;
+      ai.N = h.N;
+      ai.cached_init = true;
+      ai.gates_uniform = h.gates_uniform && b.B == h.B.p;
+      ai.chain_rows = cf.chunks > 0;
+      if (host::anchor_ap_route(ai) && ensure_anchor_ap()) {
+        // ... and iteration 1's A p with its p . Ap sums: p1 = z0 goes to the AP array (the swap below), A p1 to the P array
+        BlkInitAp ap{h.WWs.p, h.Wsum.p, b.P, h.part1.p};
+        launch_init_cached(ba, grid, h.stream, bi, plan.shape, &ap);
+        first_ap_done = true;
+        h.streamed_first_applies += 1;
+      } else {
+        launch_init_cached(ba, grid, h.stream, bi, plan.shape);
+      }
       h.cached_inits += 1;
     } else if (wy_route) {
-      h.derived.wy_nb = 0;  // (not current while this launch rewrites them)
+      h.derived.wy_nb = h.derived.wwy_nb = 0;  // (not current while this launch rewrites them)
+      h.anchor_ap_denied = false;
       h.WYs.alloc((size_t)h.N * h.ld);
       bi.WY = h.WYs.p;
       launch_apply_blocked(ba, grid, h.stream, &bi, plan.shape, true);
@@ -544,6 +563,49 @@ struct CgSolve {
     }
     std::swap(Pbuf, APbuf);  // z, the first direction, lies in the AP array
     return part_rows;
+  }
+
+  // The anchors' second row sums for the streamed first apply (L::WWs, L::Wsum), formed from WYs where they are not held:
+  // W (W Y) by the loop-form matvec itself with cs = 0, cW = -1 (its cs x - cW acc stores acc), row-major; W 1 over the ELL
+  // rows.  An INIT-time launch like the others: not counted in blk_applies.  False where the arrays do not fit (the rule of
+  // the direction ring: a quarter of the free device memory): the solve keeps its gathered first apply.
+  bool ensure_anchor_ap() {
+    if (h.derived.wwy_nb == ba.nb) return true;
+    if (h.anchor_ap_denied) return false;
+    h.derived.wwy_nb = 0;
+    const size_t n = (size_t)h.N * h.ld;
+    if (h.WWs.n != n || h.Wsum.n != (size_t)h.N) {
+      size_t free_b = 0, total_b = 0;
+      HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+      bool ok = host::anchor_ap_fits((int64_t)(n + (size_t)h.N) * 4, (int64_t)free_b + (int64_t)(h.WWs.n + h.Wsum.n) * 4);
+      if (ok) {
+        try {
+          h.WWs.alloc(n);
+          h.Wsum.alloc((size_t)h.N);
+        } catch (const HipError&) {
+          (void)hipGetLastError();
+          ok = false;
+        }
+      }
+      if (!ok) {
+        h.WWs.release();
+        h.Wsum.release();
+        h.anchor_ap_denied = true;
+        return false;
+      }
+    }
+    BlkArgs wa = ba;
+    wa.X = h.WYs.p;
+    wa.OUT = h.WWs.p;
+    wa.cs_const = wa.cs_B = 0.f;
+    wa.cW = -1.f;
+    wa.gate = nullptr;
+    wa.gate_tol = 0.f;
+    launch_apply_blocked(wa, grid, h.stream, nullptr, plan.shape);
+    launch_row_weight_sums(h.ell_w.p, h.deg.p, h.width, (int32_t)h.N, h.Wsum.p, h.stream);
+    h.derived.wwy_nb = ba.nb;
+    h.anchor_ap_builds += 1;
+    return true;
   }
 
   // How many directions the solve keeps (plan_x_ring) and where: only a solve that wants more slots than the handle holds at
@@ -652,7 +714,10 @@ struct CgSolve {
       }
       update_p();
     }
-    if (ba.nb > 0) {  // Ap and column sums of p.Ap
+    if (it == 1 && first_ap_done) {
+      // (the INIT pass left A p1 in the AP array and the p . Ap partials in part1, which this iteration's x-r kernel overwrites)
+      launch_reduce_alpha(h.part1.p, grid, b.ld, b.c0, b.c1, h.rz.p, alpha_of(it), g, h.stream);
+    } else if (ba.nb > 0) {  // Ap and column sums of p.Ap
       ProfScope ps(h, 0, it);
       ba.X = cf.X = dir(it);
       ba.OUT = cf.OUT = APbuf;
@@ -667,7 +732,8 @@ struct CgSolve {
       sa.gate_tol = tol;
       spmm_slabbed(h, plan, SPMM_AP, sa, grid, it);
     }
-    launch_reduce_alpha(h.part0.p, grid + (ba.nb > 0 ? cf.chunks : 0), b.ld, b.c0, b.c1, h.rz.p, alpha_of(it), g, h.stream);
+    if (!(it == 1 && first_ap_done))
+      launch_reduce_alpha(h.part0.p, grid + (ba.nb > 0 ? cf.chunks : 0), b.ld, b.c0, b.c1, h.rz.p, alpha_of(it), g, h.stream);
     {
       ProfScope ps(h, 1, it);
       if (ringed()) {

@@ -243,6 +243,8 @@ class OscillinkLattice:
         ok, db, da, br, bn, bm = C.c_int32(0), C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int32(0), C.c_double(0.0)
         bd = C.c_int32(0)
         self._call("osc_balance_info", C.byref(ok), C.byref(db), C.byref(da), C.byref(br), C.byref(bn), C.byref(bm), C.byref(bd))
+        af, ab, al, an = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int64(0)
+        self._call("osc_anchor_ap_info", C.byref(af), C.byref(ab), C.byref(al), C.byref(an))
         counters = nat.Counters()
         self._call("osc_counters_get", C.byref(counters))
         return {"order_kind": ("none", "bfs", "balanced")[int(ok.value)], "displaced_edges_before": int(db.value),
@@ -255,6 +257,8 @@ class OscillinkLattice:
                 "apply_blocked_shape": int(counters.blocked_shape),
                 "x_ring_slots": int(xk.value), "x_ring_flushes": int(xf.value), "x_ring_passes": int(xp.value),
                 "x_ring_bytes": int(xb.value),
+                "streamed_first_applies": int(af.value), "anchor_ap_bytes": int(ab.value),
+                "anchor_ap_last_solve": int(al.value), "anchor_ap_builds": int(an.value),
                 **{name: int(getattr(counters, name)) for name, _ in nat.Counters._fields_[1:]}}
 
     def halo_info(self) -> dict[str, int]:
