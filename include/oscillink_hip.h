@@ -78,6 +78,33 @@ int osc_create(const float* Y, int64_t N, int32_t D, int32_t k, float row_cap, i
                int64_t seed, int32_t device, int32_t build_graph, osc_handle* out);
 int osc_destroy(osc_handle h);
 
+/* A NEW handle over the rows of `base` (API order) followed by the M rows of Ynew (M x D, host), with base's creation
+ * parameters (k as requested, row_cap, deterministic, seed, device) and lambdas; gates, psi, chain and U are those of a
+ * newly created handle (U = Y).  base is only read -- its anchors travel device to device, gathered back from its internal
+ * row order -- and is left as it was whatever happens; the caller destroys it.  Not in the reference.
+ *   mode 0: the planner decides (oscillink_amd/csrc/append_plan.hpp);
+ *   mode 1: incremental -- the top-k lists are grown from base's kept lists: the new rows, and the old rows whose lists
+ *           cannot be merged (a member clipped at 0, a non-finite row: the redo set), are scored against all N + M columns
+ *           in the arithmetic base's list values come from (the score family), every other old row takes the new columns
+ *           that beat its worst member, then the graph is assembled from the lists as in any build.  The lists are those of
+ *           a build of the N + M anchors in the same score family.  OSC_E_UNSUPPORTED with the reason in
+ *           osc_last_error(NULL) when base cannot seed it: no kept lists (osc_set_csr graph), a communicator, an effective
+ *           k that changes with the row count, k > 128, N + M >= 2^31, butterfly-scored lists wider than 1536 columns or
+ *           mixed with MFMA-scored fallback rows;
+ *   mode 2: a plain build of the N + M anchors.
+ * Seam: osc_graph.hip build_graph_once takes its seeded branch iff the handle under construction carries a seed; an
+ * ordinary osc_create / osc_rebuild_graph never does. */
+int osc_create_appended(osc_handle base, const float* Ynew, int64_t M, int32_t mode, osc_handle* out);
+/* How a handle came to be: route 0 = not by osc_create_appended, 1 = incremental, 2 = rebuild; new_rows = M; merged_rows = old
+ * rows whose lists were merged in place; redo_rows = old rows recomputed; family = score family of the kept lists (1 = fp32
+ * MFMA tiles, 2 = fma chains + wave butterfly; valid for every built handle); the incremental route's wall times in ms
+ * (scores + selection / merge scan / graph assembly); merge_hits = list members replaced; scan_bytes = bytes of score
+ * block the merge scan has to read (its floor); denied = why the planner did not take the incremental route (0 = it did,
+ * or mode 2; AppendDenied in append_plan.hpp).  Any pointer may be NULL. */
+int osc_append_info(osc_handle h, int32_t* route, int64_t* new_rows, int64_t* merged_rows, int64_t* redo_rows, int32_t* family,
+                    double* score_ms, double* merge_ms, double* back_ms, int64_t* merge_hits, int64_t* scan_bytes,
+                    int32_t* denied);
+
 /* rebuild_graph (lattice.py:760-801) */
 int osc_rebuild_graph(osc_handle h, int32_t k, float row_cap, int32_t deterministic, int64_t seed);
 

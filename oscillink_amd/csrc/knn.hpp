@@ -25,6 +25,13 @@ void launch_knn_dense_many(const float* Yn, int32_t ldn, int32_t N, int32_t nlat
 // be a multiple of 128.  out_val / out_idx are the full N x k lists.
 void launch_knn_rows_any(const float* Yn, int32_t ldn, int32_t N, int32_t k, int32_t row_begin, int32_t rows, float* Sm,
                          int32_t lds_, float* out_val, int32_t* out_idx, hipStream_t s);
+// the same scores for a LIST of query rows (Sm row b = lattice row qrows[b], nq x lds_ floats): bit-identical to the range
+// form's and to k_knn_dense's.  Scores only: launch_knn_select_listed picks the rows' k best.
+void launch_knn_rows_listed(const float* Yn, int32_t ldn, int32_t N, const int32_t* qrows, int32_t nq, float* Sm, int32_t lds_,
+                            hipStream_t s);
+// the radix select of launch_knn_rows_any / launch_knn_few_rows over the rows of a score block that stand for listed rows
+void launch_knn_select_listed(const float* Sm, int32_t lds_, int32_t N, int32_t k, const int32_t* qrows, int32_t nq,
+                              float* out_val, int32_t* out_idx, hipStream_t s);
 // exact fp32 lists of a FEW rows (nq <= 32; the prefilter routes' fallback): scores of the listed rows against all
 // columns into Sm (nq x lds_ floats, lds_ >= N) in k_knn_rescore's arithmetic, then each row's k best.  Returns false
 // when the rows are too wide for it (ldn > 1536): the caller then uses the MFMA kernel's row-list form.

@@ -367,9 +367,13 @@ __global__ __launch_bounds__(256, 2) void k_knn_topk(const float* __restrict__ Y
 // bit-identical to what the streaming kernel scores), and one wave per row then picks the k best by repeated argmax.
 // (blockIdx.z = lattice of a batch of equal-sized lattices stored back to back: rows lat_yn floats apart in Yn, lat_sm in Sm;
 // single-lattice launches pass 0 and one z)
+// (QR: the query rows are the nq listed ones -- Sm row b scores lattice row qrows[b] -- instead of a contiguous range; the
+// tile arithmetic is the same, so a listed row's scores are those of the range form bit for bit: osc_create_appended)
+template <bool QR>
 __global__ __launch_bounds__(256, 2) void k_knn_dense(const float* __restrict__ Yn, int32_t ldn, int32_t N,
                                                       float* __restrict__ Sm, int32_t lds_, int32_t row_base,
-                                                      int64_t lat_yn, int64_t lat_sm) {
+                                                      int64_t lat_yn, int64_t lat_sm, const int32_t* __restrict__ qrows,
+                                                      int32_t nq) {
   __shared__ __attribute__((aligned(16))) float lds[2 * BM * LDT];
   Yn += blockIdx.z * lat_yn;
   Sm += blockIdx.z * lat_sm;
@@ -390,7 +394,8 @@ __global__ __launch_bounds__(256, 2) void k_knn_dense(const float* __restrict__ 
   const float* b_ptr[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-    a_ptr[q] = Yn + (size_t)min(row0 + srow[q], N - 1) * ldn + sc4[q];
+    if constexpr (QR) a_ptr[q] = Yn + (size_t)qrows[min(row0 + srow[q], nq - 1)] * ldn + sc4[q];
+    else a_ptr[q] = Yn + (size_t)min(row0 + srow[q], N - 1) * ldn + sc4[q];
     b_ptr[q] = Yn + (size_t)min(ct + srow[q], N - 1) * ldn + sc4[q];
   }
   f32x16 acc[4];
@@ -439,7 +444,7 @@ __global__ __launch_bounds__(256, 2) void k_knn_dense(const float* __restrict__ 
 #pragma unroll
   for (int g = 0; g < 16; ++g) {
     const int row = row0 + 32 * wave + (g & 3) + 8 * (g >> 2) + 4 * h;
-    if (row >= N) continue;
+    if (row >= (QR ? nq : N)) continue;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       const int col = ct + 32 * t + l31;
@@ -1382,7 +1387,8 @@ void launch_knn_dense_many(const float* Yn, int32_t ldn, int32_t N, int32_t nlat
   if (nlat < 1) return;
   const int nb = (N + BM - 1) / BM;
   const int64_t lat_yn = (int64_t)N * ldn, lat_sm = (int64_t)N * lds_;
-  hipLaunchKernelGGL(k_knn_dense, dim3(nb, nb, nlat), dim3(256), 0, s, Yn, ldn, N, Sm, lds_, 0, lat_yn, lat_sm);
+  hipLaunchKernelGGL(k_knn_dense<false>, dim3(nb, nb, nlat), dim3(256), 0, s, Yn, ldn, N, Sm, lds_, 0, lat_yn, lat_sm,
+                     (const int32_t*)nullptr, 0);
   const dim3 grid((unsigned)((N + 3) / 4), (unsigned)nlat), block(256);
   const int m = (N + 63) / 64;
 #define OSC_SEL(MM) hipLaunchKernelGGL(k_knn_select<MM>, grid, block, 0, s, Sm, lds_, N, k, out_val, out_idx, lat_sm)
@@ -1405,10 +1411,28 @@ void launch_knn_rows_any(const float* Yn, int32_t ldn, int32_t N, int32_t k, int
                          int32_t lds_, float* out_val, int32_t* out_idx, hipStream_t s) {
   if (rows <= 0) return;
   if (row_begin % BM != 0) throw std::runtime_error("launch_knn_rows_any: row_begin must be a multiple of 128");
-  hipLaunchKernelGGL(k_knn_dense, dim3((N + BN - 1) / BN, (rows + BM - 1) / BM), dim3(256), 0, s, Yn, ldn, N, Sm, lds_,
-                     row_begin, (int64_t)0, (int64_t)0);
+  hipLaunchKernelGGL(k_knn_dense<false>, dim3((N + BN - 1) / BN, (rows + BM - 1) / BM), dim3(256), 0, s, Yn, ldn, N, Sm, lds_,
+                     row_begin, (int64_t)0, (int64_t)0, (const int32_t*)nullptr, 0);
   hipLaunchKernelGGL(k_knn_select_any<256>, dim3((unsigned)rows), dim3(256), 0, s, Sm, lds_, N, k, row_begin, rows, out_val,
                      out_idx, nullptr);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_knn_rows_listed(const float* Yn, int32_t ldn, int32_t N, const int32_t* qrows, int32_t nq, float* Sm, int32_t lds_,
+                            hipStream_t s) {
+  if (nq <= 0) return;
+  hipLaunchKernelGGL(k_knn_dense<true>, dim3((N + BN - 1) / BN, (nq + BM - 1) / BM), dim3(256), 0, s, Yn, ldn, N, Sm, lds_, 0,
+                     (int64_t)0, (int64_t)0, qrows, nq);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_knn_select_listed(const float* Sm, int32_t lds_, int32_t N, int32_t k, const int32_t* qrows, int32_t nq,
+                              float* out_val, int32_t* out_idx, hipStream_t s) {
+  if (nq <= 0) return;
+  if (nq <= 32)  // few rows, each a pass over all N scores: 1024 threads per row
+    hipLaunchKernelGGL(k_knn_select_any<1024>, dim3((unsigned)nq), dim3(1024), 0, s, Sm, lds_, N, k, 0, nq, out_val, out_idx, qrows);
+  else
+    hipLaunchKernelGGL(k_knn_select_any<256>, dim3((unsigned)nq), dim3(256), 0, s, Sm, lds_, N, k, 0, nq, out_val, out_idx, qrows);
   HIP_CHECK(hipGetLastError());
 }
 

@@ -75,6 +75,7 @@ void read_env_build(L& h) {
   h.bfs_host = num("OSC_BFS_HOST", v) && v != 0;
   h.balance = num("OSC_BALANCE", v) ? (v != 0 ? 1 : 0) : -1;
   h.balance_host = num("OSC_BALANCE_HOST", v) && v != 0;
+  h.append_scratch_bytes = num("OSC_APPEND_SCRATCH_MB", v) ? (int64_t)std::max(1, std::min(v, 65536)) << 20 : host::kAppendScratchBytes;
   h.halo_force = 0;
   if (const char* e = getenv("OSC_HALO")) h.halo_force = !strcmp(e, "full") ? 1 : !strcmp(e, "lists") ? 2 : 0;
 }
@@ -168,8 +169,10 @@ int osc_device_synchronize(int32_t device) {
 
 const char* osc_last_error(osc_handle h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
-int osc_create(const float* Y, int64_t N, int32_t D, int32_t k, float row_cap, int32_t deterministic, int64_t seed,
-               int32_t device, int32_t build, osc_handle* out) {
+// osc_create, and osc_create_appended's way through it (sd != nullptr: Y holds the sd->n_new NEW rows; the first sd->n_old
+// rows come from the base's device copy, gathered back to API order into this handle's row pitch)
+static int create_handle(const float* Y, int64_t N, int32_t D, int32_t k, float row_cap, int32_t deterministic, int64_t seed,
+                         int32_t device, int32_t build, osc_handle* out, const osc_lattice::AppendSeed* sd) {
   if (!out) return OSC_E_INVALID;
   *out = nullptr;
   if (!Y || N < 1 || D < 1 || k < 1 || N >= (int64_t)1 << 31) {
@@ -222,6 +225,7 @@ int osc_create(const float* Y, int64_t N, int32_t D, int32_t k, float row_cap, i
     }
     h->c0 = 0;
     h->c1 = h->dcols;
+    h->k_requested = k;
     h->k_eff = (int32_t)std::min<int64_t>(k, std::max<int64_t>(1, N - 1));
     h->row_cap = row_cap;
     h->deterministic = deterministic;
@@ -243,7 +247,21 @@ int osc_create(const float* Y, int64_t N, int32_t D, int32_t k, float row_cap, i
     HIP_CHECK(hipMemsetAsync(h->psi.p, 0, (size_t)h->ld * 4, h->stream));
     // The anchors' way to the device (Y, and U = Y: lattice.py:56-58).  With a build to follow it is the build's business:
     // where it can it takes them piece by piece and works on what has arrived (osc_graph.hip: stream_pieces).
-    if (build) {
+    if (sd != nullptr) {
+      const osc_lattice& b = *sd->base;
+      launch_append_gather_rows(h->Y.p, h->ld, b.Y.p, b.ld, b.perm_h.empty() ? nullptr : b.inv_d.p, sd->n_old, h->dcols, h->stream);
+      float* dst = h->Y.p + (size_t)sd->n_old * h->ld;
+      if (h->ld == D) HIP_CHECK(hipMemcpyAsync(dst, Y, (size_t)sd->n_new * D * 4, hipMemcpyHostToDevice, h->stream));
+      else HIP_CHECK(hipMemcpy2DAsync(dst, (size_t)h->ld * 4, Y, (size_t)D * 4, (size_t)D * 4, (size_t)sd->n_new, hipMemcpyHostToDevice, h->stream));
+      host::changed(h->derived, host::Input::anchors);
+      reset_u_to_y(*h);
+      h->lamG = b.lamG, h->lamC = b.lamC, h->lamQ = b.lamQ;
+      h->append.new_rows = sd->n_new;
+      h->append_seed = sd->seed_lists ? sd : nullptr;  // (else: a plain build of the concatenated anchors)
+      build_graph(*h, nullptr);  // (an exception ends the handle under construction with it)
+      h->append_seed = nullptr;
+      if (h->append.route == 0) h->append.route = host::kRouteRebuild;
+    } else if (build) {
       build_graph(*h, Y);
     } else {
       upload_rows(*h, h->Y.p, Y);
@@ -259,6 +277,76 @@ int osc_create(const float* Y, int64_t N, int32_t D, int32_t k, float row_cap, i
   }
   *out = h.release();
   return OSC_OK;
+}
+
+int osc_create(const float* Y, int64_t N, int32_t D, int32_t k, float row_cap, int32_t deterministic, int64_t seed,
+               int32_t device, int32_t build, osc_handle* out) {
+  return create_handle(Y, N, D, k, row_cap, deterministic, seed, device, build, out, nullptr);
+}
+
+int osc_create_appended(osc_handle base, const float* Ynew, int64_t M, int32_t mode, osc_handle* out) {
+  if (!out) return OSC_E_INVALID;
+  *out = nullptr;
+  if (!base || !Ynew || M < 1 || mode < 0 || mode > 2) {
+    g_create_error = "osc_create_appended: need a base handle, Ynew != NULL, M >= 1 and mode 0, 1 or 2";
+    return OSC_E_INVALID;
+  }
+  const osc_lattice& b = *base;
+  if (b.comm != nullptr) {
+    g_create_error = std::string("osc_create_appended: ") + host::append_denied_text(host::kAppendComm);
+    return OSC_E_UNSUPPORTED;
+  }
+  if (b.N + M >= (int64_t)1 << 31) {
+    g_create_error = std::string("osc_create_appended: ") + host::append_denied_text(host::kAppendTooManyRows);
+    return OSC_E_UNSUPPORTED;
+  }
+  const int32_t why = host::append_eligible(host::AppendInputs{b.N, M, b.D, b.k_requested, b.have_graph ? b.knn_k : 0, b.score_family,
+                                                               b.knn_fallback_rows, false});
+  if (mode == 1 && why != host::kAppendOk) {
+    g_create_error = std::string("osc_create_appended: no incremental route: ") + host::append_denied_text(why);
+    return OSC_E_UNSUPPORTED;
+  }
+  // (an injected graph cannot be rebuilt from anchors either: it is not theirs.  A lattice that was never built has no
+  // graph to keep: modes 0 and 2 build its N + M anchors)
+  if (why == host::kAppendNoLists && b.N > 1 && b.have_graph) {
+    g_create_error = std::string("osc_create_appended: ") + host::append_denied_text(why);
+    return OSC_E_UNSUPPORTED;
+  }
+  (void)hipSetDevice(b.device);
+  if (b.stream && hipStreamSynchronize(b.stream) != hipSuccess) {  // (the base's anchors and lists are read from another stream)
+    g_create_error = "osc_create_appended: the base lattice's stream reports an error";
+    return OSC_E_HIP;
+  }
+  osc_lattice::AppendSeed sd;
+  sd.base = base;
+  sd.n_old = b.N;
+  sd.n_new = M;
+  sd.forced = mode == 1;
+  sd.seed_lists = mode != 2 && why == host::kAppendOk;
+  osc_handle h = nullptr;
+  const int rc = create_handle(Ynew, b.N + M, b.D, b.k_requested, b.row_cap, b.deterministic, b.seed, b.device, 1, &h, &sd);
+  if (rc != OSC_OK) return rc;
+  if (mode != 2 && why != host::kAppendOk) h->append.denied = why;
+  *out = h;
+  return OSC_OK;
+}
+
+int osc_append_info(osc_handle h, int32_t* route, int64_t* new_rows, int64_t* merged_rows, int64_t* redo_rows, int32_t* family,
+                    double* score_ms, double* merge_ms, double* back_ms, int64_t* merge_hits, int64_t* scan_bytes, int32_t* denied) {
+  return guarded(h, [&](L& l) {
+    const osc_lattice::AppendInfo& a = l.append;
+    if (route) *route = a.route;
+    if (new_rows) *new_rows = a.new_rows;
+    if (merged_rows) *merged_rows = a.merged_rows;
+    if (redo_rows) *redo_rows = a.redo_rows;
+    if (family) *family = l.score_family;
+    if (score_ms) *score_ms = a.score_ms;
+    if (merge_ms) *merge_ms = a.merge_ms;
+    if (back_ms) *back_ms = a.back_ms;
+    if (merge_hits) *merge_hits = a.merge_hits;
+    if (scan_bytes) *scan_bytes = a.scan_bytes;
+    if (denied) *denied = a.denied;
+  });
 }
 
 int osc_host_alloc(int64_t bytes, void** out) {
@@ -285,6 +373,7 @@ int osc_rebuild_graph(osc_handle h, int32_t k, float row_cap, int32_t determinis
   return guarded(h, [&](L& l) {
     if (k < 1) throw Invalid("kneighbors must be >= 1");
     read_env_build(l);  // (the build's switches only: solver and sharding switches are fixed at creation)
+    l.k_requested = k;
     l.k_eff = (int32_t)std::min<int64_t>(k, std::max<int64_t>(1, l.N - 1));
     l.row_cap = row_cap;
     l.deterministic = deterministic;

@@ -832,6 +832,157 @@ static void assemble_lists(L& h, const KnnBuildPlan& plan) {
   }
 }
 
+// compute units of a device (hipGetDeviceProperties is slow: asked once per device)
+static int device_cus(int device) {
+  static std::mutex mu;
+  static std::map<int, int> cus;
+  std::lock_guard<std::mutex> lk(mu);
+  auto it = cus.find(device);
+  if (it == cus.end()) {
+    hipDeviceProp_t prop;
+    HIP_CHECK(hipGetDeviceProperties(&prop, device));
+    it = cus.emplace(device, prop.multiProcessorCount).first;
+  }
+  return it->second;
+}
+
+// the back half of a build: a function of the lists alone (mutual test, cap, Laplacian weights, counts, row order)
+static void graph_from_lists(L& h, int32_t N, int32_t k) {
+  alloc_ell(h, k);
+  launch_mutual_ell(h.knn_val.p, h.knn_idx.p, N, k, h.width, h.ell_col.p, h.ell_a.p, h.deg.p, h.stream);
+  DevBuf<float> scale;
+  scale.alloc((size_t)h.N);
+  launch_cap_and_normalize(h.ell_a.p, h.ell_w.p, h.ell_col.p, h.deg.p, h.width, N, h.row_cap, 1, scale.p,
+                           h.sqrt_deg.p, h.stream);
+  graph_counts(h);  // synchronises
+  h.have_graph = true;
+  maybe_reorder(h);
+}
+
+// The seeded build of osc_create_appended: the handle's anchors are on the device in API order, the
+// base's lists name the first n_old rows' k best old columns.  The query rows -- the redo set (old rows whose lists
+// cannot be merged: a clipped or missing member, a non-finite row) and the new rows -- are scored against all columns in
+// the base's score family, chunk by chunk; each chunk's rows get their k best, and every other old row merges the chunk's
+// new columns into its list (append_kernels.hip).  Then the back half, unchanged.  false (auto mode only): the planner
+// expects the rebuild to be no slower; nothing but scratch was written and the unseeded build runs.
+static bool build_graph_seeded(L& h) {
+  const L::AppendSeed& sd = *h.append_seed;
+  const L& base = *sd.base;
+  const int32_t N = (int32_t)h.N, n_old = (int32_t)sd.n_old, k = base.knn_k;
+  const int32_t family = base.score_family;
+  const double t0 = now_ms();
+  // (auto mode: M alone over the threshold decides on the host, before any device work)
+  if (!sd.forced && !host::append_pays(family, n_old, (int64_t)N - n_old, 0)) {
+    h.append.denied = host::kAppendSlower;
+    return false;
+  }
+  const int32_t ldn = (int32_t)host::append_ldn(h.D);  // (an allocated lattice: N ldn floats exist)
+  DevBuf<float> Yn, kval;
+  DevBuf<int32_t> kidx, redo_list, counts, qrows;
+  DevBuf<uint8_t> flags;
+  Yn.alloc((size_t)N * ldn);
+  launch_normalize_rows(h.Y.p, h.ld, Yn.p, ldn, N, h.D, h.stream);
+  // the lists: the base's rows, then empty rows (value 0, id -1) for the new ones
+  kval.alloc((size_t)N * k);
+  kidx.alloc((size_t)N * k);
+  HIP_CHECK(hipMemcpyAsync(kval.p, base.knn_val.p, (size_t)n_old * k * 4, hipMemcpyDeviceToDevice, h.stream));
+  HIP_CHECK(hipMemcpyAsync(kidx.p, base.knn_idx.p, (size_t)n_old * k * 4, hipMemcpyDeviceToDevice, h.stream));
+  HIP_CHECK(hipMemsetAsync(kval.p + (size_t)n_old * k, 0, (size_t)(N - n_old) * k * 4, h.stream));
+  HIP_CHECK(hipMemsetAsync(kidx.p + (size_t)n_old * k, 0xFF, (size_t)(N - n_old) * k * 4, h.stream));
+  flags.alloc((size_t)N);
+  redo_list.alloc((size_t)n_old);
+  counts.alloc(3);  // redo rows, non-finite rows, merge hits
+  HIP_CHECK(hipMemsetAsync(counts.p, 0, 12, h.stream));
+  launch_append_flags(Yn.p, ldn, n_old, N, kval.p, kidx.p, k, flags.p, redo_list.p, counts.p, h.stream);
+  int32_t hc[3] = {0, 0, 0};
+  HIP_CHECK(hipMemcpyAsync(hc, counts.p, 8, hipMemcpyDeviceToHost, h.stream));
+  sync(h);
+  const int64_t redo = hc[0], nbad = hc[1], m_new = N - n_old;
+  if (!sd.forced && !host::append_pays(family, n_old, m_new, redo)) {
+    h.append.denied = host::kAppendSlower;
+    return false;
+  }
+  // the query list: the redo rows in ascending order, then the new rows
+  std::vector<int32_t> q((size_t)(redo + m_new));
+  if (redo > 0) {
+    HIP_CHECK(hipMemcpyAsync(q.data(), redo_list.p, (size_t)redo * 4, hipMemcpyDeviceToHost, h.stream));
+    sync(h);
+    std::sort(q.begin(), q.begin() + redo);
+  }
+  for (int64_t j = 0; j < m_new; ++j) q[(size_t)(redo + j)] = (int32_t)(n_old + j);
+  const int64_t nq = (int64_t)q.size();
+  qrows.alloc((size_t)nq);
+  HIP_CHECK(hipMemcpyAsync(qrows.p, q.data(), (size_t)nq * 4, hipMemcpyHostToDevice, h.stream));
+  const int64_t budget = h.append_scratch_bytes;
+  const int64_t lds = host::append_lds(N), chunk = host::append_chunk_rows(N, budget);
+  const int64_t nchunks = host::append_chunk_count(nq, chunk);
+  DevBuf<float> Sm;
+  Sm.alloc((size_t)host::append_scratch_floats(nq, N, budget));
+  const int cus = device_cus(h.device);
+  int64_t scan_bytes = 0;
+  // the phases' times come from events: three per chunk, read once after the loop (no host wait inside it)
+  struct Events {
+    std::vector<hipEvent_t> ev;
+    ~Events() {
+      for (auto e : ev) (void)hipEventDestroy(e);
+    }
+    void mark(hipStream_t s) {
+      hipEvent_t e = nullptr;
+      HIP_CHECK(hipEventCreate(&e));
+      ev.push_back(e);
+      HIP_CHECK(hipEventRecord(e, s));
+    }
+  } marks;
+  marks.ev.reserve((size_t)nchunks * 3);
+  for (int64_t c = 0; c < nchunks; ++c) {
+    int64_t b = 0, e = 0, nb = 0, ne = 0, first_col = 0;
+    host::append_chunk_range(nq, chunk, c, b, e);
+    const int32_t mc = (int32_t)(e - b);
+    marks.mark(h.stream);
+    if (family == host::kFamilyMfma) launch_knn_rows_listed(Yn.p, ldn, N, qrows.p + b, mc, Sm.p, (int32_t)lds, h.stream);
+    else launch_append_scores_butterfly(Yn.p, ldn, N, qrows.p + b, mc, Sm.p, lds, cus, h.stream);
+    if (nbad > 0) launch_append_sanitize(Sm.p, lds, mc, N, h.stream);
+    launch_knn_select_listed(Sm.p, (int32_t)lds, N, k, qrows.p + b, mc, kval.p, kidx.p, h.stream);
+    if (nbad > 0) launch_append_fix_lists(Sm.p, lds, qrows.p + b, mc, k, kval.p, kidx.p, h.stream);
+    marks.mark(h.stream);
+    host::append_chunk_new_part(redo, n_old, b, e, nb, ne, first_col);
+    launch_append_merge(Sm.p, lds, (int32_t)nb, (int32_t)ne, (int32_t)first_col, n_old, flags.p, k, kval.p, kidx.p, counts.p + 2, h.stream);
+    marks.mark(h.stream);  // (the next chunk's scores overwrite Sm behind the merge: one stream, in order)
+    scan_bytes += (ne - nb) * (int64_t)(n_old - redo) * 4;
+  }
+  HIP_CHECK(hipMemcpyAsync(hc + 2, counts.p + 2, 4, hipMemcpyDeviceToHost, h.stream));
+  sync(h);
+  double score_ms = 0, merge_ms = 0;
+  for (size_t i = 0; i + 2 < marks.ev.size(); i += 3) {
+    float a = 0.f, m = 0.f;
+    HIP_CHECK(hipEventElapsedTime(&a, marks.ev[i], marks.ev[i + 1]));
+    HIP_CHECK(hipEventElapsedTime(&m, marks.ev[i + 1], marks.ev[i + 2]));
+    score_ms += a;
+    merge_ms += m;
+  }
+  h.knn_val.swap(kval);
+  h.knn_idx.swap(kidx);
+  h.knn_k = k;
+  h.knn_last = base.knn_last;
+  h.knn_last.k = k;
+  h.knn_fallback_rows = base.knn_fallback_rows;
+  h.score_family = family;
+  const double t3 = now_ms();
+  graph_from_lists(h, N, k);
+  sync(h);
+  h.append.route = host::kRouteIncremental;
+  h.append.new_rows = m_new;
+  h.append.redo_rows = redo;
+  h.append.merged_rows = n_old - redo;
+  h.append.merge_hits = hc[2];
+  h.append.scan_bytes = scan_bytes;
+  h.append.score_ms = score_ms;
+  h.append.merge_ms = merge_ms;
+  h.append.back_ms = now_ms() - t3;
+  h.build_ms = now_ms() - t0;
+  return true;
+}
+
 // false: a streamed build gave up before its exact-kernel fallback (see build_graph); Y and U are on the device then
 static bool build_graph_once(L& h, const float* host_Y) {
   const double t0 = now_ms();
@@ -840,6 +991,7 @@ static bool build_graph_once(L& h, const float* host_Y) {
   const int32_t N = (int32_t)h.N;
   h.k_eff = std::min<int32_t>(h.k_eff, std::max<int32_t>(1, N - 1));  // lattice.py:60
   host::changed(h.derived, host::Input::graph);  // (the lists below already replace the old graph's)
+  if (h.append_seed != nullptr && build_graph_seeded(h)) return true;  // (osc_create_appended alone sets the seed)
   if (N <= 1) {  // graph.py:30-32
     upload_anchors(h, host_Y);
     alloc_ell(h, 1);
@@ -871,15 +1023,8 @@ static bool build_graph_once(L& h, const float* host_Y) {
     if (runs_part(h, plan, part)) sweep_part(h, w, part, host_Y);
   if (plan.prefilter() && !prove_fallback_rows(h, w)) return false;
   assemble_lists(h, plan);
-  alloc_ell(h, k);
-  launch_mutual_ell(h.knn_val.p, h.knn_idx.p, N, k, h.width, h.ell_col.p, h.ell_a.p, h.deg.p, h.stream);
-  DevBuf<float> scale;
-  scale.alloc((size_t)h.N);
-  launch_cap_and_normalize(h.ell_a.p, h.ell_w.p, h.ell_col.p, h.deg.p, h.width, N, h.row_cap, 1, scale.p,
-                           h.sqrt_deg.p, h.stream);
-  graph_counts(h);  // synchronises
-  h.have_graph = true;
-  maybe_reorder(h);
+  h.score_family = plan.prefilter() ? host::kFamilyButterfly : host::kFamilyMfma;
+  graph_from_lists(h, N, k);
   h.build_ms = now_ms() - t0;
   return true;
 }

@@ -25,6 +25,8 @@
 #include "comm.hpp"
 #include "knn.hpp"
 #include "knn_gemm.hpp"
+#include "append.hpp"
+#include "append_plan.hpp"
 #include "receipts.hpp"
 #include "perm.hpp"
 #include "dynamics.hpp"
@@ -115,6 +117,26 @@ struct osc_lattice {
   int32_t knn_k = 0;
   int32_t knn_fallback_rows = 0;  // rows of the last build the prefilter could not prove and the exact kernel redid
   KnnBuildPlan knn_last;          // the route of the last build (knn_plan.hpp: plan_knn_build)
+  // osc_create_appended.  k_requested: k as asked for at creation / the last rebuild, before the clamp
+  // to N - 1.  score_family: which arithmetic the kept lists' values come from (host::AppendFamily; from the build's route,
+  // inherited by an appended handle).  append_seed: set only while a handle is being built from a base's lists
+  // (build_graph_once takes its seeded branch then); append: what osc_append_info reports.
+  int32_t k_requested = 0;
+  int32_t score_family = 0;
+  struct AppendSeed {
+    const osc_lattice* base = nullptr;  // its lists are read, nothing of it is written
+    int64_t n_old = 0, n_new = 0;
+    bool forced = false;                // mode 1: the planner's thresholds do not apply
+    bool seed_lists = false;            // the base's lists seed the build (else only its anchors are taken over)
+  };
+  const AppendSeed* append_seed = nullptr;
+  int64_t append_scratch_bytes = host::kAppendScratchBytes;  // budget of one chunk's score block (OSC_APPEND_SCRATCH_MB)
+  struct AppendInfo {
+    int32_t route = 0;  // host::AppendRoute
+    int64_t new_rows = 0, merged_rows = 0, redo_rows = 0, merge_hits = 0, scan_bytes = 0;
+    int32_t denied = 0;
+    double score_ms = 0, merge_ms = 0, back_ms = 0;
+  } append;
   double build_ms = 0.0;
   int64_t nnz = 0;
   int32_t max_deg = 0;

@@ -65,6 +65,7 @@ class OscillinkLattice:
         self.N, self.D = Yc.shape
         k_eff = min(int(kneighbors), max(1, self.N - 1))
         self._kneighbors = k_eff
+        self._kneighbors_requested = int(kneighbors)  # (append: the effective k follows the row count again)
         self._deterministic_k = bool(deterministic_k)
         self._neighbor_seed = neighbor_seed
         self._row_cap_val = float(row_cap_val)
@@ -80,7 +81,8 @@ class OscillinkLattice:
         # comm = (ncclUniqueId bytes, rank, world): one process per GPU.  The graph is then built row-block-sharded
         # (all-gather of the top-k lists) and the CG runs column-sharded (one all-reduce(max) per iteration).
         build_now = bool(_build_graph) and comm is None
-        rc = L.osc_create(nat.f32(Yc), self.N, self.D, k_eff, self._row_cap_val, int(self._deterministic_k),
+        # (the library clamps k to N - 1 itself and keeps the requested value for osc_create_appended)
+        rc = L.osc_create(nat.f32(Yc), self.N, self.D, self._kneighbors_requested, self._row_cap_val, int(self._deterministic_k),
                           -1 if neighbor_seed is None else int(neighbor_seed), self._device, int(build_now),
                           C.byref(h))
         nat.check(rc, None, "osc_create")
@@ -90,7 +92,7 @@ class OscillinkLattice:
             uid, rank, world = comm
             nat.check(L.osc_comm_init(h, bytes(uid), int(rank), int(world)), h, "osc_comm_init")
             if _build_graph:
-                nat.check(L.osc_rebuild_graph(h, k_eff, self._row_cap_val, int(self._deterministic_k),
+                nat.check(L.osc_rebuild_graph(h, self._kneighbors_requested, self._row_cap_val, int(self._deterministic_k),
                                               -1 if neighbor_seed is None else int(neighbor_seed)), h,
                           "osc_rebuild_graph")
         self._graph_build_ms = 1000.0 * (time.time() - t0)
@@ -1050,12 +1052,14 @@ class OscillinkLattice:
         # the new parameters become the object's only after the device accepted them: a failed rebuild must not leave
         # the Python side describing a graph the device does not hold (_kneighbors feeds _signature and the HMAC payload)
         cap = self._row_cap_val if row_cap_val is None else float(row_cap_val)
-        k = self._kneighbors if kneighbors is None else min(int(kneighbors), max(1, self.N - 1))
+        k_req = self._kneighbors_requested if kneighbors is None else int(kneighbors)
+        k = min(k_req, max(1, self.N - 1))
         det = self._deterministic_k if deterministic_k is None else bool(deterministic_k)
         seed = self._neighbor_seed if neighbor_seed is None else neighbor_seed
         t0 = time.time()
-        self._call("osc_rebuild_graph", int(k), float(cap), int(det), -1 if seed is None else int(seed))
+        self._call("osc_rebuild_graph", int(k_req), float(cap), int(det), -1 if seed is None else int(seed))
         self._row_cap_val, self._kneighbors, self._deterministic_k, self._neighbor_seed = cap, k, det, seed
+        self._kneighbors_requested = k_req
         self._graph_build_ms = 1000.0 * (time.time() - t0)
         self._csr = None
         self._touch()
@@ -1063,6 +1067,88 @@ class OscillinkLattice:
         self._invalidate_cache()
         self._log("rebuild_graph", {"k": int(self._kneighbors), "row_cap_val": float(self._row_cap_val),
                                     "deterministic_k": self._deterministic_k, "neighbor_seed": self._neighbor_seed})
+
+    # ------------------------------------------------------------------ append (not in the reference)
+    _APPEND_MODES = {"auto": 0, "incremental": 1, "rebuild": 2}
+
+    def append(self, Ynew: np.ndarray, gates: Optional[np.ndarray] = None, *, mode: str = "auto") -> np.ndarray:
+        """Add the rows of `Ynew` (M x D) behind the lattice's own and return their ids N .. N + M - 1.
+
+        The lattice afterwards is the one `OscillinkLattice(np.concatenate([Y, Ynew]), ...)` would be with this lattice's
+        settings applied: same graph, U = Y (the state is NOT carried over an append), lambdas, psi, chain and lamP kept,
+        gates = the old gates followed by `gates` (ones when None).  Logger, callbacks, receipt secret, signature and detail
+        modes stay.  mode "incremental" grows the kNN lists from the kept ones and raises where that is not possible,
+        "rebuild" builds the concatenated anchors from scratch on the device, "auto" lets the planner choose
+        (`append_info()` says which).  Only `Ynew` crosses the bus.  A failure leaves the lattice exactly as it was."""
+        if mode not in self._APPEND_MODES:
+            raise ValueError("mode must be 'auto', 'incremental' or 'rebuild'")
+        if not isinstance(Ynew, np.ndarray) or Ynew.ndim != 2:
+            raise ValueError("Ynew must be a 2D numpy array")
+        if Ynew.shape[1] != self.D:
+            raise ValueError("Ynew column count mismatch D")
+        M = int(Ynew.shape[0])
+        g_new = None
+        if gates is not None:
+            g_new = np.ascontiguousarray(gates, dtype=np.float32).ravel()
+            if g_new.shape[0] != M:
+                raise ValueError("gates length mismatch M")
+        if M == 0:
+            return np.empty(0, dtype=np.int64)
+        if getattr(self, "_has_comm", False):
+            raise nat.NativeError("append: a lattice with a communicator cannot grow (multi-rank handles are out of scope)")
+        Yc = np.ascontiguousarray(Ynew, dtype=np.float32)
+        L = nat.lib()
+        new_h = nat.Handle()
+        t0 = time.time()
+        nat.check(L.osc_create_appended(self._h, nat.f32(Yc), M, self._APPEND_MODES[mode], C.byref(new_h)), None,
+                  "osc_create_appended")
+        N_new = self.N + M
+        B_new = np.concatenate([self._B, np.ones(M, dtype=np.float32) if g_new is None else g_new]).astype(np.float32)
+        try:  # the carried settings go to the new handle before anything of this object changes
+            nat.check(L.osc_set_lams(new_h, float(self.lamG), float(self.lamC), float(self.lamQ)), new_h, "osc_set_lams")
+            nat.check(L.osc_set_query(new_h, nat.f32(self._psi), nat.f32(B_new)), new_h, "osc_set_query")
+            if self._chain_nodes is not None:
+                ch = np.asarray(self._chain_nodes, dtype=np.int32)
+                ws = None if self._chain_weights is None else np.asarray(self._chain_weights, dtype=np.float32)
+                nat.check(L.osc_set_chain(new_h, nat.i32(ch), None if ws is None else nat.f32(ws), int(ch.size),
+                                          float(self.lamP)), new_h, "osc_set_chain")
+        except Exception:
+            L.osc_destroy(new_h)
+            raise
+        old_h, self._h = self._h, new_h
+        L.osc_destroy(old_h)
+        ids = np.arange(self.N, N_new, dtype=np.int64)
+        self.N = N_new
+        self._B = B_new
+        self._kneighbors = min(self._kneighbors_requested, max(1, self.N - 1))
+        self._lamP_dev = float(self.lamP)
+        self._graph_build_ms = 1000.0 * (time.time() - t0)
+        self._Y_host = None
+        self._U_host = None
+        self._csr = None
+        self._device_ustar_sig = None
+        self.last = {"iters": 0, "res": None, "t_ms": None}
+        self._last_dynamics = None
+        self._touch()
+        self._qb_version += 1
+        self._qb_key = None
+        self._invalidate_cache()
+        info = self.append_info()
+        self._log("append", {"rows": M, "N": self.N, "route": info["route"], "redo_rows": info["redo_rows"]})
+        return ids
+
+    def append_info(self) -> dict[str, Any]:
+        """How the handle came to be (osc_append_info): route 0 = not by `append`, 1 = incremental, 2 = rebuild; the score
+        family of its kNN lists ("mfma" / "butterfly"); the incremental route's phases in ms."""
+        route, fam, denied = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        new, merged, redo, hits, scan = (C.c_int64(0) for _ in range(5))
+        sc, mg, bk = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
+        self._call("osc_append_info", C.byref(route), C.byref(new), C.byref(merged), C.byref(redo), C.byref(fam), C.byref(sc),
+                   C.byref(mg), C.byref(bk), C.byref(hits), C.byref(scan), C.byref(denied))
+        return {"route": int(route.value), "new_rows": int(new.value), "merged_rows": int(merged.value),
+                "redo_rows": int(redo.value), "score_family": ("none", "mfma", "butterfly")[int(fam.value)],
+                "score_ms": float(sc.value), "merge_ms": float(mg.value), "back_half_ms": float(bk.value),
+                "merge_hits": int(hits.value), "merge_scan_bytes": int(scan.value), "denied": int(denied.value)}
 
     # ------------------------------------------------------------------ persistence (lattice.py:582-726)
     def _provenance(self) -> str:
