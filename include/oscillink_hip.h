@@ -164,6 +164,15 @@ int osc_x_ring_info(osc_handle h, int32_t* slots, int64_t* flushes, int64_t* pas
  * general-path solve took the route, builds = times the arrays were formed (measurement aid) */
 int osc_anchor_ap_info(osc_handle h, int64_t* streamed_first_applies, int64_t* bytes, int32_t* last_solve, int64_t* builds);
 
+/* the streamed second apply of anchor starts (on top of the streamed first apply, in a solve of at least two iterations: the
+ * cached INIT pass also leaves T = A (A p1), formed from the anchors' third row sums W (W (W Y)) and W (W 1), iteration 2's p
+ * update forms A p2 = (1 + beta1) A p1 - m alpha1 T beside p2, and that iteration's gathering matvec is not launched either;
+ * OSC_ANCHOR_AP2 = 0 off / 1 wherever the streamed first apply runs, unset: lattices of at least 96000 rows):
+ * streamed_second_applies = iterations served so since creation, bytes = device memory held for the two arrays and T (0: not
+ * built or dropped), last_solve = whether the last general-path solve took the route, builds = times the arrays were formed
+ * (measurement aid) */
+int osc_anchor_ap2_info(osc_handle h, int64_t* streamed_second_applies, int64_t* bytes, int32_t* last_solve, int64_t* builds);
+
 /* the block-major copy of the graph the blocked matvec walks, built for `nb` source blocks (test / diagnostic aid; no
  * reference counterpart): slot_col / slot_w [nb][N][4] = {neighbour row, W_ij} per (source block, row, slot), unused slots
  * {first row of the block, 0}; rows whose edges exceed 4 nb slots list the rest in over_col / over_w[over_first[i] ..

@@ -134,6 +134,7 @@ SIGNATURES = {
     "osc_apply_info": (C.c_int, [Handle, c_i32p, c_i64p]),
     "osc_x_ring_info": (C.c_int, [Handle, c_i32p, c_i64p, c_i64p, c_i64p]),
     "osc_anchor_ap_info": (C.c_int, [Handle, c_i64p, c_i64p, c_i32p, c_i64p]),
+    "osc_anchor_ap2_info": (C.c_int, [Handle, c_i64p, c_i64p, c_i32p, c_i64p]),
     "osc_balance_info": (C.c_int, [Handle, c_i32p, c_i64p, c_i64p, c_i32p, c_i32p, c_f64p, c_i32p]),
     "osc_get_blocked_copy": (C.c_int, [Handle, C.c_int32, c_i32p, c_f32p, c_i32p, c_i32p, c_i32p, c_f32p, C.c_int32]),
     "osc_comm_unique_id": (C.c_int, [C.c_char_p]),

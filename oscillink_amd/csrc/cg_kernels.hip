@@ -702,9 +702,12 @@ __device__ __forceinline__ float4 ld4_stream_at(const float* base, uint32_t byte
 // A p1 = cs z0 - cW W p1 is streamed here instead of gathered: one more row read (WWY, row-major), one more row written
 // (A p1, row-major), the column sums of p1 . A p1 into ap.part beside those of r . z.  r, z, the x0 copy and the r . z sums
 // are the other form's to the bit; the new products and sums are spelled out so that no call site contracts them its own way.
-template <int CW, bool AP>
-__device__ __forceinline__ void init_cached_body(const BlkArgs& a, const BlkInit& ii, const BlkInitAp& ap) {
-  constexpr int NT = (CW + 1) * 64, EC = 4;
+// AP == 2 (BlkInitAp2): ... and T = A (A p1) for iteration 2, by the same algebra one level up: with s2 = W s and W3Y = W WWY
+// (L::Wsum2, L::W3s), (W W p1)_i = m (qb s2_i psi + u WWY_i + cW W3Y_i), W Q1 = cs W p1 - cW W W p1, T = cs Q1 - cW W Q1.
+// One more row read (W3Y), one more row written (T, row-major); everything the AP == 1 form writes keeps its bits.
+template <int CW, int AP>
+__device__ __forceinline__ void init_cached_body(const BlkArgs& a, const BlkInit& ii, const BlkInitAp& ap, const BlkInitAp2& ap2) {
+  constexpr int NT = (CW + 1) * 64, EC = AP == 2 ? 3 : 4;  // (AP == 2: batches of three rows keep the four streams in registers; a lane's sums keep their order)
   __shared__ __attribute__((aligned(16))) float red[CW + 1][32];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int sub = lane >> 3, lr = lane & 7;
@@ -732,6 +735,8 @@ __device__ __forceinline__ void init_cached_body(const BlkArgs& a, const BlkInit
       float4 xs[2][EC], ws[2][EC];
       float4 vs[2][AP ? EC : 1];  // (AP: the rows of W W Y and the rows' weight sums)
       float ss[2][AP ? EC : 1];
+      float4 ts[2][AP == 2 ? EC : 1];  // (AP == 2: the rows of W W W Y and the rows' second weight sums)
+      float s2[2][AP == 2 ? EC : 1];
       float bv[2][EC];
       // No test around the loads: a lane without a row (past the part's rows, or a column past c1) reads the part's last row,
       // resp. the slab's first columns, and consume() drops what it got.  With the loads in straight-line code the compiler's
@@ -739,7 +744,8 @@ __device__ __forceinline__ void init_cached_body(const BlkArgs& a, const BlkInit
       const uint32_t lrc = cok ? lr16 : 0u;
       const uint32_t cbc = cok ? cb : (uint32_t)sc0 * 4u;
       const int row_last = max(wk.rhi - 1, 0);
-      auto fetch = [&](int k, float4 (&x)[EC], float4 (&w)[EC], float (&bb)[EC], float4 (&v)[AP ? EC : 1], float (&sm)[AP ? EC : 1]) {
+      auto fetch = [&](int k, float4 (&x)[EC], float4 (&w)[EC], float (&bb)[EC], float4 (&v)[AP ? EC : 1], float (&sm)[AP ? EC : 1],
+                       float4 (&t)[AP == 2 ? EC : 1], float (&sm2)[AP == 2 ? EC : 1]) {
 #pragma unroll
         for (int i = 0; i < EC; ++i) {  // (byte offsets fit 32 bits: launch_init_cached checks as launch_apply_blocked does)
           const uint32_t row = (uint32_t)min(row_first + (k * EC + i) * wk.W8, row_last);
@@ -750,10 +756,14 @@ __device__ __forceinline__ void init_cached_body(const BlkArgs& a, const BlkInit
             v[i] = ld4_stream_at(ap.WW, row * ldb + cbc);
             sm[i] = ld1_at(ap.wsum, row * 4u);
           }
+          if constexpr (AP == 2) {
+            t[i] = ld4_stream_at(ap2.W3, row * ldb + cbc);
+            sm2[i] = ld1_at(ap2.wsum2, row * 4u);
+          }
         }
       };
       auto consume = [&](int k, const float4 (&x)[EC], const float4 (&w)[EC], const float (&bb)[EC], const float4 (&v)[AP ? EC : 1],
-                         const float (&sm)[AP ? EC : 1]) {
+                         const float (&sm)[AP ? EC : 1], const float4 (&t)[AP == 2 ? EC : 1], const float (&sm2)[AP == 2 ? EC : 1]) {
 #pragma unroll
         for (int i = 0; i < EC; ++i) {
           const int g = k * EC + i, row = row_first + g * wk.W8;
@@ -777,23 +787,35 @@ __device__ __forceinline__ void init_cached_body(const BlkArgs& a, const BlkInit
                                          one(z.z, w[i].z, v[i].z, psi4.z), one(z.w, w[i].w, v[i].w, psi4.w));
             st4_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(ap.AP) + ((uint32_t)row * ldb + cb)), o);
             dot_ap = mulacc4(z, o, dot_ap);
+            if constexpr (AP == 2) {
+              const float qs2 = __fmul_rn(__fmul_rn(ii.rbB, bb[i]), sm2[i]);
+              auto two = [&](float ov, float wyv, float wwv, float w3v, float pv) {
+                const float wz = __fmul_rn(invMd, fmaf(a.cW, wwv, fmaf(u, wyv, __fmul_rn(qs, pv))));    // (W z0)_i, as in one()
+                const float wwz = __fmul_rn(invMd, fmaf(a.cW, w3v, fmaf(u, wwv, __fmul_rn(qs2, pv))));  // (W W z0)_i
+                const float wq = fmaf(cs, wz, -__fmul_rn(a.cW, wwz));                                   // (W Q1)_i
+                return fmaf(cs, ov, -__fmul_rn(a.cW, wq));
+              };
+              const float4 tt = make_float4(two(o.x, w[i].x, v[i].x, t[i].x, psi4.x), two(o.y, w[i].y, v[i].y, t[i].y, psi4.y),
+                                            two(o.z, w[i].z, v[i].z, t[i].z, psi4.z), two(o.w, w[i].w, v[i].w, t[i].w, psi4.w));
+              st4_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(ap2.T) + ((uint32_t)row * ldb + cb)), tt);
+            }
           }
         }
       };
-      fetch(0, xs[0], ws[0], bv[0], vs[0], ss[0]);
+      fetch(0, xs[0], ws[0], bv[0], vs[0], ss[0], ts[0], s2[0]);
       int k = 0;
       for (; k + 2 < nbatch; k += 2) {  // two batches per trip (the buffers keep their registers), no test around a fetch
-        fetch(k + 1, xs[1], ws[1], bv[1], vs[1], ss[1]);
-        consume(k, xs[0], ws[0], bv[0], vs[0], ss[0]);
-        fetch(k + 2, xs[0], ws[0], bv[0], vs[0], ss[0]);
-        consume(k + 1, xs[1], ws[1], bv[1], vs[1], ss[1]);
+        fetch(k + 1, xs[1], ws[1], bv[1], vs[1], ss[1], ts[1], s2[1]);
+        consume(k, xs[0], ws[0], bv[0], vs[0], ss[0], ts[0], s2[0]);
+        fetch(k + 2, xs[0], ws[0], bv[0], vs[0], ss[0], ts[0], s2[0]);
+        consume(k + 1, xs[1], ws[1], bv[1], vs[1], ss[1], ts[1], s2[1]);
       }
       if (k + 1 < nbatch) {  // the last one or two batches (batch k is in xs[0])
-        fetch(k + 1, xs[1], ws[1], bv[1], vs[1], ss[1]);
-        consume(k, xs[0], ws[0], bv[0], vs[0], ss[0]);
-        consume(k + 1, xs[1], ws[1], bv[1], vs[1], ss[1]);
+        fetch(k + 1, xs[1], ws[1], bv[1], vs[1], ss[1], ts[1], s2[1]);
+        consume(k, xs[0], ws[0], bv[0], vs[0], ss[0], ts[0], s2[0]);
+        consume(k + 1, xs[1], ws[1], bv[1], vs[1], ss[1], ts[1], s2[1]);
       } else {
-        consume(k, xs[0], ws[0], bv[0], vs[0], ss[0]);
+        consume(k, xs[0], ws[0], bv[0], vs[0], ss[0], ts[0], s2[0]);
       }
     }
     blk_fold<CW + 1>(dot, red, a.part, ld, sc0, min(a.c1, sc0 + 32), wave, lane);
@@ -802,11 +824,15 @@ __device__ __forceinline__ void init_cached_body(const BlkArgs& a, const BlkInit
 }
 template <int CW>
 __global__ __launch_bounds__((CW + 1) * 64) void k_init_cached(const BlkArgs a, const BlkInit ii) {
-  init_cached_body<CW, false>(a, ii, BlkInitAp{});
+  init_cached_body<CW, 0>(a, ii, BlkInitAp{}, BlkInitAp2{});
 }
 template <int CW>
 __global__ __launch_bounds__((CW + 1) * 64) void k_init_cached_ap(const BlkArgs a, const BlkInit ii, const BlkInitAp ap) {
-  init_cached_body<CW, true>(a, ii, ap);
+  init_cached_body<CW, 1>(a, ii, ap, BlkInitAp2{});
+}
+template <int CW>
+__global__ __launch_bounds__((CW + 1) * 64) void k_init_cached_ap2(const BlkArgs a, const BlkInit ii, const BlkInitAp ap, const BlkInitAp2 ap2) {
+  init_cached_body<CW, 2>(a, ii, ap, ap2);
 }
 
 // s_i = sum_j W_ij over the ELL row, in stored order: one thread per row (BlkInitAp::wsum)
@@ -816,6 +842,20 @@ __global__ __launch_bounds__(256) void k_row_weight_sums(const float* w, const i
   float s = 0.f;
   const int d = min(deg[row], width);
   for (int e = 0; e < d; ++e) s = __fadd_rn(s, w[(size_t)row * width + e]);
+  out[row] = s;
+}
+
+// out_i = sum_j W_ij v_j over the ELL row, in stored order: one thread per row (BlkInitAp2::wsum2 = W (W 1))
+__global__ __launch_bounds__(256) void k_row_weighted_sums(const int32_t* col, const float* w, const int32_t* deg, int32_t width, int32_t N,
+                                                           const float* v, float* out) {
+  const int row = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (row >= N) return;
+  float s = 0.f;
+  const int d = min(deg[row], width);
+  for (int e = 0; e < d; ++e) {
+    const int j = col[(size_t)row * width + e];
+    if (j >= 0 && j < N) s = fmaf(w[(size_t)row * width + e], v[j], s);
+  }
   out[row] = s;
 }
 
@@ -1119,6 +1159,71 @@ __global__ __launch_bounds__(256) void k_update_p(const UpdateArgs a) {
       }
     }
   }
+}
+
+// Iteration 2's p update of an anchor start whose INIT pass left Q1 = A p1 (in the AP array) and T = A Q1 (UpdateArgs::T):
+// p2 = z1 + beta1 p1 as k_update_p forms it (same operands, same order, and its WITHX form of iteration 1's x update), and
+// with both in hand A p2 = A z1 + beta1 Q1 = (1 + beta1) Q1 - (m alpha1) T, since z1 = m (r0 - alpha1 Q1) and A r0 = Q1 / m
+// under uniform gates (m the same in every row; alpha1, beta1 column scalars, which commute with A).  A p2 goes over Q1, the
+// column partials of p2 . A p2 to part_rr (block_fold: deterministic), where the alpha reduction of an iteration reads them:
+// the iteration launches no matvec.
+template <int LPR, int NCH, bool WITHX>
+__global__ __launch_bounds__(256) void k_update_p_ap2(const UpdateArgs a) {
+  constexpr int RPW = 64 / LPR;
+  constexpr int CPW = NCH * LPR * 4;
+  __shared__ __attribute__((aligned(16))) float red[4 * CPW];
+  if (a.gate != nullptr && *a.gate <= a.gate_tol) return;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int sub = lane / LPR, lr = lane % LPR;
+  const int32_t ld = a.ld;
+  const bool tmp = a.temporal != 0;
+  [[maybe_unused]] const float* const xin = a.Xin != nullptr ? a.Xin : a.X;
+  float* const pout = a.Pout != nullptr ? a.Pout : a.P;
+  int coff[NCH];
+  bool cok[NCH];
+  float4 be[NCH], al[NCH], pap[NCH];
+#pragma unroll
+  for (int ch = 0; ch < NCH; ++ch) {
+    coff[ch] = a.c0 + (ch * LPR + lr) * 4;
+    cok[ch] = coff[ch] < a.c1;
+    be[ch] = cok[ch] ? ld4(a.beta + coff[ch]) : f4(0.f);
+    al[ch] = cok[ch] ? ld4(a.alpha + coff[ch]) : f4(0.f);
+    pap[ch] = f4(0.f);
+  }
+  const int64_t rend = a.N;
+  for (int64_t rb = a.row0 + ((int64_t)blockIdx.x * 4 + wave) * RPW; rb < rend; rb += (int64_t)gridDim.x * 4 * RPW) {
+    const int row = (int)rb + sub;
+    if (row >= rend) continue;
+    float invMd = 1.f;
+    if (a.op.precond) invMd = 1.f / (fmaf(a.op.md_B, a.B[row], a.op.md_const) + 1e-12f);
+#pragma unroll
+    for (int ch = 0; ch < NCH; ++ch) {
+      if (!cok[ch]) continue;
+      const size_t off = (size_t)row * ld + coff[ch];
+      const size_t poff = p_off(a, row, coff[ch]);
+      float4 p = ld4_sel(a.P + poff, tmp);
+      const float4 r = ld4_sel(a.R + off, tmp);
+      const float4 q = ld4_sel(a.AP + off, tmp);
+      const float4 t = ld4_stream(a.T + off);
+      if constexpr (WITHX) {
+        float4 x = ld4_sel(xin + off, tmp);
+        x.x = fmaf(p.x, al[ch].x, x.x); x.y = fmaf(p.y, al[ch].y, x.y);
+        x.z = fmaf(p.z, al[ch].z, x.z); x.w = fmaf(p.w, al[ch].w, x.w);
+        st4_sel(a.X + off, x, tmp);
+      }
+      p.x = fmaf(p.x, be[ch].x, r.x * invMd); p.y = fmaf(p.y, be[ch].y, r.y * invMd);
+      p.z = fmaf(p.z, be[ch].z, r.z * invMd); p.w = fmaf(p.w, be[ch].w, r.w * invMd);
+      st4(pout + poff, p);
+      auto one = [&](float qv, float tv, float bv, float av) {
+        return fmaf(__fadd_rn(1.f, bv), qv, -__fmul_rn(__fmul_rn(invMd, av), tv));
+      };
+      const float4 o = make_float4(one(q.x, t.x, be[ch].x, al[ch].x), one(q.y, t.y, be[ch].y, al[ch].y),
+                                   one(q.z, t.z, be[ch].z, al[ch].z), one(q.w, t.w, be[ch].w, al[ch].w));
+      st4_sel(a.APout + off, o, tmp);
+      pap[ch] = mulacc4(p, o, pap[ch]);
+    }
+  }
+  block_fold<LPR, NCH>(pap, red, a.part_rr, ld, a.c0, a.c1);
 }
 
 // x = xin + alpha_1 p_1 + ... + alpha_M p_M from a ring of kept directions (XRingArgs), oldest first: the only kernel of such
@@ -1426,14 +1531,26 @@ static void blocked_args_check(const BlkArgs& a, int grid, int variant) {
 }
 
 // the cached INIT pass in the geometry of kernel shape `variant` (the shape fixes the gathering waves per workgroup)
-void launch_init_cached(const BlkArgs& a, int grid, hipStream_t s, const BlkInit& init, int variant, const BlkInitAp* ap) {
+void launch_init_cached(const BlkArgs& a, int grid, hipStream_t s, const BlkInit& init, int variant, const BlkInitAp* ap,
+                        const BlkInitAp2* ap2) {
   blocked_args_check(a, grid, variant);
   if (!init.R || !init.Z || !init.psi || !init.WY || init.Y != nullptr || init.Z == a.X || init.Z == init.WY)
     throw std::runtime_error("cached INIT pass: bad arguments");
+  if (ap2 != nullptr && ap == nullptr) throw std::runtime_error("cached INIT pass: the second apply needs the first");
   if (ap != nullptr) {
     if (!ap->WW || !ap->wsum || !ap->AP || !ap->part || ap->part == a.part || ap->AP == init.R || ap->AP == init.Z || ap->AP == init.Xcopy ||
         ap->AP == ap->WW)
       throw std::runtime_error("cached INIT pass: bad first-apply arguments");
+    if (ap2 != nullptr) {
+      if (!ap2->W3 || !ap2->wsum2 || !ap2->T || ap2->T == ap->AP || ap2->T == init.R || ap2->T == init.Z || ap2->T == init.Xcopy ||
+          ap2->T == ap2->W3 || ap2->T == ap->WW || ap2->T == init.WY || ap2->T == a.X)
+        throw std::runtime_error("cached INIT pass: bad second-apply arguments");
+#define CALL(G, W, P, E) hipLaunchKernelGGL((k_init_cached_ap2<W>), dim3(grid), dim3((W + 1) * 64), 0, s, a, init, *ap, *ap2)
+      OSC_BLK_SHAPE_SWITCH(variant, CALL);
+#undef CALL
+      HIP_CHECK(hipGetLastError());
+      return;
+    }
 #define CALL(G, W, P, E) hipLaunchKernelGGL((k_init_cached_ap<W>), dim3(grid), dim3((W + 1) * 64), 0, s, a, init, *ap)
     OSC_BLK_SHAPE_SWITCH(variant, CALL);
 #undef CALL
@@ -1447,6 +1564,12 @@ void launch_init_cached(const BlkArgs& a, int grid, hipStream_t s, const BlkInit
 }
 void launch_row_weight_sums(const float* w, const int32_t* deg, int32_t width, int32_t N, float* out, hipStream_t s) {
   hipLaunchKernelGGL(k_row_weight_sums, dim3((N + 255) / 256), dim3(256), 0, s, w, deg, width, N, out);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_row_weighted_sums(const int32_t* col, const float* w, const int32_t* deg, int32_t width, int32_t N, const float* v,
+                              float* out, hipStream_t s) {
+  hipLaunchKernelGGL(k_row_weighted_sums, dim3((N + 255) / 256), dim3(256), 0, s, col, w, deg, width, N, v, out);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -1530,6 +1653,22 @@ void launch_update_p(const UpdateArgs& a, int grid, hipStream_t s) {
   const Shape sh = pick_shape(a.c1 - a.c0);
 #define CALL(L, C) hipLaunchKernelGGL((k_update_p<L, C, false>), dim3(grid), dim3(256), 0, s, a)
 #define CALL_X(L, C) hipLaunchKernelGGL((k_update_p<L, C, true>), dim3(grid), dim3(256), 0, s, a)
+  if (a.xmode & OSC_XMODE_P_APPLIES_X) {
+    OSC_SHAPE_SWITCH(sh, CALL_X);
+  } else {
+    OSC_SHAPE_SWITCH(sh, CALL);
+  }
+#undef CALL
+#undef CALL_X
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_update_p_ap2(const UpdateArgs& a, int grid, hipStream_t s) {
+  if (!a.T || !a.APout || a.APout != a.AP || !a.part_rr || !a.alpha || !a.beta || a.T == a.AP || a.T == a.R || a.T == a.P || a.T == a.Pout)
+    throw std::runtime_error("p update with streamed A p: bad arguments");
+  const Shape sh = pick_shape(a.c1 - a.c0);
+#define CALL(L, C) hipLaunchKernelGGL((k_update_p_ap2<L, C, false>), dim3(grid), dim3(256), 0, s, a)
+#define CALL_X(L, C) hipLaunchKernelGGL((k_update_p_ap2<L, C, true>), dim3(grid), dim3(256), 0, s, a)
   if (a.xmode & OSC_XMODE_P_APPLIES_X) {
     OSC_SHAPE_SWITCH(sh, CALL_X);
   } else {

@@ -145,6 +145,14 @@ struct BlkInitAp {
   float* part;        // [grid][ld] column partial sums of p1 . A p1
 };
 
+// ... and, one level further, T = A (A p1) from the anchors' third row sums (L::W3s, L::Wsum2): iteration 2's p update then
+// forms A p2 = (1 + beta1) A p1 - m alpha1 T without a gather (k_update_p_ap2)
+struct BlkInitAp2 {
+  const float* W3;     // W (W (W Y)), row-major with pitch ld
+  const float* wsum2;  // [N] s2 = W (W 1)
+  float* T;            // A (A p1) out, row-major
+};
+
 enum SpmmMode { SPMM_AP = 0, SPMM_INIT = 1, SPMM_DOT = 2 };
 
 struct SpmmArgs {
@@ -215,6 +223,11 @@ struct UpdateArgs {
   // where k_update_p writes the new direction (nullptr: over P).  A solve that keeps its directions in a ring (run_cg) reads
   // the previous one from P and writes the next slot; no kernel of such a solve touches x but k_update_x_ring
   float* Pout;
+  // k_update_p_ap2 only (iteration 2 of an anchor start whose INIT pass left Q1 = A p1 in the AP array and T = A Q1): the
+  // launch also writes A p2 = (1 + beta) Q1 - (m alpha) T over Q1 (APout, the array AP names) and the column partials of
+  // p2 . A p2 into part_rr; alpha is iteration 1's.  nullptr in every other launch.
+  const float* T;
+  float* APout;
 };
 // OSC_XMODE_XR_BARE (with XR_SKIPS_X): the x-r kernel of the expected last iteration of a ring solve -- x left alone, the new
 // r not stored
@@ -299,12 +312,18 @@ void launch_apply_blocked(const BlkArgs& a, int grid, hipStream_t s, const BlkIn
                           bool store_wy = false);
 // the same INIT pass with the row sums read from init.WY instead of gathered (k_init_cached): same results to the bit
 // ap: the form that also streams iteration 1's A p1 and its p . Ap sums (BlkInitAp)
-void launch_init_cached(const BlkArgs& a, int grid, hipStream_t s, const BlkInit& init, int variant, const BlkInitAp* ap = nullptr);
+// ap2 (with ap): ... and T = A (A p1) (BlkInitAp2)
+void launch_init_cached(const BlkArgs& a, int grid, hipStream_t s, const BlkInit& init, int variant, const BlkInitAp* ap = nullptr,
+                        const BlkInitAp2* ap2 = nullptr);
 void launch_row_weight_sums(const float* w, const int32_t* deg, int32_t width, int32_t N, float* out, hipStream_t s);
+// out_i = sum_j W_ij v_j over the ELL row, in stored order (BlkInitAp2::wsum2 from BlkInitAp::wsum)
+void launch_row_weighted_sums(const int32_t* col, const float* w, const int32_t* deg, int32_t width, int32_t N, const float* v,
+                              float* out, hipStream_t s);
 int blocked_resident_per_cu(int variant);  // workgroups per CU a kernel shape (kBlkShapes) gets resident
 void launch_spmm(int mode, const SpmmArgs& a, int grid, hipStream_t s);
 void launch_update_xr(const UpdateArgs& a, int grid, hipStream_t s);
 void launch_update_p(const UpdateArgs& a, int grid, hipStream_t s);
+void launch_update_p_ap2(const UpdateArgs& a, int grid, hipStream_t s);  // (UpdateArgs::T, APout)
 void launch_update_x(const UpdateArgs& a, int grid, hipStream_t s);  // x += alpha p (UpdateArgs::xmode)
 void launch_update_x_ring(const XRingArgs& a, int grid, hipStream_t s);
 // column reductions over `nb` partial rows

@@ -14,6 +14,8 @@
 //                                       tests/host_logic/sweep_x_ring.cpp)
 //   gates_uniform / anchor_ap_route / anchor_ap_fits : whether an anchor start streams iteration 1's A p from the cached
 //                                       second row sums (swept by tests/host_logic/sweep_anchor_ap.cpp)
+//   anchor_ap2_route                  : ... and iteration 2's from the cached third row sums (swept, with cg_host_loop against
+//                                       a model of the launches, by tests/host_logic/sweep_anchor_ap2.cpp)
 //   cg_host_loop                      : the host loop of a CG solve -- which iteration is enqueued when (run_cg in
 //                                       osc_solve.hip and both sweeps run this one function)
 #pragma once
@@ -580,6 +582,27 @@ inline bool anchor_ap_route(const AnchorApInputs& in) {
 }
 // the memory rule of the direction ring: the arrays are only taken from a quarter of what is free
 inline bool anchor_ap_fits(int64_t bytes, int64_t free_bytes) { return bytes >= 0 && bytes <= free_bytes / 4; }
+// One level further: the INIT pass also leaves T = A (A p1) (from the third row sums W W W Y and W W 1), and iteration 2's p
+// update forms A p2 = (1 + beta1) A p1 - m alpha1 T beside p2 (cg_kernels.hip: k_update_p_ap2): that iteration launches no
+// matvec either.  Only on top of the depth-1 route, and only in a solve that may run a second iteration.
+struct AnchorAp2Inputs {
+  int mode = -1;         // OSC_ANCHOR_AP2: 0 off, 1 wherever the depth-1 route runs, < 0 by the lattice's rows
+  int64_t N = 0;
+  bool depth1 = false;   // anchor_ap_route holds for this solve and its arrays are held
+  int max_iters = 0;
+};
+inline bool anchor_ap2_route(const AnchorAp2Inputs& in) {
+  if (in.mode == 0 || !in.depth1 || in.max_iters < 2) return false;
+  return in.mode > 0 || in.N >= kAnchorApAutoRows;
+}
+// Where iteration `it` of a solve gets its A p (CgSolve::enqueue): from the INIT pass (first: it left A p1 and the p . Ap
+// partials), from the iteration's own p update (second: the INIT pass left T), or from a matvec.
+enum class ApSource { matvec, init_pass, p_update };
+inline ApSource cg_ap_source(int it, bool first, bool second) {
+  if (it == 1 && first) return ApSource::init_pass;
+  if (it == 2 && first && second) return ApSource::p_update;
+  return ApSource::matvec;
+}
 
 // ---- the ring of kept search directions (run_cg) ----------------------------------------------------------------------
 // x is an output of the recurrence only: x = x0 + sum alpha_it p_it.  With the last K directions (and their alpha vectors)

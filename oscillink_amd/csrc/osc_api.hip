@@ -35,6 +35,7 @@ void read_env_solver(L& h) {
   if (num("OSC_ANCHOR_SLAB", v)) h.anchor_slab = v != 0;
   if (num("OSC_ANCHOR_WY", v)) h.anchor_wy = v != 0;  // (needs the anchors' image: OSC_ANCHOR_SLAB=0 switches it off too, run_cg)
   if (num("OSC_ANCHOR_AP", v)) h.anchor_ap = v != 0 ? 1 : 0;
+  if (num("OSC_ANCHOR_AP2", v)) h.anchor_ap2 = v != 0 ? 1 : 0;
   if (num("OSC_RECEIPT_PAIR", v)) h.receipt_pair = v != 0;
   if (const char* e = getenv("OSC_SHARD")) h.shard_mode = !strcmp(e, "row") ? 1 : 0;
   if (num("OSC_ROW_FAKE_SHARDS", v)) h.fake_row_shards = std::max(0, v);
@@ -424,6 +425,15 @@ int osc_anchor_ap_info(osc_handle h, int64_t* streamed_first_applies, int64_t* b
     if (bytes) *bytes = l.derived.wwy_nb > 0 ? ((int64_t)l.WWs.n + (int64_t)l.Wsum.n) * 4 : 0;
     if (last_solve) *last_solve = l.anchor_ap_last ? 1 : 0;
     if (builds) *builds = l.anchor_ap_builds;
+  });
+}
+
+int osc_anchor_ap2_info(osc_handle h, int64_t* streamed_second_applies, int64_t* bytes, int32_t* last_solve, int64_t* builds) {
+  return guarded(h, [&](L& l) {
+    if (streamed_second_applies) *streamed_second_applies = l.streamed_second_applies;
+    if (bytes) *bytes = l.derived.w3_nb > 0 ? ((int64_t)l.W3s.n + (int64_t)l.Wsum2.n + (int64_t)l.Tap.n) * 4 : 0;
+    if (last_solve) *last_solve = l.anchor_ap2_last ? 1 : 0;
+    if (builds) *builds = l.anchor_ap2_builds;
   });
 }
 

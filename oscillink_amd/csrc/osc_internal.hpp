@@ -94,6 +94,16 @@ struct osc_lattice {
   bool gates_uniform = true;      // B holds one value (osc_set_query scans the gates it is handed)
   int64_t streamed_first_applies = 0, anchor_ap_builds = 0;
   bool anchor_ap_last = false;    // the last general-path solve took the route
+  // One level further (host_logic.hpp: anchor_ap2_route): the anchors' third row sums W.(W.(W.Y)) (row-major), W.(W.1) and the
+  // scratch array T = A (A p1) the INIT pass fills; iteration 2's p update then forms A p2 and that iteration launches no
+  // matvec either.  Built from WWs / Wsum on the first solve that takes the route -- the anchor start that built WWs, or the
+  // first one after OSC_ANCHOR_AP2 allows it -- and valid exactly as long as they are (Derived::w3_nb).  OSC_ANCHOR_AP2: 0
+  // never, 1 wherever the depth-1 route runs, unset: by the lattice's rows.
+  DevBuf<float> W3s, Wsum2, Tap;
+  int anchor_ap2 = -1;
+  bool anchor_ap2_denied = false;
+  int64_t streamed_second_applies = 0, anchor_ap2_builds = 0;
+  bool anchor_ap2_last = false;
   int64_t yu_copies = 0;     // whole-array Y -> U copies made for this handle (osc_counters::y_to_u_copies)
   int64_t slab_launches = 0;  // k_rows_to_slab launches (osc_counters::rows_to_slab_launches)
   // Which of the arrays computed from other state (ell_col_t / ell_w_t, blk_*, Ys, WYs, Ustar; by epoch: halo, query) are

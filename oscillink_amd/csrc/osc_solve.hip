@@ -354,6 +354,9 @@ struct CgSolve {
   // The INIT pass also left iteration 1's A p (in the AP array) and its p . Ap partials (in part1): init_fused, the anchor
   // start under uniform gates.  enqueue(1) then launches no matvec and forms alpha from those partials.
   bool first_ap_done = false;
+  // ... and T = A (A p1) (in the handle's Tap array): iteration 2's p update then forms A p2 over A p1 and leaves the
+  // p . Ap partials in part0 (k_update_p_ap2), and enqueue(2) launches no matvec either.
+  bool second_ap_ready = false;
 
   // ---- where x is updated ---------------------------------------------------------------------------------------------
   // Deferred x update: iteration it's x += alpha p is applied by iteration it + 1's p update, which reads p anyway (x, r,
@@ -492,6 +495,7 @@ struct CgSolve {
     ua.AP = APbuf;
     h.last_plan = plan;
     h.anchor_ap_last = first_ap_done;
+    h.anchor_ap2_last = second_ap_ready;
     return part_rows;
   }
 
@@ -530,7 +534,18 @@ struct CgSolve {
       if (host::anchor_ap_route(ai) && ensure_anchor_ap()) {
         // ... and iteration 1's A p with its p . Ap sums: p1 = z0 goes to the AP array (the swap below), A p1 to the P array
         BlkInitAp ap{h.WWs.p, h.Wsum.p, b.P, h.part1.p};
-        launch_init_cached(ba, grid, h.stream, bi, plan.shape, &ap);
+        host::AnchorAp2Inputs a2;
+        a2.mode = h.anchor_ap2;
+        a2.N = h.N;
+        a2.depth1 = true;
+        a2.max_iters = max_iters;
+        if (host::anchor_ap2_route(a2) && ensure_anchor_ap2()) {  // ... and T = A (A p1) for iteration 2's p update
+          BlkInitAp2 ap2{h.W3s.p, h.Wsum2.p, h.Tap.p};
+          launch_init_cached(ba, grid, h.stream, bi, plan.shape, &ap, &ap2);
+          second_ap_ready = true;
+        } else {
+          launch_init_cached(ba, grid, h.stream, bi, plan.shape, &ap);
+        }
         first_ap_done = true;
         h.streamed_first_applies += 1;
       } else {
@@ -538,8 +553,8 @@ struct CgSolve {
       }
       h.cached_inits += 1;
     } else if (wy_route) {
-      h.derived.wy_nb = h.derived.wwy_nb = 0;  // (not current while this launch rewrites them)
-      h.anchor_ap_denied = false;
+      h.derived.wy_nb = h.derived.wwy_nb = h.derived.w3_nb = 0;  // (not current while this launch rewrites them)
+      h.anchor_ap_denied = h.anchor_ap2_denied = false;
       h.WYs.alloc((size_t)h.N * h.ld);
       bi.WY = h.WYs.p;
       launch_apply_blocked(ba, grid, h.stream, &bi, plan.shape, true);
@@ -605,6 +620,52 @@ struct CgSolve {
     launch_row_weight_sums(h.ell_w.p, h.deg.p, h.width, (int32_t)h.N, h.Wsum.p, h.stream);
     h.derived.wwy_nb = ba.nb;
     h.anchor_ap_builds += 1;
+    return true;
+  }
+
+  // The anchors' third row sums for the streamed second apply (L::W3s, L::Wsum2) and the T array, formed from WWs / Wsum where
+  // they are not held (ensure_anchor_ap has just made those current): W (W W Y) by the loop-form matvec as there, over a
+  // slab-major image of WWs that k_rows_to_slab writes into T (free until the INIT pass fills it); W (W 1) over the ELL rows.
+  // The same memory rule: W3s and T together from a quarter of what is free, or the solve keeps depth 1.
+  bool ensure_anchor_ap2() {
+    if (h.derived.w3_nb == ba.nb && h.derived.wwy_nb == ba.nb) return true;
+    if (h.anchor_ap2_denied) return false;
+    h.derived.w3_nb = 0;
+    const size_t n = (size_t)h.N * h.ld;
+    if (h.W3s.n != n || h.Tap.n != n || h.Wsum2.n != (size_t)h.N) {
+      size_t free_b = 0, total_b = 0;
+      HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+      bool ok = host::anchor_ap_fits((int64_t)(2 * n + (size_t)h.N) * 4, (int64_t)free_b + (int64_t)(h.W3s.n + h.Tap.n + h.Wsum2.n) * 4);
+      if (ok) {
+        try {
+          h.W3s.alloc(n);
+          h.Tap.alloc(n);
+          h.Wsum2.alloc((size_t)h.N);
+        } catch (const HipError&) {
+          (void)hipGetLastError();
+          ok = false;
+        }
+      }
+      if (!ok) {
+        h.W3s.release();
+        h.Tap.release();
+        h.Wsum2.release();
+        h.anchor_ap2_denied = true;
+        return false;
+      }
+    }
+    rows_to_slab(h, h.WWs.p, h.Tap.p, h.ld, b.c0, b.c1, grid);
+    BlkArgs wa = ba;
+    wa.X = h.Tap.p;
+    wa.OUT = h.W3s.p;
+    wa.cs_const = wa.cs_B = 0.f;
+    wa.cW = -1.f;
+    wa.gate = nullptr;
+    wa.gate_tol = 0.f;
+    launch_apply_blocked(wa, grid, h.stream, nullptr, plan.shape);
+    launch_row_weighted_sums(h.ell_col.p, h.ell_w.p, h.deg.p, h.width, (int32_t)h.N, h.Wsum.p, h.Wsum2.p, h.stream);
+    h.derived.w3_nb = ba.nb;
+    h.anchor_ap2_builds += 1;
     return true;
   }
 
@@ -700,6 +761,7 @@ struct CgSolve {
     const Gate g{it > 1 && !overlap ? reinterpret_cast<const float*>(res_slots) + (it - 1) : nullptr, tol};
     host::CgXSchedule::IterForm form{false, host::CgXSchedule::XR_SKIPS_X};
     if (!ringed()) form = xs.enqueue(it, speculative);
+    const host::ApSource ap_src = host::cg_ap_source(it, first_ap_done, second_ap_ready);
     if (it > 1) {
       ProfScope ps(h, 2, it);
       if (ringed()) {
@@ -712,9 +774,21 @@ struct CgSolve {
         // (Xin: this launch applies iteration it - 1's x update)
         set_update(g.p, form.p_applies_x ? OSC_XMODE_P_APPLIES_X : 0, it == 2 ? x1_in : nullptr, h.alpha.p, Pbuf, nullptr);
       }
-      update_p();
+      if (ap_src == host::ApSource::p_update) {  // ... and A p2 over A p1, with the p . Ap partials (k_update_p_ap2; alpha: iteration 1's)
+        ua.T = h.Tap.p;
+        ua.APout = APbuf;
+        for_windows(ua, [&](const UpdateArgs& w) { launch_update_p_ap2(w, grid, h.stream); });
+        ua.T = nullptr;
+        ua.APout = nullptr;
+      } else {
+        update_p();
+      }
     }
-    if (it == 1 && first_ap_done) {
+    if (ap_src == host::ApSource::p_update) {
+      // (the p update left A p2 in the AP array and the p . Ap partials in part0, which this iteration's x-r kernel overwrites)
+      launch_reduce_alpha(h.part0.p, grid, b.ld, b.c0, b.c1, h.rz.p, alpha_of(it), g, h.stream);
+      h.streamed_second_applies += 1;
+    } else if (ap_src == host::ApSource::init_pass) {
       // (the INIT pass left A p1 in the AP array and the p . Ap partials in part1, which this iteration's x-r kernel overwrites)
       launch_reduce_alpha(h.part1.p, grid, b.ld, b.c0, b.c1, h.rz.p, alpha_of(it), g, h.stream);
     } else if (ba.nb > 0) {  // Ap and column sums of p.Ap
@@ -732,7 +806,7 @@ struct CgSolve {
       sa.gate_tol = tol;
       spmm_slabbed(h, plan, SPMM_AP, sa, grid, it);
     }
-    if (!(it == 1 && first_ap_done))
+    if (ap_src == host::ApSource::matvec)
       launch_reduce_alpha(h.part0.p, grid + (ba.nb > 0 ? cf.chunks : 0), b.ld, b.c0, b.c1, h.rz.p, alpha_of(it), g, h.stream);
     {
       ProfScope ps(h, 1, it);

@@ -247,6 +247,8 @@ class OscillinkLattice:
         self._call("osc_balance_info", C.byref(ok), C.byref(db), C.byref(da), C.byref(br), C.byref(bn), C.byref(bm), C.byref(bd))
         af, ab, al, an = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int64(0)
         self._call("osc_anchor_ap_info", C.byref(af), C.byref(ab), C.byref(al), C.byref(an))
+        a2f, a2b, a2l, a2n = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int64(0)
+        self._call("osc_anchor_ap2_info", C.byref(a2f), C.byref(a2b), C.byref(a2l), C.byref(a2n))
         counters = nat.Counters()
         self._call("osc_counters_get", C.byref(counters))
         return {"order_kind": ("none", "bfs", "balanced")[int(ok.value)], "displaced_edges_before": int(db.value),
@@ -261,6 +263,8 @@ class OscillinkLattice:
                 "x_ring_bytes": int(xb.value),
                 "streamed_first_applies": int(af.value), "anchor_ap_bytes": int(ab.value),
                 "anchor_ap_last_solve": int(al.value), "anchor_ap_builds": int(an.value),
+                "streamed_second_applies": int(a2f.value), "anchor_ap2_bytes": int(a2b.value),
+                "anchor_ap2_last_solve": int(a2l.value), "anchor_ap2_builds": int(a2n.value),
                 **{name: int(getattr(counters, name)) for name, _ in nat.Counters._fields_[1:]}}
 
     def halo_info(self) -> dict[str, int]:
