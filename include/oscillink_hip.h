@@ -105,6 +105,34 @@ int osc_append_info(osc_handle h, int32_t* route, int64_t* new_rows, int64_t* me
                     double* score_ms, double* merge_ms, double* back_ms, int64_t* merge_hits, int64_t* scan_bytes,
                     int32_t* denied);
 
+/* A NEW handle over the rows of `base` that `ids` (n entries, any order, duplicates allowed, each in [0, N)) does not name,
+ * in order and renumbered densely, with base's creation parameters (k as requested, row_cap, deterministic, seed, device)
+ * and lambdas; gates, psi, chain and U are those of a newly created handle (U = Y).  It replaces the reference's only way to
+ * drop an anchor, a new OscillinkLattice.__init__ (lattice.py:33-110) over the reduced anchors.  base is only read -- the
+ * kept anchors travel device to device, gathered from its internal row order, no anchor crosses the bus -- and is left as
+ * it was whatever happens; the caller destroys it.  OSC_E_INVALID for an id out of range or ids that name every row.  Not in
+ * the reference.
+ *   mode 0: the planner decides (oscillink_amd/csrc/remove_plan.hpp);
+ *   mode 1: incremental -- a kept row whose list names no removed row keeps its list with the ids renumbered; the rows that
+ *           lost a member (and those with a member clipped at 0 or a non-finite row: the redo set) are scored against all
+ *           N - M columns in the arithmetic base's list values come from (the score family); then the graph is assembled
+ *           from the lists as in any build.  The lists are those of a build of the kept anchors in the same score family.
+ *           OSC_E_UNSUPPORTED with the reason in osc_last_error(NULL) when base cannot seed it: no kept lists (osc_set_csr
+ *           graph, never built), a communicator, fewer than two rows left, an effective k that changes with the row count,
+ *           k > 128, butterfly-scored lists wider than 1536 columns or mixed with MFMA-scored fallback rows;
+ *   mode 2: a plain build of the kept anchors.
+ * A base with an injected graph (osc_set_csr) is refused in every mode.  Seam: osc_graph.hip build_graph_once takes its
+ * removed branch iff the handle under construction carries the seed; an ordinary osc_create / osc_rebuild_graph never
+ * does. */
+int osc_create_removed(osc_handle base, const int32_t* ids, int64_t n, int32_t mode, osc_handle* out);
+/* How a handle came to be: route 0 = not by osc_create_removed, 1 = incremental, 2 = rebuild; removed_rows = M (distinct
+ * ids); kept_rows = rows whose lists were kept (renumbered); redo_rows = rows recomputed; family as in osc_append_info; the
+ * incremental route's times in ms (scores + selection on the device / graph assembly); denied = why the planner did not
+ * take the incremental route (0 = it did, or mode 2; AppendDenied in append_plan.hpp, and 9 = fewer than two rows left).
+ * Any pointer may be NULL. */
+int osc_remove_info(osc_handle h, int32_t* route, int64_t* removed_rows, int64_t* kept_rows, int64_t* redo_rows, int32_t* family,
+                    double* score_ms, double* back_ms, int32_t* denied);
+
 /* rebuild_graph (lattice.py:760-801) */
 int osc_rebuild_graph(osc_handle h, int32_t k, float row_cap, int32_t deterministic, int64_t seed);
 

@@ -171,12 +171,14 @@ int osc_device_synchronize(int32_t device) {
 const char* osc_last_error(osc_handle h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
 // osc_create, and osc_create_appended's way through it (sd != nullptr: Y holds the sd->n_new NEW rows; the first sd->n_old
-// rows come from the base's device copy, gathered back to API order into this handle's row pitch)
+// rows come from the base's device copy, gathered back to API order into this handle's row pitch), and
+// osc_create_removed's (rs != nullptr: no host anchors at all; the N rows are the base's kept rows, gathered likewise)
 static int create_handle(const float* Y, int64_t N, int32_t D, int32_t k, float row_cap, int32_t deterministic, int64_t seed,
-                         int32_t device, int32_t build, osc_handle* out, const osc_lattice::AppendSeed* sd) {
+                         int32_t device, int32_t build, osc_handle* out, const osc_lattice::AppendSeed* sd,
+                         const osc_lattice::RemoveSeed* rs = nullptr) {
   if (!out) return OSC_E_INVALID;
   *out = nullptr;
-  if (!Y || N < 1 || D < 1 || k < 1 || N >= (int64_t)1 << 31) {
+  if ((!Y && !rs) || N < 1 || D < 1 || k < 1 || N >= (int64_t)1 << 31) {
     g_create_error = "osc_create: need Y != NULL, 1 <= N < 2^31, D >= 1, k >= 1";
     return OSC_E_INVALID;
   }
@@ -262,6 +264,25 @@ static int create_handle(const float* Y, int64_t N, int32_t D, int32_t k, float 
       build_graph(*h, nullptr);  // (an exception ends the handle under construction with it)
       h->append_seed = nullptr;
       if (h->append.route == 0) h->append.route = host::kRouteRebuild;
+    } else if (rs != nullptr) {
+      const osc_lattice& b = *rs->base;
+      {
+        DevBuf<int32_t> old_of_new, from;
+        old_of_new.alloc((size_t)N);
+        from.alloc((size_t)N);
+        HIP_CHECK(hipMemcpyAsync(old_of_new.p, rs->old_of_new.data(), (size_t)N * 4, hipMemcpyHostToDevice, h->stream));
+        launch_remove_gather_index(old_of_new.p, b.perm_h.empty() ? nullptr : b.inv_d.p, N, from.p, h->stream);
+        launch_append_gather_rows(h->Y.p, h->ld, b.Y.p, b.ld, from.p, N, h->dcols, h->stream);
+        sync(*h);  // (the gather has read the two index arrays before they go back to the pool, whatever the build does)
+      }
+      host::changed(h->derived, host::Input::anchors);
+      reset_u_to_y(*h);
+      h->lamG = b.lamG, h->lamC = b.lamC, h->lamQ = b.lamQ;
+      h->removed.removed_rows = b.N - N;
+      h->remove_seed = rs->seed_lists ? rs : nullptr;  // (else: a plain build of the kept anchors)
+      build_graph(*h, nullptr);  // (an exception ends the handle under construction with it)
+      h->remove_seed = nullptr;
+      if (h->removed.route == 0) h->removed.route = host::kRouteRebuild;
     } else if (build) {
       build_graph(*h, Y);
     } else {
@@ -347,6 +368,78 @@ int osc_append_info(osc_handle h, int32_t* route, int64_t* new_rows, int64_t* me
     if (merge_hits) *merge_hits = a.merge_hits;
     if (scan_bytes) *scan_bytes = a.scan_bytes;
     if (denied) *denied = a.denied;
+  });
+}
+
+int osc_create_removed(osc_handle base, const int32_t* ids, int64_t n, int32_t mode, osc_handle* out) {
+  if (!out) return OSC_E_INVALID;
+  *out = nullptr;
+  if (!base || !ids || n < 1 || mode < 0 || mode > 2) {
+    g_create_error = "osc_create_removed: need a base handle, ids != NULL, n >= 1 and mode 0, 1 or 2";
+    return OSC_E_INVALID;
+  }
+  const osc_lattice& b = *base;
+  if (b.comm != nullptr) {
+    g_create_error = std::string("osc_create_removed: ") + host::remove_denied_text(host::kAppendComm);
+    return OSC_E_UNSUPPORTED;
+  }
+  osc_lattice::RemoveSeed sd;
+  int64_t M = 0;
+  try {
+    sd.new_id.resize((size_t)b.N);
+    const int32_t bad = host::remove_map(ids, n, b.N, sd.new_id.data(), &M);
+    if (bad != host::kRemoveIdsOk) {
+      g_create_error = bad == host::kRemoveIdOutOfRange ? "osc_create_removed: an id is outside [0, N)"
+                       : bad == host::kRemoveAllRows    ? "osc_create_removed: the ids name every row"
+                                                        : "osc_create_removed: bad sizes";
+      return OSC_E_INVALID;
+    }
+    sd.old_of_new.resize((size_t)(b.N - M));
+    host::remove_inverse(sd.new_id.data(), b.N, sd.old_of_new.data());
+  } catch (const std::exception& e) {
+    g_create_error = e.what();
+    return OSC_E_HIP;
+  }
+  const int32_t why = host::remove_eligible(host::RemoveInputs{b.N, M, b.D, b.k_requested, b.have_graph ? b.knn_k : 0, b.score_family,
+                                                               b.knn_fallback_rows, false});
+  if (mode == 1 && why != host::kAppendOk) {
+    g_create_error = std::string("osc_create_removed: no incremental route: ") + host::remove_denied_text(why);
+    return OSC_E_UNSUPPORTED;
+  }
+  // (an injected graph cannot be rebuilt from anchors either: it is not theirs.  A lattice that was never built has no
+  // graph to keep: modes 0 and 2 build its kept anchors)
+  if (why == host::kAppendNoLists && b.N > 1 && b.have_graph) {
+    g_create_error = std::string("osc_create_removed: ") + host::remove_denied_text(why);
+    return OSC_E_UNSUPPORTED;
+  }
+  (void)hipSetDevice(b.device);
+  if (b.stream && hipStreamSynchronize(b.stream) != hipSuccess) {  // (the base's anchors and lists are read from another stream)
+    g_create_error = "osc_create_removed: the base lattice's stream reports an error";
+    return OSC_E_HIP;
+  }
+  sd.base = base;
+  sd.forced = mode == 1;
+  sd.seed_lists = mode != 2 && why == host::kAppendOk;
+  osc_handle h = nullptr;
+  const int rc = create_handle(nullptr, b.N - M, b.D, b.k_requested, b.row_cap, b.deterministic, b.seed, b.device, 1, &h, nullptr, &sd);
+  if (rc != OSC_OK) return rc;
+  if (mode != 2 && why != host::kAppendOk) h->removed.denied = why;
+  *out = h;
+  return OSC_OK;
+}
+
+int osc_remove_info(osc_handle h, int32_t* route, int64_t* removed_rows, int64_t* kept_rows, int64_t* redo_rows, int32_t* family,
+                    double* score_ms, double* back_ms, int32_t* denied) {
+  return guarded(h, [&](L& l) {
+    const osc_lattice::RemoveInfo& r = l.removed;
+    if (route) *route = r.route;
+    if (removed_rows) *removed_rows = r.removed_rows;
+    if (kept_rows) *kept_rows = r.kept_rows;
+    if (redo_rows) *redo_rows = r.redo_rows;
+    if (family) *family = l.score_family;
+    if (score_ms) *score_ms = r.score_ms;
+    if (back_ms) *back_ms = r.back_ms;
+    if (denied) *denied = r.denied;
   });
 }
 

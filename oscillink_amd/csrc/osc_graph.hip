@@ -983,6 +983,103 @@ static bool build_graph_seeded(L& h) {
   return true;
 }
 
+// The seeded build of osc_create_removed: the handle's anchors -- the base's kept rows -- are on the
+// device in API order.  k_remove_lists writes every kept row's list at its new row with the member ids renumbered and the
+// removed members emptied; the append flags' rule "an id is missing" then marks exactly the rows that lost a member (and
+// the clipped and non-finite rows: a superset, redoing a row is always correct).  Those are scored against all columns in
+// the base's score family, chunk by chunk, and get their k best: the seeded build of an append with no new rows, hence
+// without its merge pass.  Then the back half, unchanged.  false (auto mode only): the planner expects the rebuild to be
+// no slower; nothing but scratch was written and the unseeded build runs.
+static bool build_graph_removed(L& h) {
+  const L::RemoveSeed& sd = *h.remove_seed;
+  const L& base = *sd.base;
+  const int32_t N = (int32_t)h.N, k = base.knn_k;
+  const int32_t family = base.score_family;
+  const double t0 = now_ms();
+  const int32_t ldn = (int32_t)host::append_ldn(h.D);  // (an allocated lattice: N ldn floats exist)
+  DevBuf<float> Yn, kval;
+  DevBuf<int32_t> kidx, new_id, redo_list, counts, qrows;
+  DevBuf<uint8_t> flags;
+  Yn.alloc((size_t)N * ldn);
+  launch_normalize_rows(h.Y.p, h.ld, Yn.p, ldn, N, h.D, h.stream);
+  new_id.alloc((size_t)base.N);
+  HIP_CHECK(hipMemcpyAsync(new_id.p, sd.new_id.data(), (size_t)base.N * 4, hipMemcpyHostToDevice, h.stream));
+  kval.alloc((size_t)N * k);
+  kidx.alloc((size_t)N * k);
+  launch_remove_lists(base.knn_val.p, base.knn_idx.p, base.N, k, new_id.p, kval.p, kidx.p, h.stream);
+  flags.alloc((size_t)N);
+  redo_list.alloc((size_t)N);
+  counts.alloc(2);  // redo rows, non-finite rows
+  HIP_CHECK(hipMemsetAsync(counts.p, 0, 8, h.stream));
+  launch_append_flags(Yn.p, ldn, N, N, kval.p, kidx.p, k, flags.p, redo_list.p, counts.p, h.stream);
+  int32_t hc[2] = {0, 0};
+  HIP_CHECK(hipMemcpyAsync(hc, counts.p, 8, hipMemcpyDeviceToHost, h.stream));
+  sync(h);
+  const int64_t redo = hc[0], nbad = hc[1];
+  if (!sd.forced && !host::remove_pays(family, N, redo)) {
+    h.removed.denied = host::kAppendSlower;
+    return false;
+  }
+  double score_ms = 0;
+  if (redo > 0) {  // the query list: the redo rows in ascending order
+    std::vector<int32_t> q((size_t)redo);
+    HIP_CHECK(hipMemcpyAsync(q.data(), redo_list.p, (size_t)redo * 4, hipMemcpyDeviceToHost, h.stream));
+    sync(h);
+    std::sort(q.begin(), q.end());
+    qrows.alloc((size_t)redo);
+    HIP_CHECK(hipMemcpyAsync(qrows.p, q.data(), (size_t)redo * 4, hipMemcpyHostToDevice, h.stream));
+    const int64_t budget = h.append_scratch_bytes;
+    const int64_t lds = host::append_lds(N), chunk = host::append_chunk_rows(N, budget);
+    const int64_t nchunks = host::append_chunk_count(redo, chunk);
+    DevBuf<float> Sm;
+    Sm.alloc((size_t)host::append_scratch_floats(redo, N, budget));
+    const int cus = device_cus(h.device);
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    struct Events {
+      hipEvent_t* ev;
+      ~Events() {
+        for (int i = 0; i < 2; ++i)
+          if (ev[i]) (void)hipEventDestroy(ev[i]);
+      }
+    } guard{ev};
+    HIP_CHECK(hipEventCreate(&ev[0]));
+    HIP_CHECK(hipEventCreate(&ev[1]));
+    HIP_CHECK(hipEventRecord(ev[0], h.stream));
+    for (int64_t c = 0; c < nchunks; ++c) {  // (the next chunk's scores overwrite Sm behind the select: one stream, in order)
+      int64_t b = 0, e = 0;
+      host::append_chunk_range(redo, chunk, c, b, e);
+      const int32_t mc = (int32_t)(e - b);
+      if (family == host::kFamilyMfma) launch_knn_rows_listed(Yn.p, ldn, N, qrows.p + b, mc, Sm.p, (int32_t)lds, h.stream);
+      else launch_append_scores_butterfly(Yn.p, ldn, N, qrows.p + b, mc, Sm.p, lds, cus, h.stream);
+      if (nbad > 0) launch_append_sanitize(Sm.p, lds, mc, N, h.stream);
+      launch_knn_select_listed(Sm.p, (int32_t)lds, N, k, qrows.p + b, mc, kval.p, kidx.p, h.stream);
+      if (nbad > 0) launch_append_fix_lists(Sm.p, lds, qrows.p + b, mc, k, kval.p, kidx.p, h.stream);
+    }
+    HIP_CHECK(hipEventRecord(ev[1], h.stream));
+    sync(h);  // (q, Sm and the events end here)
+    float ms = 0.f;
+    HIP_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    score_ms = ms;
+  }
+  h.knn_val.swap(kval);
+  h.knn_idx.swap(kidx);
+  h.knn_k = k;
+  h.knn_last = base.knn_last;
+  h.knn_last.k = k;
+  h.knn_fallback_rows = base.knn_fallback_rows;
+  h.score_family = family;
+  const double t3 = now_ms();
+  graph_from_lists(h, N, k);
+  sync(h);
+  h.removed.route = host::kRouteIncremental;
+  h.removed.redo_rows = redo;
+  h.removed.kept_rows = N - redo;
+  h.removed.score_ms = score_ms;
+  h.removed.back_ms = now_ms() - t3;
+  h.build_ms = now_ms() - t0;
+  return true;
+}
+
 // false: a streamed build gave up before its exact-kernel fallback (see build_graph); Y and U are on the device then
 static bool build_graph_once(L& h, const float* host_Y) {
   const double t0 = now_ms();
@@ -992,6 +1089,7 @@ static bool build_graph_once(L& h, const float* host_Y) {
   h.k_eff = std::min<int32_t>(h.k_eff, std::max<int32_t>(1, N - 1));  // lattice.py:60
   host::changed(h.derived, host::Input::graph);  // (the lists below already replace the old graph's)
   if (h.append_seed != nullptr && build_graph_seeded(h)) return true;  // (osc_create_appended alone sets the seed)
+  if (h.remove_seed != nullptr && build_graph_removed(h)) return true;  // (osc_create_removed alone sets this one)
   if (N <= 1) {  // graph.py:30-32
     upload_anchors(h, host_Y);
     alloc_ell(h, 1);

@@ -27,6 +27,8 @@
 #include "knn_gemm.hpp"
 #include "append.hpp"
 #include "append_plan.hpp"
+#include "remove.hpp"
+#include "remove_plan.hpp"
 #include "receipts.hpp"
 #include "perm.hpp"
 #include "dynamics.hpp"
@@ -147,6 +149,22 @@ struct osc_lattice {
     int32_t denied = 0;
     double score_ms = 0, merge_ms = 0, back_ms = 0;
   } append;
+  // osc_create_removed: the second seed.  remove_seed is set only while a handle is being built from
+  // the kept rows of a base (build_graph_once takes its removed branch then); removed: what osc_remove_info reports.
+  struct RemoveSeed {
+    const osc_lattice* base = nullptr;  // its anchors and lists are read, nothing of it is written
+    std::vector<int32_t> new_id;        // per base row: its row here, -1 for a removed row (host::remove_map)
+    std::vector<int32_t> old_of_new;    // per row here: its base row
+    bool forced = false;                // mode 1: the planner's threshold does not apply
+    bool seed_lists = false;            // the base's lists seed the build (else only its anchors are taken over)
+  };
+  const RemoveSeed* remove_seed = nullptr;
+  struct RemoveInfo {
+    int32_t route = 0;  // host::AppendRoute
+    int64_t removed_rows = 0, kept_rows = 0, redo_rows = 0;
+    int32_t denied = 0;
+    double score_ms = 0, back_ms = 0;
+  } removed;
   double build_ms = 0.0;
   int64_t nnz = 0;
   int32_t max_deg = 0;

@@ -1108,20 +1108,33 @@ class OscillinkLattice:
                   "osc_create_appended")
         N_new = self.N + M
         B_new = np.concatenate([self._B, np.ones(M, dtype=np.float32) if g_new is None else g_new]).astype(np.float32)
-        try:  # the carried settings go to the new handle before anything of this object changes
+        self._carry_settings_to(new_h, B_new, self._chain_nodes)
+        ids = np.arange(self.N, N_new, dtype=np.int64)
+        self._swap_handle(new_h, N_new, B_new, t0)
+        info = self.append_info()
+        self._log("append", {"rows": M, "N": self.N, "route": info["route"], "redo_rows": info["redo_rows"]})
+        return ids
+
+    def _carry_settings_to(self, new_h, B_new: np.ndarray, chain_nodes) -> None:
+        """Lambdas, psi, gates and the chain onto a handle that is to replace this object's, before anything of this object
+        changes; a failure destroys the new handle and leaves the object as it was."""
+        L = nat.lib()
+        try:
             nat.check(L.osc_set_lams(new_h, float(self.lamG), float(self.lamC), float(self.lamQ)), new_h, "osc_set_lams")
             nat.check(L.osc_set_query(new_h, nat.f32(self._psi), nat.f32(B_new)), new_h, "osc_set_query")
-            if self._chain_nodes is not None:
-                ch = np.asarray(self._chain_nodes, dtype=np.int32)
+            if chain_nodes is not None:
+                ch = np.asarray(chain_nodes, dtype=np.int32)
                 ws = None if self._chain_weights is None else np.asarray(self._chain_weights, dtype=np.float32)
                 nat.check(L.osc_set_chain(new_h, nat.i32(ch), None if ws is None else nat.f32(ws), int(ch.size),
                                           float(self.lamP)), new_h, "osc_set_chain")
         except Exception:
             L.osc_destroy(new_h)
             raise
+
+    def _swap_handle(self, new_h, N_new: int, B_new: np.ndarray, t0: float) -> None:
+        """The object becomes the lattice of `new_h` (U = Y, nothing cached); the old handle is destroyed."""
         old_h, self._h = self._h, new_h
-        L.osc_destroy(old_h)
-        ids = np.arange(self.N, N_new, dtype=np.int64)
+        nat.lib().osc_destroy(old_h)
         self.N = N_new
         self._B = B_new
         self._kneighbors = min(self._kneighbors_requested, max(1, self.N - 1))
@@ -1137,9 +1150,6 @@ class OscillinkLattice:
         self._qb_version += 1
         self._qb_key = None
         self._invalidate_cache()
-        info = self.append_info()
-        self._log("append", {"rows": M, "N": self.N, "route": info["route"], "redo_rows": info["redo_rows"]})
-        return ids
 
     def append_info(self) -> dict[str, Any]:
         """How the handle came to be (osc_append_info): route 0 = not by `append`, 1 = incremental, 2 = rebuild; the score
@@ -1153,6 +1163,74 @@ class OscillinkLattice:
                 "redo_rows": int(redo.value), "score_family": ("none", "mfma", "butterfly")[int(fam.value)],
                 "score_ms": float(sc.value), "merge_ms": float(mg.value), "back_half_ms": float(bk.value),
                 "merge_hits": int(hits.value), "merge_scan_bytes": int(scan.value), "denied": int(denied.value)}
+
+    # ------------------------------------------------------------------ remove (not in the reference)
+    def remove(self, ids, *, mode: str = "auto") -> np.ndarray:
+        """Drop the rows `ids` names (any integer array-like, any order, duplicates allowed) and return `new_id_of_old`: one
+        int64 entry per old row, its id afterwards, -1 for a removed row.  Kept rows are renumbered densely, in order.
+
+        The lattice afterwards is the one `OscillinkLattice(np.delete(Y, ids, axis=0), ...)` would be with this lattice's
+        settings applied: same graph, U = Y (the state is NOT carried over a removal), lambdas, psi and lamP kept, gates =
+        `np.delete(B, ids)`, a chain carried with its nodes renumbered (`ids` naming a chain node raises: `clear_chain()`
+        first).  Logger, callbacks, receipt secret, signature and detail modes stay.  mode "incremental" shrinks the kNN
+        lists from the kept ones and raises where that is not possible, "rebuild" builds the kept anchors from scratch on the
+        device, "auto" lets the planner choose (`remove_info()` says which).  No anchor crosses the bus.  A failure leaves
+        the lattice exactly as it was."""
+        if mode not in self._APPEND_MODES:
+            raise ValueError("mode must be 'auto', 'incremental' or 'rebuild'")
+        arr = np.asarray(ids)
+        if arr.size == 0:
+            arr = arr.astype(np.int64)
+        if not np.issubdtype(arr.dtype, np.integer):
+            raise ValueError("ids must be integers")
+        arr = arr.ravel()
+        if arr.size and (int(arr.min()) < 0 or int(arr.max()) >= self.N):
+            raise ValueError("ids out of bounds")
+        keep = np.ones(self.N, dtype=bool)
+        keep[arr.astype(np.int64)] = False
+        M = self.N - int(keep.sum())
+        new_id_of_old = np.where(keep, np.cumsum(keep) - 1, -1).astype(np.int64)
+        if M == 0:
+            return new_id_of_old
+        if M == self.N:
+            raise ValueError("ids name every row: a lattice keeps at least one")
+        chain_new = None
+        if self._chain_nodes is not None:
+            chain_new = new_id_of_old[np.asarray(self._chain_nodes, dtype=np.int64)]
+            if (chain_new < 0).any():
+                raise ValueError("ids name a node of the chain: clear_chain() first (dropping a node from a weighted path has "
+                                 "no single meaning)")
+        if getattr(self, "_has_comm", False):
+            raise nat.NativeError("remove: a lattice with a communicator cannot shrink (multi-rank handles are out of scope)")
+        gone = np.ascontiguousarray(np.nonzero(~keep)[0], dtype=np.int32)
+        L = nat.lib()
+        new_h = nat.Handle()
+        t0 = time.time()
+        nat.check(L.osc_create_removed(self._h, nat.i32(gone), int(gone.size), self._APPEND_MODES[mode], C.byref(new_h)), None,
+                  "osc_create_removed")
+        B_new = np.ascontiguousarray(self._B[keep], dtype=np.float32)
+        self._carry_settings_to(new_h, B_new, chain_new)
+        if chain_new is not None:
+            self._chain_nodes = [int(c) for c in chain_new]
+        self._swap_handle(new_h, self.N - M, B_new, t0)
+        info = self.remove_info()
+        self._log("remove", {"rows": M, "N": self.N, "route": info["route"], "redo_rows": info["redo_rows"]})
+        return new_id_of_old
+
+    def remove_info(self) -> dict[str, Any]:
+        """How the handle came to be (osc_remove_info): route 0 = not by `remove`, 1 = incremental, 2 = rebuild; the rows
+        removed, kept with their lists and recomputed; the score family of its kNN lists; the incremental route's phases in
+        ms; why the planner did not take the incremental route (0: it did, or was not asked).  It describes the creation of
+        the handle, as `append_info()` does: a later `append` starts a new handle (route 0 here), while a later
+        `rebuild_graph` keeps the handle and with it this record, although the graph is then the rebuild's."""
+        route, fam, denied = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        gone, kept, redo = (C.c_int64(0) for _ in range(3))
+        sc, bk = C.c_double(0.0), C.c_double(0.0)
+        self._call("osc_remove_info", C.byref(route), C.byref(gone), C.byref(kept), C.byref(redo), C.byref(fam), C.byref(sc),
+                   C.byref(bk), C.byref(denied))
+        return {"route": int(route.value), "removed_rows": int(gone.value), "kept_rows": int(kept.value),
+                "redo_rows": int(redo.value), "score_family": ("none", "mfma", "butterfly")[int(fam.value)],
+                "score_ms": float(sc.value), "back_half_ms": float(bk.value), "denied": int(denied.value)}
 
     # ------------------------------------------------------------------ persistence (lattice.py:582-726)
     def _provenance(self) -> str:
