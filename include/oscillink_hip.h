@@ -133,6 +133,36 @@ int osc_create_removed(osc_handle base, const int32_t* ids, int64_t n, int32_t m
 int osc_remove_info(osc_handle h, int32_t* route, int64_t* removed_rows, int64_t* kept_rows, int64_t* redo_rows, int32_t* family,
                     double* score_ms, double* back_ms, int32_t* denied);
 
+/* A NEW handle over the rows of `base` with row ids[j] replaced by row j of Ynew (M x D, row-major; ids distinct, any order,
+ * each in [0, N)), with base's creation parameters (k as requested, row_cap, deterministic, seed, device) and lambdas;
+ * gates, psi, chain and U are those of a newly created handle (U = Y).  N, the row pitch and the effective k are base's.
+ * It replaces the reference's only way to change an anchor, a new OscillinkLattice.__init__ (lattice.py:33-110) over the
+ * changed anchors.  base is only read -- its anchors travel device to device, gathered from its internal row order; only
+ * ids and Ynew cross the bus -- and is left as it was whatever happens; the caller destroys it.  OSC_E_INVALID for an id
+ * out of range or named twice.  Not in the reference.
+ *   mode 0: the planner decides (oscillink_amd/csrc/update_plan.hpp);
+ *   mode 1: incremental -- a row whose list names no replaced row keeps its list; the rows that lost a member (and those
+ *           with a member clipped at 0 or a non-finite row: the redo set) and the replaced rows are scored against all N
+ *           columns in the arithmetic base's list values come from (the score family); every other row takes a replaced
+ *           column into its list iff its new score precedes the list's worst member under (score desc, index asc) -- an
+ *           equal score wins where the replaced row's id is the lower one; then the graph is assembled from the lists as
+ *           in any build.  The lists are those of a build of the changed anchors in the same score family.
+ *           OSC_E_UNSUPPORTED with the reason in osc_last_error(NULL) when base cannot seed it: no kept lists (osc_set_csr
+ *           graph, never built), a communicator, an effective k other than the lists' length, k > 128, butterfly-scored
+ *           lists wider than 1536 columns or mixed with MFMA-scored fallback rows;
+ *   mode 2: a plain build of the changed anchors.
+ * A base with an injected graph (osc_set_csr) is refused in every mode.  Seam: osc_graph.hip build_graph_once takes its
+ * updated branch iff the handle under construction carries the seed; an ordinary osc_create / osc_rebuild_graph never
+ * does. */
+int osc_create_updated(osc_handle base, const int32_t* ids, const float* Ynew, int64_t M, int32_t mode, osc_handle* out);
+/* How a handle came to be: route 0 = not by osc_create_updated, 1 = incremental, 2 = rebuild; replaced_rows = M;
+ * merged_rows = rows that kept their lists and scanned the replaced columns; redo_rows = rows recomputed other than the
+ * replaced ones; family as in osc_append_info; the incremental route's times in ms (scores + selection on the device /
+ * the merge scans / graph assembly); merge_hits = list entries the merge took; denied = why the planner did not take the
+ * incremental route (0 = it did, or mode 2; AppendDenied in append_plan.hpp).  Any pointer may be NULL. */
+int osc_update_info(osc_handle h, int32_t* route, int64_t* replaced_rows, int64_t* merged_rows, int64_t* redo_rows, int32_t* family,
+                    double* score_ms, double* merge_ms, double* back_ms, int64_t* merge_hits, int32_t* denied);
+
 /* rebuild_graph (lattice.py:760-801) */
 int osc_rebuild_graph(osc_handle h, int32_t k, float row_cap, int32_t deterministic, int64_t seed);
 
@@ -447,6 +477,12 @@ int osc_corpus_append(osc_corpus_handle h, const float* Y, int64_t M, int64_t* f
 /* Tombstones the n rows ids[]: other rows keep their ids, removed ids are not reused.  An id outside [0, N) is OSC_E_INVALID
  * and nothing changes; an id already removed is ignored.  *newly_removed = how many were live. */
 int osc_corpus_remove(osc_corpus_handle h, const int32_t* ids, int64_t n, int64_t* newly_removed);
+/* Row ids[j] gets the vector Y[j] (M x D, row-major, finite) for j < M: the rows are uploaded once and one kernel writes
+ * Y[ids[j]] and Yn[ids[j]], normalised with osc_corpus_append's arithmetic, so every later answer is byte for byte that of
+ * a corpus created over the changed rows.  Ids, tombstones, the capacity and an armed filter's meaning stay.  An id outside
+ * [0, N), an id of a removed row, an id named twice or a non-finite row is OSC_E_INVALID and nothing changes.  Synchronises
+ * before it returns.   */
+int osc_corpus_update(osc_corpus_handle h, const int32_t* ids, const float* Y, int64_t M);
 /* Drops the tombstoned rows, keeping the order of the others, and renumbers densely: Y and Yn are gathered (Yn is copied, not
  * recomputed) into fresh buffers of the live rows rounded up to 128.  new_id_of_old_or_null: N entries, the new id or -1.
  * *N_new = the new N (= the live rows).  An armed filter is dropped. */

@@ -67,6 +67,8 @@ SIGNATURES = {
                                   c_i32p]),
     "osc_create_removed": (C.c_int, [Handle, c_i32p, C.c_int64, C.c_int32, C.POINTER(Handle)]),
     "osc_remove_info": (C.c_int, [Handle, c_i32p, c_i64p, c_i64p, c_i64p, c_i32p, c_f64p, c_f64p, c_i32p]),
+    "osc_create_updated": (C.c_int, [Handle, c_i32p, c_f32p, C.c_int64, C.c_int32, C.POINTER(Handle)]),
+    "osc_update_info": (C.c_int, [Handle, c_i32p, c_i64p, c_i64p, c_i64p, c_i32p, c_f64p, c_f64p, c_f64p, c_i64p, c_i32p]),
     "osc_rebuild_graph": (C.c_int, [Handle, C.c_int32, C.c_float, C.c_int32, C.c_int64]),
     "osc_graph_stats": (C.c_int, [Handle, c_i64p, c_i32p, c_f64p]),
     "osc_build_info": (C.c_int, [Handle, c_i32p, c_i32p, c_i64p]),
@@ -118,6 +120,7 @@ SIGNATURES = {
                                    c_f32p, c_f32p, C.c_int64, c_i64p]),
     "osc_corpus_append": (C.c_int, [Handle, c_f32p, C.c_int64, c_i64p]),
     "osc_corpus_remove": (C.c_int, [Handle, c_i32p, C.c_int64, c_i64p]),
+    "osc_corpus_update": (C.c_int, [Handle, c_i32p, c_f32p, C.c_int64]),
     "osc_corpus_compact": (C.c_int, [Handle, c_i32p, c_i64p]),
     "osc_corpus_rows": (C.c_int, [Handle, c_i64p, c_i64p, c_i64p]),
     "osc_corpus_get_live": (C.c_int, [Handle, c_u32p]),

@@ -401,6 +401,37 @@ class Corpus:
         self._alive = None
         return int(gone.value)
 
+    def update(self, ids, Ynew) -> None:
+        """Row `ids[j]` gets the vector `Ynew[j]` (ids: distinct live ids; Ynew: (M, D), finite).  The rows are uploaded once
+        and normalised on the device with `append`'s arithmetic, so every later answer is byte for byte that of a fresh
+        `Corpus` over the changed rows.  Ids, tombstones, the capacity and an armed filter's meaning stay.  ValueError before
+        anything changes for an id outside [0, N), an id that names a removed row, an id named twice, a non-finite row or
+        a bad shape."""
+        if self._h is None:
+            raise ValueError("Corpus is closed")
+        r = np.asarray(ids).reshape(-1)
+        if r.size and not np.issubdtype(r.dtype, np.integer):
+            raise ValueError("ids must be integers")
+        r = r.astype(np.int64)
+        Yn = np.asarray(Ynew)
+        if Yn.ndim != 2 or Yn.shape[1] != self.D or Yn.shape[0] != r.size:
+            raise ValueError(f"Ynew must be a ({r.size}, {self.D}) array, got shape {Yn.shape}")
+        if r.size and (r.min() < 0 or r.max() >= self.N):
+            bad = int(r[(r < 0) | (r >= self.N)][0])
+            raise ValueError(f"update: id {bad} is outside [0, {self.N})")
+        if np.unique(r).size != r.size:
+            raise ValueError("update: an id is named twice")
+        if r.size and not self._alive_mask()[r].all():
+            bad = int(r[~self._alive_mask()[r]][0])
+            raise ValueError(f"update: id {bad} names a removed row")
+        Yc = np.ascontiguousarray(Yn, dtype=np.float32)
+        if not np.all(np.isfinite(Yc)):
+            raise ValueError("Ynew must be finite")
+        if r.size == 0:
+            return
+        r32 = np.ascontiguousarray(r, dtype=np.int32)
+        self._call("osc_corpus_update", nat.i32(r32), nat.f32(Yc), int(r32.size))
+
     def compact(self) -> np.ndarray:
         """Drops the removed rows, keeps the order of the others and renumbers them densely (a device gather of Y and Yn
         into fresh buffers).  Afterwards N == n_live.  Returns new_id_of_old: int64, one entry per old row, -1 for a

@@ -172,10 +172,13 @@ const char* osc_last_error(osc_handle h) { return h ? h->err.c_str() : g_create_
 
 // osc_create, and osc_create_appended's way through it (sd != nullptr: Y holds the sd->n_new NEW rows; the first sd->n_old
 // rows come from the base's device copy, gathered back to API order into this handle's row pitch), and
-// osc_create_removed's (rs != nullptr: no host anchors at all; the N rows are the base's kept rows, gathered likewise)
+// osc_create_removed's (rs != nullptr: no host anchors at all; the N rows are the base's kept rows, gathered likewise), and
+// osc_create_updated's (us != nullptr: Y holds the replaced rows' new vectors in the order of upd_ids; all N rows of the
+// base are gathered likewise, then those rows are overwritten on the device)
 static int create_handle(const float* Y, int64_t N, int32_t D, int32_t k, float row_cap, int32_t deterministic, int64_t seed,
                          int32_t device, int32_t build, osc_handle* out, const osc_lattice::AppendSeed* sd,
-                         const osc_lattice::RemoveSeed* rs = nullptr) {
+                         const osc_lattice::RemoveSeed* rs = nullptr, const osc_lattice::UpdateSeed* us = nullptr,
+                         const int32_t* upd_ids = nullptr) {
   if (!out) return OSC_E_INVALID;
   *out = nullptr;
   if ((!Y && !rs) || N < 1 || D < 1 || k < 1 || N >= (int64_t)1 << 31) {
@@ -283,6 +286,28 @@ static int create_handle(const float* Y, int64_t N, int32_t D, int32_t k, float 
       build_graph(*h, nullptr);  // (an exception ends the handle under construction with it)
       h->remove_seed = nullptr;
       if (h->removed.route == 0) h->removed.route = host::kRouteRebuild;
+    } else if (us != nullptr) {
+      const osc_lattice& b = *us->base;
+      const int64_t M = (int64_t)us->ids.size();
+      {
+        DevBuf<float> fresh;
+        DevBuf<int32_t> at;
+        fresh.alloc((size_t)M * D);
+        at.alloc((size_t)M);
+        HIP_CHECK(hipMemcpyAsync(fresh.p, Y, (size_t)M * D * 4, hipMemcpyHostToDevice, h->stream));
+        HIP_CHECK(hipMemcpyAsync(at.p, upd_ids, (size_t)M * 4, hipMemcpyHostToDevice, h->stream));
+        launch_append_gather_rows(h->Y.p, h->ld, b.Y.p, b.ld, b.perm_h.empty() ? nullptr : b.inv_d.p, N, h->dcols, h->stream);
+        launch_update_scatter_rows(h->Y.p, h->ld, fresh.p, D, h->dcols, at.p, M, h->stream);
+        sync(*h);  // (the scatter has read the two uploads before they go back to the pool, whatever the build does)
+      }
+      host::changed(h->derived, host::Input::anchors);
+      reset_u_to_y(*h);
+      h->lamG = b.lamG, h->lamC = b.lamC, h->lamQ = b.lamQ;
+      h->updated.replaced_rows = M;
+      h->update_seed = us->seed_lists ? us : nullptr;  // (else: a plain build of the changed anchors)
+      build_graph(*h, nullptr);  // (an exception ends the handle under construction with it)
+      h->update_seed = nullptr;
+      if (h->updated.route == 0) h->updated.route = host::kRouteRebuild;
     } else if (build) {
       build_graph(*h, Y);
     } else {
@@ -440,6 +465,79 @@ int osc_remove_info(osc_handle h, int32_t* route, int64_t* removed_rows, int64_t
     if (score_ms) *score_ms = r.score_ms;
     if (back_ms) *back_ms = r.back_ms;
     if (denied) *denied = r.denied;
+  });
+}
+
+int osc_create_updated(osc_handle base, const int32_t* ids, const float* Ynew, int64_t M, int32_t mode, osc_handle* out) {
+  if (!out) return OSC_E_INVALID;
+  *out = nullptr;
+  if (!base || !ids || !Ynew || M < 1 || mode < 0 || mode > 2) {
+    g_create_error = "osc_create_updated: need a base handle, ids != NULL, Ynew != NULL, M >= 1 and mode 0, 1 or 2";
+    return OSC_E_INVALID;
+  }
+  const osc_lattice& b = *base;
+  if (b.comm != nullptr) {
+    g_create_error = std::string("osc_create_updated: ") + host::append_denied_text(host::kAppendComm);
+    return OSC_E_UNSUPPORTED;
+  }
+  osc_lattice::UpdateSeed sd;
+  try {
+    sd.keep.resize((size_t)b.N);
+    const int32_t bad = host::update_ids(ids, M, b.N, sd.keep.data());
+    if (bad != host::kUpdateIdsOk) {
+      g_create_error = bad == host::kUpdateIdOutOfRange  ? "osc_create_updated: an id is outside [0, N)"
+                       : bad == host::kUpdateIdDuplicate ? "osc_create_updated: an id is named twice"
+                                                         : "osc_create_updated: bad sizes";
+      return OSC_E_INVALID;
+    }
+    sd.ids.assign(ids, ids + M);
+    std::sort(sd.ids.begin(), sd.ids.end());
+  } catch (const std::exception& e) {
+    g_create_error = e.what();
+    return OSC_E_HIP;
+  }
+  const int32_t why = host::update_eligible(host::UpdateInputs{b.N, M, b.D, b.k_requested, b.have_graph ? b.knn_k : 0, b.score_family,
+                                                               b.knn_fallback_rows, false});
+  if (mode == 1 && why != host::kAppendOk) {
+    g_create_error = std::string("osc_create_updated: no incremental route: ") + host::append_denied_text(why);
+    return OSC_E_UNSUPPORTED;
+  }
+  // (an injected graph cannot be rebuilt from anchors either: it is not theirs.  A lattice that was never built has no
+  // graph to keep: modes 0 and 2 build its changed anchors)
+  if (why == host::kAppendNoLists && b.N > 1 && b.have_graph) {
+    g_create_error = std::string("osc_create_updated: ") + host::append_denied_text(why);
+    return OSC_E_UNSUPPORTED;
+  }
+  (void)hipSetDevice(b.device);
+  if (b.stream && hipStreamSynchronize(b.stream) != hipSuccess) {  // (the base's anchors and lists are read from another stream)
+    g_create_error = "osc_create_updated: the base lattice's stream reports an error";
+    return OSC_E_HIP;
+  }
+  sd.base = base;
+  sd.forced = mode == 1;
+  sd.seed_lists = mode != 2 && why == host::kAppendOk;
+  osc_handle h = nullptr;
+  const int rc = create_handle(Ynew, b.N, b.D, b.k_requested, b.row_cap, b.deterministic, b.seed, b.device, 1, &h, nullptr, nullptr, &sd, ids);
+  if (rc != OSC_OK) return rc;
+  if (mode != 2 && why != host::kAppendOk) h->updated.denied = why;
+  *out = h;
+  return OSC_OK;
+}
+
+int osc_update_info(osc_handle h, int32_t* route, int64_t* replaced_rows, int64_t* merged_rows, int64_t* redo_rows, int32_t* family,
+                    double* score_ms, double* merge_ms, double* back_ms, int64_t* merge_hits, int32_t* denied) {
+  return guarded(h, [&](L& l) {
+    const osc_lattice::UpdateInfo& u = l.updated;
+    if (route) *route = u.route;
+    if (replaced_rows) *replaced_rows = u.replaced_rows;
+    if (merged_rows) *merged_rows = u.merged_rows;
+    if (redo_rows) *redo_rows = u.redo_rows;
+    if (family) *family = l.score_family;
+    if (score_ms) *score_ms = u.score_ms;
+    if (merge_ms) *merge_ms = u.merge_ms;
+    if (back_ms) *back_ms = u.back_ms;
+    if (merge_hits) *merge_hits = u.merge_hits;
+    if (denied) *denied = u.denied;
   });
 }
 

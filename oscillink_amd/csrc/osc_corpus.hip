@@ -1494,6 +1494,37 @@ int osc_corpus_remove(osc_corpus_handle h, const int32_t* ids, int64_t n, int64_
   });
 }
 
+int osc_corpus_update(osc_corpus_handle h, const int32_t* ids, const float* Y, int64_t M) {
+  return corpus_guarded(h, [&](osc_corpus& c) {
+    if (M < 0 || (M > 0 && (!ids || !Y))) throw Invalid("osc_corpus_update: need M >= 0, ids != NULL and Y != NULL");
+    if (M == 0) return;
+    {  // everything that can fail comes before the handle changes
+      std::vector<int32_t> keep((size_t)c.N);
+      const int32_t bad = host::update_ids(ids, M, c.N, keep.data());
+      if (bad == host::kUpdateIdOutOfRange) {
+        for (int64_t t = 0; t < M; ++t)
+          if (ids[t] < 0 || ids[t] >= c.N)
+            throw Invalid("osc_corpus_update: id " + std::to_string(ids[t]) + " is outside [0, " + std::to_string(c.N) + ")");
+      }
+      if (bad == host::kUpdateIdDuplicate) throw Invalid("osc_corpus_update: an id is named twice");
+      if (bad != host::kUpdateIdsOk) throw Invalid("osc_corpus_update: bad sizes");
+    }
+    for (int64_t t = 0; t < M; ++t)
+      if (!host::store_get(c.live.data(), ids[t]))
+        throw Invalid("osc_corpus_update: id " + std::to_string(ids[t]) + " names a removed row");
+    for (int64_t t = 0; t < M * c.D; ++t)
+      if (!std::isfinite(Y[t])) throw Invalid("osc_corpus_update: row " + std::to_string(t / c.D) + " of Y is not finite");
+    DevBuf<float> rows;
+    DevBuf<int32_t> at;
+    rows.alloc((size_t)M * c.D);
+    at.alloc((size_t)M);
+    HIP_CHECK(hipMemcpyAsync(rows.p, Y, (size_t)M * c.D * 4, hipMemcpyHostToDevice, c.stream));
+    HIP_CHECK(hipMemcpyAsync(at.p, ids, (size_t)M * 4, hipMemcpyHostToDevice, c.stream));
+    launch_corpus_update_rows(rows.p, c.D, at.p, M, c.Y.p, c.Yn.p, c.ldn, c.stream);
+    HIP_CHECK(hipStreamSynchronize(c.stream));
+  });
+}
+
 int osc_corpus_compact(osc_corpus_handle h, int32_t* new_id_of_old_or_null, int64_t* N_new) {
   return corpus_guarded(h, [&](osc_corpus& c) {
     if (c.n_live == 0) throw Invalid("the corpus has no live rows");

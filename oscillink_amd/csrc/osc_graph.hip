@@ -1080,6 +1080,129 @@ static bool build_graph_removed(L& h) {
   return true;
 }
 
+// The seeded build of osc_create_updated: the handle's anchors -- the base's rows with the replaced
+// ones overwritten -- are on the device in API order.  k_update_lists copies the base's lists with every member that names
+// a replaced row emptied and the replaced rows' own lists empty; the append flags' rule "an id is missing" then marks the
+// rows that lost a member and the replaced rows (and the clipped and non-finite rows: a superset, redoing a row is always
+// correct).  The query list -- the redo rows other than the replaced ones, ascending, then the replaced rows -- is scored
+// against all columns in the base's score family, chunk by chunk; each chunk's rows get their k best, and every row outside
+// the redo set merges the chunk's replaced columns into its list (k_update_merge: an equal score and a lower index wins).
+// Then the back half, unchanged.  false (auto mode only): the planner expects the rebuild to be no slower; nothing but
+// scratch was written and the unseeded build runs.
+static bool build_graph_updated(L& h) {
+  const L::UpdateSeed& sd = *h.update_seed;
+  const L& base = *sd.base;
+  const int32_t N = (int32_t)h.N, k = base.knn_k;
+  const int32_t family = base.score_family;
+  const int64_t M = (int64_t)sd.ids.size();
+  const double t0 = now_ms();
+  // (auto mode: M alone over the threshold decides on the host, before any device work)
+  if (!sd.forced && !host::update_pays(family, N, M, 0)) {
+    h.updated.denied = host::kAppendSlower;
+    return false;
+  }
+  const int32_t ldn = (int32_t)host::append_ldn(h.D);  // (an allocated lattice: N ldn floats exist)
+  DevBuf<float> Yn, kval;
+  DevBuf<int32_t> kidx, keep, redo_list, counts, qrows;
+  DevBuf<uint8_t> flags;
+  Yn.alloc((size_t)N * ldn);
+  launch_normalize_rows(h.Y.p, h.ld, Yn.p, ldn, N, h.D, h.stream);
+  keep.alloc((size_t)N);
+  HIP_CHECK(hipMemcpyAsync(keep.p, sd.keep.data(), (size_t)N * 4, hipMemcpyHostToDevice, h.stream));
+  kval.alloc((size_t)N * k);
+  kidx.alloc((size_t)N * k);
+  launch_update_lists(base.knn_val.p, base.knn_idx.p, N, k, keep.p, kval.p, kidx.p, h.stream);
+  flags.alloc((size_t)N);
+  redo_list.alloc((size_t)N);
+  counts.alloc(3);  // redo rows (the replaced ones among them), non-finite rows, merge hits
+  HIP_CHECK(hipMemsetAsync(counts.p, 0, 12, h.stream));
+  launch_append_flags(Yn.p, ldn, N, N, kval.p, kidx.p, k, flags.p, redo_list.p, counts.p, h.stream);
+  int32_t hc[3] = {0, 0, 0};
+  HIP_CHECK(hipMemcpyAsync(hc, counts.p, 8, hipMemcpyDeviceToHost, h.stream));
+  sync(h);
+  const int64_t flagged = hc[0], nbad = hc[1], redo = flagged - M;  // (a replaced row's list is empty: always flagged)
+  if (redo < 0) throw std::runtime_error("build_graph_updated: a replaced row was not flagged");
+  if (!sd.forced && !host::update_pays(family, N, M, redo)) {
+    h.updated.denied = host::kAppendSlower;
+    return false;
+  }
+  // the query list: the redo rows other than the replaced ones in ascending order, then the replaced rows
+  std::vector<int32_t> q((size_t)flagged);
+  HIP_CHECK(hipMemcpyAsync(q.data(), redo_list.p, (size_t)flagged * 4, hipMemcpyDeviceToHost, h.stream));
+  sync(h);
+  q.erase(std::remove_if(q.begin(), q.end(), [&](int32_t r) { return sd.keep[(size_t)r] < 0; }), q.end());
+  if ((int64_t)q.size() != redo) throw std::runtime_error("build_graph_updated: the redo list and its count disagree");
+  std::sort(q.begin(), q.end());
+  q.insert(q.end(), sd.ids.begin(), sd.ids.end());
+  const int64_t nq = (int64_t)q.size();
+  qrows.alloc((size_t)nq);
+  HIP_CHECK(hipMemcpyAsync(qrows.p, q.data(), (size_t)nq * 4, hipMemcpyHostToDevice, h.stream));
+  const int64_t budget = h.append_scratch_bytes;
+  const int64_t lds = host::append_lds(N), chunk = host::append_chunk_rows(N, budget);
+  const int64_t nchunks = host::append_chunk_count(nq, chunk);
+  DevBuf<float> Sm;
+  Sm.alloc((size_t)host::append_scratch_floats(nq, N, budget));
+  const int cus = device_cus(h.device);
+  // the phases' times come from events: three per chunk, read once after the loop (no host wait inside it)
+  struct Events {
+    std::vector<hipEvent_t> ev;
+    ~Events() {
+      for (auto e : ev) (void)hipEventDestroy(e);
+    }
+    void mark(hipStream_t s) {
+      hipEvent_t e = nullptr;
+      HIP_CHECK(hipEventCreate(&e));
+      ev.push_back(e);
+      HIP_CHECK(hipEventRecord(e, s));
+    }
+  } marks;
+  marks.ev.reserve((size_t)nchunks * 3);
+  for (int64_t c = 0; c < nchunks; ++c) {
+    int64_t b = 0, e = 0, nb = 0, ne = 0;
+    host::append_chunk_range(nq, chunk, c, b, e);
+    const int32_t mc = (int32_t)(e - b);
+    marks.mark(h.stream);
+    if (family == host::kFamilyMfma) launch_knn_rows_listed(Yn.p, ldn, N, qrows.p + b, mc, Sm.p, (int32_t)lds, h.stream);
+    else launch_append_scores_butterfly(Yn.p, ldn, N, qrows.p + b, mc, Sm.p, lds, cus, h.stream);
+    if (nbad > 0) launch_append_sanitize(Sm.p, lds, mc, N, h.stream);
+    launch_knn_select_listed(Sm.p, (int32_t)lds, N, k, qrows.p + b, mc, kval.p, kidx.p, h.stream);
+    if (nbad > 0) launch_append_fix_lists(Sm.p, lds, qrows.p + b, mc, k, kval.p, kidx.p, h.stream);
+    marks.mark(h.stream);
+    host::update_chunk_replaced_part(redo, b, e, nb, ne);  // (block row r of the chunk scores column qrows[b + r])
+    launch_update_merge(Sm.p, lds, (int32_t)nb, (int32_t)ne, qrows.p + b, N, flags.p, k, kval.p, kidx.p, counts.p + 2, h.stream);
+    marks.mark(h.stream);  // (the next chunk's scores overwrite Sm behind the merge: one stream, in order)
+  }
+  HIP_CHECK(hipMemcpyAsync(hc + 2, counts.p + 2, 4, hipMemcpyDeviceToHost, h.stream));
+  sync(h);  // (q, Sm and the events end here)
+  double score_ms = 0, merge_ms = 0;
+  for (size_t i = 0; i + 2 < marks.ev.size(); i += 3) {
+    float a = 0.f, m = 0.f;
+    HIP_CHECK(hipEventElapsedTime(&a, marks.ev[i], marks.ev[i + 1]));
+    HIP_CHECK(hipEventElapsedTime(&m, marks.ev[i + 1], marks.ev[i + 2]));
+    score_ms += a;
+    merge_ms += m;
+  }
+  h.knn_val.swap(kval);
+  h.knn_idx.swap(kidx);
+  h.knn_k = k;
+  h.knn_last = base.knn_last;
+  h.knn_last.k = k;
+  h.knn_fallback_rows = base.knn_fallback_rows;
+  h.score_family = family;
+  const double t3 = now_ms();
+  graph_from_lists(h, N, k);
+  sync(h);
+  h.updated.route = host::kRouteIncremental;
+  h.updated.redo_rows = redo;
+  h.updated.merged_rows = N - flagged;
+  h.updated.merge_hits = hc[2];
+  h.updated.score_ms = score_ms;
+  h.updated.merge_ms = merge_ms;
+  h.updated.back_ms = now_ms() - t3;
+  h.build_ms = now_ms() - t0;
+  return true;
+}
+
 // false: a streamed build gave up before its exact-kernel fallback (see build_graph); Y and U are on the device then
 static bool build_graph_once(L& h, const float* host_Y) {
   const double t0 = now_ms();
@@ -1090,6 +1213,7 @@ static bool build_graph_once(L& h, const float* host_Y) {
   host::changed(h.derived, host::Input::graph);  // (the lists below already replace the old graph's)
   if (h.append_seed != nullptr && build_graph_seeded(h)) return true;  // (osc_create_appended alone sets the seed)
   if (h.remove_seed != nullptr && build_graph_removed(h)) return true;  // (osc_create_removed alone sets this one)
+  if (h.update_seed != nullptr && build_graph_updated(h)) return true;  // (osc_create_updated alone sets this one)
   if (N <= 1) {  // graph.py:30-32
     upload_anchors(h, host_Y);
     alloc_ell(h, 1);

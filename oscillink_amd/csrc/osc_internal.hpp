@@ -29,6 +29,8 @@
 #include "append_plan.hpp"
 #include "remove.hpp"
 #include "remove_plan.hpp"
+#include "update.hpp"
+#include "update_plan.hpp"
 #include "receipts.hpp"
 #include "perm.hpp"
 #include "dynamics.hpp"
@@ -165,6 +167,22 @@ struct osc_lattice {
     int32_t denied = 0;
     double score_ms = 0, back_ms = 0;
   } removed;
+  // osc_create_updated: the third seed.  update_seed is set only while a handle is being built from
+  // a base with some rows replaced (build_graph_once takes its updated branch then); updated: what osc_update_info reports.
+  struct UpdateSeed {
+    const osc_lattice* base = nullptr;  // its anchors and lists are read, nothing of it is written
+    std::vector<int32_t> keep;          // per row: its own id, -1 for a replaced row (host::update_ids)
+    std::vector<int32_t> ids;           // the replaced rows, ascending
+    bool forced = false;                // mode 1: the planner's threshold does not apply
+    bool seed_lists = false;            // the base's lists seed the build (else only its anchors are taken over)
+  };
+  const UpdateSeed* update_seed = nullptr;
+  struct UpdateInfo {
+    int32_t route = 0;  // host::AppendRoute
+    int64_t replaced_rows = 0, merged_rows = 0, redo_rows = 0, merge_hits = 0;
+    int32_t denied = 0;
+    double score_ms = 0, merge_ms = 0, back_ms = 0;
+  } updated;
   double build_ms = 0.0;
   int64_t nnz = 0;
   int32_t max_deg = 0;

@@ -1232,6 +1232,78 @@ class OscillinkLattice:
                 "redo_rows": int(redo.value), "score_family": ("none", "mfma", "butterfly")[int(fam.value)],
                 "score_ms": float(sc.value), "back_half_ms": float(bk.value), "denied": int(denied.value)}
 
+    # ------------------------------------------------------------------ update (not in the reference)
+    def update(self, ids, Ynew: np.ndarray, gates: Optional[np.ndarray] = None, *, mode: str = "auto") -> np.ndarray:
+        """Row `ids[j]` becomes `Ynew[j]` (ids: distinct integers in [0, N), any order; Ynew: M x D) and `ids` comes back as
+        int64.  No row moves: N, the row pitch, the effective k and every id stay.
+
+        The lattice afterwards is the one `OscillinkLattice(Y2, ...)` would be, `Y2 = Y.copy(); Y2[ids] = Ynew`, with this
+        lattice's settings applied: same graph, U = Y2 (the state is NOT carried over an update), lambdas, psi, chain and lamP
+        kept (a replaced row may be a chain node: the path prior depends on node identity only), gates unchanged except
+        `B[ids] = gates` where `gates` (length M) is given.  Logger, callbacks, receipt secret, signature and detail modes
+        stay.  mode "incremental" keeps the kNN lists that name no replaced row and raises where that is not possible,
+        "rebuild" builds the changed anchors from scratch on the device, "auto" lets the planner choose (`update_info()`
+        says which).  Only `ids` and `Ynew` cross the bus.  A failure leaves the lattice exactly as it was."""
+        if mode not in self._APPEND_MODES:
+            raise ValueError("mode must be 'auto', 'incremental' or 'rebuild'")
+        arr = np.asarray(ids)
+        if arr.size == 0:
+            arr = arr.astype(np.int64)
+        if not np.issubdtype(arr.dtype, np.integer):
+            raise ValueError("ids must be integers")
+        arr = arr.ravel().astype(np.int64)
+        if not isinstance(Ynew, np.ndarray) or Ynew.ndim != 2:
+            raise ValueError("Ynew must be a 2D numpy array")
+        if Ynew.shape[1] != self.D:
+            raise ValueError("Ynew column count mismatch D")
+        M = int(Ynew.shape[0])
+        if arr.size != M:
+            raise ValueError("ids length mismatch the rows of Ynew")
+        if M and (int(arr.min()) < 0 or int(arr.max()) >= self.N):
+            raise ValueError("ids out of bounds")
+        if np.unique(arr).size != M:
+            raise ValueError("ids name a row twice: there is no single meaning for which new row wins")
+        g_new = None
+        if gates is not None:
+            g_new = np.ascontiguousarray(gates, dtype=np.float32).ravel()
+            if g_new.shape[0] != M:
+                raise ValueError("gates length mismatch M")
+        if M == 0:
+            return arr
+        if getattr(self, "_has_comm", False):
+            raise nat.NativeError("update: a lattice with a communicator cannot change rows (multi-rank handles are out of scope)")
+        Yc = np.ascontiguousarray(Ynew, dtype=np.float32)
+        i32 = np.ascontiguousarray(arr, dtype=np.int32)
+        L = nat.lib()
+        new_h = nat.Handle()
+        t0 = time.time()
+        nat.check(L.osc_create_updated(self._h, nat.i32(i32), nat.f32(Yc), M, self._APPEND_MODES[mode], C.byref(new_h)), None,
+                  "osc_create_updated")
+        B_new = np.array(self._B, dtype=np.float32)
+        if g_new is not None:
+            B_new[arr] = g_new
+        self._carry_settings_to(new_h, B_new, self._chain_nodes)
+        self._swap_handle(new_h, self.N, B_new, t0)
+        info = self.update_info()
+        self._log("update", {"rows": M, "N": self.N, "route": info["route"], "redo_rows": info["redo_rows"]})
+        return arr
+
+    def update_info(self) -> dict[str, Any]:
+        """How the handle came to be (osc_update_info): route 0 = not by `update`, 1 = incremental, 2 = rebuild; the rows
+        replaced, the rows that kept their lists and scanned the replaced columns, the other rows recomputed; the score
+        family of its kNN lists; the incremental route's phases in ms; the list entries the merge took; why the planner did
+        not take the incremental route (0: it did, or was not asked).  It describes the creation of the handle, as
+        `append_info()` and `remove_info()` do."""
+        route, fam, denied = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        rep, merged, redo, hits = (C.c_int64(0) for _ in range(4))
+        sc, mg, bk = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
+        self._call("osc_update_info", C.byref(route), C.byref(rep), C.byref(merged), C.byref(redo), C.byref(fam), C.byref(sc),
+                   C.byref(mg), C.byref(bk), C.byref(hits), C.byref(denied))
+        return {"route": int(route.value), "replaced_rows": int(rep.value), "merged_rows": int(merged.value),
+                "redo_rows": int(redo.value), "score_family": ("none", "mfma", "butterfly")[int(fam.value)],
+                "score_ms": float(sc.value), "merge_ms": float(mg.value), "back_half_ms": float(bk.value),
+                "merge_hits": int(hits.value), "denied": int(denied.value)}
+
     # ------------------------------------------------------------------ persistence (lattice.py:582-726)
     def _provenance(self) -> str:
         h = hashlib.sha256()
