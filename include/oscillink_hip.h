@@ -231,6 +231,20 @@ int osc_anchor_ap_info(osc_handle h, int64_t* streamed_first_applies, int64_t* b
  * (measurement aid) */
 int osc_anchor_ap2_info(osc_handle h, int64_t* streamed_second_applies, int64_t* bytes, int32_t* last_solve, int64_t* builds);
 
+/* iterations 1 and 2 of an anchor start inside its INIT pass (further still: the CG scalars of both iterations come from float64
+ * Gram sums of the cached row sums, kept per lattice, so neither iteration reads or writes an N x D array of its own;
+ * OSC_ANCHOR_GRAM = 0 off / 1 wherever the streamed second apply runs in a ring solve predicted to take three or more
+ * iterations, unset: lattices of at least 96000 rows): fused_two_step_solves = solves served so since creation, bytes = device
+ * memory held for the sums ((22 ld + 6) doubles; 0: not built or dropped), last_solve = whether the last general-path solve
+ * took the route, builds = times the sums were formed, redos = solves that stopped before iteration 3 (or had a column the
+ * sums cannot serve) and were run again on the summed route (measurement aid) */
+int osc_anchor_gram_info(osc_handle h, int64_t* fused_two_step_solves, int64_t* bytes, int32_t* last_solve, int64_t* builds,
+                         int64_t* redos);
+/* the Gram sums as held (test aid): 22 arrays of ld doubles -- <W^j Y, W^k Y> for j <= k <= 3 in the order (0,0) (0,1) (0,2)
+ * (0,3) (1,1) (1,2) (1,3) (2,2) (2,3) (3,3), then <a, W^j Y> for a = 1, W 1, W W 1 and j = 0..3 -- and the six <a, b> in the
+ * order (1,1) (1,s) (1,s2) (s,s) (s,s2) (s2,s2); cap = doubles `out` holds; OSC_E_UNSUPPORTED while no sums are held */
+int osc_anchor_gram_read(osc_handle h, double* out, int64_t cap);
+
 /* the block-major copy of the graph the blocked matvec walks, built for `nb` source blocks (test / diagnostic aid; no
  * reference counterpart): slot_col / slot_w [nb][N][4] = {neighbour row, W_ij} per (source block, row, slot), unused slots
  * {first row of the block, 0}; rows whose edges exceed 4 nb slots list the rest in over_col / over_w[over_first[i] ..

@@ -1,0 +1,116 @@
+// The CG scalars of iterations 1 and 2 of an anchor start under uniform gates, from the lattice's cached Gram sums: plain
+// C++, free of every HIP type (the style of host_logic.hpp), used by k_anchor_gram_scalars (cg_kernels.hip) and by the host
+// sweep tests/host_logic/sweep_anchor_gram.cpp.
+//
+// On that route (no chain prior, x0 = Y, one gate value b) every vector of the first two iterations is, per column c, a
+// combination with column-independent coefficients of the seven N-vectors
+//     psi_c 1, psi_c s, psi_c s2, Y_c, (W Y)_c, (W W Y)_c, (W W W Y)_c          (s = W 1, s2 = W s)
+// so r0.z0, p1.Ap1, |r1|^2, p2.Ap2 and |r2|^2 are quadratic forms in their 7 x 7 Gram matrix.  That matrix depends on the
+// anchors and the graph alone (the lifetime of L::W3s); psi, the gate value, the lams and dt enter through the coefficients.
+// |r2|^2 is about 1e6 times smaller than the terms it is formed from: sums and forms are float64 throughout, and alpha /
+// beta / the residuals are rounded to float exactly where k_reduce_alpha / k_reduce_beta round them.
+//
+// Storage of the sums (L::gram, read back by osc_anchor_gram_read): kGramPerColumn arrays of ld doubles, then kGramLattice
+// doubles.  Array q < 10: <W^j Y, W^k Y> for j <= k in the order (0,0) (0,1) (0,2) (0,3) (1,1) (1,2) (1,3) (2,2) (2,3) (3,3);
+// array 10 + 4 a + j: <a, W^j Y> for a in (1, s, s2); the lattice's six: <a, b> in the order (1,1) (1,s) (1,s2) (s,s) (s,s2)
+// (s2,s2).
+#pragma once
+#include <cmath>
+#include <cstddef>
+
+#if defined(__HIPCC__)
+#define OSC_GRAM_HD __host__ __device__ inline
+#else
+#define OSC_GRAM_HD inline
+#endif
+
+namespace osc {
+namespace gram {
+
+constexpr int kGramPerColumn = 22;  // 10 <W^j Y, W^k Y> + 12 <a, W^j Y>
+constexpr int kGramLattice = 6;     // <a, b>
+constexpr int kBasis = 7;           // psi 1, psi s, psi s2, Y, W Y, W W Y, W W W Y
+
+// index of <W^j Y, W^k Y>, j <= k <= 3, among the per-column arrays
+OSC_GRAM_HD int yy_index(int j, int k) { return j * 4 - j * (j - 1) / 2 + (k - j); }
+// index of <a, W^j Y>, a in 0..2
+OSC_GRAM_HD int ay_index(int a, int j) { return 10 + 4 * a + j; }
+// index of <a, b>, a <= b <= 2, among the lattice's sums
+OSC_GRAM_HD int lat_index(int a, int b) { return a * 3 - a * (a - 1) / 2 + (b - a); }
+
+// One column's 7 x 7 Gram matrix from the stored sums: col[q * stride] is array q's entry of this column.
+OSC_GRAM_HD void fill(double (&G)[kBasis][kBasis], const double* col, size_t stride, const double* lat, double psi) {
+  for (int a = 0; a < 3; ++a)
+    for (int b = a; b < 3; ++b) G[a][b] = G[b][a] = psi * psi * lat[lat_index(a, b)];
+  for (int a = 0; a < 3; ++a)
+    for (int j = 0; j < 4; ++j) G[a][3 + j] = G[3 + j][a] = psi * col[(size_t)ay_index(a, j) * stride];
+  for (int j = 0; j < 4; ++j)
+    for (int k = j; k < 4; ++k) G[3 + j][3 + k] = G[3 + k][3 + j] = col[(size_t)yy_index(j, k) * stride];
+}
+
+// the solve's scalars as the kernels form them in float (blk_init_row), converted to double
+struct Op {
+  double m;   // 1 / (Md + 1e-12)
+  double cs;  // the operator's diagonal
+  double cW;
+  double qb;  // rbB b
+  double u;   // rbU + rbY - cs
+};
+
+struct Scalars {
+  float alpha1 = 0.f, alpha2 = 0.f, beta1 = 0.f, beta2 = 0.f;
+  float res1 = 0.f, res2 = 0.f;  // |r1|, |r2| of this column
+  double rz2 = 0.0;              // r2 . z2: what iteration 3's alpha and beta divide
+  bool usable = false;
+};
+
+OSC_GRAM_HD double form(const double (&G)[kBasis][kBasis], const double (&v)[kBasis], const double (&w)[kBasis]) {
+  double t = 0.0;
+  for (int a = 0; a < kBasis; ++a) {
+    double row = 0.0;
+    for (int b = 0; b < kBasis; ++b) row += G[a][b] * w[b];
+    t += v[a] * row;
+  }
+  return t;
+}
+// out = A v = cs v - cW W v; W shifts psi 1 -> psi s -> psi s2 and Y -> W Y -> W W Y -> W W W Y (no vector of the two
+// iterations has a component W would shift out of the basis)
+OSC_GRAM_HD void apply(const Op& o, const double (&v)[kBasis], double (&out)[kBasis]) {
+  double wv[kBasis] = {0.0, v[0], v[1], 0.0, v[3], v[4], v[5]};
+  for (int a = 0; a < kBasis; ++a) out[a] = o.cs * v[a] - o.cW * wv[a];
+}
+OSC_GRAM_HD bool finite(double x) { return x - x == 0.0; }
+
+// Iterations 1 and 2 (solver.py:19-36 as the reduce kernels spell it, + 1e-18 and float roundings included).
+// usable: every value is finite, no form that must be non-negative came out negative, and the column has a residual at all
+// (a zero column has no scale its |r2|^2 could be judged against: it takes the summed route).
+OSC_GRAM_HD Scalars two_steps(const double (&G)[kBasis][kBasis], const Op& o) {
+  Scalars s;
+  double r0[kBasis] = {o.qb, 0.0, 0.0, o.u, o.cW, 0.0, 0.0};
+  double p1[kBasis], q1[kBasis], r1[kBasis], p2[kBasis], ap2[kBasis], r2[kBasis];
+  for (int a = 0; a < kBasis; ++a) p1[a] = o.m * r0[a];
+  apply(o, p1, q1);
+  const double rr0 = form(G, r0, r0), rz0 = o.m * rr0;
+  const double pq1 = form(G, p1, q1);
+  s.alpha1 = (float)(rz0 / (pq1 + 1e-18));
+  for (int a = 0; a < kBasis; ++a) r1[a] = r0[a] - (double)s.alpha1 * q1[a];
+  const double rr1 = form(G, r1, r1), rz1 = o.m * rr1;
+  s.res1 = (float)sqrt(rr1);
+  s.beta1 = (float)(rz1 / (rz0 + 1e-18));
+  for (int a = 0; a < kBasis; ++a) p2[a] = o.m * r1[a] + (double)s.beta1 * p1[a];
+  apply(o, p2, ap2);
+  const double pq2 = form(G, p2, ap2);
+  s.alpha2 = (float)(rz1 / (pq2 + 1e-18));
+  for (int a = 0; a < kBasis; ++a) r2[a] = r1[a] - (double)s.alpha2 * ap2[a];
+  const double rr2 = form(G, r2, r2);
+  s.res2 = (float)sqrt(rr2);
+  s.rz2 = o.m * rr2;
+  s.beta2 = (float)(s.rz2 / (rz1 + 1e-18));
+  s.usable = finite(rr0) && finite(pq1) && finite(rr1) && finite(pq2) && finite(rr2) && finite((double)s.alpha1) &&
+             finite((double)s.alpha2) && finite((double)s.beta1) && finite((double)s.beta2) && rr0 > 0.0 && pq1 >= 0.0 &&
+             rr1 >= 0.0 && pq2 >= 0.0 && rr2 >= 0.0;
+  return s;
+}
+
+}  // namespace gram
+}  // namespace osc

@@ -16,6 +16,7 @@
 // Column sums never use atomics: each block keeps per-lane partials in registers over its grid-stride rows,
 // folds its 4 waves through LDS and writes one row of part[grid][ld]; a small second kernel finishes in fp64.
 #include "common.hpp"
+#include "anchor_gram.hpp"
 #include <type_traits>
 
 namespace osc {
@@ -835,6 +836,249 @@ __global__ __launch_bounds__((CW + 1) * 64) void k_init_cached_ap2(const BlkArgs
   init_cached_body<CW, 2>(a, ii, ap, ap2);
 }
 
+// Iterations 1 and 2 in the INIT pass (BlkTwoSteps): with alpha1, beta1, alpha2, beta2 known before any N x D pass
+// (k_anchor_gram_scalars) nothing of the two iterations has to reach memory but their outcome.  Geometry, row mapping and fetch
+// pipeline of init_cached_body<CW, 2>; per element every value is formed with the operations and operand order of the kernel
+// that forms it on the summed route -- r0, z0 = p1 (blk_init_row), Q1 = A p1 and T = A Q1 (init_cached_body), r1 = r0 - alpha1
+// Q1 (k_update_xr), p2 = z1 + beta1 p1 and A p2 = (1 + beta1) Q1 - (m alpha1) T (k_update_p_ap2), r2 = r1 - alpha2 A p2, p3 =
+// z2 + beta2 p2 (k_update_p), x2 = (x0 + alpha1 p1) + alpha2 p2 (k_update_x_ring) -- so the same scalars give the same bits.
+// Stores r2 (row-major), p3 (slab-major) and x2 (row-major); no column sums, no fold: the list wave has nothing to do.
+template <int CW>
+__global__ __launch_bounds__((CW + 1) * 64) void k_init_two_steps(const BlkArgs a, const BlkInit ii, const BlkInitAp ap, const BlkInitAp2 ap2,
+                                                                  const BlkTwoSteps ts) {
+  constexpr int EC = 3;  // (as init_cached_body<CW, 2>: batches of three rows keep the four streams in registers)
+  if (*ts.go != 1u) return;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if ((int)(blockIdx.x >> 3) >= a.xs || wave >= CW) return;
+  const int sub = lane >> 3, lr = lane & 7;
+  const int32_t ld = a.ld;
+  const BlkWork wk = blk_work<CW>(a);
+  const uint32_t lr16 = (uint32_t)lr * 16u, ldb = (uint32_t)ld * 4u;
+  const int ngall = a.slices * a.groups, nbatch = (ngall + EC - 1) / EC;
+  const int row_first = wk.rlo + ((wk.wgx * CW + wave) << 3) + sub;
+  for (int q = 0; q < wk.nslab; ++q) {
+    const int sc0 = a.c0 + (wk.xgrp + q * wk.xgroups) * 32;
+    const bool cok = sc0 + lr * 4 < a.c1;
+    const size_t slab = (size_t)(sc0 >> 5) * (size_t)a.N * 32;
+    const float* xbase = a.X + slab;
+    const float* wybase = ii.WY + slab;
+    float* pbase = ii.Z + slab;
+    const uint32_t cb = (uint32_t)(sc0 + lr * 4) * 4u;
+    const int cc = cok ? sc0 + lr * 4 : sc0;
+    const float4 psi4 = cok ? ld4(ii.psi + cc) : f4(0.f);
+    const float4 al1 = ld4(ts.alpha1 + cc), al2 = ld4(ts.alpha2 + cc), be1 = ld4(ts.beta1 + cc), be2 = ld4(ts.beta2 + cc);
+    float4 xs[2][EC], ws[2][EC], vs[2][EC], t3[2][EC];
+    float bv[2][EC], ss[2][EC], s2[2][EC];
+    // (no test around the loads: see init_cached_body)
+    const uint32_t lrc = cok ? lr16 : 0u;
+    const uint32_t cbc = cok ? cb : (uint32_t)sc0 * 4u;
+    const int row_last = max(wk.rhi - 1, 0);
+    auto fetch = [&](int k, float4 (&x)[EC], float4 (&w)[EC], float (&bb)[EC], float4 (&v)[EC], float (&sm)[EC], float4 (&t)[EC],
+                     float (&sm2)[EC]) {
+#pragma unroll
+      for (int i = 0; i < EC; ++i) {
+        const uint32_t row = (uint32_t)min(row_first + (k * EC + i) * wk.W8, row_last);
+        x[i] = ld4_stream_at(xbase, row * 128u + lrc);
+        w[i] = ld4_stream_at(wybase, row * 128u + lrc);
+        bb[i] = ld1_at(a.B, row * 4u);
+        v[i] = ld4_stream_at(ap.WW, row * ldb + cbc);
+        sm[i] = ld1_at(ap.wsum, row * 4u);
+        t[i] = ld4_stream_at(ap2.W3, row * ldb + cbc);
+        sm2[i] = ld1_at(ap2.wsum2, row * 4u);
+      }
+    };
+    auto consume = [&](int k, const float4 (&x)[EC], const float4 (&w)[EC], const float (&bb)[EC], const float4 (&v)[EC],
+                       const float (&sm)[EC], const float4 (&t)[EC], const float (&sm2)[EC]) {
+#pragma unroll
+      for (int i = 0; i < EC; ++i) {
+        const int g = k * EC + i, row = row_first + g * wk.W8;
+        if (g >= ngall || row >= wk.rhi || !cok) continue;
+        float4 r0, z0;
+        blk_init_row(a, ii, bb[i], x[i], x[i], w[i], psi4, r0, z0);
+        const float cs = fmaf(a.cs_B, bb[i], a.cs_const);  // (init_cached_body's scalars)
+        const float invMd = 1.f / (fmaf(ii.md_B, bb[i], ii.md_const) + 1e-12f);
+        const float u = __fsub_rn(__fadd_rn(ii.rbU, ii.rbY), cs);
+        const float qs = __fmul_rn(__fmul_rn(ii.rbB, bb[i]), sm[i]);
+        const float qs2 = __fmul_rn(__fmul_rn(ii.rbB, bb[i]), sm2[i]);
+        float r2v, p3v, x2v;
+        auto one = [&](float xv, float rv, float zv, float wyv, float wwv, float w3v, float pv, float a1, float b1, float a2, float b2) {
+          const float wz = __fmul_rn(invMd, fmaf(a.cW, wwv, fmaf(u, wyv, __fmul_rn(qs, pv))));    // (W z0)_i
+          const float q1 = fmaf(cs, zv, -__fmul_rn(a.cW, wz));                                     // Q1 = A p1
+          const float wwz = __fmul_rn(invMd, fmaf(a.cW, w3v, fmaf(u, wwv, __fmul_rn(qs2, pv))));  // (W W z0)_i
+          const float wq = fmaf(cs, wz, -__fmul_rn(a.cW, wwz));                                    // (W Q1)_i
+          const float tt = fmaf(cs, q1, -__fmul_rn(a.cW, wq));                                     // T = A Q1
+          const float r1 = fmaf(-q1, a1, rv);
+          const float p2 = fmaf(zv, b1, __fmul_rn(r1, invMd));
+          const float ap2v = fmaf(__fadd_rn(1.f, b1), q1, -__fmul_rn(__fmul_rn(invMd, a1), tt));
+          r2v = fmaf(-ap2v, a2, r1);
+          p3v = fmaf(p2, b2, __fmul_rn(r2v, invMd));
+          x2v = fmaf(p2, a2, fmaf(zv, a1, xv));
+        };
+        float4 r2, p3, x2;
+        one(x[i].x, r0.x, z0.x, w[i].x, v[i].x, t[i].x, psi4.x, al1.x, be1.x, al2.x, be2.x); r2.x = r2v; p3.x = p3v; x2.x = x2v;
+        one(x[i].y, r0.y, z0.y, w[i].y, v[i].y, t[i].y, psi4.y, al1.y, be1.y, al2.y, be2.y); r2.y = r2v; p3.y = p3v; x2.y = x2v;
+        one(x[i].z, r0.z, z0.z, w[i].z, v[i].z, t[i].z, psi4.z, al1.z, be1.z, al2.z, be2.z); r2.z = r2v; p3.z = p3v; x2.z = x2v;
+        one(x[i].w, r0.w, z0.w, w[i].w, v[i].w, t[i].w, psi4.w, al1.w, be1.w, al2.w, be2.w); r2.w = r2v; p3.w = p3v; x2.w = x2v;
+        st4_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(ii.R) + ((uint32_t)row * ldb + cb)), r2);
+        st4_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(ii.Xcopy) + ((uint32_t)row * ldb + cb)), x2);
+        st4(reinterpret_cast<float*>(reinterpret_cast<char*>(pbase) + ((uint32_t)row * 128u + lr16)), p3);
+      }
+    };
+    fetch(0, xs[0], ws[0], bv[0], vs[0], ss[0], t3[0], s2[0]);
+    int k = 0;
+    for (; k + 2 < nbatch; k += 2) {  // two batches per trip (the buffers keep their registers), no test around a fetch
+      fetch(k + 1, xs[1], ws[1], bv[1], vs[1], ss[1], t3[1], s2[1]);
+      consume(k, xs[0], ws[0], bv[0], vs[0], ss[0], t3[0], s2[0]);
+      fetch(k + 2, xs[0], ws[0], bv[0], vs[0], ss[0], t3[0], s2[0]);
+      consume(k + 1, xs[1], ws[1], bv[1], vs[1], ss[1], t3[1], s2[1]);
+    }
+    if (k + 1 < nbatch) {
+      fetch(k + 1, xs[1], ws[1], bv[1], vs[1], ss[1], t3[1], s2[1]);
+      consume(k, xs[0], ws[0], bv[0], vs[0], ss[0], t3[0], s2[0]);
+      consume(k + 1, xs[1], ws[1], bv[1], vs[1], ss[1], t3[1], s2[1]);
+    } else {
+      consume(k, xs[0], ws[0], bv[0], vs[0], ss[0], t3[0], s2[0]);
+    }
+  }
+}
+
+// The Gram sums, first stage: workgroup (slab, chunk) sums its chunk's rows of the slab's 32 columns, a thread one column of
+// every eighth row, in float64 (the product of two floats is exact there); the eight row lanes are folded through LDS in
+// lane order.  Every real row of the window's columns is visited once.  The lattice's six sums ride in the slab-0 workgroups.
+__global__ __launch_bounds__(256) void k_anchor_gram_part(const GramArgs a) {
+  constexpr int NQ = gram::kGramPerColumn, NL = gram::kGramLattice;
+  __shared__ double red[8][32];
+  const int cl = threadIdx.x & 31, half = threadIdx.x >> 5;
+  const int sc0 = a.c0 + (int)blockIdx.x * 32, col = sc0 + cl, chunk = (int)blockIdx.y;
+  const bool cok = col < a.c1;
+  const bool lat = blockIdx.x == 0 && cl == 0;
+  const int r0 = (int)((int64_t)a.N * chunk / OSC_GRAM_CHUNKS), r1 = (int)((int64_t)a.N * (chunk + 1) / OSC_GRAM_CHUNKS);
+  const size_t slab = (size_t)(sc0 >> 5) * (size_t)a.N * 32;
+  double acc[NQ], la[NL];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) acc[q] = 0.0;
+#pragma unroll
+  for (int q = 0; q < NL; ++q) la[q] = 0.0;
+  for (int row = r0 + half; row < r1; row += 8) {
+    const double s[3] = {1.0, (double)a.wsum[row], (double)a.wsum2[row]};
+    if (cok) {
+      const double y[4] = {(double)a.Ys[slab + (size_t)row * 32 + cl], (double)a.WYs[slab + (size_t)row * 32 + cl],
+                           (double)a.WW[(size_t)row * a.ld + col], (double)a.W3[(size_t)row * a.ld + col]};
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int k = j; k < 4; ++k) acc[gram::yy_index(j, k)] += y[j] * y[k];
+#pragma unroll
+      for (int b = 0; b < 3; ++b)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[gram::ay_index(b, j)] += s[b] * y[j];
+    }
+    if (lat) {
+#pragma unroll
+      for (int b = 0; b < 3; ++b)
+#pragma unroll
+        for (int c = b; c < 3; ++c) la[gram::lat_index(b, c)] += s[b] * s[c];
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    __syncthreads();
+    red[half][cl] = acc[q];
+    __syncthreads();
+    if (half == 0 && cok) {
+      double t = 0.0;
+#pragma unroll
+      for (int h = 0; h < 8; ++h) t += red[h][cl];
+      a.part[((size_t)chunk * NQ + q) * a.ld + col] = t;
+    }
+  }
+  if (blockIdx.x == 0) {
+#pragma unroll
+    for (int q = 0; q < NL; ++q) {
+      __syncthreads();
+      if (cl == 0) red[half][0] = la[q];
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        double t = 0.0;
+#pragma unroll
+        for (int h = 0; h < 8; ++h) t += red[h][0];
+        a.part[(size_t)OSC_GRAM_CHUNKS * NQ * a.ld + (size_t)chunk * NL + q] = t;
+      }
+    }
+  }
+}
+// ... second stage: the chunks' partials in chunk order (columns outside the window: 0)
+__global__ __launch_bounds__(256) void k_anchor_gram_fold(const GramArgs a) {
+  constexpr int NQ = gram::kGramPerColumn, NL = gram::kGramLattice;
+  const int idx = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (idx < NQ * a.ld) {
+    const int q = idx / a.ld, col = idx % a.ld;
+    double t = 0.0;
+    if (col >= a.c0 && col < a.c1)
+      for (int ch = 0; ch < OSC_GRAM_CHUNKS; ++ch) t += a.part[((size_t)ch * NQ + q) * a.ld + col];
+    a.out[idx] = t;
+  } else if (idx < NQ * a.ld + NL) {
+    const int q = idx - NQ * a.ld;
+    double t = 0.0;
+    for (int ch = 0; ch < OSC_GRAM_CHUNKS; ++ch) t += a.part[(size_t)OSC_GRAM_CHUNKS * NQ * a.ld + (size_t)ch * NL + q];
+    a.out[idx] = t;
+  }
+}
+
+// One workgroup, a thread per column (anchor_gram.hpp: two_steps): the scalars of iterations 1 and 2, their residuals as
+// k_reduce_beta publishes them (nanmax over the columns, device slot and host-mapped word), and the fused pass's gate word.
+// A solve with an unusable column publishes 0 for both residuals: the host loop stops in iteration 1, nothing was written,
+// and run_cg solves again on the summed route.
+__global__ __launch_bounds__(256) void k_anchor_gram_scalars(const GramScalarArgs a) {
+  __shared__ float sh1[4], sh2[4];
+  __shared__ int shu[4];
+  const float b = a.B[0];
+  gram::Op o;
+  const float cs = fmaf(a.cs_B, b, a.cs_const);  // (blk_init_row's and init_cached_body's scalars)
+  o.cs = (double)cs;
+  o.cW = (double)a.cW;
+  o.qb = (double)__fmul_rn(a.rbB, b);
+  o.m = (double)(1.f / (fmaf(a.md_B, b, a.md_const) + 1e-12f));
+  o.u = (double)__fsub_rn(__fadd_rn(a.rbU, a.rbY), cs);
+  const double* lat = a.gram + (size_t)gram::kGramPerColumn * a.ld;
+  float res1 = 0.f, res2 = 0.f;
+  int usable = 1;
+  for (int col = a.c0 + (int)threadIdx.x; col < a.c1; col += 256) {
+    double G[gram::kBasis][gram::kBasis];
+    gram::fill(G, a.gram + col, (size_t)a.ld, lat, (double)a.psi[col]);
+    const gram::Scalars s = gram::two_steps(G, o);
+    a.alpha1[col] = s.alpha1;
+    a.alpha2[col] = s.alpha2;
+    a.beta1[col] = s.beta1;
+    a.beta2[col] = s.beta2;
+    a.rz[col] = s.rz2;
+    res1 = nanmax(res1, s.res1);
+    res2 = nanmax(res2, s.res2);
+    usable &= s.usable ? 1 : 0;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    res1 = nanmax(res1, __shfl_xor(res1, off, 64));
+    res2 = nanmax(res2, __shfl_xor(res2, off, 64));
+    usable &= __shfl_xor(usable, off, 64);
+  }
+  if ((threadIdx.x & 63) == 0) sh1[threadIdx.x >> 6] = res1, sh2[threadIdx.x >> 6] = res2, shu[threadIdx.x >> 6] = usable;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; ++w) res1 = nanmax(res1, sh1[w]), res2 = nanmax(res2, sh2[w]), usable &= shu[w];
+    if (!usable) res1 = res2 = 0.f;
+    a.res_slots[1] = __float_as_uint(res1);
+    a.res_slots[2] = __float_as_uint(res2);
+    *a.go = (usable && res1 > a.tol && res2 > a.tol) ? 1u : 0u;
+    __threadfence();
+    // word 2 first: the host polls word 1, and once it has that it may give the solve up and reuse the words (run_cg)
+    reinterpret_cast<volatile uint32_t*>(a.host_words)[2] = __float_as_uint(res2);
+    __threadfence_system();
+    reinterpret_cast<volatile uint32_t*>(a.host_words)[1] = __float_as_uint(res1);
+    __threadfence_system();
+  }
+}
+
 // s_i = sum_j W_ij over the ELL row, in stored order: one thread per row (BlkInitAp::wsum)
 __global__ __launch_bounds__(256) void k_row_weight_sums(const float* w, const int32_t* deg, int32_t width, int32_t N, float* out) {
   const int row = (int)(blockIdx.x * 256 + threadIdx.x);
@@ -1560,6 +1804,35 @@ void launch_init_cached(const BlkArgs& a, int grid, hipStream_t s, const BlkInit
 #define CALL(G, W, P, E) hipLaunchKernelGGL((k_init_cached<W>), dim3(grid), dim3((W + 1) * 64), 0, s, a, init)
   OSC_BLK_SHAPE_SWITCH(variant, CALL);
 #undef CALL
+  HIP_CHECK(hipGetLastError());
+}
+void launch_init_two_steps(const BlkArgs& a, int grid, hipStream_t s, const BlkInit& init, int variant, const BlkInitAp& ap,
+                           const BlkInitAp2& ap2, const BlkTwoSteps& ts) {
+  blocked_args_check(a, grid, variant);
+  if (!init.R || !init.Z || !init.Xcopy || !init.psi || !init.WY || init.Y != nullptr || !ap.WW || !ap.wsum || !ap2.W3 || !ap2.wsum2 ||
+      !ts.alpha1 || !ts.alpha2 || !ts.beta1 || !ts.beta2 || !ts.go)
+    throw std::runtime_error("two-step INIT pass: bad arguments");
+  for (const float* out : {init.R, init.Z, init.Xcopy})  // no output is an input ...
+    if (out == a.X || out == init.WY || out == ap.WW || out == ap2.W3) throw std::runtime_error("two-step INIT pass: aliased arrays");
+  if (init.R == init.Z || init.R == init.Xcopy || init.Z == init.Xcopy)  // ... or another output
+    throw std::runtime_error("two-step INIT pass: aliased arrays");
+#define CALL(G, W, P, E) hipLaunchKernelGGL((k_init_two_steps<W>), dim3(grid), dim3((W + 1) * 64), 0, s, a, init, ap, ap2, ts)
+  OSC_BLK_SHAPE_SWITCH(variant, CALL);
+#undef CALL
+  HIP_CHECK(hipGetLastError());
+}
+void launch_anchor_gram(const GramArgs& a, hipStream_t s) {
+  if (!a.Ys || !a.WYs || !a.WW || !a.W3 || !a.wsum || !a.wsum2 || !a.part || !a.out || a.N < 1 || (a.c0 & 31) != 0 || a.c1 <= a.c0 ||
+      a.c1 > a.ld)
+    throw std::runtime_error("anchor Gram sums: bad arguments");
+  hipLaunchKernelGGL(k_anchor_gram_part, dim3((a.c1 - a.c0 + 31) / 32, OSC_GRAM_CHUNKS), dim3(256), 0, s, a);
+  HIP_CHECK(hipGetLastError());
+  const int n = gram::kGramPerColumn * a.ld + gram::kGramLattice;
+  hipLaunchKernelGGL(k_anchor_gram_fold, dim3((n + 255) / 256), dim3(256), 0, s, a);
+  HIP_CHECK(hipGetLastError());
+}
+void launch_anchor_gram_scalars(const GramScalarArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(k_anchor_gram_scalars, dim3(1), dim3(256), 0, s, a);
   HIP_CHECK(hipGetLastError());
 }
 void launch_row_weight_sums(const float* w, const int32_t* deg, int32_t width, int32_t N, float* out, hipStream_t s) {

@@ -153,6 +153,54 @@ struct BlkInitAp2 {
   float* T;            // A (A p1) out, row-major
 };
 
+// The Gram sums of an anchor start's seven basis vectors (anchor_gram.hpp has the layout): one streaming pass over the cached
+// row sums, per-chunk partials in float64, folded in chunk order (k_anchor_gram_part, k_anchor_gram_fold)
+constexpr int OSC_GRAM_CHUNKS = 64;
+struct GramArgs {
+  const float* Ys;     // the anchors, slab-major (BlkArgs::X)
+  const float* WYs;    // W Y, slab-major (BlkInit::WY)
+  const float* WW;     // W W Y, row-major
+  const float* W3;     // W W W Y, row-major
+  const float* wsum;   // [N] s = W 1
+  const float* wsum2;  // [N] s2 = W s
+  double* part;        // [OSC_GRAM_CHUNKS][22][ld], then [OSC_GRAM_CHUNKS][6]
+  double* out;         // [22][ld], then [6]
+  int32_t N, ld, c0, c1;
+};
+void launch_anchor_gram(const GramArgs& a, hipStream_t s);
+
+// k_anchor_gram_scalars: iterations 1 and 2's alpha, beta, residuals and r2 . z2 per column from the Gram sums, the two
+// residuals (max over the columns) into the solve's residual slots and host-mapped words, and the word that lets
+// k_init_two_steps run: 1 only if every column is usable and both residuals are above tol
+struct GramScalarArgs {
+  const double* gram;
+  const float* psi;  // [ld]
+  const float* B;    // [N], one value
+  float cs_const, cs_B, cW, rbU, rbY, rbB, md_B, md_const;  // BlkArgs' / BlkInit's
+  float tol;
+  int32_t ld, c0, c1;
+  float* alpha1;
+  float* alpha2;
+  float* beta1;
+  float* beta2;
+  double* rz;
+  uint32_t* res_slots;   // the solve's residual slots: [1] and [2] are written
+  uint32_t* host_words;  // the same two, host-mapped
+  uint32_t* go;
+};
+void launch_anchor_gram_scalars(const GramScalarArgs& a, hipStream_t s);
+
+// k_init_two_steps: the cached INIT pass of BlkInitAp2 run through iterations 1 and 2 with the scalars above.  Of BlkInit it
+// writes R (r2, row-major), Z (p3, slab-major) and Xcopy (x2 = x0 + alpha1 p1 + alpha2 p2, row-major; required); of BlkInitAp
+// and BlkInitAp2 it reads WW, wsum, W3, wsum2 and writes nothing.  A no-op unless *go == 1.
+struct BlkTwoSteps {
+  const float* alpha1;
+  const float* alpha2;
+  const float* beta1;
+  const float* beta2;
+  const uint32_t* go;
+};
+
 enum SpmmMode { SPMM_AP = 0, SPMM_INIT = 1, SPMM_DOT = 2 };
 
 struct SpmmArgs {
@@ -315,6 +363,8 @@ void launch_apply_blocked(const BlkArgs& a, int grid, hipStream_t s, const BlkIn
 // ap2 (with ap): ... and T = A (A p1) (BlkInitAp2)
 void launch_init_cached(const BlkArgs& a, int grid, hipStream_t s, const BlkInit& init, int variant, const BlkInitAp* ap = nullptr,
                         const BlkInitAp2* ap2 = nullptr);
+void launch_init_two_steps(const BlkArgs& a, int grid, hipStream_t s, const BlkInit& init, int variant, const BlkInitAp& ap,
+                           const BlkInitAp2& ap2, const BlkTwoSteps& ts);
 void launch_row_weight_sums(const float* w, const int32_t* deg, int32_t width, int32_t N, float* out, hipStream_t s);
 // out_i = sum_j W_ij v_j over the ELL row, in stored order (BlkInitAp2::wsum2 from BlkInitAp::wsum)
 void launch_row_weighted_sums(const int32_t* col, const float* w, const int32_t* deg, int32_t width, int32_t N, const float* v,

@@ -16,6 +16,8 @@
 //                                       second row sums (swept by tests/host_logic/sweep_anchor_ap.cpp)
 //   anchor_ap2_route                  : ... and iteration 2's from the cached third row sums (swept, with cg_host_loop against
 //                                       a model of the launches, by tests/host_logic/sweep_anchor_ap2.cpp)
+//   anchor_gram_route                 : ... and both iterations inside the INIT pass, their scalars from cached Gram sums (swept
+//                                       by tests/host_logic/sweep_anchor_gram.cpp)
 //   cg_host_loop                      : the host loop of a CG solve -- which iteration is enqueued when (run_cg in
 //                                       osc_solve.hip and both sweeps run this one function)
 #pragma once
@@ -593,6 +595,25 @@ struct AnchorAp2Inputs {
 };
 inline bool anchor_ap2_route(const AnchorAp2Inputs& in) {
   if (in.mode == 0 || !in.depth1 || in.max_iters < 2) return false;
+  return in.mode > 0 || in.N >= kAnchorApAutoRows;
+}
+// Further still: with the float64 Gram sums of the seven vectors the first two iterations are combinations of (anchor_gram.hpp)
+// every scalar of those iterations is known before the INIT pass, which then runs both iterations per element and leaves r2,
+// p3 and x2 (cg_kernels.hip: k_anchor_gram_scalars, k_init_two_steps): enqueue(1) and enqueue(2) launch nothing.  Only on top
+// of the depth-2 route, on one GPU, in a ring solve (x2 is written once, directions 1 and 2 never exist) that may run a third
+// iteration and whose predecessor of this kind took one: a solve that stops earlier has its fused pass gated off and is run
+// again on the depth-2 route (run_cg).
+struct AnchorGramInputs {
+  int mode = -1;        // OSC_ANCHOR_GRAM: 0 off, 1 wherever the depth-2 route runs, < 0 by the lattice's rows
+  int64_t N = 0;
+  bool depth2 = false;  // anchor_ap2_route holds for this solve and its arrays are held
+  bool comm = false;    // the solve runs under a communicator
+  int ring_slots = 1;   // CgXRing::K of this solve
+  int max_iters = 0;
+  int predicted = 0;    // iterations the handle's previous solve of this kind took (0: unknown)
+};
+inline bool anchor_gram_route(const AnchorGramInputs& in) {
+  if (in.mode == 0 || !in.depth2 || in.comm || in.ring_slots < 2 || in.max_iters < 3 || in.predicted < 3) return false;
   return in.mode > 0 || in.N >= kAnchorApAutoRows;
 }
 // Where iteration `it` of a solve gets its A p (CgSolve::enqueue): from the INIT pass (first: it left A p1 and the p . Ap

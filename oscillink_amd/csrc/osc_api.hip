@@ -36,6 +36,7 @@ void read_env_solver(L& h) {
   if (num("OSC_ANCHOR_WY", v)) h.anchor_wy = v != 0;  // (needs the anchors' image: OSC_ANCHOR_SLAB=0 switches it off too, run_cg)
   if (num("OSC_ANCHOR_AP", v)) h.anchor_ap = v != 0 ? 1 : 0;
   if (num("OSC_ANCHOR_AP2", v)) h.anchor_ap2 = v != 0 ? 1 : 0;
+  if (num("OSC_ANCHOR_GRAM", v)) h.anchor_gram = v != 0 ? 1 : 0;
   if (num("OSC_RECEIPT_PAIR", v)) h.receipt_pair = v != 0;
   if (const char* e = getenv("OSC_SHARD")) h.shard_mode = !strcmp(e, "row") ? 1 : 0;
   if (num("OSC_ROW_FAKE_SHARDS", v)) h.fake_row_shards = std::max(0, v);
@@ -625,6 +626,25 @@ int osc_anchor_ap2_info(osc_handle h, int64_t* streamed_second_applies, int64_t*
     if (bytes) *bytes = l.derived.w3_nb > 0 ? ((int64_t)l.W3s.n + (int64_t)l.Wsum2.n + (int64_t)l.Tap.n) * 4 : 0;
     if (last_solve) *last_solve = l.anchor_ap2_last ? 1 : 0;
     if (builds) *builds = l.anchor_ap2_builds;
+  });
+}
+
+int osc_anchor_gram_info(osc_handle h, int64_t* fused_two_step_solves, int64_t* bytes, int32_t* last_solve, int64_t* builds, int64_t* redos) {
+  return guarded(h, [&](L& l) {
+    if (fused_two_step_solves) *fused_two_step_solves = l.fused_two_step_solves;
+    if (bytes) *bytes = l.derived.gram_nb > 0 ? (int64_t)l.gram.n * 8 : 0;
+    if (last_solve) *last_solve = l.anchor_gram_last ? 1 : 0;
+    if (builds) *builds = l.anchor_gram_builds;
+    if (redos) *redos = l.anchor_gram_redos;
+  });
+}
+
+int osc_anchor_gram_read(osc_handle h, double* out, int64_t cap) {
+  return guarded(h, [&](L& l) {
+    if (l.derived.gram_nb <= 0) throw Unsupported("osc_anchor_gram_read: no Gram sums are held");
+    if (out == nullptr || cap < (int64_t)l.gram.n) throw Invalid("osc_anchor_gram_read: out holds fewer than 22 ld + 6 doubles");
+    HIP_CHECK(hipMemcpyAsync(out, l.gram.p, l.gram.n * sizeof(double), hipMemcpyDeviceToHost, l.stream));
+    sync(l);
   });
 }
 

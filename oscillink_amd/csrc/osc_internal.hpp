@@ -108,6 +108,16 @@ struct osc_lattice {
   bool anchor_ap2_denied = false;
   int64_t streamed_second_applies = 0, anchor_ap2_builds = 0;
   bool anchor_ap2_last = false;
+  // Further still (host_logic.hpp: anchor_gram_route): the float64 Gram sums of the seven vectors iterations 1 and 2 are
+  // combinations of (anchor_gram.hpp; (22 ld + 6) doubles).  With them k_anchor_gram_scalars has both iterations' alpha, beta
+  // and residuals before any N x D pass, and k_init_two_steps runs both iterations inside the INIT pass.  Built by the first
+  // solve that takes the route, valid exactly as long as W3s (Derived::gram_nb).  OSC_ANCHOR_GRAM: 0 never, 1 wherever the
+  // depth-2 route runs, unset: by the lattice's rows.
+  DevBuf<double> gram;
+  DevBuf<uint32_t> gram_go;  // the fused pass's gate word
+  int anchor_gram = -1;
+  int64_t fused_two_step_solves = 0, anchor_gram_builds = 0, anchor_gram_redos = 0;
+  bool anchor_gram_last = false;
   int64_t yu_copies = 0;     // whole-array Y -> U copies made for this handle (osc_counters::y_to_u_copies)
   int64_t slab_launches = 0;  // k_rows_to_slab launches (osc_counters::rows_to_slab_launches)
   // Which of the arrays computed from other state (ell_col_t / ell_w_t, blk_*, Ys, WYs, Ustar; by epoch: halo, query) are

@@ -1,5 +1,6 @@
 // Operator parameters, apply plans and the CG drivers of liboscillink_hip.so (see osc_internal.hpp).
 #include "osc_internal.hpp"
+#include "anchor_gram.hpp"
 
 #include <limits>
 
@@ -357,6 +358,13 @@ struct CgSolve {
   // ... and T = A (A p1) (in the handle's Tap array): iteration 2's p update then forms A p2 over A p1 and leaves the
   // p . Ap partials in part0 (k_update_p_ap2), and enqueue(2) launches no matvec either.
   bool second_ap_ready = false;
+  // Iterations 1 and 2 ran inside the INIT pass, with their scalars from the lattice's Gram sums (init_fused; host_logic.hpp:
+  // anchor_gram_route): r2, p3 (in dir(3)) and x2 are in place, alpha_of(1), alpha_of(2), h.beta and h.rz hold what the two
+  // iterations' reductions would have left, residual slots 1 and 2 are published.  enqueue(1) and enqueue(2) launch nothing,
+  // enqueue(3) launches no p update, and the ring starts with two directions applied.
+  const bool allow_gram;  // (false: the solve run again after a fused pass that was gated off)
+  bool gram_route = false;
+  bool ring_planned = false;
 
   // ---- where x is updated ---------------------------------------------------------------------------------------------
   // Deferred x update: iteration it's x += alpha p is applied by iteration it + 1's p update, which reads p anyway (x, r,
@@ -385,13 +393,13 @@ struct CgSolve {
   BlkArgs ba{};
   ChainFixArgs cf{};
 
-  CgSolve(L& h_, const OpParams& op_, const CgBuffers& b_, bool with_path_, int max_iters_, float tol_)
+  CgSolve(L& h_, const OpParams& op_, const CgBuffers& b_, bool with_path_, int max_iters_, float tol_, bool allow_gram_)
       : h(h_), op(op_), b(b_), with_path(with_path_), max_iters(max_iters_), tol(tol_), grid(cg_grid(h_)),
         plan(apply_plan(h_, b_.c0, b_.c1, b_.ld, with_path_)), nslots((size_t)max_iters_ + 2), mapped(h_.comm == nullptr),
         overlap(h_.comm != nullptr && (h_.comm_overlap == 1 || (h_.comm_overlap < 0 && h_.world >= 4)) && h_.x_defer),
         polled(mapped || overlap), x1_in(b_.defer_x0 && b_.X != b_.x0 && !overlap ? b_.x0 : nullptr),
         x_init(x1_in != nullptr ? const_cast<float*>(b_.x0) : b_.X), stop_guess(h_.predicted_iters[b_.kind]), Pbuf(b_.P),
-        APbuf(b_.AP) {
+        APbuf(b_.AP), allow_gram(allow_gram_) {
     ensure_ctrl(h, nslots);
     res_slots = ctrl_segment(h, 2 * nslots);
     done_ctr = res_slots + nslots;
@@ -450,6 +458,7 @@ struct CgSolve {
   // r = b - A x0 ; z ; p ; rz.  Returns the rows of r . z partials the pass left (+ the chain fix-up's behind the fused pass).
   int init() {
     int part_rows = grid;
+    h.anchor_gram_last = false;
     // (the rhs rows the fused pass can take besides x0 itself: one -- the state term must be x0 or absent, and if y is a
     // third array the solution array must be x0)
     const bool fuse_u = b.rhsU == b.x0 || op.rbU == 0.f;
@@ -491,7 +500,7 @@ struct CgSolve {
       sa.gate_tol = 0.f;
       spmm_slabbed(h, plan, SPMM_INIT, sa, grid);
     }
-    launch_reduce_init(h.part0.p, part_rows, b.ld, b.c0, b.c1, h.rz.p, h.stream);
+    if (!gram_route) launch_reduce_init(h.part0.p, part_rows, b.ld, b.c0, b.c1, h.rz.p, h.stream);
     ua.AP = APbuf;
     h.last_plan = plan;
     h.anchor_ap_last = first_ap_done;
@@ -541,6 +550,7 @@ struct CgSolve {
         a2.max_iters = max_iters;
         if (host::anchor_ap2_route(a2) && ensure_anchor_ap2()) {  // ... and T = A (A p1) for iteration 2's p update
           BlkInitAp2 ap2{h.W3s.p, h.Wsum2.p, h.Tap.p};
+          if (two_steps(bi, ap, ap2)) return grid;  // ... or both iterations here and now
           launch_init_cached(ba, grid, h.stream, bi, plan.shape, &ap, &ap2);
           second_ap_ready = true;
         } else {
@@ -553,7 +563,7 @@ struct CgSolve {
       }
       h.cached_inits += 1;
     } else if (wy_route) {
-      h.derived.wy_nb = h.derived.wwy_nb = h.derived.w3_nb = 0;  // (not current while this launch rewrites them)
+      h.derived.wy_nb = h.derived.wwy_nb = h.derived.w3_nb = h.derived.gram_nb = 0;  // (not current while this launch rewrites them)
       h.anchor_ap_denied = h.anchor_ap2_denied = false;
       h.WYs.alloc((size_t)h.N * h.ld);
       bi.WY = h.WYs.p;
@@ -576,8 +586,98 @@ struct CgSolve {
       launch_chain_fix(ci, h.stream);
       part_rows = grid + cf.chunks;
     }
-    std::swap(Pbuf, APbuf);  // z, the first direction, lies in the AP array
+    if (!ring_planned) std::swap(Pbuf, APbuf);  // z, the first direction, lies in the AP array (two_steps has swapped them already)
     return part_rows;
+  }
+
+  // Iterations 1 and 2 inside the cached INIT pass (anchor_gram_route).  The ring has to be planned first -- p3 goes to its slot
+  // -- hence with the P and AP arrays swapped as every fused INIT pass leaves them.  False: the route does not hold (the ring
+  // stays planned), and the depth-2 pass runs.
+  bool two_steps(BlkInit& bi, const BlkInitAp& ap, const BlkInitAp2& ap2) {
+    if (!allow_gram || h.anchor_gram == 0 || b.X == b.x0 || b.X == h.Ys.p) return false;
+    std::swap(Pbuf, APbuf);
+    plan_ring();
+    host::AnchorGramInputs gi;
+    gi.mode = h.anchor_gram;
+    gi.N = h.N;
+    gi.depth2 = true;
+    gi.comm = h.comm != nullptr;
+    gi.ring_slots = ring.K;
+    gi.max_iters = max_iters;
+    gi.predicted = stop_guess;
+    if (!host::anchor_gram_route(gi) || !ensure_anchor_gram()) return false;
+    GramScalarArgs ga{};
+    ga.gram = h.gram.p;
+    ga.psi = b.psi;
+    ga.B = b.B;
+    ga.cs_const = ba.cs_const;
+    ga.cs_B = ba.cs_B;
+    ga.cW = ba.cW;
+    ga.rbU = bi.rbU;
+    ga.rbY = bi.rbY;
+    ga.rbB = bi.rbB;
+    ga.md_B = bi.md_B;
+    ga.md_const = bi.md_const;
+    ga.tol = tol;
+    ga.ld = b.ld;
+    ga.c0 = b.c0;
+    ga.c1 = b.c1;
+    ga.alpha1 = alpha_of(1);
+    ga.alpha2 = alpha_of(2);
+    ga.beta1 = h.part1.p;  // (beta1 has no array of its own on the summed route either: the r . z partials' first row is free here)
+    ga.beta2 = h.beta.p;
+    ga.rz = h.rz.p;
+    ga.res_slots = res_slots;
+    ga.host_words = reinterpret_cast<uint32_t*>(h.res_host_dev);
+    if (h.gram_go.n < 1) h.gram_go.alloc(1);
+    ga.go = h.gram_go.p;
+    launch_anchor_gram_scalars(ga, h.stream);
+    BlkInit ti = bi;
+    ti.Z = dir(3);
+    ti.Xcopy = b.X;
+    BlkTwoSteps ts{ga.alpha1, ga.alpha2, ga.beta1, ga.beta2, ga.go};
+    launch_init_two_steps(ba, grid, h.stream, ti, plan.shape, ap, ap2, ts);
+    gram_route = true;
+    ring.applied = 2;  // directions 1 and 2 are in x2
+    h.fused_two_step_solves += 1;
+    h.anchor_gram_last = true;
+    h.cached_inits += 1;
+    return true;
+  }
+
+  // The Gram sums of the seven vectors (L::gram; anchor_gram.hpp), formed where they are not held: one streaming pass over the
+  // arrays ensure_anchor_ap2 has just made current.  135 KB at 768 columns: no memory rule.
+  bool ensure_anchor_gram() {
+    if (h.derived.gram_nb == ba.nb && h.derived.w3_nb == ba.nb) return true;
+    h.derived.gram_nb = 0;
+    const size_t n = (size_t)gram::kGramPerColumn * h.ld + gram::kGramLattice;
+    DevBuf<double> part;
+    try {
+      if (h.gram.n != n) h.gram.alloc(n);
+      part.alloc(n * OSC_GRAM_CHUNKS);
+    } catch (const HipError&) {
+      (void)hipGetLastError();
+      h.gram.release();
+      return false;
+    }
+    GramArgs g{};
+    g.Ys = h.Ys.p;
+    g.WYs = h.WYs.p;
+    g.WW = h.WWs.p;
+    g.W3 = h.W3s.p;
+    g.wsum = h.Wsum.p;
+    g.wsum2 = h.Wsum2.p;
+    g.part = part.p;
+    g.out = h.gram.p;
+    g.N = (int32_t)h.N;
+    g.ld = h.ld;
+    g.c0 = h.c0;
+    g.c1 = h.c1;
+    launch_anchor_gram(g, h.stream);
+    sync(h);  // part goes out of scope
+    h.derived.gram_nb = ba.nb;
+    h.anchor_gram_builds += 1;
+    return true;
   }
 
   // The anchors' second row sums for the streamed first apply (L::WWs, L::Wsum), formed from WYs where they are not held:
@@ -630,7 +730,7 @@ struct CgSolve {
   bool ensure_anchor_ap2() {
     if (h.derived.w3_nb == ba.nb && h.derived.wwy_nb == ba.nb) return true;
     if (h.anchor_ap2_denied) return false;
-    h.derived.w3_nb = 0;
+    h.derived.w3_nb = h.derived.gram_nb = 0;
     const size_t n = (size_t)h.N * h.ld;
     if (h.W3s.n != n || h.Tap.n != n || h.Wsum2.n != (size_t)h.N) {
       size_t free_b = 0, total_b = 0;
@@ -672,6 +772,8 @@ struct CgSolve {
   // How many directions the solve keeps (plan_x_ring) and where: only a solve that wants more slots than the handle holds at
   // this size asks the device what is free; no solve fails over its ring.
   void plan_ring() {
+    if (ring_planned) return;
+    ring_planned = true;
     host::XRingInputs ri;
     ri.predicted = stop_guess;
     ri.max_iters = max_iters;
@@ -758,11 +860,12 @@ struct CgSolve {
   // everything of iteration `it` up to its residual, gated on iteration it - 1
   // (overlap: no gates -- an iteration writes scratch arrays only until the host has seen its predecessor unconverged)
   void enqueue(int it, bool speculative) {
+    if (gram_route && it <= 2) return;  // (both ran inside the INIT pass; their residuals are out)
     const Gate g{it > 1 && !overlap ? reinterpret_cast<const float*>(res_slots) + (it - 1) : nullptr, tol};
     host::CgXSchedule::IterForm form{false, host::CgXSchedule::XR_SKIPS_X};
     if (!ringed()) form = xs.enqueue(it, speculative);
     const host::ApSource ap_src = host::cg_ap_source(it, first_ap_done, second_ap_ready);
-    if (it > 1) {
+    if (it > 1 && !(gram_route && it == 3)) {  // (the fused INIT pass left p3 in dir(3))
       ProfScope ps(h, 2, it);
       if (ringed()) {
         // the slot p_it goes to still holds a direction x lacks: this iteration's flush, then p_it = z + beta p_{it-1}
@@ -904,13 +1007,24 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
     CgResult one{};
     if (run_cg_small(h, op, b, with_path, max_iters, tol, one)) return one;
   }
-  CgSolve s(h, op, b, with_path, max_iters, tol);
-  s.init();
-  s.plan_ring();
-  h.history.clear();
-  s.prof_mark = h.prof_pending.size();
-  const int iters = host::cg_host_loop(max_iters, s.stop_guess, (double)tol, s);
-  return s.finish(iters);
+  for (const bool allow_gram : {true, false}) {
+    CgSolve s(h, op, b, with_path, max_iters, tol, allow_gram);
+    s.init();
+    s.plan_ring();
+    h.history.clear();
+    s.prof_mark = h.prof_pending.size();
+    const int iters = host::cg_host_loop(max_iters, s.stop_guess, (double)tol, s);
+    if (s.gram_route && iters < 3) {
+      // The solve stopped before iteration 3 (or a column's sums were unusable): the fused pass was gated off, nothing but
+      // scratch scalars was written.  The same solve again, on the depth-2 route; its count keeps the next one off the route.
+      h.anchor_gram_redos += 1;
+      h.fused_two_step_solves -= 1;
+      h.cached_inits -= 1;  // (the solve counts once, where it ends)
+      continue;
+    }
+    return s.finish(iters);
+  }
+  throw std::runtime_error("run_cg: the summed route did not finish");
 }
 
 // Column-sharded runs: every rank owns columns [c0, c1) of an N x ld array.  Make the whole array valid on every

@@ -249,6 +249,8 @@ class OscillinkLattice:
         self._call("osc_anchor_ap_info", C.byref(af), C.byref(ab), C.byref(al), C.byref(an))
         a2f, a2b, a2l, a2n = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int64(0)
         self._call("osc_anchor_ap2_info", C.byref(a2f), C.byref(a2b), C.byref(a2l), C.byref(a2n))
+        gf, gb, gl, gn, gr = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int64(0), C.c_int64(0)
+        self._call("osc_anchor_gram_info", C.byref(gf), C.byref(gb), C.byref(gl), C.byref(gn), C.byref(gr))
         counters = nat.Counters()
         self._call("osc_counters_get", C.byref(counters))
         return {"order_kind": ("none", "bfs", "balanced")[int(ok.value)], "displaced_edges_before": int(db.value),
@@ -265,7 +267,19 @@ class OscillinkLattice:
                 "anchor_ap_last_solve": int(al.value), "anchor_ap_builds": int(an.value),
                 "streamed_second_applies": int(a2f.value), "anchor_ap2_bytes": int(a2b.value),
                 "anchor_ap2_last_solve": int(a2l.value), "anchor_ap2_builds": int(a2n.value),
+                "fused_two_step_solves": int(gf.value), "anchor_gram_bytes": int(gb.value),
+                "anchor_gram_last_solve": int(gl.value), "anchor_gram_builds": int(gn.value),
+                "anchor_gram_redos": int(gr.value),
                 **{name: int(getattr(counters, name)) for name, _ in nat.Counters._fields_[1:]}}
+
+    def anchor_gram(self) -> np.ndarray:
+        """The float64 Gram sums the fused two-step INIT pass takes its CG scalars from, as held on the device: (22 ld + 6,)
+        in the layout of include/oscillink_hip.h: osc_anchor_gram_read (test aid; raises while none are held)."""
+        gb = C.c_int64(0)
+        self._call("osc_anchor_gram_info", None, C.byref(gb), None, None, None)
+        out = np.zeros(max(int(gb.value) // 8, 1), dtype=np.float64)
+        self._call("osc_anchor_gram_read", out.ctypes.data_as(C.POINTER(C.c_double)), out.size)
+        return out
 
     def halo_info(self) -> dict[str, int]:
         """Row-sharded runs (OSC_SHARD=row under a communicator): the rows of the search direction this rank receives
