@@ -342,6 +342,19 @@ int osc_get_query_basis(osc_handle h, float* X_out, float* x_out);
  * mmr_diversify (graph.py:114-133, lambda_div) over the anchors.  ids / score / align are Q x min(k, N), API ids. */
 int osc_bundle_many(osc_handle h, const float* psis, int32_t Q, int32_t k, float alpha, float lambda_div, int32_t* ids,
                     float* score, float* align);
+/* compute_diffusion_gates (preprocess/diffusion.py:104-124, 130-151: the sources, the screened-diffusion solve, the min-max
+ * normalisation and the clip) for Q queries psis (Q x D) on the lattice's graph, as ONE Jacobi-PCG with a right-hand side
+ * per query: (L_sym + gamma I) h_q = beta max(0, cos(Y_i, psi_q)).  method 0 ("direct"): every
+ * column runs to |r_q| <= 1e-7 max(1, |s_q|), 2048 iterations at most; method 1 ("cg"): to |r_q| <= tol, max_iters at most.
+ * A column stops at its own residual and is not touched afterwards, so row q is what the single-query path
+ * (osc_cosine_to + osc_cg_single_rhs) gives for psi_q, and is the same to the bit whatever else the batch holds.
+ * gates_out is Q x N in API row order (clamp != 0: min-max normalised, ones where max - min < 1e-12; always clipped to
+ * [0, 1]); iters_out / res_out (Q each, may be NULL) receive each query's own iteration count and final |r_q|.  Queries run
+ * OSC_GATES_CHUNK (read at every call; default and at most 256, a multiple of 32) at a time.  Changes no state of the handle.
+ * OSC_E_INVALID for gamma <= 0, max_iters < 1, an unknown method or a non-finite query, OSC_E_STATE without a graph,
+ * OSC_E_UNSUPPORTED with a communicator. */
+int osc_gates_many(osc_handle h, const float* psis, int32_t Q, float beta, float gamma, int32_t method, float tol,
+                   int32_t max_iters, int32_t clamp, float* gates_out, int32_t* iters_out, float* res_out);
 /* Not in the reference: receipt() (lattice.py:298-455, receipts.py:10-83) for Q queries psis (Q x D) with the current U,
  * gates, chain and lambdas held fixed, U*(psi) from the resident basis.  Per query: dH (deltaH_trace
  * of U against U*(psi_q)); with detail != 0 also coh_sum / anchor_sum / query_sum and the null points at z_th (else 0 and

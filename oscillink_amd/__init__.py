@@ -5,7 +5,7 @@ Drop-in for the reference's public names on that path (oscillink/__init__.py:4-2
 """
 from .lattice import OscillinkLattice, __version__, json_line_logger  # noqa: F401
 from .receipts import verify_receipt, verify_receipt_mode  # noqa: F401
-from .diffusion import compute_diffusion_gates  # noqa: F401
+from .diffusion import compute_diffusion_gates, compute_diffusion_gates_many  # noqa: F401
 from .corpus import Corpus  # noqa: F401
 
 Oscillink = OscillinkLattice
@@ -16,6 +16,7 @@ __all__ = [
     "verify_receipt",
     "verify_receipt_mode",
     "compute_diffusion_gates",
+    "compute_diffusion_gates_many",
     "Corpus",
     "json_line_logger",
 ]

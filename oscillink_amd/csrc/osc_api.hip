@@ -1230,6 +1230,17 @@ int osc_bundle_many(osc_handle h, const float* psis, int32_t Q, int32_t k, float
   });
 }
 
+int osc_gates_many(osc_handle h, const float* psis, int32_t Q, float beta, float gamma, int32_t method, float tol,
+                   int32_t max_iters, int32_t clamp, float* gates_out, int32_t* iters_out, float* res_out) {
+  return guarded(h, [&](L& l) {
+    if (Q < 0) throw Invalid("osc_gates_many: Q must be >= 0");
+    if (Q > 0 && (!psis || !gates_out)) throw Invalid("osc_gates_many: NULL buffer");
+    for (int64_t i = 0; i < (int64_t)Q * l.D; ++i)
+      if (!std::isfinite(psis[i])) throw Invalid("osc_gates_many: non-finite query");
+    query_gates_many(l, psis, Q, beta, gamma, method, tol, max_iters, clamp, gates_out, iters_out, res_out);
+  });
+}
+
 int osc_receipt_many(osc_handle h, const float* psis, int32_t Q, int32_t detail, float z_th, int32_t null_cap, double* dH,
                      double* coh_sum, double* anchor_sum, double* query_sum, int32_t* null_total, int64_t* null_offsets,
                      int32_t* i_out, int32_t* j_out, float* z_out, float* r_out, int64_t capacity) {

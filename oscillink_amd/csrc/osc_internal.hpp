@@ -36,6 +36,7 @@
 #include "dynamics.hpp"
 #include "small.hpp"
 #include "query.hpp"
+#include "gates_many.hpp"
 
 using namespace osc;
 
@@ -479,6 +480,9 @@ double quad_form_of_difference(L& l, const float* A, const float* B);
 void query_bundle_many(L& l, const float* psis, int32_t Q, int32_t k, float alpha, float lambda_div, int32_t* ids,
                        float* score, float* align);
 void query_mmr_many(L& l, const float* scores, int32_t Q, int32_t k, float lambda_div, int32_t* ids);
+// osc_gates_many (gates_many.hpp)
+void query_gates_many(L& l, const float* psis, int32_t Q, float beta, float gamma, int32_t method, float tol, int32_t max_iters,
+                      int32_t clamp, float* gates_out, int32_t* iters_out, float* res_out);
 
 struct ProfScope {
   L& h;

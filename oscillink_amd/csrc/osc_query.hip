@@ -677,3 +677,111 @@ void query_chain_receipt_many(L& l, const float* psis, int32_t Q, const int64_t*
     sync(l);  // (the host vectors above are reused by the next chunk)
   }
 }
+
+// ---- diffusion gates for many queries ----------------------------------------------------------
+// compute_diffusion_gates (preprocess/diffusion.py:104-124, 130-151) for Q queries on the handle's graph: per chunk one
+// GEMM for the sources, one Jacobi-PCG over the panel with a stop per column (gates_many_kernels.hip), the min-max
+// normalisation and the transpose to query-major API order.  The operator (L_sym + gamma I) is the query-free part of a gated
+// request; nothing of the handle's state is read but the anchors and the graph, and nothing is written.
+void query_gates_many(L& l, const float* psis, int32_t Q, float beta, float gamma, int32_t method, float tol, int32_t max_iters,
+                      int32_t clamp, float* gates_out, int32_t* iters_out, float* res_out) {
+  require_graph(l);
+  if (l.comm) throw Unsupported("osc_gates_many: lattices with a communicator are not supported");
+  if (!(gamma > 0)) throw Invalid("gamma must be > 0 for SPD");
+  if (max_iters < 1) throw Invalid("max_iters must be >= 1");
+  if (method != 0 && method != 1) throw Invalid("osc_gates_many: method must be 0 (direct) or 1 (cg)");
+  if (Q <= 0) return;
+  const bool direct = method == 0;
+  const int32_t cap = direct ? 2048 : max_iters;  // diffusion.py's "direct" as served here: CG to round-off
+  const int32_t N = (int32_t)l.N, D = l.D;
+  ensure_yn(l);
+  int requested = host::kGatesMaxChunk;
+  env_num("OSC_GATES_CHUNK", requested);
+  const int32_t qc_max = host::gates_chunk(N, D, requested, host::kGatesBudgetBytes);
+  const int32_t kpad = query_kpad(D);
+  DevBuf<char> scratch;
+  scratch.alloc((size_t)host::gates_layout(N, qc_max, host::gates_bt_floats(qc_max, D)).total);
+  // the operator and its Jacobi diagonal as osc_cg_single_rhs states them (cs_const = md_const = 1 + gamma)
+  const float cs = 1.0f + gamma;
+  const float inv_md = 1.f / (cs + 1e-12f);
+  const GmGraph g{l.ell_col.p, l.ell_w.p, l.deg.p, l.width};
+  const int32_t* inv = permuted(l) ? l.inv_d.p : nullptr;
+  std::vector<float> bt;
+  for (int32_t c = 0; c < host::gates_chunk_count(Q, qc_max); ++c) {
+    const int32_t q0 = host::gates_chunk_begin(c, qc_max), nq = host::gates_chunk_size(Q, c, qc_max);
+    const int32_t qc = host::gates_width(nq);
+    const int64_t btn = host::gates_bt_floats(qc, D);
+    const host::GatesLayout lay = host::gates_layout(N, qc, btn);
+    char* const base = scratch.p;
+    GmPanel p{};
+    p.X = reinterpret_cast<float*>(base + lay.X);
+    p.R = reinterpret_cast<float*>(base + lay.R);
+    p.P = reinterpret_cast<float*>(base + lay.P);
+    p.AP = reinterpret_cast<float*>(base + lay.AP);
+    p.part_a = reinterpret_cast<double*>(base + lay.part_a);
+    p.part_b = reinterpret_cast<double*>(base + lay.part_b);
+    p.rz = reinterpret_cast<double*>(base + lay.rz);
+    p.tol = reinterpret_cast<float*>(base + lay.tol);
+    p.alpha = reinterpret_cast<float*>(base + lay.alpha);
+    p.beta = reinterpret_cast<float*>(base + lay.beta);
+    p.res = reinterpret_cast<float*>(base + lay.res);
+    p.lo = reinterpret_cast<float*>(base + lay.lo);
+    p.hi = reinterpret_cast<float*>(base + lay.hi);
+    p.live = reinterpret_cast<int32_t*>(base + lay.live);
+    p.iters = reinterpret_cast<int32_t*>(base + lay.iters);
+    p.slab_live = reinterpret_cast<int32_t*>(base + lay.slab_live);
+    p.n_live = reinterpret_cast<int32_t*>(base + lay.n_live);
+    p.N = N;
+    p.slabs = qc / host::kGatesSlab;
+    p.parts = host::gates_parts(N);
+    p.part_rows = host::gates_part_rows(N);
+    p.nq = nq;
+    float* const out = reinterpret_cast<float*>(base + lay.out);
+    float* const Bt = reinterpret_cast<float*>(base + lay.Bt);
+    // the sources: cosines of the normalised anchors to psi / (|psi| + 1e-12) (rows_cosine_to's normalisation)
+    bt.assign((size_t)btn, 0.f);
+    for (int32_t t = 0; t < nq; ++t) {
+      const float* q = psis + (size_t)(q0 + t) * D;
+      float ss = 0.f;
+      for (int32_t d = 0; d < D; ++d) ss += q[d] * q[d];
+      const float qinv = 1.0f / (std::sqrt(ss) + 1e-12f);
+      for (int32_t d = 0; d < D; ++d) bt[(size_t)t * kpad + d] = q[d] * qinv;
+    }
+    HIP_CHECK(hipMemcpyAsync(Bt, bt.data(), bt.size() * 4, hipMemcpyHostToDevice, l.stream));
+    float* const C = p.AP;  // N x qc, row-major, until the first apply overwrites it
+    HIP_CHECK(hipMemsetAsync(C, 0, (size_t)N * qc * 4, l.stream));
+    QueryGemmArgs gm{};
+    gm.A = l.query.Yn.p;
+    gm.Bt = Bt;
+    gm.N = N;
+    gm.D = D;
+    gm.ld = l.ld;
+    gm.kpad = kpad;
+    gm.qs = qc;
+    gm.nq = nq;
+    gm.mode = 1;   // C = <Yn_i, Bt_q>, stored as it is (first: replaces the zeros)
+    gm.first = 1;
+    gm.maxsim = C;
+    launch_query_gemm(gm, l.stream);
+    launch_gm_source(p, C, beta, inv_md, l.stream);
+    launch_gm_init(p, direct ? 1 : 0, tol, l.stream);
+    for (int32_t it = 1; it <= cap; ++it) {
+      launch_gm_apply(p, g, cs, l.stream);
+      launch_gm_alpha(p, l.stream);
+      launch_gm_update(p, inv_md, l.stream);
+      launch_gm_beta(p, it, l.stream);
+      int32_t live = 0;
+      // the next direction is enqueued before the host waits for the count (after the last iteration nothing reads it)
+      if (it < cap) launch_gm_direction(p, inv_md, l.stream);
+      HIP_CHECK(hipMemcpyAsync(&live, p.n_live + (it & 1), 4, hipMemcpyDeviceToHost, l.stream));
+      sync(l);
+      if (live == 0) break;
+    }
+    launch_gm_finish(p, clamp, inv, out, l.stream);
+    if (iters_out) HIP_CHECK(hipMemcpyAsync(iters_out + q0, p.iters, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
+    if (res_out) HIP_CHECK(hipMemcpyAsync(res_out + q0, p.res, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
+    download_contiguous(l, reinterpret_cast<char*>(gates_out + (size_t)q0 * N), reinterpret_cast<const char*>(out),
+                        (size_t)nq * N * 4);
+    sync(l);  // (bt and the scratch block are reused by the next chunk)
+  }
+}

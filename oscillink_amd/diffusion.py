@@ -86,3 +86,47 @@ def compute_diffusion_gates(
         lo, hi = float(np.min(h)), float(np.max(h))
         h = np.ones(N, dtype=np.float32) if hi - lo < 1e-12 else (h - lo) / (hi - lo)
     return np.clip(h, 0.0, 1.0).astype(np.float32)
+
+
+def compute_diffusion_gates_many(
+    Y: np.ndarray,
+    psis: np.ndarray,
+    *,
+    kneighbors: int = 6,
+    row_cap_val: float = 1.0,
+    beta: float = 1.0,
+    gamma: float = 0.1,
+    similarity: str = "cosine",
+    deterministic_k: bool = False,
+    neighbor_seed: Optional[int] = None,
+    clamp: bool = True,
+    method: str = "direct",
+    tol: float = 1e-4,
+    max_iters: int = 256,
+    lattice: Optional[OscillinkLattice] = None,
+) -> np.ndarray:
+    """`compute_diffusion_gates` for each row of `psis` (Q x D): gates of shape (Q, N), row q what the single call returns
+    for psis[q] with the same arguments, from one batched solve on the device (`OscillinkLattice.diffusion_gates_many`,
+    DESIGN.md section 17).  Builds and closes its own lattice when none is given."""
+    if Y.ndim != 2:
+        raise ValueError("Y must be 2D")
+    N, D = Y.shape
+    P = np.asarray(psis)
+    if P.ndim != 2 or P.shape[1] != D:
+        raise ValueError("psi dimension mismatch")
+    if gamma <= 0:
+        raise ValueError("gamma must be > 0 for SPD")
+    if kneighbors < 1:
+        raise ValueError("kneighbors must be >=1")
+    if similarity != "cosine":
+        raise ValueError("unsupported similarity metric")
+    own = lattice is None
+    lat = lattice if lattice is not None else OscillinkLattice(
+        np.ascontiguousarray(Y, dtype=np.float32), kneighbors=kneighbors, row_cap_val=row_cap_val,
+        deterministic_k=deterministic_k, neighbor_seed=neighbor_seed)
+    try:
+        return lat.diffusion_gates_many(P, beta=beta, gamma=gamma, method=method, tol=tol, max_iters=max_iters,
+                                        clamp=clamp)["gates"]
+    finally:
+        if own:
+            lat.close()

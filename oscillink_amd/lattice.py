@@ -897,6 +897,41 @@ class OscillinkLattice:
                    chain_verdict=verdict != 0, chain_weakest_k=weak_k, chain_weakest_z=weak_z)
         return arr if as_arrays else rc.chain_receipt_dicts(lists, arr)
 
+    def diffusion_gates_many(self, psis: np.ndarray, *, beta: float = 1.0, gamma: float = 0.1, method: str = "direct",
+                             tol: float = 1e-4, max_iters: int = 256, clamp: bool = True) -> dict:
+        """`compute_diffusion_gates(self.Y, psis[q], ..., lattice=self)` for each row of `psis` (Q x D) in one device call
+        (DESIGN.md section 17): the operator L_sym + gamma I is the same for every query, so the Q gate solves are one CG
+        with Q right-hand sides over the lattice's graph, each column stopped at its own residual.  Returns `gates`
+        (Q x N float32, API row order, clipped to [0, 1] for either value of `clamp`), `iters` (Q int32) and `res` (Q
+        float32), each query's own iteration count and final |r_q|.  `method="direct"` means what it means there: CG to
+        1e-7 max(1, |s_q|), 2048 iterations at most.  A query's row is the same to the bit whatever else the batch
+        holds.  Non-finite gates come back as computed, with one RuntimeWarning naming the first such query.  Changes no
+        state of the lattice."""
+        if self._has_comm:
+            raise NotImplementedError("diffusion_gates_many: lattices with a communicator (sharded / multi-rank) are not "
+                                      "supported")
+        P = rc.check_queries(psis, self.D)
+        if gamma <= 0:
+            raise ValueError("gamma must be > 0 for SPD")
+        if method not in ("direct", "cg"):
+            raise ValueError(f"method must be 'direct' or 'cg', got {method!r}")
+        Q = int(P.shape[0])
+        gates = nat.result_array((Q, self.N)) if Q > 0 else np.zeros((0, self.N), dtype=np.float32)
+        iters = np.zeros(Q, dtype=np.int32)
+        res = np.zeros(Q, dtype=np.float32)
+        self._call("osc_gates_many", nat.f32(P), Q, float(beta), float(gamma), 1 if method == "cg" else 0, float(tol),
+                   int(max_iters), 1 if clamp else 0, nat.f32(gates), nat.i32(iters), nat.f32(res))
+        bad = np.nonzero(~np.all(np.isfinite(gates), axis=1))[0] if Q > 0 else np.zeros(0, dtype=np.intp)
+        if bad.size:
+            import warnings
+
+            q = int(bad[0])
+            warnings.warn(f"diffusion_gates_many: the screened-diffusion solve of query {q} produced non-finite values "
+                          f"(iters={int(iters[q])}, res={float(res[q])!r}); returned as computed, like the reference's cg "
+                          "path", RuntimeWarning, stacklevel=2)
+        self._log("diffusion_gates_many", {"Q": Q, "method": method, "iters_max": int(iters.max()) if Q else 0})
+        return {"gates": gates, "iters": iters, "res": res}
+
     def query_basis(self, tol: float = 1e-4, max_iters: int = 256) -> tuple[np.ndarray, np.ndarray]:
         """The query basis (X N x D, x N) in API row order: U*(psi) = X + x psi^T (diagnostic; not in the reference).
         Solved for the current psi's |psi|_inf unless a basis of the same graph, gates, chain, lambdas and tolerance is
