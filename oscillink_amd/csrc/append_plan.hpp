@@ -1,5 +1,7 @@
-// The route and the sizes of osc_create_appended.  HIP-free: osc_graph.hip / osc_api.hip run it,
-// tests/host_logic/sweep_append_plan.cpp sweeps it under the sanitizers.
+// The route and the sizes of osc_create_appended, and what the three builds seeded from a base's kept
+// lists share (append, remove, update): the eligibility checks, the threshold, the query list and its
+// chunks.  HIP-free: osc_graph.hip / osc_api.hip run it, tests/host_logic/sweep_append_plan.cpp and sweep_update_plan.cpp
+// sweep it under the sanitizers.
 //
 // An appended lattice holds the N rows of a base lattice followed by M new ones.  Its top-k lists are either built from
 // scratch (route rebuild) or grown from the base's kept lists (route incremental): the new rows -- and the old rows whose
@@ -9,6 +11,7 @@
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <vector>
 
 namespace osc {
 namespace host {
@@ -37,6 +40,7 @@ enum AppendDenied : int32_t {
   kAppendWideRows,     // butterfly family with unit rows wider than the score kernel's registers
   kAppendMixedLists,   // butterfly family whose build sent rows to the MFMA kernel (more than 32 fallback rows)
   kAppendSlower,       // eligible, but the planner expects the rebuild to be no slower (auto mode only)
+  kRemoveTooFewRows,   // fewer than two rows are left (only a removal gets there; remove_plan.hpp has its text)
 };
 
 inline const char* append_denied_text(int32_t why) {
@@ -54,8 +58,8 @@ inline const char* append_denied_text(int32_t why) {
   }
 }
 
-struct AppendInputs {
-  int64_t N = 0, M = 0;       // rows of the base, new rows
+struct SeedInputs {
+  int64_t N = 0, M = 0;       // rows of the base; rows appended, distinct rows removed, rows replaced
   int32_t D = 0;
   int32_t k_requested = 0;    // k as asked for at the base's creation
   int32_t knn_k = 0;          // length of the base's kept lists (0: none)
@@ -63,6 +67,7 @@ struct AppendInputs {
   int32_t fallback_rows = 0;  // rows the base's prefilter build handed to its fallback
   bool comm = false;
 };
+using AppendInputs = SeedInputs;
 
 inline int64_t append_ldn(int32_t D) { return (((int64_t)D + 31) / 32) * 32; }  // pitch of the unit rows (int64: D near 2^31)
 inline int64_t append_lds(int64_t cols) { return ((cols + 31) / 32) * 32; }               // pitch of a score block's rows
@@ -70,16 +75,22 @@ inline int32_t append_k_eff(int32_t k_requested, int64_t rows) {
   return (int32_t)std::min<int64_t>(k_requested, std::max<int64_t>(1, rows - 1));
 }
 
-// Eligibility of the incremental route, thresholds aside (they need the redo count, which the device computes)
-inline int32_t append_eligible(const AppendInputs& in) {
-  if (in.N < 0 || in.M < 0 || in.N + in.M > kAppendMaxRows) return kAppendTooManyRows;  // (int64: no overflow below 2^63)
+// What every seeded build asks of its base, sizes aside: `rows_after` rows stand in the lattice afterwards
+inline int32_t seed_eligible(const SeedInputs& in, int64_t rows_after) {
   if (in.knn_k <= 0 || in.family == kFamilyNone || in.N < 2) return kAppendNoLists;
   if (in.comm) return kAppendComm;
-  if (append_k_eff(in.k_requested, in.N + in.M) != in.knn_k) return kAppendKChanges;
+  if (rows_after < 2) return kRemoveTooFewRows;
+  if (append_k_eff(in.k_requested, rows_after) != in.knn_k) return kAppendKChanges;
   if (in.knn_k > kAppendListMax) return kAppendKTooLong;
   if (in.family == kFamilyButterfly && append_ldn(in.D) > kAppendBflyMaxLdn) return kAppendWideRows;
   if (in.family == kFamilyButterfly && in.fallback_rows > 32) return kAppendMixedLists;
   return kAppendOk;
+}
+
+// Eligibility of the incremental route, thresholds aside (they need the redo count, which the device computes)
+inline int32_t append_eligible(const AppendInputs& in) {
+  if (in.N < 0 || in.M < 0 || in.N + in.M > kAppendMaxRows) return kAppendTooManyRows;  // (int64: no overflow below 2^63)
+  return seed_eligible(in, in.N + in.M);
 }
 
 // The thresholds of the automatic route, from scripts/bench_append.py on an MI355X (DESIGN.md section 14 has the table).  The
@@ -95,9 +106,10 @@ inline int64_t append_max_query_rows(int32_t family, int64_t rows) {
   if (family == kFamilyMfma) return std::max<int64_t>(32, rows / 32);
   return std::max<int64_t>(32, rows / 256);
 }
-inline bool append_pays(int32_t family, int64_t N, int64_t M, int64_t redo) {
-  return redo + M <= append_max_query_rows(family, N + M);
+inline bool seed_pays(int32_t family, int64_t rows_after, int64_t query_rows) {
+  return query_rows <= append_max_query_rows(family, rows_after);
 }
+inline bool append_pays(int32_t family, int64_t N, int64_t M, int64_t redo) { return seed_pays(family, N + M, redo + M); }
 
 // Query rows of one chunk: as many as fit the scratch budget, whole 128-row tiles, at least one tile.  `cols` = N + M.
 inline int64_t append_chunk_rows(int64_t cols, int64_t budget_bytes = kAppendScratchBytes) {
@@ -118,14 +130,22 @@ inline int64_t append_scratch_floats(int64_t query_rows, int64_t cols, int64_t b
   const int64_t rows = std::min(std::max<int64_t>(1, query_rows), append_chunk_rows(cols, budget_bytes));
   return rows * append_lds(std::max<int64_t>(1, cols));
 }
-// The part of a chunk [begin, end) of the query list that holds NEW rows, given that the list is the `redo` old rows
-// followed by the M new ones: query rows [nb, ne) of the chunk-local block score new columns first_col + (0 .. ne - nb).
-inline void append_chunk_new_part(int64_t redo, int64_t N, int64_t begin, int64_t end, int64_t& nb, int64_t& ne, int64_t& first_col) {
-  const int64_t a = std::max(begin, redo);
-  nb = std::min(end, a) - begin;
+// The query list of a seeded build: the flagged rows that are not fresh in ascending order, then the fresh rows (the
+// appended rows, none, the replaced rows; ascending as given).  `flagged` is in any order (the device's).
+inline std::vector<int32_t> seed_query_list(const std::vector<int32_t>& flagged, const std::vector<int32_t>& fresh) {
+  std::vector<int32_t> q;
+  q.reserve(flagged.size() + fresh.size());
+  for (int32_t r : flagged)
+    if (!std::binary_search(fresh.begin(), fresh.end(), r)) q.push_back(r);
+  std::sort(q.begin(), q.end());
+  q.insert(q.end(), fresh.begin(), fresh.end());
+  return q;
+}
+// The part of a chunk [begin, end) of that list that holds FRESH rows, `redo` other rows standing before them: query rows
+// [nb, ne) of the chunk-local block, which score the columns named by entries [begin + nb, begin + ne) of the list.
+inline void seed_chunk_fresh_part(int64_t redo, int64_t begin, int64_t end, int64_t& nb, int64_t& ne) {
+  nb = std::min(end, std::max(begin, redo)) - begin;
   ne = end - begin;
-  first_col = N + (a - redo);
-  if (nb >= ne) nb = ne;
 }
 
 }  // namespace host

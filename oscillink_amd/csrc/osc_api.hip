@@ -171,18 +171,16 @@ int osc_device_synchronize(int32_t device) {
 
 const char* osc_last_error(osc_handle h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
-// osc_create, and osc_create_appended's way through it (sd != nullptr: Y holds the sd->n_new NEW rows; the first sd->n_old
-// rows come from the base's device copy, gathered back to API order into this handle's row pitch), and
-// osc_create_removed's (rs != nullptr: no host anchors at all; the N rows are the base's kept rows, gathered likewise), and
-// osc_create_updated's (us != nullptr: Y holds the replaced rows' new vectors in the order of upd_ids; all N rows of the
-// base are gathered likewise, then those rows are overwritten on the device)
+// osc_create, and the seeded creations' way through it (sd != nullptr: osc_create_appended, osc_create_removed,
+// osc_create_updated).  The anchors then come from the base's device copy, gathered back to API order into this handle's
+// row pitch: append -- the first n_old rows, and Y holds the NEW rows that follow them; remove -- no host anchors at all,
+// the N rows are the base's kept rows; update -- all N rows, then Y's rows (the replaced rows' new vectors, in the order
+// of sd->ids_as_given) overwrite theirs on the device.
 static int create_handle(const float* Y, int64_t N, int32_t D, int32_t k, float row_cap, int32_t deterministic, int64_t seed,
-                         int32_t device, int32_t build, osc_handle* out, const osc_lattice::AppendSeed* sd,
-                         const osc_lattice::RemoveSeed* rs = nullptr, const osc_lattice::UpdateSeed* us = nullptr,
-                         const int32_t* upd_ids = nullptr) {
+                         int32_t device, int32_t build, osc_handle* out, const osc_lattice::Seed* sd = nullptr) {
   if (!out) return OSC_E_INVALID;
   *out = nullptr;
-  if ((!Y && !rs) || N < 1 || D < 1 || k < 1 || N >= (int64_t)1 << 31) {
+  if ((!Y && !(sd && sd->kind == L::SeedKind::remove)) || N < 1 || D < 1 || k < 1 || N >= (int64_t)1 << 31) {
     g_create_error = "osc_create: need Y != NULL, 1 <= N < 2^31, D >= 1, k >= 1";
     return OSC_E_INVALID;
   }
@@ -256,59 +254,42 @@ static int create_handle(const float* Y, int64_t N, int32_t D, int32_t k, float 
     // where it can it takes them piece by piece and works on what has arrived (osc_graph.hip: stream_pieces).
     if (sd != nullptr) {
       const osc_lattice& b = *sd->base;
-      launch_append_gather_rows(h->Y.p, h->ld, b.Y.p, b.ld, b.perm_h.empty() ? nullptr : b.inv_d.p, sd->n_old, h->dcols, h->stream);
-      float* dst = h->Y.p + (size_t)sd->n_old * h->ld;
-      if (h->ld == D) HIP_CHECK(hipMemcpyAsync(dst, Y, (size_t)sd->n_new * D * 4, hipMemcpyHostToDevice, h->stream));
-      else HIP_CHECK(hipMemcpy2DAsync(dst, (size_t)h->ld * 4, Y, (size_t)D * 4, (size_t)D * 4, (size_t)sd->n_new, hipMemcpyHostToDevice, h->stream));
-      host::changed(h->derived, host::Input::anchors);
-      reset_u_to_y(*h);
-      h->lamG = b.lamG, h->lamC = b.lamC, h->lamQ = b.lamQ;
-      h->append.new_rows = sd->n_new;
-      h->append_seed = sd->seed_lists ? sd : nullptr;  // (else: a plain build of the concatenated anchors)
-      build_graph(*h, nullptr);  // (an exception ends the handle under construction with it)
-      h->append_seed = nullptr;
-      if (h->append.route == 0) h->append.route = host::kRouteRebuild;
-    } else if (rs != nullptr) {
-      const osc_lattice& b = *rs->base;
-      {
+      const int32_t* base_order = b.perm_h.empty() ? nullptr : b.inv_d.p;
+      const int64_t M = (int64_t)sd->fresh.size();
+      if (sd->kind == L::SeedKind::append) {
+        launch_append_gather_rows(h->Y.p, h->ld, b.Y.p, b.ld, base_order, sd->n_old, h->dcols, h->stream);
+        float* dst = h->Y.p + (size_t)sd->n_old * h->ld;
+        if (h->ld == D) HIP_CHECK(hipMemcpyAsync(dst, Y, (size_t)M * D * 4, hipMemcpyHostToDevice, h->stream));
+        else HIP_CHECK(hipMemcpy2DAsync(dst, (size_t)h->ld * 4, Y, (size_t)D * 4, (size_t)D * 4, (size_t)M, hipMemcpyHostToDevice, h->stream));
+      } else if (sd->kind == L::SeedKind::remove) {
         DevBuf<int32_t> old_of_new, from;
         old_of_new.alloc((size_t)N);
         from.alloc((size_t)N);
-        HIP_CHECK(hipMemcpyAsync(old_of_new.p, rs->old_of_new.data(), (size_t)N * 4, hipMemcpyHostToDevice, h->stream));
-        launch_remove_gather_index(old_of_new.p, b.perm_h.empty() ? nullptr : b.inv_d.p, N, from.p, h->stream);
+        HIP_CHECK(hipMemcpyAsync(old_of_new.p, sd->old_of_new.data(), (size_t)N * 4, hipMemcpyHostToDevice, h->stream));
+        launch_remove_gather_index(old_of_new.p, base_order, N, from.p, h->stream);
         launch_append_gather_rows(h->Y.p, h->ld, b.Y.p, b.ld, from.p, N, h->dcols, h->stream);
         sync(*h);  // (the gather has read the two index arrays before they go back to the pool, whatever the build does)
-      }
-      host::changed(h->derived, host::Input::anchors);
-      reset_u_to_y(*h);
-      h->lamG = b.lamG, h->lamC = b.lamC, h->lamQ = b.lamQ;
-      h->removed.removed_rows = b.N - N;
-      h->remove_seed = rs->seed_lists ? rs : nullptr;  // (else: a plain build of the kept anchors)
-      build_graph(*h, nullptr);  // (an exception ends the handle under construction with it)
-      h->remove_seed = nullptr;
-      if (h->removed.route == 0) h->removed.route = host::kRouteRebuild;
-    } else if (us != nullptr) {
-      const osc_lattice& b = *us->base;
-      const int64_t M = (int64_t)us->ids.size();
-      {
+        h->made.removed_rows = b.N - N;
+      } else {
         DevBuf<float> fresh;
         DevBuf<int32_t> at;
         fresh.alloc((size_t)M * D);
         at.alloc((size_t)M);
         HIP_CHECK(hipMemcpyAsync(fresh.p, Y, (size_t)M * D * 4, hipMemcpyHostToDevice, h->stream));
-        HIP_CHECK(hipMemcpyAsync(at.p, upd_ids, (size_t)M * 4, hipMemcpyHostToDevice, h->stream));
-        launch_append_gather_rows(h->Y.p, h->ld, b.Y.p, b.ld, b.perm_h.empty() ? nullptr : b.inv_d.p, N, h->dcols, h->stream);
+        HIP_CHECK(hipMemcpyAsync(at.p, sd->ids_as_given, (size_t)M * 4, hipMemcpyHostToDevice, h->stream));
+        launch_append_gather_rows(h->Y.p, h->ld, b.Y.p, b.ld, base_order, N, h->dcols, h->stream);
         launch_update_scatter_rows(h->Y.p, h->ld, fresh.p, D, h->dcols, at.p, M, h->stream);
         sync(*h);  // (the scatter has read the two uploads before they go back to the pool, whatever the build does)
       }
       host::changed(h->derived, host::Input::anchors);
       reset_u_to_y(*h);
       h->lamG = b.lamG, h->lamC = b.lamC, h->lamQ = b.lamQ;
-      h->updated.replaced_rows = M;
-      h->update_seed = us->seed_lists ? us : nullptr;  // (else: a plain build of the changed anchors)
+      h->made.kind = sd->kind;
+      h->made.fresh_rows = M;
+      h->list_seed = sd->seed_lists ? sd : nullptr;  // (else: a plain build of the new anchors)
       build_graph(*h, nullptr);  // (an exception ends the handle under construction with it)
-      h->update_seed = nullptr;
-      if (h->updated.route == 0) h->updated.route = host::kRouteRebuild;
+      h->list_seed = nullptr;
+      if (h->made.route == 0) h->made.route = host::kRouteRebuild;
     } else if (build) {
       build_graph(*h, Y);
     } else {
@@ -329,63 +310,107 @@ static int create_handle(const float* Y, int64_t N, int32_t D, int32_t k, float 
 
 int osc_create(const float* Y, int64_t N, int32_t D, int32_t k, float row_cap, int32_t deterministic, int64_t seed,
                int32_t device, int32_t build, osc_handle* out) {
-  return create_handle(Y, N, D, k, row_cap, deterministic, seed, device, build, out, nullptr);
+  return create_handle(Y, N, D, k, row_cap, deterministic, seed, device, build, out);
 }
 
-int osc_create_appended(osc_handle base, const float* Ynew, int64_t M, int32_t mode, osc_handle* out) {
+}  // extern "C"
+
+// What osc_create_appended, osc_create_removed and osc_create_updated share.  `fn`: the entry point's name, for the error
+// texts; args_ok / need: its own argument check.  After the communicator check, prepare(sd, rows_after, why) normalises
+// the entry point's ids into the seed, names the rows the new lattice has and asks its *_eligible; it returns what is
+// wrong with the ids (nullptr: nothing).
+template <typename Prepare>
+static int create_from_base(const char* fn, L::SeedKind kind, bool args_ok, const char* need, osc_handle base, const float* Ynew,
+                            int32_t mode, osc_handle* out, Prepare&& prepare) {
   if (!out) return OSC_E_INVALID;
   *out = nullptr;
-  if (!base || !Ynew || M < 1 || mode < 0 || mode > 2) {
-    g_create_error = "osc_create_appended: need a base handle, Ynew != NULL, M >= 1 and mode 0, 1 or 2";
+  const std::string at = std::string(fn) + ": ";
+  if (!args_ok) {
+    g_create_error = at + "need " + need;
     return OSC_E_INVALID;
   }
   const osc_lattice& b = *base;
+  auto text = [&](int32_t why) { return kind == L::SeedKind::remove ? host::remove_denied_text(why) : host::append_denied_text(why); };
   if (b.comm != nullptr) {
-    g_create_error = std::string("osc_create_appended: ") + host::append_denied_text(host::kAppendComm);
+    g_create_error = at + text(host::kAppendComm);
     return OSC_E_UNSUPPORTED;
   }
-  if (b.N + M >= (int64_t)1 << 31) {
-    g_create_error = std::string("osc_create_appended: ") + host::append_denied_text(host::kAppendTooManyRows);
+  osc_lattice::Seed sd;
+  sd.kind = kind;
+  sd.base = base;
+  sd.n_old = b.N;
+  int64_t rows_after = 0;
+  int32_t why = host::kAppendOk;
+  try {
+    if (const char* bad_ids = prepare(sd, rows_after, why)) {
+      g_create_error = at + bad_ids;
+      return OSC_E_INVALID;
+    }
+  } catch (const std::exception& e) {
+    g_create_error = e.what();
+    return OSC_E_HIP;
+  }
+  if (why == host::kAppendTooManyRows) {  // (an append alone gets here: ids are int32)
+    g_create_error = at + text(why);
     return OSC_E_UNSUPPORTED;
   }
-  const int32_t why = host::append_eligible(host::AppendInputs{b.N, M, b.D, b.k_requested, b.have_graph ? b.knn_k : 0, b.score_family,
-                                                               b.knn_fallback_rows, false});
   if (mode == 1 && why != host::kAppendOk) {
-    g_create_error = std::string("osc_create_appended: no incremental route: ") + host::append_denied_text(why);
+    g_create_error = at + "no incremental route: " + text(why);
     return OSC_E_UNSUPPORTED;
   }
   // (an injected graph cannot be rebuilt from anchors either: it is not theirs.  A lattice that was never built has no
-  // graph to keep: modes 0 and 2 build its N + M anchors)
+  // graph to keep: modes 0 and 2 build the new anchors)
   if (why == host::kAppendNoLists && b.N > 1 && b.have_graph) {
-    g_create_error = std::string("osc_create_appended: ") + host::append_denied_text(why);
+    g_create_error = at + text(why);
     return OSC_E_UNSUPPORTED;
   }
   (void)hipSetDevice(b.device);
   if (b.stream && hipStreamSynchronize(b.stream) != hipSuccess) {  // (the base's anchors and lists are read from another stream)
-    g_create_error = "osc_create_appended: the base lattice's stream reports an error";
+    g_create_error = at + "the base lattice's stream reports an error";
     return OSC_E_HIP;
   }
-  osc_lattice::AppendSeed sd;
-  sd.base = base;
-  sd.n_old = b.N;
-  sd.n_new = M;
   sd.forced = mode == 1;
   sd.seed_lists = mode != 2 && why == host::kAppendOk;
   osc_handle h = nullptr;
-  const int rc = create_handle(Ynew, b.N + M, b.D, b.k_requested, b.row_cap, b.deterministic, b.seed, b.device, 1, &h, &sd);
+  const int rc = create_handle(Ynew, rows_after, b.D, b.k_requested, b.row_cap, b.deterministic, b.seed, b.device, 1, &h, &sd);
   if (rc != OSC_OK) return rc;
-  if (mode != 2 && why != host::kAppendOk) h->append.denied = why;
+  if (mode != 2 && why != host::kAppendOk) h->made.denied = why;
   *out = h;
   return OSC_OK;
+}
+
+static host::SeedInputs seed_inputs(const osc_lattice& b, int64_t M) {
+  return host::SeedInputs{b.N, M, b.D, b.k_requested, b.have_graph ? b.knn_k : 0, b.score_family, b.knn_fallback_rows, false};
+}
+
+// the record of a handle made by `kind`, zeros for any other handle
+static const osc_lattice::SeedInfo& made_by(const L& l, L::SeedKind kind) {
+  static const osc_lattice::SeedInfo none;
+  return l.made.kind == kind ? l.made : none;
+}
+
+extern "C" {
+
+int osc_create_appended(osc_handle base, const float* Ynew, int64_t M, int32_t mode, osc_handle* out) {
+  return create_from_base("osc_create_appended", L::SeedKind::append, base && Ynew && M >= 1 && mode >= 0 && mode <= 2,
+                          "a base handle, Ynew != NULL, M >= 1 and mode 0, 1 or 2", base, Ynew, mode, out,
+                          [&](osc_lattice::Seed& sd, int64_t& rows_after, int32_t& why) -> const char* {
+                            rows_after = sd.n_old + M;
+                            why = host::append_eligible(seed_inputs(*base, M));
+                            if (why == host::kAppendTooManyRows) return nullptr;
+                            sd.fresh.resize((size_t)M);
+                            for (int64_t j = 0; j < M; ++j) sd.fresh[(size_t)j] = (int32_t)(sd.n_old + j);
+                            return nullptr;
+                          });
 }
 
 int osc_append_info(osc_handle h, int32_t* route, int64_t* new_rows, int64_t* merged_rows, int64_t* redo_rows, int32_t* family,
                     double* score_ms, double* merge_ms, double* back_ms, int64_t* merge_hits, int64_t* scan_bytes, int32_t* denied) {
   return guarded(h, [&](L& l) {
-    const osc_lattice::AppendInfo& a = l.append;
+    const osc_lattice::SeedInfo& a = made_by(l, L::SeedKind::append);
     if (route) *route = a.route;
-    if (new_rows) *new_rows = a.new_rows;
-    if (merged_rows) *merged_rows = a.merged_rows;
+    if (new_rows) *new_rows = a.fresh_rows;
+    if (merged_rows) *merged_rows = a.kept_rows;
     if (redo_rows) *redo_rows = a.redo_rows;
     if (family) *family = l.score_family;
     if (score_ms) *score_ms = a.score_ms;
@@ -398,66 +423,28 @@ int osc_append_info(osc_handle h, int32_t* route, int64_t* new_rows, int64_t* me
 }
 
 int osc_create_removed(osc_handle base, const int32_t* ids, int64_t n, int32_t mode, osc_handle* out) {
-  if (!out) return OSC_E_INVALID;
-  *out = nullptr;
-  if (!base || !ids || n < 1 || mode < 0 || mode > 2) {
-    g_create_error = "osc_create_removed: need a base handle, ids != NULL, n >= 1 and mode 0, 1 or 2";
-    return OSC_E_INVALID;
-  }
-  const osc_lattice& b = *base;
-  if (b.comm != nullptr) {
-    g_create_error = std::string("osc_create_removed: ") + host::remove_denied_text(host::kAppendComm);
-    return OSC_E_UNSUPPORTED;
-  }
-  osc_lattice::RemoveSeed sd;
-  int64_t M = 0;
-  try {
-    sd.new_id.resize((size_t)b.N);
-    const int32_t bad = host::remove_map(ids, n, b.N, sd.new_id.data(), &M);
-    if (bad != host::kRemoveIdsOk) {
-      g_create_error = bad == host::kRemoveIdOutOfRange ? "osc_create_removed: an id is outside [0, N)"
-                       : bad == host::kRemoveAllRows    ? "osc_create_removed: the ids name every row"
-                                                        : "osc_create_removed: bad sizes";
-      return OSC_E_INVALID;
-    }
-    sd.old_of_new.resize((size_t)(b.N - M));
-    host::remove_inverse(sd.new_id.data(), b.N, sd.old_of_new.data());
-  } catch (const std::exception& e) {
-    g_create_error = e.what();
-    return OSC_E_HIP;
-  }
-  const int32_t why = host::remove_eligible(host::RemoveInputs{b.N, M, b.D, b.k_requested, b.have_graph ? b.knn_k : 0, b.score_family,
-                                                               b.knn_fallback_rows, false});
-  if (mode == 1 && why != host::kAppendOk) {
-    g_create_error = std::string("osc_create_removed: no incremental route: ") + host::remove_denied_text(why);
-    return OSC_E_UNSUPPORTED;
-  }
-  // (an injected graph cannot be rebuilt from anchors either: it is not theirs.  A lattice that was never built has no
-  // graph to keep: modes 0 and 2 build its kept anchors)
-  if (why == host::kAppendNoLists && b.N > 1 && b.have_graph) {
-    g_create_error = std::string("osc_create_removed: ") + host::remove_denied_text(why);
-    return OSC_E_UNSUPPORTED;
-  }
-  (void)hipSetDevice(b.device);
-  if (b.stream && hipStreamSynchronize(b.stream) != hipSuccess) {  // (the base's anchors and lists are read from another stream)
-    g_create_error = "osc_create_removed: the base lattice's stream reports an error";
-    return OSC_E_HIP;
-  }
-  sd.base = base;
-  sd.forced = mode == 1;
-  sd.seed_lists = mode != 2 && why == host::kAppendOk;
-  osc_handle h = nullptr;
-  const int rc = create_handle(nullptr, b.N - M, b.D, b.k_requested, b.row_cap, b.deterministic, b.seed, b.device, 1, &h, nullptr, &sd);
-  if (rc != OSC_OK) return rc;
-  if (mode != 2 && why != host::kAppendOk) h->removed.denied = why;
-  *out = h;
-  return OSC_OK;
+  return create_from_base("osc_create_removed", L::SeedKind::remove, base && ids && n >= 1 && mode >= 0 && mode <= 2,
+                          "a base handle, ids != NULL, n >= 1 and mode 0, 1 or 2", base, nullptr, mode, out,
+                          [&](osc_lattice::Seed& sd, int64_t& rows_after, int32_t& why) -> const char* {
+                            int64_t M = 0;
+                            sd.row_map.resize((size_t)sd.n_old);
+                            const int32_t bad = host::remove_map(ids, n, sd.n_old, sd.row_map.data(), &M);
+                            if (bad != host::kRemoveIdsOk)
+                              return bad == host::kRemoveIdOutOfRange ? "an id is outside [0, N)"
+                                     : bad == host::kRemoveAllRows    ? "the ids name every row"
+                                                                      : "bad sizes";
+                            sd.old_of_new.resize((size_t)(sd.n_old - M));
+                            host::remove_inverse(sd.row_map.data(), sd.n_old, sd.old_of_new.data());
+                            rows_after = sd.n_old - M;
+                            why = host::remove_eligible(seed_inputs(*base, M));
+                            return nullptr;
+                          });
 }
 
 int osc_remove_info(osc_handle h, int32_t* route, int64_t* removed_rows, int64_t* kept_rows, int64_t* redo_rows, int32_t* family,
                     double* score_ms, double* back_ms, int32_t* denied) {
   return guarded(h, [&](L& l) {
-    const osc_lattice::RemoveInfo& r = l.removed;
+    const osc_lattice::SeedInfo& r = made_by(l, L::SeedKind::remove);
     if (route) *route = r.route;
     if (removed_rows) *removed_rows = r.removed_rows;
     if (kept_rows) *kept_rows = r.kept_rows;
@@ -470,68 +457,31 @@ int osc_remove_info(osc_handle h, int32_t* route, int64_t* removed_rows, int64_t
 }
 
 int osc_create_updated(osc_handle base, const int32_t* ids, const float* Ynew, int64_t M, int32_t mode, osc_handle* out) {
-  if (!out) return OSC_E_INVALID;
-  *out = nullptr;
-  if (!base || !ids || !Ynew || M < 1 || mode < 0 || mode > 2) {
-    g_create_error = "osc_create_updated: need a base handle, ids != NULL, Ynew != NULL, M >= 1 and mode 0, 1 or 2";
-    return OSC_E_INVALID;
-  }
-  const osc_lattice& b = *base;
-  if (b.comm != nullptr) {
-    g_create_error = std::string("osc_create_updated: ") + host::append_denied_text(host::kAppendComm);
-    return OSC_E_UNSUPPORTED;
-  }
-  osc_lattice::UpdateSeed sd;
-  try {
-    sd.keep.resize((size_t)b.N);
-    const int32_t bad = host::update_ids(ids, M, b.N, sd.keep.data());
-    if (bad != host::kUpdateIdsOk) {
-      g_create_error = bad == host::kUpdateIdOutOfRange  ? "osc_create_updated: an id is outside [0, N)"
-                       : bad == host::kUpdateIdDuplicate ? "osc_create_updated: an id is named twice"
-                                                         : "osc_create_updated: bad sizes";
-      return OSC_E_INVALID;
-    }
-    sd.ids.assign(ids, ids + M);
-    std::sort(sd.ids.begin(), sd.ids.end());
-  } catch (const std::exception& e) {
-    g_create_error = e.what();
-    return OSC_E_HIP;
-  }
-  const int32_t why = host::update_eligible(host::UpdateInputs{b.N, M, b.D, b.k_requested, b.have_graph ? b.knn_k : 0, b.score_family,
-                                                               b.knn_fallback_rows, false});
-  if (mode == 1 && why != host::kAppendOk) {
-    g_create_error = std::string("osc_create_updated: no incremental route: ") + host::append_denied_text(why);
-    return OSC_E_UNSUPPORTED;
-  }
-  // (an injected graph cannot be rebuilt from anchors either: it is not theirs.  A lattice that was never built has no
-  // graph to keep: modes 0 and 2 build its changed anchors)
-  if (why == host::kAppendNoLists && b.N > 1 && b.have_graph) {
-    g_create_error = std::string("osc_create_updated: ") + host::append_denied_text(why);
-    return OSC_E_UNSUPPORTED;
-  }
-  (void)hipSetDevice(b.device);
-  if (b.stream && hipStreamSynchronize(b.stream) != hipSuccess) {  // (the base's anchors and lists are read from another stream)
-    g_create_error = "osc_create_updated: the base lattice's stream reports an error";
-    return OSC_E_HIP;
-  }
-  sd.base = base;
-  sd.forced = mode == 1;
-  sd.seed_lists = mode != 2 && why == host::kAppendOk;
-  osc_handle h = nullptr;
-  const int rc = create_handle(Ynew, b.N, b.D, b.k_requested, b.row_cap, b.deterministic, b.seed, b.device, 1, &h, nullptr, nullptr, &sd, ids);
-  if (rc != OSC_OK) return rc;
-  if (mode != 2 && why != host::kAppendOk) h->updated.denied = why;
-  *out = h;
-  return OSC_OK;
+  return create_from_base("osc_create_updated", L::SeedKind::update, base && ids && Ynew && M >= 1 && mode >= 0 && mode <= 2,
+                          "a base handle, ids != NULL, Ynew != NULL, M >= 1 and mode 0, 1 or 2", base, Ynew, mode, out,
+                          [&](osc_lattice::Seed& sd, int64_t& rows_after, int32_t& why) -> const char* {
+                            sd.row_map.resize((size_t)sd.n_old);
+                            const int32_t bad = host::update_ids(ids, M, sd.n_old, sd.row_map.data());
+                            if (bad != host::kUpdateIdsOk)
+                              return bad == host::kUpdateIdOutOfRange  ? "an id is outside [0, N)"
+                                     : bad == host::kUpdateIdDuplicate ? "an id is named twice"
+                                                                       : "bad sizes";
+                            sd.ids_as_given = ids;
+                            sd.fresh.assign(ids, ids + M);
+                            std::sort(sd.fresh.begin(), sd.fresh.end());
+                            rows_after = sd.n_old;
+                            why = host::update_eligible(seed_inputs(*base, M));
+                            return nullptr;
+                          });
 }
 
 int osc_update_info(osc_handle h, int32_t* route, int64_t* replaced_rows, int64_t* merged_rows, int64_t* redo_rows, int32_t* family,
                     double* score_ms, double* merge_ms, double* back_ms, int64_t* merge_hits, int32_t* denied) {
   return guarded(h, [&](L& l) {
-    const osc_lattice::UpdateInfo& u = l.updated;
+    const osc_lattice::SeedInfo& u = made_by(l, L::SeedKind::update);
     if (route) *route = u.route;
-    if (replaced_rows) *replaced_rows = u.replaced_rows;
-    if (merged_rows) *merged_rows = u.merged_rows;
+    if (replaced_rows) *replaced_rows = u.fresh_rows;
+    if (merged_rows) *merged_rows = u.kept_rows;
     if (redo_rows) *redo_rows = u.redo_rows;
     if (family) *family = l.score_family;
     if (score_ms) *score_ms = u.score_ms;

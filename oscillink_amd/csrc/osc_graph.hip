@@ -859,303 +859,113 @@ static void graph_from_lists(L& h, int32_t N, int32_t k) {
   maybe_reorder(h);
 }
 
-// The seeded build of osc_create_appended: the handle's anchors are on the device in API order, the
-// base's lists name the first n_old rows' k best old columns.  The query rows -- the redo set (old rows whose lists
-// cannot be merged: a clipped or missing member, a non-finite row) and the new rows -- are scored against all columns in
-// the base's score family, chunk by chunk; each chunk's rows get their k best, and every other old row merges the chunk's
-// new columns into its list (append_kernels.hip).  Then the back half, unchanged.  false (auto mode only): the planner
-// expects the rebuild to be no slower; nothing but scratch was written and the unseeded build runs.
-static bool build_graph_seeded(L& h) {
-  const L::AppendSeed& sd = *h.append_seed;
+// Events recorded in a stream, destroyed with the scope
+struct Events {
+  std::vector<hipEvent_t> ev;
+  ~Events() {
+    for (auto e : ev) (void)hipEventDestroy(e);
+  }
+  void mark(hipStream_t s) {
+    hipEvent_t e = nullptr;
+    HIP_CHECK(hipEventCreate(&e));
+    ev.push_back(e);
+    HIP_CHECK(hipEventRecord(e, s));
+  }
+};
+
+// The lists a seeded build starts from, rows [0, n_listed) of kval / kidx (N rows of k entries each):
+//   append: the base's rows, then empty rows (value 0, id -1) for the new ones
+//   remove: every kept row's list at its new row, the member ids renumbered and the removed members emptied
+//   update: the base's lists with every member that names a replaced row emptied and the replaced rows' own lists empty
+// `row_map` is the scratch array the seed's map is uploaded to (it lives as long as the build's other scratch).
+static void seed_lists(const L& h, const L::Seed& sd, int32_t k, DevBuf<int32_t>& row_map, float* kval, int32_t* kidx) {
   const L& base = *sd.base;
-  const int32_t N = (int32_t)h.N, n_old = (int32_t)sd.n_old, k = base.knn_k;
+  const size_t n_old = (size_t)sd.n_old, fresh = (size_t)h.N - n_old;
+  switch (sd.kind) {
+    case L::SeedKind::append:
+      HIP_CHECK(hipMemcpyAsync(kval, base.knn_val.p, n_old * k * 4, hipMemcpyDeviceToDevice, h.stream));
+      HIP_CHECK(hipMemcpyAsync(kidx, base.knn_idx.p, n_old * k * 4, hipMemcpyDeviceToDevice, h.stream));
+      HIP_CHECK(hipMemsetAsync(kval + n_old * k, 0, fresh * k * 4, h.stream));
+      HIP_CHECK(hipMemsetAsync(kidx + n_old * k, 0xFF, fresh * k * 4, h.stream));
+      return;
+    case L::SeedKind::remove:
+    case L::SeedKind::update:
+      row_map.alloc(n_old);
+      HIP_CHECK(hipMemcpyAsync(row_map.p, sd.row_map.data(), n_old * 4, hipMemcpyHostToDevice, h.stream));
+      if (sd.kind == L::SeedKind::remove) launch_remove_lists(base.knn_val.p, base.knn_idx.p, base.N, k, row_map.p, kval, kidx, h.stream);
+      else launch_update_lists(base.knn_val.p, base.knn_idx.p, base.N, k, row_map.p, kval, kidx, h.stream);
+      return;
+    case L::SeedKind::none: break;
+  }
+  throw std::runtime_error("seed_lists: no seed kind");
+}
+
+// The seeded build of osc_create_appended, osc_create_removed and osc_create_updated (14-16 have what
+// differs): the handle's anchors are on the device in API order, and seed_lists has written the lists of the first n_listed
+// rows (all but an append's new rows) from the base's.  The append flags' rules -- a clipped or missing member, a
+// non-finite row -- mark the listed rows whose lists cannot be kept (a superset: redoing a row is always correct); an
+// update's replaced rows, whose lists are empty, are among them.  The query list -- the flagged rows that are not fresh,
+// ascending, then the fresh rows -- is scored against all columns in the base's score family, chunk by chunk; each chunk's
+// rows get their k best, and every listed row outside the flagged set merges the chunk's fresh columns into its list
+// (k_append_merge / k_update_merge).  Then the back half, unchanged.  false (auto mode only): the planner expects the rebuild to be no
+// slower; nothing but scratch was written and the unseeded build runs.
+static bool build_graph_from_base(L& h) {
+  const L::Seed& sd = *h.list_seed;
+  const L& base = *sd.base;
+  const bool fresh_flagged = sd.kind == L::SeedKind::update;
+  const int32_t N = (int32_t)h.N, k = base.knn_k;
+  const int32_t n_listed = sd.kind == L::SeedKind::append ? (int32_t)sd.n_old : N;
   const int32_t family = base.score_family;
+  const int64_t M = (int64_t)sd.fresh.size();
   const double t0 = now_ms();
-  // (auto mode: M alone over the threshold decides on the host, before any device work)
-  if (!sd.forced && !host::append_pays(family, n_old, (int64_t)N - n_old, 0)) {
-    h.append.denied = host::kAppendSlower;
+  // (auto mode: the fresh rows alone over the threshold decide on the host, before any device work)
+  if (!sd.forced && !host::seed_pays(family, N, M)) {
+    h.made.denied = host::kAppendSlower;
     return false;
   }
   const int32_t ldn = (int32_t)host::append_ldn(h.D);  // (an allocated lattice: N ldn floats exist)
-  DevBuf<float> Yn, kval;
-  DevBuf<int32_t> kidx, redo_list, counts, qrows;
+  DevBuf<float> Yn, kval, Sm;
+  DevBuf<int32_t> kidx, row_map, redo_list, counts, qrows;
   DevBuf<uint8_t> flags;
   Yn.alloc((size_t)N * ldn);
   launch_normalize_rows(h.Y.p, h.ld, Yn.p, ldn, N, h.D, h.stream);
-  // the lists: the base's rows, then empty rows (value 0, id -1) for the new ones
   kval.alloc((size_t)N * k);
   kidx.alloc((size_t)N * k);
-  HIP_CHECK(hipMemcpyAsync(kval.p, base.knn_val.p, (size_t)n_old * k * 4, hipMemcpyDeviceToDevice, h.stream));
-  HIP_CHECK(hipMemcpyAsync(kidx.p, base.knn_idx.p, (size_t)n_old * k * 4, hipMemcpyDeviceToDevice, h.stream));
-  HIP_CHECK(hipMemsetAsync(kval.p + (size_t)n_old * k, 0, (size_t)(N - n_old) * k * 4, h.stream));
-  HIP_CHECK(hipMemsetAsync(kidx.p + (size_t)n_old * k, 0xFF, (size_t)(N - n_old) * k * 4, h.stream));
+  seed_lists(h, sd, k, row_map, kval.p, kidx.p);
   flags.alloc((size_t)N);
-  redo_list.alloc((size_t)n_old);
-  counts.alloc(3);  // redo rows, non-finite rows, merge hits
+  redo_list.alloc((size_t)n_listed);
+  counts.alloc(3);  // flagged rows, non-finite rows, merge hits
   HIP_CHECK(hipMemsetAsync(counts.p, 0, 12, h.stream));
-  launch_append_flags(Yn.p, ldn, n_old, N, kval.p, kidx.p, k, flags.p, redo_list.p, counts.p, h.stream);
+  launch_append_flags(Yn.p, ldn, n_listed, N, kval.p, kidx.p, k, flags.p, redo_list.p, counts.p, h.stream);
   int32_t hc[3] = {0, 0, 0};
   HIP_CHECK(hipMemcpyAsync(hc, counts.p, 8, hipMemcpyDeviceToHost, h.stream));
   sync(h);
-  const int64_t redo = hc[0], nbad = hc[1], m_new = N - n_old;
-  if (!sd.forced && !host::append_pays(family, n_old, m_new, redo)) {
-    h.append.denied = host::kAppendSlower;
+  const int64_t flagged = hc[0], nbad = hc[1];
+  const int64_t redo = fresh_flagged ? flagged - M : flagged;  // (a replaced row's list is empty: always flagged)
+  if (redo < 0) throw std::runtime_error("build_graph_updated: a replaced row was not flagged");
+  if (!sd.forced && !host::seed_pays(family, N, redo + M)) {
+    h.made.denied = host::kAppendSlower;
     return false;
   }
-  // the query list: the redo rows in ascending order, then the new rows
-  std::vector<int32_t> q((size_t)(redo + m_new));
-  if (redo > 0) {
-    HIP_CHECK(hipMemcpyAsync(q.data(), redo_list.p, (size_t)redo * 4, hipMemcpyDeviceToHost, h.stream));
+  std::vector<int32_t> q((size_t)flagged);
+  if (flagged > 0) {
+    HIP_CHECK(hipMemcpyAsync(q.data(), redo_list.p, (size_t)flagged * 4, hipMemcpyDeviceToHost, h.stream));
     sync(h);
-    std::sort(q.begin(), q.begin() + redo);
   }
-  for (int64_t j = 0; j < m_new; ++j) q[(size_t)(redo + j)] = (int32_t)(n_old + j);
+  q = host::seed_query_list(q, sd.fresh);
   const int64_t nq = (int64_t)q.size();
-  qrows.alloc((size_t)nq);
-  HIP_CHECK(hipMemcpyAsync(qrows.p, q.data(), (size_t)nq * 4, hipMemcpyHostToDevice, h.stream));
+  if (nq != redo + M) throw std::runtime_error("build_graph_updated: the redo list and its count disagree");
   const int64_t budget = h.append_scratch_bytes;
   const int64_t lds = host::append_lds(N), chunk = host::append_chunk_rows(N, budget);
   const int64_t nchunks = host::append_chunk_count(nq, chunk);
-  DevBuf<float> Sm;
-  Sm.alloc((size_t)host::append_scratch_floats(nq, N, budget));
+  if (nq > 0) {  // (a removal that left every kept list whole has nothing to score)
+    qrows.alloc((size_t)nq);
+    HIP_CHECK(hipMemcpyAsync(qrows.p, q.data(), (size_t)nq * 4, hipMemcpyHostToDevice, h.stream));
+    Sm.alloc((size_t)host::append_scratch_floats(nq, N, budget));
+  }
   const int cus = device_cus(h.device);
   int64_t scan_bytes = 0;
-  // the phases' times come from events: three per chunk, read once after the loop (no host wait inside it)
-  struct Events {
-    std::vector<hipEvent_t> ev;
-    ~Events() {
-      for (auto e : ev) (void)hipEventDestroy(e);
-    }
-    void mark(hipStream_t s) {
-      hipEvent_t e = nullptr;
-      HIP_CHECK(hipEventCreate(&e));
-      ev.push_back(e);
-      HIP_CHECK(hipEventRecord(e, s));
-    }
-  } marks;
-  marks.ev.reserve((size_t)nchunks * 3);
-  for (int64_t c = 0; c < nchunks; ++c) {
-    int64_t b = 0, e = 0, nb = 0, ne = 0, first_col = 0;
-    host::append_chunk_range(nq, chunk, c, b, e);
-    const int32_t mc = (int32_t)(e - b);
-    marks.mark(h.stream);
-    if (family == host::kFamilyMfma) launch_knn_rows_listed(Yn.p, ldn, N, qrows.p + b, mc, Sm.p, (int32_t)lds, h.stream);
-    else launch_append_scores_butterfly(Yn.p, ldn, N, qrows.p + b, mc, Sm.p, lds, cus, h.stream);
-    if (nbad > 0) launch_append_sanitize(Sm.p, lds, mc, N, h.stream);
-    launch_knn_select_listed(Sm.p, (int32_t)lds, N, k, qrows.p + b, mc, kval.p, kidx.p, h.stream);
-    if (nbad > 0) launch_append_fix_lists(Sm.p, lds, qrows.p + b, mc, k, kval.p, kidx.p, h.stream);
-    marks.mark(h.stream);
-    host::append_chunk_new_part(redo, n_old, b, e, nb, ne, first_col);
-    launch_append_merge(Sm.p, lds, (int32_t)nb, (int32_t)ne, (int32_t)first_col, n_old, flags.p, k, kval.p, kidx.p, counts.p + 2, h.stream);
-    marks.mark(h.stream);  // (the next chunk's scores overwrite Sm behind the merge: one stream, in order)
-    scan_bytes += (ne - nb) * (int64_t)(n_old - redo) * 4;
-  }
-  HIP_CHECK(hipMemcpyAsync(hc + 2, counts.p + 2, 4, hipMemcpyDeviceToHost, h.stream));
-  sync(h);
-  double score_ms = 0, merge_ms = 0;
-  for (size_t i = 0; i + 2 < marks.ev.size(); i += 3) {
-    float a = 0.f, m = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&a, marks.ev[i], marks.ev[i + 1]));
-    HIP_CHECK(hipEventElapsedTime(&m, marks.ev[i + 1], marks.ev[i + 2]));
-    score_ms += a;
-    merge_ms += m;
-  }
-  h.knn_val.swap(kval);
-  h.knn_idx.swap(kidx);
-  h.knn_k = k;
-  h.knn_last = base.knn_last;
-  h.knn_last.k = k;
-  h.knn_fallback_rows = base.knn_fallback_rows;
-  h.score_family = family;
-  const double t3 = now_ms();
-  graph_from_lists(h, N, k);
-  sync(h);
-  h.append.route = host::kRouteIncremental;
-  h.append.new_rows = m_new;
-  h.append.redo_rows = redo;
-  h.append.merged_rows = n_old - redo;
-  h.append.merge_hits = hc[2];
-  h.append.scan_bytes = scan_bytes;
-  h.append.score_ms = score_ms;
-  h.append.merge_ms = merge_ms;
-  h.append.back_ms = now_ms() - t3;
-  h.build_ms = now_ms() - t0;
-  return true;
-}
-
-// The seeded build of osc_create_removed: the handle's anchors -- the base's kept rows -- are on the
-// device in API order.  k_remove_lists writes every kept row's list at its new row with the member ids renumbered and the
-// removed members emptied; the append flags' rule "an id is missing" then marks exactly the rows that lost a member (and
-// the clipped and non-finite rows: a superset, redoing a row is always correct).  Those are scored against all columns in
-// the base's score family, chunk by chunk, and get their k best: the seeded build of an append with no new rows, hence
-// without its merge pass.  Then the back half, unchanged.  false (auto mode only): the planner expects the rebuild to be
-// no slower; nothing but scratch was written and the unseeded build runs.
-static bool build_graph_removed(L& h) {
-  const L::RemoveSeed& sd = *h.remove_seed;
-  const L& base = *sd.base;
-  const int32_t N = (int32_t)h.N, k = base.knn_k;
-  const int32_t family = base.score_family;
-  const double t0 = now_ms();
-  const int32_t ldn = (int32_t)host::append_ldn(h.D);  // (an allocated lattice: N ldn floats exist)
-  DevBuf<float> Yn, kval;
-  DevBuf<int32_t> kidx, new_id, redo_list, counts, qrows;
-  DevBuf<uint8_t> flags;
-  Yn.alloc((size_t)N * ldn);
-  launch_normalize_rows(h.Y.p, h.ld, Yn.p, ldn, N, h.D, h.stream);
-  new_id.alloc((size_t)base.N);
-  HIP_CHECK(hipMemcpyAsync(new_id.p, sd.new_id.data(), (size_t)base.N * 4, hipMemcpyHostToDevice, h.stream));
-  kval.alloc((size_t)N * k);
-  kidx.alloc((size_t)N * k);
-  launch_remove_lists(base.knn_val.p, base.knn_idx.p, base.N, k, new_id.p, kval.p, kidx.p, h.stream);
-  flags.alloc((size_t)N);
-  redo_list.alloc((size_t)N);
-  counts.alloc(2);  // redo rows, non-finite rows
-  HIP_CHECK(hipMemsetAsync(counts.p, 0, 8, h.stream));
-  launch_append_flags(Yn.p, ldn, N, N, kval.p, kidx.p, k, flags.p, redo_list.p, counts.p, h.stream);
-  int32_t hc[2] = {0, 0};
-  HIP_CHECK(hipMemcpyAsync(hc, counts.p, 8, hipMemcpyDeviceToHost, h.stream));
-  sync(h);
-  const int64_t redo = hc[0], nbad = hc[1];
-  if (!sd.forced && !host::remove_pays(family, N, redo)) {
-    h.removed.denied = host::kAppendSlower;
-    return false;
-  }
-  double score_ms = 0;
-  if (redo > 0) {  // the query list: the redo rows in ascending order
-    std::vector<int32_t> q((size_t)redo);
-    HIP_CHECK(hipMemcpyAsync(q.data(), redo_list.p, (size_t)redo * 4, hipMemcpyDeviceToHost, h.stream));
-    sync(h);
-    std::sort(q.begin(), q.end());
-    qrows.alloc((size_t)redo);
-    HIP_CHECK(hipMemcpyAsync(qrows.p, q.data(), (size_t)redo * 4, hipMemcpyHostToDevice, h.stream));
-    const int64_t budget = h.append_scratch_bytes;
-    const int64_t lds = host::append_lds(N), chunk = host::append_chunk_rows(N, budget);
-    const int64_t nchunks = host::append_chunk_count(redo, chunk);
-    DevBuf<float> Sm;
-    Sm.alloc((size_t)host::append_scratch_floats(redo, N, budget));
-    const int cus = device_cus(h.device);
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    struct Events {
-      hipEvent_t* ev;
-      ~Events() {
-        for (int i = 0; i < 2; ++i)
-          if (ev[i]) (void)hipEventDestroy(ev[i]);
-      }
-    } guard{ev};
-    HIP_CHECK(hipEventCreate(&ev[0]));
-    HIP_CHECK(hipEventCreate(&ev[1]));
-    HIP_CHECK(hipEventRecord(ev[0], h.stream));
-    for (int64_t c = 0; c < nchunks; ++c) {  // (the next chunk's scores overwrite Sm behind the select: one stream, in order)
-      int64_t b = 0, e = 0;
-      host::append_chunk_range(redo, chunk, c, b, e);
-      const int32_t mc = (int32_t)(e - b);
-      if (family == host::kFamilyMfma) launch_knn_rows_listed(Yn.p, ldn, N, qrows.p + b, mc, Sm.p, (int32_t)lds, h.stream);
-      else launch_append_scores_butterfly(Yn.p, ldn, N, qrows.p + b, mc, Sm.p, lds, cus, h.stream);
-      if (nbad > 0) launch_append_sanitize(Sm.p, lds, mc, N, h.stream);
-      launch_knn_select_listed(Sm.p, (int32_t)lds, N, k, qrows.p + b, mc, kval.p, kidx.p, h.stream);
-      if (nbad > 0) launch_append_fix_lists(Sm.p, lds, qrows.p + b, mc, k, kval.p, kidx.p, h.stream);
-    }
-    HIP_CHECK(hipEventRecord(ev[1], h.stream));
-    sync(h);  // (q, Sm and the events end here)
-    float ms = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    score_ms = ms;
-  }
-  h.knn_val.swap(kval);
-  h.knn_idx.swap(kidx);
-  h.knn_k = k;
-  h.knn_last = base.knn_last;
-  h.knn_last.k = k;
-  h.knn_fallback_rows = base.knn_fallback_rows;
-  h.score_family = family;
-  const double t3 = now_ms();
-  graph_from_lists(h, N, k);
-  sync(h);
-  h.removed.route = host::kRouteIncremental;
-  h.removed.redo_rows = redo;
-  h.removed.kept_rows = N - redo;
-  h.removed.score_ms = score_ms;
-  h.removed.back_ms = now_ms() - t3;
-  h.build_ms = now_ms() - t0;
-  return true;
-}
-
-// The seeded build of osc_create_updated: the handle's anchors -- the base's rows with the replaced
-// ones overwritten -- are on the device in API order.  k_update_lists copies the base's lists with every member that names
-// a replaced row emptied and the replaced rows' own lists empty; the append flags' rule "an id is missing" then marks the
-// rows that lost a member and the replaced rows (and the clipped and non-finite rows: a superset, redoing a row is always
-// correct).  The query list -- the redo rows other than the replaced ones, ascending, then the replaced rows -- is scored
-// against all columns in the base's score family, chunk by chunk; each chunk's rows get their k best, and every row outside
-// the redo set merges the chunk's replaced columns into its list (k_update_merge: an equal score and a lower index wins).
-// Then the back half, unchanged.  false (auto mode only): the planner expects the rebuild to be no slower; nothing but
-// scratch was written and the unseeded build runs.
-static bool build_graph_updated(L& h) {
-  const L::UpdateSeed& sd = *h.update_seed;
-  const L& base = *sd.base;
-  const int32_t N = (int32_t)h.N, k = base.knn_k;
-  const int32_t family = base.score_family;
-  const int64_t M = (int64_t)sd.ids.size();
-  const double t0 = now_ms();
-  // (auto mode: M alone over the threshold decides on the host, before any device work)
-  if (!sd.forced && !host::update_pays(family, N, M, 0)) {
-    h.updated.denied = host::kAppendSlower;
-    return false;
-  }
-  const int32_t ldn = (int32_t)host::append_ldn(h.D);  // (an allocated lattice: N ldn floats exist)
-  DevBuf<float> Yn, kval;
-  DevBuf<int32_t> kidx, keep, redo_list, counts, qrows;
-  DevBuf<uint8_t> flags;
-  Yn.alloc((size_t)N * ldn);
-  launch_normalize_rows(h.Y.p, h.ld, Yn.p, ldn, N, h.D, h.stream);
-  keep.alloc((size_t)N);
-  HIP_CHECK(hipMemcpyAsync(keep.p, sd.keep.data(), (size_t)N * 4, hipMemcpyHostToDevice, h.stream));
-  kval.alloc((size_t)N * k);
-  kidx.alloc((size_t)N * k);
-  launch_update_lists(base.knn_val.p, base.knn_idx.p, N, k, keep.p, kval.p, kidx.p, h.stream);
-  flags.alloc((size_t)N);
-  redo_list.alloc((size_t)N);
-  counts.alloc(3);  // redo rows (the replaced ones among them), non-finite rows, merge hits
-  HIP_CHECK(hipMemsetAsync(counts.p, 0, 12, h.stream));
-  launch_append_flags(Yn.p, ldn, N, N, kval.p, kidx.p, k, flags.p, redo_list.p, counts.p, h.stream);
-  int32_t hc[3] = {0, 0, 0};
-  HIP_CHECK(hipMemcpyAsync(hc, counts.p, 8, hipMemcpyDeviceToHost, h.stream));
-  sync(h);
-  const int64_t flagged = hc[0], nbad = hc[1], redo = flagged - M;  // (a replaced row's list is empty: always flagged)
-  if (redo < 0) throw std::runtime_error("build_graph_updated: a replaced row was not flagged");
-  if (!sd.forced && !host::update_pays(family, N, M, redo)) {
-    h.updated.denied = host::kAppendSlower;
-    return false;
-  }
-  // the query list: the redo rows other than the replaced ones in ascending order, then the replaced rows
-  std::vector<int32_t> q((size_t)flagged);
-  HIP_CHECK(hipMemcpyAsync(q.data(), redo_list.p, (size_t)flagged * 4, hipMemcpyDeviceToHost, h.stream));
-  sync(h);
-  q.erase(std::remove_if(q.begin(), q.end(), [&](int32_t r) { return sd.keep[(size_t)r] < 0; }), q.end());
-  if ((int64_t)q.size() != redo) throw std::runtime_error("build_graph_updated: the redo list and its count disagree");
-  std::sort(q.begin(), q.end());
-  q.insert(q.end(), sd.ids.begin(), sd.ids.end());
-  const int64_t nq = (int64_t)q.size();
-  qrows.alloc((size_t)nq);
-  HIP_CHECK(hipMemcpyAsync(qrows.p, q.data(), (size_t)nq * 4, hipMemcpyHostToDevice, h.stream));
-  const int64_t budget = h.append_scratch_bytes;
-  const int64_t lds = host::append_lds(N), chunk = host::append_chunk_rows(N, budget);
-  const int64_t nchunks = host::append_chunk_count(nq, chunk);
-  DevBuf<float> Sm;
-  Sm.alloc((size_t)host::append_scratch_floats(nq, N, budget));
-  const int cus = device_cus(h.device);
-  // the phases' times come from events: three per chunk, read once after the loop (no host wait inside it)
-  struct Events {
-    std::vector<hipEvent_t> ev;
-    ~Events() {
-      for (auto e : ev) (void)hipEventDestroy(e);
-    }
-    void mark(hipStream_t s) {
-      hipEvent_t e = nullptr;
-      HIP_CHECK(hipEventCreate(&e));
-      ev.push_back(e);
-      HIP_CHECK(hipEventRecord(e, s));
-    }
-  } marks;
+  Events marks;  // the phases' times come from events: three per chunk, read once after the loop (no host wait inside it)
   marks.ev.reserve((size_t)nchunks * 3);
   for (int64_t c = 0; c < nchunks; ++c) {
     int64_t b = 0, e = 0, nb = 0, ne = 0;
@@ -1168,11 +978,19 @@ static bool build_graph_updated(L& h) {
     launch_knn_select_listed(Sm.p, (int32_t)lds, N, k, qrows.p + b, mc, kval.p, kidx.p, h.stream);
     if (nbad > 0) launch_append_fix_lists(Sm.p, lds, qrows.p + b, mc, k, kval.p, kidx.p, h.stream);
     marks.mark(h.stream);
-    host::update_chunk_replaced_part(redo, b, e, nb, ne);  // (block row r of the chunk scores column qrows[b + r])
-    launch_update_merge(Sm.p, lds, (int32_t)nb, (int32_t)ne, qrows.p + b, N, flags.p, k, kval.p, kidx.p, counts.p + 2, h.stream);
+    // Block row r of the chunk scores column qrows[b + r].  An append's fresh columns are consecutive, n_old + (b + nb -
+    // redo) onwards, and none can win a tie: it keeps the merge kernel that computes the ids and compares strictly (the
+    // general one measured 4-6 % slower on its scan).
+    host::seed_chunk_fresh_part(redo, b, e, nb, ne);
+    if (sd.kind == L::SeedKind::append)
+      launch_append_merge(Sm.p, lds, (int32_t)nb, (int32_t)ne, (int32_t)(n_listed + (b + nb - redo)), n_listed, flags.p, k, kval.p, kidx.p,
+                          counts.p + 2, h.stream);
+    else
+      launch_update_merge(Sm.p, lds, (int32_t)nb, (int32_t)ne, qrows.p + b, n_listed, flags.p, k, kval.p, kidx.p, counts.p + 2, h.stream);
     marks.mark(h.stream);  // (the next chunk's scores overwrite Sm behind the merge: one stream, in order)
+    scan_bytes += (ne - nb) * (n_listed - flagged) * 4;
   }
-  HIP_CHECK(hipMemcpyAsync(hc + 2, counts.p + 2, 4, hipMemcpyDeviceToHost, h.stream));
+  if (M > 0) HIP_CHECK(hipMemcpyAsync(hc + 2, counts.p + 2, 4, hipMemcpyDeviceToHost, h.stream));
   sync(h);  // (q, Sm and the events end here)
   double score_ms = 0, merge_ms = 0;
   for (size_t i = 0; i + 2 < marks.ev.size(); i += 3) {
@@ -1192,13 +1010,14 @@ static bool build_graph_updated(L& h) {
   const double t3 = now_ms();
   graph_from_lists(h, N, k);
   sync(h);
-  h.updated.route = host::kRouteIncremental;
-  h.updated.redo_rows = redo;
-  h.updated.merged_rows = N - flagged;
-  h.updated.merge_hits = hc[2];
-  h.updated.score_ms = score_ms;
-  h.updated.merge_ms = merge_ms;
-  h.updated.back_ms = now_ms() - t3;
+  h.made.route = host::kRouteIncremental;
+  h.made.redo_rows = redo;
+  h.made.kept_rows = n_listed - flagged;
+  h.made.merge_hits = hc[2];
+  h.made.scan_bytes = scan_bytes;
+  h.made.score_ms = score_ms;
+  h.made.merge_ms = merge_ms;
+  h.made.back_ms = now_ms() - t3;
   h.build_ms = now_ms() - t0;
   return true;
 }
@@ -1211,9 +1030,7 @@ static bool build_graph_once(L& h, const float* host_Y) {
   const int32_t N = (int32_t)h.N;
   h.k_eff = std::min<int32_t>(h.k_eff, std::max<int32_t>(1, N - 1));  // lattice.py:60
   host::changed(h.derived, host::Input::graph);  // (the lists below already replace the old graph's)
-  if (h.append_seed != nullptr && build_graph_seeded(h)) return true;  // (osc_create_appended alone sets the seed)
-  if (h.remove_seed != nullptr && build_graph_removed(h)) return true;  // (osc_create_removed alone sets this one)
-  if (h.update_seed != nullptr && build_graph_updated(h)) return true;  // (osc_create_updated alone sets this one)
+  if (h.list_seed != nullptr && build_graph_from_base(h)) return true;  // (create_handle alone sets the seed)
   if (N <= 1) {  // graph.py:30-32
     upload_anchors(h, host_Y);
     alloc_ell(h, 1);

@@ -142,58 +142,39 @@ struct osc_lattice {
   int32_t knn_k = 0;
   int32_t knn_fallback_rows = 0;  // rows of the last build the prefilter could not prove and the exact kernel redid
   KnnBuildPlan knn_last;          // the route of the last build (knn_plan.hpp: plan_knn_build)
-  // osc_create_appended.  k_requested: k as asked for at creation / the last rebuild, before the clamp
-  // to N - 1.  score_family: which arithmetic the kept lists' values come from (host::AppendFamily; from the build's route,
-  // inherited by an appended handle).  append_seed: set only while a handle is being built from a base's lists
-  // (build_graph_once takes its seeded branch then); append: what osc_append_info reports.
+  // The builds seeded from a base's kept lists: osc_create_appended, osc_create_removed, osc_create_updated (DESIGN.md
+  // sections 14.1, 14-16).  k_requested: k as asked for at creation / the last rebuild, before the clamp to N - 1.
+  // score_family: which arithmetic the kept lists' values come from (host::AppendFamily; from the build's route, inherited by
+  // a seeded handle).  list_seed: set only while a handle is being built from a base's lists (build_graph_once takes its seeded
+  // branch then; create_handle alone sets it).  made: how the handle came to be, what osc_append_info / osc_remove_info /
+  // osc_update_info report -- each its own kind, zeros otherwise.
   int32_t k_requested = 0;
   int32_t score_family = 0;
-  struct AppendSeed {
-    const osc_lattice* base = nullptr;  // its lists are read, nothing of it is written
-    int64_t n_old = 0, n_new = 0;
+  enum class SeedKind : int32_t { none = 0, append, remove, update };
+  struct Seed {
+    SeedKind kind = SeedKind::none;
+    const osc_lattice* base = nullptr;  // its anchors and lists are read, nothing of it is written
     bool forced = false;                // mode 1: the planner's thresholds do not apply
     bool seed_lists = false;            // the base's lists seed the build (else only its anchors are taken over)
+    int64_t n_old = 0;                  // rows of the base
+    std::vector<int32_t> row_map;       // per base row.  remove: its row here, -1 for a removed row (host::remove_map);
+                                        // update: its own id, -1 for a replaced row (host::update_ids)
+    std::vector<int32_t> old_of_new;    // remove: per row here, its base row
+    std::vector<int32_t> fresh;         // ascending: the appended rows n_old .. N - 1, none, the replaced rows
+    const int32_t* ids_as_given = nullptr;  // update: the replaced rows in the order of the new vectors (the caller's array)
   };
-  const AppendSeed* append_seed = nullptr;
+  const Seed* list_seed = nullptr;
   int64_t append_scratch_bytes = host::kAppendScratchBytes;  // budget of one chunk's score block (OSC_APPEND_SCRATCH_MB)
-  struct AppendInfo {
+  struct SeedInfo {
+    SeedKind kind = SeedKind::none;
     int32_t route = 0;  // host::AppendRoute
-    int64_t new_rows = 0, merged_rows = 0, redo_rows = 0, merge_hits = 0, scan_bytes = 0;
+    int64_t fresh_rows = 0;    // rows appended / replaced
+    int64_t removed_rows = 0;
+    int64_t kept_rows = 0;     // listed rows that neither were recomputed nor are fresh: append's and update's merged rows
+    int64_t redo_rows = 0, merge_hits = 0, scan_bytes = 0;
     int32_t denied = 0;
     double score_ms = 0, merge_ms = 0, back_ms = 0;
-  } append;
-  // osc_create_removed: the second seed.  remove_seed is set only while a handle is being built from
-  // the kept rows of a base (build_graph_once takes its removed branch then); removed: what osc_remove_info reports.
-  struct RemoveSeed {
-    const osc_lattice* base = nullptr;  // its anchors and lists are read, nothing of it is written
-    std::vector<int32_t> new_id;        // per base row: its row here, -1 for a removed row (host::remove_map)
-    std::vector<int32_t> old_of_new;    // per row here: its base row
-    bool forced = false;                // mode 1: the planner's threshold does not apply
-    bool seed_lists = false;            // the base's lists seed the build (else only its anchors are taken over)
-  };
-  const RemoveSeed* remove_seed = nullptr;
-  struct RemoveInfo {
-    int32_t route = 0;  // host::AppendRoute
-    int64_t removed_rows = 0, kept_rows = 0, redo_rows = 0;
-    int32_t denied = 0;
-    double score_ms = 0, back_ms = 0;
-  } removed;
-  // osc_create_updated: the third seed.  update_seed is set only while a handle is being built from
-  // a base with some rows replaced (build_graph_once takes its updated branch then); updated: what osc_update_info reports.
-  struct UpdateSeed {
-    const osc_lattice* base = nullptr;  // its anchors and lists are read, nothing of it is written
-    std::vector<int32_t> keep;          // per row: its own id, -1 for a replaced row (host::update_ids)
-    std::vector<int32_t> ids;           // the replaced rows, ascending
-    bool forced = false;                // mode 1: the planner's threshold does not apply
-    bool seed_lists = false;            // the base's lists seed the build (else only its anchors are taken over)
-  };
-  const UpdateSeed* update_seed = nullptr;
-  struct UpdateInfo {
-    int32_t route = 0;  // host::AppendRoute
-    int64_t replaced_rows = 0, merged_rows = 0, redo_rows = 0, merge_hits = 0;
-    int32_t denied = 0;
-    double score_ms = 0, merge_ms = 0, back_ms = 0;
-  } updated;
+  } made;
   double build_ms = 0.0;
   int64_t nnz = 0;
   int32_t max_deg = 0;

@@ -6,16 +6,15 @@
 // incremental): a kept row whose list names no removed row keeps it with the ids renumbered -- the renumbering is
 // monotone, so (score desc, index asc) and every tie decision survive it -- and the rows that lost a member, the redo set,
 // are scored against all N' columns in chunks of query rows like an appended build's redo rows.  There is no merge pass:
-// no column is new.  The enums, pitches, chunk arithmetic and thresholds are append_plan.hpp's.
+// no column is new.  The enums, pitches, chunk arithmetic, shared eligibility checks (seed_eligible) and thresholds are
+// append_plan.hpp's.
 #pragma once
 #include "append_plan.hpp"
 
 namespace osc {
 namespace host {
 
-// Why a base cannot seed an incremental removal: AppendDenied's codes, and one of its own behind them
-constexpr int32_t kRemoveTooFewRows = kAppendSlower + 1;  // fewer than two rows are left
-
+// Why a base cannot seed an incremental removal: AppendDenied's codes, the last of them (kRemoveTooFewRows) its own
 inline const char* remove_denied_text(int32_t why) {
   if (why == kRemoveTooFewRows) return "fewer than two rows are left";
   if (why == kAppendKChanges) return "the effective k changes with the new row count";
@@ -55,28 +54,12 @@ inline void remove_inverse(const int32_t* new_id_of_old, int64_t N, int32_t* old
     if (new_id_of_old[i] >= 0) old_of_new[new_id_of_old[i]] = (int32_t)i;
 }
 
-struct RemoveInputs {
-  int64_t N = 0, M = 0;       // rows of the base, distinct rows removed
-  int32_t D = 0;
-  int32_t k_requested = 0;    // k as asked for at the base's creation
-  int32_t knn_k = 0;          // length of the base's kept lists (0: none, or no graph)
-  int32_t family = kFamilyNone;
-  int32_t fallback_rows = 0;  // rows the base's prefilter build handed to its fallback
-  bool comm = false;
-};
+using RemoveInputs = SeedInputs;  // (M: distinct rows removed)
 
 // Eligibility of the incremental route, the threshold aside (it needs the redo count, which the device computes)
 inline int32_t remove_eligible(const RemoveInputs& in) {
   if (in.N < 0 || in.M < 0 || in.N > kAppendMaxRows) return kAppendTooManyRows;
-  if (in.knn_k <= 0 || in.family == kFamilyNone || in.N < 2) return kAppendNoLists;
-  if (in.comm) return kAppendComm;
-  const int64_t left = remove_rows_left(in.N, in.M);
-  if (left < 2) return kRemoveTooFewRows;
-  if (append_k_eff(in.k_requested, left) != in.knn_k) return kAppendKChanges;
-  if (in.knn_k > kAppendListMax) return kAppendKTooLong;
-  if (in.family == kFamilyButterfly && append_ldn(in.D) > kAppendBflyMaxLdn) return kAppendWideRows;
-  if (in.family == kFamilyButterfly && in.fallback_rows > 32) return kAppendMixedLists;
-  return kAppendOk;
+  return seed_eligible(in, remove_rows_left(in.N, in.M));
 }
 
 // The threshold of the automatic route.  The incremental removal costs the new handle, the list pass, the back half and
@@ -88,7 +71,7 @@ inline int32_t remove_eligible(const RemoveInputs& in) {
 //     redo ~ 5000 = N / 200.  N / 256 keeps a margin at both, as it does for append.
 //   mfma (8000 x 64, k 16): 0.34-0.36 ms from 14 to 473 redo rows against 0.46 ms: no crossing up to N / 17.  N / 32.
 inline int64_t remove_max_query_rows(int32_t family, int64_t rows_left) { return append_max_query_rows(family, rows_left); }
-inline bool remove_pays(int32_t family, int64_t rows_left, int64_t redo) { return redo <= remove_max_query_rows(family, rows_left); }
+inline bool remove_pays(int32_t family, int64_t rows_left, int64_t redo) { return seed_pays(family, rows_left, redo); }
 
 }  // namespace host
 }  // namespace osc

@@ -7,8 +7,8 @@
 // redo set) and the replaced rows themselves are scored against all N columns in chunks of query rows, like an appended
 // build's redo rows and new rows; every other row scans its column of the replaced rows' score block for replaced columns
 // that now precede its worst member.  Unlike an appended column a replaced column's index can be BELOW a member's, so an
-// equal score can win there (update_kernels.hip: k_update_merge).  The enums, pitches, chunk arithmetic and thresholds are
-// append_plan.hpp's.
+// equal score can win there (update_kernels.hip: k_update_merge).  The enums, pitches, chunk arithmetic, shared
+// eligibility checks (seed_eligible), query list and thresholds are append_plan.hpp's.
 #pragma once
 #include "append_plan.hpp"
 
@@ -35,26 +35,12 @@ inline int32_t update_ids(const Id* ids, int64_t n, int64_t N, int32_t* keep) {
   return kUpdateIdsOk;
 }
 
-struct UpdateInputs {
-  int64_t N = 0, M = 0;       // rows of the base, rows replaced
-  int32_t D = 0;
-  int32_t k_requested = 0;    // k as asked for at the base's creation
-  int32_t knn_k = 0;          // length of the base's kept lists (0: none, or no graph)
-  int32_t family = kFamilyNone;
-  int32_t fallback_rows = 0;  // rows the base's prefilter build handed to its fallback
-  bool comm = false;
-};
+using UpdateInputs = SeedInputs;  // (M: rows replaced)
 
 // Eligibility of the incremental route, the threshold aside (it needs the redo count, which the device computes)
 inline int32_t update_eligible(const UpdateInputs& in) {
   if (in.N < 0 || in.M < 0 || in.M > in.N || in.N > kAppendMaxRows) return kAppendTooManyRows;
-  if (in.knn_k <= 0 || in.family == kFamilyNone || in.N < 2) return kAppendNoLists;
-  if (in.comm) return kAppendComm;
-  if (append_k_eff(in.k_requested, in.N) != in.knn_k) return kAppendKChanges;  // (a rebuild with another k came between)
-  if (in.knn_k > kAppendListMax) return kAppendKTooLong;
-  if (in.family == kFamilyButterfly && append_ldn(in.D) > kAppendBflyMaxLdn) return kAppendWideRows;
-  if (in.family == kFamilyButterfly && in.fallback_rows > 32) return kAppendMixedLists;
-  return kAppendOk;
+  return seed_eligible(in, in.N);  // (k changes: a rebuild with another k came between)
 }
 
 // The threshold of the automatic route.  The incremental update costs the new handle, the list pass, the back half, the
@@ -77,17 +63,7 @@ inline int32_t update_eligible(const UpdateInputs& in) {
 //     against [0.47, 0.50] and [0.38, 0.40] against [0.47, 0.50].
 //   The merge scan is 0.05-0.5 ms of any of these; one replaced row costs what one removed row costs (6.75 against 6.73 ms).
 inline int64_t update_max_query_rows(int32_t family, int64_t N) { return append_max_query_rows(family, N); }
-inline bool update_pays(int32_t family, int64_t N, int64_t M, int64_t redo) {
-  return redo + M <= update_max_query_rows(family, N);
-}
-
-// The part of a chunk [begin, end) of the query list that holds REPLACED rows, given that the list is the `redo` other
-// rows followed by the M replaced ones: query rows [nb, ne) of the chunk-local block, whose ids are entries
-// [begin + nb, begin + ne) of the query list.
-inline void update_chunk_replaced_part(int64_t redo, int64_t begin, int64_t end, int64_t& nb, int64_t& ne) {
-  int64_t first_col = 0;  // (an appended build's new rows stand where the replaced rows stand here; their columns do not)
-  append_chunk_new_part(redo, 0, begin, end, nb, ne, first_col);
-}
+inline bool update_pays(int32_t family, int64_t N, int64_t M, int64_t redo) { return seed_pays(family, N, redo + M); }
 
 }  // namespace host
 }  // namespace osc

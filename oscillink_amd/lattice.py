@@ -1124,6 +1124,37 @@ class OscillinkLattice:
     # ------------------------------------------------------------------ append (not in the reference)
     _APPEND_MODES = {"auto": 0, "incremental": 1, "rebuild": 2}
 
+    def _mode_code(self, mode: str) -> int:
+        if mode not in self._APPEND_MODES:
+            raise ValueError("mode must be 'auto', 'incremental' or 'rebuild'")
+        return self._APPEND_MODES[mode]
+
+    def _become(self, op: str, cannot: str, create, rows: int, N_new: int, B_new: np.ndarray, chain_nodes) -> None:
+        """What append, remove and update share once their arguments are checked: `create(new_h)` calls the operation's
+        osc_create_* on this lattice's handle; lambdas, psi, the gates `B_new` and the chain (on `chain_nodes`) are carried
+        to the new handle, which then replaces this object's.  A failure leaves the lattice exactly as it was."""
+        if getattr(self, "_has_comm", False):
+            raise nat.NativeError(f"{op}: a lattice with a communicator cannot {cannot} (multi-rank handles are out of scope)")
+        new_h = nat.Handle()
+        t0 = time.time()
+        create(new_h)
+        self._carry_settings_to(new_h, B_new, chain_nodes)
+        if chain_nodes is not None:
+            self._chain_nodes = [int(c) for c in chain_nodes]
+        self._swap_handle(new_h, N_new, B_new, t0)
+        info = getattr(self, op + "_info")()
+        self._log(op, {"rows": rows, "N": self.N, "route": info["route"], "redo_rows": info["redo_rows"]})
+
+    def _seeded_info(self, fn: str, keys: str) -> dict[str, Any]:
+        """One of osc_append_info / osc_remove_info / osc_update_info: `keys` names its outputs in order (route,
+        score_family and denied are int32, the *_ms doubles, the counts int64)."""
+        slots = [(key, C.c_double(0.0) if key.endswith("_ms") else
+                  C.c_int32(0) if key in ("route", "score_family", "denied") else C.c_int64(0)) for key in keys.split()]
+        self._call(fn, *[C.byref(v) for _, v in slots])
+        info: dict[str, Any] = {key: float(v.value) if key.endswith("_ms") else int(v.value) for key, v in slots}
+        info["score_family"] = ("none", "mfma", "butterfly")[info["score_family"]]
+        return info
+
     def append(self, Ynew: np.ndarray, gates: Optional[np.ndarray] = None, *, mode: str = "auto") -> np.ndarray:
         """Add the rows of `Ynew` (M x D) behind the lattice's own and return their ids N .. N + M - 1.
 
@@ -1133,8 +1164,7 @@ class OscillinkLattice:
         modes stay.  mode "incremental" grows the kNN lists from the kept ones and raises where that is not possible,
         "rebuild" builds the concatenated anchors from scratch on the device, "auto" lets the planner choose
         (`append_info()` says which).  Only `Ynew` crosses the bus.  A failure leaves the lattice exactly as it was."""
-        if mode not in self._APPEND_MODES:
-            raise ValueError("mode must be 'auto', 'incremental' or 'rebuild'")
+        code = self._mode_code(mode)
         if not isinstance(Ynew, np.ndarray) or Ynew.ndim != 2:
             raise ValueError("Ynew must be a 2D numpy array")
         if Ynew.shape[1] != self.D:
@@ -1147,21 +1177,13 @@ class OscillinkLattice:
                 raise ValueError("gates length mismatch M")
         if M == 0:
             return np.empty(0, dtype=np.int64)
-        if getattr(self, "_has_comm", False):
-            raise nat.NativeError("append: a lattice with a communicator cannot grow (multi-rank handles are out of scope)")
-        Yc = np.ascontiguousarray(Ynew, dtype=np.float32)
-        L = nat.lib()
-        new_h = nat.Handle()
-        t0 = time.time()
-        nat.check(L.osc_create_appended(self._h, nat.f32(Yc), M, self._APPEND_MODES[mode], C.byref(new_h)), None,
-                  "osc_create_appended")
-        N_new = self.N + M
+        def create(new_h) -> None:
+            Yc = np.ascontiguousarray(Ynew, dtype=np.float32)
+            nat.check(nat.lib().osc_create_appended(self._h, nat.f32(Yc), M, code, C.byref(new_h)), None, "osc_create_appended")
+
+        ids = np.arange(self.N, self.N + M, dtype=np.int64)
         B_new = np.concatenate([self._B, np.ones(M, dtype=np.float32) if g_new is None else g_new]).astype(np.float32)
-        self._carry_settings_to(new_h, B_new, self._chain_nodes)
-        ids = np.arange(self.N, N_new, dtype=np.int64)
-        self._swap_handle(new_h, N_new, B_new, t0)
-        info = self.append_info()
-        self._log("append", {"rows": M, "N": self.N, "route": info["route"], "redo_rows": info["redo_rows"]})
+        self._become("append", "grow", create, M, self.N + M, B_new, self._chain_nodes)
         return ids
 
     def _carry_settings_to(self, new_h, B_new: np.ndarray, chain_nodes) -> None:
@@ -1203,15 +1225,8 @@ class OscillinkLattice:
     def append_info(self) -> dict[str, Any]:
         """How the handle came to be (osc_append_info): route 0 = not by `append`, 1 = incremental, 2 = rebuild; the score
         family of its kNN lists ("mfma" / "butterfly"); the incremental route's phases in ms."""
-        route, fam, denied = C.c_int32(0), C.c_int32(0), C.c_int32(0)
-        new, merged, redo, hits, scan = (C.c_int64(0) for _ in range(5))
-        sc, mg, bk = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
-        self._call("osc_append_info", C.byref(route), C.byref(new), C.byref(merged), C.byref(redo), C.byref(fam), C.byref(sc),
-                   C.byref(mg), C.byref(bk), C.byref(hits), C.byref(scan), C.byref(denied))
-        return {"route": int(route.value), "new_rows": int(new.value), "merged_rows": int(merged.value),
-                "redo_rows": int(redo.value), "score_family": ("none", "mfma", "butterfly")[int(fam.value)],
-                "score_ms": float(sc.value), "merge_ms": float(mg.value), "back_half_ms": float(bk.value),
-                "merge_hits": int(hits.value), "merge_scan_bytes": int(scan.value), "denied": int(denied.value)}
+        return self._seeded_info("osc_append_info", "route new_rows merged_rows redo_rows score_family score_ms merge_ms "
+                                 "back_half_ms merge_hits merge_scan_bytes denied")
 
     # ------------------------------------------------------------------ remove (not in the reference; DESIGN.md section 15)
     def remove(self, ids, *, mode: str = "auto") -> np.ndarray:
@@ -1225,8 +1240,7 @@ class OscillinkLattice:
         lists from the kept ones and raises where that is not possible, "rebuild" builds the kept anchors from scratch on the
         device, "auto" lets the planner choose (`remove_info()` says which).  No anchor crosses the bus.  A failure leaves
         the lattice exactly as it was."""
-        if mode not in self._APPEND_MODES:
-            raise ValueError("mode must be 'auto', 'incremental' or 'rebuild'")
+        code = self._mode_code(mode)
         arr = np.asarray(ids)
         if arr.size == 0:
             arr = arr.astype(np.int64)
@@ -1249,21 +1263,13 @@ class OscillinkLattice:
             if (chain_new < 0).any():
                 raise ValueError("ids name a node of the chain: clear_chain() first (dropping a node from a weighted path has "
                                  "no single meaning)")
-        if getattr(self, "_has_comm", False):
-            raise nat.NativeError("remove: a lattice with a communicator cannot shrink (multi-rank handles are out of scope)")
-        gone = np.ascontiguousarray(np.nonzero(~keep)[0], dtype=np.int32)
-        L = nat.lib()
-        new_h = nat.Handle()
-        t0 = time.time()
-        nat.check(L.osc_create_removed(self._h, nat.i32(gone), int(gone.size), self._APPEND_MODES[mode], C.byref(new_h)), None,
-                  "osc_create_removed")
+        def create(new_h) -> None:
+            gone = np.ascontiguousarray(np.nonzero(~keep)[0], dtype=np.int32)
+            nat.check(nat.lib().osc_create_removed(self._h, nat.i32(gone), int(gone.size), code, C.byref(new_h)), None,
+                      "osc_create_removed")
+
         B_new = np.ascontiguousarray(self._B[keep], dtype=np.float32)
-        self._carry_settings_to(new_h, B_new, chain_new)
-        if chain_new is not None:
-            self._chain_nodes = [int(c) for c in chain_new]
-        self._swap_handle(new_h, self.N - M, B_new, t0)
-        info = self.remove_info()
-        self._log("remove", {"rows": M, "N": self.N, "route": info["route"], "redo_rows": info["redo_rows"]})
+        self._become("remove", "shrink", create, M, self.N - M, B_new, chain_new)
         return new_id_of_old
 
     def remove_info(self) -> dict[str, Any]:
@@ -1272,14 +1278,8 @@ class OscillinkLattice:
         ms; why the planner did not take the incremental route (0: it did, or was not asked).  It describes the creation of
         the handle, as `append_info()` does: a later `append` starts a new handle (route 0 here), while a later
         `rebuild_graph` keeps the handle and with it this record, although the graph is then the rebuild's."""
-        route, fam, denied = C.c_int32(0), C.c_int32(0), C.c_int32(0)
-        gone, kept, redo = (C.c_int64(0) for _ in range(3))
-        sc, bk = C.c_double(0.0), C.c_double(0.0)
-        self._call("osc_remove_info", C.byref(route), C.byref(gone), C.byref(kept), C.byref(redo), C.byref(fam), C.byref(sc),
-                   C.byref(bk), C.byref(denied))
-        return {"route": int(route.value), "removed_rows": int(gone.value), "kept_rows": int(kept.value),
-                "redo_rows": int(redo.value), "score_family": ("none", "mfma", "butterfly")[int(fam.value)],
-                "score_ms": float(sc.value), "back_half_ms": float(bk.value), "denied": int(denied.value)}
+        return self._seeded_info("osc_remove_info", "route removed_rows kept_rows redo_rows score_family score_ms back_half_ms "
+                                 "denied")
 
     # ------------------------------------------------------------------ update (not in the reference; DESIGN.md section 16)
     def update(self, ids, Ynew: np.ndarray, gates: Optional[np.ndarray] = None, *, mode: str = "auto") -> np.ndarray:
@@ -1293,8 +1293,7 @@ class OscillinkLattice:
         stay.  mode "incremental" keeps the kNN lists that name no replaced row and raises where that is not possible,
         "rebuild" builds the changed anchors from scratch on the device, "auto" lets the planner choose (`update_info()`
         says which).  Only `ids` and `Ynew` cross the bus.  A failure leaves the lattice exactly as it was."""
-        if mode not in self._APPEND_MODES:
-            raise ValueError("mode must be 'auto', 'incremental' or 'rebuild'")
+        code = self._mode_code(mode)
         arr = np.asarray(ids)
         if arr.size == 0:
             arr = arr.astype(np.int64)
@@ -1319,22 +1318,16 @@ class OscillinkLattice:
                 raise ValueError("gates length mismatch M")
         if M == 0:
             return arr
-        if getattr(self, "_has_comm", False):
-            raise nat.NativeError("update: a lattice with a communicator cannot change rows (multi-rank handles are out of scope)")
-        Yc = np.ascontiguousarray(Ynew, dtype=np.float32)
-        i32 = np.ascontiguousarray(arr, dtype=np.int32)
-        L = nat.lib()
-        new_h = nat.Handle()
-        t0 = time.time()
-        nat.check(L.osc_create_updated(self._h, nat.i32(i32), nat.f32(Yc), M, self._APPEND_MODES[mode], C.byref(new_h)), None,
-                  "osc_create_updated")
+        def create(new_h) -> None:
+            Yc = np.ascontiguousarray(Ynew, dtype=np.float32)
+            i32 = np.ascontiguousarray(arr, dtype=np.int32)
+            nat.check(nat.lib().osc_create_updated(self._h, nat.i32(i32), nat.f32(Yc), M, code, C.byref(new_h)), None,
+                      "osc_create_updated")
+
         B_new = np.array(self._B, dtype=np.float32)
         if g_new is not None:
             B_new[arr] = g_new
-        self._carry_settings_to(new_h, B_new, self._chain_nodes)
-        self._swap_handle(new_h, self.N, B_new, t0)
-        info = self.update_info()
-        self._log("update", {"rows": M, "N": self.N, "route": info["route"], "redo_rows": info["redo_rows"]})
+        self._become("update", "change rows", create, M, self.N, B_new, self._chain_nodes)
         return arr
 
     def update_info(self) -> dict[str, Any]:
@@ -1343,15 +1336,8 @@ class OscillinkLattice:
         family of its kNN lists; the incremental route's phases in ms; the list entries the merge took; why the planner did
         not take the incremental route (0: it did, or was not asked).  It describes the creation of the handle, as
         `append_info()` and `remove_info()` do."""
-        route, fam, denied = C.c_int32(0), C.c_int32(0), C.c_int32(0)
-        rep, merged, redo, hits = (C.c_int64(0) for _ in range(4))
-        sc, mg, bk = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
-        self._call("osc_update_info", C.byref(route), C.byref(rep), C.byref(merged), C.byref(redo), C.byref(fam), C.byref(sc),
-                   C.byref(mg), C.byref(bk), C.byref(hits), C.byref(denied))
-        return {"route": int(route.value), "replaced_rows": int(rep.value), "merged_rows": int(merged.value),
-                "redo_rows": int(redo.value), "score_family": ("none", "mfma", "butterfly")[int(fam.value)],
-                "score_ms": float(sc.value), "merge_ms": float(mg.value), "back_half_ms": float(bk.value),
-                "merge_hits": int(hits.value), "denied": int(denied.value)}
+        return self._seeded_info("osc_update_info", "route replaced_rows merged_rows redo_rows score_family score_ms merge_ms "
+                                 "back_half_ms merge_hits denied")
 
     # ------------------------------------------------------------------ persistence (lattice.py:582-726)
     def _provenance(self) -> str:

@@ -102,18 +102,34 @@ int main() {
           const long long nc = append_chunk_count(nq, chunk);
           if (nq == 0 && nc != 0) return fail("chunks of nothing", cols, nc);
           if (nc > 4096) continue;  // (walking them adds nothing)
+          // the query list, whose fresh entries are the column ids the merge computes as n_old + (b + nb - redo) + j: `redo`
+          // old rows in the device's (any) order, then the new rows (where the case has that many old rows; the arithmetic
+          // below is asserted in every case)
+          std::vector<int32_t> q;
+          if (redo <= n_old) {
+            std::vector<int32_t> flagged, fresh;
+            for (long long j = redo - 1; j >= 0; --j) flagged.push_back((int32_t)j);  // (here: descending)
+            for (long long j = 0; j < m; ++j) fresh.push_back((int32_t)(n_old + j));
+            q = seed_query_list(flagged, fresh);
+            if ((long long)q.size() != nq) return fail("query list length", (long long)q.size(), nq);
+            for (long long j = 0; j < redo; ++j)
+              if (q[(size_t)j] != (int32_t)j) return fail("redo rows ascending", j, q[(size_t)j]);
+          }
           long long at = 0, new_seen = 0;
           for (long long c = 0; c < nc; ++c) {
-            int64_t b, e, nb, ne, fc;
+            int64_t b, e, nb, ne;
             append_chunk_range(nq, chunk, c, b, e);
             if (b != at || e <= b || e - b > chunk || e > nq) return fail("chunk range", c, b);
             if ((e - b) > fl / append_lds(cols)) return fail("chunk beyond scratch", c, e - b);
-            append_chunk_new_part(redo, n_old, b, e, nb, ne, fc);
+            seed_chunk_fresh_part(redo, b, e, nb, ne);
             if (nb < 0 || nb > ne || ne != e - b) return fail("new part", c, nb);
             if (ne > nb) {
-              if (fc != n_old + new_seen) return fail("first new column", c, fc);
+              // entries [b + nb, b + ne) of the query list are the columns n_old + new_seen, ...: none skipped, none twice
+              if (b + nb - redo != new_seen) return fail("first new column", c, b + nb - redo);
               if (b + nb < redo) return fail("new part holds a redo row", c, nb);
-              if (fc + (ne - nb) > cols) return fail("new column past the lattice", c, fc);
+              if (n_old + new_seen + (ne - nb) > cols) return fail("new column past the lattice", c, n_old + new_seen);
+              for (long long j = nb; j < ne && !q.empty(); ++j)
+                if (q[(size_t)(b + j)] != n_old + new_seen + (j - nb)) return fail("new column id", c, q[(size_t)(b + j)]);
             }
             new_seen += ne - nb;
             at = e;

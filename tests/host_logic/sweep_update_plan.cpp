@@ -1,7 +1,9 @@
 // Sweep of update_plan.hpp (the route and sizes of osc_create_updated): the id check against a brute-force one (any order,
 // extremes, n = 0, ids at 0 and N - 1, duplicates as an error of their own, int32 and int64 ids), the eligibility table row
-// by row, the threshold, and the chunks of the query list with the replaced rows' part of each chunk.  Run under
-// -fsanitize=address,undefined.
+// by row, the threshold, and the chunks of the query list with the replaced rows' part of each chunk; and what append,
+// remove and update share (append_plan.hpp): the query list and the fresh part of a chunk against a brute-force
+// construction, for all three kinds.  Run under -fsanitize=address,undefined.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -52,8 +54,76 @@ static int check_ids(const std::vector<Id>& ids, long long N) {
   return 0;
 }
 
+// seed_query_list and seed_chunk_fresh_part against the definition: n rows, the rows `flagged` marks and the ascending
+// `fresh` rows (among the flagged ones or not); the list is every flagged row that is not fresh, ascending, then the fresh
+// rows, and position p of it is fresh iff p >= redo.  Chunks of `chunk` rows: edges before, inside and after the fresh part.
+static int check_query_list(long long n, const std::vector<char>& flagged, const std::vector<int32_t>& fresh, long long n_old,
+                            long long& cases) {
+  std::vector<char> is_fresh((size_t)n, 0);
+  for (int32_t f : fresh) is_fresh[(size_t)f] = 1;
+  std::vector<int32_t> expect, given;
+  for (long long i = 0; i < n; ++i)
+    if (flagged[(size_t)i] && !is_fresh[(size_t)i]) expect.push_back((int32_t)i);
+  const long long redo = (long long)expect.size();
+  for (long long i = 0; i < n; ++i)
+    if (is_fresh[(size_t)i]) expect.push_back((int32_t)i);
+  for (long long i = n - 1; i >= 0; --i)  // the device's order is any order: descending, the odd rows first
+    if (flagged[(size_t)i] && (i & 1)) given.push_back((int32_t)i);
+  for (long long i = n - 1; i >= 0; --i)
+    if (flagged[(size_t)i] && !(i & 1)) given.push_back((int32_t)i);
+  const std::vector<int32_t> q = seed_query_list(given, fresh);
+  if (q != expect) return fail("query list", n, redo);
+  const long long nq = (long long)q.size();
+  for (long long chunk : {1LL, 2LL, 3LL, 5LL, 128LL}) {
+    long long fresh_at = redo;
+    for (long long c = 0; c < append_chunk_count(nq, chunk); ++c) {
+      int64_t b, e, nb, ne;
+      append_chunk_range(nq, chunk, c, b, e);
+      seed_chunk_fresh_part(redo, b, e, nb, ne);
+      if (nb < 0 || nb > ne || ne != e - b) return fail("fresh part bounds", nb, ne);
+      for (long long r = 0; r < e - b; ++r)  // block row r of the chunk: in the fresh part iff its row is fresh
+        if ((r >= nb && r < ne) != (is_fresh[(size_t)q[(size_t)(b + r)]] != 0)) return fail("fresh part membership", c, r);
+      for (long long r = nb; r < ne; ++r, ++fresh_at) {
+        if (q[(size_t)(b + r)] != fresh[(size_t)(fresh_at - redo)]) return fail("fresh part order", c, r);
+        if (n_old >= 0 && q[(size_t)(b + r)] != n_old + (fresh_at - redo)) return fail("appended column id", c, r);  // append: n_old + j
+      }
+      ++cases;
+    }
+    if (fresh_at != nq) return fail("fresh parts do not cover", fresh_at, nq);
+  }
+  return 0;
+}
+
 int main() {
   long long cases = 0;
+  // ---- the shared query list: append (fresh rows behind the listed ones, never flagged), remove (none), update (fresh
+  // rows among the flagged ones: interleaved with the others, below them, above them) at redo = 0, 1 and many ----
+  for (long long n : {2LL, 9LL, 64LL, 301LL})
+    for (int pattern = 0; pattern < 3; ++pattern) {  // flagged among the listed rows: none, one, every third
+      auto flag = [&](long long i) { return pattern == 1 ? i == n / 3 : pattern == 2 ? i % 3 == 1 : false; };
+      for (long long m : {1LL, 2LL, 7LL}) {  // append: rows n .. n + m - 1 are fresh
+        std::vector<char> fl((size_t)(n + m), 0);
+        std::vector<int32_t> fresh;
+        for (long long i = 0; i < n; ++i) fl[(size_t)i] = flag(i);
+        for (long long j = 0; j < m; ++j) fresh.push_back((int32_t)(n + j));
+        if (check_query_list(n + m, fl, fresh, n, cases)) return 1;
+      }
+      {  // remove: no fresh row
+        std::vector<char> fl((size_t)n, 0);
+        for (long long i = 0; i < n; ++i) fl[(size_t)i] = flag(i);
+        if (check_query_list(n, fl, {}, -1, cases)) return 1;
+      }
+      for (int where = 0; where < 3; ++where)  // update: fresh rows interleaved with, below, above the other flagged rows
+        for (long long m : {1LL, 2LL, 5LL}) {
+          if (m > n) continue;
+          std::vector<char> fl((size_t)n, 0);
+          std::vector<int32_t> fresh;
+          for (long long j = 0; j < m; ++j) fresh.push_back((int32_t)(where == 0 ? j * (n / m) : where == 1 ? j : n - m + j));
+          for (long long i = 0; i < n; ++i) fl[(size_t)i] = flag(i);
+          for (int32_t f : fresh) fl[(size_t)f] = 1;  // (a replaced row's list is empty: always flagged)
+          if (check_query_list(n, fl, fresh, -1, cases)) return 1;
+        }
+    }
   // ---- the id map ----
   for (long long N : {1LL, 2LL, 3LL, 17LL, 128LL, 129LL, 1000LL}) {
     if (check_ids<int32_t>({}, N)) return 1;  // n = 0: the identity
@@ -179,7 +249,7 @@ int main() {
             append_chunk_range(nq, chunk, c, b, e);
             if (b != at || e <= b || e - b > chunk || e > nq) return fail("chunk range", c, b);
             if ((e - b) > fl / append_lds(N)) return fail("chunk beyond scratch", c, e - b);
-            update_chunk_replaced_part(redo, b, e, nb, ne);
+            seed_chunk_fresh_part(redo, b, e, nb, ne);
             if (nb < 0 || nb > ne || ne != e - b) return fail("replaced part bounds", nb, ne);
             if (nb < ne) {  // entries [b + nb, b + ne) of the query list: replaced rows only, none skipped
               if (b + nb != replaced_at) return fail("replaced part start", b + nb, replaced_at);
