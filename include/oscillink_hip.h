@@ -176,6 +176,12 @@ int osc_graph_stats(osc_handle h, int64_t* nnz, int32_t* max_deg, double* build_
  * one-launch small-lattice CG since creation */
 int osc_build_info(osc_handle h, int32_t* prefilter, int32_t* fallback_rows, int64_t* small_solves);
 
+/* the one-launch solve's plan for an N x D lattice: cols = columns per workgroup (0: general path), workgroups, LDS bytes per
+ * workgroup (both 0 with cols = 0).  Pure: takes no handle and needs no device (csrc/small_plan.hpp).  A handle follows it
+ * unless it has a communicator, a padded row pitch (OSC_LD), OSC_SMALL_PATH=0, or the solve asks for more than 4096
+ * iterations.  OSC_E_INVALID for N < 1 or D < 1.  Any pointer may be NULL. */
+int osc_small_plan(int32_t N, int32_t D, int32_t* cols, int32_t* workgroups, int64_t* lds_bytes);
+
 /* internal row order of the last graph: reordered != 0 -> the rows are stored in BFS (locality-preserving) order, which
  * is invisible at this API (every call speaks the caller's row ids); clustering = sampled local clustering
  * coefficient that decided it (OSC_REORDER=0/1 overrides the automatic choice) */

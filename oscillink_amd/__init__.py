@@ -7,6 +7,7 @@ from .lattice import OscillinkLattice, __version__, json_line_logger  # noqa: F4
 from .receipts import verify_receipt, verify_receipt_mode  # noqa: F401
 from .diffusion import compute_diffusion_gates, compute_diffusion_gates_many  # noqa: F401
 from .corpus import Corpus  # noqa: F401
+from ._native import small_plan  # noqa: F401
 
 Oscillink = OscillinkLattice
 
@@ -19,4 +20,5 @@ __all__ = [
     "compute_diffusion_gates_many",
     "Corpus",
     "json_line_logger",
+    "small_plan",
 ]

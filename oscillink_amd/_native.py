@@ -72,6 +72,7 @@ SIGNATURES = {
     "osc_rebuild_graph": (C.c_int, [Handle, C.c_int32, C.c_float, C.c_int32, C.c_int64]),
     "osc_graph_stats": (C.c_int, [Handle, c_i64p, c_i32p, c_f64p]),
     "osc_build_info": (C.c_int, [Handle, c_i32p, c_i32p, c_i64p]),
+    "osc_small_plan": (C.c_int, [C.c_int32, C.c_int32, c_i32p, c_i32p, c_i64p]),
     "osc_order_info": (C.c_int, [Handle, c_i32p, c_f64p]),
     "osc_get_row_order": (C.c_int, [Handle, c_i32p]),
     "osc_spmm_plan": (C.c_int, [Handle, c_i32p, c_i32p, c_i32p]),
@@ -188,6 +189,14 @@ def device_count() -> int:
     n = C.c_int32(0)
     lib().osc_device_count(C.byref(n))
     return int(n.value)
+
+
+def small_plan(N: int, D: int) -> dict:
+    """The one-launch LDS solve's plan for an N x D lattice (osc_small_plan; needs no device): `cols` columns per
+    workgroup (0: the general path), `workgroups`, `lds_bytes` per workgroup."""
+    cols, wgs, lds = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+    check(lib().osc_small_plan(int(N), int(D), C.byref(cols), C.byref(wgs), C.byref(lds)), None, "osc_small_plan")
+    return {"cols": int(cols.value), "workgroups": int(wgs.value), "lds_bytes": int(lds.value)}
 
 
 _PINNED_MIN_BYTES = 8 << 20

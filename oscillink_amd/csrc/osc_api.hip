@@ -542,6 +542,15 @@ int osc_build_info(osc_handle h, int32_t* prefilter, int32_t* fallback_rows, int
   });
 }
 
+int osc_small_plan(int32_t N, int32_t D, int32_t* cols, int32_t* workgroups, int64_t* lds_bytes) {
+  if (N < 1 || D < 1) return OSC_E_INVALID;
+  const host::SmallPlan p = host::small_plan(N, D);  // (pure: no handle, no device)
+  if (cols) *cols = p.cols;
+  if (workgroups) *workgroups = p.workgroups;
+  if (lds_bytes) *lds_bytes = p.lds_bytes;
+  return OSC_OK;
+}
+
 int osc_apply_info(osc_handle h, int32_t* src_blocks, int64_t* blocked_applies) {
   return guarded(h, [&](L& l) {
     if (src_blocks) *src_blocks = l.last_plan.src_blocks;

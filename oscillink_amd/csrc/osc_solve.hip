@@ -140,8 +140,9 @@ void for_windows(Args a, F&& launch) {
 // lattice does not fit that path (or its barrier timed out) and the general path must run.
 bool run_cg_small(L& h, const OpParams& op, const CgBuffers& b, bool with_path, int max_iters, float tol,
                   CgResult& out) {
-  if (!h.small_path || h.comm != nullptr || b.c0 != 0 || b.c1 != h.dcols || b.ld != h.dcols || max_iters > 4096) return false;
-  const int C = small_pick_cols((int32_t)h.N, b.ld);
+  if (!h.small_path || h.comm != nullptr || b.c0 != 0 || b.c1 != h.dcols || b.ld != h.dcols || max_iters > host::kSmallMaxIters)
+    return false;
+  const int C = host::small_pick_cols((int32_t)h.N, b.ld);
   if (C <= 0) return false;
   const size_t nslots = (size_t)max_iters + 2;
   const size_t nctl = 2 * nslots + 2;  // [residual slots | arrival counters | status | finish counter]

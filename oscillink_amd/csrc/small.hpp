@@ -1,5 +1,6 @@
 #pragma once
 #include "common.hpp"
+#include "small_plan.hpp"
 
 namespace osc {
 
@@ -25,9 +26,7 @@ struct SmallArgs {
   float tol;
 };
 
-// columns per workgroup (0 = the lattice does not fit the one-launch path)
-int small_pick_cols(int32_t N, int32_t ld);
-size_t small_lds_bytes(int32_t N, int C);
+// (the plan -- columns per workgroup, workgroups, LDS bytes -- is small_plan.hpp's)
 void launch_settle_small(const SmallArgs& a, int C, hipStream_t s);
 void launch_transpose_ell(const int32_t* col, const float* w, int32_t N, int32_t width, int32_t* col_t, float* w_t,
                           hipStream_t s);

@@ -22,8 +22,8 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   return v;
 }
 
-constexpr int T = 512;  // threads per workgroup: one row per thread per sweep keeps the gather latency chain short
-constexpr int NW = T / 64;
+constexpr int T = host::kSmallThreads;  // threads per workgroup (small_plan.hpp)
+constexpr int NW = host::kSmallWaves;
 
 // block-wide sum of C per-thread partials -> every thread gets the totals
 template <int C>
@@ -242,25 +242,6 @@ __global__ __launch_bounds__(T) void k_settle_small(const SmallArgs a) {
 
 }  // namespace
 
-size_t small_lds_bytes(int32_t N, int C) { return (size_t)N * C * 4 * sizeof(float) + NW * C * sizeof(double) + 64; }
-
-// every workgroup must be resident at once (counter barrier with a timeout that falls back to the general path)
-int small_pick_cols(int32_t N, int32_t ld) {
-  for (int C : {4, 2, 1}) {
-    const int blocks = (ld + C - 1) / C;
-    // one column per workgroup leaves most of the chip idle behind long serial row loops: past N = 6000 the general
-    // multi-launch path is faster (measured: N = 5000 0.18 vs 0.23 ms, 7000 0.24 vs 0.23, 9000 0.30 vs 0.23)
-    if (C == 1 && N > 6000) continue;
-    // co-residency: one workgroup per CU always fits (256 CUs); two per CU when each stays under half the LDS
-    const size_t lds = small_lds_bytes(N, C);
-    // a second workgroup per CU only pays while the per-workgroup row loops are short (measured, 384 workgroups:
-    // N = 2000 x 768 0.162 vs 0.236 ms general; N = 2500 x 768 a tie; N = 5000 x 384 0.319 vs 0.240)
-    const int resident = (lds <= 79 * 1024 && N <= 2200) ? 512 : 256;
-    if (blocks <= resident && lds <= 150 * 1024) return C;
-  }
-  return 0;
-}
-
 __global__ void k_transpose_ell(const int32_t* col, const float* w, int32_t N, int32_t width, int32_t* col_t, float* w_t) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (int64_t)N * width) return;
@@ -277,8 +258,8 @@ void launch_transpose_ell(const int32_t* col, const float* w, int32_t N, int32_t
 }
 
 void launch_settle_small(const SmallArgs& a, int C, hipStream_t s) {
-  const int blocks = (a.ld + C - 1) / C;
-  const size_t shmem = small_lds_bytes(a.N, C);
+  const int blocks = host::small_workgroups(a.ld, C);
+  const size_t shmem = host::small_lds_bytes(a.N, C);
 #define OSC_SMALL(CC)                                                                                             \
   do {                                                                                                            \
     HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_settle_small<CC>),                              \

@@ -1069,6 +1069,8 @@ def test_padded_row_pitch_is_invisible(amd, name, ld, small, monkeypatch):
     assert np.array_equal(lat._fetch_rows(1, rows), Y[rows])
     _configure(lat, case, rc, psi)
     _check_solves(lat, case, rc, tol_u=TOL)
+    # (a padded pitch never reaches the one-launch kernel, whatever OSC_SMALL_PATH says: tests/test_gpu_small_solve.py has it)
+    assert lat.build_info()["small_solves"] == 0
     if rc["chain"]:
         lat.chain_receipt(list(rc["chain"]))
     assert len(lat.bundle(k=5)) == 5
