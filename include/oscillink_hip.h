@@ -385,6 +385,30 @@ int osc_receipt_many(osc_handle h, const float* psis, int32_t Q, int32_t detail,
 int osc_chain_receipt_many(osc_handle h, const float* psis, int32_t Q, const int64_t* chain_offsets,
                            const int32_t* chain_nodes, float z_th, float* z_struct, float* z_path, float* r_struct,
                            float* r_path, double* gain, int32_t* verdict, int32_t* weakest_k, float* weakest_z);
+/* Not in the reference: per-query chain priors on a resident lattice.  Query q gets what
+ * osc_set_chain(chain_q, weights_q, lamP); osc_set_query(psi_q); chain_receipt(chain_q, z_th) gives, from one basis of the
+ * shifted operator M' = M + lamP I and a low-rank update: M + lamP L_path,q = M' - S_q K_q S_q^T over the chain's distinct nodes.
+ *
+ * osc_query_basis_shifted solves that basis (M' X' = lamG Y, M' x' = lamQ B) into a slot of its own beside osc_query_basis's
+ * (one more N x ld array and N x 4 floats); arguments and outputs as osc_query_basis, lamP > 0, res[0] the residual of the
+ * stored (scaled) X'.  fresh == 0 keeps X' when the slot holds this lamP for the current graph.  OSC_E_STATE on a lattice
+ * with a chain of its own, OSC_E_UNSUPPORTED with a communicator.
+ *
+ * osc_chain_prior_many: osc_chain_receipt_many's arguments and outputs, and lamP >= 0, chain_weights (flat over the chains'
+ * edges like z_struct, or NULL for ones), tol / max_iters of the Green's columns M' g = e_node (one Jacobi-PCG over a panel with
+ * a column per distinct chain node, stopped per column at a tolerance derived from tol and the basis), prior_res[q] (the bound
+ * |r_basis| + sum_e |r_e| max_c |(T_q V_q)[e, c]| on the residual of the implied U*_q) and prior_iters[q] (the most iterations any
+ * of its columns took).  lamP == 0 reads osc_query_basis's basis and solves nothing; only the path weights differ from
+ * osc_chain_receipt_many.  A chain has at most 64 distinct nodes.  A query's outputs are the same to the bit whatever else the
+ * batch holds.  OSC_E_STATE without the basis (shifted for lamP > 0), OSC_E_UNSUPPORTED with a communicator, OSC_E_INVALID for
+ * a lattice with a chain of its own, lamP < 0, a non-finite weight, more than 64 distinct nodes and osc_chain_receipt_many's
+ * reasons. */
+int osc_query_basis_shifted(osc_handle h, float lamP, float tol, int32_t max_iters, float scale, int32_t fresh, int32_t* iters,
+                            float* res, double* ms);
+int osc_chain_prior_many(osc_handle h, const float* psis, int32_t Q, const int64_t* chain_offsets, const int32_t* chain_nodes,
+                         const float* chain_weights, float lamP, float tol, int32_t max_iters, float z_th, float* z_struct,
+                         float* z_path, float* r_struct, float* r_path, double* gain, int32_t* verdict, int32_t* weakest_k,
+                         float* weakest_z, float* prior_res, int32_t* prior_iters);
 /* mmr_diversify (graph.py:114-133) for Q score columns at once: scores N x Q (API row order, queries contiguous per row);
  * out_idx Q x min(k, N) API ids, the same picks as osc_mmr per column up to rounding of the similarities. */
 int osc_mmr_many(osc_handle h, const float* scores, int32_t Q, int32_t k, float lambda_div, int32_t* out_idx);

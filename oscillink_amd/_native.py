@@ -108,6 +108,11 @@ SIGNATURES = {
     "osc_receipt_many": (C.c_int, [Handle, c_f32p, C.c_int32, C.c_int32, C.c_float, C.c_int32, *_RECEIPT_MANY_OUT]),
     "osc_chain_receipt_many": (C.c_int, [Handle, c_f32p, C.c_int32, c_i64p, c_i32p, C.c_float, c_f32p, c_f32p, c_f32p, c_f32p,
                                          c_f64p, c_i32p, c_i32p, c_f32p]),
+    "osc_query_basis_shifted": (C.c_int, [Handle, C.c_float, C.c_float, C.c_int32, C.c_float, C.c_int32, c_i32p, c_f32p,
+                                          c_f64p]),
+    "osc_chain_prior_many": (C.c_int, [Handle, c_f32p, C.c_int32, c_i64p, c_i32p, c_f32p, C.c_float, C.c_float, C.c_int32,
+                                       C.c_float, c_f32p, c_f32p, c_f32p, c_f32p, c_f64p, c_i32p, c_i32p, c_f32p, c_f32p,
+                                       c_i32p]),
     "osc_corpus_create": (C.c_int, [c_f32p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(Handle)]),
     "osc_corpus_destroy": (C.c_int, [Handle]),
     "osc_corpus_last_error": (C.c_char_p, [Handle]),

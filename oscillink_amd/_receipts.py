@@ -60,6 +60,7 @@ def check_queries(psis, D: int, finite: bool = True) -> np.ndarray:
 
 
 MAX_CHAIN = 1024  # nodes of one query's chain (include/oscillink_hip.h)
+MAX_PRIOR_NODES = 64  # distinct nodes of a chain that is its own prior (csrc/chain_prior_plan.hpp: kChainPriorMaxNodes)
 CHAIN_EDGE_KEYS = ("chain_z_struct", "chain_z_path", "chain_r_struct", "chain_r_path")
 
 
@@ -98,6 +99,50 @@ def chain_block(chains, Q: int, N: int):
     np.cumsum([len(ch) for ch in lists], out=offsets[1:])
     nodes = np.array([c for ch in lists for c in ch], dtype=np.int32)
     return lists, offsets, nodes
+
+
+def chain_weights_one(w, n_edges: int, who: str) -> np.ndarray:
+    """One chain's weights as add_chain checks them: n_edges finite floats, as float32."""
+    w = np.asarray(w, dtype=np.float32).reshape(-1)
+    if w.size != n_edges:
+        raise ValueError(f"{who}: weights length must equal len(chain)-1")
+    if not np.all(np.isfinite(w)):
+        raise ValueError(f"{who}: chain weights must be finite")
+    return w
+
+
+def chain_weights_flat(wlists, edge_offsets):
+    """Per-query weights (None or an array each) flat over the chains' edges, or None when no query has any; None beside
+    given weights: ones."""
+    if not any(w is not None for w in wlists):
+        return None
+    weights = np.ones(max(int(edge_offsets[-1]), 1), dtype=np.float32)
+    for q, w in enumerate(wlists):
+        if w is not None:
+            weights[int(edge_offsets[q]):int(edge_offsets[q + 1])] = w
+    return weights
+
+
+def chain_prior_weights(chain_weights, chains, lists, edge_offsets):
+    """chain_receipt_many's `chain_weights` for its `chains` (parsed into `lists`): None, one list shared with a shared chain,
+    or a sequence parallel to `chains` of None or len(chain) - 1 finite floats.  Returns the flat float32 weights or None."""
+    Q = len(lists)
+    if chain_weights is None:
+        return None
+    shared = Q > 0 and len(chains) > 0 and (isinstance(chains[0], (int, np.integer)) or
+                                            (isinstance(chains, np.ndarray) and chains.ndim == 1))
+    if shared:
+        w = chain_weights_one(chain_weights, len(lists[0]) - 1, "chain")
+        return chain_weights_flat([w] * Q, edge_offsets)
+    try:
+        n = len(chain_weights)
+    except TypeError:
+        n = -1
+    if n != Q:
+        raise ValueError(f"chain_weights must be None or hold {Q} entries parallel to chains, got {n}")
+    wl = [None if chain_weights[q] is None else chain_weights_one(chain_weights[q], len(lists[q]) - 1, f"query {q}")
+          for q in range(Q)]
+    return chain_weights_flat(wl, edge_offsets)
 
 
 def chain_receipt_dict(chain, *, weakest_k, weakest_z, gain, verdict, z_struct, z_path, r_struct, r_path) -> dict[str, Any]:

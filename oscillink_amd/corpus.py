@@ -279,11 +279,7 @@ class Corpus:
             if len(ch) > MAX_CHAIN:
                 raise ValueError(f"query {q}: a chain has at most {MAX_CHAIN} indices, got {len(ch)}")
             if w is not None:
-                w = np.asarray(w, dtype=np.float32).reshape(-1)
-                if w.size != len(ch) - 1:
-                    raise ValueError(f"query {q}: weights length must equal len(chain)-1")
-                if not np.all(np.isfinite(w)):
-                    raise ValueError(f"query {q}: chain weights must be finite")
+                w = rc.chain_weights_one(w, len(ch) - 1, f"query {q}")
             lists.append(ch)
             wlists.append(w)
         lens = np.array([0 if ch is None else len(ch) for ch in lists], dtype=np.int64)
@@ -292,12 +288,7 @@ class Corpus:
         edge_offsets = np.zeros(Q + 1, dtype=np.int64)
         np.cumsum(np.maximum(lens - 1, 0), out=edge_offsets[1:])
         nodes = np.array([c for ch in lists if ch is not None for c in ch], dtype=np.int32)
-        weights = None
-        if any(w is not None for w in wlists):
-            weights = np.ones(max(int(edge_offsets[-1]), 1), dtype=np.float32)  # None beside given weights: ones
-            for q, w in enumerate(wlists):
-                if w is not None:
-                    weights[int(edge_offsets[q]):int(edge_offsets[q + 1])] = w
+        weights = rc.chain_weights_flat(wlists, edge_offsets)
         return {"offsets": offsets, "nodes": nodes if nodes.size else np.zeros(1, dtype=np.int32), "weights": weights,
                 "edge_offsets": edge_offsets, "lists": lists, "lamP": float(lamP), "z_th": float(chain_z_th)}
 

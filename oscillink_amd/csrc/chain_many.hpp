@@ -5,6 +5,7 @@
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
 #include <map>
 #include <vector>
 
@@ -67,6 +68,28 @@ struct ChainManyPaths {
     seen.emplace(std::move(key), id);
     return id;
   }
+  // ... with weights in the key as well (osc_chain_prior_many): a chain is the same path only with the same weights.  The
+  // weighted key is the nodes, -1, then the weights' bits; without weights it is add's own.
+  int32_t add_weighted(const int32_t* nodes, const float* weights, int32_t len, int32_t N) {
+    if (!weights) return add(nodes, nullptr, len, N);
+    std::vector<int32_t> key(nodes, nodes + len);
+    key.push_back(-1);
+    for (int32_t t = 0; t + 1 < len; ++t) {
+      int32_t bits;
+      static_assert(sizeof bits == sizeof weights[t], "float is 32 bits");
+      std::memcpy(&bits, weights + t, sizeof bits);
+      key.push_back(bits);
+    }
+    auto it = seen.find(key);
+    if (it != seen.end()) return it->second;
+    const int32_t id = (int32_t)paths.size();
+    paths.push_back(build_chain_path(nodes, weights, len, N));
+    base.push_back((int32_t)pcol.size());
+    pcol.insert(pcol.end(), paths.back().col.begin(), paths.back().col.end());
+    pa.insert(pa.end(), paths.back().a.begin(), paths.back().a.end());
+    seen.emplace(std::move(key), id);
+    return id;
+  }
   // row's entries of path id: [*pb, *pe), empty when the row owns none
   void range(int32_t id, int32_t row, int32_t* pb, int32_t* pe) const {
     const ChainPath& p = paths[(size_t)id];
@@ -96,6 +119,32 @@ inline void chain_many_units(const int64_t* off, const int32_t* nodes, int32_t c
     rows.resize((size_t)len);
     for (int32_t s = 0; s < len; ++s) rows[(size_t)s] = dev ? dev[nodes[b + s]] : nodes[b + s];
     const int32_t id = own >= 0 ? own : paths.add(rows.data(), nullptr, len, N);
+    for (int32_t s = 0; s + 1 < len; ++s) {
+      ChainManyUnit u{t, rows[(size_t)s], rows[(size_t)s + 1], 0, 0};
+      paths.range(id, u.i, &u.pb, &u.pe);
+      units.push_back(u);
+    }
+    eoff[(size_t)t + 1] = (int32_t)units.size();
+  }
+}
+
+// chain_many_units for chains with weights of their own (osc_chain_prior_many): weights is flat over the chains' edges like
+// the per-edge outputs (query q's at chain_many_edge_at(off, q)), or nullptr for ones.  Every query's chain is packed once per
+// distinct (chain, weights); path_of[t] receives the path of the chunk's query t.
+inline void chain_many_units_weighted(const int64_t* off, const int32_t* nodes, const float* weights, int32_t c0, int32_t nq,
+                                      const int32_t* dev, int32_t N, ChainManyPaths& paths, std::vector<ChainManyUnit>& units,
+                                      std::vector<int32_t>& eoff, std::vector<int32_t>& path_of) {
+  units.clear();
+  eoff.assign((size_t)nq + 1, 0);
+  path_of.assign((size_t)nq, 0);
+  std::vector<int32_t> rows;
+  for (int32_t t = 0; t < nq; ++t) {
+    const int64_t b = off[c0 + t];
+    const int32_t len = (int32_t)(off[c0 + t + 1] - b);
+    rows.resize((size_t)len);
+    for (int32_t s = 0; s < len; ++s) rows[(size_t)s] = dev ? dev[nodes[b + s]] : nodes[b + s];
+    const int32_t id = paths.add_weighted(rows.data(), weights ? weights + chain_many_edge_at(off, c0 + t) : nullptr, len, N);
+    path_of[(size_t)t] = id;
     for (int32_t s = 0; s + 1 < len; ++s) {
       ChainManyUnit u{t, rows[(size_t)s], rows[(size_t)s + 1], 0, 0};
       paths.range(id, u.i, &u.pb, &u.pe);

@@ -38,6 +38,12 @@ struct GmGraph {
   int32_t width;
 };
 
+// a per-row diagonal and the graph term's factor: the operator diag(d) - lamC W of the Green's columns
+struct GmRowOp {
+  const float* d = nullptr;  // [N]
+  float lamC = 0.f;
+};
+
 // S = beta max(0, C) from the GEMM's cosines C (N x qc, row-major; columns >= nq count as 0); x = 0, r = S, p = z = r inv_md;
 // part_a / part_b: the parts' column sums of r . z and s . s
 void launch_gm_source(const GmPanel& p, const float* C, float beta, float inv_md, hipStream_t s);
@@ -57,5 +63,15 @@ void launch_gm_direction(const GmPanel& p, float inv_md, hipStream_t s);
 // lo / hi per column (two stages, fixed order, NaN kept), then out[q][api row] = clip((x - lo) / (hi - lo)) -- ones when
 // hi - lo < 1e-12 -- or clip(x) with clamp == 0; inv: API row -> device row, nullptr = identity
 void launch_gm_finish(const GmPanel& p, int clamp, const int32_t* inv, float* out, hipStream_t s);
+
+// The same solve over M' = diag(d) - lamC W for unit right-hand sides (osc_chain_prior_many): d_i = c + lamQ B_i; column c
+// starts from the unit vector of row node[c] (x = 0, r = e, p = r / d; node[c] < 0: a zero column); then launch_gm_init
+// (direct = 0), and per iteration apply_rows / launch_gm_alpha / update_rows / launch_gm_beta / direction_rows, the Jacobi
+// preconditioner being 1 / d_i.  The panel's lo / hi are not used.
+void launch_gm_row_diag(const float* B, float c, float lamQ, int32_t N, float* d, hipStream_t s);
+void launch_gm_unit_source(const GmPanel& p, const int32_t* node, const GmRowOp& op, hipStream_t s);
+void launch_gm_apply_rows(const GmPanel& p, const GmGraph& g, const GmRowOp& op, hipStream_t s);
+void launch_gm_update_rows(const GmPanel& p, const GmRowOp& op, hipStream_t s);
+void launch_gm_direction_rows(const GmPanel& p, const GmRowOp& op, hipStream_t s);
 
 }  // namespace osc

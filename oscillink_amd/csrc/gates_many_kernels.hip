@@ -102,6 +102,39 @@ __global__ __launch_bounds__(256) void k_gm_source(const GmPanel p, const float*
   gm_fold(ss, sh, p.part_b + gm_part_at(p));
 }
 
+// The Green's columns' start: column c's right-hand side is the unit vector of row node[c] (node[c] < 0: a pad column, all
+// zero); x = 0, r = e, p = z = r / d.  part_a / part_b: r . z and e . e like k_gm_source.
+__global__ __launch_bounds__(256) void k_gm_unit_source(const GmPanel p, const int32_t* __restrict__ node, const GmRowOp op) {
+  __shared__ double sh[1024];
+  const int t = threadIdx.x, lr = t & 7;
+  const int slab = blockIdx.y, c0 = slab * 32 + lr * 4;
+  const size_t so = (size_t)slab * p.N * 32;
+  const int4 nd = *reinterpret_cast<const int4*>(node + c0);
+  const GmRows rr = gm_rows(p);
+  float4 rz = f4(0.f), ss = f4(0.f);
+  for (int64_t rb = rr.r0; rb < rr.r1; rb += 32) {
+    const int64_t row = rb + (t >> 3);
+    if (row >= rr.r1) continue;
+    const float4 s = make_float4(nd.x == row ? 1.f : 0.f, nd.y == row ? 1.f : 0.f, nd.z == row ? 1.f : 0.f, nd.w == row ? 1.f : 0.f);
+    const float inv_md = 1.0f / op.d[row];
+    const float4 z = make_float4(s.x * inv_md, s.y * inv_md, s.z * inv_md, s.w * inv_md);
+    const size_t o = so + (size_t)row * 32 + lr * 4;
+    st4(p.X + o, f4(0.f));
+    st4(p.R + o, s);
+    st4(p.P + o, z);
+    rz = mulacc4(s, z, rz);
+    ss = mulacc4(s, s, ss);
+  }
+  gm_fold(rz, sh, p.part_a + gm_part_at(p));
+  gm_fold(ss, sh, p.part_b + gm_part_at(p));
+}
+
+// d_i = c + lamQ B_i
+__global__ __launch_bounds__(256) void k_gm_row_diag(const float* __restrict__ B, float c, float lamQ, int32_t N, float* __restrict__ d) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < N) d[i] = fmaf(lamQ, B[i], c);
+}
+
 __global__ __launch_bounds__(kGmSumThreads) void k_gm_init(const GmPanel p, int direct, float tol) {
   __shared__ double sh[kGmSumThreads];
   const int slab = blockIdx.x, t = threadIdx.x;
@@ -133,7 +166,10 @@ __global__ __launch_bounds__(kGmSumThreads) void k_gm_init(const GmPanel p, int 
 // One wave: 8 rows, 8 lanes a row.  A row's ELL entries are read 8 at a time (one per lane of the row's group) and handed
 // round by shuffles; the 8 neighbour lines of that step are all requested before the first is used, so a wave keeps up to
 // 64 gathered lines in flight.  The sum runs in slot order with one fmaf per entry.
-__global__ __launch_bounds__(256) void k_gm_apply(const GmPanel p, const GmGraph g, float cs) {
+// ROWD (the Green's columns of osc_chain_prior_many): AP = d_i p_i - lamC (W p)_i with the per-row
+// diagonal op.d, where the gates' operator has the one scalar cs and the factor 1.
+template <bool ROWD>
+__global__ __launch_bounds__(256) void k_gm_apply(const GmPanel p, const GmGraph g, float cs, const GmRowOp op) {
   __shared__ double sh[1024];
   const int slab = blockIdx.y;
   if (p.slab_live[slab] == 0) return;
@@ -175,7 +211,13 @@ __global__ __launch_bounds__(256) void k_gm_apply(const GmPanel p, const GmGraph
     if (ok) {
       const size_t o = (size_t)row * 32 + lr * 4;
       const float4 x = ld4(P + o);
-      const float4 a = make_float4(fmaf(cs, x.x, -sum.x), fmaf(cs, x.y, -sum.y), fmaf(cs, x.z, -sum.z), fmaf(cs, x.w, -sum.w));
+      float4 a;
+      if constexpr (ROWD) {
+        const float d = op.d[row], nc = -op.lamC;
+        a = make_float4(fmaf(d, x.x, nc * sum.x), fmaf(d, x.y, nc * sum.y), fmaf(d, x.z, nc * sum.z), fmaf(d, x.w, nc * sum.w));
+      } else {
+        a = make_float4(fmaf(cs, x.x, -sum.x), fmaf(cs, x.y, -sum.y), fmaf(cs, x.z, -sum.z), fmaf(cs, x.w, -sum.w));
+      }
       st4(AP + o, a);
       pap = mulacc4(x, a, pap);
     }
@@ -194,7 +236,8 @@ __global__ __launch_bounds__(kGmSumThreads) void k_gm_alpha(const GmPanel p) {
   }
 }
 
-__global__ __launch_bounds__(256) void k_gm_update(const GmPanel p, float inv_md) {
+template <bool ROWD>
+__global__ __launch_bounds__(256) void k_gm_update(const GmPanel p, float inv_md_all, const GmRowOp op) {
   __shared__ double sh[1024];
   const int slab = blockIdx.y;
   if (p.slab_live[slab] == 0) return;
@@ -208,6 +251,7 @@ __global__ __launch_bounds__(256) void k_gm_update(const GmPanel p, float inv_md
     const int64_t row = rb + (t >> 3);
     if (row >= rr.r1) continue;
     const size_t o = so + (size_t)row * 32 + lr * 4;
+    const float inv_md = ROWD ? 1.0f / op.d[row] : inv_md_all;
     float4 x = ld4(p.X + o), r = ld4(p.R + o);
     const float4 d = ld4(p.P + o), a = ld4(p.AP + o);
     // a frozen column keeps its x and r bit for bit
@@ -257,7 +301,8 @@ __global__ __launch_bounds__(kGmSumThreads) void k_gm_beta(const GmPanel p, int 
   }
 }
 
-__global__ __launch_bounds__(256) void k_gm_direction(const GmPanel p, float inv_md) {
+template <bool ROWD>
+__global__ __launch_bounds__(256) void k_gm_direction(const GmPanel p, float inv_md_all, const GmRowOp op) {
   const int slab = blockIdx.y;
   if (p.slab_live[slab] == 0) return;
   const int t = threadIdx.x, lr = t & 7;
@@ -268,6 +313,7 @@ __global__ __launch_bounds__(256) void k_gm_direction(const GmPanel p, float inv
     const int64_t row = rb + (t >> 3);
     if (row >= rr.r1) continue;
     const size_t o = so + (size_t)row * 32 + lr * 4;
+    const float inv_md = ROWD ? 1.0f / op.d[row] : inv_md_all;
     const float4 r = ld4(p.R + o);
     float4 d = ld4(p.P + o);
     d.x = fmaf(d.x, be.x, r.x * inv_md);
@@ -382,7 +428,7 @@ void launch_gm_init(const GmPanel& p, int direct, float tol, hipStream_t s) {
 }
 
 void launch_gm_apply(const GmPanel& p, const GmGraph& g, float cs, hipStream_t s) {
-  hipLaunchKernelGGL(k_gm_apply, gm_grid(p), dim3(256), 0, s, p, g, cs);
+  hipLaunchKernelGGL(k_gm_apply<false>, gm_grid(p), dim3(256), 0, s, p, g, cs, GmRowOp{});
   HIP_CHECK(hipGetLastError());
 }
 
@@ -392,7 +438,7 @@ void launch_gm_alpha(const GmPanel& p, hipStream_t s) {
 }
 
 void launch_gm_update(const GmPanel& p, float inv_md, hipStream_t s) {
-  hipLaunchKernelGGL(k_gm_update, gm_grid(p), dim3(256), 0, s, p, inv_md);
+  hipLaunchKernelGGL(k_gm_update<false>, gm_grid(p), dim3(256), 0, s, p, inv_md, GmRowOp{});
   HIP_CHECK(hipGetLastError());
 }
 
@@ -402,7 +448,7 @@ void launch_gm_beta(const GmPanel& p, int it, hipStream_t s) {
 }
 
 void launch_gm_direction(const GmPanel& p, float inv_md, hipStream_t s) {
-  hipLaunchKernelGGL(k_gm_direction, gm_grid(p), dim3(256), 0, s, p, inv_md);
+  hipLaunchKernelGGL(k_gm_direction<false>, gm_grid(p), dim3(256), 0, s, p, inv_md, GmRowOp{});
   HIP_CHECK(hipGetLastError());
 }
 
@@ -412,6 +458,32 @@ void launch_gm_finish(const GmPanel& p, int clamp, const int32_t* inv, float* ou
     hipLaunchKernelGGL(k_gm_range, dim3((unsigned)p.slabs), dim3(256), 0, s, p);
   }
   hipLaunchKernelGGL(k_gm_finish, dim3((unsigned)((p.N + 31) / 32), (unsigned)p.slabs), dim3(256), 0, s, p, clamp, inv, out);
+  HIP_CHECK(hipGetLastError());
+}
+
+// ---- the Green's columns of osc_chain_prior_many: the same solve over M' = diag(d) - lamC W -----------------------------------
+void launch_gm_row_diag(const float* B, float c, float lamQ, int32_t N, float* d, hipStream_t s) {
+  hipLaunchKernelGGL(k_gm_row_diag, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, B, c, lamQ, N, d);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_gm_unit_source(const GmPanel& p, const int32_t* node, const GmRowOp& op, hipStream_t s) {
+  hipLaunchKernelGGL(k_gm_unit_source, gm_grid(p), dim3(256), 0, s, p, node, op);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_gm_apply_rows(const GmPanel& p, const GmGraph& g, const GmRowOp& op, hipStream_t s) {
+  hipLaunchKernelGGL(k_gm_apply<true>, gm_grid(p), dim3(256), 0, s, p, g, 0.f, op);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_gm_update_rows(const GmPanel& p, const GmRowOp& op, hipStream_t s) {
+  hipLaunchKernelGGL(k_gm_update<true>, gm_grid(p), dim3(256), 0, s, p, 0.f, op);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_gm_direction_rows(const GmPanel& p, const GmRowOp& op, hipStream_t s) {
+  hipLaunchKernelGGL(k_gm_direction<true>, gm_grid(p), dim3(256), 0, s, p, 0.f, op);
   HIP_CHECK(hipGetLastError());
 }
 

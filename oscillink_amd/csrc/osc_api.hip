@@ -1228,6 +1228,28 @@ int osc_chain_receipt_many(osc_handle h, const float* psis, int32_t Q, const int
   });
 }
 
+int osc_query_basis_shifted(osc_handle h, float lamP, float tol, int32_t max_iters, float scale, int32_t fresh, int32_t* iters,
+                            float* res, double* ms) {
+  return guarded(h, [&](L& l) {
+    if (!iters || !res) throw Invalid("osc_query_basis_shifted: NULL buffer");
+    query_basis_shifted_solve(l, lamP, tol, max_iters, scale, fresh != 0, iters, res, ms);
+  });
+}
+
+int osc_chain_prior_many(osc_handle h, const float* psis, int32_t Q, const int64_t* chain_offsets, const int32_t* chain_nodes,
+                         const float* chain_weights, float lamP, float tol, int32_t max_iters, float z_th, float* z_struct,
+                         float* z_path, float* r_struct, float* r_path, double* gain, int32_t* verdict, int32_t* weakest_k,
+                         float* weakest_z, float* prior_res, int32_t* prior_iters) {
+  return guarded(h, [&](L& l) {
+    if (Q < 0) throw Invalid("osc_chain_prior_many: Q must be >= 0");
+    if (Q > 0 && (!psis || !chain_offsets || !chain_nodes || !z_struct || !z_path || !r_struct || !r_path || !gain ||
+                  !verdict || !weakest_k || !weakest_z || !prior_res || !prior_iters))
+      throw Invalid("osc_chain_prior_many: NULL buffer");
+    query_chain_prior_many(l, psis, Q, chain_offsets, chain_nodes, chain_weights, lamP, tol, max_iters, z_th, z_struct, z_path,
+                           r_struct, r_path, gain, verdict, weakest_k, weakest_z, prior_res, prior_iters);
+  });
+}
+
 int osc_mmr_many(osc_handle h, const float* scores, int32_t Q, int32_t k, float lambda_div, int32_t* out_idx) {
   return guarded(h, [&](L& l) {
     if (Q < 0) throw Invalid("osc_mmr_many: Q must be >= 0");

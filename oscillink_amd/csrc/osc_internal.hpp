@@ -37,6 +37,7 @@
 #include "small.hpp"
 #include "query.hpp"
 #include "gates_many.hpp"
+#include "chain_prior_plan.hpp"
 
 using namespace osc;
 
@@ -322,6 +323,23 @@ struct osc_lattice {
     DevBuf<host::ChainManyUnit> cm_units;
     DevBuf<int32_t> cm_pcol, cm_eoff, cm_verdict, cm_wk;
     DevBuf<double> cm_term, cm_gain;
+    // osc_chain_prior_many.  res_X / res_x: the resident basis's residuals, |r_X| and |r_x| of the
+    // unscaled x.  shifted: the basis of M + lamP I in a slot of its own, X' stored scaled by lamG / (lamG + lamP); epoch-keyed
+    // like the first, and by lamP; max_X / max_x = max |X'| / max |x'| (the Green's columns' stop is derived from them).
+    float res_X = 0.f, res_x = 0.f;
+    struct Shifted {
+      bool have = false;
+      uint64_t epoch = 0;
+      float lamP = 0.f, scale = 0.f;
+      DevBuf<float> X, x4;
+      float res_X = 0.f, res_x = 0.f, max_X = 0.f, max_x = 0.f;
+    } shifted;
+    DevBuf<char> cp_scratch;     // one pass's panels and per-column scalars (chain_prior_plan.hpp: ChainPriorLayout)
+    DevBuf<float> cp_diag;       // [N] d_i = lamG + lamP + lamC + lamQ B_i
+    DevBuf<int32_t> cp_ints;     // one pass's systems and per-query indices
+    DevBuf<int64_t> cp_longs;
+    DevBuf<float> cp_flts, cp_tv;
+    DevBuf<double> cp_T;
   } query;
   std::string err;
 
@@ -456,6 +474,13 @@ void query_receipt_many(L& l, const float* psis, int32_t Q, int32_t detail, floa
 void query_chain_receipt_many(L& l, const float* psis, int32_t Q, const int64_t* chain_offsets, const int32_t* chain_nodes,
                               float z_th, float* z_struct, float* z_path, float* r_struct, float* r_path, double* gain,
                               int32_t* verdict, int32_t* weakest_k, float* weakest_z);
+// osc_query_basis_shifted / osc_chain_prior_many
+void query_basis_shifted_solve(L& l, float lamP, float tol, int32_t max_iters, float scale, bool fresh, int32_t* iters,
+                               float* res, double* ms);
+void query_chain_prior_many(L& l, const float* psis, int32_t Q, const int64_t* chain_offsets, const int32_t* chain_nodes,
+                            const float* chain_weights, float lamP, float tol, int32_t max_iters, float z_th, float* z_struct,
+                            float* z_path, float* r_struct, float* r_path, double* gain, int32_t* verdict, int32_t* weakest_k,
+                            float* weakest_z, float* prior_res, int32_t* prior_iters);
 // sum (A - B) . M (A - B) with the stationary operator (osc_api.hip; receipts.py:21-25)
 double quad_form_of_difference(L& l, const float* A, const float* B);
 void query_bundle_many(L& l, const float* psis, int32_t Q, int32_t k, float alpha, float lambda_div, int32_t* ids,

@@ -75,34 +75,23 @@ void mmr_many_run(L& l, int32_t qs, int32_t nq, int32_t kk, float lambda_div) {
 
 }  // namespace
 
-void query_basis_solve(L& l, float tol, int32_t max_iters, float scale, bool fresh, int32_t* iters, float* res, double* ms) {
-  require_graph(l);
-  if (l.comm) throw Unsupported("osc_query_basis: lattices with a communicator are not supported");
-  if (max_iters < 1) throw Invalid("max_iters must be >= 1");
-  if (!(tol > 0.f) || !std::isfinite(tol)) throw Invalid("osc_query_basis: tol must be > 0");
-  if (!(scale > 0.f) || !std::isfinite(scale)) throw Invalid("osc_query_basis: scale must be a finite value > 0");
+namespace {
+
+// The two solves of a query basis into (X, x4): M X = lamG Y (only when fresh) and M x = lamQ B, both to tol / 2 -- X directly,
+// x through its right-hand side scaled by |psi|_inf (solved for scale * x).  op states M.
+void basis_cg(L& l, const OpParams& op, DevBuf<float>& X, DevBuf<float>& x4, bool fresh, float tol, int32_t max_iters,
+              float scale, int32_t* iters, float* res) {
   auto& q = l.query;
-  if (!q.have || q.epoch != l.derived.epoch) fresh = true;
-  ensure_cg_scratch(l, max_iters);
-  // the lattice's own solves keep their iteration predictions and residual history
-  int saved_pred[3];
-  std::copy(l.predicted_iters, l.predicted_iters + 3, saved_pred);
-  std::vector<float> saved_hist = l.history;
-  const OpParams op = ustar_op(l);
   const size_t n = (size_t)l.N;
-  sync(l);
-  const double t0 = now_ms();
-  // both parts stop at tol / 2: X directly, x through its right-hand side scaled by |psi|_inf (solved for scale * x)
   if (fresh) {
-    q.have = false;
-    q.X.alloc(n * l.ld);
+    X.alloc(n * l.ld);
     q.zero_psi.alloc((size_t)l.ld);
     HIP_CHECK(hipMemsetAsync(q.zero_psi.p, 0, (size_t)l.ld * 4, l.stream));
-    CgBuffers b{l.Y.p, q.X.p, l.R.p, l.P.p, l.AP.p, u_read(l), l.Y.p, l.B.p, q.zero_psi.p, l.ld, l.c0, l.c1};
+    CgBuffers b{l.Y.p, X.p, l.R.p, l.P.p, l.AP.p, u_read(l), l.Y.p, l.B.p, q.zero_psi.p, l.ld, l.c0, l.c1};
     b.kind = 1;
-    b.defer_x0 = true;  // (as in osc_solve_ustar: x0 is the anchors, nothing copies them into q.X first)
+    b.defer_x0 = true;  // (as in osc_solve_ustar: x0 is the anchors, nothing copies them into X first)
     const CgResult r = run_cg(l, op, b, path_active(l), max_iters, 0.5f * tol);
-    if (r.sol != q.X.p) HIP_CHECK(hipMemcpyAsync(q.X.p, r.sol, n * l.ld * 4, hipMemcpyDeviceToDevice, l.stream));
+    if (r.sol != X.p) HIP_CHECK(hipMemcpyAsync(X.p, r.sol, n * l.ld * 4, hipMemcpyDeviceToDevice, l.stream));
     iters[0] = r.iters;
     res[0] = r.res;
   } else {
@@ -120,16 +109,45 @@ void query_basis_solve(L& l, float tol, int32_t max_iters, float scale, bool fre
     const float p4[4] = {scale, 0.f, 0.f, 0.f};
     psi4.alloc(ld1);
     HIP_CHECK(hipMemcpyAsync(psi4.p, p4, sizeof p4, hipMemcpyHostToDevice, l.stream));
-    if (!fresh) launch_axpby(X0.p, q.x4.p, scale, q.x4.p, 0.f, (int64_t)(n * ld1), l.stream);
+    if (!fresh) launch_axpby(X0.p, x4.p, scale, x4.p, 0.f, (int64_t)(n * ld1), l.stream);
     CgBuffers b{X0.p, Xs.p, R.p, P.p, AP.p, S.p, S.p, l.B.p, psi4.p, ld1, 0, ld1};
     b.kind = 2;
     const CgResult r = run_cg(l, op, b, path_active(l), max_iters, 0.5f * tol);
-    q.x4.alloc(n * ld1);
-    launch_axpby(q.x4.p, r.sol, 1.0f / scale, r.sol, 0.f, (int64_t)(n * ld1), l.stream);
+    x4.alloc(n * ld1);
+    launch_axpby(x4.p, r.sol, 1.0f / scale, r.sol, 0.f, (int64_t)(n * ld1), l.stream);
     iters[1] = r.iters;
     res[1] = r.res / scale;  // |r_x| of the unscaled x
     sync(l);                 // (psi4 / the scratch above are released at scope exit)
   }
+}
+
+void check_basis_args(L& l, const char* fn, float tol, int32_t max_iters, float scale) {
+  require_graph(l);
+  if (l.comm) throw Unsupported(std::string(fn) + ": lattices with a communicator are not supported");
+  if (max_iters < 1) throw Invalid("max_iters must be >= 1");
+  if (!(tol > 0.f) || !std::isfinite(tol)) throw Invalid(std::string(fn) + ": tol must be > 0");
+  if (!(scale > 0.f) || !std::isfinite(scale)) throw Invalid(std::string(fn) + ": scale must be a finite value > 0");
+}
+
+}  // namespace
+
+void query_basis_solve(L& l, float tol, int32_t max_iters, float scale, bool fresh, int32_t* iters, float* res, double* ms) {
+  check_basis_args(l, "osc_query_basis", tol, max_iters, scale);
+  auto& q = l.query;
+  if (!q.have || q.epoch != l.derived.epoch) fresh = true;
+  ensure_cg_scratch(l, max_iters);
+  // the lattice's own solves keep their iteration predictions and residual history
+  int saved_pred[3];
+  std::copy(l.predicted_iters, l.predicted_iters + 3, saved_pred);
+  std::vector<float> saved_hist = l.history;
+  const OpParams op = ustar_op(l);
+  const size_t n = (size_t)l.N;
+  sync(l);
+  const double t0 = now_ms();
+  if (fresh) q.have = false;
+  basis_cg(l, op, q.X, q.x4, fresh, tol, max_iters, scale, iters, res);
+  if (fresh) q.res_X = res[0];
+  q.res_x = res[1];
   q.s.alloc(n);
   q.xn2.alloc(n);
   q.c0.alloc(n);
@@ -159,6 +177,61 @@ void query_basis_solve(L& l, float tol, int32_t max_iters, float scale, bool fre
   ++q.gen;
   q.epoch = l.derived.epoch;
   q.scale = scale;
+  if (ms) *ms = now_ms() - t0;
+}
+
+// The basis of the shifted operator M' = M + lamP I in a slot of its own: M' X' = lamG Y,
+// M' x' = lamQ B.  M' is M with lamG + lamP in lamG's place, so the solve is query_basis_solve's with that lamG and the
+// right-hand side (lamG + lamP) Y, and X' is its X times lamG / (lamG + lamP) <= 1 (the tol / 2 contract carries over),
+// stored scaled.
+void query_basis_shifted_solve(L& l, float lamP, float tol, int32_t max_iters, float scale, bool fresh, int32_t* iters,
+                               float* res, double* ms) {
+  check_basis_args(l, "osc_query_basis_shifted", tol, max_iters, scale);
+  if (!(lamP > 0.f) || !std::isfinite(lamP)) throw Invalid("osc_query_basis_shifted: lamP must be a finite value > 0");
+  if (l.chain_present) throw StateError("osc_query_basis_shifted: the lattice has a chain of its own (osc_clear_chain first)");
+  auto& sh = l.query.shifted;
+  if (!sh.have || sh.epoch != l.derived.epoch || sh.lamP != lamP) fresh = true;
+  ensure_cg_scratch(l, max_iters);
+  int saved_pred[3];
+  std::copy(l.predicted_iters, l.predicted_iters + 3, saved_pred);
+  std::vector<float> saved_hist = l.history;
+  const float f = l.lamG / (l.lamG + lamP);
+  OpParams op{};
+  {  // ustar_op of the handle with lamG + lamP in lamG's place; the handle's own lamG is back before anything else reads it
+    const float lamG = l.lamG;
+    l.lamG = lamG + lamP;
+    op = ustar_op(l);
+    l.lamG = lamG;
+  }
+  sync(l);
+  const double t0 = now_ms();
+  if (fresh) sh.have = false;
+  basis_cg(l, op, sh.X, sh.x4, fresh, tol, max_iters, scale, iters, res);
+  const int nb = cp_scale_blocks(l.N);
+  DevBuf<float> part;
+  part.alloc((size_t)nb);
+  std::vector<float> hp((size_t)nb);
+  auto max_of = [&](float* arr, int32_t D, int32_t ld, float factor) {
+    launch_cp_scale_max(arr, (int32_t)l.N, D, ld, factor, part.p, l.stream);
+    HIP_CHECK(hipMemcpyAsync(hp.data(), part.p, (size_t)nb * 4, hipMemcpyDeviceToHost, l.stream));
+    sync(l);
+    float m = 0.f;
+    for (float v : hp) m = (v > m || v != v) ? v : m;
+    return m;
+  };
+  if (fresh) {
+    sh.max_X = max_of(sh.X.p, l.D, l.ld, f);
+    sh.res_X = res[0] * f;
+    res[0] = sh.res_X;
+  }
+  sh.max_x = max_of(sh.x4.p, 1, 4, 1.0f);
+  sh.res_x = res[1];
+  std::copy(saved_pred, saved_pred + 3, l.predicted_iters);
+  l.history = std::move(saved_hist);
+  sh.have = true;
+  sh.epoch = l.derived.epoch;
+  sh.lamP = lamP;
+  sh.scale = scale;
   if (ms) *ms = now_ms() - t0;
 }
 
@@ -675,6 +748,300 @@ void query_chain_receipt_many(L& l, const float* psis, int32_t Q, const int64_t*
     HIP_CHECK(hipMemcpyAsync(weakest_k + c0, q.cm_wk.p, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
     HIP_CHECK(hipMemcpyAsync(weakest_z + c0, q.cm_wz.p, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
     sync(l);  // (the host vectors above are reused by the next chunk)
+  }
+}
+
+// ---- per-query chain priors ------------------------------------------------------------------
+// Query q's answer is chain_receipt(chain_q) on the U* of M + lamP L_path,q = M' - S_q K_q S_q^T (M' = M + lamP I):
+//   U*_q = U'0 + G T_q (S_q^T U'0),  U'0 = X' + x' psi_q^T,  G = M'^-1 S_q,  T_q = (I - K_q Ghat)^-1 K_q.
+// Per pass (chain_prior_plan.hpp): one Jacobi-PCG over a panel of unit right-hand sides, one column per distinct chain node
+// (gates_many_kernels.hip), T per distinct chain, T_q V_q and the residual bound per query, then k_cm_edges with the
+// correction on every gathered row.  lamP == 0: the resident basis and no panel; only the path weights differ from
+// osc_chain_receipt_many.  Nothing outlives the call but the scratch's allocation.
+void query_chain_prior_many(L& l, const float* psis, int32_t Q, const int64_t* chain_offsets, const int32_t* chain_nodes,
+                            const float* chain_weights, float lamP, float tol, int32_t max_iters, float z_th, float* z_struct,
+                            float* z_path, float* r_struct, float* r_path, double* gain, int32_t* verdict, int32_t* weakest_k,
+                            float* weakest_z, float* prior_res, int32_t* prior_iters) {
+  if (l.comm) throw Unsupported("osc_chain_prior_many: lattices with a communicator are not supported");
+  require_graph(l);
+  if (!(lamP >= 0.f) || !std::isfinite(lamP)) throw Invalid("osc_chain_prior_many: lamP must be a finite value >= 0");
+  if (!(tol > 0.f) || !std::isfinite(tol)) throw Invalid("osc_chain_prior_many: tol must be > 0");
+  if (max_iters < 1) throw Invalid("max_iters must be >= 1");
+  if (l.chain_present) throw Invalid("osc_chain_prior_many: the lattice has a chain of its own (osc_clear_chain first)");
+  const bool prior = lamP > 0.f;
+  auto& q = l.query;
+  auto& sh = q.shifted;
+  if (prior) {
+    if (!sh.have || sh.epoch != l.derived.epoch || sh.lamP != lamP)
+      throw StateError("no shifted query basis for this lamP and the current graph (call osc_query_basis_shifted first)");
+  } else {
+    require_basis(l);
+  }
+  if (Q <= 0) return;
+  int32_t where = 0;
+  switch (host::chain_many_check(chain_offsets, chain_nodes, Q, l.N, &where)) {
+    case 1:
+      throw Invalid("osc_chain_prior_many: query " + std::to_string(where) + ": a chain has 2 to " +
+                    std::to_string(host::kCorpusMaxChain) + " nodes, at offsets that start from 0");
+    case 2:
+      throw Invalid("osc_chain_prior_many: query " + std::to_string(where) + ": chain indices out of bounds");
+  }
+  where = host::chain_prior_check(chain_offsets, chain_nodes, Q);
+  if (where >= 0)
+    throw Invalid("osc_chain_prior_many: query " + std::to_string(where) + ": a chain has at most " +
+                  std::to_string(host::kChainPriorMaxNodes) + " distinct nodes");
+  if (chain_weights)
+    for (int64_t e = 0; e < host::chain_many_edge_at(chain_offsets, Q); ++e)
+      if (!std::isfinite(chain_weights[e])) throw Invalid("osc_chain_prior_many: non-finite chain weight");
+  const int32_t N = (int32_t)l.N, D = l.D;
+  const int32_t* dev = permuted(l) ? l.inv_h.data() : nullptr;
+  const float* const bX = prior ? sh.X.p : q.X.p;
+  const float* const bx4 = prior ? sh.x4.p : q.x4.p;
+  const float res_X = prior ? sh.res_X : q.res_X, res_x = prior ? sh.res_x : q.res_x;
+  // the passes: by the panel's budget with a prior, osc_chain_receipt_many's chunks without
+  std::vector<host::ChainPriorPass> passes;
+  if (prior) {
+    int max_cols = 0;
+    env_num("OSC_CHAIN_PRIOR_COLS", max_cols);
+    passes = host::chain_prior_passes(chain_offsets, chain_nodes, Q, N, kQueryChunk, max_cols, host::kChainPriorBudgetBytes);
+  } else {
+    for (int32_t c0 = 0; c0 < Q; c0 += kQueryChunk) {
+      host::ChainPriorPass ps;
+      ps.q0 = c0;
+      ps.nq = std::min<int32_t>(kQueryChunk, Q - c0);
+      passes.push_back(ps);
+    }
+  }
+  GmRowOp rop{};
+  const GmGraph g{l.ell_col.p, l.ell_w.p, l.deg.p, l.width};
+  float tol_g = 0.f;
+  if (prior) {
+    q.cp_diag.alloc((size_t)N);
+    launch_gm_row_diag(l.B.p, l.lamG + lamP + l.lamC, l.lamQ, N, q.cp_diag.p, l.stream);
+    rop.d = q.cp_diag.p;
+    rop.lamC = l.lamC;
+    tol_g = host::chain_prior_tol_g(tol, l.lamG, lamP, sh.max_X + sh.max_x * sh.scale);
+  }
+  q.cm_eoff.alloc((size_t)kQueryChunk + 1);
+  q.cm_gain.alloc(kQueryChunk);
+  q.cm_verdict.alloc(kQueryChunk);
+  q.cm_wk.alloc(kQueryChunk);
+  q.cm_wz.alloc(kQueryChunk);
+  host::ChainManyPaths paths;
+  host::ChainPriorSystems sys;
+  std::vector<host::ChainManyUnit> units;
+  std::vector<int32_t> eoff, path_of, hints, hnode;
+  std::vector<int64_t> hlongs;
+  std::vector<float> hpsi, hflts;
+  std::map<int32_t, int32_t> column_of;
+  for (const host::ChainPriorPass& ps : passes) {
+    const int32_t c0 = ps.q0, nq = ps.nq;
+    paths.clear();
+    host::chain_many_units_weighted(chain_offsets, chain_nodes, chain_weights, c0, nq, dev, N, paths, units, eoff, path_of);
+    q.cm_pcol.alloc(std::max<size_t>(paths.pcol.size(), 1));
+    q.cm_pa.alloc(std::max<size_t>(paths.pa.size(), 1));
+    if (!paths.pcol.empty()) {
+      HIP_CHECK(hipMemcpyAsync(q.cm_pcol.p, paths.pcol.data(), paths.pcol.size() * 4, hipMemcpyHostToDevice, l.stream));
+      HIP_CHECK(hipMemcpyAsync(q.cm_pa.p, paths.pa.data(), paths.pa.size() * 4, hipMemcpyHostToDevice, l.stream));
+    }
+    const size_t nu = units.size();
+    hpsi.assign((size_t)nq * l.ld, 0.f);
+    for (int32_t t = 0; t < nq; ++t)
+      std::copy(psis + (size_t)(c0 + t) * D, psis + (size_t)(c0 + t + 1) * D, hpsi.data() + (size_t)t * l.ld);
+    q.cm_psi.alloc(hpsi.size());
+    q.cm_units.alloc(nu);
+    q.cm_edge.alloc(4 * nu);
+    q.cm_term.alloc(2 * nu);
+    HIP_CHECK(hipMemcpyAsync(q.cm_psi.p, hpsi.data(), hpsi.size() * 4, hipMemcpyHostToDevice, l.stream));
+    HIP_CHECK(hipMemcpyAsync(q.cm_units.p, units.data(), nu * sizeof(host::ChainManyUnit), hipMemcpyHostToDevice, l.stream));
+    HIP_CHECK(hipMemcpyAsync(q.cm_eoff.p, eoff.data(), eoff.size() * 4, hipMemcpyHostToDevice, l.stream));
+    // the basis's own residual per query: |r_X| + |psi_q|_inf |r_x|
+    hflts.assign((size_t)nq, 0.f);
+    for (int32_t t = 0; t < nq; ++t) {
+      float pinf = 0.f;
+      for (int32_t d = 0; d < D; ++d) {
+        const float v = std::fabs(psis[(size_t)(c0 + t) * D + d]);
+        pinf = (v > pinf || v != v) ? v : pinf;
+      }
+      hflts[(size_t)t] = res_X + pinf * res_x;
+    }
+    CmEdgesArgs e{};
+    if (!prior) {
+      for (int32_t t = 0; t < nq; ++t) {
+        prior_res[c0 + t] = hflts[(size_t)t];
+        prior_iters[c0 + t] = 0;
+      }
+    } else {
+      // the panel: one unit right-hand side per distinct node of the pass
+      const int32_t ncol = (int32_t)ps.cols.size(), qc = ps.qc;
+      const host::ChainPriorLayout lay = host::chain_prior_layout(N, qc);
+      q.cp_scratch.alloc((size_t)lay.total);
+      char* const base = q.cp_scratch.p;
+      GmPanel p{};
+      p.X = reinterpret_cast<float*>(base + lay.X);
+      p.R = reinterpret_cast<float*>(base + lay.R);
+      p.P = reinterpret_cast<float*>(base + lay.P);
+      p.AP = reinterpret_cast<float*>(base + lay.AP);
+      p.part_a = reinterpret_cast<double*>(base + lay.part_a);
+      p.part_b = reinterpret_cast<double*>(base + lay.part_b);
+      p.rz = reinterpret_cast<double*>(base + lay.rz);
+      p.tol = reinterpret_cast<float*>(base + lay.tol);
+      p.alpha = reinterpret_cast<float*>(base + lay.alpha);
+      p.beta = reinterpret_cast<float*>(base + lay.beta);
+      p.res = reinterpret_cast<float*>(base + lay.res);
+      p.live = reinterpret_cast<int32_t*>(base + lay.live);
+      p.iters = reinterpret_cast<int32_t*>(base + lay.iters);
+      p.slab_live = reinterpret_cast<int32_t*>(base + lay.slab_live);
+      p.n_live = reinterpret_cast<int32_t*>(base + lay.n_live);
+      p.N = N;
+      p.slabs = qc / host::kGatesSlab;
+      p.parts = host::gates_parts(N);
+      p.part_rows = host::gates_part_rows(N);
+      p.nq = ncol;
+      int32_t* const node_d = reinterpret_cast<int32_t*>(base + lay.node);
+      hnode.assign((size_t)qc, -1);
+      column_of.clear();
+      for (int32_t c = 0; c < ncol; ++c) {
+        hnode[(size_t)c] = dev ? dev[ps.cols[(size_t)c]] : ps.cols[(size_t)c];
+        column_of[hnode[(size_t)c]] = c;
+      }
+      HIP_CHECK(hipMemcpyAsync(node_d, hnode.data(), (size_t)qc * 4, hipMemcpyHostToDevice, l.stream));
+      launch_gm_unit_source(p, node_d, rop, l.stream);
+      launch_gm_init(p, 0, tol_g, l.stream);
+      for (int32_t it = 1; it <= max_iters; ++it) {
+        launch_gm_apply_rows(p, g, rop, l.stream);
+        launch_gm_alpha(p, l.stream);
+        launch_gm_update_rows(p, rop, l.stream);
+        launch_gm_beta(p, it, l.stream);
+        int32_t live = 0;
+        if (it < max_iters) launch_gm_direction_rows(p, rop, l.stream);
+        HIP_CHECK(hipMemcpyAsync(&live, p.n_live + (it & 1), 4, hipMemcpyDeviceToHost, l.stream));
+        sync(l);
+        if (live == 0) break;
+      }
+      // the systems: one per distinct (chain, weights) of the pass
+      sys.clear();
+      for (const host::ChainPath& cp : paths.paths) sys.add(cp.rows, cp.ptr, cp.col, cp.w, column_of);
+      const size_t ns = sys.m.size();
+      hints.clear();
+      auto put = [&](const std::vector<int32_t>& v) {
+        const size_t at = hints.size();
+        hints.insert(hints.end(), v.begin(), v.end());
+        return at;
+      };
+      const size_t i_m = put(sys.m), i_col_at = put(sys.col_at), i_k_at = put(sys.k_at), i_cols = put(sys.cols),
+                   i_rows = put(sys.rows), i_kr = put(sys.kr), i_kc = put(sys.kc), i_qsys = put(path_of);
+      hlongs.assign(sys.t_at.begin(), sys.t_at.end());
+      int64_t tv_n = 0;
+      for (int32_t t = 0; t < nq; ++t) {
+        hlongs.push_back(tv_n);
+        tv_n += (int64_t)sys.m[(size_t)path_of[(size_t)t]] * l.ld;
+      }
+      hflts.insert(hflts.end(), sys.kw.begin(), sys.kw.end());  // [base | kw]
+      q.cp_ints.alloc(hints.size());
+      q.cp_longs.alloc(hlongs.size());
+      q.cp_flts.alloc(hflts.size() + 2 * (size_t)nq);
+      q.cp_T.alloc((size_t)std::max<int64_t>(sys.t_doubles, 1));
+      q.cp_tv.alloc((size_t)std::max<int64_t>(tv_n, 1));
+      HIP_CHECK(hipMemcpyAsync(q.cp_ints.p, hints.data(), hints.size() * 4, hipMemcpyHostToDevice, l.stream));
+      HIP_CHECK(hipMemcpyAsync(q.cp_longs.p, hlongs.data(), hlongs.size() * 8, hipMemcpyHostToDevice, l.stream));
+      HIP_CHECK(hipMemcpyAsync(q.cp_flts.p, hflts.data(), hflts.size() * 4, hipMemcpyHostToDevice, l.stream));
+      float* const pres_d = q.cp_flts.p + hflts.size();
+      int32_t* const pit_d = reinterpret_cast<int32_t*>(pres_d + nq);
+      CpSystemsArgs sa{};
+      sa.G = p.X;
+      sa.m = q.cp_ints.p + i_m;
+      sa.col_at = q.cp_ints.p + i_col_at;
+      sa.k_at = q.cp_ints.p + i_k_at;
+      sa.t_at = q.cp_longs.p;
+      sa.cols = q.cp_ints.p + i_cols;
+      sa.rows = q.cp_ints.p + i_rows;
+      sa.kr = q.cp_ints.p + i_kr;
+      sa.kc = q.cp_ints.p + i_kc;
+      sa.kw = q.cp_flts.p + nq;
+      sa.N = N;
+      sa.n_sys = (int32_t)ns;
+      sa.lamP = lamP;
+      sa.T = q.cp_T.p;
+      launch_cp_systems(sa, l.stream);
+      CpTvArgs ta{};
+      ta.X = bX;
+      ta.x4 = bx4;
+      ta.psi = q.cm_psi.p;
+      ta.T = q.cp_T.p;
+      ta.q_sys = q.cp_ints.p + i_qsys;
+      ta.m = sa.m;
+      ta.col_at = sa.col_at;
+      ta.t_at = sa.t_at;
+      ta.cols = sa.cols;
+      ta.rows = sa.rows;
+      ta.col_res = p.res;
+      ta.col_iters = p.iters;
+      ta.base = q.cp_flts.p;
+      ta.tv_at = q.cp_longs.p + ns;
+      ta.nq = nq;
+      ta.D = D;
+      ta.ld = l.ld;
+      ta.TV = q.cp_tv.p;
+      ta.prior_res = pres_d;
+      ta.prior_iters = pit_d;
+      launch_cp_tv(ta, l.stream);
+      HIP_CHECK(hipMemcpyAsync(prior_res + c0, pres_d, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
+      HIP_CHECK(hipMemcpyAsync(prior_iters + c0, pit_d, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
+      e.G = p.X;
+      e.q_sys = ta.q_sys;
+      e.sys_m = sa.m;
+      e.sys_col_at = sa.col_at;
+      e.sys_cols = sa.cols;
+      e.TV = q.cp_tv.p;
+      e.tv_at = ta.tv_at;
+    }
+    e.X = bX;
+    e.x4 = bx4;
+    e.Y = l.Y.p;
+    e.sqrt_deg = l.sqrt_deg.p;
+    e.col = l.ell_col.p;
+    e.adj = l.ell_a.p;
+    e.deg = l.deg.p;
+    e.psi = q.cm_psi.p;
+    e.units = q.cm_units.p;
+    e.pcol = q.cm_pcol.p;
+    e.pa = q.cm_pa.p;
+    e.width = l.width;
+    e.N = N;
+    e.D = D;
+    e.ld = l.ld;
+    e.n_units = (int64_t)nu;
+    e.lamC = l.lamC;
+    e.z_struct = q.cm_edge.p;
+    e.z_path = q.cm_edge.p + nu;
+    e.r_struct = q.cm_edge.p + 2 * nu;
+    e.r_path = q.cm_edge.p + 3 * nu;
+    e.term = q.cm_term.p;
+    e.zmax = q.cm_term.p + nu;
+    if (prior) launch_cm_edges_prior(e, l.stream);
+    else launch_cm_edges(e, l.stream);
+    CmFinishArgs f{};
+    f.eoff = q.cm_eoff.p;
+    f.term = e.term;
+    f.zmax = e.zmax;
+    f.nq = nq;
+    f.z_th = z_th;
+    f.gain = q.cm_gain.p;
+    f.verdict = q.cm_verdict.p;
+    f.weak_k = q.cm_wk.p;
+    f.weak_z = q.cm_wz.p;
+    launch_cm_finish(f, l.stream);
+    const int64_t at = host::chain_many_edge_at(chain_offsets, c0);
+    HIP_CHECK(hipMemcpyAsync(z_struct + at, e.z_struct, nu * 4, hipMemcpyDeviceToHost, l.stream));
+    HIP_CHECK(hipMemcpyAsync(z_path + at, e.z_path, nu * 4, hipMemcpyDeviceToHost, l.stream));
+    HIP_CHECK(hipMemcpyAsync(r_struct + at, e.r_struct, nu * 4, hipMemcpyDeviceToHost, l.stream));
+    HIP_CHECK(hipMemcpyAsync(r_path + at, e.r_path, nu * 4, hipMemcpyDeviceToHost, l.stream));
+    HIP_CHECK(hipMemcpyAsync(gain + c0, q.cm_gain.p, (size_t)nq * 8, hipMemcpyDeviceToHost, l.stream));
+    HIP_CHECK(hipMemcpyAsync(verdict + c0, q.cm_verdict.p, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
+    HIP_CHECK(hipMemcpyAsync(weakest_k + c0, q.cm_wk.p, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
+    HIP_CHECK(hipMemcpyAsync(weakest_z + c0, q.cm_wz.p, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
+    sync(l);  // (the host vectors above are reused by the next pass)
   }
 }
 

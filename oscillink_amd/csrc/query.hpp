@@ -217,9 +217,66 @@ struct CmEdgesArgs {
   float* r_path;
   double* term;
   double* zmax;          // max(z_struct, z_path) in fp64
+  // per-query chain priors (launch_cm_edges_prior): every gathered row r of query q becomes
+  // X'_r + x'_r psi_q + sum_b G[r, col_b] TV_q[b, :] over the m nodes of the query's chain system
+  const float* G;            // the pass's Green's columns, slab-major (gates_many_plan.hpp)
+  const int32_t* q_sys;      // [nq] the query's system
+  const int32_t* sys_m;      // per system: its nodes,
+  const int32_t* sys_col_at; // where their panel columns start in sys_cols
+  const int32_t* sys_cols;
+  const float* TV;           // query q's T_q V_q: m x ld floats at tv_at[q], pad columns zero
+  const int64_t* tv_at;
 };
 int cm_edge_blocks(int64_t n_units);
 void launch_cm_edges(const CmEdgesArgs& a, hipStream_t s);
+void launch_cm_edges_prior(const CmEdgesArgs& a, hipStream_t s);
+
+// T = (I - K Ghat)^-1 K per chain system of a pass, one 64-thread workgroup each: Ghat gathered from the panel, K = lamP W_path
+// scattered from the system's entries, Gauss-Jordan with partial pivoting in fp64 in LDS (two 64 x 64 arrays)
+struct CpSystemsArgs {
+  const float* G;
+  const int32_t* m;       // [n_sys]
+  const int32_t* col_at;  // [n_sys]
+  const int32_t* k_at;    // [n_sys + 1]
+  const int64_t* t_at;    // [n_sys]
+  const int32_t* cols;    // panel column per (system, local node)
+  const int32_t* rows;    // device row per (system, local node)
+  const int32_t* kr;
+  const int32_t* kc;
+  const float* kw;
+  int32_t N, n_sys;
+  float lamP;
+  double* T;
+};
+void launch_cp_systems(const CpSystemsArgs& a, hipStream_t s);
+
+// per query of the pass: TV_q = T_q V_q with V_q the chain rows of X' + x' psi_q^T (fp64 sums, stored fp32), the bound
+// base[q] + max_c sum_e res_e |TV_q[e, c]| and the most iterations of its columns
+struct CpTvArgs {
+  const float* X;      // the shifted basis, N x ld
+  const float* x4;
+  const float* psi;    // nq x ld
+  const double* T;
+  const int32_t* q_sys;
+  const int32_t* m;
+  const int32_t* col_at;
+  const int64_t* t_at;
+  const int32_t* cols;
+  const int32_t* rows;
+  const float* col_res;     // [qc] |r_e| of the panel's columns
+  const int32_t* col_iters;
+  const float* base;        // [nq] the basis's own residual for the query
+  const int64_t* tv_at;
+  int32_t nq, D, ld;
+  float* TV;
+  float* prior_res;         // [nq]
+  int32_t* prior_iters;     // [nq]
+};
+void launch_cp_tv(const CpTvArgs& a, hipStream_t s);
+
+// X *= f in place (the shifted basis's X' = lamG / (lamG + lamP) X''); part[b] = the block's max |X f| over the real columns
+int cp_scale_blocks(int64_t N);
+void launch_cp_scale_max(float* X, int32_t N, int32_t D, int32_t ld, float f, float* part, hipStream_t s);
 
 // per query of the chunk over its units [eoff[q], eoff[q + 1]): the gain, the verdict, the weakest link
 struct CmFinishArgs {

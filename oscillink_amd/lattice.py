@@ -118,6 +118,11 @@ class OscillinkLattice:
         self._qb_key: Optional[tuple] = None
         self._qb_scale = 0.0
         self.last_query_basis: dict[str, Any] = {}
+        # the basis of M + lamP I behind chain_receipt_many(lamP=...): a second slot, keyed like the first plus the shift
+        self._qbs_key: Optional[tuple] = None
+        self._qbs_scale = 0.0
+        self.last_shifted_basis: dict[str, Any] = {}
+        self.shifted_basis_solves = 0
         self._settle_callbacks: list = []
         self._logger = None
         self._receipt_secret: Optional[bytes] = None
@@ -270,6 +275,9 @@ class OscillinkLattice:
                 "fused_two_step_solves": int(gf.value), "anchor_gram_bytes": int(gb.value),
                 "anchor_gram_last_solve": int(gl.value), "anchor_gram_builds": int(gn.value),
                 "anchor_gram_redos": int(gr.value),
+                # chain_receipt_many(lamP=...) keeps the basis of M + lamP I beside the query basis: N x ld + N x 4 floats
+                # (ld >= D rounded up to 4); 0 until the first such call
+                "shifted_basis_bytes": 4 * self.N * (((self.D + 3) // 4) * 4 + 4) if self._qbs_key is not None else 0,
                 **{name: int(getattr(counters, name)) for name, _ in nat.Counters._fields_[1:]}}
 
     def anchor_gram(self) -> np.ndarray:
@@ -857,7 +865,7 @@ class OscillinkLattice:
         return out
 
     def chain_receipt_many(self, psis: np.ndarray, chains, z_th: float = 2.5, *, tol: float = 1e-4, max_iters: int = 256,
-                           as_arrays: bool = False):
+                           as_arrays: bool = False, lamP: Optional[float] = None, chain_weights=None):
         """`chain_receipt(chains[q], z_th)` for each row of `psis` (Q x D), as if `set_query(psis[q])` had been called, with
         the current graph, gates, own chain (add_chain), lambdas and U held fixed and without touching the lattice's state.
         `chains` is one chain (a sequence of API row ids, shared by every query) or a sequence of Q chains, 2 to 1024 nodes
@@ -867,35 +875,118 @@ class OscillinkLattice:
         the chain nodes and their graph and path neighbours are read.  A non-finite query row gets
         non-finite answers and changes no other query's.
 
+        With `lamP` (>= 0) every query's chain is also its chain PRIOR: query q gets what
+        `add_chain(chains[q], lamP=lamP, weights=chain_weights[q]); set_query(psis[q]); chain_receipt(chains[q], z_th)` gives
+        -- lamP L_path,q in the operator, the weighted path in the path residuals -- from one basis of the shifted operator
+        M + lamP I (a slot of its own beside the query basis: one more N x D array) and one Green's column per distinct chain
+        node.  The lattice must carry no chain of its own and a chain has at most 64 distinct nodes.  `chain_weights` is
+        None, one list shared with a shared chain, or a sequence parallel to `chains` of None or len(chain) - 1 finite
+        floats.  `lamP=0` reads the query basis and solves nothing.
+
         Returns Q dicts with chain_receipt's keys, or with `as_arrays=True` the arrays they are assembled from, under
         `Corpus.refine_many`'s names: `chain_offsets` int64 (Q + 1, over chain edges), `chain_z_struct`, `chain_z_path`,
         `chain_r_struct`, `chain_r_path` float32 (flat), `chain_gain` float64, `chain_verdict` bool, `chain_weakest_k` int32
-        (-1 when no edge's max(z) exceeds -1) and `chain_weakest_z` float32."""
+        (-1 when no edge's max(z) exceeds -1) and `chain_weakest_z` float32; with `lamP` also `chain_prior_res` float32 (per
+        query the bound on the residual of the implied U*, the stop test's quantity) and `chain_prior_iters` int32 (the most
+        iterations any of the query's Green's columns took)."""
         if self._has_comm:
             raise NotImplementedError("chain_receipt_many: lattices with a communicator (sharded / multi-rank) are not "
                                       "supported")
+        prior = lamP is not None
+        if not prior and chain_weights is not None:
+            raise ValueError("chain_weights given without lamP")
+        if prior:
+            if not np.isfinite(float(lamP)) or float(lamP) < 0:
+                raise ValueError("lamP must be >= 0")
+            if self._chain_nodes is not None:
+                raise ValueError("chain_receipt_many with lamP: the lattice has a chain of its own (clear_chain first)")
         P = rc.check_queries(psis, self.D, finite=False)
         Q = int(P.shape[0])
         lists, offsets, nodes = rc.chain_block(chains, Q, self.N)
         edge_offsets = offsets - np.arange(Q + 1, dtype=np.int64)
         n_edges = int(edge_offsets[-1])
+        weights = None
+        if prior:
+            weights = rc.chain_prior_weights(chain_weights, chains, lists, edge_offsets)
+            checked = set()  # (a shared chain is one list Q times)
+            for q, ch in enumerate(lists):
+                if id(ch) not in checked and len(set(ch)) > rc.MAX_PRIOR_NODES:
+                    raise ValueError(f"query {q}: with lamP a chain has at most {rc.MAX_PRIOR_NODES} distinct nodes, got "
+                                     f"{len(set(ch))}")
+                checked.add(id(ch))
         edge = np.zeros((4, max(n_edges, 1)), dtype=np.float32)
         gain = np.zeros(Q, dtype=np.float64)
         verdict, weak_k = np.zeros(Q, dtype=np.int32), np.zeros(Q, dtype=np.int32)
         weak_z = np.zeros(Q, dtype=np.float32)
+        prior_res, prior_iters = np.zeros(Q, dtype=np.float32), np.zeros(Q, dtype=np.int32)
         solved = False
         if Q > 0:
-            n0 = self.stats["query_basis_solves"]
-            self._ensure_query_basis(tol, max_iters, float(np.max(np.abs(P), where=np.isfinite(P), initial=0.0)))
-            solved = self.stats["query_basis_solves"] != n0
-            self._call("osc_chain_receipt_many", nat.f32(P), Q, nat.i64(offsets), nat.i32(nodes), float(z_th),
-                       *[nat.f32(edge[t]) for t in range(4)], gain.ctypes.data_as(C.POINTER(C.c_double)), nat.i32(verdict),
-                       nat.i32(weak_k), nat.f32(weak_z))
-        self._log("chain_receipt_many", {"Q": Q, "edges": n_edges, "basis_solved": solved})
+            psi_inf = float(np.max(np.abs(P), where=np.isfinite(P), initial=0.0))
+            outs = [*[nat.f32(edge[t]) for t in range(4)], gain.ctypes.data_as(C.POINTER(C.c_double)), nat.i32(verdict),
+                    nat.i32(weak_k), nat.f32(weak_z)]
+            if prior and float(lamP) > 0:
+                solved = self._ensure_shifted_basis(float(lamP), tol, max_iters, psi_inf)
+            else:
+                n0 = self.stats["query_basis_solves"]
+                self._ensure_query_basis(tol, max_iters, psi_inf)
+                solved = self.stats["query_basis_solves"] != n0
+            if prior:
+                self._call("osc_chain_prior_many", nat.f32(P), Q, nat.i64(offsets), nat.i32(nodes),
+                           None if weights is None else nat.f32(weights), float(lamP), float(tol), int(max_iters), float(z_th),
+                           *outs, nat.f32(prior_res), nat.i32(prior_iters))
+            else:
+                self._call("osc_chain_receipt_many", nat.f32(P), Q, nat.i64(offsets), nat.i32(nodes), float(z_th), *outs)
+        payload = {"Q": Q, "edges": n_edges, "basis_solved": solved}
+        if prior:
+            payload["lamP"] = float(lamP)
+        self._log("chain_receipt_many", payload)
+        if prior and Q > 0:
+            over = np.nonzero(~(prior_res <= tol) & np.all(np.isfinite(P), axis=1))[0]
+            if over.size:
+                self._log("chain_prior_convergence_warn", {"queries": int(over.size), "first": int(over[0]),
+                                                           "res": float(prior_res[over[0]]), "tol": tol,
+                                                           "iters": int(prior_iters[over[0]])})
         arr = dict(chain_offsets=edge_offsets, chain_z_struct=edge[0, :n_edges].copy(), chain_z_path=edge[1, :n_edges].copy(),
                    chain_r_struct=edge[2, :n_edges].copy(), chain_r_path=edge[3, :n_edges].copy(), chain_gain=gain,
                    chain_verdict=verdict != 0, chain_weakest_k=weak_k, chain_weakest_z=weak_z)
-        return arr if as_arrays else rc.chain_receipt_dicts(lists, arr)
+        if not as_arrays:
+            return rc.chain_receipt_dicts(lists, arr)
+        if prior:
+            arr.update(chain_prior_res=prior_res, chain_prior_iters=prior_iters)
+        return arr
+
+    def _ensure_shifted_basis(self, lamP: float, tol: float, max_iters: int, psi_inf: float) -> bool:
+        """Solve (or extend) the basis of the shifted operator M + lamP I in its own slot unless the resident one serves
+        |psi|_inf at this tolerance: `_qb_key`'s fields plus the shift.  True when a solve ran.  Touches neither the query
+        basis nor `stats`."""
+        self._push_params()
+        key = (self._qb_version, float(self.lamG), float(self.lamC), float(self.lamQ), float(self.lamP), float(tol),
+               int(max_iters), float(lamP))
+        scale = max(float(psi_inf), 1e-6)
+        if key == self._qbs_key and scale <= self._qbs_scale:
+            return False
+        fresh = key != self._qbs_key
+        iters = np.zeros(2, dtype=np.int32)
+        res = np.zeros(2, dtype=np.float32)
+        ms = C.c_double(0.0)
+        self._call("osc_query_basis_shifted", float(lamP), float(tol), int(max_iters), scale, int(fresh), nat.i32(iters),
+                   nat.f32(res), C.byref(ms))
+        prev = self.last_shifted_basis if not fresh else {}
+        it_X = int(iters[0]) if fresh else int(prev["iters"]["X"])
+        res_X = float(res[0]) if fresh else float(prev["res"]["X"])
+        it_x, res_x = int(iters[1]), float(res[1])
+        converged = bool(res_X <= 0.5 * tol * (1 + 1e-5) and res_x * scale <= 0.5 * tol * (1 + 1e-5))
+        self.last_shifted_basis = {"lamP": float(lamP), "iters": {"X": it_X, "x": it_x}, "res": {"X": res_X, "x": res_x},
+                                   "converged": converged, "solve_ms": float(ms.value), "psi_inf": scale,
+                                   "x_only": not fresh}
+        self._qbs_key = key
+        self._qbs_scale = scale
+        self.shifted_basis_solves += 1
+        self._log("shifted_basis_solve", {"tol": tol, "max_iters": max_iters, **self.last_shifted_basis})
+        if not converged:
+            self._log("shifted_basis_convergence_warn", {"res": self.last_shifted_basis["res"], "tol": tol,
+                                                         "iters": self.last_shifted_basis["iters"], "psi_inf": scale})
+        return True
 
     def diffusion_gates_many(self, psis: np.ndarray, *, beta: float = 1.0, gamma: float = 0.1, method: str = "direct",
                              tol: float = 1e-4, max_iters: int = 256, clamp: bool = True) -> dict:
@@ -1220,6 +1311,7 @@ class OscillinkLattice:
         self._touch()
         self._qb_version += 1
         self._qb_key = None
+        self._qbs_key = None
         self._invalidate_cache()
 
     def append_info(self) -> dict[str, Any]:
