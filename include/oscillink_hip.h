@@ -243,7 +243,8 @@ int osc_anchor_ap2_info(osc_handle h, int64_t* streamed_second_applies, int64_t*
  * iterations, unset: lattices of at least 96000 rows): fused_two_step_solves = solves served so since creation, bytes = device
  * memory held for the sums ((22 ld + 6) doubles; 0: not built or dropped), last_solve = whether the last general-path solve
  * took the route, builds = times the sums were formed, redos = solves that stopped before iteration 3 (or had a column the
- * sums cannot serve) and were run again on the summed route (measurement aid) */
+ * sums cannot serve) and were run again on the summed route (measurement aid).  OSC_TWO_STEPS = stream (unset) / blocked: the
+ * launch geometry of the fused pass -- the update kernels' or the blocked matvec's (the reference form); same bits either way */
 int osc_anchor_gram_info(osc_handle h, int64_t* fused_two_step_solves, int64_t* bytes, int32_t* last_solve, int64_t* builds,
                          int64_t* redos);
 /* the Gram sums as held (test aid): 22 arrays of ld doubles -- <W^j Y, W^k Y> for j <= k <= 3 in the order (0,0) (0,1) (0,2)

@@ -843,6 +843,40 @@ __global__ __launch_bounds__((CW + 1) * 64) void k_init_cached_ap2(const BlkArgs
 // Q1 (k_update_xr), p2 = z1 + beta1 p1 and A p2 = (1 + beta1) Q1 - (m alpha1) T (k_update_p_ap2), r2 = r1 - alpha2 A p2, p3 =
 // z2 + beta2 p2 (k_update_p), x2 = (x0 + alpha1 p1) + alpha2 p2 (k_update_x_ring) -- so the same scalars give the same bits.
 // Stores r2 (row-major), p3 (slab-major) and x2 (row-major); no column sums, no fold: the list wave has nothing to do.
+//
+// One float4 of that pass (two_steps_elem): from the element's x0, W Y, W W Y, W W W Y, the row's b, s and s2 and the column's
+// psi, alpha1, beta1, alpha2, beta2 to r2, p3 and x2.  Both forms of the pass call it -- the blocked one below (the reference
+// form) and k_init_two_steps_stream -- and every output element depends on nothing else, so the launch geometry cannot
+// change a bit.
+__device__ __forceinline__ void two_steps_elem(const BlkArgs& a, const BlkInit& ii, float b, float sm, float sm2, float4 x, float4 w,
+                                               float4 v, float4 t, float4 psi4, float4 al1, float4 be1, float4 al2, float4 be2,
+                                               float4& r2, float4& p3, float4& x2) {
+  float4 r0, z0;
+  blk_init_row(a, ii, b, x, x, w, psi4, r0, z0);
+  const float cs = fmaf(a.cs_B, b, a.cs_const);  // (init_cached_body's scalars)
+  const float invMd = 1.f / (fmaf(ii.md_B, b, ii.md_const) + 1e-12f);
+  const float u = __fsub_rn(__fadd_rn(ii.rbU, ii.rbY), cs);
+  const float qs = __fmul_rn(__fmul_rn(ii.rbB, b), sm);
+  const float qs2 = __fmul_rn(__fmul_rn(ii.rbB, b), sm2);
+  float r2v, p3v, x2v;
+  auto one = [&](float xv, float rv, float zv, float wyv, float wwv, float w3v, float pv, float a1, float b1, float a2, float b2) {
+    const float wz = __fmul_rn(invMd, fmaf(a.cW, wwv, fmaf(u, wyv, __fmul_rn(qs, pv))));    // (W z0)_i
+    const float q1 = fmaf(cs, zv, -__fmul_rn(a.cW, wz));                                     // Q1 = A p1
+    const float wwz = __fmul_rn(invMd, fmaf(a.cW, w3v, fmaf(u, wwv, __fmul_rn(qs2, pv))));  // (W W z0)_i
+    const float wq = fmaf(cs, wz, -__fmul_rn(a.cW, wwz));                                    // (W Q1)_i
+    const float tt = fmaf(cs, q1, -__fmul_rn(a.cW, wq));                                     // T = A Q1
+    const float r1 = fmaf(-q1, a1, rv);
+    const float p2 = fmaf(zv, b1, __fmul_rn(r1, invMd));
+    const float ap2v = fmaf(__fadd_rn(1.f, b1), q1, -__fmul_rn(__fmul_rn(invMd, a1), tt));
+    r2v = fmaf(-ap2v, a2, r1);
+    p3v = fmaf(p2, b2, __fmul_rn(r2v, invMd));
+    x2v = fmaf(p2, a2, fmaf(zv, a1, xv));
+  };
+  one(x.x, r0.x, z0.x, w.x, v.x, t.x, psi4.x, al1.x, be1.x, al2.x, be2.x); r2.x = r2v; p3.x = p3v; x2.x = x2v;
+  one(x.y, r0.y, z0.y, w.y, v.y, t.y, psi4.y, al1.y, be1.y, al2.y, be2.y); r2.y = r2v; p3.y = p3v; x2.y = x2v;
+  one(x.z, r0.z, z0.z, w.z, v.z, t.z, psi4.z, al1.z, be1.z, al2.z, be2.z); r2.z = r2v; p3.z = p3v; x2.z = x2v;
+  one(x.w, r0.w, z0.w, w.w, v.w, t.w, psi4.w, al1.w, be1.w, al2.w, be2.w); r2.w = r2v; p3.w = p3v; x2.w = x2v;
+}
 template <int CW>
 __global__ __launch_bounds__((CW + 1) * 64) void k_init_two_steps(const BlkArgs a, const BlkInit ii, const BlkInitAp ap, const BlkInitAp2 ap2,
                                                                   const BlkTwoSteps ts) {
@@ -893,32 +927,8 @@ __global__ __launch_bounds__((CW + 1) * 64) void k_init_two_steps(const BlkArgs 
       for (int i = 0; i < EC; ++i) {
         const int g = k * EC + i, row = row_first + g * wk.W8;
         if (g >= ngall || row >= wk.rhi || !cok) continue;
-        float4 r0, z0;
-        blk_init_row(a, ii, bb[i], x[i], x[i], w[i], psi4, r0, z0);
-        const float cs = fmaf(a.cs_B, bb[i], a.cs_const);  // (init_cached_body's scalars)
-        const float invMd = 1.f / (fmaf(ii.md_B, bb[i], ii.md_const) + 1e-12f);
-        const float u = __fsub_rn(__fadd_rn(ii.rbU, ii.rbY), cs);
-        const float qs = __fmul_rn(__fmul_rn(ii.rbB, bb[i]), sm[i]);
-        const float qs2 = __fmul_rn(__fmul_rn(ii.rbB, bb[i]), sm2[i]);
-        float r2v, p3v, x2v;
-        auto one = [&](float xv, float rv, float zv, float wyv, float wwv, float w3v, float pv, float a1, float b1, float a2, float b2) {
-          const float wz = __fmul_rn(invMd, fmaf(a.cW, wwv, fmaf(u, wyv, __fmul_rn(qs, pv))));    // (W z0)_i
-          const float q1 = fmaf(cs, zv, -__fmul_rn(a.cW, wz));                                     // Q1 = A p1
-          const float wwz = __fmul_rn(invMd, fmaf(a.cW, w3v, fmaf(u, wwv, __fmul_rn(qs2, pv))));  // (W W z0)_i
-          const float wq = fmaf(cs, wz, -__fmul_rn(a.cW, wwz));                                    // (W Q1)_i
-          const float tt = fmaf(cs, q1, -__fmul_rn(a.cW, wq));                                     // T = A Q1
-          const float r1 = fmaf(-q1, a1, rv);
-          const float p2 = fmaf(zv, b1, __fmul_rn(r1, invMd));
-          const float ap2v = fmaf(__fadd_rn(1.f, b1), q1, -__fmul_rn(__fmul_rn(invMd, a1), tt));
-          r2v = fmaf(-ap2v, a2, r1);
-          p3v = fmaf(p2, b2, __fmul_rn(r2v, invMd));
-          x2v = fmaf(p2, a2, fmaf(zv, a1, xv));
-        };
         float4 r2, p3, x2;
-        one(x[i].x, r0.x, z0.x, w[i].x, v[i].x, t[i].x, psi4.x, al1.x, be1.x, al2.x, be2.x); r2.x = r2v; p3.x = p3v; x2.x = x2v;
-        one(x[i].y, r0.y, z0.y, w[i].y, v[i].y, t[i].y, psi4.y, al1.y, be1.y, al2.y, be2.y); r2.y = r2v; p3.y = p3v; x2.y = x2v;
-        one(x[i].z, r0.z, z0.z, w[i].z, v[i].z, t[i].z, psi4.z, al1.z, be1.z, al2.z, be2.z); r2.z = r2v; p3.z = p3v; x2.z = x2v;
-        one(x[i].w, r0.w, z0.w, w[i].w, v[i].w, t[i].w, psi4.w, al1.w, be1.w, al2.w, be2.w); r2.w = r2v; p3.w = p3v; x2.w = x2v;
+        two_steps_elem(a, ii, bb[i], sm[i], sm2[i], x[i], w[i], v[i], t[i], psi4, al1, be1, al2, be2, r2, p3, x2);
         st4_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(ii.R) + ((uint32_t)row * ldb + cb)), r2);
         st4_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(ii.Xcopy) + ((uint32_t)row * ldb + cb)), x2);
         st4(reinterpret_cast<float*>(reinterpret_cast<char*>(pbase) + ((uint32_t)row * 128u + lr16)), p3);
@@ -938,6 +948,83 @@ __global__ __launch_bounds__((CW + 1) * 64) void k_init_two_steps(const BlkArgs 
       consume(k + 1, xs[1], ws[1], bv[1], vs[1], ss[1], t3[1], s2[1]);
     } else {
       consume(k, xs[0], ws[0], bv[0], vs[0], ss[0], t3[0], s2[0]);
+    }
+  }
+}
+
+// The same pass in the geometry of the update kernels (k_update_x_ring): 256 threads, the rows [row0, N) a plain grid-stride
+// range, LPR lanes over a row's columns in NCH chunks of LPR float4s, RPT row groups per wave and trip.  blockIdx.y picks the
+// column tile of NCH * LPR * 4 columns (windows wider than one tile; tiles start at multiples of 32).  Row-major operands
+// (W W Y, W W W Y, r2, x2) sit at row * ld + col, slab-major ones (x0 = Ys, W Y, p3) at blk_off(N, row, col).  The per-column
+// scalars are loaded once, before the row loop.  No test around a load (see init_cached_body): a lane without a column reads the
+// window's first, a lane without a row the last row, and only the stores are guarded -- so all RPT * NCH * 4 loads of a trip are
+// in flight before the first use.  No LDS, no barrier.  Same bits as k_init_two_steps (two_steps_elem).
+template <int LPR, int NCH, int RPT>
+__global__ __launch_bounds__(256) void k_init_two_steps_stream(const BlkArgs a, const BlkInit ii, const BlkInitAp ap, const BlkInitAp2 ap2,
+                                                               const BlkTwoSteps ts) {
+  constexpr int RPW = 64 / LPR;
+  if (*ts.go != 1u) return;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int sub = lane / LPR, lr = lane % LPR;
+  const int32_t ld = a.ld;
+  const int32_t t0 = a.c0 + (int32_t)blockIdx.y * (NCH * LPR * 4);
+  int coff[NCH], cld[NCH];
+  bool cok[NCH];
+  float4 psi4[NCH], al1[NCH], be1[NCH], al2[NCH], be2[NCH];
+#pragma unroll
+  for (int ch = 0; ch < NCH; ++ch) {
+    coff[ch] = t0 + (ch * LPR + lr) * 4;
+    cok[ch] = coff[ch] < a.c1;
+    cld[ch] = cok[ch] ? coff[ch] : a.c0;
+    psi4[ch] = ld4(ii.psi + cld[ch]);
+    al1[ch] = ld4(ts.alpha1 + cld[ch]);
+    be1[ch] = ld4(ts.beta1 + cld[ch]);
+    al2[ch] = ld4(ts.alpha2 + cld[ch]);
+    be2[ch] = ld4(ts.beta2 + cld[ch]);
+  }
+  uint32_t cb[NCH], sb[NCH];  // byte offsets of the lane's columns within a row: row-major, slab-major (blk_off less the row)
+#pragma unroll
+  for (int ch = 0; ch < NCH; ++ch) {
+    cb[ch] = (uint32_t)cld[ch] * 4u;
+    sb[ch] = ((uint32_t)(cld[ch] >> 5) * (uint32_t)a.N * 32u + (uint32_t)(cld[ch] & 31)) * 4u;
+  }
+  const int rend = a.N, rlast = a.N - 1;
+  for (int64_t rb = ts.row0 + ((int64_t)blockIdx.x * 4 + wave) * (RPW * RPT); rb < rend; rb += (int64_t)gridDim.x * 4 * (RPW * RPT)) {
+    int row[RPT], rld[RPT];
+    float bv[RPT], sm[RPT], sm2[RPT];
+    float4 x[RPT][NCH], w[RPT][NCH], v[RPT][NCH], t[RPT][NCH];
+#pragma unroll
+    for (int j = 0; j < RPT; ++j) {
+      row[j] = (int)rb + j * RPW + sub;
+      rld[j] = min(row[j], rlast);
+      if constexpr (LPR == 64) rld[j] = __builtin_amdgcn_readfirstlane(rld[j]);  // (wave-uniform: the row's scalars by scalar loads)
+      bv[j] = a.B[rld[j]];
+      sm[j] = ap.wsum[rld[j]];
+      sm2[j] = ap2.wsum2[rld[j]];
+      // row base (wave-uniform at LPR == 64) + the lane's 32-bit column offset (the launcher checks that N * ld * 4 fits)
+      const size_t rrow = (size_t)rld[j] * ld, rslab = (size_t)rld[j] * 32;
+#pragma unroll
+      for (int ch = 0; ch < NCH; ++ch) {
+        x[j][ch] = ld4_stream_at(a.X + rslab, sb[ch]);
+        w[j][ch] = ld4_stream_at(ii.WY + rslab, sb[ch]);
+        v[j][ch] = ld4_stream_at(ap.WW + rrow, cb[ch]);
+        t[j][ch] = ld4_stream_at(ap2.W3 + rrow, cb[ch]);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < RPT; ++j) {
+      if (row[j] >= rend) continue;
+#pragma unroll
+      for (int ch = 0; ch < NCH; ++ch) {
+        if (!cok[ch]) continue;
+        float4 r2, p3, x2;
+        two_steps_elem(a, ii, bv[j], sm[j], sm2[j], x[j][ch], w[j][ch], v[j][ch], t[j][ch], psi4[ch], al1[ch], be1[ch], al2[ch], be2[ch], r2,
+                       p3, x2);
+        // (a row and a column that are stored are the ones that were loaded: the same offsets)
+        st4_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(ii.R + (size_t)rld[j] * ld) + cb[ch]), r2);
+        st4_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(ii.Xcopy + (size_t)rld[j] * ld) + cb[ch]), x2);
+        st4(reinterpret_cast<float*>(reinterpret_cast<char*>(ii.Z + (size_t)rld[j] * 32) + sb[ch]), p3);
+      }
     }
   }
 }
@@ -1687,6 +1774,30 @@ inline Shape pick_shape(int ncols) {
     }                                                                \
   } while (0)
 
+// k_init_two_steps_stream: lanes per row x float4 chunks per lane x row groups per trip of one column tile; a window wider than a
+// tile takes several (blockIdx.y), cut evenly.  Up to 768 columns these are the update kernels' shapes (pick_shape) on the solve's
+// grid: the sweep at 100 000 x 768 over chunks, rows per trip and grid is flat (profiles/two_steps_stream_sweep.txt; RPT > 1 is
+// instantiated by scripts/exp/two_steps_stream_sweep.hip alone).
+struct TwoStepsShape {
+  int lpr, nch, rpt;
+};
+inline TwoStepsShape pick_two_steps_shape(int ncols) {
+  if (ncols <= 64) return {16, 1, 1};
+  if (ncols <= 128) return {32, 1, 1};
+  const int tiles = (ncols + 767) / 768;
+  return {64, ((ncols + tiles - 1) / tiles + 255) / 256, 1};
+}
+#define OSC_TWO_STEPS_SHAPE_SWITCH(sh, CALL)                         \
+  do {                                                               \
+    if ((sh).lpr == 16) { CALL(16, 1, 1); }                          \
+    else if ((sh).lpr == 32) { CALL(32, 1, 1); }                     \
+    else switch ((sh).nch) {                                         \
+      case 1: CALL(64, 1, 1); break;                                 \
+      case 2: CALL(64, 2, 1); break;                                 \
+      default: CALL(64, 3, 1); break;                                \
+    }                                                                \
+  } while (0)
+
 }  // namespace
 
 int spmm_grid(int64_t N, int32_t ncols) {
@@ -1807,8 +1918,15 @@ void launch_init_cached(const BlkArgs& a, int grid, hipStream_t s, const BlkInit
   HIP_CHECK(hipGetLastError());
 }
 void launch_init_two_steps(const BlkArgs& a, int grid, hipStream_t s, const BlkInit& init, int variant, const BlkInitAp& ap,
-                           const BlkInitAp2& ap2, const BlkTwoSteps& ts) {
-  blocked_args_check(a, grid, variant);
+                           const BlkInitAp2& ap2, const BlkTwoSteps& ts, bool stream) {
+  if (stream) {
+    if (grid < 1 || a.N < 1 || ts.row0 < 0 || ts.row0 > a.N || (a.c0 & 31) != 0 || a.c1 <= a.c0 || a.c1 > a.ld || (a.c1 & 3) != 0 ||
+        (a.ld & 31) != 0 || (int64_t)a.N * a.ld * 4 >= ((int64_t)1 << 32) || !a.X || !a.B)
+      throw std::runtime_error("two-step INIT pass: unsupported arguments");
+  } else {
+    blocked_args_check(a, grid, variant);
+    if (ts.row0 != 0) throw std::runtime_error("two-step INIT pass: the blocked form covers every row");
+  }
   if (!init.R || !init.Z || !init.Xcopy || !init.psi || !init.WY || init.Y != nullptr || !ap.WW || !ap.wsum || !ap2.W3 || !ap2.wsum2 ||
       !ts.alpha1 || !ts.alpha2 || !ts.beta1 || !ts.beta2 || !ts.go)
     throw std::runtime_error("two-step INIT pass: bad arguments");
@@ -1816,6 +1934,18 @@ void launch_init_two_steps(const BlkArgs& a, int grid, hipStream_t s, const BlkI
     if (out == a.X || out == init.WY || out == ap.WW || out == ap2.W3) throw std::runtime_error("two-step INIT pass: aliased arrays");
   if (init.R == init.Z || init.R == init.Xcopy || init.Z == init.Xcopy)  // ... or another output
     throw std::runtime_error("two-step INIT pass: aliased arrays");
+  if (stream) {
+    const TwoStepsShape sh = pick_two_steps_shape(a.c1 - a.c0);
+    const int tile = sh.lpr * 4 * sh.nch, tiles = (a.c1 - a.c0 + tile - 1) / tile;
+    const int rows_per_wg = 4 * (64 / sh.lpr) * sh.rpt;
+    const int64_t need = ((int64_t)(a.N - ts.row0) + rows_per_wg - 1) / rows_per_wg;
+    const dim3 g((unsigned)std::max<int64_t>(1, std::min<int64_t>(need, grid / tiles)), (unsigned)tiles);  // (the solve's grid over the tiles)
+#define CALLS(L, C, R) hipLaunchKernelGGL((k_init_two_steps_stream<L, C, R>), g, dim3(256), 0, s, a, init, ap, ap2, ts)
+    OSC_TWO_STEPS_SHAPE_SWITCH(sh, CALLS);
+#undef CALLS
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
 #define CALL(G, W, P, E) hipLaunchKernelGGL((k_init_two_steps<W>), dim3(grid), dim3((W + 1) * 64), 0, s, a, init, ap, ap2, ts)
   OSC_BLK_SHAPE_SWITCH(variant, CALL);
 #undef CALL

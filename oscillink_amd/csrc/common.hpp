@@ -193,12 +193,15 @@ void launch_anchor_gram_scalars(const GramScalarArgs& a, hipStream_t s);
 // k_init_two_steps: the cached INIT pass of BlkInitAp2 run through iterations 1 and 2 with the scalars above.  Of BlkInit it
 // writes R (r2, row-major), Z (p3, slab-major) and Xcopy (x2 = x0 + alpha1 p1 + alpha2 p2, row-major; required); of BlkInitAp
 // and BlkInitAp2 it reads WW, wsum, W3, wsum2 and writes nothing.  A no-op unless *go == 1.
+// Two forms with the same bits (launch_init_two_steps): the streaming one (k_init_two_steps_stream, the update kernels' launch
+// geometry; of BlkArgs it reads X, B, N, ld, c0, c1 and the operator's scalars only) and the blocked one, the reference form.
 struct BlkTwoSteps {
   const float* alpha1;
   const float* alpha2;
   const float* beta1;
   const float* beta2;
   const uint32_t* go;
+  int32_t row0;  // first row (streaming form; the blocked form's geometry covers every row: 0 there)
 };
 
 enum SpmmMode { SPMM_AP = 0, SPMM_INIT = 1, SPMM_DOT = 2 };
@@ -363,8 +366,9 @@ void launch_apply_blocked(const BlkArgs& a, int grid, hipStream_t s, const BlkIn
 // ap2 (with ap): ... and T = A (A p1) (BlkInitAp2)
 void launch_init_cached(const BlkArgs& a, int grid, hipStream_t s, const BlkInit& init, int variant, const BlkInitAp* ap = nullptr,
                         const BlkInitAp2* ap2 = nullptr);
+// stream: the streaming form (its shape by the window alone, as launch_update_x_ring's; `variant` is the blocked form's)
 void launch_init_two_steps(const BlkArgs& a, int grid, hipStream_t s, const BlkInit& init, int variant, const BlkInitAp& ap,
-                           const BlkInitAp2& ap2, const BlkTwoSteps& ts);
+                           const BlkInitAp2& ap2, const BlkTwoSteps& ts, bool stream);
 void launch_row_weight_sums(const float* w, const int32_t* deg, int32_t width, int32_t N, float* out, hipStream_t s);
 // out_i = sum_j W_ij v_j over the ELL row, in stored order (BlkInitAp2::wsum2 from BlkInitAp::wsum)
 void launch_row_weighted_sums(const int32_t* col, const float* w, const int32_t* deg, int32_t width, int32_t N, const float* v,

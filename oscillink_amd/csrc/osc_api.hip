@@ -37,6 +37,7 @@ void read_env_solver(L& h) {
   if (num("OSC_ANCHOR_AP", v)) h.anchor_ap = v != 0 ? 1 : 0;
   if (num("OSC_ANCHOR_AP2", v)) h.anchor_ap2 = v != 0 ? 1 : 0;
   if (num("OSC_ANCHOR_GRAM", v)) h.anchor_gram = v != 0 ? 1 : 0;
+  if (const char* e = getenv("OSC_TWO_STEPS")) h.two_steps_stream = strcmp(e, "blocked") != 0;
   if (num("OSC_RECEIPT_PAIR", v)) h.receipt_pair = v != 0;
   if (const char* e = getenv("OSC_SHARD")) h.shard_mode = !strcmp(e, "row") ? 1 : 0;
   if (num("OSC_ROW_FAKE_SHARDS", v)) h.fake_row_shards = std::max(0, v);

@@ -118,6 +118,9 @@ struct osc_lattice {
   DevBuf<double> gram;
   DevBuf<uint32_t> gram_go;  // the fused pass's gate word
   int anchor_gram = -1;
+  // The form of that pass (launch_init_two_steps), same bits either way.  OSC_TWO_STEPS: stream (unset) -- the update kernels'
+  // launch geometry -- or blocked, the matvec's: the reference form.
+  bool two_steps_stream = true;
   int64_t fused_two_step_solves = 0, anchor_gram_builds = 0, anchor_gram_redos = 0;
   bool anchor_gram_last = false;
   int64_t yu_copies = 0;     // whole-array Y -> U copies made for this handle (osc_counters::y_to_u_copies)

@@ -636,8 +636,8 @@ struct CgSolve {
     BlkInit ti = bi;
     ti.Z = dir(3);
     ti.Xcopy = b.X;
-    BlkTwoSteps ts{ga.alpha1, ga.alpha2, ga.beta1, ga.beta2, ga.go};
-    launch_init_two_steps(ba, grid, h.stream, ti, plan.shape, ap, ap2, ts);
+    BlkTwoSteps ts{ga.alpha1, ga.alpha2, ga.beta1, ga.beta2, ga.go, 0};
+    launch_init_two_steps(ba, grid, h.stream, ti, plan.shape, ap, ap2, ts, h.two_steps_stream);
     gram_route = true;
     ring.applied = 2;  // directions 1 and 2 are in x2
     h.fused_two_step_solves += 1;
