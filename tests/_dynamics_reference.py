@@ -78,8 +78,8 @@ def with_isolated_rows(g, extra):
 
 def hub_graph(N, rng):
     """One row of degree 300 (row 0), rows of degree 65 - 130 (310, 320, 330), everything else of degree 2 - 6 (half of them: 3);
-    random weights.  N = 400."""
-    assert N == 400
+    random weights.  N >= 400 (the dynamics fixtures: 400; rows from 400 on sit on the ring only)."""
+    assert N >= 400
     edges = set()
 
     def add(i, j):
