@@ -163,6 +163,20 @@ int osc_create_updated(osc_handle base, const int32_t* ids, const float* Ynew, i
 int osc_update_info(osc_handle h, int32_t* route, int64_t* replaced_rows, int64_t* merged_rows, int64_t* redo_rows, int32_t* family,
                     double* score_ms, double* merge_ms, double* back_ms, int64_t* merge_hits, int32_t* denied);
 
+/* The state U of `src` carried onto `dst`, device to device: row a of dst (API ids on both sides) takes U's row
+ * src_row_of_dst[a] of src bit for bit, all row-pitch columns of it, or -- entry -1 -- starts at dst's own anchor Y[a].
+ * The map has dst.N entries.  Made for a handle that osc_create_appended / osc_create_removed / osc_create_updated built
+ * from src: it replaces the host round trip that keeps a settled state over such a change, `U = lat.U` -> the mutation ->
+ * `lat.U = U2` (osc_get_U, two N x D host arrays, osc_set_U), which the reference has no counterpart of (its lattice
+ * cannot change).  Nothing else of dst changes and src is only read.
+ * While src's U still aliases its anchors (never settled, or reset) the carried state is dst's anchors row for row under
+ * all three creations: dst is left at U = Y and nothing moves.  Otherwise one kernel writes dst's U in dst's internal row
+ * order, ordered behind the work enqueued on src's stream; the call returns when it has finished, so src may be
+ * destroyed at once.  OSC_E_INVALID, before any device work and with nothing changed, for a NULL handle or map (message in
+ * osc_last_error(NULL) when dst is NULL, else osc_last_error(dst)), dst == src, handles on different devices, differing D
+ * or row pitch, a communicator on either handle, a column-sharded U in src, a map entry outside [-1, src.N). */
+int osc_carry_state(osc_handle dst, osc_handle src, const int32_t* src_row_of_dst);
+
 /* rebuild_graph (lattice.py:760-801) */
 int osc_rebuild_graph(osc_handle h, int32_t k, float row_cap, int32_t deterministic, int64_t seed);
 

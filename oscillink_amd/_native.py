@@ -69,6 +69,7 @@ SIGNATURES = {
     "osc_remove_info": (C.c_int, [Handle, c_i32p, c_i64p, c_i64p, c_i64p, c_i32p, c_f64p, c_f64p, c_i32p]),
     "osc_create_updated": (C.c_int, [Handle, c_i32p, c_f32p, C.c_int64, C.c_int32, C.POINTER(Handle)]),
     "osc_update_info": (C.c_int, [Handle, c_i32p, c_i64p, c_i64p, c_i64p, c_i32p, c_f64p, c_f64p, c_f64p, c_i64p, c_i32p]),
+    "osc_carry_state": (C.c_int, [Handle, Handle, c_i32p]),
     "osc_rebuild_graph": (C.c_int, [Handle, C.c_int32, C.c_float, C.c_int32, C.c_int64]),
     "osc_graph_stats": (C.c_int, [Handle, c_i64p, c_i32p, c_f64p]),
     "osc_build_info": (C.c_int, [Handle, c_i32p, c_i32p, c_i64p]),

@@ -493,6 +493,46 @@ int osc_update_info(osc_handle h, int32_t* route, int64_t* replaced_rows, int64_
   });
 }
 
+int osc_carry_state(osc_handle dst, osc_handle src, const int32_t* src_row_of_dst) {
+  auto refuse = [&](const std::string& why) {
+    (dst ? dst->err : g_create_error) = "osc_carry_state: " + why;
+    return OSC_E_INVALID;
+  };
+  // everything below runs on the host: a refused call has touched no device and neither handle
+  if (!dst || !src || !src_row_of_dst) return refuse("need dst, src and a map of dst.N entries");
+  if (dst == src) return refuse("dst and src are one handle");
+  if (dst->device != src->device) return refuse("the handles live on different devices");
+  if (dst->D != src->D || dst->ld != src->ld) return refuse("the handles differ in D or in the row pitch");
+  if (dst->comm != nullptr || src->comm != nullptr) return refuse("a handle with a communicator keeps its own state");
+  if (src->u_sharded) return refuse("src holds a column-sharded U");
+  for (int64_t a = 0; a < dst->N; ++a)
+    if (src_row_of_dst[a] < -1 || (int64_t)src_row_of_dst[a] >= src->N) return refuse("a map entry is outside [-1, src.N)");
+  return guarded(dst, [&](L& d) {
+    d.u_sharded = false;
+    if (src->u_is_y) {  // every carried row is an anchor the new handle holds already, under all three seeded creations
+      reset_u_to_y(d);
+      return;
+    }
+    struct Event {
+      hipEvent_t e = nullptr;
+      ~Event() {
+        if (e) (void)hipEventDestroy(e);
+      }
+    } after_src;
+    DevBuf<int32_t> map;
+    map.alloc((size_t)d.N);
+    HIP_CHECK(hipMemcpyAsync(map.p, src_row_of_dst, (size_t)d.N * 4, hipMemcpyHostToDevice, d.stream));
+    // src's U is written in src's stream, the kernel runs in dst's: it waits for what src has enqueued so far
+    HIP_CHECK(hipEventCreateWithFlags(&after_src.e, hipEventDisableTiming));
+    HIP_CHECK(hipEventRecord(after_src.e, src->stream));
+    HIP_CHECK(hipStreamWaitEvent(d.stream, after_src.e, 0));
+    launch_carry_rows(d.U.p, d.Y.p, src->U.p, map.p, permuted(d) ? d.perm_d.p : nullptr, permuted(*src) ? src->inv_d.p : nullptr,
+                      d.N, d.ld, d.stream);
+    d.u_is_y = false;
+    sync(d);  // (src and the map have been read: the caller may destroy src, the map's block goes back to the pool)
+  });
+}
+
 int osc_host_alloc(int64_t bytes, void** out) {
   if (!out || bytes <= 0) return OSC_E_INVALID;
   *out = host_pool_alloc((size_t)bytes);

@@ -9,6 +9,10 @@ namespace osc {
 // scatter == false: out[i] = in[map[i]] ; scatter == true: out[map[i]] = in[i]
 void launch_move_rows(float* out, const float* in, const int32_t* map, int64_t N, int32_t ld, bool scatter,
                       hipStream_t s);
+// dstU[d] = srcU[src_inv[map[dst_perm[d]]]] where map[.] >= 0, else dstY[d]: rows of ld floats (ld % 4 == 0), d < N; map in the
+// API ids of both handles, a null order = the identity (osc_carry_state)
+void launch_carry_rows(float* dstU, const float* dstY, const float* srcU, const int32_t* map, const int32_t* dst_perm,
+                       const int32_t* src_inv, int64_t N, int32_t ld, hipStream_t s);
 void launch_move_f32(float* out, const float* in, const int32_t* map, int64_t N, bool scatter, hipStream_t s);
 void launch_permute_ell(const int32_t* col_in, const float* a_in, const float* w_in, const int32_t* deg_in,
                         const int32_t* from, const int32_t* relabel, int32_t width, int64_t N, int32_t* col_out,

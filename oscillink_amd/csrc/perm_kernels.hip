@@ -22,6 +22,35 @@ __global__ __launch_bounds__(256) void k_move_rows(float* out, const float* in, 
   }
 }
 
+// The state of one handle carried onto another (osc_carry_state).  Destination device row d is API
+// row a = dst_perm[d] of the destination; map[a] = o names the API row of the source whose state it takes -- device row
+// src_inv[o] of srcU -- or, o < 0, the row starts at its own anchor dstY[d].  A null order is the identity.  One 8-lane group
+// per row, a float4 per lane (a row of a line-aligned pitch is a run of whole 128-byte lines, 32 rows per workgroup as in
+// gates_many_kernels.hip); the row's three index loads are one dependent chain, issued before its first line is asked for,
+// then up to four lines of the row are in flight per group.  All ld columns are copied, the padding as it is.
+__global__ __launch_bounds__(256) void k_carry_rows(float* __restrict__ dstU, const float* __restrict__ dstY,
+                                                    const float* __restrict__ srcU, const int32_t* __restrict__ map,
+                                                    const int32_t* __restrict__ dst_perm, const int32_t* __restrict__ src_inv,
+                                                    int64_t N, int32_t ld) {
+  const int lr = threadIdx.x & 7;
+  const int64_t d = (int64_t)blockIdx.x * 32 + (threadIdx.x >> 3);
+  if (d >= N) return;
+  const int32_t a = dst_perm ? dst_perm[d] : (int32_t)d;
+  const int32_t o = map[a];
+  const float* __restrict__ from = dstY + d * ld;
+  if (o >= 0) from = srcU + (int64_t)(src_inv ? src_inv[o] : o) * ld;
+  float* __restrict__ to = dstU + d * ld;
+  int c = lr * 4;
+  for (; c + 96 < ld; c += 128) {
+    const float4 v0 = ld4(from + c), v1 = ld4(from + c + 32), v2 = ld4(from + c + 64), v3 = ld4(from + c + 96);
+    st4(to + c, v0);
+    st4(to + c + 32, v1);
+    st4(to + c + 64, v2);
+    st4(to + c + 96, v3);
+  }
+  for (; c < ld; c += 32) st4(to + c, ld4(from + c));
+}
+
 template <typename T, bool SCATTER>
 __global__ void k_move_1d(T* out, const T* in, const int32_t* map, int64_t N) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -129,6 +158,13 @@ void launch_move_rows(float* out, const float* in, const int32_t* map, int64_t N
   const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((N + 3) / 4, 4096));
   if (scatter) hipLaunchKernelGGL(k_move_rows<true>, dim3(grid), dim3(256), 0, s, out, in, map, N, ld);
   else hipLaunchKernelGGL(k_move_rows<false>, dim3(grid), dim3(256), 0, s, out, in, map, N, ld);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_carry_rows(float* dstU, const float* dstY, const float* srcU, const int32_t* map, const int32_t* dst_perm,
+                       const int32_t* src_inv, int64_t N, int32_t ld, hipStream_t s) {
+  hipLaunchKernelGGL(k_carry_rows, dim3((unsigned)((N + 31) / 32)), dim3(256), 0, s, dstU, dstY, srcU, map, dst_perm, src_inv,
+                     N, ld);
   HIP_CHECK(hipGetLastError());
 }
 

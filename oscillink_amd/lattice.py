@@ -29,6 +29,22 @@ _DENSE_VIEW_LIMIT = 20000  # N above which dense N x N views are refused (1.6 GB
 _DENSE_EXPORT_LIMIT = 4096  # N up to which export_state / save_state also write the reference's dense `A`
 
 
+# The maps of `keep_state=True`: per row of the lattice afterwards, the row before whose state it
+# keeps, -1 for a fresh row, which starts at its anchor.  int32, the form osc_carry_state takes.
+def _state_map_append(N: int, M: int) -> np.ndarray:
+    return np.concatenate([np.arange(N, dtype=np.int32), np.full(M, -1, dtype=np.int32)])
+
+
+def _state_map_remove(keep: np.ndarray) -> np.ndarray:
+    return np.ascontiguousarray(np.nonzero(keep)[0], dtype=np.int32)
+
+
+def _state_map_update(N: int, ids: np.ndarray) -> np.ndarray:
+    src = np.arange(N, dtype=np.int32)
+    src[ids] = -1
+    return src
+
+
 class OscillinkLattice:
     """Short-term coherence lattice: mutual-kNN graph + SPD system + Jacobi-PCG settle (reference lattice.py:23-31)."""
 
@@ -1220,21 +1236,28 @@ class OscillinkLattice:
             raise ValueError("mode must be 'auto', 'incremental' or 'rebuild'")
         return self._APPEND_MODES[mode]
 
-    def _become(self, op: str, cannot: str, create, rows: int, N_new: int, B_new: np.ndarray, chain_nodes) -> None:
+    def _become(self, op: str, cannot: str, create, rows: int, N_new: int, B_new: np.ndarray, chain_nodes,
+                state_map: Optional[np.ndarray] = None) -> None:
         """What append, remove and update share once their arguments are checked: `create(new_h)` calls the operation's
         osc_create_* on this lattice's handle; lambdas, psi, the gates `B_new` and the chain (on `chain_nodes`) are carried
-        to the new handle, which then replaces this object's.  A failure leaves the lattice exactly as it was."""
+        to the new handle, and with `state_map` (keep_state=True: one of the `_state_map_*`) the state U, device to device;
+        the new handle then replaces this object's.  A failure leaves the lattice exactly as it was."""
         if getattr(self, "_has_comm", False):
             raise nat.NativeError(f"{op}: a lattice with a communicator cannot {cannot} (multi-rank handles are out of scope)")
         new_h = nat.Handle()
         t0 = time.time()
         create(new_h)
         self._carry_settings_to(new_h, B_new, chain_nodes)
+        if state_map is not None:
+            self._carry_state_to(new_h, state_map, N_new)
         if chain_nodes is not None:
             self._chain_nodes = [int(c) for c in chain_nodes]
         self._swap_handle(new_h, N_new, B_new, t0)
         info = getattr(self, op + "_info")()
-        self._log(op, {"rows": rows, "N": self.N, "route": info["route"], "redo_rows": info["redo_rows"]})
+        payload = {"rows": rows, "N": self.N, "route": info["route"], "redo_rows": info["redo_rows"]}
+        if state_map is not None:
+            payload["keep_state"] = True
+        self._log(op, payload)
 
     def _seeded_info(self, fn: str, keys: str) -> dict[str, Any]:
         """One of osc_append_info / osc_remove_info / osc_update_info: `keys` names its outputs in order (route,
@@ -1246,13 +1269,15 @@ class OscillinkLattice:
         info["score_family"] = ("none", "mfma", "butterfly")[info["score_family"]]
         return info
 
-    def append(self, Ynew: np.ndarray, gates: Optional[np.ndarray] = None, *, mode: str = "auto") -> np.ndarray:
+    def append(self, Ynew: np.ndarray, gates: Optional[np.ndarray] = None, *, mode: str = "auto",
+               keep_state: bool = False) -> np.ndarray:
         """Add the rows of `Ynew` (M x D) behind the lattice's own and return their ids N .. N + M - 1.
 
         The lattice afterwards is the one `OscillinkLattice(np.concatenate([Y, Ynew]), ...)` would be with this lattice's
-        settings applied: same graph, U = Y (the state is NOT carried over an append), lambdas, psi, chain and lamP kept,
-        gates = the old gates followed by `gates` (ones when None).  Logger, callbacks, receipt secret, signature and detail
-        modes stay.  mode "incremental" grows the kNN lists from the kept ones and raises where that is not possible,
+        settings applied: same graph, U = Y (the state is NOT carried over an append unless `keep_state=True`: then every
+        old row keeps its row of U bit for bit, moved on the device, and only the new rows start at their anchors), lambdas,
+        psi, chain and lamP kept, gates = the old gates followed by `gates` (ones when None).  Logger, callbacks, receipt
+        secret, signature and detail modes stay.  mode "incremental" grows the kNN lists from the kept ones and raises where that is not possible,
         "rebuild" builds the concatenated anchors from scratch on the device, "auto" lets the planner choose
         (`append_info()` says which).  Only `Ynew` crosses the bus.  A failure leaves the lattice exactly as it was."""
         code = self._mode_code(mode)
@@ -1274,7 +1299,8 @@ class OscillinkLattice:
 
         ids = np.arange(self.N, self.N + M, dtype=np.int64)
         B_new = np.concatenate([self._B, np.ones(M, dtype=np.float32) if g_new is None else g_new]).astype(np.float32)
-        self._become("append", "grow", create, M, self.N + M, B_new, self._chain_nodes)
+        self._become("append", "grow", create, M, self.N + M, B_new, self._chain_nodes,
+                     _state_map_append(self.N, M) if keep_state else None)
         return ids
 
     def _carry_settings_to(self, new_h, B_new: np.ndarray, chain_nodes) -> None:
@@ -1293,8 +1319,23 @@ class OscillinkLattice:
             L.osc_destroy(new_h)
             raise
 
+    def _carry_state_to(self, new_h, state_map: np.ndarray, N_new: int) -> None:
+        """This lattice's U onto a handle that is to replace this object's (osc_carry_state), row `a` of the new handle from
+        row `state_map[a]`, its own anchor where that is -1; a failure destroys the new handle and leaves the object as it
+        was."""
+        L = nat.lib()
+        try:
+            m = np.ascontiguousarray(state_map, dtype=np.int32)
+            if m.shape != (N_new,):
+                raise ValueError("state map length mismatch the rows of the new lattice")
+            nat.check(L.osc_carry_state(new_h, self._h, nat.i32(m)), new_h, "osc_carry_state")
+        except Exception:
+            L.osc_destroy(new_h)
+            raise
+
     def _swap_handle(self, new_h, N_new: int, B_new: np.ndarray, t0: float) -> None:
-        """The object becomes the lattice of `new_h` (U = Y, nothing cached); the old handle is destroyed."""
+        """The object becomes the lattice of `new_h` (U as the handle holds it: its anchors unless a state was carried onto
+        it; nothing cached); the old handle is destroyed."""
         old_h, self._h = self._h, new_h
         nat.lib().osc_destroy(old_h)
         self.N = N_new
@@ -1321,12 +1362,13 @@ class OscillinkLattice:
                                  "back_half_ms merge_hits merge_scan_bytes denied")
 
     # ------------------------------------------------------------------ remove (not in the reference)
-    def remove(self, ids, *, mode: str = "auto") -> np.ndarray:
+    def remove(self, ids, *, mode: str = "auto", keep_state: bool = False) -> np.ndarray:
         """Drop the rows `ids` names (any integer array-like, any order, duplicates allowed) and return `new_id_of_old`: one
         int64 entry per old row, its id afterwards, -1 for a removed row.  Kept rows are renumbered densely, in order.
 
         The lattice afterwards is the one `OscillinkLattice(np.delete(Y, ids, axis=0), ...)` would be with this lattice's
-        settings applied: same graph, U = Y (the state is NOT carried over a removal), lambdas, psi and lamP kept, gates =
+        settings applied: same graph, U = Y (the state is NOT carried over a removal unless `keep_state=True`: then every
+        kept row keeps its row of U bit for bit, moved on the device), lambdas, psi and lamP kept, gates =
         `np.delete(B, ids)`, a chain carried with its nodes renumbered (`ids` naming a chain node raises: `clear_chain()`
         first).  Logger, callbacks, receipt secret, signature and detail modes stay.  mode "incremental" shrinks the kNN
         lists from the kept ones and raises where that is not possible, "rebuild" builds the kept anchors from scratch on the
@@ -1361,7 +1403,8 @@ class OscillinkLattice:
                       "osc_create_removed")
 
         B_new = np.ascontiguousarray(self._B[keep], dtype=np.float32)
-        self._become("remove", "shrink", create, M, self.N - M, B_new, chain_new)
+        self._become("remove", "shrink", create, M, self.N - M, B_new, chain_new,
+                     _state_map_remove(keep) if keep_state else None)
         return new_id_of_old
 
     def remove_info(self) -> dict[str, Any]:
@@ -1374,13 +1417,16 @@ class OscillinkLattice:
                                  "denied")
 
     # ------------------------------------------------------------------ update (not in the reference)
-    def update(self, ids, Ynew: np.ndarray, gates: Optional[np.ndarray] = None, *, mode: str = "auto") -> np.ndarray:
+    def update(self, ids, Ynew: np.ndarray, gates: Optional[np.ndarray] = None, *, mode: str = "auto",
+               keep_state: bool = False) -> np.ndarray:
         """Row `ids[j]` becomes `Ynew[j]` (ids: distinct integers in [0, N), any order; Ynew: M x D) and `ids` comes back as
         int64.  No row moves: N, the row pitch, the effective k and every id stay.
 
         The lattice afterwards is the one `OscillinkLattice(Y2, ...)` would be, `Y2 = Y.copy(); Y2[ids] = Ynew`, with this
-        lattice's settings applied: same graph, U = Y2 (the state is NOT carried over an update), lambdas, psi, chain and lamP
-        kept (a replaced row may be a chain node: the path prior depends on node identity only), gates unchanged except
+        lattice's settings applied: same graph, U = Y2 (the state is NOT carried over an update unless `keep_state=True`:
+        then every row that is not replaced keeps its row of U bit for bit, moved on the device, and a replaced row starts at
+        its new anchor, since its old state describes another vector), lambdas, psi, chain and lamP kept
+        (a replaced row may be a chain node: the path prior depends on node identity only), gates unchanged except
         `B[ids] = gates` where `gates` (length M) is given.  Logger, callbacks, receipt secret, signature and detail modes
         stay.  mode "incremental" keeps the kNN lists that name no replaced row and raises where that is not possible,
         "rebuild" builds the changed anchors from scratch on the device, "auto" lets the planner choose (`update_info()`
@@ -1419,7 +1465,8 @@ class OscillinkLattice:
         B_new = np.array(self._B, dtype=np.float32)
         if g_new is not None:
             B_new[arr] = g_new
-        self._become("update", "change rows", create, M, self.N, B_new, self._chain_nodes)
+        self._become("update", "change rows", create, M, self.N, B_new, self._chain_nodes,
+                     _state_map_update(self.N, arr) if keep_state else None)
         return arr
 
     def update_info(self) -> dict[str, Any]:
