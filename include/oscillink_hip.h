@@ -266,6 +266,18 @@ int osc_anchor_gram_info(osc_handle h, int64_t* fused_two_step_solves, int64_t* 
  * order (1,1) (1,s) (1,s2) (s,s) (s,s2) (s2,s2); cap = doubles `out` holds; OSC_E_UNSUPPORTED while no sums are held */
 int osc_anchor_gram_read(osc_handle h, double* out, int64_t cap);
 
+/* iteration 3 of such a solve in one launch (one step further: alpha3, beta3 and |r3| come from the sums of the two vectors A p3
+ * adds to the seven, W W W 1 and W W W W Y, so the iteration's matvec forms r3 and p4 in its epilogue and the alpha reduction, the
+ * x-r kernel, the beta reduction and iteration 4's p update are not launched; OSC_ANCHOR_GRAM3 = 0 off / 1 wherever the fused
+ * two-step pass runs, unset: lattices of at least 96000 rows): fused_three_step_solves = solves served so since creation, bytes
+ * = device memory held ((13 ld + 4) doubles and N floats; 0: not built or dropped), last_solve = whether the last general-path
+ * solve took the route, builds = times the sums were formed (measurement aid) */
+int osc_anchor_gram3_info(osc_handle h, int64_t* fused_three_step_solves, int64_t* bytes, int32_t* last_solve, int64_t* builds);
+/* those sums as held (test aid): 13 arrays of ld doubles -- <W^j Y, W^4 Y> for j = 0..4, then <a, W^4 Y> for a = 1, s, s2, s3 (s
+ * = W 1, s2 = W s, s3 = W s2), then <s3, W^j Y> for j = 0..3 -- and the four <a, s3>, a = 1, s, s2, s3; cap = doubles `out`
+ * holds; OSC_E_UNSUPPORTED while none are held */
+int osc_anchor_gram3_read(osc_handle h, double* out, int64_t cap);
+
 /* the block-major copy of the graph the blocked matvec walks, built for `nb` source blocks (test / diagnostic aid; no
  * reference counterpart): slot_col / slot_w [nb][N][4] = {neighbour row, W_ij} per (source block, row, slot), unused slots
  * {first row of the block, 0}; rows whose edges exceed 4 nb slots list the rest in over_col / over_w[over_first[i] ..

@@ -112,5 +112,105 @@ OSC_GRAM_HD Scalars two_steps(const double (&G)[kBasis][kBasis], const Op& o) {
   return s;
 }
 
+// ---- the third step ------------------------------------------------------------------------------------------------------
+// A p3 adds two vectors to the seven: psi_c s3 (s3 = W s2) and (W W W W Y)_c.  p3 . A p3 and |r3|^2 are then quadratic forms in
+// the 9 x 9 Gram matrix of
+//     psi 1, psi s, psi s2, psi s3, Y, W Y, W W Y, W W W Y, W W W W Y
+// (the a-vectors first, as above, so that the seven-vector forms are sums of the same terms in the same order).  The sums that
+// matrix needs beyond the seven vectors' are a second block (L::gram3, read back by osc_anchor_gram3_read): kGram3PerColumn
+// arrays of ld doubles, then kGram3Lattice doubles.  Array j < 5: <W^j Y, W^4 Y>; array 5 + a: <a, W^4 Y> for a in (1, s, s2,
+// s3); array 9 + j: <s3, W^j Y>, j < 4; the lattice's four: <a, s3> for a in (1, s, s2, s3).  Every one is summed directly from
+// the stored float arrays (no <W^j Y, W^4 Y> = <W^(j+1) Y, W^3 Y>).
+constexpr int kGram3PerColumn = 13;  // 5 <W^j Y, W^4 Y> + 4 <a, W^4 Y> + 4 <s3, W^j Y>
+constexpr int kGram3Lattice = 4;     // <a, s3>
+constexpr int kBasis3 = 9;
+
+OSC_GRAM_HD int y4_index(int j) { return j; }        // <W^j Y, W^4 Y>, j <= 4
+OSC_GRAM_HD int a4_index(int a) { return 5 + a; }    // <a, W^4 Y>, a in 0..3
+OSC_GRAM_HD int s3y_index(int j) { return 9 + j; }   // <s3, W^j Y>, j <= 3
+OSC_GRAM_HD int lat3_index(int a) { return a; }      // <a, s3>, a in 0..3
+
+// One column's 9 x 9 Gram matrix: the seven vectors' part from the first block (fill's entries, moved to the new order), the
+// rest from the second (col3[q * stride3], lat3).
+OSC_GRAM_HD void fill3(double (&G)[kBasis3][kBasis3], const double* col, size_t stride, const double* lat, const double* col3,
+                       size_t stride3, const double* lat3, double psi) {
+  for (int a = 0; a < 3; ++a)
+    for (int b = a; b < 3; ++b) G[a][b] = G[b][a] = psi * psi * lat[lat_index(a, b)];
+  for (int a = 0; a < 4; ++a) G[a][3] = G[3][a] = psi * psi * lat3[lat3_index(a)];
+  for (int a = 0; a < 3; ++a)
+    for (int j = 0; j < 4; ++j) G[a][4 + j] = G[4 + j][a] = psi * col[(size_t)ay_index(a, j) * stride];
+  for (int j = 0; j < 4; ++j) G[3][4 + j] = G[4 + j][3] = psi * col3[(size_t)s3y_index(j) * stride3];
+  for (int a = 0; a < 4; ++a) G[a][8] = G[8][a] = psi * col3[(size_t)a4_index(a) * stride3];
+  for (int j = 0; j < 4; ++j)
+    for (int k = j; k < 4; ++k) G[4 + j][4 + k] = G[4 + k][4 + j] = col[(size_t)yy_index(j, k) * stride];
+  for (int j = 0; j < 5; ++j) G[4 + j][8] = G[8][4 + j] = col3[(size_t)y4_index(j) * stride3];
+}
+
+struct Scalars3 {
+  Scalars two;       // iterations 1 and 2: two_steps()' values to the bit (the same terms in the same order, the rest zeros)
+  float alpha3 = 0.f, beta3 = 0.f;
+  float res3 = 0.f;  // |r3| of this column
+  double rz3 = 0.0;  // r3 . z3: what iteration 4's alpha and beta divide
+  bool usable3 = false;
+};
+
+OSC_GRAM_HD double form3(const double (&G)[kBasis3][kBasis3], const double (&v)[kBasis3], const double (&w)[kBasis3]) {
+  double t = 0.0;
+  for (int a = 0; a < kBasis3; ++a) {
+    double row = 0.0;
+    for (int b = 0; b < kBasis3; ++b) row += G[a][b] * w[b];
+    t += v[a] * row;
+  }
+  return t;
+}
+// out = A v; W shifts psi 1 -> psi s -> psi s2 -> psi s3 and Y -> ... -> W W W W Y (p1, p2 and p3 have no psi s3 and no
+// W W W W Y component)
+OSC_GRAM_HD void apply3(const Op& o, const double (&v)[kBasis3], double (&out)[kBasis3]) {
+  double wv[kBasis3] = {0.0, v[0], v[1], v[2], 0.0, v[4], v[5], v[6], v[7]};
+  for (int a = 0; a < kBasis3; ++a) out[a] = o.cs * v[a] - o.cW * wv[a];
+}
+
+// two_steps()' recurrence one iteration further: p3 = z2 + beta2 p2 (k_update_p), alpha3 = r2 . z2 / (p3 . A p3 + 1e-18)
+// (k_reduce_alpha), r3 = r2 - alpha3 A p3 (k_update_xr), res3, beta3 and r3 . z3 as k_reduce_beta rounds them.  usable3: two's
+// rules, and the same for the third iteration's values.
+OSC_GRAM_HD Scalars3 three_steps(const double (&G)[kBasis3][kBasis3], const Op& o) {
+  Scalars3 t;
+  Scalars& s = t.two;
+  double r0[kBasis3] = {o.qb, 0.0, 0.0, 0.0, o.u, o.cW, 0.0, 0.0, 0.0};
+  double p1[kBasis3], q1[kBasis3], r1[kBasis3], p2[kBasis3], ap2[kBasis3], r2[kBasis3], p3[kBasis3], ap3[kBasis3], r3[kBasis3];
+  for (int a = 0; a < kBasis3; ++a) p1[a] = o.m * r0[a];
+  apply3(o, p1, q1);
+  const double rr0 = form3(G, r0, r0), rz0 = o.m * rr0;
+  const double pq1 = form3(G, p1, q1);
+  s.alpha1 = (float)(rz0 / (pq1 + 1e-18));
+  for (int a = 0; a < kBasis3; ++a) r1[a] = r0[a] - (double)s.alpha1 * q1[a];
+  const double rr1 = form3(G, r1, r1), rz1 = o.m * rr1;
+  s.res1 = (float)sqrt(rr1);
+  s.beta1 = (float)(rz1 / (rz0 + 1e-18));
+  for (int a = 0; a < kBasis3; ++a) p2[a] = o.m * r1[a] + (double)s.beta1 * p1[a];
+  apply3(o, p2, ap2);
+  const double pq2 = form3(G, p2, ap2);
+  s.alpha2 = (float)(rz1 / (pq2 + 1e-18));
+  for (int a = 0; a < kBasis3; ++a) r2[a] = r1[a] - (double)s.alpha2 * ap2[a];
+  const double rr2 = form3(G, r2, r2);
+  s.res2 = (float)sqrt(rr2);
+  s.rz2 = o.m * rr2;
+  s.beta2 = (float)(s.rz2 / (rz1 + 1e-18));
+  s.usable = finite(rr0) && finite(pq1) && finite(rr1) && finite(pq2) && finite(rr2) && finite((double)s.alpha1) &&
+             finite((double)s.alpha2) && finite((double)s.beta1) && finite((double)s.beta2) && rr0 > 0.0 && pq1 >= 0.0 &&
+             rr1 >= 0.0 && pq2 >= 0.0 && rr2 >= 0.0;
+  for (int a = 0; a < kBasis3; ++a) p3[a] = o.m * r2[a] + (double)s.beta2 * p2[a];
+  apply3(o, p3, ap3);
+  const double pq3 = form3(G, p3, ap3);
+  t.alpha3 = (float)(s.rz2 / (pq3 + 1e-18));
+  for (int a = 0; a < kBasis3; ++a) r3[a] = r2[a] - (double)t.alpha3 * ap3[a];
+  const double rr3 = form3(G, r3, r3);
+  t.res3 = (float)sqrt(rr3);
+  t.rz3 = o.m * rr3;
+  t.beta3 = (float)(t.rz3 / (s.rz2 + 1e-18));
+  t.usable3 = s.usable && finite(pq3) && finite(rr3) && finite((double)t.alpha3) && finite((double)t.beta3) && pq3 >= 0.0 && rr3 >= 0.0;
+  return t;
+}
+
 }  // namespace gram
 }  // namespace osc

@@ -437,10 +437,17 @@ __device__ __forceinline__ void blk_init_row(const BlkArgs& a, const BlkInit& ii
 // WY (INIT only): the pass also stores every row's sum (acc, as it enters the epilogue's arithmetic) slab-major into ii.WY:
 // the operand of k_init_cached, which serves the later solves from the same x0 on the same graph copy.  That form takes
 // no separate rhs term (ii.Y == nullptr: y is x0), so the y rows' registers pay for the store.
-template <int GM, int CW, bool INIT = false, int PD = 1, int WPE = 4, bool WY = false>
-__global__ __launch_bounds__((CW + 1) * 64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_apply_blocked(const BlkArgs a,
-                                                                                                                const BlkInit ii) {
+// FUSED (BlkFused in BlkInit's place; not with INIT): iteration 3 of an anchor start whose alpha3 and beta3 were known before the
+// launch (k_anchor_gram_scalars, three_steps).  Gather rounds, list wave and phases are the loop form's; the epilogue also
+// fetches the row of r2 (streamed, with the own-row loads), loads the slab's four alpha3 and beta3 per lane, forms o = A p3 as
+// the loop form does, r3 = r2 - alpha3 o as k_update_xr does and p4 = z3 + beta3 p3 as k_update_p does (p3: the own row, in
+// hand for the diagonal term), and stores r3 over r2 and p4 slab-major.  o is never stored, and with nothing to sum there is no
+// fold: the two streaming passes and the two column reductions between matvec 3 and matvec 4 are gone.
+template <int GM, int CW, bool INIT = false, int PD = 1, int WPE = 4, bool WY = false, bool FUSED = false>
+__global__ __launch_bounds__((CW + 1) * 64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_apply_blocked(
+    const BlkArgs a, const std::conditional_t<FUSED, BlkFused, BlkInit> ii) {
   static_assert(INIT || !WY, "only the INIT pass stores the row sums");
+  static_assert(!(INIT && FUSED), "the fused form is an iteration, not the INIT pass");
   constexpr int SL = OSC_BLK_SLOTS, NT = (CW + 1) * 64;
   __shared__ __attribute__((aligned(16))) float red[CW + 1][32];
   // per gathering wave: the slots of each of its rows in the current block, and (other half) in the next one
@@ -448,10 +455,15 @@ __global__ __launch_bounds__((CW + 1) * 64) __attribute__((amdgpu_waves_per_eu(W
   if constexpr (!INIT) {  // (the INIT pass is never speculative)
     if (a.gate != nullptr && *a.gate <= a.gate_tol) return;
   }
+  if constexpr (FUSED) {
+    if (*ii.go != 1u) return;
+  }
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int sub = lane >> 3, lr = lane & 7;
   const int32_t ld = a.ld;
-  for (int c = a.c0 + threadIdx.x; c < a.c1; c += NT) a.part[(size_t)blockIdx.x * ld + c] = 0.f;
+  if constexpr (!FUSED) {
+    for (int c = a.c0 + threadIdx.x; c < a.c1; c += NT) a.part[(size_t)blockIdx.x * ld + c] = 0.f;
+  }
   if ((int)(blockIdx.x >> 3) >= a.xs) return;
   const int xcd = (int)(blockIdx.x & 7), wgx = (int)(blockIdx.x >> 3);  // (blk_work's arithmetic, spelled out: see there)
   const int xgroups = a.xs_groups, xgrp = xcd % xgroups, xpart = xcd / xgroups, parts = 8 / xgroups;
@@ -517,9 +529,11 @@ __global__ __launch_bounds__((CW + 1) * 64) __attribute__((amdgpu_waves_per_eu(W
       if (ph + 1 < nphase) fetch_slots(ph + 1);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      if ((ph + 1) % per_slab == 0) {
-        const int sc0 = phase(ph).sc0;
-        blk_fold<CW + 1>(f4(0.f), red, a.part, ld, sc0, min(a.c1, sc0 + 32), wave, lane);
+      if constexpr (!FUSED) {
+        if ((ph + 1) % per_slab == 0) {
+          const int sc0 = phase(ph).sc0;
+          blk_fold<CW + 1>(f4(0.f), red, a.part, ld, sc0, min(a.c1, sc0 + 32), wave, lane);
+        }
       }
     }
     return;
@@ -599,9 +613,10 @@ __global__ __launch_bounds__((CW + 1) * 64) __attribute__((amdgpu_waves_per_eu(W
       // Own rows / gates / rest descriptors of EC groups at a time (these loads miss).  Loads and stores of a wave retire
       // in issue order, so the loads of batch k + 1 are issued BEFORE the stores of batch k: otherwise every batch would
       // also wait for the previous batch's stores to be acknowledged.
-      constexpr int EC = WPE <= 2 ? 4 : INIT ? 1 : 2, NBATCH = (GM + EC - 1) / EC;  // (INIT: the y rows take the second group's registers; two groups: 72 spills)
+      // (FUSED: the r rows are a second stream per group, as the y rows are for INIT)
+      constexpr int EC = FUSED ? (WPE <= 2 ? 2 : 1) : WPE <= 2 ? 4 : INIT ? 1 : 2, NBATCH = (GM + EC - 1) / EC;  // (INIT: the y rows take the second group's registers; two groups: 72 spills)
       float4 xs[2][EC];
-      float4 ys[2][INIT && !WY ? EC : 1];
+      float4 ys[2][(INIT && !WY) || FUSED ? EC : 1];  // (FUSED: the rows of r2)
       int2 rr[2][EC];
       float bv[2][EC];
       float4 psi4 = f4(0.f);
@@ -615,14 +630,19 @@ __global__ __launch_bounds__((CW + 1) * 64) __attribute__((amdgpu_waves_per_eu(W
         zbase = ii.Z + (size_t)(p.sc0 >> 5) * (size_t)a.N * 32;
         if constexpr (WY) wybase = ii.WY + (size_t)(p.sc0 >> 5) * (size_t)a.N * 32;
       }
-      auto fetch = [&](int k, float4 (&x)[EC], float4 (&y)[INIT && !WY ? EC : 1], int2 (&r)[EC], float (&bb)[EC]) {
+      [[maybe_unused]] float4 al4 = f4(0.f), be4 = f4(0.f);
+      if constexpr (FUSED) {
+        if (cok) al4 = ld4(ii.alpha + p.sc0 + lr * 4), be4 = ld4(ii.beta + p.sc0 + lr * 4);
+        zbase = ii.Pout + (size_t)(p.sc0 >> 5) * (size_t)a.N * 32;
+      }
+      auto fetch = [&](int k, float4 (&x)[EC], float4 (&y)[(INIT && !WY) || FUSED ? EC : 1], int2 (&r)[EC], float (&bb)[EC]) {
 #pragma unroll
         for (int i = 0; i < EC; ++i) {
           const int g = k * EC + i, row = row_first + g * w8;
           x[i] = f4(0.f);
           r[i] = make_int2(0, 0);
           bb[i] = 0.f;
-          if constexpr (INIT && !WY) y[i] = f4(0.f);
+          if constexpr ((INIT && !WY) || FUSED) y[i] = f4(0.f);
           if (g < GM && g < ng && row < rhi && cok) {
             x[i] = ld4_at(xbase, (uint32_t)row * 128u + lr16);
             r[i] = ld2_at(a.rest, (uint32_t)row * 8u);  // edges beyond SL per block: {first, count}, ascending columns
@@ -630,6 +650,7 @@ __global__ __launch_bounds__((CW + 1) * 64) __attribute__((amdgpu_waves_per_eu(W
             if constexpr (INIT && !WY) {  // (byte offsets of a row-major array fit 32 bits: launch_apply_blocked checks N * ld)
               if (ii.Y != nullptr) y[i] = ld4_stream(reinterpret_cast<const float*>(reinterpret_cast<const char*>(ii.Y) + ((uint32_t)row * ldb + cb)));
             }
+            if constexpr (FUSED) y[i] = ld4_stream(reinterpret_cast<const float*>(reinterpret_cast<const char*>(ii.R) + ((uint32_t)row * ldb + cb)));
           }
         }
       };
@@ -664,6 +685,23 @@ __global__ __launch_bounds__((CW + 1) * 64) __attribute__((amdgpu_waves_per_eu(W
             if (ii.Xcopy != nullptr) st4_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(ii.Xcopy) + ((uint32_t)row * ldb + cb)), x);
             st4(reinterpret_cast<float*>(reinterpret_cast<char*>(zbase) + ((uint32_t)row * 128u + lr16)), z);
             dot[0] = mulacc4(r, z, dot[0]);
+          } else if constexpr (FUSED) {
+            const float bq = bv[k & 1][i];
+            const float cs = fmaf(a.cs_B, bq, a.cs_const);
+            const float invMd = 1.f / (fmaf(ii.md_B, bq, ii.md_const) + 1e-12f);
+            const float4 x = xs[k & 1][i];
+            float4 r = ys[k & 1][i], pn;
+            auto one = [&](float xv, float av, float al, float be, float& rv, float& pv) {
+              const float o = fmaf(cs, xv, -__fmul_rn(a.cW, av));  // (the loop form's o, in the form blk_init_row records)
+              rv = fmaf(-o, al, rv);                               // k_update_xr
+              pv = fmaf(xv, be, __fmul_rn(rv, invMd));             // k_update_p
+            };
+            one(x.x, acc[g].x, al4.x, be4.x, r.x, pn.x);
+            one(x.y, acc[g].y, al4.y, be4.y, r.y, pn.y);
+            one(x.z, acc[g].z, al4.z, be4.z, r.z, pn.z);
+            one(x.w, acc[g].w, al4.w, be4.w, r.w, pn.w);
+            st4_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(ii.R) + ((uint32_t)row * ldb + cb)), r);
+            st4(reinterpret_cast<float*>(reinterpret_cast<char*>(zbase) + ((uint32_t)row * 128u + lr16)), pn);
           } else {
             const float cs = fmaf(a.cs_B, bv[k & 1][i], a.cs_const);
             float4 o;
@@ -678,9 +716,11 @@ __global__ __launch_bounds__((CW + 1) * 64) __attribute__((amdgpu_waves_per_eu(W
       }
     }
     __syncthreads();
-    if ((ph + 1) % per_slab == 0) {  // the slab's column sums
-      blk_fold<CW + 1>(dot[0], red, a.part, ld, p.sc0, min(a.c1, p.sc0 + 32), wave, lane);
-      dot[0] = f4(0.f);
+    if constexpr (!FUSED) {
+      if ((ph + 1) % per_slab == 0) {  // the slab's column sums
+        blk_fold<CW + 1>(dot[0], red, a.part, ld, p.sc0, min(a.c1, p.sc0 + 32), wave, lane);
+        dot[0] = f4(0.f);
+      }
     }
   }
 }
@@ -1112,13 +1152,96 @@ __global__ __launch_bounds__(256) void k_anchor_gram_fold(const GramArgs a) {
   }
 }
 
+// The third step's sums (anchor_gram.hpp: kGram3PerColumn, kGram3Lattice), same scheme: workgroup (slab, chunk), a thread one
+// column of every eighth row, float64, the eight row lanes folded through LDS in lane order, the lattice's four sums in the
+// slab-0 workgroups.
+__global__ __launch_bounds__(256) void k_anchor_gram3_part(const Gram3Args b) {
+  constexpr int NQ = gram::kGram3PerColumn, NL = gram::kGram3Lattice;
+  const GramArgs& a = b.g;
+  __shared__ double red[8][32];
+  const int cl = threadIdx.x & 31, half = threadIdx.x >> 5;
+  const int sc0 = a.c0 + (int)blockIdx.x * 32, col = sc0 + cl, chunk = (int)blockIdx.y;
+  const bool cok = col < a.c1;
+  const bool lat = blockIdx.x == 0 && cl == 0;
+  const int r0 = (int)((int64_t)a.N * chunk / OSC_GRAM_CHUNKS), r1 = (int)((int64_t)a.N * (chunk + 1) / OSC_GRAM_CHUNKS);
+  const size_t slab = (size_t)(sc0 >> 5) * (size_t)a.N * 32;
+  double acc[NQ], la[NL];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) acc[q] = 0.0;
+#pragma unroll
+  for (int q = 0; q < NL; ++q) la[q] = 0.0;
+  for (int row = r0 + half; row < r1; row += 8) {
+    const double s[4] = {1.0, (double)a.wsum[row], (double)a.wsum2[row], (double)b.wsum3[row]};
+    if (cok) {
+      const double y[5] = {(double)a.Ys[slab + (size_t)row * 32 + cl], (double)a.WYs[slab + (size_t)row * 32 + cl],
+                           (double)a.WW[(size_t)row * a.ld + col], (double)a.W3[(size_t)row * a.ld + col],
+                           (double)b.W4[(size_t)row * a.ld + col]};
+#pragma unroll
+      for (int j = 0; j < 5; ++j) acc[gram::y4_index(j)] += y[j] * y[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc[gram::a4_index(q)] += s[q] * y[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[gram::s3y_index(j)] += s[3] * y[j];
+    }
+    if (lat) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) la[gram::lat3_index(q)] += s[q] * s[3];
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    __syncthreads();
+    red[half][cl] = acc[q];
+    __syncthreads();
+    if (half == 0 && cok) {
+      double t = 0.0;
+#pragma unroll
+      for (int h = 0; h < 8; ++h) t += red[h][cl];
+      a.part[((size_t)chunk * NQ + q) * a.ld + col] = t;
+    }
+  }
+  if (blockIdx.x == 0) {
+#pragma unroll
+    for (int q = 0; q < NL; ++q) {
+      __syncthreads();
+      if (cl == 0) red[half][0] = la[q];
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        double t = 0.0;
+#pragma unroll
+        for (int h = 0; h < 8; ++h) t += red[h][0];
+        a.part[(size_t)OSC_GRAM_CHUNKS * NQ * a.ld + (size_t)chunk * NL + q] = t;
+      }
+    }
+  }
+}
+__global__ __launch_bounds__(256) void k_anchor_gram3_fold(const GramArgs a) {
+  constexpr int NQ = gram::kGram3PerColumn, NL = gram::kGram3Lattice;
+  const int idx = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (idx < NQ * a.ld) {
+    const int q = idx / a.ld, col = idx % a.ld;
+    double t = 0.0;
+    if (col >= a.c0 && col < a.c1)
+      for (int ch = 0; ch < OSC_GRAM_CHUNKS; ++ch) t += a.part[((size_t)ch * NQ + q) * a.ld + col];
+    a.out[idx] = t;
+  } else if (idx < NQ * a.ld + NL) {
+    const int q = idx - NQ * a.ld;
+    double t = 0.0;
+    for (int ch = 0; ch < OSC_GRAM_CHUNKS; ++ch) t += a.part[(size_t)OSC_GRAM_CHUNKS * NQ * a.ld + (size_t)ch * NL + q];
+    a.out[idx] = t;
+  }
+}
+
 // One workgroup, a thread per column (anchor_gram.hpp: two_steps): the scalars of iterations 1 and 2, their residuals as
 // k_reduce_beta publishes them (nanmax over the columns, device slot and host-mapped word), and the fused pass's gate word.
 // A solve with an unusable column publishes 0 for both residuals: the host loop stops in iteration 1, nothing was written,
 // and run_cg solves again on the summed route.
+// With the third step planned (GramScalarArgs::gram3; three_steps on the nine vectors' matrix) also alpha3, beta3, r3 . z3 in
+// rz's place, the third residual and go[1], the gate word of iteration 3's fused matvec; usable3 takes usable's place.
 __global__ __launch_bounds__(256) void k_anchor_gram_scalars(const GramScalarArgs a) {
-  __shared__ float sh1[4], sh2[4];
+  __shared__ float sh1[4], sh2[4], sh3[4];
   __shared__ int shu[4];
+  const bool three = a.gram3 != nullptr;  // (three_steps: the same iterations 1 and 2 to the bit, and iteration 3's scalars)
   const float b = a.B[0];
   gram::Op o;
   const float cs = fmaf(a.cs_B, b, a.cs_const);  // (blk_init_row's and init_cached_body's scalars)
@@ -1128,17 +1251,31 @@ __global__ __launch_bounds__(256) void k_anchor_gram_scalars(const GramScalarArg
   o.m = (double)(1.f / (fmaf(a.md_B, b, a.md_const) + 1e-12f));
   o.u = (double)__fsub_rn(__fadd_rn(a.rbU, a.rbY), cs);
   const double* lat = a.gram + (size_t)gram::kGramPerColumn * a.ld;
-  float res1 = 0.f, res2 = 0.f;
+  float res1 = 0.f, res2 = 0.f, res3 = 0.f;
   int usable = 1;
   for (int col = a.c0 + (int)threadIdx.x; col < a.c1; col += 256) {
-    double G[gram::kBasis][gram::kBasis];
-    gram::fill(G, a.gram + col, (size_t)a.ld, lat, (double)a.psi[col]);
-    const gram::Scalars s = gram::two_steps(G, o);
+    gram::Scalars s;
+    if (three) {
+      const double* lat3 = a.gram3 + (size_t)gram::kGram3PerColumn * a.ld;
+      double G[gram::kBasis3][gram::kBasis3];
+      gram::fill3(G, a.gram + col, (size_t)a.ld, lat, a.gram3 + col, (size_t)a.ld, lat3, (double)a.psi[col]);
+      const gram::Scalars3 t = gram::three_steps(G, o);
+      s = t.two;
+      s.usable = t.usable3;
+      a.alpha3[col] = t.alpha3;
+      a.beta3[col] = t.beta3;
+      a.rz[col] = t.rz3;
+      res3 = nanmax(res3, t.res3);
+    } else {
+      double G[gram::kBasis][gram::kBasis];
+      gram::fill(G, a.gram + col, (size_t)a.ld, lat, (double)a.psi[col]);
+      s = gram::two_steps(G, o);
+      a.rz[col] = s.rz2;
+    }
     a.alpha1[col] = s.alpha1;
     a.alpha2[col] = s.alpha2;
     a.beta1[col] = s.beta1;
     a.beta2[col] = s.beta2;
-    a.rz[col] = s.rz2;
     res1 = nanmax(res1, s.res1);
     res2 = nanmax(res2, s.res2);
     usable &= s.usable ? 1 : 0;
@@ -1147,18 +1284,28 @@ __global__ __launch_bounds__(256) void k_anchor_gram_scalars(const GramScalarArg
   for (int off = 32; off > 0; off >>= 1) {
     res1 = nanmax(res1, __shfl_xor(res1, off, 64));
     res2 = nanmax(res2, __shfl_xor(res2, off, 64));
+    res3 = nanmax(res3, __shfl_xor(res3, off, 64));
     usable &= __shfl_xor(usable, off, 64);
   }
-  if ((threadIdx.x & 63) == 0) sh1[threadIdx.x >> 6] = res1, sh2[threadIdx.x >> 6] = res2, shu[threadIdx.x >> 6] = usable;
+  if ((threadIdx.x & 63) == 0)
+    sh1[threadIdx.x >> 6] = res1, sh2[threadIdx.x >> 6] = res2, sh3[threadIdx.x >> 6] = res3, shu[threadIdx.x >> 6] = usable;
   __syncthreads();
   if (threadIdx.x == 0) {
-    for (int w = 1; w < 4; ++w) res1 = nanmax(res1, sh1[w]), res2 = nanmax(res2, sh2[w]), usable &= shu[w];
-    if (!usable) res1 = res2 = 0.f;
+    for (int w = 1; w < 4; ++w) res1 = nanmax(res1, sh1[w]), res2 = nanmax(res2, sh2[w]), res3 = nanmax(res3, sh3[w]), usable &= shu[w];
+    if (!usable) res1 = res2 = res3 = 0.f;
     a.res_slots[1] = __float_as_uint(res1);
     a.res_slots[2] = __float_as_uint(res2);
-    *a.go = (usable && res1 > a.tol && res2 > a.tol) ? 1u : 0u;
+    a.go[0] = (usable && res1 > a.tol && res2 > a.tol) ? 1u : 0u;
+    if (three) {
+      a.res_slots[3] = __float_as_uint(res3);
+      a.go[1] = (usable && res1 > a.tol && res2 > a.tol && res3 > a.tol) ? 1u : 0u;
+    }
     __threadfence();
-    // word 2 first: the host polls word 1, and once it has that it may give the solve up and reuse the words (run_cg)
+    // words 3 and 2 first: the host polls word 1, and once it has that it may give the solve up and reuse the words (run_cg)
+    if (three) {
+      reinterpret_cast<volatile uint32_t*>(a.host_words)[3] = __float_as_uint(res3);
+      __threadfence_system();
+    }
     reinterpret_cast<volatile uint32_t*>(a.host_words)[2] = __float_as_uint(res2);
     __threadfence_system();
     reinterpret_cast<volatile uint32_t*>(a.host_words)[1] = __float_as_uint(res1);
@@ -1961,7 +2108,20 @@ void launch_anchor_gram(const GramArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(k_anchor_gram_fold, dim3((n + 255) / 256), dim3(256), 0, s, a);
   HIP_CHECK(hipGetLastError());
 }
+void launch_anchor_gram3(const Gram3Args& b, hipStream_t s) {
+  const GramArgs& a = b.g;
+  if (!a.Ys || !a.WYs || !a.WW || !a.W3 || !b.W4 || !a.wsum || !a.wsum2 || !b.wsum3 || !a.part || !a.out || a.N < 1 || (a.c0 & 31) != 0 ||
+      a.c1 <= a.c0 || a.c1 > a.ld)
+    throw std::runtime_error("anchor Gram sums, third step: bad arguments");
+  hipLaunchKernelGGL(k_anchor_gram3_part, dim3((a.c1 - a.c0 + 31) / 32, OSC_GRAM_CHUNKS), dim3(256), 0, s, b);
+  HIP_CHECK(hipGetLastError());
+  const int n = gram::kGram3PerColumn * a.ld + gram::kGram3Lattice;
+  hipLaunchKernelGGL(k_anchor_gram3_fold, dim3((n + 255) / 256), dim3(256), 0, s, a);
+  HIP_CHECK(hipGetLastError());
+}
 void launch_anchor_gram_scalars(const GramScalarArgs& a, hipStream_t s) {
+  if (a.gram3 != nullptr && (!a.alpha3 || !a.beta3 || a.beta3 == a.beta2 || a.alpha3 == a.alpha1 || a.alpha3 == a.alpha2))
+    throw std::runtime_error("anchor Gram scalars: bad arguments of the third step");
   hipLaunchKernelGGL(k_anchor_gram_scalars, dim3(1), dim3(256), 0, s, a);
   HIP_CHECK(hipGetLastError());
 }
@@ -1994,6 +2154,17 @@ void launch_apply_blocked(const BlkArgs& a, int grid, hipStream_t s, const BlkIn
     OSC_BLK_SHAPE_SWITCH(variant, CALL);
 #undef CALL
   }
+  HIP_CHECK(hipGetLastError());
+}
+
+// iteration 3 of an anchor start in one launch (BlkFused)
+void launch_apply_blocked_fused(const BlkArgs& a, int grid, hipStream_t s, const BlkFused& f, int variant) {
+  blocked_args_check(a, grid, variant);
+  if (!f.R || !f.Pout || !f.alpha || !f.beta || !f.go || f.Pout == a.X || f.R == a.X || f.R == f.Pout || (a.c1 & 3) != 0 || a.c1 > a.ld)
+    throw std::runtime_error("blocked apply: bad arguments of the fused form");
+#define CALL(G, W, P, E) hipLaunchKernelGGL((k_apply_blocked<G, W, false, P, E, false, true>), dim3(grid), dim3((W + 1) * 64), 0, s, a, f)
+  OSC_BLK_SHAPE_SWITCH(variant, CALL);
+#undef CALL
   HIP_CHECK(hipGetLastError());
 }
 

@@ -168,6 +168,15 @@ struct GramArgs {
   int32_t N, ld, c0, c1;
 };
 void launch_anchor_gram(const GramArgs& a, hipStream_t s);
+// ... and of the two vectors the third step adds (anchor_gram.hpp: kGram3PerColumn, kGram3Lattice): the same two kernels' scheme
+// (k_anchor_gram3_part, k_anchor_gram3_fold) with W W W W Y (row-major, scratch: read here and never again) and s3 = W s2 beside
+// the six arrays above
+struct Gram3Args {
+  GramArgs g;          // part: [OSC_GRAM_CHUNKS][13][ld], then [OSC_GRAM_CHUNKS][4]; out: [13][ld], then [4]
+  const float* W4;     // W W W W Y, row-major
+  const float* wsum3;  // [N] s3 = W s2
+};
+void launch_anchor_gram3(const Gram3Args& a, hipStream_t s);
 
 // k_anchor_gram_scalars: iterations 1 and 2's alpha, beta, residuals and r2 . z2 per column from the Gram sums, the two
 // residuals (max over the columns) into the solve's residual slots and host-mapped words, and the word that lets
@@ -186,7 +195,13 @@ struct GramScalarArgs {
   double* rz;
   uint32_t* res_slots;   // the solve's residual slots: [1] and [2] are written
   uint32_t* host_words;  // the same two, host-mapped
-  uint32_t* go;
+  uint32_t* go;          // two words: [0] lets k_init_two_steps run, [1] (third step only) iteration 3's fused matvec
+  // The third step (anchor_gram.hpp: three_steps), planned iff gram3 != nullptr: alpha3, beta3 and r3 . z3 per column (rz then
+  // holds r3 . z3, not r2 . z2), |r3| into residual slot and host word 3, and go[1], the word that lets the FUSED matvec of
+  // iteration 3 run: 1 only if every column is usable and all three residuals are above tol.
+  const double* gram3;
+  float* alpha3;
+  float* beta3;
 };
 void launch_anchor_gram_scalars(const GramScalarArgs& a, hipStream_t s);
 
@@ -202,6 +217,18 @@ struct BlkTwoSteps {
   const float* beta2;
   const uint32_t* go;
   int32_t row0;  // first row (streaming form; the blocked form's geometry covers every row: 0 there)
+};
+
+// k_apply_blocked as iteration 3 of an anchor start whose alpha3 and beta3 are known beforehand (GramScalarArgs::gram3): the
+// epilogue forms r3 = r2 - alpha3 A p3 (k_update_xr's expression) in place in R and p4 = z3 + beta3 p3 (k_update_p's) slab-major
+// into Pout; BlkArgs::OUT and BlkArgs::part are not written.  A no-op unless *go == 1.
+struct BlkFused {
+  float* R;            // r2 in, r3 out, row-major
+  float* Pout;         // p4 out, slab-major like BlkArgs::X (must not be that array)
+  const float* alpha;  // [ld] alpha3
+  const float* beta;   // [ld] beta3
+  const uint32_t* go;
+  float md_B, md_const;  // no preconditioner: 0, 1
 };
 
 enum SpmmMode { SPMM_AP = 0, SPMM_INIT = 1, SPMM_DOT = 2 };
@@ -361,6 +388,7 @@ void launch_chain_fix(const ChainFixArgs& a, hipStream_t s);
 // store_wy: the INIT pass (init != nullptr) also writes its row sums to init->WY
 void launch_apply_blocked(const BlkArgs& a, int grid, hipStream_t s, const BlkInit* init = nullptr, int variant = 0,
                           bool store_wy = false);
+void launch_apply_blocked_fused(const BlkArgs& a, int grid, hipStream_t s, const BlkFused& f, int variant);
 // the same INIT pass with the row sums read from init.WY instead of gathered (k_init_cached): same results to the bit
 // ap: the form that also streams iteration 1's A p1 and its p . Ap sums (BlkInitAp)
 // ap2 (with ap): ... and T = A (A p1) (BlkInitAp2)

@@ -18,6 +18,8 @@
 //                                       a model of the launches, by tests/host_logic/sweep_anchor_ap2.cpp)
 //   anchor_gram_route                 : ... and both iterations inside the INIT pass, their scalars from cached Gram sums (swept
 //                                       by tests/host_logic/sweep_anchor_gram.cpp)
+//   anchor_gram3_route                : ... and iteration 3 in one launch, its scalars from two more vectors' sums (swept by
+//                                       tests/host_logic/sweep_anchor_gram3.cpp)
 //   cg_host_loop                      : the host loop of a CG solve -- which iteration is enqueued when (run_cg in
 //                                       osc_solve.hip and both sweeps run this one function)
 #pragma once
@@ -614,6 +616,23 @@ struct AnchorGramInputs {
 };
 inline bool anchor_gram_route(const AnchorGramInputs& in) {
   if (in.mode == 0 || !in.depth2 || in.comm || in.ring_slots < 2 || in.max_iters < 3 || in.predicted < 3) return false;
+  return in.mode > 0 || in.N >= kAnchorApAutoRows;
+}
+// One iteration further: with the sums of the two vectors A p3 adds (anchor_gram.hpp: three_steps) alpha3, beta3 and |r3| are
+// known before the solve's first launch as well, and iteration 3 is ONE launch: its gathering matvec, whose epilogue forms r3 and
+// p4 beside A p3 instead of storing it (cg_kernels.hip: k_apply_blocked's FUSED form).  No alpha reduction, no x-r kernel, no
+// beta reduction, and iteration 4 launches no p update.  Only on top of the Gram route of this very solve.
+struct AnchorGram3Inputs {
+  int mode = -1;           // OSC_ANCHOR_GRAM3: 0 off, 1 wherever the Gram route runs, < 0 by the lattice's rows
+  int64_t N = 0;
+  bool gram_route = false;  // anchor_gram_route holds for this solve and its sums are held
+  bool comm = false;
+  int ring_slots = 1;
+  int max_iters = 0;
+  int predicted = 0;
+};
+inline bool anchor_gram3_route(const AnchorGram3Inputs& in) {
+  if (in.mode == 0 || !in.gram_route || in.comm || in.ring_slots < 2 || in.max_iters < 3 || in.predicted < 3) return false;
   return in.mode > 0 || in.N >= kAnchorApAutoRows;
 }
 // Where iteration `it` of a solve gets its A p (CgSolve::enqueue): from the INIT pass (first: it left A p1 and the p . Ap

@@ -123,7 +123,17 @@ struct osc_lattice {
   bool two_steps_stream = true;
   int64_t fused_two_step_solves = 0, anchor_gram_builds = 0, anchor_gram_redos = 0;
   bool anchor_gram_last = false;
-  int64_t yu_copies = 0;     // whole-array Y -> U copies made for this handle (osc_counters::y_to_u_copies)
+  // One iteration further (host_logic.hpp: anchor_gram3_route): the sums of the two vectors A p3 adds to the seven -- psi s3, s3 =
+  // W.(W.(W.1)), and W.(W3s), formed once into the solve's AP scratch array, summed against and dropped (anchor_gram.hpp; (13 ld +
+  // 4) doubles and the N floats of s3 are held).  With them k_anchor_gram_scalars also has alpha3, beta3 and |r3|, and iteration 3
+  // is one launch (k_apply_blocked's FUSED form).  Built by the first solve that takes the route, valid exactly as long as gram
+  // (Derived::gram3_nb).  OSC_ANCHOR_GRAM3: 0 never, 1 wherever the Gram route runs, unset: by the lattice's rows.
+  DevBuf<double> gram3;
+  DevBuf<float> Wsum3;
+  int anchor_gram3 = -1;
+  int64_t fused_three_step_solves = 0, anchor_gram3_builds = 0;
+  bool anchor_gram3_last = false;
+  int64_t yu_copies = 0;    // whole-array Y -> U copies made for this handle (osc_counters::y_to_u_copies)
   int64_t slab_launches = 0;  // k_rows_to_slab launches (osc_counters::rows_to_slab_launches)
   // Which of the arrays computed from other state (ell_col_t / ell_w_t, blk_*, Ys, WYs, Ustar; by epoch: halo, query) are
   // current.  Dropped by host::changed(derived, <what changed>) alone (derived_state.hpp has the dependency table).

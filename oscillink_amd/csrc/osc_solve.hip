@@ -365,6 +365,11 @@ struct CgSolve {
   // enqueue(3) launches no p update, and the ring starts with two directions applied.
   const bool allow_gram;  // (false: the solve run again after a fused pass that was gated off)
   bool gram_route = false;
+  // ... and iteration 3's scalars are known as well (anchor_gram3_route): alpha_of(3) holds alpha3, h.beta beta3, h.rz r3 . z3,
+  // residual slot 3 is published.  enqueue(3) launches the matvec's fused form alone -- r3 over r2, p4 into dir(4), under its own
+  // gate word --, enqueue(4) launches no p update.
+  bool gram3_route = false;
+  float fused_md_B = 0.f, fused_md_const = 1.f;  // (BlkInit's, for the fused launch)
   bool ring_planned = false;
 
   // ---- where x is updated ---------------------------------------------------------------------------------------------
@@ -460,6 +465,7 @@ struct CgSolve {
   int init() {
     int part_rows = grid;
     h.anchor_gram_last = false;
+    h.anchor_gram3_last = false;
     // (the rhs rows the fused pass can take besides x0 itself: one -- the state term must be x0 or absent, and if y is a
     // third array the solution array must be x0)
     const bool fuse_u = b.rhsU == b.x0 || op.rbU == 0.f;
@@ -564,7 +570,7 @@ struct CgSolve {
       }
       h.cached_inits += 1;
     } else if (wy_route) {
-      h.derived.wy_nb = h.derived.wwy_nb = h.derived.w3_nb = h.derived.gram_nb = 0;  // (not current while this launch rewrites them)
+      h.derived.wy_nb = h.derived.wwy_nb = h.derived.w3_nb = h.derived.gram_nb = h.derived.gram3_nb = 0;  // (not current while this launch rewrites them)
       h.anchor_ap_denied = h.anchor_ap2_denied = false;
       h.WYs.alloc((size_t)h.N * h.ld);
       bi.WY = h.WYs.p;
@@ -607,6 +613,15 @@ struct CgSolve {
     gi.max_iters = max_iters;
     gi.predicted = stop_guess;
     if (!host::anchor_gram_route(gi) || !ensure_anchor_gram()) return false;
+    host::AnchorGram3Inputs g3;
+    g3.mode = h.anchor_gram3;
+    g3.N = h.N;
+    g3.gram_route = true;
+    g3.comm = gi.comm;
+    g3.ring_slots = ring.K;
+    g3.max_iters = max_iters;
+    g3.predicted = stop_guess;
+    const bool three = host::anchor_gram3_route(g3) && ensure_anchor_gram3();
     GramScalarArgs ga{};
     ga.gram = h.gram.p;
     ga.psi = b.psi;
@@ -630,8 +645,17 @@ struct CgSolve {
     ga.rz = h.rz.p;
     ga.res_slots = res_slots;
     ga.host_words = reinterpret_cast<uint32_t*>(h.res_host_dev);
-    if (h.gram_go.n < 1) h.gram_go.alloc(1);
+    if (h.gram_go.n < 2) h.gram_go.alloc(2);
     ga.go = h.gram_go.p;
+    if (three) {
+      // beta3 takes h.beta, where iteration 4 would look for it, and with two ring slots alpha3 takes alpha1's: the INIT pass,
+      // their only reader, finds beta2 and alpha1 in further free rows of the r . z partials
+      ga.gram3 = h.gram3.p;
+      ga.alpha3 = alpha_of(3);
+      ga.beta3 = h.beta.p;
+      ga.beta2 = h.part1.p + (size_t)b.ld;
+      if (ga.alpha1 == ga.alpha3) ga.alpha1 = h.part1.p + 2 * (size_t)b.ld;
+    }
     launch_anchor_gram_scalars(ga, h.stream);
     BlkInit ti = bi;
     ti.Z = dir(3);
@@ -639,9 +663,14 @@ struct CgSolve {
     BlkTwoSteps ts{ga.alpha1, ga.alpha2, ga.beta1, ga.beta2, ga.go, 0};
     launch_init_two_steps(ba, grid, h.stream, ti, plan.shape, ap, ap2, ts, h.two_steps_stream);
     gram_route = true;
+    gram3_route = three;
+    fused_md_B = bi.md_B;
+    fused_md_const = bi.md_const;
     ring.applied = 2;  // directions 1 and 2 are in x2
     h.fused_two_step_solves += 1;
     h.anchor_gram_last = true;
+    if (three) h.fused_three_step_solves += 1;
+    h.anchor_gram3_last = three;
     h.cached_inits += 1;
     return true;
   }
@@ -650,7 +679,7 @@ struct CgSolve {
   // arrays ensure_anchor_ap2 has just made current.  135 KB at 768 columns: no memory rule.
   bool ensure_anchor_gram() {
     if (h.derived.gram_nb == ba.nb && h.derived.w3_nb == ba.nb) return true;
-    h.derived.gram_nb = 0;
+    h.derived.gram_nb = h.derived.gram3_nb = 0;
     const size_t n = (size_t)gram::kGramPerColumn * h.ld + gram::kGramLattice;
     DevBuf<double> part;
     try {
@@ -678,6 +707,57 @@ struct CgSolve {
     sync(h);  // part goes out of scope
     h.derived.gram_nb = ba.nb;
     h.anchor_gram_builds += 1;
+    return true;
+  }
+
+  // The third step's sums (L::gram3; anchor_gram.hpp), formed where they are not held: s3 = W s2 over the ELL rows, W (W3s) as
+  // ensure_anchor_ap2 forms W3s -- over a slab-major image in T, by the loop-form matvec with cs = 0, cW = -1 -- into the solve's
+  // AP scratch array, where nothing lives before the INIT pass, then one streaming pass.  Only the sums and s3 are kept.
+  bool ensure_anchor_gram3() {
+    if (h.derived.gram3_nb == ba.nb && h.derived.gram_nb == ba.nb) return true;
+    h.derived.gram3_nb = 0;
+    if (b.ld != h.ld || h.part1.n < 3 * (size_t)b.ld) return false;
+    const size_t n = (size_t)gram::kGram3PerColumn * h.ld + gram::kGram3Lattice;
+    DevBuf<double> part;
+    try {
+      if (h.gram3.n != n) h.gram3.alloc(n);
+      if (h.Wsum3.n != (size_t)h.N) h.Wsum3.alloc((size_t)h.N);
+      part.alloc(n * OSC_GRAM_CHUNKS);
+    } catch (const HipError&) {
+      (void)hipGetLastError();
+      h.gram3.release();
+      h.Wsum3.release();
+      return false;
+    }
+    launch_row_weighted_sums(h.ell_col.p, h.ell_w.p, h.deg.p, h.width, (int32_t)h.N, h.Wsum2.p, h.Wsum3.p, h.stream);
+    rows_to_slab(h, h.W3s.p, h.Tap.p, h.ld, b.c0, b.c1, grid);
+    BlkArgs wa = ba;
+    wa.X = h.Tap.p;
+    wa.OUT = b.AP;
+    wa.cs_const = wa.cs_B = 0.f;
+    wa.cW = -1.f;
+    wa.gate = nullptr;
+    wa.gate_tol = 0.f;
+    launch_apply_blocked(wa, grid, h.stream, nullptr, plan.shape);
+    Gram3Args g{};
+    g.g.Ys = h.Ys.p;
+    g.g.WYs = h.WYs.p;
+    g.g.WW = h.WWs.p;
+    g.g.W3 = h.W3s.p;
+    g.g.wsum = h.Wsum.p;
+    g.g.wsum2 = h.Wsum2.p;
+    g.g.part = part.p;
+    g.g.out = h.gram3.p;
+    g.g.N = (int32_t)h.N;
+    g.g.ld = h.ld;
+    g.g.c0 = h.c0;
+    g.g.c1 = h.c1;
+    g.W4 = b.AP;
+    g.wsum3 = h.Wsum3.p;
+    launch_anchor_gram3(g, h.stream);
+    sync(h);  // part goes out of scope
+    h.derived.gram3_nb = ba.nb;
+    h.anchor_gram3_builds += 1;
     return true;
   }
 
@@ -731,7 +811,7 @@ struct CgSolve {
   bool ensure_anchor_ap2() {
     if (h.derived.w3_nb == ba.nb && h.derived.wwy_nb == ba.nb) return true;
     if (h.anchor_ap2_denied) return false;
-    h.derived.w3_nb = h.derived.gram_nb = 0;
+    h.derived.w3_nb = h.derived.gram_nb = h.derived.gram3_nb = 0;
     const size_t n = (size_t)h.N * h.ld;
     if (h.W3s.n != n || h.Tap.n != n || h.Wsum2.n != (size_t)h.N) {
       size_t free_b = 0, total_b = 0;
@@ -865,8 +945,22 @@ struct CgSolve {
     const Gate g{it > 1 && !overlap ? reinterpret_cast<const float*>(res_slots) + (it - 1) : nullptr, tol};
     host::CgXSchedule::IterForm form{false, host::CgXSchedule::XR_SKIPS_X};
     if (!ringed()) form = xs.enqueue(it, speculative);
+    if (gram3_route && it == 3) {
+      // The whole iteration in the matvec's fused form: r3 over r2, p4 into dir(4); alpha3, beta3, r3 . z3 and the residual are
+      // out already.  (A sample of iteration 4: a solve that stops in 3 had the launch gated off.)
+      ProfScope ps(h, 4, 4);
+      BlkArgs fa = ba;
+      fa.X = dir(3);
+      fa.OUT = nullptr;
+      fa.gate = nullptr;
+      fa.gate_tol = 0.f;
+      const BlkFused f{b.R, dir(4), alpha_of(3), h.beta.p, h.gram_go.p + 1, fused_md_B, fused_md_const};
+      launch_apply_blocked_fused(fa, grid, h.stream, f, plan.shape);
+      h.blk_applies += 1;
+      return;
+    }
     const host::ApSource ap_src = host::cg_ap_source(it, first_ap_done, second_ap_ready);
-    if (it > 1 && !(gram_route && it == 3)) {  // (the fused INIT pass left p3 in dir(3))
+    if (it > 1 && !(gram_route && it == 3) && !(gram3_route && it == 4)) {  // (the fused INIT pass left p3 in dir(3), the fused matvec p4 in dir(4))
       ProfScope ps(h, 2, it);
       if (ringed()) {
         // the slot p_it goes to still holds a direction x lacks: this iteration's flush, then p_it = z + beta p_{it-1}
@@ -1020,6 +1114,7 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
       // scratch scalars was written.  The same solve again, on the depth-2 route; its count keeps the next one off the route.
       h.anchor_gram_redos += 1;
       h.fused_two_step_solves -= 1;
+      if (s.gram3_route) h.fused_three_step_solves -= 1;
       h.cached_inits -= 1;  // (the solve counts once, where it ends)
       continue;
     }

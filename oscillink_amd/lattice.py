@@ -272,6 +272,8 @@ class OscillinkLattice:
         self._call("osc_anchor_ap2_info", C.byref(a2f), C.byref(a2b), C.byref(a2l), C.byref(a2n))
         gf, gb, gl, gn, gr = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int64(0), C.c_int64(0)
         self._call("osc_anchor_gram_info", C.byref(gf), C.byref(gb), C.byref(gl), C.byref(gn), C.byref(gr))
+        g3f, g3b, g3l, g3n = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int64(0)
+        self._call("osc_anchor_gram3_info", C.byref(g3f), C.byref(g3b), C.byref(g3l), C.byref(g3n))
         counters = nat.Counters()
         self._call("osc_counters_get", C.byref(counters))
         return {"order_kind": ("none", "bfs", "balanced")[int(ok.value)], "displaced_edges_before": int(db.value),
@@ -291,6 +293,8 @@ class OscillinkLattice:
                 "fused_two_step_solves": int(gf.value), "anchor_gram_bytes": int(gb.value),
                 "anchor_gram_last_solve": int(gl.value), "anchor_gram_builds": int(gn.value),
                 "anchor_gram_redos": int(gr.value),
+                "fused_three_step_solves": int(g3f.value), "anchor_gram3_bytes": int(g3b.value),
+                "anchor_gram3_last_solve": int(g3l.value), "anchor_gram3_builds": int(g3n.value),
                 # chain_receipt_many(lamP=...) keeps the basis of M + lamP I beside the query basis: N x ld + N x 4 floats
                 # (ld >= D rounded up to 4); 0 until the first such call
                 "shifted_basis_bytes": 4 * self.N * (((self.D + 3) // 4) * 4 + 4) if self._qbs_key is not None else 0,
@@ -303,6 +307,14 @@ class OscillinkLattice:
         self._call("osc_anchor_gram_info", None, C.byref(gb), None, None, None)
         out = np.zeros(max(int(gb.value) // 8, 1), dtype=np.float64)
         self._call("osc_anchor_gram_read", out.ctypes.data_as(C.POINTER(C.c_double)), out.size)
+        return out
+
+    def anchor_gram3(self) -> np.ndarray:
+        """The float64 sums of the two vectors the third step adds, as held on the device: (13 ld + 4,) in the layout of
+        include/oscillink_hip.h: osc_anchor_gram3_read (test aid; raises while none are held)."""
+        ld = self.anchor_gram().size - 6
+        out = np.zeros(13 * (ld // 22) + 4, dtype=np.float64)
+        self._call("osc_anchor_gram3_read", out.ctypes.data_as(C.POINTER(C.c_double)), out.size)
         return out
 
     def halo_info(self) -> dict[str, int]:
