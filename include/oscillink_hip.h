@@ -436,6 +436,18 @@ int osc_chain_prior_many(osc_handle h, const float* psis, int32_t Q, const int64
                          const float* chain_weights, float lamP, float tol, int32_t max_iters, float z_th, float* z_struct,
                          float* z_path, float* r_struct, float* r_path, double* gain, int32_t* verdict, int32_t* weakest_k,
                          float* weakest_z, float* prior_res, int32_t* prior_iters);
+/* Not in the reference as one call: bundle(k, alpha) (lattice.py:530-568) for Q (query, chain) pairs, query q on the stationary
+ * state of M + lamP L_path,q -- what add_chain(chain_q, lamP, weights_q) (lattice.py:129-150), set_query(psi_q) and bundle give
+ * on a lattice without a chain of its own.  psis, chain_offsets, chain_nodes, chain_weights, lamP, tol,
+ * max_iters, prior_res and prior_iters are osc_chain_prior_many's, the shifted basis osc_query_basis_shifted's; k, alpha,
+ * lambda_div, ids, score and align are osc_bundle_many's (Q x min(k, N) each).  U*_q is never formed: its alignment and
+ * coherence terms are expanded over the shifted basis, the Green's columns of the chain's nodes and T_q V_q.  lamP == 0 is
+ * osc_bundle_many on osc_query_basis's basis.  A query's outputs are the same to the bit whatever else the batch holds.
+ * OSC_E_STATE without the basis (shifted for lamP > 0), OSC_E_UNSUPPORTED with a communicator, OSC_E_INVALID for a lattice with
+ * a chain of its own, a non-finite query and osc_chain_prior_many's reasons. */
+int osc_bundle_prior_many(osc_handle h, const float* psis, int32_t Q, const int64_t* chain_offsets, const int32_t* chain_nodes,
+                          const float* chain_weights, float lamP, float tol, int32_t max_iters, int32_t k, float alpha,
+                          float lambda_div, int32_t* ids, float* score, float* align, float* prior_res, int32_t* prior_iters);
 /* mmr_diversify (graph.py:114-133) for Q score columns at once: scores N x Q (API row order, queries contiguous per row);
  * out_idx Q x min(k, N) API ids, the same picks as osc_mmr per column up to rounding of the similarities. */
 int osc_mmr_many(osc_handle h, const float* scores, int32_t Q, int32_t k, float lambda_div, int32_t* out_idx);

@@ -1310,6 +1310,21 @@ int osc_chain_prior_many(osc_handle h, const float* psis, int32_t Q, const int64
   });
 }
 
+int osc_bundle_prior_many(osc_handle h, const float* psis, int32_t Q, const int64_t* chain_offsets, const int32_t* chain_nodes,
+                          const float* chain_weights, float lamP, float tol, int32_t max_iters, int32_t k, float alpha,
+                          float lambda_div, int32_t* ids, float* score, float* align, float* prior_res, int32_t* prior_iters) {
+  return guarded(h, [&](L& l) {
+    if (Q < 0) throw Invalid("osc_bundle_prior_many: Q must be >= 0");
+    if (Q > 0 && (!psis || !chain_offsets || !chain_nodes || !prior_res || !prior_iters))
+      throw Invalid("osc_bundle_prior_many: NULL buffer");
+    if (Q > 0 && k > 0 && (!ids || !score || !align)) throw Invalid("osc_bundle_prior_many: NULL buffer");
+    for (int64_t i = 0; i < (int64_t)Q * l.D; ++i)
+      if (!std::isfinite(psis[i])) throw Invalid("osc_bundle_prior_many: non-finite query");
+    query_bundle_prior_many(l, psis, Q, chain_offsets, chain_nodes, chain_weights, lamP, tol, max_iters, k, alpha, lambda_div,
+                            ids, score, align, prior_res, prior_iters);
+  });
+}
+
 int osc_mmr_many(osc_handle h, const float* scores, int32_t Q, int32_t k, float lambda_div, int32_t* out_idx) {
   return guarded(h, [&](L& l) {
     if (Q < 0) throw Invalid("osc_mmr_many: Q must be >= 0");

@@ -38,6 +38,7 @@
 #include "query.hpp"
 #include "gates_many.hpp"
 #include "chain_prior_plan.hpp"
+#include "bundle_prior_plan.hpp"
 
 using namespace osc;
 
@@ -346,6 +347,12 @@ struct osc_lattice {
       float lamP = 0.f, scale = 0.f;
       DevBuf<float> X, x4;
       float res_X = 0.f, res_x = 0.f, max_X = 0.f, max_x = 0.f;
+      // osc_bundle_prior_many: k_query_basis_stats of (X', x'), kept until the next solve (gen).
+      // gen is bumped by every shifted solve or extension; a new epoch or lamP forces a solve first, so it keys the constants
+      // as (epoch, lamP) would -- at the cost that an x-only extension also recomputes c0 and |X'|^2, which did not change.
+      uint64_t gen = 0, stats_gen = 0;
+      DevBuf<float> s;
+      DevBuf<double> xn2, c0, c2;
     } shifted;
     DevBuf<char> cp_scratch;     // one pass's panels and per-column scalars (chain_prior_plan.hpp: ChainPriorLayout)
     DevBuf<float> cp_diag;       // [N] d_i = lamG + lamP + lamC + lamQ B_i
@@ -496,6 +503,11 @@ void query_chain_prior_many(L& l, const float* psis, int32_t Q, const int64_t* c
                             float* weakest_z, float* prior_res, int32_t* prior_iters);
 // sum (A - B) . M (A - B) with the stationary operator (osc_api.hip; receipts.py:21-25)
 double quad_form_of_difference(L& l, const float* A, const float* B);
+// osc_bundle_prior_many
+void query_bundle_prior_many(L& l, const float* psis, int32_t Q, const int64_t* chain_offsets, const int32_t* chain_nodes,
+                             const float* chain_weights, float lamP, float tol, int32_t max_iters, int32_t k, float alpha,
+                             float lambda_div, int32_t* ids, float* score, float* align, float* prior_res,
+                             int32_t* prior_iters);
 void query_bundle_many(L& l, const float* psis, int32_t Q, int32_t k, float alpha, float lambda_div, int32_t* ids,
                        float* score, float* align);
 void query_mmr_many(L& l, const float* scores, int32_t Q, int32_t k, float lambda_div, int32_t* ids);

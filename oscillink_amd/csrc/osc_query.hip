@@ -1,6 +1,6 @@
 // Multi-query bundles and receipts (DESIGN.md sections 11 and 12): the query basis solve and the batched bundle / MMR /
 // receipt drivers behind osc_query_basis, osc_get_query_basis, osc_bundle_many, osc_mmr_many and osc_receipt_many (see
-// osc_internal.hpp).
+// osc_internal.hpp); further down the chain receipts (12.1), per-query chain priors (12.2) and bundles under them (11.1).
 //
 // For the lattice's graph, gates, chain and lambdas, U*(psi) = X + x psi^T with M X = lamG Y and M x = lamQ B, so one
 // basis serves every query: a batch is one GEMM (query dots), one pass over the graph (coherence drop), per-query column
@@ -229,6 +229,7 @@ void query_basis_shifted_solve(L& l, float lamP, float tol, int32_t max_iters, f
   std::copy(saved_pred, saved_pred + 3, l.predicted_iters);
   l.history = std::move(saved_hist);
   sh.have = true;
+  ++sh.gen;
   sh.epoch = l.derived.epoch;
   sh.lamP = lamP;
   sh.scale = scale;
@@ -752,6 +753,172 @@ void query_chain_receipt_many(L& l, const float* psis, int32_t Q, const int64_t*
 }
 
 // ---- per-query chain priors ------------------------------------------------------------------
+namespace {
+
+// host vectors the panel stage reuses from pass to pass
+struct CpHostScratch {
+  host::ChainPriorSystems sys;
+  std::vector<int32_t> hints, hnode;
+  std::vector<int64_t> hlongs;
+  std::map<int32_t, int32_t> column_of;
+};
+
+// what the panel stage of a pass leaves on the device (in l.query's cp_* buffers)
+struct CpPanelOut {
+  const float* G;             // the Green's columns, slab-major
+  const int32_t* q_sys;       // [nq]
+  const int32_t* sys_m;
+  const int32_t* sys_col_at;
+  const int32_t* sys_cols;
+  const int64_t* tv_at;       // [nq] into q.cp_tv
+  float* prior_res;           // [nq]
+  int32_t* prior_iters;       // [nq]
+};
+
+// The panel stage of one pass, shared by osc_chain_prior_many and osc_bundle_prior_many: the unit sources of the pass's
+// columns (cols: API ids, qc = their count rounded up to 32), the Jacobi-PCG over the panel, T per distinct chain of `paths`
+// (k_cp_systems), T_q V_q and the residual bound per query (k_cp_tv).  hflts enters as the nq per-query base residuals and
+// leaves with the systems' weights behind them.  The panel lives at chain_prior_layout's offsets from the start of
+// q.cp_scratch, which the caller has sized for the pass (at least chain_prior_layout(N, qc).total bytes).
+CpPanelOut chain_prior_panel_stage(L& l, const std::vector<int32_t>& cols, int32_t qc, int32_t nq,
+                                   const host::ChainManyPaths& paths, const std::vector<int32_t>& path_of,
+                                   std::vector<float>& hflts, const int32_t* dev, const float* bX, const float* bx4, float lamP,
+                                   float tol_g, int32_t max_iters, const GmRowOp& rop, const GmGraph& g, CpHostScratch& hs) {
+  auto& q = l.query;
+  const int32_t N = (int32_t)l.N, D = l.D;
+  host::ChainPriorSystems& sys = hs.sys;
+  std::vector<int32_t>& hints = hs.hints;
+  std::vector<int32_t>& hnode = hs.hnode;
+  std::vector<int64_t>& hlongs = hs.hlongs;
+  std::map<int32_t, int32_t>& column_of = hs.column_of;
+  // the panel: one unit right-hand side per distinct node of the pass
+  const int32_t ncol = (int32_t)cols.size();
+  const host::ChainPriorLayout lay = host::chain_prior_layout(N, qc);
+  if (q.cp_scratch.n < (size_t)lay.total) throw Invalid("chain_prior_panel_stage: the caller's block is too small");
+  char* const base = q.cp_scratch.p;
+  GmPanel p{};
+  p.X = reinterpret_cast<float*>(base + lay.X);
+  p.R = reinterpret_cast<float*>(base + lay.R);
+  p.P = reinterpret_cast<float*>(base + lay.P);
+  p.AP = reinterpret_cast<float*>(base + lay.AP);
+  p.part_a = reinterpret_cast<double*>(base + lay.part_a);
+  p.part_b = reinterpret_cast<double*>(base + lay.part_b);
+  p.rz = reinterpret_cast<double*>(base + lay.rz);
+  p.tol = reinterpret_cast<float*>(base + lay.tol);
+  p.alpha = reinterpret_cast<float*>(base + lay.alpha);
+  p.beta = reinterpret_cast<float*>(base + lay.beta);
+  p.res = reinterpret_cast<float*>(base + lay.res);
+  p.live = reinterpret_cast<int32_t*>(base + lay.live);
+  p.iters = reinterpret_cast<int32_t*>(base + lay.iters);
+  p.slab_live = reinterpret_cast<int32_t*>(base + lay.slab_live);
+  p.n_live = reinterpret_cast<int32_t*>(base + lay.n_live);
+  p.N = N;
+  p.slabs = qc / host::kGatesSlab;
+  p.parts = host::gates_parts(N);
+  p.part_rows = host::gates_part_rows(N);
+  p.nq = ncol;
+  int32_t* const node_d = reinterpret_cast<int32_t*>(base + lay.node);
+  hnode.assign((size_t)qc, -1);
+  column_of.clear();
+  for (int32_t c = 0; c < ncol; ++c) {
+    hnode[(size_t)c] = dev ? dev[cols[(size_t)c]] : cols[(size_t)c];
+    column_of[hnode[(size_t)c]] = c;
+  }
+  HIP_CHECK(hipMemcpyAsync(node_d, hnode.data(), (size_t)qc * 4, hipMemcpyHostToDevice, l.stream));
+  launch_gm_unit_source(p, node_d, rop, l.stream);
+  launch_gm_init(p, 0, tol_g, l.stream);
+  for (int32_t it = 1; it <= max_iters; ++it) {
+    launch_gm_apply_rows(p, g, rop, l.stream);
+    launch_gm_alpha(p, l.stream);
+    launch_gm_update_rows(p, rop, l.stream);
+    launch_gm_beta(p, it, l.stream);
+    int32_t live = 0;
+    if (it < max_iters) launch_gm_direction_rows(p, rop, l.stream);
+    HIP_CHECK(hipMemcpyAsync(&live, p.n_live + (it & 1), 4, hipMemcpyDeviceToHost, l.stream));
+    sync(l);
+    if (live == 0) break;
+  }
+  // the systems: one per distinct (chain, weights) of the pass
+  sys.clear();
+  for (const host::ChainPath& cp : paths.paths) sys.add(cp.rows, cp.ptr, cp.col, cp.w, column_of);
+  const size_t ns = sys.m.size();
+  hints.clear();
+  auto put = [&](const std::vector<int32_t>& v) {
+    const size_t at = hints.size();
+    hints.insert(hints.end(), v.begin(), v.end());
+    return at;
+  };
+  const size_t i_m = put(sys.m), i_col_at = put(sys.col_at), i_k_at = put(sys.k_at), i_cols = put(sys.cols),
+               i_rows = put(sys.rows), i_kr = put(sys.kr), i_kc = put(sys.kc), i_qsys = put(path_of);
+  hlongs.assign(sys.t_at.begin(), sys.t_at.end());
+  int64_t tv_n = 0;
+  for (int32_t t = 0; t < nq; ++t) {
+    hlongs.push_back(tv_n);
+    tv_n += (int64_t)sys.m[(size_t)path_of[(size_t)t]] * l.ld;
+  }
+  hflts.insert(hflts.end(), sys.kw.begin(), sys.kw.end());  // [base | kw]
+  q.cp_ints.alloc(hints.size());
+  q.cp_longs.alloc(hlongs.size());
+  q.cp_flts.alloc(hflts.size() + 2 * (size_t)nq);
+  q.cp_T.alloc((size_t)std::max<int64_t>(sys.t_doubles, 1));
+  q.cp_tv.alloc((size_t)std::max<int64_t>(tv_n, 1));
+  HIP_CHECK(hipMemcpyAsync(q.cp_ints.p, hints.data(), hints.size() * 4, hipMemcpyHostToDevice, l.stream));
+  HIP_CHECK(hipMemcpyAsync(q.cp_longs.p, hlongs.data(), hlongs.size() * 8, hipMemcpyHostToDevice, l.stream));
+  HIP_CHECK(hipMemcpyAsync(q.cp_flts.p, hflts.data(), hflts.size() * 4, hipMemcpyHostToDevice, l.stream));
+  float* const pres_d = q.cp_flts.p + hflts.size();
+  int32_t* const pit_d = reinterpret_cast<int32_t*>(pres_d + nq);
+  CpSystemsArgs sa{};
+  sa.G = p.X;
+  sa.m = q.cp_ints.p + i_m;
+  sa.col_at = q.cp_ints.p + i_col_at;
+  sa.k_at = q.cp_ints.p + i_k_at;
+  sa.t_at = q.cp_longs.p;
+  sa.cols = q.cp_ints.p + i_cols;
+  sa.rows = q.cp_ints.p + i_rows;
+  sa.kr = q.cp_ints.p + i_kr;
+  sa.kc = q.cp_ints.p + i_kc;
+  sa.kw = q.cp_flts.p + nq;
+  sa.N = N;
+  sa.n_sys = (int32_t)ns;
+  sa.lamP = lamP;
+  sa.T = q.cp_T.p;
+  launch_cp_systems(sa, l.stream);
+  CpTvArgs ta{};
+  ta.X = bX;
+  ta.x4 = bx4;
+  ta.psi = q.cm_psi.p;
+  ta.T = q.cp_T.p;
+  ta.q_sys = q.cp_ints.p + i_qsys;
+  ta.m = sa.m;
+  ta.col_at = sa.col_at;
+  ta.t_at = sa.t_at;
+  ta.cols = sa.cols;
+  ta.rows = sa.rows;
+  ta.col_res = p.res;
+  ta.col_iters = p.iters;
+  ta.base = q.cp_flts.p;
+  ta.tv_at = q.cp_longs.p + ns;
+  ta.nq = nq;
+  ta.D = D;
+  ta.ld = l.ld;
+  ta.TV = q.cp_tv.p;
+  ta.prior_res = pres_d;
+  ta.prior_iters = pit_d;
+  launch_cp_tv(ta, l.stream);
+  CpPanelOut out{};
+  out.G = p.X;
+  out.q_sys = ta.q_sys;
+  out.sys_m = sa.m;
+  out.sys_col_at = sa.col_at;
+  out.sys_cols = sa.cols;
+  out.tv_at = ta.tv_at;
+  out.prior_res = pres_d;
+  out.prior_iters = pit_d;
+  return out;
+}
+
+}  // namespace
+
 // Query q's answer is chain_receipt(chain_q) on the U* of M + lamP L_path,q = M' - S_q K_q S_q^T (M' = M + lamP I):
 //   U*_q = U'0 + G T_q (S_q^T U'0),  U'0 = X' + x' psi_q^T,  G = M'^-1 S_q,  T_q = (I - K_q Ghat)^-1 K_q.
 // Per pass (chain_prior_plan.hpp): one Jacobi-PCG over a panel of unit right-hand sides, one column per distinct chain node
@@ -828,12 +995,10 @@ void query_chain_prior_many(L& l, const float* psis, int32_t Q, const int64_t* c
   q.cm_wk.alloc(kQueryChunk);
   q.cm_wz.alloc(kQueryChunk);
   host::ChainManyPaths paths;
-  host::ChainPriorSystems sys;
+  CpHostScratch hs;
   std::vector<host::ChainManyUnit> units;
-  std::vector<int32_t> eoff, path_of, hints, hnode;
-  std::vector<int64_t> hlongs;
+  std::vector<int32_t> eoff, path_of;
   std::vector<float> hpsi, hflts;
-  std::map<int32_t, int32_t> column_of;
   for (const host::ChainPriorPass& ps : passes) {
     const int32_t c0 = ps.q0, nq = ps.nq;
     paths.clear();
@@ -872,129 +1037,20 @@ void query_chain_prior_many(L& l, const float* psis, int32_t Q, const int64_t* c
         prior_iters[c0 + t] = 0;
       }
     } else {
-      // the panel: one unit right-hand side per distinct node of the pass
-      const int32_t ncol = (int32_t)ps.cols.size(), qc = ps.qc;
-      const host::ChainPriorLayout lay = host::chain_prior_layout(N, qc);
-      q.cp_scratch.alloc((size_t)lay.total);
-      char* const base = q.cp_scratch.p;
-      GmPanel p{};
-      p.X = reinterpret_cast<float*>(base + lay.X);
-      p.R = reinterpret_cast<float*>(base + lay.R);
-      p.P = reinterpret_cast<float*>(base + lay.P);
-      p.AP = reinterpret_cast<float*>(base + lay.AP);
-      p.part_a = reinterpret_cast<double*>(base + lay.part_a);
-      p.part_b = reinterpret_cast<double*>(base + lay.part_b);
-      p.rz = reinterpret_cast<double*>(base + lay.rz);
-      p.tol = reinterpret_cast<float*>(base + lay.tol);
-      p.alpha = reinterpret_cast<float*>(base + lay.alpha);
-      p.beta = reinterpret_cast<float*>(base + lay.beta);
-      p.res = reinterpret_cast<float*>(base + lay.res);
-      p.live = reinterpret_cast<int32_t*>(base + lay.live);
-      p.iters = reinterpret_cast<int32_t*>(base + lay.iters);
-      p.slab_live = reinterpret_cast<int32_t*>(base + lay.slab_live);
-      p.n_live = reinterpret_cast<int32_t*>(base + lay.n_live);
-      p.N = N;
-      p.slabs = qc / host::kGatesSlab;
-      p.parts = host::gates_parts(N);
-      p.part_rows = host::gates_part_rows(N);
-      p.nq = ncol;
-      int32_t* const node_d = reinterpret_cast<int32_t*>(base + lay.node);
-      hnode.assign((size_t)qc, -1);
-      column_of.clear();
-      for (int32_t c = 0; c < ncol; ++c) {
-        hnode[(size_t)c] = dev ? dev[ps.cols[(size_t)c]] : ps.cols[(size_t)c];
-        column_of[hnode[(size_t)c]] = c;
-      }
-      HIP_CHECK(hipMemcpyAsync(node_d, hnode.data(), (size_t)qc * 4, hipMemcpyHostToDevice, l.stream));
-      launch_gm_unit_source(p, node_d, rop, l.stream);
-      launch_gm_init(p, 0, tol_g, l.stream);
-      for (int32_t it = 1; it <= max_iters; ++it) {
-        launch_gm_apply_rows(p, g, rop, l.stream);
-        launch_gm_alpha(p, l.stream);
-        launch_gm_update_rows(p, rop, l.stream);
-        launch_gm_beta(p, it, l.stream);
-        int32_t live = 0;
-        if (it < max_iters) launch_gm_direction_rows(p, rop, l.stream);
-        HIP_CHECK(hipMemcpyAsync(&live, p.n_live + (it & 1), 4, hipMemcpyDeviceToHost, l.stream));
-        sync(l);
-        if (live == 0) break;
-      }
-      // the systems: one per distinct (chain, weights) of the pass
-      sys.clear();
-      for (const host::ChainPath& cp : paths.paths) sys.add(cp.rows, cp.ptr, cp.col, cp.w, column_of);
-      const size_t ns = sys.m.size();
-      hints.clear();
-      auto put = [&](const std::vector<int32_t>& v) {
-        const size_t at = hints.size();
-        hints.insert(hints.end(), v.begin(), v.end());
-        return at;
-      };
-      const size_t i_m = put(sys.m), i_col_at = put(sys.col_at), i_k_at = put(sys.k_at), i_cols = put(sys.cols),
-                   i_rows = put(sys.rows), i_kr = put(sys.kr), i_kc = put(sys.kc), i_qsys = put(path_of);
-      hlongs.assign(sys.t_at.begin(), sys.t_at.end());
-      int64_t tv_n = 0;
-      for (int32_t t = 0; t < nq; ++t) {
-        hlongs.push_back(tv_n);
-        tv_n += (int64_t)sys.m[(size_t)path_of[(size_t)t]] * l.ld;
-      }
-      hflts.insert(hflts.end(), sys.kw.begin(), sys.kw.end());  // [base | kw]
-      q.cp_ints.alloc(hints.size());
-      q.cp_longs.alloc(hlongs.size());
-      q.cp_flts.alloc(hflts.size() + 2 * (size_t)nq);
-      q.cp_T.alloc((size_t)std::max<int64_t>(sys.t_doubles, 1));
-      q.cp_tv.alloc((size_t)std::max<int64_t>(tv_n, 1));
-      HIP_CHECK(hipMemcpyAsync(q.cp_ints.p, hints.data(), hints.size() * 4, hipMemcpyHostToDevice, l.stream));
-      HIP_CHECK(hipMemcpyAsync(q.cp_longs.p, hlongs.data(), hlongs.size() * 8, hipMemcpyHostToDevice, l.stream));
-      HIP_CHECK(hipMemcpyAsync(q.cp_flts.p, hflts.data(), hflts.size() * 4, hipMemcpyHostToDevice, l.stream));
-      float* const pres_d = q.cp_flts.p + hflts.size();
-      int32_t* const pit_d = reinterpret_cast<int32_t*>(pres_d + nq);
-      CpSystemsArgs sa{};
-      sa.G = p.X;
-      sa.m = q.cp_ints.p + i_m;
-      sa.col_at = q.cp_ints.p + i_col_at;
-      sa.k_at = q.cp_ints.p + i_k_at;
-      sa.t_at = q.cp_longs.p;
-      sa.cols = q.cp_ints.p + i_cols;
-      sa.rows = q.cp_ints.p + i_rows;
-      sa.kr = q.cp_ints.p + i_kr;
-      sa.kc = q.cp_ints.p + i_kc;
-      sa.kw = q.cp_flts.p + nq;
-      sa.N = N;
-      sa.n_sys = (int32_t)ns;
-      sa.lamP = lamP;
-      sa.T = q.cp_T.p;
-      launch_cp_systems(sa, l.stream);
-      CpTvArgs ta{};
-      ta.X = bX;
-      ta.x4 = bx4;
-      ta.psi = q.cm_psi.p;
-      ta.T = q.cp_T.p;
-      ta.q_sys = q.cp_ints.p + i_qsys;
-      ta.m = sa.m;
-      ta.col_at = sa.col_at;
-      ta.t_at = sa.t_at;
-      ta.cols = sa.cols;
-      ta.rows = sa.rows;
-      ta.col_res = p.res;
-      ta.col_iters = p.iters;
-      ta.base = q.cp_flts.p;
-      ta.tv_at = q.cp_longs.p + ns;
-      ta.nq = nq;
-      ta.D = D;
-      ta.ld = l.ld;
-      ta.TV = q.cp_tv.p;
-      ta.prior_res = pres_d;
-      ta.prior_iters = pit_d;
-      launch_cp_tv(ta, l.stream);
+      q.cp_scratch.alloc((size_t)host::chain_prior_layout(N, ps.qc).total);
+      const CpPanelOut po = chain_prior_panel_stage(l, ps.cols, ps.qc, nq, paths, path_of, hflts, dev, bX, bx4, lamP, tol_g,
+                                                    max_iters, rop, g, hs);
+      float* const pres_d = po.prior_res;
+      int32_t* const pit_d = po.prior_iters;
       HIP_CHECK(hipMemcpyAsync(prior_res + c0, pres_d, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
       HIP_CHECK(hipMemcpyAsync(prior_iters + c0, pit_d, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
-      e.G = p.X;
-      e.q_sys = ta.q_sys;
-      e.sys_m = sa.m;
-      e.sys_col_at = sa.col_at;
-      e.sys_cols = sa.cols;
+      e.G = po.G;
+      e.q_sys = po.q_sys;
+      e.sys_m = po.sys_m;
+      e.sys_col_at = po.sys_col_at;
+      e.sys_cols = po.sys_cols;
       e.TV = q.cp_tv.p;
-      e.tv_at = ta.tv_at;
+      e.tv_at = po.tv_at;
     }
     e.X = bX;
     e.x4 = bx4;
@@ -1043,6 +1099,253 @@ void query_chain_prior_many(L& l, const float* psis, int32_t Q, const int64_t* c
     HIP_CHECK(hipMemcpyAsync(weakest_z + c0, q.cm_wz.p, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
     sync(l);  // (the host vectors above are reused by the next pass)
   }
+}
+
+// ---- bundles under per-query chain priors ------------------------------------------------------
+namespace {
+
+// k_query_basis_stats on the shifted basis, kept in its slot until the next shifted solve or extension
+void ensure_shifted_stats(L& l) {
+  auto& sh = l.query.shifted;
+  if (sh.stats_gen == sh.gen && sh.s.p) return;
+  const size_t n = (size_t)l.N;
+  sh.s.alloc(n);
+  sh.xn2.alloc(n);
+  sh.c0.alloc(n);
+  sh.c2.alloc(n);
+  QueryBasisArgs a{};
+  a.Y = l.Y.p;
+  a.X = sh.X.p;
+  a.x4 = sh.x4.p;
+  a.sqrt_deg = l.sqrt_deg.p;
+  a.col = l.ell_col.p;
+  a.adj = l.ell_a.p;
+  a.deg = l.deg.p;
+  a.width = l.width;
+  a.N = (int32_t)l.N;
+  a.D = l.D;
+  a.ld = l.ld;
+  a.lamC = l.lamC;
+  a.s = sh.s.p;
+  a.xn2 = sh.xn2.p;
+  a.c0 = sh.c0.p;
+  a.c2 = sh.c2.p;
+  launch_query_basis_stats(a, l.stream);
+  sh.stats_gen = sh.gen;
+}
+
+}  // namespace
+
+// bundle(k, alpha) of Q (query, chain) pairs, query q on the U* of M + lamP L_path,q (lattice.py:530-568 after
+// lattice.py:129-150).  Per pass (bundle_prior_plan.hpp): section 12.2's panel stage, then the query dots and kappa (two
+// GEMMs on the shifted basis), e and H per query, nu / align and coh per (row, query), and section 11's score, MMR and pack.
+// lamP == 0: osc_bundle_many on the resident basis.
+void query_bundle_prior_many(L& l, const float* psis, int32_t Q, const int64_t* chain_offsets, const int32_t* chain_nodes,
+                             const float* chain_weights, float lamP, float tol, int32_t max_iters, int32_t k, float alpha,
+                             float lambda_div, int32_t* ids, float* score, float* align, float* prior_res,
+                             int32_t* prior_iters) {
+  if (l.comm) throw Unsupported("osc_bundle_prior_many: lattices with a communicator are not supported");
+  require_graph(l);
+  if (!(lamP >= 0.f) || !std::isfinite(lamP)) throw Invalid("osc_bundle_prior_many: lamP must be a finite value >= 0");
+  if (!(tol > 0.f) || !std::isfinite(tol)) throw Invalid("osc_bundle_prior_many: tol must be > 0");
+  if (max_iters < 1) throw Invalid("max_iters must be >= 1");
+  if (l.chain_present) throw Invalid("osc_bundle_prior_many: the lattice has a chain of its own (osc_clear_chain first)");
+  const bool prior = lamP > 0.f;
+  auto& q = l.query;
+  auto& sh = q.shifted;
+  if (prior) {
+    if (!sh.have || sh.epoch != l.derived.epoch || sh.lamP != lamP)
+      throw StateError("no shifted query basis for this lamP and the current graph (call osc_query_basis_shifted first)");
+  } else {
+    require_basis(l);
+  }
+  if (Q <= 0) return;
+  int32_t where = 0;
+  switch (host::chain_many_check(chain_offsets, chain_nodes, Q, l.N, &where)) {
+    case 1:
+      throw Invalid("osc_bundle_prior_many: query " + std::to_string(where) + ": a chain has 2 to " +
+                    std::to_string(host::kCorpusMaxChain) + " nodes, at offsets that start from 0");
+    case 2:
+      throw Invalid("osc_bundle_prior_many: query " + std::to_string(where) + ": chain indices out of bounds");
+  }
+  where = host::chain_prior_check(chain_offsets, chain_nodes, Q);
+  if (where >= 0)
+    throw Invalid("osc_bundle_prior_many: query " + std::to_string(where) + ": a chain has at most " +
+                  std::to_string(host::kChainPriorMaxNodes) + " distinct nodes");
+  if (chain_weights)
+    for (int64_t e = 0; e < host::chain_many_edge_at(chain_offsets, Q); ++e)
+      if (!std::isfinite(chain_weights[e])) throw Invalid("osc_bundle_prior_many: non-finite chain weight");
+  const int32_t N = (int32_t)l.N, D = l.D;
+  const float res_X = prior ? sh.res_X : q.res_X, res_x = prior ? sh.res_x : q.res_x;
+  auto base_res = [&](int32_t t) {  // the basis's own residual for query t: |r_X| + |psi_t|_inf |r_x|
+    float pinf = 0.f;
+    for (int32_t d = 0; d < D; ++d) pinf = std::max(pinf, std::fabs(psis[(size_t)t * D + d]));
+    return res_X + pinf * res_x;
+  };
+  if (!prior) {
+    query_bundle_many(l, psis, Q, k, alpha, lambda_div, ids, score, align);
+    for (int32_t t = 0; t < Q; ++t) {
+      prior_res[t] = base_res(t);
+      prior_iters[t] = 0;
+    }
+    return;
+  }
+  const int32_t kk = (int32_t)std::min<int64_t>(std::max(k, 0), l.N);
+  const int32_t kpad = query_kpad(D);
+  const int32_t* dev = permuted(l) ? l.inv_h.data() : nullptr;
+  int max_cols = 0;
+  env_num("OSC_CHAIN_PRIOR_COLS", max_cols);
+  const std::vector<host::BundlePriorPass> passes = host::bundle_prior_passes(
+      chain_offsets, chain_nodes, Q, N, kpad, kQueryChunk, max_cols, host::kChainPriorBudgetBytes);
+  ensure_yn(l);
+  ensure_shifted_stats(l);
+  GmRowOp rop{};
+  const GmGraph g{l.ell_col.p, l.ell_w.p, l.deg.p, l.width};
+  q.cp_diag.alloc((size_t)N);
+  launch_gm_row_diag(l.B.p, l.lamG + lamP + l.lamC, l.lamQ, N, q.cp_diag.p, l.stream);
+  rop.d = q.cp_diag.p;
+  rop.lamC = l.lamC;
+  const float tol_g = host::chain_prior_tol_g(tol, l.lamG, lamP, sh.max_X + sh.max_x * sh.scale);
+  q.Bt.alloc((size_t)query_qpad(kQueryChunk) * kpad);
+  q.pn2.alloc(kQueryChunk);
+  q.pinv.alloc(kQueryChunk);
+  q.part.alloc((size_t)query_stat_parts(N) * kQueryChunk);
+  q.stats.alloc(kQueryChunk);
+  if (kk > 0) {
+    q.out_score.alloc((size_t)kQueryChunk * kk);
+    q.out_align.alloc((size_t)kQueryChunk * kk);
+  }
+  host::ChainManyPaths paths;
+  CpHostScratch hs;
+  std::vector<host::ChainManyUnit> units;
+  std::vector<int32_t> eoff, path_of;
+  std::vector<float> hpsi, hflts, bt;
+  std::vector<double> pn2, pinv;
+  for (const host::BundlePriorPass& ps : passes) {
+    const int32_t c0 = ps.q0, nq = ps.nq;
+    paths.clear();
+    host::chain_many_units_weighted(chain_offsets, chain_nodes, chain_weights, c0, nq, dev, N, paths, units, eoff, path_of);
+    const int32_t qs = query_qs(nq), qpad = query_qpad(nq);
+    hpsi.assign((size_t)nq * l.ld, 0.f);
+    bt.assign((size_t)qpad * kpad, 0.f);
+    pn2.assign((size_t)nq, 0.0);
+    pinv.assign((size_t)nq, 0.0);
+    hflts.assign((size_t)nq, 0.f);
+    for (int32_t t = 0; t < nq; ++t) {
+      const float* p = psis + (size_t)(c0 + t) * D;
+      double s = 0.0;
+      for (int32_t c = 0; c < D; ++c) {
+        hpsi[(size_t)t * l.ld + c] = p[c];
+        bt[(size_t)t * kpad + c] = p[c];
+        s += (double)p[c] * (double)p[c];
+      }
+      pn2[(size_t)t] = s;
+      pinv[(size_t)t] = 1.0 / (std::sqrt(s) + 1e-12);
+      hflts[(size_t)t] = base_res(c0 + t);
+    }
+    q.cm_psi.alloc(hpsi.size());
+    HIP_CHECK(hipMemcpyAsync(q.cm_psi.p, hpsi.data(), hpsi.size() * 4, hipMemcpyHostToDevice, l.stream));
+    HIP_CHECK(hipMemcpyAsync(q.Bt.p, bt.data(), bt.size() * 4, hipMemcpyHostToDevice, l.stream));
+    HIP_CHECK(hipMemcpyAsync(q.pn2.p, pn2.data(), (size_t)nq * 8, hipMemcpyHostToDevice, l.stream));
+    HIP_CHECK(hipMemcpyAsync(q.pinv.p, pinv.data(), (size_t)nq * 8, hipMemcpyHostToDevice, l.stream));
+    const host::BundlePriorLayout lay = host::bundle_prior_layout(N, ps.qc, ps.msum, nq, kpad);
+    q.cp_scratch.alloc((size_t)lay.total);
+    const CpPanelOut po = chain_prior_panel_stage(l, ps.cols, ps.qc, nq, paths, path_of, hflts, dev, sh.X.p, sh.x4.p, lamP,
+                                                  tol_g, max_iters, rop, g, hs);
+    HIP_CHECK(hipMemcpyAsync(prior_res + c0, po.prior_res, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
+    HIP_CHECK(hipMemcpyAsync(prior_iters + c0, po.prior_iters, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
+    if (kk <= 0) {
+      sync(l);
+      continue;
+    }
+    char* const base = q.cp_scratch.p;
+    float* const kappa = reinterpret_cast<float*>(base + lay.kappa);
+    float* const btk = reinterpret_cast<float*>(base + lay.bt);
+    q.align.alloc((size_t)N * qs);
+    q.pm.alloc((size_t)N * qs);
+    q.cs.alloc((size_t)N * qs);
+    // kappa: the rows of every query's T_q V_q against X', in the query-dot GEMM's tile and K order
+    launch_bp_pack(q.cp_tv.p, ps.msum, query_qpad((int32_t)ps.msum), D, l.ld, kpad, btk, l.stream);
+    QueryGemmArgs gk{};
+    gk.A = sh.X.p;
+    gk.Bt = btk;
+    gk.N = N;
+    gk.D = D;
+    gk.ld = l.ld;
+    gk.kpad = kpad;
+    gk.qs = lay.ks;
+    gk.nq = (int32_t)ps.msum;
+    gk.mode = 2;
+    gk.sqrt_deg = l.sqrt_deg.p;
+    gk.p = kappa;
+    launch_query_gemm(gk, l.stream);
+    // p: section 11's query dots on the shifted basis (its align is overwritten below)
+    QueryGemmArgs gp{};
+    gp.A = sh.X.p;
+    gp.Bt = q.Bt.p;
+    gp.N = N;
+    gp.D = D;
+    gp.ld = l.ld;
+    gp.kpad = kpad;
+    gp.qs = qs;
+    gp.nq = nq;
+    gp.mode = 0;
+    gp.x4 = sh.x4.p;
+    gp.xn2 = sh.xn2.p;
+    gp.sqrt_deg = l.sqrt_deg.p;
+    gp.pn2 = q.pn2.p;
+    gp.pinv = q.pinv.p;
+    gp.align = q.align.p;
+    gp.p = q.pm.p;
+    launch_query_gemm(gp, l.stream);
+    BpArgs b{};
+    b.col = l.ell_col.p;
+    b.adj = l.ell_a.p;
+    b.deg = l.deg.p;
+    b.width = l.width;
+    b.N = N;
+    b.lamC = l.lamC;
+    b.sqrt_deg = l.sqrt_deg.p;
+    b.s = sh.s.p;
+    b.xn2 = sh.xn2.p;
+    b.c0 = sh.c0.p;
+    b.c2 = sh.c2.p;
+    b.p = q.pm.p;
+    b.G = po.G;
+    b.kappa = kappa;
+    b.TV = q.cp_tv.p;
+    b.psi = q.cm_psi.p;
+    b.q_sys = po.q_sys;
+    b.sys_m = po.sys_m;
+    b.sys_col_at = po.sys_col_at;
+    b.sys_cols = po.sys_cols;
+    b.tv_at = po.tv_at;
+    b.pn2 = q.pn2.p;
+    b.pinv = q.pinv.p;
+    b.D = D;
+    b.ld = l.ld;
+    b.ks = lay.ks;
+    b.qs = qs;
+    b.nq = nq;
+    b.gs = host::bundle_prior_group(ps.mmax);
+    b.e = reinterpret_cast<double*>(base + lay.e);
+    b.H = reinterpret_cast<double*>(base + lay.H);
+    b.nu = reinterpret_cast<double*>(base + lay.nu);
+    b.align = q.align.p;
+    b.coh = q.cs.p;
+    launch_bp_scalars(b, l.stream);
+    launch_bp_rows_self(b, l.stream);
+    launch_bp_rows_coh(b, l.stream);
+    launch_query_score(q.cs.p, q.align.p, N, qs, nq, (double)alpha, q.part.p, q.stats.p, l.stream);
+    mmr_many_run(l, qs, nq, kk, lambda_div);
+    launch_query_pack(q.cs.p, q.align.p, q.chosen_row.p, qs, nq, kk, q.out_score.p, q.out_align.p, l.stream);
+    const size_t m = (size_t)nq * kk, off = (size_t)c0 * kk;
+    HIP_CHECK(hipMemcpyAsync(ids + off, q.chosen_api.p, m * 4, hipMemcpyDeviceToHost, l.stream));
+    HIP_CHECK(hipMemcpyAsync(score + off, q.out_score.p, m * 4, hipMemcpyDeviceToHost, l.stream));
+    HIP_CHECK(hipMemcpyAsync(align + off, q.out_align.p, m * 4, hipMemcpyDeviceToHost, l.stream));
+    sync(l);  // (the host vectors above are reused by the next pass)
+  }
+  q.cp_scratch.release();  // up to 1 GiB a pass: back to the allocator's pool, not kept on the handle between calls
 }
 
 // ---- diffusion gates for many queries ----------------------------------------------------------

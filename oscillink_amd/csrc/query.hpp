@@ -36,6 +36,8 @@ void launch_query_basis_stats(const QueryBasisArgs& a, hipStream_t s);
 // C[N x qs] = A[N x D] (row pitch ld) . Bt[qpad x kpad]^T on v_mfma_f32_32x32x2_f32, K in one fixed order for every output.
 // mode 0 (dots): C = g = X psi^T; the epilogue writes align (cos(U*_i, psi_q)) and p = g / (sd_i + 1e-12)
 // mode 1 (mmr):  C = <Yn_i, Yn_pick(q)>; the epilogue folds it into the running maximum (first: replaces it; +inf = taken)
+// mode 2 (rows): C = A Bt^T for any rows of Bt (the nq rows of a pass's T_q V_q blocks); the epilogue
+//                writes p = C / (sd_i + 1e-12) and nothing else (sqrt_deg and p of mode 0's fields)
 struct QueryGemmArgs {
   const float* A;
   const float* Bt;
@@ -89,6 +91,58 @@ void launch_mmr_many_argmax(const MmrManyArgs& a, int step, hipStream_t st);
 // out[q * k + t] = score / align of query q at its t-th pick (0 past the end)
 void launch_query_pack(const float* score, const float* align, const int32_t* chosen_row, int32_t qs, int32_t nq, int32_t k,
                        float* out_score, float* out_align, hipStream_t st);
+
+}  // namespace osc
+
+// ---- bundles under per-query chain priors: bundle_prior_kernels.hip ---------------------------
+namespace osc {
+
+constexpr int kBpNodes = 64;  // nodes of a chain system at most (chain_prior_plan.hpp: kChainPriorMaxNodes): one per lane
+
+// Bt[r][0 .. kpad) = TV[r][0 .. D) then zeros for r < rows, zeros for rows <= r < rows_pad (TV at pitch ld)
+void launch_bp_pack(const float* TV, int64_t rows, int64_t rows_pad, int32_t D, int32_t ld, int32_t kpad, float* Bt,
+                    hipStream_t s);
+
+// Per (row, query) of a pass on U*_q,i = X'_i + x'_i psi_q + sum_b G_ib C_b (C = T_q V_q, the query's m rows of TV), in the
+// units of section 11: di = sd_i + 1e-12, s = x' / di, p = X'_i . psi / di, gamma_ib = G_ib / di, kappa_ib = X'_i . C_b / di.
+struct BpArgs {
+  const int32_t* col;     // ELL, device rows
+  const float* adj;       // capped adjacency
+  const int32_t* deg;
+  int32_t width, N;
+  float lamC;
+  const float* sqrt_deg;
+  const float* s;         // [N] of the shifted basis, with xn2 / c0 / c2 (k_query_basis_stats on (X', x'))
+  const double* xn2;
+  const double* c0;
+  const double* c2;
+  const float* p;         // N x qs (k_query_gemm<0> on the shifted basis)
+  const float* G;         // the pass's Green's columns, slab-major
+  const float* kappa;     // N x ks (k_query_gemm<2>); query q's columns start at tv_at[q] / ld
+  const float* TV;        // the pass's T_q V_q blocks, m x ld each at tv_at[q]
+  const float* psi;       // nq x ld
+  const int32_t* q_sys;   // [nq] the query's chain system
+  const int32_t* sys_m;
+  const int32_t* sys_col_at;
+  const int32_t* sys_cols;
+  const int64_t* tv_at;   // [nq]
+  const double* pn2;      // [nq] |psi_q|^2
+  const double* pinv;     // [nq] 1 / (|psi_q| + 1e-12)
+  int32_t D, ld, ks, qs, nq;
+  int32_t gs;             // lanes of a (row, query) pair in the row kernels: a power of two in [max m of the pass, 64]
+  double* e;              // [nq][64]      e_b = C_b . psi (0 past m)
+  double* H;              // [nq][64][64]  H_bb' = C_b . C_b' (0 past m)
+  double* nu;             // N x qs  gamma_i^T H gamma_i
+  float* align;           // N x qs
+  float* coh;             // N x qs
+};
+// e and H per query: fp64 sums over the columns in column order
+void launch_bp_scalars(const BpArgs& a, hipStream_t s);
+// nu and align per (row, query): gs lanes each, lane b of the group owns node b
+void launch_bp_rows_self(const BpArgs& a, hipStream_t s);
+// coh per (row, query): section 11's three terms on the shifted basis and, per graph edge in slot order,
+//   1/2 lamC A_ij [2 sum_b dgamma_b (dkappa_b + ds e_b) + nu_i + nu_j - 2 gamma_j . (H gamma_i)]
+void launch_bp_rows_coh(const BpArgs& a, hipStream_t s);
 
 }  // namespace osc
 

@@ -157,6 +157,7 @@ __global__ __launch_bounds__(256) void k_query_gemm(const QueryGemmArgs a) {
         x = a.x4[row * 4];
         xn2 = a.xn2[row];
       }
+      if (MODE == 2) inv = 1.0f / (a.sqrt_deg[row] + 1e-12f);
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const int q = q0 + wc * 64 + j * 32 + (lane & 31);
@@ -174,6 +175,8 @@ __global__ __launch_bounds__(256) void k_query_gemm(const QueryGemmArgs a) {
             a.align[o] = 0.f;
             a.p[o] = 0.f;
           }
+        } else if (MODE == 2) {
+          a.p[o] = q < a.nq ? g * inv : 0.f;
         } else if (q < a.nq) {
           const float m = a.maxsim[o];
           if (m != INFINITY) a.maxsim[o] = a.first ? g : fmaxf(m, g);
@@ -383,6 +386,7 @@ void launch_query_basis_stats(const QueryBasisArgs& a, hipStream_t s) {
 void launch_query_gemm(const QueryGemmArgs& a, hipStream_t s) {
   const dim3 grid((unsigned)((a.N + kTM - 1) / kTM), (unsigned)(query_qpad(a.nq) / kQueryTileQ));
   if (a.mode == 0) hipLaunchKernelGGL(k_query_gemm<0>, grid, dim3(256), 0, s, a);
+  else if (a.mode == 2) hipLaunchKernelGGL(k_query_gemm<2>, grid, dim3(256), 0, s, a);
   else hipLaunchKernelGGL(k_query_gemm<1>, grid, dim3(256), 0, s, a);
   HIP_CHECK(hipGetLastError());
 }

@@ -137,6 +137,8 @@ class OscillinkLattice:
         # the basis of M + lamP I behind chain_receipt_many(lamP=...): a second slot, keyed like the first plus the shift
         self._qbs_key: Optional[tuple] = None
         self._qbs_scale = 0.0
+        self._qbs_stats = False  # the shifted slot also holds its per-row constants (bundle_many with lamP)
+        self.last_bundle_prior: dict[str, Any] = {}
         self.last_shifted_basis: dict[str, Any] = {}
         self.shifted_basis_solves = 0
         self._settle_callbacks: list = []
@@ -297,7 +299,8 @@ class OscillinkLattice:
                 "anchor_gram3_last_solve": int(g3l.value), "anchor_gram3_builds": int(g3n.value),
                 # chain_receipt_many(lamP=...) keeps the basis of M + lamP I beside the query basis: N x ld + N x 4 floats
                 # (ld >= D rounded up to 4); 0 until the first such call
-                "shifted_basis_bytes": 4 * self.N * (((self.D + 3) // 4) * 4 + 4) if self._qbs_key is not None else 0,
+                "shifted_basis_bytes": (4 * self.N * (((self.D + 3) // 4) * 4 + 4) if self._qbs_key is not None else 0)
+                + (28 * self.N if self._qbs_key is not None and self._qbs_stats else 0),
                 **{name: int(getattr(counters, name)) for name, _ in nat.Counters._fields_[1:]}}
 
     def anchor_gram(self) -> np.ndarray:
@@ -804,21 +807,68 @@ class OscillinkLattice:
 
     # ------------------------------------------------------------------ multi-query bundles (not in the reference)
     def bundle_many(self, psis: np.ndarray, k: int = 8, alpha: float = 0.5, *, tol: float = 1e-4, max_iters: int = 256,
-                    as_arrays: bool = False):
+                    as_arrays: bool = False, chains=None, lamP: Optional[float] = None, chain_weights=None):
         """`bundle(k, alpha)` for each row of `psis` (Q x D), as if `set_query(psis[q])` had been called, without touching
         the lattice's state (psi, U, the U* cache, receipts).  One query basis solve (U*(psi) =
         X + x psi^T) serves every query; a batch is then a GEMM, one graph pass, column statistics and a batched MMR on
         the device.  Returns Q lists of {"id", "score", "align"} (bundle()'s order), or with `as_arrays=True`
-        (ids, score, align), each Q x min(k, N)."""
+        (ids, score, align), each Q x min(k, N).
+
+        With `chains` and `lamP` (>= 0) query q also carries a chain PRIOR: it gets what
+        `add_chain(chains[q], lamP, chain_weights[q]); set_query(psis[q]); bundle(k, alpha)` gives on a lattice without a
+        chain of its own, from the basis of the shifted operator `chain_receipt_many(lamP=...)` uses (the same slot and
+        key) and one Green's column per distinct chain node.  `chains` and `chain_weights` take `chain_receipt_many`'s
+        forms; a chain has at most 64 distinct nodes.  Per query the residual bound and the Green's columns' iterations
+        go to `last_bundle_prior` = {"lamP", "res" (float32), "iters" (int32)}.  `lamP=0` is the plain call."""
         if self._has_comm:
             raise NotImplementedError("bundle_many: lattices with a communicator (sharded / multi-rank) are not supported")
+        prior = chains is not None or lamP is not None
+        if prior:
+            if lamP is None:
+                raise ValueError("chains given without lamP")
+            if chains is None:
+                raise ValueError("lamP given without chains")
+            if not np.isfinite(float(lamP)) or float(lamP) < 0:
+                raise ValueError("lamP must be >= 0")
+            if self._chain_nodes is not None:
+                raise ValueError("bundle_many with lamP: the lattice has a chain of its own (clear_chain first)")
+        elif chain_weights is not None:
+            raise ValueError("chain_weights given without chains and lamP")
         P = rc.check_queries(psis, self.D)
         Q = int(P.shape[0])
         kk = min(int(k), self.N) if k > 0 else 0
         ids = np.zeros((Q, kk), dtype=np.int32)
         score = np.zeros((Q, kk), dtype=np.float32)
         align = np.zeros((Q, kk), dtype=np.float32)
-        if Q > 0 and kk > 0:
+        if prior:
+            lists, offsets, nodes = rc.chain_block(chains, Q, self.N)
+            edge_offsets = offsets - np.arange(Q + 1, dtype=np.int64)
+            weights = rc.chain_prior_weights(chain_weights, chains, lists, edge_offsets)
+            checked = set()  # (a shared chain is one list Q times)
+            for q, ch in enumerate(lists):
+                if id(ch) not in checked and len(set(ch)) > rc.MAX_PRIOR_NODES:
+                    raise ValueError(f"query {q}: with lamP a chain has at most {rc.MAX_PRIOR_NODES} distinct nodes, got "
+                                     f"{len(set(ch))}")
+                checked.add(id(ch))
+            prior_res, prior_iters = np.zeros(Q, dtype=np.float32), np.zeros(Q, dtype=np.int32)
+            if Q > 0 and kk > 0:
+                psi_inf = float(np.max(np.abs(P)))
+                if float(lamP) > 0:
+                    self._ensure_shifted_basis(float(lamP), tol, max_iters, psi_inf)
+                else:
+                    self._ensure_query_basis(tol, max_iters, psi_inf)
+                self._call("osc_bundle_prior_many", nat.f32(P), Q, nat.i64(offsets), nat.i32(nodes),
+                           None if weights is None else nat.f32(weights), float(lamP), float(tol), int(max_iters), kk,
+                           float(alpha), 0.5, nat.i32(ids), nat.f32(score), nat.f32(align), nat.f32(prior_res),
+                           nat.i32(prior_iters))
+                self._qbs_stats = self._qbs_stats or float(lamP) > 0
+            self.last_bundle_prior = {"lamP": float(lamP), "res": prior_res, "iters": prior_iters}
+            over = np.nonzero(~(prior_res <= tol))[0]
+            if over.size:
+                self._log("chain_prior_convergence_warn", {"queries": int(over.size), "first": int(over[0]),
+                                                           "res": float(prior_res[over[0]]), "tol": tol,
+                                                           "iters": int(prior_iters[over[0]])})
+        elif Q > 0 and kk > 0:
             self._ensure_query_basis(tol, max_iters, float(np.max(np.abs(P))))
             self._call("osc_bundle_many", nat.f32(P), Q, kk, float(alpha), 0.5, nat.i32(ids), nat.f32(score), nat.f32(align))
         if as_arrays:
