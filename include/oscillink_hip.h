@@ -448,6 +448,22 @@ int osc_chain_prior_many(osc_handle h, const float* psis, int32_t Q, const int64
 int osc_bundle_prior_many(osc_handle h, const float* psis, int32_t Q, const int64_t* chain_offsets, const int32_t* chain_nodes,
                           const float* chain_weights, float lamP, float tol, int32_t max_iters, int32_t k, float alpha,
                           float lambda_div, int32_t* ids, float* score, float* align, float* prior_res, int32_t* prior_iters);
+/* Not in the reference as one call: receipt() (lattice.py:298-455, receipts.py:10-83) for Q (query, chain) pairs, query q on the
+ * stationary state of M + lamP L_path,q -- what add_chain(chain_q, lamP, weights_q) (lattice.py:129-150), set_query(psi_q) and
+ * receipt() give on a lattice without a chain of its own, with the current U, gates and lambdas held fixed (DESIGN.md section
+ * 12.3).  psis, chain_offsets, chain_nodes, chain_weights, lamP, tol, max_iters, prior_res and prior_iters are
+ * osc_chain_prior_many's, the shifted basis osc_query_basis_shifted's; detail, z_th, null_cap, the four sums, the null-point
+ * outputs and capacity are osc_receipt_many's.  The null points run over the graph's edges on U*_q (add_chain does not touch
+ * A).  U*_q is never formed: deltaH comes from m rows of U, X' and x' at the chain's nodes, the sums from the moments of the
+ * Green's columns, the null points from section 11.1's per-(row, query) expansion.  lamP == 0 is osc_receipt_many on
+ * osc_query_basis's basis.  A query's outputs are the same to the bit whatever else the batch holds.
+ * OSC_E_INVALID for a NULL handle, a lattice with a chain of its own, a non-finite query, osc_bundle_prior_many's and
+ * osc_receipt_many's reasons; OSC_E_STATE without the basis (shifted for lamP > 0); OSC_E_UNSUPPORTED with a communicator. */
+int osc_receipt_prior_many(osc_handle h, const float* psis, int32_t Q, const int64_t* chain_offsets,
+                           const int32_t* chain_nodes, const float* chain_weights, float lamP, float tol, int32_t max_iters,
+                           int32_t detail, float z_th, int32_t null_cap, double* dH, double* coh_sum, double* anchor_sum,
+                           double* query_sum, int32_t* null_total, int64_t* null_offsets, int32_t* i_out, int32_t* j_out,
+                           float* z_out, float* r_out, int64_t capacity, float* prior_res, int32_t* prior_iters);
 /* mmr_diversify (graph.py:114-133) for Q score columns at once: scores N x Q (API row order, queries contiguous per row);
  * out_idx Q x min(k, N) API ids, the same picks as osc_mmr per column up to rounding of the similarities. */
 int osc_mmr_many(osc_handle h, const float* scores, int32_t Q, int32_t k, float lambda_div, int32_t* out_idx);

@@ -116,6 +116,8 @@ SIGNATURES = {
                                        c_i32p]),
     "osc_bundle_prior_many": (C.c_int, [Handle, c_f32p, C.c_int32, c_i64p, c_i32p, c_f32p, C.c_float, C.c_float, C.c_int32,
                                         C.c_int32, C.c_float, C.c_float, c_i32p, c_f32p, c_f32p, c_f32p, c_i32p]),
+    "osc_receipt_prior_many": (C.c_int, [Handle, c_f32p, C.c_int32, c_i64p, c_i32p, c_f32p, C.c_float, C.c_float, C.c_int32,
+                                         C.c_int32, C.c_float, C.c_int32, *_RECEIPT_MANY_OUT, c_f32p, c_i32p]),
     "osc_corpus_create": (C.c_int, [c_f32p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(Handle)]),
     "osc_corpus_destroy": (C.c_int, [Handle]),
     "osc_corpus_last_error": (C.c_char_p, [Handle]),

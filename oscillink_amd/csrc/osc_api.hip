@@ -1325,6 +1325,25 @@ int osc_bundle_prior_many(osc_handle h, const float* psis, int32_t Q, const int6
   });
 }
 
+int osc_receipt_prior_many(osc_handle h, const float* psis, int32_t Q, const int64_t* chain_offsets,
+                           const int32_t* chain_nodes, const float* chain_weights, float lamP, float tol, int32_t max_iters,
+                           int32_t detail, float z_th, int32_t null_cap, double* dH, double* coh_sum, double* anchor_sum,
+                           double* query_sum, int32_t* null_total, int64_t* null_offsets, int32_t* i_out, int32_t* j_out,
+                           float* z_out, float* r_out, int64_t capacity, float* prior_res, int32_t* prior_iters) {
+  return guarded(h, [&](L& l) {
+    if (Q < 0) throw Invalid("osc_receipt_prior_many: Q must be >= 0");
+    if (capacity < 0) throw Invalid("osc_receipt_prior_many: capacity must be >= 0");
+    if (Q > 0 && (!psis || !chain_offsets || !chain_nodes || !dH || !coh_sum || !anchor_sum || !query_sum || !null_total ||
+                  !null_offsets || !prior_res || !prior_iters))
+      throw Invalid("osc_receipt_prior_many: NULL buffer");
+    for (int64_t i = 0; i < (int64_t)Q * l.D; ++i)
+      if (!std::isfinite(psis[i])) throw Invalid("osc_receipt_prior_many: non-finite query");
+    query_receipt_prior_many(l, psis, Q, chain_offsets, chain_nodes, chain_weights, lamP, tol, max_iters, detail, z_th, null_cap,
+                             dH, coh_sum, anchor_sum, query_sum, null_total, null_offsets, i_out, j_out, z_out, r_out, capacity,
+                             prior_res, prior_iters);
+  });
+}
+
 int osc_mmr_many(osc_handle h, const float* scores, int32_t Q, int32_t k, float lambda_div, int32_t* out_idx) {
   return guarded(h, [&](L& l) {
     if (Q < 0) throw Invalid("osc_mmr_many: Q must be >= 0");

@@ -39,6 +39,7 @@
 #include "gates_many.hpp"
 #include "chain_prior_plan.hpp"
 #include "bundle_prior_plan.hpp"
+#include "receipt_prior_plan.hpp"
 
 using namespace osc;
 
@@ -353,6 +354,13 @@ struct osc_lattice {
       uint64_t gen = 0, stats_gen = 0;
       DevBuf<float> s;
       DevBuf<double> xn2, c0, c2;
+      // osc_receipt_prior_many: section 12's per-basis terms on (X', x') and M', under the same gen
+      uint64_t rm_gen = 0, rd_gen = 0;
+      DevBuf<double> Mx;           // [N] M' x'
+      DevBuf<float> dslot;         // [N * width] |P'_i - P'_j|^2 per ELL slot
+      std::vector<double> rm_vec;  // 4 x D, as QueryState's
+      double rm_a0 = 0, rm_b0 = 0, rm_a2 = 0, rm_b2 = 0, rm_h2 = 0;
+      DevBuf<double> rp_base;      // one call's [8 scalars | h1' | a1 | b1] for k_rp_scalars
     } shifted;
     DevBuf<char> cp_scratch;     // one pass's panels and per-column scalars (chain_prior_plan.hpp: ChainPriorLayout)
     DevBuf<float> cp_diag;       // [N] d_i = lamG + lamP + lamC + lamQ B_i
@@ -508,6 +516,12 @@ void query_bundle_prior_many(L& l, const float* psis, int32_t Q, const int64_t* 
                              const float* chain_weights, float lamP, float tol, int32_t max_iters, int32_t k, float alpha,
                              float lambda_div, int32_t* ids, float* score, float* align, float* prior_res,
                              int32_t* prior_iters);
+// osc_receipt_prior_many
+void query_receipt_prior_many(L& l, const float* psis, int32_t Q, const int64_t* chain_offsets, const int32_t* chain_nodes,
+                              const float* chain_weights, float lamP, float tol, int32_t max_iters, int32_t detail, float z_th,
+                              int32_t null_cap, double* dH, double* coh_sum, double* anchor_sum, double* query_sum,
+                              int32_t* null_total, int64_t* null_offsets, int32_t* i_out, int32_t* j_out, float* z_out,
+                              float* r_out, int64_t capacity, float* prior_res, int32_t* prior_iters);
 void query_bundle_many(L& l, const float* psis, int32_t Q, int32_t k, float alpha, float lambda_div, int32_t* ids,
                        float* score, float* align);
 void query_mmr_many(L& l, const float* scores, int32_t Q, int32_t k, float lambda_div, int32_t* ids);

@@ -354,8 +354,10 @@ size_t rm_sum_size(const L& l) { return std::max<size_t>((size_t)4 * l.ld + 3, k
 
 // the per-basis terms: M x, the D-vectors of the anchor / query sums and the scalars beside them; with full != 0 also the
 // per-slot |P_i - P_j|^2 of the null-point residuals
-void ensure_receipt_basis(L& l, bool full) {
-  auto& q = l.query;
+// (q: the slot of the basis -- l.query with the handle's operator, l.query.shifted with M'; sc: the scratch, l.query)
+template <class Slot>
+void ensure_receipt_terms(L& l, Slot& q, const OpParams& op, bool full) {
+  auto& sc = l.query;
   const bool need_sums = q.rm_gen != q.gen, need_d = full && q.rd_gen != q.gen;
   if (!need_sums && !need_d) return;
   const size_t n = (size_t)l.N;
@@ -366,7 +368,7 @@ void ensure_receipt_basis(L& l, bool full) {
   b.sqrt_deg = l.sqrt_deg.p;
   b.g = graph_view(l, path_active(l));
   b.adj = l.ell_a.p;
-  b.op = ustar_op(l);
+  b.op = op;
   b.N = (int32_t)l.N;
   b.D = l.D;
   b.ld = l.ld;
@@ -389,17 +391,17 @@ void ensure_receipt_basis(L& l, bool full) {
   c.D = l.D;
   c.ld = l.ld;
   c.nb = rm_col_parts(l.N);
-  q.rpart.alloc((size_t)c.nb * 4 * l.ld);
-  q.rspart.alloc((size_t)c.nb * 3);
-  q.rsum.alloc(rm_sum_size(l));
-  c.part = q.rpart.p;
-  c.spart = q.rspart.p;
+  sc.rpart.alloc((size_t)c.nb * 4 * l.ld);
+  sc.rspart.alloc((size_t)c.nb * 3);
+  sc.rsum.alloc(rm_sum_size(l));
+  c.part = sc.rpart.p;
+  c.spart = sc.rspart.p;
   launch_rm_cols(c, 0, l.stream);
-  q.rfin.alloc((size_t)rm_finish_groups(c.nb) * 4 * l.ld);
-  launch_rm_colfinish(q.rpart.p, c.nb, (int64_t)4 * l.ld, q.rsum.p, q.rfin.p, l.stream);
-  launch_rm_colfinish(q.rspart.p, c.nb, 3, q.rsum.p + (size_t)4 * l.ld, q.rfin.p, l.stream);
+  sc.rfin.alloc((size_t)rm_finish_groups(c.nb) * 4 * l.ld);
+  launch_rm_colfinish(sc.rpart.p, c.nb, (int64_t)4 * l.ld, sc.rsum.p, sc.rfin.p, l.stream);
+  launch_rm_colfinish(sc.rspart.p, c.nb, 3, sc.rsum.p + (size_t)4 * l.ld, sc.rfin.p, l.stream);
   std::vector<double> h((size_t)4 * l.ld + 3);
-  HIP_CHECK(hipMemcpyAsync(h.data(), q.rsum.p, h.size() * 8, hipMemcpyDeviceToHost, l.stream));
+  HIP_CHECK(hipMemcpyAsync(h.data(), sc.rsum.p, h.size() * 8, hipMemcpyDeviceToHost, l.stream));
   sync(l);
   q.rm_vec.assign((size_t)4 * l.D, 0.0);
   for (int k = 0; k < 4; ++k)
@@ -415,10 +417,91 @@ void ensure_receipt_basis(L& l, bool full) {
   q.rm_gen = q.gen;
 }
 
+void ensure_receipt_basis(L& l, bool full) { ensure_receipt_terms(l, l.query, ustar_op(l), full); }
+
 double dot_f(const float* a, const double* b, int32_t D) {
   double s = 0.0;
   for (int32_t d = 0; d < D; ++d) s += (double)a[d] * b[d];
   return s;
+}
+
+}  // namespace
+
+namespace {
+
+// The tail of a full-detail chunk, shared by osc_receipt_many and osc_receipt_prior_many: from the counted null points of the
+// chunk's nq queries (tot; zt = z per query in API row order, rj / rr the N x qs candidates) the kept records of each query
+// -- every null point, or the cap highest z -- into the caller's arrays at null_offsets.
+void receipt_null_stage(L& l, const char* fn, int32_t c0, int32_t nq, int32_t qs, int32_t null_cap,
+                        const std::vector<int32_t>& tot, const float* zt, const int32_t* rj, const float* rr,
+                        int32_t* null_total, int64_t* null_offsets, int32_t* i_out, int32_t* j_out, float* z_out, float* r_out,
+                        int64_t capacity) {
+  auto& q = l.query;
+  const int32_t N = (int32_t)l.N;
+  const int32_t* inv = permuted(l) ? l.inv_d.p : nullptr;
+  std::vector<int32_t> sel, hi, hj;
+  std::vector<int64_t> off;
+  std::vector<float> hz, hr;
+  // kept per query: every null point, or the cap highest z (selected on the device up to kRmSelectMax, else here)
+  sel.assign((size_t)nq, 0);
+  off.assign((size_t)nq, 0);
+  int64_t dev_n = 0;
+  for (int32_t t = 0; t < nq; ++t) {
+    null_total[c0 + t] = tot[(size_t)t];
+    const bool capped = null_cap > 0 && tot[(size_t)t] > null_cap;
+    sel[(size_t)t] = capped && null_cap <= kRmSelectMax;
+    off[(size_t)t] = dev_n;
+    dev_n += sel[(size_t)t] ? null_cap : tot[(size_t)t];
+    const int64_t kept = capped ? null_cap : tot[(size_t)t];
+    null_offsets[c0 + t + 1] = null_offsets[c0 + t] + kept;
+  }
+  if (null_offsets[c0 + nq] > capacity) throw Invalid(std::string(fn) + ": capacity too small for the null points");
+  if (dev_n == 0) return;
+  q.roi.alloc((size_t)dev_n);
+  q.roj.alloc((size_t)dev_n);
+  q.roz.alloc((size_t)dev_n);
+  q.ror.alloc((size_t)dev_n);
+  HIP_CHECK(hipMemcpyAsync(q.roff.p, off.data(), (size_t)nq * 8, hipMemcpyHostToDevice, l.stream));
+  HIP_CHECK(hipMemcpyAsync(q.rsel.p, sel.data(), (size_t)nq * 4, hipMemcpyHostToDevice, l.stream));
+  RmSelectArgs sa{};
+  sa.zt = zt;
+  sa.j = rj;
+  sa.r = rr;
+  sa.inv = inv;
+  sa.off = q.roff.p;
+  sa.sel = q.rsel.p;
+  sa.N = N;
+  sa.qs = qs;
+  sa.nq = nq;
+  sa.cap = null_cap;
+  sa.oi = q.roi.p;
+  sa.oj = q.roj.p;
+  sa.oz = q.roz.p;
+  sa.orr = q.ror.p;
+  launch_rm_null_select(sa, l.stream);
+  hi.resize((size_t)dev_n);
+  hj.resize((size_t)dev_n);
+  hz.resize((size_t)dev_n);
+  hr.resize((size_t)dev_n);
+  HIP_CHECK(hipMemcpyAsync(hi.data(), q.roi.p, (size_t)dev_n * 4, hipMemcpyDeviceToHost, l.stream));
+  HIP_CHECK(hipMemcpyAsync(hj.data(), q.roj.p, (size_t)dev_n * 4, hipMemcpyDeviceToHost, l.stream));
+  HIP_CHECK(hipMemcpyAsync(hz.data(), q.roz.p, (size_t)dev_n * 4, hipMemcpyDeviceToHost, l.stream));
+  HIP_CHECK(hipMemcpyAsync(hr.data(), q.ror.p, (size_t)dev_n * 4, hipMemcpyDeviceToHost, l.stream));
+  sync(l);
+  for (int32_t t = 0; t < nq; ++t) {
+    const int64_t src = off[(size_t)t], dst = null_offsets[c0 + t], kept = null_offsets[c0 + t + 1] - dst;
+    std::vector<int64_t> order((size_t)(sel[(size_t)t] ? kept : tot[(size_t)t]));
+    for (size_t k = 0; k < order.size(); ++k) order[k] = src + (int64_t)k;
+    if (!sel[(size_t)t] && kept < (int64_t)order.size())  // a cap above the device selection's: the stable z sort here
+      std::stable_sort(order.begin(), order.end(), [&](int64_t x, int64_t y) { return hz[(size_t)x] > hz[(size_t)y]; });
+    for (int64_t k = 0; k < kept; ++k) {
+      const size_t s = (size_t)order[(size_t)k];
+      if (i_out) i_out[dst + k] = hi[s];
+      if (j_out) j_out[dst + k] = hj[s];
+      if (z_out) z_out[dst + k] = hz[s];
+      if (r_out) r_out[dst + k] = hr[s];
+    }
+  }
 }
 
 }  // namespace
@@ -501,9 +584,7 @@ void query_receipt_many(L& l, const float* psis, int32_t Q, int32_t detail, floa
   const int32_t* inv = permuted(l) ? l.inv_d.p : nullptr;
   std::vector<float> bt;
   std::vector<double> pn2, pinv, csum;
-  std::vector<int32_t> tot, sel, hi, hj;
-  std::vector<int64_t> off;
-  std::vector<float> hz, hr;
+  std::vector<int32_t> tot;
   for (int32_t c0 = 0; c0 < Q; c0 += kQueryChunk) {
     const int32_t nq = std::min<int32_t>(kQueryChunk, Q - c0);
     const int32_t qs = query_qs(nq), qpad = query_qpad(nq);
@@ -578,67 +659,9 @@ void query_receipt_many(L& l, const float* psis, int32_t Q, int32_t detail, floa
     HIP_CHECK(hipMemcpyAsync(csum.data(), q.rsum.p, (size_t)nq * 8, hipMemcpyDeviceToHost, l.stream));
     HIP_CHECK(hipMemcpyAsync(tot.data(), q.rtot.p, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
     sync(l);
-    // kept per query: every null point, or the cap highest z (selected on the device up to kRmSelectMax, else here)
-    sel.assign((size_t)nq, 0);
-    off.assign((size_t)nq, 0);
-    int64_t dev_n = 0;
-    for (int32_t t = 0; t < nq; ++t) {
-      coh_sum[c0 + t] = csum[(size_t)t];
-      null_total[c0 + t] = tot[(size_t)t];
-      const bool capped = null_cap > 0 && tot[(size_t)t] > null_cap;
-      sel[(size_t)t] = capped && null_cap <= kRmSelectMax;
-      off[(size_t)t] = dev_n;
-      dev_n += sel[(size_t)t] ? null_cap : tot[(size_t)t];
-      const int64_t kept = capped ? null_cap : tot[(size_t)t];
-      null_offsets[c0 + t + 1] = null_offsets[c0 + t] + kept;
-    }
-    if (null_offsets[c0 + nq] > capacity) throw Invalid("osc_receipt_many: capacity too small for the null points");
-    if (dev_n == 0) continue;
-    q.roi.alloc((size_t)dev_n);
-    q.roj.alloc((size_t)dev_n);
-    q.roz.alloc((size_t)dev_n);
-    q.ror.alloc((size_t)dev_n);
-    HIP_CHECK(hipMemcpyAsync(q.roff.p, off.data(), (size_t)nq * 8, hipMemcpyHostToDevice, l.stream));
-    HIP_CHECK(hipMemcpyAsync(q.rsel.p, sel.data(), (size_t)nq * 4, hipMemcpyHostToDevice, l.stream));
-    RmSelectArgs sa{};
-    sa.zt = q.zt.p;
-    sa.j = q.rj.p;
-    sa.r = q.rr.p;
-    sa.inv = inv;
-    sa.off = q.roff.p;
-    sa.sel = q.rsel.p;
-    sa.N = N;
-    sa.qs = qs;
-    sa.nq = nq;
-    sa.cap = null_cap;
-    sa.oi = q.roi.p;
-    sa.oj = q.roj.p;
-    sa.oz = q.roz.p;
-    sa.orr = q.ror.p;
-    launch_rm_null_select(sa, l.stream);
-    hi.resize((size_t)dev_n);
-    hj.resize((size_t)dev_n);
-    hz.resize((size_t)dev_n);
-    hr.resize((size_t)dev_n);
-    HIP_CHECK(hipMemcpyAsync(hi.data(), q.roi.p, (size_t)dev_n * 4, hipMemcpyDeviceToHost, l.stream));
-    HIP_CHECK(hipMemcpyAsync(hj.data(), q.roj.p, (size_t)dev_n * 4, hipMemcpyDeviceToHost, l.stream));
-    HIP_CHECK(hipMemcpyAsync(hz.data(), q.roz.p, (size_t)dev_n * 4, hipMemcpyDeviceToHost, l.stream));
-    HIP_CHECK(hipMemcpyAsync(hr.data(), q.ror.p, (size_t)dev_n * 4, hipMemcpyDeviceToHost, l.stream));
-    sync(l);
-    for (int32_t t = 0; t < nq; ++t) {
-      const int64_t src = off[(size_t)t], dst = null_offsets[c0 + t], kept = null_offsets[c0 + t + 1] - dst;
-      std::vector<int64_t> order((size_t)(sel[(size_t)t] ? kept : tot[(size_t)t]));
-      for (size_t k = 0; k < order.size(); ++k) order[k] = src + (int64_t)k;
-      if (!sel[(size_t)t] && kept < (int64_t)order.size())  // a cap above the device selection's: the stable z sort here
-        std::stable_sort(order.begin(), order.end(), [&](int64_t x, int64_t y) { return hz[(size_t)x] > hz[(size_t)y]; });
-      for (int64_t k = 0; k < kept; ++k) {
-        const size_t s = (size_t)order[(size_t)k];
-        if (i_out) i_out[dst + k] = hi[s];
-        if (j_out) j_out[dst + k] = hj[s];
-        if (z_out) z_out[dst + k] = hz[s];
-        if (r_out) r_out[dst + k] = hr[s];
-      }
-    }
+    for (int32_t t = 0; t < nq; ++t) coh_sum[c0 + t] = csum[(size_t)t];
+    receipt_null_stage(l, "osc_receipt_many", c0, nq, qs, null_cap, tot, q.zt.p, q.rj.p, q.rr.p, null_total, null_offsets, i_out,
+                       j_out, z_out, r_out, capacity);
   }
 }
 
@@ -773,6 +796,12 @@ struct CpPanelOut {
   const int64_t* tv_at;       // [nq] into q.cp_tv
   float* prior_res;           // [nq]
   int32_t* prior_iters;       // [nq]
+  const int32_t* sys_rows;    // device row per (system, local node), beside sys_cols
+  const int32_t* k_at;        // [n_sys + 1] the systems' K entries: local row, local column, normalised path weight
+  const int32_t* kr;
+  const int32_t* kc;
+  const float* kw;
+  int32_t n_sys;
 };
 
 // The panel stage of one pass, shared by osc_chain_prior_many and osc_bundle_prior_many: the unit sources of the pass's
@@ -914,6 +943,12 @@ CpPanelOut chain_prior_panel_stage(L& l, const std::vector<int32_t>& cols, int32
   out.tv_at = ta.tv_at;
   out.prior_res = pres_d;
   out.prior_iters = pit_d;
+  out.sys_rows = sa.rows;
+  out.k_at = sa.k_at;
+  out.kr = sa.kr;
+  out.kc = sa.kc;
+  out.kw = sa.kw;
+  out.n_sys = (int32_t)ns;
   return out;
 }
 
@@ -1344,6 +1379,391 @@ void query_bundle_prior_many(L& l, const float* psis, int32_t Q, const int64_t* 
     HIP_CHECK(hipMemcpyAsync(score + off, q.out_score.p, m * 4, hipMemcpyDeviceToHost, l.stream));
     HIP_CHECK(hipMemcpyAsync(align + off, q.out_align.p, m * 4, hipMemcpyDeviceToHost, l.stream));
     sync(l);  // (the host vectors above are reused by the next pass)
+  }
+  q.cp_scratch.release();  // up to 1 GiB a pass: back to the allocator's pool, not kept on the handle between calls
+}
+
+// ---- receipts under per-query chain priors -----------------------------------------------------
+// receipt() of Q (query, chain) pairs, query q on the U* of M + lamP L_path,q (lattice.py:298-455 and receipts.py:10-83 after
+// lattice.py:129-150).  Per call h0' and h1' on the shifted slot; per pass (receipt_prior_plan.hpp) section 12.2's panel
+// stage and k_rp_scalars, and in full detail the moments of the Green's columns, the chains' Gram blocks, section 11.1's two
+// GEMMs, the fused row pass and section 12's null-point stage.  lamP == 0: osc_receipt_many on the resident basis.
+void query_receipt_prior_many(L& l, const float* psis, int32_t Q, const int64_t* chain_offsets, const int32_t* chain_nodes,
+                              const float* chain_weights, float lamP, float tol, int32_t max_iters, int32_t detail, float z_th,
+                              int32_t null_cap, double* dH, double* coh_sum, double* anchor_sum, double* query_sum,
+                              int32_t* null_total, int64_t* null_offsets, int32_t* i_out, int32_t* j_out, float* z_out,
+                              float* r_out, int64_t capacity, float* prior_res, int32_t* prior_iters) {
+  if (l.comm) throw Unsupported("osc_receipt_prior_many: lattices with a communicator are not supported");
+  require_graph(l);
+  if (!(lamP >= 0.f) || !std::isfinite(lamP)) throw Invalid("osc_receipt_prior_many: lamP must be a finite value >= 0");
+  if (!(tol > 0.f) || !std::isfinite(tol)) throw Invalid("osc_receipt_prior_many: tol must be > 0");
+  if (max_iters < 1) throw Invalid("max_iters must be >= 1");
+  if (l.chain_present) throw Invalid("osc_receipt_prior_many: the lattice has a chain of its own (osc_clear_chain first)");
+  const bool prior = lamP > 0.f;
+  auto& q = l.query;
+  auto& sh = q.shifted;
+  if (prior) {
+    if (!sh.have || sh.epoch != l.derived.epoch || sh.lamP != lamP)
+      throw StateError("no shifted query basis for this lamP and the current graph (call osc_query_basis_shifted first)");
+  } else {
+    require_basis(l);
+  }
+  if (Q <= 0) {
+    if (null_offsets) null_offsets[0] = 0;
+    return;
+  }
+  int32_t where = 0;
+  switch (host::chain_many_check(chain_offsets, chain_nodes, Q, l.N, &where)) {
+    case 1:
+      throw Invalid("osc_receipt_prior_many: query " + std::to_string(where) + ": a chain has 2 to " +
+                    std::to_string(host::kCorpusMaxChain) + " nodes, at offsets that start from 0");
+    case 2:
+      throw Invalid("osc_receipt_prior_many: query " + std::to_string(where) + ": chain indices out of bounds");
+  }
+  where = host::chain_prior_check(chain_offsets, chain_nodes, Q);
+  if (where >= 0)
+    throw Invalid("osc_receipt_prior_many: query " + std::to_string(where) + ": a chain has at most " +
+                  std::to_string(host::kChainPriorMaxNodes) + " distinct nodes");
+  if (chain_weights)
+    for (int64_t e = 0; e < host::chain_many_edge_at(chain_offsets, Q); ++e)
+      if (!std::isfinite(chain_weights[e])) throw Invalid("osc_receipt_prior_many: non-finite chain weight");
+  const int32_t N = (int32_t)l.N, D = l.D;
+  const size_t n = (size_t)l.N;
+  const float res_X = prior ? sh.res_X : q.res_X, res_x = prior ? sh.res_x : q.res_x;
+  auto base_res = [&](int32_t t) {  // the basis's own residual for query t: |r_X| + |psi_t|_inf |r_x|
+    float pinf = 0.f;
+    for (int32_t d = 0; d < D; ++d) pinf = std::max(pinf, std::fabs(psis[(size_t)t * D + d]));
+    return res_X + pinf * res_x;
+  };
+  if (!prior) {
+    query_receipt_many(l, psis, Q, detail, z_th, null_cap, dH, coh_sum, anchor_sum, query_sum, null_total, null_offsets, i_out,
+                       j_out, z_out, r_out, capacity);
+    for (int32_t t = 0; t < Q; ++t) {
+      prior_res[t] = base_res(t);
+      prior_iters[t] = 0;
+    }
+    return;
+  }
+  const bool full = detail != 0;
+  // the shifted slot's per-basis terms (section 12's, with lamG + lamP in lamG's place) and, full detail, its row constants
+  const float lamG0 = l.lamG;
+  OpParams op{};
+  l.lamG = lamG0 + lamP;
+  op = ustar_op(l);
+  l.lamG = lamG0;
+  ensure_receipt_terms(l, sh, op, full);
+  if (full) ensure_shifted_stats(l);
+  // per call: h1' = E0'^T (M' x') over E0' = U - X' - x' psi0^T, and h0' = tr(E0'^T M' E0') through the operator's quad form
+  std::vector<float> psi0((size_t)l.ld, 0.f);
+  HIP_CHECK(hipMemcpyAsync(psi0.data(), l.psi.p, (size_t)l.ld * 4, hipMemcpyDeviceToHost, l.stream));
+  RmColArgs c{};
+  c.X = sh.X.p;
+  c.x4 = sh.x4.p;
+  c.Mx = sh.Mx.p;
+  c.U = u_read(l);
+  c.psi0 = l.psi.p;
+  q.U0.alloc(n * l.ld);
+  c.U0 = q.U0.p;
+  c.N = N;
+  c.D = D;
+  c.ld = l.ld;
+  c.nb = rm_col_parts(l.N);
+  q.rpart.alloc((size_t)c.nb * 4 * l.ld);
+  q.rsum.alloc(rm_sum_size(l));
+  c.part = q.rpart.p;
+  launch_rm_cols(c, 1, l.stream);
+  q.rfin.alloc((size_t)rm_finish_groups(c.nb) * 4 * l.ld);
+  launch_rm_colfinish(q.rpart.p, c.nb, l.ld, q.rsum.p, q.rfin.p, l.stream);
+  std::vector<double> h1((size_t)l.ld);
+  HIP_CHECK(hipMemcpyAsync(h1.data(), q.rsum.p, h1.size() * 8, hipMemcpyDeviceToHost, l.stream));
+  sync(l);
+  double h0 = 0.0;
+  l.lamG = lamG0 + lamP;
+  try {
+    h0 = quad_form_of_difference(l, u_read(l), q.U0.p);
+  } catch (...) {
+    l.lamG = lamG0;
+    throw;
+  }
+  l.lamG = lamG0;
+  std::vector<double> hbase((size_t)8 + 3 * (size_t)D, 0.0);
+  hbase[0] = h0;
+  hbase[1] = sh.rm_h2;
+  hbase[2] = sh.rm_a0;
+  hbase[3] = sh.rm_a2;
+  hbase[4] = sh.rm_b0;
+  hbase[5] = sh.rm_b2;
+  hbase[6] = (double)l.lamG;
+  hbase[7] = (double)l.lamQ;
+  for (int32_t d = 0; d < D; ++d) {
+    hbase[(size_t)8 + d] = h1[(size_t)d];
+    hbase[(size_t)8 + D + d] = sh.rm_vec[(size_t)d];
+    hbase[(size_t)8 + 2 * D + d] = sh.rm_vec[(size_t)D + d];
+  }
+  sh.rp_base.alloc(hbase.size());
+  HIP_CHECK(hipMemcpyAsync(sh.rp_base.p, hbase.data(), hbase.size() * 8, hipMemcpyHostToDevice, l.stream));
+  const int32_t kpad = query_kpad(D);
+  const int32_t* dev = permuted(l) ? l.inv_h.data() : nullptr;
+  const int32_t* inv = permuted(l) ? l.inv_d.p : nullptr;
+  const int cparts = rm_col_parts(l.N), cgroups = rm_finish_groups(cparts);
+  int max_cols = 0;
+  env_num("OSC_CHAIN_PRIOR_COLS", max_cols);
+  const std::vector<host::ReceiptPriorPass> passes =
+      host::receipt_prior_passes(chain_offsets, chain_nodes, Q, N, kpad, l.ld, full, cparts, cgroups, kQueryChunk, max_cols,
+                                 host::kChainPriorBudgetBytes);
+  GmRowOp rop{};
+  const GmGraph g{l.ell_col.p, l.ell_w.p, l.deg.p, l.width};
+  q.cp_diag.alloc((size_t)N);
+  launch_gm_row_diag(l.B.p, l.lamG + lamP + l.lamC, l.lamQ, N, q.cp_diag.p, l.stream);
+  rop.d = q.cp_diag.p;
+  rop.lamC = l.lamC;
+  const float tol_g = host::chain_prior_tol_g(tol, l.lamG, lamP, sh.max_X + sh.max_x * sh.scale);
+  q.pn2.alloc(kQueryChunk);
+  q.pinv.alloc(kQueryChunk);
+  if (full) {
+    q.Bt.alloc((size_t)query_qpad(kQueryChunk) * kpad);
+    q.rtot.alloc(kQueryChunk);
+    q.rsel.alloc(kQueryChunk);
+    q.roff.alloc(kQueryChunk);
+  }
+  const int32_t parts = host::gates_parts(N), part_rows = host::gates_part_rows(N);
+  host::ChainManyPaths paths;
+  CpHostScratch hs;
+  std::vector<host::ChainManyUnit> units;
+  std::vector<int32_t> eoff, path_of, tot;
+  std::vector<float> hpsi, hflts, bt;
+  std::vector<double> pn2, pinv, hscal, csum;
+  std::vector<int64_t> hgat;
+  DevBuf<int64_t> gat;
+  null_offsets[0] = 0;
+  for (const host::ReceiptPriorPass& ps : passes) {
+    const int32_t c0 = ps.q0, nq = ps.nq;
+    paths.clear();
+    host::chain_many_units_weighted(chain_offsets, chain_nodes, chain_weights, c0, nq, dev, N, paths, units, eoff, path_of);
+    const int32_t qs = query_qs(nq), qpad = query_qpad(nq);
+    hpsi.assign((size_t)nq * l.ld, 0.f);
+    if (full) bt.assign((size_t)qpad * kpad, 0.f);
+    pn2.assign((size_t)nq, 0.0);
+    pinv.assign((size_t)nq, 0.0);
+    hflts.assign((size_t)nq, 0.f);
+    for (int32_t t = 0; t < nq; ++t) {
+      const float* p = psis + (size_t)(c0 + t) * D;
+      double s = 0.0;
+      for (int32_t d = 0; d < D; ++d) {
+        hpsi[(size_t)t * l.ld + d] = p[d];
+        if (full) bt[(size_t)t * kpad + d] = p[d];
+        s += (double)p[d] * (double)p[d];
+      }
+      pn2[(size_t)t] = s;
+      pinv[(size_t)t] = 1.0 / (std::sqrt(s) + 1e-12);
+      hflts[(size_t)t] = base_res(c0 + t);
+    }
+    q.cm_psi.alloc(hpsi.size());
+    HIP_CHECK(hipMemcpyAsync(q.cm_psi.p, hpsi.data(), hpsi.size() * 4, hipMemcpyHostToDevice, l.stream));
+    if (full) HIP_CHECK(hipMemcpyAsync(q.Bt.p, bt.data(), bt.size() * 4, hipMemcpyHostToDevice, l.stream));
+    HIP_CHECK(hipMemcpyAsync(q.pn2.p, pn2.data(), (size_t)nq * 8, hipMemcpyHostToDevice, l.stream));
+    HIP_CHECK(hipMemcpyAsync(q.pinv.p, pinv.data(), (size_t)nq * 8, hipMemcpyHostToDevice, l.stream));
+    const host::ReceiptPriorLayout lay =
+        host::receipt_prior_layout(N, ps.qc, ps.msum, ps.msq, nq, kpad, l.ld, full, cparts, cgroups);
+    q.cp_scratch.alloc((size_t)lay.total);
+    const CpPanelOut po = chain_prior_panel_stage(l, ps.cols, ps.qc, nq, paths, path_of, hflts, dev, sh.X.p, sh.x4.p, lamP,
+                                                  tol_g, max_iters, rop, g, hs);
+    // where each system's m x m Gram entries start (their sum is at most the pass's msq: distinct systems, one query each at least)
+    hgat.assign(hs.sys.m.size(), 0);
+    int64_t gtot = 0;
+    for (size_t sy = 0; sy < hs.sys.m.size(); ++sy) {
+      hgat[sy] = gtot;
+      gtot += (int64_t)hs.sys.m[sy] * hs.sys.m[sy];
+    }
+    if (gtot > ps.msq) throw Invalid("osc_receipt_prior_many: the pass's Gram blocks exceed its plan");
+    gat.alloc(std::max<size_t>(hgat.size(), 1));
+    HIP_CHECK(hipMemcpyAsync(gat.p, hgat.data(), hgat.size() * 8, hipMemcpyHostToDevice, l.stream));
+    char* const base = q.cp_scratch.p;
+    BpArgs b{};
+    b.col = l.ell_col.p;
+    b.adj = l.ell_a.p;
+    b.deg = l.deg.p;
+    b.width = l.width;
+    b.N = N;
+    b.lamC = l.lamC;
+    b.sqrt_deg = l.sqrt_deg.p;
+    b.G = po.G;
+    b.TV = q.cp_tv.p;
+    b.psi = q.cm_psi.p;
+    b.q_sys = po.q_sys;
+    b.sys_m = po.sys_m;
+    b.sys_col_at = po.sys_col_at;
+    b.sys_cols = po.sys_cols;
+    b.tv_at = po.tv_at;
+    b.pn2 = q.pn2.p;
+    b.pinv = q.pinv.p;
+    b.D = D;
+    b.ld = l.ld;
+    b.qs = qs;
+    b.nq = nq;
+    b.gs = host::bundle_prior_group(ps.mmax);
+    b.e = reinterpret_cast<double*>(base + lay.e);
+    b.H = reinterpret_cast<double*>(base + lay.H);
+    launch_bp_scalars(b, l.stream);
+    double* const scal = reinterpret_cast<double*>(base + lay.scal);
+    RpScalArgs sa{};
+    sa.U = u_read(l);
+    sa.X = sh.X.p;
+    sa.x4 = sh.x4.p;
+    sa.psi0 = l.psi.p;
+    sa.sys_rows = po.sys_rows;
+    sa.k_at = po.k_at;
+    sa.kr = po.kr;
+    sa.kc = po.kc;
+    sa.kw = po.kw;
+    sa.lamP = lamP;
+    sa.base = sh.rp_base.p;
+    sa.full = full ? 1 : 0;
+    sa.g_at = gat.p;
+    sa.msq = ps.msq;
+    sa.res_in = po.prior_res;
+    sa.iters_in = po.prior_iters;
+    sa.J = reinterpret_cast<double*>(base + lay.J);
+    sa.Z = reinterpret_cast<double*>(base + lay.Z);
+    sa.scal = scal;
+    sa.res_out = reinterpret_cast<float*>(scal + (size_t)4 * nq);
+    sa.iters_out = reinterpret_cast<int32_t*>(sa.res_out + nq);
+    if (full) {
+      // the moments of the pass's Green's columns, mom_slabs slabs of partials at a time, and the chains' Gram blocks
+      RpMomArgs ma{};
+      ma.G = po.G;
+      ma.X = sh.X.p;
+      ma.x4 = sh.x4.p;
+      ma.Y = l.Y.p;
+      ma.B = l.B.p;
+      ma.N = N;
+      ma.D = D;
+      ma.ld = l.ld;
+      ma.parts = parts;
+      ma.part_rows = part_rows;
+      ma.wout = lay.wout;
+      ma.part = reinterpret_cast<float*>(base + lay.mom_part);
+      double* const mom = reinterpret_cast<double*>(base + lay.mom);
+      const int32_t slabs = ps.qc / host::kGatesSlab;
+      for (int32_t s0 = 0; s0 < slabs; s0 += lay.mom_slabs) {
+        ma.slab0 = s0;
+        ma.nslab = std::min(lay.mom_slabs, slabs - s0);
+        launch_rp_moments(ma, l.stream);
+        launch_rp_moments_finish(ma.part, parts, s0, ma.nslab, lay.wout, mom, l.stream);
+      }
+      RpGramArgs ga{};
+      ga.G = po.G;
+      ga.B = l.B.p;
+      ga.sys_m = po.sys_m;
+      ga.sys_col_at = po.sys_col_at;
+      ga.sys_cols = po.sys_cols;
+      ga.g_at = gat.p;
+      ga.N = N;
+      ga.n_sys = po.n_sys;
+      ga.parts = parts;
+      ga.part_rows = part_rows;
+      ga.groups = lay.groups;
+      ga.per = host::receipt_prior_gram_group_parts(N);
+      ga.msq = ps.msq;
+      ga.part = reinterpret_cast<double*>(base + lay.gram_part);
+      launch_rp_gram(ga, l.stream);
+      sa.mom = mom;
+      sa.wout = lay.wout;
+      sa.gram_part = ga.part;
+      sa.groups = lay.groups;
+      // kappa and p on the shifted basis (section 11.1), nu per (row, query)
+      float* const kappa = reinterpret_cast<float*>(base + lay.kappa);
+      float* const btk = reinterpret_cast<float*>(base + lay.bt);
+      q.align.alloc(n * qs);
+      q.pm.alloc(n * qs);
+      launch_bp_pack(q.cp_tv.p, ps.msum, query_qpad((int32_t)ps.msum), D, l.ld, kpad, btk, l.stream);
+      QueryGemmArgs gk{};
+      gk.A = sh.X.p;
+      gk.Bt = btk;
+      gk.N = N;
+      gk.D = D;
+      gk.ld = l.ld;
+      gk.kpad = kpad;
+      gk.qs = lay.ks;
+      gk.nq = (int32_t)ps.msum;
+      gk.mode = 2;
+      gk.sqrt_deg = l.sqrt_deg.p;
+      gk.p = kappa;
+      launch_query_gemm(gk, l.stream);
+      QueryGemmArgs gp{};
+      gp.A = sh.X.p;
+      gp.Bt = q.Bt.p;
+      gp.N = N;
+      gp.D = D;
+      gp.ld = l.ld;
+      gp.kpad = kpad;
+      gp.qs = qs;
+      gp.nq = nq;
+      gp.mode = 0;
+      gp.x4 = sh.x4.p;
+      gp.xn2 = sh.xn2.p;
+      gp.sqrt_deg = l.sqrt_deg.p;
+      gp.pn2 = q.pn2.p;
+      gp.pinv = q.pinv.p;
+      gp.align = q.align.p;
+      gp.p = q.pm.p;
+      launch_query_gemm(gp, l.stream);
+      b.s = sh.s.p;
+      b.xn2 = sh.xn2.p;
+      b.c0 = sh.c0.p;
+      b.c2 = sh.c2.p;
+      b.p = q.pm.p;
+      b.kappa = kappa;
+      b.ks = lay.ks;
+      b.nu = reinterpret_cast<double*>(base + lay.nu);
+      b.align = q.align.p;
+      launch_bp_rows_self(b, l.stream);
+    }
+    sa.b = b;
+    launch_rp_scalars(sa, l.stream);
+    hscal.assign((size_t)4 * nq, 0.0);
+    HIP_CHECK(hipMemcpyAsync(hscal.data(), scal, hscal.size() * 8, hipMemcpyDeviceToHost, l.stream));
+    HIP_CHECK(hipMemcpyAsync(prior_res + c0, sa.res_out, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
+    HIP_CHECK(hipMemcpyAsync(prior_iters + c0, sa.iters_out, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
+    if (!full) {
+      sync(l);
+      for (int32_t t = 0; t < nq; ++t) {
+        dH[c0 + t] = hscal[(size_t)4 * t];
+        anchor_sum[c0 + t] = query_sum[c0 + t] = coh_sum[c0 + t] = 0.0;
+        null_total[c0 + t] = 0;
+        null_offsets[c0 + t + 1] = null_offsets[c0 + t];
+      }
+      continue;
+    }
+    RpRowsArgs ra{};
+    ra.b = b;
+    ra.dslot = sh.dslot.p;
+    ra.api_id = permuted(l) ? l.perm_d.p : nullptr;
+    ra.z_th = z_th;
+    ra.cohd = reinterpret_cast<double*>(base + lay.coh);
+    ra.z = reinterpret_cast<float*>(base + lay.z);
+    ra.j = reinterpret_cast<int32_t*>(base + lay.j);
+    ra.r = reinterpret_cast<float*>(base + lay.r);
+    launch_rp_rows(ra, l.stream);
+    double* const cohpart = reinterpret_cast<double*>(base + lay.cohpart);
+    float* const zt = reinterpret_cast<float*>(base + lay.zt);
+    launch_rp_colsum(ra.cohd, N, qs, nq, cparts, cohpart, l.stream);
+    launch_rm_colfinish(cohpart, cparts, nq, q.rsum.p, reinterpret_cast<double*>(base + lay.cohfin), l.stream);
+    launch_rm_transpose(ra.z, inv, N, qs, nq, zt, l.stream);
+    launch_rm_null_count(zt, N, nq, q.rtot.p, l.stream);
+    csum.assign((size_t)nq, 0.0);
+    tot.assign((size_t)nq, 0);
+    HIP_CHECK(hipMemcpyAsync(csum.data(), q.rsum.p, (size_t)nq * 8, hipMemcpyDeviceToHost, l.stream));
+    HIP_CHECK(hipMemcpyAsync(tot.data(), q.rtot.p, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
+    sync(l);
+    for (int32_t t = 0; t < nq; ++t) {
+      dH[c0 + t] = hscal[(size_t)4 * t];
+      anchor_sum[c0 + t] = hscal[(size_t)4 * t + 1];
+      query_sum[c0 + t] = hscal[(size_t)4 * t + 2];
+      coh_sum[c0 + t] = csum[(size_t)t];
+    }
+    receipt_null_stage(l, "osc_receipt_prior_many", c0, nq, qs, null_cap, tot, zt, ra.j, ra.r, null_total, null_offsets, i_out,
+                       j_out, z_out, r_out, capacity);
   }
   q.cp_scratch.release();  // up to 1 GiB a pass: back to the allocator's pool, not kept on the handle between calls
 }

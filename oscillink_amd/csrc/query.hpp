@@ -239,6 +239,93 @@ void launch_rm_null_select(const RmSelectArgs& a, hipStream_t s);
 
 }  // namespace osc
 
+// ---- receipts under per-query chain priors: receipt_prior_kernels.hip -----------------------
+namespace osc {
+
+// The moments of the Green's columns: per 32-column slab of the slab-major panel and per row part (gates_many_plan.hpp),
+//   part[(sl * parts + p) * 32 + c][w] = sum over the part's rows of G[i, 32 (slab0 + sl) + c] V[i, w],
+//   V_i = [X'_i - Y_i | B_i X'_i | x'_i | B_i (x'_i - 1)]  (wout = 2 ld + 2 columns; zeros at and past D in both blocks)
+// on v_mfma_f32_32x32x2_f32, the rows of a part in order.  launch_rp_moments_finish adds the parts in fp64 in part order into
+// mom[32 (slab0 + sl) + c][w].  A column's moments depend on its own column and N alone.
+struct RpMomArgs {
+  const float* G;   // slab-major panel
+  const float* X;   // the shifted basis, N x ld
+  const float* x4;
+  const float* Y;
+  const float* B;
+  int32_t N, D, ld, parts, part_rows, slab0, nslab, wout;
+  float* part;
+};
+void launch_rp_moments(const RpMomArgs& a, hipStream_t s);
+void launch_rp_moments_finish(const float* part, int32_t parts, int32_t slab0, int32_t nslab, int32_t wout, double* mom,
+                              hipStream_t s);
+
+// Gamma_A = G^T G and Gamma_B = G^T diag(B) G on the m columns of every chain system of a pass: per run of `per` consecutive
+// parts, part[(grp * 2 + k) * msq + g_at[sys] + b * m + c] in fp64 (a part's rows in order, then the parts in order)
+struct RpGramArgs {
+  const float* G;
+  const float* B;
+  const int32_t* sys_m;
+  const int32_t* sys_col_at;
+  const int32_t* sys_cols;
+  const int64_t* g_at;   // [n_sys]
+  int32_t N, n_sys, parts, part_rows, groups, per;
+  int64_t msq;
+  double* part;
+};
+void launch_rp_gram(const RpGramArgs& a, hipStream_t s);
+
+// One workgroup per query: deltaH under M_q = M' - S K S^T by the identity of section 12.3 and, in full detail, the anchor
+// and query sums.  base = [h0', h2', a0, a2, b0, b2, lamG, lamQ | h1' (D) | a1 (D) | b1 (D)] of the shifted slot and the call.
+struct RpScalArgs {
+  BpArgs b;              // TV, psi, q_sys, sys_*, tv_at, e, H (launch_bp_scalars has run), G, N, D, ld, nq
+  const float* U;        // the state, N x ld
+  const float* X;        // X'
+  const float* x4;
+  const float* psi0;     // [ld]
+  const int32_t* sys_rows;  // device row per (system, local node), at sys_col_at
+  const int32_t* k_at;   // [n_sys + 1] the systems' K entries
+  const int32_t* kr;
+  const int32_t* kc;
+  const float* kw;
+  float lamP;
+  const double* base;
+  int32_t full;
+  const double* mom;     // [qc][wout]
+  int32_t wout;
+  const double* gram_part;
+  const int64_t* g_at;
+  int32_t groups;
+  int64_t msq;
+  const float* res_in;   // [nq] k_cp_tv's bound and iterations
+  const int32_t* iters_in;
+  double* J;             // [nq][64][64]
+  double* Z;
+  double* scal;          // [nq][4]: deltaH, anchor sum, query sum
+  float* res_out;
+  int32_t* iters_out;
+};
+void launch_rp_scalars(const RpScalArgs& a, hipStream_t s);
+
+// The fused row pass: k_bp_rows_coh's arithmetic per (row, query) and, per graph edge in slot order,
+//   R_ij = lamC A_ij [d_ij + 2 ds dp + ds^2 n2 + 2 sum_b dgamma_b (dkappa_b + ds e_b) + nu_i + nu_j - 2 gamma_j . (H gamma_i)]
+// with fp64 S1 / S2 / first argmax and k_rm_rows' dense-row rule.  coh is N x qs doubles; z / j / r as RmRowsArgs'.
+struct RpRowsArgs {
+  BpArgs b;              // nu written (launch_bp_rows_self has run)
+  const float* dslot;    // the shifted basis's |P'_i - P'_j|^2 per ELL slot
+  const int32_t* api_id;
+  float z_th;
+  double* cohd;
+  float* z;
+  int32_t* j;
+  float* r;
+};
+void launch_rp_rows(const RpRowsArgs& a, hipStream_t s);
+// part[b * nq + q] = sum of coh[r * qs + q] over the rows r = b, b + nb, ... in row order
+void launch_rp_colsum(const double* coh, int32_t N, int32_t qs, int32_t nq, int32_t nb, double* part, hipStream_t s);
+
+}  // namespace osc
+
 // ---- multi-query chain receipts: chain_many_kernels.hip -------------------------------------
 #include "chain_many.hpp"
 

@@ -139,6 +139,8 @@ class OscillinkLattice:
         self._qbs_scale = 0.0
         self._qbs_stats = False  # the shifted slot also holds its per-row constants (bundle_many with lamP)
         self.last_bundle_prior: dict[str, Any] = {}
+        self._qbs_receipt = 0  # receipt_many with lamP: 1 = the slot holds M' x' (8 N bytes), 2 = also d_ij per ELL slot
+        self.last_receipt_prior: dict[str, Any] = {}
         self.last_shifted_basis: dict[str, Any] = {}
         self.shifted_basis_solves = 0
         self._settle_callbacks: list = []
@@ -300,7 +302,10 @@ class OscillinkLattice:
                 # chain_receipt_many(lamP=...) keeps the basis of M + lamP I beside the query basis: N x ld + N x 4 floats
                 # (ld >= D rounded up to 4); 0 until the first such call
                 "shifted_basis_bytes": (4 * self.N * (((self.D + 3) // 4) * 4 + 4) if self._qbs_key is not None else 0)
-                + (28 * self.N if self._qbs_key is not None and self._qbs_stats else 0),
+                + (28 * self.N if self._qbs_key is not None and self._qbs_stats else 0)
+                # receipt_many(lamP=...): M' x' (fp64) and, full detail, |P'_i - P'_j|^2 per ELL slot (max degree wide)
+                + (8 * self.N if self._qbs_key is not None and self._qbs_receipt >= 1 else 0)
+                + (4 * self.N * max(1, self.graph_stats()[1]) if self._qbs_key is not None and self._qbs_receipt >= 2 else 0),
                 **{name: int(getattr(counters, name)) for name, _ in nat.Counters._fields_[1:]}}
 
     def anchor_gram(self) -> np.ndarray:
@@ -877,7 +882,8 @@ class OscillinkLattice:
             return []
         return [rc.bundle_dicts(ids[q], score[q], align[q]) for q in range(Q)]
 
-    def receipt_many(self, psis: np.ndarray, *, tol: float = 1e-4, max_iters: int = 256, as_arrays: bool = False):
+    def receipt_many(self, psis: np.ndarray, *, tol: float = 1e-4, max_iters: int = 256, as_arrays: bool = False,
+                     chains=None, lamP: Optional[float] = None, chain_weights=None):
         """`receipt()` for each row of `psis` (Q x D), as if `set_query(psis[q]); receipt()` had run with the current U,
         gates, chain, lambdas and receipt / signature settings held fixed, without touching the lattice's state.  U*(psi_q)
         comes from the query basis `bundle_many` uses (same key, cache and tolerance contract): every
@@ -887,50 +893,113 @@ class OscillinkLattice:
         Full detail at a large N reports a null point on most rows (about N per query): set OSCILLINK_RECEIPT_NULL_CAP
         (the cap is selected on the device) or use `as_arrays=True`, which returns a dict of NumPy arrays instead of dicts:
         deltaH, coh_drop_sum, anchor_pen_sum, query_term_sum, null_total (Q each), null_offsets (Q + 1) and the kept null
-        points null_i / null_j / null_z / null_r of every query, concatenated."""
+        points null_i / null_j / null_z / null_r of every query, concatenated.
+
+        With `chains` and `lamP` (>= 0) query q also carries a chain PRIOR: it gets the receipt
+        that `add_chain(chains[q], lamP, chain_weights[q]); set_query(psis[q]); receipt()` returns on a lattice without a
+        chain of its own, from the basis of the shifted operator `chain_receipt_many(lamP=...)` and `bundle_many(lamP=...)`
+        use (the same slot and key) and one Green's column per distinct chain node, without a U* solve per query.  `chains`
+        and `chain_weights` take `bundle_many`'s forms; a chain has at most 64 distinct nodes.  The signature carries the
+        argument's lamP, `chain_present` and the chain's length; `meta.ustar_res` is the per-query residual bound,
+        `ustar_source` is `"chain_prior_basis"`.  `as_arrays=True` adds `chain_prior_res` (float32) and `chain_prior_iters`
+        (int32); both also go to `last_receipt_prior` = {"lamP", "res", "iters"}.  `lamP=0` gives the plain call's numbers."""
         if self._has_comm:
             raise NotImplementedError("receipt_many: lattices with a communicator (sharded / multi-rank) are not supported")
+        prior = chains is not None or lamP is not None
+        if prior:
+            if lamP is None:
+                raise ValueError("chains given without lamP")
+            if chains is None:
+                raise ValueError("lamP given without chains")
+            if not np.isfinite(float(lamP)) or float(lamP) < 0:
+                raise ValueError("lamP must be >= 0")
+            if self._chain_nodes is not None:
+                raise ValueError("receipt_many with lamP: the lattice has a chain of its own (clear_chain first)")
+        elif chain_weights is not None:
+            raise ValueError("chain_weights given without chains and lamP")
         P = rc.check_queries(psis, self.D)
         Q = int(P.shape[0])
+        lists = None
+        if prior:
+            lists, offsets, nodes = rc.chain_block(chains, Q, self.N)
+            edge_offsets = offsets - np.arange(Q + 1, dtype=np.int64)
+            weights = rc.chain_prior_weights(chain_weights, chains, lists, edge_offsets)
+            checked = set()  # (a shared chain is one list Q times)
+            for q, ch in enumerate(lists):
+                if id(ch) not in checked and len(set(ch)) > rc.MAX_PRIOR_NODES:
+                    raise ValueError(f"query {q}: with lamP a chain has at most {rc.MAX_PRIOR_NODES} distinct nodes, got "
+                                     f"{len(set(ch))}")
+                checked.add(id(ch))
+        shifted = prior and float(lamP) > 0
         full = self._receipt_detail != "light"
         cap_val = rc.null_cap()
         ra = rc.ReceiptArrays(Q, (min(cap_val, self.N) if cap_val > 0 else self.N) if full else 0)
+        prior_res, prior_iters = np.zeros(Q, dtype=np.float32), np.zeros(Q, dtype=np.int32)
         solved = False
         if Q > 0:
-            n0 = self.stats["query_basis_solves"]
-            self._ensure_query_basis(tol, max_iters, float(np.max(np.abs(P))))
-            solved = self.stats["query_basis_solves"] != n0
-            self._call("osc_receipt_many", nat.f32(P), Q, int(full), 3.0, cap_val, *ra.pointers())
+            psi_inf_all = float(np.max(np.abs(P)))
+            if shifted:
+                solved = self._ensure_shifted_basis(float(lamP), tol, max_iters, psi_inf_all)
+            else:
+                n0 = self.stats["query_basis_solves"]
+                self._ensure_query_basis(tol, max_iters, psi_inf_all)
+                solved = self.stats["query_basis_solves"] != n0
+            if prior:
+                self._call("osc_receipt_prior_many", nat.f32(P), Q, nat.i64(offsets), nat.i32(nodes),
+                           None if weights is None else nat.f32(weights), float(lamP), float(tol), int(max_iters), int(full),
+                           3.0, cap_val, *ra.pointers(), nat.f32(prior_res), nat.i32(prior_iters))
+                self._qbs_stats = self._qbs_stats or (shifted and full)
+                self._qbs_receipt = max(self._qbs_receipt, (2 if full else 1) if shifted else 0)
+            else:
+                self._call("osc_receipt_many", nat.f32(P), Q, int(full), 3.0, cap_val, *ra.pointers())
         ra.round_sums()
-        self._log("receipt_many", {"Q": Q, "receipt_detail": self._receipt_detail, "basis_solved": solved,
-                                   "null_points": ra.kept})
+        payload = {"Q": Q, "receipt_detail": self._receipt_detail, "basis_solved": solved, "null_points": ra.kept}
+        if prior:
+            payload["lamP"] = float(lamP)
+            self.last_receipt_prior = {"lamP": float(lamP), "res": prior_res, "iters": prior_iters}
+        self._log("receipt_many", payload)
+        if prior:
+            over = np.nonzero(~(prior_res <= tol))[0]
+            if over.size:
+                self._log("chain_prior_convergence_warn", {"queries": int(over.size), "first": int(over[0]),
+                                                           "res": float(prior_res[over[0]]), "tol": tol,
+                                                           "iters": int(prior_iters[over[0]])})
         if as_arrays:
-            return {**ra.scalar_arrays(), **ra.null_arrays()}
+            out = {**ra.scalar_arrays(), **ra.null_arrays()}
+            if prior:
+                out.update(chain_prior_res=prior_res, chain_prior_iters=prior_iters)
+            return out
         if Q == 0:
             return []
         # everything but psi, the energies, the null points and the ustar fields is shared by the batch
         nnz, _, _ = self.graph_stats()
-        qb = self.last_query_basis
+        qb = self.last_shifted_basis if shifted else self.last_query_basis
         res_X, res_x = float(qb["res"]["X"]), float(qb["res"]["x"])
         adj_sig = hashlib.sha256(np.ascontiguousarray(self._edge_prefix()).tobytes()).hexdigest()
-        sig_rest = {"lam": [self.lamG, self.lamC, self.lamQ, self.lamP], "chain_present": self._chain_nodes is not None,
+        sig_rest = {"lam": [self.lamG, self.lamC, self.lamQ, float(lamP) if prior else self.lamP],
+                    "chain_present": prior or self._chain_nodes is not None,
                     "chain_len": len(self._chain_nodes) if self._chain_nodes else 0, "k": self._kneighbors,
                     "detk": self._deterministic_k, "adj": adj_sig}
         degree, gates = rc.degree_stats(nnz, self.N), rc.gate_stats(self._B)
         settle, signed = self._last_settle_fields(), self._signed_settings()
+        if prior:
+            signed = {**signed, "params": {**signed["params"], "lamP": float(lamP)}}
         dyn = self._last_dynamics if os.getenv("OSCILLINK_RECEIPT_DYNAMICS", "0").strip().lower() in {"1", "true", "yes"} \
             else None
         psi_inf = np.max(np.abs(P), axis=1) if self.D else np.zeros(Q)
+        source = "chain_prior_basis" if prior else "query_basis"
         out = []
         for q in range(Q):
+            if prior:
+                sig_rest["chain_len"] = len(lists[q])
             sig = self._signature_digest({"psi": np.round(P[q], 6).tolist(), **sig_rest}, self._B)
             dH = float(ra.sums[0, q])
-            res_q = res_X + float(psi_inf[q]) * res_x
+            res_q = float(prior_res[q]) if prior else res_X + float(psi_inf[q]) * res_x
             ustar = {"ustar_iters": int(qb["iters"]["X"]), "ustar_res": float(res_q), "ustar_converged": bool(res_q <= tol)}
             nulls, tot = ra.nulls(q)
             meta = rc.meta(ustar_cached=not solved, ustar_solves=self.stats["ustar_solves"],
                            ustar_cache_hits=self.stats["ustar_cache_hits"], ustar=ustar,
-                           ustar_solve_ms=float(qb["solve_ms"]) if solved else 0.0, ustar_source="query_basis",
+                           ustar_solve_ms=float(qb["solve_ms"]) if solved else 0.0, ustar_source=source,
                            graph_build_ms=self._graph_build_ms, last_settle_ms=settle["t_ms"], degree=degree, gates=gates,
                            state_sig=sig, receipt_detail=self._receipt_detail,
                            null_points_summary=rc.null_summary(tot, cap_val))
@@ -1415,6 +1484,7 @@ class OscillinkLattice:
         self._qb_version += 1
         self._qb_key = None
         self._qbs_key = None
+        self._qbs_receipt = 0
         self._invalidate_cache()
 
     def append_info(self) -> dict[str, Any]:
