@@ -278,6 +278,18 @@ int osc_anchor_gram3_info(osc_handle h, int64_t* fused_three_step_solves, int64_
  * holds; OSC_E_UNSUPPORTED while none are held */
 int osc_anchor_gram3_read(osc_handle h, double* out, int64_t cap);
 
+/* a solve of that kind that ends in iteration 4 without a fourth matvec (one level of scalars further: alpha4 and |r4| come from
+ * the sums of the two vectors A p4 adds, W W W W 1 and W^5 Y; where the published residuals show the solve to end in iteration 4,
+ * iteration 3's matvec writes x4 = x3 + alpha4 p4 from its epilogue and iteration 4 launches nothing; OSC_ANCHOR_GRAM4 = 0 off /
+ * 1 wherever the three-step route runs, unset: lattices of at least 96000 rows): fused_four_step_solves = solves that ended so
+ * since creation, bytes = device memory held ((16 ld + 5) doubles; 0: not built or dropped), last_solve = whether the last
+ * general-path solve ended so, builds = times the sums were formed (measurement aid) */
+int osc_anchor_gram4_info(osc_handle h, int64_t* fused_four_step_solves, int64_t* bytes, int32_t* last_solve, int64_t* builds);
+/* those sums as held (test aid): 16 arrays of ld doubles -- <W^j Y, W^5 Y> for j = 0..5, then <a, W^5 Y> for a = 1, s, s2, s3, s4
+ * (s4 = W s3), then <s4, W^j Y> for j = 0..4 -- and the five <a, s4>, a = 1, s, s2, s3, s4; cap = doubles `out` holds;
+ * OSC_E_UNSUPPORTED while none are held */
+int osc_anchor_gram4_read(osc_handle h, double* out, int64_t cap);
+
 /* the block-major copy of the graph the blocked matvec walks, built for `nb` source blocks (test / diagnostic aid; no
  * reference counterpart): slot_col / slot_w [nb][N][4] = {neighbour row, W_ij} per (source block, row, slot), unused slots
  * {first row of the block, 0}; rows whose edges exceed 4 nb slots list the rest in over_col / over_w[over_first[i] ..

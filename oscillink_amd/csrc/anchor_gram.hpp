@@ -212,5 +212,121 @@ OSC_GRAM_HD Scalars3 three_steps(const double (&G)[kBasis3][kBasis3], const Op& 
   return t;
 }
 
+// ---- the fourth step's scalars ---------------------------------------------------------------------------------------------
+// A p4 adds psi_c s4 (s4 = W s3) and (W^5 Y)_c: p4 . A p4 and |r4|^2 are quadratic forms in the 11 x 11 Gram matrix of
+//     psi 1, psi s, psi s2, psi s3, psi s4, Y, W Y, W W Y, W W W Y, W^4 Y, W^5 Y
+// (the a-vectors first again: with finite sums the nine-vector forms are sums of the same terms in the same order, the rest
+// zeros).  Only scalars
+// are taken from this level -- alpha4 and |r4| of a solve that ends in iteration 4 (host_logic.hpp: anchor_gram4_route); no
+// vector of iteration 4 is formed from them but x4 = x3 + alpha4 p4.  The sums beyond the nine vectors' are a third block
+// (L::gram4, read back by osc_anchor_gram4_read): kGram4PerColumn arrays of ld doubles, then kGram4Lattice doubles.  Array j < 6:
+// <W^j Y, W^5 Y>; array 6 + a: <a, W^5 Y> for a in (1, s, s2, s3, s4); array 11 + j: <s4, W^j Y>, j < 5; the lattice's five: <a, s4>
+// for a in (1, s, s2, s3, s4).  Every one is summed directly from the stored float arrays.
+constexpr int kGram4PerColumn = 16;  // 6 <W^j Y, W^5 Y> + 5 <a, W^5 Y> + 5 <s4, W^j Y>
+constexpr int kGram4Lattice = 5;     // <a, s4>
+constexpr int kBasis4 = 11;
+
+OSC_GRAM_HD int y5_index(int j) { return j; }        // <W^j Y, W^5 Y>, j <= 5
+OSC_GRAM_HD int a5_index(int a) { return 6 + a; }    // <a, W^5 Y>, a in 0..4
+OSC_GRAM_HD int s4y_index(int j) { return 11 + j; }  // <s4, W^j Y>, j <= 4
+OSC_GRAM_HD int lat4_index(int a) { return a; }      // <a, s4>, a in 0..4
+
+// One column's 11 x 11 Gram matrix: the nine vectors' part from the first two blocks (fill3's entries, moved to the new order),
+// the rest from the third (col4[q * stride4], lat4).
+OSC_GRAM_HD void fill4(double (&G)[kBasis4][kBasis4], const double* col, size_t stride, const double* lat, const double* col3,
+                       size_t stride3, const double* lat3, const double* col4, size_t stride4, const double* lat4, double psi) {
+  for (int a = 0; a < 3; ++a)
+    for (int b = a; b < 3; ++b) G[a][b] = G[b][a] = psi * psi * lat[lat_index(a, b)];
+  for (int a = 0; a < 4; ++a) G[a][3] = G[3][a] = psi * psi * lat3[lat3_index(a)];
+  for (int a = 0; a < 5; ++a) G[a][4] = G[4][a] = psi * psi * lat4[lat4_index(a)];
+  for (int a = 0; a < 3; ++a)
+    for (int j = 0; j < 4; ++j) G[a][5 + j] = G[5 + j][a] = psi * col[(size_t)ay_index(a, j) * stride];
+  for (int j = 0; j < 4; ++j) G[3][5 + j] = G[5 + j][3] = psi * col3[(size_t)s3y_index(j) * stride3];
+  for (int a = 0; a < 4; ++a) G[a][9] = G[9][a] = psi * col3[(size_t)a4_index(a) * stride3];
+  for (int j = 0; j < 5; ++j) G[4][5 + j] = G[5 + j][4] = psi * col4[(size_t)s4y_index(j) * stride4];
+  for (int a = 0; a < 5; ++a) G[a][10] = G[10][a] = psi * col4[(size_t)a5_index(a) * stride4];
+  for (int j = 0; j < 4; ++j)
+    for (int k = j; k < 4; ++k) G[5 + j][5 + k] = G[5 + k][5 + j] = col[(size_t)yy_index(j, k) * stride];
+  for (int j = 0; j < 5; ++j) G[5 + j][9] = G[9][5 + j] = col3[(size_t)y4_index(j) * stride3];
+  for (int j = 0; j < 6; ++j) G[5 + j][10] = G[10][5 + j] = col4[(size_t)y5_index(j) * stride4];
+}
+
+struct Scalars4 {
+  Scalars3 three;    // iterations 1 to 3: three_steps()' values to the bit
+  float alpha4 = 0.f, beta4 = 0.f;
+  float res4 = 0.f;  // |r4| of this column
+  double rz4 = 0.0;  // r4 . z4
+  bool usable4 = false;
+};
+
+OSC_GRAM_HD double form4(const double (&G)[kBasis4][kBasis4], const double (&v)[kBasis4], const double (&w)[kBasis4]) {
+  double t = 0.0;
+  for (int a = 0; a < kBasis4; ++a) {
+    double row = 0.0;
+    for (int b = 0; b < kBasis4; ++b) row += G[a][b] * w[b];
+    t += v[a] * row;
+  }
+  return t;
+}
+// out = A v; W shifts psi 1 -> ... -> psi s4 and Y -> ... -> W^5 Y (p1 .. p4 have no psi s4 and no W^5 Y component)
+OSC_GRAM_HD void apply4(const Op& o, const double (&v)[kBasis4], double (&out)[kBasis4]) {
+  double wv[kBasis4] = {0.0, v[0], v[1], v[2], v[3], 0.0, v[5], v[6], v[7], v[8], v[9]};
+  for (int a = 0; a < kBasis4; ++a) out[a] = o.cs * v[a] - o.cW * wv[a];
+}
+
+// three_steps()' recurrence one iteration further: p4 = z3 + beta3 p3, alpha4 = r3 . z3 / (p4 . A p4 + 1e-18), r4 = r3 - alpha4 A
+// p4, res4, beta4 and r4 . z4 as k_reduce_alpha / k_reduce_beta round them.  usable4: three's rules, and the same for the fourth
+// iteration's values.
+OSC_GRAM_HD Scalars4 four_steps(const double (&G)[kBasis4][kBasis4], const Op& o) {
+  Scalars4 f;
+  Scalars3& t = f.three;
+  Scalars& s = t.two;
+  double r0[kBasis4] = {o.qb, 0.0, 0.0, 0.0, 0.0, o.u, o.cW, 0.0, 0.0, 0.0, 0.0};
+  double p1[kBasis4], q1[kBasis4], r1[kBasis4], p2[kBasis4], ap2[kBasis4], r2[kBasis4], p3[kBasis4], ap3[kBasis4], r3[kBasis4];
+  double p4[kBasis4], ap4[kBasis4], r4[kBasis4];
+  for (int a = 0; a < kBasis4; ++a) p1[a] = o.m * r0[a];
+  apply4(o, p1, q1);
+  const double rr0 = form4(G, r0, r0), rz0 = o.m * rr0;
+  const double pq1 = form4(G, p1, q1);
+  s.alpha1 = (float)(rz0 / (pq1 + 1e-18));
+  for (int a = 0; a < kBasis4; ++a) r1[a] = r0[a] - (double)s.alpha1 * q1[a];
+  const double rr1 = form4(G, r1, r1), rz1 = o.m * rr1;
+  s.res1 = (float)sqrt(rr1);
+  s.beta1 = (float)(rz1 / (rz0 + 1e-18));
+  for (int a = 0; a < kBasis4; ++a) p2[a] = o.m * r1[a] + (double)s.beta1 * p1[a];
+  apply4(o, p2, ap2);
+  const double pq2 = form4(G, p2, ap2);
+  s.alpha2 = (float)(rz1 / (pq2 + 1e-18));
+  for (int a = 0; a < kBasis4; ++a) r2[a] = r1[a] - (double)s.alpha2 * ap2[a];
+  const double rr2 = form4(G, r2, r2);
+  s.res2 = (float)sqrt(rr2);
+  s.rz2 = o.m * rr2;
+  s.beta2 = (float)(s.rz2 / (rz1 + 1e-18));
+  s.usable = finite(rr0) && finite(pq1) && finite(rr1) && finite(pq2) && finite(rr2) && finite((double)s.alpha1) &&
+             finite((double)s.alpha2) && finite((double)s.beta1) && finite((double)s.beta2) && rr0 > 0.0 && pq1 >= 0.0 &&
+             rr1 >= 0.0 && pq2 >= 0.0 && rr2 >= 0.0;
+  for (int a = 0; a < kBasis4; ++a) p3[a] = o.m * r2[a] + (double)s.beta2 * p2[a];
+  apply4(o, p3, ap3);
+  const double pq3 = form4(G, p3, ap3);
+  t.alpha3 = (float)(s.rz2 / (pq3 + 1e-18));
+  for (int a = 0; a < kBasis4; ++a) r3[a] = r2[a] - (double)t.alpha3 * ap3[a];
+  const double rr3 = form4(G, r3, r3);
+  t.res3 = (float)sqrt(rr3);
+  t.rz3 = o.m * rr3;
+  t.beta3 = (float)(t.rz3 / (s.rz2 + 1e-18));
+  t.usable3 = s.usable && finite(pq3) && finite(rr3) && finite((double)t.alpha3) && finite((double)t.beta3) && pq3 >= 0.0 && rr3 >= 0.0;
+  for (int a = 0; a < kBasis4; ++a) p4[a] = o.m * r3[a] + (double)t.beta3 * p3[a];
+  apply4(o, p4, ap4);
+  const double pq4 = form4(G, p4, ap4);
+  f.alpha4 = (float)(t.rz3 / (pq4 + 1e-18));
+  for (int a = 0; a < kBasis4; ++a) r4[a] = r3[a] - (double)f.alpha4 * ap4[a];
+  const double rr4 = form4(G, r4, r4);
+  f.res4 = (float)sqrt(rr4);
+  f.rz4 = o.m * rr4;
+  f.beta4 = (float)(f.rz4 / (t.rz3 + 1e-18));
+  f.usable4 = t.usable3 && finite(pq4) && finite(rr4) && finite((double)f.alpha4) && finite((double)f.beta4) && pq4 >= 0.0 && rr4 >= 0.0;
+  return f;
+}
+
 }  // namespace gram
 }  // namespace osc

@@ -443,9 +443,13 @@ __device__ __forceinline__ void blk_init_row(const BlkArgs& a, const BlkInit& ii
 // the loop form does, r3 = r2 - alpha3 o as k_update_xr does and p4 = z3 + beta3 p3 as k_update_p does (p3: the own row, in
 // hand for the diagonal term), and stores r3 over r2 and p4 slab-major.  o is never stored, and with nothing to sum there is no
 // fold: the two streaming passes and the two column reductions between matvec 3 and matvec 4 are gone.
-template <int GM, int CW, bool INIT = false, int PD = 1, int WPE = 4, bool WY = false, bool FUSED = false>
+// FMODE == 2 (FUSED_LAST): the same iteration where the solve is known to end in iteration 4 and alpha4 is out as well (four_steps).
+// The epilogue fetches the row of x3 as a third stream, forms r3 and p4 with the FUSED form's expressions in registers only and
+// stores x4 = x3 + alpha4 p4 (k_update_x_ring's fmaf) over x3: nothing else is written, and iteration 4 has no launch at all.
+template <int GM, int CW, bool INIT = false, int PD = 1, int WPE = 4, bool WY = false, int FMODE = 0>
 __global__ __launch_bounds__((CW + 1) * 64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_apply_blocked(
-    const BlkArgs a, const std::conditional_t<FUSED, BlkFused, BlkInit> ii) {
+    const BlkArgs a, const std::conditional_t<FMODE != 0, BlkFused, BlkInit> ii) {
+  constexpr bool FUSED = FMODE != 0, LAST = FMODE == 2;
   static_assert(INIT || !WY, "only the INIT pass stores the row sums");
   static_assert(!(INIT && FUSED), "the fused form is an iteration, not the INIT pass");
   constexpr int SL = OSC_BLK_SLOTS, NT = (CW + 1) * 64;
@@ -617,6 +621,7 @@ __global__ __launch_bounds__((CW + 1) * 64) __attribute__((amdgpu_waves_per_eu(W
       constexpr int EC = FUSED ? (WPE <= 2 ? 2 : 1) : WPE <= 2 ? 4 : INIT ? 1 : 2, NBATCH = (GM + EC - 1) / EC;  // (INIT: the y rows take the second group's registers; two groups: 72 spills)
       float4 xs[2][EC];
       float4 ys[2][(INIT && !WY) || FUSED ? EC : 1];  // (FUSED: the rows of r2)
+      [[maybe_unused]] float4 x3s[2][LAST ? EC : 1];  // (FUSED_LAST: the rows of x3)
       int2 rr[2][EC];
       float bv[2][EC];
       float4 psi4 = f4(0.f);
@@ -630,12 +635,17 @@ __global__ __launch_bounds__((CW + 1) * 64) __attribute__((amdgpu_waves_per_eu(W
         zbase = ii.Z + (size_t)(p.sc0 >> 5) * (size_t)a.N * 32;
         if constexpr (WY) wybase = ii.WY + (size_t)(p.sc0 >> 5) * (size_t)a.N * 32;
       }
-      [[maybe_unused]] float4 al4 = f4(0.f), be4 = f4(0.f);
+      [[maybe_unused]] float4 al4 = f4(0.f), be4 = f4(0.f), aln = f4(0.f);
       if constexpr (FUSED) {
         if (cok) al4 = ld4(ii.alpha + p.sc0 + lr * 4), be4 = ld4(ii.beta + p.sc0 + lr * 4);
-        zbase = ii.Pout + (size_t)(p.sc0 >> 5) * (size_t)a.N * 32;
+        if constexpr (LAST) {
+          if (cok) aln = ld4(ii.alpha_last + p.sc0 + lr * 4);
+        } else {
+          zbase = ii.Pout + (size_t)(p.sc0 >> 5) * (size_t)a.N * 32;
+        }
       }
-      auto fetch = [&](int k, float4 (&x)[EC], float4 (&y)[(INIT && !WY) || FUSED ? EC : 1], int2 (&r)[EC], float (&bb)[EC]) {
+      auto fetch = [&](int k, float4 (&x)[EC], float4 (&y)[(INIT && !WY) || FUSED ? EC : 1], int2 (&r)[EC], float (&bb)[EC],
+                       float4 (&xl)[LAST ? EC : 1]) {
 #pragma unroll
         for (int i = 0; i < EC; ++i) {
           const int g = k * EC + i, row = row_first + g * w8;
@@ -643,6 +653,7 @@ __global__ __launch_bounds__((CW + 1) * 64) __attribute__((amdgpu_waves_per_eu(W
           r[i] = make_int2(0, 0);
           bb[i] = 0.f;
           if constexpr ((INIT && !WY) || FUSED) y[i] = f4(0.f);
+          if constexpr (LAST) xl[i] = f4(0.f);
           if (g < GM && g < ng && row < rhi && cok) {
             x[i] = ld4_at(xbase, (uint32_t)row * 128u + lr16);
             r[i] = ld2_at(a.rest, (uint32_t)row * 8u);  // edges beyond SL per block: {first, count}, ascending columns
@@ -651,13 +662,14 @@ __global__ __launch_bounds__((CW + 1) * 64) __attribute__((amdgpu_waves_per_eu(W
               if (ii.Y != nullptr) y[i] = ld4_stream(reinterpret_cast<const float*>(reinterpret_cast<const char*>(ii.Y) + ((uint32_t)row * ldb + cb)));
             }
             if constexpr (FUSED) y[i] = ld4_stream(reinterpret_cast<const float*>(reinterpret_cast<const char*>(ii.R) + ((uint32_t)row * ldb + cb)));
+            if constexpr (LAST) xl[i] = ld4_stream(reinterpret_cast<const float*>(reinterpret_cast<const char*>(ii.X) + ((uint32_t)row * ldb + cb)));
           }
         }
       };
-      fetch(0, xs[0], ys[0], rr[0], bv[0]);
+      fetch(0, xs[0], ys[0], rr[0], bv[0], x3s[0]);
 #pragma unroll
       for (int k = 0; k < NBATCH; ++k) {
-        if (k + 1 < NBATCH) fetch(k + 1, xs[(k + 1) & 1], ys[(k + 1) & 1], rr[(k + 1) & 1], bv[(k + 1) & 1]);
+        if (k + 1 < NBATCH) fetch(k + 1, xs[(k + 1) & 1], ys[(k + 1) & 1], rr[(k + 1) & 1], bv[(k + 1) & 1], x3s[(k + 1) & 1]);
 #pragma unroll
         for (int i = 0; i < EC; ++i) {
           const int g = k * EC + i, row = row_first + g * w8;
@@ -700,8 +712,17 @@ __global__ __launch_bounds__((CW + 1) * 64) __attribute__((amdgpu_waves_per_eu(W
             one(x.y, acc[g].y, al4.y, be4.y, r.y, pn.y);
             one(x.z, acc[g].z, al4.z, be4.z, r.z, pn.z);
             one(x.w, acc[g].w, al4.w, be4.w, r.w, pn.w);
-            st4_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(ii.R) + ((uint32_t)row * ldb + cb)), r);
-            st4(reinterpret_cast<float*>(reinterpret_cast<char*>(zbase) + ((uint32_t)row * 128u + lr16)), pn);
+            if constexpr (LAST) {
+              float4 xn = x3s[k & 1][i];
+              xn.x = fmaf(pn.x, aln.x, xn.x);  // k_update_x_ring
+              xn.y = fmaf(pn.y, aln.y, xn.y);
+              xn.z = fmaf(pn.z, aln.z, xn.z);
+              xn.w = fmaf(pn.w, aln.w, xn.w);
+              st4_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(ii.X) + ((uint32_t)row * ldb + cb)), xn);
+            } else {
+              st4_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(ii.R) + ((uint32_t)row * ldb + cb)), r);
+              st4(reinterpret_cast<float*>(reinterpret_cast<char*>(zbase) + ((uint32_t)row * 128u + lr16)), pn);
+            }
           } else {
             const float cs = fmaf(a.cs_B, bv[k & 1][i], a.cs_const);
             float4 o;
@@ -890,7 +911,7 @@ __global__ __launch_bounds__((CW + 1) * 64) void k_init_cached_ap2(const BlkArgs
 // change a bit.
 __device__ __forceinline__ void two_steps_elem(const BlkArgs& a, const BlkInit& ii, float b, float sm, float sm2, float4 x, float4 w,
                                                float4 v, float4 t, float4 psi4, float4 al1, float4 be1, float4 al2, float4 be2,
-                                               float4& r2, float4& p3, float4& x2) {
+                                               float4& r2, float4& p3, float4& x2, bool third = false, float4 al3 = float4{0.f, 0.f, 0.f, 0.f}) {
   float4 r0, z0;
   blk_init_row(a, ii, b, x, x, w, psi4, r0, z0);
   const float cs = fmaf(a.cs_B, b, a.cs_const);  // (init_cached_body's scalars)
@@ -916,6 +937,12 @@ __device__ __forceinline__ void two_steps_elem(const BlkArgs& a, const BlkInit& 
   one(x.y, r0.y, z0.y, w.y, v.y, t.y, psi4.y, al1.y, be1.y, al2.y, be2.y); r2.y = r2v; p3.y = p3v; x2.y = x2v;
   one(x.z, r0.z, z0.z, w.z, v.z, t.z, psi4.z, al1.z, be1.z, al2.z, be2.z); r2.z = r2v; p3.z = p3v; x2.z = x2v;
   one(x.w, r0.w, z0.w, w.w, v.w, t.w, psi4.w, al1.w, be1.w, al2.w, be2.w); r2.w = r2v; p3.w = p3v; x2.w = x2v;
+  if (third) {  // (the three-step route: x3 = x2 + alpha3 p3, k_update_x_ring's operation on the same floats)
+    x2.x = fmaf(p3.x, al3.x, x2.x);
+    x2.y = fmaf(p3.y, al3.y, x2.y);
+    x2.z = fmaf(p3.z, al3.z, x2.z);
+    x2.w = fmaf(p3.w, al3.w, x2.w);
+  }
 }
 template <int CW>
 __global__ __launch_bounds__((CW + 1) * 64) void k_init_two_steps(const BlkArgs a, const BlkInit ii, const BlkInitAp ap, const BlkInitAp2 ap2,
@@ -941,6 +968,8 @@ __global__ __launch_bounds__((CW + 1) * 64) void k_init_two_steps(const BlkArgs 
     const int cc = cok ? sc0 + lr * 4 : sc0;
     const float4 psi4 = cok ? ld4(ii.psi + cc) : f4(0.f);
     const float4 al1 = ld4(ts.alpha1 + cc), al2 = ld4(ts.alpha2 + cc), be1 = ld4(ts.beta1 + cc), be2 = ld4(ts.beta2 + cc);
+    const bool third = ts.alpha3 != nullptr;
+    const float4 al3 = third ? ld4(ts.alpha3 + cc) : f4(0.f);
     float4 xs[2][EC], ws[2][EC], vs[2][EC], t3[2][EC];
     float bv[2][EC], ss[2][EC], s2[2][EC];
     // (no test around the loads: see init_cached_body)
@@ -968,7 +997,7 @@ __global__ __launch_bounds__((CW + 1) * 64) void k_init_two_steps(const BlkArgs 
         const int g = k * EC + i, row = row_first + g * wk.W8;
         if (g >= ngall || row >= wk.rhi || !cok) continue;
         float4 r2, p3, x2;
-        two_steps_elem(a, ii, bb[i], sm[i], sm2[i], x[i], w[i], v[i], t[i], psi4, al1, be1, al2, be2, r2, p3, x2);
+        two_steps_elem(a, ii, bb[i], sm[i], sm2[i], x[i], w[i], v[i], t[i], psi4, al1, be1, al2, be2, r2, p3, x2, third, al3);
         st4_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(ii.R) + ((uint32_t)row * ldb + cb)), r2);
         st4_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(ii.Xcopy) + ((uint32_t)row * ldb + cb)), x2);
         st4(reinterpret_cast<float*>(reinterpret_cast<char*>(pbase) + ((uint32_t)row * 128u + lr16)), p3);
@@ -1010,7 +1039,8 @@ __global__ __launch_bounds__(256) void k_init_two_steps_stream(const BlkArgs a, 
   const int32_t t0 = a.c0 + (int32_t)blockIdx.y * (NCH * LPR * 4);
   int coff[NCH], cld[NCH];
   bool cok[NCH];
-  float4 psi4[NCH], al1[NCH], be1[NCH], al2[NCH], be2[NCH];
+  float4 psi4[NCH], al1[NCH], be1[NCH], al2[NCH], be2[NCH], al3[NCH];
+  const bool third = ts.alpha3 != nullptr;
 #pragma unroll
   for (int ch = 0; ch < NCH; ++ch) {
     coff[ch] = t0 + (ch * LPR + lr) * 4;
@@ -1021,6 +1051,7 @@ __global__ __launch_bounds__(256) void k_init_two_steps_stream(const BlkArgs a, 
     be1[ch] = ld4(ts.beta1 + cld[ch]);
     al2[ch] = ld4(ts.alpha2 + cld[ch]);
     be2[ch] = ld4(ts.beta2 + cld[ch]);
+    al3[ch] = third ? ld4(ts.alpha3 + cld[ch]) : f4(0.f);
   }
   uint32_t cb[NCH], sb[NCH];  // byte offsets of the lane's columns within a row: row-major, slab-major (blk_off less the row)
 #pragma unroll
@@ -1059,7 +1090,7 @@ __global__ __launch_bounds__(256) void k_init_two_steps_stream(const BlkArgs a, 
         if (!cok[ch]) continue;
         float4 r2, p3, x2;
         two_steps_elem(a, ii, bv[j], sm[j], sm2[j], x[j][ch], w[j][ch], v[j][ch], t[j][ch], psi4[ch], al1[ch], be1[ch], al2[ch], be2[ch], r2,
-                       p3, x2);
+                       p3, x2, third, al3[ch]);
         // (a row and a column that are stored are the ones that were loaded: the same offsets)
         st4_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(ii.R + (size_t)rld[j] * ld) + cb[ch]), r2);
         st4_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(ii.Xcopy + (size_t)rld[j] * ld) + cb[ch]), x2);
@@ -1232,16 +1263,100 @@ __global__ __launch_bounds__(256) void k_anchor_gram3_fold(const GramArgs a) {
   }
 }
 
+// The sums the fourth step's scalars add (anchor_gram.hpp: kGram4PerColumn, kGram4Lattice), same scheme once more: workgroup (slab,
+// chunk), a thread one column of every eighth row, float64, the eight row lanes folded through LDS in lane order, the lattice's
+// five sums in the slab-0 workgroups.
+__global__ __launch_bounds__(256) void k_anchor_gram4_part(const Gram4Args b) {
+  constexpr int NQ = gram::kGram4PerColumn, NL = gram::kGram4Lattice;
+  const GramArgs& a = b.g;
+  __shared__ double red[8][32];
+  const int cl = threadIdx.x & 31, half = threadIdx.x >> 5;
+  const int sc0 = a.c0 + (int)blockIdx.x * 32, col = sc0 + cl, chunk = (int)blockIdx.y;
+  const bool cok = col < a.c1;
+  const bool lat = blockIdx.x == 0 && cl == 0;
+  const int r0 = (int)((int64_t)a.N * chunk / OSC_GRAM_CHUNKS), r1 = (int)((int64_t)a.N * (chunk + 1) / OSC_GRAM_CHUNKS);
+  const size_t slab = (size_t)(sc0 >> 5) * (size_t)a.N * 32;
+  double acc[NQ], la[NL];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) acc[q] = 0.0;
+#pragma unroll
+  for (int q = 0; q < NL; ++q) la[q] = 0.0;
+  for (int row = r0 + half; row < r1; row += 8) {
+    const double s[5] = {1.0, (double)a.wsum[row], (double)a.wsum2[row], (double)b.wsum3[row], (double)b.wsum4[row]};
+    if (cok) {
+      const double y[6] = {(double)a.Ys[slab + (size_t)row * 32 + cl], (double)a.WYs[slab + (size_t)row * 32 + cl],
+                           (double)a.WW[(size_t)row * a.ld + col], (double)a.W3[(size_t)row * a.ld + col],
+                           (double)b.W4[(size_t)row * a.ld + col], (double)b.W5[(size_t)row * a.ld + col]};
+#pragma unroll
+      for (int j = 0; j < 6; ++j) acc[gram::y5_index(j)] += y[j] * y[5];
+#pragma unroll
+      for (int q = 0; q < 5; ++q) acc[gram::a5_index(q)] += s[q] * y[5];
+#pragma unroll
+      for (int j = 0; j < 5; ++j) acc[gram::s4y_index(j)] += s[4] * y[j];
+    }
+    if (lat) {
+#pragma unroll
+      for (int q = 0; q < 5; ++q) la[gram::lat4_index(q)] += s[q] * s[4];
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    __syncthreads();
+    red[half][cl] = acc[q];
+    __syncthreads();
+    if (half == 0 && cok) {
+      double t = 0.0;
+#pragma unroll
+      for (int h = 0; h < 8; ++h) t += red[h][cl];
+      a.part[((size_t)chunk * NQ + q) * a.ld + col] = t;
+    }
+  }
+  if (blockIdx.x == 0) {
+#pragma unroll
+    for (int q = 0; q < NL; ++q) {
+      __syncthreads();
+      if (cl == 0) red[half][0] = la[q];
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        double t = 0.0;
+#pragma unroll
+        for (int h = 0; h < 8; ++h) t += red[h][0];
+        a.part[(size_t)OSC_GRAM_CHUNKS * NQ * a.ld + (size_t)chunk * NL + q] = t;
+      }
+    }
+  }
+}
+__global__ __launch_bounds__(256) void k_anchor_gram4_fold(const GramArgs a) {
+  constexpr int NQ = gram::kGram4PerColumn, NL = gram::kGram4Lattice;
+  const int idx = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (idx < NQ * a.ld) {
+    const int q = idx / a.ld, col = idx % a.ld;
+    double t = 0.0;
+    if (col >= a.c0 && col < a.c1)
+      for (int ch = 0; ch < OSC_GRAM_CHUNKS; ++ch) t += a.part[((size_t)ch * NQ + q) * a.ld + col];
+    a.out[idx] = t;
+  } else if (idx < NQ * a.ld + NL) {
+    const int q = idx - NQ * a.ld;
+    double t = 0.0;
+    for (int ch = 0; ch < OSC_GRAM_CHUNKS; ++ch) t += a.part[(size_t)OSC_GRAM_CHUNKS * NQ * a.ld + (size_t)ch * NL + q];
+    a.out[idx] = t;
+  }
+}
+
 // One workgroup, a thread per column (anchor_gram.hpp: two_steps): the scalars of iterations 1 and 2, their residuals as
 // k_reduce_beta publishes them (nanmax over the columns, device slot and host-mapped word), and the fused pass's gate word.
 // A solve with an unusable column publishes 0 for both residuals: the host loop stops in iteration 1, nothing was written,
 // and run_cg solves again on the summed route.
 // With the third step planned (GramScalarArgs::gram3; three_steps on the nine vectors' matrix) also alpha3, beta3, r3 . z3 in
 // rz's place, the third residual and go[1], the gate word of iteration 3's fused matvec; usable3 takes usable's place.
+// With the fourth step's scalars planned as well (GramScalarArgs::gram4; four_steps on the eleven vectors' matrix: the same three
+// iterations to the bit) also alpha4 and the fourth residual, the latter into its host word alone.  A column whose fourth iteration is unusable makes that residual
+// NaN -- the host then keeps iteration 4 on the summed route -- and leaves the three-step route as it is.
 __global__ __launch_bounds__(256) void k_anchor_gram_scalars(const GramScalarArgs a) {
-  __shared__ float sh1[4], sh2[4], sh3[4];
+  __shared__ float sh1[4], sh2[4], sh3[4], sh4[4];
   __shared__ int shu[4];
   const bool three = a.gram3 != nullptr;  // (three_steps: the same iterations 1 and 2 to the bit, and iteration 3's scalars)
+  const bool four = three && a.gram4 != nullptr;
   const float b = a.B[0];
   gram::Op o;
   const float cs = fmaf(a.cs_B, b, a.cs_const);  // (blk_init_row's and init_cached_body's scalars)
@@ -1251,11 +1366,25 @@ __global__ __launch_bounds__(256) void k_anchor_gram_scalars(const GramScalarArg
   o.m = (double)(1.f / (fmaf(a.md_B, b, a.md_const) + 1e-12f));
   o.u = (double)__fsub_rn(__fadd_rn(a.rbU, a.rbY), cs);
   const double* lat = a.gram + (size_t)gram::kGramPerColumn * a.ld;
-  float res1 = 0.f, res2 = 0.f, res3 = 0.f;
+  float res1 = 0.f, res2 = 0.f, res3 = 0.f, res4 = 0.f;
   int usable = 1;
   for (int col = a.c0 + (int)threadIdx.x; col < a.c1; col += 256) {
     gram::Scalars s;
-    if (three) {
+    if (four) {
+      const double* lat3 = a.gram3 + (size_t)gram::kGram3PerColumn * a.ld;
+      const double* lat4 = a.gram4 + (size_t)gram::kGram4PerColumn * a.ld;
+      double G[gram::kBasis4][gram::kBasis4];
+      gram::fill4(G, a.gram + col, (size_t)a.ld, lat, a.gram3 + col, (size_t)a.ld, lat3, a.gram4 + col, (size_t)a.ld, lat4, (double)a.psi[col]);
+      const gram::Scalars4 f = gram::four_steps(G, o);
+      s = f.three.two;
+      s.usable = f.three.usable3;
+      a.alpha3[col] = f.three.alpha3;
+      a.beta3[col] = f.three.beta3;
+      a.rz[col] = f.three.rz3;
+      a.alpha4[col] = f.alpha4;
+      res3 = nanmax(res3, f.three.res3);
+      res4 = nanmax(res4, f.usable4 ? f.res4 : __uint_as_float(0x7FC00000u));
+    } else if (three) {
       const double* lat3 = a.gram3 + (size_t)gram::kGram3PerColumn * a.ld;
       double G[gram::kBasis3][gram::kBasis3];
       gram::fill3(G, a.gram + col, (size_t)a.ld, lat, a.gram3 + col, (size_t)a.ld, lat3, (double)a.psi[col]);
@@ -1285,14 +1414,17 @@ __global__ __launch_bounds__(256) void k_anchor_gram_scalars(const GramScalarArg
     res1 = nanmax(res1, __shfl_xor(res1, off, 64));
     res2 = nanmax(res2, __shfl_xor(res2, off, 64));
     res3 = nanmax(res3, __shfl_xor(res3, off, 64));
+    res4 = nanmax(res4, __shfl_xor(res4, off, 64));
     usable &= __shfl_xor(usable, off, 64);
   }
   if ((threadIdx.x & 63) == 0)
-    sh1[threadIdx.x >> 6] = res1, sh2[threadIdx.x >> 6] = res2, sh3[threadIdx.x >> 6] = res3, shu[threadIdx.x >> 6] = usable;
+    sh1[threadIdx.x >> 6] = res1, sh2[threadIdx.x >> 6] = res2, sh3[threadIdx.x >> 6] = res3, sh4[threadIdx.x >> 6] = res4,
+                       shu[threadIdx.x >> 6] = usable;
   __syncthreads();
   if (threadIdx.x == 0) {
-    for (int w = 1; w < 4; ++w) res1 = nanmax(res1, sh1[w]), res2 = nanmax(res2, sh2[w]), res3 = nanmax(res3, sh3[w]), usable &= shu[w];
-    if (!usable) res1 = res2 = res3 = 0.f;
+    for (int w = 1; w < 4; ++w)
+      res1 = nanmax(res1, sh1[w]), res2 = nanmax(res2, sh2[w]), res3 = nanmax(res3, sh3[w]), res4 = nanmax(res4, sh4[w]), usable &= shu[w];
+    if (!usable) res1 = res2 = res3 = res4 = 0.f;
     a.res_slots[1] = __float_as_uint(res1);
     a.res_slots[2] = __float_as_uint(res2);
     a.go[0] = (usable && res1 > a.tol && res2 > a.tol) ? 1u : 0u;
@@ -1300,8 +1432,14 @@ __global__ __launch_bounds__(256) void k_anchor_gram_scalars(const GramScalarArg
       a.res_slots[3] = __float_as_uint(res3);
       a.go[1] = (usable && res1 > a.tol && res2 > a.tol && res3 > a.tol) ? 1u : 0u;
     }
+    // (no device slot for the fourth residual: where the host keeps iteration 4 on the summed route, k_reduce_beta forms that
+    // slot by atomicMax over zero, and where it does not, nothing is launched that would read it as a gate)
     __threadfence();
-    // words 3 and 2 first: the host polls word 1, and once it has that it may give the solve up and reuse the words (run_cg)
+    // words 4, 3 and 2 first: the host polls word 1, and once it has that it may give the solve up and reuse the words (run_cg)
+    if (four) {
+      reinterpret_cast<volatile uint32_t*>(a.host_words)[4] = __float_as_uint(res4);
+      __threadfence_system();
+    }
     if (three) {
       reinterpret_cast<volatile uint32_t*>(a.host_words)[3] = __float_as_uint(res3);
       __threadfence_system();
@@ -2119,9 +2257,22 @@ void launch_anchor_gram3(const Gram3Args& b, hipStream_t s) {
   hipLaunchKernelGGL(k_anchor_gram3_fold, dim3((n + 255) / 256), dim3(256), 0, s, a);
   HIP_CHECK(hipGetLastError());
 }
+void launch_anchor_gram4(const Gram4Args& b, hipStream_t s) {
+  const GramArgs& a = b.g;
+  if (!a.Ys || !a.WYs || !a.WW || !a.W3 || !b.W4 || !b.W5 || b.W4 == b.W5 || !a.wsum || !a.wsum2 || !b.wsum3 || !b.wsum4 || !a.part ||
+      !a.out || a.N < 1 || (a.c0 & 31) != 0 || a.c1 <= a.c0 || a.c1 > a.ld)
+    throw std::runtime_error("anchor Gram sums, fourth step: bad arguments");
+  hipLaunchKernelGGL(k_anchor_gram4_part, dim3((a.c1 - a.c0 + 31) / 32, OSC_GRAM_CHUNKS), dim3(256), 0, s, b);
+  HIP_CHECK(hipGetLastError());
+  const int n = gram::kGram4PerColumn * a.ld + gram::kGram4Lattice;
+  hipLaunchKernelGGL(k_anchor_gram4_fold, dim3((n + 255) / 256), dim3(256), 0, s, a);
+  HIP_CHECK(hipGetLastError());
+}
 void launch_anchor_gram_scalars(const GramScalarArgs& a, hipStream_t s) {
   if (a.gram3 != nullptr && (!a.alpha3 || !a.beta3 || a.beta3 == a.beta2 || a.alpha3 == a.alpha1 || a.alpha3 == a.alpha2))
     throw std::runtime_error("anchor Gram scalars: bad arguments of the third step");
+  if (a.gram4 != nullptr && (a.gram3 == nullptr || !a.alpha4 || a.alpha4 == a.alpha1 || a.alpha4 == a.alpha2 || a.alpha4 == a.alpha3))
+    throw std::runtime_error("anchor Gram scalars: bad arguments of the fourth step");
   hipLaunchKernelGGL(k_anchor_gram_scalars, dim3(1), dim3(256), 0, s, a);
   HIP_CHECK(hipGetLastError());
 }
@@ -2157,12 +2308,21 @@ void launch_apply_blocked(const BlkArgs& a, int grid, hipStream_t s, const BlkIn
   HIP_CHECK(hipGetLastError());
 }
 
-// iteration 3 of an anchor start in one launch (BlkFused)
+// iteration 3 of an anchor start in one launch (BlkFused); with BlkFused::X the last form, which leaves x4 and nothing else
 void launch_apply_blocked_fused(const BlkArgs& a, int grid, hipStream_t s, const BlkFused& f, int variant) {
   blocked_args_check(a, grid, variant);
+  if (f.X != nullptr) {
+    if (!f.R || !f.alpha || !f.beta || !f.alpha_last || !f.go || f.R == a.X || f.X == a.X || f.X == f.R || (a.c1 & 3) != 0 || a.c1 > a.ld)
+      throw std::runtime_error("blocked apply: bad arguments of the last fused form");
+#define CALL(G, W, P, E) hipLaunchKernelGGL((k_apply_blocked<G, W, false, P, E, false, 2>), dim3(grid), dim3((W + 1) * 64), 0, s, a, f)
+    OSC_BLK_SHAPE_SWITCH(variant, CALL);
+#undef CALL
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
   if (!f.R || !f.Pout || !f.alpha || !f.beta || !f.go || f.Pout == a.X || f.R == a.X || f.R == f.Pout || (a.c1 & 3) != 0 || a.c1 > a.ld)
     throw std::runtime_error("blocked apply: bad arguments of the fused form");
-#define CALL(G, W, P, E) hipLaunchKernelGGL((k_apply_blocked<G, W, false, P, E, false, true>), dim3(grid), dim3((W + 1) * 64), 0, s, a, f)
+#define CALL(G, W, P, E) hipLaunchKernelGGL((k_apply_blocked<G, W, false, P, E, false, 1>), dim3(grid), dim3((W + 1) * 64), 0, s, a, f)
   OSC_BLK_SHAPE_SWITCH(variant, CALL);
 #undef CALL
   HIP_CHECK(hipGetLastError());

@@ -177,6 +177,16 @@ struct Gram3Args {
   const float* wsum3;  // [N] s3 = W s2
 };
 void launch_anchor_gram3(const Gram3Args& a, hipStream_t s);
+// ... and of the two the fourth step's scalars add (anchor_gram.hpp: kGram4PerColumn, kGram4Lattice): the same scheme again
+// (k_anchor_gram4_part, k_anchor_gram4_fold) with W^4 Y and W^5 Y (row-major, scratch) and s3, s4 = W s3
+struct Gram4Args {
+  GramArgs g;          // part: [OSC_GRAM_CHUNKS][16][ld], then [OSC_GRAM_CHUNKS][5]; out: [16][ld], then [5]
+  const float* W4;     // W^4 Y, row-major
+  const float* W5;     // W^5 Y, row-major
+  const float* wsum3;  // [N] s3 = W s2
+  const float* wsum4;  // [N] s4 = W s3
+};
+void launch_anchor_gram4(const Gram4Args& a, hipStream_t s);
 
 // k_anchor_gram_scalars: iterations 1 and 2's alpha, beta, residuals and r2 . z2 per column from the Gram sums, the two
 // residuals (max over the columns) into the solve's residual slots and host-mapped words, and the word that lets
@@ -202,11 +212,17 @@ struct GramScalarArgs {
   const double* gram3;
   float* alpha3;
   float* beta3;
+  // The fourth step's scalars (anchor_gram.hpp: four_steps), planned iff gram4 != nullptr (only with gram3): alpha4 per column and
+  // |r4| into host word 4 (the device's residual slot 4 stays zero for k_reduce_beta's atomicMax: only the host acts on |r4|).  rz and beta3 keep iteration 3's values: a solve that goes on past iteration 4 sums
+  // that iteration's scalars as ever.  The host words go out in the order 4, 3, 2, 1.
+  const double* gram4;
+  float* alpha4;
 };
 void launch_anchor_gram_scalars(const GramScalarArgs& a, hipStream_t s);
 
 // k_init_two_steps: the cached INIT pass of BlkInitAp2 run through iterations 1 and 2 with the scalars above.  Of BlkInit it
-// writes R (r2, row-major), Z (p3, slab-major) and Xcopy (x2 = x0 + alpha1 p1 + alpha2 p2, row-major; required); of BlkInitAp
+// writes R (r2, row-major), Z (p3, slab-major) and Xcopy (x2 = x0 + alpha1 p1 + alpha2 p2, or with BlkTwoSteps::alpha3 x3 = x2 +
+// alpha3 p3, row-major; required); of BlkInitAp
 // and BlkInitAp2 it reads WW, wsum, W3, wsum2 and writes nothing.  A no-op unless *go == 1.
 // Two forms with the same bits (launch_init_two_steps): the streaming one (k_init_two_steps_stream, the update kernels' launch
 // geometry; of BlkArgs it reads X, B, N, ld, c0, c1 and the operator's scalars only) and the blocked one, the reference form.
@@ -217,6 +233,9 @@ struct BlkTwoSteps {
   const float* beta2;
   const uint32_t* go;
   int32_t row0;  // first row (streaming form; the blocked form's geometry covers every row: 0 there)
+  // The three-step route: alpha3 is out before the pass runs, and Xcopy takes x3 = x2 + alpha3 p3 (k_update_x_ring's fmaf on
+  // the same floats) instead of x2.  nullptr: x2.
+  const float* alpha3;
 };
 
 // k_apply_blocked as iteration 3 of an anchor start whose alpha3 and beta3 are known beforehand (GramScalarArgs::gram3): the
@@ -229,6 +248,11 @@ struct BlkFused {
   const float* beta;   // [ld] beta3
   const uint32_t* go;
   float md_B, md_const;  // no preconditioner: 0, 1
+  // The last form (FUSED_LAST: the solve ends in iteration 4 and alpha4 is known, GramScalarArgs::gram4): r3 and p4 are formed in
+  // registers with the same expressions and x4 = x3 + alpha4 p4 is written in place over X; R and Pout are not written (Pout may
+  // be nullptr).
+  float* X;                  // x3 in, x4 out, row-major
+  const float* alpha_last;   // [ld] alpha4
 };
 
 enum SpmmMode { SPMM_AP = 0, SPMM_INIT = 1, SPMM_DOT = 2 };

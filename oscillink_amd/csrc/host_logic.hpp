@@ -20,6 +20,8 @@
 //                                       by tests/host_logic/sweep_anchor_gram.cpp)
 //   anchor_gram3_route                : ... and iteration 3 in one launch, its scalars from two more vectors' sums (swept by
 //                                       tests/host_logic/sweep_anchor_gram3.cpp)
+//   anchor_gram4_route                : ... and a solve that ends in iteration 4 has no fourth matvec, alpha4 and |r4| from two
+//                                       more vectors' sums (swept by tests/host_logic/sweep_anchor_gram4.cpp)
 //   cg_host_loop                      : the host loop of a CG solve -- which iteration is enqueued when (run_cg in
 //                                       osc_solve.hip and both sweeps run this one function)
 #pragma once
@@ -634,6 +636,25 @@ struct AnchorGram3Inputs {
 inline bool anchor_gram3_route(const AnchorGram3Inputs& in) {
   if (in.mode == 0 || !in.gram_route || in.comm || in.ring_slots < 2 || in.max_iters < 3 || in.predicted < 3) return false;
   return in.mode > 0 || in.N >= kAnchorApAutoRows;
+}
+// One level of scalars further: with the sums of the two vectors A p4 adds (anchor_gram.hpp: four_steps) alpha4 and |r4| are known
+// before the solve's first launch too.  Iteration 4's vectors are never used by a solve that ends there, so such a solve needs no
+// A p4 at all: iteration 3's fused matvec has p4 in its epilogue and writes x4 = x3 + alpha4 p4 (k_apply_blocked's FUSED_LAST
+// form), and iteration 4 launches nothing.  Planned only on top of the three-step route of this very solve; whether the solve
+// takes it is the host's decision at enqueue(3), when all four residuals are host-visible (anchor_gram4_last_form).
+struct AnchorGram4Inputs {
+  int mode = -1;             // OSC_ANCHOR_GRAM4: 0 off, 1 wherever the three-step route runs, < 0 by the lattice's rows
+  int64_t N = 0;
+  bool gram3_route = false;  // anchor_gram3_route holds for this solve and its sums are held
+  int max_iters = 0;
+};
+inline bool anchor_gram4_route(const AnchorGram4Inputs& in) {
+  if (in.mode == 0 || !in.gram3_route || in.max_iters < 4) return false;
+  return in.mode > 0 || in.N >= kAnchorApAutoRows;
+}
+// The published residuals say that the solve ends in iteration 4 and in no earlier one (a NaN compares false: the loop form).
+inline bool anchor_gram4_last_form(float res1, float res2, float res3, float res4, double tol) {
+  return (double)res1 > tol && (double)res2 > tol && (double)res3 > tol && (double)res4 <= tol;
 }
 // Where iteration `it` of a solve gets its A p (CgSolve::enqueue): from the INIT pass (first: it left A p1 and the p . Ap
 // partials), from the iteration's own p update (second: the INIT pass left T), or from a matvec.

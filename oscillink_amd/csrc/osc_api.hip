@@ -38,6 +38,7 @@ void read_env_solver(L& h) {
   if (num("OSC_ANCHOR_AP2", v)) h.anchor_ap2 = v != 0 ? 1 : 0;
   if (num("OSC_ANCHOR_GRAM", v)) h.anchor_gram = v != 0 ? 1 : 0;
   if (num("OSC_ANCHOR_GRAM3", v)) h.anchor_gram3 = v != 0 ? 1 : 0;
+  if (num("OSC_ANCHOR_GRAM4", v)) h.anchor_gram4 = v != 0 ? 1 : 0;
   if (const char* e = getenv("OSC_TWO_STEPS")) h.two_steps_stream = strcmp(e, "blocked") != 0;
   if (num("OSC_RECEIPT_PAIR", v)) h.receipt_pair = v != 0;
   if (const char* e = getenv("OSC_SHARD")) h.shard_mode = !strcmp(e, "row") ? 1 : 0;
@@ -663,6 +664,24 @@ int osc_anchor_gram3_read(osc_handle h, double* out, int64_t cap) {
     if (l.derived.gram3_nb <= 0) throw Unsupported("osc_anchor_gram3_read: no sums of the third step are held");
     if (out == nullptr || cap < (int64_t)l.gram3.n) throw Invalid("osc_anchor_gram3_read: out holds fewer than 13 ld + 4 doubles");
     HIP_CHECK(hipMemcpyAsync(out, l.gram3.p, l.gram3.n * sizeof(double), hipMemcpyDeviceToHost, l.stream));
+    sync(l);
+  });
+}
+
+int osc_anchor_gram4_info(osc_handle h, int64_t* fused_four_step_solves, int64_t* bytes, int32_t* last_solve, int64_t* builds) {
+  return guarded(h, [&](L& l) {
+    if (fused_four_step_solves) *fused_four_step_solves = l.fused_four_step_solves;
+    if (bytes) *bytes = l.derived.gram4_nb > 0 ? (int64_t)l.gram4.n * 8 : 0;
+    if (last_solve) *last_solve = l.anchor_gram4_last ? 1 : 0;
+    if (builds) *builds = l.anchor_gram4_builds;
+  });
+}
+
+int osc_anchor_gram4_read(osc_handle h, double* out, int64_t cap) {
+  return guarded(h, [&](L& l) {
+    if (l.derived.gram4_nb <= 0) throw Unsupported("osc_anchor_gram4_read: no sums of the fourth step are held");
+    if (out == nullptr || cap < (int64_t)l.gram4.n) throw Invalid("osc_anchor_gram4_read: out holds fewer than 16 ld + 5 doubles");
+    HIP_CHECK(hipMemcpyAsync(out, l.gram4.p, l.gram4.n * sizeof(double), hipMemcpyDeviceToHost, l.stream));
     sync(l);
   });
 }

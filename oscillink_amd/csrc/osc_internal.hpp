@@ -135,6 +135,16 @@ struct osc_lattice {
   int anchor_gram3 = -1;
   int64_t fused_three_step_solves = 0, anchor_gram3_builds = 0;
   bool anchor_gram3_last = false;
+  // One level of scalars further (host_logic.hpp: anchor_gram4_route): the sums of the two vectors A p4 adds -- psi s4, s4 = W s3,
+  // and W^5 Y; W^4 Y and W^5 Y are formed once into two of the solve's scratch arrays, summed against and dropped (anchor_gram.hpp;
+  // (16 ld + 5) doubles are held).  With them k_anchor_gram_scalars also has alpha4 and |r4|, and a solve that ends in iteration 4
+  // writes x4 in iteration 3's fused matvec (FUSED_LAST) and launches nothing for iteration 4.  Built by the first solve that plans
+  // the route, valid exactly as long as gram3 (Derived::gram4_nb).  OSC_ANCHOR_GRAM4: 0 never, 1 wherever the three-step route
+  // runs, unset: by the lattice's rows.
+  DevBuf<double> gram4;
+  int anchor_gram4 = -1;
+  int64_t fused_four_step_solves = 0, anchor_gram4_builds = 0;
+  bool anchor_gram4_last = false;
   int64_t yu_copies = 0;    // whole-array Y -> U copies made for this handle (osc_counters::y_to_u_copies)
   int64_t slab_launches = 0;  // k_rows_to_slab launches (osc_counters::rows_to_slab_launches)
   // Which of the arrays computed from other state (ell_col_t / ell_w_t, blk_*, Ys, WYs, Ustar; by epoch: halo, query) are

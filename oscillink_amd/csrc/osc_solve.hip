@@ -367,8 +367,15 @@ struct CgSolve {
   bool gram_route = false;
   // ... and iteration 3's scalars are known as well (anchor_gram3_route): alpha_of(3) holds alpha3, h.beta beta3, h.rz r3 . z3,
   // residual slot 3 is published.  enqueue(3) launches the matvec's fused form alone -- r3 over r2, p4 into dir(4), under its own
-  // gate word --, enqueue(4) launches no p update.
+  // gate word --, enqueue(4) launches no p update.  The INIT pass has alpha3 and p3 in hand and runs only if iteration 3 is a real
+  // one: it leaves x3 instead of x2, and the ring starts with three directions applied.
   bool gram3_route = false;
+  // ... and alpha4 and |r4| too (anchor_gram4_route): alpha_of(4) holds alpha4 and host word 4 is published (the device's slot 4 is not).
+  // enqueue(3) reads the four published words -- cg_host_loop calls it behind wait(1), and word 1 is the last to go out -- and
+  // where they say the solve ends in iteration 4 it launches the matvec's last form (x4 over x3, nothing else) and sets
+  // gram4_taken: no launch belongs to iteration 4 or to one behind it, and x is complete.  Otherwise it takes word 4 back
+  // (iteration 4's beta reduction publishes it anew) and everything is the three-step route's.
+  bool gram4_planned = false, gram4_taken = false;
   float fused_md_B = 0.f, fused_md_const = 1.f;  // (BlkInit's, for the fused launch)
   bool ring_planned = false;
 
@@ -466,6 +473,7 @@ struct CgSolve {
     int part_rows = grid;
     h.anchor_gram_last = false;
     h.anchor_gram3_last = false;
+    h.anchor_gram4_last = false;
     // (the rhs rows the fused pass can take besides x0 itself: one -- the state term must be x0 or absent, and if y is a
     // third array the solution array must be x0)
     const bool fuse_u = b.rhsU == b.x0 || op.rbU == 0.f;
@@ -570,7 +578,7 @@ struct CgSolve {
       }
       h.cached_inits += 1;
     } else if (wy_route) {
-      h.derived.wy_nb = h.derived.wwy_nb = h.derived.w3_nb = h.derived.gram_nb = h.derived.gram3_nb = 0;  // (not current while this launch rewrites them)
+      h.derived.wy_nb = h.derived.wwy_nb = h.derived.w3_nb = h.derived.gram_nb = h.derived.gram3_nb = h.derived.gram4_nb = 0;  // (not current while this launch rewrites them)
       h.anchor_ap_denied = h.anchor_ap2_denied = false;
       h.WYs.alloc((size_t)h.N * h.ld);
       bi.WY = h.WYs.p;
@@ -622,6 +630,12 @@ struct CgSolve {
     g3.max_iters = max_iters;
     g3.predicted = stop_guess;
     const bool three = host::anchor_gram3_route(g3) && ensure_anchor_gram3();
+    host::AnchorGram4Inputs g4;
+    g4.mode = h.anchor_gram4;
+    g4.N = h.N;
+    g4.gram3_route = three;
+    g4.max_iters = max_iters;
+    const bool four = host::anchor_gram4_route(g4) && ensure_anchor_gram4();
     GramScalarArgs ga{};
     ga.gram = h.gram.p;
     ga.psi = b.psi;
@@ -656,17 +670,25 @@ struct CgSolve {
       ga.beta2 = h.part1.p + (size_t)b.ld;
       if (ga.alpha1 == ga.alpha3) ga.alpha1 = h.part1.p + 2 * (size_t)b.ld;
     }
+    if (four) {  // alpha4 takes alpha1's slot in a ring of three and alpha2's in one of two: the same way out
+      ga.gram4 = h.gram4.p;
+      ga.alpha4 = alpha_of(4);
+      if (ga.alpha1 == ga.alpha4) ga.alpha1 = h.part1.p + 2 * (size_t)b.ld;
+      if (ga.alpha2 == ga.alpha4) ga.alpha2 = h.part1.p + 3 * (size_t)b.ld;
+    }
     launch_anchor_gram_scalars(ga, h.stream);
     BlkInit ti = bi;
     ti.Z = dir(3);
     ti.Xcopy = b.X;
-    BlkTwoSteps ts{ga.alpha1, ga.alpha2, ga.beta1, ga.beta2, ga.go, 0};
+    // (three steps: alpha3 is out as well, the pass has p3 in hand and runs only if iteration 3 is a real one: it leaves x3)
+    BlkTwoSteps ts{ga.alpha1, ga.alpha2, ga.beta1, ga.beta2, ga.go, 0, three ? ga.alpha3 : nullptr};
     launch_init_two_steps(ba, grid, h.stream, ti, plan.shape, ap, ap2, ts, h.two_steps_stream);
     gram_route = true;
     gram3_route = three;
+    gram4_planned = four;
     fused_md_B = bi.md_B;
     fused_md_const = bi.md_const;
-    ring.applied = 2;  // directions 1 and 2 are in x2
+    ring.applied = three ? 3 : 2;  // directions 1 and 2 (and 3) are in what the pass left in x
     h.fused_two_step_solves += 1;
     h.anchor_gram_last = true;
     if (three) h.fused_three_step_solves += 1;
@@ -679,7 +701,7 @@ struct CgSolve {
   // arrays ensure_anchor_ap2 has just made current.  135 KB at 768 columns: no memory rule.
   bool ensure_anchor_gram() {
     if (h.derived.gram_nb == ba.nb && h.derived.w3_nb == ba.nb) return true;
-    h.derived.gram_nb = h.derived.gram3_nb = 0;
+    h.derived.gram_nb = h.derived.gram3_nb = h.derived.gram4_nb = 0;
     const size_t n = (size_t)gram::kGramPerColumn * h.ld + gram::kGramLattice;
     DevBuf<double> part;
     try {
@@ -715,7 +737,7 @@ struct CgSolve {
   // AP scratch array, where nothing lives before the INIT pass, then one streaming pass.  Only the sums and s3 are kept.
   bool ensure_anchor_gram3() {
     if (h.derived.gram3_nb == ba.nb && h.derived.gram_nb == ba.nb) return true;
-    h.derived.gram3_nb = 0;
+    h.derived.gram3_nb = h.derived.gram4_nb = 0;
     if (b.ld != h.ld || h.part1.n < 3 * (size_t)b.ld) return false;
     const size_t n = (size_t)gram::kGram3PerColumn * h.ld + gram::kGram3Lattice;
     DevBuf<double> part;
@@ -758,6 +780,63 @@ struct CgSolve {
     sync(h);  // part goes out of scope
     h.derived.gram3_nb = ba.nb;
     h.anchor_gram3_builds += 1;
+    return true;
+  }
+
+  // The fourth step's sums (L::gram4; anchor_gram.hpp), formed where they are not held: s4 = W s3 over the ELL rows, W^4 Y as
+  // ensure_anchor_gram3 forms it, into the solve's AP scratch array, W^5 Y = W (W^4 Y) the same way over a slab-major image in T
+  // into the solve's R array -- both are free until the INIT pass, and both must be live for <W^4 Y, W^5 Y> --, then one
+  // streaming pass.  Only the sums are kept.
+  bool ensure_anchor_gram4() {
+    if (h.derived.gram4_nb == ba.nb && h.derived.gram3_nb == ba.nb && h.derived.gram_nb == ba.nb) return true;
+    h.derived.gram4_nb = 0;
+    if (b.ld != h.ld || h.part1.n < 4 * (size_t)b.ld || b.R == nullptr || b.R == b.AP) return false;
+    const size_t n = (size_t)gram::kGram4PerColumn * h.ld + gram::kGram4Lattice;
+    DevBuf<double> part;
+    DevBuf<float> wsum4;
+    try {
+      if (h.gram4.n != n) h.gram4.alloc(n);
+      wsum4.alloc((size_t)h.N);
+      part.alloc(n * OSC_GRAM_CHUNKS);
+    } catch (const HipError&) {
+      (void)hipGetLastError();
+      h.gram4.release();
+      return false;
+    }
+    launch_row_weighted_sums(h.ell_col.p, h.ell_w.p, h.deg.p, h.width, (int32_t)h.N, h.Wsum3.p, wsum4.p, h.stream);
+    BlkArgs wa = ba;
+    wa.X = h.Tap.p;
+    wa.cs_const = wa.cs_B = 0.f;
+    wa.cW = -1.f;
+    wa.gate = nullptr;
+    wa.gate_tol = 0.f;
+    rows_to_slab(h, h.W3s.p, h.Tap.p, h.ld, b.c0, b.c1, grid);
+    wa.OUT = b.AP;
+    launch_apply_blocked(wa, grid, h.stream, nullptr, plan.shape);
+    rows_to_slab(h, b.AP, h.Tap.p, h.ld, b.c0, b.c1, grid);
+    wa.OUT = b.R;
+    launch_apply_blocked(wa, grid, h.stream, nullptr, plan.shape);
+    Gram4Args g{};
+    g.g.Ys = h.Ys.p;
+    g.g.WYs = h.WYs.p;
+    g.g.WW = h.WWs.p;
+    g.g.W3 = h.W3s.p;
+    g.g.wsum = h.Wsum.p;
+    g.g.wsum2 = h.Wsum2.p;
+    g.g.part = part.p;
+    g.g.out = h.gram4.p;
+    g.g.N = (int32_t)h.N;
+    g.g.ld = h.ld;
+    g.g.c0 = h.c0;
+    g.g.c1 = h.c1;
+    g.W4 = b.AP;
+    g.W5 = b.R;
+    g.wsum3 = h.Wsum3.p;
+    g.wsum4 = wsum4.p;
+    launch_anchor_gram4(g, h.stream);
+    sync(h);  // part and s4 go out of scope
+    h.derived.gram4_nb = ba.nb;
+    h.anchor_gram4_builds += 1;
     return true;
   }
 
@@ -811,7 +890,7 @@ struct CgSolve {
   bool ensure_anchor_ap2() {
     if (h.derived.w3_nb == ba.nb && h.derived.wwy_nb == ba.nb) return true;
     if (h.anchor_ap2_denied) return false;
-    h.derived.w3_nb = h.derived.gram_nb = h.derived.gram3_nb = 0;
+    h.derived.w3_nb = h.derived.gram_nb = h.derived.gram3_nb = h.derived.gram4_nb = 0;
     const size_t n = (size_t)h.N * h.ld;
     if (h.W3s.n != n || h.Tap.n != n || h.Wsum2.n != (size_t)h.N) {
       size_t free_b = 0, total_b = 0;
@@ -942,9 +1021,36 @@ struct CgSolve {
   // (overlap: no gates -- an iteration writes scratch arrays only until the host has seen its predecessor unconverged)
   void enqueue(int it, bool speculative) {
     if (gram_route && it <= 2) return;  // (both ran inside the INIT pass; their residuals are out)
+    if (gram4_taken && it >= 4) return;  // (x4 is written and the solve is known to end in iteration 4: nothing is left to launch)
     const Gate g{it > 1 && !overlap ? reinterpret_cast<const float*>(res_slots) + (it - 1) : nullptr, tol};
     host::CgXSchedule::IterForm form{false, host::CgXSchedule::XR_SKIPS_X};
     if (!ringed()) form = xs.enqueue(it, speculative);
+    if (gram4_planned && it == 3) {
+      // All four residuals are out (the host has read word 1, the last the scalars kernel publishes).  A solve they show to end in
+      // iteration 4 needs no A p4: the matvec's last form writes x4 = x3 + alpha4 p4 from its epilogue, and that is the solve's
+      // one operator apply (profile slot 0).
+      const volatile float* words = reinterpret_cast<const volatile float*>(h.res_host);
+      if (host::anchor_gram4_last_form(words[1], words[2], words[3], words[4], (double)tol)) {
+        ProfScope ps(h, 0, 4);
+        BlkArgs fa = ba;
+        fa.X = dir(3);
+        fa.OUT = nullptr;
+        fa.gate = nullptr;
+        fa.gate_tol = 0.f;
+        BlkFused f{b.R, nullptr, alpha_of(3), h.beta.p, h.gram_go.p + 1, fused_md_B, fused_md_const};
+        f.X = b.X;
+        f.alpha_last = alpha_of(4);
+        launch_apply_blocked_fused(fa, grid, h.stream, f, plan.shape);
+        h.blk_applies += 1;
+        gram4_taken = true;
+        ring.applied = 4;  // (directions 3 and 4 are in x: no pass is left)
+        h.fused_four_step_solves += 1;
+        h.anchor_gram4_last = true;
+        return;
+      }
+      // (iteration 4 runs on the summed route and publishes its own residual: the word is pending again)
+      reinterpret_cast<volatile uint32_t*>(h.res_host)[4] = kCtrlPending;
+    }
     if (gram3_route && it == 3) {
       // The whole iteration in the matvec's fused form: r3 over r2, p4 into dir(4); alpha3, beta3, r3 . z3 and the residual are
       // out already.  (A sample of iteration 4: a solve that stops in 3 had the launch gated off.)
@@ -1041,6 +1147,7 @@ struct CgSolve {
   }
 
   void idle_before_wait(int it) {
+    if (gram4_taken) return;  // (x is complete)
     if (ringed()) {
       // the pending directions up to `it` go into x behind its x-r kernel, while the host waits for its residual
       ring_pass(ring.pass_before_wait(it), nullptr);
@@ -1072,7 +1179,9 @@ struct CgSolve {
     h.predicted_iters[b.kind] = iters;
     // the last iteration's x update rode in a gated p update that did not run (the solve converged under a speculative
     // iteration): alpha and p are still that iteration's
-    if (ringed()) {  // what the ring still holds for x: with at most K iterations the solve's only x pass
+    if (gram4_taken) {
+      // (x4 was written by iteration 3's launch; the ring holds nothing)
+    } else if (ringed()) {  // what the ring still holds for x: with at most K iterations the solve's only x pass
       ring_pass(ring.final_pass(iters), nullptr);
     } else if (xs.finish_at_end(iters)) {
       finish_x(iters);
@@ -1084,7 +1193,9 @@ struct CgSolve {
     // the speculative iteration (they return at once and write nothing).  With the polled read-back the stream is left
     // to drain on its own -- later calls are ordered behind it anyway; the copy + event path keeps its full wait.
     // (overlap: the same; the second stream is drained by whoever next touches the residual slots it writes -- drain_comm_stream)
-    if (!polled || h.prof_on) sync(h);
+    // (the route without a fourth matvec has every residual before its first N x D pass: what is queued then is the solve itself,
+    // and it is waited for, so that the caller's time is the solve's)
+    if (!polled || h.prof_on || gram4_taken) sync(h);
     drop_speculative_samples(h, prof_mark, iters);
     return CgResult{iters, h.history.empty() ? 0.f : h.history.back(), b.X};
   }
@@ -1093,7 +1204,8 @@ struct CgSolve {
 }  // namespace
 
 // cg_solve (solver.py:6-37) on the device; returns once the last residual is out (what may still be queued then touches
-// scratch arrays only, and later calls are ordered behind it by the stream).  Which iteration is enqueued when is
+// scratch arrays only, or is the ring's last x pass, and later calls are ordered behind it by the stream; a solve on the route
+// without a fourth matvec, whose residuals are out before its first pass, returns when its last launch has finished).  Which iteration is enqueued when is
 // host::cg_host_loop's business (host_logic.hpp; the sweeps under tests/host_logic run that same function against a model
 // of the device's gating); CgSolve is what it drives.
 CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, int max_iters, float tol) {
@@ -1115,6 +1227,7 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
       h.anchor_gram_redos += 1;
       h.fused_two_step_solves -= 1;
       if (s.gram3_route) h.fused_three_step_solves -= 1;
+      if (s.gram4_taken) h.fused_four_step_solves -= 1;
       h.cached_inits -= 1;  // (the solve counts once, where it ends)
       continue;
     }

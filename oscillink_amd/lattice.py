@@ -278,6 +278,8 @@ class OscillinkLattice:
         self._call("osc_anchor_gram_info", C.byref(gf), C.byref(gb), C.byref(gl), C.byref(gn), C.byref(gr))
         g3f, g3b, g3l, g3n = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int64(0)
         self._call("osc_anchor_gram3_info", C.byref(g3f), C.byref(g3b), C.byref(g3l), C.byref(g3n))
+        g4f, g4b, g4l, g4n = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int64(0)
+        self._call("osc_anchor_gram4_info", C.byref(g4f), C.byref(g4b), C.byref(g4l), C.byref(g4n))
         counters = nat.Counters()
         self._call("osc_counters_get", C.byref(counters))
         return {"order_kind": ("none", "bfs", "balanced")[int(ok.value)], "displaced_edges_before": int(db.value),
@@ -299,6 +301,8 @@ class OscillinkLattice:
                 "anchor_gram_redos": int(gr.value),
                 "fused_three_step_solves": int(g3f.value), "anchor_gram3_bytes": int(g3b.value),
                 "anchor_gram3_last_solve": int(g3l.value), "anchor_gram3_builds": int(g3n.value),
+                "fused_four_step_solves": int(g4f.value), "anchor_gram4_bytes": int(g4b.value),
+                "anchor_gram4_last_solve": int(g4l.value), "anchor_gram4_builds": int(g4n.value),
                 # chain_receipt_many(lamP=...) keeps the basis of M + lamP I beside the query basis: N x ld + N x 4 floats
                 # (ld >= D rounded up to 4); 0 until the first such call
                 "shifted_basis_bytes": (4 * self.N * (((self.D + 3) // 4) * 4 + 4) if self._qbs_key is not None else 0)
@@ -323,6 +327,14 @@ class OscillinkLattice:
         ld = self.anchor_gram().size - 6
         out = np.zeros(13 * (ld // 22) + 4, dtype=np.float64)
         self._call("osc_anchor_gram3_read", out.ctypes.data_as(C.POINTER(C.c_double)), out.size)
+        return out
+
+    def anchor_gram4(self) -> np.ndarray:
+        """The float64 sums of the two vectors the fourth step's scalars add, as held on the device: (16 ld + 5,) in the layout
+        of include/oscillink_hip.h: osc_anchor_gram4_read (test aid; raises while none are held)."""
+        ld = self.anchor_gram().size - 6
+        out = np.zeros(16 * (ld // 22) + 5, dtype=np.float64)
+        self._call("osc_anchor_gram4_read", out.ctypes.data_as(C.POINTER(C.c_double)), out.size)
         return out
 
     def halo_info(self) -> dict[str, int]:
