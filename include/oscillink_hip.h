@@ -285,6 +285,10 @@ int osc_anchor_gram3_read(osc_handle h, double* out, int64_t cap);
  * since creation, bytes = device memory held ((16 ld + 5) doubles; 0: not built or dropped), last_solve = whether the last
  * general-path solve ended so, builds = times the sums were formed (measurement aid) */
 int osc_anchor_gram4_info(osc_handle h, int64_t* fused_four_step_solves, int64_t* bytes, int32_t* last_solve, int64_t* builds);
+/* the form of such a solve's one matvec: folded_four_step_solves = those of fused_four_step_solves whose INIT pass stored x4 less
+ * the term in the gathered row sum, so that the matvec reads and writes that one row stream (solves predicted to end in iteration 4); enabled = 0 under OSC_GRAM4_FOLD=0,
+ * which keeps the unfolded form (the reference: its results are bit-identical to the route before the fold existed) */
+int osc_gram4_fold_info(osc_handle h, int64_t* folded_four_step_solves, int32_t* enabled);
 /* those sums as held (test aid): 16 arrays of ld doubles -- <W^j Y, W^5 Y> for j = 0..5, then <a, W^5 Y> for a = 1, s, s2, s3, s4
  * (s4 = W s3), then <s4, W^j Y> for j = 0..4 -- and the five <a, s4>, a = 1, s, s2, s3, s4; cap = doubles `out` holds;
  * OSC_E_UNSUPPORTED while none are held */

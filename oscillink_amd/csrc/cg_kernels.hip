@@ -446,10 +446,20 @@ __device__ __forceinline__ void blk_init_row(const BlkArgs& a, const BlkInit& ii
 // FMODE == 2 (FUSED_LAST): the same iteration where the solve is known to end in iteration 4 and alpha4 is out as well (four_steps).
 // The epilogue fetches the row of x3 as a third stream, forms r3 and p4 with the FUSED form's expressions in registers only and
 // stores x4 = x3 + alpha4 p4 (k_update_x_ring's fmaf) over x3: nothing else is written, and iteration 4 has no launch at all.
+// FMODE == 3 (the folded last form, BlkFused::go_fold): that x4 is affine in the gathered row sum, and the INIT pass, which runs
+// behind alpha3, beta3 and alpha4, has stored everything else of it as e in x's place (two_steps_elem).  The epilogue streams the
+// row of e -- no own row of p3, no r2 -- and stores x4 = e + ((alpha4 alpha3) (M^-1 cW)) acc over it: one row in, one row out, as
+// the loop form, and like it in batches of that form's width.
+#ifndef OSC_FOLD_EC_WIDE
+#define OSC_FOLD_EC_WIDE 4
+#endif
+#ifndef OSC_FOLD_EC_NARROW
+#define OSC_FOLD_EC_NARROW 2
+#endif
 template <int GM, int CW, bool INIT = false, int PD = 1, int WPE = 4, bool WY = false, int FMODE = 0>
 __global__ __launch_bounds__((CW + 1) * 64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_apply_blocked(
     const BlkArgs a, const std::conditional_t<FMODE != 0, BlkFused, BlkInit> ii) {
-  constexpr bool FUSED = FMODE != 0, LAST = FMODE == 2;
+  constexpr bool FUSED = FMODE != 0, LAST = FMODE == 2, FOLD = FMODE == 3;
   static_assert(INIT || !WY, "only the INIT pass stores the row sums");
   static_assert(!(INIT && FUSED), "the fused form is an iteration, not the INIT pass");
   constexpr int SL = OSC_BLK_SLOTS, NT = (CW + 1) * 64;
@@ -461,6 +471,9 @@ __global__ __launch_bounds__((CW + 1) * 64) __attribute__((amdgpu_waves_per_eu(W
   }
   if constexpr (FUSED) {
     if (*ii.go != 1u) return;
+  }
+  if constexpr (FOLD) {
+    if (*ii.go_fold != 1u) return;  // (the INIT pass stored e only under this word)
   }
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int sub = lane >> 3, lr = lane & 7;
@@ -618,9 +631,11 @@ __global__ __launch_bounds__((CW + 1) * 64) __attribute__((amdgpu_waves_per_eu(W
       // in issue order, so the loads of batch k + 1 are issued BEFORE the stores of batch k: otherwise every batch would
       // also wait for the previous batch's stores to be acknowledged.
       // (FUSED: the r rows are a second stream per group, as the y rows are for INIT)
-      constexpr int EC = FUSED ? (WPE <= 2 ? 2 : 1) : WPE <= 2 ? 4 : INIT ? 1 : 2, NBATCH = (GM + EC - 1) / EC;  // (INIT: the y rows take the second group's registers; two groups: 72 spills)
-      float4 xs[2][EC];
-      float4 ys[2][(INIT && !WY) || FUSED ? EC : 1];  // (FUSED: the rows of r2)
+      // (FOLD: one stream, the loop form's width; OSC_FOLD_EC_WIDE / _NARROW: A/B builds of that choice)
+      constexpr int EC = FOLD ? (WPE <= 2 ? OSC_FOLD_EC_WIDE : OSC_FOLD_EC_NARROW) : FUSED ? (WPE <= 2 ? 2 : 1) : WPE <= 2 ? 4 : INIT ? 1 : 2, NBATCH = (GM + EC - 1) / EC;  // (INIT: the y rows take the second group's registers; two groups: 72 spills)
+      constexpr int YC = (INIT && !WY) || (FUSED && !FOLD) ? EC : 1;
+      float4 xs[2][EC];    // (FOLD: the rows of e, not the own rows of the operand)
+      float4 ys[2][YC];    // (FUSED: the rows of r2)
       [[maybe_unused]] float4 x3s[2][LAST ? EC : 1];  // (FUSED_LAST: the rows of x3)
       int2 rr[2][EC];
       float bv[2][EC];
@@ -637,14 +652,20 @@ __global__ __launch_bounds__((CW + 1) * 64) __attribute__((amdgpu_waves_per_eu(W
       }
       [[maybe_unused]] float4 al4 = f4(0.f), be4 = f4(0.f), aln = f4(0.f);
       if constexpr (FUSED) {
-        if (cok) al4 = ld4(ii.alpha + p.sc0 + lr * 4), be4 = ld4(ii.beta + p.sc0 + lr * 4);
-        if constexpr (LAST) {
+        if (cok) al4 = ld4(ii.alpha + p.sc0 + lr * 4);
+        if constexpr (!FOLD) {
+          if (cok) be4 = ld4(ii.beta + p.sc0 + lr * 4);
+        }
+        if constexpr (FOLD) {  // g = alpha4 alpha3 of the lane's four columns, in al4's registers
+          if (cok) aln = ld4(ii.alpha_last + p.sc0 + lr * 4);
+          al4 = make_float4(__fmul_rn(aln.x, al4.x), __fmul_rn(aln.y, al4.y), __fmul_rn(aln.z, al4.z), __fmul_rn(aln.w, al4.w));
+        } else if constexpr (LAST) {
           if (cok) aln = ld4(ii.alpha_last + p.sc0 + lr * 4);
         } else {
           zbase = ii.Pout + (size_t)(p.sc0 >> 5) * (size_t)a.N * 32;
         }
       }
-      auto fetch = [&](int k, float4 (&x)[EC], float4 (&y)[(INIT && !WY) || FUSED ? EC : 1], int2 (&r)[EC], float (&bb)[EC],
+      auto fetch = [&](int k, float4 (&x)[EC], float4 (&y)[YC], int2 (&r)[EC], float (&bb)[EC],
                        float4 (&xl)[LAST ? EC : 1]) {
 #pragma unroll
         for (int i = 0; i < EC; ++i) {
@@ -652,16 +673,17 @@ __global__ __launch_bounds__((CW + 1) * 64) __attribute__((amdgpu_waves_per_eu(W
           x[i] = f4(0.f);
           r[i] = make_int2(0, 0);
           bb[i] = 0.f;
-          if constexpr ((INIT && !WY) || FUSED) y[i] = f4(0.f);
+          if constexpr ((INIT && !WY) || (FUSED && !FOLD)) y[i] = f4(0.f);
           if constexpr (LAST) xl[i] = f4(0.f);
           if (g < GM && g < ng && row < rhi && cok) {
-            x[i] = ld4_at(xbase, (uint32_t)row * 128u + lr16);
+            if constexpr (FOLD) x[i] = ld4_stream(reinterpret_cast<const float*>(reinterpret_cast<const char*>(ii.X) + ((uint32_t)row * ldb + cb)));
+            else x[i] = ld4_at(xbase, (uint32_t)row * 128u + lr16);
             r[i] = ld2_at(a.rest, (uint32_t)row * 8u);  // edges beyond SL per block: {first, count}, ascending columns
             bb[i] = ld1_at(a.B, (uint32_t)row * 4u);
             if constexpr (INIT && !WY) {  // (byte offsets of a row-major array fit 32 bits: launch_apply_blocked checks N * ld)
               if (ii.Y != nullptr) y[i] = ld4_stream(reinterpret_cast<const float*>(reinterpret_cast<const char*>(ii.Y) + ((uint32_t)row * ldb + cb)));
             }
-            if constexpr (FUSED) y[i] = ld4_stream(reinterpret_cast<const float*>(reinterpret_cast<const char*>(ii.R) + ((uint32_t)row * ldb + cb)));
+            if constexpr (FUSED && !FOLD) y[i] = ld4_stream(reinterpret_cast<const float*>(reinterpret_cast<const char*>(ii.R) + ((uint32_t)row * ldb + cb)));
             if constexpr (LAST) xl[i] = ld4_stream(reinterpret_cast<const float*>(reinterpret_cast<const char*>(ii.X) + ((uint32_t)row * ldb + cb)));
           }
         }
@@ -697,6 +719,15 @@ __global__ __launch_bounds__((CW + 1) * 64) __attribute__((amdgpu_waves_per_eu(W
             if (ii.Xcopy != nullptr) st4_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(ii.Xcopy) + ((uint32_t)row * ldb + cb)), x);
             st4(reinterpret_cast<float*>(reinterpret_cast<char*>(zbase) + ((uint32_t)row * 128u + lr16)), z);
             dot[0] = mulacc4(r, z, dot[0]);
+          } else if constexpr (FOLD) {
+            const float invMd = 1.f / (fmaf(ii.md_B, bv[k & 1][i], ii.md_const) + 1e-12f);
+            const float hq = __fmul_rn(invMd, a.cW);
+            float4 xn = xs[k & 1][i];  // e
+            xn.x = fmaf(__fmul_rn(al4.x, hq), acc[g].x, xn.x);
+            xn.y = fmaf(__fmul_rn(al4.y, hq), acc[g].y, xn.y);
+            xn.z = fmaf(__fmul_rn(al4.z, hq), acc[g].z, xn.z);
+            xn.w = fmaf(__fmul_rn(al4.w, hq), acc[g].w, xn.w);
+            st4_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(ii.X) + ((uint32_t)row * ldb + cb)), xn);
           } else if constexpr (FUSED) {
             const float bq = bv[k & 1][i];
             const float cs = fmaf(a.cs_B, bq, a.cs_const);
@@ -904,6 +935,8 @@ __global__ __launch_bounds__((CW + 1) * 64) void k_init_cached_ap2(const BlkArgs
 // Q1 (k_update_xr), p2 = z1 + beta1 p1 and A p2 = (1 + beta1) Q1 - (m alpha1) T (k_update_p_ap2), r2 = r1 - alpha2 A p2, p3 =
 // z2 + beta2 p2 (k_update_p), x2 = (x0 + alpha1 p1) + alpha2 p2 (k_update_x_ring) -- so the same scalars give the same bits.
 // Stores r2 (row-major), p3 (slab-major) and x2 (row-major); no column sums, no fold: the list wave has nothing to do.
+// Where the solve is known to end in iteration 4 (BlkTwoSteps::go_fold) it stores p3 and, in x's place, e -- x4 less the one term
+// that needs the gathered row sum -- and no r2: the matvec's folded last form (k_apply_blocked, FMODE == 3) reads and writes e alone.
 //
 // One float4 of that pass (two_steps_elem): from the element's x0, W Y, W W Y, W W W Y, the row's b, s and s2 and the column's
 // psi, alpha1, beta1, alpha2, beta2 to r2, p3 and x2.  Both forms of the pass call it -- the blocked one below (the reference
@@ -911,7 +944,9 @@ __global__ __launch_bounds__((CW + 1) * 64) void k_init_cached_ap2(const BlkArgs
 // change a bit.
 __device__ __forceinline__ void two_steps_elem(const BlkArgs& a, const BlkInit& ii, float b, float sm, float sm2, float4 x, float4 w,
                                                float4 v, float4 t, float4 psi4, float4 al1, float4 be1, float4 al2, float4 be2,
-                                               float4& r2, float4& p3, float4& x2, bool third = false, float4 al3 = float4{0.f, 0.f, 0.f, 0.f}) {
+                                               float4& r2, float4& p3, float4& x2, bool third = false, float4 al3 = float4{0.f, 0.f, 0.f, 0.f},
+                                               bool fold = false, float4 be3 = float4{0.f, 0.f, 0.f, 0.f},
+                                               float4 al4 = float4{0.f, 0.f, 0.f, 0.f}) {
   float4 r0, z0;
   blk_init_row(a, ii, b, x, x, w, psi4, r0, z0);
   const float cs = fmaf(a.cs_B, b, a.cs_const);  // (init_cached_body's scalars)
@@ -943,12 +978,27 @@ __device__ __forceinline__ void two_steps_elem(const BlkArgs& a, const BlkInit& 
     x2.z = fmaf(p3.z, al3.z, x2.z);
     x2.w = fmaf(p3.w, al3.w, x2.w);
   }
+  if (fold) {
+    // (the folded last form, behind `third`: k_apply_blocked's FUSED_LAST epilogue on this element with a zero row sum -- its
+    // operations in its operand order; fmaf(cs, p3, -(cW * 0)) is the rounded product -- so x4 = e + (alpha4 alpha3)(M^-1 cW) acc)
+    auto last = [&](float pv, float rv, float xv, float a3, float b3, float a4) {
+      const float o = __fmul_rn(cs, pv);
+      const float r3 = fmaf(-o, a3, rv);
+      const float p4 = fmaf(pv, b3, __fmul_rn(r3, invMd));
+      return fmaf(p4, a4, xv);
+    };
+    x2.x = last(p3.x, r2.x, x2.x, al3.x, be3.x, al4.x);
+    x2.y = last(p3.y, r2.y, x2.y, al3.y, be3.y, al4.y);
+    x2.z = last(p3.z, r2.z, x2.z, al3.z, be3.z, al4.z);
+    x2.w = last(p3.w, r2.w, x2.w, al3.w, be3.w, al4.w);
+  }
 }
 template <int CW>
 __global__ __launch_bounds__((CW + 1) * 64) void k_init_two_steps(const BlkArgs a, const BlkInit ii, const BlkInitAp ap, const BlkInitAp2 ap2,
                                                                   const BlkTwoSteps ts) {
   constexpr int EC = 3;  // (as init_cached_body<CW, 2>: batches of three rows keep the four streams in registers)
   if (*ts.go != 1u) return;
+  const bool fold = ts.go_fold != nullptr && *ts.go_fold == 1u;  // (wave-uniform: the solve ends in iteration 4, BlkTwoSteps::go_fold)
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if ((int)(blockIdx.x >> 3) >= a.xs || wave >= CW) return;
   const int sub = lane >> 3, lr = lane & 7;
@@ -970,6 +1020,7 @@ __global__ __launch_bounds__((CW + 1) * 64) void k_init_two_steps(const BlkArgs 
     const float4 al1 = ld4(ts.alpha1 + cc), al2 = ld4(ts.alpha2 + cc), be1 = ld4(ts.beta1 + cc), be2 = ld4(ts.beta2 + cc);
     const bool third = ts.alpha3 != nullptr;
     const float4 al3 = third ? ld4(ts.alpha3 + cc) : f4(0.f);
+    const float4 be3 = fold ? ld4(ts.beta3 + cc) : f4(0.f), al4 = fold ? ld4(ts.alpha4 + cc) : f4(0.f);
     float4 xs[2][EC], ws[2][EC], vs[2][EC], t3[2][EC];
     float bv[2][EC], ss[2][EC], s2[2][EC];
     // (no test around the loads: see init_cached_body)
@@ -997,8 +1048,8 @@ __global__ __launch_bounds__((CW + 1) * 64) void k_init_two_steps(const BlkArgs 
         const int g = k * EC + i, row = row_first + g * wk.W8;
         if (g >= ngall || row >= wk.rhi || !cok) continue;
         float4 r2, p3, x2;
-        two_steps_elem(a, ii, bb[i], sm[i], sm2[i], x[i], w[i], v[i], t[i], psi4, al1, be1, al2, be2, r2, p3, x2, third, al3);
-        st4_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(ii.R) + ((uint32_t)row * ldb + cb)), r2);
+        two_steps_elem(a, ii, bb[i], sm[i], sm2[i], x[i], w[i], v[i], t[i], psi4, al1, be1, al2, be2, r2, p3, x2, third, al3, fold, be3, al4);
+        if (!fold) st4_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(ii.R) + ((uint32_t)row * ldb + cb)), r2);
         st4_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(ii.Xcopy) + ((uint32_t)row * ldb + cb)), x2);
         st4(reinterpret_cast<float*>(reinterpret_cast<char*>(pbase) + ((uint32_t)row * 128u + lr16)), p3);
       }
@@ -1028,11 +1079,16 @@ __global__ __launch_bounds__((CW + 1) * 64) void k_init_two_steps(const BlkArgs 
 // scalars are loaded once, before the row loop.  No test around a load (see init_cached_body): a lane without a column reads the
 // window's first, a lane without a row the last row, and only the stores are guarded -- so all RPT * NCH * 4 loads of a trip are
 // in flight before the first use.  No LDS, no barrier.  Same bits as k_init_two_steps (two_steps_elem).
-template <int LPR, int NCH, int RPT>
+// FOLDABLE: the instantiation that can store the folded last form's e (BlkTwoSteps::go_fold; beta3 and alpha4 per column cost eight
+// registers a chunk and a wave per SIMD at two and three chunks).  The launcher picks it only where the solve may fold, so every
+// other solve runs the pass with the registers it always had.
+template <int LPR, int NCH, int RPT, bool FOLDABLE = false>
 __global__ __launch_bounds__(256) void k_init_two_steps_stream(const BlkArgs a, const BlkInit ii, const BlkInitAp ap, const BlkInitAp2 ap2,
                                                                const BlkTwoSteps ts) {
   constexpr int RPW = 64 / LPR;
   if (*ts.go != 1u) return;
+  bool fold = false;
+  if constexpr (FOLDABLE) fold = *ts.go_fold == 1u;  // (wave-uniform, as in k_init_two_steps)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int sub = lane / LPR, lr = lane % LPR;
   const int32_t ld = a.ld;
@@ -1040,6 +1096,7 @@ __global__ __launch_bounds__(256) void k_init_two_steps_stream(const BlkArgs a, 
   int coff[NCH], cld[NCH];
   bool cok[NCH];
   float4 psi4[NCH], al1[NCH], be1[NCH], al2[NCH], be2[NCH], al3[NCH];
+  [[maybe_unused]] float4 be3[FOLDABLE ? NCH : 1], al4[FOLDABLE ? NCH : 1];
   const bool third = ts.alpha3 != nullptr;
 #pragma unroll
   for (int ch = 0; ch < NCH; ++ch) {
@@ -1052,6 +1109,10 @@ __global__ __launch_bounds__(256) void k_init_two_steps_stream(const BlkArgs a, 
     al2[ch] = ld4(ts.alpha2 + cld[ch]);
     be2[ch] = ld4(ts.beta2 + cld[ch]);
     al3[ch] = third ? ld4(ts.alpha3 + cld[ch]) : f4(0.f);
+    if constexpr (FOLDABLE) {
+      be3[ch] = fold ? ld4(ts.beta3 + cld[ch]) : f4(0.f);
+      al4[ch] = fold ? ld4(ts.alpha4 + cld[ch]) : f4(0.f);
+    }
   }
   uint32_t cb[NCH], sb[NCH];  // byte offsets of the lane's columns within a row: row-major, slab-major (blk_off less the row)
 #pragma unroll
@@ -1090,9 +1151,9 @@ __global__ __launch_bounds__(256) void k_init_two_steps_stream(const BlkArgs a, 
         if (!cok[ch]) continue;
         float4 r2, p3, x2;
         two_steps_elem(a, ii, bv[j], sm[j], sm2[j], x[j][ch], w[j][ch], v[j][ch], t[j][ch], psi4[ch], al1[ch], be1[ch], al2[ch], be2[ch], r2,
-                       p3, x2, third, al3[ch]);
-        // (a row and a column that are stored are the ones that were loaded: the same offsets)
-        st4_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(ii.R + (size_t)rld[j] * ld) + cb[ch]), r2);
+                       p3, x2, third, al3[ch], fold, be3[FOLDABLE ? ch : 0], al4[FOLDABLE ? ch : 0]);
+        // (a row and a column that are stored are the ones that were loaded: the same offsets; the folded last form keeps no r2)
+        if (!fold) st4_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(ii.R + (size_t)rld[j] * ld) + cb[ch]), r2);
         st4_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(ii.Xcopy + (size_t)rld[j] * ld) + cb[ch]), x2);
         st4(reinterpret_cast<float*>(reinterpret_cast<char*>(ii.Z + (size_t)rld[j] * 32) + sb[ch]), p3);
       }
@@ -1428,10 +1489,14 @@ __global__ __launch_bounds__(256) void k_anchor_gram_scalars(const GramScalarArg
     a.res_slots[1] = __float_as_uint(res1);
     a.res_slots[2] = __float_as_uint(res2);
     a.go[0] = (usable && res1 > a.tol && res2 > a.tol) ? 1u : 0u;
+    uint32_t go1 = 0u;
     if (three) {
       a.res_slots[3] = __float_as_uint(res3);
-      a.go[1] = (usable && res1 > a.tol && res2 > a.tol && res3 > a.tol) ? 1u : 0u;
+      go1 = (usable && res1 > a.tol && res2 > a.tol && res3 > a.tol) ? 1u : 0u;
+      a.go[1] = go1;
     }
+    // the solve ends in iteration 4 and in no earlier one: host::anchor_gram4_last_form on the floats published below (NaN: 0)
+    a.go[2] = (four && go1 == 1u && res4 <= a.tol) ? 1u : 0u;
     // (no device slot for the fourth residual: where the host keeps iteration 4 on the summed route, k_reduce_beta forms that
     // slot by atomicMax over zero, and where it does not, nothing is launched that would read it as a gate)
     __threadfence();
@@ -2213,7 +2278,8 @@ void launch_init_two_steps(const BlkArgs& a, int grid, hipStream_t s, const BlkI
     if (ts.row0 != 0) throw std::runtime_error("two-step INIT pass: the blocked form covers every row");
   }
   if (!init.R || !init.Z || !init.Xcopy || !init.psi || !init.WY || init.Y != nullptr || !ap.WW || !ap.wsum || !ap2.W3 || !ap2.wsum2 ||
-      !ts.alpha1 || !ts.alpha2 || !ts.beta1 || !ts.beta2 || !ts.go)
+      !ts.alpha1 || !ts.alpha2 || !ts.beta1 || !ts.beta2 || !ts.go ||
+      (ts.go_fold != nullptr && (!ts.alpha3 || !ts.beta3 || !ts.alpha4)))
     throw std::runtime_error("two-step INIT pass: bad arguments");
   for (const float* out : {init.R, init.Z, init.Xcopy})  // no output is an input ...
     if (out == a.X || out == init.WY || out == ap.WW || out == ap2.W3) throw std::runtime_error("two-step INIT pass: aliased arrays");
@@ -2225,9 +2291,15 @@ void launch_init_two_steps(const BlkArgs& a, int grid, hipStream_t s, const BlkI
     const int rows_per_wg = 4 * (64 / sh.lpr) * sh.rpt;
     const int64_t need = ((int64_t)(a.N - ts.row0) + rows_per_wg - 1) / rows_per_wg;
     const dim3 g((unsigned)std::max<int64_t>(1, std::min<int64_t>(need, grid / tiles)), (unsigned)tiles);  // (the solve's grid over the tiles)
-#define CALLS(L, C, R) hipLaunchKernelGGL((k_init_two_steps_stream<L, C, R>), g, dim3(256), 0, s, a, init, ap, ap2, ts)
-    OSC_TWO_STEPS_SHAPE_SWITCH(sh, CALLS);
+    if (ts.go_fold != nullptr) {
+#define CALLS(L, C, R) hipLaunchKernelGGL((k_init_two_steps_stream<L, C, R, true>), g, dim3(256), 0, s, a, init, ap, ap2, ts)
+      OSC_TWO_STEPS_SHAPE_SWITCH(sh, CALLS);
 #undef CALLS
+    } else {
+#define CALLS(L, C, R) hipLaunchKernelGGL((k_init_two_steps_stream<L, C, R>), g, dim3(256), 0, s, a, init, ap, ap2, ts)
+      OSC_TWO_STEPS_SHAPE_SWITCH(sh, CALLS);
+#undef CALLS
+    }
     HIP_CHECK(hipGetLastError());
     return;
   }
@@ -2311,6 +2383,15 @@ void launch_apply_blocked(const BlkArgs& a, int grid, hipStream_t s, const BlkIn
 // iteration 3 of an anchor start in one launch (BlkFused); with BlkFused::X the last form, which leaves x4 and nothing else
 void launch_apply_blocked_fused(const BlkArgs& a, int grid, hipStream_t s, const BlkFused& f, int variant) {
   blocked_args_check(a, grid, variant);
+  if (f.go_fold != nullptr) {
+    if (!f.X || !f.alpha || !f.alpha_last || !f.go || f.X == a.X || (a.c1 & 3) != 0 || a.c1 > a.ld)
+      throw std::runtime_error("blocked apply: bad arguments of the folded last form");
+#define CALL(G, W, P, E) hipLaunchKernelGGL((k_apply_blocked<G, W, false, P, E, false, 3>), dim3(grid), dim3((W + 1) * 64), 0, s, a, f)
+    OSC_BLK_SHAPE_SWITCH(variant, CALL);
+#undef CALL
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
   if (f.X != nullptr) {
     if (!f.R || !f.alpha || !f.beta || !f.alpha_last || !f.go || f.R == a.X || f.X == a.X || f.X == f.R || (a.c1 & 3) != 0 || a.c1 > a.ld)
       throw std::runtime_error("blocked apply: bad arguments of the last fused form");

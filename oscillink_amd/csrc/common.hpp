@@ -205,7 +205,7 @@ struct GramScalarArgs {
   double* rz;
   uint32_t* res_slots;   // the solve's residual slots: [1] and [2] are written
   uint32_t* host_words;  // the same two, host-mapped
-  uint32_t* go;          // two words: [0] lets k_init_two_steps run, [1] (third step only) iteration 3's fused matvec
+  uint32_t* go;          // three words: [0] lets k_init_two_steps run, [1] (third step only) iteration 3's fused matvec, [2] see gram4
   // The third step (anchor_gram.hpp: three_steps), planned iff gram3 != nullptr: alpha3, beta3 and r3 . z3 per column (rz then
   // holds r3 . z3, not r2 . z2), |r3| into residual slot and host word 3, and go[1], the word that lets the FUSED matvec of
   // iteration 3 run: 1 only if every column is usable and all three residuals are above tol.
@@ -215,6 +215,8 @@ struct GramScalarArgs {
   // The fourth step's scalars (anchor_gram.hpp: four_steps), planned iff gram4 != nullptr (only with gram3): alpha4 per column and
   // |r4| into host word 4 (the device's residual slot 4 stays zero for k_reduce_beta's atomicMax: only the host acts on |r4|).  rz and beta3 keep iteration 3's values: a solve that goes on past iteration 4 sums
   // that iteration's scalars as ever.  The host words go out in the order 4, 3, 2, 1.
+  // go[2] (always written): 1 exactly if the fourth step is planned, go[1] == 1 and |r4| <= tol -- host::anchor_gram4_last_form on
+  // the very floats that are published, as a device word: the INIT pass and the matvec's folded last form act on it.
   const double* gram4;
   float* alpha4;
 };
@@ -236,6 +238,13 @@ struct BlkTwoSteps {
   // The three-step route: alpha3 is out before the pass runs, and Xcopy takes x3 = x2 + alpha3 p3 (k_update_x_ring's fmaf on
   // the same floats) instead of x2.  nullptr: x2.
   const float* alpha3;
+  // The folded last form (only with alpha3; go_fold == nullptr: never): where *go_fold == 1 the solve ends in iteration 4, beta3 and
+  // alpha4 are out, and Xcopy takes e = x4 with a zero row sum in A p3's place -- r3 = r2 - alpha3 (cs p3), p4 = beta3 p3 + M^-1 r3,
+  // e = x3 + alpha4 p4, the FUSED_LAST epilogue's operations in its operand order -- instead of x3.  R is not written then; Z takes
+  // p3 as ever.  With *go_fold == 0 every stored bit is the pass's without it.
+  const float* beta3;
+  const float* alpha4;
+  const uint32_t* go_fold;
 };
 
 // k_apply_blocked as iteration 3 of an anchor start whose alpha3 and beta3 are known beforehand (GramScalarArgs::gram3): the
@@ -253,6 +262,10 @@ struct BlkFused {
   // be nullptr).
   float* X;                  // x3 in, x4 out, row-major
   const float* alpha_last;   // [ld] alpha4
+  // The folded last form (go_fold != nullptr; needs X and alpha_last): the INIT pass left e in X (BlkTwoSteps::go_fold), x4 is affine
+  // in the gathered row sum, x4 = e + (alpha4 alpha3) (M^-1 cW) acc, and the epilogue is one fmaf per element on the row of e: no own
+  // row of p3, no R, no beta.  A no-op unless *go_fold == 1 (the word the INIT pass acted on).
+  const uint32_t* go_fold;
 };
 
 enum SpmmMode { SPMM_AP = 0, SPMM_INIT = 1, SPMM_DOT = 2 };

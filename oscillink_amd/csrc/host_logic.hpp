@@ -656,6 +656,19 @@ inline bool anchor_gram4_route(const AnchorGram4Inputs& in) {
 inline bool anchor_gram4_last_form(float res1, float res2, float res3, float res4, double tol) {
   return (double)res1 > tol && (double)res2 > tol && (double)res3 > tol && (double)res4 <= tol;
 }
+// The same decision as the device takes it (k_anchor_gram_scalars' go[2]; GramScalarArgs::go): the INIT pass is enqueued before the
+// host has a residual, so the folded last form needs the predicate as a device word.  This is the kernel's tail in host C++ -- the
+// zeroing of an unusable solve, the gate of iteration 3's fused matvec, then |r4| <= tol in float -- on the floats it publishes;
+// tests/host_logic/sweep_gram4_fold.cpp holds it equal to anchor_gram4_last_form on what the host then reads.
+struct AnchorGram4Words {
+  float res1, res2, res3, res4;  // as published (all zero where a column was unusable)
+  bool fold;                     // go[2]
+};
+inline AnchorGram4Words anchor_gram4_device_words(bool four, bool usable, float res1, float res2, float res3, float res4, float tol) {
+  if (!usable) res1 = res2 = res3 = res4 = 0.f;
+  const bool go1 = usable && res1 > tol && res2 > tol && res3 > tol;
+  return AnchorGram4Words{res1, res2, res3, res4, four && go1 && res4 <= tol};
+}
 // Where iteration `it` of a solve gets its A p (CgSolve::enqueue): from the INIT pass (first: it left A p1 and the p . Ap
 // partials), from the iteration's own p update (second: the INIT pass left T), or from a matvec.
 enum class ApSource { matvec, init_pass, p_update };

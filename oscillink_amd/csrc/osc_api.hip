@@ -39,6 +39,7 @@ void read_env_solver(L& h) {
   if (num("OSC_ANCHOR_GRAM", v)) h.anchor_gram = v != 0 ? 1 : 0;
   if (num("OSC_ANCHOR_GRAM3", v)) h.anchor_gram3 = v != 0 ? 1 : 0;
   if (num("OSC_ANCHOR_GRAM4", v)) h.anchor_gram4 = v != 0 ? 1 : 0;
+  if (num("OSC_GRAM4_FOLD", v)) h.gram4_fold = v != 0;
   if (const char* e = getenv("OSC_TWO_STEPS")) h.two_steps_stream = strcmp(e, "blocked") != 0;
   if (num("OSC_RECEIPT_PAIR", v)) h.receipt_pair = v != 0;
   if (const char* e = getenv("OSC_SHARD")) h.shard_mode = !strcmp(e, "row") ? 1 : 0;
@@ -674,6 +675,13 @@ int osc_anchor_gram4_info(osc_handle h, int64_t* fused_four_step_solves, int64_t
     if (bytes) *bytes = l.derived.gram4_nb > 0 ? (int64_t)l.gram4.n * 8 : 0;
     if (last_solve) *last_solve = l.anchor_gram4_last ? 1 : 0;
     if (builds) *builds = l.anchor_gram4_builds;
+  });
+}
+
+int osc_gram4_fold_info(osc_handle h, int64_t* folded_four_step_solves, int32_t* enabled) {
+  return guarded(h, [&](L& l) {
+    if (folded_four_step_solves) *folded_four_step_solves = l.folded_four_step_solves;
+    if (enabled) *enabled = l.gram4_fold ? 1 : 0;
   });
 }
 

@@ -118,7 +118,7 @@ struct osc_lattice {
   // solve that takes the route, valid exactly as long as W3s (Derived::gram_nb).  OSC_ANCHOR_GRAM: 0 never, 1 wherever the
   // depth-2 route runs, unset: by the lattice's rows.
   DevBuf<double> gram;
-  DevBuf<uint32_t> gram_go;  // the fused pass's gate word
+  DevBuf<uint32_t> gram_go;  // the fused pass's gate word, iteration 3's and the folded last form's (GramScalarArgs::go)
   int anchor_gram = -1;
   // The form of that pass (launch_init_two_steps), same bits either way.  OSC_TWO_STEPS: stream (unset) -- the update kernels'
   // launch geometry -- or blocked, the matvec's: the reference form.
@@ -145,6 +145,13 @@ struct osc_lattice {
   int anchor_gram4 = -1;
   int64_t fused_four_step_solves = 0, anchor_gram4_builds = 0;
   bool anchor_gram4_last = false;
+  // The form of such a solve's one matvec.  Folded (unset): the INIT pass, which runs behind alpha3, beta3 and alpha4, stores e = x4
+  // less the term in the gathered row sum in x's place and no r2, and the matvec's epilogue is one fmaf on the row of e
+  // (k_apply_blocked, FMODE == 3).  OSC_GRAM4_FOLD=0: the INIT pass stores x3, r2, p3 and the epilogue forms r3, p4 and x4
+  // (FUSED_LAST), the reference form -- also the form of a solve that ends in iteration 4 behind another prediction (run_cg:
+  // two_steps).  After a folded solve the R array holds nothing defined.
+  bool gram4_fold = true;
+  int64_t folded_four_step_solves = 0;
   int64_t yu_copies = 0;    // whole-array Y -> U copies made for this handle (osc_counters::y_to_u_copies)
   int64_t slab_launches = 0;  // k_rows_to_slab launches (osc_counters::rows_to_slab_launches)
   // Which of the arrays computed from other state (ell_col_t / ell_w_t, blk_*, Ys, WYs, Ustar; by epoch: halo, query) are

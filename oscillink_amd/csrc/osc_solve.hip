@@ -376,6 +376,7 @@ struct CgSolve {
   // gram4_taken: no launch belongs to iteration 4 or to one behind it, and x is complete.  Otherwise it takes word 4 back
   // (iteration 4's beta reduction publishes it anew) and everything is the three-step route's.
   bool gram4_planned = false, gram4_taken = false;
+  bool gram4_fold = false;  // ... and the INIT pass was given go[2]: a solve that ends so takes the folded last form (OSC_GRAM4_FOLD)
   float fused_md_B = 0.f, fused_md_const = 1.f;  // (BlkInit's, for the fused launch)
   bool ring_planned = false;
 
@@ -659,7 +660,7 @@ struct CgSolve {
     ga.rz = h.rz.p;
     ga.res_slots = res_slots;
     ga.host_words = reinterpret_cast<uint32_t*>(h.res_host_dev);
-    if (h.gram_go.n < 2) h.gram_go.alloc(2);
+    if (h.gram_go.n < 3) h.gram_go.alloc(3);
     ga.go = h.gram_go.p;
     if (three) {
       // beta3 takes h.beta, where iteration 4 would look for it, and with two ring slots alpha3 takes alpha1's: the INIT pass,
@@ -681,11 +682,18 @@ struct CgSolve {
     ti.Z = dir(3);
     ti.Xcopy = b.X;
     // (three steps: alpha3 is out as well, the pass has p3 in hand and runs only if iteration 3 is a real one: it leaves x3)
-    BlkTwoSteps ts{ga.alpha1, ga.alpha2, ga.beta1, ga.beta2, ga.go, 0, three ? ga.alpha3 : nullptr};
+    BlkTwoSteps ts{ga.alpha1, ga.alpha2, ga.beta1, ga.beta2, ga.go, 0, three ? ga.alpha3 : nullptr, nullptr, nullptr, nullptr};
+    // (four steps: beta3 and alpha4 are out too, and where go[2] says that the solve ends in iteration 4 the pass leaves e for the
+    // matvec's folded last form instead of x3 and r2.  Only behind a prediction of 4: the pass's foldable form holds a wave per SIMD
+    // less, which a solve that runs on past iteration 4 pays for nothing -- 0.18 ms of a 14.4 ms settle at 1 M rows.  A solve that
+    // ends in iteration 4 unannounced takes the unfolded form once and leaves the prediction.)
+    const bool fold = four && h.gram4_fold && stop_guess == 4;
+    if (fold) ts.beta3 = ga.beta3, ts.alpha4 = ga.alpha4, ts.go_fold = ga.go + 2;
     launch_init_two_steps(ba, grid, h.stream, ti, plan.shape, ap, ap2, ts, h.two_steps_stream);
     gram_route = true;
     gram3_route = three;
     gram4_planned = four;
+    gram4_fold = fold;
     fused_md_B = bi.md_B;
     fused_md_const = bi.md_const;
     ring.applied = three ? 3 : 2;  // directions 1 and 2 (and 3) are in what the pass left in x
@@ -1040,11 +1048,14 @@ struct CgSolve {
         BlkFused f{b.R, nullptr, alpha_of(3), h.beta.p, h.gram_go.p + 1, fused_md_B, fused_md_const};
         f.X = b.X;
         f.alpha_last = alpha_of(4);
+        // (go[2] is this predicate on the same bits: the INIT pass left e in x and no r2, and the folded form is the one to run)
+        if (gram4_fold) f.go_fold = h.gram_go.p + 2;
         launch_apply_blocked_fused(fa, grid, h.stream, f, plan.shape);
         h.blk_applies += 1;
         gram4_taken = true;
         ring.applied = 4;  // (directions 3 and 4 are in x: no pass is left)
         h.fused_four_step_solves += 1;
+        if (gram4_fold) h.folded_four_step_solves += 1;
         h.anchor_gram4_last = true;
         return;
       }
@@ -1228,6 +1239,7 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
       h.fused_two_step_solves -= 1;
       if (s.gram3_route) h.fused_three_step_solves -= 1;
       if (s.gram4_taken) h.fused_four_step_solves -= 1;
+      if (s.gram4_taken && s.gram4_fold) h.folded_four_step_solves -= 1;
       h.cached_inits -= 1;  // (the solve counts once, where it ends)
       continue;
     }

@@ -280,6 +280,8 @@ class OscillinkLattice:
         self._call("osc_anchor_gram3_info", C.byref(g3f), C.byref(g3b), C.byref(g3l), C.byref(g3n))
         g4f, g4b, g4l, g4n = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int64(0)
         self._call("osc_anchor_gram4_info", C.byref(g4f), C.byref(g4b), C.byref(g4l), C.byref(g4n))
+        g4d = C.c_int64(0)
+        self._call("osc_gram4_fold_info", C.byref(g4d), None)
         counters = nat.Counters()
         self._call("osc_counters_get", C.byref(counters))
         return {"order_kind": ("none", "bfs", "balanced")[int(ok.value)], "displaced_edges_before": int(db.value),
@@ -303,6 +305,7 @@ class OscillinkLattice:
                 "anchor_gram3_last_solve": int(g3l.value), "anchor_gram3_builds": int(g3n.value),
                 "fused_four_step_solves": int(g4f.value), "anchor_gram4_bytes": int(g4b.value),
                 "anchor_gram4_last_solve": int(g4l.value), "anchor_gram4_builds": int(g4n.value),
+                "folded_four_step_solves": int(g4d.value),
                 # chain_receipt_many(lamP=...) keeps the basis of M + lamP I beside the query basis: N x ld + N x 4 floats
                 # (ld >= D rounded up to 4); 0 until the first such call
                 "shifted_basis_bytes": (4 * self.N * (((self.D + 3) // 4) * 4 + 4) if self._qbs_key is not None else 0)
