@@ -696,6 +696,9 @@ typedef struct osc_counters {
   int64_t anchor_wy_bytes;
   /* the INIT passes of solves from the anchors that streamed those sums instead of gathering them */
   int64_t cached_inits;
+  /* 1: the rows are stored in a breadth-first order that the device kernels computed (bfs_order.hip); 0: no breadth-first
+   * order, OSC_BFS_HOST=1, or the device form declined the graph (too deep for its key layout) and the host walked it */
+  int64_t bfs_on_device;
 } osc_counters;
 int osc_counters_get(osc_handle h, osc_counters* out);
 

@@ -47,7 +47,7 @@ class Counters(C.Structure):
     """struct osc_counters of include/oscillink_hip.h (the fields' meanings are there)."""
     _fields_ = [(name, C.c_int64) for name in (
         "blocked_shape", "create_pieces", "knn_sweep", "y_to_u_copies", "rows_to_slab_launches", "anchor_slab_bytes",
-        "anchor_wy_bytes", "cached_inits")]
+        "anchor_wy_bytes", "cached_inits", "bfs_on_device")]
 
 
 # name -> (restype, argtypes): exactly the declarations of include/oscillink_hip.h

@@ -1816,6 +1816,7 @@ int osc_counters_get(osc_handle h, osc_counters* out) {
     out->anchor_slab_bytes = l.derived.ys ? (int64_t)l.Ys.n * 4 : 0;
     out->anchor_wy_bytes = l.derived.wy_nb > 0 ? (int64_t)l.WYs.n * 4 : 0;
     out->cached_inits = l.cached_inits;
+    out->bfs_on_device = l.bfs_on_device ? 1 : 0;
   });
 }
 

@@ -129,6 +129,7 @@ void drop_order(L& l) {  // back to the API's row order
   l.inv_h.clear();
   l.reordered = false;
   l.order_kind = 0;
+  l.bfs_on_device = false;
   install_chain(l);
 }
 
@@ -219,6 +220,7 @@ static bool maybe_balance(L& l) {
 void maybe_reorder(L& l) {
   l.reordered = false;
   l.order_kind = 0;
+  l.bfs_on_device = false;
   l.clustering = 0.0;
   // under a communicator only the row-sharded CG re-orders (every rank holds the same graph and takes the same
   // deterministic decision and order; the halo lists shrink with locality); the column-sharded default keeps API order
@@ -259,6 +261,7 @@ void maybe_reorder(L& l) {
   if (!on_device) apply_order(l, bfs_order(l));
   l.reordered = true;
   l.order_kind = 1;
+  l.bfs_on_device = on_device;
 }
 
 // Sharded half sweep: every rank holds partial buckets of ALL rows; rank q needs the other ranks' entries of the buckets of

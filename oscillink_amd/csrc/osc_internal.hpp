@@ -218,7 +218,8 @@ struct osc_lattice {
   // Which order the rows are stored in: 0 the API's, 1 BFS, 2 balanced source blocks (block_balance.hpp: every row's
   // neighbours spread over the blocked matvec's source blocks; the graph keeps no locality, so nothing BFS-specific applies).
   int order_kind = 0;
-  int balance = -1;         // OSC_BALANCE: 0 never, 1 wherever the apply plan has source blocks, unset = auto (maybe_reorder)
+  bool bfs_on_device = false;  // order_kind == 1 and the device kernels computed that order (osc_counters::bfs_on_device)
+  int balance = -1;        // OSC_BALANCE: 0 never, 1 wherever the apply plan has source blocks, unset = auto (maybe_reorder)
   bool balance_host = false;  // OSC_BALANCE_HOST=1: the host reference computes the order (A/B, tests)
   int64_t displaced_before = 0, displaced_after = 0;  // displaced edges of the last balanced order: API order / stored order
   int32_t balance_rounds = 0, balance_nb = 0;

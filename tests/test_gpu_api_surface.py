@@ -555,7 +555,10 @@ def test_device_bfs_order_equals_the_host_walk(amd, N, D, k, csize, monkeypatch)
     for host in ("0", "1"):
         monkeypatch.setenv("OSC_BFS_HOST", host)
         lat = amd.Oscillink(Y, kneighbors=k, deterministic_k=True)
-        assert lat.build_info()["reordered"] == 1
+        info = lat.build_info()
+        assert info["reordered"] == 1
+        # (the device form may decline and leave the walk to the host: without this both sides could be the host walk)
+        assert info["bfs_on_device"] == (1 if host == "0" else 0), info
         perm = np.zeros(N, dtype=np.int32)
         lat._call("osc_get_row_order", nat.i32(perm))
         orders[host] = perm

@@ -45,7 +45,7 @@ def test_counters_struct_matches_the_header():
     body = re.search(r"typedef struct osc_counters \{(.*?)\} osc_counters;", txt, re.S).group(1)
     body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
     fields = [m for decl in re.findall(r"int64_t\s+([^;]+);", body) for m in re.findall(r"\w+", decl)]
-    assert len(fields) == 8 and not re.sub(r"int64_t\s+[^;]+;", "", body).strip()  # nothing but int64_t fields
+    assert len(fields) == 9 and not re.sub(r"int64_t\s+[^;]+;", "", body).strip()  # nothing but int64_t fields
     assert [(n, ctypes.c_int64) for n in fields] == list(_native.Counters._fields_)
     assert ctypes.sizeof(_native.Counters) == 8 * len(fields)
 

@@ -32,8 +32,8 @@ def test_carry_state_is_declared_exported_and_bound(lib):
     assert "lat.U" in comment and "osc_get_U" in comment and "osc_set_U" in comment  # what it replaces
     assert nat.SIGNATURES["osc_carry_state"] == (ctypes.c_int, [nat.Handle, nat.Handle, nat.c_i32p])
     assert hasattr(lib, "osc_carry_state")
-    # (the counters keep their eight fields: the carry adds none)
-    assert len(nat.Counters._fields_) == 8
+    # (the counters keep their nine fields: the carry adds none)
+    assert len(nat.Counters._fields_) == 9
 
 
 def test_null_arguments_are_refused_without_a_device(lib):
