@@ -145,6 +145,43 @@ def chain_prior_weights(chain_weights, chains, lists, edge_offsets):
     return chain_weights_flat(wl, edge_offsets)
 
 
+def check_prior_lamP(fn: str, lamP, own_chain: bool) -> None:
+    """What every batched call with a chain prior asks of `lamP` and of the lattice it runs on."""
+    if not np.isfinite(float(lamP)) or float(lamP) < 0:
+        raise ValueError("lamP must be >= 0")
+    if own_chain:
+        raise ValueError(f"{fn} with lamP: the lattice has a chain of its own (clear_chain first)")
+
+
+def check_prior_args(fn: str, chains, lamP, chain_weights, own_chain: bool) -> bool:
+    """bundle_many's and receipt_many's optional `chains` / `lamP` / `chain_weights`: True when the call carries a prior (both
+    of `chains` and `lamP` given), or the ValueError for a partial set."""
+    if chains is None and lamP is None:
+        if chain_weights is not None:
+            raise ValueError("chain_weights given without chains and lamP")
+        return False
+    if lamP is None:
+        raise ValueError("chains given without lamP")
+    if chains is None:
+        raise ValueError("lamP given without chains")
+    check_prior_lamP(fn, lamP, own_chain)
+    return True
+
+
+def prior_chain_block(chains, chain_weights, Q: int, N: int):
+    """`chains` and `chain_weights` of a call with a chain prior as (lists, offsets, nodes, weights): chain_block's three, the
+    flat float32 weights of chain_prior_weights (or None), and the ValueError for a chain of more than MAX_PRIOR_NODES
+    distinct nodes."""
+    lists, offsets, nodes = chain_block(chains, Q, N)
+    weights = chain_prior_weights(chain_weights, chains, lists, offsets - np.arange(Q + 1, dtype=np.int64))
+    checked = set()  # (a shared chain is one list Q times)
+    for q, ch in enumerate(lists):
+        if id(ch) not in checked and len(set(ch)) > MAX_PRIOR_NODES:
+            raise ValueError(f"query {q}: with lamP a chain has at most {MAX_PRIOR_NODES} distinct nodes, got {len(set(ch))}")
+        checked.add(id(ch))
+    return lists, offsets, nodes, weights
+
+
 def chain_receipt_dict(chain, *, weakest_k, weakest_z, gain, verdict, z_struct, z_path, r_struct, r_path) -> dict[str, Any]:
     """chain_receipt()'s dict (lattice.py:466-528) for one chain from the device's numbers: the per-edge arrays hold the
     chain's len(chain) - 1 edges; weakest_k = -1 (no edge's max(z) exceeds -1) reads edge [-1, -1]."""

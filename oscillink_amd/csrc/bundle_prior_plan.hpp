@@ -1,8 +1,9 @@
 // The host plan of osc_bundle_prior_many: bundle() of Q (query, chain prior) pairs on a resident
 // lattice.  HIP-free: osc_query.hip runs it, tests/host_logic/sweep_bundle_prior_plan.cpp sweeps it under the sanitizers.
 //
-// A pass is a run of consecutive queries -- chain_prior_plan.hpp's: one panel column per distinct chain node of the pass, a
-// query never split -- that also holds, for its queries' m_q distinct nodes, kappa (N x sum m_q floats, row pitch ks), nu
+// A pass is chain_prior_plan.hpp's ChainPriorPass, cut by its packer -- a run of consecutive queries, one panel column per
+// distinct chain node of the pass, a query never split -- whose block also holds, for its queries' m_q distinct nodes (msum
+// their sum, mmax the largest), kappa (N x sum m_q floats, row pitch ks), nu
 // (N x qs doubles), the kappa GEMM's operand and section 11's three N x qs float arrays.  The pass takes queries while all of
 // that fits the budget; a pass of one query is as large as that query needs.
 #pragma once
@@ -46,45 +47,12 @@ inline BundlePriorLayout bundle_prior_layout(int64_t N, int32_t qc, int64_t msum
   return L;
 }
 
-struct BundlePriorPass {
-  int32_t q0 = 0, nq = 0;
-  int32_t qc = 0;             // panel columns: cols.size() rounded up to 32
-  int64_t msum = 0;           // sum of the queries' distinct node counts: kappa's live columns
-  int32_t mmax = 0;           // the largest of them
-  std::vector<int32_t> cols;  // the node (an API id) of every panel column, first seen first
-};
-
-// Passes over queries [0, Q): at most max_queries queries and max_cols distinct nodes each (max_cols <= 0: no limit beside the
-// budget), layout.resident within `budget` bytes unless the pass holds one query.
-inline std::vector<BundlePriorPass> bundle_prior_passes(const int64_t* off, const int32_t* nodes, int32_t Q, int64_t N,
-                                                        int32_t kpad, int32_t max_queries, int32_t max_cols, int64_t budget) {
-  std::vector<BundlePriorPass> out;
-  std::map<int32_t, int32_t> at;
-  BundlePriorPass cur;
-  auto close = [&]() {
-    if (cur.nq == 0) return;
-    cur.qc = gates_width((int32_t)cur.cols.size());
-    out.push_back(std::move(cur));
-    cur = BundlePriorPass{};
-    at.clear();
-  };
-  for (int32_t q = 0; q < Q; ++q) {
-    const std::vector<int32_t> d = chain_prior_distinct(nodes + off[q], off[q + 1] - off[q]);
-    int32_t fresh = 0;
-    for (int32_t v : d) fresh += at.count(v) ? 0 : 1;
-    const int32_t want = (int32_t)cur.cols.size() + fresh;
-    const bool fits = cur.nq < std::max(max_queries, 1) && (max_cols <= 0 || want <= max_cols) &&
-                      bundle_prior_layout(N, gates_width(want), cur.msum + (int64_t)d.size(), cur.nq + 1, kpad).resident <= budget;
-    if (cur.nq > 0 && !fits) close();
-    if (cur.nq == 0) cur.q0 = q;
-    for (int32_t v : d)
-      if (at.emplace(v, (int32_t)cur.cols.size()).second) cur.cols.push_back(v);
-    cur.msum += (int64_t)d.size();
-    cur.mmax = std::max(cur.mmax, (int32_t)d.size());
-    ++cur.nq;
-  }
-  close();
-  return out;
+// Passes over queries [0, Q) by chain_prior_pack: layout.resident within `budget` bytes unless the pass holds one query.
+inline std::vector<ChainPriorPass> bundle_prior_passes(const int64_t* off, const int32_t* nodes, int32_t Q, int64_t N,
+                                                       int32_t kpad, int32_t max_queries, int32_t max_cols, int64_t budget) {
+  return chain_prior_pack(off, nodes, Q, max_queries, max_cols, [&](int32_t qc, int64_t msum, int64_t, int32_t nq) {
+    return bundle_prior_layout(N, qc, msum, nq, kpad).resident <= budget;
+  });
 }
 
 // lanes a (row, query) pair takes in the row kernels: mmax rounded up to a power of two, 1 to 64

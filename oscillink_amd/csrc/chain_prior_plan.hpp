@@ -5,8 +5,10 @@
 //
 // A pass is a run of consecutive queries whose distinct chain nodes -- one panel column each, in the order they are first
 // seen -- are solved together: four slab-major N x qc panels (gates_many_plan.hpp's layout and row partition) beside the
-// per-column scalars.  A query's nodes never straddle two passes.  A pass takes queries while its panel fits the budget and
-// the column limit; a pass of one query is as wide as that query needs, whatever the budget says.
+// per-column scalars.  A query's nodes never straddle two passes.  A pass takes queries while it fits the budget and the
+// column limit; a pass of one query is as wide as that query needs, whatever the budget says.  ChainPriorPass and
+// chain_prior_pack are also the pass and the packer of bundle_prior_plan.hpp and receipt_prior_plan.hpp, which differ in the
+// layout whose bytes the budget bounds.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -82,13 +84,18 @@ inline int32_t chain_prior_check(const int64_t* off, const int32_t* nodes, int32
 struct ChainPriorPass {
   int32_t q0 = 0, nq = 0;      // queries [q0, q0 + nq)
   int32_t qc = 0;              // panel columns: cols.size() rounded up to 32
+  int64_t msum = 0, msq = 0;   // sums of the queries' distinct node counts and of their squares
+  int32_t mmax = 0;            // the largest of them
   std::vector<int32_t> cols;   // the node (as given: an API id) of every panel column, first seen first
 };
 
-// Passes over queries [0, Q): at most max_queries queries and max_cols distinct nodes each (max_cols <= 0: no limit beside the
-// budget), the panel within `budget` bytes unless the pass holds one query.
-inline std::vector<ChainPriorPass> chain_prior_passes(const int64_t* off, const int32_t* nodes, int32_t Q, int64_t N,
-                                                      int32_t max_queries, int32_t max_cols, int64_t budget) {
+// The one packer of the three per-query-prior calls: passes over queries [0, Q), at most max_queries queries (floored at 1)
+// and max_cols distinct nodes each (max_cols <= 0: no limit beside the budget).  fits(qc, msum, msq, nq) says whether a pass
+// of that shape is within the caller's budget; it is asked about the pass as it would be after taking the next query, and a
+// pass of one query is taken whatever it says.
+template <class Fits>
+std::vector<ChainPriorPass> chain_prior_pack(const int64_t* off, const int32_t* nodes, int32_t Q, int32_t max_queries,
+                                             int32_t max_cols, Fits fits) {
   std::vector<ChainPriorPass> out;
   std::map<int32_t, int32_t> at;  // node -> column of the open pass
   ChainPriorPass cur;
@@ -101,19 +108,31 @@ inline std::vector<ChainPriorPass> chain_prior_passes(const int64_t* off, const 
   };
   for (int32_t q = 0; q < Q; ++q) {
     const std::vector<int32_t> d = chain_prior_distinct(nodes + off[q], off[q + 1] - off[q]);
+    const int64_t m = (int64_t)d.size();
     int32_t fresh = 0;
     for (int32_t v : d) fresh += at.count(v) ? 0 : 1;
     const int32_t want = (int32_t)cur.cols.size() + fresh;
-    const bool fits = cur.nq < std::max(max_queries, 1) && (max_cols <= 0 || want <= max_cols) &&
-                      chain_prior_layout(N, gates_width(want)).total <= budget;
-    if (cur.nq > 0 && !fits) close();
+    const bool take = cur.nq < std::max(max_queries, 1) && (max_cols <= 0 || want <= max_cols) &&
+                      fits(gates_width(want), cur.msum + m, cur.msq + m * m, cur.nq + 1);
+    if (cur.nq > 0 && !take) close();
     if (cur.nq == 0) cur.q0 = q;
     for (int32_t v : d)
       if (at.emplace(v, (int32_t)cur.cols.size()).second) cur.cols.push_back(v);
+    cur.msum += m;
+    cur.msq += m * m;
+    cur.mmax = std::max(cur.mmax, (int32_t)m);
     ++cur.nq;
   }
   close();
   return out;
+}
+
+// osc_chain_prior_many's passes: the panel within `budget` bytes unless the pass holds one query
+inline std::vector<ChainPriorPass> chain_prior_passes(const int64_t* off, const int32_t* nodes, int32_t Q, int64_t N,
+                                                      int32_t max_queries, int32_t max_cols, int64_t budget) {
+  return chain_prior_pack(off, nodes, Q, max_queries, max_cols, [&](int32_t qc, int64_t, int64_t, int32_t) {
+    return chain_prior_layout(N, qc).total <= budget;
+  });
 }
 
 // The per-chain systems of a pass: chain c (a path of ChainManyPaths) has m[c] distinct rows, ascending; its panel columns

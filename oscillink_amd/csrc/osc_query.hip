@@ -22,6 +22,26 @@ void require_basis(const L& l) {
     throw StateError("no query basis for the current graph (call osc_query_basis first)");
 }
 
+// The handle with lamG + lamP in lamG's place (the shifted operator M' = M + lamP I) for as long as the guard lives; the
+// handle's own lamG is back when it ends, by a throw too, before anything outside the guarded expression reads it.
+class ShiftedLamG {
+ public:
+  ShiftedLamG(L& l, float lamP) : l_(l), lamG_(l.lamG) { l_.lamG = lamG_ + lamP; }
+  ~ShiftedLamG() { l_.lamG = lamG_; }
+  ShiftedLamG(const ShiftedLamG&) = delete;
+  ShiftedLamG& operator=(const ShiftedLamG&) = delete;
+
+ private:
+  L& l_;
+  const float lamG_;
+};
+
+// ustar_op of the shifted operator
+OpParams shifted_ustar_op(L& l, float lamP) {
+  const ShiftedLamG shifted(l, lamP);
+  return ustar_op(l);
+}
+
 // the batched greedy MMR over the scores in q.cs (N x qs, device order) for nq queries; picks in q.chosen_api / chosen_row
 void mmr_many_run(L& l, int32_t qs, int32_t nq, int32_t kk, float lambda_div) {
   auto& q = l.query;
@@ -196,13 +216,7 @@ void query_basis_shifted_solve(L& l, float lamP, float tol, int32_t max_iters, f
   std::copy(l.predicted_iters, l.predicted_iters + 3, saved_pred);
   std::vector<float> saved_hist = l.history;
   const float f = l.lamG / (l.lamG + lamP);
-  OpParams op{};
-  {  // ustar_op of the handle with lamG + lamP in lamG's place; the handle's own lamG is back before anything else reads it
-    const float lamG = l.lamG;
-    l.lamG = lamG + lamP;
-    op = ustar_op(l);
-    l.lamG = lamG;
-  }
+  const OpParams op = shifted_ustar_op(l, lamP);
   sync(l);
   const double t0 = now_ms();
   if (fresh) sh.have = false;
@@ -804,7 +818,8 @@ struct CpPanelOut {
   int32_t n_sys;
 };
 
-// The panel stage of one pass, shared by osc_chain_prior_many and osc_bundle_prior_many: the unit sources of the pass's
+// The panel stage of one pass (a host::ChainPriorPass), shared by osc_chain_prior_many, osc_bundle_prior_many and
+// osc_receipt_prior_many, whose checks, solve setup and per-pass staging are the helpers behind it: the unit sources of the pass's
 // columns (cols: API ids, qc = their count rounded up to 32), the Jacobi-PCG over the panel, T per distinct chain of `paths`
 // (k_cp_systems), T_q V_q and the residual bound per query (k_cp_tv).  hflts enters as the nq per-query base residuals and
 // leaves with the systems' weights behind them.  The panel lives at chain_prior_layout's offsets from the start of
@@ -952,6 +967,194 @@ CpPanelOut chain_prior_panel_stage(L& l, const std::vector<int32_t>& cols, int32
   return out;
 }
 
+// The argument and state checks of the three per-query-prior calls, under the entry point's name `fn`; true when the call
+// carries a prior (lamP > 0).  The chains are looked at only when there are queries.
+bool chain_prior_call_check(L& l, const std::string& fn, int32_t Q, const int64_t* chain_offsets, const int32_t* chain_nodes,
+                            const float* chain_weights, float lamP, float tol, int32_t max_iters) {
+  if (l.comm) throw Unsupported(fn + ": lattices with a communicator are not supported");
+  require_graph(l);
+  if (!(lamP >= 0.f) || !std::isfinite(lamP)) throw Invalid(fn + ": lamP must be a finite value >= 0");
+  if (!(tol > 0.f) || !std::isfinite(tol)) throw Invalid(fn + ": tol must be > 0");
+  if (max_iters < 1) throw Invalid("max_iters must be >= 1");
+  if (l.chain_present) throw Invalid(fn + ": the lattice has a chain of its own (osc_clear_chain first)");
+  const bool prior = lamP > 0.f;
+  const auto& sh = l.query.shifted;
+  if (prior) {
+    if (!sh.have || sh.epoch != l.derived.epoch || sh.lamP != lamP)
+      throw StateError("no shifted query basis for this lamP and the current graph (call osc_query_basis_shifted first)");
+  } else {
+    require_basis(l);
+  }
+  if (Q <= 0) return prior;
+  int32_t where = 0;
+  switch (host::chain_many_check(chain_offsets, chain_nodes, Q, l.N, &where)) {
+    case 1:
+      throw Invalid(fn + ": query " + std::to_string(where) + ": a chain has 2 to " + std::to_string(host::kCorpusMaxChain) +
+                    " nodes, at offsets that start from 0");
+    case 2:
+      throw Invalid(fn + ": query " + std::to_string(where) + ": chain indices out of bounds");
+  }
+  where = host::chain_prior_check(chain_offsets, chain_nodes, Q);
+  if (where >= 0)
+    throw Invalid(fn + ": query " + std::to_string(where) + ": a chain has at most " +
+                  std::to_string(host::kChainPriorMaxNodes) + " distinct nodes");
+  if (chain_weights)
+    for (int64_t e = 0; e < host::chain_many_edge_at(chain_offsets, Q); ++e)
+      if (!std::isfinite(chain_weights[e])) throw Invalid(fn + ": non-finite chain weight");
+  return prior;
+}
+
+// the basis's own residual for one query: |r_X| + |psi|_inf |r_x|, NaN for a psi that holds one
+float chain_prior_base_res(const float* psi, int32_t D, float res_X, float res_x) {
+  float pinf = 0.f;
+  for (int32_t d = 0; d < D; ++d) {
+    const float v = std::fabs(psi[d]);
+    pinf = (v > pinf || v != v) ? v : pinf;
+  }
+  return res_X + pinf * res_x;
+}
+
+// what the Green's columns' solve of a call needs: the operator diag(d) - lamC W of M' (d in q.cp_diag), the graph, the
+// columns' stop and the forced column limit of a pass (OSC_CHAIN_PRIOR_COLS, read once per call; 0: none)
+struct CpSolve {
+  GmRowOp rop;
+  GmGraph g;
+  float tol_g;
+  int max_cols;
+};
+
+CpSolve chain_prior_solve_setup(L& l, float lamP, float tol) {
+  auto& q = l.query;
+  const auto& sh = q.shifted;
+  CpSolve sv{};
+  q.cp_diag.alloc((size_t)l.N);
+  launch_gm_row_diag(l.B.p, l.lamG + lamP + l.lamC, l.lamQ, (int32_t)l.N, q.cp_diag.p, l.stream);
+  sv.rop.d = q.cp_diag.p;
+  sv.rop.lamC = l.lamC;
+  sv.g = GmGraph{l.ell_col.p, l.ell_w.p, l.deg.p, l.width};
+  sv.tol_g = host::chain_prior_tol_g(tol, l.lamG, lamP, sh.max_X + sh.max_x * sh.scale);
+  env_num("OSC_CHAIN_PRIOR_COLS", sv.max_cols);
+  return sv;
+}
+
+// Queries [c0, c0 + nq) of a pass: their rows into q.cm_psi at pitch ld (through hpsi) and their base residuals into hflts
+void stage_pass_psi(L& l, const float* psis, int32_t c0, int32_t nq, float res_X, float res_x, std::vector<float>& hpsi,
+                    std::vector<float>& hflts) {
+  auto& q = l.query;
+  const int32_t D = l.D;
+  hpsi.assign((size_t)nq * l.ld, 0.f);
+  hflts.assign((size_t)nq, 0.f);
+  for (int32_t t = 0; t < nq; ++t) {
+    const float* p = psis + (size_t)(c0 + t) * D;
+    std::copy(p, p + D, hpsi.data() + (size_t)t * l.ld);
+    hflts[(size_t)t] = chain_prior_base_res(p, D, res_X, res_x);
+  }
+  q.cm_psi.alloc(hpsi.size());
+  HIP_CHECK(hipMemcpyAsync(q.cm_psi.p, hpsi.data(), hpsi.size() * 4, hipMemcpyHostToDevice, l.stream));
+}
+
+// host vectors the query staging reuses from pass to pass
+struct CpQueryScratch {
+  std::vector<float> hpsi, bt;
+  std::vector<double> pn2, pinv;
+};
+
+// The per-pass query staging of the bundle and receipt paths: stage_pass_psi, |psi|^2 and 1 / (|psi| + 1e-12) into q.pn2 and
+// q.pinv and, with_bt, the query-dot GEMM's operand into q.Bt (the caller has sized the three for a chunk)
+void stage_pass_queries(L& l, const float* psis, int32_t c0, int32_t nq, bool with_bt, float res_X, float res_x,
+                        CpQueryScratch& st, std::vector<float>& hflts) {
+  auto& q = l.query;
+  const int32_t D = l.D, kpad = query_kpad(D);
+  stage_pass_psi(l, psis, c0, nq, res_X, res_x, st.hpsi, hflts);
+  st.pn2.assign((size_t)nq, 0.0);
+  st.pinv.assign((size_t)nq, 0.0);
+  if (with_bt) st.bt.assign((size_t)query_qpad(nq) * kpad, 0.f);
+  for (int32_t t = 0; t < nq; ++t) {
+    const float* p = psis + (size_t)(c0 + t) * D;
+    double s = 0.0;
+    for (int32_t d = 0; d < D; ++d) s += (double)p[d] * (double)p[d];
+    st.pn2[(size_t)t] = s;
+    st.pinv[(size_t)t] = 1.0 / (std::sqrt(s) + 1e-12);
+    if (with_bt) std::copy(p, p + D, st.bt.data() + (size_t)t * kpad);
+  }
+  if (with_bt) HIP_CHECK(hipMemcpyAsync(q.Bt.p, st.bt.data(), st.bt.size() * 4, hipMemcpyHostToDevice, l.stream));
+  HIP_CHECK(hipMemcpyAsync(q.pn2.p, st.pn2.data(), (size_t)nq * 8, hipMemcpyHostToDevice, l.stream));
+  HIP_CHECK(hipMemcpyAsync(q.pinv.p, st.pinv.data(), (size_t)nq * 8, hipMemcpyHostToDevice, l.stream));
+}
+
+// Section 11.1's two GEMMs on the shifted basis: kappa (N x ks), the rows of every query's T_q V_q (q.cp_tv, msum of them)
+// against X' in the query-dot GEMM's tile and K order (btk: its packed operand), then section 11's query dots of the nq
+// queries staged in q.Bt into q.pm and q.align (the callers overwrite that align)
+void shifted_kappa_and_dots(L& l, int64_t msum, int32_t ks, float* kappa, float* btk, int32_t qs, int32_t nq) {
+  auto& q = l.query;
+  auto& sh = q.shifted;
+  const int32_t kpad = query_kpad(l.D);
+  launch_bp_pack(q.cp_tv.p, msum, query_qpad((int32_t)msum), l.D, l.ld, kpad, btk, l.stream);
+  QueryGemmArgs gk{};
+  gk.A = sh.X.p;
+  gk.Bt = btk;
+  gk.N = (int32_t)l.N;
+  gk.D = l.D;
+  gk.ld = l.ld;
+  gk.kpad = kpad;
+  gk.qs = ks;
+  gk.nq = (int32_t)msum;
+  gk.mode = 2;
+  gk.sqrt_deg = l.sqrt_deg.p;
+  gk.p = kappa;
+  launch_query_gemm(gk, l.stream);
+  QueryGemmArgs gp{};
+  gp.A = sh.X.p;
+  gp.Bt = q.Bt.p;
+  gp.N = (int32_t)l.N;
+  gp.D = l.D;
+  gp.ld = l.ld;
+  gp.kpad = kpad;
+  gp.qs = qs;
+  gp.nq = nq;
+  gp.mode = 0;
+  gp.x4 = sh.x4.p;
+  gp.xn2 = sh.xn2.p;
+  gp.sqrt_deg = l.sqrt_deg.p;
+  gp.pn2 = q.pn2.p;
+  gp.pinv = q.pinv.p;
+  gp.align = q.align.p;
+  gp.p = q.pm.p;
+  launch_query_gemm(gp, l.stream);
+}
+
+// BpArgs as far as the bundle and the receipt path fill it alike: the graph, the panel stage's outputs, the staged queries,
+// the pass's shape and its e / H blocks
+BpArgs bp_common_args(L& l, const CpPanelOut& po, int32_t qs, int32_t nq, int32_t mmax, double* e, double* H) {
+  auto& q = l.query;
+  BpArgs b{};
+  b.col = l.ell_col.p;
+  b.adj = l.ell_a.p;
+  b.deg = l.deg.p;
+  b.width = l.width;
+  b.N = (int32_t)l.N;
+  b.lamC = l.lamC;
+  b.sqrt_deg = l.sqrt_deg.p;
+  b.G = po.G;
+  b.TV = q.cp_tv.p;
+  b.psi = q.cm_psi.p;
+  b.q_sys = po.q_sys;
+  b.sys_m = po.sys_m;
+  b.sys_col_at = po.sys_col_at;
+  b.sys_cols = po.sys_cols;
+  b.tv_at = po.tv_at;
+  b.pn2 = q.pn2.p;
+  b.pinv = q.pinv.p;
+  b.D = l.D;
+  b.ld = l.ld;
+  b.qs = qs;
+  b.nq = nq;
+  b.gs = host::bundle_prior_group(mmax);
+  b.e = e;
+  b.H = H;
+  return b;
+}
+
 }  // namespace
 
 // Query q's answer is chain_receipt(chain_q) on the U* of M + lamP L_path,q = M' - S_q K_q S_q^T (M' = M + lamP I):
@@ -964,48 +1167,21 @@ void query_chain_prior_many(L& l, const float* psis, int32_t Q, const int64_t* c
                             const float* chain_weights, float lamP, float tol, int32_t max_iters, float z_th, float* z_struct,
                             float* z_path, float* r_struct, float* r_path, double* gain, int32_t* verdict, int32_t* weakest_k,
                             float* weakest_z, float* prior_res, int32_t* prior_iters) {
-  if (l.comm) throw Unsupported("osc_chain_prior_many: lattices with a communicator are not supported");
-  require_graph(l);
-  if (!(lamP >= 0.f) || !std::isfinite(lamP)) throw Invalid("osc_chain_prior_many: lamP must be a finite value >= 0");
-  if (!(tol > 0.f) || !std::isfinite(tol)) throw Invalid("osc_chain_prior_many: tol must be > 0");
-  if (max_iters < 1) throw Invalid("max_iters must be >= 1");
-  if (l.chain_present) throw Invalid("osc_chain_prior_many: the lattice has a chain of its own (osc_clear_chain first)");
-  const bool prior = lamP > 0.f;
+  const bool prior = chain_prior_call_check(l, "osc_chain_prior_many", Q, chain_offsets, chain_nodes, chain_weights, lamP, tol,
+                                            max_iters);
+  if (Q <= 0) return;
   auto& q = l.query;
   auto& sh = q.shifted;
-  if (prior) {
-    if (!sh.have || sh.epoch != l.derived.epoch || sh.lamP != lamP)
-      throw StateError("no shifted query basis for this lamP and the current graph (call osc_query_basis_shifted first)");
-  } else {
-    require_basis(l);
-  }
-  if (Q <= 0) return;
-  int32_t where = 0;
-  switch (host::chain_many_check(chain_offsets, chain_nodes, Q, l.N, &where)) {
-    case 1:
-      throw Invalid("osc_chain_prior_many: query " + std::to_string(where) + ": a chain has 2 to " +
-                    std::to_string(host::kCorpusMaxChain) + " nodes, at offsets that start from 0");
-    case 2:
-      throw Invalid("osc_chain_prior_many: query " + std::to_string(where) + ": chain indices out of bounds");
-  }
-  where = host::chain_prior_check(chain_offsets, chain_nodes, Q);
-  if (where >= 0)
-    throw Invalid("osc_chain_prior_many: query " + std::to_string(where) + ": a chain has at most " +
-                  std::to_string(host::kChainPriorMaxNodes) + " distinct nodes");
-  if (chain_weights)
-    for (int64_t e = 0; e < host::chain_many_edge_at(chain_offsets, Q); ++e)
-      if (!std::isfinite(chain_weights[e])) throw Invalid("osc_chain_prior_many: non-finite chain weight");
   const int32_t N = (int32_t)l.N, D = l.D;
   const int32_t* dev = permuted(l) ? l.inv_h.data() : nullptr;
   const float* const bX = prior ? sh.X.p : q.X.p;
   const float* const bx4 = prior ? sh.x4.p : q.x4.p;
   const float res_X = prior ? sh.res_X : q.res_X, res_x = prior ? sh.res_x : q.res_x;
+  const CpSolve sv = prior ? chain_prior_solve_setup(l, lamP, tol) : CpSolve{};
   // the passes: by the panel's budget with a prior, osc_chain_receipt_many's chunks without
   std::vector<host::ChainPriorPass> passes;
   if (prior) {
-    int max_cols = 0;
-    env_num("OSC_CHAIN_PRIOR_COLS", max_cols);
-    passes = host::chain_prior_passes(chain_offsets, chain_nodes, Q, N, kQueryChunk, max_cols, host::kChainPriorBudgetBytes);
+    passes = host::chain_prior_passes(chain_offsets, chain_nodes, Q, N, kQueryChunk, sv.max_cols, host::kChainPriorBudgetBytes);
   } else {
     for (int32_t c0 = 0; c0 < Q; c0 += kQueryChunk) {
       host::ChainPriorPass ps;
@@ -1013,16 +1189,6 @@ void query_chain_prior_many(L& l, const float* psis, int32_t Q, const int64_t* c
       ps.nq = std::min<int32_t>(kQueryChunk, Q - c0);
       passes.push_back(ps);
     }
-  }
-  GmRowOp rop{};
-  const GmGraph g{l.ell_col.p, l.ell_w.p, l.deg.p, l.width};
-  float tol_g = 0.f;
-  if (prior) {
-    q.cp_diag.alloc((size_t)N);
-    launch_gm_row_diag(l.B.p, l.lamG + lamP + l.lamC, l.lamQ, N, q.cp_diag.p, l.stream);
-    rop.d = q.cp_diag.p;
-    rop.lamC = l.lamC;
-    tol_g = host::chain_prior_tol_g(tol, l.lamG, lamP, sh.max_X + sh.max_x * sh.scale);
   }
   q.cm_eoff.alloc((size_t)kQueryChunk + 1);
   q.cm_gain.alloc(kQueryChunk);
@@ -1045,26 +1211,13 @@ void query_chain_prior_many(L& l, const float* psis, int32_t Q, const int64_t* c
       HIP_CHECK(hipMemcpyAsync(q.cm_pa.p, paths.pa.data(), paths.pa.size() * 4, hipMemcpyHostToDevice, l.stream));
     }
     const size_t nu = units.size();
-    hpsi.assign((size_t)nq * l.ld, 0.f);
-    for (int32_t t = 0; t < nq; ++t)
-      std::copy(psis + (size_t)(c0 + t) * D, psis + (size_t)(c0 + t + 1) * D, hpsi.data() + (size_t)t * l.ld);
-    q.cm_psi.alloc(hpsi.size());
+    // the rows of psi and the basis's own residual per query
+    stage_pass_psi(l, psis, c0, nq, res_X, res_x, hpsi, hflts);
     q.cm_units.alloc(nu);
     q.cm_edge.alloc(4 * nu);
     q.cm_term.alloc(2 * nu);
-    HIP_CHECK(hipMemcpyAsync(q.cm_psi.p, hpsi.data(), hpsi.size() * 4, hipMemcpyHostToDevice, l.stream));
     HIP_CHECK(hipMemcpyAsync(q.cm_units.p, units.data(), nu * sizeof(host::ChainManyUnit), hipMemcpyHostToDevice, l.stream));
     HIP_CHECK(hipMemcpyAsync(q.cm_eoff.p, eoff.data(), eoff.size() * 4, hipMemcpyHostToDevice, l.stream));
-    // the basis's own residual per query: |r_X| + |psi_q|_inf |r_x|
-    hflts.assign((size_t)nq, 0.f);
-    for (int32_t t = 0; t < nq; ++t) {
-      float pinf = 0.f;
-      for (int32_t d = 0; d < D; ++d) {
-        const float v = std::fabs(psis[(size_t)(c0 + t) * D + d]);
-        pinf = (v > pinf || v != v) ? v : pinf;
-      }
-      hflts[(size_t)t] = res_X + pinf * res_x;
-    }
     CmEdgesArgs e{};
     if (!prior) {
       for (int32_t t = 0; t < nq; ++t) {
@@ -1073,8 +1226,8 @@ void query_chain_prior_many(L& l, const float* psis, int32_t Q, const int64_t* c
       }
     } else {
       q.cp_scratch.alloc((size_t)host::chain_prior_layout(N, ps.qc).total);
-      const CpPanelOut po = chain_prior_panel_stage(l, ps.cols, ps.qc, nq, paths, path_of, hflts, dev, bX, bx4, lamP, tol_g,
-                                                    max_iters, rop, g, hs);
+      const CpPanelOut po = chain_prior_panel_stage(l, ps.cols, ps.qc, nq, paths, path_of, hflts, dev, bX, bx4, lamP, sv.tol_g,
+                                                    max_iters, sv.rop, sv.g, hs);
       float* const pres_d = po.prior_res;
       int32_t* const pit_d = po.prior_iters;
       HIP_CHECK(hipMemcpyAsync(prior_res + c0, pres_d, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
@@ -1179,48 +1332,16 @@ void query_bundle_prior_many(L& l, const float* psis, int32_t Q, const int64_t* 
                              const float* chain_weights, float lamP, float tol, int32_t max_iters, int32_t k, float alpha,
                              float lambda_div, int32_t* ids, float* score, float* align, float* prior_res,
                              int32_t* prior_iters) {
-  if (l.comm) throw Unsupported("osc_bundle_prior_many: lattices with a communicator are not supported");
-  require_graph(l);
-  if (!(lamP >= 0.f) || !std::isfinite(lamP)) throw Invalid("osc_bundle_prior_many: lamP must be a finite value >= 0");
-  if (!(tol > 0.f) || !std::isfinite(tol)) throw Invalid("osc_bundle_prior_many: tol must be > 0");
-  if (max_iters < 1) throw Invalid("max_iters must be >= 1");
-  if (l.chain_present) throw Invalid("osc_bundle_prior_many: the lattice has a chain of its own (osc_clear_chain first)");
-  const bool prior = lamP > 0.f;
+  const bool prior = chain_prior_call_check(l, "osc_bundle_prior_many", Q, chain_offsets, chain_nodes, chain_weights, lamP, tol,
+                                            max_iters);
+  if (Q <= 0) return;
   auto& q = l.query;
   auto& sh = q.shifted;
-  if (prior) {
-    if (!sh.have || sh.epoch != l.derived.epoch || sh.lamP != lamP)
-      throw StateError("no shifted query basis for this lamP and the current graph (call osc_query_basis_shifted first)");
-  } else {
-    require_basis(l);
-  }
-  if (Q <= 0) return;
-  int32_t where = 0;
-  switch (host::chain_many_check(chain_offsets, chain_nodes, Q, l.N, &where)) {
-    case 1:
-      throw Invalid("osc_bundle_prior_many: query " + std::to_string(where) + ": a chain has 2 to " +
-                    std::to_string(host::kCorpusMaxChain) + " nodes, at offsets that start from 0");
-    case 2:
-      throw Invalid("osc_bundle_prior_many: query " + std::to_string(where) + ": chain indices out of bounds");
-  }
-  where = host::chain_prior_check(chain_offsets, chain_nodes, Q);
-  if (where >= 0)
-    throw Invalid("osc_bundle_prior_many: query " + std::to_string(where) + ": a chain has at most " +
-                  std::to_string(host::kChainPriorMaxNodes) + " distinct nodes");
-  if (chain_weights)
-    for (int64_t e = 0; e < host::chain_many_edge_at(chain_offsets, Q); ++e)
-      if (!std::isfinite(chain_weights[e])) throw Invalid("osc_bundle_prior_many: non-finite chain weight");
   const int32_t N = (int32_t)l.N, D = l.D;
-  const float res_X = prior ? sh.res_X : q.res_X, res_x = prior ? sh.res_x : q.res_x;
-  auto base_res = [&](int32_t t) {  // the basis's own residual for query t: |r_X| + |psi_t|_inf |r_x|
-    float pinf = 0.f;
-    for (int32_t d = 0; d < D; ++d) pinf = std::max(pinf, std::fabs(psis[(size_t)t * D + d]));
-    return res_X + pinf * res_x;
-  };
   if (!prior) {
     query_bundle_many(l, psis, Q, k, alpha, lambda_div, ids, score, align);
     for (int32_t t = 0; t < Q; ++t) {
-      prior_res[t] = base_res(t);
+      prior_res[t] = chain_prior_base_res(psis + (size_t)t * D, D, q.res_X, q.res_x);
       prior_iters[t] = 0;
     }
     return;
@@ -1228,19 +1349,11 @@ void query_bundle_prior_many(L& l, const float* psis, int32_t Q, const int64_t* 
   const int32_t kk = (int32_t)std::min<int64_t>(std::max(k, 0), l.N);
   const int32_t kpad = query_kpad(D);
   const int32_t* dev = permuted(l) ? l.inv_h.data() : nullptr;
-  int max_cols = 0;
-  env_num("OSC_CHAIN_PRIOR_COLS", max_cols);
-  const std::vector<host::BundlePriorPass> passes = host::bundle_prior_passes(
-      chain_offsets, chain_nodes, Q, N, kpad, kQueryChunk, max_cols, host::kChainPriorBudgetBytes);
   ensure_yn(l);
   ensure_shifted_stats(l);
-  GmRowOp rop{};
-  const GmGraph g{l.ell_col.p, l.ell_w.p, l.deg.p, l.width};
-  q.cp_diag.alloc((size_t)N);
-  launch_gm_row_diag(l.B.p, l.lamG + lamP + l.lamC, l.lamQ, N, q.cp_diag.p, l.stream);
-  rop.d = q.cp_diag.p;
-  rop.lamC = l.lamC;
-  const float tol_g = host::chain_prior_tol_g(tol, l.lamG, lamP, sh.max_X + sh.max_x * sh.scale);
+  const CpSolve sv = chain_prior_solve_setup(l, lamP, tol);
+  const std::vector<host::ChainPriorPass> passes = host::bundle_prior_passes(
+      chain_offsets, chain_nodes, Q, N, kpad, kQueryChunk, sv.max_cols, host::kChainPriorBudgetBytes);
   q.Bt.alloc((size_t)query_qpad(kQueryChunk) * kpad);
   q.pn2.alloc(kQueryChunk);
   q.pinv.alloc(kQueryChunk);
@@ -1254,39 +1367,18 @@ void query_bundle_prior_many(L& l, const float* psis, int32_t Q, const int64_t* 
   CpHostScratch hs;
   std::vector<host::ChainManyUnit> units;
   std::vector<int32_t> eoff, path_of;
-  std::vector<float> hpsi, hflts, bt;
-  std::vector<double> pn2, pinv;
-  for (const host::BundlePriorPass& ps : passes) {
+  std::vector<float> hflts;
+  CpQueryScratch st;
+  for (const host::ChainPriorPass& ps : passes) {
     const int32_t c0 = ps.q0, nq = ps.nq;
     paths.clear();
     host::chain_many_units_weighted(chain_offsets, chain_nodes, chain_weights, c0, nq, dev, N, paths, units, eoff, path_of);
-    const int32_t qs = query_qs(nq), qpad = query_qpad(nq);
-    hpsi.assign((size_t)nq * l.ld, 0.f);
-    bt.assign((size_t)qpad * kpad, 0.f);
-    pn2.assign((size_t)nq, 0.0);
-    pinv.assign((size_t)nq, 0.0);
-    hflts.assign((size_t)nq, 0.f);
-    for (int32_t t = 0; t < nq; ++t) {
-      const float* p = psis + (size_t)(c0 + t) * D;
-      double s = 0.0;
-      for (int32_t c = 0; c < D; ++c) {
-        hpsi[(size_t)t * l.ld + c] = p[c];
-        bt[(size_t)t * kpad + c] = p[c];
-        s += (double)p[c] * (double)p[c];
-      }
-      pn2[(size_t)t] = s;
-      pinv[(size_t)t] = 1.0 / (std::sqrt(s) + 1e-12);
-      hflts[(size_t)t] = base_res(c0 + t);
-    }
-    q.cm_psi.alloc(hpsi.size());
-    HIP_CHECK(hipMemcpyAsync(q.cm_psi.p, hpsi.data(), hpsi.size() * 4, hipMemcpyHostToDevice, l.stream));
-    HIP_CHECK(hipMemcpyAsync(q.Bt.p, bt.data(), bt.size() * 4, hipMemcpyHostToDevice, l.stream));
-    HIP_CHECK(hipMemcpyAsync(q.pn2.p, pn2.data(), (size_t)nq * 8, hipMemcpyHostToDevice, l.stream));
-    HIP_CHECK(hipMemcpyAsync(q.pinv.p, pinv.data(), (size_t)nq * 8, hipMemcpyHostToDevice, l.stream));
+    const int32_t qs = query_qs(nq);
+    stage_pass_queries(l, psis, c0, nq, true, sh.res_X, sh.res_x, st, hflts);
     const host::BundlePriorLayout lay = host::bundle_prior_layout(N, ps.qc, ps.msum, nq, kpad);
     q.cp_scratch.alloc((size_t)lay.total);
     const CpPanelOut po = chain_prior_panel_stage(l, ps.cols, ps.qc, nq, paths, path_of, hflts, dev, sh.X.p, sh.x4.p, lamP,
-                                                  tol_g, max_iters, rop, g, hs);
+                                                  sv.tol_g, max_iters, sv.rop, sv.g, hs);
     HIP_CHECK(hipMemcpyAsync(prior_res + c0, po.prior_res, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
     HIP_CHECK(hipMemcpyAsync(prior_iters + c0, po.prior_iters, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
     if (kk <= 0) {
@@ -1299,72 +1391,16 @@ void query_bundle_prior_many(L& l, const float* psis, int32_t Q, const int64_t* 
     q.align.alloc((size_t)N * qs);
     q.pm.alloc((size_t)N * qs);
     q.cs.alloc((size_t)N * qs);
-    // kappa: the rows of every query's T_q V_q against X', in the query-dot GEMM's tile and K order
-    launch_bp_pack(q.cp_tv.p, ps.msum, query_qpad((int32_t)ps.msum), D, l.ld, kpad, btk, l.stream);
-    QueryGemmArgs gk{};
-    gk.A = sh.X.p;
-    gk.Bt = btk;
-    gk.N = N;
-    gk.D = D;
-    gk.ld = l.ld;
-    gk.kpad = kpad;
-    gk.qs = lay.ks;
-    gk.nq = (int32_t)ps.msum;
-    gk.mode = 2;
-    gk.sqrt_deg = l.sqrt_deg.p;
-    gk.p = kappa;
-    launch_query_gemm(gk, l.stream);
-    // p: section 11's query dots on the shifted basis (its align is overwritten below)
-    QueryGemmArgs gp{};
-    gp.A = sh.X.p;
-    gp.Bt = q.Bt.p;
-    gp.N = N;
-    gp.D = D;
-    gp.ld = l.ld;
-    gp.kpad = kpad;
-    gp.qs = qs;
-    gp.nq = nq;
-    gp.mode = 0;
-    gp.x4 = sh.x4.p;
-    gp.xn2 = sh.xn2.p;
-    gp.sqrt_deg = l.sqrt_deg.p;
-    gp.pn2 = q.pn2.p;
-    gp.pinv = q.pinv.p;
-    gp.align = q.align.p;
-    gp.p = q.pm.p;
-    launch_query_gemm(gp, l.stream);
-    BpArgs b{};
-    b.col = l.ell_col.p;
-    b.adj = l.ell_a.p;
-    b.deg = l.deg.p;
-    b.width = l.width;
-    b.N = N;
-    b.lamC = l.lamC;
-    b.sqrt_deg = l.sqrt_deg.p;
+    shifted_kappa_and_dots(l, ps.msum, lay.ks, kappa, btk, qs, nq);
+    BpArgs b = bp_common_args(l, po, qs, nq, ps.mmax, reinterpret_cast<double*>(base + lay.e),
+                              reinterpret_cast<double*>(base + lay.H));
     b.s = sh.s.p;
     b.xn2 = sh.xn2.p;
     b.c0 = sh.c0.p;
     b.c2 = sh.c2.p;
     b.p = q.pm.p;
-    b.G = po.G;
     b.kappa = kappa;
-    b.TV = q.cp_tv.p;
-    b.psi = q.cm_psi.p;
-    b.q_sys = po.q_sys;
-    b.sys_m = po.sys_m;
-    b.sys_col_at = po.sys_col_at;
-    b.sys_cols = po.sys_cols;
-    b.tv_at = po.tv_at;
-    b.pn2 = q.pn2.p;
-    b.pinv = q.pinv.p;
-    b.D = D;
-    b.ld = l.ld;
     b.ks = lay.ks;
-    b.qs = qs;
-    b.nq = nq;
-    b.gs = host::bundle_prior_group(ps.mmax);
-    b.e = reinterpret_cast<double*>(base + lay.e);
-    b.H = reinterpret_cast<double*>(base + lay.H);
     b.nu = reinterpret_cast<double*>(base + lay.nu);
     b.align = q.align.p;
     b.coh = q.cs.p;
@@ -1393,64 +1429,28 @@ void query_receipt_prior_many(L& l, const float* psis, int32_t Q, const int64_t*
                               int32_t null_cap, double* dH, double* coh_sum, double* anchor_sum, double* query_sum,
                               int32_t* null_total, int64_t* null_offsets, int32_t* i_out, int32_t* j_out, float* z_out,
                               float* r_out, int64_t capacity, float* prior_res, int32_t* prior_iters) {
-  if (l.comm) throw Unsupported("osc_receipt_prior_many: lattices with a communicator are not supported");
-  require_graph(l);
-  if (!(lamP >= 0.f) || !std::isfinite(lamP)) throw Invalid("osc_receipt_prior_many: lamP must be a finite value >= 0");
-  if (!(tol > 0.f) || !std::isfinite(tol)) throw Invalid("osc_receipt_prior_many: tol must be > 0");
-  if (max_iters < 1) throw Invalid("max_iters must be >= 1");
-  if (l.chain_present) throw Invalid("osc_receipt_prior_many: the lattice has a chain of its own (osc_clear_chain first)");
-  const bool prior = lamP > 0.f;
-  auto& q = l.query;
-  auto& sh = q.shifted;
-  if (prior) {
-    if (!sh.have || sh.epoch != l.derived.epoch || sh.lamP != lamP)
-      throw StateError("no shifted query basis for this lamP and the current graph (call osc_query_basis_shifted first)");
-  } else {
-    require_basis(l);
-  }
+  const bool prior = chain_prior_call_check(l, "osc_receipt_prior_many", Q, chain_offsets, chain_nodes, chain_weights, lamP,
+                                            tol, max_iters);
   if (Q <= 0) {
     if (null_offsets) null_offsets[0] = 0;
     return;
   }
-  int32_t where = 0;
-  switch (host::chain_many_check(chain_offsets, chain_nodes, Q, l.N, &where)) {
-    case 1:
-      throw Invalid("osc_receipt_prior_many: query " + std::to_string(where) + ": a chain has 2 to " +
-                    std::to_string(host::kCorpusMaxChain) + " nodes, at offsets that start from 0");
-    case 2:
-      throw Invalid("osc_receipt_prior_many: query " + std::to_string(where) + ": chain indices out of bounds");
-  }
-  where = host::chain_prior_check(chain_offsets, chain_nodes, Q);
-  if (where >= 0)
-    throw Invalid("osc_receipt_prior_many: query " + std::to_string(where) + ": a chain has at most " +
-                  std::to_string(host::kChainPriorMaxNodes) + " distinct nodes");
-  if (chain_weights)
-    for (int64_t e = 0; e < host::chain_many_edge_at(chain_offsets, Q); ++e)
-      if (!std::isfinite(chain_weights[e])) throw Invalid("osc_receipt_prior_many: non-finite chain weight");
+  auto& q = l.query;
+  auto& sh = q.shifted;
   const int32_t N = (int32_t)l.N, D = l.D;
   const size_t n = (size_t)l.N;
-  const float res_X = prior ? sh.res_X : q.res_X, res_x = prior ? sh.res_x : q.res_x;
-  auto base_res = [&](int32_t t) {  // the basis's own residual for query t: |r_X| + |psi_t|_inf |r_x|
-    float pinf = 0.f;
-    for (int32_t d = 0; d < D; ++d) pinf = std::max(pinf, std::fabs(psis[(size_t)t * D + d]));
-    return res_X + pinf * res_x;
-  };
   if (!prior) {
     query_receipt_many(l, psis, Q, detail, z_th, null_cap, dH, coh_sum, anchor_sum, query_sum, null_total, null_offsets, i_out,
                        j_out, z_out, r_out, capacity);
     for (int32_t t = 0; t < Q; ++t) {
-      prior_res[t] = base_res(t);
+      prior_res[t] = chain_prior_base_res(psis + (size_t)t * D, D, q.res_X, q.res_x);
       prior_iters[t] = 0;
     }
     return;
   }
   const bool full = detail != 0;
   // the shifted slot's per-basis terms (section 12's, with lamG + lamP in lamG's place) and, full detail, its row constants
-  const float lamG0 = l.lamG;
-  OpParams op{};
-  l.lamG = lamG0 + lamP;
-  op = ustar_op(l);
-  l.lamG = lamG0;
+  const OpParams op = shifted_ustar_op(l, lamP);
   ensure_receipt_terms(l, sh, op, full);
   if (full) ensure_shifted_stats(l);
   // per call: h1' = E0'^T (M' x') over E0' = U - X' - x' psi0^T, and h0' = tr(E0'^T M' E0') through the operator's quad form
@@ -1478,14 +1478,10 @@ void query_receipt_prior_many(L& l, const float* psis, int32_t Q, const int64_t*
   HIP_CHECK(hipMemcpyAsync(h1.data(), q.rsum.p, h1.size() * 8, hipMemcpyDeviceToHost, l.stream));
   sync(l);
   double h0 = 0.0;
-  l.lamG = lamG0 + lamP;
-  try {
+  {
+    const ShiftedLamG shifted(l, lamP);
     h0 = quad_form_of_difference(l, u_read(l), q.U0.p);
-  } catch (...) {
-    l.lamG = lamG0;
-    throw;
   }
-  l.lamG = lamG0;
   std::vector<double> hbase((size_t)8 + 3 * (size_t)D, 0.0);
   hbase[0] = h0;
   hbase[1] = sh.rm_h2;
@@ -1506,18 +1502,10 @@ void query_receipt_prior_many(L& l, const float* psis, int32_t Q, const int64_t*
   const int32_t* dev = permuted(l) ? l.inv_h.data() : nullptr;
   const int32_t* inv = permuted(l) ? l.inv_d.p : nullptr;
   const int cparts = rm_col_parts(l.N), cgroups = rm_finish_groups(cparts);
-  int max_cols = 0;
-  env_num("OSC_CHAIN_PRIOR_COLS", max_cols);
-  const std::vector<host::ReceiptPriorPass> passes =
-      host::receipt_prior_passes(chain_offsets, chain_nodes, Q, N, kpad, l.ld, full, cparts, cgroups, kQueryChunk, max_cols,
+  const CpSolve sv = chain_prior_solve_setup(l, lamP, tol);
+  const std::vector<host::ChainPriorPass> passes =
+      host::receipt_prior_passes(chain_offsets, chain_nodes, Q, N, kpad, l.ld, full, cparts, cgroups, kQueryChunk, sv.max_cols,
                                  host::kChainPriorBudgetBytes);
-  GmRowOp rop{};
-  const GmGraph g{l.ell_col.p, l.ell_w.p, l.deg.p, l.width};
-  q.cp_diag.alloc((size_t)N);
-  launch_gm_row_diag(l.B.p, l.lamG + lamP + l.lamC, l.lamQ, N, q.cp_diag.p, l.stream);
-  rop.d = q.cp_diag.p;
-  rop.lamC = l.lamC;
-  const float tol_g = host::chain_prior_tol_g(tol, l.lamG, lamP, sh.max_X + sh.max_x * sh.scale);
   q.pn2.alloc(kQueryChunk);
   q.pinv.alloc(kQueryChunk);
   if (full) {
@@ -1531,43 +1519,23 @@ void query_receipt_prior_many(L& l, const float* psis, int32_t Q, const int64_t*
   CpHostScratch hs;
   std::vector<host::ChainManyUnit> units;
   std::vector<int32_t> eoff, path_of, tot;
-  std::vector<float> hpsi, hflts, bt;
-  std::vector<double> pn2, pinv, hscal, csum;
+  std::vector<float> hflts;
+  std::vector<double> hscal, csum;
+  CpQueryScratch st;
   std::vector<int64_t> hgat;
   DevBuf<int64_t> gat;
   null_offsets[0] = 0;
-  for (const host::ReceiptPriorPass& ps : passes) {
+  for (const host::ChainPriorPass& ps : passes) {
     const int32_t c0 = ps.q0, nq = ps.nq;
     paths.clear();
     host::chain_many_units_weighted(chain_offsets, chain_nodes, chain_weights, c0, nq, dev, N, paths, units, eoff, path_of);
-    const int32_t qs = query_qs(nq), qpad = query_qpad(nq);
-    hpsi.assign((size_t)nq * l.ld, 0.f);
-    if (full) bt.assign((size_t)qpad * kpad, 0.f);
-    pn2.assign((size_t)nq, 0.0);
-    pinv.assign((size_t)nq, 0.0);
-    hflts.assign((size_t)nq, 0.f);
-    for (int32_t t = 0; t < nq; ++t) {
-      const float* p = psis + (size_t)(c0 + t) * D;
-      double s = 0.0;
-      for (int32_t d = 0; d < D; ++d) {
-        hpsi[(size_t)t * l.ld + d] = p[d];
-        if (full) bt[(size_t)t * kpad + d] = p[d];
-        s += (double)p[d] * (double)p[d];
-      }
-      pn2[(size_t)t] = s;
-      pinv[(size_t)t] = 1.0 / (std::sqrt(s) + 1e-12);
-      hflts[(size_t)t] = base_res(c0 + t);
-    }
-    q.cm_psi.alloc(hpsi.size());
-    HIP_CHECK(hipMemcpyAsync(q.cm_psi.p, hpsi.data(), hpsi.size() * 4, hipMemcpyHostToDevice, l.stream));
-    if (full) HIP_CHECK(hipMemcpyAsync(q.Bt.p, bt.data(), bt.size() * 4, hipMemcpyHostToDevice, l.stream));
-    HIP_CHECK(hipMemcpyAsync(q.pn2.p, pn2.data(), (size_t)nq * 8, hipMemcpyHostToDevice, l.stream));
-    HIP_CHECK(hipMemcpyAsync(q.pinv.p, pinv.data(), (size_t)nq * 8, hipMemcpyHostToDevice, l.stream));
+    const int32_t qs = query_qs(nq);
+    stage_pass_queries(l, psis, c0, nq, full, sh.res_X, sh.res_x, st, hflts);
     const host::ReceiptPriorLayout lay =
         host::receipt_prior_layout(N, ps.qc, ps.msum, ps.msq, nq, kpad, l.ld, full, cparts, cgroups);
     q.cp_scratch.alloc((size_t)lay.total);
     const CpPanelOut po = chain_prior_panel_stage(l, ps.cols, ps.qc, nq, paths, path_of, hflts, dev, sh.X.p, sh.x4.p, lamP,
-                                                  tol_g, max_iters, rop, g, hs);
+                                                  sv.tol_g, max_iters, sv.rop, sv.g, hs);
     // where each system's m x m Gram entries start (their sum is at most the pass's msq: distinct systems, one query each at least)
     hgat.assign(hs.sys.m.size(), 0);
     int64_t gtot = 0;
@@ -1579,31 +1547,8 @@ void query_receipt_prior_many(L& l, const float* psis, int32_t Q, const int64_t*
     gat.alloc(std::max<size_t>(hgat.size(), 1));
     HIP_CHECK(hipMemcpyAsync(gat.p, hgat.data(), hgat.size() * 8, hipMemcpyHostToDevice, l.stream));
     char* const base = q.cp_scratch.p;
-    BpArgs b{};
-    b.col = l.ell_col.p;
-    b.adj = l.ell_a.p;
-    b.deg = l.deg.p;
-    b.width = l.width;
-    b.N = N;
-    b.lamC = l.lamC;
-    b.sqrt_deg = l.sqrt_deg.p;
-    b.G = po.G;
-    b.TV = q.cp_tv.p;
-    b.psi = q.cm_psi.p;
-    b.q_sys = po.q_sys;
-    b.sys_m = po.sys_m;
-    b.sys_col_at = po.sys_col_at;
-    b.sys_cols = po.sys_cols;
-    b.tv_at = po.tv_at;
-    b.pn2 = q.pn2.p;
-    b.pinv = q.pinv.p;
-    b.D = D;
-    b.ld = l.ld;
-    b.qs = qs;
-    b.nq = nq;
-    b.gs = host::bundle_prior_group(ps.mmax);
-    b.e = reinterpret_cast<double*>(base + lay.e);
-    b.H = reinterpret_cast<double*>(base + lay.H);
+    BpArgs b = bp_common_args(l, po, qs, nq, ps.mmax, reinterpret_cast<double*>(base + lay.e),
+                              reinterpret_cast<double*>(base + lay.H));
     launch_bp_scalars(b, l.stream);
     double* const scal = reinterpret_cast<double*>(base + lay.scal);
     RpScalArgs sa{};
@@ -1676,38 +1621,7 @@ void query_receipt_prior_many(L& l, const float* psis, int32_t Q, const int64_t*
       float* const btk = reinterpret_cast<float*>(base + lay.bt);
       q.align.alloc(n * qs);
       q.pm.alloc(n * qs);
-      launch_bp_pack(q.cp_tv.p, ps.msum, query_qpad((int32_t)ps.msum), D, l.ld, kpad, btk, l.stream);
-      QueryGemmArgs gk{};
-      gk.A = sh.X.p;
-      gk.Bt = btk;
-      gk.N = N;
-      gk.D = D;
-      gk.ld = l.ld;
-      gk.kpad = kpad;
-      gk.qs = lay.ks;
-      gk.nq = (int32_t)ps.msum;
-      gk.mode = 2;
-      gk.sqrt_deg = l.sqrt_deg.p;
-      gk.p = kappa;
-      launch_query_gemm(gk, l.stream);
-      QueryGemmArgs gp{};
-      gp.A = sh.X.p;
-      gp.Bt = q.Bt.p;
-      gp.N = N;
-      gp.D = D;
-      gp.ld = l.ld;
-      gp.kpad = kpad;
-      gp.qs = qs;
-      gp.nq = nq;
-      gp.mode = 0;
-      gp.x4 = sh.x4.p;
-      gp.xn2 = sh.xn2.p;
-      gp.sqrt_deg = l.sqrt_deg.p;
-      gp.pn2 = q.pn2.p;
-      gp.pinv = q.pinv.p;
-      gp.align = q.align.p;
-      gp.p = q.pm.p;
-      launch_query_gemm(gp, l.stream);
+      shifted_kappa_and_dots(l, ps.msum, lay.ks, kappa, btk, qs, nq);
       b.s = sh.s.p;
       b.xn2 = sh.xn2.p;
       b.c0 = sh.c0.p;

@@ -1,8 +1,8 @@
 // The host plan of osc_receipt_prior_many: receipt() of Q (query, chain prior) pairs on a resident
 // lattice.  HIP-free: osc_query.hip runs it, tests/host_logic/sweep_receipt_prior_plan.cpp sweeps it under the sanitizers.
 //
-// A pass is bundle_prior_plan.hpp's: a run of consecutive queries, one panel column per distinct chain node of the pass, a
-// query never split.  Its block holds, behind bundle_prior_layout's arrays, the per-query Gram blocks and scalars of deltaH
+// A pass is chain_prior_plan.hpp's ChainPriorPass, cut by its packer: a run of consecutive queries, one panel column per
+// distinct chain node of the pass, a query never split.  Its block holds, behind bundle_prior_layout's arrays, the per-query Gram blocks and scalars of deltaH
 // and -- full detail only -- the moments of the Green's columns (partials per (part, slab) for mom_slabs slabs at a time,
 // then one row of wout doubles per column), the chains' Gram partials and the per-(row, query) arrays of the row pass and
 // the null-point stage.  A light pass holds the panel and the per-query scalars alone.  The rows are cut by section 17's
@@ -106,49 +106,13 @@ inline ReceiptPriorLayout receipt_prior_layout(int64_t N, int32_t qc, int64_t ms
   return L;
 }
 
-struct ReceiptPriorPass {
-  int32_t q0 = 0, nq = 0;
-  int32_t qc = 0;             // panel columns: cols.size() rounded up to 32
-  int64_t msum = 0, msq = 0;  // sums of the queries' distinct node counts and of their squares
-  int32_t mmax = 0;
-  std::vector<int32_t> cols;  // the node (an API id) of every panel column, first seen first
-};
-
-// Passes over queries [0, Q): at most max_queries queries and max_cols distinct nodes each (max_cols <= 0: no limit beside the
-// budget), layout.resident within `budget` bytes unless the pass holds one query.
-inline std::vector<ReceiptPriorPass> receipt_prior_passes(const int64_t* off, const int32_t* nodes, int32_t Q, int64_t N,
-                                                          int32_t kpad, int32_t ld, bool full, int32_t cparts, int32_t cgroups,
-                                                          int32_t max_queries, int32_t max_cols, int64_t budget) {
-  std::vector<ReceiptPriorPass> out;
-  std::map<int32_t, int32_t> at;
-  ReceiptPriorPass cur;
-  auto close = [&]() {
-    if (cur.nq == 0) return;
-    cur.qc = gates_width((int32_t)cur.cols.size());
-    out.push_back(std::move(cur));
-    cur = ReceiptPriorPass{};
-    at.clear();
-  };
-  for (int32_t q = 0; q < Q; ++q) {
-    const std::vector<int32_t> d = chain_prior_distinct(nodes + off[q], off[q + 1] - off[q]);
-    const int64_t m = (int64_t)d.size();
-    int32_t fresh = 0;
-    for (int32_t v : d) fresh += at.count(v) ? 0 : 1;
-    const int32_t want = (int32_t)cur.cols.size() + fresh;
-    const bool fits = cur.nq < std::max(max_queries, 1) && (max_cols <= 0 || want <= max_cols) &&
-                      receipt_prior_layout(N, gates_width(want), cur.msum + m, cur.msq + m * m, cur.nq + 1, kpad, ld, full,
-                                           cparts, cgroups).resident <= budget;
-    if (cur.nq > 0 && !fits) close();
-    if (cur.nq == 0) cur.q0 = q;
-    for (int32_t v : d)
-      if (at.emplace(v, (int32_t)cur.cols.size()).second) cur.cols.push_back(v);
-    cur.msum += m;
-    cur.msq += m * m;
-    cur.mmax = std::max(cur.mmax, (int32_t)m);
-    ++cur.nq;
-  }
-  close();
-  return out;
+// Passes over queries [0, Q) by chain_prior_pack: layout.resident within `budget` bytes unless the pass holds one query.
+inline std::vector<ChainPriorPass> receipt_prior_passes(const int64_t* off, const int32_t* nodes, int32_t Q, int64_t N,
+                                                        int32_t kpad, int32_t ld, bool full, int32_t cparts, int32_t cgroups,
+                                                        int32_t max_queries, int32_t max_cols, int64_t budget) {
+  return chain_prior_pack(off, nodes, Q, max_queries, max_cols, [&](int32_t qc, int64_t msum, int64_t msq, int32_t nq) {
+    return receipt_prior_layout(N, qc, msum, msq, nq, kpad, ld, full, cparts, cgroups).resident <= budget;
+  });
 }
 
 }  // namespace host

@@ -842,18 +842,7 @@ class OscillinkLattice:
         go to `last_bundle_prior` = {"lamP", "res" (float32), "iters" (int32)}.  `lamP=0` is the plain call."""
         if self._has_comm:
             raise NotImplementedError("bundle_many: lattices with a communicator (sharded / multi-rank) are not supported")
-        prior = chains is not None or lamP is not None
-        if prior:
-            if lamP is None:
-                raise ValueError("chains given without lamP")
-            if chains is None:
-                raise ValueError("lamP given without chains")
-            if not np.isfinite(float(lamP)) or float(lamP) < 0:
-                raise ValueError("lamP must be >= 0")
-            if self._chain_nodes is not None:
-                raise ValueError("bundle_many with lamP: the lattice has a chain of its own (clear_chain first)")
-        elif chain_weights is not None:
-            raise ValueError("chain_weights given without chains and lamP")
+        prior = rc.check_prior_args("bundle_many", chains, lamP, chain_weights, self._chain_nodes is not None)
         P = rc.check_queries(psis, self.D)
         Q = int(P.shape[0])
         kk = min(int(k), self.N) if k > 0 else 0
@@ -861,15 +850,7 @@ class OscillinkLattice:
         score = np.zeros((Q, kk), dtype=np.float32)
         align = np.zeros((Q, kk), dtype=np.float32)
         if prior:
-            lists, offsets, nodes = rc.chain_block(chains, Q, self.N)
-            edge_offsets = offsets - np.arange(Q + 1, dtype=np.int64)
-            weights = rc.chain_prior_weights(chain_weights, chains, lists, edge_offsets)
-            checked = set()  # (a shared chain is one list Q times)
-            for q, ch in enumerate(lists):
-                if id(ch) not in checked and len(set(ch)) > rc.MAX_PRIOR_NODES:
-                    raise ValueError(f"query {q}: with lamP a chain has at most {rc.MAX_PRIOR_NODES} distinct nodes, got "
-                                     f"{len(set(ch))}")
-                checked.add(id(ch))
+            _, offsets, nodes, weights = rc.prior_chain_block(chains, chain_weights, Q, self.N)
             prior_res, prior_iters = np.zeros(Q, dtype=np.float32), np.zeros(Q, dtype=np.int32)
             if Q > 0 and kk > 0:
                 psi_inf = float(np.max(np.abs(P)))
@@ -883,11 +864,7 @@ class OscillinkLattice:
                            nat.i32(prior_iters))
                 self._qbs_stats = self._qbs_stats or float(lamP) > 0
             self.last_bundle_prior = {"lamP": float(lamP), "res": prior_res, "iters": prior_iters}
-            over = np.nonzero(~(prior_res <= tol))[0]
-            if over.size:
-                self._log("chain_prior_convergence_warn", {"queries": int(over.size), "first": int(over[0]),
-                                                           "res": float(prior_res[over[0]]), "tol": tol,
-                                                           "iters": int(prior_iters[over[0]])})
+            self._warn_chain_prior(prior_res, prior_iters, tol)
         elif Q > 0 and kk > 0:
             self._ensure_query_basis(tol, max_iters, float(np.max(np.abs(P))))
             self._call("osc_bundle_many", nat.f32(P), Q, kk, float(alpha), 0.5, nat.i32(ids), nat.f32(score), nat.f32(align))
@@ -920,31 +897,12 @@ class OscillinkLattice:
         (int32); both also go to `last_receipt_prior` = {"lamP", "res", "iters"}.  `lamP=0` gives the plain call's numbers."""
         if self._has_comm:
             raise NotImplementedError("receipt_many: lattices with a communicator (sharded / multi-rank) are not supported")
-        prior = chains is not None or lamP is not None
-        if prior:
-            if lamP is None:
-                raise ValueError("chains given without lamP")
-            if chains is None:
-                raise ValueError("lamP given without chains")
-            if not np.isfinite(float(lamP)) or float(lamP) < 0:
-                raise ValueError("lamP must be >= 0")
-            if self._chain_nodes is not None:
-                raise ValueError("receipt_many with lamP: the lattice has a chain of its own (clear_chain first)")
-        elif chain_weights is not None:
-            raise ValueError("chain_weights given without chains and lamP")
+        prior = rc.check_prior_args("receipt_many", chains, lamP, chain_weights, self._chain_nodes is not None)
         P = rc.check_queries(psis, self.D)
         Q = int(P.shape[0])
         lists = None
         if prior:
-            lists, offsets, nodes = rc.chain_block(chains, Q, self.N)
-            edge_offsets = offsets - np.arange(Q + 1, dtype=np.int64)
-            weights = rc.chain_prior_weights(chain_weights, chains, lists, edge_offsets)
-            checked = set()  # (a shared chain is one list Q times)
-            for q, ch in enumerate(lists):
-                if id(ch) not in checked and len(set(ch)) > rc.MAX_PRIOR_NODES:
-                    raise ValueError(f"query {q}: with lamP a chain has at most {rc.MAX_PRIOR_NODES} distinct nodes, got "
-                                     f"{len(set(ch))}")
-                checked.add(id(ch))
+            lists, offsets, nodes, weights = rc.prior_chain_block(chains, chain_weights, Q, self.N)
         shifted = prior and float(lamP) > 0
         full = self._receipt_detail != "light"
         cap_val = rc.null_cap()
@@ -974,11 +932,7 @@ class OscillinkLattice:
             self.last_receipt_prior = {"lamP": float(lamP), "res": prior_res, "iters": prior_iters}
         self._log("receipt_many", payload)
         if prior:
-            over = np.nonzero(~(prior_res <= tol))[0]
-            if over.size:
-                self._log("chain_prior_convergence_warn", {"queries": int(over.size), "first": int(over[0]),
-                                                           "res": float(prior_res[over[0]]), "tol": tol,
-                                                           "iters": int(prior_iters[over[0]])})
+            self._warn_chain_prior(prior_res, prior_iters, tol)
         if as_arrays:
             out = {**ra.scalar_arrays(), **ra.null_arrays()}
             if prior:
@@ -1058,24 +1012,15 @@ class OscillinkLattice:
         if not prior and chain_weights is not None:
             raise ValueError("chain_weights given without lamP")
         if prior:
-            if not np.isfinite(float(lamP)) or float(lamP) < 0:
-                raise ValueError("lamP must be >= 0")
-            if self._chain_nodes is not None:
-                raise ValueError("chain_receipt_many with lamP: the lattice has a chain of its own (clear_chain first)")
+            rc.check_prior_lamP("chain_receipt_many", lamP, self._chain_nodes is not None)
         P = rc.check_queries(psis, self.D, finite=False)
         Q = int(P.shape[0])
-        lists, offsets, nodes = rc.chain_block(chains, Q, self.N)
+        if prior:
+            lists, offsets, nodes, weights = rc.prior_chain_block(chains, chain_weights, Q, self.N)
+        else:
+            (lists, offsets, nodes), weights = rc.chain_block(chains, Q, self.N), None
         edge_offsets = offsets - np.arange(Q + 1, dtype=np.int64)
         n_edges = int(edge_offsets[-1])
-        weights = None
-        if prior:
-            weights = rc.chain_prior_weights(chain_weights, chains, lists, edge_offsets)
-            checked = set()  # (a shared chain is one list Q times)
-            for q, ch in enumerate(lists):
-                if id(ch) not in checked and len(set(ch)) > rc.MAX_PRIOR_NODES:
-                    raise ValueError(f"query {q}: with lamP a chain has at most {rc.MAX_PRIOR_NODES} distinct nodes, got "
-                                     f"{len(set(ch))}")
-                checked.add(id(ch))
         edge = np.zeros((4, max(n_edges, 1)), dtype=np.float32)
         gain = np.zeros(Q, dtype=np.float64)
         verdict, weak_k = np.zeros(Q, dtype=np.int32), np.zeros(Q, dtype=np.int32)
@@ -1102,12 +1047,8 @@ class OscillinkLattice:
         if prior:
             payload["lamP"] = float(lamP)
         self._log("chain_receipt_many", payload)
-        if prior and Q > 0:
-            over = np.nonzero(~(prior_res <= tol) & np.all(np.isfinite(P), axis=1))[0]
-            if over.size:
-                self._log("chain_prior_convergence_warn", {"queries": int(over.size), "first": int(over[0]),
-                                                           "res": float(prior_res[over[0]]), "tol": tol,
-                                                           "iters": int(prior_iters[over[0]])})
+        if prior:  # (a non-finite query's bound is non-finite by design)
+            self._warn_chain_prior(prior_res, prior_iters, tol, rows=np.all(np.isfinite(P), axis=1))
         arr = dict(chain_offsets=edge_offsets, chain_z_struct=edge[0, :n_edges].copy(), chain_z_path=edge[1, :n_edges].copy(),
                    chain_r_struct=edge[2, :n_edges].copy(), chain_r_path=edge[3, :n_edges].copy(), chain_gain=gain,
                    chain_verdict=verdict != 0, chain_weakest_k=weak_k, chain_weakest_z=weak_z)
@@ -1116,6 +1057,15 @@ class OscillinkLattice:
         if prior:
             arr.update(chain_prior_res=prior_res, chain_prior_iters=prior_iters)
         return arr
+
+    def _warn_chain_prior(self, prior_res: np.ndarray, prior_iters: np.ndarray, tol: float, rows=None) -> None:
+        """Log the queries (of `rows`, a boolean mask, when given) whose residual bound is not within `tol`."""
+        over = ~(prior_res <= tol)
+        over = np.nonzero(over if rows is None else over & rows)[0]
+        if over.size:
+            self._log("chain_prior_convergence_warn", {"queries": int(over.size), "first": int(over[0]),
+                                                       "res": float(prior_res[over[0]]), "tol": tol,
+                                                       "iters": int(prior_iters[over[0]])})
 
     def _ensure_shifted_basis(self, lamP: float, tol: float, max_iters: int, psi_inf: float) -> bool:
         """Solve (or extend) the basis of the shifted operator M + lamP I in its own slot unless the resident one serves

@@ -3,44 +3,26 @@
 // column of its pass, once; msum is the sum of the queries' distinct node counts; a pass of more than one query keeps its
 // resident bytes within the budget, its queries within the chunk and its columns within the forced limit; the arrays of a
 // layout are 256-byte aligned, pairwise disjoint, inside the block and large enough for what the kernels index (kappa's
-// last column of the last query, the GEMM operand's last padded row).  Run under -fsanitize=address,undefined.
-#include <cstdio>
+// last column of the last query, the GEMM operand's last padded row); the passes are the greedy ones and their columns stand
+// in first-seen order (sweep_prior_common.hpp).  Run under -fsanitize=address,undefined.
 #include <cstdlib>
-#include <set>
-#include <vector>
 
 #include "../../oscillink_amd/csrc/bundle_prior_plan.hpp"
-
-using namespace osc::host;
-
-static int fail(const char* what, long long a, long long b) {
-  std::printf("ERROR %s (%lld, %lld)\n", what, a, b);
-  return 1;
-}
-
-struct Block {
-  long long at, bytes;
-};
+#include "sweep_prior_common.hpp"
 
 static int check_layout(long long N, int qc, long long msum, int nq, int kpad) {
   const BundlePriorLayout L = bundle_prior_layout(N, qc, msum, nq, kpad);
   if (L.ks % 4 != 0 || L.ks < msum || L.ks >= msum + 4) return fail("kappa pitch", L.ks, msum);
   if (L.qs % 4 != 0 || L.qs < nq || L.qs >= nq + 4) return fail("query pitch", L.qs, nq);
   const long long rows_pad = (msum + 127) / 128 * 128;
-  const Block b[] = {{0, L.panel.total},
-                     {L.kappa, N * (long long)L.ks * 4},
-                     {L.nu, N * (long long)L.qs * 8},
-                     {L.bt, rows_pad * kpad * 4},
-                     {L.e, nq * 64LL * 8},
-                     {L.H, nq * 4096LL * 8}};
-  long long end = 0;
-  for (int i = 0; i < (int)(sizeof b / sizeof b[0]); ++i) {
-    if (b[i].at % 256 != 0) return fail("alignment", i, b[i].at);
-    if (b[i].at < end) return fail("blocks overlap", i, b[i].at);
-    if (b[i].bytes <= 0) return fail("empty block", i, b[i].bytes);
-    end = b[i].at + b[i].bytes;
-  }
-  if (end > L.total) return fail("block passes total", end, L.total);
+  if (check_blocks({{0, L.panel.total},
+                    {L.kappa, N * (long long)L.ks * 4},
+                    {L.nu, N * (long long)L.qs * 8},
+                    {L.bt, rows_pad * kpad * 4},
+                    {L.e, nq * 64LL * 8},
+                    {L.H, nq * 4096LL * 8}},
+                   L.total))
+    return 1;
   if (L.resident < L.total + 3 * N * (long long)L.qs * 4) return fail("resident bytes leave out section 11's arrays", L.resident, L.total);
   // the panel's own offsets are chain_prior_layout's: osc_chain_prior_many's stage addresses them from the block's start
   const ChainPriorLayout P = chain_prior_layout(N, qc);
@@ -50,76 +32,23 @@ static int check_layout(long long N, int qc, long long msum, int nq, int kpad) {
   return 0;
 }
 
-static unsigned long long rng_state = 88172645463325252ULL;
-static unsigned rnd(unsigned n) {
-  rng_state ^= rng_state << 13;
-  rng_state ^= rng_state >> 7;
-  rng_state ^= rng_state << 17;
-  return (unsigned)(rng_state % n);
-}
-
-// Q chains on N rows: kind 0 one chain of m distinct nodes shared by all, 1 a chain per query (2..9 nodes, repeats), 2 a chain
-// of m distinct nodes per query
-static void make_chains(long long N, int Q, int kind, int m, std::vector<int64_t>& off, std::vector<int>& nodes) {
-  off.assign(1, 0);
-  nodes.clear();
-  std::vector<int> shared;
-  for (int q = 0; q < Q; ++q) {
-    std::vector<int> ch;
-    if (kind == 0 && !shared.empty()) {
-      ch = shared;
-    } else if (kind == 1) {
-      const int len = 2 + (int)rnd(8);
-      for (int t = 0; t < len; ++t) ch.push_back((int)rnd((unsigned)std::min<long long>(N, 1 << 30)));
-      if (len > 3) ch[3] = ch[1];  // a revisit
-    } else {
-      const long long mm = std::min<long long>(N, m);
-      const long long start = N > mm ? rnd((unsigned)(N - mm)) : 0;
-      for (long long t = 0; t < mm; ++t) ch.push_back((int)(start + t));
-      ch.push_back(ch[0]);
-    }
-    if (kind == 0) shared = ch;
-    nodes.insert(nodes.end(), ch.begin(), ch.end());
-    off.push_back((int64_t)nodes.size());
-  }
-}
-
+// kind 0 one chain of m distinct nodes shared by all, 1 a chain per query (2..9 nodes, repeats), 2 a chain of m distinct nodes
+// per query
 static int check_passes(long long N, int Q, int kind, int m, int kpad, int max_queries, int max_cols, long long budget) {
   std::vector<int64_t> off;
   std::vector<int> nodes;
-  make_chains(N, Q, kind, m, off, nodes);
+  make_chains(N, Q, kind == 0, kind == 1 ? 0 : m, off, nodes);
   if (chain_prior_check(off.data(), nodes.data(), Q) != -1) return fail("a chain of at most 64 distinct nodes refused", N, m);
-  const std::vector<BundlePriorPass> ps = bundle_prior_passes(off.data(), nodes.data(), Q, N, kpad, max_queries, max_cols, budget);
-  int next = 0;
-  for (const BundlePriorPass& p : ps) {
-    if (p.q0 != next || p.nq < 1) return fail("passes do not tile the queries", p.q0, next);
-    next = p.q0 + p.nq;
-    if (p.nq > std::max(max_queries, 1)) return fail("pass over the chunk", p.nq, max_queries);
-    const std::set<int> cols(p.cols.begin(), p.cols.end());
-    if (cols.size() != p.cols.size()) return fail("a node is two columns of one pass", (long long)cols.size(), (long long)p.cols.size());
-    if (p.qc % kGatesSlab != 0 || p.qc < (int)p.cols.size() || p.qc >= (int)p.cols.size() + kGatesSlab) return fail("panel width", p.qc, (long long)p.cols.size());
-    std::set<int> want;
-    long long msum = 0, mmax = 0;
-    for (int q = p.q0; q < p.q0 + p.nq; ++q) {
-      std::set<int> mine;
-      for (int64_t t = off[(size_t)q]; t < off[(size_t)q + 1]; ++t) mine.insert(nodes[(size_t)t]);
-      if (mine.size() < 1 || mine.size() > 64) return fail("a query's distinct nodes", q, (long long)mine.size());
-      msum += (long long)mine.size();
-      mmax = std::max<long long>(mmax, (long long)mine.size());
-      want.insert(mine.begin(), mine.end());
-    }
-    if (want != cols) return fail("a pass's columns are not its queries' nodes: a query was split", (long long)want.size(), (long long)cols.size());
-    if (msum != p.msum) return fail("msum", msum, p.msum);
-    if (mmax != p.mmax) return fail("mmax", mmax, p.mmax);
+  const std::vector<ChainPriorPass> ps = bundle_prior_passes(off.data(), nodes.data(), Q, N, kpad, max_queries, max_cols, budget);
+  if (check_packing(ps, off, nodes, Q, max_queries, max_cols, [&](int qc, long long msum, long long, int nq) {
+        return bundle_prior_layout(N, qc, msum, nq, kpad).resident > budget;
+      }))
+    return 1;
+  for (const ChainPriorPass& p : ps) {
     const int gs = bundle_prior_group(p.mmax);
     if (gs < p.mmax || gs > 64 || (gs & (gs - 1)) != 0 || (gs > 1 && gs / 2 >= p.mmax)) return fail("group size", gs, p.mmax);
-    if (p.nq > 1) {
-      if (bundle_prior_layout(N, p.qc, p.msum, p.nq, kpad).resident > budget) return fail("pass over budget", N, p.qc);
-      if (max_cols > 0 && (int)p.cols.size() > max_cols) return fail("pass over the column limit", (long long)p.cols.size(), max_cols);
-    }
     if (check_layout(N, p.qc, p.msum, p.nq, kpad)) return 1;
   }
-  if (next != Q) return fail("passes end early", next, Q);
   return 0;
 }
 
@@ -151,8 +80,8 @@ int main() {
   {
     std::vector<int64_t> off;
     std::vector<int> nodes;
-    make_chains(2000000, 3, 2, 64, off, nodes);
-    const std::vector<BundlePriorPass> ps = bundle_prior_passes(off.data(), nodes.data(), 3, 2000000, 768, 256, 0, kChainPriorBudgetBytes);
+    make_chains(2000000, 3, false, 64, off, nodes);
+    const std::vector<ChainPriorPass> ps = bundle_prior_passes(off.data(), nodes.data(), 3, 2000000, 768, 256, 0, kChainPriorBudgetBytes);
     if (ps.size() != 3) return fail("three lone queries", (long long)ps.size(), 3);
     if (bundle_prior_layout(2000000, ps[0].qc, ps[0].msum, 1, 768).resident <= kChainPriorBudgetBytes) return fail("expected a pass over the budget", 0, 0);
   }

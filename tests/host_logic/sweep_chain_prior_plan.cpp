@@ -2,105 +2,38 @@
 // the passes tile [0, Q) in order; no query is split -- every distinct node of a query is a column of its pass; a node is a
 // column once per pass, so a chain many queries share is solved once; a pass of more than one query keeps its panel within
 // the budget, its queries within the chunk and its columns within the forced limit; the arrays of a layout are 256-byte
-// aligned, pairwise disjoint and inside the block; chains of 1 and 64 distinct nodes pass the check and 65 do not; the
+// aligned, pairwise disjoint and inside the block; the passes are the greedy ones and their columns stand in first-seen
+// order (sweep_prior_common.hpp); chains of 1 and 64 distinct nodes pass the check and 65 do not; the
 // per-chain systems index inside their arrays (walked here the way the kernels walk them, so the sanitizers see it); the
 // weighted path key keeps chains with different weights apart.  Run under -fsanitize=address,undefined.
-#include <cstdio>
 #include <cstdlib>
-#include <set>
-#include <vector>
+#include <map>
 
 #include "../../oscillink_amd/csrc/chain_many.hpp"
-#include "../../oscillink_amd/csrc/chain_prior_plan.hpp"
-
-using namespace osc::host;
-
-static int fail(const char* what, long long a, long long b) {
-  std::printf("ERROR %s (%lld, %lld)\n", what, a, b);
-  return 1;
-}
-
-struct Block {
-  long long at, bytes;
-};
+#include "sweep_prior_common.hpp"
 
 static int check_layout(long long N, int qc) {
   const ChainPriorLayout L = chain_prior_layout(N, qc);
   const long long slabs = qc / kGatesSlab, parts = gates_parts(N), panel = N * (long long)qc * 4;
-  const Block b[] = {{L.X, panel},       {L.R, panel},       {L.P, panel},        {L.AP, panel},
-                     {L.part_a, slabs * parts * 32 * 8},     {L.part_b, slabs * parts * 32 * 8},
-                     {L.rz, qc * 8LL},   {L.tol, qc * 4LL},  {L.alpha, qc * 4LL}, {L.beta, qc * 4LL},
-                     {L.res, qc * 4LL},  {L.live, qc * 4LL}, {L.iters, qc * 4LL}, {L.node, qc * 4LL},
-                     {L.slab_live, slabs * 4},               {L.n_live, 8}};
-  long long end = 0;
-  for (int i = 0; i < (int)(sizeof b / sizeof b[0]); ++i) {
-    if (b[i].at % 256 != 0) return fail("alignment", i, b[i].at);
-    if (b[i].at < end) return fail("blocks overlap", i, b[i].at);
-    if (b[i].bytes <= 0) return fail("empty block", i, b[i].bytes);
-    end = b[i].at + b[i].bytes;
-  }
-  if (end > L.total) return fail("block passes total", end, L.total);
-  return 0;
+  return check_blocks({{L.X, panel},       {L.R, panel},       {L.P, panel},        {L.AP, panel},
+                       {L.part_a, slabs * parts * 32 * 8},     {L.part_b, slabs * parts * 32 * 8},
+                       {L.rz, qc * 8LL},   {L.tol, qc * 4LL},  {L.alpha, qc * 4LL}, {L.beta, qc * 4LL},
+                       {L.res, qc * 4LL},  {L.live, qc * 4LL}, {L.iters, qc * 4LL}, {L.node, qc * 4LL},
+                       {L.slab_live, slabs * 4},               {L.n_live, 8}},
+                      L.total);
 }
 
-static unsigned long long rng_state = 88172645463325252ULL;
-static unsigned rnd(unsigned n) {
-  rng_state ^= rng_state << 13;
-  rng_state ^= rng_state >> 7;
-  rng_state ^= rng_state << 17;
-  return (unsigned)(rng_state % n);
-}
-
-// Q chains on N rows: kind 0 one chain shared by all, 1 a chain per query (2..9 nodes, repeats), 2 chains of 64 distinct nodes
-static void make_chains(long long N, int Q, int kind, std::vector<long long>& off, std::vector<int>& nodes) {
-  off.assign(1, 0);
-  nodes.clear();
-  std::vector<int> shared;
-  for (int q = 0; q < Q; ++q) {
-    std::vector<int> ch;
-    if (kind == 0 && !shared.empty()) {
-      ch = shared;
-    } else if (kind == 2) {
-      const long long m = std::min<long long>(N, 64);
-      const long long start = N > m ? rnd((unsigned)(N - m)) : 0;
-      for (long long t = 0; t < m; ++t) ch.push_back((int)(start + t));
-      ch.push_back(ch[0]);
-    } else {
-      const int len = 2 + (int)rnd(8);
-      for (int t = 0; t < len; ++t) ch.push_back((int)rnd((unsigned)std::min<long long>(N, 1 << 30)));
-      if (len > 3) ch[3] = ch[1];  // a revisit
-    }
-    if (kind == 0) shared = ch;
-    nodes.insert(nodes.end(), ch.begin(), ch.end());
-    off.push_back((long long)nodes.size());
-  }
-}
-
+// kind 0 one chain shared by all, 1 a chain per query (2..9 nodes, repeats), 2 chains of 64 distinct nodes
 static int check_passes(long long N, int Q, int kind, int max_queries, int max_cols, long long budget) {
-  std::vector<long long> off64;
+  std::vector<int64_t> off;
   std::vector<int> nodes;
-  make_chains(N, Q, kind, off64, nodes);
-  std::vector<int64_t> off(off64.begin(), off64.end());
+  make_chains(N, Q, kind == 0, kind == 2 ? 64 : 0, off, nodes);
   const std::vector<ChainPriorPass> ps = chain_prior_passes(off.data(), nodes.data(), Q, N, max_queries, max_cols, budget);
-  int next = 0;
-  for (const ChainPriorPass& p : ps) {
-    if (p.q0 != next || p.nq < 1) return fail("passes do not tile the queries", p.q0, next);
-    next = p.q0 + p.nq;
-    if (p.nq > std::max(max_queries, 1)) return fail("pass over the chunk", p.nq, max_queries);
-    const std::set<int> cols(p.cols.begin(), p.cols.end());
-    if (cols.size() != p.cols.size()) return fail("a node is two columns of one pass", (long long)cols.size(), (long long)p.cols.size());
-    if (p.qc % kGatesSlab != 0 || p.qc < (int)p.cols.size() || p.qc >= (int)p.cols.size() + kGatesSlab) return fail("panel width", p.qc, (long long)p.cols.size());
-    std::set<int> want;
-    for (int q = p.q0; q < p.q0 + p.nq; ++q)
-      for (int64_t t = off[(size_t)q]; t < off[(size_t)q + 1]; ++t) want.insert(nodes[(size_t)t]);
-    if (want != cols) return fail("a pass's columns are not its queries' nodes", (long long)want.size(), (long long)cols.size());
-    if (p.nq > 1) {
-      if (chain_prior_layout(N, p.qc).total > budget) return fail("panel over budget", N, p.qc);
-      if (max_cols > 0 && (int)p.cols.size() > max_cols) return fail("pass over the column limit", (long long)p.cols.size(), max_cols);
-    }
+  if (check_packing(ps, off, nodes, Q, max_queries, max_cols,
+                    [&](int qc, long long, long long, int) { return chain_prior_layout(N, qc).total > budget; }))
+    return 1;
+  for (const ChainPriorPass& p : ps)
     if (check_layout(N, p.qc)) return 1;
-  }
-  if (next != Q) return fail("passes end early", next, Q);
   if (kind == 0 && max_cols <= 0 && chain_prior_layout(N, 32).total <= budget && (int)ps.size() != (Q + std::max(max_queries, 1) - 1) / std::max(max_queries, 1))
     return fail("a shared chain splits passes beyond the chunk", (long long)ps.size(), Q);
   return 0;
