@@ -289,6 +289,14 @@ int osc_anchor_gram4_info(osc_handle h, int64_t* fused_four_step_solves, int64_t
  * the term in the gathered row sum, so that the matvec reads and writes that one row stream (solves predicted to end in iteration 4); enabled = 0 under OSC_GRAM4_FOLD=0,
  * which keeps the unfolded form (the reference: its results are bit-identical to the route before the fold existed) */
 int osc_gram4_fold_info(osc_handle h, int64_t* folded_four_step_solves, int32_t* enabled);
+/* such a solve without any matvec (the polynomial last form: x4 = sum_k a_k W^k Y + sum_k q_k W^k 1 per column, one elementwise pass
+ * over the lattice's held row sums, W^4 Y among them; OSC_ANCHOR_POLY = 0 off / 1 wherever the folded form would run, unset:
+ * lattices of at least 96000 rows): poly_four_step_solves = those of fused_four_step_solves that ran so, bytes = device memory W^4 Y
+ * holds (N x ld floats; 0: not kept, denied by the memory rule, or dropped), last_solve = whether the last general-path solve ran
+ * so, builds = times W^4 Y was kept, redos = solves predicted to end in iteration 4 whose residuals said otherwise: the pass was
+ * gated off and the solve ran again on the folded form's route */
+int osc_anchor_poly_info(osc_handle h, int64_t* poly_four_step_solves, int64_t* bytes, int32_t* last_solve, int64_t* builds,
+                         int64_t* redos);
 /* those sums as held (test aid): 16 arrays of ld doubles -- <W^j Y, W^5 Y> for j = 0..5, then <a, W^5 Y> for a = 1, s, s2, s3, s4
  * (s4 = W s3), then <s4, W^j Y> for j = 0..4 -- and the five <a, s4>, a = 1, s, s2, s3, s4; cap = doubles `out` holds;
  * OSC_E_UNSUPPORTED while none are held */

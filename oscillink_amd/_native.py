@@ -159,6 +159,7 @@ SIGNATURES = {
     "osc_anchor_gram3_read": (C.c_int, [Handle, C.POINTER(C.c_double), C.c_int64]),
     "osc_anchor_gram4_info": (C.c_int, [Handle, c_i64p, c_i64p, c_i32p, c_i64p]),
     "osc_gram4_fold_info": (C.c_int, [Handle, c_i64p, c_i32p]),
+    "osc_anchor_poly_info": (C.c_int, [Handle, c_i64p, c_i64p, c_i32p, c_i64p, c_i64p]),
     "osc_anchor_gram4_read": (C.c_int, [Handle, C.POINTER(C.c_double), C.c_int64]),
     "osc_balance_info": (C.c_int, [Handle, c_i32p, c_i64p, c_i64p, c_i32p, c_i32p, c_f64p, c_i32p]),
     "osc_get_blocked_copy": (C.c_int, [Handle, C.c_int32, c_i32p, c_f32p, c_i32p, c_i32p, c_i32p, c_f32p, C.c_int32]),

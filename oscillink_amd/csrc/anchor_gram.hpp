@@ -9,6 +9,8 @@
 // anchors and the graph alone (the lifetime of L::W3s); psi, the gate value, the lams and dt enter through the coefficients.
 // |r2|^2 is about 1e6 times smaller than the terms it is formed from: sums and forms are float64 throughout, and alpha /
 // beta / the residuals are rounded to float exactly where k_reduce_alpha / k_reduce_beta round them.
+// At the end of the file: poly4_coeffs, the coefficients of x4 itself in the two families W^k Y and psi W^k 1, for the solve that
+// ends in iteration 4 (k_settle_poly; swept by tests/host_logic/sweep_poly4.cpp).
 //
 // Storage of the sums (L::gram, read back by osc_anchor_gram_read): kGramPerColumn arrays of ld doubles, then kGramLattice
 // doubles.  Array q < 10: <W^j Y, W^k Y> for j <= k in the order (0,0) (0,1) (0,2) (0,3) (1,1) (1,2) (1,3) (2,2) (2,3) (3,3);
@@ -257,6 +259,8 @@ struct Scalars4 {
   float res4 = 0.f;  // |r4| of this column
   double rz4 = 0.0;  // r4 . z4
   bool usable4 = false;
+  double alpha_d[4] = {0.0, 0.0, 0.0, 0.0};  // alpha1 .. alpha4 and beta1 .. beta3 before they are rounded to float (poly4_coeffs)
+  double beta_d[3] = {0.0, 0.0, 0.0};
 };
 
 OSC_GRAM_HD double form4(const double (&G)[kBasis4][kBasis4], const double (&v)[kBasis4], const double (&w)[kBasis4]) {
@@ -288,37 +292,44 @@ OSC_GRAM_HD Scalars4 four_steps(const double (&G)[kBasis4][kBasis4], const Op& o
   apply4(o, p1, q1);
   const double rr0 = form4(G, r0, r0), rz0 = o.m * rr0;
   const double pq1 = form4(G, p1, q1);
-  s.alpha1 = (float)(rz0 / (pq1 + 1e-18));
+  f.alpha_d[0] = rz0 / (pq1 + 1e-18);
+  s.alpha1 = (float)f.alpha_d[0];
   for (int a = 0; a < kBasis4; ++a) r1[a] = r0[a] - (double)s.alpha1 * q1[a];
   const double rr1 = form4(G, r1, r1), rz1 = o.m * rr1;
   s.res1 = (float)sqrt(rr1);
-  s.beta1 = (float)(rz1 / (rz0 + 1e-18));
+  f.beta_d[0] = rz1 / (rz0 + 1e-18);
+  s.beta1 = (float)f.beta_d[0];
   for (int a = 0; a < kBasis4; ++a) p2[a] = o.m * r1[a] + (double)s.beta1 * p1[a];
   apply4(o, p2, ap2);
   const double pq2 = form4(G, p2, ap2);
-  s.alpha2 = (float)(rz1 / (pq2 + 1e-18));
+  f.alpha_d[1] = rz1 / (pq2 + 1e-18);
+  s.alpha2 = (float)f.alpha_d[1];
   for (int a = 0; a < kBasis4; ++a) r2[a] = r1[a] - (double)s.alpha2 * ap2[a];
   const double rr2 = form4(G, r2, r2);
   s.res2 = (float)sqrt(rr2);
   s.rz2 = o.m * rr2;
-  s.beta2 = (float)(s.rz2 / (rz1 + 1e-18));
+  f.beta_d[1] = s.rz2 / (rz1 + 1e-18);
+  s.beta2 = (float)f.beta_d[1];
   s.usable = finite(rr0) && finite(pq1) && finite(rr1) && finite(pq2) && finite(rr2) && finite((double)s.alpha1) &&
              finite((double)s.alpha2) && finite((double)s.beta1) && finite((double)s.beta2) && rr0 > 0.0 && pq1 >= 0.0 &&
              rr1 >= 0.0 && pq2 >= 0.0 && rr2 >= 0.0;
   for (int a = 0; a < kBasis4; ++a) p3[a] = o.m * r2[a] + (double)s.beta2 * p2[a];
   apply4(o, p3, ap3);
   const double pq3 = form4(G, p3, ap3);
-  t.alpha3 = (float)(s.rz2 / (pq3 + 1e-18));
+  f.alpha_d[2] = s.rz2 / (pq3 + 1e-18);
+  t.alpha3 = (float)f.alpha_d[2];
   for (int a = 0; a < kBasis4; ++a) r3[a] = r2[a] - (double)t.alpha3 * ap3[a];
   const double rr3 = form4(G, r3, r3);
   t.res3 = (float)sqrt(rr3);
   t.rz3 = o.m * rr3;
-  t.beta3 = (float)(t.rz3 / (s.rz2 + 1e-18));
+  f.beta_d[2] = t.rz3 / (s.rz2 + 1e-18);
+  t.beta3 = (float)f.beta_d[2];
   t.usable3 = s.usable && finite(pq3) && finite(rr3) && finite((double)t.alpha3) && finite((double)t.beta3) && pq3 >= 0.0 && rr3 >= 0.0;
   for (int a = 0; a < kBasis4; ++a) p4[a] = o.m * r3[a] + (double)t.beta3 * p3[a];
   apply4(o, p4, ap4);
   const double pq4 = form4(G, p4, ap4);
-  f.alpha4 = (float)(t.rz3 / (pq4 + 1e-18));
+  f.alpha_d[3] = t.rz3 / (pq4 + 1e-18);
+  f.alpha4 = (float)f.alpha_d[3];
   for (int a = 0; a < kBasis4; ++a) r4[a] = r3[a] - (double)f.alpha4 * ap4[a];
   const double rr4 = form4(G, r4, r4);
   f.res4 = (float)sqrt(rr4);
@@ -326,6 +337,49 @@ OSC_GRAM_HD Scalars4 four_steps(const double (&G)[kBasis4][kBasis4], const Op& o
   f.beta4 = (float)(f.rz4 / (t.rz3 + 1e-18));
   f.usable4 = t.usable3 && finite(pq4) && finite(rr4) && finite((double)f.alpha4) && finite((double)f.beta4) && pq4 >= 0.0 && rr4 >= 0.0;
   return f;
+}
+
+// ---- the polynomial last form ------------------------------------------------------------------------------------------------
+// Every vector of the solve lies, per column, in the span of W^k Y and psi s_k (s_0 = 1, s_k = W s_{k-1}), and A shifts either
+// family by one: A v_k = cs v_k - cW v_{k+1}.  So a solve that ends in iteration 4 has
+//     x4[i] = sum_{k <= 4} a[k] (W^k Y)[i] + sum_{k <= 3} q[k] s_k[i]
+// with nine coefficients a column, which follow from the CG recurrences run on coefficient vectors (x0 = Y, r0 = qb psi 1 + u Y
+// + cW W Y, z = m r) with the solve's alpha1 .. alpha4 and beta1 .. beta3.  Only x is formed from them, and at A = cs (I - (cW /
+// cs) W) with cW / cs well below 1 they are all of one sign and fall from power to power: nothing cancels (unlike the small
+// vectors A p3, r3, p4, which do -- see DESIGN.md section 10 (f)).  psi is multiplied into q.
+constexpr int kPolyY = 5;  // a[0..4]
+constexpr int kPolyS = 4;  // q[0..3]
+constexpr int kPolyCoeffs = kPolyY + kPolyS;
+struct Poly4 {
+  double a[kPolyY];
+  double q[kPolyS];
+};
+OSC_GRAM_HD Poly4 poly4_coeffs(const Op& o, const double (&alpha)[4], const double (&beta)[3], double psi) {
+  // (one slot more than x4 needs in either family: A p3's shift lands there and nothing reads it)
+  double xy[kPolyY + 1] = {1.0, 0.0, 0.0, 0.0, 0.0, 0.0}, xs[kPolyS + 1] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  double ry[kPolyY + 1] = {o.u, o.cW, 0.0, 0.0, 0.0, 0.0}, rs[kPolyS + 1] = {o.qb, 0.0, 0.0, 0.0, 0.0};
+  double py[kPolyY + 1], ps[kPolyS + 1];
+  for (int k = 0; k <= kPolyY; ++k) py[k] = o.m * ry[k];
+  for (int k = 0; k <= kPolyS; ++k) ps[k] = o.m * rs[k];
+  for (int it = 1; it <= 4; ++it) {
+    const double al = alpha[it - 1];
+    for (int k = 0; k <= kPolyY; ++k) xy[k] += al * py[k];
+    for (int k = 0; k <= kPolyS; ++k) xs[k] += al * ps[k];
+    if (it == 4) break;
+    const double be = beta[it - 1];
+    for (int k = kPolyY; k >= 0; --k) {  // r -= alpha A p; p = m r + beta p (descending: p[k - 1] is still the old one)
+      ry[k] -= al * (o.cs * py[k] - (k > 0 ? o.cW * py[k - 1] : 0.0));
+      py[k] = o.m * ry[k] + be * py[k];
+    }
+    for (int k = kPolyS; k >= 0; --k) {
+      rs[k] -= al * (o.cs * ps[k] - (k > 0 ? o.cW * ps[k - 1] : 0.0));
+      ps[k] = o.m * rs[k] + be * ps[k];
+    }
+  }
+  Poly4 c;
+  for (int k = 0; k < kPolyY; ++k) c.a[k] = xy[k];
+  for (int k = 0; k < kPolyS; ++k) c.q[k] = psi * xs[k];
+  return c;
 }
 
 }  // namespace gram

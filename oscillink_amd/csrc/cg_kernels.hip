@@ -1161,6 +1161,82 @@ __global__ __launch_bounds__(256) void k_init_two_steps_stream(const BlkArgs a, 
   }
 }
 
+// The polynomial last form (SettlePolyArgs; anchor_gram.hpp: poly4_coeffs) in the same geometry and addressing: five row streams in,
+// x4 out, nine coefficients a column loaded once before the row loop, three scalars a row.  One fixed order per element: the Y family
+// from a4 W^4 Y down to a0 Y by fmaf, the psi family from q3 s3 down to q0 the same way, then one add (tests/host_logic/
+// sweep_poly4.cpp evaluates it so).  Loads untested, stores guarded, as above.  No LDS, no barrier, no atomics.
+template <int LPR, int NCH, int RPT>
+__global__ __launch_bounds__(256) void k_settle_poly(const SettlePolyArgs a) {
+  constexpr int RPW = 64 / LPR;
+  if (*a.go != 1u || *a.go_fold != 1u) return;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int sub = lane / LPR, lr = lane % LPR;
+  const int32_t ld = a.ld;
+  const int32_t t0 = a.c0 + (int32_t)blockIdx.y * (NCH * LPR * 4);
+  bool cok[NCH];
+  float4 ca[gram::kPolyY][NCH], cq[gram::kPolyS][NCH];
+  uint32_t cb[NCH], sb[NCH];  // byte offsets of the lane's columns within a row: row-major, slab-major (blk_off less the row)
+#pragma unroll
+  for (int ch = 0; ch < NCH; ++ch) {
+    const int coff = t0 + (ch * LPR + lr) * 4;
+    cok[ch] = coff < a.c1;
+    const int cld = cok[ch] ? coff : a.c0;
+#pragma unroll
+    for (int k = 0; k < gram::kPolyY; ++k) ca[k][ch] = ld4(a.coef + (size_t)k * ld + cld);
+#pragma unroll
+    for (int k = 0; k < gram::kPolyS; ++k) cq[k][ch] = ld4(a.coef + (size_t)(gram::kPolyY + k) * ld + cld);
+    cb[ch] = (uint32_t)cld * 4u;
+    sb[ch] = ((uint32_t)(cld >> 5) * (uint32_t)a.N * 32u + (uint32_t)(cld & 31)) * 4u;
+  }
+  const int rend = a.N, rlast = a.N - 1;
+  for (int64_t rb = ((int64_t)blockIdx.x * 4 + wave) * (RPW * RPT); rb < rend; rb += (int64_t)gridDim.x * 4 * (RPW * RPT)) {
+    int row[RPT], rld[RPT];
+    float s1[RPT], s2[RPT], s3[RPT];
+    float4 y0[RPT][NCH], y1[RPT][NCH], y2[RPT][NCH], y3[RPT][NCH], y4[RPT][NCH];
+#pragma unroll
+    for (int j = 0; j < RPT; ++j) {
+      row[j] = (int)rb + j * RPW + sub;
+      rld[j] = min(row[j], rlast);
+      if constexpr (LPR == 64) rld[j] = __builtin_amdgcn_readfirstlane(rld[j]);  // (wave-uniform: the row's scalars by scalar loads)
+      s1[j] = a.wsum[rld[j]];
+      s2[j] = a.wsum2[rld[j]];
+      s3[j] = a.wsum3[rld[j]];
+      // row base (wave-uniform at LPR == 64) + the lane's 32-bit column offset (settle_poly_supported: N * ld * 4 fits)
+      const size_t rrow = (size_t)rld[j] * ld, rslab = (size_t)rld[j] * 32;
+#pragma unroll
+      for (int ch = 0; ch < NCH; ++ch) {
+        y0[j][ch] = ld4_stream_at(a.Ys + rslab, sb[ch]);
+        y1[j][ch] = ld4_stream_at(a.WYs + rslab, sb[ch]);
+        y2[j][ch] = ld4_stream_at(a.WW + rrow, cb[ch]);
+        y3[j][ch] = ld4_stream_at(a.W3 + rrow, cb[ch]);
+        y4[j][ch] = ld4_stream_at(a.W4 + rrow, cb[ch]);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < RPT; ++j) {
+      if (row[j] >= rend) continue;
+#pragma unroll
+      for (int ch = 0; ch < NCH; ++ch) {
+        if (!cok[ch]) continue;
+        float4 acc = make_float4(__fmul_rn(ca[4][ch].x, y4[j][ch].x), __fmul_rn(ca[4][ch].y, y4[j][ch].y), __fmul_rn(ca[4][ch].z, y4[j][ch].z),
+                                 __fmul_rn(ca[4][ch].w, y4[j][ch].w));
+        acc = mulacc4(ca[3][ch], y3[j][ch], acc);
+        acc = mulacc4(ca[2][ch], y2[j][ch], acc);
+        acc = mulacc4(ca[1][ch], y1[j][ch], acc);
+        acc = mulacc4(ca[0][ch], y0[j][ch], acc);
+        float4 ps = make_float4(__fmul_rn(cq[3][ch].x, s3[j]), __fmul_rn(cq[3][ch].y, s3[j]), __fmul_rn(cq[3][ch].z, s3[j]),
+                                __fmul_rn(cq[3][ch].w, s3[j]));
+        ps = fma4(s2[j], cq[2][ch], ps);
+        ps = fma4(s1[j], cq[1][ch], ps);
+        ps = make_float4(__fadd_rn(ps.x, cq[0][ch].x), __fadd_rn(ps.y, cq[0][ch].y), __fadd_rn(ps.z, cq[0][ch].z), __fadd_rn(ps.w, cq[0][ch].w));
+        const float4 x4 = make_float4(__fadd_rn(acc.x, ps.x), __fadd_rn(acc.y, ps.y), __fadd_rn(acc.z, ps.z), __fadd_rn(acc.w, ps.w));
+        // (a row and a column that are stored are the ones that were loaded: the same offsets)
+        st4_stream(reinterpret_cast<float*>(reinterpret_cast<char*>(a.X + (size_t)rld[j] * ld) + cb[ch]), x4);
+      }
+    }
+  }
+}
+
 // The Gram sums, first stage: workgroup (slab, chunk) sums its chunk's rows of the slab's 32 columns, a thread one column of
 // every eighth row, in float64 (the product of two floats is exact there); the eight row lanes are folded through LDS in
 // lane order.  Every real row of the window's columns is visited once.  The lattice's six sums ride in the slab-0 workgroups.
@@ -1445,6 +1521,13 @@ __global__ __launch_bounds__(256) void k_anchor_gram_scalars(const GramScalarArg
       a.alpha4[col] = f.alpha4;
       res3 = nanmax(res3, f.three.res3);
       res4 = nanmax(res4, f.usable4 ? f.res4 : __uint_as_float(0x7FC00000u));
+      if (a.poly != nullptr) {  // (for every column: go[2], under which alone they are read, is known only behind the fold below)
+        const gram::Poly4 pc = gram::poly4_coeffs(o, f.alpha_d, f.beta_d, (double)a.psi[col]);
+#pragma unroll
+        for (int k = 0; k < gram::kPolyY; ++k) a.poly[(size_t)k * a.ld + col] = (float)pc.a[k];
+#pragma unroll
+        for (int k = 0; k < gram::kPolyS; ++k) a.poly[(size_t)(gram::kPolyY + k) * a.ld + col] = (float)pc.q[k];
+      }
     } else if (three) {
       const double* lat3 = a.gram3 + (size_t)gram::kGram3PerColumn * a.ld;
       double G[gram::kBasis3][gram::kBasis3];
@@ -2308,6 +2391,26 @@ void launch_init_two_steps(const BlkArgs& a, int grid, hipStream_t s, const BlkI
 #undef CALL
   HIP_CHECK(hipGetLastError());
 }
+bool settle_poly_supported(const SettlePolyArgs& a) {
+  return a.N >= 1 && (a.c0 & 31) == 0 && a.c1 > a.c0 && a.c1 <= a.ld && (a.c1 & 3) == 0 && (a.ld & 31) == 0 &&
+         (int64_t)a.N * a.ld * 4 < ((int64_t)1 << 32);
+}
+void launch_settle_poly(const SettlePolyArgs& a, int grid, hipStream_t s) {
+  if (grid < 1 || !settle_poly_supported(a)) throw std::runtime_error("polynomial settle pass: unsupported arguments");
+  if (!a.Ys || !a.WYs || !a.WW || !a.W3 || !a.W4 || !a.wsum || !a.wsum2 || !a.wsum3 || !a.coef || !a.X || !a.go || !a.go_fold)
+    throw std::runtime_error("polynomial settle pass: bad arguments");
+  for (const float* in : {a.Ys, a.WYs, a.WW, a.W3, a.W4})
+    if (in == a.X) throw std::runtime_error("polynomial settle pass: aliased arrays");
+  const TwoStepsShape sh = pick_two_steps_shape(a.c1 - a.c0);
+  const int tile = sh.lpr * 4 * sh.nch, tiles = (a.c1 - a.c0 + tile - 1) / tile;
+  const int rows_per_wg = 4 * (64 / sh.lpr) * sh.rpt;
+  const int64_t need = ((int64_t)a.N + rows_per_wg - 1) / rows_per_wg;
+  const dim3 g((unsigned)std::max<int64_t>(1, std::min<int64_t>(need, grid / tiles)), (unsigned)tiles);  // (the solve's grid over the tiles)
+#define CALLS(L, C, R) hipLaunchKernelGGL((k_settle_poly<L, C, R>), g, dim3(256), 0, s, a)
+  OSC_TWO_STEPS_SHAPE_SWITCH(sh, CALLS);
+#undef CALLS
+  HIP_CHECK(hipGetLastError());
+}
 void launch_anchor_gram(const GramArgs& a, hipStream_t s) {
   if (!a.Ys || !a.WYs || !a.WW || !a.W3 || !a.wsum || !a.wsum2 || !a.part || !a.out || a.N < 1 || (a.c0 & 31) != 0 || a.c1 <= a.c0 ||
       a.c1 > a.ld)
@@ -2345,6 +2448,7 @@ void launch_anchor_gram_scalars(const GramScalarArgs& a, hipStream_t s) {
     throw std::runtime_error("anchor Gram scalars: bad arguments of the third step");
   if (a.gram4 != nullptr && (a.gram3 == nullptr || !a.alpha4 || a.alpha4 == a.alpha1 || a.alpha4 == a.alpha2 || a.alpha4 == a.alpha3))
     throw std::runtime_error("anchor Gram scalars: bad arguments of the fourth step");
+  if (a.poly != nullptr && a.gram4 == nullptr) throw std::runtime_error("anchor Gram scalars: the polynomial form needs the fourth step");
   hipLaunchKernelGGL(k_anchor_gram_scalars, dim3(1), dim3(256), 0, s, a);
   HIP_CHECK(hipGetLastError());
 }

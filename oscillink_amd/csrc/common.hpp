@@ -219,8 +219,35 @@ struct GramScalarArgs {
   // the very floats that are published, as a device word: the INIT pass and the matvec's folded last form act on it.
   const double* gram4;
   float* alpha4;
+  // The polynomial last form's coefficients (anchor_gram.hpp: poly4_coeffs; only with gram4; nullptr: not planned): nine rows of ld
+  // floats, a0 .. a4 then q0 .. q3, from alpha1 .. alpha4 and beta1 .. beta3 before they are rounded to float.  Written for every
+  // column of the window; k_settle_poly, their one reader, runs only where go[2] == 1.
+  float* poly;
 };
 void launch_anchor_gram_scalars(const GramScalarArgs& a, hipStream_t s);
+
+// k_settle_poly: an anchor start that ends in iteration 4 as one elementwise pass over the lattice's five row-sum arrays,
+//   x4 = a0 Y + a1 W Y + a2 W W Y + a3 W^3 Y + a4 W^4 Y + (q0 + q1 s + q2 s2 + q3 s3)
+// with GramScalarArgs::poly's coefficients per column.  Writes X alone; a no-op unless *go == 1 and *go_fold == 1 (go[0] and go[2]
+// of the scalars kernel).  The launch geometry and addressing are k_init_two_steps_stream's.
+struct SettlePolyArgs {
+  const float* Ys;     // the anchors, slab-major
+  const float* WYs;    // W Y, slab-major
+  const float* WW;     // W W Y, row-major with pitch ld
+  const float* W3;     // W^3 Y, row-major
+  const float* W4;     // W^4 Y, row-major
+  const float* wsum;   // [N] s = W 1
+  const float* wsum2;  // [N] s2 = W s
+  const float* wsum3;  // [N] s3 = W s2
+  const float* coef;   // [9][ld]
+  float* X;            // x4 out, row-major
+  const uint32_t* go;
+  const uint32_t* go_fold;
+  int32_t N, ld, c0, c1;
+};
+// false (nothing launched): the arguments are outside what the kernel's 32-bit offsets and float4 columns cover
+bool settle_poly_supported(const SettlePolyArgs& a);
+void launch_settle_poly(const SettlePolyArgs& a, int grid, hipStream_t s);
 
 // k_init_two_steps: the cached INIT pass of BlkInitAp2 run through iterations 1 and 2 with the scalars above.  Of BlkInit it
 // writes R (r2, row-major), Z (p3, slab-major) and Xcopy (x2 = x0 + alpha1 p1 + alpha2 p2, or with BlkTwoSteps::alpha3 x3 = x2 +

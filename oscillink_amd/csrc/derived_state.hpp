@@ -64,6 +64,7 @@ struct Derived {
   int gram_nb = 0;  // gram (the Gram sums of Ys, WYs, WWs, W3s, Wsum, Wsum2: anchor_gram.hpp): same validity again
   int gram3_nb = 0;  // gram3 / Wsum3 (the third step's sums, over W.W3s and W.Wsum2 as well): same validity again
   int gram4_nb = 0;  // gram4 (the fourth step's sums, over W.W.W3s and W.Wsum3 as well): same validity again
+  int w4_nb = 0;   // W4s (the fourth row sums W.W3s, kept from the pass that forms gram4: the polynomial last form): same validity again
   bool ustar = false;
   uint64_t epoch = 1;  // what an epoch_keyed cache was built for (its own 0 = never built)
 };
@@ -73,7 +74,7 @@ inline void drop(Derived& d, Cache c) {
     case Cache::ell_t: d.ell_t = false; break;
     case Cache::blocked_copy: d.blk_nb = 0; break;
     case Cache::anchor_slab: d.ys = false; break;
-    case Cache::anchor_wy: d.wy_nb = d.wwy_nb = d.w3_nb = d.gram_nb = d.gram3_nb = d.gram4_nb = 0; break;
+    case Cache::anchor_wy: d.wy_nb = d.wwy_nb = d.w3_nb = d.gram_nb = d.gram3_nb = d.gram4_nb = d.w4_nb = 0; break;
     case Cache::ustar: d.ustar = false; break;
     case Cache::epoch_keyed: ++d.epoch; break;
     case Cache::count: break;

@@ -22,6 +22,8 @@
 //                                       tests/host_logic/sweep_anchor_gram3.cpp)
 //   anchor_gram4_route                : ... and a solve that ends in iteration 4 has no fourth matvec, alpha4 and |r4| from two
 //                                       more vectors' sums (swept by tests/host_logic/sweep_anchor_gram4.cpp)
+//   anchor_poly_keeps / anchor_poly_route : ... and, where the lattice keeps W^4 Y, no matvec at all: x4 as a polynomial in W
+//                                       applied to Y and 1 (anchor_gram.hpp: poly4_coeffs; tests/host_logic/sweep_poly4.cpp)
 //   cg_host_loop                      : the host loop of a CG solve -- which iteration is enqueued when (run_cg in
 //                                       osc_solve.hip and both sweeps run this one function)
 #pragma once
@@ -669,6 +671,18 @@ inline AnchorGram4Words anchor_gram4_device_words(bool four, bool usable, float 
   const bool go1 = usable && res1 > tol && res2 > tol && res3 > tol;
   return AnchorGram4Words{res1, res2, res3, res4, four && go1 && res4 <= tol};
 }
+// The polynomial last form (anchor_gram.hpp: poly4_coeffs; cg_kernels.hip: k_settle_poly): a solve the folded form would serve -- four
+// steps planned, predicted to end in iteration 4 -- whose lattice holds W^4 Y (L::W4s) runs no matvec at all: the scalars kernel and
+// one elementwise pass, gated by the device's go[2].  Where the published residuals then disagree (anchor_gram4_last_form false)
+// nothing was written and run_cg solves again without it.  anchor_poly_keeps: whether the lattice keeps W^4 Y when it forms gram4.
+inline bool anchor_poly_keeps(int mode, int64_t N) { return mode != 0 && (mode > 0 || N >= kAnchorApAutoRows); }
+struct AnchorPolyInputs {
+  int mode = -1;       // OSC_ANCHOR_POLY: 0 off, 1 wherever the folded form would run, < 0 by the lattice's rows
+  int64_t N = 0;
+  bool fold = false;   // the four-step route is planned, the fold is allowed and the prediction is 4
+  bool w4_held = false;
+};
+inline bool anchor_poly_route(const AnchorPolyInputs& in) { return in.fold && in.w4_held && anchor_poly_keeps(in.mode, in.N); }
 // Where iteration `it` of a solve gets its A p (CgSolve::enqueue): from the INIT pass (first: it left A p1 and the p . Ap
 // partials), from the iteration's own p update (second: the INIT pass left T), or from a matvec.
 enum class ApSource { matvec, init_pass, p_update };

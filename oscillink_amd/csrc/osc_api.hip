@@ -40,6 +40,8 @@ void read_env_solver(L& h) {
   if (num("OSC_ANCHOR_GRAM3", v)) h.anchor_gram3 = v != 0 ? 1 : 0;
   if (num("OSC_ANCHOR_GRAM4", v)) h.anchor_gram4 = v != 0 ? 1 : 0;
   if (num("OSC_GRAM4_FOLD", v)) h.gram4_fold = v != 0;
+  if (num("OSC_ANCHOR_POLY", v)) h.anchor_poly = v != 0 ? 1 : 0;
+  if (num("OSC_ANCHOR_POLY_MAX_MB", v)) h.anchor_poly_max_mb = std::max(0, v);
   if (const char* e = getenv("OSC_TWO_STEPS")) h.two_steps_stream = strcmp(e, "blocked") != 0;
   if (num("OSC_RECEIPT_PAIR", v)) h.receipt_pair = v != 0;
   if (const char* e = getenv("OSC_SHARD")) h.shard_mode = !strcmp(e, "row") ? 1 : 0;
@@ -682,6 +684,16 @@ int osc_gram4_fold_info(osc_handle h, int64_t* folded_four_step_solves, int32_t*
   return guarded(h, [&](L& l) {
     if (folded_four_step_solves) *folded_four_step_solves = l.folded_four_step_solves;
     if (enabled) *enabled = l.gram4_fold ? 1 : 0;
+  });
+}
+
+int osc_anchor_poly_info(osc_handle h, int64_t* poly_four_step_solves, int64_t* bytes, int32_t* last_solve, int64_t* builds, int64_t* redos) {
+  return guarded(h, [&](L& l) {
+    if (poly_four_step_solves) *poly_four_step_solves = l.poly_four_step_solves;
+    if (bytes) *bytes = l.derived.w4_nb > 0 ? (int64_t)l.W4s.n * 4 : 0;
+    if (last_solve) *last_solve = l.anchor_poly_last ? 1 : 0;
+    if (builds) *builds = l.anchor_poly_builds;
+    if (redos) *redos = l.anchor_poly_redos;
   });
 }
 

@@ -152,6 +152,17 @@ struct osc_lattice {
   // two_steps).  After a folded solve the R array holds nothing defined.
   bool gram4_fold = true;
   int64_t folded_four_step_solves = 0;
+  // The polynomial last form (host_logic.hpp: anchor_poly_route): W^4 Y, which the pass that forms gram4 computes anyway, is kept
+  // (row-major N x ld like W3s; the memory rule of ensure_anchor_ap, a denial remembered until WYs is formed anew; Derived::w4_nb),
+  // and a solve predicted and shown to end in iteration 4 is the scalars kernel and one elementwise pass over Ys, WYs, WWs, W3s and
+  // W4s with nine coefficients a column (poly_coef).  After such a solve R, P and AP hold nothing defined.  OSC_ANCHOR_POLY: 0
+  // never, 1 wherever the folded form would run, unset: by the lattice's rows.
+  DevBuf<float> W4s, poly_coef;
+  int anchor_poly = -1;
+  int anchor_poly_max_mb = -1;  // OSC_ANCHOR_POLY_MAX_MB: W4s is kept only if it is no larger than this many MiB (unset: the free memory alone decides)
+  bool anchor_poly_denied = false;
+  int64_t poly_four_step_solves = 0, anchor_poly_builds = 0, anchor_poly_redos = 0;
+  bool anchor_poly_last = false;
   int64_t yu_copies = 0;    // whole-array Y -> U copies made for this handle (osc_counters::y_to_u_copies)
   int64_t slab_launches = 0;  // k_rows_to_slab launches (osc_counters::rows_to_slab_launches)
   // Which of the arrays computed from other state (ell_col_t / ell_w_t, blk_*, Ys, WYs, Ustar; by epoch: halo, query) are

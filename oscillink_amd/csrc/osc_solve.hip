@@ -364,6 +364,7 @@ struct CgSolve {
   // iterations' reductions would have left, residual slots 1 and 2 are published.  enqueue(1) and enqueue(2) launch nothing,
   // enqueue(3) launches no p update, and the ring starts with two directions applied.
   const bool allow_gram;  // (false: the solve run again after a fused pass that was gated off)
+  const bool allow_poly;  // (false: the solve run again after a polynomial pass that was gated off)
   bool gram_route = false;
   // ... and iteration 3's scalars are known as well (anchor_gram3_route): alpha_of(3) holds alpha3, h.beta beta3, h.rz r3 . z3,
   // residual slot 3 is published.  enqueue(3) launches the matvec's fused form alone -- r3 over r2, p4 into dir(4), under its own
@@ -377,6 +378,9 @@ struct CgSolve {
   // (iteration 4's beta reduction publishes it anew) and everything is the three-step route's.
   bool gram4_planned = false, gram4_taken = false;
   bool gram4_fold = false;  // ... and the INIT pass was given go[2]: a solve that ends so takes the folded last form (OSC_GRAM4_FOLD)
+  // The polynomial last form (host_logic.hpp: anchor_poly_route): in the INIT pass's place the scalars kernel and k_settle_poly are
+  // enqueued, both acting on go[2], and nothing else: run_cg reads the four words (poly_done) instead of running the host loop.
+  bool poly_pending = false;
   float fused_md_B = 0.f, fused_md_const = 1.f;  // (BlkInit's, for the fused launch)
   bool ring_planned = false;
 
@@ -407,13 +411,13 @@ struct CgSolve {
   BlkArgs ba{};
   ChainFixArgs cf{};
 
-  CgSolve(L& h_, const OpParams& op_, const CgBuffers& b_, bool with_path_, int max_iters_, float tol_, bool allow_gram_)
+  CgSolve(L& h_, const OpParams& op_, const CgBuffers& b_, bool with_path_, int max_iters_, float tol_, bool allow_gram_, bool allow_poly_)
       : h(h_), op(op_), b(b_), with_path(with_path_), max_iters(max_iters_), tol(tol_), grid(cg_grid(h_)),
         plan(apply_plan(h_, b_.c0, b_.c1, b_.ld, with_path_)), nslots((size_t)max_iters_ + 2), mapped(h_.comm == nullptr),
         overlap(h_.comm != nullptr && (h_.comm_overlap == 1 || (h_.comm_overlap < 0 && h_.world >= 4)) && h_.x_defer),
         polled(mapped || overlap), x1_in(b_.defer_x0 && b_.X != b_.x0 && !overlap ? b_.x0 : nullptr),
         x_init(x1_in != nullptr ? const_cast<float*>(b_.x0) : b_.X), stop_guess(h_.predicted_iters[b_.kind]), Pbuf(b_.P),
-        APbuf(b_.AP), allow_gram(allow_gram_) {
+        APbuf(b_.AP), allow_gram(allow_gram_), allow_poly(allow_poly_) {
     ensure_ctrl(h, nslots);
     res_slots = ctrl_segment(h, 2 * nslots);
     done_ctr = res_slots + nslots;
@@ -475,6 +479,7 @@ struct CgSolve {
     h.anchor_gram_last = false;
     h.anchor_gram3_last = false;
     h.anchor_gram4_last = false;
+    h.anchor_poly_last = false;
     // (the rhs rows the fused pass can take besides x0 itself: one -- the state term must be x0 or absent, and if y is a
     // third array the solution array must be x0)
     const bool fuse_u = b.rhsU == b.x0 || op.rbU == 0.f;
@@ -579,8 +584,8 @@ struct CgSolve {
       }
       h.cached_inits += 1;
     } else if (wy_route) {
-      h.derived.wy_nb = h.derived.wwy_nb = h.derived.w3_nb = h.derived.gram_nb = h.derived.gram3_nb = h.derived.gram4_nb = 0;  // (not current while this launch rewrites them)
-      h.anchor_ap_denied = h.anchor_ap2_denied = false;
+      h.derived.wy_nb = h.derived.wwy_nb = h.derived.w3_nb = h.derived.gram_nb = h.derived.gram3_nb = h.derived.gram4_nb = h.derived.w4_nb = 0;  // (not current while this launch rewrites them)
+      h.anchor_ap_denied = h.anchor_ap2_denied = h.anchor_poly_denied = false;
       h.WYs.alloc((size_t)h.N * h.ld);
       bi.WY = h.WYs.p;
       launch_apply_blocked(ba, grid, h.stream, &bi, plan.shape, true);
@@ -677,6 +682,8 @@ struct CgSolve {
       if (ga.alpha1 == ga.alpha4) ga.alpha1 = h.part1.p + 2 * (size_t)b.ld;
       if (ga.alpha2 == ga.alpha4) ga.alpha2 = h.part1.p + 3 * (size_t)b.ld;
     }
+    const bool fold = four && h.gram4_fold && stop_guess == 4;
+    if (fold && allow_poly && poly_pass(ga)) return true;
     launch_anchor_gram_scalars(ga, h.stream);
     BlkInit ti = bi;
     ti.Z = dir(3);
@@ -687,7 +694,6 @@ struct CgSolve {
     // matvec's folded last form instead of x3 and r2.  Only behind a prediction of 4: the pass's foldable form holds a wave per SIMD
     // less, which a solve that runs on past iteration 4 pays for nothing -- 0.18 ms of a 14.4 ms settle at 1 M rows.  A solve that
     // ends in iteration 4 unannounced takes the unfolded form once and leaves the prediction.)
-    const bool fold = four && h.gram4_fold && stop_guess == 4;
     if (fold) ts.beta3 = ga.beta3, ts.alpha4 = ga.alpha4, ts.go_fold = ga.go + 2;
     launch_init_two_steps(ba, grid, h.stream, ti, plan.shape, ap, ap2, ts, h.two_steps_stream);
     gram_route = true;
@@ -702,6 +708,69 @@ struct CgSolve {
     if (three) h.fused_three_step_solves += 1;
     h.anchor_gram3_last = three;
     h.cached_inits += 1;
+    return true;
+  }
+
+  // The polynomial last form in the INIT pass's place: the scalars kernel, which also leaves the nine coefficients a column, and the one
+  // elementwise pass that writes x4, gated by go[0] and go[2].  False: the route does not hold, nothing was enqueued.
+  bool poly_pass(GramScalarArgs& ga) {
+    host::AnchorPolyInputs pi;
+    pi.mode = h.anchor_poly;
+    pi.N = h.N;
+    pi.fold = true;
+    pi.w4_held = h.derived.w4_nb == ba.nb && h.derived.gram4_nb == ba.nb && h.Wsum3.n == (size_t)h.N;
+    if (!host::anchor_poly_route(pi) || !polled) return false;
+    SettlePolyArgs pa{};
+    pa.Ys = h.Ys.p;
+    pa.WYs = h.WYs.p;
+    pa.WW = h.WWs.p;
+    pa.W3 = h.W3s.p;
+    pa.W4 = h.W4s.p;
+    pa.wsum = h.Wsum.p;
+    pa.wsum2 = h.Wsum2.p;
+    pa.wsum3 = h.Wsum3.p;
+    pa.X = b.X;
+    pa.N = (int32_t)h.N;
+    pa.ld = b.ld;
+    pa.c0 = b.c0;
+    pa.c1 = b.c1;
+    if (!settle_poly_supported(pa)) return false;
+    const size_t nc = (size_t)gram::kPolyCoeffs * b.ld;
+    try {
+      if (h.poly_coef.n < nc) h.poly_coef.alloc(nc);
+    } catch (const HipError&) {
+      (void)hipGetLastError();
+      h.poly_coef.release();
+      return false;
+    }
+    ga.poly = h.poly_coef.p;
+    pa.coef = h.poly_coef.p;
+    pa.go = ga.go;
+    pa.go_fold = ga.go + 2;
+    launch_anchor_gram_scalars(ga, h.stream);
+    launch_settle_poly(pa, grid, h.stream);
+    poly_pending = true;
+    gram_route = true;  // (every scalar comes from the sums: init() launches no reduction)
+    return true;
+  }
+  // ... and its end: word 1 is the last the scalars kernel publishes.  True: the four words say what go[2] said, x4 is written (or
+  // about to be: finish waits) and the solve is over -- iterations, residuals and every counter but blk_applies as the folded form
+  // leaves them.  False: the pass was gated off and wrote nothing (U still aliases Y); run_cg solves again without this form.
+  bool poly_done() {
+    (void)poll_host_word(h, reinterpret_cast<volatile uint32_t*>(h.res_host) + 1, nullptr, "the polynomial settle's residuals");
+    const volatile float* words = reinterpret_cast<const volatile float*>(h.res_host);
+    const float r1 = words[1], r2 = words[2], r3 = words[3], r4 = words[4];
+    if (!host::anchor_gram4_last_form(r1, r2, r3, r4, (double)tol)) return false;
+    for (const float r : {r1, r2, r3, r4}) h.history.push_back(r);
+    gram_route = gram3_route = gram4_planned = gram4_fold = gram4_taken = true;
+    ring.applied = 4;  // (x is complete: no pass is left)
+    h.fused_two_step_solves += 1;
+    h.fused_three_step_solves += 1;
+    h.fused_four_step_solves += 1;
+    h.folded_four_step_solves += 1;
+    h.poly_four_step_solves += 1;
+    h.cached_inits += 1;
+    h.anchor_gram_last = h.anchor_gram3_last = h.anchor_gram4_last = h.anchor_poly_last = true;
     return true;
   }
 
@@ -797,7 +866,7 @@ struct CgSolve {
   // streaming pass.  Only the sums are kept.
   bool ensure_anchor_gram4() {
     if (h.derived.gram4_nb == ba.nb && h.derived.gram3_nb == ba.nb && h.derived.gram_nb == ba.nb) return true;
-    h.derived.gram4_nb = 0;
+    h.derived.gram4_nb = h.derived.w4_nb = 0;
     if (b.ld != h.ld || h.part1.n < 4 * (size_t)b.ld || b.R == nullptr || b.R == b.AP) return false;
     const size_t n = (size_t)gram::kGram4PerColumn * h.ld + gram::kGram4Lattice;
     DevBuf<double> part;
@@ -811,6 +880,33 @@ struct CgSolve {
       h.gram4.release();
       return false;
     }
+    // W^4 Y goes to an array of its own where the polynomial last form may read it later (the memory rule of ensure_anchor_ap, a
+    // denial remembered), and to the AP scratch array, to be dropped, otherwise
+    float* w4 = b.AP;
+    if (host::anchor_poly_keeps(h.anchor_poly, h.N) && !h.anchor_poly_denied) {
+      const size_t n4 = (size_t)h.N * h.ld;
+      if (h.W4s.n != n4) {
+        size_t free_b = 0, total_b = 0;
+        HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+        int64_t avail = (int64_t)free_b + (int64_t)h.W4s.n * 4;
+        // (OSC_ANCHOR_POLY_MAX_MB: the array may not be larger than that either; anchor_ap_fits takes a quarter of what it is given)
+        if (h.anchor_poly_max_mb >= 0) avail = std::min<int64_t>(avail, (int64_t)h.anchor_poly_max_mb * 4 * 1048576);
+        bool ok = host::anchor_ap_fits((int64_t)n4 * 4, avail);
+        if (ok) {
+          try {
+            h.W4s.alloc(n4);
+          } catch (const HipError&) {
+            (void)hipGetLastError();
+            ok = false;
+          }
+        }
+        if (!ok) {
+          h.W4s.release();
+          h.anchor_poly_denied = true;
+        }
+      }
+      if (h.W4s.n == n4) w4 = h.W4s.p;
+    }
     launch_row_weighted_sums(h.ell_col.p, h.ell_w.p, h.deg.p, h.width, (int32_t)h.N, h.Wsum3.p, wsum4.p, h.stream);
     BlkArgs wa = ba;
     wa.X = h.Tap.p;
@@ -819,9 +915,9 @@ struct CgSolve {
     wa.gate = nullptr;
     wa.gate_tol = 0.f;
     rows_to_slab(h, h.W3s.p, h.Tap.p, h.ld, b.c0, b.c1, grid);
-    wa.OUT = b.AP;
+    wa.OUT = w4;
     launch_apply_blocked(wa, grid, h.stream, nullptr, plan.shape);
-    rows_to_slab(h, b.AP, h.Tap.p, h.ld, b.c0, b.c1, grid);
+    rows_to_slab(h, w4, h.Tap.p, h.ld, b.c0, b.c1, grid);
     wa.OUT = b.R;
     launch_apply_blocked(wa, grid, h.stream, nullptr, plan.shape);
     Gram4Args g{};
@@ -837,7 +933,7 @@ struct CgSolve {
     g.g.ld = h.ld;
     g.g.c0 = h.c0;
     g.g.c1 = h.c1;
-    g.W4 = b.AP;
+    g.W4 = w4;
     g.W5 = b.R;
     g.wsum3 = h.Wsum3.p;
     g.wsum4 = wsum4.p;
@@ -845,6 +941,10 @@ struct CgSolve {
     sync(h);  // part and s4 go out of scope
     h.derived.gram4_nb = ba.nb;
     h.anchor_gram4_builds += 1;
+    if (w4 == h.W4s.p) {
+      h.derived.w4_nb = ba.nb;
+      h.anchor_poly_builds += 1;
+    }
     return true;
   }
 
@@ -1225,12 +1325,21 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
     CgResult one{};
     if (run_cg_small(h, op, b, with_path, max_iters, tol, one)) return one;
   }
-  for (const bool allow_gram : {true, false}) {
-    CgSolve s(h, op, b, with_path, max_iters, tol, allow_gram);
+  bool allow_gram = true, allow_poly = true;
+  for (int attempt = 0; attempt < 3; ++attempt) {
+    CgSolve s(h, op, b, with_path, max_iters, tol, allow_gram, allow_poly);
     s.init();
     s.plan_ring();
     h.history.clear();
     s.prof_mark = h.prof_pending.size();
+    if (s.poly_pending) {
+      if (s.poly_done()) return s.finish(4);
+      // The solve does not end in iteration 4 after all (or a column's sums were unusable): the pass was gated off and nothing but
+      // scratch scalars was written.  The same solve again on the folded form's route, which takes it from there as it always did.
+      h.anchor_poly_redos += 1;
+      allow_poly = false;
+      continue;
+    }
     const int iters = host::cg_host_loop(max_iters, s.stop_guess, (double)tol, s);
     if (s.gram_route && iters < 3) {
       // The solve stopped before iteration 3 (or a column's sums were unusable): the fused pass was gated off, nothing but
@@ -1241,6 +1350,7 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
       if (s.gram4_taken) h.fused_four_step_solves -= 1;
       if (s.gram4_taken && s.gram4_fold) h.folded_four_step_solves -= 1;
       h.cached_inits -= 1;  // (the solve counts once, where it ends)
+      allow_gram = false;
       continue;
     }
     return s.finish(iters);

@@ -282,6 +282,8 @@ class OscillinkLattice:
         self._call("osc_anchor_gram4_info", C.byref(g4f), C.byref(g4b), C.byref(g4l), C.byref(g4n))
         g4d = C.c_int64(0)
         self._call("osc_gram4_fold_info", C.byref(g4d), None)
+        pf4, pb4, pl4, pn4, pr4 = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int64(0), C.c_int64(0)
+        self._call("osc_anchor_poly_info", C.byref(pf4), C.byref(pb4), C.byref(pl4), C.byref(pn4), C.byref(pr4))
         counters = nat.Counters()
         self._call("osc_counters_get", C.byref(counters))
         return {"order_kind": ("none", "bfs", "balanced")[int(ok.value)], "displaced_edges_before": int(db.value),
@@ -306,6 +308,9 @@ class OscillinkLattice:
                 "fused_four_step_solves": int(g4f.value), "anchor_gram4_bytes": int(g4b.value),
                 "anchor_gram4_last_solve": int(g4l.value), "anchor_gram4_builds": int(g4n.value),
                 "folded_four_step_solves": int(g4d.value),
+                "poly_four_step_solves": int(pf4.value), "anchor_poly_bytes": int(pb4.value),
+                "anchor_poly_last_solve": int(pl4.value), "anchor_poly_builds": int(pn4.value),
+                "anchor_poly_redos": int(pr4.value),
                 # chain_receipt_many(lamP=...) keeps the basis of M + lamP I beside the query basis: N x ld + N x 4 floats
                 # (ld >= D rounded up to 4); 0 until the first such call
                 "shifted_basis_bytes": (4 * self.N * (((self.D + 3) // 4) * 4 + 4) if self._qbs_key is not None else 0)
