@@ -635,6 +635,23 @@ int osc_corpus_get_live(osc_corpus_handle h, uint32_t* words);
  * OSC_E_INVALID with the first such query and its count in the message, before any device work.  A filter together with
  * cand_in is OSC_E_INVALID.  A filter of all ones returns what no filter returns, bit for bit. */
 int osc_corpus_filter(osc_corpus_handle h, const uint32_t* words, int32_t rows, int64_t words_per_row);
+/* Arms the NEXT osc_corpus_search / _refine* / _gates / _graph call on this handle as ragged; that
+ * call spends the arming whether it succeeds or fails, like the filter.  The reference's filtered loop
+ * (scripts/proof_hallucination.py:203-221) builds the lattice over whichever rows pass its filter, with
+ * kneighbors = min(k, rows - 1): a ragged call gives query q a lattice of n_q rows, 1 <= n_q <= K = min(top_k, live rows), at
+ * the front of its K-row slot, and every output keeps its (Q, K) / (Q, min(k, K)) shape.  rows_or_null = NULL: with a filter
+ * n_q = min(K, eligible rows of query q) and the candidates are all eligible rows in the search order (zero eligible rows is
+ * still OSC_E_INVALID naming the query); with cand_in, row q holds n_q ids in front and -1 behind them; with neither every
+ * n_q is K.  rows_or_null = Q counts (copied here): checked against cand_in's padding, or against the eligible rows.  Per query the
+ * list length is min(kneighbors, n_q - 1) (a one-row lattice has no edge and sqrt_deg 1e-6), bundle picks are min(k, n_q),
+ * gates_in and chain ids are read and checked below n_q only.  Behind n_q (or min(k, n_q)) the outputs hold -1 in ids
+ * (cand_out, local, search ids) and 0 in values (cos, gates, score, align).  Everything a lattice returns is, byte for byte,
+ * what a call over that lattice alone returns.  When every n_q is K the call runs the kernels of a call that was not armed.
+ * Q < 0 clears the arming. */
+int osc_corpus_ragged(osc_corpus_handle h, const int32_t* rows_or_null, int32_t Q);
+/* the n_q of the last call on this handle that was armed by osc_corpus_ragged (proof_hallucination.py:203-221: the size is
+ * whatever the filter leaves); Q must be that call's Q */
+int osc_corpus_ragged_rows(osc_corpus_handle h, int32_t* rows, int32_t Q);
 
 /* ---- receipts ------------------------------------------------------------------------------- */
 /* deltaH_trace (receipts.py:10-25) on the resident U and U* */

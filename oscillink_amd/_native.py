@@ -138,6 +138,8 @@ SIGNATURES = {
     "osc_corpus_rows": (C.c_int, [Handle, c_i64p, c_i64p, c_i64p]),
     "osc_corpus_get_live": (C.c_int, [Handle, c_u32p]),
     "osc_corpus_filter": (C.c_int, [Handle, c_u32p, C.c_int32, C.c_int64]),
+    "osc_corpus_ragged": (C.c_int, [Handle, c_i32p, C.c_int32]),
+    "osc_corpus_ragged_rows": (C.c_int, [Handle, c_i32p, C.c_int32]),
     "osc_deltaH": (C.c_int, [Handle, c_f64p]),
     "osc_receipt_components": (C.c_int, [Handle, c_f32p, c_f32p, c_f32p]),
     "osc_null_points": (C.c_int, [Handle, C.c_float, c_i32p, c_i32p, c_f32p, c_f32p, c_i32p]),

@@ -33,8 +33,9 @@ MAX_CHAIN = rc.MAX_CHAIN
 class _RefineOut:
     """The result arrays of one refine_many call, zeroed, and the two forms every path hands them back in."""
 
-    def __init__(self, Q: int, K: int, kk: int, gated: bool):
+    def __init__(self, Q: int, K: int, kk: int, gated: bool, rows: Optional[np.ndarray] = None):
         self.gated = gated
+        self.rows = rows  # a ragged call's rows per lattice (int32 (Q,)), else None
         self.cand = np.zeros((Q, K), dtype=np.int32)
         self.local = np.zeros((Q, kk), dtype=np.int32)
         self.score = np.zeros((Q, kk), dtype=np.float32)
@@ -55,14 +56,22 @@ class _RefineOut:
         """(ids, the `as_arrays` dict without receipts) once the native call has filled the arrays."""
         Q, kk = self.local.shape
         ids = np.take_along_axis(self.cand, self.local, axis=1) if kk else np.zeros((Q, 0), dtype=np.int32)
+        if self.rows is not None and kk:  # behind min(k, n_q) picks `local` is -1, and so is the id
+            ids = np.where(self.local >= 0, np.take_along_axis(self.cand, np.maximum(self.local, 0), axis=1),
+                           np.int32(-1)).astype(np.int32)
         out = {"ids": ids, "local": self.local, "score": self.score, "align": self.align, "candidates": self.cand,
                "ustar_iters": self.iters, "ustar_res": self.res}
+        if self.rows is not None:
+            out["rows"] = self.rows
         if self.gated:
             out.update(gates=self.g, gate_iters=self.g_iters, gate_res=self.g_res)
         return ids, out
 
     def bundles(self, ids):
         """Per query the list of {"id", "score", "align"} that bundle() returns."""
+        if self.rows is not None:  # min(k, n_q) entries per query
+            n = np.minimum(self.rows, ids.shape[1])
+            return [rc.bundle_dicts(ids[q, :n[q]], self.score[q, :n[q]], self.align[q, :n[q]]) for q in range(ids.shape[0])]
         return [rc.bundle_dicts(ids[q], self.score[q], self.align[q]) for q in range(ids.shape[0])]
 
 
@@ -124,11 +133,20 @@ class Corpus:
     def __exit__(self, *exc) -> None:
         self.close()
 
-    def _call_filtered(self, allow: Optional[np.ndarray], name: str, *args) -> None:
-        """_call(name, ...) with `allow` (_allow's words or None) armed as the call's filter: the native call consumes it."""
+    def _call_filtered(self, allow: Optional[np.ndarray], name: str, *args, ragged: Optional[np.ndarray] = None) -> None:
+        """_call(name, ...) with `allow` (_allow's words or None) armed as the call's filter: the native call consumes it.
+        ragged = the rows per lattice (int32 (Q,)) of a ragged call, which is armed as such; afterwards the counts the native
+        call used are read back and must be these."""
         if allow is not None:
             self._call("osc_corpus_filter", nat.u32(allow), allow.shape[0], allow.shape[1])
+        if ragged is not None:  # with a filter the native side derives the counts itself
+            self._call("osc_corpus_ragged", None if allow is not None else nat.i32(ragged), int(ragged.shape[0]))
         self._call(name, *args)
+        if ragged is not None:
+            used = np.zeros_like(ragged)
+            self._call("osc_corpus_ragged_rows", nat.i32(used), int(used.shape[0]))
+            if not np.array_equal(used, ragged):
+                raise nat.NativeError(f"{name}: the native call used other row counts than the ones checked here")
 
     def _call(self, name: str, *args) -> None:
         if self._h is None:
@@ -183,11 +201,58 @@ class Corpus:
             raise ValueError("candidates: repeated id within a row")
         return cand.astype(np.int32)
 
+    def _candidates_ragged(self, candidates, Q: int, K: int):
+        """`candidates` of a ragged call -- Q integer sequences of 1 .. K ids each, or the (Q, K) integer array with -1
+        behind each row's ids -- as (the (Q, K) int32 array padded with -1, the rows per query int32 (Q,)); _candidates'
+        checks on the real entries."""
+        if isinstance(candidates, np.ndarray) and candidates.ndim == 2:
+            if candidates.shape != (Q, K):
+                raise ValueError(f"candidates must be a ({Q}, {K}) array or {Q} sequences, got shape {candidates.shape}")
+            if candidates.size and not np.issubdtype(candidates.dtype, np.integer):
+                raise ValueError("candidates must hold integer corpus ids")
+            lists = []
+            for q in range(Q):
+                row = candidates[q]
+                n = int(np.argmax(row < 0)) if (row < 0).any() else K
+                if np.any(row[n:] != -1):
+                    raise ValueError(f"candidates: query {q} has an id behind a -1 (the padding is -1, behind the ids)")
+                lists.append(row[:n])
+        else:
+            try:
+                lists = [np.asarray(row) for row in candidates]
+            except TypeError:
+                lists = None
+            if lists is None or len(lists) != Q:
+                raise ValueError(f"candidates must be a ({Q}, {K}) array or {Q} sequences of ids")
+        cand = np.full((Q, K), -1, dtype=np.int64)
+        rows = np.zeros(Q, dtype=np.int32)
+        for q, row in enumerate(lists):
+            if row.ndim != 1 or (row.size and not np.issubdtype(row.dtype, np.integer)):
+                raise ValueError("candidates must hold integer corpus ids")
+            if row.size < 1 or row.size > K:
+                raise ValueError(f"candidates: query {q} has {row.size} ids, need 1 .. K = {K}")
+            if row.min() < 0 and np.any(row[int(np.argmax(row < 0)):] >= 0):
+                raise ValueError(f"candidates: query {q} has an id behind a -1 (the padding is -1, behind the ids)")
+            if row.min() < 0 or row.max() >= self.N:
+                raise ValueError(f"candidates: corpus ids must lie in [0, {self.N})")
+            if self.n_live < self.N and not self._alive_mask()[row].all():
+                raise ValueError(f"candidates: query {q} names removed id {int(row[~self._alive_mask()[row]][0])}")
+            if np.unique(row).size != row.size:
+                raise ValueError("candidates: repeated id within a row")
+            cand[q, :row.size] = row
+            rows[q] = row.size
+        return cand.astype(np.int32), rows
+
     def _allow(self, allow, candidates, Q: int, K: int) -> Optional[np.ndarray]:
         """The `allow` argument of search / refine_many / diffusion_gates_many as the native filter's words, (1, W) for
         one filter or (Q, W) for one per query, or None; checked before any device work."""
+        return self._allow_rows(allow, candidates, Q, K, False)[0]
+
+    def _allow_rows(self, allow, candidates, Q: int, K: int, ragged: bool):
+        """(_allow's words, the rows per lattice of a ragged call or None).  ragged: a query keeps its min(K, eligible)
+        rows, and only a query without any eligible row is an error."""
         if allow is None:
-            return None
+            return None, (np.full(Q, K, dtype=np.int32) if ragged else None)
         if candidates is not None:
             raise ValueError("allow cannot be combined with candidates")
         a = np.asarray(allow)
@@ -196,11 +261,12 @@ class Corpus:
         if a.shape != (self.N,) and a.shape != (Q, self.N):
             raise ValueError(f"allow must have shape ({self.N},) or ({Q}, {self.N}), got {a.shape}")
         counts = np.atleast_2d(a & self._alive_mask()).sum(axis=1)
-        short = np.flatnonzero(counts < K)
+        short = np.flatnonzero(counts < (1 if ragged else K))
         if short.size and Q:
             q = int(short[0])
             raise ValueError(f"allow: query {q} has {int(counts[q])} eligible rows (live and allowed), fewer than K = {K}")
-        return mk.pack_mask(a)
+        rows = np.broadcast_to(np.minimum(counts, K), (Q,)).astype(np.int32) if ragged else None
+        return mk.pack_mask(a), rows
 
     @staticmethod
     def _gate_settings(beta, gamma, method, max_iters, prefix: str = ""):
@@ -231,7 +297,7 @@ class Corpus:
                 float(settle_tol))
 
     @staticmethod
-    def _chains(chains, chain_weights, lamP, chain_z_th, Q: int, K: int):
+    def _chains(chains, chain_weights, lamP, chain_z_th, Q: int, K: int, rows: Optional[np.ndarray] = None):
         """refine_many's chain arguments, checked as add_chain checks them (with the query index in front), as the entry
         point's chain block: None without chains, else a dict of `offsets` int64 (Q + 1, over nodes), `nodes` int32,
         `weights` float32 per chain edge or None, `edge_offsets` int64 (Q + 1), `lists` (per query the chain or None),
@@ -272,7 +338,7 @@ class Corpus:
                 ch = [int(operator.index(c)) for c in ch]
             except TypeError:
                 raise ValueError(f"query {q}: chain must be None or a sequence of integers") from None
-            if any((c < 0 or c >= K) for c in ch):
+            if any((c < 0 or c >= (K if rows is None else int(rows[q]))) for c in ch):
                 raise ValueError(f"query {q}: chain indices out of bounds")
             if len(ch) < 2:
                 raise ValueError(f"query {q}: chain must contain at least two indices")
@@ -304,22 +370,26 @@ class Corpus:
                           "computed, like the reference's cg path", RuntimeWarning, stacklevel=3)
 
     # ------------------------------------------------------------------ public API
-    def search(self, psis, top_k: int, *, allow=None):
+    def search(self, psis, top_k: int, *, allow=None, ragged: bool = False):
         """Per query the K = min(top_k, n_live) corpus ids of the largest cosine Yn_i . psi / (|psi| + 1e-12) (fp32 on the
         device), ties to the smaller id, in that order.  Returns (ids int32 (Q, K), cos float32 (Q, K)).
 
         Removed rows are never returned.  `allow` narrows the search on the device: a bool array (N,) for every query or
         (Q, N) with one row per query; a row is eligible iff it is live and allowed, and the order within the eligible rows
-        is the same.  Every query needs at least K eligible rows (ValueError naming the first query that has fewer)."""
+        is the same.  Every query needs at least K eligible rows (ValueError naming the first query that has fewer).
+
+        `ragged=True` lifts that: a query with n < K eligible rows gets all n of them, in the same
+        order, with -1 in `ids` and 0 in `cos` behind them; only a query without any eligible row is an error.  Returns
+        (ids, cos, rows) with rows int32 (Q,) = min(K, eligible rows)."""
         P = self._queries(psis)
         K = self._top_k(top_k)
         Q = P.shape[0]
-        words = self._allow(allow, None, Q, K)
+        words, rows = self._allow_rows(allow, None, Q, K, bool(ragged))
         ids = np.zeros((Q, K), dtype=np.int32)
         cos = np.zeros((Q, K), dtype=np.float32)
         if Q:
-            self._call_filtered(words, "osc_corpus_search", nat.f32(P), Q, int(top_k), nat.i32(ids), nat.f32(cos))
-        return ids, cos
+            self._call_filtered(words, "osc_corpus_search", nat.f32(P), Q, int(top_k), nat.i32(ids), nat.f32(cos), ragged=rows)
+        return (ids, cos, rows) if ragged else (ids, cos)
 
     # ------------------------------------------------------------------ rows
     @property
@@ -441,7 +511,7 @@ class Corpus:
                     gate_method: str = "direct", gate_tol: float = 1e-4, gate_max_iters: int = 256,
                     receipts: Optional[str] = None, settle_dt: float = 1.0, settle_max_iters: int = 12,
                     settle_tol: float = 1e-3, chains=None, lamP: float = 0.2, chain_weights=None,
-                    chain_z_th: float = 2.5, allow=None):
+                    chain_z_th: float = 2.5, allow=None, ragged: bool = False):
         """For each query q, what the reference's loop returns with `cand = search(psis, top_k)[0][q]` (or
         `candidates[q]`):
 
@@ -500,7 +570,19 @@ class Corpus:
         with one row per query -- narrows the device search to the rows that are live and allowed, as in `search`; it
         cannot be combined with `candidates`, and every query needs at least K eligible rows.  Either way the answer is
         the one a fresh `Corpus` over the eligible rows gives, ids mapped; `allow=None` on a corpus without removed rows is
-        the call as it was."""
+        the call as it was.
+
+        `ragged=True` runs candidate lattices of different sizes in the one batch, as the
+        reference's filtered loop does (scripts/proof_hallucination.py:203-221: the lattice is built over whichever rows pass,
+        with kneighbors = min(k, rows - 1)).  Query q gets a lattice of n_q rows, 1 <= n_q <= K: with `allow`, n_q =
+        min(K, eligible rows) and the candidates are all eligible rows in the search order (only a query without any eligible
+        row is an error); with `candidates`, Q integer sequences of 1 .. K ids each, or the (Q, K) array with -1 behind each
+        row's ids; with neither, every n_q is K.  Per query: min(k, n_q) picks, min(kneighbors, n_q - 1) neighbours (a one-row
+        lattice has no edge), a (Q, K) `gates` array is read and checked below n_q only, and chain ids must be < n_q.  The
+        array form keeps its shapes and gains `rows` int32 (Q,) = n_q; behind n_q (or min(k, n_q)) `ids`, `local` and
+        `candidates` hold -1 and `score`, `align` and `gates` 0.  The list and dict forms have min(k, n_q) bundle entries, and
+        a receipt's meta and `state_sig` are those of the n_q-row lattice.  Everything returned for a query is byte for byte
+        what a call over its lattice alone returns.  `ragged=False` is the call as it was."""
         P = self._queries(psis)
         K = self._top_k(top_k)
         knn = self._knn(kneighbors, K)
@@ -511,8 +593,14 @@ class Corpus:
             if float(val) < 0:
                 raise ValueError(f"{name} must be >= 0")
         Q = P.shape[0]
-        cand_in = None if candidates is None else self._candidates(candidates, Q, K)
-        words = self._allow(allow, candidates, Q, K)
+        rg = bool(ragged)
+        cand_rows = None
+        if candidates is not None and rg:
+            cand_in, cand_rows = self._candidates_ragged(candidates, Q, K)
+        else:
+            cand_in = None if candidates is None else self._candidates(candidates, Q, K)
+        words, rows = self._allow_rows(allow, candidates, Q, K, rg)
+        rows = rows if cand_rows is None else cand_rows
         kk = min(max(int(k), 0), K)
         gates_in, gate_set = None, None
         if isinstance(gates, str):
@@ -524,13 +612,15 @@ class Corpus:
             if gates_in.shape != (Q, K):
                 raise ValueError(f"gates must be a ({Q}, {K}) array, got shape {gates_in.shape}")
             gates_in = np.ascontiguousarray(gates_in, dtype=np.float32)
+            if rg:  # only a lattice's own entries are read and checked
+                gates_in = np.where(np.arange(K)[None, :] < rows[:, None], gates_in, np.float32(0.0))
             if not np.all(np.isfinite(gates_in)):
                 raise ValueError("gates must be finite")
             if np.any(gates_in < 0):
                 raise ValueError("gates must be >= 0")
-        chain = self._chains(chains, chain_weights, lamP, chain_z_th, Q, K)
+        chain = self._chains(chains, chain_weights, lamP, chain_z_th, Q, K, rows)
         gated = gates is not None
-        o = _RefineOut(Q, K, kk, gated)
+        o = _RefineOut(Q, K, kk, gated, rows)
         cand_arg = None if cand_in is None else nat.i32(cand_in)
         gates_arg = None if gates_in is None else nat.f32(gates_in)
         beta, gamma, method, g_max = gate_set if gate_set is not None else (1.0, 0.1, 0, 1)
@@ -542,25 +632,27 @@ class Corpus:
                                          mode=0 if not gated else (2 if gates_in is not None else 1), gates_arg=gates_arg,
                                          gate_args=gate_args, solve_args=solve_args, detail=detail,
                                          settle_args=(s_dt, s_max, s_tol), lam=[lamG, lamC, lamQ, 0.0],
-                                         deterministic_k=deterministic_k, as_arrays=as_arrays, chain=chain, allow=words)
+                                         deterministic_k=deterministic_k, as_arrays=as_arrays, chain=chain, allow=words,
+                                         kneighbors=int(kneighbors))
         if Q and not gated:
             self._call_filtered(words, "osc_corpus_refine", nat.f32(P), Q, int(top_k), cand_arg, *solve_args,
-                                *o.pointers(False))
+                                *o.pointers(False), ragged=rows)
         elif Q:
             self._call_filtered(words, "osc_corpus_refine_gated", nat.f32(P), Q, int(top_k), cand_arg, gates_arg, *gate_args,
-                                *solve_args, *o.pointers(True))
+                                *solve_args, *o.pointers(True), ragged=rows)
             if gates_in is None:
                 self._warn_non_finite(o.g, o.g_iters, o.g_res, "refine_many")
         ids, arrays = o.ids_and_arrays()
         return arrays if as_arrays else o.bundles(ids)
 
     def _refine_receipts(self, P, o, *, top_k, knn, cand_arg, mode, gates_arg, gate_args, solve_args, detail,
-                         settle_args, lam, deterministic_k, as_arrays, chain=None, allow=None):
+                         settle_args, lam, deterministic_k, as_arrays, chain=None, allow=None, kneighbors=None):
         """refine_many with receipts or chains, behind its validation: one osc_corpus_refine_receipts call (or, with
         chains, one osc_corpus_refine_chains call), then the arrays or the loop's dicts.  o = the result arrays; mode = the
         entry point's gate_mode; gate_args, solve_args and settle_args (dt, max_iters, tol) = its argument runs of those
         names; detail = None (chains only: no settle, no receipt), 0 or 1; lam = the state signature's lambdas, as given;
-        chain = _chains' block or None; allow = _allow's words or None."""
+        chain = _chains' block or None; allow = _allow's words or None; kneighbors = as given (a ragged call's signatures
+        take min(kneighbors, max(1, n_q - 1)) per lattice)."""
         from .lattice import OscillinkLattice, __version__
 
         Q, K = o.cand.shape
@@ -589,10 +681,12 @@ class Corpus:
                        nat.i64(chain["offsets"]), nat.i32(chain["nodes"]),
                        None if chain["weights"] is None else nat.f32(chain["weights"]), chain["lamP"], chain["z_th"],
                        *o.pointers(True), *receipt_out, *[nat.f32(c_edge[t]) for t in range(4)],
-                       c_gain.ctypes.data_as(nat.c_f64p), nat.i32(c_verdict), nat.i32(c_weak_k), nat.f32(c_weak_z))
+                       c_gain.ctypes.data_as(nat.c_f64p), nat.i32(c_verdict), nat.i32(c_weak_k), nat.f32(c_weak_z),
+                       ragged=o.rows)
         elif Q:
             self._call_filtered(allow, "osc_corpus_refine_receipts", nat.f32(P), Q, int(top_k), cand_arg, mode, gates_arg,
-                       *gate_args, *solve_args, *settle_args, detail, RECEIPT_Z_TH, cap_val, *o.pointers(True), *receipt_out)
+                       *gate_args, *solve_args, *settle_args, detail, RECEIPT_Z_TH, cap_val, *o.pointers(True), *receipt_out,
+                       ragged=o.rows)
         if Q:
             if mode == 1:
                 self._warn_non_finite(g, g_iters, g_res, "refine_many")
@@ -616,19 +710,21 @@ class Corpus:
         bundles = o.bundles(ids)
         out = []
         for q in range(Q):
-            B = g[q] if gated else ones
+            n = K if o.rows is None else int(o.rows[q])  # the lattice's own rows: its gates, degree and signature
+            B = (g[q] if gated else ones)[:n]
             adj_sig = hashlib.sha256(np.ascontiguousarray(pairs[q, :int(pairs_n[q])]).tobytes()).hexdigest()
             ch = None if chain is None else chain["lists"][q]
             sig = OscillinkLattice._signature_digest(
                 {"psi": np.round(P[q], 6).tolist(), "lam": lam if ch is None else [*lam[:3], chain["lamP"]],
                  "chain_present": ch is not None, "chain_len": 0 if ch is None else len(ch),
-                 "k": knn, "detk": bool(deterministic_k), "adj": adj_sig}, B)
+                 "k": knn if o.rows is None else min(kneighbors, max(1, n - 1)), "detk": bool(deterministic_k),
+                 "adj": adj_sig}, B)
             nulls, tot = ra.nulls(q)
             meta = rc.meta(ustar_cached=False, ustar_solves=1, ustar_cache_hits=0,
                            ustar={"ustar_iters": int(iters[q]), "ustar_res": float(res[q]),
                                   "ustar_converged": bool(float(res[q]) <= USTAR_TOL)},
                            ustar_solve_ms=0.0, ustar_source="corpus_batch", graph_build_ms=0.0, last_settle_ms=0.0,
-                           degree=rc.degree_stats(int(nnz[q]), K), gates=rc.gate_stats(B), state_sig=sig,
+                           degree=rc.degree_stats(int(nnz[q]), n), gates=rc.gate_stats(B), state_sig=sig,
                            receipt_detail=detail_name, null_points_summary=rc.null_summary(tot, cap_val))
             rec = rc.record(version=__version__, deltaH=ra.sums[0, q], coh_drop_sum=ra.sums[1, q],
                             anchor_pen_sum=ra.sums[2, q], query_term_sum=ra.sums[3, q], cg_iters=s_iters[q],
@@ -645,7 +741,7 @@ class Corpus:
 
     def diffusion_gates_many(self, psis, top_k: int, *, kneighbors: int = 6, row_cap_val: float = 1.0, beta: float = 1.0,
                              gamma: float = 0.1, method: str = "direct", tol: float = 1e-4, max_iters: int = 256,
-                             clamp: bool = True, candidates=None, allow=None) -> dict[str, Any]:
+                             clamp: bool = True, candidates=None, allow=None, ragged: bool = False) -> dict[str, Any]:
         """For each query q, with `cand` its candidates (searched, or `candidates[q]`),
 
             compute_diffusion_gates(Y[cand], psis[q], kneighbors=..., row_cap_val=..., beta=..., gamma=..., method=...,
@@ -656,7 +752,8 @@ class Corpus:
         diffusion.py:123) still clips h to [0, 1]: `np.clip(out["gates"], 0, 1)` gives its answer.  method="direct" is
         served, as in compute_diffusion_gates, by the CG run to 1e-7 max(1, |s|) with at most 2048 iterations.  Non-finite
         gates come back as computed, with a RuntimeWarning naming the first such query.  `allow` narrows the search as in
-        `search`.
+        `search`.  `ragged=True` means what it means for `refine_many`: query q's lattice has n_q <= K rows, `gates` holds 0 and
+        `candidates` -1 behind them, and the dict gains `rows` int32 (Q,).
 
         Returns a dict of `gates` (Q, K) float32 in candidate order, `candidates` (Q, K), `iters` and `res` (Q,)."""
         P = self._queries(psis)
@@ -664,8 +761,14 @@ class Corpus:
         self._knn(kneighbors, K)
         b, g, m, mi = self._gate_settings(beta, gamma, method, max_iters)
         Q = P.shape[0]
-        cand_in = None if candidates is None else self._candidates(candidates, Q, K)
-        words = self._allow(allow, candidates, Q, K)
+        rg = bool(ragged)
+        cand_rows = None
+        if candidates is not None and rg:
+            cand_in, cand_rows = self._candidates_ragged(candidates, Q, K)
+        else:
+            cand_in = None if candidates is None else self._candidates(candidates, Q, K)
+        words, rows = self._allow_rows(allow, candidates, Q, K, rg)
+        rows = rows if cand_rows is None else cand_rows
         cand = np.zeros((Q, K), dtype=np.int32)
         gates = np.zeros((Q, K), dtype=np.float32)
         iters = np.zeros(Q, dtype=np.int32)
@@ -674,9 +777,12 @@ class Corpus:
             self._call_filtered(words, "osc_corpus_gates", nat.f32(P), Q, int(top_k),
                                 None if cand_in is None else nat.i32(cand_in), int(kneighbors), float(row_cap_val), b, g, m,
                                 float(tol), mi, int(bool(clamp)), nat.i32(cand), nat.f32(gates), nat.i32(iters),
-                                nat.f32(res))
+                                nat.f32(res), ragged=rows)
             self._warn_non_finite(gates, iters, res, "diffusion_gates_many")
-        return {"gates": gates, "candidates": cand, "iters": iters, "res": res}
+        out = {"gates": gates, "candidates": cand, "iters": iters, "res": res}
+        if rg:
+            out["rows"] = rows
+        return out
 
     def info(self, top_k: int, kneighbors: int = 6, k: int = 8) -> dict[str, Any]:
         """Queries per chunk and one chunk's device scratch for a refine with these settings."""

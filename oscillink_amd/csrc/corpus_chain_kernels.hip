@@ -37,10 +37,11 @@ __global__ __launch_bounds__(256) void k_cq_solve_chain(const CqChainPcgArgs ca)
   const CqLattice& g = a.lat;
   const int tid = threadIdx.x, lat = blockIdx.x;
   const int64_t r0 = (int64_t)lat * g.K;
+  const int n = g.rows(lat);
   const bool present = ca.chain.rec(lat)[0] > 0, active = present && ca.chain.lamP > 0.f;
   const float cP = active ? ca.chain.lamP : 0.f;
-  cq_path_slots(ca.chain, lat, g.K, active, s_slot);
-  for (int r = tid; r < g.K; r += 256) {
+  cq_path_slots(ca.chain, lat, n, active, s_slot);
+  for (int r = tid; r < n; r += 256) {
     const float Bi = g.B ? g.B[r0 + r] : 1.0f;
     const float cs = fmaf(g.lamQ, Bi, g.lamG + g.lamC);
     s_cs[r] = active ? cs + cP : cs;
@@ -64,8 +65,8 @@ __global__ __launch_bounds__(256) void k_cq_chain_receipt(const CqChainEdgesArgs
   __shared__ int32_t s_slot[kCqMaxRows];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const CqLattice& g = a.lat;
-  const int lat = blockIdx.x, K = g.K;
-  const int64_t r0 = (int64_t)lat * K;
+  const int lat = blockIdx.x, K = g.rows(lat);  // (the lattice's own row count; its slot is g.K rows)
+  const int64_t r0 = (int64_t)lat * g.K;
   const int32_t* rec = a.chain.rec(lat);
   const int E = min(rec[0], min(a.chain.cap, kCqMaxChainEdges));
   if (E <= 0) {  // (uniform) no chain

@@ -16,7 +16,9 @@ namespace osc {
 constexpr int kCqMaxRows = host::kCorpusMaxTopK;  // rows of a candidate lattice
 constexpr int kCqMaxCols = 1536;                  // columns (Corpus: D <= 1536)
 
-// the lattices of one chunk, back to back: lattice q is union rows [q K, q K + K) and query row q
+// the lattices of one chunk, back to back: lattice q is union rows [q K, q K + K) and query row q.  In a ragged chunk
+//  lattice q has nrows[q] <= K rows at the front of its K-row slot: row bases, strides and LDS
+// sizes stay functions of K, every row loop and every row count runs to rows(q)
 struct CqLattice {
   const float* Y;       // union rows x ldn
   const float* psi;     // nq x ldn
@@ -29,6 +31,8 @@ struct CqLattice {
   const float* B;       // union rows: the gates, or nullptr (B = 1)
   int32_t K, k, ldn;
   float lamG, lamC, lamQ;
+  const int32_t* nrows; // nq: rows of each lattice, or nullptr (every lattice has K)
+  __device__ __forceinline__ int32_t rows(int lat) const { return nrows ? nrows[lat] : K; }
 };
 
 // k_cq_solve and k_cq_settle
@@ -67,10 +71,10 @@ struct CqPathRows {
   float cP;            // lamP for the solve, dt lamP for the settle
 };
 
-// fills s_slot for one lattice (the caller's barrier publishes it); active = the lattice has a chain and lamP > 0
-__device__ __forceinline__ void cq_path_slots(const CqChain& c, int lat, int K, bool active, int32_t* s_slot) {
+// fills s_slot for one lattice of n rows (the caller's barrier publishes it); active = the lattice has a chain and lamP > 0
+__device__ __forceinline__ void cq_path_slots(const CqChain& c, int lat, int n, bool active, int32_t* s_slot) {
   const int32_t* rec = c.rec(lat);
-  for (int r = threadIdx.x; r < K; r += 256) s_slot[r] = -1;
+  for (int r = threadIdx.x; r < n; r += 256) s_slot[r] = -1;
   __syncthreads();
   if (active)
     for (int t = threadIdx.x; t < rec[1]; t += 256) s_slot[rec[c.rows_at + t]] = t;
@@ -138,7 +142,7 @@ __device__ __forceinline__ void cq_pcg(const CqPcgArgs& a, const Op& op, float* 
   const CqLattice& g = a.lat;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lat = blockIdx.x;
-  const int64_t r0 = (int64_t)lat * g.K, r1 = r0 + g.K;
+  const int64_t r0 = (int64_t)lat * g.K, r1 = r0 + g.rows(lat);
   const float* psi = g.psi + (size_t)lat * g.ldn;
   int cidx[NC];
   bool on[NC];

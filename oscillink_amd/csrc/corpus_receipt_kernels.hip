@@ -44,8 +44,9 @@ __global__ __launch_bounds__(256) void k_cq_settle(const CqPcgArgs a) {
   const CqLattice& g = a.lat;
   const int tid = threadIdx.x, lat = blockIdx.x;
   const int64_t r0 = (int64_t)lat * g.K;
+  const int n = g.rows(lat);
   const float cW = a.dt * g.lamC, rbY = cq_rounded_mul(a.dt, g.lamG), cQ = a.dt * g.lamQ;
-  for (int r = tid; r < g.K; r += 256) {
+  for (int r = tid; r < n; r += 256) {
     const float Bi = g.B ? g.B[r0 + r] : 1.0f;
     s_cs[r] = fmaf(cQ, Bi, 1.0f + a.dt * (g.lamG + g.lamC));
     s_inv[r] = 1.f / (fmaf(cQ, Bi, 1.0f + rbY) + 1e-12f);
@@ -73,12 +74,13 @@ __global__ __launch_bounds__(256) void k_cq_settle_chain(const CqChainPcgArgs ca
   const CqLattice& g = a.lat;
   const int tid = threadIdx.x, lat = blockIdx.x;
   const int64_t r0 = (int64_t)lat * g.K;
+  const int n = g.rows(lat);
   const bool present = ca.chain.rec(lat)[0] > 0, active = present && ca.chain.lamP > 0.f;
   const float cW = a.dt * g.lamC, rbY = cq_rounded_mul(a.dt, g.lamG), cQ = a.dt * g.lamQ;
   const float cP = active ? cq_rounded_mul(a.dt, ca.chain.lamP) : 0.f;
   const float dP = present ? cq_rounded_mul(a.dt, ca.chain.lamP) : 0.f;
-  cq_path_slots(ca.chain, lat, g.K, active, s_slot);
-  for (int r = tid; r < g.K; r += 256) {
+  cq_path_slots(ca.chain, lat, n, active, s_slot);
+  for (int r = tid; r < n; r += 256) {
     const float Bi = g.B ? g.B[r0 + r] : 1.0f;
     const float cs = fmaf(cQ, Bi, 1.0f + a.dt * (g.lamG + g.lamC));
     s_cs[r] = active ? cs + cP : cs;
@@ -112,8 +114,8 @@ __global__ __launch_bounds__(256) void k_cq_receipt(const std::conditional_t<CHA
   __shared__ int s_cnt[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const CqLattice& g = a.lat;
-  const int lat = blockIdx.x, K = g.K;
-  const int64_t r0 = (int64_t)lat * K;
+  const int lat = blockIdx.x, K = g.rows(lat);  // (the lattice's own row count; its slot is g.K rows)
+  const int64_t r0 = (int64_t)lat * g.K;
   const float* psi = g.psi + (size_t)lat * g.ldn;
   for (int c = tid; c < g.ldn; c += 256) s_psi[c] = psi[c];
   [[maybe_unused]] CqPathRows path{};

@@ -36,6 +36,10 @@ __device__ __forceinline__ int block_scan(bool flag, int* wsum, int* total) {
 // eligible rows per query.
 void launch_cq_select_masked(const float* dots, int64_t N, int32_t K, const uint32_t* live, const uint32_t* allow,
                              int64_t allow_stride, int32_t* cand, float* ccos, int32_t nq, hipStream_t s);
+// the ragged form: a query with n < K eligible rows keeps all n, sorted as always; nrows[q] =
+// min(K, eligible rows), cand is -1 and ccos 0 behind it.  The caller guarantees one eligible row per query.
+void launch_cq_select_ragged(const float* dots, int64_t N, int32_t K, const uint32_t* live, const uint32_t* allow,
+                             int64_t allow_stride, int32_t* cand, float* ccos, int32_t* nrows, int32_t nq, hipStream_t s);
 // dst row g <- src row kept[g], for Y and Yn at once (rows of ldn floats, ldn a multiple of 4)
 void launch_cq_compact(const float* Y, const float* Yn, int32_t ldn, const int32_t* kept, int64_t rows, float* Yd, float* Ynd,
                        hipStream_t s);

@@ -13,15 +13,22 @@ namespace {
 // score load that waits for the word's would double it.  A row that is not eligible takes no part at all: it is in no histogram, it is not collected, and it is not counted by the scan that
 // numbers the rows of the K-th key's tie class (counted there, a masked row in front of a live one with the same key would
 // push the live one out).
+// RAGGED (the reference's filtered loop keeps whichever rows pass, proof_hallucination.py:203-221):
+// a query may have fewer than K eligible rows.  The first histogram pass counts them; with fewer than K the radix walk has no
+// K-th key to find (its `cum + h >= k` never fires), so the walk is skipped, every eligible key is collected (T = 0: finite
+// keys are > 0) and sorted as always, n = the count goes to nrows[q], and cand / ccos behind n are -1 / 0.  Only tid < n
+// indexes d[].  The uniform instance is the kernel as it was.
+template <bool RAGGED>
 __global__ __launch_bounds__(kSelT) void k_cq_select_masked(const float* dots, int64_t N, int32_t K, const uint32_t* live,
                                                             const uint32_t* allow, int64_t allow_stride, int32_t* cand,
-                                                            float* ccos) {
+                                                            float* ccos, int32_t* nrows) {
   __shared__ uint32_t hist[256];
   __shared__ uint32_t skey[kSelT];
   __shared__ int32_t sid[kSelT];
   __shared__ int wsum[kSelT / 64];
   __shared__ uint32_t st_prefix, st_mask, st_k;
   __shared__ int st_n;
+  __shared__ int st_rows;  // (RAGGED only)
   const int q = blockIdx.x, tid = threadIdx.x;
   const float* d = dots + (size_t)q * N;
   const uint32_t* arow = allow ? allow + (size_t)q * allow_stride : nullptr;
@@ -42,6 +49,17 @@ __global__ __launch_bounds__(kSelT) void k_cq_select_masked(const float* dots, i
       if (on && (kk & mask) == prefix) atomicAdd(&hist[(kk >> shift) & 255u], 1u);
     }
     __syncthreads();
+    if constexpr (RAGGED) {
+      if (pass == 0) {
+        if (tid == 0) {
+          uint32_t tot = 0u;
+          for (int b = 0; b < 256; ++b) tot += hist[b];
+          st_rows = (int)(tot < (uint32_t)K ? tot : (uint32_t)K);
+        }
+        __syncthreads();
+      }
+      if (st_rows < K) break;  // (uniform) fewer than K eligible rows: all of them are kept
+    }
     if (tid == 0) {
       uint32_t cum = 0u;
       for (int b = 255; b >= 0; --b) {
@@ -104,7 +122,16 @@ __global__ __launch_bounds__(kSelT) void k_cq_select_masked(const float* dots, i
       __syncthreads();
     }
   }
-  if (tid < K) {
+  if constexpr (RAGGED) {
+    const int n = st_rows;
+    if (tid == 0) nrows[q] = n;
+    if (tid < K) {
+      const int32_t i = sid[tid];
+      const bool real = tid < n && i >= 0 && i < N;  // (tid < n implies the rest: n keys were collected)
+      cand[(size_t)q * K + tid] = real ? i : -1;
+      ccos[(size_t)q * K + tid] = real ? d[i] : 0.f;
+    }
+  } else if (tid < K) {
     const int32_t i = sid[tid];
     cand[(size_t)q * K + tid] = i;
     ccos[(size_t)q * K + tid] = i < N ? d[i] : 0.f;  // (i < N always: the host checked K <= eligible rows)
@@ -129,8 +156,15 @@ __global__ __launch_bounds__(256) void k_cq_compact(const float* __restrict__ Y,
 
 void launch_cq_select_masked(const float* dots, int64_t N, int32_t K, const uint32_t* live, const uint32_t* allow,
                              int64_t allow_stride, int32_t* cand, float* ccos, int32_t nq, hipStream_t s) {
-  hipLaunchKernelGGL(k_cq_select_masked, dim3((unsigned)nq), dim3(kSelT), 0, s, dots, N, K, live, allow, allow_stride, cand,
-                     ccos);
+  hipLaunchKernelGGL(k_cq_select_masked<false>, dim3((unsigned)nq), dim3(kSelT), 0, s, dots, N, K, live, allow, allow_stride,
+                     cand, ccos, (int32_t*)nullptr);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_cq_select_ragged(const float* dots, int64_t N, int32_t K, const uint32_t* live, const uint32_t* allow,
+                             int64_t allow_stride, int32_t* cand, float* ccos, int32_t* nrows, int32_t nq, hipStream_t s) {
+  hipLaunchKernelGGL(k_cq_select_masked<true>, dim3((unsigned)nq), dim3(kSelT), 0, s, dots, N, K, live, allow, allow_stride,
+                     cand, ccos, nrows);
   HIP_CHECK(hipGetLastError());
 }
 

@@ -370,13 +370,10 @@ __global__ __launch_bounds__(256, 2) void k_knn_topk(const float* __restrict__ Y
 // (QR: the query rows are the nq listed ones -- Sm row b scores lattice row qrows[b] -- instead of a contiguous range; the
 // tile arithmetic is the same, so a listed row's scores are those of the range form bit for bit: osc_create_appended)
 template <bool QR>
-__global__ __launch_bounds__(256, 2) void k_knn_dense(const float* __restrict__ Yn, int32_t ldn, int32_t N,
-                                                      float* __restrict__ Sm, int32_t lds_, int32_t row_base,
-                                                      int64_t lat_yn, int64_t lat_sm, const int32_t* __restrict__ qrows,
-                                                      int32_t nq) {
+__device__ __forceinline__ void knn_dense_body(const float* __restrict__ Yn, int32_t ldn, int32_t N, float* __restrict__ Sm,
+                                               int32_t lds_, int32_t row_base, const int32_t* __restrict__ qrows,
+                                               int32_t nq) {
   __shared__ __attribute__((aligned(16))) float lds[2 * BM * LDT];
-  Yn += blockIdx.z * lat_yn;
-  Sm += blockIdx.z * lat_sm;
   float* As = lds;
   float* Bs = lds + BM * LDT;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -453,26 +450,42 @@ __global__ __launch_bounds__(256, 2) void k_knn_dense(const float* __restrict__ 
   }
 }
 
+template <bool QR>
+__global__ __launch_bounds__(256, 2) void k_knn_dense(const float* __restrict__ Yn, int32_t ldn, int32_t N,
+                                                      float* __restrict__ Sm, int32_t lds_, int32_t row_base,
+                                                      int64_t lat_yn, int64_t lat_sm, const int32_t* __restrict__ qrows,
+                                                      int32_t nq) {
+  knn_dense_body<QR>(Yn + blockIdx.z * lat_yn, ldn, N, Sm + blockIdx.z * lat_sm, lds_, row_base, qrows, nq);
+}
+
+// the ragged batch (corpus refine): lattice z has nrows[z] <= K rows at the front of a K-row slot.
+// Strides come from K, the row and column guards (and the clamped staging rows) from nrows[z]; a tile past the lattice's
+// rows has nothing to write.  A tile's arithmetic does not depend on N, so S is what the lattice's own launch writes.
+__global__ __launch_bounds__(256, 2) void k_knn_dense_ragged(const float* __restrict__ Yn, int32_t ldn, int32_t K,
+                                                             const int32_t* __restrict__ nrows, float* __restrict__ Sm,
+                                                             int32_t lds_) {
+  const int n = nrows[blockIdx.z];
+  if ((int)(blockIdx.y * BM) >= n || (int)(blockIdx.x * BN) >= n) return;  // (uniform)
+  knn_dense_body<false>(Yn + (size_t)blockIdx.z * K * ldn, ldn, n, Sm + (size_t)blockIdx.z * K * lds_, lds_, 0, nullptr, 0);
+}
+
 // one wave per row: the k best columns by (similarity desc, index asc), diagonal excluded (graph.py:37, 46-49), values
 // clipped at 0 (graph.py:62).  M = registers per lane (64 M >= N).
 // (blockIdx.y = lattice of a batch as in k_knn_dense: its rows and column ids are offset by blockIdx.y * N in the lists)
+// (knn_select_row: the wave's work for one row -- the `take` best of the N columns into the row's lists ov / oi, column ids
+// offset by id0; returns how many it wrote)
 template <int M>
-__global__ __launch_bounds__(256) void k_knn_select(const float* __restrict__ Sm, int32_t lds_, int32_t N, int32_t k,
-                                                    float* out_val, int32_t* out_idx, int64_t lat_sm) {
+__device__ __forceinline__ int knn_select_row(const float* __restrict__ Sm, int32_t lds_, int32_t N, int32_t take, int row,
+                                              int id0, float* ov, int32_t* oi) {
   const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= N) return;
-  Sm += blockIdx.y * lat_sm;
-  out_val += (size_t)blockIdx.y * N * k;
-  out_idx += (size_t)blockIdx.y * N * k;
-  const int id0 = (int)blockIdx.y * N;
   float v[M];
 #pragma unroll
   for (int m = 0; m < M; ++m) {
     const int c = lane + 64 * m;
     v[m] = (c < N && c != row) ? Sm[(size_t)row * lds_ + c] : NEG;
   }
-  for (int r = 0; r < k; ++r) {
+  int r = 0;
+  for (; r < take; ++r) {
     float bv = v[0];
     int bm = 0;
 #pragma unroll
@@ -500,9 +513,42 @@ __global__ __launch_bounds__(256) void k_knn_select(const float* __restrict__ Sm
         if (m == bm) v[m] = NEG;
     }
     if (lane == 0) {
-      out_val[(size_t)row * k + r] = fmaxf(wv, 0.f);
-      out_idx[(size_t)row * k + r] = id0 + wi;
+      ov[r] = fmaxf(wv, 0.f);
+      oi[r] = id0 + wi;
     }
+  }
+  return r;
+}
+
+template <int M>
+__global__ __launch_bounds__(256) void k_knn_select(const float* __restrict__ Sm, int32_t lds_, int32_t N, int32_t k,
+                                                    float* out_val, int32_t* out_idx, int64_t lat_sm) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= N) return;
+  const size_t at = ((size_t)blockIdx.y * N + row) * k;
+  knn_select_row<M>(Sm + blockIdx.y * lat_sm, lds_, N, k, row, (int)blockIdx.y * N, out_val + at, out_idx + at);
+}
+
+// the ragged batch: lattice y has n = nrows[y] rows in a K-row slot.  A row below n takes its
+// min(k, n - 1) best among the lattice's n columns (graph.py:30-32 for a lattice of n rows; the reference's filtered loop,
+// proof_hallucination.py:203-221, builds exactly that); the rest of its k-wide list, and the whole list of a row at or
+// beyond n, is (idx -1, val 0), which k_mutual_ell's `v > 0 && j >= 0` drops -- such a row ends with deg 0.
+template <int M>
+__global__ __launch_bounds__(256) void k_knn_select_ragged(const float* __restrict__ Sm, int32_t lds_, int32_t K, int32_t k,
+                                                           const int32_t* __restrict__ nrows, float* out_val,
+                                                           int32_t* out_idx) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= K) return;
+  const int n = nrows[blockIdx.y];
+  const size_t at = ((size_t)blockIdx.y * K + row) * k;
+  int done = 0;
+  if (row < n)
+    done = knn_select_row<M>(Sm + (size_t)blockIdx.y * K * lds_, lds_, n, min(k, n - 1), row, (int)blockIdx.y * K,
+                             out_val + at, out_idx + at);
+  for (int e = done + lane; e < k; e += 64) {
+    out_val[at + e] = 0.f;
+    out_idx[at + e] = -1;
   }
 }
 
@@ -1403,6 +1449,22 @@ void launch_knn_dense_many(const float* Yn, int32_t ldn, int32_t N, int32_t nlat
   else if (m <= 96) OSC_SEL(96);
   else if (m <= 112) OSC_SEL(112);
   else OSC_SEL(128);
+#undef OSC_SEL
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_knn_dense_ragged(const float* Yn, int32_t ldn, int32_t K, const int32_t* nrows, int32_t nlat, int32_t k, float* Sm,
+                             int32_t lds_, float* out_val, int32_t* out_idx, hipStream_t s) {
+  if (K > 1024) throw std::runtime_error("launch_knn_dense_ragged: K > 1024");
+  if (nlat < 1) return;
+  const int nb = (K + BM - 1) / BM;
+  hipLaunchKernelGGL(k_knn_dense_ragged, dim3(nb, nb, nlat), dim3(256), 0, s, Yn, ldn, K, nrows, Sm, lds_);
+  const dim3 grid((unsigned)((K + 3) / 4), (unsigned)nlat), block(256);
+  const int m = (K + 63) / 64;
+#define OSC_SEL(MM) hipLaunchKernelGGL(k_knn_select_ragged<MM>, grid, block, 0, s, Sm, lds_, K, k, nrows, out_val, out_idx)
+  if (m <= 4) OSC_SEL(4);
+  else if (m <= 8) OSC_SEL(8);
+  else OSC_SEL(16);  // (K <= 1024: the corpus refine's limit)
 #undef OSC_SEL
   HIP_CHECK(hipGetLastError());
 }

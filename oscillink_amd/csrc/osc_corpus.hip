@@ -22,11 +22,16 @@
 //   k_cq_solve_chain / k_cq_settle_chain / k_cq_receipt_chain : the three above with lamP L_path in the operator
 //   k_cq_chain_receipt : chain_receipt() of every lattice's own chain from U*, behind the bundle
 //
+//   (a call armed by osc_corpus_ragged) lattice q has nrows[q] <= K rows at the front of its K-row
+//   slot: the ragged instances of the masked select, the gather and the dense kNN write -1 / 0 behind them, and every
+//   per-lattice kernel runs its row loops to CqLattice::rows(q).  When every lattice has K rows the chunk is the one above.
+//
 // No workgroup waits on another: every kernel's workgroups are independent.  Every per-lattice kernel's arguments begin with
 // the same CqLattice block (corpus_pcg.hpp), which run_chunk fills once.
 #include "osc_internal.hpp"
 #include "knn.hpp"
 #include "corpus_plan.hpp"
+#include "corpus_ragged.hpp"
 #include "corpus_select.hpp"
 #include "corpus_store.hpp"
 #include "corpus_receipts.hpp"
@@ -40,6 +45,13 @@ struct CorpusFilter {
   std::vector<uint32_t> words;
   int32_t rows = 0;
   int64_t words_per_row = 0;
+};
+
+// armed by osc_corpus_ragged for the next query call: that call's lattices may have fewer than K
+// rows.  rows empty = the counts come from the filter, or from the -1 padding of cand_in
+struct CorpusRagged {
+  bool armed = false;
+  std::vector<int32_t> rows;
 };
 
 struct osc_corpus {
@@ -56,6 +68,9 @@ struct osc_corpus {
   bool d_live_current = false;
   CorpusFilter filter;
   osc::DevBuf<uint32_t> d_filter;  // one chunk's rows of the call's filter
+  CorpusRagged ragged;
+  std::vector<int32_t> last_rows;  // the row counts of the last call that was armed ragged (osc_corpus_ragged_rows)
+  osc::DevBuf<int32_t> d_rows;     // one chunk's row counts of a ragged call
   osc::DevBuf<unsigned char> scratch;
   std::string err;
   ~osc_corpus() {
@@ -63,6 +78,7 @@ struct osc_corpus {
     Yn.release();
     d_live.release();
     d_filter.release();
+    d_rows.release();
     scratch.release();
     if (stream) release_stream(device, stream);
   }
@@ -251,12 +267,29 @@ __global__ __launch_bounds__(kSelT) void k_cq_select(const float* dots, int64_t 
 }
 
 // union row g = q K + r <- corpus row cand[q][r]: Y, Yn and the solve's x0 = Y (lattice.py:245-263)
+// RAGGED: lattice q has nrows[q] <= K rows; the rows behind them in its slot are written as zeros
+// (cand is -1 there), so that nothing downstream can meet scratch left by an earlier chunk
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void k_cq_gather(const float* Y, const float* Yn, int32_t ldn, const int32_t* cand,
-                                                   int64_t rows, float* Yc, float* Ync, float* X) {
+                                                   int64_t rows, float* Yc, float* Ync, float* X, int32_t K,
+                                                   const int32_t* nrows) {
   const int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (g >= rows) return;
   const int lane = threadIdx.x & 63;
-  const size_t src = (size_t)cand[g] * ldn, dst = (size_t)g * ldn;
+  const size_t dst = (size_t)g * ldn;
+  if constexpr (RAGGED) {
+    const int64_t q = g / K;
+    if (g - q * K >= nrows[q]) {  // (wave-uniform: a wave per row)
+      const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int c = lane * 4; c < ldn; c += 256) {
+        *reinterpret_cast<float4*>(Yc + dst + c) = z;
+        *reinterpret_cast<float4*>(X + dst + c) = z;
+        *reinterpret_cast<float4*>(Ync + dst + c) = z;
+      }
+      return;
+    }
+  }
+  const size_t src = (size_t)cand[g] * ldn;
   for (int c = lane * 4; c < ldn; c += 256) {
     const float4 y = *reinterpret_cast<const float4*>(Y + src + c);
     *reinterpret_cast<float4*>(Yc + dst + c) = y;
@@ -304,7 +337,8 @@ __global__ __launch_bounds__(256) void k_cq_solve(const CqPcgArgs a) {
     __shared__ float s_cs[host::kCorpusMaxTopK], s_inv[host::kCorpusMaxTopK];
     const int tid = threadIdx.x, lat = blockIdx.x;
     const int64_t r0 = (int64_t)lat * g.K;
-    for (int r = tid; r < g.K; r += 256) {
+    const int n = g.rows(lat);
+    for (int r = tid; r < n; r += 256) {
       const float Bi = g.B[r0 + r];
       s_cs[r] = fmaf(g.lamQ, Bi, g.lamG + g.lamC);
       s_inv[r] = 1.f / (fmaf(g.lamQ, Bi, g.lamG) + 1e-12f);
@@ -346,8 +380,9 @@ __global__ __launch_bounds__(256) void k_cq_bundle(const BundleArgs a) {
   __shared__ int s_bi[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const CqLattice& g = a.lat;
-  const int lat = blockIdx.x, K = g.K;
-  const int64_t r0 = (int64_t)lat * K;
+  const int lat = blockIdx.x, K = g.rows(lat);  // (the lattice's own row count; its slot is g.K rows)
+  const int64_t r0 = (int64_t)lat * g.K;
+  const int steps = min(a.kk, K);               // a lattice of fewer than kk rows is picked empty: the rest is padding
   const float* psi = g.psi + (size_t)lat * g.ldn;
   const float qinv = 1.0f / g.qnorm[lat];
   for (int c = tid; c < g.ldn; c += 256) qn[c] = psi[c] * qinv;
@@ -415,8 +450,13 @@ __global__ __launch_bounds__(256) void k_cq_bundle(const BundleArgs a) {
     s_max[r] = 0.0;
   }
   __syncthreads();
-  const float* S = a.Sm + (size_t)lat * K * a.lds;
-  for (int t = 0; t < a.kk; ++t) {
+  const float* S = a.Sm + (size_t)lat * g.K * a.lds;
+  for (int t = tid + steps; t < a.kk; t += 256) {  // (ragged chunks only: steps = kk otherwise)
+    a.o_local[(size_t)lat * a.kk + t] = -1;
+    a.o_score[(size_t)lat * a.kk + t] = 0.f;
+    a.o_align[(size_t)lat * a.kk + t] = 0.f;
+  }
+  for (int t = 0; t < steps; ++t) {
     double bv = -1.0e300;
     int bi = 0x7fffffff;
     for (int r = tid; r < K; r += 256) {
@@ -457,7 +497,7 @@ __global__ __launch_bounds__(256) void k_cq_bundle(const BundleArgs a) {
       a.o_align[(size_t)lat * a.kk + t] = s_align[bi];
       s_base[bi] = -INFINITY;
     }
-    if (t + 1 < a.kk) {
+    if (t + 1 < steps) {
       const float* srow = S + (size_t)bi * a.lds;
       for (int r = tid; r < K; r += 256) {
         const double sv = (double)srow[r];
@@ -495,8 +535,8 @@ __global__ __launch_bounds__(256) void k_cq_gates(const GateArgs a) {
   __shared__ float s_mm[2][4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const CqLattice& g = a.lat;
-  const int lat = blockIdx.x, K = g.K;
-  const int64_t r0 = (int64_t)lat * K;
+  const int lat = blockIdx.x, K = g.rows(lat);  // (the lattice's own row count; its slot is g.K rows)
+  const int64_t r0 = (int64_t)lat * g.K;
   const float* psi = g.psi + (size_t)lat * g.ldn;
   const float qinv = 1.0f / g.qnorm[lat];
   for (int c = tid; c < g.ldn; c += 256) qn[c] = psi[c] * qinv;
@@ -624,6 +664,7 @@ __global__ __launch_bounds__(256) void k_cq_gates(const GateArgs a) {
       a.gates[r0 + row] = g;
     }
   }
+  for (int row = K + tid; row < a.lat.K; row += 256) a.gates[r0 + row] = 0.f;  // a ragged slot's padding
   if (tid == 0) {
     a.iters[lat] = it > a.max_iters ? a.max_iters : it;
     a.res[lat] = resv;
@@ -659,11 +700,12 @@ int corpus_guarded(osc_corpus* h, F&& f) {
   }
 }
 
-// a call that searches or takes candidates: whatever it returns, the filter armed for it is spent
+// a call that searches or takes candidates: whatever it returns, the filter and the ragged arming made for it are spent
 template <class F>
 int corpus_query(osc_corpus* h, F&& f) {
   const int rc = corpus_guarded(h, f);
   if (h) h->filter = CorpusFilter{};
+  if (h) h->ragged = CorpusRagged{};
   return rc;
 }
 
@@ -700,6 +742,12 @@ struct RefineReq {
   // the call's filter (osc_corpus_filter), set by set_k_and_filter: rows of store_words(N) words, nullptr = none
   const uint32_t* allow = nullptr;
   int64_t allow_stride = 0;  // words from one query's row to the next; 0 = one row for every query
+  // a call armed by osc_corpus_ragged (set_k_and_filter / set_ragged): rows_store = the Q row counts, empty when the call was
+  // not armed; ragged = some lattice has fewer than K rows, so the chunk runs the ragged kernels
+  std::vector<int32_t> rows_store;
+  std::vector<float> gates_store;  // gates_in of a ragged call with zeros behind each lattice's rows
+  bool ragged = false;
+  int32_t rows_of(int32_t q) const { return rows_store.empty() ? K : rows_store[(size_t)q]; }
 };
 
 // the device copy of the live bitmap, as of now
@@ -727,6 +775,12 @@ host::CorpusLayout run_chunk(osc_corpus& c, const RefineReq& rq, int32_t q0, int
   float* psi = at<float>(c, L.psi);
   float* qnorm = at<float>(c, L.qnorm);
   int32_t* cand = at<int32_t>(c, L.cand);
+  const int32_t* nrows = nullptr;  // the chunk's row counts on the device: a ragged chunk only
+  if (rq.ragged) {
+    if (c.d_rows.n < (size_t)cap_nq) c.d_rows.alloc((size_t)cap_nq);
+    HIP_CHECK(hipMemcpyAsync(c.d_rows.p, rq.rows_store.data() + q0, (size_t)nq * 4, hipMemcpyHostToDevice, s));
+    nrows = c.d_rows.p;
+  }
   // prep, and the candidates: given, or gemm + select
   HIP_CHECK(hipMemcpyAsync(psi, hp.data(), hp.size() * 4, hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_cq_prep, dim3((unsigned)((nq + 3) / 4)), wg, 0, s, psi, ldn, nq, qnorm);
@@ -747,7 +801,11 @@ host::CorpusLayout run_chunk(osc_corpus& c, const RefineReq& rq, int32_t q0, int
         HIP_CHECK(hipMemcpyAsync(c.d_filter.p, rq.allow + (size_t)q0 * rq.allow_stride, words * 4, hipMemcpyHostToDevice, s));
         d_allow = c.d_filter.p;
       }
-      launch_cq_select_masked(dots, c.N, K, live_on_device(c), d_allow, rq.allow_stride, cand, at<float>(c, L.ccos), nq, s);
+      if (rq.ragged)  // (writes the counts it finds over the uploaded ones: the same numbers, from the device's own popcount)
+        launch_cq_select_ragged(dots, c.N, K, live_on_device(c), d_allow, rq.allow_stride, cand, at<float>(c, L.ccos),
+                                c.d_rows.p, nq, s);
+      else
+        launch_cq_select_masked(dots, c.N, K, live_on_device(c), d_allow, rq.allow_stride, cand, at<float>(c, L.ccos), nq, s);
     }
   }
   HIP_CHECK(hipGetLastError());
@@ -757,7 +815,12 @@ host::CorpusLayout run_chunk(osc_corpus& c, const RefineReq& rq, int32_t q0, int
   float* Yc = at<float>(c, L.Y);
   float* Ync = at<float>(c, L.Yn);
   float* X = at<float>(c, L.X);
-  hipLaunchKernelGGL(k_cq_gather, dim3((unsigned)((rows + 3) / 4)), wg, 0, s, c.Y.p, c.Yn.p, ldn, cand, rows, Yc, Ync, X);
+  if (rq.ragged)
+    hipLaunchKernelGGL(k_cq_gather<true>, dim3((unsigned)((rows + 3) / 4)), wg, 0, s, c.Y.p, c.Yn.p, ldn, cand, rows, Yc, Ync, X,
+                       K, nrows);
+  else
+    hipLaunchKernelGGL(k_cq_gather<false>, dim3((unsigned)((rows + 3) / 4)), wg, 0, s, c.Y.p, c.Yn.p, ldn, cand, rows, Yc, Ync,
+                       X, K, nrows);
   HIP_CHECK(hipGetLastError());
   // the graph of every lattice
   const int32_t lds = host::corpus_lds(K);
@@ -768,14 +831,16 @@ host::CorpusLayout run_chunk(osc_corpus& c, const RefineReq& rq, int32_t q0, int
   float* sd = at<float>(c, L.sd);
   float* Sm = at<float>(c, L.Sm);
   if (rq.knn > 0) {  // the dense route of the lattice build (osc_graph.hip, KnnRoute::dense), every lattice at once
-    launch_knn_dense_many(Ync, ldn, K, nq, k, Sm, lds, at<float>(c, L.kval), at<int32_t>(c, L.kidx), s);
+    if (rq.ragged) launch_knn_dense_ragged(Ync, ldn, K, nrows, nq, k, Sm, lds, at<float>(c, L.kval), at<int32_t>(c, L.kidx), s);
+    else launch_knn_dense_many(Ync, ldn, K, nq, k, Sm, lds, at<float>(c, L.kval), at<int32_t>(c, L.kidx), s);
     launch_mutual_ell(at<float>(c, L.kval), at<int32_t>(c, L.kidx), (int32_t)rows, k, k, col, adj, deg, s);
   } else {  // one-row lattices have no edges (graph.py:30-32)
     HIP_CHECK(hipMemsetAsync(deg, 0, (size_t)rows * 4, s));
   }
   launch_cap_and_normalize(adj, w, col, deg, k, (int32_t)rows, rq.row_cap, 1, at<float>(c, L.scale), sd, s);
   float* gates = at<float>(c, L.gates);
-  const CqLattice lat{Yc, psi, qnorm, col, w, adj, deg, sd, rq.gate ? gates : nullptr, K, k, ldn, rq.lamG, rq.lamC, rq.lamQ};
+  const CqLattice lat{Yc, psi, qnorm, col, w, adj, deg, sd, rq.gate ? gates : nullptr, K, k, ldn, rq.lamG, rq.lamC, rq.lamQ,
+                      nrows};
   // gates: solved per lattice, or given
   if (rq.gate == 1) {
     const GateArgs ga{lat, Ync, gates, at<int32_t>(c, L.g_iters), at<float>(c, L.g_res), rq.g_max_iters, rq.g_direct,
@@ -864,18 +929,40 @@ void check_candidates(const osc_corpus& c, const int32_t* cand, int32_t Q, int32
   }
 }
 
+// the same for a ragged call: row q's first rows[q] entries are checked, the entries behind them must be the pad id
+void check_candidates_ragged(const osc_corpus& c, const int32_t* cand, int32_t Q, int32_t K, const int32_t* rows) {
+  for (int32_t q = 0; q < Q; ++q) {
+    const int32_t* row = cand + (size_t)q * K;
+    if (host::ragged_lead(row, K) != rows[q])
+      throw Invalid("candidates: query " + std::to_string(q) + " must hold its " + std::to_string(rows[q]) +
+                    " ids in front and -1 behind them");
+    for (int32_t t = 0; t < rows[q]; ++t) {
+      if (row[t] >= c.N) throw Invalid("candidates: corpus id out of range");
+      if (!host::store_get(c.live.data(), row[t]))
+        throw Invalid("candidates: query " + std::to_string(q) + " names removed id " + std::to_string(row[t]));
+    }
+  }
+}
+
 // K of a call, and its filter attached to the request: min(top_k, live rows), of which every query must have K eligible
 // ones (live and allowed).  Before any device work.
 int32_t set_k_and_filter(const osc_corpus& c, RefineReq& rq, int32_t top_k) {
   if (c.n_live == 0) throw Invalid("the corpus has no live rows");
   const int32_t K = (int32_t)std::min<int64_t>(top_k, c.n_live);
   const CorpusFilter& fl = c.filter;
+  const bool rg = c.ragged.armed;  // a ragged call keeps whichever rows pass (proof_hallucination.py:203-221): 1 .. K of them
+  if (rg) rq.rows_store.assign((size_t)rq.Q, K);
   if (fl.rows == 0) return K;
   if (rq.cand_in) throw Invalid("a filter cannot be combined with candidates");
   if (fl.rows != 1 && fl.rows != rq.Q) throw Invalid("the filter must have 1 row or one row per query");
   if (fl.words_per_row != host::store_words(c.N)) throw Invalid("the filter was armed for another row count");
   for (int32_t q = 0; q < (fl.rows == 1 ? std::min(rq.Q, 1) : rq.Q); ++q) {
     const int64_t n = host::store_count(c.live.data(), fl.words.data() + (size_t)q * fl.words_per_row, c.N);
+    if (rg && n > 0) {
+      if (fl.rows == 1) rq.rows_store.assign((size_t)rq.Q, host::ragged_rows(n, K));
+      else rq.rows_store[(size_t)q] = host::ragged_rows(n, K);
+      continue;
+    }
     if (n < K)
       throw Invalid("filter: query " + std::to_string(q) + " has " + std::to_string(n) + " eligible rows, fewer than K = " +
                     std::to_string(K));
@@ -883,6 +970,32 @@ int32_t set_k_and_filter(const osc_corpus& c, RefineReq& rq, int32_t top_k) {
   rq.allow = fl.words.data();
   rq.allow_stride = fl.rows == 1 ? 0 : fl.words_per_row;
   return K;
+}
+
+// the row counts of a call armed by osc_corpus_ragged, behind set_k_and_filter (which took them from the filter): given with
+// the arming, or read off cand_in's padding; checked, kept for osc_corpus_ragged_rows, and the call marked ragged unless
+// every lattice fills its slot.  Before any device work.
+void set_ragged(osc_corpus& c, RefineReq& rq) {
+  if (!c.ragged.armed) return;
+  const int32_t Q = rq.Q, K = rq.K;
+  if (!c.ragged.rows.empty()) {
+    if ((int64_t)c.ragged.rows.size() != Q) throw Invalid("ragged: the row counts were armed for another Q");
+    if (!rq.cand_in && c.ragged.rows != rq.rows_store)  // (searched candidates: the counts are the eligible rows', or K)
+      throw Invalid("ragged: the row counts given are not min(K, eligible rows)");
+    rq.rows_store = c.ragged.rows;
+  } else if (rq.cand_in) {
+    for (int32_t q = 0; q < Q; ++q) {
+      const int32_t n = host::ragged_lead(rq.cand_in + (size_t)q * K, K);
+      if (n < 0) throw Invalid("candidates: query " + std::to_string(q) + " has an id behind a -1");
+      rq.rows_store[(size_t)q] = n;
+    }
+  }
+  const int32_t bad = host::ragged_first_bad(rq.rows_store.data(), Q, K);
+  if (bad >= 0)
+    throw Invalid("ragged: query " + std::to_string(bad) + " has " + std::to_string(rq.rows_store[(size_t)bad]) +
+                  " rows, need 1 .. K = " + std::to_string(K));
+  c.last_rows = rq.rows_store;
+  rq.ragged = !host::ragged_is_uniform(rq.rows_store.data(), Q, K);
 }
 
 int32_t chunk_for(const osc_corpus& c, int32_t K, int32_t knn, int32_t kk, bool receipts = false, int32_t null_slots = 0,
@@ -1019,11 +1132,13 @@ void check_request(const osc_corpus& c, const RefineReq& rq) {
 }
 
 // K and the list length of the request's lattices, its filter attached, and its candidates checked if given
-void set_shape(const osc_corpus& c, RefineReq& rq) {
+void set_shape(osc_corpus& c, RefineReq& rq) {
   rq.K = set_k_and_filter(c, rq, rq.top_k);
   rq.knn = rq.K > 1 ? host::corpus_knn(rq.kneighbors, rq.K) : 0;
   if (rq.knn > host::kCorpusMaxKnn) throw Invalid("min(kneighbors, K - 1) must be at most 128");
-  if (rq.cand_in) check_candidates(c, rq.cand_in, rq.Q, rq.K);
+  set_ragged(c, rq);
+  if (rq.cand_in && !rq.rows_store.empty()) check_candidates_ragged(c, rq.cand_in, rq.Q, rq.K, rq.rows_store.data());
+  else if (rq.cand_in) check_candidates(c, rq.cand_in, rq.Q, rq.K);
 }
 
 // runs the request chunk by chunk; fetch(L, q0, n, down) queues the chunk's downloads, then the stream is drained
@@ -1129,8 +1244,17 @@ void refine_body(osc_corpus& c, RefineReq rq, const RefineOut& o, const char* nu
   set_shape(c, rq);
   rq.kk = std::min(std::max(rq.kk, 0), rq.K);
   if (rq.gate == 2)
-    for (int64_t i = 0; i < (int64_t)Q * rq.K; ++i)
-      if (!std::isfinite(rq.gates_in[i]) || rq.gates_in[i] < 0.f) throw Invalid("gates must be finite and >= 0");
+    for (int32_t q = 0; q < Q; ++q)
+      for (int32_t r = 0; r < rq.rows_of(q); ++r) {
+        const float gv = rq.gates_in[(size_t)q * rq.K + r];
+        if (!std::isfinite(gv) || gv < 0.f) throw Invalid("gates must be finite and >= 0");
+      }
+  if (rq.gate == 2 && rq.ragged) {  // only a lattice's own rows are read: zeros behind them
+    rq.gates_store.resize((size_t)Q * rq.K);
+    for (int32_t q = 0; q < Q; ++q)
+      host::ragged_copy_padded(rq.gates_in + (size_t)q * rq.K, rq.rows_of(q), rq.K, 0.f, rq.gates_store.data() + (size_t)q * rq.K);
+    rq.gates_in = rq.gates_store.data();
+  }
   if (ro) {
     if (!ro->null_offsets) throw Invalid(null_msg);
     ro->null_offsets[0] = 0;
@@ -1148,7 +1272,7 @@ void refine_body(osc_corpus& c, RefineReq rq, const RefineOut& o, const char* nu
       if (len > host::kCorpusMaxChain) throw Invalid("a chain has at most 1024 indices");
       if (len > 0 && !rq.c_nodes) throw Invalid(null_msg);
       for (int64_t t = rq.c_off[q]; t < rq.c_off[q + 1]; ++t)
-        if (rq.c_nodes[t] < 0 || rq.c_nodes[t] >= rq.K) throw Invalid("chain indices out of bounds");
+        if (rq.c_nodes[t] < 0 || rq.c_nodes[t] >= rq.rows_of(q)) throw Invalid("chain indices out of bounds");
       eoff[(size_t)q + 1] = eoff[(size_t)q] + std::max<int64_t>(0, len - 1);
       rq.chain_cap = std::max(rq.chain_cap, (int32_t)std::max<int64_t>(0, len - 1));
     }
@@ -1275,6 +1399,7 @@ int osc_corpus_search(osc_corpus_handle h, const float* psis, int32_t Q, int32_t
     rq.psis = psis;
     rq.Q = Q;
     rq.K = set_k_and_filter(c, rq, top_k);
+    set_ragged(c, rq);
     rq.stage = 0;
     for_each_chunk(c, rq, [&](const host::CorpusLayout& L, int32_t q0, int32_t n, auto& down) {
       down(ids + (size_t)q0 * rq.K, L.cand, (size_t)n * rq.K * 4);
@@ -1553,6 +1678,7 @@ int osc_corpus_compact(osc_corpus_handle h, int32_t* new_id_of_old_or_null, int6
     c.d_live_current = false;
     c.N = c.n_live = n;
     c.filter = CorpusFilter{};  // (armed for ids that no longer exist)
+    c.ragged = CorpusRagged{};
   });
 }
 
@@ -1566,6 +1692,23 @@ int osc_corpus_filter(osc_corpus_handle h, const uint32_t* words, int32_t rows, 
     c.filter.words.assign(words, words + (size_t)rows * words_per_row);
     c.filter.rows = rows;
     c.filter.words_per_row = words_per_row;
+  });
+}
+
+int osc_corpus_ragged(osc_corpus_handle h, const int32_t* rows_or_null, int32_t Q) {
+  return corpus_guarded(h, [&](osc_corpus& c) {
+    c.ragged = CorpusRagged{};
+    if (Q < 0) return;
+    c.ragged.armed = true;
+    if (rows_or_null) c.ragged.rows.assign(rows_or_null, rows_or_null + Q);
+  });
+}
+
+int osc_corpus_ragged_rows(osc_corpus_handle h, int32_t* rows, int32_t Q) {
+  return corpus_guarded(h, [&](osc_corpus& c) {
+    if (Q < 0 || (Q > 0 && !rows)) throw Invalid("osc_corpus_ragged_rows: need Q >= 0 and rows != NULL");
+    if ((int64_t)c.last_rows.size() != Q) throw Invalid("osc_corpus_ragged_rows: the last ragged call had another Q");
+    std::copy(c.last_rows.begin(), c.last_rows.end(), rows);
   });
 }
 
