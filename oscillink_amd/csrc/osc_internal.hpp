@@ -339,7 +339,7 @@ struct osc_lattice {
     uint64_t epoch = 0;        // derived.epoch of the basis
     float scale = 0.f;         // |psi|_inf the x part was solved for (its residual target is tol / (2 scale))
     DevBuf<float> X, x4;       // N x ld, N x 4 (column 0 = x)
-    DevBuf<float> s;           // [N] x / (sd + 1e-12)
+    DevBuf<double> s;          // [N] x / (sd + 1e-12)
     DevBuf<double> xn2, c0, c2;
     DevBuf<float> Yn;          // row-normalised anchors (the MMR's representers)
     uint64_t yn_epoch = 0;
@@ -381,7 +381,7 @@ struct osc_lattice {
       // gen is bumped by every shifted solve or extension; a new epoch or lamP forces a solve first, so it keys the constants
       // as (epoch, lamP) would -- at the cost that an x-only extension also recomputes c0 and |X'|^2, which did not change.
       uint64_t gen = 0, stats_gen = 0;
-      DevBuf<float> s;
+      DevBuf<double> s;
       DevBuf<double> xn2, c0, c2;
       // osc_receipt_prior_many: section 12's per-basis terms on (X', x') and M', under the same gen
       uint64_t rm_gen = 0, rd_gen = 0;

@@ -26,7 +26,7 @@ struct QueryBasisArgs {
   const int32_t* deg;
   int32_t width, N, D, ld;
   float lamC;
-  float* s;             // [N]
+  double* s;            // [N] (fp64: (s_i - s_j)^2 |psi|^2 carries its rounding through every column)
   double* xn2;          // [N]
   double* c0;           // [N]
   double* c2;           // [N]
@@ -58,7 +58,7 @@ void launch_query_gemm(const QueryGemmArgs& a, hipStream_t s);
 
 // coh_iq = c0_i - |psi_q|^2 c2_i - sum_j lamC A_ij (s_i - s_j)(p_iq - p_jq) in fp64, stored fp32
 void launch_query_coh(const int32_t* col, const float* adj, const int32_t* deg, int32_t width, int32_t N, float lamC,
-                      const float* s, const double* c0, const double* c2, const double* pn2, const float* p, int32_t qs,
+                      const double* s, const double* c0, const double* c2, const double* pn2, const float* p, int32_t qs,
                       int32_t nq, float* coh, hipStream_t st);
 // score = alpha (coh - mu_q) / sigma_q + (1 - alpha) align, in place over coh; mu / sigma per query from a deterministic
 // two-stage fp64 column reduction (part: [nb x nq] double2 partials, stats: [nq] double2)
@@ -112,7 +112,7 @@ struct BpArgs {
   int32_t width, N;
   float lamC;
   const float* sqrt_deg;
-  const float* s;         // [N] of the shifted basis, with xn2 / c0 / c2 (k_query_basis_stats on (X', x'))
+  const double* s;        // [N] of the shifted basis, with xn2 / c0 / c2 (k_query_basis_stats on (X', x'))
   const double* xn2;
   const double* c0;
   const double* c2;
@@ -200,7 +200,7 @@ struct RmRowsArgs {
   const float* adj;
   const int32_t* deg;
   const float* dslot;
-  const float* s;
+  const double* s;
   const double* c0;
   const double* c2;
   const double* pn2;

@@ -47,8 +47,8 @@ __global__ __launch_bounds__(256) void k_query_basis_stats(const QueryBasisArgs 
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= a.N) return;
   const float inv_i = 1.0f / (a.sqrt_deg[row] + 1e-12f);
-  const float x_i = a.x4[(size_t)row * 4];
-  const float s_i = x_i * inv_i;
+  // s in fp64: (s_i - s_j)^2 |psi|^2 carries one rounding of s through every column of the row
+  const double s_i = (double)a.x4[(size_t)row * 4] / ((double)a.sqrt_deg[row] + 1e-12);
   const float* yi = a.Y + (size_t)row * a.ld;
   const float* Xi = a.X + (size_t)row * a.ld;
   double n2 = 0.0;
@@ -82,7 +82,7 @@ __global__ __launch_bounds__(256) void k_query_basis_stats(const QueryBasisArgs 
     dy = wave_sum_f(dy);
     dp = wave_sum_f(dp);
     const double hw = 0.5 * (double)a.lamC * (double)w;
-    const double ds = (double)s_i - (double)(a.x4[(size_t)j * 4] * inv_j);
+    const double ds = s_i - (double)a.x4[(size_t)j * 4] / ((double)a.sqrt_deg[j] + 1e-12);
     c0 += hw * ((double)dy - (double)dp);
     c2 += hw * ds * ds;
   }
@@ -189,7 +189,7 @@ __global__ __launch_bounds__(256) void k_query_gemm(const QueryGemmArgs a) {
 // ---- coherence drop per (row, query): one wave per row, lanes over the queries (Q-wide, coalesced neighbour rows) -----
 __global__ __launch_bounds__(256) void k_query_coh(const int32_t* __restrict__ col, const float* __restrict__ adj,
                                                    const int32_t* __restrict__ degs, int32_t width, int32_t N, float lamC,
-                                                   const float* __restrict__ s, const double* __restrict__ c0,
+                                                   const double* __restrict__ s, const double* __restrict__ c0,
                                                    const double* __restrict__ c2, const double* __restrict__ pn2,
                                                    const float* __restrict__ p, int32_t qs, int32_t nq,
                                                    float* __restrict__ coh) {
@@ -205,7 +205,7 @@ __global__ __launch_bounds__(256) void k_query_coh(const int32_t* __restrict__ c
     acc[u] = 0.0;
     pi[u] = q < nq ? (double)prow[q] : 0.0;
   }
-  const double si = (double)s[row];
+  const double si = s[row];
   const int deg = degs[row];
   const int32_t* crow = col + (size_t)row * width;
   const float* arow = adj + (size_t)row * width;
@@ -213,14 +213,14 @@ __global__ __launch_bounds__(256) void k_query_coh(const int32_t* __restrict__ c
     const int e = e0 + lane;
     const int jl = e < deg ? crow[e] : 0;
     const float wl = e < deg ? arow[e] : 0.f;
-    const float sl = e < deg ? s[jl] : 0.f;
+    const double sl = e < deg ? s[jl] : 0.0;
     const int n = min(64, deg - e0);
     for (int tt = 0; tt < n; ++tt) {
       const float wt = __shfl(wl, tt, 64);
       const int jt = __shfl(jl, tt, 64);
-      const float st = __shfl(sl, tt, 64);
+      const double st = __shfl(sl, tt, 64);
       if (!(wt > 0.f)) continue;
-      const double f = (double)lamC * (double)wt * (si - (double)st);
+      const double f = (double)lamC * (double)wt * (si - st);
       const float* pj = p + (size_t)jt * qs;
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -392,7 +392,7 @@ void launch_query_gemm(const QueryGemmArgs& a, hipStream_t s) {
 }
 
 void launch_query_coh(const int32_t* col, const float* adj, const int32_t* deg, int32_t width, int32_t N, float lamC,
-                      const float* s, const double* c0, const double* c2, const double* pn2, const float* p, int32_t qs,
+                      const double* s, const double* c0, const double* c2, const double* pn2, const float* p, int32_t qs,
                       int32_t nq, float* coh, hipStream_t st) {
   hipLaunchKernelGGL(k_query_coh, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, col, adj, deg, width, N, lamC, s, c0, c2,
                      pn2, p, qs, nq, coh);

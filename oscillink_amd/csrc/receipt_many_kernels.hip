@@ -174,23 +174,23 @@ __global__ __launch_bounds__(256) void k_rm_rows(const RmRowsArgs a) {
       jmax[u] = -1;
       pi[u] = q < a.nq ? (double)prow[q] : 0.0;
     }
-    const double si = (double)a.s[row];
+    const double si = a.s[row];
     const int deg = a.deg[row];
     const size_t eo = (size_t)row * a.width;
     for (int e0 = 0; e0 < deg; e0 += 64) {
       const int e = e0 + lane;
       const int jl = e < deg ? a.col[eo + e] : 0;
       const float wl = e < deg ? a.adj[eo + e] : 0.f;
-      const float sl = e < deg ? a.s[jl] : 0.f;
+      const double sl = e < deg ? a.s[jl] : 0.0;
       const float dl = e < deg ? a.dslot[eo + e] : 0.f;
       const int n = min(64, deg - e0);
       for (int tt = 0; tt < n; ++tt) {
         const float wt = __shfl(wl, tt, 64);
         const int jt = __shfl(jl, tt, 64);
-        const float st = __shfl(sl, tt, 64);
+        const double st = __shfl(sl, tt, 64);
         const float dt = __shfl(dl, tt, 64);
         if (!(wt > 0.f)) continue;
-        const double ds = si - (double)st;
+        const double ds = si - st;
         const double fw = lamC * (double)wt;
         const double f = fw * ds;  // k_query_coh's factor
         const double ds2p = ds * ds;
