@@ -5,7 +5,9 @@
 //   kDependsOn    : per cache, the inputs it is computed from (the one place that says so)
 //   Derived       : the validity of every cache (osc_lattice::derived)
 //   changed       : an input changed -- every cache computed from it is dropped
-// A cache is marked as built by assigning its field where it is built (osc_solve.hip, osc_api.hip: osc_solve_ustar).
+//   Level         : the chain of arrays an anchor start keeps, each computed from the ones before it (Cache::anchor_wy is
+//                   the whole chain); held / begin_build / built are the only way a level's validity is read or written
+// Every other cache is marked as built by assigning its field where it is built (osc_solve.hip, osc_api.hip: osc_solve_ustar).
 #pragma once
 #include <cstdint>
 
@@ -28,7 +30,7 @@ enum class Cache : unsigned {
   ell_t,         // ell_col_t / ell_w_t: the transposed ELL of the one-launch solve
   blocked_copy,  // blk_slots / blk_rest / blk_over: the block-major graph copy (Derived::blk_nb blocks)
   anchor_slab,   // Ys: the slab-major image of the anchors over the window
-  anchor_wy,     // WYs: the anchors' row sums W.Y, in the slot placement of a copy of Derived::wy_nb blocks
+  anchor_wy,     // WYs and every Level above it: the anchors' row sums W.Y, in the slot placement of the graph copy
   ustar,         // Ustar
   epoch_keyed,   // the halo plan, the query basis, query.Yn: each keeps the epoch it was built for and compares on use
   count
@@ -54,27 +56,48 @@ constexpr unsigned kDependsOn[(unsigned)Cache::count] = {
 
 constexpr bool depends_on(Cache c, Input i) { return (kDependsOn[(unsigned)c] & bit(i)) != 0; }
 
+// The anchor-start chain, in the order it is built.  Each level is computed from the levels before it and from the block-major
+// graph copy, so it is current exactly while all of them are and were formed with the same block count:
+//   wy     WYs: the anchors' row sums W.Y, slab-major, in the slot placement of the copy
+//   wwy    WWs / Wsum: W.(W.Y) and W.1
+//   w3     W3s / Wsum2 (and the T array): W.(W.(W.Y)) and W.(W.1)
+//   gram   gram: the Gram sums of Ys, WYs, WWs, W3s, Wsum, Wsum2 (anchor_gram.hpp)
+//   gram3  gram3 / Wsum3: the third step's sums, over W.W3s and W.Wsum2 as well
+//   gram4  gram4: the fourth step's sums, over W.W.W3s and W.Wsum3 as well
+//   w4     W4s: W.W3s, kept from the pass that forms gram4 (the polynomial last form)
+enum class Level : unsigned { wy, wwy, w3, gram, gram3, gram4, w4, count };
+constexpr unsigned kLevels = (unsigned)Level::count;
+
 struct Derived {
   bool ell_t = false;
   int blk_nb = 0;  // blocks of the copy held (0 = none)
   bool ys = false;
-  int wy_nb = 0;  // block count the sums were formed with (0 = none held)
-  int wwy_nb = 0;  // WWs / Wsum (the second row sums W.(W.Y) and W.1, built from WYs): same validity, dropped with anchor_wy
-  int w3_nb = 0;   // W3s / Wsum2 (the third row sums W.(W.(W.Y)) and W.(W.1), built from WWs / Wsum): same validity again
-  int gram_nb = 0;  // gram (the Gram sums of Ys, WYs, WWs, W3s, Wsum, Wsum2: anchor_gram.hpp): same validity again
-  int gram3_nb = 0;  // gram3 / Wsum3 (the third step's sums, over W.W3s and W.Wsum2 as well): same validity again
-  int gram4_nb = 0;  // gram4 (the fourth step's sums, over W.W.W3s and W.Wsum3 as well): same validity again
-  int w4_nb = 0;   // W4s (the fourth row sums W.W3s, kept from the pass that forms gram4: the polynomial last form): same validity again
+  int level_nb[kLevels] = {};  // per Level, the block count it was built with (0 = not held): held, begin_build, built
   bool ustar = false;
   uint64_t epoch = 1;  // what an epoch_keyed cache was built for (its own 0 = never built)
 };
+
+// `level` and every level below it were built with `nb` blocks
+inline bool held(const Derived& d, Level level, int nb) {
+  if (nb <= 0) return false;
+  for (unsigned l = 0; l <= (unsigned)level; ++l)
+    if (d.level_nb[l] != nb) return false;
+  return true;
+}
+// ... with whatever block count the chain was begun with (what a reader of the arrays asks)
+inline bool held(const Derived& d, Level level) { return held(d, level, d.level_nb[0]); }
+// `level` is about to be formed anew: it and every level above it are dropped
+inline void begin_build(Derived& d, Level level) {
+  for (unsigned l = (unsigned)level; l < kLevels; ++l) d.level_nb[l] = 0;
+}
+inline void built(Derived& d, Level level, int nb) { d.level_nb[(unsigned)level] = nb; }
 
 inline void drop(Derived& d, Cache c) {
   switch (c) {
     case Cache::ell_t: d.ell_t = false; break;
     case Cache::blocked_copy: d.blk_nb = 0; break;
     case Cache::anchor_slab: d.ys = false; break;
-    case Cache::anchor_wy: d.wy_nb = d.wwy_nb = d.w3_nb = d.gram_nb = d.gram3_nb = d.gram4_nb = d.w4_nb = 0; break;
+    case Cache::anchor_wy: begin_build(d, Level::wy); break;
     case Cache::ustar: d.ustar = false; break;
     case Cache::epoch_keyed: ++d.epoch; break;
     case Cache::count: break;

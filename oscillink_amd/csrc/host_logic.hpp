@@ -22,7 +22,7 @@
 //                                       tests/host_logic/sweep_anchor_gram3.cpp)
 //   anchor_gram4_route                : ... and a solve that ends in iteration 4 has no fourth matvec, alpha4 and |r4| from two
 //                                       more vectors' sums (swept by tests/host_logic/sweep_anchor_gram4.cpp)
-//   anchor_poly_keeps / anchor_poly_route : ... and, where the lattice keeps W^4 Y, no matvec at all: x4 as a polynomial in W
+//   anchor_poly_route                 : ... and, where the lattice keeps W^4 Y, no matvec at all: x4 as a polynomial in W
 //                                       applied to Y and 1 (anchor_gram.hpp: poly4_coeffs; tests/host_logic/sweep_poly4.cpp)
 //   cg_host_loop                      : the host loop of a CG solve -- which iteration is enqueued when (run_cg in
 //                                       osc_solve.hip and both sweeps run this one function)
@@ -577,6 +577,8 @@ inline bool gates_uniform(const float* gates, int64_t n) {
 // Rows from which plan_apply picks the wide kernel shapes on its own: where auto mode serves (smaller lattices keep the
 // gathered first apply until they have a measurement of their own).
 constexpr int64_t kAnchorApAutoRows = 96000;
+// What every level's OSC_ANCHOR_* switch says once the level below holds: 0 never, 1 always, < 0 (unset) by the lattice's rows.
+inline bool anchor_auto_rows(int mode, int64_t N) { return mode != 0 && (mode > 0 || N >= kAnchorApAutoRows); }
 struct AnchorApInputs {
   int mode = -1;               // OSC_ANCHOR_AP: 0 off, 1 wherever the cached INIT runs, < 0 by the lattice's rows
   int64_t N = 0;
@@ -585,8 +587,7 @@ struct AnchorApInputs {
   bool chain_rows = false;     // a chain prior's rows take part in the operator
 };
 inline bool anchor_ap_route(const AnchorApInputs& in) {
-  if (in.mode == 0 || !in.cached_init || !in.gates_uniform || in.chain_rows) return false;
-  return in.mode > 0 || in.N >= kAnchorApAutoRows;
+  return in.cached_init && in.gates_uniform && !in.chain_rows && anchor_auto_rows(in.mode, in.N);
 }
 // the memory rule of the direction ring: the arrays are only taken from a quarter of what is free
 inline bool anchor_ap_fits(int64_t bytes, int64_t free_bytes) { return bytes >= 0 && bytes <= free_bytes / 4; }
@@ -600,8 +601,7 @@ struct AnchorAp2Inputs {
   int max_iters = 0;
 };
 inline bool anchor_ap2_route(const AnchorAp2Inputs& in) {
-  if (in.mode == 0 || !in.depth1 || in.max_iters < 2) return false;
-  return in.mode > 0 || in.N >= kAnchorApAutoRows;
+  return in.depth1 && in.max_iters >= 2 && anchor_auto_rows(in.mode, in.N);
 }
 // Further still: with the float64 Gram sums of the seven vectors the first two iterations are combinations of (anchor_gram.hpp)
 // every scalar of those iterations is known before the INIT pass, which then runs both iterations per element and leaves r2,
@@ -619,8 +619,8 @@ struct AnchorGramInputs {
   int predicted = 0;    // iterations the handle's previous solve of this kind took (0: unknown)
 };
 inline bool anchor_gram_route(const AnchorGramInputs& in) {
-  if (in.mode == 0 || !in.depth2 || in.comm || in.ring_slots < 2 || in.max_iters < 3 || in.predicted < 3) return false;
-  return in.mode > 0 || in.N >= kAnchorApAutoRows;
+  if (!in.depth2 || in.comm || in.ring_slots < 2 || in.max_iters < 3 || in.predicted < 3) return false;
+  return anchor_auto_rows(in.mode, in.N);
 }
 // One iteration further: with the sums of the two vectors A p3 adds (anchor_gram.hpp: three_steps) alpha3, beta3 and |r3| are
 // known before the solve's first launch as well, and iteration 3 is ONE launch: its gathering matvec, whose epilogue forms r3 and
@@ -636,8 +636,8 @@ struct AnchorGram3Inputs {
   int predicted = 0;
 };
 inline bool anchor_gram3_route(const AnchorGram3Inputs& in) {
-  if (in.mode == 0 || !in.gram_route || in.comm || in.ring_slots < 2 || in.max_iters < 3 || in.predicted < 3) return false;
-  return in.mode > 0 || in.N >= kAnchorApAutoRows;
+  if (!in.gram_route || in.comm || in.ring_slots < 2 || in.max_iters < 3 || in.predicted < 3) return false;
+  return anchor_auto_rows(in.mode, in.N);
 }
 // One level of scalars further: with the sums of the two vectors A p4 adds (anchor_gram.hpp: four_steps) alpha4 and |r4| are known
 // before the solve's first launch too.  Iteration 4's vectors are never used by a solve that ends there, so such a solve needs no
@@ -651,8 +651,7 @@ struct AnchorGram4Inputs {
   int max_iters = 0;
 };
 inline bool anchor_gram4_route(const AnchorGram4Inputs& in) {
-  if (in.mode == 0 || !in.gram3_route || in.max_iters < 4) return false;
-  return in.mode > 0 || in.N >= kAnchorApAutoRows;
+  return in.gram3_route && in.max_iters >= 4 && anchor_auto_rows(in.mode, in.N);
 }
 // The published residuals say that the solve ends in iteration 4 and in no earlier one (a NaN compares false: the loop form).
 inline bool anchor_gram4_last_form(float res1, float res2, float res3, float res4, double tol) {
@@ -674,15 +673,15 @@ inline AnchorGram4Words anchor_gram4_device_words(bool four, bool usable, float 
 // The polynomial last form (anchor_gram.hpp: poly4_coeffs; cg_kernels.hip: k_settle_poly): a solve the folded form would serve -- four
 // steps planned, predicted to end in iteration 4 -- whose lattice holds W^4 Y (L::W4s) runs no matvec at all: the scalars kernel and
 // one elementwise pass, gated by the device's go[2].  Where the published residuals then disagree (anchor_gram4_last_form false)
-// nothing was written and run_cg solves again without it.  anchor_poly_keeps: whether the lattice keeps W^4 Y when it forms gram4.
-inline bool anchor_poly_keeps(int mode, int64_t N) { return mode != 0 && (mode > 0 || N >= kAnchorApAutoRows); }
+// nothing was written and run_cg solves again without it.  Whether the lattice keeps W^4 Y when it forms gram4 is anchor_auto_rows
+// of the same switch.
 struct AnchorPolyInputs {
   int mode = -1;       // OSC_ANCHOR_POLY: 0 off, 1 wherever the folded form would run, < 0 by the lattice's rows
   int64_t N = 0;
   bool fold = false;   // the four-step route is planned, the fold is allowed and the prediction is 4
   bool w4_held = false;
 };
-inline bool anchor_poly_route(const AnchorPolyInputs& in) { return in.fold && in.w4_held && anchor_poly_keeps(in.mode, in.N); }
+inline bool anchor_poly_route(const AnchorPolyInputs& in) { return in.fold && in.w4_held && anchor_auto_rows(in.mode, in.N); }
 // Where iteration `it` of a solve gets its A p (CgSolve::enqueue): from the INIT pass (first: it left A p1 and the p . Ap
 // partials), from the iteration's own p update (second: the INIT pass left T), or from a matvec.
 enum class ApSource { matvec, init_pass, p_update };

@@ -34,13 +34,12 @@ void read_env_solver(L& h) {
   if (num("OSC_SMALL_PATH", v)) h.small_path = v != 0;
   if (num("OSC_ANCHOR_SLAB", v)) h.anchor_slab = v != 0;
   if (num("OSC_ANCHOR_WY", v)) h.anchor_wy = v != 0;  // (needs the anchors' image: OSC_ANCHOR_SLAB=0 switches it off too, run_cg)
-  if (num("OSC_ANCHOR_AP", v)) h.anchor_ap = v != 0 ? 1 : 0;
-  if (num("OSC_ANCHOR_AP2", v)) h.anchor_ap2 = v != 0 ? 1 : 0;
-  if (num("OSC_ANCHOR_GRAM", v)) h.anchor_gram = v != 0 ? 1 : 0;
-  if (num("OSC_ANCHOR_GRAM3", v)) h.anchor_gram3 = v != 0 ? 1 : 0;
-  if (num("OSC_ANCHOR_GRAM4", v)) h.anchor_gram4 = v != 0 ? 1 : 0;
+  static const struct { host::Level level; const char* name; } kLevelSwitch[] = {
+      {host::Level::wwy, "OSC_ANCHOR_AP"},     {host::Level::w3, "OSC_ANCHOR_AP2"},     {host::Level::gram, "OSC_ANCHOR_GRAM"},
+      {host::Level::gram3, "OSC_ANCHOR_GRAM3"}, {host::Level::gram4, "OSC_ANCHOR_GRAM4"}, {host::Level::w4, "OSC_ANCHOR_POLY"}};
+  for (const auto& sw : kLevelSwitch)
+    if (num(sw.name, v)) h.at(sw.level).mode = v != 0 ? 1 : 0;
   if (num("OSC_GRAM4_FOLD", v)) h.gram4_fold = v != 0;
-  if (num("OSC_ANCHOR_POLY", v)) h.anchor_poly = v != 0 ? 1 : 0;
   if (num("OSC_ANCHOR_POLY_MAX_MB", v)) h.anchor_poly_max_mb = std::max(0, v);
   if (const char* e = getenv("OSC_TWO_STEPS")) h.two_steps_stream = strcmp(e, "blocked") != 0;
   if (num("OSC_RECEIPT_PAIR", v)) h.receipt_pair = v != 0;
@@ -96,6 +95,22 @@ void read_env(L& h) {
 // U = Y without the copy where a solve owns all of U: one process, the full column window, no row shards.  A windowed
 // handle's or a rank's U keeps columns or rows its solves do not write, so those keep the eager copy (and are not what the
 // alias is for: the first settle of a fresh lattice on one GPU).
+// What a level of the anchor-start chain holds on the device (0 while it is not held)
+int64_t anchor_level_bytes(const L& h, host::Level level) {
+  if (!host::held(h.derived, level)) return 0;
+  switch (level) {
+    case host::Level::wy: return (int64_t)h.WYs.n * 4;
+    case host::Level::wwy: return ((int64_t)h.WWs.n + (int64_t)h.Wsum.n) * 4;
+    case host::Level::w3: return ((int64_t)h.W3s.n + (int64_t)h.Wsum2.n + (int64_t)h.Tap.n) * 4;
+    case host::Level::gram: return (int64_t)h.gram.n * 8;
+    case host::Level::gram3: return (int64_t)h.gram3.n * 8 + (int64_t)h.Wsum3.n * 4;
+    case host::Level::gram4: return (int64_t)h.gram4.n * 8;
+    case host::Level::w4: return (int64_t)h.W4s.n * 4;
+    case host::Level::count: break;
+  }
+  return 0;
+}
+
 bool u_alias_ok(const L& h) { return h.comm == nullptr && h.c0 == 0 && h.c1 == h.dcols && !row_mode(h); }
 
 void reset_u_to_y(L& h) {
@@ -616,68 +631,58 @@ int osc_x_ring_info(osc_handle h, int32_t* slots, int64_t* flushes, int64_t* pas
   });
 }
 
-int osc_anchor_ap_info(osc_handle h, int64_t* streamed_first_applies, int64_t* bytes, int32_t* last_solve, int64_t* builds) {
+// One body for the six osc_anchor_*_info calls and one for the three osc_anchor_gram*_read calls: a level's record and bytes.
+static int anchor_info(osc_handle h, host::Level level, int64_t* solves, int64_t* bytes, int32_t* last_solve, int64_t* builds,
+                       int64_t* redos = nullptr) {
   return guarded(h, [&](L& l) {
-    if (streamed_first_applies) *streamed_first_applies = l.streamed_first_applies;
-    if (bytes) *bytes = l.derived.wwy_nb > 0 ? ((int64_t)l.WWs.n + (int64_t)l.Wsum.n) * 4 : 0;
-    if (last_solve) *last_solve = l.anchor_ap_last ? 1 : 0;
-    if (builds) *builds = l.anchor_ap_builds;
+    const L::AnchorLevel& a = l.at(level);
+    if (solves) *solves = a.solves;
+    if (bytes) *bytes = anchor_level_bytes(l, level);
+    if (last_solve) *last_solve = a.last ? 1 : 0;
+    if (builds) *builds = a.builds;
+    if (redos) *redos = a.redos;
   });
+}
+
+static int anchor_read(osc_handle h, host::Level level, DevBuf<double> L::*sums, double* out, int64_t cap, const char* none_held,
+                       const char* too_small) {
+  return guarded(h, [&](L& l) {
+    const DevBuf<double>& g = l.*sums;
+    if (!host::held(l.derived, level)) throw Unsupported(none_held);
+    if (out == nullptr || cap < (int64_t)g.n) throw Invalid(too_small);
+    HIP_CHECK(hipMemcpyAsync(out, g.p, g.n * sizeof(double), hipMemcpyDeviceToHost, l.stream));
+    sync(l);
+  });
+}
+
+int osc_anchor_ap_info(osc_handle h, int64_t* streamed_first_applies, int64_t* bytes, int32_t* last_solve, int64_t* builds) {
+  return anchor_info(h, host::Level::wwy, streamed_first_applies, bytes, last_solve, builds);
 }
 
 int osc_anchor_ap2_info(osc_handle h, int64_t* streamed_second_applies, int64_t* bytes, int32_t* last_solve, int64_t* builds) {
-  return guarded(h, [&](L& l) {
-    if (streamed_second_applies) *streamed_second_applies = l.streamed_second_applies;
-    if (bytes) *bytes = l.derived.w3_nb > 0 ? ((int64_t)l.W3s.n + (int64_t)l.Wsum2.n + (int64_t)l.Tap.n) * 4 : 0;
-    if (last_solve) *last_solve = l.anchor_ap2_last ? 1 : 0;
-    if (builds) *builds = l.anchor_ap2_builds;
-  });
+  return anchor_info(h, host::Level::w3, streamed_second_applies, bytes, last_solve, builds);
 }
 
 int osc_anchor_gram_info(osc_handle h, int64_t* fused_two_step_solves, int64_t* bytes, int32_t* last_solve, int64_t* builds, int64_t* redos) {
-  return guarded(h, [&](L& l) {
-    if (fused_two_step_solves) *fused_two_step_solves = l.fused_two_step_solves;
-    if (bytes) *bytes = l.derived.gram_nb > 0 ? (int64_t)l.gram.n * 8 : 0;
-    if (last_solve) *last_solve = l.anchor_gram_last ? 1 : 0;
-    if (builds) *builds = l.anchor_gram_builds;
-    if (redos) *redos = l.anchor_gram_redos;
-  });
+  return anchor_info(h, host::Level::gram, fused_two_step_solves, bytes, last_solve, builds, redos);
 }
 
 int osc_anchor_gram_read(osc_handle h, double* out, int64_t cap) {
-  return guarded(h, [&](L& l) {
-    if (l.derived.gram_nb <= 0) throw Unsupported("osc_anchor_gram_read: no Gram sums are held");
-    if (out == nullptr || cap < (int64_t)l.gram.n) throw Invalid("osc_anchor_gram_read: out holds fewer than 22 ld + 6 doubles");
-    HIP_CHECK(hipMemcpyAsync(out, l.gram.p, l.gram.n * sizeof(double), hipMemcpyDeviceToHost, l.stream));
-    sync(l);
-  });
+  return anchor_read(h, host::Level::gram, &L::gram, out, cap, "osc_anchor_gram_read: no Gram sums are held",
+                     "osc_anchor_gram_read: out holds fewer than 22 ld + 6 doubles");
 }
 
 int osc_anchor_gram3_info(osc_handle h, int64_t* fused_three_step_solves, int64_t* bytes, int32_t* last_solve, int64_t* builds) {
-  return guarded(h, [&](L& l) {
-    if (fused_three_step_solves) *fused_three_step_solves = l.fused_three_step_solves;
-    if (bytes) *bytes = l.derived.gram3_nb > 0 ? (int64_t)l.gram3.n * 8 + (int64_t)l.Wsum3.n * 4 : 0;
-    if (last_solve) *last_solve = l.anchor_gram3_last ? 1 : 0;
-    if (builds) *builds = l.anchor_gram3_builds;
-  });
+  return anchor_info(h, host::Level::gram3, fused_three_step_solves, bytes, last_solve, builds);
 }
 
 int osc_anchor_gram3_read(osc_handle h, double* out, int64_t cap) {
-  return guarded(h, [&](L& l) {
-    if (l.derived.gram3_nb <= 0) throw Unsupported("osc_anchor_gram3_read: no sums of the third step are held");
-    if (out == nullptr || cap < (int64_t)l.gram3.n) throw Invalid("osc_anchor_gram3_read: out holds fewer than 13 ld + 4 doubles");
-    HIP_CHECK(hipMemcpyAsync(out, l.gram3.p, l.gram3.n * sizeof(double), hipMemcpyDeviceToHost, l.stream));
-    sync(l);
-  });
+  return anchor_read(h, host::Level::gram3, &L::gram3, out, cap, "osc_anchor_gram3_read: no sums of the third step are held",
+                     "osc_anchor_gram3_read: out holds fewer than 13 ld + 4 doubles");
 }
 
 int osc_anchor_gram4_info(osc_handle h, int64_t* fused_four_step_solves, int64_t* bytes, int32_t* last_solve, int64_t* builds) {
-  return guarded(h, [&](L& l) {
-    if (fused_four_step_solves) *fused_four_step_solves = l.fused_four_step_solves;
-    if (bytes) *bytes = l.derived.gram4_nb > 0 ? (int64_t)l.gram4.n * 8 : 0;
-    if (last_solve) *last_solve = l.anchor_gram4_last ? 1 : 0;
-    if (builds) *builds = l.anchor_gram4_builds;
-  });
+  return anchor_info(h, host::Level::gram4, fused_four_step_solves, bytes, last_solve, builds);
 }
 
 int osc_gram4_fold_info(osc_handle h, int64_t* folded_four_step_solves, int32_t* enabled) {
@@ -688,22 +693,12 @@ int osc_gram4_fold_info(osc_handle h, int64_t* folded_four_step_solves, int32_t*
 }
 
 int osc_anchor_poly_info(osc_handle h, int64_t* poly_four_step_solves, int64_t* bytes, int32_t* last_solve, int64_t* builds, int64_t* redos) {
-  return guarded(h, [&](L& l) {
-    if (poly_four_step_solves) *poly_four_step_solves = l.poly_four_step_solves;
-    if (bytes) *bytes = l.derived.w4_nb > 0 ? (int64_t)l.W4s.n * 4 : 0;
-    if (last_solve) *last_solve = l.anchor_poly_last ? 1 : 0;
-    if (builds) *builds = l.anchor_poly_builds;
-    if (redos) *redos = l.anchor_poly_redos;
-  });
+  return anchor_info(h, host::Level::w4, poly_four_step_solves, bytes, last_solve, builds, redos);
 }
 
 int osc_anchor_gram4_read(osc_handle h, double* out, int64_t cap) {
-  return guarded(h, [&](L& l) {
-    if (l.derived.gram4_nb <= 0) throw Unsupported("osc_anchor_gram4_read: no sums of the fourth step are held");
-    if (out == nullptr || cap < (int64_t)l.gram4.n) throw Invalid("osc_anchor_gram4_read: out holds fewer than 16 ld + 5 doubles");
-    HIP_CHECK(hipMemcpyAsync(out, l.gram4.p, l.gram4.n * sizeof(double), hipMemcpyDeviceToHost, l.stream));
-    sync(l);
-  });
+  return anchor_read(h, host::Level::gram4, &L::gram4, out, cap, "osc_anchor_gram4_read: no sums of the fourth step are held",
+                     "osc_anchor_gram4_read: out holds fewer than 16 ld + 5 doubles");
 }
 
 int osc_get_blocked_copy(osc_handle h, int32_t nb, int32_t* slot_col, float* slot_w, int32_t* over_first, int32_t* over_count,
@@ -1826,7 +1821,7 @@ int osc_counters_get(osc_handle h, osc_counters* out) {
     out->y_to_u_copies = l.yu_copies;
     out->rows_to_slab_launches = l.slab_launches;
     out->anchor_slab_bytes = l.derived.ys ? (int64_t)l.Ys.n * 4 : 0;
-    out->anchor_wy_bytes = l.derived.wy_nb > 0 ? (int64_t)l.WYs.n * 4 : 0;
+    out->anchor_wy_bytes = anchor_level_bytes(l, host::Level::wy);
     out->cached_inits = l.cached_inits;
     out->bfs_on_device = l.bfs_on_device ? 1 : 0;
   });

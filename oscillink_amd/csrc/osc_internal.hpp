@@ -4,6 +4,7 @@
 //                     host <-> device transfers, profiling events, per-handle scratch
 //   osc_graph.hip   : lattice build orchestration (graph.py:8-93 on the device), chain prior, internal row order
 //   osc_solve.hip   : operator parameters, apply plans, the CG drivers (one GPU, column windows, row-sharded + halo lists)
+//   osc_anchor_build.hip : the builders of the anchor-start chain's levels (derived_state.hpp: Level)
 //   osc_api.hip     : environment switches and the extern "C" entry points of include/oscillink_hip.h
 #pragma once
 #include <algorithm>
@@ -94,57 +95,40 @@ struct osc_lattice {
   // The anchors' second row sums W.(W.Y) (row-major) and the rows' weight sums W.1: with them the cached INIT pass of an anchor
   // start under uniform gates also emits iteration 1's A p (k_init_cached_ap) and that iteration's gathering matvec is not
   // launched.  Built from WYs on the first solve that takes the route (a lattice's second anchor start), valid exactly as
-  // long as WYs (Derived::wwy_nb).  OSC_ANCHOR_AP: 0 never, 1 wherever the cached INIT runs, unset: by the lattice's rows
+  // long as WYs (Level::wwy).  OSC_ANCHOR_AP: 0 never, 1 wherever the cached INIT runs, unset: by the lattice's rows
   // (host_logic.hpp: anchor_ap_route).
   DevBuf<float> WWs, Wsum;
-  int anchor_ap = -1;
-  bool anchor_ap_denied = false;  // the arrays did not fit (asked again once WYs is formed anew)
   bool gates_uniform = true;      // B holds one value (osc_set_query scans the gates it is handed)
-  int64_t streamed_first_applies = 0, anchor_ap_builds = 0;
-  bool anchor_ap_last = false;    // the last general-path solve took the route
   // One level further (host_logic.hpp: anchor_ap2_route): the anchors' third row sums W.(W.(W.Y)) (row-major), W.(W.1) and the
   // scratch array T = A (A p1) the INIT pass fills; iteration 2's p update then forms A p2 and that iteration launches no
   // matvec either.  Built from WWs / Wsum on the first solve that takes the route -- the anchor start that built WWs, or the
-  // first one after OSC_ANCHOR_AP2 allows it -- and valid exactly as long as they are (Derived::w3_nb).  OSC_ANCHOR_AP2: 0
+  // first one after OSC_ANCHOR_AP2 allows it -- and valid exactly as long as they are (Level::w3).  OSC_ANCHOR_AP2: 0
   // never, 1 wherever the depth-1 route runs, unset: by the lattice's rows.
   DevBuf<float> W3s, Wsum2, Tap;
-  int anchor_ap2 = -1;
-  bool anchor_ap2_denied = false;
-  int64_t streamed_second_applies = 0, anchor_ap2_builds = 0;
-  bool anchor_ap2_last = false;
   // Further still (host_logic.hpp: anchor_gram_route): the float64 Gram sums of the seven vectors iterations 1 and 2 are
   // combinations of (anchor_gram.hpp; (22 ld + 6) doubles).  With them k_anchor_gram_scalars has both iterations' alpha, beta
   // and residuals before any N x D pass, and k_init_two_steps runs both iterations inside the INIT pass.  Built by the first
-  // solve that takes the route, valid exactly as long as W3s (Derived::gram_nb).  OSC_ANCHOR_GRAM: 0 never, 1 wherever the
+  // solve that takes the route, valid exactly as long as W3s (Level::gram).  OSC_ANCHOR_GRAM: 0 never, 1 wherever the
   // depth-2 route runs, unset: by the lattice's rows.
   DevBuf<double> gram;
   DevBuf<uint32_t> gram_go;  // the fused pass's gate word, iteration 3's and the folded last form's (GramScalarArgs::go)
-  int anchor_gram = -1;
   // The form of that pass (launch_init_two_steps), same bits either way.  OSC_TWO_STEPS: stream (unset) -- the update kernels'
   // launch geometry -- or blocked, the matvec's: the reference form.
   bool two_steps_stream = true;
-  int64_t fused_two_step_solves = 0, anchor_gram_builds = 0, anchor_gram_redos = 0;
-  bool anchor_gram_last = false;
   // One iteration further (host_logic.hpp: anchor_gram3_route): the sums of the two vectors A p3 adds to the seven -- psi s3, s3 =
   // W.(W.(W.1)), and W.(W3s), formed once into the solve's AP scratch array, summed against and dropped (anchor_gram.hpp; (13 ld +
   // 4) doubles and the N floats of s3 are held).  With them k_anchor_gram_scalars also has alpha3, beta3 and |r3|, and iteration 3
   // is one launch (k_apply_blocked's FUSED form).  Built by the first solve that takes the route, valid exactly as long as gram
-  // (Derived::gram3_nb).  OSC_ANCHOR_GRAM3: 0 never, 1 wherever the Gram route runs, unset: by the lattice's rows.
+  // (Level::gram3).  OSC_ANCHOR_GRAM3: 0 never, 1 wherever the Gram route runs, unset: by the lattice's rows.
   DevBuf<double> gram3;
   DevBuf<float> Wsum3;
-  int anchor_gram3 = -1;
-  int64_t fused_three_step_solves = 0, anchor_gram3_builds = 0;
-  bool anchor_gram3_last = false;
   // One level of scalars further (host_logic.hpp: anchor_gram4_route): the sums of the two vectors A p4 adds -- psi s4, s4 = W s3,
   // and W^5 Y; W^4 Y and W^5 Y are formed once into two of the solve's scratch arrays, summed against and dropped (anchor_gram.hpp;
   // (16 ld + 5) doubles are held).  With them k_anchor_gram_scalars also has alpha4 and |r4|, and a solve that ends in iteration 4
   // writes x4 in iteration 3's fused matvec (FUSED_LAST) and launches nothing for iteration 4.  Built by the first solve that plans
-  // the route, valid exactly as long as gram3 (Derived::gram4_nb).  OSC_ANCHOR_GRAM4: 0 never, 1 wherever the three-step route
+  // the route, valid exactly as long as gram3 (Level::gram4).  OSC_ANCHOR_GRAM4: 0 never, 1 wherever the three-step route
   // runs, unset: by the lattice's rows.
   DevBuf<double> gram4;
-  int anchor_gram4 = -1;
-  int64_t fused_four_step_solves = 0, anchor_gram4_builds = 0;
-  bool anchor_gram4_last = false;
   // The form of such a solve's one matvec.  Folded (unset): the INIT pass, which runs behind alpha3, beta3 and alpha4, stores e = x4
   // less the term in the gathered row sum in x's place and no r2, and the matvec's epilogue is one fmaf on the row of e
   // (k_apply_blocked, FMODE == 3).  OSC_GRAM4_FOLD=0: the INIT pass stores x3, r2, p3 and the epilogue forms r3, p4 and x4
@@ -153,16 +137,26 @@ struct osc_lattice {
   bool gram4_fold = true;
   int64_t folded_four_step_solves = 0;
   // The polynomial last form (host_logic.hpp: anchor_poly_route): W^4 Y, which the pass that forms gram4 computes anyway, is kept
-  // (row-major N x ld like W3s; the memory rule of ensure_anchor_ap, a denial remembered until WYs is formed anew; Derived::w4_nb),
+  // (row-major N x ld like W3s; the memory rule of WWs, a denial remembered until WYs is formed anew; Level::w4),
   // and a solve predicted and shown to end in iteration 4 is the scalars kernel and one elementwise pass over Ys, WYs, WWs, W3s and
   // W4s with nine coefficients a column (poly_coef).  After such a solve R, P and AP hold nothing defined.  OSC_ANCHOR_POLY: 0
   // never, 1 wherever the folded form would run, unset: by the lattice's rows.
   DevBuf<float> W4s, poly_coef;
-  int anchor_poly = -1;
   int anchor_poly_max_mb = -1;  // OSC_ANCHOR_POLY_MAX_MB: W4s is kept only if it is no larger than this many MiB (unset: the free memory alone decides)
-  bool anchor_poly_denied = false;
-  int64_t poly_four_step_solves = 0, anchor_poly_builds = 0, anchor_poly_redos = 0;
-  bool anchor_poly_last = false;
+  // What the handle keeps per level of that chain (derived_state.hpp: Level; wy's record stays unused: anchor_wy and cached_inits
+  // above).  mode: the level's OSC_ANCHOR_* switch (0 never, 1 wherever the level below runs, < 0 by the lattice's rows); denied:
+  // its arrays did not fit (asked again once WYs is formed anew); last: the last general-path solve took its route; solves: the
+  // solves that took it (wwy: streamed first applies, w3: streamed second applies, gram / gram3 / gram4: fused two- / three- /
+  // four-step solves, w4: polynomial four-step solves); builds, redos: times its arrays were formed / a solve on its route was
+  // gated off and run again.
+  struct AnchorLevel {
+    int mode = -1;
+    bool denied = false, last = false;
+    int64_t solves = 0, builds = 0, redos = 0;
+  };
+  AnchorLevel anchor[host::kLevels];
+  AnchorLevel& at(host::Level l) { return anchor[(unsigned)l]; }
+  const AnchorLevel& at(host::Level l) const { return anchor[(unsigned)l]; }
   int64_t yu_copies = 0;    // whole-array Y -> U copies made for this handle (osc_counters::y_to_u_copies)
   int64_t slab_launches = 0;  // k_rows_to_slab launches (osc_counters::rows_to_slab_launches)
   // Which of the arrays computed from other state (ell_col_t / ell_w_t, blk_*, Ys, WYs, Ustar; by epoch: halo, query) are
@@ -458,6 +452,7 @@ hipEvent_t prof_event(L& h);
 void prof_drain(L& h, bool nothrow = false);
 void use_device(L& h);
 void sync(L& h);
+int64_t device_free_bytes();  // of the current device
 void upload_rows(L& h, float* dst, const float* src);
 StagePair acquire_stage(int device);
 void release_stage(int device, const StagePair& sp);
@@ -517,6 +512,19 @@ bool u_alias_ok(const L& h);
 void reset_u_to_y(L& h);
 void materialise_u(L& h);
 void rows_to_slab(L& h, const float* src, float* dst, int32_t ld, int32_t c0, int32_t c1, int grid, const float* sub = nullptr);
+// osc_anchor_build.hip: a level of the anchor-start chain formed where it is not held (derived_state.hpp: Level; wwy to gram4 --
+// wy is a by-product of the gathering INIT pass, w4 of gram4's build).  False: not held and not to be had, the solve stays on the
+// route of the level below.  What a solve lends the builders: its blocked-matvec arguments, kernel shape and grid, its window and
+// pitch, and two N x ld arrays that are free until its INIT pass (gram3 borrows the first, gram4 both).
+struct AnchorBuild {
+  L& h;
+  const BlkArgs& ba;
+  int shape, grid;
+  int32_t ld, c0, c1;
+  float *scratch0, *scratch1;
+};
+bool ensure_anchor(const AnchorBuild& c, host::Level level);
+int64_t anchor_level_bytes(const L& h, host::Level level);  // what the level holds on the device, 0 while it is not held
 bool env_num(const char* name, int& out);
 void read_env_solver(L& h);
 void read_env_build(L& h);

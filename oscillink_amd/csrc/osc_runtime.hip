@@ -169,6 +169,11 @@ void prof_drain(L& h, bool nothrow) {
 
 void use_device(L& h) { HIP_CHECK(hipSetDevice(h.device)); }
 void sync(L& h) { HIP_CHECK(hipStreamSynchronize(h.stream)); }
+int64_t device_free_bytes() {
+  size_t free_b = 0, total_b = 0;
+  HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+  return (int64_t)free_b;
+}
 
 void upload_rows(L& h, float* dst, const float* src) {  // N x D host -> N x ld device
   if (h.ld == h.D) {  // no row padding: one contiguous copy (much faster than the strided form from pageable memory)

@@ -310,6 +310,8 @@ int blocked_quad_form(L& h, const host::ApplyPlan& plan, const OpParams& op, con
 
 namespace {
 
+using host::Level;
+
 // One general-path solve: the host side of cg_solve (solver.py:6-37) as run_cg stages it -- construction (control words, stop
 // test route, the arguments that hold for the whole solve), init() (r = b - A x0, z, p, r . z), plan_ring(), the loop methods
 // host::cg_host_loop drives (host_logic.hpp), finish().
@@ -469,6 +471,8 @@ struct CgSolve {
     ring.K = 1;  // (until plan_ring)
   }
 
+  // what the builders of the anchor-start chain borrow (osc_anchor_build.hip): AP and R hold nothing before the INIT pass
+  AnchorBuild builder() { return AnchorBuild{h, ba, plan.shape, grid, b.ld, b.c0, b.c1, b.AP, b.R}; }
   bool ringed() const { return ring.K > 1; }
   float* dir(int it) const { return ringed() ? slot[it % ring.K] : Pbuf; }  // where direction `it` lives
   float* alpha_of(int it) const { return ringed() ? aslot[it % ring.K] : h.alpha.p; }
@@ -476,10 +480,7 @@ struct CgSolve {
   // r = b - A x0 ; z ; p ; rz.  Returns the rows of r . z partials the pass left (+ the chain fix-up's behind the fused pass).
   int init() {
     int part_rows = grid;
-    h.anchor_gram_last = false;
-    h.anchor_gram3_last = false;
-    h.anchor_gram4_last = false;
-    h.anchor_poly_last = false;
+    for (const Level l : {Level::gram, Level::gram3, Level::gram4, Level::w4}) h.at(l).last = false;
     // (the rhs rows the fused pass can take besides x0 itself: one -- the state term must be x0 or absent, and if y is a
     // third array the solution array must be x0)
     const bool fuse_u = b.rhsU == b.x0 || op.rbU == 0.f;
@@ -524,8 +525,8 @@ struct CgSolve {
     if (!gram_route) launch_reduce_init(h.part0.p, part_rows, b.ld, b.c0, b.c1, h.rz.p, h.stream);
     ua.AP = APbuf;
     h.last_plan = plan;
-    h.anchor_ap_last = first_ap_done;
-    h.anchor_ap2_last = second_ap_ready;
+    h.at(Level::wwy).last = first_ap_done;
+    h.at(Level::w3).last = second_ap_ready;
     return part_rows;
   }
 
@@ -553,23 +554,23 @@ struct CgSolve {
     // one gathers them and leaves them behind (one more store per row), the later ones stream them (k_init_cached: the
     // same r, z and r . z sums to the bit).  (INIT passes are not counted in blk_applies.)
     const bool wy_route = h.anchor_wy && h.anchor_slab && ba.X == h.Ys.p && bi.Y == nullptr;
-    if (wy_route && h.derived.wy_nb == ba.nb) {
+    if (wy_route && host::held(h.derived, Level::wy, ba.nb)) {
       bi.WY = h.WYs.p;
       host::AnchorApInputs ai;
-      ai.mode = h.anchor_ap;
+      ai.mode = h.at(Level::wwy).mode;
       ai.N = h.N;
       ai.cached_init = true;
       ai.gates_uniform = h.gates_uniform && b.B == h.B.p;
       ai.chain_rows = cf.chunks > 0;
-      if (host::anchor_ap_route(ai) && ensure_anchor_ap()) {
+      if (host::anchor_ap_route(ai) && ensure_anchor(builder(), Level::wwy)) {
         // ... and iteration 1's A p with its p . Ap sums: p1 = z0 goes to the AP array (the swap below), A p1 to the P array
         BlkInitAp ap{h.WWs.p, h.Wsum.p, b.P, h.part1.p};
         host::AnchorAp2Inputs a2;
-        a2.mode = h.anchor_ap2;
+        a2.mode = h.at(Level::w3).mode;
         a2.N = h.N;
         a2.depth1 = true;
         a2.max_iters = max_iters;
-        if (host::anchor_ap2_route(a2) && ensure_anchor_ap2()) {  // ... and T = A (A p1) for iteration 2's p update
+        if (host::anchor_ap2_route(a2) && ensure_anchor(builder(), Level::w3)) {  // ... and T = A (A p1) for iteration 2's p update
           BlkInitAp2 ap2{h.W3s.p, h.Wsum2.p, h.Tap.p};
           if (two_steps(bi, ap, ap2)) return grid;  // ... or both iterations here and now
           launch_init_cached(ba, grid, h.stream, bi, plan.shape, &ap, &ap2);
@@ -578,18 +579,18 @@ struct CgSolve {
           launch_init_cached(ba, grid, h.stream, bi, plan.shape, &ap);
         }
         first_ap_done = true;
-        h.streamed_first_applies += 1;
+        h.at(Level::wwy).solves += 1;
       } else {
         launch_init_cached(ba, grid, h.stream, bi, plan.shape);
       }
       h.cached_inits += 1;
     } else if (wy_route) {
-      h.derived.wy_nb = h.derived.wwy_nb = h.derived.w3_nb = h.derived.gram_nb = h.derived.gram3_nb = h.derived.gram4_nb = h.derived.w4_nb = 0;  // (not current while this launch rewrites them)
-      h.anchor_ap_denied = h.anchor_ap2_denied = h.anchor_poly_denied = false;
+      host::begin_build(h.derived, Level::wy);  // (not current while this launch rewrites them)
+      for (L::AnchorLevel& a : h.anchor) a.denied = false;
       h.WYs.alloc((size_t)h.N * h.ld);
       bi.WY = h.WYs.p;
       launch_apply_blocked(ba, grid, h.stream, &bi, plan.shape, true);
-      h.derived.wy_nb = ba.nb;
+      host::built(h.derived, Level::wy, ba.nb);
     } else {
       launch_apply_blocked(ba, grid, h.stream, &bi, plan.shape);
     }
@@ -615,33 +616,33 @@ struct CgSolve {
   // -- hence with the P and AP arrays swapped as every fused INIT pass leaves them.  False: the route does not hold (the ring
   // stays planned), and the depth-2 pass runs.
   bool two_steps(BlkInit& bi, const BlkInitAp& ap, const BlkInitAp2& ap2) {
-    if (!allow_gram || h.anchor_gram == 0 || b.X == b.x0 || b.X == h.Ys.p) return false;
+    if (!allow_gram || h.at(Level::gram).mode == 0 || b.X == b.x0 || b.X == h.Ys.p) return false;
     std::swap(Pbuf, APbuf);
     plan_ring();
     host::AnchorGramInputs gi;
-    gi.mode = h.anchor_gram;
+    gi.mode = h.at(Level::gram).mode;
     gi.N = h.N;
     gi.depth2 = true;
     gi.comm = h.comm != nullptr;
     gi.ring_slots = ring.K;
     gi.max_iters = max_iters;
     gi.predicted = stop_guess;
-    if (!host::anchor_gram_route(gi) || !ensure_anchor_gram()) return false;
+    if (!host::anchor_gram_route(gi) || !ensure_anchor(builder(), Level::gram)) return false;
     host::AnchorGram3Inputs g3;
-    g3.mode = h.anchor_gram3;
+    g3.mode = h.at(Level::gram3).mode;
     g3.N = h.N;
     g3.gram_route = true;
     g3.comm = gi.comm;
     g3.ring_slots = ring.K;
     g3.max_iters = max_iters;
     g3.predicted = stop_guess;
-    const bool three = host::anchor_gram3_route(g3) && ensure_anchor_gram3();
+    const bool three = host::anchor_gram3_route(g3) && ensure_anchor(builder(), Level::gram3);
     host::AnchorGram4Inputs g4;
-    g4.mode = h.anchor_gram4;
+    g4.mode = h.at(Level::gram4).mode;
     g4.N = h.N;
     g4.gram3_route = three;
     g4.max_iters = max_iters;
-    const bool four = host::anchor_gram4_route(g4) && ensure_anchor_gram4();
+    const bool four = host::anchor_gram4_route(g4) && ensure_anchor(builder(), Level::gram4);
     GramScalarArgs ga{};
     ga.gram = h.gram.p;
     ga.psi = b.psi;
@@ -703,10 +704,10 @@ struct CgSolve {
     fused_md_B = bi.md_B;
     fused_md_const = bi.md_const;
     ring.applied = three ? 3 : 2;  // directions 1 and 2 (and 3) are in what the pass left in x
-    h.fused_two_step_solves += 1;
-    h.anchor_gram_last = true;
-    if (three) h.fused_three_step_solves += 1;
-    h.anchor_gram3_last = three;
+    h.at(Level::gram).solves += 1;
+    h.at(Level::gram).last = true;
+    if (three) h.at(Level::gram3).solves += 1;
+    h.at(Level::gram3).last = three;
     h.cached_inits += 1;
     return true;
   }
@@ -715,10 +716,10 @@ struct CgSolve {
   // elementwise pass that writes x4, gated by go[0] and go[2].  False: the route does not hold, nothing was enqueued.
   bool poly_pass(GramScalarArgs& ga) {
     host::AnchorPolyInputs pi;
-    pi.mode = h.anchor_poly;
+    pi.mode = h.at(Level::w4).mode;
     pi.N = h.N;
     pi.fold = true;
-    pi.w4_held = h.derived.w4_nb == ba.nb && h.derived.gram4_nb == ba.nb && h.Wsum3.n == (size_t)h.N;
+    pi.w4_held = host::held(h.derived, Level::w4, ba.nb) && h.Wsum3.n == (size_t)h.N;
     if (!host::anchor_poly_route(pi) || !polled) return false;
     SettlePolyArgs pa{};
     pa.Ys = h.Ys.p;
@@ -764,276 +765,12 @@ struct CgSolve {
     for (const float r : {r1, r2, r3, r4}) h.history.push_back(r);
     gram_route = gram3_route = gram4_planned = gram4_fold = gram4_taken = true;
     ring.applied = 4;  // (x is complete: no pass is left)
-    h.fused_two_step_solves += 1;
-    h.fused_three_step_solves += 1;
-    h.fused_four_step_solves += 1;
+    for (const Level l : {Level::gram, Level::gram3, Level::gram4, Level::w4}) {
+      h.at(l).solves += 1;
+      h.at(l).last = true;
+    }
     h.folded_four_step_solves += 1;
-    h.poly_four_step_solves += 1;
     h.cached_inits += 1;
-    h.anchor_gram_last = h.anchor_gram3_last = h.anchor_gram4_last = h.anchor_poly_last = true;
-    return true;
-  }
-
-  // The Gram sums of the seven vectors (L::gram; anchor_gram.hpp), formed where they are not held: one streaming pass over the
-  // arrays ensure_anchor_ap2 has just made current.  135 KB at 768 columns: no memory rule.
-  bool ensure_anchor_gram() {
-    if (h.derived.gram_nb == ba.nb && h.derived.w3_nb == ba.nb) return true;
-    h.derived.gram_nb = h.derived.gram3_nb = h.derived.gram4_nb = 0;
-    const size_t n = (size_t)gram::kGramPerColumn * h.ld + gram::kGramLattice;
-    DevBuf<double> part;
-    try {
-      if (h.gram.n != n) h.gram.alloc(n);
-      part.alloc(n * OSC_GRAM_CHUNKS);
-    } catch (const HipError&) {
-      (void)hipGetLastError();
-      h.gram.release();
-      return false;
-    }
-    GramArgs g{};
-    g.Ys = h.Ys.p;
-    g.WYs = h.WYs.p;
-    g.WW = h.WWs.p;
-    g.W3 = h.W3s.p;
-    g.wsum = h.Wsum.p;
-    g.wsum2 = h.Wsum2.p;
-    g.part = part.p;
-    g.out = h.gram.p;
-    g.N = (int32_t)h.N;
-    g.ld = h.ld;
-    g.c0 = h.c0;
-    g.c1 = h.c1;
-    launch_anchor_gram(g, h.stream);
-    sync(h);  // part goes out of scope
-    h.derived.gram_nb = ba.nb;
-    h.anchor_gram_builds += 1;
-    return true;
-  }
-
-  // The third step's sums (L::gram3; anchor_gram.hpp), formed where they are not held: s3 = W s2 over the ELL rows, W (W3s) as
-  // ensure_anchor_ap2 forms W3s -- over a slab-major image in T, by the loop-form matvec with cs = 0, cW = -1 -- into the solve's
-  // AP scratch array, where nothing lives before the INIT pass, then one streaming pass.  Only the sums and s3 are kept.
-  bool ensure_anchor_gram3() {
-    if (h.derived.gram3_nb == ba.nb && h.derived.gram_nb == ba.nb) return true;
-    h.derived.gram3_nb = h.derived.gram4_nb = 0;
-    if (b.ld != h.ld || h.part1.n < 3 * (size_t)b.ld) return false;
-    const size_t n = (size_t)gram::kGram3PerColumn * h.ld + gram::kGram3Lattice;
-    DevBuf<double> part;
-    try {
-      if (h.gram3.n != n) h.gram3.alloc(n);
-      if (h.Wsum3.n != (size_t)h.N) h.Wsum3.alloc((size_t)h.N);
-      part.alloc(n * OSC_GRAM_CHUNKS);
-    } catch (const HipError&) {
-      (void)hipGetLastError();
-      h.gram3.release();
-      h.Wsum3.release();
-      return false;
-    }
-    launch_row_weighted_sums(h.ell_col.p, h.ell_w.p, h.deg.p, h.width, (int32_t)h.N, h.Wsum2.p, h.Wsum3.p, h.stream);
-    rows_to_slab(h, h.W3s.p, h.Tap.p, h.ld, b.c0, b.c1, grid);
-    BlkArgs wa = ba;
-    wa.X = h.Tap.p;
-    wa.OUT = b.AP;
-    wa.cs_const = wa.cs_B = 0.f;
-    wa.cW = -1.f;
-    wa.gate = nullptr;
-    wa.gate_tol = 0.f;
-    launch_apply_blocked(wa, grid, h.stream, nullptr, plan.shape);
-    Gram3Args g{};
-    g.g.Ys = h.Ys.p;
-    g.g.WYs = h.WYs.p;
-    g.g.WW = h.WWs.p;
-    g.g.W3 = h.W3s.p;
-    g.g.wsum = h.Wsum.p;
-    g.g.wsum2 = h.Wsum2.p;
-    g.g.part = part.p;
-    g.g.out = h.gram3.p;
-    g.g.N = (int32_t)h.N;
-    g.g.ld = h.ld;
-    g.g.c0 = h.c0;
-    g.g.c1 = h.c1;
-    g.W4 = b.AP;
-    g.wsum3 = h.Wsum3.p;
-    launch_anchor_gram3(g, h.stream);
-    sync(h);  // part goes out of scope
-    h.derived.gram3_nb = ba.nb;
-    h.anchor_gram3_builds += 1;
-    return true;
-  }
-
-  // The fourth step's sums (L::gram4; anchor_gram.hpp), formed where they are not held: s4 = W s3 over the ELL rows, W^4 Y as
-  // ensure_anchor_gram3 forms it, into the solve's AP scratch array, W^5 Y = W (W^4 Y) the same way over a slab-major image in T
-  // into the solve's R array -- both are free until the INIT pass, and both must be live for <W^4 Y, W^5 Y> --, then one
-  // streaming pass.  Only the sums are kept.
-  bool ensure_anchor_gram4() {
-    if (h.derived.gram4_nb == ba.nb && h.derived.gram3_nb == ba.nb && h.derived.gram_nb == ba.nb) return true;
-    h.derived.gram4_nb = h.derived.w4_nb = 0;
-    if (b.ld != h.ld || h.part1.n < 4 * (size_t)b.ld || b.R == nullptr || b.R == b.AP) return false;
-    const size_t n = (size_t)gram::kGram4PerColumn * h.ld + gram::kGram4Lattice;
-    DevBuf<double> part;
-    DevBuf<float> wsum4;
-    try {
-      if (h.gram4.n != n) h.gram4.alloc(n);
-      wsum4.alloc((size_t)h.N);
-      part.alloc(n * OSC_GRAM_CHUNKS);
-    } catch (const HipError&) {
-      (void)hipGetLastError();
-      h.gram4.release();
-      return false;
-    }
-    // W^4 Y goes to an array of its own where the polynomial last form may read it later (the memory rule of ensure_anchor_ap, a
-    // denial remembered), and to the AP scratch array, to be dropped, otherwise
-    float* w4 = b.AP;
-    if (host::anchor_poly_keeps(h.anchor_poly, h.N) && !h.anchor_poly_denied) {
-      const size_t n4 = (size_t)h.N * h.ld;
-      if (h.W4s.n != n4) {
-        size_t free_b = 0, total_b = 0;
-        HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-        int64_t avail = (int64_t)free_b + (int64_t)h.W4s.n * 4;
-        // (OSC_ANCHOR_POLY_MAX_MB: the array may not be larger than that either; anchor_ap_fits takes a quarter of what it is given)
-        if (h.anchor_poly_max_mb >= 0) avail = std::min<int64_t>(avail, (int64_t)h.anchor_poly_max_mb * 4 * 1048576);
-        bool ok = host::anchor_ap_fits((int64_t)n4 * 4, avail);
-        if (ok) {
-          try {
-            h.W4s.alloc(n4);
-          } catch (const HipError&) {
-            (void)hipGetLastError();
-            ok = false;
-          }
-        }
-        if (!ok) {
-          h.W4s.release();
-          h.anchor_poly_denied = true;
-        }
-      }
-      if (h.W4s.n == n4) w4 = h.W4s.p;
-    }
-    launch_row_weighted_sums(h.ell_col.p, h.ell_w.p, h.deg.p, h.width, (int32_t)h.N, h.Wsum3.p, wsum4.p, h.stream);
-    BlkArgs wa = ba;
-    wa.X = h.Tap.p;
-    wa.cs_const = wa.cs_B = 0.f;
-    wa.cW = -1.f;
-    wa.gate = nullptr;
-    wa.gate_tol = 0.f;
-    rows_to_slab(h, h.W3s.p, h.Tap.p, h.ld, b.c0, b.c1, grid);
-    wa.OUT = w4;
-    launch_apply_blocked(wa, grid, h.stream, nullptr, plan.shape);
-    rows_to_slab(h, w4, h.Tap.p, h.ld, b.c0, b.c1, grid);
-    wa.OUT = b.R;
-    launch_apply_blocked(wa, grid, h.stream, nullptr, plan.shape);
-    Gram4Args g{};
-    g.g.Ys = h.Ys.p;
-    g.g.WYs = h.WYs.p;
-    g.g.WW = h.WWs.p;
-    g.g.W3 = h.W3s.p;
-    g.g.wsum = h.Wsum.p;
-    g.g.wsum2 = h.Wsum2.p;
-    g.g.part = part.p;
-    g.g.out = h.gram4.p;
-    g.g.N = (int32_t)h.N;
-    g.g.ld = h.ld;
-    g.g.c0 = h.c0;
-    g.g.c1 = h.c1;
-    g.W4 = w4;
-    g.W5 = b.R;
-    g.wsum3 = h.Wsum3.p;
-    g.wsum4 = wsum4.p;
-    launch_anchor_gram4(g, h.stream);
-    sync(h);  // part and s4 go out of scope
-    h.derived.gram4_nb = ba.nb;
-    h.anchor_gram4_builds += 1;
-    if (w4 == h.W4s.p) {
-      h.derived.w4_nb = ba.nb;
-      h.anchor_poly_builds += 1;
-    }
-    return true;
-  }
-
-  // The anchors' second row sums for the streamed first apply (L::WWs, L::Wsum), formed from WYs where they are not held:
-  // W (W Y) by the loop-form matvec itself with cs = 0, cW = -1 (its cs x - cW acc stores acc), row-major; W 1 over the ELL
-  // rows.  An INIT-time launch like the others: not counted in blk_applies.  False where the arrays do not fit (the rule of
-  // the direction ring: a quarter of the free device memory): the solve keeps its gathered first apply.
-  bool ensure_anchor_ap() {
-    if (h.derived.wwy_nb == ba.nb) return true;
-    if (h.anchor_ap_denied) return false;
-    h.derived.wwy_nb = 0;
-    const size_t n = (size_t)h.N * h.ld;
-    if (h.WWs.n != n || h.Wsum.n != (size_t)h.N) {
-      size_t free_b = 0, total_b = 0;
-      HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-      bool ok = host::anchor_ap_fits((int64_t)(n + (size_t)h.N) * 4, (int64_t)free_b + (int64_t)(h.WWs.n + h.Wsum.n) * 4);
-      if (ok) {
-        try {
-          h.WWs.alloc(n);
-          h.Wsum.alloc((size_t)h.N);
-        } catch (const HipError&) {
-          (void)hipGetLastError();
-          ok = false;
-        }
-      }
-      if (!ok) {
-        h.WWs.release();
-        h.Wsum.release();
-        h.anchor_ap_denied = true;
-        return false;
-      }
-    }
-    BlkArgs wa = ba;
-    wa.X = h.WYs.p;
-    wa.OUT = h.WWs.p;
-    wa.cs_const = wa.cs_B = 0.f;
-    wa.cW = -1.f;
-    wa.gate = nullptr;
-    wa.gate_tol = 0.f;
-    launch_apply_blocked(wa, grid, h.stream, nullptr, plan.shape);
-    launch_row_weight_sums(h.ell_w.p, h.deg.p, h.width, (int32_t)h.N, h.Wsum.p, h.stream);
-    h.derived.wwy_nb = ba.nb;
-    h.anchor_ap_builds += 1;
-    return true;
-  }
-
-  // The anchors' third row sums for the streamed second apply (L::W3s, L::Wsum2) and the T array, formed from WWs / Wsum where
-  // they are not held (ensure_anchor_ap has just made those current): W (W W Y) by the loop-form matvec as there, over a
-  // slab-major image of WWs that k_rows_to_slab writes into T (free until the INIT pass fills it); W (W 1) over the ELL rows.
-  // The same memory rule: W3s and T together from a quarter of what is free, or the solve keeps depth 1.
-  bool ensure_anchor_ap2() {
-    if (h.derived.w3_nb == ba.nb && h.derived.wwy_nb == ba.nb) return true;
-    if (h.anchor_ap2_denied) return false;
-    h.derived.w3_nb = h.derived.gram_nb = h.derived.gram3_nb = h.derived.gram4_nb = 0;
-    const size_t n = (size_t)h.N * h.ld;
-    if (h.W3s.n != n || h.Tap.n != n || h.Wsum2.n != (size_t)h.N) {
-      size_t free_b = 0, total_b = 0;
-      HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-      bool ok = host::anchor_ap_fits((int64_t)(2 * n + (size_t)h.N) * 4, (int64_t)free_b + (int64_t)(h.W3s.n + h.Tap.n + h.Wsum2.n) * 4);
-      if (ok) {
-        try {
-          h.W3s.alloc(n);
-          h.Tap.alloc(n);
-          h.Wsum2.alloc((size_t)h.N);
-        } catch (const HipError&) {
-          (void)hipGetLastError();
-          ok = false;
-        }
-      }
-      if (!ok) {
-        h.W3s.release();
-        h.Tap.release();
-        h.Wsum2.release();
-        h.anchor_ap2_denied = true;
-        return false;
-      }
-    }
-    rows_to_slab(h, h.WWs.p, h.Tap.p, h.ld, b.c0, b.c1, grid);
-    BlkArgs wa = ba;
-    wa.X = h.Tap.p;
-    wa.OUT = h.W3s.p;
-    wa.cs_const = wa.cs_B = 0.f;
-    wa.cW = -1.f;
-    wa.gate = nullptr;
-    wa.gate_tol = 0.f;
-    launch_apply_blocked(wa, grid, h.stream, nullptr, plan.shape);
-    launch_row_weighted_sums(h.ell_col.p, h.ell_w.p, h.deg.p, h.width, (int32_t)h.N, h.Wsum.p, h.Wsum2.p, h.stream);
-    h.derived.w3_nb = ba.nb;
-    h.anchor_ap2_builds += 1;
     return true;
   }
 
@@ -1053,11 +790,7 @@ struct CgSolve {
     int held = 0;
     while (held < host::kXRingMax - 1 && h.xring[held].n >= ring_n) ++held;
     ri.free_bytes = std::numeric_limits<int64_t>::max();
-    if (host::plan_x_ring(ri) - 1 > held) {
-      size_t free_b = 0, total_b = 0;
-      HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-      ri.free_bytes = (int64_t)free_b + ri.array_bytes * held;
-    }
+    if (host::plan_x_ring(ri) - 1 > held) ri.free_bytes = device_free_bytes() + ri.array_bytes * held;
     ring.K = host::plan_x_ring(ri);
     ring.last_form = h.x_last_form;
     ring.stop_guess = stop_guess;
@@ -1154,9 +887,9 @@ struct CgSolve {
         h.blk_applies += 1;
         gram4_taken = true;
         ring.applied = 4;  // (directions 3 and 4 are in x: no pass is left)
-        h.fused_four_step_solves += 1;
+        h.at(Level::gram4).solves += 1;
         if (gram4_fold) h.folded_four_step_solves += 1;
-        h.anchor_gram4_last = true;
+        h.at(Level::gram4).last = true;
         return;
       }
       // (iteration 4 runs on the summed route and publishes its own residual: the word is pending again)
@@ -1202,7 +935,7 @@ struct CgSolve {
     if (ap_src == host::ApSource::p_update) {
       // (the p update left A p2 in the AP array and the p . Ap partials in part0, which this iteration's x-r kernel overwrites)
       launch_reduce_alpha(h.part0.p, grid, b.ld, b.c0, b.c1, h.rz.p, alpha_of(it), g, h.stream);
-      h.streamed_second_applies += 1;
+      h.at(Level::w3).solves += 1;
     } else if (ap_src == host::ApSource::init_pass) {
       // (the INIT pass left A p1 in the AP array and the p . Ap partials in part1, which this iteration's x-r kernel overwrites)
       launch_reduce_alpha(h.part1.p, grid, b.ld, b.c0, b.c1, h.rz.p, alpha_of(it), g, h.stream);
@@ -1336,7 +1069,7 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
       if (s.poly_done()) return s.finish(4);
       // The solve does not end in iteration 4 after all (or a column's sums were unusable): the pass was gated off and nothing but
       // scratch scalars was written.  The same solve again on the folded form's route, which takes it from there as it always did.
-      h.anchor_poly_redos += 1;
+      h.at(Level::w4).redos += 1;
       allow_poly = false;
       continue;
     }
@@ -1344,10 +1077,10 @@ CgResult run_cg(L& h, const OpParams& op, const CgBuffers& b, bool with_path, in
     if (s.gram_route && iters < 3) {
       // The solve stopped before iteration 3 (or a column's sums were unusable): the fused pass was gated off, nothing but
       // scratch scalars was written.  The same solve again, on the depth-2 route; its count keeps the next one off the route.
-      h.anchor_gram_redos += 1;
-      h.fused_two_step_solves -= 1;
-      if (s.gram3_route) h.fused_three_step_solves -= 1;
-      if (s.gram4_taken) h.fused_four_step_solves -= 1;
+      h.at(Level::gram).redos += 1;
+      h.at(Level::gram).solves -= 1;
+      if (s.gram3_route) h.at(Level::gram3).solves -= 1;
+      if (s.gram4_taken) h.at(Level::gram4).solves -= 1;
       if (s.gram4_taken && s.gram4_fold) h.folded_four_step_solves -= 1;
       h.cached_inits -= 1;  // (the solve counts once, where it ends)
       allow_gram = false;

@@ -29,6 +29,17 @@ _DENSE_VIEW_LIMIT = 20000  # N above which dense N x N views are refused (1.6 GB
 _DENSE_EXPORT_LIMIT = 4096  # N up to which export_state / save_state also write the reference's dense `A`
 
 
+# build_info()'s anchor-start levels: (info function, key prefix, key of its solves counter, whether it reports redos)
+_ANCHOR_LEVELS = (
+    ("osc_anchor_ap_info", "anchor_ap", "streamed_first_applies", False),
+    ("osc_anchor_ap2_info", "anchor_ap2", "streamed_second_applies", False),
+    ("osc_anchor_gram_info", "anchor_gram", "fused_two_step_solves", True),
+    ("osc_anchor_gram3_info", "anchor_gram3", "fused_three_step_solves", False),
+    ("osc_anchor_gram4_info", "anchor_gram4", "fused_four_step_solves", False),
+    ("osc_anchor_poly_info", "anchor_poly", "poly_four_step_solves", True),
+)
+
+
 # The maps of `keep_state=True`: per row of the lattice afterwards, the row before whose state it
 # keeps, -1 for a fresh row, which starts at its anchor.  int32, the form osc_carry_state takes.
 def _state_map_append(N: int, M: int) -> np.ndarray:
@@ -270,20 +281,18 @@ class OscillinkLattice:
         ok, db, da, br, bn, bm = C.c_int32(0), C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int32(0), C.c_double(0.0)
         bd = C.c_int32(0)
         self._call("osc_balance_info", C.byref(ok), C.byref(db), C.byref(da), C.byref(br), C.byref(bn), C.byref(bm), C.byref(bd))
-        af, ab, al, an = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int64(0)
-        self._call("osc_anchor_ap_info", C.byref(af), C.byref(ab), C.byref(al), C.byref(an))
-        a2f, a2b, a2l, a2n = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int64(0)
-        self._call("osc_anchor_ap2_info", C.byref(a2f), C.byref(a2b), C.byref(a2l), C.byref(a2n))
-        gf, gb, gl, gn, gr = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int64(0), C.c_int64(0)
-        self._call("osc_anchor_gram_info", C.byref(gf), C.byref(gb), C.byref(gl), C.byref(gn), C.byref(gr))
-        g3f, g3b, g3l, g3n = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int64(0)
-        self._call("osc_anchor_gram3_info", C.byref(g3f), C.byref(g3b), C.byref(g3l), C.byref(g3n))
-        g4f, g4b, g4l, g4n = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int64(0)
-        self._call("osc_anchor_gram4_info", C.byref(g4f), C.byref(g4b), C.byref(g4l), C.byref(g4n))
-        g4d = C.c_int64(0)
-        self._call("osc_gram4_fold_info", C.byref(g4d), None)
-        pf4, pb4, pl4, pn4, pr4 = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int64(0), C.c_int64(0)
-        self._call("osc_anchor_poly_info", C.byref(pf4), C.byref(pb4), C.byref(pl4), C.byref(pn4), C.byref(pr4))
+        levels: dict[str, int] = {}
+        for fn, prefix, solves_key, has_redos in _ANCHOR_LEVELS:
+            solves, nbytes, last, builds, redos = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int64(0), C.c_int64(0)
+            self._call(fn, C.byref(solves), C.byref(nbytes), C.byref(last), C.byref(builds), *([C.byref(redos)] if has_redos else []))
+            levels.update({solves_key: int(solves.value), prefix + "_bytes": int(nbytes.value),
+                           prefix + "_last_solve": int(last.value), prefix + "_builds": int(builds.value)})
+            if has_redos:
+                levels[prefix + "_redos"] = int(redos.value)
+            if prefix == "anchor_gram4":
+                folded = C.c_int64(0)
+                self._call("osc_gram4_fold_info", C.byref(folded), None)
+                levels["folded_four_step_solves"] = int(folded.value)
         counters = nat.Counters()
         self._call("osc_counters_get", C.byref(counters))
         return {"order_kind": ("none", "bfs", "balanced")[int(ok.value)], "displaced_edges_before": int(db.value),
@@ -296,21 +305,7 @@ class OscillinkLattice:
                 "apply_blocked_shape": int(counters.blocked_shape),
                 "x_ring_slots": int(xk.value), "x_ring_flushes": int(xf.value), "x_ring_passes": int(xp.value),
                 "x_ring_bytes": int(xb.value),
-                "streamed_first_applies": int(af.value), "anchor_ap_bytes": int(ab.value),
-                "anchor_ap_last_solve": int(al.value), "anchor_ap_builds": int(an.value),
-                "streamed_second_applies": int(a2f.value), "anchor_ap2_bytes": int(a2b.value),
-                "anchor_ap2_last_solve": int(a2l.value), "anchor_ap2_builds": int(a2n.value),
-                "fused_two_step_solves": int(gf.value), "anchor_gram_bytes": int(gb.value),
-                "anchor_gram_last_solve": int(gl.value), "anchor_gram_builds": int(gn.value),
-                "anchor_gram_redos": int(gr.value),
-                "fused_three_step_solves": int(g3f.value), "anchor_gram3_bytes": int(g3b.value),
-                "anchor_gram3_last_solve": int(g3l.value), "anchor_gram3_builds": int(g3n.value),
-                "fused_four_step_solves": int(g4f.value), "anchor_gram4_bytes": int(g4b.value),
-                "anchor_gram4_last_solve": int(g4l.value), "anchor_gram4_builds": int(g4n.value),
-                "folded_four_step_solves": int(g4d.value),
-                "poly_four_step_solves": int(pf4.value), "anchor_poly_bytes": int(pb4.value),
-                "anchor_poly_last_solve": int(pl4.value), "anchor_poly_builds": int(pn4.value),
-                "anchor_poly_redos": int(pr4.value),
+                **levels,
                 # chain_receipt_many(lamP=...) keeps the basis of M + lamP I beside the query basis: N x ld + N x 4 floats
                 # (ld >= D rounded up to 4); 0 until the first such call
                 "shifted_basis_bytes": (4 * self.N * (((self.D + 3) // 4) * 4 + 4) if self._qbs_key is not None else 0)
@@ -320,30 +315,27 @@ class OscillinkLattice:
                 + (4 * self.N * max(1, self.graph_stats()[1]) if self._qbs_key is not None and self._qbs_receipt >= 2 else 0),
                 **{name: int(getattr(counters, name)) for name, _ in nat.Counters._fields_[1:]}}
 
+    def _anchor_sums(self, fn: str, size: int) -> np.ndarray:
+        out = np.zeros(size, dtype=np.float64)
+        self._call(fn, out.ctypes.data_as(C.POINTER(C.c_double)), out.size)
+        return out
+
     def anchor_gram(self) -> np.ndarray:
         """The float64 Gram sums the fused two-step INIT pass takes its CG scalars from, as held on the device: (22 ld + 6,)
         in the layout of include/oscillink_hip.h: osc_anchor_gram_read (test aid; raises while none are held)."""
         gb = C.c_int64(0)
         self._call("osc_anchor_gram_info", None, C.byref(gb), None, None, None)
-        out = np.zeros(max(int(gb.value) // 8, 1), dtype=np.float64)
-        self._call("osc_anchor_gram_read", out.ctypes.data_as(C.POINTER(C.c_double)), out.size)
-        return out
+        return self._anchor_sums("osc_anchor_gram_read", max(int(gb.value) // 8, 1))
 
     def anchor_gram3(self) -> np.ndarray:
         """The float64 sums of the two vectors the third step adds, as held on the device: (13 ld + 4,) in the layout of
         include/oscillink_hip.h: osc_anchor_gram3_read (test aid; raises while none are held)."""
-        ld = self.anchor_gram().size - 6
-        out = np.zeros(13 * (ld // 22) + 4, dtype=np.float64)
-        self._call("osc_anchor_gram3_read", out.ctypes.data_as(C.POINTER(C.c_double)), out.size)
-        return out
+        return self._anchor_sums("osc_anchor_gram3_read", 13 * ((self.anchor_gram().size - 6) // 22) + 4)
 
     def anchor_gram4(self) -> np.ndarray:
         """The float64 sums of the two vectors the fourth step's scalars add, as held on the device: (16 ld + 5,) in the layout
         of include/oscillink_hip.h: osc_anchor_gram4_read (test aid; raises while none are held)."""
-        ld = self.anchor_gram().size - 6
-        out = np.zeros(16 * (ld // 22) + 5, dtype=np.float64)
-        self._call("osc_anchor_gram4_read", out.ctypes.data_as(C.POINTER(C.c_double)), out.size)
-        return out
+        return self._anchor_sums("osc_anchor_gram4_read", 16 * ((self.anchor_gram().size - 6) // 22) + 5)
 
     def halo_info(self) -> dict[str, int]:
         """Row-sharded runs (OSC_SHARD=row under a communicator): the rows of the search direction this rank receives

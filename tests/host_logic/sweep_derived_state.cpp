@@ -38,7 +38,7 @@ static unsigned lost(const Derived& a, const Derived& b) {
   if (a.ell_t && !b.ell_t) m |= 1u << ELL_T;
   if (a.blk_nb != 0 && b.blk_nb == 0) m |= 1u << BLOCKED;
   if (a.ys && !b.ys) m |= 1u << SLAB;
-  if (a.wy_nb != 0 && b.wy_nb == 0) m |= 1u << WY;
+  if (held(a, Level::wy) && !held(b, Level::wy)) m |= 1u << WY;
   if (a.ustar && !b.ustar) m |= 1u << USTAR;
   return m;
 }
@@ -66,28 +66,29 @@ int main() {
                 d0.ell_t = ell_t != 0;
                 d0.blk_nb = blk;
                 d0.ys = ys != 0;
-                d0.wy_nb = wy;
+                if (wy != 0) built(d0, Level::wy, wy);
                 d0.ustar = ustar != 0;
                 d0.epoch = epoch;
                 Derived d1 = d0;
                 changed(d1, kInputs[i]);
                 // 1. dropped if and only if the dependency set holds the input; nothing is ever gained or altered
-                const bool now[NCACHE - 1] = {d1.ell_t, d1.blk_nb != 0, d1.ys, d1.wy_nb != 0, d1.ustar};
-                const bool was[NCACHE - 1] = {d0.ell_t, d0.blk_nb != 0, d0.ys, d0.wy_nb != 0, d0.ustar};
+                const bool now[NCACHE - 1] = {d1.ell_t, d1.blk_nb != 0, d1.ys, held(d1, Level::wy), d1.ustar};
+                const bool was[NCACHE - 1] = {d0.ell_t, d0.blk_nb != 0, d0.ys, held(d0, Level::wy), d0.ustar};
                 for (int c = 0; c < NCACHE - 1; ++c)
                   if (now[c] != (was[c] && !kExpect[c][i])) return fail("dropped iff dependent", c, i);
                 if (d1.blk_nb != 0 && d1.blk_nb != d0.blk_nb) return fail("block count altered", d0.blk_nb, d1.blk_nb);
-                if (d1.wy_nb != 0 && d1.wy_nb != d0.wy_nb) return fail("sum block count altered", d0.wy_nb, d1.wy_nb);
+                if (held(d1, Level::wy) && !held(d1, Level::wy, wy)) return fail("sum block count altered", wy, 0);
                 // 2. the row sums go with the image and with the graph copy
                 const bool ys_dropped = kExpect[SLAB][i], blk_dropped = kExpect[BLOCKED][i];
-                if ((ys_dropped || blk_dropped) && d1.wy_nb != 0) return fail("row sums outlive their sources", i, d1.wy_nb);
+                if ((ys_dropped || blk_dropped) && held(d1, Level::wy)) return fail("row sums outlive their sources", i, wy);
                 // 3. the epoch
                 if (d1.epoch != d0.epoch + (kExpect[EPOCH][i] ? 1 : 0)) return fail("epoch", i, (long long)d1.epoch);
                 // 4. the same input again: only the epoch moves
                 Derived d2 = d1;
                 changed(d2, kInputs[i]);
                 if (lost(d1, d2) != 0) return fail("second report dropped more", i, lost(d1, d2));
-                if (d2.blk_nb != d1.blk_nb || d2.wy_nb != d1.wy_nb) return fail("second report altered a count", i, d2.blk_nb);
+                // (the sums' count is the same number: held at all alike, and held at the count they were given alike)
+                if (d2.blk_nb != d1.blk_nb || held(d2, Level::wy) != held(d1, Level::wy) || held(d2, Level::wy, wy) != held(d1, Level::wy, wy)) return fail("second report altered a count", i, d2.blk_nb);
                 if (d2.epoch != d1.epoch + (kExpect[EPOCH][i] ? 1 : 0)) return fail("epoch, second report", i, (long long)d2.epoch);
                 ++cases;
               }
