@@ -649,6 +649,27 @@ int osc_corpus_filter(osc_corpus_handle h, const uint32_t* words, int32_t rows, 
  * what a call over that lattice alone returns.  When every n_q is K the call runs the kernels of a call that was not armed.
  * Q < 0 clears the arming. */
 int osc_corpus_ragged(osc_corpus_handle h, const int32_t* rows_or_null, int32_t Q);
+/* One query's operator and solver settings: the values the reference carries per request
+ * (cloud/app/models.py:8-23: Params.{lamG, lamC, lamQ, lamP, kneighbors}, SettleOptions.{max_iters, tol, dt, bundle_k}). */
+typedef struct osc_corpus_setting {
+  float lamG, lamC, lamQ, lamP, alpha, settle_dt, settle_tol;
+  int32_t kneighbors, k, settle_max_iters;
+} osc_corpus_setting;
+/* Arms the NEXT osc_corpus_refine* / _gates / _graph call on this handle with one settings record per query (copied here); that
+ * call spends the arming whether it succeeds or fails, like the filter and the ragged arming.  The reference builds every
+ * request's lattice from the request's own settings (_build_lattice, cloud/app/main.py:887-947), overrides them per API key
+ * and jitters them per request while exploring (cloud/app/learners.py:148-192), and sweeps them per query when tuning
+ * (scripts/benchmark_adaptive.py:186-232): armed, any set of requests over one corpus is one batch.  Q must equal the armed
+ * call's Q (otherwise that call returns OSC_E_INVALID), and the armed call ignores its own scalar arguments of the record's
+ * names (lamG, lamC, lamQ, lamP, alpha, dt, settle_max_iters, settle_tol, kneighbors, k).  Per lattice of n_q rows the list
+ * length is min(kneighbors[q], n_q - 1) (0 for one row) and the picks are min(k[q], n_q); the (Q, .) pick outputs are
+ * max_q min(k[q], K) wide, with -1 in local and 0 in score and align behind a query's own picks.  Every record gets the
+ * scalars' checks here -- lamG > 0; lamC, lamQ, lamP >= 0 and finite; kneighbors >= 1; settle_dt finite and > 0;
+ * settle_max_iters >= 1; settle_tol and alpha finite -- and min(kneighbors[q], K - 1) <= 128 in the armed call, each
+ * OSC_E_INVALID with the first offending query in the message.  Everything returned for query q is byte for byte what the same
+ * call returns for that query alone with its settings as scalars; the per-lattice reads run even when all records are equal.
+ * Q = 0 or per_query = NULL clears the arming. */
+int osc_corpus_settings(osc_corpus_handle h, const osc_corpus_setting* per_query, int32_t Q);
 /* the n_q of the last call on this handle that was armed by osc_corpus_ragged (proof_hallucination.py:203-221: the size is
  * whatever the filter leaves); Q must be that call's Q */
 int osc_corpus_ragged_rows(osc_corpus_handle h, int32_t* rows, int32_t Q);

@@ -24,6 +24,10 @@ c_i64p = C.POINTER(C.c_int64)
 c_f64p = C.POINTER(C.c_double)
 c_u32p = C.POINTER(C.c_uint32)
 Handle = C.c_void_p
+# osc_corpus_setting (include/oscillink_hip.h): one query's record of a call armed by osc_corpus_settings
+SETTING_DTYPE = np.dtype([("lamG", "<f4"), ("lamC", "<f4"), ("lamQ", "<f4"), ("lamP", "<f4"), ("alpha", "<f4"),
+                          ("settle_dt", "<f4"), ("settle_tol", "<f4"), ("kneighbors", "<i4"), ("k", "<i4"),
+                          ("settle_max_iters", "<i4")])
 
 _i32, _i64, _f32 = C.c_int32, C.c_int64, C.c_float
 # The argument runs of the Corpus refine entry points, in the header's order (corpus.py passes the same runs by name).
@@ -140,6 +144,7 @@ SIGNATURES = {
     "osc_corpus_filter": (C.c_int, [Handle, c_u32p, C.c_int32, C.c_int64]),
     "osc_corpus_ragged": (C.c_int, [Handle, c_i32p, C.c_int32]),
     "osc_corpus_ragged_rows": (C.c_int, [Handle, c_i32p, C.c_int32]),
+    "osc_corpus_settings": (C.c_int, [Handle, C.c_void_p, C.c_int32]),
     "osc_deltaH": (C.c_int, [Handle, c_f64p]),
     "osc_receipt_components": (C.c_int, [Handle, c_f32p, c_f32p, c_f32p]),
     "osc_null_points": (C.c_int, [Handle, C.c_float, c_i32p, c_i32p, c_f32p, c_f32p, c_i32p]),

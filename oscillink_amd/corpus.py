@@ -33,9 +33,11 @@ MAX_CHAIN = rc.MAX_CHAIN
 class _RefineOut:
     """The result arrays of one refine_many call, zeroed, and the two forms every path hands them back in."""
 
-    def __init__(self, Q: int, K: int, kk: int, gated: bool, rows: Optional[np.ndarray] = None):
+    def __init__(self, Q: int, K: int, kk: int, gated: bool, rows: Optional[np.ndarray] = None,
+                 picks: Optional[np.ndarray] = None):
         self.gated = gated
         self.rows = rows  # a ragged call's rows per lattice (int32 (Q,)), else None
+        self.picks = picks  # a call with a per-query k: min(k[q], n_q) picks per lattice (int32 (Q,)), else None
         self.cand = np.zeros((Q, K), dtype=np.int32)
         self.local = np.zeros((Q, kk), dtype=np.int32)
         self.score = np.zeros((Q, kk), dtype=np.float32)
@@ -56,21 +58,23 @@ class _RefineOut:
         """(ids, the `as_arrays` dict without receipts) once the native call has filled the arrays."""
         Q, kk = self.local.shape
         ids = np.take_along_axis(self.cand, self.local, axis=1) if kk else np.zeros((Q, 0), dtype=np.int32)
-        if self.rows is not None and kk:  # behind min(k, n_q) picks `local` is -1, and so is the id
+        if (self.rows is not None or self.picks is not None) and kk:  # behind a query's picks `local` is -1, and so is the id
             ids = np.where(self.local >= 0, np.take_along_axis(self.cand, np.maximum(self.local, 0), axis=1),
                            np.int32(-1)).astype(np.int32)
         out = {"ids": ids, "local": self.local, "score": self.score, "align": self.align, "candidates": self.cand,
                "ustar_iters": self.iters, "ustar_res": self.res}
         if self.rows is not None:
             out["rows"] = self.rows
+        if self.picks is not None:
+            out["picks"] = self.picks
         if self.gated:
             out.update(gates=self.g, gate_iters=self.g_iters, gate_res=self.g_res)
         return ids, out
 
     def bundles(self, ids):
         """Per query the list of {"id", "score", "align"} that bundle() returns."""
-        if self.rows is not None:  # min(k, n_q) entries per query
-            n = np.minimum(self.rows, ids.shape[1])
+        if self.rows is not None or self.picks is not None:  # min(k, n_q) entries per query
+            n = self.picks if self.picks is not None else np.minimum(self.rows, ids.shape[1])
             return [rc.bundle_dicts(ids[q, :n[q]], self.score[q, :n[q]], self.align[q, :n[q]]) for q in range(ids.shape[0])]
         return [rc.bundle_dicts(ids[q], self.score[q], self.align[q]) for q in range(ids.shape[0])]
 
@@ -133,14 +137,18 @@ class Corpus:
     def __exit__(self, *exc) -> None:
         self.close()
 
-    def _call_filtered(self, allow: Optional[np.ndarray], name: str, *args, ragged: Optional[np.ndarray] = None) -> None:
+    def _call_filtered(self, allow: Optional[np.ndarray], name: str, *args, ragged: Optional[np.ndarray] = None,
+                       settings: Optional[np.ndarray] = None) -> None:
         """_call(name, ...) with `allow` (_allow's words or None) armed as the call's filter: the native call consumes it.
         ragged = the rows per lattice (int32 (Q,)) of a ragged call, which is armed as such; afterwards the counts the native
-        call used are read back and must be these."""
+        call used are read back and must be these.  settings = _settings' records (one per query) of a call with per-query
+        settings, armed the same way; None arms nothing."""
         if allow is not None:
             self._call("osc_corpus_filter", nat.u32(allow), allow.shape[0], allow.shape[1])
         if ragged is not None:  # with a filter the native side derives the counts itself
             self._call("osc_corpus_ragged", None if allow is not None else nat.i32(ragged), int(ragged.shape[0]))
+        if settings is not None:
+            self._call("osc_corpus_settings", settings.ctypes.data_as(C.c_void_p), int(settings.shape[0]))
         self._call(name, *args)
         if ragged is not None:
             used = np.zeros_like(ragged)
@@ -267,6 +275,61 @@ class Corpus:
             raise ValueError(f"allow: query {q} has {int(counts[q])} eligible rows (live and allowed), fewer than K = {K}")
         rows = np.broadcast_to(np.minimum(counts, K), (Q,)).astype(np.int32) if ragged else None
         return mk.pack_mask(a), rows
+
+    # refine_many's arguments that may be given per query, with the scalar's own check of one value (None = passes)
+    _PER_QUERY = {
+        "lamG": lambda v: None if v > 0 else "lamG must be > 0 for SPD",
+        "lamC": lambda v: None if v >= 0 and np.isfinite(v) else "lamC must be >= 0",
+        "lamQ": lambda v: None if v >= 0 and np.isfinite(v) else "lamQ must be >= 0",
+        "lamP": lambda v: None if v >= 0 and np.isfinite(v) else "lamP must be >= 0",
+        "kneighbors": lambda v: None if v >= 1 else "kneighbors must be >= 1",
+        "k": lambda v: None,
+        "alpha": lambda v: None if np.isfinite(v) else "alpha must be finite",
+        "settle_dt": lambda v: None if np.isfinite(v) and v > 0 else "settle_dt must be finite and > 0",
+        "settle_max_iters": lambda v: None if v >= 1 else "settle_max_iters must be >= 1",
+        "settle_tol": lambda v: None if np.isfinite(v) else "settle_tol must be finite",
+    }
+    _PER_QUERY_INT = ("kneighbors", "k", "settle_max_iters")
+    _PER_QUERY_DEFAULTS = {"lamG": 1.0, "lamC": 0.5, "lamQ": 4.0, "lamP": 0.2, "kneighbors": 6, "k": 8, "alpha": 0.5,
+                           "settle_dt": 1.0, "settle_max_iters": 12, "settle_tol": 1e-3}
+
+    @classmethod
+    def _settings(cls, Q: int, K: int, **given):
+        """The arguments of `_PER_QUERY` as given to refine_many / diffusion_gates_many (a subset for the latter; the rest
+        take refine_many's defaults).  None when every one is a scalar (a 0-d array and a NumPy scalar are scalars): the
+        call is the scalar call.  Otherwise (records, named, raw): `records` = Q osc_corpus_setting records, every value checked
+        as the scalar is with the first offending query in the message, before any native call; `named` = the names that
+        were given per query; `raw` = per name the Q values as Python numbers, as given (what a state signature holds)."""
+        named = [n for n, v in given.items() if np.ndim(v) != 0]
+        if not named:
+            return None
+        rec = np.zeros(Q, dtype=nat.SETTING_DTYPE)
+        raw = {}
+        for name, check in cls._PER_QUERY.items():
+            v = np.asarray(given.get(name, cls._PER_QUERY_DEFAULTS[name]))
+            if v.ndim != 0 and v.shape != (Q,):
+                raise ValueError(f"{name} must be a scalar or a ({Q},) array, got shape {v.shape}")
+            if not (np.issubdtype(v.dtype, np.number) or v.dtype == np.bool_) or np.issubdtype(v.dtype, np.complexfloating):
+                raise ValueError(f"{name} must hold real numbers, got dtype {v.dtype}")
+            raw[name] = v.tolist() if v.ndim else [given.get(name, cls._PER_QUERY_DEFAULTS[name])] * Q
+            v = np.broadcast_to(v, (Q,))
+            if name in cls._PER_QUERY_INT:  # int(x)'s truncation, as the scalar path; NaN / inf cannot be converted
+                if not np.all(np.isfinite(v)):
+                    raise ValueError(f"query {int(np.flatnonzero(~np.isfinite(v))[0])}: {name} must be an integer")
+                col = np.clip(np.trunc(v).astype(np.int64), -2**31, 2**31 - 1).astype(np.int32)
+            else:
+                col = v.astype(np.float32)
+            for q in range(Q):
+                msg = check(col[q])
+                if msg is not None:
+                    raise ValueError(f"query {q}: {msg}")
+            rec[name] = col
+        for q in range(Q):
+            eff = min(int(rec["kneighbors"][q]), max(1, K - 1))
+            if eff > MAX_KNEIGHBORS:
+                raise ValueError(f"query {q}: min(kneighbors, K - 1) = {eff} exceeds the limit of {MAX_KNEIGHBORS} "
+                                 "(the dense route)")
+        return rec, named, raw
 
     @staticmethod
     def _gate_settings(beta, gamma, method, max_iters, prefix: str = ""):
@@ -582,9 +645,33 @@ class Corpus:
         array form keeps its shapes and gains `rows` int32 (Q,) = n_q; behind n_q (or min(k, n_q)) `ids`, `local` and
         `candidates` hold -1 and `score`, `align` and `gates` 0.  The list and dict forms have min(k, n_q) bundle entries, and
         a receipt's meta and `state_sig` are those of the n_q-row lattice.  Everything returned for a query is byte for byte
-        what a call over its lattice alone returns.  `ragged=False` is the call as it was."""
+        what a call over its lattice alone returns.  `ragged=False` is the call as it was.
+
+        Per-query settings: `lamG`, `lamC`, `lamQ`, `lamP`, `kneighbors`, `k`, `alpha`, `settle_dt`,
+        `settle_max_iters` and `settle_tol` each take a scalar or a length-Q sequence or 1-D array, as the reference's service
+        carries them per request (cloud/app/models.py:8-23) and its adaptive profiles override and jitter them per request
+        (cloud/app/learners.py:148-192).  Everything returned for query q is byte for byte what the same call returns for
+        that query alone with its settings as scalars, in every mode above.  Lattice q has lists of min(kneighbors[q],
+        n_q - 1) and min(k[q], n_q) picks; with a per-query `k` the (Q, .) pick arrays are min(max(k), K) wide with the ragged
+        fill behind a query's own picks, and the array form gains `picks` int32 (Q,).  Each value gets the scalar's check,
+        with the first offending query in the message, before any native call.  With all ten scalars (a 0-d array and a NumPy
+        scalar are scalars) the call is the one it was."""
         P = self._queries(psis)
         K = self._top_k(top_k)
+        st = self._settings(P.shape[0], K, lamG=lamG, lamC=lamC, lamQ=lamQ, lamP=lamP, kneighbors=kneighbors, k=k, alpha=alpha,
+                            settle_dt=settle_dt, settle_max_iters=settle_max_iters, settle_tol=settle_tol)
+        recs, k_per_query, raw = None, None, None
+        if st is not None and P.shape[0]:
+            # per-query settings: the records are armed for the native call, which ignores its scalars of those names; below
+            # they stand as query 0's values (checked), and k as the widest query's
+            recs, raw = st[0], st[2]
+            k_per_query = recs["k"].astype(np.int64) if "k" in st[1] else None
+            lamG, lamC, lamQ, lamP, alpha, settle_dt, settle_tol = (float(recs[n][0]) for n in (
+                "lamG", "lamC", "lamQ", "lamP", "alpha", "settle_dt", "settle_tol"))
+            kneighbors, settle_max_iters, k = int(recs["kneighbors"][0]), int(recs["settle_max_iters"][0]), int(recs["k"].max())
+        elif st is not None:  # no query: nothing to arm, and nothing to read a value from
+            lamG, lamC, lamQ, lamP, kneighbors, k, alpha, settle_dt, settle_max_iters, settle_tol = (
+                self._PER_QUERY_DEFAULTS[n] for n in self._PER_QUERY_DEFAULTS)
         knn = self._knn(kneighbors, K)
         detail, s_dt, s_max, s_tol = self._receipt_settings(receipts, settle_dt, settle_max_iters, settle_tol)
         if float(lamG) <= 0:
@@ -620,7 +707,10 @@ class Corpus:
                 raise ValueError("gates must be >= 0")
         chain = self._chains(chains, chain_weights, lamP, chain_z_th, Q, K, rows)
         gated = gates is not None
-        o = _RefineOut(Q, K, kk, gated, rows)
+        picks = None
+        if k_per_query is not None:
+            picks = np.minimum(np.maximum(k_per_query, 0), K if rows is None else rows).astype(np.int32)
+        o = _RefineOut(Q, K, kk, gated, rows, picks)
         cand_arg = None if cand_in is None else nat.i32(cand_in)
         gates_arg = None if gates_in is None else nat.f32(gates_in)
         beta, gamma, method, g_max = gate_set if gate_set is not None else (1.0, 0.1, 0, 1)
@@ -633,26 +723,29 @@ class Corpus:
                                          gate_args=gate_args, solve_args=solve_args, detail=detail,
                                          settle_args=(s_dt, s_max, s_tol), lam=[lamG, lamC, lamQ, 0.0],
                                          deterministic_k=deterministic_k, as_arrays=as_arrays, chain=chain, allow=words,
-                                         kneighbors=int(kneighbors))
+                                         kneighbors=int(kneighbors), settings=recs, raw=raw)
         if Q and not gated:
             self._call_filtered(words, "osc_corpus_refine", nat.f32(P), Q, int(top_k), cand_arg, *solve_args,
-                                *o.pointers(False), ragged=rows)
+                                *o.pointers(False), ragged=rows, settings=recs)
         elif Q:
             self._call_filtered(words, "osc_corpus_refine_gated", nat.f32(P), Q, int(top_k), cand_arg, gates_arg, *gate_args,
-                                *solve_args, *o.pointers(True), ragged=rows)
+                                *solve_args, *o.pointers(True), ragged=rows, settings=recs)
             if gates_in is None:
                 self._warn_non_finite(o.g, o.g_iters, o.g_res, "refine_many")
         ids, arrays = o.ids_and_arrays()
         return arrays if as_arrays else o.bundles(ids)
 
     def _refine_receipts(self, P, o, *, top_k, knn, cand_arg, mode, gates_arg, gate_args, solve_args, detail,
-                         settle_args, lam, deterministic_k, as_arrays, chain=None, allow=None, kneighbors=None):
+                         settle_args, lam, deterministic_k, as_arrays, chain=None, allow=None, kneighbors=None,
+                         settings=None, raw=None):
         """refine_many with receipts or chains, behind its validation: one osc_corpus_refine_receipts call (or, with
         chains, one osc_corpus_refine_chains call), then the arrays or the loop's dicts.  o = the result arrays; mode = the
         entry point's gate_mode; gate_args, solve_args and settle_args (dt, max_iters, tol) = its argument runs of those
         names; detail = None (chains only: no settle, no receipt), 0 or 1; lam = the state signature's lambdas, as given;
         chain = _chains' block or None; allow = _allow's words or None; kneighbors = as given (a ragged call's signatures
-        take min(kneighbors, max(1, n_q - 1)) per lattice)."""
+        take min(kneighbors, max(1, n_q - 1)) per lattice); settings = _settings' records of a call with per-query settings
+        (armed for the native call; a receipt's lambdas and `k` are then the query's own, from `raw`, _settings' values as
+        given) or None."""
         from .lattice import OscillinkLattice, __version__
 
         Q, K = o.cand.shape
@@ -682,11 +775,11 @@ class Corpus:
                        None if chain["weights"] is None else nat.f32(chain["weights"]), chain["lamP"], chain["z_th"],
                        *o.pointers(True), *receipt_out, *[nat.f32(c_edge[t]) for t in range(4)],
                        c_gain.ctypes.data_as(nat.c_f64p), nat.i32(c_verdict), nat.i32(c_weak_k), nat.f32(c_weak_z),
-                       ragged=o.rows)
+                       ragged=o.rows, settings=settings)
         elif Q:
             self._call_filtered(allow, "osc_corpus_refine_receipts", nat.f32(P), Q, int(top_k), cand_arg, mode, gates_arg,
                        *gate_args, *solve_args, *settle_args, detail, RECEIPT_Z_TH, cap_val, *o.pointers(True), *receipt_out,
-                       ragged=o.rows)
+                       ragged=o.rows, settings=settings)
         if Q:
             if mode == 1:
                 self._warn_non_finite(g, g_iters, g_res, "refine_many")
@@ -714,11 +807,15 @@ class Corpus:
             B = (g[q] if gated else ones)[:n]
             adj_sig = hashlib.sha256(np.ascontiguousarray(pairs[q, :int(pairs_n[q])]).tobytes()).hexdigest()
             ch = None if chain is None else chain["lists"][q]
+            lam_q, lamP_q, kn_q = lam, None if chain is None else chain["lamP"], kneighbors
+            if settings is not None:  # the query's own values, as float(...) of the scalar call would hold them
+                lam_q = [raw[name][q] for name in ("lamG", "lamC", "lamQ")] + [0.0]
+                lamP_q, kn_q = float(raw["lamP"][q]), int(settings["kneighbors"][q])
             sig = OscillinkLattice._signature_digest(
-                {"psi": np.round(P[q], 6).tolist(), "lam": lam if ch is None else [*lam[:3], chain["lamP"]],
+                {"psi": np.round(P[q], 6).tolist(), "lam": lam_q if ch is None else [*lam_q[:3], lamP_q],
                  "chain_present": ch is not None, "chain_len": 0 if ch is None else len(ch),
-                 "k": knn if o.rows is None else min(kneighbors, max(1, n - 1)), "detk": bool(deterministic_k),
-                 "adj": adj_sig}, B)
+                 "k": knn if o.rows is None and settings is None else min(kn_q, max(1, n - 1)),
+                 "detk": bool(deterministic_k), "adj": adj_sig}, B)
             nulls, tot = ra.nulls(q)
             meta = rc.meta(ustar_cached=False, ustar_solves=1, ustar_cache_hits=0,
                            ustar={"ustar_iters": int(iters[q]), "ustar_res": float(res[q]),
@@ -753,11 +850,18 @@ class Corpus:
         served, as in compute_diffusion_gates, by the CG run to 1e-7 max(1, |s|) with at most 2048 iterations.  Non-finite
         gates come back as computed, with a RuntimeWarning naming the first such query.  `allow` narrows the search as in
         `search`.  `ragged=True` means what it means for `refine_many`: query q's lattice has n_q <= K rows, `gates` holds 0 and
-        `candidates` -1 behind them, and the dict gains `rows` int32 (Q,).
+        `candidates` -1 behind them, and the dict gains `rows` int32 (Q,).  `kneighbors` may be a length-Q sequence, as for
+        `refine_many`: query q's lattice then has lists of min(kneighbors[q], n_q - 1), and its gates, `iters` and `res` are
+        those of the one-query call with that value.
 
         Returns a dict of `gates` (Q, K) float32 in candidate order, `candidates` (Q, K), `iters` and `res` (Q,)."""
         P = self._queries(psis)
         K = self._top_k(top_k)
+        st = self._settings(P.shape[0], K, kneighbors=kneighbors)
+        recs = None
+        if st is not None:  # per-query kneighbors: armed for the native call; query 0's stands in below
+            recs = st[0] if P.shape[0] else None
+            kneighbors = int(st[0]["kneighbors"][0]) if P.shape[0] else 6
         self._knn(kneighbors, K)
         b, g, m, mi = self._gate_settings(beta, gamma, method, max_iters)
         Q = P.shape[0]
@@ -777,7 +881,7 @@ class Corpus:
             self._call_filtered(words, "osc_corpus_gates", nat.f32(P), Q, int(top_k),
                                 None if cand_in is None else nat.i32(cand_in), int(kneighbors), float(row_cap_val), b, g, m,
                                 float(tol), mi, int(bool(clamp)), nat.i32(cand), nat.f32(gates), nat.i32(iters),
-                                nat.f32(res), ragged=rows)
+                                nat.f32(res), ragged=rows, settings=recs)
             self._warn_non_finite(gates, iters, res, "diffusion_gates_many")
         out = {"gates": gates, "candidates": cand, "iters": iters, "res": res}
         if rg:

@@ -38,17 +38,20 @@ __global__ __launch_bounds__(256) void k_cq_solve_chain(const CqChainPcgArgs ca)
   const int tid = threadIdx.x, lat = blockIdx.x;
   const int64_t r0 = (int64_t)lat * g.K;
   const int n = g.rows(lat);
-  const bool present = ca.chain.rec(lat)[0] > 0, active = present && ca.chain.lamP > 0.f;
-  const float cP = active ? ca.chain.lamP : 0.f;
+  const float lamG = g.lamG(lat), lamC = g.lamC(lat), lamQ = g.lamQ(lat);  // (uniform: the lattice's own, or the launch's)
+  const float lamP = g.lamP(lat, ca.chain.lamP);
+  const bool present = ca.chain.rec(lat)[0] > 0, active = present && lamP > 0.f;
+  const float cP = active ? lamP : 0.f;
   cq_path_slots(ca.chain, lat, n, active, s_slot);
   for (int r = tid; r < n; r += 256) {
     const float Bi = g.B ? g.B[r0 + r] : 1.0f;
-    const float cs = fmaf(g.lamQ, Bi, g.lamG + g.lamC);
+    const float cs = fmaf(lamQ, Bi, lamG + lamC);
     s_cs[r] = active ? cs + cP : cs;
-    s_inv[r] = 1.f / (fmaf(g.lamQ, Bi, present ? g.lamG + ca.chain.lamP : g.lamG) + 1e-12f);
+    s_inv[r] = 1.f / (fmaf(lamQ, Bi, present ? lamG + lamP : lamG) + 1e-12f);
   }
   __syncthreads();
-  cq_pcg<NC>(a, CqChainSolveOp{s_cs, s_inv, g.B, r0, g.lamC, g.lamG, g.lamQ, cq_path_rows(ca.chain, lat, s_slot, cP)}, red);
+  cq_pcg<NC>(a, CqChainSolveOp{s_cs, s_inv, g.B, r0, lamC, lamG, lamQ, cq_path_rows(ca.chain, lat, s_slot, cP)}, red,
+             a.max_iters, a.tol);
 }
 
 // chain_receipt(chain, z_th) of the lattice's own chain (lattice.py:466-528), one workgroup per lattice, a wave per chain
@@ -84,7 +87,8 @@ __global__ __launch_bounds__(256) void k_cq_chain_receipt(const CqChainEdgesArgs
   const int32_t* pptr = rec + a.chain.ptr_at;
   const int32_t* pcol = rec + a.chain.col_at;
   const float* pa = a.chain.a(lat);
-  const float lam_p = fmaxf(g.lamC, 1e-6f);
+  const float lamC = g.lamC(lat);  // (uniform: the lattice's own, or the launch's)
+  const float lam_p = fmaxf(lamC, 1e-6f);
   float* out = a.edge + (size_t)lat * 4 * a.chain.cap;
   for (int t = wave; t < E; t += 4) {
     const int li = nodes[t], lj = nodes[t + 1];
@@ -110,7 +114,7 @@ __global__ __launch_bounds__(256) void k_cq_chain_receipt(const CqChainEdgesArgs
       const float wij = g.adj[i * g.k + e];
       const float du = du_to(jj);
       if (!(wij > 0.f)) continue;
-      const float R = g.lamC * wij * du;
+      const float R = lamC * wij * du;
       s1 += (double)R;
       s2 += (double)R * (double)R;
       if (jj != j) continue;
@@ -123,7 +127,7 @@ __global__ __launch_bounds__(256) void k_cq_chain_receipt(const CqChainEdgesArgs
         dy = fmaf(y, y, dy);
       }
       dy = wave_sum_f(dy);
-      term = 0.5 * (double)g.lamC * (double)wij * ((double)dy - (double)du);
+      term = 0.5 * (double)lamC * (double)wij * ((double)dy - (double)du);
     }
     const double z_s = chain_row_z(s1, s2, rs, (double)K);
     // path row i (every chain node owns one)

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include "corpus_plan.hpp"
+#include "corpus_settings.hpp"
 
 namespace osc {
 
@@ -18,7 +19,10 @@ constexpr int kCqMaxCols = 1536;                  // columns (Corpus: D <= 1536)
 
 // the lattices of one chunk, back to back: lattice q is union rows [q K, q K + K) and query row q.  In a ragged chunk
 //  lattice q has nrows[q] <= K rows at the front of its K-row slot: row bases, strides and LDS
-// sizes stay functions of K, every row loop and every row count runs to rows(q)
+// sizes stay functions of K, every row loop and every row count runs to rows(q).  In a chunk armed by osc_corpus_settings
+//  lattice q has its own record st[q], and every reader of a setting takes it through the accessors
+// below: a workgroup serves one lattice, so each is one uniform load, and the value enters the expression the launch's
+// scalar enters otherwise
 struct CqLattice {
   const float* Y;       // union rows x ldn
   const float* psi;     // nq x ldn
@@ -30,9 +34,22 @@ struct CqLattice {
   const float* sd;      // sqrt of the capped degree
   const float* B;       // union rows: the gates, or nullptr (B = 1)
   int32_t K, k, ldn;
-  float lamG, lamC, lamQ;
+  float lamG_, lamC_, lamQ_;  // the launch's values: a call that is not armed
   const int32_t* nrows; // nq: rows of each lattice, or nullptr (every lattice has K)
+  const host::CorpusSetting* st = nullptr;  // nq: the lattices' own settings, or nullptr (the call is not armed)
   __device__ __forceinline__ int32_t rows(int lat) const { return nrows ? nrows[lat] : K; }
+  __device__ __forceinline__ float lamG(int lat) const { return st ? st[lat].lamG : lamG_; }
+  __device__ __forceinline__ float lamC(int lat) const { return st ? st[lat].lamC : lamC_; }
+  __device__ __forceinline__ float lamQ(int lat) const { return st ? st[lat].lamQ : lamQ_; }
+  // the settings that live in other argument blocks: `given` is that block's scalar
+  __device__ __forceinline__ float lamP(int lat, float given) const { return st ? st[lat].lamP : given; }
+  __device__ __forceinline__ float alpha(int lat, float given) const { return st ? st[lat].alpha : given; }
+  __device__ __forceinline__ int32_t picks(int lat, int32_t given) const { return st ? st[lat].k : given; }
+  __device__ __forceinline__ float settle_dt(int lat, float given) const { return st ? st[lat].settle_dt : given; }
+  __device__ __forceinline__ float settle_tol(int lat, float given) const { return st ? st[lat].settle_tol : given; }
+  __device__ __forceinline__ int32_t settle_max_iters(int lat, int32_t given) const {
+    return st ? st[lat].settle_max_iters : given;
+  }
 };
 
 // k_cq_solve and k_cq_settle
@@ -44,7 +61,7 @@ struct CqPcgArgs {
   float* AP;
   int32_t* iters;     // nq
   float* res;         // nq
-  int32_t max_iters;
+  int32_t max_iters;  // the three below: the launch's values; an armed settle takes the lattice's own (CqLattice)
   float tol;
   float dt;           // the settle's step (the solve ignores it)
 };
@@ -136,9 +153,10 @@ void cq_with_nc(int32_t ldn, F&& f) {
 //   kPath                       true: the policy has a CqPathRows `path`, and rows with path entries get
 //                               - path.cP sum_p w_p v_col(p) on top (a chain prior; its diagonal part is in cs(i)).  A
 //                               compile-time switch: the kPath = false instantiations hold no trace of it
-// red: four floats of LDS.  Writes a.X, a.R, a.P, a.AP and, from thread 0, a.iters / a.res of the lattice.
+// red: four floats of LDS.  max_iters, tol: the lattice's stop rule (a.max_iters / a.tol, or its own under per-query
+// settings).  Writes a.X, a.R, a.P, a.AP and, from thread 0, a.iters / a.res of the lattice.
 template <int NC, class Op>
-__device__ __forceinline__ void cq_pcg(const CqPcgArgs& a, const Op& op, float* red) {
+__device__ __forceinline__ void cq_pcg(const CqPcgArgs& a, const Op& op, float* red, const int max_iters, const float tol) {
   const CqLattice& g = a.lat;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lat = blockIdx.x;
@@ -205,7 +223,7 @@ __device__ __forceinline__ void cq_pcg(const CqPcgArgs& a, const Op& op, float* 
   }
   int it = 1;
   float resv = 0.f;
-  for (; it <= a.max_iters; ++it) {
+  for (; it <= max_iters; ++it) {
 #pragma unroll
     for (int m = 0; m < NC; ++m) t1[m] = 0.0;
     for (int64_t i = r0; i < r1; ++i) {
@@ -249,8 +267,8 @@ __device__ __forceinline__ void cq_pcg(const CqPcgArgs& a, const Op& op, float* 
 #pragma unroll
     for (int u = 1; u < 4; ++u) resv = nan_max(resv, red[u]);
     __syncthreads();
-    if (resv <= a.tol) break;  // solver.py:30-31, before the beta / p update
-    if (it == a.max_iters) break;
+    if (resv <= tol) break;  // solver.py:30-31, before the beta / p update
+    if (it == max_iters) break;
     for (int64_t i = r0; i < r1; ++i) {
       const float invMdi = op.inv_diag(i);
 #pragma unroll
@@ -265,7 +283,7 @@ __device__ __forceinline__ void cq_pcg(const CqPcgArgs& a, const Op& op, float* 
     for (int m = 0; m < NC; ++m) rz[m] = t2[m];
   }
   if (tid == 0) {
-    a.iters[lat] = it > a.max_iters ? a.max_iters : it;
+    a.iters[lat] = it > max_iters ? max_iters : it;
     a.res[lat] = resv;
   }
 }

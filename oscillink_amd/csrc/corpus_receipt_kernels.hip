@@ -45,15 +45,17 @@ __global__ __launch_bounds__(256) void k_cq_settle(const CqPcgArgs a) {
   const int tid = threadIdx.x, lat = blockIdx.x;
   const int64_t r0 = (int64_t)lat * g.K;
   const int n = g.rows(lat);
-  const float cW = a.dt * g.lamC, rbY = cq_rounded_mul(a.dt, g.lamG), cQ = a.dt * g.lamQ;
+  const float lamG = g.lamG(lat), lamC = g.lamC(lat), lamQ = g.lamQ(lat), dt = g.settle_dt(lat, a.dt);  // (uniform)
+  const float cW = dt * lamC, rbY = cq_rounded_mul(dt, lamG), cQ = dt * lamQ;
   for (int r = tid; r < n; r += 256) {
     const float Bi = g.B ? g.B[r0 + r] : 1.0f;
-    s_cs[r] = fmaf(cQ, Bi, 1.0f + a.dt * (g.lamG + g.lamC));
+    s_cs[r] = fmaf(cQ, Bi, 1.0f + dt * (lamG + lamC));
     s_inv[r] = 1.f / (fmaf(cQ, Bi, 1.0f + rbY) + 1e-12f);
     s_qb[r] = cQ * Bi;
   }
   __syncthreads();
-  cq_pcg<NC>(a, CqSettleOp{s_cs, s_inv, s_qb, r0, cW, rbY}, red);
+  cq_pcg<NC>(a, CqSettleOp{s_cs, s_inv, s_qb, r0, cW, rbY}, red, g.settle_max_iters(lat, a.max_iters),
+             g.settle_tol(lat, a.tol));
 }
 
 // the same step of a lattice with a chain prior (lattice.py:180-181, 187-191): the operator gains dt lamP L_path while
@@ -75,20 +77,23 @@ __global__ __launch_bounds__(256) void k_cq_settle_chain(const CqChainPcgArgs ca
   const int tid = threadIdx.x, lat = blockIdx.x;
   const int64_t r0 = (int64_t)lat * g.K;
   const int n = g.rows(lat);
-  const bool present = ca.chain.rec(lat)[0] > 0, active = present && ca.chain.lamP > 0.f;
-  const float cW = a.dt * g.lamC, rbY = cq_rounded_mul(a.dt, g.lamG), cQ = a.dt * g.lamQ;
-  const float cP = active ? cq_rounded_mul(a.dt, ca.chain.lamP) : 0.f;
-  const float dP = present ? cq_rounded_mul(a.dt, ca.chain.lamP) : 0.f;
+  const float lamG = g.lamG(lat), lamC = g.lamC(lat), lamQ = g.lamQ(lat), dt = g.settle_dt(lat, a.dt);  // (uniform)
+  const float lamP = g.lamP(lat, ca.chain.lamP);
+  const bool present = ca.chain.rec(lat)[0] > 0, active = present && lamP > 0.f;
+  const float cW = dt * lamC, rbY = cq_rounded_mul(dt, lamG), cQ = dt * lamQ;
+  const float cP = active ? cq_rounded_mul(dt, lamP) : 0.f;
+  const float dP = present ? cq_rounded_mul(dt, lamP) : 0.f;
   cq_path_slots(ca.chain, lat, n, active, s_slot);
   for (int r = tid; r < n; r += 256) {
     const float Bi = g.B ? g.B[r0 + r] : 1.0f;
-    const float cs = fmaf(cQ, Bi, 1.0f + a.dt * (g.lamG + g.lamC));
+    const float cs = fmaf(cQ, Bi, 1.0f + dt * (lamG + lamC));
     s_cs[r] = active ? cs + cP : cs;
     s_inv[r] = 1.f / (fmaf(cQ, Bi, present ? (1.0f + rbY) + dP : 1.0f + rbY) + 1e-12f);
     s_qb[r] = cQ * Bi;
   }
   __syncthreads();
-  cq_pcg<NC>(a, CqChainSettleOp{{s_cs, s_inv, s_qb, r0, cW, rbY}, cq_path_rows(ca.chain, lat, s_slot, cP)}, red);
+  cq_pcg<NC>(a, CqChainSettleOp{{s_cs, s_inv, s_qb, r0, cW, rbY}, cq_path_rows(ca.chain, lat, s_slot, cP)}, red,
+             g.settle_max_iters(lat, a.max_iters), g.settle_tol(lat, a.tol));
 }
 
 __device__ __forceinline__ const CqReceiptArgs& cq_receipt_args(const CqReceiptArgs& a) { return a; }
@@ -117,22 +122,24 @@ __global__ __launch_bounds__(256) void k_cq_receipt(const std::conditional_t<CHA
   const int lat = blockIdx.x, K = g.rows(lat);  // (the lattice's own row count; its slot is g.K rows)
   const int64_t r0 = (int64_t)lat * g.K;
   const float* psi = g.psi + (size_t)lat * g.ldn;
+  const float lamG = g.lamG(lat), lamC = g.lamC(lat), lamQ = g.lamQ(lat);  // (uniform: the lattice's own, or the launch's)
   for (int c = tid; c < g.ldn; c += 256) s_psi[c] = psi[c];
   [[maybe_unused]] CqPathRows path{};
   [[maybe_unused]] bool active = false;
   if constexpr (CHAIN) {
     __shared__ int32_t s_slot[kCqMaxRows];
     const CqChain& ch = args.chain;
-    active = ch.rec(lat)[0] > 0 && ch.lamP > 0.f;
+    const float lamP = g.lamP(lat, ch.lamP);
+    active = ch.rec(lat)[0] > 0 && lamP > 0.f;
     cq_path_slots(ch, lat, K, active, s_slot);
-    path = cq_path_rows(ch, lat, s_slot, active ? ch.lamP : 0.f);
+    path = cq_path_rows(ch, lat, s_slot, active ? lamP : 0.f);
   }
   __syncthreads();
   for (int r = wave; r < K; r += 4) {
     const int64_t i = r0 + r;
     const size_t io = (size_t)i * g.ldn;
     const float Bi = g.B ? g.B[i] : 1.0f;
-    float cs = fmaf(g.lamQ, Bi, g.lamG + g.lamC);
+    float cs = fmaf(lamQ, Bi, lamG + lamC);
     [[maybe_unused]] int ps = -1;
     if constexpr (CHAIN) {
       if (active) cs = cs + path.cP;
@@ -148,7 +155,7 @@ __global__ __launch_bounds__(256) void k_cq_receipt(const std::conditional_t<CHA
         const size_t jo = (size_t)crow[e] * g.ldn + c;
         acc = fmaf(g.w[i * g.k + e], a.Up[jo] - a.Us[jo], acc);
       }
-      float me = cs * ei - g.lamC * acc;
+      float me = cs * ei - lamC * acc;
       if constexpr (CHAIN) {
         if (ps >= 0) {
           float accp = 0.f;
@@ -192,8 +199,8 @@ __global__ __launch_bounds__(256) void k_cq_receipt(const std::conditional_t<CHA
       dy = wave_sum_f(dy);
       du = wave_sum_f(du);
       if (wij > 0.f) {
-        coh += 0.5f * g.lamC * wij * (dy - du);
-        const float R = g.lamC * wij * du;
+        coh += 0.5f * lamC * wij * (dy - du);
+        const float R = lamC * wij * du;
         s1 += (double)R;
         s2 += (double)R * (double)R;
         if (R > rmax || (R == rmax && R > 0.f && jmax >= 0 && j < jmax)) {
@@ -209,8 +216,8 @@ __global__ __launch_bounds__(256) void k_cq_receipt(const std::conditional_t<CHA
       const double z = ((double)rmax - mu) / (sqrt(var) + 1e-12);
       const bool is_null = (jmax >= 0) && (rmax > 0.f) && (z > (double)a.z_th);
       s_coh[r] = coh;
-      s_anc[r] = g.lamG * an;
-      s_qry[r] = g.lamQ * Bi * qu;
+      s_anc[r] = lamG * an;
+      s_qry[r] = lamQ * Bi * qu;
       s_nj[r] = is_null ? (int32_t)(jmax - r0) : -1;
       s_nz[r] = (float)z;
       s_nr[r] = rmax;

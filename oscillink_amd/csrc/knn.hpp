@@ -23,9 +23,9 @@ void launch_knn_dense_many(const float* Yn, int32_t ldn, int32_t N, int32_t nlat
 // the ragged batch (corpus refine): nlat slots of K <= 1024 rows, lattice z in the first nrows[z]
 // (device array, 1 .. K) rows of slot z.  Per lattice the similarity matrix and the min(k, nrows[z] - 1) best of each row are
 // what its own launch_knn_dense gives; the rest of every k-wide list, and every list of a row at or beyond nrows[z], is
-// (idx -1, val 0)
+// (idx -1, val 0).  kq (device array, or nullptr): lattice z's own list length kq[z] <= k in place of k
 void launch_knn_dense_ragged(const float* Yn, int32_t ldn, int32_t K, const int32_t* nrows, int32_t nlat, int32_t k, float* Sm,
-                             int32_t lds_, float* out_val, int32_t* out_idx, hipStream_t s);
+                             int32_t lds_, float* out_val, int32_t* out_idx, hipStream_t s, const int32_t* kq = nullptr);
 // any k (the k > 128 route): rows [row_begin, row_begin + rows) of the dense similarity matrix into the scratch Sm
 // (rows_cap x lds_ floats, rows <= rows_cap, lds_ >= N) and a radix select of each row's k best columns; row_begin must
 // be a multiple of 128.  out_val / out_idx are the full N x k lists.

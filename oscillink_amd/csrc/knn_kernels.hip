@@ -533,18 +533,22 @@ __global__ __launch_bounds__(256) void k_knn_select(const float* __restrict__ Sm
 // min(k, n - 1) best among the lattice's n columns (graph.py:30-32 for a lattice of n rows; the reference's filtered loop,
 // proof_hallucination.py:203-221, builds exactly that); the rest of its k-wide list, and the whole list of a row at or
 // beyond n, is (idx -1, val 0), which k_mutual_ell's `v > 0 && j >= 0` drops -- such a row ends with deg 0.
+// kq (per-query settings): lattice y's own list length kq[y] <= k inside the k-wide list, or nullptr
+// (every lattice has the launch's k).
 template <int M>
 __global__ __launch_bounds__(256) void k_knn_select_ragged(const float* __restrict__ Sm, int32_t lds_, int32_t K, int32_t k,
-                                                           const int32_t* __restrict__ nrows, float* out_val,
+                                                           const int32_t* __restrict__ nrows,
+                                                           const int32_t* __restrict__ kq, float* out_val,
                                                            int32_t* out_idx) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= K) return;
   const int n = nrows[blockIdx.y];
+  const int kl = kq ? max(0, min(kq[blockIdx.y], k)) : k;  // (uniform; never beyond the k entries the list has)
   const size_t at = ((size_t)blockIdx.y * K + row) * k;
   int done = 0;
   if (row < n)
-    done = knn_select_row<M>(Sm + (size_t)blockIdx.y * K * lds_, lds_, n, min(k, n - 1), row, (int)blockIdx.y * K,
+    done = knn_select_row<M>(Sm + (size_t)blockIdx.y * K * lds_, lds_, n, min(kl, n - 1), row, (int)blockIdx.y * K,
                              out_val + at, out_idx + at);
   for (int e = done + lane; e < k; e += 64) {
     out_val[at + e] = 0.f;
@@ -1454,14 +1458,14 @@ void launch_knn_dense_many(const float* Yn, int32_t ldn, int32_t N, int32_t nlat
 }
 
 void launch_knn_dense_ragged(const float* Yn, int32_t ldn, int32_t K, const int32_t* nrows, int32_t nlat, int32_t k, float* Sm,
-                             int32_t lds_, float* out_val, int32_t* out_idx, hipStream_t s) {
+                             int32_t lds_, float* out_val, int32_t* out_idx, hipStream_t s, const int32_t* kq) {
   if (K > 1024) throw std::runtime_error("launch_knn_dense_ragged: K > 1024");
   if (nlat < 1) return;
   const int nb = (K + BM - 1) / BM;
   hipLaunchKernelGGL(k_knn_dense_ragged, dim3(nb, nb, nlat), dim3(256), 0, s, Yn, ldn, K, nrows, Sm, lds_);
   const dim3 grid((unsigned)((K + 3) / 4), (unsigned)nlat), block(256);
   const int m = (K + 63) / 64;
-#define OSC_SEL(MM) hipLaunchKernelGGL(k_knn_select_ragged<MM>, grid, block, 0, s, Sm, lds_, K, k, nrows, out_val, out_idx)
+#define OSC_SEL(MM) hipLaunchKernelGGL(k_knn_select_ragged<MM>, grid, block, 0, s, Sm, lds_, K, k, nrows, kq, out_val, out_idx)
   if (m <= 4) OSC_SEL(4);
   else if (m <= 8) OSC_SEL(8);
   else OSC_SEL(16);  // (K <= 1024: the corpus refine's limit)

@@ -26,6 +26,10 @@
 //   slot: the ragged instances of the masked select, the gather and the dense kNN write -1 / 0 behind them, and every
 //   per-lattice kernel runs its row loops to CqLattice::rows(q).  When every lattice has K rows the chunk is the one above.
 //
+//   (a call armed by osc_corpus_settings) lattice q has its own lambdas, list length, picks, alpha and
+//   settle settings: the chunk's records are uploaded once, CqLattice points at them, and every per-lattice kernel reads its
+//   lattice's values through CqLattice's accessors; the lists and the outputs are as wide as the chunk's maxima.
+//
 // No workgroup waits on another: every kernel's workgroups are independent.  Every per-lattice kernel's arguments begin with
 // the same CqLattice block (corpus_pcg.hpp), which run_chunk fills once.
 #include "osc_internal.hpp"
@@ -33,11 +37,13 @@
 #include "corpus_plan.hpp"
 #include "corpus_ragged.hpp"
 #include "corpus_select.hpp"
+#include "corpus_settings.hpp"
 #include "corpus_store.hpp"
 #include "corpus_receipts.hpp"
 #include "corpus_chain.hpp"
 
 #include <cmath>
+#include <cstddef>
 #include <vector>
 
 // a filter armed by osc_corpus_filter for the next query call: rows = 0 none, 1 shared, else one row of words per query
@@ -53,6 +59,11 @@ struct CorpusRagged {
   bool armed = false;
   std::vector<int32_t> rows;
 };
+
+static_assert(sizeof(osc_corpus_setting) == sizeof(osc::host::CorpusSetting) &&
+                  offsetof(osc_corpus_setting, kneighbors) == offsetof(osc::host::CorpusSetting, kneighbors) &&
+                  offsetof(osc_corpus_setting, settle_max_iters) == offsetof(osc::host::CorpusSetting, settle_max_iters),
+              "the public record is corpus_settings.hpp's");
 
 struct osc_corpus {
   int device = 0;
@@ -71,6 +82,9 @@ struct osc_corpus {
   CorpusRagged ragged;
   std::vector<int32_t> last_rows;  // the row counts of the last call that was armed ragged (osc_corpus_ragged_rows)
   osc::DevBuf<int32_t> d_rows;     // one chunk's row counts of a ragged call
+  std::vector<osc::host::CorpusSetting> settings;  // armed by osc_corpus_settings for the next query call (section 13.8)
+  osc::DevBuf<osc::host::CorpusSetting> d_settings;  // one chunk's records of such a call
+  osc::DevBuf<int32_t> d_klist;    // and its lattices' list lengths
   osc::DevBuf<unsigned char> scratch;
   std::string err;
   ~osc_corpus() {
@@ -79,6 +93,8 @@ struct osc_corpus {
     d_live.release();
     d_filter.release();
     d_rows.release();
+    d_settings.release();
+    d_klist.release();
     scratch.release();
     if (stream) release_stream(device, stream);
   }
@@ -333,22 +349,24 @@ template <int NC, bool GATED>
 __global__ __launch_bounds__(256) void k_cq_solve(const CqPcgArgs a) {
   __shared__ float red[4];
   const CqLattice& g = a.lat;
+  const int lat = blockIdx.x;
+  const float lamG = g.lamG(lat), lamC = g.lamC(lat), lamQ = g.lamQ(lat);  // (uniform: the lattice's own, or the launch's)
   if constexpr (GATED) {
     __shared__ float s_cs[host::kCorpusMaxTopK], s_inv[host::kCorpusMaxTopK];
-    const int tid = threadIdx.x, lat = blockIdx.x;
+    const int tid = threadIdx.x;
     const int64_t r0 = (int64_t)lat * g.K;
     const int n = g.rows(lat);
     for (int r = tid; r < n; r += 256) {
       const float Bi = g.B[r0 + r];
-      s_cs[r] = fmaf(g.lamQ, Bi, g.lamG + g.lamC);
-      s_inv[r] = 1.f / (fmaf(g.lamQ, Bi, g.lamG) + 1e-12f);
+      s_cs[r] = fmaf(lamQ, Bi, lamG + lamC);
+      s_inv[r] = 1.f / (fmaf(lamQ, Bi, lamG) + 1e-12f);
     }
     __syncthreads();
-    cq_pcg<NC>(a, CqGatedSolveOp{s_cs, s_inv, g.B, r0, g.lamC, g.lamG, g.lamQ}, red);
+    cq_pcg<NC>(a, CqGatedSolveOp{s_cs, s_inv, g.B, r0, lamC, lamG, lamQ}, red, a.max_iters, a.tol);
   } else {
-    const float cs = fmaf(g.lamQ, 1.0f, g.lamG + g.lamC);
-    const float invMd = 1.f / (fmaf(g.lamQ, 1.0f, g.lamG) + 1e-12f);
-    cq_pcg<NC>(a, CqSolveOp{cs, invMd, g.lamC, g.lamG, g.lamQ}, red);
+    const float cs = fmaf(lamQ, 1.0f, lamG + lamC);
+    const float invMd = 1.f / (fmaf(lamQ, 1.0f, lamG) + 1e-12f);
+    cq_pcg<NC>(a, CqSolveOp{cs, invMd, lamC, lamG, lamQ}, red, a.max_iters, a.tol);
   }
 }
 
@@ -382,7 +400,10 @@ __global__ __launch_bounds__(256) void k_cq_bundle(const BundleArgs a) {
   const CqLattice& g = a.lat;
   const int lat = blockIdx.x, K = g.rows(lat);  // (the lattice's own row count; its slot is g.K rows)
   const int64_t r0 = (int64_t)lat * g.K;
-  const int steps = min(a.kk, K);               // a lattice of fewer than kk rows is picked empty: the rest is padding
+  const int steps = min(min(g.picks(lat, a.kk), a.kk), K);  // the lattice's own picks (at most the kk-wide output); a
+                                                            // lattice of fewer rows is picked empty: the rest is padding
+  const float lamC = g.lamC(lat);
+  const double alpha = g.st ? (double)g.alpha(lat, 0.f) : a.alpha;
   const float* psi = g.psi + (size_t)lat * g.ldn;
   const float qinv = 1.0f / g.qnorm[lat];
   for (int c = tid; c < g.ldn; c += 256) qn[c] = psi[c] * qinv;
@@ -416,7 +437,7 @@ __global__ __launch_bounds__(256) void k_cq_bundle(const BundleArgs a) {
       }
       dy = wave_sum_f(dy);
       du = wave_sum_f(du);
-      if (wij > 0.f) coh += 0.5f * g.lamC * wij * (dy - du);
+      if (wij > 0.f) coh += 0.5f * lamC * wij * (dy - du);
     }
     if (lane == 0) {
       s_coh[r] = coh;
@@ -444,14 +465,14 @@ __global__ __launch_bounds__(256) void k_cq_bundle(const BundleArgs a) {
   const double sigma = sqrt(block_sum(part) / (double)K) + 1e-12;
   for (int r = tid; r < K; r += 256) {
     const double z = sigma > 0.0 ? ((double)s_coh[r] - mu) / sigma : 0.0;
-    const float score = (float)(a.alpha * z + (1.0 - a.alpha) * (double)s_align[r]);
+    const float score = (float)(alpha * z + (1.0 - alpha) * (double)s_align[r]);
     s_coh[r] = score;  // (coh is not needed any more)
     s_base[r] = (1.0 - a.lambda) * (double)score;
     s_max[r] = 0.0;
   }
   __syncthreads();
   const float* S = a.Sm + (size_t)lat * g.K * a.lds;
-  for (int t = tid + steps; t < a.kk; t += 256) {  // (ragged chunks only: steps = kk otherwise)
+  for (int t = tid + steps; t < a.kk; t += 256) {  // (ragged or armed chunks only: steps = kk otherwise)
     a.o_local[(size_t)lat * a.kk + t] = -1;
     a.o_score[(size_t)lat * a.kk + t] = 0.f;
     a.o_align[(size_t)lat * a.kk + t] = 0.f;
@@ -700,12 +721,14 @@ int corpus_guarded(osc_corpus* h, F&& f) {
   }
 }
 
-// a call that searches or takes candidates: whatever it returns, the filter and the ragged arming made for it are spent
+// a call that searches or takes candidates: whatever it returns, the filter, the ragged arming and the per-query settings
+// made for it are spent
 template <class F>
 int corpus_query(osc_corpus* h, F&& f) {
   const int rc = corpus_guarded(h, f);
   if (h) h->filter = CorpusFilter{};
   if (h) h->ragged = CorpusRagged{};
+  if (h) h->settings.clear();
   return rc;
 }
 
@@ -747,6 +770,11 @@ struct RefineReq {
   std::vector<int32_t> rows_store;
   std::vector<float> gates_store;  // gates_in of a ragged call with zeros behind each lattice's rows
   bool ragged = false;
+  // a call armed by osc_corpus_settings (set_settings): the Q lattices' effective records (host::setting_effective) and their
+  // list lengths, empty when the call was not armed; knn and kk are then the records' maxima
+  std::vector<host::CorpusSetting> settings;
+  std::vector<int32_t> klist;
+  bool armed() const { return !settings.empty(); }
   int32_t rows_of(int32_t q) const { return rows_store.empty() ? K : rows_store[(size_t)q]; }
 };
 
@@ -780,6 +808,27 @@ host::CorpusLayout run_chunk(osc_corpus& c, const RefineReq& rq, int32_t q0, int
     if (c.d_rows.n < (size_t)cap_nq) c.d_rows.alloc((size_t)cap_nq);
     HIP_CHECK(hipMemcpyAsync(c.d_rows.p, rq.rows_store.data() + q0, (size_t)nq * 4, hipMemcpyHostToDevice, s));
     nrows = c.d_rows.p;
+  }
+  // an armed chunk: its lattices' records and list lengths, and -- for the ragged dense build, which gives every lattice its
+  // own list length -- the row counts even when every lattice has K rows
+  const host::CorpusSetting* st = nullptr;
+  const int32_t* klist = nullptr;
+  const int32_t* knn_rows = nrows;
+  if (rq.armed()) {
+    const host::CorpusSetting* hs = host::settings_slice(rq.settings.data(), rq.Q, q0, nq);
+    if (!hs) throw Invalid("settings: chunk outside the armed records");
+    if (c.d_settings.n < (size_t)cap_nq) c.d_settings.alloc((size_t)cap_nq);
+    if (c.d_klist.n < (size_t)cap_nq) c.d_klist.alloc((size_t)cap_nq);
+    HIP_CHECK(hipMemcpyAsync(c.d_settings.p, hs, (size_t)nq * sizeof(host::CorpusSetting), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(c.d_klist.p, rq.klist.data() + q0, (size_t)nq * 4, hipMemcpyHostToDevice, s));
+    st = c.d_settings.p;
+    klist = c.d_klist.p;
+    if (!rq.ragged) {
+      if (c.d_rows.n < (size_t)cap_nq) c.d_rows.alloc((size_t)cap_nq);
+      const std::vector<int32_t> full((size_t)nq, K);
+      HIP_CHECK(hipMemcpyAsync(c.d_rows.p, full.data(), (size_t)nq * 4, hipMemcpyHostToDevice, s));
+      knn_rows = c.d_rows.p;
+    }
   }
   // prep, and the candidates: given, or gemm + select
   HIP_CHECK(hipMemcpyAsync(psi, hp.data(), hp.size() * 4, hipMemcpyHostToDevice, s));
@@ -831,7 +880,8 @@ host::CorpusLayout run_chunk(osc_corpus& c, const RefineReq& rq, int32_t q0, int
   float* sd = at<float>(c, L.sd);
   float* Sm = at<float>(c, L.Sm);
   if (rq.knn > 0) {  // the dense route of the lattice build (osc_graph.hip, KnnRoute::dense), every lattice at once
-    if (rq.ragged) launch_knn_dense_ragged(Ync, ldn, K, nrows, nq, k, Sm, lds, at<float>(c, L.kval), at<int32_t>(c, L.kidx), s);
+    if (knn_rows)
+      launch_knn_dense_ragged(Ync, ldn, K, knn_rows, nq, k, Sm, lds, at<float>(c, L.kval), at<int32_t>(c, L.kidx), s, klist);
     else launch_knn_dense_many(Ync, ldn, K, nq, k, Sm, lds, at<float>(c, L.kval), at<int32_t>(c, L.kidx), s);
     launch_mutual_ell(at<float>(c, L.kval), at<int32_t>(c, L.kidx), (int32_t)rows, k, k, col, adj, deg, s);
   } else {  // one-row lattices have no edges (graph.py:30-32)
@@ -840,7 +890,7 @@ host::CorpusLayout run_chunk(osc_corpus& c, const RefineReq& rq, int32_t q0, int
   launch_cap_and_normalize(adj, w, col, deg, k, (int32_t)rows, rq.row_cap, 1, at<float>(c, L.scale), sd, s);
   float* gates = at<float>(c, L.gates);
   const CqLattice lat{Yc, psi, qnorm, col, w, adj, deg, sd, rq.gate ? gates : nullptr, K, k, ldn, rq.lamG, rq.lamC, rq.lamQ,
-                      nrows};
+                      nrows, st};
   // gates: solved per lattice, or given
   if (rq.gate == 1) {
     const GateArgs ga{lat, Ync, gates, at<int32_t>(c, L.g_iters), at<float>(c, L.g_res), rq.g_max_iters, rq.g_direct,
@@ -1131,12 +1181,58 @@ void check_request(const osc_corpus& c, const RefineReq& rq) {
   if (rq.kneighbors < 1) throw Invalid("kneighbors must be >= 1");
 }
 
+// the records of a call armed by osc_corpus_settings, behind set_ragged (which knows the lattices' rows): each lattice's
+// effective record and list length, and the request's list width and output width as their maxima.  Before any device work.
+void set_settings(const osc_corpus& c, RefineReq& rq) {
+  if (c.settings.empty()) return;
+  const int32_t Q = rq.Q, K = rq.K;
+  if ((int64_t)c.settings.size() != Q) throw Invalid("settings: the records were armed for another Q");
+  const int32_t lng = host::settings_first_long_list(c.settings.data(), Q, K);
+  if (lng >= 0) throw Invalid("settings: query " + std::to_string(lng) + ": min(kneighbors, K - 1) must be at most 128");
+  rq.settings.resize((size_t)Q);
+  rq.klist.resize((size_t)Q);
+  for (int32_t q = 0; q < Q; ++q) {
+    rq.settings[(size_t)q] = host::setting_effective(c.settings[(size_t)q], rq.rows_of(q), K);
+    rq.klist[(size_t)q] = rq.settings[(size_t)q].kneighbors;
+  }
+  rq.knn = host::settings_max_knn(rq.settings.data(), Q);
+  rq.kk = host::settings_max_kk(rq.settings.data(), Q);
+}
+
+// what an armed call's own scalar arguments of the records' names become: query 0's (checked) values, so that the scalar
+// checks pass and say nothing about arguments the call ignores; nothing reads them afterwards.  Any pointer may be null.
+struct SettingScalars {
+  int32_t* kneighbors = nullptr;
+  float *lamG = nullptr, *lamC = nullptr, *lamQ = nullptr;
+  int32_t* k = nullptr;
+  float* alpha = nullptr;
+  float* dt = nullptr;
+  int32_t* settle_max_iters = nullptr;
+  float *settle_tol = nullptr, *lamP = nullptr;
+};
+void take_armed(const osc_corpus& c, int32_t Q, const SettingScalars& a) {
+  if (c.settings.empty()) return;
+  if ((int64_t)c.settings.size() != Q) throw Invalid("settings: the records were armed for another Q");
+  const host::CorpusSetting& s0 = c.settings[0];
+  if (a.kneighbors) *a.kneighbors = s0.kneighbors;
+  if (a.lamG) *a.lamG = s0.lamG;
+  if (a.lamC) *a.lamC = s0.lamC;
+  if (a.lamQ) *a.lamQ = s0.lamQ;
+  if (a.k) *a.k = s0.k;
+  if (a.alpha) *a.alpha = s0.alpha;
+  if (a.dt) *a.dt = s0.settle_dt;
+  if (a.settle_max_iters) *a.settle_max_iters = s0.settle_max_iters;
+  if (a.settle_tol) *a.settle_tol = s0.settle_tol;
+  if (a.lamP) *a.lamP = s0.lamP;
+}
+
 // K and the list length of the request's lattices, its filter attached, and its candidates checked if given
 void set_shape(osc_corpus& c, RefineReq& rq) {
   rq.K = set_k_and_filter(c, rq, rq.top_k);
   rq.knn = rq.K > 1 ? host::corpus_knn(rq.kneighbors, rq.K) : 0;
-  if (rq.knn > host::kCorpusMaxKnn) throw Invalid("min(kneighbors, K - 1) must be at most 128");
+  if (c.settings.empty() && rq.knn > host::kCorpusMaxKnn) throw Invalid("min(kneighbors, K - 1) must be at most 128");
   set_ragged(c, rq);
+  set_settings(c, rq);
   if (rq.cand_in && !rq.rows_store.empty()) check_candidates_ragged(c, rq.cand_in, rq.Q, rq.K, rq.rows_store.data());
   else if (rq.cand_in) check_candidates(c, rq.cand_in, rq.Q, rq.K);
 }
@@ -1413,6 +1509,7 @@ int osc_corpus_refine(osc_corpus_handle h, const float* psis, int32_t Q, int32_t
                       int32_t k, float alpha, int32_t* cand_out, int32_t* local, float* score, float* align, int32_t* iters,
                       float* res) {
   return corpus_query(h, [&](osc_corpus& c) {
+    take_armed(c, Q, SettingScalars{&kneighbors, &lamG, &lamC, &lamQ, &k, &alpha});
     refine_body(c, refine_request(psis, Q, top_k, cand_in, kneighbors, row_cap, lamG, lamC, lamQ, tol, max_iters, k, alpha),
                 RefineOut{cand_out, local, score, align, iters, res}, "osc_corpus_refine: NULL buffer");
   });
@@ -1425,6 +1522,7 @@ int osc_corpus_refine_gated(osc_corpus_handle h, const float* psis, int32_t Q, i
                             int32_t* local, float* score, float* align, int32_t* iters, float* res, int32_t* gate_iters,
                             float* gate_res) {
   return corpus_query(h, [&](osc_corpus& c) {
+    take_armed(c, Q, SettingScalars{&kneighbors, &lamG, &lamC, &lamQ, &k, &alpha});
     RefineReq rq = refine_request(psis, Q, top_k, cand_in, kneighbors, row_cap, lamG, lamC, lamQ, tol, max_iters, k, alpha);
     set_gate_request(rq, gates_in ? 2 : 1, gates_in, beta, gamma, method, gate_tol, gate_max_iters);
     refine_body(c, rq, RefineOut{cand_out, local, score, align, iters, res, gates_out, gate_iters, gate_res},
@@ -1444,6 +1542,7 @@ int osc_corpus_refine_receipts(osc_corpus_handle h, const float* psis, int32_t Q
                                float* null_r, int64_t null_capacity, int64_t* nnz_out, int64_t* edge_prefix,
                                int32_t* edge_prefix_n, int32_t edge_prefix_cap) {
   return corpus_query(h, [&](osc_corpus& c) {
+    take_armed(c, Q, SettingScalars{&kneighbors, &lamG, &lamC, &lamQ, &k, &alpha, &dt, &settle_max_iters, &settle_tol});
     check_gate_mode(gate_mode, gates_in, Q);
     if (detail != 0 && detail != 1) throw Invalid("detail must be 0 (light) or 1 (full)");
     RefineReq rq = refine_request(psis, Q, top_k, cand_in, kneighbors, row_cap, lamG, lamC, lamQ, tol, max_iters, k, alpha);
@@ -1472,6 +1571,7 @@ int osc_corpus_refine_chains(osc_corpus_handle h, const float* psis, int32_t Q, 
                              float* chain_r_struct, float* chain_r_path, double* chain_gain, int32_t* chain_verdict,
                              int32_t* chain_weakest_k, float* chain_weakest_z) {
   return corpus_query(h, [&](osc_corpus& c) {
+    take_armed(c, Q, SettingScalars{&kneighbors, &lamG, &lamC, &lamQ, &k, &alpha, &dt, &settle_max_iters, &settle_tol, &lamP});
     check_gate_mode(gate_mode, gates_in, Q);
     if (detail < -1 || detail > 1) throw Invalid("detail must be -1 (no receipts), 0 (light) or 1 (full)");
     RefineReq rq = refine_request(psis, Q, top_k, cand_in, kneighbors, row_cap, lamG, lamC, lamQ, tol, max_iters, k, alpha);
@@ -1497,6 +1597,7 @@ int osc_corpus_gates(osc_corpus_handle h, const float* psis, int32_t Q, int32_t 
                      int32_t kneighbors, float row_cap, float beta, float gamma, int32_t method, float tol,
                      int32_t max_iters, int32_t clamp, int32_t* cand_out, float* gates_out, int32_t* iters, float* res) {
   return corpus_query(h, [&](osc_corpus& c) {
+    take_armed(c, Q, SettingScalars{&kneighbors});
     RefineReq rq = lattice_request(psis, Q, top_k, kneighbors, cand_in);
     check_request(c, rq);
     set_gate_request(rq, 1, nullptr, beta, gamma, method, tol, max_iters);
@@ -1519,6 +1620,7 @@ int osc_corpus_graph(osc_corpus_handle h, const float* psi, const int32_t* cand_
                      float row_cap, int32_t* cand_out, int64_t* rowptr, int32_t* col, float* a, float* w, float* sqrt_deg,
                      int64_t capacity, int64_t* nnz) {
   return corpus_query(h, [&](osc_corpus& c) {
+    take_armed(c, 1, SettingScalars{&kneighbors});
     RefineReq rq = lattice_request(psi, 1, top_k, kneighbors, cand_in);
     check_request(c, rq);
     set_shape(c, rq);
@@ -1679,6 +1781,7 @@ int osc_corpus_compact(osc_corpus_handle h, int32_t* new_id_of_old_or_null, int6
     c.N = c.n_live = n;
     c.filter = CorpusFilter{};  // (armed for ids that no longer exist)
     c.ragged = CorpusRagged{};
+    c.settings.clear();
   });
 }
 
@@ -1701,6 +1804,19 @@ int osc_corpus_ragged(osc_corpus_handle h, const int32_t* rows_or_null, int32_t 
     if (Q < 0) return;
     c.ragged.armed = true;
     if (rows_or_null) c.ragged.rows.assign(rows_or_null, rows_or_null + Q);
+  });
+}
+
+int osc_corpus_settings(osc_corpus_handle h, const osc_corpus_setting* per_query, int32_t Q) {
+  return corpus_guarded(h, [&](osc_corpus& c) {
+    c.settings.clear();
+    if (Q == 0 || !per_query) return;
+    if (Q < 0) throw Invalid("osc_corpus_settings: need Q >= 0");
+    const host::CorpusSetting* s = reinterpret_cast<const host::CorpusSetting*>(per_query);
+    const char* what = nullptr;
+    const int32_t bad = host::settings_first_bad(s, Q, &what);
+    if (bad >= 0) throw Invalid("osc_corpus_settings: query " + std::to_string(bad) + ": " + what);
+    c.settings.assign(s, s + Q);
   });
 }
 
