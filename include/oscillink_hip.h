@@ -412,6 +412,29 @@ int osc_bundle_many(osc_handle h, const float* psis, int32_t Q, int32_t k, float
  * OSC_E_UNSUPPORTED with a communicator. */
 int osc_gates_many(osc_handle h, const float* psis, int32_t Q, float beta, float gamma, int32_t method, float tol,
                    int32_t max_iters, int32_t clamp, float* gates_out, int32_t* iters_out, float* res_out);
+/* Not in the reference as one call: set_query(psi_q, gates = g_q); bundle(k, alpha) (lattice.py:114-120, 245-263, 530-568;
+ * the second half of examples/rag_replacement.py:159-177) for Q queries psis (Q x D) on the lattice's graph and lambdas
+ * (DESIGN.md section 11.2).  With gates M_q = lamG I + lamC L_sym + lamQ diag(g_q) differs per query, so every query gets
+ * its own N x D solve of solve_Ustar -- RHS = lamG Y + lamQ g_q psi_q^T, x0 = Y, the Jacobi diagonal lamG + lamQ g_q + 1e-12,
+ * alpha / beta per column (solver.py:6-37) -- and the solves of a chunk run as ONE panel PCG over the shared graph.  A query
+ * stops at the first iteration where its largest column residual is <= tol, all its columns together, after max_iters at
+ * most.  gates is Q x N in API row order; with diffusion != 0 it is an OUTPUT first: osc_gates_many(psis, gate_beta,
+ * gate_gamma, gate_method, gate_tol, gate_max_iters, clamp = 1) writes it, then the solves read it.  ids / score / align are
+ * osc_bundle_many's (Q x min(k, N) each; k <= 0: not written); iters_out / res_out (Q each, may be NULL) receive each query's
+ * iteration count and its largest column residual.  A query's outputs are the same to the bit whatever else the batch holds;
+ * a non-finite query or gate row gives that query non-finite answers and changes no other's.  Queries run OSC_GATED_CHUNK
+ * (read at every call; default and at most 256) at a time, fewer where one chunk's scratch would pass 1 GiB, never fewer than
+ * one.  The lattice's own gates, psi, U, U* and query basis are neither read nor changed.  OSC_E_INVALID for max_iters < 1
+ * (and osc_gates_many's with diffusion), OSC_E_STATE without a graph, OSC_E_UNSUPPORTED with a communicator or a chain of the
+ * lattice's own. */
+int osc_bundle_gated_many(osc_handle h, const float* psis, int32_t Q, float* gates, int32_t diffusion, float gate_beta,
+                          float gate_gamma, int32_t gate_method, float gate_tol, int32_t gate_max_iters, float tol,
+                          int32_t max_iters, int32_t k, float alpha, float lambda_div, int32_t* ids, float* score, float* align,
+                          int32_t* iters_out, float* res_out);
+/* The solves of osc_bundle_gated_many alone, read out: U_out is Q x N x D (API row order), U*_q of solve_Ustar under gates
+ * g_q (diagnostic; the batched MMR's osc_mmr_many plays the same role). */
+int osc_ustar_gated_many(osc_handle h, const float* psis, int32_t Q, const float* gates, float tol, int32_t max_iters,
+                         float* U_out, int32_t* iters_out, float* res_out);
 /* Not in the reference: receipt() (lattice.py:298-455, receipts.py:10-83) for Q queries psis (Q x D) with the current U,
  * gates, chain and lambdas held fixed, U*(psi) from the resident basis.  Per query: dH (deltaH_trace
  * of U against U*(psi_q)); with detail != 0 also coh_sum / anchor_sum / query_sum and the null points at z_th (else 0 and

@@ -1294,6 +1294,29 @@ int osc_gates_many(osc_handle h, const float* psis, int32_t Q, float beta, float
   });
 }
 
+int osc_bundle_gated_many(osc_handle h, const float* psis, int32_t Q, float* gates, int32_t diffusion, float gate_beta,
+                          float gate_gamma, int32_t gate_method, float gate_tol, int32_t gate_max_iters, float tol,
+                          int32_t max_iters, int32_t k, float alpha, float lambda_div, int32_t* ids, float* score, float* align,
+                          int32_t* iters_out, float* res_out) {
+  return guarded(h, [&](L& l) {
+    if (Q < 0) throw Invalid("osc_bundle_gated_many: Q must be >= 0");
+    if (Q > 0 && (!psis || !gates)) throw Invalid("osc_bundle_gated_many: NULL buffer");
+    if (Q > 0 && k > 0 && (!ids || !score || !align)) throw Invalid("osc_bundle_gated_many: NULL buffer");
+    query_bundle_gated_many(l, psis, Q, gates, diffusion, gate_beta, gate_gamma, gate_method, gate_tol, gate_max_iters, tol,
+                            max_iters, k, alpha, lambda_div, ids, score, align, iters_out, res_out, nullptr);
+  });
+}
+
+int osc_ustar_gated_many(osc_handle h, const float* psis, int32_t Q, const float* gates, float tol, int32_t max_iters,
+                         float* U_out, int32_t* iters_out, float* res_out) {
+  return guarded(h, [&](L& l) {
+    if (Q < 0) throw Invalid("osc_ustar_gated_many: Q must be >= 0");
+    if (Q > 0 && (!psis || !gates || !U_out)) throw Invalid("osc_ustar_gated_many: NULL buffer");
+    query_bundle_gated_many(l, psis, Q, const_cast<float*>(gates), 0, 0.f, 0.f, 0, 0.f, 0, tol, max_iters, 0, 0.f, 0.f, nullptr,
+                            nullptr, nullptr, iters_out, res_out, U_out);
+  });
+}
+
 int osc_receipt_many(osc_handle h, const float* psis, int32_t Q, int32_t detail, float z_th, int32_t null_cap, double* dH,
                      double* coh_sum, double* anchor_sum, double* query_sum, int32_t* null_total, int64_t* null_offsets,
                      int32_t* i_out, int32_t* j_out, float* z_out, float* r_out, int64_t capacity) {

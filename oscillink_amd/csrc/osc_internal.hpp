@@ -38,6 +38,7 @@
 #include "small.hpp"
 #include "query.hpp"
 #include "gates_many.hpp"
+#include "bundle_gated.hpp"
 #include "chain_prior_plan.hpp"
 #include "bundle_prior_plan.hpp"
 #include "receipt_prior_plan.hpp"
@@ -565,6 +566,11 @@ void query_mmr_many(L& l, const float* scores, int32_t Q, int32_t k, float lambd
 // osc_gates_many (gates_many.hpp)
 void query_gates_many(L& l, const float* psis, int32_t Q, float beta, float gamma, int32_t method, float tol, int32_t max_iters,
                       int32_t clamp, float* gates_out, int32_t* iters_out, float* res_out);
+// osc_bundle_gated_many / osc_ustar_gated_many (bundle_gated.hpp)
+void query_bundle_gated_many(L& l, const float* psis, int32_t Q, float* gates, int32_t diffusion, float gate_beta,
+                             float gate_gamma, int32_t gate_method, float gate_tol, int32_t gate_max_iters, float tol,
+                             int32_t max_iters, int32_t k, float alpha, float lambda_div, int32_t* ids, float* score,
+                             float* align, int32_t* iters_out, float* res_out, float* U_out);
 
 struct ProfScope {
   L& h;

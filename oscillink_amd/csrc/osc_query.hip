@@ -1789,3 +1789,141 @@ void query_gates_many(L& l, const float* psis, int32_t Q, float beta, float gamm
     sync(l);  // (bt and the scratch block are reused by the next chunk)
   }
 }
+
+// ---- bundles under per-query gates -----------------------------------------------------------
+// set_query(psi_q, gates = g_q); bundle(k, alpha) (lattice.py:114-120, 245-263, 530-568) for Q queries on the handle's
+// graph and lambdas.  M_q = lamG I + lamC L_sym + lamQ diag(g_q) differs per query, so a chunk is nq whole N x D solves, run
+// as one panel PCG (bundle_gated_kernels.hip) with the reference's stop per query; the solved panel then gives the align /
+// coh columns that the batched score, MMR and pack of osc_bundle_many take.  With diffusion != 0 the gates are
+// osc_gates_many's, written to `gates` first.  Nothing of the handle's state is read but the anchors, the graph and the
+// lambdas, and nothing is written.  U_out (Q x N x D, API rows) is the private read-out of the solves; k <= 0 skips the bundle.
+void query_bundle_gated_many(L& l, const float* psis, int32_t Q, float* gates, int32_t diffusion, float gate_beta,
+                             float gate_gamma, int32_t gate_method, float gate_tol, int32_t gate_max_iters, float tol,
+                             int32_t max_iters, int32_t k, float alpha, float lambda_div, int32_t* ids, float* score,
+                             float* align, int32_t* iters_out, float* res_out, float* U_out) {
+  require_graph(l);
+  if (l.comm) throw Unsupported("osc_bundle_gated_many: lattices with a communicator are not supported");
+  if (l.chain_present) throw Unsupported("osc_bundle_gated_many: a lattice with a chain of its own is not supported");
+  if (max_iters < 1) throw Invalid("max_iters must be >= 1");
+  if (Q <= 0) return;
+  if (diffusion)
+    query_gates_many(l, psis, Q, gate_beta, gate_gamma, gate_method, gate_tol, gate_max_iters, 1, gates, nullptr, nullptr);
+  const int32_t N = (int32_t)l.N, D = l.D;
+  const int32_t kk = (int32_t)std::min<int64_t>(std::max(k, 0), l.N);
+  const int32_t spq = host::gated_slabs_per_query(D), qcols = spq * host::kGatesSlab;
+  int requested = host::kGatedMaxChunk;
+  env_num("OSC_GATED_CHUNK", requested);
+  static_assert(host::kGatedMaxChunk <= kQueryChunk, "a chunk's score, MMR and pack run as one pass of osc_bundle_many's");
+  const int32_t chunk = host::gated_chunk(N, D, requested, host::kGatedBudgetBytes);
+  DevBuf<char> scratch;
+  scratch.alloc((size_t)host::gated_layout(N, D, std::min(chunk, Q)).total);
+  auto& q = l.query;
+  DevBuf<double> ysum;
+  if (kk > 0) {
+    ensure_yn(l);
+    q.part.alloc((size_t)query_stat_parts(N) * kQueryChunk);
+    q.stats.alloc(kQueryChunk);
+    q.out_score.alloc((size_t)kQueryChunk * kk);
+    q.out_align.alloc((size_t)kQueryChunk * kk);
+    ysum.alloc((size_t)N);
+  }
+  const GmGraph g{l.ell_col.p, l.ell_w.p, l.deg.p, l.width};
+  const int32_t* api_id = permuted(l) ? l.perm_d.p : nullptr;
+  std::vector<float> hpsi, hx;
+  bool have_ysum = false;
+  for (int32_t c = 0; c < host::gates_chunk_count(Q, chunk); ++c) {
+    const int32_t q0 = host::gates_chunk_begin(c, chunk), nq = host::gates_chunk_size(Q, c, chunk);
+    const host::GatedLayout lay = host::gated_layout(N, D, nq);
+    char* const base = scratch.p;
+    float* const gate_api = reinterpret_cast<float*>(base + lay.gate_api);
+    float* const gate = reinterpret_cast<float*>(base + lay.gate);
+    float* const psi = reinterpret_cast<float*>(base + lay.psi);
+    BgPanel p{};
+    p.X = reinterpret_cast<float*>(base + lay.X);
+    p.R = reinterpret_cast<float*>(base + lay.R);
+    p.P = reinterpret_cast<float*>(base + lay.P);
+    p.AP = reinterpret_cast<float*>(base + lay.AP);
+    p.gate = gate;
+    p.psi = psi;
+    p.part_a = reinterpret_cast<double*>(base + lay.part_a);
+    p.part_b = reinterpret_cast<double*>(base + lay.part_b);
+    p.rz = reinterpret_cast<double*>(base + lay.rz);
+    p.alpha = reinterpret_cast<float*>(base + lay.alpha);
+    p.beta = reinterpret_cast<float*>(base + lay.beta);
+    p.res = reinterpret_cast<float*>(base + lay.res);
+    p.live = reinterpret_cast<int32_t*>(base + lay.live);
+    p.iters = reinterpret_cast<int32_t*>(base + lay.iters);
+    p.n_live = reinterpret_cast<int32_t*>(base + lay.n_live);
+    p.N = N;
+    p.slabs = nq * spq;
+    p.parts = host::gates_parts(N);
+    p.part_rows = host::gates_part_rows(N);
+    p.nq = nq;
+    p.spq = spq;
+    p.D = D;
+    p.lamG = l.lamG;
+    p.lamC = l.lamC;
+    p.lamQ = l.lamQ;
+    p.tol = tol;
+    hpsi.assign((size_t)nq * qcols, 0.f);
+    for (int32_t t = 0; t < nq; ++t) std::copy(psis + (size_t)(q0 + t) * D, psis + (size_t)(q0 + t + 1) * D, hpsi.data() + (size_t)t * qcols);
+    HIP_CHECK(hipMemcpyAsync(psi, hpsi.data(), hpsi.size() * 4, hipMemcpyHostToDevice, l.stream));
+    HIP_CHECK(hipMemcpyAsync(gate_api, gates + (size_t)q0 * N, (size_t)nq * N * 4, hipMemcpyHostToDevice, l.stream));
+    launch_bg_gates(gate_api, api_id, N, nq, gate, l.stream);
+    launch_bg_init(p, g, l.Y.p, l.ld, l.stream);
+    launch_bg_start(p, l.stream);
+    for (int32_t it = 1; it <= max_iters; ++it) {
+      launch_bg_apply(p, g, l.stream);
+      launch_bg_alpha(p, l.stream);
+      launch_bg_update(p, l.stream);
+      launch_bg_beta(p, it, l.stream);
+      int32_t live = 0;
+      // the next direction is enqueued before the host waits for the count (after the last iteration nothing reads it)
+      if (it < max_iters) launch_bg_direction(p, l.stream);
+      HIP_CHECK(hipMemcpyAsync(&live, p.n_live + (it & 1), 4, hipMemcpyDeviceToHost, l.stream));
+      sync(l);
+      if (live == 0) break;
+    }
+    if (iters_out) HIP_CHECK(hipMemcpyAsync(iters_out + q0, p.iters, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
+    if (res_out) HIP_CHECK(hipMemcpyAsync(res_out + q0, p.res, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
+    if (U_out) {
+      hx.resize((size_t)p.slabs * N * 32);
+      HIP_CHECK(hipMemcpyAsync(hx.data(), p.X, hx.size() * 4, hipMemcpyDeviceToHost, l.stream));
+      sync(l);
+      for (int32_t t = 0; t < nq; ++t)
+        for (int32_t r = 0; r < N; ++r) {
+          float* dst = U_out + ((size_t)(q0 + t) * N + (size_t)(permuted(l) ? l.perm_h[(size_t)r] : r)) * D;
+          for (int32_t d = 0; d < D; ++d) dst[d] = hx[((size_t)(t * spq + d / 32) * N + r) * 32 + d % 32];
+        }
+    }
+    if (kk > 0) {
+      const int32_t qs = query_qs(nq);
+      q.align.alloc((size_t)N * qs);
+      q.pm.alloc((size_t)N * qs);
+      q.cs.alloc((size_t)N * qs);
+      BgBundleArgs b{};
+      b.col = l.ell_col.p;
+      b.adj = l.ell_a.p;
+      b.deg = l.deg.p;
+      b.width = l.width;
+      b.sqrt_deg = l.sqrt_deg.p;
+      b.Y = l.Y.p;
+      b.ld = l.ld;
+      b.qs = qs;
+      b.ysum = ysum.p;
+      b.align = q.align.p;
+      b.coh = q.cs.p;
+      if (!have_ysum) launch_bg_ysum(p, b, l.stream);
+      have_ysum = true;
+      launch_bg_bundle(p, b, l.stream);
+      launch_query_score(q.cs.p, q.align.p, N, qs, nq, (double)alpha, q.part.p, q.stats.p, l.stream);
+      mmr_many_run(l, qs, nq, kk, lambda_div);
+      launch_query_pack(q.cs.p, q.align.p, q.chosen_row.p, qs, nq, kk, q.out_score.p, q.out_align.p, l.stream);
+      const size_t m = (size_t)nq * kk, off = (size_t)q0 * kk;
+      HIP_CHECK(hipMemcpyAsync(ids + off, q.chosen_api.p, m * 4, hipMemcpyDeviceToHost, l.stream));
+      HIP_CHECK(hipMemcpyAsync(score + off, q.out_score.p, m * 4, hipMemcpyDeviceToHost, l.stream));
+      HIP_CHECK(hipMemcpyAsync(align + off, q.out_align.p, m * 4, hipMemcpyDeviceToHost, l.stream));
+    }
+    sync(l);  // (hpsi and the scratch block are reused by the next chunk)
+  }
+}

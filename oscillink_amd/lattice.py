@@ -150,6 +150,7 @@ class OscillinkLattice:
         self._qbs_scale = 0.0
         self._qbs_stats = False  # the shifted slot also holds its per-row constants (bundle_many with lamP)
         self.last_bundle_prior: dict[str, Any] = {}
+        self.last_bundle_gated: dict[str, Any] = {}
         self._qbs_receipt = 0  # receipt_many with lamP: 1 = the slot holds M' x' (8 N bytes), 2 = also d_ij per ELL slot
         self.last_receipt_prior: dict[str, Any] = {}
         self.last_shifted_basis: dict[str, Any] = {}
@@ -836,7 +837,9 @@ class OscillinkLattice:
         chain of its own, from the basis of the shifted operator `chain_receipt_many(lamP=...)` uses (the same slot and
         key) and one Green's column per distinct chain node.  `chains` and `chain_weights` take `chain_receipt_many`'s
         forms; a chain has at most 64 distinct nodes.  Per query the residual bound and the Green's columns' iterations
-        go to `last_bundle_prior` = {"lamP", "res" (float32), "iters" (int32)}.  `lamP=0` is the plain call."""
+        go to `last_bundle_prior` = {"lamP", "res" (float32), "iters" (int32)}.  `lamP=0` is the plain call.
+
+        Per-query GATES are `bundle_gated_many`'s."""
         if self._has_comm:
             raise NotImplementedError("bundle_many: lattices with a communicator (sharded / multi-rank) are not supported")
         prior = rc.check_prior_args("bundle_many", chains, lamP, chain_weights, self._chain_nodes is not None)
@@ -870,6 +873,116 @@ class OscillinkLattice:
         if Q == 0:
             return []
         return [rc.bundle_dicts(ids[q], score[q], align[q]) for q in range(Q)]
+
+    def _check_gate_rows(self, gates) -> np.ndarray:
+        """Per-query gates as a contiguous float32 (Q, N) array (Q is not checked here), or the ValueError for a single
+        gate vector."""
+        G = np.asarray(gates)
+        if G.ndim == 1:
+            raise ValueError(f"gates must be a (Q, {self.N}) array, one row per query; one gate vector for every query is "
+                             "set_gates(gates) followed by bundle_many(psis)")
+        if G.ndim != 2 or G.shape[1] != self.N:
+            raise ValueError(f"gates must be a (Q, {self.N}) array, got shape {G.shape}")
+        return np.ascontiguousarray(G, dtype=np.float32)
+
+    def bundle_gated_many(self, psis: np.ndarray, gates, k: int = 8, alpha: float = 0.5, *, tol: float = 1e-4,
+                          max_iters: int = 256, as_arrays: bool = False, gate_beta: float = 1.0, gate_gamma: float = 0.1,
+                          gate_method: str = "direct", gate_tol: float = 1e-4, gate_max_iters: int = 256):
+        """`bundle_many` with gates of its own for every query: query q gets what
+        `set_query(psis[q], gates=G[q]); bundle(k, alpha)` gives, the lattice's own gates, psi, U, U* cache, query basis
+        and receipts being neither read nor changed.  `gates` is a (Q, N) array in API row order (finite, >= 0), or
+        "diffusion": `diffusion_gates_many(psis, beta=gate_beta, gamma=gate_gamma, method=gate_method, tol=gate_tol,
+        max_iters=gate_max_iters)["gates"]`, computed in the same call.  M differs per query, so every query is its own
+        N x D solve of `solve_Ustar` -- the reference's rule: stop at the first iteration where the query's largest column
+        residual is <= `tol` -- and the Q solves run as one panel CG over the shared graph, `OSC_GATED_CHUNK` queries at
+        a time.  The loop's `solve_Ustar()` runs to 1e-4 in at most 64 iterations; the default `max_iters=256` here only
+        matters for a query that has not converged at 64.  Returns `bundle_many`'s forms: Q lists of {"id", "score",
+        "align"}, or with `as_arrays=True` (ids, score, align).  The solve report goes to `last_bundle_gated` = {"iters"
+        (int32), "res" (float32), "converged" (bool), "gates" ((Q, N) float32 for "diffusion", else None)}.  A non-finite
+        query row (or non-finite diffusion gates, which raise `diffusion_gates_many`'s warning) gives that query
+        non-finite answers and changes no other query's.  Its own method because `bundle_many`'s parameter list is
+        pinned; chain priors (`bundle_many(chains=..., lamP=...)`) do not combine with per-query gates, and a lattice
+        with a chain of its own raises NotImplementedError."""
+        if self._has_comm:
+            raise NotImplementedError("bundle_gated_many: lattices with a communicator (sharded / multi-rank) are not "
+                                      "supported")
+        if self._chain_nodes is not None:
+            raise NotImplementedError("bundle_gated_many: a lattice with a chain of its own is not supported "
+                                      "(clear_chain first)")
+        P = rc.check_queries(psis, self.D, finite=False)
+        Q = int(P.shape[0])
+        diffusion = isinstance(gates, str)
+        if diffusion:
+            if gates != "diffusion":
+                raise ValueError(f"gates must be 'diffusion' or a ({Q}, {self.N}) array, got {gates!r}")
+            if not float(gate_gamma) > 0:
+                raise ValueError("gate_gamma must be > 0 for SPD")
+            if gate_method not in ("direct", "cg"):
+                raise ValueError(f"gate_method must be 'direct' or 'cg', got {gate_method!r}")
+            if int(gate_max_iters) < 1:
+                raise ValueError("gate_max_iters must be >= 1")
+            G = nat.result_array((Q, self.N)) if Q > 0 else np.zeros((0, self.N), dtype=np.float32)
+        else:
+            G = self._check_gate_rows(gates)
+            if G.shape[0] != Q:
+                raise ValueError(f"gates must be a ({Q}, {self.N}) array, got shape {G.shape}")
+            for q in range(Q):
+                if not np.all(np.isfinite(G[q])):
+                    raise ValueError(f"query {q}: gates must be finite")
+                if np.any(G[q] < 0):
+                    raise ValueError(f"query {q}: gates must be >= 0")
+        if int(max_iters) < 1:
+            raise ValueError("max_iters must be >= 1")
+        kk = min(int(k), self.N) if k > 0 else 0
+        ids = np.zeros((Q, kk), dtype=np.int32)
+        score = np.zeros((Q, kk), dtype=np.float32)
+        align = np.zeros((Q, kk), dtype=np.float32)
+        iters = np.zeros(Q, dtype=np.int32)
+        res = np.zeros(Q, dtype=np.float32)
+        if Q > 0:
+            self._push_params()
+            self._call("osc_bundle_gated_many", nat.f32(P), Q, nat.f32(G), int(diffusion), float(gate_beta),
+                       float(gate_gamma), 1 if gate_method == "cg" else 0, float(gate_tol), int(gate_max_iters), float(tol),
+                       int(max_iters), kk, float(alpha), 0.5, nat.i32(ids), nat.f32(score), nat.f32(align), nat.i32(iters),
+                       nat.f32(res))
+        if diffusion:
+            bad = np.nonzero(~np.all(np.isfinite(G), axis=1))[0]
+            if bad.size:
+                import warnings
+
+                warnings.warn(f"diffusion_gates_many: the screened-diffusion solve of query {int(bad[0])} produced "
+                              "non-finite values; returned as computed, like the reference's cg path", RuntimeWarning,
+                              stacklevel=2)
+        self.last_bundle_gated = {"iters": iters, "res": res, "converged": res <= np.float32(tol),
+                                  "gates": G if diffusion else None}
+        self._log("bundle_gated_many", {"Q": Q, "k": kk, "gates": "diffusion" if diffusion else "given",
+                                        "iters_max": int(iters.max()) if Q else 0,
+                                        "converged": int(np.count_nonzero(res <= np.float32(tol)))})
+        if as_arrays:
+            return ids, score, align
+        if Q == 0:
+            return []
+        return [rc.bundle_dicts(ids[q], score[q], align[q]) for q in range(Q)]
+
+    def _ustar_gated_many(self, psis: np.ndarray, gates: np.ndarray, tol: float = 1e-4, max_iters: int = 256):
+        """The solves of bundle_gated_many alone: (U (Q, N, D) float32 in API row order, iters (Q,) int32, res (Q,)
+        float32).  Private: exposed for tests, as `_mmr_many` is; neither the queries nor the gates are checked for
+        finite values."""
+        if self._has_comm:
+            raise NotImplementedError("_ustar_gated_many: lattices with a communicator are not supported")
+        P = rc.check_queries(psis, self.D, finite=False)
+        G = self._check_gate_rows(gates)
+        Q = int(P.shape[0])
+        if G.shape[0] != Q:
+            raise ValueError(f"gates must be a ({Q}, {self.N}) array, got shape {G.shape}")
+        U = np.zeros((Q, self.N, self.D), dtype=np.float32)
+        iters = np.zeros(Q, dtype=np.int32)
+        res = np.zeros(Q, dtype=np.float32)
+        if Q > 0:
+            self._push_params()
+            self._call("osc_ustar_gated_many", nat.f32(P), Q, nat.f32(G), float(tol), int(max_iters), nat.f32(U),
+                       nat.i32(iters), nat.f32(res))
+        return U, iters, res
 
     def receipt_many(self, psis: np.ndarray, *, tol: float = 1e-4, max_iters: int = 256, as_arrays: bool = False,
                      chains=None, lamP: Optional[float] = None, chain_weights=None):
