@@ -435,6 +435,26 @@ int osc_bundle_gated_many(osc_handle h, const float* psis, int32_t Q, float* gat
  * g_q (diagnostic; the batched MMR's osc_mmr_many plays the same role). */
 int osc_ustar_gated_many(osc_handle h, const float* psis, int32_t Q, const float* gates, float tol, int32_t max_iters,
                          float* U_out, int32_t* iters_out, float* res_out);
+/* Not in the reference: the gated flow's set_query(psi_q, gates = g_q); [settle(dt, settle_max_iters, settle_tol);] receipt();
+ * [bundle(k, alpha)] (lattice.py:159-230, 298-455, receipts.py:10-83) for Q queries in one call.
+ * psis, gates, diffusion and the gate_* arguments are osc_bundle_gated_many's, and so are tol / max_iters of the U* solve,
+ * iters_out / res_out and -- with k > 0 -- ids / score / align, bit for bit.  With settle != 0 every query's implicit Euler
+ * step starts from the handle's current U (warm_start, no inertia) and stops by solver.py:23-37; settle_iters / settle_res
+ * (Q each) report it and deltaH is measured from the query's settled state, which is not written back.  With settle == 0
+ * deltaH is measured from U as it is.  dH ... capacity are osc_receipt_many's outputs (detail, z_th, null_cap as there), the
+ * energies and null points being those of U*_q under M_q = lamG I + lamC L_sym + lamQ diag(g_q).  settle_ms / solve_ms (Q
+ * each): the wall time of the query's chunk in that phase divided by the chunk's queries.  A query's outputs are the same to
+ * the bit whatever else the batch holds; queries run OSC_GATED_CHUNK at a time, fewer where a chunk's scratch would pass
+ * 1 GiB, never fewer than one.  The handle's U is read; nothing of its state is changed.  Errors as osc_bundle_gated_many;
+ * OSC_E_INVALID also for dt <= 0 or settle_max_iters < 1 with settle, or a capacity too small for the null points. */
+int osc_receipt_gated_many(osc_handle h, const float* psis, int32_t Q, float* gates, int32_t diffusion, float gate_beta,
+                           float gate_gamma, int32_t gate_method, float gate_tol, int32_t gate_max_iters, float tol,
+                           int32_t max_iters, int32_t settle, float dt, int32_t settle_max_iters, float settle_tol,
+                           int32_t detail, float z_th, int32_t null_cap, int32_t k, float alpha, float lambda_div,
+                           int32_t* settle_iters, float* settle_res, double* dH, double* coh_sum, double* anchor_sum,
+                           double* query_sum, int32_t* null_total, int64_t* null_offsets, int32_t* i_out, int32_t* j_out,
+                           float* z_out, float* r_out, int64_t capacity, int32_t* ids, float* score, float* align,
+                           int32_t* iters_out, float* res_out, double* settle_ms, double* solve_ms);
 /* Not in the reference: receipt() (lattice.py:298-455, receipts.py:10-83) for Q queries psis (Q x D) with the current U,
  * gates, chain and lambdas held fixed, U*(psi) from the resident basis.  Per query: dH (deltaH_trace
  * of U against U*(psi_q)); with detail != 0 also coh_sum / anchor_sum / query_sum and the null points at z_th (else 0 and

@@ -7,32 +7,10 @@
 // gates' solve is the diagonal, indexed by (row, query of the slab), the start at x0 = Y with the initial residual formed
 // on the fly from the anchors, and the stop: the largest column residual of a QUERY decides for all its columns.  Nothing
 // depends on which other queries fill the panel, so a query's answers are the same to the bit in any batch or chunk.
-#include "bundle_gated.hpp"
-#include "gates_many_dev.hpp"
+#include "bundle_gated_dev.hpp"
 
 namespace osc {
 namespace {
-
-// the reference's Jacobi diagonal lamG + lamQ g (+ 1e-12), inverted (lattice.py:257-259, solver.py:20)
-__device__ __forceinline__ float bg_inv_md(const BgPanel& p, float g) { return 1.0f / (fmaf(p.lamQ, g, p.lamG) + 1e-12f); }
-
-__device__ __forceinline__ float4 scale4(const float4 v, float s) { return make_float4(v.x * s, v.y * s, v.z * s, v.w * s); }
-
-// four anchor columns of a row (pitch ld), zero past D
-__device__ __forceinline__ float4 ld_anchor(const float* __restrict__ Y, int64_t row, int32_t ld, int c, int32_t D) {
-  if (c >= D) return f4(0.f);
-  float4 v = ld4(Y + (size_t)row * ld + c);  // c < D and c % 4 == 0: the four floats lie inside the row's pitch (>= D rounded up to 4)
-  if (c + 1 >= D) v.y = 0.f;
-  if (c + 2 >= D) v.z = 0.f;
-  if (c + 3 >= D) v.w = 0.f;
-  return v;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 __global__ __launch_bounds__(256) void k_bg_gates(const float* __restrict__ gate_api, const int32_t* __restrict__ api_id,
                                                   int32_t N, float* __restrict__ gate) {
@@ -279,12 +257,6 @@ __global__ __launch_bounds__(256) void k_bg_direction(const BgPanel p) {
 }
 
 // ---- the bundle's columns ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ double sqdiff4(const float4 a, double sa, const float4 b, double sb) {
-  const double dx = (double)a.x * sa - (double)b.x * sb, dy = (double)a.y * sa - (double)b.y * sb;
-  const double dz = (double)a.z * sa - (double)b.z * sb, dw = (double)a.w * sa - (double)b.w * sb;
-  return dx * dx + dy * dy + dz * dz + dw * dw;
-}
-
 // one wave per row: ysum_i = sum_j A_ij |Yn_i - Yn_j|^2 over the slots with A_ij > 0 (receipts.py:40, 45-56).  A lane owns
 // the columns 4 lane + 256 u and adds its share in (u, slot) order; the lanes are added by a fixed butterfly.
 __global__ __launch_bounds__(256) void k_bg_ysum(const BgPanel p, const BgBundleArgs a) {

@@ -39,6 +39,7 @@
 #include "query.hpp"
 #include "gates_many.hpp"
 #include "bundle_gated.hpp"
+#include "receipt_gated.hpp"
 #include "chain_prior_plan.hpp"
 #include "bundle_prior_plan.hpp"
 #include "receipt_prior_plan.hpp"
@@ -571,6 +572,15 @@ void query_bundle_gated_many(L& l, const float* psis, int32_t Q, float* gates, i
                              float gate_gamma, int32_t gate_method, float gate_tol, int32_t gate_max_iters, float tol,
                              int32_t max_iters, int32_t k, float alpha, float lambda_div, int32_t* ids, float* score,
                              float* align, int32_t* iters_out, float* res_out, float* U_out);
+// osc_receipt_gated_many (receipt_gated.hpp)
+void query_receipt_gated_many(L& l, const float* psis, int32_t Q, float* gates, int32_t diffusion, float gate_beta,
+                              float gate_gamma, int32_t gate_method, float gate_tol, int32_t gate_max_iters, float tol,
+                              int32_t max_iters, int32_t settle, float dt, int32_t settle_max_iters, float settle_tol,
+                              int32_t detail, float z_th, int32_t null_cap, int32_t k, float alpha, float lambda_div,
+                              int32_t* settle_iters, float* settle_res, double* dH, double* coh_sum, double* anchor_sum,
+                              double* query_sum, int32_t* null_total, int64_t* null_offsets, int32_t* i_out, int32_t* j_out,
+                              float* z_out, float* r_out, int64_t capacity, int32_t* ids, float* score, float* align,
+                              int32_t* iters_out, float* res_out, double* settle_ms, double* solve_ms);
 
 struct ProfScope {
   L& h;

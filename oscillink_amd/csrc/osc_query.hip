@@ -1790,6 +1790,119 @@ void query_gates_many(L& l, const float* psis, int32_t Q, float beta, float gamm
   }
 }
 
+// ---- the gated panel (DESIGN.md sections 11.2 and 12.4): what osc_bundle_gated_many and osc_receipt_gated_many share ------
+namespace {
+
+// one chunk's panel over the scratch block at lay's offsets, with the handle's lambdas
+BgPanel gated_panel(L& l, char* base, const host::GatedLayout& lay, int32_t nq, int32_t spq, float tol) {
+  BgPanel p{};
+  p.X = reinterpret_cast<float*>(base + lay.X);
+  p.R = reinterpret_cast<float*>(base + lay.R);
+  p.P = reinterpret_cast<float*>(base + lay.P);
+  p.AP = reinterpret_cast<float*>(base + lay.AP);
+  p.gate = reinterpret_cast<float*>(base + lay.gate);
+  p.psi = reinterpret_cast<float*>(base + lay.psi);
+  p.part_a = reinterpret_cast<double*>(base + lay.part_a);
+  p.part_b = reinterpret_cast<double*>(base + lay.part_b);
+  p.rz = reinterpret_cast<double*>(base + lay.rz);
+  p.alpha = reinterpret_cast<float*>(base + lay.alpha);
+  p.beta = reinterpret_cast<float*>(base + lay.beta);
+  p.res = reinterpret_cast<float*>(base + lay.res);
+  p.live = reinterpret_cast<int32_t*>(base + lay.live);
+  p.iters = reinterpret_cast<int32_t*>(base + lay.iters);
+  p.n_live = reinterpret_cast<int32_t*>(base + lay.n_live);
+  p.N = (int32_t)l.N;
+  p.slabs = nq * spq;
+  p.parts = host::gates_parts(l.N);
+  p.part_rows = host::gates_part_rows(l.N);
+  p.nq = nq;
+  p.spq = spq;
+  p.D = l.D;
+  p.lamG = l.lamG;
+  p.lamC = l.lamC;
+  p.lamQ = l.lamQ;
+  p.tol = tol;
+  return p;
+}
+
+// the chunk's queries (zero past D) and gates (API row order -> device row order) into the panel's arrays
+void gated_panel_inputs(L& l, const BgPanel& p, char* base, const host::GatedLayout& lay, const float* psis, const float* gates,
+                        int32_t q0, std::vector<float>& hpsi) {
+  const int32_t N = p.N, D = p.D, nq = p.nq, qcols = p.spq * host::kGatesSlab;
+  float* const gate_api = reinterpret_cast<float*>(base + lay.gate_api);
+  hpsi.assign((size_t)nq * qcols, 0.f);
+  for (int32_t t = 0; t < nq; ++t) std::copy(psis + (size_t)(q0 + t) * D, psis + (size_t)(q0 + t + 1) * D, hpsi.data() + (size_t)t * qcols);
+  HIP_CHECK(hipMemcpyAsync(const_cast<float*>(p.psi), hpsi.data(), hpsi.size() * 4, hipMemcpyHostToDevice, l.stream));
+  HIP_CHECK(hipMemcpyAsync(gate_api, gates + (size_t)q0 * N, (size_t)nq * N * 4, hipMemcpyHostToDevice, l.stream));
+  launch_bg_gates(gate_api, permuted(l) ? l.perm_d.p : nullptr, N, nq, const_cast<float*>(p.gate), l.stream);
+}
+
+// cg_solve's loop (solver.py:23-37) over an initialised panel: the stop per query, at most max_iters iterations
+void gated_panel_pcg(L& l, const BgPanel& p, const GmGraph& g, int32_t max_iters) {
+  launch_bg_start(p, l.stream);
+  for (int32_t it = 1; it <= max_iters; ++it) {
+    launch_bg_apply(p, g, l.stream);
+    launch_bg_alpha(p, l.stream);
+    launch_bg_update(p, l.stream);
+    launch_bg_beta(p, it, l.stream);
+    int32_t live = 0;
+    // the next direction is enqueued before the host waits for the count (after the last iteration nothing reads it)
+    if (it < max_iters) launch_bg_direction(p, l.stream);
+    HIP_CHECK(hipMemcpyAsync(&live, p.n_live + (it & 1), 4, hipMemcpyDeviceToHost, l.stream));
+    sync(l);
+    if (live == 0) break;
+  }
+}
+
+BgBundleArgs gated_bundle_args(L& l, int32_t qs, double* ysum) {
+  BgBundleArgs b{};
+  b.col = l.ell_col.p;
+  b.adj = l.ell_a.p;
+  b.deg = l.deg.p;
+  b.width = l.width;
+  b.sqrt_deg = l.sqrt_deg.p;
+  b.Y = l.Y.p;
+  b.ld = l.ld;
+  b.qs = qs;
+  b.ysum = ysum;
+  b.align = l.query.align.p;
+  b.coh = l.query.cs.p;
+  return b;
+}
+
+// the buffers of gated_bundle_stage, once per call
+void gated_bundle_alloc(L& l, int32_t kk) {
+  auto& q = l.query;
+  ensure_yn(l);
+  q.part.alloc((size_t)query_stat_parts((int32_t)l.N) * kQueryChunk);
+  q.stats.alloc(kQueryChunk);
+  q.out_score.alloc((size_t)kQueryChunk * kk);
+  q.out_align.alloc((size_t)kQueryChunk * kk);
+}
+
+// the bundle of the chunk's queries from the solved panel: align / coh columns, then osc_bundle_many's score, MMR and pack
+void gated_bundle_stage(L& l, const BgPanel& p, int32_t q0, int32_t kk, float alpha, float lambda_div, double* ysum,
+                        bool& have_ysum, int32_t* ids, float* score, float* align) {
+  auto& q = l.query;
+  const int32_t N = p.N, nq = p.nq, qs = query_qs(nq);
+  q.align.alloc((size_t)N * qs);
+  q.pm.alloc((size_t)N * qs);
+  q.cs.alloc((size_t)N * qs);
+  const BgBundleArgs b = gated_bundle_args(l, qs, ysum);
+  if (!have_ysum) launch_bg_ysum(p, b, l.stream);
+  have_ysum = true;
+  launch_bg_bundle(p, b, l.stream);
+  launch_query_score(q.cs.p, q.align.p, N, qs, nq, (double)alpha, q.part.p, q.stats.p, l.stream);
+  mmr_many_run(l, qs, nq, kk, lambda_div);
+  launch_query_pack(q.cs.p, q.align.p, q.chosen_row.p, qs, nq, kk, q.out_score.p, q.out_align.p, l.stream);
+  const size_t m = (size_t)nq * kk, off = (size_t)q0 * kk;
+  HIP_CHECK(hipMemcpyAsync(ids + off, q.chosen_api.p, m * 4, hipMemcpyDeviceToHost, l.stream));
+  HIP_CHECK(hipMemcpyAsync(score + off, q.out_score.p, m * 4, hipMemcpyDeviceToHost, l.stream));
+  HIP_CHECK(hipMemcpyAsync(align + off, q.out_align.p, m * 4, hipMemcpyDeviceToHost, l.stream));
+}
+
+}  // namespace
+
 // ---- bundles under per-query gates -----------------------------------------------------------
 // set_query(psi_q, gates = g_q); bundle(k, alpha) (lattice.py:114-120, 245-263, 530-568) for Q queries on the handle's
 // graph and lambdas.  M_q = lamG I + lamC L_sym + lamQ diag(g_q) differs per query, so a chunk is nq whole N x D solves, run
@@ -1810,80 +1923,29 @@ void query_bundle_gated_many(L& l, const float* psis, int32_t Q, float* gates, i
     query_gates_many(l, psis, Q, gate_beta, gate_gamma, gate_method, gate_tol, gate_max_iters, 1, gates, nullptr, nullptr);
   const int32_t N = (int32_t)l.N, D = l.D;
   const int32_t kk = (int32_t)std::min<int64_t>(std::max(k, 0), l.N);
-  const int32_t spq = host::gated_slabs_per_query(D), qcols = spq * host::kGatesSlab;
+  const int32_t spq = host::gated_slabs_per_query(D);
   int requested = host::kGatedMaxChunk;
   env_num("OSC_GATED_CHUNK", requested);
   static_assert(host::kGatedMaxChunk <= kQueryChunk, "a chunk's score, MMR and pack run as one pass of osc_bundle_many's");
   const int32_t chunk = host::gated_chunk(N, D, requested, host::kGatedBudgetBytes);
   DevBuf<char> scratch;
   scratch.alloc((size_t)host::gated_layout(N, D, std::min(chunk, Q)).total);
-  auto& q = l.query;
   DevBuf<double> ysum;
   if (kk > 0) {
-    ensure_yn(l);
-    q.part.alloc((size_t)query_stat_parts(N) * kQueryChunk);
-    q.stats.alloc(kQueryChunk);
-    q.out_score.alloc((size_t)kQueryChunk * kk);
-    q.out_align.alloc((size_t)kQueryChunk * kk);
+    gated_bundle_alloc(l, kk);
     ysum.alloc((size_t)N);
   }
   const GmGraph g{l.ell_col.p, l.ell_w.p, l.deg.p, l.width};
-  const int32_t* api_id = permuted(l) ? l.perm_d.p : nullptr;
   std::vector<float> hpsi, hx;
   bool have_ysum = false;
   for (int32_t c = 0; c < host::gates_chunk_count(Q, chunk); ++c) {
     const int32_t q0 = host::gates_chunk_begin(c, chunk), nq = host::gates_chunk_size(Q, c, chunk);
     const host::GatedLayout lay = host::gated_layout(N, D, nq);
     char* const base = scratch.p;
-    float* const gate_api = reinterpret_cast<float*>(base + lay.gate_api);
-    float* const gate = reinterpret_cast<float*>(base + lay.gate);
-    float* const psi = reinterpret_cast<float*>(base + lay.psi);
-    BgPanel p{};
-    p.X = reinterpret_cast<float*>(base + lay.X);
-    p.R = reinterpret_cast<float*>(base + lay.R);
-    p.P = reinterpret_cast<float*>(base + lay.P);
-    p.AP = reinterpret_cast<float*>(base + lay.AP);
-    p.gate = gate;
-    p.psi = psi;
-    p.part_a = reinterpret_cast<double*>(base + lay.part_a);
-    p.part_b = reinterpret_cast<double*>(base + lay.part_b);
-    p.rz = reinterpret_cast<double*>(base + lay.rz);
-    p.alpha = reinterpret_cast<float*>(base + lay.alpha);
-    p.beta = reinterpret_cast<float*>(base + lay.beta);
-    p.res = reinterpret_cast<float*>(base + lay.res);
-    p.live = reinterpret_cast<int32_t*>(base + lay.live);
-    p.iters = reinterpret_cast<int32_t*>(base + lay.iters);
-    p.n_live = reinterpret_cast<int32_t*>(base + lay.n_live);
-    p.N = N;
-    p.slabs = nq * spq;
-    p.parts = host::gates_parts(N);
-    p.part_rows = host::gates_part_rows(N);
-    p.nq = nq;
-    p.spq = spq;
-    p.D = D;
-    p.lamG = l.lamG;
-    p.lamC = l.lamC;
-    p.lamQ = l.lamQ;
-    p.tol = tol;
-    hpsi.assign((size_t)nq * qcols, 0.f);
-    for (int32_t t = 0; t < nq; ++t) std::copy(psis + (size_t)(q0 + t) * D, psis + (size_t)(q0 + t + 1) * D, hpsi.data() + (size_t)t * qcols);
-    HIP_CHECK(hipMemcpyAsync(psi, hpsi.data(), hpsi.size() * 4, hipMemcpyHostToDevice, l.stream));
-    HIP_CHECK(hipMemcpyAsync(gate_api, gates + (size_t)q0 * N, (size_t)nq * N * 4, hipMemcpyHostToDevice, l.stream));
-    launch_bg_gates(gate_api, api_id, N, nq, gate, l.stream);
+    const BgPanel p = gated_panel(l, base, lay, nq, spq, tol);
+    gated_panel_inputs(l, p, base, lay, psis, gates, q0, hpsi);
     launch_bg_init(p, g, l.Y.p, l.ld, l.stream);
-    launch_bg_start(p, l.stream);
-    for (int32_t it = 1; it <= max_iters; ++it) {
-      launch_bg_apply(p, g, l.stream);
-      launch_bg_alpha(p, l.stream);
-      launch_bg_update(p, l.stream);
-      launch_bg_beta(p, it, l.stream);
-      int32_t live = 0;
-      // the next direction is enqueued before the host waits for the count (after the last iteration nothing reads it)
-      if (it < max_iters) launch_bg_direction(p, l.stream);
-      HIP_CHECK(hipMemcpyAsync(&live, p.n_live + (it & 1), 4, hipMemcpyDeviceToHost, l.stream));
-      sync(l);
-      if (live == 0) break;
-    }
+    gated_panel_pcg(l, p, g, max_iters);
     if (iters_out) HIP_CHECK(hipMemcpyAsync(iters_out + q0, p.iters, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
     if (res_out) HIP_CHECK(hipMemcpyAsync(res_out + q0, p.res, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
     if (U_out) {
@@ -1896,34 +1958,158 @@ void query_bundle_gated_many(L& l, const float* psis, int32_t Q, float* gates, i
           for (int32_t d = 0; d < D; ++d) dst[d] = hx[((size_t)(t * spq + d / 32) * N + r) * 32 + d % 32];
         }
     }
-    if (kk > 0) {
-      const int32_t qs = query_qs(nq);
-      q.align.alloc((size_t)N * qs);
-      q.pm.alloc((size_t)N * qs);
-      q.cs.alloc((size_t)N * qs);
-      BgBundleArgs b{};
-      b.col = l.ell_col.p;
-      b.adj = l.ell_a.p;
-      b.deg = l.deg.p;
-      b.width = l.width;
-      b.sqrt_deg = l.sqrt_deg.p;
-      b.Y = l.Y.p;
-      b.ld = l.ld;
-      b.qs = qs;
-      b.ysum = ysum.p;
-      b.align = q.align.p;
-      b.coh = q.cs.p;
-      if (!have_ysum) launch_bg_ysum(p, b, l.stream);
-      have_ysum = true;
-      launch_bg_bundle(p, b, l.stream);
-      launch_query_score(q.cs.p, q.align.p, N, qs, nq, (double)alpha, q.part.p, q.stats.p, l.stream);
-      mmr_many_run(l, qs, nq, kk, lambda_div);
-      launch_query_pack(q.cs.p, q.align.p, q.chosen_row.p, qs, nq, kk, q.out_score.p, q.out_align.p, l.stream);
-      const size_t m = (size_t)nq * kk, off = (size_t)q0 * kk;
-      HIP_CHECK(hipMemcpyAsync(ids + off, q.chosen_api.p, m * 4, hipMemcpyDeviceToHost, l.stream));
-      HIP_CHECK(hipMemcpyAsync(score + off, q.out_score.p, m * 4, hipMemcpyDeviceToHost, l.stream));
-      HIP_CHECK(hipMemcpyAsync(align + off, q.out_align.p, m * 4, hipMemcpyDeviceToHost, l.stream));
+    if (kk > 0) gated_bundle_stage(l, p, q0, kk, alpha, lambda_div, ysum.p, have_ysum, ids, score, align);
+    sync(l);  // (hpsi and the scratch block are reused by the next chunk)
+  }
+}
+
+// ---- receipts under per-query gates ----------------------------------------------------------
+// set_query(psi_q, gates = g_q); [settle(dt, max_iters, tol);] receipt(); [bundle(k, alpha)] (lattice.py:159-230, 298-455,
+// receipts.py:10-83) for Q queries on the handle's graph, lambdas and state.  Per chunk: the settle (with `settle`) as the
+// panel PCG of section 11.2 on (I + dt M_q) -- the same operator with primed lambdas -- started at the handle's U; section
+// 11.2's U* solve; deltaH as the quadratic form of U_q - U*_q through the panel apply; in full detail the components and the
+// null points of U*_q (receipt_gated_kernels.hip, then osc_receipt_many's selection); with k > 0 section 11.2's bundle from
+// the same solve.  U is read; nothing of the handle's state is written.
+void query_receipt_gated_many(L& l, const float* psis, int32_t Q, float* gates, int32_t diffusion, float gate_beta,
+                              float gate_gamma, int32_t gate_method, float gate_tol, int32_t gate_max_iters, float tol,
+                              int32_t max_iters, int32_t settle, float dt, int32_t settle_max_iters, float settle_tol,
+                              int32_t detail, float z_th, int32_t null_cap, int32_t k, float alpha, float lambda_div,
+                              int32_t* settle_iters, float* settle_res, double* dH, double* coh_sum, double* anchor_sum,
+                              double* query_sum, int32_t* null_total, int64_t* null_offsets, int32_t* i_out, int32_t* j_out,
+                              float* z_out, float* r_out, int64_t capacity, int32_t* ids, float* score, float* align,
+                              int32_t* iters_out, float* res_out, double* settle_ms, double* solve_ms) {
+  require_graph(l);
+  if (l.comm) throw Unsupported("osc_receipt_gated_many: lattices with a communicator are not supported");
+  if (l.chain_present) throw Unsupported("osc_receipt_gated_many: a lattice with a chain of its own is not supported");
+  if (max_iters < 1) throw Invalid("max_iters must be >= 1");
+  if (settle && settle_max_iters < 1) throw Invalid("osc_receipt_gated_many: the settle's max_iters must be >= 1");
+  if (null_offsets) null_offsets[0] = 0;
+  if (Q <= 0) return;
+  if (diffusion)
+    query_gates_many(l, psis, Q, gate_beta, gate_gamma, gate_method, gate_tol, gate_max_iters, 1, gates, nullptr, nullptr);
+  const bool full = detail != 0, settled = settle != 0;
+  const int32_t N = (int32_t)l.N, D = l.D;
+  const int32_t kk = (int32_t)std::min<int64_t>(std::max(k, 0), l.N);
+  const int32_t spq = host::gated_slabs_per_query(D);
+  int requested = host::kGatedMaxChunk;
+  env_num("OSC_GATED_CHUNK", requested);
+  const int32_t chunk = host::receipt_gated_chunk(N, D, settled, full, requested, host::kGatedBudgetBytes);
+  DevBuf<char> scratch;
+  scratch.alloc((size_t)host::receipt_gated_layout(N, D, std::min(chunk, Q), settled, full).total);
+  auto& q = l.query;
+  DevBuf<double> ysum;
+  if (kk > 0) gated_bundle_alloc(l, kk);
+  if (kk > 0 || full) ysum.alloc((size_t)N);
+  const int cparts = rm_col_parts(l.N);
+  static_assert(host::kReceiptGatedFinishRows == kRmFinishRows, "the plan sizes launch_rm_colfinish's scratch");
+  if (full) {
+    if (cparts != host::receipt_gated_sum_parts(N)) throw std::logic_error("osc_receipt_gated_many: sum parts");
+    q.rtot.alloc(kQueryChunk);
+    q.rsel.alloc(kQueryChunk);
+    q.roff.alloc(kQueryChunk);
+  }
+  const GmGraph g{l.ell_col.p, l.ell_w.p, l.deg.p, l.width};
+  const int32_t* inv = permuted(l) ? l.inv_d.p : nullptr;
+  const float* const U = u_read(l);
+  std::vector<float> hpsi;
+  std::vector<double> hdh, hsum;
+  std::vector<int32_t> tot;
+  bool have_ysum = false;
+  for (int32_t c = 0; c < host::gates_chunk_count(Q, chunk); ++c) {
+    const int32_t q0 = host::gates_chunk_begin(c, chunk), nq = host::gates_chunk_size(Q, c, chunk);
+    const host::ReceiptGatedLayout lay = host::receipt_gated_layout(N, D, nq, settled, full);
+    char* const base = scratch.p;
+    BgPanel p = gated_panel(l, base, lay.panel, nq, spq, tol);
+    gated_panel_inputs(l, p, base, lay.panel, psis, gates, q0, hpsi);
+    const float* Us = nullptr;
+    if (settled) {
+      // (I + dt M_q) is the panel operator with primed lambdas: every kernel of the solve runs on them as it is
+      BgPanel ps = p;
+      ps.lamG = 1.0f + dt * l.lamG;
+      ps.lamC = dt * l.lamC;
+      ps.lamQ = dt * l.lamQ;
+      ps.tol = settle_tol;
+      sync(l);
+      const double t0 = now_ms();
+      launch_rg_settle_init(ps, g, U, l.Y.p, l.ld, dt, l.lamG, l.lamC, l.lamQ, l.stream);
+      gated_panel_pcg(l, ps, g, settle_max_iters);
+      HIP_CHECK(hipMemcpyAsync(settle_iters + q0, ps.iters, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
+      HIP_CHECK(hipMemcpyAsync(settle_res + q0, ps.res, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
+      sync(l);
+      const double per = (now_ms() - t0) / nq;
+      for (int32_t t = 0; t < nq; ++t) settle_ms[q0 + t] = per;
+      Us = ps.X;  // kept as the fifth panel: the U* solve writes the other one
+      p.X = reinterpret_cast<float*>(base + lay.U);
     }
+    const double t1 = now_ms();
+    launch_bg_init(p, g, l.Y.p, l.ld, l.stream);
+    gated_panel_pcg(l, p, g, max_iters);
+    if (iters_out) HIP_CHECK(hipMemcpyAsync(iters_out + q0, p.iters, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
+    if (res_out) HIP_CHECK(hipMemcpyAsync(res_out + q0, p.res, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
+    sync(l);
+    const double per_solve = (now_ms() - t1) / nq;
+    for (int32_t t = 0; t < nq; ++t) solve_ms[q0 + t] = per_solve;
+    // deltaH = tr((U_q - U*_q)^T M_q (U_q - U*_q)): the panel apply on the difference, its p . Ap per column
+    double* const dh = reinterpret_cast<double*>(base + lay.dh);
+    launch_rg_diff(p, Us, U, l.ld, l.stream);
+    launch_bg_apply(p, g, l.stream);
+    launch_rg_deltah(p, dh, l.stream);
+    hdh.assign((size_t)nq, 0.0);
+    HIP_CHECK(hipMemcpyAsync(hdh.data(), dh, (size_t)nq * 8, hipMemcpyDeviceToHost, l.stream));
+    if (!full) {
+      sync(l);
+      for (int32_t t = 0; t < nq; ++t) {
+        dH[q0 + t] = hdh[(size_t)t];
+        anchor_sum[q0 + t] = query_sum[q0 + t] = coh_sum[q0 + t] = 0.0;
+        null_total[q0 + t] = 0;
+        null_offsets[q0 + t + 1] = null_offsets[q0 + t];
+      }
+    } else {
+      const int32_t qs = lay.qs;
+      if (!have_ysum) launch_bg_ysum(p, gated_bundle_args(l, qs, ysum.p), l.stream);
+      have_ysum = true;
+      RgRowsArgs ra{};
+      ra.col = l.ell_col.p;
+      ra.adj = l.ell_a.p;
+      ra.deg = l.deg.p;
+      ra.width = l.width;
+      ra.sqrt_deg = l.sqrt_deg.p;
+      ra.Y = l.Y.p;
+      ra.ld = l.ld;
+      ra.qs = qs;
+      ra.ysum = ysum.p;
+      ra.api_id = permuted(l) ? l.perm_d.p : nullptr;
+      ra.z_th = z_th;
+      ra.comp = reinterpret_cast<double*>(base + lay.comp);
+      ra.z = reinterpret_cast<float*>(base + lay.z);
+      ra.j = reinterpret_cast<int32_t*>(base + lay.j);
+      ra.r = reinterpret_cast<float*>(base + lay.r);
+      launch_rg_components(p, ra, l.stream);
+      double* const sumpart = reinterpret_cast<double*>(base + lay.sumpart);
+      double* const sums = reinterpret_cast<double*>(base + lay.sums);
+      float* const zt = reinterpret_cast<float*>(base + lay.zt);
+      for (int t = 0; t < 3; ++t) {  // coh, anchor, query: rows dealt to cparts partials in row order, then the partials in order
+        double* const part = sumpart + (size_t)t * cparts * nq;
+        launch_rp_colsum(ra.comp + (size_t)t * N * qs, N, qs, nq, cparts, part, l.stream);
+        launch_rm_colfinish(part, cparts, nq, sums + (size_t)t * nq, reinterpret_cast<double*>(base + lay.sumfin), l.stream);
+      }
+      launch_rm_transpose(ra.z, inv, N, qs, nq, zt, l.stream);
+      launch_rm_null_count(zt, N, nq, q.rtot.p, l.stream);
+      hsum.assign((size_t)3 * nq, 0.0);
+      tot.assign((size_t)nq, 0);
+      HIP_CHECK(hipMemcpyAsync(hsum.data(), sums, hsum.size() * 8, hipMemcpyDeviceToHost, l.stream));
+      HIP_CHECK(hipMemcpyAsync(tot.data(), q.rtot.p, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
+      sync(l);
+      for (int32_t t = 0; t < nq; ++t) {
+        dH[q0 + t] = hdh[(size_t)t];
+        coh_sum[q0 + t] = hsum[(size_t)t];
+        anchor_sum[q0 + t] = hsum[(size_t)nq + t];
+        query_sum[q0 + t] = hsum[(size_t)2 * nq + t];
+      }
+      receipt_null_stage(l, "osc_receipt_gated_many", q0, nq, qs, null_cap, tot, zt, ra.j, ra.r, null_total, null_offsets, i_out,
+                         j_out, z_out, r_out, capacity);
+    }
+    if (kk > 0) gated_bundle_stage(l, p, q0, kk, alpha, lambda_div, ysum.p, have_ysum, ids, score, align);
     sync(l);  // (hpsi and the scratch block are reused by the next chunk)
   }
 }

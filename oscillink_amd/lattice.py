@@ -984,6 +984,152 @@ class OscillinkLattice:
                        nat.i32(iters), nat.f32(res))
         return U, iters, res
 
+    _GATED_SETTLE_DEFAULTS = {"dt": 1.0, "max_iters": 12, "tol": 1e-3}
+
+    def receipt_gated_many(self, psis: np.ndarray, gates, *, settle=None, bundle_k: Optional[int] = None, alpha: float = 0.5,
+                           tol: float = 1e-4, max_iters: int = 256, as_arrays: bool = False, gate_beta: float = 1.0,
+                           gate_gamma: float = 0.1, gate_method: str = "direct", gate_tol: float = 1e-4,
+                           gate_max_iters: int = 256):
+        """The gated flow's receipt -- and optionally its settle and bundle -- for every row of `psis` in one call
+        (DESIGN.md section 12.4).  `psis`, `gates` ((Q, N) in API row order, or "diffusion") and the `gate_*` arguments are
+        `bundle_gated_many`'s, with its validation and errors.  The lattice's psi, gates, U, U* cache, query basis, `stats`,
+        `last` and receipts are not changed; of its state only U is read.
+
+        `settle=None`: query q gets the record of `set_query(psis[q], gates=G[q]); receipt()` with the current U held fixed
+        (`receipt_many`'s contract: the settle fields are the lattice's last settle).  `settle=True` or a dict with any of
+        {"dt": 1.0, "max_iters": 12, "tol": 1e-3}: the record of `set_query(...); settle(dt, max_iters, tol); receipt()`,
+        every query started from the lattice's current U (warm start, no inertia) and no settled state written back;
+        `cg_iters` / `residual` are the query's own settle, `t_ms` and `meta.last_settle_ms` its chunk's settle time divided
+        by the chunk's queries.  U*_q is `bundle_gated_many`'s solve (`tol`, `max_iters`): `ustar_iters` / `ustar_res` /
+        `ustar_converged` are the query's own, `ustar_cached` is False, `ustar_source` is "gated_panel".
+
+        `bundle_k=None` returns the Q records; an int returns `(records, bundles)`, the bundles being
+        `bundle_gated_many(psis, gates, bundle_k, alpha)`'s from the same solve, bit for bit.  `as_arrays=True` returns
+        `receipt_many`'s dict of arrays plus `ustar_iters`, `ustar_res`, with `settle` also `settle_iters`, `settle_res`, and
+        with `bundle_k` also `ids`, `score`, `align`.  Detail mode, OSCILLINK_RECEIPT_NULL_CAP, the secret and signature mode
+        and OSCILLINK_RECEIPT_DYNAMICS behave as in `receipt_many`.  The report goes to `last_receipt_gated` = {"iters",
+        "res", "converged", "settle_iters", "settle_res" (None without `settle`), "gates" (as `last_bundle_gated`)}."""
+        if self._has_comm:
+            raise NotImplementedError("receipt_gated_many: lattices with a communicator (sharded / multi-rank) are not "
+                                      "supported")
+        if self._chain_nodes is not None:
+            raise NotImplementedError("receipt_gated_many: a lattice with a chain of its own is not supported "
+                                      "(clear_chain first)")
+        P = rc.check_queries(psis, self.D, finite=False)
+        Q = int(P.shape[0])
+        diffusion = isinstance(gates, str)
+        if diffusion:
+            if gates != "diffusion":
+                raise ValueError(f"gates must be 'diffusion' or a ({Q}, {self.N}) array, got {gates!r}")
+            if not float(gate_gamma) > 0:
+                raise ValueError("gate_gamma must be > 0 for SPD")
+            if gate_method not in ("direct", "cg"):
+                raise ValueError(f"gate_method must be 'direct' or 'cg', got {gate_method!r}")
+            if int(gate_max_iters) < 1:
+                raise ValueError("gate_max_iters must be >= 1")
+            G = nat.result_array((Q, self.N)) if Q > 0 else np.zeros((0, self.N), dtype=np.float32)
+        else:
+            G = self._check_gate_rows(gates)
+            if G.shape[0] != Q:
+                raise ValueError(f"gates must be a ({Q}, {self.N}) array, got shape {G.shape}")
+            for q in range(Q):
+                if not np.all(np.isfinite(G[q])):
+                    raise ValueError(f"query {q}: gates must be finite")
+                if np.any(G[q] < 0):
+                    raise ValueError(f"query {q}: gates must be >= 0")
+        if int(max_iters) < 1:
+            raise ValueError("max_iters must be >= 1")
+        st = None
+        if settle is not None and settle is not False:
+            st = dict(self._GATED_SETTLE_DEFAULTS)
+            if settle is not True:
+                if not isinstance(settle, dict):
+                    raise ValueError("settle must be None, True or a dict of dt / max_iters / tol")
+                unknown = sorted(set(settle) - set(st))
+                if unknown:
+                    raise ValueError(f"settle: unknown keys {unknown}")
+                st.update(settle)
+            if not float(st["dt"]) > 0:
+                raise ValueError("settle: dt must be > 0")
+            if int(st["max_iters"]) < 1:
+                raise ValueError("settle: max_iters must be >= 1")
+        if bundle_k is not None and int(bundle_k) < 0:
+            raise ValueError("bundle_k must be None or >= 0")
+        with_bundle = bundle_k is not None
+        kk = min(int(bundle_k), self.N) if with_bundle else 0
+        full = self._receipt_detail != "light"
+        cap_val = rc.null_cap()
+        ra = rc.ReceiptArrays(Q, (min(cap_val, self.N) if cap_val > 0 else self.N) if full else 0, settle=st is not None)
+        ids = np.zeros((Q, kk), dtype=np.int32)
+        score = np.zeros((Q, kk), dtype=np.float32)
+        align = np.zeros((Q, kk), dtype=np.float32)
+        iters = np.zeros(Q, dtype=np.int32)
+        res = np.zeros(Q, dtype=np.float32)
+        settle_ms, solve_ms = np.zeros(Q, dtype=np.float64), np.zeros(Q, dtype=np.float64)
+        if Q > 0:
+            self._push_params()
+            s_args = (1, float(st["dt"]), int(st["max_iters"]), float(st["tol"])) if st else (0, 1.0, 1, 0.0)
+            self._call("osc_receipt_gated_many", nat.f32(P), Q, nat.f32(G), int(diffusion), float(gate_beta),
+                       float(gate_gamma), 1 if gate_method == "cg" else 0, float(gate_tol), int(gate_max_iters), float(tol),
+                       int(max_iters), *s_args, int(full), 3.0, cap_val, kk, float(alpha), 0.5,
+                       *([] if st else [None, None]), *ra.pointers(), nat.i32(ids), nat.f32(score), nat.f32(align),
+                       nat.i32(iters), nat.f32(res), settle_ms.ctypes.data_as(nat.c_f64p), solve_ms.ctypes.data_as(nat.c_f64p))
+        ra.round_sums()
+        if diffusion:
+            bad = np.nonzero(~np.all(np.isfinite(G), axis=1))[0]
+            if bad.size:
+                import warnings
+
+                warnings.warn(f"diffusion_gates_many: the screened-diffusion solve of query {int(bad[0])} produced "
+                              "non-finite values; returned as computed, like the reference's cg path", RuntimeWarning,
+                              stacklevel=2)
+        converged = res <= np.float32(tol)
+        self.last_receipt_gated = {"iters": iters, "res": res, "converged": converged,
+                                   "settle_iters": ra.settle[0] if st else None,
+                                   "settle_res": ra.settle[1] if st else None, "gates": G if diffusion else None}
+        self._log("receipt_gated_many", {"Q": Q, "receipt_detail": self._receipt_detail, "settle": st is not None,
+                                         "bundle_k": kk if with_bundle else None,
+                                         "gates": "diffusion" if diffusion else "given",
+                                         "iters_max": int(iters.max()) if Q else 0,
+                                         "converged": int(np.count_nonzero(converged)), "null_points": ra.kept})
+        if as_arrays:
+            out = {**ra.scalar_arrays(), **ra.null_arrays(), "ustar_iters": iters, "ustar_res": res}
+            if with_bundle:
+                out.update(ids=ids, score=score, align=align)
+            return out
+        bundles = [rc.bundle_dicts(ids[q], score[q], align[q]) for q in range(Q)]
+        if Q == 0:
+            return ([], []) if with_bundle else []
+        # everything but psi, the gates, the energies, the null points, the settle and the ustar fields is shared by the batch
+        nnz, _, _ = self.graph_stats()
+        adj_sig = hashlib.sha256(np.ascontiguousarray(self._edge_prefix()).tobytes()).hexdigest()
+        sig_rest = {"lam": [self.lamG, self.lamC, self.lamQ, self.lamP], "chain_present": False, "chain_len": 0,
+                    "k": self._kneighbors, "detk": self._deterministic_k, "adj": adj_sig}
+        degree, signed = rc.degree_stats(nnz, self.N), self._signed_settings()
+        last = self._last_settle_fields()
+        dyn = self._last_dynamics if os.getenv("OSCILLINK_RECEIPT_DYNAMICS", "0").strip().lower() in {"1", "true", "yes"} \
+            else None
+        out = []
+        for q in range(Q):
+            sig = self._signature_digest({"psi": np.round(P[q], 6).tolist(), **sig_rest}, G[q])
+            dH = float(ra.sums[0, q])
+            ustar = {"ustar_iters": int(iters[q]), "ustar_res": float(res[q]), "ustar_converged": bool(converged[q])}
+            fields = last if st is None else {"cg_iters": int(ra.settle[0][q]), "residual": float(ra.settle[1][q]),
+                                              "t_ms": float(settle_ms[q])}
+            nulls, tot = ra.nulls(q)
+            meta = rc.meta(ustar_cached=False, ustar_solves=self.stats["ustar_solves"],
+                           ustar_cache_hits=self.stats["ustar_cache_hits"], ustar=ustar, ustar_solve_ms=float(solve_ms[q]),
+                           ustar_source="gated_panel", graph_build_ms=self._graph_build_ms, last_settle_ms=fields["t_ms"],
+                           degree=degree, gates=rc.gate_stats(G[q]), state_sig=sig, receipt_detail=self._receipt_detail,
+                           null_points_summary=rc.null_summary(tot, cap_val))
+            rc.sign(meta, self._receipt_secret, self._signature_mode, state_sig=sig, deltaH=dH, ustar=ustar, **signed)
+            rec = rc.record(version=__version__, deltaH=dH, coh_drop_sum=ra.sums[1, q], anchor_pen_sum=ra.sums[2, q],
+                            query_term_sum=ra.sums[3, q], **fields, null_points=nulls, meta=meta)
+            if dyn:
+                meta["dynamics"] = dyn
+            out.append(rec)
+        return (out, bundles) if with_bundle else out
+
     def receipt_many(self, psis: np.ndarray, *, tol: float = 1e-4, max_iters: int = 256, as_arrays: bool = False,
                      chains=None, lamP: Optional[float] = None, chain_weights=None):
         """`receipt()` for each row of `psis` (Q x D), as if `set_query(psis[q]); receipt()` had run with the current U,
