@@ -1335,8 +1335,10 @@ int osc_receipt_gated_many(osc_handle h, const float* psis, int32_t Q, float* ga
     if (Q > 0 && k > 0 && (!ids || !score || !align)) throw Invalid("osc_receipt_gated_many: NULL buffer");
     query_receipt_gated_many(l, psis, Q, gates, diffusion, gate_beta, gate_gamma, gate_method, gate_tol, gate_max_iters, tol,
                              max_iters, settle, dt, settle_max_iters, settle_tol, detail, z_th, null_cap, k, alpha, lambda_div,
-                             settle_iters, settle_res, dH, coh_sum, anchor_sum, query_sum, null_total, null_offsets, i_out, j_out,
-                             z_out, r_out, capacity, ids, score, align, iters_out, res_out, settle_ms, solve_ms);
+                             settle_iters, settle_res,
+                             ReceiptManyOut{dH, coh_sum, anchor_sum, query_sum, null_total, null_offsets, i_out, j_out, z_out, r_out,
+                                        capacity},
+                             ids, score, align, iters_out, res_out, settle_ms, solve_ms);
   });
 }
 
@@ -1350,8 +1352,9 @@ int osc_receipt_many(osc_handle h, const float* psis, int32_t Q, int32_t detail,
       throw Invalid("osc_receipt_many: NULL buffer");
     for (int64_t i = 0; i < (int64_t)Q * l.D; ++i)
       if (!std::isfinite(psis[i])) throw Invalid("osc_receipt_many: non-finite query");
-    query_receipt_many(l, psis, Q, detail, z_th, null_cap, dH, coh_sum, anchor_sum, query_sum, null_total, null_offsets,
-                       i_out, j_out, z_out, r_out, capacity);
+    query_receipt_many(l, psis, Q, detail, z_th, null_cap,
+                       ReceiptManyOut{dH, coh_sum, anchor_sum, query_sum, null_total, null_offsets, i_out, j_out, z_out, r_out,
+                                  capacity});
   });
 }
 
@@ -1363,8 +1366,8 @@ int osc_chain_receipt_many(osc_handle h, const float* psis, int32_t Q, const int
     if (Q > 0 && (!psis || !chain_offsets || !chain_nodes || !z_struct || !z_path || !r_struct || !r_path || !gain ||
                   !verdict || !weakest_k || !weakest_z))
       throw Invalid("osc_chain_receipt_many: NULL buffer");
-    query_chain_receipt_many(l, psis, Q, chain_offsets, chain_nodes, z_th, z_struct, z_path, r_struct, r_path, gain, verdict,
-                             weakest_k, weakest_z);
+    query_chain_receipt_many(l, psis, Q, chain_offsets, chain_nodes, z_th,
+                             ChainManyOut{z_struct, z_path, r_struct, r_path, gain, verdict, weakest_k, weakest_z});
   });
 }
 
@@ -1385,8 +1388,9 @@ int osc_chain_prior_many(osc_handle h, const float* psis, int32_t Q, const int64
     if (Q > 0 && (!psis || !chain_offsets || !chain_nodes || !z_struct || !z_path || !r_struct || !r_path || !gain ||
                   !verdict || !weakest_k || !weakest_z || !prior_res || !prior_iters))
       throw Invalid("osc_chain_prior_many: NULL buffer");
-    query_chain_prior_many(l, psis, Q, chain_offsets, chain_nodes, chain_weights, lamP, tol, max_iters, z_th, z_struct, z_path,
-                           r_struct, r_path, gain, verdict, weakest_k, weakest_z, prior_res, prior_iters);
+    query_chain_prior_many(l, psis, Q, chain_offsets, chain_nodes, chain_weights, lamP, tol, max_iters, z_th,
+                           ChainManyOut{z_struct, z_path, r_struct, r_path, gain, verdict, weakest_k, weakest_z}, prior_res,
+                           prior_iters);
   });
 }
 
@@ -1419,7 +1423,8 @@ int osc_receipt_prior_many(osc_handle h, const float* psis, int32_t Q, const int
     for (int64_t i = 0; i < (int64_t)Q * l.D; ++i)
       if (!std::isfinite(psis[i])) throw Invalid("osc_receipt_prior_many: non-finite query");
     query_receipt_prior_many(l, psis, Q, chain_offsets, chain_nodes, chain_weights, lamP, tol, max_iters, detail, z_th, null_cap,
-                             dH, coh_sum, anchor_sum, query_sum, null_total, null_offsets, i_out, j_out, z_out, r_out, capacity,
+                             ReceiptManyOut{dH, coh_sum, anchor_sum, query_sum, null_total, null_offsets, i_out, j_out, z_out, r_out,
+                                        capacity},
                              prior_res, prior_iters);
   });
 }

@@ -535,19 +535,32 @@ void require_graph(L& h);
 // osc_query.hip (include/oscillink_hip.h: osc_query_basis, osc_get_query_basis, osc_bundle_many, osc_mmr_many)
 void query_basis_solve(L& l, float tol, int32_t max_iters, float scale, bool fresh, int32_t* iters, float* res, double* ms);
 void query_basis_download(L& l, float* X_out, float* x_out);
-void query_receipt_many(L& l, const float* psis, int32_t Q, int32_t detail, float z_th, int32_t null_cap, double* dH,
-                        double* coh_sum, double* anchor_sum, double* query_sum, int32_t* null_total, int64_t* null_offsets,
-                        int32_t* i_out, int32_t* j_out, float* z_out, float* r_out, int64_t capacity);
+// the caller's arrays of a receipt batch (osc_receipt_many's outputs): four sums and the null-point count per query, then the
+// kept null points of all queries at null_offsets, `capacity` of them at most
+struct ReceiptManyOut {
+  double *dH, *coh_sum, *anchor_sum, *query_sum;
+  int32_t* null_total;
+  int64_t* null_offsets;
+  int32_t *i, *j;
+  float *z, *r;
+  int64_t capacity;
+};
+// the caller's arrays of a chain-receipt batch (osc_chain_receipt_many's outputs): four values per chain edge, four per query
+struct ChainManyOut {
+  float *z_struct, *z_path, *r_struct, *r_path;
+  double* gain;
+  int32_t *verdict, *weakest_k;
+  float* weakest_z;
+};
+void query_receipt_many(L& l, const float* psis, int32_t Q, int32_t detail, float z_th, int32_t null_cap, const ReceiptManyOut& o);
 void query_chain_receipt_many(L& l, const float* psis, int32_t Q, const int64_t* chain_offsets, const int32_t* chain_nodes,
-                              float z_th, float* z_struct, float* z_path, float* r_struct, float* r_path, double* gain,
-                              int32_t* verdict, int32_t* weakest_k, float* weakest_z);
+                              float z_th, const ChainManyOut& o);
 // osc_query_basis_shifted / osc_chain_prior_many
 void query_basis_shifted_solve(L& l, float lamP, float tol, int32_t max_iters, float scale, bool fresh, int32_t* iters,
                                float* res, double* ms);
 void query_chain_prior_many(L& l, const float* psis, int32_t Q, const int64_t* chain_offsets, const int32_t* chain_nodes,
-                            const float* chain_weights, float lamP, float tol, int32_t max_iters, float z_th, float* z_struct,
-                            float* z_path, float* r_struct, float* r_path, double* gain, int32_t* verdict, int32_t* weakest_k,
-                            float* weakest_z, float* prior_res, int32_t* prior_iters);
+                            const float* chain_weights, float lamP, float tol, int32_t max_iters, float z_th,
+                            const ChainManyOut& o, float* prior_res, int32_t* prior_iters);
 // sum (A - B) . M (A - B) with the stationary operator (osc_api.hip; receipts.py:21-25)
 double quad_form_of_difference(L& l, const float* A, const float* B);
 // osc_bundle_prior_many
@@ -558,9 +571,7 @@ void query_bundle_prior_many(L& l, const float* psis, int32_t Q, const int64_t* 
 // osc_receipt_prior_many
 void query_receipt_prior_many(L& l, const float* psis, int32_t Q, const int64_t* chain_offsets, const int32_t* chain_nodes,
                               const float* chain_weights, float lamP, float tol, int32_t max_iters, int32_t detail, float z_th,
-                              int32_t null_cap, double* dH, double* coh_sum, double* anchor_sum, double* query_sum,
-                              int32_t* null_total, int64_t* null_offsets, int32_t* i_out, int32_t* j_out, float* z_out,
-                              float* r_out, int64_t capacity, float* prior_res, int32_t* prior_iters);
+                              int32_t null_cap, const ReceiptManyOut& o, float* prior_res, int32_t* prior_iters);
 void query_bundle_many(L& l, const float* psis, int32_t Q, int32_t k, float alpha, float lambda_div, int32_t* ids,
                        float* score, float* align);
 void query_mmr_many(L& l, const float* scores, int32_t Q, int32_t k, float lambda_div, int32_t* ids);
@@ -577,10 +588,8 @@ void query_receipt_gated_many(L& l, const float* psis, int32_t Q, float* gates, 
                               float gate_gamma, int32_t gate_method, float gate_tol, int32_t gate_max_iters, float tol,
                               int32_t max_iters, int32_t settle, float dt, int32_t settle_max_iters, float settle_tol,
                               int32_t detail, float z_th, int32_t null_cap, int32_t k, float alpha, float lambda_div,
-                              int32_t* settle_iters, float* settle_res, double* dH, double* coh_sum, double* anchor_sum,
-                              double* query_sum, int32_t* null_total, int64_t* null_offsets, int32_t* i_out, int32_t* j_out,
-                              float* z_out, float* r_out, int64_t capacity, int32_t* ids, float* score, float* align,
-                              int32_t* iters_out, float* res_out, double* settle_ms, double* solve_ms);
+                              int32_t* settle_iters, float* settle_res, const ReceiptManyOut& o, int32_t* ids, float* score,
+                              float* align, int32_t* iters_out, float* res_out, double* settle_ms, double* solve_ms);
 
 struct ProfScope {
   L& h;

@@ -1,6 +1,15 @@
-// Multi-query bundles and receipts (DESIGN.md sections 11 and 12): the query basis solve and the batched bundle / MMR /
-// receipt drivers behind osc_query_basis, osc_get_query_basis, osc_bundle_many, osc_mmr_many and osc_receipt_many (see
-// osc_internal.hpp); further down the chain receipts (12.1), per-query chain priors (12.2) and bundles under them (11.1).
+// Multi-query bundles and receipts (DESIGN.md sections 11, 12 and 17): the query basis solves (osc_query_basis,
+// osc_query_basis_shifted, osc_get_query_basis) and the drivers of the nine batched calls (see osc_internal.hpp), in this order:
+// osc_bundle_many and osc_mmr_many (11), osc_receipt_many (12), osc_chain_receipt_many (12.1), the three calls under per-query
+// chain priors -- osc_chain_prior_many (12.2), osc_bundle_prior_many (11.1), osc_receipt_prior_many (12.3) -- osc_gates_many
+// (17), and the two under per-query gates, osc_bundle_gated_many (11.2, also osc_ustar_gated_many) and osc_receipt_gated_many
+// (12.4).
+//
+// Each step of a chunk has one home, in the anonymous namespaces ahead of its first driver: stage_queries (with stage_pass_psi
+// on request) and launch_query_dots; bundle_alloc and bundle_tail; rm_col_base, receipt_call_terms, receipt_light_chunk and
+// receipt_null_stage; chain_upload_paths, chain_upload_units and chain_edge_stage; chain_prior_panel_stage and its call
+// prelude; gated_call_check, gated_call_setup, gated_ustar_solve and gated_bundle_stage.  The callers' output arrays travel as
+// ReceiptManyOut and ChainManyOut.
 //
 // For the lattice's graph, gates, chain and lambdas, U*(psi) = X + x psi^T with M X = lamG Y and M x = lamQ B, so one
 // basis serves every query: a batch is one GEMM (query dots), one pass over the graph (coherence drop), per-query column
@@ -91,6 +100,118 @@ void mmr_many_run(L& l, int32_t qs, int32_t nq, int32_t kk, float lambda_div) {
     }
     launch_mmr_many_argmax(m, step, l.stream);
   }
+}
+
+// the basis's own residual for one query: |r_X| + |psi|_inf |r_x|, NaN for a psi that holds one
+float chain_prior_base_res(const float* psi, int32_t D, float res_X, float res_x) {
+  float pinf = 0.f;
+  for (int32_t d = 0; d < D; ++d) {
+    const float v = std::fabs(psi[d]);
+    pinf = (v > pinf || v != v) ? v : pinf;
+  }
+  return res_X + pinf * res_x;
+}
+
+// the rows of queries [c0, c0 + nq) into q.cm_psi at pitch ld (through hpsi)
+void stage_psi_rows(L& l, const float* psis, int32_t c0, int32_t nq, std::vector<float>& hpsi) {
+  auto& q = l.query;
+  hpsi.assign((size_t)nq * l.ld, 0.f);
+  for (int32_t t = 0; t < nq; ++t)
+    std::copy(psis + (size_t)(c0 + t) * l.D, psis + (size_t)(c0 + t + 1) * l.D, hpsi.data() + (size_t)t * l.ld);
+  q.cm_psi.alloc(hpsi.size());
+  HIP_CHECK(hipMemcpyAsync(q.cm_psi.p, hpsi.data(), hpsi.size() * 4, hipMemcpyHostToDevice, l.stream));
+}
+
+// what a chain-prior pass stages beside its queries: their rows in q.cm_psi and, in base_res, the basis's own residual per query
+struct PassPsi {
+  float res_X, res_x;
+  std::vector<float>& base_res;
+};
+
+void stage_pass_psi(L& l, const float* psis, int32_t c0, int32_t nq, const PassPsi& pp, std::vector<float>& hpsi) {
+  stage_psi_rows(l, psis, c0, nq, hpsi);
+  pp.base_res.assign((size_t)nq, 0.f);
+  for (int32_t t = 0; t < nq; ++t)
+    pp.base_res[(size_t)t] = chain_prior_base_res(psis + (size_t)(c0 + t) * l.D, l.D, pp.res_X, pp.res_x);
+}
+
+// host vectors the query staging reuses from chunk to chunk
+struct QueryStageScratch {
+  std::vector<float> hpsi, bt;
+  std::vector<double> pn2, pinv;
+};
+
+// The query staging of a chunk or pass, queries [c0, c0 + nq): with pp stage_pass_psi first; |psi|^2 and 1 / (|psi| + 1e-12)
+// into q.pn2 and q.pinv and, with_bt, the query-dot GEMM's zero-padded operand into q.Bt (the caller has sized the three for a
+// chunk)
+void stage_queries(L& l, const float* psis, int32_t c0, int32_t nq, bool with_bt, QueryStageScratch& st,
+                   const PassPsi* pp = nullptr) {
+  auto& q = l.query;
+  const int32_t D = l.D, kpad = query_kpad(D);
+  if (pp) stage_pass_psi(l, psis, c0, nq, *pp, st.hpsi);
+  st.pn2.assign((size_t)nq, 0.0);
+  st.pinv.assign((size_t)nq, 0.0);
+  if (with_bt) st.bt.assign((size_t)query_qpad(nq) * kpad, 0.f);
+  for (int32_t t = 0; t < nq; ++t) {
+    const float* p = psis + (size_t)(c0 + t) * D;
+    double s = 0.0;
+    for (int32_t d = 0; d < D; ++d) s += (double)p[d] * (double)p[d];
+    st.pn2[(size_t)t] = s;
+    st.pinv[(size_t)t] = 1.0 / (std::sqrt(s) + 1e-12);
+    if (with_bt) std::copy(p, p + D, st.bt.data() + (size_t)t * kpad);
+  }
+  if (with_bt) HIP_CHECK(hipMemcpyAsync(q.Bt.p, st.bt.data(), st.bt.size() * 4, hipMemcpyHostToDevice, l.stream));
+  HIP_CHECK(hipMemcpyAsync(q.pn2.p, st.pn2.data(), (size_t)nq * 8, hipMemcpyHostToDevice, l.stream));
+  HIP_CHECK(hipMemcpyAsync(q.pinv.p, st.pinv.data(), (size_t)nq * 8, hipMemcpyHostToDevice, l.stream));
+}
+
+// section 11's query dots of the nq queries staged in q.Bt / q.pn2 / q.pinv against the basis in slot b (l.query, or
+// l.query.shifted) into q.pm and q.align
+template <class Slot>
+void launch_query_dots(L& l, const Slot& b, int32_t qs, int32_t nq) {
+  auto& q = l.query;
+  QueryGemmArgs g{};
+  g.A = b.X.p;
+  g.Bt = q.Bt.p;
+  g.N = (int32_t)l.N;
+  g.D = l.D;
+  g.ld = l.ld;
+  g.kpad = query_kpad(l.D);
+  g.qs = qs;
+  g.nq = nq;
+  g.mode = 0;
+  g.x4 = b.x4.p;
+  g.xn2 = b.xn2.p;
+  g.sqrt_deg = l.sqrt_deg.p;
+  g.pn2 = q.pn2.p;
+  g.pinv = q.pinv.p;
+  g.align = q.align.p;
+  g.p = q.pm.p;
+  launch_query_gemm(g, l.stream);
+}
+
+// the buffers of bundle_tail, once per call
+void bundle_alloc(L& l, int32_t kk) {
+  auto& q = l.query;
+  ensure_yn(l);
+  q.part.alloc((size_t)query_stat_parts((int32_t)l.N) * kQueryChunk);
+  q.stats.alloc(kQueryChunk);
+  q.out_score.alloc((size_t)kQueryChunk * kk);
+  q.out_align.alloc((size_t)kQueryChunk * kk);
+}
+
+// The tail of a bundle chunk, queries [c0, c0 + nq) with their coh in q.cs and alignment in q.align (N x qs): the score, the
+// batched MMR, the pack and the three copies out.  The caller syncs.
+void bundle_tail(L& l, int32_t qs, int32_t nq, int32_t c0, int32_t kk, float alpha, float lambda_div, int32_t* ids,
+                 float* score, float* align) {
+  auto& q = l.query;
+  launch_query_score(q.cs.p, q.align.p, (int32_t)l.N, qs, nq, (double)alpha, q.part.p, q.stats.p, l.stream);
+  mmr_many_run(l, qs, nq, kk, lambda_div);
+  launch_query_pack(q.cs.p, q.align.p, q.chosen_row.p, qs, nq, kk, q.out_score.p, q.out_align.p, l.stream);
+  const size_t m = (size_t)nq * kk, off = (size_t)c0 * kk;
+  HIP_CHECK(hipMemcpyAsync(ids + off, q.chosen_api.p, m * 4, hipMemcpyDeviceToHost, l.stream));
+  HIP_CHECK(hipMemcpyAsync(score + off, q.out_score.p, m * 4, hipMemcpyDeviceToHost, l.stream));
+  HIP_CHECK(hipMemcpyAsync(align + off, q.out_align.p, m * 4, hipMemcpyDeviceToHost, l.stream));
 }
 
 }  // namespace
@@ -268,68 +389,23 @@ void query_bundle_many(L& l, const float* psis, int32_t Q, int32_t k, float alph
   const int32_t kk = (int32_t)std::min<int64_t>(std::max(k, 0), l.N);
   if (Q <= 0 || kk <= 0) return;
   auto& q = l.query;
-  ensure_yn(l);
-  const int32_t kpad = query_kpad(l.D);
+  bundle_alloc(l, kk);
   const int32_t N = (int32_t)l.N;
-  q.Bt.alloc((size_t)query_qpad(kQueryChunk) * kpad);
+  q.Bt.alloc((size_t)query_qpad(kQueryChunk) * query_kpad(l.D));
   q.pn2.alloc(kQueryChunk);
   q.pinv.alloc(kQueryChunk);
-  const int nbs = query_stat_parts(N);
-  q.part.alloc((size_t)nbs * kQueryChunk);
-  q.stats.alloc(kQueryChunk);
-  q.out_score.alloc((size_t)kQueryChunk * kk);
-  q.out_align.alloc((size_t)kQueryChunk * kk);
-  std::vector<float> bt;
-  std::vector<double> pn2, pinv;
+  QueryStageScratch st;
   for (int32_t c0 = 0; c0 < Q; c0 += kQueryChunk) {
     const int32_t nq = std::min<int32_t>(kQueryChunk, Q - c0);
-    const int32_t qs = query_qs(nq), qpad = query_qpad(nq);
+    const int32_t qs = query_qs(nq);
     q.align.alloc((size_t)N * qs);
     q.pm.alloc((size_t)N * qs);
     q.cs.alloc((size_t)N * qs);
-    bt.assign((size_t)qpad * kpad, 0.f);
-    pn2.assign((size_t)nq, 0.0);
-    pinv.assign((size_t)nq, 0.0);
-    for (int32_t t = 0; t < nq; ++t) {
-      const float* p = psis + (size_t)(c0 + t) * l.D;
-      double s = 0.0;
-      for (int32_t c = 0; c < l.D; ++c) {
-        bt[(size_t)t * kpad + c] = p[c];
-        s += (double)p[c] * (double)p[c];
-      }
-      pn2[(size_t)t] = s;
-      pinv[(size_t)t] = 1.0 / (std::sqrt(s) + 1e-12);
-    }
-    HIP_CHECK(hipMemcpyAsync(q.Bt.p, bt.data(), bt.size() * 4, hipMemcpyHostToDevice, l.stream));
-    HIP_CHECK(hipMemcpyAsync(q.pn2.p, pn2.data(), (size_t)nq * 8, hipMemcpyHostToDevice, l.stream));
-    HIP_CHECK(hipMemcpyAsync(q.pinv.p, pinv.data(), (size_t)nq * 8, hipMemcpyHostToDevice, l.stream));
-    QueryGemmArgs g{};
-    g.A = q.X.p;
-    g.Bt = q.Bt.p;
-    g.N = N;
-    g.D = l.D;
-    g.ld = l.ld;
-    g.kpad = kpad;
-    g.qs = qs;
-    g.nq = nq;
-    g.mode = 0;
-    g.x4 = q.x4.p;
-    g.xn2 = q.xn2.p;
-    g.sqrt_deg = l.sqrt_deg.p;
-    g.pn2 = q.pn2.p;
-    g.pinv = q.pinv.p;
-    g.align = q.align.p;
-    g.p = q.pm.p;
-    launch_query_gemm(g, l.stream);
+    stage_queries(l, psis, c0, nq, true, st);
+    launch_query_dots(l, q, qs, nq);
     launch_query_coh(l.ell_col.p, l.ell_a.p, l.deg.p, l.width, N, l.lamC, q.s.p, q.c0.p, q.c2.p, q.pn2.p, q.pm.p, qs, nq,
                      q.cs.p, l.stream);
-    launch_query_score(q.cs.p, q.align.p, N, qs, nq, (double)alpha, q.part.p, q.stats.p, l.stream);
-    mmr_many_run(l, qs, nq, kk, lambda_div);
-    launch_query_pack(q.cs.p, q.align.p, q.chosen_row.p, qs, nq, kk, q.out_score.p, q.out_align.p, l.stream);
-    const size_t m = (size_t)nq * kk, off = (size_t)c0 * kk;
-    HIP_CHECK(hipMemcpyAsync(ids + off, q.chosen_api.p, m * 4, hipMemcpyDeviceToHost, l.stream));
-    HIP_CHECK(hipMemcpyAsync(score + off, q.out_score.p, m * 4, hipMemcpyDeviceToHost, l.stream));
-    HIP_CHECK(hipMemcpyAsync(align + off, q.out_align.p, m * 4, hipMemcpyDeviceToHost, l.stream));
+    bundle_tail(l, qs, nq, c0, kk, alpha, lambda_div, ids, score, align);
     sync(l);
   }
 }
@@ -366,6 +442,20 @@ namespace {
 
 size_t rm_sum_size(const L& l) { return std::max<size_t>((size_t)4 * l.ld + 3, kQueryChunk); }
 
+// RmColArgs as far as every column pass over the basis in slot b fills it alike
+template <class Slot>
+RmColArgs rm_col_base(const L& l, const Slot& b) {
+  RmColArgs c{};
+  c.X = b.X.p;
+  c.x4 = b.x4.p;
+  c.Mx = b.Mx.p;
+  c.N = (int32_t)l.N;
+  c.D = l.D;
+  c.ld = l.ld;
+  c.nb = rm_col_parts(l.N);
+  return c;
+}
+
 // the per-basis terms: M x, the D-vectors of the anchor / query sums and the scalars beside them; with full != 0 also the
 // per-slot |P_i - P_j|^2 of the null-point residuals
 // (q: the slot of the basis -- l.query with the handle's operator, l.query.shifted with M'; sc: the scratch, l.query)
@@ -395,16 +485,9 @@ void ensure_receipt_terms(L& l, Slot& q, const OpParams& op, bool full) {
   launch_rm_basis_rows(b, l.stream);
   if (need_d) q.rd_gen = q.gen;
   if (!need_sums) return;
-  RmColArgs c{};
-  c.X = q.X.p;
-  c.x4 = q.x4.p;
+  RmColArgs c = rm_col_base(l, q);
   c.Y = l.Y.p;
   c.B = l.B.p;
-  c.Mx = q.Mx.p;
-  c.N = (int32_t)l.N;
-  c.D = l.D;
-  c.ld = l.ld;
-  c.nb = rm_col_parts(l.N);
   sc.rpart.alloc((size_t)c.nb * 4 * l.ld);
   sc.rspart.alloc((size_t)c.nb * 3);
   sc.rsum.alloc(rm_sum_size(l));
@@ -443,16 +526,77 @@ double dot_f(const float* a, const double* b, int32_t D) {
 
 namespace {
 
-// The tail of a full-detail chunk, shared by osc_receipt_many and osc_receipt_prior_many: from the counted null points of the
-// chunk's nq queries (tot; zt = z per query in API row order, rj / rr the N x qs candidates) the kept records of each query
-// -- every null point, or the cap highest z -- into the caller's arrays at null_offsets.
-void receipt_null_stage(L& l, const char* fn, int32_t c0, int32_t nq, int32_t qs, int32_t null_cap,
-                        const std::vector<int32_t>& tot, const float* zt, const int32_t* rj, const float* rr,
-                        int32_t* null_total, int64_t* null_offsets, int32_t* i_out, int32_t* j_out, float* z_out, float* r_out,
-                        int64_t capacity) {
+// the per-call terms of a receipt batch on the basis in a slot
+struct ReceiptCallTerms {
+  double h0;
+  std::vector<double> h1;   // [ld]
+  std::vector<float> psi0;  // [ld] the handle's psi
+};
+
+// Per call, on the basis in slot b (l.query with lamP == 0, l.query.shifted with M' = M + lamP I): h1 = E0^T (M x) over
+// E0 = U - X - x psi0^T (left in q.U0), and h0 = tr(E0^T M E0) through the operator's quad form
+template <class Slot>
+ReceiptCallTerms receipt_call_terms(L& l, const Slot& b, float lamP) {
   auto& q = l.query;
-  const int32_t N = (int32_t)l.N;
+  ReceiptCallTerms ct{0.0, std::vector<double>((size_t)l.ld), std::vector<float>((size_t)l.ld, 0.f)};
+  HIP_CHECK(hipMemcpyAsync(ct.psi0.data(), l.psi.p, (size_t)l.ld * 4, hipMemcpyDeviceToHost, l.stream));
+  RmColArgs c = rm_col_base(l, b);
+  c.U = u_read(l);
+  c.psi0 = l.psi.p;
+  q.U0.alloc((size_t)l.N * l.ld);
+  c.U0 = q.U0.p;
+  q.rpart.alloc((size_t)c.nb * 4 * l.ld);
+  q.rsum.alloc(rm_sum_size(l));
+  c.part = q.rpart.p;
+  launch_rm_cols(c, 1, l.stream);
+  q.rfin.alloc((size_t)rm_finish_groups(c.nb) * 4 * l.ld);
+  launch_rm_colfinish(q.rpart.p, c.nb, l.ld, q.rsum.p, q.rfin.p, l.stream);
+  HIP_CHECK(hipMemcpyAsync(ct.h1.data(), q.rsum.p, ct.h1.size() * 8, hipMemcpyDeviceToHost, l.stream));
+  sync(l);
+  const ShiftedLamG shifted(l, lamP);  // (lamP == 0: the handle's own lamG)
+  ct.h0 = quad_form_of_difference(l, u_read(l), q.U0.p);
+  return ct;
+}
+
+// a chunk of a light-detail batch, queries [c0, c0 + nq): deltaH from dh (one value every `stride`), nothing else
+void receipt_light_chunk(L& l, const ReceiptManyOut& o, int32_t c0, int32_t nq, const double* dh, int stride) {
+  sync(l);
+  for (int32_t t = 0; t < nq; ++t) {
+    o.dH[c0 + t] = dh[(size_t)stride * t];
+    o.anchor_sum[c0 + t] = o.query_sum[c0 + t] = o.coh_sum[c0 + t] = 0.0;
+    o.null_total[c0 + t] = 0;
+    o.null_offsets[c0 + t + 1] = o.null_offsets[c0 + t];
+  }
+}
+
+// one full-detail chunk's null-point candidates, queries [c0, c0 + nq): z / j / r are N x qs in device row order, zt is the
+// nq x N block the stage transposes z into (API row order)
+struct NullChunk {
+  int32_t c0, nq, qs;
+  const float* z;
+  const int32_t* j;
+  const float* r;
+  float* zt;
+};
+
+// The tail of a full-detail chunk, shared by osc_receipt_many, osc_receipt_prior_many and osc_receipt_gated_many: the
+// transpose, the null count and the chunk's n_sums device sums (`sums`) to the host, where fill(const double*) writes them to
+// the caller's arrays; then the kept records of each query -- every null point, or the cap highest z -- into the caller's
+// arrays at null_offsets.  The caller has sized q.rtot, q.rsel and q.roff for a chunk.
+template <class Fill>
+void receipt_null_stage(L& l, const char* fn, const NullChunk& ch, int32_t null_cap, const double* sums, size_t n_sums,
+                        Fill fill, const ReceiptManyOut& o) {
+  auto& q = l.query;
+  const int32_t N = (int32_t)l.N, c0 = ch.c0, nq = ch.nq, qs = ch.qs;
   const int32_t* inv = permuted(l) ? l.inv_d.p : nullptr;
+  launch_rm_transpose(ch.z, inv, N, qs, nq, ch.zt, l.stream);
+  launch_rm_null_count(ch.zt, N, nq, q.rtot.p, l.stream);
+  std::vector<double> hsum(n_sums, 0.0);
+  std::vector<int32_t> tot((size_t)nq, 0);
+  HIP_CHECK(hipMemcpyAsync(hsum.data(), sums, n_sums * 8, hipMemcpyDeviceToHost, l.stream));
+  HIP_CHECK(hipMemcpyAsync(tot.data(), q.rtot.p, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
+  sync(l);
+  fill(hsum.data());
   std::vector<int32_t> sel, hi, hj;
   std::vector<int64_t> off;
   std::vector<float> hz, hr;
@@ -461,15 +605,15 @@ void receipt_null_stage(L& l, const char* fn, int32_t c0, int32_t nq, int32_t qs
   off.assign((size_t)nq, 0);
   int64_t dev_n = 0;
   for (int32_t t = 0; t < nq; ++t) {
-    null_total[c0 + t] = tot[(size_t)t];
+    o.null_total[c0 + t] = tot[(size_t)t];
     const bool capped = null_cap > 0 && tot[(size_t)t] > null_cap;
     sel[(size_t)t] = capped && null_cap <= kRmSelectMax;
     off[(size_t)t] = dev_n;
     dev_n += sel[(size_t)t] ? null_cap : tot[(size_t)t];
     const int64_t kept = capped ? null_cap : tot[(size_t)t];
-    null_offsets[c0 + t + 1] = null_offsets[c0 + t] + kept;
+    o.null_offsets[c0 + t + 1] = o.null_offsets[c0 + t] + kept;
   }
-  if (null_offsets[c0 + nq] > capacity) throw Invalid(std::string(fn) + ": capacity too small for the null points");
+  if (o.null_offsets[c0 + nq] > o.capacity) throw Invalid(std::string(fn) + ": capacity too small for the null points");
   if (dev_n == 0) return;
   q.roi.alloc((size_t)dev_n);
   q.roj.alloc((size_t)dev_n);
@@ -478,9 +622,9 @@ void receipt_null_stage(L& l, const char* fn, int32_t c0, int32_t nq, int32_t qs
   HIP_CHECK(hipMemcpyAsync(q.roff.p, off.data(), (size_t)nq * 8, hipMemcpyHostToDevice, l.stream));
   HIP_CHECK(hipMemcpyAsync(q.rsel.p, sel.data(), (size_t)nq * 4, hipMemcpyHostToDevice, l.stream));
   RmSelectArgs sa{};
-  sa.zt = zt;
-  sa.j = rj;
-  sa.r = rr;
+  sa.zt = ch.zt;
+  sa.j = ch.j;
+  sa.r = ch.r;
   sa.inv = inv;
   sa.off = q.roff.p;
   sa.sel = q.rsel.p;
@@ -503,30 +647,28 @@ void receipt_null_stage(L& l, const char* fn, int32_t c0, int32_t nq, int32_t qs
   HIP_CHECK(hipMemcpyAsync(hr.data(), q.ror.p, (size_t)dev_n * 4, hipMemcpyDeviceToHost, l.stream));
   sync(l);
   for (int32_t t = 0; t < nq; ++t) {
-    const int64_t src = off[(size_t)t], dst = null_offsets[c0 + t], kept = null_offsets[c0 + t + 1] - dst;
+    const int64_t src = off[(size_t)t], dst = o.null_offsets[c0 + t], kept = o.null_offsets[c0 + t + 1] - dst;
     std::vector<int64_t> order((size_t)(sel[(size_t)t] ? kept : tot[(size_t)t]));
     for (size_t k = 0; k < order.size(); ++k) order[k] = src + (int64_t)k;
     if (!sel[(size_t)t] && kept < (int64_t)order.size())  // a cap above the device selection's: the stable z sort here
       std::stable_sort(order.begin(), order.end(), [&](int64_t x, int64_t y) { return hz[(size_t)x] > hz[(size_t)y]; });
     for (int64_t k = 0; k < kept; ++k) {
       const size_t s = (size_t)order[(size_t)k];
-      if (i_out) i_out[dst + k] = hi[s];
-      if (j_out) j_out[dst + k] = hj[s];
-      if (z_out) z_out[dst + k] = hz[s];
-      if (r_out) r_out[dst + k] = hr[s];
+      if (o.i) o.i[dst + k] = hi[s];
+      if (o.j) o.j[dst + k] = hj[s];
+      if (o.z) o.z[dst + k] = hz[s];
+      if (o.r) o.r[dst + k] = hr[s];
     }
   }
 }
 
 }  // namespace
 
-void query_receipt_many(L& l, const float* psis, int32_t Q, int32_t detail, float z_th, int32_t null_cap, double* dH,
-                        double* coh_sum, double* anchor_sum, double* query_sum, int32_t* null_total, int64_t* null_offsets,
-                        int32_t* i_out, int32_t* j_out, float* z_out, float* r_out, int64_t capacity) {
+void query_receipt_many(L& l, const float* psis, int32_t Q, int32_t detail, float z_th, int32_t null_cap, const ReceiptManyOut& o) {
   require_basis(l);
   if (l.comm) throw Unsupported("osc_receipt_many: lattices with a communicator are not supported");
   if (Q <= 0) {
-    if (null_offsets) null_offsets[0] = 0;
+    if (o.null_offsets) o.null_offsets[0] = 0;
     return;
   }
   const bool full = detail != 0;
@@ -534,54 +676,30 @@ void query_receipt_many(L& l, const float* psis, int32_t Q, int32_t detail, floa
   ensure_receipt_basis(l, full);
   const int32_t D = l.D, N = (int32_t)l.N;
   const size_t n = (size_t)l.N;
-  // per call: h1 = E0^T (M x) over E0 = U - X - x psi0^T, and h0 = tr(E0^T M E0) through the operator's quad form
-  std::vector<float> psi0((size_t)l.ld, 0.f);
-  HIP_CHECK(hipMemcpyAsync(psi0.data(), l.psi.p, (size_t)l.ld * 4, hipMemcpyDeviceToHost, l.stream));
-  RmColArgs c{};
-  c.X = q.X.p;
-  c.x4 = q.x4.p;
-  c.Mx = q.Mx.p;
-  c.U = u_read(l);
-  c.psi0 = l.psi.p;
-  q.U0.alloc(n * l.ld);
-  c.U0 = q.U0.p;
-  c.N = N;
-  c.D = D;
-  c.ld = l.ld;
-  c.nb = rm_col_parts(l.N);
-  q.rpart.alloc((size_t)c.nb * 4 * l.ld);
-  q.rsum.alloc(rm_sum_size(l));
-  c.part = q.rpart.p;
-  launch_rm_cols(c, 1, l.stream);
-  q.rfin.alloc((size_t)rm_finish_groups(c.nb) * 4 * l.ld);
-  launch_rm_colfinish(q.rpart.p, c.nb, l.ld, q.rsum.p, q.rfin.p, l.stream);
-  std::vector<double> h1((size_t)l.ld);
-  HIP_CHECK(hipMemcpyAsync(h1.data(), q.rsum.p, h1.size() * 8, hipMemcpyDeviceToHost, l.stream));
-  sync(l);
-  const double h0 = quad_form_of_difference(l, u_read(l), q.U0.p);
+  const ReceiptCallTerms ct = receipt_call_terms(l, q, 0.f);
   const double* a1 = q.rm_vec.data();
   const double* b1 = a1 + D;
   for (int32_t t = 0; t < Q; ++t) {
     const float* p = psis + (size_t)t * D;
     double dh1 = 0.0, dd = 0.0, pp = 0.0;
     for (int32_t d = 0; d < D; ++d) {
-      const double dl = (double)p[d] - (double)psi0[(size_t)d];
-      dh1 += dl * h1[(size_t)d];
+      const double dl = (double)p[d] - (double)ct.psi0[(size_t)d];
+      dh1 += dl * ct.h1[(size_t)d];
       dd += dl * dl;
       pp += (double)p[d] * (double)p[d];
     }
-    dH[t] = h0 - 2.0 * dh1 + dd * q.rm_h2;
+    o.dH[t] = ct.h0 - 2.0 * dh1 + dd * q.rm_h2;
     if (full) {
-      anchor_sum[t] = (double)l.lamG * (q.rm_a0 + 2.0 * dot_f(p, a1, D) + pp * q.rm_a2);
-      query_sum[t] = (double)l.lamQ * (q.rm_b0 + 2.0 * dot_f(p, b1, D) + pp * q.rm_b2);
+      o.anchor_sum[t] = (double)l.lamG * (q.rm_a0 + 2.0 * dot_f(p, a1, D) + pp * q.rm_a2);
+      o.query_sum[t] = (double)l.lamQ * (q.rm_b0 + 2.0 * dot_f(p, b1, D) + pp * q.rm_b2);
     } else {
-      anchor_sum[t] = query_sum[t] = coh_sum[t] = 0.0;
+      o.anchor_sum[t] = o.query_sum[t] = o.coh_sum[t] = 0.0;
     }
-    null_total[t] = 0;
+    o.null_total[t] = 0;
   }
-  null_offsets[0] = 0;
+  o.null_offsets[0] = 0;
   if (!full) {
-    for (int32_t t = 0; t < Q; ++t) null_offsets[t + 1] = 0;
+    for (int32_t t = 0; t < Q; ++t) o.null_offsets[t + 1] = 0;
     return;
   }
   // full detail: per chunk the query dots (GEMM), the fused row pass, then the null points per query
@@ -595,53 +713,18 @@ void query_receipt_many(L& l, const float* psis, int32_t Q, int32_t detail, floa
   q.rtot.alloc(kQueryChunk);
   q.rsel.alloc(kQueryChunk);
   q.roff.alloc(kQueryChunk);
-  const int32_t* inv = permuted(l) ? l.inv_d.p : nullptr;
-  std::vector<float> bt;
-  std::vector<double> pn2, pinv, csum;
-  std::vector<int32_t> tot;
+  QueryStageScratch st;
   for (int32_t c0 = 0; c0 < Q; c0 += kQueryChunk) {
     const int32_t nq = std::min<int32_t>(kQueryChunk, Q - c0);
-    const int32_t qs = query_qs(nq), qpad = query_qpad(nq);
+    const int32_t qs = query_qs(nq);
     q.align.alloc(n * qs);
     q.pm.alloc(n * qs);
     q.rz.alloc(n * qs);
     q.rj.alloc(n * qs);
     q.rr.alloc(n * qs);
     q.zt.alloc(n * nq);
-    bt.assign((size_t)qpad * kpad, 0.f);
-    pn2.assign((size_t)nq, 0.0);
-    pinv.assign((size_t)nq, 0.0);
-    for (int32_t t = 0; t < nq; ++t) {
-      const float* p = psis + (size_t)(c0 + t) * D;
-      double s = 0.0;
-      for (int32_t d = 0; d < D; ++d) {
-        bt[(size_t)t * kpad + d] = p[d];
-        s += (double)p[d] * (double)p[d];
-      }
-      pn2[(size_t)t] = s;
-      pinv[(size_t)t] = 1.0 / (std::sqrt(s) + 1e-12);
-    }
-    HIP_CHECK(hipMemcpyAsync(q.Bt.p, bt.data(), bt.size() * 4, hipMemcpyHostToDevice, l.stream));
-    HIP_CHECK(hipMemcpyAsync(q.pn2.p, pn2.data(), (size_t)nq * 8, hipMemcpyHostToDevice, l.stream));
-    HIP_CHECK(hipMemcpyAsync(q.pinv.p, pinv.data(), (size_t)nq * 8, hipMemcpyHostToDevice, l.stream));
-    QueryGemmArgs g{};
-    g.A = q.X.p;
-    g.Bt = q.Bt.p;
-    g.N = N;
-    g.D = D;
-    g.ld = l.ld;
-    g.kpad = kpad;
-    g.qs = qs;
-    g.nq = nq;
-    g.mode = 0;
-    g.x4 = q.x4.p;
-    g.xn2 = q.xn2.p;
-    g.sqrt_deg = l.sqrt_deg.p;
-    g.pn2 = q.pn2.p;
-    g.pinv = q.pinv.p;
-    g.align = q.align.p;
-    g.p = q.pm.p;
-    launch_query_gemm(g, l.stream);
+    stage_queries(l, psis, c0, nq, true, st);
+    launch_query_dots(l, q, qs, nq);
     RmRowsArgs r{};
     r.col = l.ell_col.p;
     r.adj = l.ell_a.p;
@@ -666,141 +749,16 @@ void query_receipt_many(L& l, const float* psis, int32_t Q, int32_t detail, floa
     r.r = q.rr.p;
     launch_rm_rows(r, l.stream);
     launch_rm_colfinish(q.cohpart.p, nw, nq, q.rsum.p, q.cohfin.p, l.stream);
-    launch_rm_transpose(q.rz.p, inv, N, qs, nq, q.zt.p, l.stream);
-    launch_rm_null_count(q.zt.p, N, nq, q.rtot.p, l.stream);
-    csum.assign((size_t)nq, 0.0);
-    tot.assign((size_t)nq, 0);
-    HIP_CHECK(hipMemcpyAsync(csum.data(), q.rsum.p, (size_t)nq * 8, hipMemcpyDeviceToHost, l.stream));
-    HIP_CHECK(hipMemcpyAsync(tot.data(), q.rtot.p, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
-    sync(l);
-    for (int32_t t = 0; t < nq; ++t) coh_sum[c0 + t] = csum[(size_t)t];
-    receipt_null_stage(l, "osc_receipt_many", c0, nq, qs, null_cap, tot, q.zt.p, q.rj.p, q.rr.p, null_total, null_offsets, i_out,
-                       j_out, z_out, r_out, capacity);
+    receipt_null_stage(
+        l, "osc_receipt_many", NullChunk{c0, nq, qs, q.rz.p, q.rj.p, q.rr.p, q.zt.p}, null_cap, q.rsum.p, (size_t)nq,
+        [&](const double* csum) { std::copy(csum, csum + nq, o.coh_sum + c0); }, o);
   }
 }
 
 // ---- chain receipts -------------------------------------------------------------------------
-// chain_receipt(chain_q, z_th) of U*(psi_q) for Q (query, chain) pairs: per chunk the path structures (the lattice's own
-// chain once per call, else once per distinct chain of the chunk), the (query, edge) units, one gather kernel over them and
-// one finish kernel over the queries.  Nothing outlives the call but the scratch's allocation.
-void query_chain_receipt_many(L& l, const float* psis, int32_t Q, const int64_t* chain_offsets, const int32_t* chain_nodes,
-                              float z_th, float* z_struct, float* z_path, float* r_struct, float* r_path, double* gain,
-                              int32_t* verdict, int32_t* weakest_k, float* weakest_z) {
-  if (l.comm) throw Unsupported("osc_chain_receipt_many: lattices with a communicator are not supported");
-  require_basis(l);
-  if (Q <= 0) return;
-  int32_t where = 0;
-  switch (host::chain_many_check(chain_offsets, chain_nodes, Q, l.N, &where)) {
-    case 1:
-      throw Invalid("osc_chain_receipt_many: query " + std::to_string(where) + ": a chain has 2 to " +
-                    std::to_string(host::kCorpusMaxChain) + " nodes, at offsets that start from 0");
-    case 2:
-      throw Invalid("osc_chain_receipt_many: query " + std::to_string(where) + ": chain indices out of bounds");
-  }
-  auto& q = l.query;
-  const int32_t N = (int32_t)l.N, D = l.D;
-  const int32_t* dev = permuted(l) ? l.inv_h.data() : nullptr;
-  host::ChainManyPaths paths;
-  int32_t own = -1;
-  if (l.chain_present) {  // lattice.py:479-483: the lattice's own A_path, weights included, whatever the argument is
-    std::vector<int32_t> rows(l.chain_nodes);
-    if (dev)
-      for (int32_t& v : rows) v = dev[v];
-    own = paths.add(rows.data(), l.chain_w.empty() ? nullptr : l.chain_w.data(), (int32_t)rows.size(), N);
-  }
-  auto upload_paths = [&]() {
-    q.cm_pcol.alloc(std::max<size_t>(paths.pcol.size(), 1));
-    q.cm_pa.alloc(std::max<size_t>(paths.pa.size(), 1));
-    if (paths.pcol.empty()) return;
-    HIP_CHECK(hipMemcpyAsync(q.cm_pcol.p, paths.pcol.data(), paths.pcol.size() * 4, hipMemcpyHostToDevice, l.stream));
-    HIP_CHECK(hipMemcpyAsync(q.cm_pa.p, paths.pa.data(), paths.pa.size() * 4, hipMemcpyHostToDevice, l.stream));
-  };
-  if (own >= 0) upload_paths();
-  q.cm_eoff.alloc((size_t)kQueryChunk + 1);
-  q.cm_gain.alloc(kQueryChunk);
-  q.cm_verdict.alloc(kQueryChunk);
-  q.cm_wk.alloc(kQueryChunk);
-  q.cm_wz.alloc(kQueryChunk);
-  std::vector<host::ChainManyUnit> units;
-  std::vector<int32_t> eoff;
-  std::vector<float> hpsi;
-  for (int32_t c0 = 0; c0 < Q; c0 += kQueryChunk) {
-    const int32_t nq = std::min<int32_t>(kQueryChunk, Q - c0);
-    if (own < 0) paths.clear();
-    host::chain_many_units(chain_offsets, chain_nodes, c0, nq, dev, N, own, paths, units, eoff);
-    if (own < 0) upload_paths();
-    const size_t nu = units.size();
-    hpsi.assign((size_t)nq * l.ld, 0.f);
-    for (int32_t t = 0; t < nq; ++t)
-      std::copy(psis + (size_t)(c0 + t) * D, psis + (size_t)(c0 + t + 1) * D, hpsi.data() + (size_t)t * l.ld);
-    q.cm_psi.alloc(hpsi.size());
-    q.cm_units.alloc(nu);
-    q.cm_edge.alloc(4 * nu);
-    q.cm_term.alloc(2 * nu);
-    HIP_CHECK(hipMemcpyAsync(q.cm_psi.p, hpsi.data(), hpsi.size() * 4, hipMemcpyHostToDevice, l.stream));
-    HIP_CHECK(hipMemcpyAsync(q.cm_units.p, units.data(), nu * sizeof(host::ChainManyUnit), hipMemcpyHostToDevice, l.stream));
-    HIP_CHECK(hipMemcpyAsync(q.cm_eoff.p, eoff.data(), eoff.size() * 4, hipMemcpyHostToDevice, l.stream));
-    CmEdgesArgs e{};
-    e.X = q.X.p;
-    e.x4 = q.x4.p;
-    e.Y = l.Y.p;
-    e.sqrt_deg = l.sqrt_deg.p;
-    e.col = l.ell_col.p;
-    e.adj = l.ell_a.p;
-    e.deg = l.deg.p;
-    e.psi = q.cm_psi.p;
-    e.units = q.cm_units.p;
-    e.pcol = q.cm_pcol.p;
-    e.pa = q.cm_pa.p;
-    e.width = l.width;
-    e.N = N;
-    e.D = D;
-    e.ld = l.ld;
-    e.n_units = (int64_t)nu;
-    e.lamC = l.lamC;
-    e.z_struct = q.cm_edge.p;
-    e.z_path = q.cm_edge.p + nu;
-    e.r_struct = q.cm_edge.p + 2 * nu;
-    e.r_path = q.cm_edge.p + 3 * nu;
-    e.term = q.cm_term.p;
-    e.zmax = q.cm_term.p + nu;
-    launch_cm_edges(e, l.stream);
-    CmFinishArgs f{};
-    f.eoff = q.cm_eoff.p;
-    f.term = e.term;
-    f.zmax = e.zmax;
-    f.nq = nq;
-    f.z_th = z_th;
-    f.gain = q.cm_gain.p;
-    f.verdict = q.cm_verdict.p;
-    f.weak_k = q.cm_wk.p;
-    f.weak_z = q.cm_wz.p;
-    launch_cm_finish(f, l.stream);
-    const int64_t at = host::chain_many_edge_at(chain_offsets, c0);  // the chunk's units are its queries' edges, in order
-    HIP_CHECK(hipMemcpyAsync(z_struct + at, e.z_struct, nu * 4, hipMemcpyDeviceToHost, l.stream));
-    HIP_CHECK(hipMemcpyAsync(z_path + at, e.z_path, nu * 4, hipMemcpyDeviceToHost, l.stream));
-    HIP_CHECK(hipMemcpyAsync(r_struct + at, e.r_struct, nu * 4, hipMemcpyDeviceToHost, l.stream));
-    HIP_CHECK(hipMemcpyAsync(r_path + at, e.r_path, nu * 4, hipMemcpyDeviceToHost, l.stream));
-    HIP_CHECK(hipMemcpyAsync(gain + c0, q.cm_gain.p, (size_t)nq * 8, hipMemcpyDeviceToHost, l.stream));
-    HIP_CHECK(hipMemcpyAsync(verdict + c0, q.cm_verdict.p, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
-    HIP_CHECK(hipMemcpyAsync(weakest_k + c0, q.cm_wk.p, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
-    HIP_CHECK(hipMemcpyAsync(weakest_z + c0, q.cm_wz.p, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
-    sync(l);  // (the host vectors above are reused by the next chunk)
-  }
-}
-
-// ---- per-query chain priors (DESIGN.md section 12.2) ------------------------------------------------------------------
 namespace {
 
-// host vectors the panel stage reuses from pass to pass
-struct CpHostScratch {
-  host::ChainPriorSystems sys;
-  std::vector<int32_t> hints, hnode;
-  std::vector<int64_t> hlongs;
-  std::map<int32_t, int32_t> column_of;
-};
-
-// what the panel stage of a pass leaves on the device (in l.query's cp_* buffers)
+// what the panel stage of a chain-prior pass leaves on the device (in l.query's cp_* buffers)
 struct CpPanelOut {
   const float* G;             // the Green's columns, slab-major
   const int32_t* q_sys;       // [nq]
@@ -816,6 +774,166 @@ struct CpPanelOut {
   const int32_t* kc;
   const float* kw;
   int32_t n_sys;
+};
+
+// the basis a chain call reads -- the resident one, or the shifted slot's -- with its residuals
+struct BasisView {
+  const float *X, *x4;
+  float res_X, res_x;
+};
+
+template <class Slot>
+BasisView basis_view(const Slot& s) {
+  return BasisView{s.X.p, s.x4.p, s.res_X, s.res_x};
+}
+
+// the per-chunk result buffers of chain_edge_stage, once per call
+void chain_scratch_alloc(L& l) {
+  auto& q = l.query;
+  q.cm_eoff.alloc((size_t)kQueryChunk + 1);
+  q.cm_gain.alloc(kQueryChunk);
+  q.cm_verdict.alloc(kQueryChunk);
+  q.cm_wk.alloc(kQueryChunk);
+  q.cm_wz.alloc(kQueryChunk);
+}
+
+void chain_upload_paths(L& l, const host::ChainManyPaths& paths) {
+  auto& q = l.query;
+  q.cm_pcol.alloc(std::max<size_t>(paths.pcol.size(), 1));
+  q.cm_pa.alloc(std::max<size_t>(paths.pa.size(), 1));
+  if (paths.pcol.empty()) return;
+  HIP_CHECK(hipMemcpyAsync(q.cm_pcol.p, paths.pcol.data(), paths.pcol.size() * 4, hipMemcpyHostToDevice, l.stream));
+  HIP_CHECK(hipMemcpyAsync(q.cm_pa.p, paths.pa.data(), paths.pa.size() * 4, hipMemcpyHostToDevice, l.stream));
+}
+
+// a chunk's (query, edge) units and per-query edge offsets to the device, with the edge scratch sized for them
+void chain_upload_units(L& l, const std::vector<host::ChainManyUnit>& units, const std::vector<int32_t>& eoff) {
+  auto& q = l.query;
+  const size_t nu = units.size();
+  q.cm_units.alloc(nu);
+  q.cm_edge.alloc(4 * nu);
+  q.cm_term.alloc(2 * nu);
+  HIP_CHECK(hipMemcpyAsync(q.cm_units.p, units.data(), nu * sizeof(host::ChainManyUnit), hipMemcpyHostToDevice, l.stream));
+  HIP_CHECK(hipMemcpyAsync(q.cm_eoff.p, eoff.data(), eoff.size() * 4, hipMemcpyHostToDevice, l.stream));
+}
+
+// The edge stage of a chunk, queries [c0, c0 + nq) with their rows in q.cm_psi, their nu units and the paths uploaded: the
+// gather kernel over the units on basis b -- with po the correction of a chain-prior pass on every gathered row -- the finish
+// kernel over the queries and the eight copies out.  The caller syncs.
+void chain_edge_stage(L& l, const BasisView& b, const CpPanelOut* po, int32_t c0, int32_t nq, size_t nu, float z_th,
+                      const int64_t* chain_offsets, const ChainManyOut& o) {
+  auto& q = l.query;
+  CmEdgesArgs e{};
+  if (po) {
+    e.G = po->G;
+    e.q_sys = po->q_sys;
+    e.sys_m = po->sys_m;
+    e.sys_col_at = po->sys_col_at;
+    e.sys_cols = po->sys_cols;
+    e.TV = q.cp_tv.p;
+    e.tv_at = po->tv_at;
+  }
+  e.X = b.X;
+  e.x4 = b.x4;
+  e.Y = l.Y.p;
+  e.sqrt_deg = l.sqrt_deg.p;
+  e.col = l.ell_col.p;
+  e.adj = l.ell_a.p;
+  e.deg = l.deg.p;
+  e.psi = q.cm_psi.p;
+  e.units = q.cm_units.p;
+  e.pcol = q.cm_pcol.p;
+  e.pa = q.cm_pa.p;
+  e.width = l.width;
+  e.N = (int32_t)l.N;
+  e.D = l.D;
+  e.ld = l.ld;
+  e.n_units = (int64_t)nu;
+  e.lamC = l.lamC;
+  e.z_struct = q.cm_edge.p;
+  e.z_path = q.cm_edge.p + nu;
+  e.r_struct = q.cm_edge.p + 2 * nu;
+  e.r_path = q.cm_edge.p + 3 * nu;
+  e.term = q.cm_term.p;
+  e.zmax = q.cm_term.p + nu;
+  if (po) launch_cm_edges_prior(e, l.stream);
+  else launch_cm_edges(e, l.stream);
+  CmFinishArgs f{};
+  f.eoff = q.cm_eoff.p;
+  f.term = e.term;
+  f.zmax = e.zmax;
+  f.nq = nq;
+  f.z_th = z_th;
+  f.gain = q.cm_gain.p;
+  f.verdict = q.cm_verdict.p;
+  f.weak_k = q.cm_wk.p;
+  f.weak_z = q.cm_wz.p;
+  launch_cm_finish(f, l.stream);
+  const int64_t at = host::chain_many_edge_at(chain_offsets, c0);  // the chunk's units are its queries' edges, in order
+  HIP_CHECK(hipMemcpyAsync(o.z_struct + at, e.z_struct, nu * 4, hipMemcpyDeviceToHost, l.stream));
+  HIP_CHECK(hipMemcpyAsync(o.z_path + at, e.z_path, nu * 4, hipMemcpyDeviceToHost, l.stream));
+  HIP_CHECK(hipMemcpyAsync(o.r_struct + at, e.r_struct, nu * 4, hipMemcpyDeviceToHost, l.stream));
+  HIP_CHECK(hipMemcpyAsync(o.r_path + at, e.r_path, nu * 4, hipMemcpyDeviceToHost, l.stream));
+  HIP_CHECK(hipMemcpyAsync(o.gain + c0, q.cm_gain.p, (size_t)nq * 8, hipMemcpyDeviceToHost, l.stream));
+  HIP_CHECK(hipMemcpyAsync(o.verdict + c0, q.cm_verdict.p, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
+  HIP_CHECK(hipMemcpyAsync(o.weakest_k + c0, q.cm_wk.p, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
+  HIP_CHECK(hipMemcpyAsync(o.weakest_z + c0, q.cm_wz.p, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
+}
+
+}  // namespace
+
+// chain_receipt(chain_q, z_th) of U*(psi_q) for Q (query, chain) pairs: per chunk the path structures (the lattice's own
+// chain once per call, else once per distinct chain of the chunk), the (query, edge) units, one gather kernel over them and
+// one finish kernel over the queries.  Nothing outlives the call but the scratch's allocation.
+void query_chain_receipt_many(L& l, const float* psis, int32_t Q, const int64_t* chain_offsets, const int32_t* chain_nodes,
+                              float z_th, const ChainManyOut& o) {
+  if (l.comm) throw Unsupported("osc_chain_receipt_many: lattices with a communicator are not supported");
+  require_basis(l);
+  if (Q <= 0) return;
+  int32_t where = 0;
+  switch (host::chain_many_check(chain_offsets, chain_nodes, Q, l.N, &where)) {
+    case 1:
+      throw Invalid("osc_chain_receipt_many: query " + std::to_string(where) + ": a chain has 2 to " +
+                    std::to_string(host::kCorpusMaxChain) + " nodes, at offsets that start from 0");
+    case 2:
+      throw Invalid("osc_chain_receipt_many: query " + std::to_string(where) + ": chain indices out of bounds");
+  }
+  const int32_t N = (int32_t)l.N;
+  const int32_t* dev = permuted(l) ? l.inv_h.data() : nullptr;
+  host::ChainManyPaths paths;
+  int32_t own = -1;
+  if (l.chain_present) {  // lattice.py:479-483: the lattice's own A_path, weights included, whatever the argument is
+    std::vector<int32_t> rows(l.chain_nodes);
+    if (dev)
+      for (int32_t& v : rows) v = dev[v];
+    own = paths.add(rows.data(), l.chain_w.empty() ? nullptr : l.chain_w.data(), (int32_t)rows.size(), N);
+  }
+  if (own >= 0) chain_upload_paths(l, paths);
+  chain_scratch_alloc(l);
+  std::vector<host::ChainManyUnit> units;
+  std::vector<int32_t> eoff;
+  std::vector<float> hpsi;
+  for (int32_t c0 = 0; c0 < Q; c0 += kQueryChunk) {
+    const int32_t nq = std::min<int32_t>(kQueryChunk, Q - c0);
+    if (own < 0) paths.clear();
+    host::chain_many_units(chain_offsets, chain_nodes, c0, nq, dev, N, own, paths, units, eoff);
+    if (own < 0) chain_upload_paths(l, paths);
+    stage_psi_rows(l, psis, c0, nq, hpsi);
+    chain_upload_units(l, units, eoff);
+    chain_edge_stage(l, basis_view(l.query), nullptr, c0, nq, units.size(), z_th, chain_offsets, o);
+    sync(l);  // (the host vectors above are reused by the next chunk)
+  }
+}
+
+// ---- per-query chain priors (DESIGN.md section 12.2) ------------------------------------------------------------------
+namespace {
+
+// host vectors the panel stage reuses from pass to pass
+struct CpHostScratch {
+  host::ChainPriorSystems sys;
+  std::vector<int32_t> hints, hnode;
+  std::vector<int64_t> hlongs;
+  std::map<int32_t, int32_t> column_of;
 };
 
 // The panel stage of one pass (a host::ChainPriorPass), shared by osc_chain_prior_many, osc_bundle_prior_many and
@@ -1004,16 +1122,6 @@ bool chain_prior_call_check(L& l, const std::string& fn, int32_t Q, const int64_
   return prior;
 }
 
-// the basis's own residual for one query: |r_X| + |psi|_inf |r_x|, NaN for a psi that holds one
-float chain_prior_base_res(const float* psi, int32_t D, float res_X, float res_x) {
-  float pinf = 0.f;
-  for (int32_t d = 0; d < D; ++d) {
-    const float v = std::fabs(psi[d]);
-    pinf = (v > pinf || v != v) ? v : pinf;
-  }
-  return res_X + pinf * res_x;
-}
-
 // what the Green's columns' solve of a call needs: the operator diag(d) - lamC W of M' (d in q.cp_diag), the graph, the
 // columns' stop and the forced column limit of a pass (OSC_CHAIN_PRIOR_COLS, read once per call; 0: none)
 struct CpSolve {
@@ -1037,51 +1145,6 @@ CpSolve chain_prior_solve_setup(L& l, float lamP, float tol) {
   return sv;
 }
 
-// Queries [c0, c0 + nq) of a pass: their rows into q.cm_psi at pitch ld (through hpsi) and their base residuals into hflts
-void stage_pass_psi(L& l, const float* psis, int32_t c0, int32_t nq, float res_X, float res_x, std::vector<float>& hpsi,
-                    std::vector<float>& hflts) {
-  auto& q = l.query;
-  const int32_t D = l.D;
-  hpsi.assign((size_t)nq * l.ld, 0.f);
-  hflts.assign((size_t)nq, 0.f);
-  for (int32_t t = 0; t < nq; ++t) {
-    const float* p = psis + (size_t)(c0 + t) * D;
-    std::copy(p, p + D, hpsi.data() + (size_t)t * l.ld);
-    hflts[(size_t)t] = chain_prior_base_res(p, D, res_X, res_x);
-  }
-  q.cm_psi.alloc(hpsi.size());
-  HIP_CHECK(hipMemcpyAsync(q.cm_psi.p, hpsi.data(), hpsi.size() * 4, hipMemcpyHostToDevice, l.stream));
-}
-
-// host vectors the query staging reuses from pass to pass
-struct CpQueryScratch {
-  std::vector<float> hpsi, bt;
-  std::vector<double> pn2, pinv;
-};
-
-// The per-pass query staging of the bundle and receipt paths: stage_pass_psi, |psi|^2 and 1 / (|psi| + 1e-12) into q.pn2 and
-// q.pinv and, with_bt, the query-dot GEMM's operand into q.Bt (the caller has sized the three for a chunk)
-void stage_pass_queries(L& l, const float* psis, int32_t c0, int32_t nq, bool with_bt, float res_X, float res_x,
-                        CpQueryScratch& st, std::vector<float>& hflts) {
-  auto& q = l.query;
-  const int32_t D = l.D, kpad = query_kpad(D);
-  stage_pass_psi(l, psis, c0, nq, res_X, res_x, st.hpsi, hflts);
-  st.pn2.assign((size_t)nq, 0.0);
-  st.pinv.assign((size_t)nq, 0.0);
-  if (with_bt) st.bt.assign((size_t)query_qpad(nq) * kpad, 0.f);
-  for (int32_t t = 0; t < nq; ++t) {
-    const float* p = psis + (size_t)(c0 + t) * D;
-    double s = 0.0;
-    for (int32_t d = 0; d < D; ++d) s += (double)p[d] * (double)p[d];
-    st.pn2[(size_t)t] = s;
-    st.pinv[(size_t)t] = 1.0 / (std::sqrt(s) + 1e-12);
-    if (with_bt) std::copy(p, p + D, st.bt.data() + (size_t)t * kpad);
-  }
-  if (with_bt) HIP_CHECK(hipMemcpyAsync(q.Bt.p, st.bt.data(), st.bt.size() * 4, hipMemcpyHostToDevice, l.stream));
-  HIP_CHECK(hipMemcpyAsync(q.pn2.p, st.pn2.data(), (size_t)nq * 8, hipMemcpyHostToDevice, l.stream));
-  HIP_CHECK(hipMemcpyAsync(q.pinv.p, st.pinv.data(), (size_t)nq * 8, hipMemcpyHostToDevice, l.stream));
-}
-
 // Section 11.1's two GEMMs on the shifted basis: kappa (N x ks), the rows of every query's T_q V_q (q.cp_tv, msum of them)
 // against X' in the query-dot GEMM's tile and K order (btk: its packed operand), then section 11's query dots of the nq
 // queries staged in q.Bt into q.pm and q.align (the callers overwrite that align)
@@ -1103,24 +1166,7 @@ void shifted_kappa_and_dots(L& l, int64_t msum, int32_t ks, float* kappa, float*
   gk.sqrt_deg = l.sqrt_deg.p;
   gk.p = kappa;
   launch_query_gemm(gk, l.stream);
-  QueryGemmArgs gp{};
-  gp.A = sh.X.p;
-  gp.Bt = q.Bt.p;
-  gp.N = (int32_t)l.N;
-  gp.D = l.D;
-  gp.ld = l.ld;
-  gp.kpad = kpad;
-  gp.qs = qs;
-  gp.nq = nq;
-  gp.mode = 0;
-  gp.x4 = sh.x4.p;
-  gp.xn2 = sh.xn2.p;
-  gp.sqrt_deg = l.sqrt_deg.p;
-  gp.pn2 = q.pn2.p;
-  gp.pinv = q.pinv.p;
-  gp.align = q.align.p;
-  gp.p = q.pm.p;
-  launch_query_gemm(gp, l.stream);
+  launch_query_dots(l, sh, qs, nq);
 }
 
 // BpArgs as far as the bundle and the receipt path fill it alike: the graph, the panel stage's outputs, the staged queries,
@@ -1164,19 +1210,15 @@ BpArgs bp_common_args(L& l, const CpPanelOut& po, int32_t qs, int32_t nq, int32_
 // correction on every gathered row.  lamP == 0: the resident basis and no panel; only the path weights differ from
 // osc_chain_receipt_many.  Nothing outlives the call but the scratch's allocation.
 void query_chain_prior_many(L& l, const float* psis, int32_t Q, const int64_t* chain_offsets, const int32_t* chain_nodes,
-                            const float* chain_weights, float lamP, float tol, int32_t max_iters, float z_th, float* z_struct,
-                            float* z_path, float* r_struct, float* r_path, double* gain, int32_t* verdict, int32_t* weakest_k,
-                            float* weakest_z, float* prior_res, int32_t* prior_iters) {
+                            const float* chain_weights, float lamP, float tol, int32_t max_iters, float z_th,
+                            const ChainManyOut& o, float* prior_res, int32_t* prior_iters) {
   const bool prior = chain_prior_call_check(l, "osc_chain_prior_many", Q, chain_offsets, chain_nodes, chain_weights, lamP, tol,
                                             max_iters);
   if (Q <= 0) return;
   auto& q = l.query;
-  auto& sh = q.shifted;
-  const int32_t N = (int32_t)l.N, D = l.D;
+  const int32_t N = (int32_t)l.N;
   const int32_t* dev = permuted(l) ? l.inv_h.data() : nullptr;
-  const float* const bX = prior ? sh.X.p : q.X.p;
-  const float* const bx4 = prior ? sh.x4.p : q.x4.p;
-  const float res_X = prior ? sh.res_X : q.res_X, res_x = prior ? sh.res_x : q.res_x;
+  const BasisView bv = prior ? basis_view(q.shifted) : basis_view(q);
   const CpSolve sv = prior ? chain_prior_solve_setup(l, lamP, tol) : CpSolve{};
   // the passes: by the panel's budget with a prior, osc_chain_receipt_many's chunks without
   std::vector<host::ChainPriorPass> passes;
@@ -1190,11 +1232,7 @@ void query_chain_prior_many(L& l, const float* psis, int32_t Q, const int64_t* c
       passes.push_back(ps);
     }
   }
-  q.cm_eoff.alloc((size_t)kQueryChunk + 1);
-  q.cm_gain.alloc(kQueryChunk);
-  q.cm_verdict.alloc(kQueryChunk);
-  q.cm_wk.alloc(kQueryChunk);
-  q.cm_wz.alloc(kQueryChunk);
+  chain_scratch_alloc(l);
   host::ChainManyPaths paths;
   CpHostScratch hs;
   std::vector<host::ChainManyUnit> units;
@@ -1204,21 +1242,11 @@ void query_chain_prior_many(L& l, const float* psis, int32_t Q, const int64_t* c
     const int32_t c0 = ps.q0, nq = ps.nq;
     paths.clear();
     host::chain_many_units_weighted(chain_offsets, chain_nodes, chain_weights, c0, nq, dev, N, paths, units, eoff, path_of);
-    q.cm_pcol.alloc(std::max<size_t>(paths.pcol.size(), 1));
-    q.cm_pa.alloc(std::max<size_t>(paths.pa.size(), 1));
-    if (!paths.pcol.empty()) {
-      HIP_CHECK(hipMemcpyAsync(q.cm_pcol.p, paths.pcol.data(), paths.pcol.size() * 4, hipMemcpyHostToDevice, l.stream));
-      HIP_CHECK(hipMemcpyAsync(q.cm_pa.p, paths.pa.data(), paths.pa.size() * 4, hipMemcpyHostToDevice, l.stream));
-    }
-    const size_t nu = units.size();
+    chain_upload_paths(l, paths);
     // the rows of psi and the basis's own residual per query
-    stage_pass_psi(l, psis, c0, nq, res_X, res_x, hpsi, hflts);
-    q.cm_units.alloc(nu);
-    q.cm_edge.alloc(4 * nu);
-    q.cm_term.alloc(2 * nu);
-    HIP_CHECK(hipMemcpyAsync(q.cm_units.p, units.data(), nu * sizeof(host::ChainManyUnit), hipMemcpyHostToDevice, l.stream));
-    HIP_CHECK(hipMemcpyAsync(q.cm_eoff.p, eoff.data(), eoff.size() * 4, hipMemcpyHostToDevice, l.stream));
-    CmEdgesArgs e{};
+    stage_pass_psi(l, psis, c0, nq, PassPsi{bv.res_X, bv.res_x, hflts}, hpsi);
+    chain_upload_units(l, units, eoff);
+    CpPanelOut po{};
     if (!prior) {
       for (int32_t t = 0; t < nq; ++t) {
         prior_res[c0 + t] = hflts[(size_t)t];
@@ -1226,65 +1254,12 @@ void query_chain_prior_many(L& l, const float* psis, int32_t Q, const int64_t* c
       }
     } else {
       q.cp_scratch.alloc((size_t)host::chain_prior_layout(N, ps.qc).total);
-      const CpPanelOut po = chain_prior_panel_stage(l, ps.cols, ps.qc, nq, paths, path_of, hflts, dev, bX, bx4, lamP, sv.tol_g,
-                                                    max_iters, sv.rop, sv.g, hs);
-      float* const pres_d = po.prior_res;
-      int32_t* const pit_d = po.prior_iters;
-      HIP_CHECK(hipMemcpyAsync(prior_res + c0, pres_d, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
-      HIP_CHECK(hipMemcpyAsync(prior_iters + c0, pit_d, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
-      e.G = po.G;
-      e.q_sys = po.q_sys;
-      e.sys_m = po.sys_m;
-      e.sys_col_at = po.sys_col_at;
-      e.sys_cols = po.sys_cols;
-      e.TV = q.cp_tv.p;
-      e.tv_at = po.tv_at;
+      po = chain_prior_panel_stage(l, ps.cols, ps.qc, nq, paths, path_of, hflts, dev, bv.X, bv.x4, lamP, sv.tol_g, max_iters,
+                                   sv.rop, sv.g, hs);
+      HIP_CHECK(hipMemcpyAsync(prior_res + c0, po.prior_res, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
+      HIP_CHECK(hipMemcpyAsync(prior_iters + c0, po.prior_iters, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
     }
-    e.X = bX;
-    e.x4 = bx4;
-    e.Y = l.Y.p;
-    e.sqrt_deg = l.sqrt_deg.p;
-    e.col = l.ell_col.p;
-    e.adj = l.ell_a.p;
-    e.deg = l.deg.p;
-    e.psi = q.cm_psi.p;
-    e.units = q.cm_units.p;
-    e.pcol = q.cm_pcol.p;
-    e.pa = q.cm_pa.p;
-    e.width = l.width;
-    e.N = N;
-    e.D = D;
-    e.ld = l.ld;
-    e.n_units = (int64_t)nu;
-    e.lamC = l.lamC;
-    e.z_struct = q.cm_edge.p;
-    e.z_path = q.cm_edge.p + nu;
-    e.r_struct = q.cm_edge.p + 2 * nu;
-    e.r_path = q.cm_edge.p + 3 * nu;
-    e.term = q.cm_term.p;
-    e.zmax = q.cm_term.p + nu;
-    if (prior) launch_cm_edges_prior(e, l.stream);
-    else launch_cm_edges(e, l.stream);
-    CmFinishArgs f{};
-    f.eoff = q.cm_eoff.p;
-    f.term = e.term;
-    f.zmax = e.zmax;
-    f.nq = nq;
-    f.z_th = z_th;
-    f.gain = q.cm_gain.p;
-    f.verdict = q.cm_verdict.p;
-    f.weak_k = q.cm_wk.p;
-    f.weak_z = q.cm_wz.p;
-    launch_cm_finish(f, l.stream);
-    const int64_t at = host::chain_many_edge_at(chain_offsets, c0);
-    HIP_CHECK(hipMemcpyAsync(z_struct + at, e.z_struct, nu * 4, hipMemcpyDeviceToHost, l.stream));
-    HIP_CHECK(hipMemcpyAsync(z_path + at, e.z_path, nu * 4, hipMemcpyDeviceToHost, l.stream));
-    HIP_CHECK(hipMemcpyAsync(r_struct + at, e.r_struct, nu * 4, hipMemcpyDeviceToHost, l.stream));
-    HIP_CHECK(hipMemcpyAsync(r_path + at, e.r_path, nu * 4, hipMemcpyDeviceToHost, l.stream));
-    HIP_CHECK(hipMemcpyAsync(gain + c0, q.cm_gain.p, (size_t)nq * 8, hipMemcpyDeviceToHost, l.stream));
-    HIP_CHECK(hipMemcpyAsync(verdict + c0, q.cm_verdict.p, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
-    HIP_CHECK(hipMemcpyAsync(weakest_k + c0, q.cm_wk.p, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
-    HIP_CHECK(hipMemcpyAsync(weakest_z + c0, q.cm_wz.p, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
+    chain_edge_stage(l, bv, prior ? &po : nullptr, c0, nq, units.size(), z_th, chain_offsets, o);
     sync(l);  // (the host vectors above are reused by the next pass)
   }
 }
@@ -1349,7 +1324,7 @@ void query_bundle_prior_many(L& l, const float* psis, int32_t Q, const int64_t* 
   const int32_t kk = (int32_t)std::min<int64_t>(std::max(k, 0), l.N);
   const int32_t kpad = query_kpad(D);
   const int32_t* dev = permuted(l) ? l.inv_h.data() : nullptr;
-  ensure_yn(l);
+  bundle_alloc(l, kk);
   ensure_shifted_stats(l);
   const CpSolve sv = chain_prior_solve_setup(l, lamP, tol);
   const std::vector<host::ChainPriorPass> passes = host::bundle_prior_passes(
@@ -1357,24 +1332,19 @@ void query_bundle_prior_many(L& l, const float* psis, int32_t Q, const int64_t* 
   q.Bt.alloc((size_t)query_qpad(kQueryChunk) * kpad);
   q.pn2.alloc(kQueryChunk);
   q.pinv.alloc(kQueryChunk);
-  q.part.alloc((size_t)query_stat_parts(N) * kQueryChunk);
-  q.stats.alloc(kQueryChunk);
-  if (kk > 0) {
-    q.out_score.alloc((size_t)kQueryChunk * kk);
-    q.out_align.alloc((size_t)kQueryChunk * kk);
-  }
   host::ChainManyPaths paths;
   CpHostScratch hs;
   std::vector<host::ChainManyUnit> units;
   std::vector<int32_t> eoff, path_of;
   std::vector<float> hflts;
-  CpQueryScratch st;
+  QueryStageScratch st;
+  const PassPsi pp{sh.res_X, sh.res_x, hflts};
   for (const host::ChainPriorPass& ps : passes) {
     const int32_t c0 = ps.q0, nq = ps.nq;
     paths.clear();
     host::chain_many_units_weighted(chain_offsets, chain_nodes, chain_weights, c0, nq, dev, N, paths, units, eoff, path_of);
     const int32_t qs = query_qs(nq);
-    stage_pass_queries(l, psis, c0, nq, true, sh.res_X, sh.res_x, st, hflts);
+    stage_queries(l, psis, c0, nq, true, st, &pp);
     const host::BundlePriorLayout lay = host::bundle_prior_layout(N, ps.qc, ps.msum, nq, kpad);
     q.cp_scratch.alloc((size_t)lay.total);
     const CpPanelOut po = chain_prior_panel_stage(l, ps.cols, ps.qc, nq, paths, path_of, hflts, dev, sh.X.p, sh.x4.p, lamP,
@@ -1407,13 +1377,7 @@ void query_bundle_prior_many(L& l, const float* psis, int32_t Q, const int64_t* 
     launch_bp_scalars(b, l.stream);
     launch_bp_rows_self(b, l.stream);
     launch_bp_rows_coh(b, l.stream);
-    launch_query_score(q.cs.p, q.align.p, N, qs, nq, (double)alpha, q.part.p, q.stats.p, l.stream);
-    mmr_many_run(l, qs, nq, kk, lambda_div);
-    launch_query_pack(q.cs.p, q.align.p, q.chosen_row.p, qs, nq, kk, q.out_score.p, q.out_align.p, l.stream);
-    const size_t m = (size_t)nq * kk, off = (size_t)c0 * kk;
-    HIP_CHECK(hipMemcpyAsync(ids + off, q.chosen_api.p, m * 4, hipMemcpyDeviceToHost, l.stream));
-    HIP_CHECK(hipMemcpyAsync(score + off, q.out_score.p, m * 4, hipMemcpyDeviceToHost, l.stream));
-    HIP_CHECK(hipMemcpyAsync(align + off, q.out_align.p, m * 4, hipMemcpyDeviceToHost, l.stream));
+    bundle_tail(l, qs, nq, c0, kk, alpha, lambda_div, ids, score, align);
     sync(l);  // (the host vectors above are reused by the next pass)
   }
   q.cp_scratch.release();  // up to 1 GiB a pass: back to the allocator's pool, not kept on the handle between calls
@@ -1426,13 +1390,11 @@ void query_bundle_prior_many(L& l, const float* psis, int32_t Q, const int64_t* 
 // GEMMs, the fused row pass and section 12's null-point stage.  lamP == 0: osc_receipt_many on the resident basis.
 void query_receipt_prior_many(L& l, const float* psis, int32_t Q, const int64_t* chain_offsets, const int32_t* chain_nodes,
                               const float* chain_weights, float lamP, float tol, int32_t max_iters, int32_t detail, float z_th,
-                              int32_t null_cap, double* dH, double* coh_sum, double* anchor_sum, double* query_sum,
-                              int32_t* null_total, int64_t* null_offsets, int32_t* i_out, int32_t* j_out, float* z_out,
-                              float* r_out, int64_t capacity, float* prior_res, int32_t* prior_iters) {
+                              int32_t null_cap, const ReceiptManyOut& o, float* prior_res, int32_t* prior_iters) {
   const bool prior = chain_prior_call_check(l, "osc_receipt_prior_many", Q, chain_offsets, chain_nodes, chain_weights, lamP,
                                             tol, max_iters);
   if (Q <= 0) {
-    if (null_offsets) null_offsets[0] = 0;
+    if (o.null_offsets) o.null_offsets[0] = 0;
     return;
   }
   auto& q = l.query;
@@ -1440,8 +1402,7 @@ void query_receipt_prior_many(L& l, const float* psis, int32_t Q, const int64_t*
   const int32_t N = (int32_t)l.N, D = l.D;
   const size_t n = (size_t)l.N;
   if (!prior) {
-    query_receipt_many(l, psis, Q, detail, z_th, null_cap, dH, coh_sum, anchor_sum, query_sum, null_total, null_offsets, i_out,
-                       j_out, z_out, r_out, capacity);
+    query_receipt_many(l, psis, Q, detail, z_th, null_cap, o);
     for (int32_t t = 0; t < Q; ++t) {
       prior_res[t] = chain_prior_base_res(psis + (size_t)t * D, D, q.res_X, q.res_x);
       prior_iters[t] = 0;
@@ -1453,37 +1414,9 @@ void query_receipt_prior_many(L& l, const float* psis, int32_t Q, const int64_t*
   const OpParams op = shifted_ustar_op(l, lamP);
   ensure_receipt_terms(l, sh, op, full);
   if (full) ensure_shifted_stats(l);
-  // per call: h1' = E0'^T (M' x') over E0' = U - X' - x' psi0^T, and h0' = tr(E0'^T M' E0') through the operator's quad form
-  std::vector<float> psi0((size_t)l.ld, 0.f);
-  HIP_CHECK(hipMemcpyAsync(psi0.data(), l.psi.p, (size_t)l.ld * 4, hipMemcpyDeviceToHost, l.stream));
-  RmColArgs c{};
-  c.X = sh.X.p;
-  c.x4 = sh.x4.p;
-  c.Mx = sh.Mx.p;
-  c.U = u_read(l);
-  c.psi0 = l.psi.p;
-  q.U0.alloc(n * l.ld);
-  c.U0 = q.U0.p;
-  c.N = N;
-  c.D = D;
-  c.ld = l.ld;
-  c.nb = rm_col_parts(l.N);
-  q.rpart.alloc((size_t)c.nb * 4 * l.ld);
-  q.rsum.alloc(rm_sum_size(l));
-  c.part = q.rpart.p;
-  launch_rm_cols(c, 1, l.stream);
-  q.rfin.alloc((size_t)rm_finish_groups(c.nb) * 4 * l.ld);
-  launch_rm_colfinish(q.rpart.p, c.nb, l.ld, q.rsum.p, q.rfin.p, l.stream);
-  std::vector<double> h1((size_t)l.ld);
-  HIP_CHECK(hipMemcpyAsync(h1.data(), q.rsum.p, h1.size() * 8, hipMemcpyDeviceToHost, l.stream));
-  sync(l);
-  double h0 = 0.0;
-  {
-    const ShiftedLamG shifted(l, lamP);
-    h0 = quad_form_of_difference(l, u_read(l), q.U0.p);
-  }
+  const ReceiptCallTerms ct = receipt_call_terms(l, sh, lamP);  // h0' and h1', on M'
   std::vector<double> hbase((size_t)8 + 3 * (size_t)D, 0.0);
-  hbase[0] = h0;
+  hbase[0] = ct.h0;
   hbase[1] = sh.rm_h2;
   hbase[2] = sh.rm_a0;
   hbase[3] = sh.rm_a2;
@@ -1492,7 +1425,7 @@ void query_receipt_prior_many(L& l, const float* psis, int32_t Q, const int64_t*
   hbase[6] = (double)l.lamG;
   hbase[7] = (double)l.lamQ;
   for (int32_t d = 0; d < D; ++d) {
-    hbase[(size_t)8 + d] = h1[(size_t)d];
+    hbase[(size_t)8 + d] = ct.h1[(size_t)d];
     hbase[(size_t)8 + D + d] = sh.rm_vec[(size_t)d];
     hbase[(size_t)8 + 2 * D + d] = sh.rm_vec[(size_t)D + d];
   }
@@ -1500,7 +1433,6 @@ void query_receipt_prior_many(L& l, const float* psis, int32_t Q, const int64_t*
   HIP_CHECK(hipMemcpyAsync(sh.rp_base.p, hbase.data(), hbase.size() * 8, hipMemcpyHostToDevice, l.stream));
   const int32_t kpad = query_kpad(D);
   const int32_t* dev = permuted(l) ? l.inv_h.data() : nullptr;
-  const int32_t* inv = permuted(l) ? l.inv_d.p : nullptr;
   const int cparts = rm_col_parts(l.N), cgroups = rm_finish_groups(cparts);
   const CpSolve sv = chain_prior_solve_setup(l, lamP, tol);
   const std::vector<host::ChainPriorPass> passes =
@@ -1518,19 +1450,20 @@ void query_receipt_prior_many(L& l, const float* psis, int32_t Q, const int64_t*
   host::ChainManyPaths paths;
   CpHostScratch hs;
   std::vector<host::ChainManyUnit> units;
-  std::vector<int32_t> eoff, path_of, tot;
+  std::vector<int32_t> eoff, path_of;
   std::vector<float> hflts;
-  std::vector<double> hscal, csum;
-  CpQueryScratch st;
+  std::vector<double> hscal;
+  QueryStageScratch st;
+  const PassPsi pp{sh.res_X, sh.res_x, hflts};
   std::vector<int64_t> hgat;
   DevBuf<int64_t> gat;
-  null_offsets[0] = 0;
+  o.null_offsets[0] = 0;
   for (const host::ChainPriorPass& ps : passes) {
     const int32_t c0 = ps.q0, nq = ps.nq;
     paths.clear();
     host::chain_many_units_weighted(chain_offsets, chain_nodes, chain_weights, c0, nq, dev, N, paths, units, eoff, path_of);
     const int32_t qs = query_qs(nq);
-    stage_pass_queries(l, psis, c0, nq, full, sh.res_X, sh.res_x, st, hflts);
+    stage_queries(l, psis, c0, nq, full, st, &pp);
     const host::ReceiptPriorLayout lay =
         host::receipt_prior_layout(N, ps.qc, ps.msum, ps.msq, nq, kpad, l.ld, full, cparts, cgroups);
     q.cp_scratch.alloc((size_t)lay.total);
@@ -1640,13 +1573,7 @@ void query_receipt_prior_many(L& l, const float* psis, int32_t Q, const int64_t*
     HIP_CHECK(hipMemcpyAsync(prior_res + c0, sa.res_out, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
     HIP_CHECK(hipMemcpyAsync(prior_iters + c0, sa.iters_out, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
     if (!full) {
-      sync(l);
-      for (int32_t t = 0; t < nq; ++t) {
-        dH[c0 + t] = hscal[(size_t)4 * t];
-        anchor_sum[c0 + t] = query_sum[c0 + t] = coh_sum[c0 + t] = 0.0;
-        null_total[c0 + t] = 0;
-        null_offsets[c0 + t + 1] = null_offsets[c0 + t];
-      }
+      receipt_light_chunk(l, o, c0, nq, hscal.data(), 4);
       continue;
     }
     RpRowsArgs ra{};
@@ -1663,21 +1590,17 @@ void query_receipt_prior_many(L& l, const float* psis, int32_t Q, const int64_t*
     float* const zt = reinterpret_cast<float*>(base + lay.zt);
     launch_rp_colsum(ra.cohd, N, qs, nq, cparts, cohpart, l.stream);
     launch_rm_colfinish(cohpart, cparts, nq, q.rsum.p, reinterpret_cast<double*>(base + lay.cohfin), l.stream);
-    launch_rm_transpose(ra.z, inv, N, qs, nq, zt, l.stream);
-    launch_rm_null_count(zt, N, nq, q.rtot.p, l.stream);
-    csum.assign((size_t)nq, 0.0);
-    tot.assign((size_t)nq, 0);
-    HIP_CHECK(hipMemcpyAsync(csum.data(), q.rsum.p, (size_t)nq * 8, hipMemcpyDeviceToHost, l.stream));
-    HIP_CHECK(hipMemcpyAsync(tot.data(), q.rtot.p, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
-    sync(l);
-    for (int32_t t = 0; t < nq; ++t) {
-      dH[c0 + t] = hscal[(size_t)4 * t];
-      anchor_sum[c0 + t] = hscal[(size_t)4 * t + 1];
-      query_sum[c0 + t] = hscal[(size_t)4 * t + 2];
-      coh_sum[c0 + t] = csum[(size_t)t];
-    }
-    receipt_null_stage(l, "osc_receipt_prior_many", c0, nq, qs, null_cap, tot, zt, ra.j, ra.r, null_total, null_offsets, i_out,
-                       j_out, z_out, r_out, capacity);
+    receipt_null_stage(
+        l, "osc_receipt_prior_many", NullChunk{c0, nq, qs, ra.z, ra.j, ra.r, zt}, null_cap, q.rsum.p, (size_t)nq,
+        [&](const double* csum) {
+          for (int32_t t = 0; t < nq; ++t) {
+            o.dH[c0 + t] = hscal[(size_t)4 * t];
+            o.anchor_sum[c0 + t] = hscal[(size_t)4 * t + 1];
+            o.query_sum[c0 + t] = hscal[(size_t)4 * t + 2];
+            o.coh_sum[c0 + t] = csum[(size_t)t];
+          }
+        },
+        o);
   }
   q.cp_scratch.release();  // up to 1 GiB a pass: back to the allocator's pool, not kept on the handle between calls
 }
@@ -1870,17 +1793,7 @@ BgBundleArgs gated_bundle_args(L& l, int32_t qs, double* ysum) {
   return b;
 }
 
-// the buffers of gated_bundle_stage, once per call
-void gated_bundle_alloc(L& l, int32_t kk) {
-  auto& q = l.query;
-  ensure_yn(l);
-  q.part.alloc((size_t)query_stat_parts((int32_t)l.N) * kQueryChunk);
-  q.stats.alloc(kQueryChunk);
-  q.out_score.alloc((size_t)kQueryChunk * kk);
-  q.out_align.alloc((size_t)kQueryChunk * kk);
-}
-
-// the bundle of the chunk's queries from the solved panel: align / coh columns, then osc_bundle_many's score, MMR and pack
+// the bundle of the chunk's queries from the solved panel: align / coh columns, then bundle_tail (the caller syncs)
 void gated_bundle_stage(L& l, const BgPanel& p, int32_t q0, int32_t kk, float alpha, float lambda_div, double* ysum,
                         bool& have_ysum, int32_t* ids, float* score, float* align) {
   auto& q = l.query;
@@ -1892,13 +1805,43 @@ void gated_bundle_stage(L& l, const BgPanel& p, int32_t q0, int32_t kk, float al
   if (!have_ysum) launch_bg_ysum(p, b, l.stream);
   have_ysum = true;
   launch_bg_bundle(p, b, l.stream);
-  launch_query_score(q.cs.p, q.align.p, N, qs, nq, (double)alpha, q.part.p, q.stats.p, l.stream);
-  mmr_many_run(l, qs, nq, kk, lambda_div);
-  launch_query_pack(q.cs.p, q.align.p, q.chosen_row.p, qs, nq, kk, q.out_score.p, q.out_align.p, l.stream);
-  const size_t m = (size_t)nq * kk, off = (size_t)q0 * kk;
-  HIP_CHECK(hipMemcpyAsync(ids + off, q.chosen_api.p, m * 4, hipMemcpyDeviceToHost, l.stream));
-  HIP_CHECK(hipMemcpyAsync(score + off, q.out_score.p, m * 4, hipMemcpyDeviceToHost, l.stream));
-  HIP_CHECK(hipMemcpyAsync(align + off, q.out_align.p, m * 4, hipMemcpyDeviceToHost, l.stream));
+  bundle_tail(l, qs, nq, q0, kk, alpha, lambda_div, ids, score, align);
+}
+
+// the state and argument checks of the two gated calls, under the entry point's name `fn`
+void gated_call_check(L& l, const std::string& fn, int32_t max_iters) {
+  require_graph(l);
+  if (l.comm) throw Unsupported(fn + ": lattices with a communicator are not supported");
+  if (l.chain_present) throw Unsupported(fn + ": a lattice with a chain of its own is not supported");
+  if (max_iters < 1) throw Invalid("max_iters must be >= 1");
+}
+
+// what the chunks of a gated call share: the slabs of a query, the requested chunk (OSC_GATED_CHUNK, read once per call) and
+// the graph
+struct GatedCall {
+  int32_t spq;
+  int requested;
+  GmGraph g;
+};
+
+// a gated call of Q > 0 queries after its checks: with `diffusion` osc_gates_many's gates into `gates`, then the shared sizes
+GatedCall gated_call_setup(L& l, const float* psis, int32_t Q, float* gates, int32_t diffusion, float gate_beta,
+                           float gate_gamma, int32_t gate_method, float gate_tol, int32_t gate_max_iters) {
+  if (diffusion)
+    query_gates_many(l, psis, Q, gate_beta, gate_gamma, gate_method, gate_tol, gate_max_iters, 1, gates, nullptr, nullptr);
+  GatedCall gc{host::gated_slabs_per_query(l.D), host::kGatedMaxChunk, GmGraph{l.ell_col.p, l.ell_w.p, l.deg.p, l.width}};
+  env_num("OSC_GATED_CHUNK", gc.requested);
+  static_assert(host::kGatedMaxChunk <= kQueryChunk, "a chunk's score, MMR and pack run as one pass of osc_bundle_many's");
+  return gc;
+}
+
+// section 11.2's U* solve of a chunk's panel, with the iteration counts and residuals of queries [q0, q0 + nq) copied out
+void gated_ustar_solve(L& l, const BgPanel& p, const GmGraph& g, int32_t max_iters, int32_t q0, int32_t* iters_out,
+                       float* res_out) {
+  launch_bg_init(p, g, l.Y.p, l.ld, l.stream);
+  gated_panel_pcg(l, p, g, max_iters);
+  if (iters_out) HIP_CHECK(hipMemcpyAsync(iters_out + q0, p.iters, (size_t)p.nq * 4, hipMemcpyDeviceToHost, l.stream));
+  if (res_out) HIP_CHECK(hipMemcpyAsync(res_out + q0, p.res, (size_t)p.nq * 4, hipMemcpyDeviceToHost, l.stream));
 }
 
 }  // namespace
@@ -1914,28 +1857,21 @@ void query_bundle_gated_many(L& l, const float* psis, int32_t Q, float* gates, i
                              float gate_gamma, int32_t gate_method, float gate_tol, int32_t gate_max_iters, float tol,
                              int32_t max_iters, int32_t k, float alpha, float lambda_div, int32_t* ids, float* score,
                              float* align, int32_t* iters_out, float* res_out, float* U_out) {
-  require_graph(l);
-  if (l.comm) throw Unsupported("osc_bundle_gated_many: lattices with a communicator are not supported");
-  if (l.chain_present) throw Unsupported("osc_bundle_gated_many: a lattice with a chain of its own is not supported");
-  if (max_iters < 1) throw Invalid("max_iters must be >= 1");
+  gated_call_check(l, "osc_bundle_gated_many", max_iters);
   if (Q <= 0) return;
-  if (diffusion)
-    query_gates_many(l, psis, Q, gate_beta, gate_gamma, gate_method, gate_tol, gate_max_iters, 1, gates, nullptr, nullptr);
-  const int32_t N = (int32_t)l.N, D = l.D;
+  const GatedCall gc = gated_call_setup(l, psis, Q, gates, diffusion, gate_beta, gate_gamma, gate_method, gate_tol,
+                                        gate_max_iters);
+  const int32_t N = (int32_t)l.N, D = l.D, spq = gc.spq;
+  const GmGraph& g = gc.g;
   const int32_t kk = (int32_t)std::min<int64_t>(std::max(k, 0), l.N);
-  const int32_t spq = host::gated_slabs_per_query(D);
-  int requested = host::kGatedMaxChunk;
-  env_num("OSC_GATED_CHUNK", requested);
-  static_assert(host::kGatedMaxChunk <= kQueryChunk, "a chunk's score, MMR and pack run as one pass of osc_bundle_many's");
-  const int32_t chunk = host::gated_chunk(N, D, requested, host::kGatedBudgetBytes);
+  const int32_t chunk = host::gated_chunk(N, D, gc.requested, host::kGatedBudgetBytes);
   DevBuf<char> scratch;
   scratch.alloc((size_t)host::gated_layout(N, D, std::min(chunk, Q)).total);
   DevBuf<double> ysum;
   if (kk > 0) {
-    gated_bundle_alloc(l, kk);
+    bundle_alloc(l, kk);
     ysum.alloc((size_t)N);
   }
-  const GmGraph g{l.ell_col.p, l.ell_w.p, l.deg.p, l.width};
   std::vector<float> hpsi, hx;
   bool have_ysum = false;
   for (int32_t c = 0; c < host::gates_chunk_count(Q, chunk); ++c) {
@@ -1944,10 +1880,7 @@ void query_bundle_gated_many(L& l, const float* psis, int32_t Q, float* gates, i
     char* const base = scratch.p;
     const BgPanel p = gated_panel(l, base, lay, nq, spq, tol);
     gated_panel_inputs(l, p, base, lay, psis, gates, q0, hpsi);
-    launch_bg_init(p, g, l.Y.p, l.ld, l.stream);
-    gated_panel_pcg(l, p, g, max_iters);
-    if (iters_out) HIP_CHECK(hipMemcpyAsync(iters_out + q0, p.iters, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
-    if (res_out) HIP_CHECK(hipMemcpyAsync(res_out + q0, p.res, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
+    gated_ustar_solve(l, p, g, max_iters, q0, iters_out, res_out);
     if (U_out) {
       hx.resize((size_t)p.slabs * N * 32);
       HIP_CHECK(hipMemcpyAsync(hx.data(), p.X, hx.size() * 4, hipMemcpyDeviceToHost, l.stream));
@@ -1974,31 +1907,24 @@ void query_receipt_gated_many(L& l, const float* psis, int32_t Q, float* gates, 
                               float gate_gamma, int32_t gate_method, float gate_tol, int32_t gate_max_iters, float tol,
                               int32_t max_iters, int32_t settle, float dt, int32_t settle_max_iters, float settle_tol,
                               int32_t detail, float z_th, int32_t null_cap, int32_t k, float alpha, float lambda_div,
-                              int32_t* settle_iters, float* settle_res, double* dH, double* coh_sum, double* anchor_sum,
-                              double* query_sum, int32_t* null_total, int64_t* null_offsets, int32_t* i_out, int32_t* j_out,
-                              float* z_out, float* r_out, int64_t capacity, int32_t* ids, float* score, float* align,
-                              int32_t* iters_out, float* res_out, double* settle_ms, double* solve_ms) {
-  require_graph(l);
-  if (l.comm) throw Unsupported("osc_receipt_gated_many: lattices with a communicator are not supported");
-  if (l.chain_present) throw Unsupported("osc_receipt_gated_many: a lattice with a chain of its own is not supported");
-  if (max_iters < 1) throw Invalid("max_iters must be >= 1");
+                              int32_t* settle_iters, float* settle_res, const ReceiptManyOut& o, int32_t* ids, float* score,
+                              float* align, int32_t* iters_out, float* res_out, double* settle_ms, double* solve_ms) {
+  gated_call_check(l, "osc_receipt_gated_many", max_iters);
   if (settle && settle_max_iters < 1) throw Invalid("osc_receipt_gated_many: the settle's max_iters must be >= 1");
-  if (null_offsets) null_offsets[0] = 0;
+  if (o.null_offsets) o.null_offsets[0] = 0;
   if (Q <= 0) return;
-  if (diffusion)
-    query_gates_many(l, psis, Q, gate_beta, gate_gamma, gate_method, gate_tol, gate_max_iters, 1, gates, nullptr, nullptr);
+  const GatedCall gc = gated_call_setup(l, psis, Q, gates, diffusion, gate_beta, gate_gamma, gate_method, gate_tol,
+                                        gate_max_iters);
   const bool full = detail != 0, settled = settle != 0;
-  const int32_t N = (int32_t)l.N, D = l.D;
+  const int32_t N = (int32_t)l.N, D = l.D, spq = gc.spq;
+  const GmGraph& g = gc.g;
   const int32_t kk = (int32_t)std::min<int64_t>(std::max(k, 0), l.N);
-  const int32_t spq = host::gated_slabs_per_query(D);
-  int requested = host::kGatedMaxChunk;
-  env_num("OSC_GATED_CHUNK", requested);
-  const int32_t chunk = host::receipt_gated_chunk(N, D, settled, full, requested, host::kGatedBudgetBytes);
+  const int32_t chunk = host::receipt_gated_chunk(N, D, settled, full, gc.requested, host::kGatedBudgetBytes);
   DevBuf<char> scratch;
   scratch.alloc((size_t)host::receipt_gated_layout(N, D, std::min(chunk, Q), settled, full).total);
   auto& q = l.query;
   DevBuf<double> ysum;
-  if (kk > 0) gated_bundle_alloc(l, kk);
+  if (kk > 0) bundle_alloc(l, kk);
   if (kk > 0 || full) ysum.alloc((size_t)N);
   const int cparts = rm_col_parts(l.N);
   static_assert(host::kReceiptGatedFinishRows == kRmFinishRows, "the plan sizes launch_rm_colfinish's scratch");
@@ -2008,12 +1934,9 @@ void query_receipt_gated_many(L& l, const float* psis, int32_t Q, float* gates, 
     q.rsel.alloc(kQueryChunk);
     q.roff.alloc(kQueryChunk);
   }
-  const GmGraph g{l.ell_col.p, l.ell_w.p, l.deg.p, l.width};
-  const int32_t* inv = permuted(l) ? l.inv_d.p : nullptr;
   const float* const U = u_read(l);
   std::vector<float> hpsi;
-  std::vector<double> hdh, hsum;
-  std::vector<int32_t> tot;
+  std::vector<double> hdh;
   bool have_ysum = false;
   for (int32_t c = 0; c < host::gates_chunk_count(Q, chunk); ++c) {
     const int32_t q0 = host::gates_chunk_begin(c, chunk), nq = host::gates_chunk_size(Q, c, chunk);
@@ -2042,10 +1965,7 @@ void query_receipt_gated_many(L& l, const float* psis, int32_t Q, float* gates, 
       p.X = reinterpret_cast<float*>(base + lay.U);
     }
     const double t1 = now_ms();
-    launch_bg_init(p, g, l.Y.p, l.ld, l.stream);
-    gated_panel_pcg(l, p, g, max_iters);
-    if (iters_out) HIP_CHECK(hipMemcpyAsync(iters_out + q0, p.iters, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
-    if (res_out) HIP_CHECK(hipMemcpyAsync(res_out + q0, p.res, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
+    gated_ustar_solve(l, p, g, max_iters, q0, iters_out, res_out);
     sync(l);
     const double per_solve = (now_ms() - t1) / nq;
     for (int32_t t = 0; t < nq; ++t) solve_ms[q0 + t] = per_solve;
@@ -2057,13 +1977,7 @@ void query_receipt_gated_many(L& l, const float* psis, int32_t Q, float* gates, 
     hdh.assign((size_t)nq, 0.0);
     HIP_CHECK(hipMemcpyAsync(hdh.data(), dh, (size_t)nq * 8, hipMemcpyDeviceToHost, l.stream));
     if (!full) {
-      sync(l);
-      for (int32_t t = 0; t < nq; ++t) {
-        dH[q0 + t] = hdh[(size_t)t];
-        anchor_sum[q0 + t] = query_sum[q0 + t] = coh_sum[q0 + t] = 0.0;
-        null_total[q0 + t] = 0;
-        null_offsets[q0 + t + 1] = null_offsets[q0 + t];
-      }
+      receipt_light_chunk(l, o, q0, nq, hdh.data(), 1);
     } else {
       const int32_t qs = lay.qs;
       if (!have_ysum) launch_bg_ysum(p, gated_bundle_args(l, qs, ysum.p), l.stream);
@@ -2093,21 +2007,17 @@ void query_receipt_gated_many(L& l, const float* psis, int32_t Q, float* gates, 
         launch_rp_colsum(ra.comp + (size_t)t * N * qs, N, qs, nq, cparts, part, l.stream);
         launch_rm_colfinish(part, cparts, nq, sums + (size_t)t * nq, reinterpret_cast<double*>(base + lay.sumfin), l.stream);
       }
-      launch_rm_transpose(ra.z, inv, N, qs, nq, zt, l.stream);
-      launch_rm_null_count(zt, N, nq, q.rtot.p, l.stream);
-      hsum.assign((size_t)3 * nq, 0.0);
-      tot.assign((size_t)nq, 0);
-      HIP_CHECK(hipMemcpyAsync(hsum.data(), sums, hsum.size() * 8, hipMemcpyDeviceToHost, l.stream));
-      HIP_CHECK(hipMemcpyAsync(tot.data(), q.rtot.p, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
-      sync(l);
-      for (int32_t t = 0; t < nq; ++t) {
-        dH[q0 + t] = hdh[(size_t)t];
-        coh_sum[q0 + t] = hsum[(size_t)t];
-        anchor_sum[q0 + t] = hsum[(size_t)nq + t];
-        query_sum[q0 + t] = hsum[(size_t)2 * nq + t];
-      }
-      receipt_null_stage(l, "osc_receipt_gated_many", q0, nq, qs, null_cap, tot, zt, ra.j, ra.r, null_total, null_offsets, i_out,
-                         j_out, z_out, r_out, capacity);
+      receipt_null_stage(
+          l, "osc_receipt_gated_many", NullChunk{q0, nq, qs, ra.z, ra.j, ra.r, zt}, null_cap, sums, (size_t)3 * nq,
+          [&](const double* hsum) {
+            for (int32_t t = 0; t < nq; ++t) {
+              o.dH[q0 + t] = hdh[(size_t)t];
+              o.coh_sum[q0 + t] = hsum[(size_t)t];
+              o.anchor_sum[q0 + t] = hsum[(size_t)nq + t];
+              o.query_sum[q0 + t] = hsum[(size_t)2 * nq + t];
+            }
+          },
+          o);
     }
     if (kk > 0) gated_bundle_stage(l, p, q0, kk, alpha, lambda_div, ysum.p, have_ysum, ids, score, align);
     sync(l);  // (hpsi and the scratch block are reused by the next chunk)

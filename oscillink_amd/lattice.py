@@ -56,6 +56,65 @@ def _state_map_update(N: int, ids: np.ndarray) -> np.ndarray:
     return src
 
 
+# What the batched bundle calls share.  Module functions: they read of a lattice only what the calls' own bodies read.
+def _bundle_arrays(Q: int, kk: int):
+    """The (ids, score, align) arrays a batched bundle call fills, each Q x kk."""
+    return np.zeros((Q, kk), dtype=np.int32), np.zeros((Q, kk), dtype=np.float32), np.zeros((Q, kk), dtype=np.float32)
+
+
+def _bundle_result(ids, score, align, as_arrays: bool):
+    """A batched bundle call's return: the arrays, or one list of bundle()'s dicts per query."""
+    if as_arrays:
+        return ids, score, align
+    return [rc.bundle_dicts(ids[q], score[q], align[q]) for q in range(ids.shape[0])]
+
+
+def _gated_call_inputs(lat, fn: str, psis, gates, gate_gamma, gate_method, gate_max_iters, max_iters):
+    """The refusals and argument checks `bundle_gated_many` and `receipt_gated_many` (`fn`) share.  Returns (P, Q, G,
+    diffusion): the queries, their count, the (Q, N) float32 gates -- with `diffusion` the array the call's own
+    "diffusion" gates are written to -- and whether the gates are to be computed."""
+    if lat._has_comm:
+        raise NotImplementedError(f"{fn}: lattices with a communicator (sharded / multi-rank) are not supported")
+    if lat._chain_nodes is not None:
+        raise NotImplementedError(f"{fn}: a lattice with a chain of its own is not supported (clear_chain first)")
+    P = rc.check_queries(psis, lat.D, finite=False)
+    Q = int(P.shape[0])
+    diffusion = isinstance(gates, str)
+    if diffusion:
+        if gates != "diffusion":
+            raise ValueError(f"gates must be 'diffusion' or a ({Q}, {lat.N}) array, got {gates!r}")
+        if not float(gate_gamma) > 0:
+            raise ValueError("gate_gamma must be > 0 for SPD")
+        if gate_method not in ("direct", "cg"):
+            raise ValueError(f"gate_method must be 'direct' or 'cg', got {gate_method!r}")
+        if int(gate_max_iters) < 1:
+            raise ValueError("gate_max_iters must be >= 1")
+        G = nat.result_array((Q, lat.N)) if Q > 0 else np.zeros((0, lat.N), dtype=np.float32)
+    else:
+        G = lat._check_gate_rows(gates)
+        if G.shape[0] != Q:
+            raise ValueError(f"gates must be a ({Q}, {lat.N}) array, got shape {G.shape}")
+        for q in range(Q):
+            if not np.all(np.isfinite(G[q])):
+                raise ValueError(f"query {q}: gates must be finite")
+            if np.any(G[q] < 0):
+                raise ValueError(f"query {q}: gates must be >= 0")
+    if int(max_iters) < 1:
+        raise ValueError("max_iters must be >= 1")
+    return P, Q, G, diffusion
+
+
+def _warn_diffusion_gates(G: np.ndarray) -> None:
+    """`diffusion_gates_many`'s warning for gates a gated call computed itself, raised at that call's caller."""
+    bad = np.nonzero(~np.all(np.isfinite(G), axis=1))[0]
+    if bad.size:
+        import warnings
+
+        warnings.warn(f"diffusion_gates_many: the screened-diffusion solve of query {int(bad[0])} produced "
+                      "non-finite values; returned as computed, like the reference's cg path", RuntimeWarning,
+                      stacklevel=3)
+
+
 class OscillinkLattice:
     """Short-term coherence lattice: mutual-kNN graph + SPD system + Jacobi-PCG settle (reference lattice.py:23-31)."""
 
@@ -846,9 +905,7 @@ class OscillinkLattice:
         P = rc.check_queries(psis, self.D)
         Q = int(P.shape[0])
         kk = min(int(k), self.N) if k > 0 else 0
-        ids = np.zeros((Q, kk), dtype=np.int32)
-        score = np.zeros((Q, kk), dtype=np.float32)
-        align = np.zeros((Q, kk), dtype=np.float32)
+        ids, score, align = _bundle_arrays(Q, kk)
         if prior:
             _, offsets, nodes, weights = rc.prior_chain_block(chains, chain_weights, Q, self.N)
             prior_res, prior_iters = np.zeros(Q, dtype=np.float32), np.zeros(Q, dtype=np.int32)
@@ -868,11 +925,7 @@ class OscillinkLattice:
         elif Q > 0 and kk > 0:
             self._ensure_query_basis(tol, max_iters, float(np.max(np.abs(P))))
             self._call("osc_bundle_many", nat.f32(P), Q, kk, float(alpha), 0.5, nat.i32(ids), nat.f32(score), nat.f32(align))
-        if as_arrays:
-            return ids, score, align
-        if Q == 0:
-            return []
-        return [rc.bundle_dicts(ids[q], score[q], align[q]) for q in range(Q)]
+        return _bundle_result(ids, score, align, as_arrays)
 
     def _check_gate_rows(self, gates) -> np.ndarray:
         """Per-query gates as a contiguous float32 (Q, N) array (Q is not checked here), or the ValueError for a single
@@ -903,40 +956,10 @@ class OscillinkLattice:
         non-finite answers and changes no other query's.  Its own method because `bundle_many`'s parameter list is
         pinned; chain priors (`bundle_many(chains=..., lamP=...)`) do not combine with per-query gates, and a lattice
         with a chain of its own raises NotImplementedError."""
-        if self._has_comm:
-            raise NotImplementedError("bundle_gated_many: lattices with a communicator (sharded / multi-rank) are not "
-                                      "supported")
-        if self._chain_nodes is not None:
-            raise NotImplementedError("bundle_gated_many: a lattice with a chain of its own is not supported "
-                                      "(clear_chain first)")
-        P = rc.check_queries(psis, self.D, finite=False)
-        Q = int(P.shape[0])
-        diffusion = isinstance(gates, str)
-        if diffusion:
-            if gates != "diffusion":
-                raise ValueError(f"gates must be 'diffusion' or a ({Q}, {self.N}) array, got {gates!r}")
-            if not float(gate_gamma) > 0:
-                raise ValueError("gate_gamma must be > 0 for SPD")
-            if gate_method not in ("direct", "cg"):
-                raise ValueError(f"gate_method must be 'direct' or 'cg', got {gate_method!r}")
-            if int(gate_max_iters) < 1:
-                raise ValueError("gate_max_iters must be >= 1")
-            G = nat.result_array((Q, self.N)) if Q > 0 else np.zeros((0, self.N), dtype=np.float32)
-        else:
-            G = self._check_gate_rows(gates)
-            if G.shape[0] != Q:
-                raise ValueError(f"gates must be a ({Q}, {self.N}) array, got shape {G.shape}")
-            for q in range(Q):
-                if not np.all(np.isfinite(G[q])):
-                    raise ValueError(f"query {q}: gates must be finite")
-                if np.any(G[q] < 0):
-                    raise ValueError(f"query {q}: gates must be >= 0")
-        if int(max_iters) < 1:
-            raise ValueError("max_iters must be >= 1")
+        P, Q, G, diffusion = _gated_call_inputs(self, "bundle_gated_many", psis, gates, gate_gamma, gate_method,
+                                                gate_max_iters, max_iters)
         kk = min(int(k), self.N) if k > 0 else 0
-        ids = np.zeros((Q, kk), dtype=np.int32)
-        score = np.zeros((Q, kk), dtype=np.float32)
-        align = np.zeros((Q, kk), dtype=np.float32)
+        ids, score, align = _bundle_arrays(Q, kk)
         iters = np.zeros(Q, dtype=np.int32)
         res = np.zeros(Q, dtype=np.float32)
         if Q > 0:
@@ -946,23 +969,13 @@ class OscillinkLattice:
                        int(max_iters), kk, float(alpha), 0.5, nat.i32(ids), nat.f32(score), nat.f32(align), nat.i32(iters),
                        nat.f32(res))
         if diffusion:
-            bad = np.nonzero(~np.all(np.isfinite(G), axis=1))[0]
-            if bad.size:
-                import warnings
-
-                warnings.warn(f"diffusion_gates_many: the screened-diffusion solve of query {int(bad[0])} produced "
-                              "non-finite values; returned as computed, like the reference's cg path", RuntimeWarning,
-                              stacklevel=2)
+            _warn_diffusion_gates(G)
         self.last_bundle_gated = {"iters": iters, "res": res, "converged": res <= np.float32(tol),
                                   "gates": G if diffusion else None}
         self._log("bundle_gated_many", {"Q": Q, "k": kk, "gates": "diffusion" if diffusion else "given",
                                         "iters_max": int(iters.max()) if Q else 0,
                                         "converged": int(np.count_nonzero(res <= np.float32(tol)))})
-        if as_arrays:
-            return ids, score, align
-        if Q == 0:
-            return []
-        return [rc.bundle_dicts(ids[q], score[q], align[q]) for q in range(Q)]
+        return _bundle_result(ids, score, align, as_arrays)
 
     def _ustar_gated_many(self, psis: np.ndarray, gates: np.ndarray, tol: float = 1e-4, max_iters: int = 256):
         """The solves of bundle_gated_many alone: (U (Q, N, D) float32 in API row order, iters (Q,) int32, res (Q,)
@@ -1009,36 +1022,8 @@ class OscillinkLattice:
         with `bundle_k` also `ids`, `score`, `align`.  Detail mode, OSCILLINK_RECEIPT_NULL_CAP, the secret and signature mode
         and OSCILLINK_RECEIPT_DYNAMICS behave as in `receipt_many`.  The report goes to `last_receipt_gated` = {"iters",
         "res", "converged", "settle_iters", "settle_res" (None without `settle`), "gates" (as `last_bundle_gated`)}."""
-        if self._has_comm:
-            raise NotImplementedError("receipt_gated_many: lattices with a communicator (sharded / multi-rank) are not "
-                                      "supported")
-        if self._chain_nodes is not None:
-            raise NotImplementedError("receipt_gated_many: a lattice with a chain of its own is not supported "
-                                      "(clear_chain first)")
-        P = rc.check_queries(psis, self.D, finite=False)
-        Q = int(P.shape[0])
-        diffusion = isinstance(gates, str)
-        if diffusion:
-            if gates != "diffusion":
-                raise ValueError(f"gates must be 'diffusion' or a ({Q}, {self.N}) array, got {gates!r}")
-            if not float(gate_gamma) > 0:
-                raise ValueError("gate_gamma must be > 0 for SPD")
-            if gate_method not in ("direct", "cg"):
-                raise ValueError(f"gate_method must be 'direct' or 'cg', got {gate_method!r}")
-            if int(gate_max_iters) < 1:
-                raise ValueError("gate_max_iters must be >= 1")
-            G = nat.result_array((Q, self.N)) if Q > 0 else np.zeros((0, self.N), dtype=np.float32)
-        else:
-            G = self._check_gate_rows(gates)
-            if G.shape[0] != Q:
-                raise ValueError(f"gates must be a ({Q}, {self.N}) array, got shape {G.shape}")
-            for q in range(Q):
-                if not np.all(np.isfinite(G[q])):
-                    raise ValueError(f"query {q}: gates must be finite")
-                if np.any(G[q] < 0):
-                    raise ValueError(f"query {q}: gates must be >= 0")
-        if int(max_iters) < 1:
-            raise ValueError("max_iters must be >= 1")
+        P, Q, G, diffusion = _gated_call_inputs(self, "receipt_gated_many", psis, gates, gate_gamma, gate_method,
+                                                gate_max_iters, max_iters)
         st = None
         if settle is not None and settle is not False:
             st = dict(self._GATED_SETTLE_DEFAULTS)
@@ -1060,9 +1045,7 @@ class OscillinkLattice:
         full = self._receipt_detail != "light"
         cap_val = rc.null_cap()
         ra = rc.ReceiptArrays(Q, (min(cap_val, self.N) if cap_val > 0 else self.N) if full else 0, settle=st is not None)
-        ids = np.zeros((Q, kk), dtype=np.int32)
-        score = np.zeros((Q, kk), dtype=np.float32)
-        align = np.zeros((Q, kk), dtype=np.float32)
+        ids, score, align = _bundle_arrays(Q, kk)
         iters = np.zeros(Q, dtype=np.int32)
         res = np.zeros(Q, dtype=np.float32)
         settle_ms, solve_ms = np.zeros(Q, dtype=np.float64), np.zeros(Q, dtype=np.float64)
@@ -1076,13 +1059,7 @@ class OscillinkLattice:
                        nat.i32(iters), nat.f32(res), settle_ms.ctypes.data_as(nat.c_f64p), solve_ms.ctypes.data_as(nat.c_f64p))
         ra.round_sums()
         if diffusion:
-            bad = np.nonzero(~np.all(np.isfinite(G), axis=1))[0]
-            if bad.size:
-                import warnings
-
-                warnings.warn(f"diffusion_gates_many: the screened-diffusion solve of query {int(bad[0])} produced "
-                              "non-finite values; returned as computed, like the reference's cg path", RuntimeWarning,
-                              stacklevel=2)
+            _warn_diffusion_gates(G)
         converged = res <= np.float32(tol)
         self.last_receipt_gated = {"iters": iters, "res": res, "converged": converged,
                                    "settle_iters": ra.settle[0] if st else None,
