@@ -455,6 +455,30 @@ int osc_receipt_gated_many(osc_handle h, const float* psis, int32_t Q, float* ga
                            double* query_sum, int32_t* null_total, int64_t* null_offsets, int32_t* i_out, int32_t* j_out,
                            float* z_out, float* r_out, int64_t capacity, int32_t* ids, float* score, float* align,
                            int32_t* iters_out, float* res_out, double* settle_ms, double* solve_ms);
+/* Not in the reference: the request sequence with per-query gates AND a per-query chain prior -- add_chain(chain_q, lamP,
+ * weights_q); set_query(psi_q, gates = g_q); [settle(...);] receipt(); chain_receipt(chain_q, chain_z_th); [bundle(k, alpha)]
+ * (lattice.py:129-149, 159-296, 298-455, 466-528, 530-568) -- for Q queries in one call on a handle without a chain of its
+ * own.  Everything but the chain arguments is osc_receipt_gated_many's, with its outputs; the
+ * diffusion gates are those of the lattice without the chain.  chain_offsets / chain_nodes are osc_chain_receipt_many's (a chain
+ * has 2 to 1024 nodes, repeats allowed, any number of distinct ones); chain_weights is NULL for ones or flat over the chains'
+ * edges like the per-edge outputs (build_path_laplacian's rules: the largest weight of a revisited edge, below zero counts as
+ * zero).  Query q's operator in the settle, the U* solve and deltaH is M_q = lamG I + lamC L_sym + lamQ diag(g_q) +
+ * lamP L_path,q, with the reference's Jacobi diagonal lamG + lamQ g + lamP; lamP == 0 leaves the operator alone, and every
+ * receipt and bundle output is then osc_receipt_gated_many's to the bit.  The chain outputs are osc_chain_receipt_many's, of
+ * U*_q from the call's own solve, the path residuals on the weighted path of the argument.  A query's outputs are the same to
+ * the bit whatever else the batch holds.  Errors as osc_receipt_gated_many; OSC_E_INVALID also for lamP < 0, chains outside
+ * the limits or non-finite weights. */
+int osc_chain_gated_many(osc_handle h, const float* psis, int32_t Q, float* gates, int32_t diffusion, float gate_beta,
+                         float gate_gamma, int32_t gate_method, float gate_tol, int32_t gate_max_iters,
+                         const int64_t* chain_offsets, const int32_t* chain_nodes, const float* chain_weights, float lamP,
+                         float chain_z_th, float tol, int32_t max_iters, int32_t settle, float dt, int32_t settle_max_iters,
+                         float settle_tol, int32_t detail, float z_th, int32_t null_cap, int32_t k, float alpha,
+                         float lambda_div, int32_t* settle_iters, float* settle_res, double* dH, double* coh_sum,
+                         double* anchor_sum, double* query_sum, int32_t* null_total, int64_t* null_offsets, int32_t* i_out,
+                         int32_t* j_out, float* z_out, float* r_out, int64_t capacity, int32_t* ids, float* score, float* align,
+                         int32_t* iters_out, float* res_out, double* settle_ms, double* solve_ms, float* chain_z_struct,
+                         float* chain_z_path, float* chain_r_struct, float* chain_r_path, double* chain_gain,
+                         int32_t* chain_verdict, int32_t* chain_weakest_k, float* chain_weakest_z);
 /* Not in the reference: receipt() (lattice.py:298-455, receipts.py:10-83) for Q queries psis (Q x D) with the current U,
  * gates, chain and lambdas held fixed, U*(psi) from the resident basis.  Per query: dH (deltaH_trace
  * of U against U*(psi_q)); with detail != 0 also coh_sum / anchor_sum / query_sum and the null points at z_th (else 0 and

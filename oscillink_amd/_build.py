@@ -8,8 +8,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "liboscillink_hip.so")
-SOURCES = ["osc_api.hip", "osc_runtime.hip", "osc_graph.hip", "osc_solve.hip", "osc_anchor_build.hip", "cg_kernels.hip", "knn_kernels.hip", "receipt_kernels.hip", "small_kernels.hip", "perm_kernels.hip", "comm.hip", "dynamics_kernels.hip", "knn_gemm.hip", "bfs_order.hip", "osc_query.hip", "query_kernels.hip", "receipt_many_kernels.hip", "osc_corpus.hip", "corpus_receipt_kernels.hip", "corpus_chain_kernels.hip", "chain_many_kernels.hip", "balance_kernels.hip", "corpus_store_kernels.hip", "append_kernels.hip", "remove_kernels.hip", "update_kernels.hip", "gates_many_kernels.hip", "bundle_gated_kernels.hip", "receipt_gated_kernels.hip", "bundle_prior_kernels.hip", "receipt_prior_kernels.hip"]
-HEADERS = ["osc_internal.hpp", "common.hpp", "host_logic.hpp", "derived_state.hpp", "loop_group.hpp", "knn.hpp", "knn_rowmap.hpp", "knn_plan.hpp", "receipts.hpp", "small.hpp", "small_plan.hpp", "perm.hpp", "comm.hpp", "dynamics.hpp", "knn_gemm.hpp", "query.hpp", "corpus_plan.hpp", "corpus_ragged.hpp", "corpus_settings.hpp", "corpus_store.hpp", "corpus_select.hpp", "corpus_pcg.hpp", "corpus_receipts.hpp", "corpus_chain.hpp", "chain_many.hpp", "block_balance.hpp", "chain_receipt_dev.hpp", "append.hpp", "append_plan.hpp", "remove.hpp", "remove_plan.hpp", "update.hpp", "update_plan.hpp", "anchor_gram.hpp", "gates_many.hpp", "gates_many_plan.hpp", "gates_many_dev.hpp", "bundle_gated.hpp", "bundle_gated_plan.hpp", "bundle_gated_dev.hpp", "receipt_gated.hpp", "receipt_gated_plan.hpp", "chain_prior_plan.hpp", "bundle_prior_plan.hpp", "bundle_prior_dev.hpp", "receipt_prior_plan.hpp", os.path.join("..", "..", "include", "oscillink_hip.h")]
+SOURCES = ["osc_api.hip", "osc_runtime.hip", "osc_graph.hip", "osc_solve.hip", "osc_anchor_build.hip", "cg_kernels.hip", "knn_kernels.hip", "receipt_kernels.hip", "small_kernels.hip", "perm_kernels.hip", "comm.hip", "dynamics_kernels.hip", "knn_gemm.hip", "bfs_order.hip", "osc_query.hip", "query_kernels.hip", "receipt_many_kernels.hip", "osc_corpus.hip", "corpus_receipt_kernels.hip", "corpus_chain_kernels.hip", "chain_many_kernels.hip", "balance_kernels.hip", "corpus_store_kernels.hip", "append_kernels.hip", "remove_kernels.hip", "update_kernels.hip", "gates_many_kernels.hip", "bundle_gated_kernels.hip", "receipt_gated_kernels.hip", "chain_gated_kernels.hip", "bundle_prior_kernels.hip", "receipt_prior_kernels.hip"]
+HEADERS = ["osc_internal.hpp", "common.hpp", "host_logic.hpp", "derived_state.hpp", "loop_group.hpp", "knn.hpp", "knn_rowmap.hpp", "knn_plan.hpp", "receipts.hpp", "small.hpp", "small_plan.hpp", "perm.hpp", "comm.hpp", "dynamics.hpp", "knn_gemm.hpp", "query.hpp", "corpus_plan.hpp", "corpus_ragged.hpp", "corpus_settings.hpp", "corpus_store.hpp", "corpus_select.hpp", "corpus_pcg.hpp", "corpus_receipts.hpp", "corpus_chain.hpp", "chain_many.hpp", "block_balance.hpp", "chain_receipt_dev.hpp", "append.hpp", "append_plan.hpp", "remove.hpp", "remove_plan.hpp", "update.hpp", "update_plan.hpp", "anchor_gram.hpp", "gates_many.hpp", "gates_many_plan.hpp", "gates_many_dev.hpp", "bundle_gated.hpp", "bundle_gated_plan.hpp", "bundle_gated_dev.hpp", "receipt_gated.hpp", "receipt_gated_plan.hpp", "chain_gated.hpp", "chain_gated_plan.hpp", "chain_gated_dev.hpp", "chain_edges_dev.hpp", "chain_prior_plan.hpp", "bundle_prior_plan.hpp", "bundle_prior_dev.hpp", "receipt_prior_plan.hpp", os.path.join("..", "..", "include", "oscillink_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # kernel A/B experiments: OSC_BUILD_DEFINES="FOO BAR=1" adds -DFOO -DBAR=1 (part of the stamp)
 FLAGS += [f"-D{d}" for d in os.environ.get("OSC_BUILD_DEFINES", "").split()]

@@ -117,6 +117,11 @@ SIGNATURES = {
                                          C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_float, C.c_int32,
                                          C.c_float, C.c_int32, C.c_int32, C.c_float, C.c_float, c_i32p, c_f32p,
                                          *_RECEIPT_MANY_OUT, c_i32p, c_f32p, c_f32p, c_i32p, c_f32p, c_f64p, c_f64p]),
+    "osc_chain_gated_many": (C.c_int, [Handle, c_f32p, C.c_int32, c_f32p, C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_float,
+                                       C.c_int32, c_i64p, c_i32p, c_f32p, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32,
+                                       C.c_float, C.c_int32, C.c_float, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_float,
+                                       C.c_float, c_i32p, c_f32p, *_RECEIPT_MANY_OUT, c_i32p, c_f32p, c_f32p, c_i32p, c_f32p,
+                                       c_f64p, c_f64p, c_f32p, c_f32p, c_f32p, c_f32p, c_f64p, c_i32p, c_i32p, c_f32p]),
     "osc_mmr_many": (C.c_int, [Handle, c_f32p, C.c_int32, C.c_int32, C.c_float, c_i32p]),
     "osc_receipt_many": (C.c_int, [Handle, c_f32p, C.c_int32, C.c_int32, C.c_float, C.c_int32, *_RECEIPT_MANY_OUT]),
     "osc_chain_receipt_many": (C.c_int, [Handle, c_f32p, C.c_int32, c_i64p, c_i32p, C.c_float, c_f32p, c_f32p, c_f32p, c_f32p,

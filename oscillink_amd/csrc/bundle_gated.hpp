@@ -11,6 +11,9 @@
 
 namespace osc {
 
+struct CgChain;  // chain_gated.hpp: a chunk's chain priors; nullptr for a call without them
+struct CgPrior;
+
 // one chunk's arrays (pointers into the scratch block at GatedLayout's offsets)
 struct BgPanel {
   float* X;
@@ -36,13 +39,14 @@ struct BgPanel {
 void launch_bg_gates(const float* gate_api, const int32_t* api_id, int32_t N, int32_t nq, float* gate, hipStream_t s);
 // x = Y, r = RHS - M_q Y = lamQ g (psi - y) + lamC (W y - y) formed on the fly from the anchors (N x ld, device rows),
 // p = z = r / (lamG + lamQ g + 1e-12); part_a: r . z
-void launch_bg_init(const BgPanel& p, const GmGraph& g, const float* Y, int32_t ld, hipStream_t s);
-// rz per column from those sums; every query live, iters = 0; n_live = 0
-void launch_bg_start(const BgPanel& p, hipStream_t s);
+// (prior: chain_gated.hpp's form with -cP y on every row)
+void launch_bg_init(const BgPanel& p, const GmGraph& g, const float* Y, int32_t ld, hipStream_t s, const CgPrior* prior = nullptr);
+// rz per column from those sums (with chain: and the fix units' behind them); every query live, iters = 0; n_live = 0
+void launch_bg_start(const BgPanel& p, hipStream_t s, const CgChain* chain = nullptr);
 // AP = (lamG + lamC + lamQ g) p - lamC W p over the live queries' slabs; part_a: p . Ap
 void launch_bg_apply(const BgPanel& p, const GmGraph& g, hipStream_t s);
-// alpha = rz / (p . Ap + 1e-18) per column of a live query
-void launch_bg_alpha(const BgPanel& p, hipStream_t s);
+// alpha = rz / (p . Ap + 1e-18) per column of a live query (with chain: p . Ap with the fix units' share, added in unit order)
+void launch_bg_alpha(const BgPanel& p, hipStream_t s, const CgChain* chain = nullptr);
 // x += alpha p, r -= alpha Ap over the live queries' slabs; part_a: r . r, part_b: r . z
 void launch_bg_update(const BgPanel& p, hipStream_t s);
 // per live query: res = max over its columns of sqrt(r . r), slabs and columns in order (a NaN stays); records (it, res) and

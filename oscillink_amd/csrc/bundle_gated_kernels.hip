@@ -7,7 +7,7 @@
 // gates' solve is the diagonal, indexed by (row, query of the slab), the start at x0 = Y with the initial residual formed
 // on the fly from the anchors, and the stop: the largest column residual of a QUERY decides for all its columns.  Nothing
 // depends on which other queries fill the panel, so a query's answers are the same to the bit in any batch or chunk.
-#include "bundle_gated_dev.hpp"
+#include "chain_gated_dev.hpp"
 
 namespace osc {
 namespace {
@@ -21,8 +21,11 @@ __global__ __launch_bounds__(256) void k_bg_gates(const float* __restrict__ gate
 }
 
 // The gather of k_gm_apply over the anchors (row-major, pitch ld) instead of a slab: r0 = RHS - M_q Y without a stored RHS.
-// lamG Y cancels, so r0 = lamQ g (psi - y) + lamC (W y - y).
-__global__ __launch_bounds__(256) void k_bg_init(const BgPanel p, const GmGraph g, const float* __restrict__ Y, int32_t ld) {
+// lamG Y cancels, so r0 = lamQ g (psi - y) + lamC (W y - y).  With a prior (chain_gated.hpp) the panel's lamG carries lamP and
+// every row adds -lamP y; the chain rows' share is launch_cg_path_init's.
+template <class Prior>
+__global__ __launch_bounds__(256) void k_bg_init(const BgPanel p, const GmGraph g, const float* __restrict__ Y, int32_t ld,
+                                                 const Prior pr) {
   __shared__ double sh[1024];
   const int slab = blockIdx.y, q = slab / p.spq, cq = (slab % p.spq) * 32;
   const int t = threadIdx.x, lane = t & 63, lr = lane & 7, g0 = lane & ~7;
@@ -69,6 +72,7 @@ __global__ __launch_bounds__(256) void k_bg_init(const BgPanel p, const GmGraph 
       r.y = fmaf(qg, ps.y - y.y, lc * (sum.y - y.y));
       r.z = fmaf(qg, ps.z - y.z, lc * (sum.z - y.z));
       r.w = fmaf(qg, ps.w - y.w, lc * (sum.w - y.w));
+      if constexpr (Prior::active) r = mulacc4(f4(-pr.cP), y, r);
       const float4 z = scale4(r, inv_md);
       const size_t o = so + (size_t)row * 32 + lr * 4;
       st4(p.X + o, y);
@@ -80,10 +84,12 @@ __global__ __launch_bounds__(256) void k_bg_init(const BgPanel p, const GmGraph 
   gm_fold(rz, sh, p.part_a + gm_part_at(p));
 }
 
-__global__ __launch_bounds__(kGmSumThreads) void k_bg_start(const BgPanel p) {
+template <class Chain>
+__global__ __launch_bounds__(kGmSumThreads) void k_bg_start(const BgPanel p, const Chain ch) {
   __shared__ double sh[kGmSumThreads];
   const int slab = blockIdx.x, t = threadIdx.x;
-  const double rz = gm_part_sum(p.part_a + (size_t)slab * p.parts * 32, p.parts, sh);
+  double rz = gm_part_sum(p.part_a + (size_t)slab * p.parts * 32, p.parts, sh);
+  if constexpr (Chain::active) rz += cg_unit_sum(ch, slab, slab / p.spq);
   if (t < 32) {
     const int c = slab * 32 + t;
     p.rz[c] = rz;
@@ -156,11 +162,13 @@ __global__ __launch_bounds__(256) void k_bg_apply(const BgPanel p, const GmGraph
   gm_fold(pap, sh, p.part_a + gm_part_at(p));
 }
 
-__global__ __launch_bounds__(kGmSumThreads) void k_bg_alpha(const BgPanel p) {
+template <class Chain>
+__global__ __launch_bounds__(kGmSumThreads) void k_bg_alpha(const BgPanel p, const Chain ch) {
   __shared__ double sh[kGmSumThreads];
   const int slab = blockIdx.x, t = threadIdx.x;
   if (p.live[slab / p.spq] == 0) return;
-  const double pap = gm_part_sum(p.part_a + (size_t)slab * p.parts * 32, p.parts, sh);
+  double pap = gm_part_sum(p.part_a + (size_t)slab * p.parts * 32, p.parts, sh);
+  if constexpr (Chain::active) pap += cg_unit_sum(ch, slab, slab / p.spq);
   if (t < 32) {
     const int c = slab * 32 + t;
     p.alpha[c] = (float)(p.rz[c] / (pap + 1e-18));  // solver.py:25-26 (a pad column: 0 / 1e-18)
@@ -324,13 +332,15 @@ void launch_bg_gates(const float* gate_api, const int32_t* api_id, int32_t N, in
   HIP_CHECK(hipGetLastError());
 }
 
-void launch_bg_init(const BgPanel& p, const GmGraph& g, const float* Y, int32_t ld, hipStream_t s) {
-  hipLaunchKernelGGL(k_bg_init, bg_grid(p), dim3(256), 0, s, p, g, Y, ld);
+void launch_bg_init(const BgPanel& p, const GmGraph& g, const float* Y, int32_t ld, hipStream_t s, const CgPrior* prior) {
+  if (prior) hipLaunchKernelGGL(k_bg_init<CgPrior>, bg_grid(p), dim3(256), 0, s, p, g, Y, ld, *prior);
+  else hipLaunchKernelGGL(k_bg_init<CgNoPrior>, bg_grid(p), dim3(256), 0, s, p, g, Y, ld, CgNoPrior{});
   HIP_CHECK(hipGetLastError());
 }
 
-void launch_bg_start(const BgPanel& p, hipStream_t s) {
-  hipLaunchKernelGGL(k_bg_start, dim3((unsigned)p.slabs), dim3(kGmSumThreads), 0, s, p);
+void launch_bg_start(const BgPanel& p, hipStream_t s, const CgChain* chain) {
+  if (chain) hipLaunchKernelGGL(k_bg_start<CgChain>, dim3((unsigned)p.slabs), dim3(kGmSumThreads), 0, s, p, *chain);
+  else hipLaunchKernelGGL(k_bg_start<CgNoChain>, dim3((unsigned)p.slabs), dim3(kGmSumThreads), 0, s, p, CgNoChain{});
   HIP_CHECK(hipGetLastError());
 }
 
@@ -339,8 +349,9 @@ void launch_bg_apply(const BgPanel& p, const GmGraph& g, hipStream_t s) {
   HIP_CHECK(hipGetLastError());
 }
 
-void launch_bg_alpha(const BgPanel& p, hipStream_t s) {
-  hipLaunchKernelGGL(k_bg_alpha, dim3((unsigned)p.slabs), dim3(kGmSumThreads), 0, s, p);
+void launch_bg_alpha(const BgPanel& p, hipStream_t s, const CgChain* chain) {
+  if (chain) hipLaunchKernelGGL(k_bg_alpha<CgChain>, dim3((unsigned)p.slabs), dim3(kGmSumThreads), 0, s, p, *chain);
+  else hipLaunchKernelGGL(k_bg_alpha<CgNoChain>, dim3((unsigned)p.slabs), dim3(kGmSumThreads), 0, s, p, CgNoChain{});
   HIP_CHECK(hipGetLastError());
 }
 

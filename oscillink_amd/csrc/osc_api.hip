@@ -1342,6 +1342,39 @@ int osc_receipt_gated_many(osc_handle h, const float* psis, int32_t Q, float* ga
   });
 }
 
+int osc_chain_gated_many(osc_handle h, const float* psis, int32_t Q, float* gates, int32_t diffusion, float gate_beta,
+                         float gate_gamma, int32_t gate_method, float gate_tol, int32_t gate_max_iters,
+                         const int64_t* chain_offsets, const int32_t* chain_nodes, const float* chain_weights, float lamP,
+                         float chain_z_th, float tol, int32_t max_iters, int32_t settle, float dt, int32_t settle_max_iters,
+                         float settle_tol, int32_t detail, float z_th, int32_t null_cap, int32_t k, float alpha,
+                         float lambda_div, int32_t* settle_iters, float* settle_res, double* dH, double* coh_sum,
+                         double* anchor_sum, double* query_sum, int32_t* null_total, int64_t* null_offsets, int32_t* i_out,
+                         int32_t* j_out, float* z_out, float* r_out, int64_t capacity, int32_t* ids, float* score, float* align,
+                         int32_t* iters_out, float* res_out, double* settle_ms, double* solve_ms, float* chain_z_struct,
+                         float* chain_z_path, float* chain_r_struct, float* chain_r_path, double* chain_gain,
+                         int32_t* chain_verdict, int32_t* chain_weakest_k, float* chain_weakest_z) {
+  return guarded(h, [&](L& l) {
+    if (Q < 0) throw Invalid("osc_chain_gated_many: Q must be >= 0");
+    if (Q > 0 && (!psis || !gates || !chain_offsets || !chain_nodes)) throw Invalid("osc_chain_gated_many: NULL buffer");
+    if (Q > 0 && (!dH || !coh_sum || !anchor_sum || !query_sum || !null_total || !null_offsets || !solve_ms))
+      throw Invalid("osc_chain_gated_many: NULL buffer");
+    if (Q > 0 && (!chain_z_struct || !chain_z_path || !chain_r_struct || !chain_r_path || !chain_gain || !chain_verdict ||
+                  !chain_weakest_k || !chain_weakest_z))
+      throw Invalid("osc_chain_gated_many: NULL buffer");
+    if (Q > 0 && settle && (!settle_iters || !settle_res || !settle_ms)) throw Invalid("osc_chain_gated_many: NULL buffer");
+    if (Q > 0 && settle && !(dt > 0)) throw Invalid("osc_chain_gated_many: dt must be > 0");
+    if (Q > 0 && k > 0 && (!ids || !score || !align)) throw Invalid("osc_chain_gated_many: NULL buffer");
+    query_chain_gated_many(l, psis, Q, gates, diffusion, gate_beta, gate_gamma, gate_method, gate_tol, gate_max_iters,
+                           chain_offsets, chain_nodes, chain_weights, lamP, chain_z_th, tol, max_iters, settle, dt,
+                           settle_max_iters, settle_tol, detail, z_th, null_cap, k, alpha, lambda_div, settle_iters, settle_res,
+                           ReceiptManyOut{dH, coh_sum, anchor_sum, query_sum, null_total, null_offsets, i_out, j_out, z_out, r_out,
+                                          capacity},
+                           ChainManyOut{chain_z_struct, chain_z_path, chain_r_struct, chain_r_path, chain_gain, chain_verdict,
+                                        chain_weakest_k, chain_weakest_z},
+                           ids, score, align, iters_out, res_out, settle_ms, solve_ms);
+  });
+}
+
 int osc_receipt_many(osc_handle h, const float* psis, int32_t Q, int32_t detail, float z_th, int32_t null_cap, double* dH,
                      double* coh_sum, double* anchor_sum, double* query_sum, int32_t* null_total, int64_t* null_offsets,
                      int32_t* i_out, int32_t* j_out, float* z_out, float* r_out, int64_t capacity) {

@@ -40,6 +40,7 @@
 #include "gates_many.hpp"
 #include "bundle_gated.hpp"
 #include "receipt_gated.hpp"
+#include "chain_gated.hpp"
 #include "chain_prior_plan.hpp"
 #include "bundle_prior_plan.hpp"
 #include "receipt_prior_plan.hpp"
@@ -590,6 +591,15 @@ void query_receipt_gated_many(L& l, const float* psis, int32_t Q, float* gates, 
                               int32_t detail, float z_th, int32_t null_cap, int32_t k, float alpha, float lambda_div,
                               int32_t* settle_iters, float* settle_res, const ReceiptManyOut& o, int32_t* ids, float* score,
                               float* align, int32_t* iters_out, float* res_out, double* settle_ms, double* solve_ms);
+// osc_chain_gated_many (chain_gated.hpp)
+void query_chain_gated_many(L& l, const float* psis, int32_t Q, float* gates, int32_t diffusion, float gate_beta,
+                            float gate_gamma, int32_t gate_method, float gate_tol, int32_t gate_max_iters,
+                            const int64_t* chain_offsets, const int32_t* chain_nodes, const float* chain_weights, float lamP,
+                            float chain_z_th, float tol, int32_t max_iters, int32_t settle, float dt,
+                            int32_t settle_max_iters, float settle_tol, int32_t detail, float z_th, int32_t null_cap,
+                            int32_t k, float alpha, float lambda_div, int32_t* settle_iters, float* settle_res,
+                            const ReceiptManyOut& o, const ChainManyOut& co, int32_t* ids, float* score, float* align,
+                            int32_t* iters_out, float* res_out, double* settle_ms, double* solve_ms);
 
 struct ProfScope {
   L& h;

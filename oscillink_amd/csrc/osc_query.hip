@@ -1,14 +1,15 @@
 // Multi-query bundles and receipts (DESIGN.md sections 11, 12 and 17): the query basis solves (osc_query_basis,
-// osc_query_basis_shifted, osc_get_query_basis) and the drivers of the nine batched calls (see osc_internal.hpp), in this order:
+// osc_query_basis_shifted, osc_get_query_basis) and the drivers of the ten batched calls (see osc_internal.hpp), in this order:
 // osc_bundle_many and osc_mmr_many (11), osc_receipt_many (12), osc_chain_receipt_many (12.1), the three calls under per-query
 // chain priors -- osc_chain_prior_many (12.2), osc_bundle_prior_many (11.1), osc_receipt_prior_many (12.3) -- osc_gates_many
-// (17), and the two under per-query gates, osc_bundle_gated_many (11.2, also osc_ustar_gated_many) and osc_receipt_gated_many
-// (12.4).
+// (17), the two under per-query gates, osc_bundle_gated_many (11.2, also osc_ustar_gated_many) and osc_receipt_gated_many
+// (12.4), and osc_chain_gated_many (12.5), which is the latter's chunks with a chain prior per query.
 //
 // Each step of a chunk has one home, in the anonymous namespaces ahead of its first driver: stage_queries (with stage_pass_psi
 // on request) and launch_query_dots; bundle_alloc and bundle_tail; rm_col_base, receipt_call_terms, receipt_light_chunk and
 // receipt_null_stage; chain_upload_paths, chain_upload_units and chain_edge_stage; chain_prior_panel_stage and its call
-// prelude; gated_call_check, gated_call_setup, gated_ustar_solve and gated_bundle_stage.  The callers' output arrays travel as
+// prelude; gated_call_check, gated_call_setup, gated_panel_pcg, gated_ustar_solve and gated_bundle_stage; chain_gated_upload
+// and receipt_gated_chunks, the chunk loop the two gated receipt calls share.  The callers' output arrays travel as
 // ReceiptManyOut and ChainManyOut.
 //
 // For the lattice's graph, gates, chain and lambdas, U*(psi) = X + x psi^T with M X = lamG Y and M x = lamQ B, so one
@@ -818,10 +819,11 @@ void chain_upload_units(L& l, const std::vector<host::ChainManyUnit>& units, con
 }
 
 // The edge stage of a chunk, queries [c0, c0 + nq) with their rows in q.cm_psi, their nu units and the paths uploaded: the
-// gather kernel over the units on basis b -- with po the correction of a chain-prior pass on every gathered row -- the finish
-// kernel over the queries and the eight copies out.  The caller syncs.
+// gather kernel over the units on basis b -- with po the correction of a chain-prior pass on every gathered row; with `panel`
+// the rows of U*_q come from that solved gated panel instead (chain_gated.hpp) and b is not read -- the finish kernel over the
+// queries and the eight copies out.  The caller syncs.
 void chain_edge_stage(L& l, const BasisView& b, const CpPanelOut* po, int32_t c0, int32_t nq, size_t nu, float z_th,
-                      const int64_t* chain_offsets, const ChainManyOut& o) {
+                      const int64_t* chain_offsets, const ChainManyOut& o, const float* panel = nullptr) {
   auto& q = l.query;
   CmEdgesArgs e{};
   if (po) {
@@ -833,7 +835,7 @@ void chain_edge_stage(L& l, const BasisView& b, const CpPanelOut* po, int32_t c0
     e.TV = q.cp_tv.p;
     e.tv_at = po->tv_at;
   }
-  e.X = b.X;
+  e.X = panel ? panel : b.X;
   e.x4 = b.x4;
   e.Y = l.Y.p;
   e.sqrt_deg = l.sqrt_deg.p;
@@ -856,7 +858,8 @@ void chain_edge_stage(L& l, const BasisView& b, const CpPanelOut* po, int32_t c0
   e.r_path = q.cm_edge.p + 3 * nu;
   e.term = q.cm_term.p;
   e.zmax = q.cm_term.p + nu;
-  if (po) launch_cm_edges_prior(e, l.stream);
+  if (panel) launch_cg_edges(e, l.stream);
+  else if (po) launch_cm_edges_prior(e, l.stream);
   else launch_cm_edges(e, l.stream);
   CmFinishArgs f{};
   f.eoff = q.cm_eoff.p;
@@ -1760,12 +1763,22 @@ void gated_panel_inputs(L& l, const BgPanel& p, char* base, const host::GatedLay
   launch_bg_gates(gate_api, permuted(l) ? l.perm_d.p : nullptr, N, nq, const_cast<float*>(p.gate), l.stream);
 }
 
-// cg_solve's loop (solver.py:23-37) over an initialised panel: the stop per query, at most max_iters iterations
-void gated_panel_pcg(L& l, const BgPanel& p, const GmGraph& g, int32_t max_iters) {
-  launch_bg_start(p, l.stream);
+// a chunk's chain priors in a panel solve: the paths on the device and the path term's factor --
+// lamP for M_q, dt lamP for the settle's I + dt M_q.  The panel it goes with carries lamP in its lamG.
+struct GatedChain {
+  CgChain dev;
+  float cP;
+};
+
+// cg_solve's loop (solver.py:23-37) over an initialised panel: the stop per query, at most max_iters iterations; with
+// `chain` the path term behind every apply and its sums beside the panel's
+void gated_panel_pcg(L& l, const BgPanel& p, const GmGraph& g, int32_t max_iters, const GatedChain* chain = nullptr) {
+  const CgChain* const ch = chain ? &chain->dev : nullptr;
+  launch_bg_start(p, l.stream, ch);
   for (int32_t it = 1; it <= max_iters; ++it) {
     launch_bg_apply(p, g, l.stream);
-    launch_bg_alpha(p, l.stream);
+    if (chain) launch_cg_path_apply(p, chain->dev, chain->cP, l.stream);
+    launch_bg_alpha(p, l.stream, ch);
     launch_bg_update(p, l.stream);
     launch_bg_beta(p, it, l.stream);
     int32_t live = 0;
@@ -1835,11 +1848,18 @@ GatedCall gated_call_setup(L& l, const float* psis, int32_t Q, float* gates, int
   return gc;
 }
 
-// section 11.2's U* solve of a chunk's panel, with the iteration counts and residuals of queries [q0, q0 + nq) copied out
+// section 11.2's U* solve of a chunk's panel, with the iteration counts and residuals of queries [q0, q0 + nq) copied out;
+// with `chain` (cP = lamP) the start residual carries the prior as well
 void gated_ustar_solve(L& l, const BgPanel& p, const GmGraph& g, int32_t max_iters, int32_t q0, int32_t* iters_out,
-                       float* res_out) {
-  launch_bg_init(p, g, l.Y.p, l.ld, l.stream);
-  gated_panel_pcg(l, p, g, max_iters);
+                       float* res_out, const GatedChain* chain = nullptr) {
+  if (chain) {
+    const CgPrior prior{chain->cP};
+    launch_bg_init(p, g, l.Y.p, l.ld, l.stream, &prior);
+    launch_cg_path_init(p, chain->dev, l.Y.p, l.ld, chain->cP, l.stream);
+  } else {
+    launch_bg_init(p, g, l.Y.p, l.ld, l.stream);
+  }
+  gated_panel_pcg(l, p, g, max_iters, chain);
   if (iters_out) HIP_CHECK(hipMemcpyAsync(iters_out + q0, p.iters, (size_t)p.nq * 4, hipMemcpyDeviceToHost, l.stream));
   if (res_out) HIP_CHECK(hipMemcpyAsync(res_out + q0, p.res, (size_t)p.nq * 4, hipMemcpyDeviceToHost, l.stream));
 }
@@ -1903,33 +1923,120 @@ void query_bundle_gated_many(L& l, const float* psis, int32_t Q, float* gates, i
 // 11.2's U* solve; deltaH as the quadratic form of U_q - U*_q through the panel apply; in full detail the components and the
 // null points of U*_q (receipt_gated_kernels.hip, then osc_receipt_many's selection); with k > 0 section 11.2's bundle from
 // the same solve.  U is read; nothing of the handle's state is written.
-void query_receipt_gated_many(L& l, const float* psis, int32_t Q, float* gates, int32_t diffusion, float gate_beta,
-                              float gate_gamma, int32_t gate_method, float gate_tol, int32_t gate_max_iters, float tol,
-                              int32_t max_iters, int32_t settle, float dt, int32_t settle_max_iters, float settle_tol,
-                              int32_t detail, float z_th, int32_t null_cap, int32_t k, float alpha, float lambda_div,
-                              int32_t* settle_iters, float* settle_res, const ReceiptManyOut& o, int32_t* ids, float* score,
-                              float* align, int32_t* iters_out, float* res_out, double* settle_ms, double* solve_ms) {
-  gated_call_check(l, "osc_receipt_gated_many", max_iters);
-  if (settle && settle_max_iters < 1) throw Invalid("osc_receipt_gated_many: the settle's max_iters must be >= 1");
-  if (o.null_offsets) o.null_offsets[0] = 0;
-  if (Q <= 0) return;
-  const GatedCall gc = gated_call_setup(l, psis, Q, gates, diffusion, gate_beta, gate_gamma, gate_method, gate_tol,
-                                        gate_max_iters);
-  const bool full = detail != 0, settled = settle != 0;
+namespace {
+
+// the chains of an osc_chain_gated_many call: the caller's (checked) chains, the prior's weight and
+// where the chain receipts go
+struct ChainGatedCall {
+  const int64_t* offsets;
+  const int32_t* nodes;
+  const float* weights;  // flat over the chains' edges, or nullptr for ones
+  float lamP, z_th;
+  ChainManyOut out;
+};
+
+// a chunk's paths, units and per-query path rows (queries [q0, q0 + nq)) to the device: ChainManyPaths' columns and A_path and
+// the units by the stages of osc_chain_receipt_many, the rest at the layout's offsets
+struct ChainGatedHost {
+  host::ChainManyPaths paths;
+  std::vector<host::ChainManyUnit> units;
+  std::vector<int32_t> eoff, path_of;
+  host::ChainGatedPack pack;
+};
+CgChain chain_gated_upload(L& l, const ChainGatedCall& cc, int32_t q0, int32_t nq, char* base,
+                           const host::ChainGatedLayout& lay, ChainGatedHost& hs) {
+  auto& q = l.query;
+  hs.paths.clear();
+  host::chain_many_units_weighted(cc.offsets, cc.nodes, cc.weights, q0, nq, permuted(l) ? l.inv_h.data() : nullptr, (int32_t)l.N,
+                                  hs.paths, hs.units, hs.eoff, hs.path_of);
+  chain_upload_paths(l, hs.paths);
+  chain_upload_units(l, hs.units, hs.eoff);
+  host::chain_gated_pack(hs.paths, hs.path_of, hs.pack);
+  const host::ChainGatedPack& k = hs.pack;
+  if (k.max_units > lay.max_units || (int64_t)k.prow.size() * 4 > lay.pbeg - lay.prow ||
+      (int64_t)k.pw.size() * 4 > lay.q_row0 - lay.pw)
+    throw std::logic_error("osc_chain_gated_many: the chunk's paths pass their layout");
+  auto put = [&](int64_t at, const void* src, size_t bytes) {
+    if (bytes) HIP_CHECK(hipMemcpyAsync(base + at, src, bytes, hipMemcpyHostToDevice, l.stream));
+  };
+  put(lay.prow, k.prow.data(), k.prow.size() * 4);
+  put(lay.pbeg, k.pbeg.data(), k.pbeg.size() * 4);
+  put(lay.pend, k.pend.data(), k.pend.size() * 4);
+  put(lay.pw, k.pw.data(), k.pw.size() * 4);
+  put(lay.q_row0, k.q_row0.data(), k.q_row0.size() * 4);
+  put(lay.q_rows, k.q_rows.data(), k.q_rows.size() * 4);
+  CgChain ch{};
+  ch.prow = reinterpret_cast<const int32_t*>(base + lay.prow);
+  ch.pbeg = reinterpret_cast<const int32_t*>(base + lay.pbeg);
+  ch.pend = reinterpret_cast<const int32_t*>(base + lay.pend);
+  ch.pcol = q.cm_pcol.p;
+  ch.pw = reinterpret_cast<const float*>(base + lay.pw);
+  ch.q_row0 = reinterpret_cast<const int32_t*>(base + lay.q_row0);
+  ch.q_rows = reinterpret_cast<const int32_t*>(base + lay.q_rows);
+  ch.part = reinterpret_cast<double*>(base + lay.cpart);
+  ch.max_units = lay.max_units;
+  ch.grid_units = k.max_units;
+  return ch;
+}
+
+// what the two gated receipt calls ask of the chunk loop, in their entry points' names: the queries and gates, the U* solve,
+// the settle (settle != 0), the receipt's detail and null points, the bundle (k > 0) and where the answers go
+struct GatedReceiptCall {
+  const float* psis;
+  int32_t Q;
+  float* gates;
+  float tol;
+  int32_t max_iters, settle;
+  float dt;
+  int32_t settle_max_iters;
+  float settle_tol;
+  int32_t detail;
+  float z_th;
+  int32_t null_cap, k;
+  float alpha, lambda_div;
+  int32_t* settle_iters;
+  float* settle_res;
+  ReceiptManyOut o;
+  int32_t* ids;
+  float *score, *align;
+  int32_t* iters_out;
+  float* res_out;
+  double *settle_ms, *solve_ms;
+};
+
+// The chunks of osc_receipt_gated_many (cc == nullptr: its launch sequence as it was) and of osc_chain_gated_many: with cc
+// query q's operator carries its chain prior in the settle, the U* solve and deltaH, and the chunk ends with the chain
+// receipts from the solved panel.  cc->lamP == 0 leaves the operator alone (lattice.py:180, 253).
+void receipt_gated_chunks(L& l, const char* fn, const GatedReceiptCall& a, const GatedCall& gc, const ChainGatedCall* cc) {
+  const float* const psis = a.psis;
+  float* const gates = a.gates;
+  const int32_t Q = a.Q, max_iters = a.max_iters, settle_max_iters = a.settle_max_iters, null_cap = a.null_cap, k = a.k;
+  const float tol = a.tol, dt = a.dt, settle_tol = a.settle_tol, z_th = a.z_th, alpha = a.alpha, lambda_div = a.lambda_div;
+  int32_t *const settle_iters = a.settle_iters, *const ids = a.ids, *const iters_out = a.iters_out;
+  float *const settle_res = a.settle_res, *const score = a.score, *const align = a.align, *const res_out = a.res_out;
+  double *const settle_ms = a.settle_ms, *const solve_ms = a.solve_ms;
+  const ReceiptManyOut& o = a.o;
+  const bool full = a.detail != 0, settled = a.settle != 0;
   const int32_t N = (int32_t)l.N, D = l.D, spq = gc.spq;
   const GmGraph& g = gc.g;
   const int32_t kk = (int32_t)std::min<int64_t>(std::max(k, 0), l.N);
-  const int32_t chunk = host::receipt_gated_chunk(N, D, settled, full, gc.requested, host::kGatedBudgetBytes);
+  const int32_t max_len = cc ? host::chain_gated_max_len(cc->offsets, Q) : 0;
+  const bool prior = cc && cc->lamP > 0.f;
+  const int32_t chunk = cc ? host::chain_gated_chunk(N, D, settled, full, max_len, gc.requested, host::kGatedBudgetBytes)
+                           : host::receipt_gated_chunk(N, D, settled, full, gc.requested, host::kGatedBudgetBytes);
   DevBuf<char> scratch;
-  scratch.alloc((size_t)host::receipt_gated_layout(N, D, std::min(chunk, Q), settled, full).total);
+  scratch.alloc((size_t)(cc ? host::chain_gated_layout(N, D, std::min(chunk, Q), settled, full, max_len).total
+                            : host::receipt_gated_layout(N, D, std::min(chunk, Q), settled, full).total));
   auto& q = l.query;
+  ChainGatedHost chs;
+  if (cc) chain_scratch_alloc(l);
   DevBuf<double> ysum;
   if (kk > 0) bundle_alloc(l, kk);
   if (kk > 0 || full) ysum.alloc((size_t)N);
   const int cparts = rm_col_parts(l.N);
   static_assert(host::kReceiptGatedFinishRows == kRmFinishRows, "the plan sizes launch_rm_colfinish's scratch");
   if (full) {
-    if (cparts != host::receipt_gated_sum_parts(N)) throw std::logic_error("osc_receipt_gated_many: sum parts");
+    if (cparts != host::receipt_gated_sum_parts(N)) throw std::logic_error(std::string(fn) + ": sum parts");
     q.rtot.alloc(kQueryChunk);
     q.rsel.alloc(kQueryChunk);
     q.roff.alloc(kQueryChunk);
@@ -1940,22 +2047,36 @@ void query_receipt_gated_many(L& l, const float* psis, int32_t Q, float* gates, 
   bool have_ysum = false;
   for (int32_t c = 0; c < host::gates_chunk_count(Q, chunk); ++c) {
     const int32_t q0 = host::gates_chunk_begin(c, chunk), nq = host::gates_chunk_size(Q, c, chunk);
-    const host::ReceiptGatedLayout lay = host::receipt_gated_layout(N, D, nq, settled, full);
+    host::ChainGatedLayout clay{};
+    if (cc) clay = host::chain_gated_layout(N, D, nq, settled, full, max_len);
+    const host::ReceiptGatedLayout lay = cc ? clay.rg : host::receipt_gated_layout(N, D, nq, settled, full);
     char* const base = scratch.p;
     BgPanel p = gated_panel(l, base, lay.panel, nq, spq, tol);
     gated_panel_inputs(l, p, base, lay.panel, psis, gates, q0, hpsi);
+    // with a prior the solves' panels carry lamP in lamG (the flat Jacobi diagonal) and the path term's factor beside them
+    GatedChain chain{};
+    if (cc) chain.dev = chain_gated_upload(l, *cc, q0, nq, base, clay, chs);
+    const float lamGP = prior ? l.lamG + cc->lamP : l.lamG;
     const float* Us = nullptr;
     if (settled) {
       // (I + dt M_q) is the panel operator with primed lambdas: every kernel of the solve runs on them as it is
       BgPanel ps = p;
-      ps.lamG = 1.0f + dt * l.lamG;
+      ps.lamG = 1.0f + dt * lamGP;
       ps.lamC = dt * l.lamC;
       ps.lamQ = dt * l.lamQ;
       ps.tol = settle_tol;
       sync(l);
       const double t0 = now_ms();
-      launch_rg_settle_init(ps, g, U, l.Y.p, l.ld, dt, l.lamG, l.lamC, l.lamQ, l.stream);
-      gated_panel_pcg(l, ps, g, settle_max_iters);
+      if (prior) {
+        chain.cP = dt * cc->lamP;
+        const CgPrior every_row{chain.cP};
+        launch_rg_settle_init(ps, g, U, l.Y.p, l.ld, dt, l.lamG, l.lamC, l.lamQ, l.stream, &every_row);
+        launch_cg_path_init(ps, chain.dev, U, l.ld, chain.cP, l.stream);
+        gated_panel_pcg(l, ps, g, settle_max_iters, &chain);
+      } else {
+        launch_rg_settle_init(ps, g, U, l.Y.p, l.ld, dt, l.lamG, l.lamC, l.lamQ, l.stream);
+        gated_panel_pcg(l, ps, g, settle_max_iters);
+      }
       HIP_CHECK(hipMemcpyAsync(settle_iters + q0, ps.iters, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
       HIP_CHECK(hipMemcpyAsync(settle_res + q0, ps.res, (size_t)nq * 4, hipMemcpyDeviceToHost, l.stream));
       sync(l);
@@ -1964,16 +2085,21 @@ void query_receipt_gated_many(L& l, const float* psis, int32_t Q, float* gates, 
       Us = ps.X;  // kept as the fifth panel: the U* solve writes the other one
       p.X = reinterpret_cast<float*>(base + lay.U);
     }
+    BgPanel pm = p;  // M_q's panel: p with lamP in lamG (p itself keeps the handle's lamG for the components)
+    pm.lamG = lamGP;
+    if (prior) chain.cP = cc->lamP;
+    const GatedChain* const in_op = prior ? &chain : nullptr;
     const double t1 = now_ms();
-    gated_ustar_solve(l, p, g, max_iters, q0, iters_out, res_out);
+    gated_ustar_solve(l, pm, g, max_iters, q0, iters_out, res_out, in_op);
     sync(l);
     const double per_solve = (now_ms() - t1) / nq;
     for (int32_t t = 0; t < nq; ++t) solve_ms[q0 + t] = per_solve;
     // deltaH = tr((U_q - U*_q)^T M_q (U_q - U*_q)): the panel apply on the difference, its p . Ap per column
     double* const dh = reinterpret_cast<double*>(base + lay.dh);
-    launch_rg_diff(p, Us, U, l.ld, l.stream);
-    launch_bg_apply(p, g, l.stream);
-    launch_rg_deltah(p, dh, l.stream);
+    launch_rg_diff(pm, Us, U, l.ld, l.stream);
+    launch_bg_apply(pm, g, l.stream);
+    if (prior) launch_cg_path_apply(pm, chain.dev, chain.cP, l.stream);
+    launch_rg_deltah(pm, dh, l.stream, prior ? &chain.dev : nullptr);
     hdh.assign((size_t)nq, 0.0);
     HIP_CHECK(hipMemcpyAsync(hdh.data(), dh, (size_t)nq * 8, hipMemcpyDeviceToHost, l.stream));
     if (!full) {
@@ -2008,7 +2134,7 @@ void query_receipt_gated_many(L& l, const float* psis, int32_t Q, float* gates, 
         launch_rm_colfinish(part, cparts, nq, sums + (size_t)t * nq, reinterpret_cast<double*>(base + lay.sumfin), l.stream);
       }
       receipt_null_stage(
-          l, "osc_receipt_gated_many", NullChunk{q0, nq, qs, ra.z, ra.j, ra.r, zt}, null_cap, sums, (size_t)3 * nq,
+          l, fn, NullChunk{q0, nq, qs, ra.z, ra.j, ra.r, zt}, null_cap, sums, (size_t)3 * nq,
           [&](const double* hsum) {
             for (int32_t t = 0; t < nq; ++t) {
               o.dH[q0 + t] = hdh[(size_t)t];
@@ -2019,7 +2145,69 @@ void query_receipt_gated_many(L& l, const float* psis, int32_t Q, float* gates, 
           },
           o);
     }
+    if (cc)  // chain_receipt(chain_q, z_th) of U*_q from the solved panel
+      chain_edge_stage(l, BasisView{}, nullptr, q0, nq, chs.units.size(), cc->z_th, cc->offsets, cc->out, p.X);
     if (kk > 0) gated_bundle_stage(l, p, q0, kk, alpha, lambda_div, ysum.p, have_ysum, ids, score, align);
     sync(l);  // (hpsi and the scratch block are reused by the next chunk)
   }
+}
+
+}  // namespace
+
+void query_receipt_gated_many(L& l, const float* psis, int32_t Q, float* gates, int32_t diffusion, float gate_beta,
+                              float gate_gamma, int32_t gate_method, float gate_tol, int32_t gate_max_iters, float tol,
+                              int32_t max_iters, int32_t settle, float dt, int32_t settle_max_iters, float settle_tol,
+                              int32_t detail, float z_th, int32_t null_cap, int32_t k, float alpha, float lambda_div,
+                              int32_t* settle_iters, float* settle_res, const ReceiptManyOut& o, int32_t* ids, float* score,
+                              float* align, int32_t* iters_out, float* res_out, double* settle_ms, double* solve_ms) {
+  gated_call_check(l, "osc_receipt_gated_many", max_iters);
+  if (settle && settle_max_iters < 1) throw Invalid("osc_receipt_gated_many: the settle's max_iters must be >= 1");
+  if (o.null_offsets) o.null_offsets[0] = 0;
+  if (Q <= 0) return;
+  const GatedCall gc = gated_call_setup(l, psis, Q, gates, diffusion, gate_beta, gate_gamma, gate_method, gate_tol,
+                                        gate_max_iters);
+  const GatedReceiptCall call{psis, Q, gates, tol, max_iters, settle, dt, settle_max_iters, settle_tol, detail, z_th, null_cap, k,
+                              alpha, lambda_div, settle_iters, settle_res, o, ids, score, align, iters_out, res_out, settle_ms,
+                              solve_ms};
+  receipt_gated_chunks(l, "osc_receipt_gated_many", call, gc, nullptr);
+}
+
+// ---- per-query gates with per-query chain priors ---------------------------------------------
+// add_chain(chain_q, lamP, weights_q); set_query(psi_q, gates = g_q); [settle(dt, max_iters, tol);] receipt();
+// chain_receipt(chain_q, chain_z_th); [bundle(k, alpha)] (lattice.py:129-149, 159-296, 298-455, 466-528, 530-568) for Q
+// queries on a handle without a chain of its own: osc_receipt_gated_many's chunks with query q's path term in its operator
+// (chain_gated_kernels.hip) and the chain receipts read from the solved panel.  U is read; nothing of the handle's state is
+// written.
+void query_chain_gated_many(L& l, const float* psis, int32_t Q, float* gates, int32_t diffusion, float gate_beta,
+                            float gate_gamma, int32_t gate_method, float gate_tol, int32_t gate_max_iters,
+                            const int64_t* chain_offsets, const int32_t* chain_nodes, const float* chain_weights, float lamP,
+                            float chain_z_th, float tol, int32_t max_iters, int32_t settle, float dt,
+                            int32_t settle_max_iters, float settle_tol, int32_t detail, float z_th, int32_t null_cap,
+                            int32_t k, float alpha, float lambda_div, int32_t* settle_iters, float* settle_res,
+                            const ReceiptManyOut& o, const ChainManyOut& co, int32_t* ids, float* score, float* align,
+                            int32_t* iters_out, float* res_out, double* settle_ms, double* solve_ms) {
+  const std::string fn = "osc_chain_gated_many";
+  gated_call_check(l, fn, max_iters);
+  if (!(lamP >= 0.f) || !std::isfinite(lamP)) throw Invalid(fn + ": lamP must be a finite value >= 0");
+  if (settle && settle_max_iters < 1) throw Invalid(fn + ": the settle's max_iters must be >= 1");
+  if (o.null_offsets) o.null_offsets[0] = 0;
+  if (Q <= 0) return;
+  int32_t where = 0;
+  switch (host::chain_many_check(chain_offsets, chain_nodes, Q, l.N, &where)) {
+    case 1:
+      throw Invalid(fn + ": query " + std::to_string(where) + ": a chain has 2 to " + std::to_string(host::kCorpusMaxChain) +
+                    " nodes, at offsets that start from 0");
+    case 2:
+      throw Invalid(fn + ": query " + std::to_string(where) + ": chain indices out of bounds");
+  }
+  if (chain_weights)
+    for (int64_t e = 0; e < host::chain_many_edge_at(chain_offsets, Q); ++e)
+      if (!std::isfinite(chain_weights[e])) throw Invalid(fn + ": chain weights must be finite");
+  const GatedCall gc = gated_call_setup(l, psis, Q, gates, diffusion, gate_beta, gate_gamma, gate_method, gate_tol,
+                                        gate_max_iters);
+  const ChainGatedCall cc{chain_offsets, chain_nodes, chain_weights, lamP, chain_z_th, co};
+  const GatedReceiptCall call{psis, Q, gates, tol, max_iters, settle, dt, settle_max_iters, settle_tol, detail, z_th, null_cap, k,
+                              alpha, lambda_div, settle_iters, settle_res, o, ids, score, align, iters_out, res_out, settle_ms,
+                              solve_ms};
+  receipt_gated_chunks(l, fn.c_str(), call, gc, &cc);
 }

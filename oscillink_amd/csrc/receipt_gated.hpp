@@ -10,13 +10,14 @@ namespace osc {
 
 // The settle's start (lattice.py:184-196, solver.py:18-22 with x0 = U): ps carries the primed lambdas and the settle's
 // tol; x = U (N x ld, device rows), r = dt [lamG (y - u) + lamQ g (psi - u) + lamC (W u - u)] with the true lambdas,
-// p = z = r / (lamG' + lamQ' g + 1e-12); part_a: r . z
+// p = z = r / (lamG' + lamQ' g + 1e-12); part_a: r . z (prior: chain_gated.hpp's form with -dt lamP u on every row)
 void launch_rg_settle_init(const BgPanel& ps, const GmGraph& g, const float* U, const float* Y, int32_t ld, float dt, float lamG,
-                           float lamC, float lamQ, hipStream_t s);
+                           float lamC, float lamQ, hipStream_t s, const CgPrior* prior = nullptr);
 // P = Us - X over every slab, Us the settled panel or (Us == nullptr) the state U (N x ld) for every query; every query live
 void launch_rg_diff(const BgPanel& p, const float* Us, const float* U, int32_t ld, hipStream_t s);
 // dh[q] = sum over the query's columns of part_a (launch_bg_apply's p . M_q p): parts, then columns, then slabs, in order
-void launch_rg_deltah(const BgPanel& p, double* dh, hipStream_t s);
+// (with chain: and the fix units' share of each column, chain_gated.hpp)
+void launch_rg_deltah(const BgPanel& p, double* dh, hipStream_t s, const CgChain* chain = nullptr);
 
 // per (row, query) on the solved panel p.X, one wave each, fp64 (receipts.py:28-83 on the capped adjacency):
 //   anchor = lamG |U*_i - Y_i|^2, query = lamQ g_i |U*_i - psi|^2, coh = 1/2 lamC (ysum_i - sum_j A_ij |Un_i - Un_j|^2),

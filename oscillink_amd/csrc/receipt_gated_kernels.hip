@@ -6,16 +6,18 @@
 // x 8 lanes x float4); the row kernel is k_bg_bundle's (one wave per (row, query)).  Sums are fp64 in a fixed order that
 // knows N and the query's own slabs alone, so a query's answers are the same to the bit in any batch or chunk.
 #include "receipt_gated.hpp"
-#include "bundle_gated_dev.hpp"
+#include "chain_gated_dev.hpp"
 
 namespace osc {
 namespace {
 
 // k_bg_init's gather over the state U (row-major, pitch ld): x0 = U and r0 = b - (I + dt M_q) U without a stored b,
-// b = U + dt (lamG Y + lamQ g psi^T): the U terms cancel, r0 = dt [lamG (y - u) + lamQ g (psi - u) + lamC (W u - u)]
+// b = U + dt (lamG Y + lamQ g psi^T): the U terms cancel, r0 = dt [lamG (y - u) + lamQ g (psi - u) + lamC (W u - u)].  With a
+// prior (chain_gated.hpp) every row adds -dt lamP u; the chain rows' share is launch_cg_path_init's.
+template <class Prior>
 __global__ __launch_bounds__(256) void k_rg_settle_init(const BgPanel p, const GmGraph g, const float* __restrict__ U,
                                                         const float* __restrict__ Y, int32_t ld, float dt, float lamG,
-                                                        float lamC, float lamQ) {
+                                                        float lamC, float lamQ, const Prior pr) {
   __shared__ double sh[1024];
   const int slab = blockIdx.y, q = slab / p.spq, cq = (slab % p.spq) * 32;
   const int t = threadIdx.x, lane = t & 63, lr = lane & 7, g0 = lane & ~7;
@@ -62,6 +64,7 @@ __global__ __launch_bounds__(256) void k_rg_settle_init(const BgPanel p, const G
       r.y = dt * fmaf(lamG, y.y - x.y, fmaf(qg, ps.y - x.y, lamC * (sum.y - x.y)));
       r.z = dt * fmaf(lamG, y.z - x.z, fmaf(qg, ps.z - x.z, lamC * (sum.z - x.z)));
       r.w = dt * fmaf(lamG, y.w - x.w, fmaf(qg, ps.w - x.w, lamC * (sum.w - x.w)));
+      if constexpr (Prior::active) r = mulacc4(f4(-pr.cP), x, r);
       const float4 z = scale4(r, inv_md);
       const size_t o = so + (size_t)row * 32 + lr * 4;
       st4(p.X + o, x);
@@ -92,13 +95,15 @@ __global__ __launch_bounds__(256) void k_rg_diff(const BgPanel p, const float* _
 }
 
 // one workgroup per query: the columns' p . M_q p, parts in gm_part_sum's order, then columns and slabs in order
-__global__ __launch_bounds__(kGmSumThreads) void k_rg_deltah(const BgPanel p, double* __restrict__ dh) {
+template <class Chain>
+__global__ __launch_bounds__(kGmSumThreads) void k_rg_deltah(const BgPanel p, double* __restrict__ dh, const Chain ch) {
   __shared__ double sh[kGmSumThreads];
   __shared__ double col[32];
   const int q = blockIdx.x, t = threadIdx.x;
   double acc = 0.0;
   for (int s = 0; s < p.spq; ++s) {
-    const double v = gm_part_sum(p.part_a + (size_t)(q * p.spq + s) * p.parts * 32, p.parts, sh);
+    double v = gm_part_sum(p.part_a + (size_t)(q * p.spq + s) * p.parts * 32, p.parts, sh);
+    if constexpr (Chain::active) v += cg_unit_sum(ch, q * p.spq + s, q);
     if (t < 32) col[t] = v;
     __syncthreads();
     if (t == 0)
@@ -179,8 +184,12 @@ dim3 rg_grid(const BgPanel& p) { return dim3((unsigned)p.parts, (unsigned)p.slab
 }  // namespace
 
 void launch_rg_settle_init(const BgPanel& ps, const GmGraph& g, const float* U, const float* Y, int32_t ld, float dt, float lamG,
-                           float lamC, float lamQ, hipStream_t s) {
-  hipLaunchKernelGGL(k_rg_settle_init, rg_grid(ps), dim3(256), 0, s, ps, g, U, Y, ld, dt, lamG, lamC, lamQ);
+                           float lamC, float lamQ, hipStream_t s, const CgPrior* prior) {
+  if (prior)
+    hipLaunchKernelGGL(k_rg_settle_init<CgPrior>, rg_grid(ps), dim3(256), 0, s, ps, g, U, Y, ld, dt, lamG, lamC, lamQ, *prior);
+  else
+    hipLaunchKernelGGL(k_rg_settle_init<CgNoPrior>, rg_grid(ps), dim3(256), 0, s, ps, g, U, Y, ld, dt, lamG, lamC, lamQ,
+                       CgNoPrior{});
   HIP_CHECK(hipGetLastError());
 }
 
@@ -189,8 +198,9 @@ void launch_rg_diff(const BgPanel& p, const float* Us, const float* U, int32_t l
   HIP_CHECK(hipGetLastError());
 }
 
-void launch_rg_deltah(const BgPanel& p, double* dh, hipStream_t s) {
-  hipLaunchKernelGGL(k_rg_deltah, dim3((unsigned)p.nq), dim3(kGmSumThreads), 0, s, p, dh);
+void launch_rg_deltah(const BgPanel& p, double* dh, hipStream_t s, const CgChain* chain) {
+  if (chain) hipLaunchKernelGGL(k_rg_deltah<CgChain>, dim3((unsigned)p.nq), dim3(kGmSumThreads), 0, s, p, dh, *chain);
+  else hipLaunchKernelGGL(k_rg_deltah<CgNoChain>, dim3((unsigned)p.nq), dim3(kGmSumThreads), 0, s, p, dh, CgNoChain{});
   HIP_CHECK(hipGetLastError());
 }
 

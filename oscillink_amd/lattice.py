@@ -954,8 +954,8 @@ class OscillinkLattice:
         (int32), "res" (float32), "converged" (bool), "gates" ((Q, N) float32 for "diffusion", else None)}.  A non-finite
         query row (or non-finite diffusion gates, which raise `diffusion_gates_many`'s warning) gives that query
         non-finite answers and changes no other query's.  Its own method because `bundle_many`'s parameter list is
-        pinned; chain priors (`bundle_many(chains=..., lamP=...)`) do not combine with per-query gates, and a lattice
-        with a chain of its own raises NotImplementedError."""
+        pinned; per-query gates combined with per-query chain priors are `chain_gated_many`'s, and a lattice with a
+        chain of its own raises NotImplementedError."""
         P, Q, G, diffusion = _gated_call_inputs(self, "bundle_gated_many", psis, gates, gate_gamma, gate_method,
                                                 gate_max_iters, max_iters)
         kk = min(int(k), self.N) if k > 0 else 0
@@ -1022,24 +1022,49 @@ class OscillinkLattice:
         with `bundle_k` also `ids`, `score`, `align`.  Detail mode, OSCILLINK_RECEIPT_NULL_CAP, the secret and signature mode
         and OSCILLINK_RECEIPT_DYNAMICS behave as in `receipt_many`.  The report goes to `last_receipt_gated` = {"iters",
         "res", "converged", "settle_iters", "settle_res" (None without `settle`), "gates" (as `last_bundle_gated`)}."""
-        P, Q, G, diffusion = _gated_call_inputs(self, "receipt_gated_many", psis, gates, gate_gamma, gate_method,
-                                                gate_max_iters, max_iters)
-        st = None
-        if settle is not None and settle is not False:
-            st = dict(self._GATED_SETTLE_DEFAULTS)
-            if settle is not True:
-                if not isinstance(settle, dict):
-                    raise ValueError("settle must be None, True or a dict of dt / max_iters / tol")
-                unknown = sorted(set(settle) - set(st))
-                if unknown:
-                    raise ValueError(f"settle: unknown keys {unknown}")
-                st.update(settle)
-            if not float(st["dt"]) > 0:
-                raise ValueError("settle: dt must be > 0")
-            if int(st["max_iters"]) < 1:
-                raise ValueError("settle: max_iters must be >= 1")
+        return OscillinkLattice._gated_receipts(self, "receipt_gated_many", psis, gates, None, settle, bundle_k, alpha, tol,
+                                                max_iters, as_arrays, gate_beta, gate_gamma, gate_method, gate_tol,
+                                                gate_max_iters)
+
+    def _gated_settle_arg(self, settle) -> Optional[dict]:
+        """The `settle` argument of the gated calls as None or the checked dict of dt / max_iters / tol."""
+        if settle is None or settle is False:
+            return None
+        st = dict(self._GATED_SETTLE_DEFAULTS)
+        if settle is not True:
+            if not isinstance(settle, dict):
+                raise ValueError("settle must be None, True or a dict of dt / max_iters / tol")
+            unknown = sorted(set(settle) - set(st))
+            if unknown:
+                raise ValueError(f"settle: unknown keys {unknown}")
+            st.update(settle)
+        if not float(st["dt"]) > 0:
+            raise ValueError("settle: dt must be > 0")
+        if int(st["max_iters"]) < 1:
+            raise ValueError("settle: max_iters must be >= 1")
+        return st
+
+    def _gated_receipts(self, fn, psis, gates, chain, settle, bundle_k, alpha, tol, max_iters, as_arrays, gate_beta,
+                        gate_gamma, gate_method, gate_tol, gate_max_iters):
+        """`receipt_gated_many` (chain=None) and `chain_gated_many` (chain = {"chains", "lamP", "chain_weights", "z_th"}):
+        one argument check, one native call, one record assembly.  With a chain the return carries the chain receipts
+        behind the records, and the signature the argument's lamP, `chain_present` and the chain's length."""
+        P, Q, G, diffusion = _gated_call_inputs(self, fn, psis, gates, gate_gamma, gate_method, gate_max_iters, max_iters)
+        st = OscillinkLattice._gated_settle_arg(self, settle)  # (by the class: the host tests pass a stub)
         if bundle_k is not None and int(bundle_k) < 0:
             raise ValueError("bundle_k must be None or >= 0")
+        lamP = None
+        if chain is not None:
+            rc.check_prior_lamP(fn, chain["lamP"], False)
+            lamP = float(chain["lamP"])
+            lists, offsets, nodes = rc.chain_block(chain["chains"], Q, self.N)
+            edge_offsets = offsets - np.arange(Q + 1, dtype=np.int64)
+            weights = rc.chain_prior_weights(chain["chain_weights"], chain["chains"], lists, edge_offsets)
+            n_edges = int(edge_offsets[-1])
+            edge = np.zeros((4, max(n_edges, 1)), dtype=np.float32)
+            gain = np.zeros(Q, dtype=np.float64)
+            verdict, weak_k = np.zeros(Q, dtype=np.int32), np.zeros(Q, dtype=np.int32)
+            weak_z = np.zeros(Q, dtype=np.float32)
         with_bundle = bundle_k is not None
         kk = min(int(bundle_k), self.N) if with_bundle else 0
         full = self._receipt_detail != "light"
@@ -1052,42 +1077,67 @@ class OscillinkLattice:
         if Q > 0:
             self._push_params()
             s_args = (1, float(st["dt"]), int(st["max_iters"]), float(st["tol"])) if st else (0, 1.0, 1, 0.0)
-            self._call("osc_receipt_gated_many", nat.f32(P), Q, nat.f32(G), int(diffusion), float(gate_beta),
-                       float(gate_gamma), 1 if gate_method == "cg" else 0, float(gate_tol), int(gate_max_iters), float(tol),
-                       int(max_iters), *s_args, int(full), 3.0, cap_val, kk, float(alpha), 0.5,
-                       *([] if st else [None, None]), *ra.pointers(), nat.i32(ids), nat.f32(score), nat.f32(align),
-                       nat.i32(iters), nat.f32(res), settle_ms.ctypes.data_as(nat.c_f64p), solve_ms.ctypes.data_as(nat.c_f64p))
+            head = [nat.f32(P), Q, nat.f32(G), int(diffusion), float(gate_beta), float(gate_gamma),
+                    1 if gate_method == "cg" else 0, float(gate_tol), int(gate_max_iters)]
+            tail = [float(tol), int(max_iters), *s_args, int(full), 3.0, cap_val, kk, float(alpha), 0.5,
+                    *([] if st else [None, None]), *ra.pointers(), nat.i32(ids), nat.f32(score), nat.f32(align),
+                    nat.i32(iters), nat.f32(res), settle_ms.ctypes.data_as(nat.c_f64p), solve_ms.ctypes.data_as(nat.c_f64p)]
+            if chain is None:
+                self._call("osc_receipt_gated_many", *head, *tail)
+            else:
+                self._call("osc_chain_gated_many", *head, nat.i64(offsets), nat.i32(nodes),
+                           None if weights is None else nat.f32(weights), lamP, float(chain["z_th"]), *tail,
+                           *[nat.f32(edge[t]) for t in range(4)], gain.ctypes.data_as(nat.c_f64p), nat.i32(verdict),
+                           nat.i32(weak_k), nat.f32(weak_z))
         ra.round_sums()
         if diffusion:
             _warn_diffusion_gates(G)
         converged = res <= np.float32(tol)
-        self.last_receipt_gated = {"iters": iters, "res": res, "converged": converged,
-                                   "settle_iters": ra.settle[0] if st else None,
-                                   "settle_res": ra.settle[1] if st else None, "gates": G if diffusion else None}
-        self._log("receipt_gated_many", {"Q": Q, "receipt_detail": self._receipt_detail, "settle": st is not None,
-                                         "bundle_k": kk if with_bundle else None,
-                                         "gates": "diffusion" if diffusion else "given",
-                                         "iters_max": int(iters.max()) if Q else 0,
-                                         "converged": int(np.count_nonzero(converged)), "null_points": ra.kept})
+        report = {"iters": iters, "res": res, "converged": converged, "settle_iters": ra.settle[0] if st else None,
+                  "settle_res": ra.settle[1] if st else None, "gates": G if diffusion else None}
+        payload = {"Q": Q, "receipt_detail": self._receipt_detail, "settle": st is not None,
+                   "bundle_k": kk if with_bundle else None, "gates": "diffusion" if diffusion else "given",
+                   "iters_max": int(iters.max()) if Q else 0, "converged": int(np.count_nonzero(converged)),
+                   "null_points": ra.kept}
+        if chain is None:
+            self.last_receipt_gated = report
+        else:
+            self.last_chain_gated = {**report, "lamP": lamP}
+            payload.update(lamP=lamP, edges=n_edges)
+            carr = dict(chain_offsets=edge_offsets, chain_z_struct=edge[0, :n_edges].copy(),
+                        chain_z_path=edge[1, :n_edges].copy(), chain_r_struct=edge[2, :n_edges].copy(),
+                        chain_r_path=edge[3, :n_edges].copy(), chain_gain=gain, chain_verdict=verdict != 0,
+                        chain_weakest_k=weak_k, chain_weakest_z=weak_z)
+        self._log(fn, payload)
         if as_arrays:
             out = {**ra.scalar_arrays(), **ra.null_arrays(), "ustar_iters": iters, "ustar_res": res}
+            if chain is not None:
+                out.update(carr)
             if with_bundle:
                 out.update(ids=ids, score=score, align=align)
             return out
         bundles = [rc.bundle_dicts(ids[q], score[q], align[q]) for q in range(Q)]
+        crecs = rc.chain_receipt_dicts(lists, carr) if chain is not None else None
         if Q == 0:
-            return ([], []) if with_bundle else []
+            if chain is None:
+                return ([], []) if with_bundle else []
+            return ([], [], []) if with_bundle else ([], [])
         # everything but psi, the gates, the energies, the null points, the settle and the ustar fields is shared by the batch
         nnz, _, _ = self.graph_stats()
         adj_sig = hashlib.sha256(np.ascontiguousarray(self._edge_prefix()).tobytes()).hexdigest()
-        sig_rest = {"lam": [self.lamG, self.lamC, self.lamQ, self.lamP], "chain_present": False, "chain_len": 0,
-                    "k": self._kneighbors, "detk": self._deterministic_k, "adj": adj_sig}
+        sig_rest = {"lam": [self.lamG, self.lamC, self.lamQ, self.lamP if chain is None else lamP],
+                    "chain_present": chain is not None, "chain_len": 0, "k": self._kneighbors, "detk": self._deterministic_k,
+                    "adj": adj_sig}
         degree, signed = rc.degree_stats(nnz, self.N), self._signed_settings()
+        if chain is not None:
+            signed = {**signed, "params": {**signed["params"], "lamP": lamP}}
         last = self._last_settle_fields()
         dyn = self._last_dynamics if os.getenv("OSCILLINK_RECEIPT_DYNAMICS", "0").strip().lower() in {"1", "true", "yes"} \
             else None
         out = []
         for q in range(Q):
+            if chain is not None:
+                sig_rest["chain_len"] = len(lists[q])
             sig = self._signature_digest({"psi": np.round(P[q], 6).tolist(), **sig_rest}, G[q])
             dH = float(ra.sums[0, q])
             ustar = {"ustar_iters": int(iters[q]), "ustar_res": float(res[q]), "ustar_converged": bool(converged[q])}
@@ -1105,7 +1155,41 @@ class OscillinkLattice:
             if dyn:
                 meta["dynamics"] = dyn
             out.append(rec)
+        if chain is not None:
+            return (out, crecs, bundles) if with_bundle else (out, crecs)
         return (out, bundles) if with_bundle else out
+
+    def chain_gated_many(self, psis: np.ndarray, gates, chains, lamP: float = 0.2, *, chain_weights=None, z_th: float = 2.5,
+                         settle=None, bundle_k: Optional[int] = None, alpha: float = 0.5, tol: float = 1e-4,
+                         max_iters: int = 256, as_arrays: bool = False, gate_beta: float = 1.0, gate_gamma: float = 0.1,
+                         gate_method: str = "direct", gate_tol: float = 1e-4, gate_max_iters: int = 256):
+        """The whole request sequence under per-query gates AND a per-query chain prior, for every row of `psis` in one
+        call.  On a lattice without a chain of its own, holding this lattice's U, query q gets
+        what `add_chain(chains[q], lamP, chain_weights[q]); set_query(psis[q], gates=G[q]); [settle(**settle);]
+        r = receipt(); c = chain_receipt(chains[q], z_th); [b = bundle(bundle_k, alpha)]` returns.  The lattice's psi,
+        gates, U, U* cache, query basis, shifted-basis slot, `stats`, `last` and receipts are not changed; of its state
+        only U is read.
+
+        `psis`, `gates` ((Q, N) or "diffusion": the gates of the lattice WITHOUT the chain), `settle`, `bundle_k`, `alpha`,
+        `tol`, `max_iters` and the `gate_*` arguments are `receipt_gated_many`'s, with its validation and errors.  `chains`
+        and `chain_weights` take `chain_receipt_many`'s forms -- one chain shared by all queries, or Q chains of 2 to 1024
+        nodes; repeated nodes, self-steps and revisited edges behave as in `add_chain` -- without the 64-distinct-node limit
+        of the low-rank calls: with gates every query is its own N x D solve already, and its chain is a term of its own
+        operator.  `lamP` >= 0; with `lamP == 0` the operator carries no path term and the receipts and bundles are
+        `receipt_gated_many`'s bit for bit, the signature still says `chain_present`, and the chain receipt is still
+        computed.
+
+        Returns `(records, chain_records)`, with `bundle_k` `(records, chain_records, bundles)`: `receipt_gated_many`'s
+        records (the signature carries the argument's lamP, `chain_present` and the chain's length; `ustar_source` is
+        "gated_panel") and `chain_receipt`'s dicts.  `as_arrays=True` returns one dict: `receipt_gated_many`'s arrays,
+        `chain_receipt_many`'s (`chain_offsets`, `chain_z_struct`, ... `chain_weakest_z`) and with `bundle_k` `ids`, `score`,
+        `align`.  The report goes to `last_chain_gated` = `last_receipt_gated`'s keys plus "lamP".  A non-finite query row
+        gives that query non-finite answers and changes no other query's bytes.  A lattice with a chain of its own or with
+        a communicator raises NotImplementedError."""
+        chain = {"chains": chains, "lamP": lamP, "chain_weights": chain_weights, "z_th": z_th}
+        return OscillinkLattice._gated_receipts(self, "chain_gated_many", psis, gates, chain, settle, bundle_k, alpha, tol,
+                                                max_iters, as_arrays, gate_beta, gate_gamma, gate_method, gate_tol,
+                                                gate_max_iters)
 
     def receipt_many(self, psis: np.ndarray, *, tol: float = 1e-4, max_iters: int = 256, as_arrays: bool = False,
                      chains=None, lamP: Optional[float] = None, chain_weights=None):
